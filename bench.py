@@ -277,6 +277,26 @@ def series_flops_per_line(dim):
     return 80 * 8 * L + 2.5 * Q * math.log2(Q) * L
 
 
+DUMP_BYTES = 60 << 20        # --dump-outputs: array bytes in all (under 64 MB with the .npy headers)
+
+
+def dump_outputs(path, fit, psum):
+    """--dump-outputs: the fit table [rows][nl][16] and the stamp sum [nl][40][40] (float64) of the last timed step
+    as <path>/fit.npy and <path>/psf_sum.npy.  A table too large for DUMP_BYTES is cut to a fixed, seeded sample of
+    its rows, whose indices go to <path>/fit_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {'psf_sum': psum}
+    room = DUMP_BYTES - psum.nbytes
+    if fit.nbytes > room:
+        keep = room // (fit[0].nbytes + 8)
+        rows_ = np.sort(np.random.default_rng(0).choice(fit.shape[0], keep, replace=False))
+        arrays['fit_rows'] = rows_.astype(np.float64)
+        fit = fit[rows_]
+    arrays['fit'] = fit
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(v, dtype=np.float64))
+
+
 def load_json(name):
     f = os.path.join(ROOT, 'profiles', name)
     return json.load(open(f)) if os.path.exists(f) else None
@@ -326,6 +346,8 @@ def main():
                     help='HIP events on every n-th launch of the dominant kernel in the timed region')
     ap.add_argument('--profile-steps', type=int, default=-1,
                     help='steps of the untimed per-kernel event pass (-1: min(steps, 40), 0: skip)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (fit table, stamp sum; float64) as DIR/*.npy')
     a = ap.parse_args()
 
     if 'WORLD_SIZE' not in os.environ and a.gpus > 1:
@@ -606,9 +628,17 @@ def main():
             t = torch.tensor([1.0 if ok else 0.0], dtype=torch.float64, device=dev if backend == 'nccl' else 'cpu')
             dist.all_reduce(t, op=dist.ReduceOp.MIN)
             return bool(t.item() == 1.0)
+
+        def last_outputs():
+            """Host copies of what the last step handed its caller: the fit table [rows][nl][16] and the stamp sum
+            [nl][40][40] of its buffer set; with an exchange, the gathered table and (rank 0) the reduced sum.
+            Call after a fence."""
+            b = (state['i'] - 1) % nset
+            fit, psum = (state['fit_all'], state.get('psum', psums[b])) if xchg else (fits[b], psums[b])
+            return fit.cpu().numpy().copy(), psum.cpu().numpy().reshape(nl, 40, 40).copy()
         return dict(ctxs=ctxs, step=step, fence=fence, timed=timed, profile_sum=profile_sum,
                     fits=fits, close=close, host_lib=host_lib, rank_times=rank_times, exchange_times=exchange_times,
-                    exchange_check=exchange_check)
+                    exchange_check=exchange_check, last_outputs=last_outputs)
 
     def parity_block(fitg, n):
         return {'rows_checked': n,
@@ -737,6 +767,8 @@ def main():
         R['step']()
     dt, t_enq = R['timed'](a.steps)
     exch_ok = R['exchange_check']()
+    # --dump-outputs: the last timed step's outputs, taken before any later pass reuses the buffers
+    last_out = R['last_outputs']() if a.dump_outputs and rank == 0 else None
     rank_dt = R['rank_times']()
     prof = R['profile_sum']()
     host_lib_s = R['host_lib']()
@@ -1258,6 +1290,8 @@ def main():
             if ratio:
                 out['speedup_vs_reference_calibrated'] = round(out['value'] / (cpu['value'] * ratio), 1)
                 out['speedup_calibration'] = {'reference_psfs_per_s_over_port': round(ratio, 3), 'source': 'profiles/r02_cpu_calibration.json'}
+        if last_out is not None:
+            dump_outputs(a.dump_outputs, *last_out)
         print(json.dumps(out), flush=True)
     if xchg:
         dist.destroy_process_group()

@@ -43,7 +43,7 @@ def env_run():
     # used by the asynchronous-parts path -- needs the system's)
     sysstd = '/usr/lib/x86_64-linux-gnu/libstdc++.so.6'
     if os.path.exists(sysstd):
-        env['LD_PRELOAD'] = sysstd
+        env['LD_PRELOAD'] = ':'.join(p for p in (sysstd, env.get('LD_PRELOAD')) if p)
     env.pop('PYTHONPATH', None)
     p = subprocess.run([PY, '-W', 'ignore', os.path.join(ROOT, 'tests', 'astropy_env_driver.py'), ROOT],
                        capture_output=True, text=True, env=env, timeout=300)

@@ -213,7 +213,9 @@ def test_multi_context_call_selects_every_device(tmp_path):
             c.close()
         print('OK')
     ''') % (ROOT, log)
-    env = dict(os.environ, LD_PRELOAD=shim, MPSFR_SHIM_DEVICES='4', MPSFR_SHIM_LOG=log)
+    # (in front of whatever the environment already preloads)
+    preload = ':'.join(p for p in (shim, os.environ.get('LD_PRELOAD')) if p)
+    env = dict(os.environ, LD_PRELOAD=preload, MPSFR_SHIM_DEVICES='4', MPSFR_SHIM_LOG=log)
     r = subprocess.run([sys.executable, '-c', script], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and 'OK' in r.stdout, (r.stdout[-1000:], r.stderr[-2000:])
     by_thread = {}
