@@ -248,6 +248,27 @@ int mpsfr_psf_from_psd(mpsfr_ctx* ctx, int ndir, const double* psd, int nl, cons
 int mpsfr_convolve_stamps(mpsfr_ctx* ctx, int ntask, const double* seeing, const double* gl, const double* l0,
                           int nl, const double* lbda_nm, const double* psf_in, double* psf_out);
 
+/* psd_to_psf (psfrec.py:689-807): the full dimnum x dimnum PSF of any PSD, any pupil and an optional static
+ * phase, for FoV == FoVnum and samp <= dim / npup (the reference's other branches are not supported).
+ *   psd           [npsd][dim][dim] float64, centred (DC at [dim/2][dim/2]), nm^2 m^2 at the PSF wavelength;
+ *                 dim is the context's grid
+ *   pup           [npup][npup] float64, any real values (apodised, spiders, gaps); sum(pup) != 0
+ *   phase_static  [npup][npup] or NULL.  The field is pup exp(2 pi i phase_static / lbda_m) as psfrec.py:785-786
+ *                 computes it: phase_static is in METRES (the reference's docstring says nm; its code divides
+ *                 by the wavelength in metres, and this follows the code)
+ *   D             pupil diameter [m]; L = D dim / npup (psfrec.py:710-711)
+ *   lbda_m        [nl] wavelengths in metres, as the reference's `lbda`
+ *   dimnum        output side: 128, 256, 512, 1024 or 1280, <= dim and >= npup (psfrec.py:731:
+ *                 int(fix(dim samp / sampnum / 2)) 2)
+ *   psf_out       [npsd][nl][dimnum][dimnum] float64, centred, each plane normalised to sum 1
+ *   on_device     0: host buffer; 1: device pointer on the context's device.  The call is synchronous either way.
+ * Everything is computed in fp64 whatever the context's precision.  The call uses a stream and workspaces of its
+ * own (bounded: the wavelengths go in chunks), so asynchronous mpsfr_reconstruct calls in flight are unaffected.
+ * Every plane is computed independently: a batched call equals the same planes called one at a time, bit for bit. */
+int mpsfr_psd_to_psf(mpsfr_ctx* ctx, int npsd, const double* psd, int npup, const double* pup,
+                     const double* phase_static, double D, int nl, const double* lbda_m, int dimnum,
+                     double* psf_out, int on_device);
+
 /* FIT_ROWS assembly on the host (pure C, no GPU): the columns fit_psf_cube keeps from the fit object
  * (psfrec.py:866-870) -- center[2], flux, fwhm[2] (arcsec), n, peak, err_center[2], err_flux, err_fwhm[2] (arcsec),
  * err_n, err_peak: 14 doubles -- of `n` fit rows ([n][MPSFR_NFIT], as mpsfr_reconstruct writes them) into

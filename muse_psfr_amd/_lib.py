@@ -78,6 +78,8 @@ def load():
     lib.mpsfr_simul_psd.restype = C.c_int
     lib.mpsfr_psf_from_psd.argtypes = [p, C.c_int, dp, C.c_int, dp, dp]
     lib.mpsfr_psf_from_psd.restype = C.c_int
+    lib.mpsfr_psd_to_psf.argtypes = [p, C.c_int, dp, C.c_int, dp, dp, C.c_double, C.c_int, dp, C.c_int, p, C.c_int]
+    lib.mpsfr_psd_to_psf.restype = C.c_int
     lib.mpsfr_convolve_stamps.argtypes = [p, C.c_int, dp, dp, dp, C.c_int, dp, dp, dp]
     lib.mpsfr_convolve_stamps.restype = C.c_int
     lib.mpsfr_fit_rows.argtypes = [dp, C.c_long, C.c_double, dp, C.c_long]
@@ -120,6 +122,7 @@ def load():
 
 EXPORTS = ['mpsfr_create', 'mpsfr_destroy', 'mpsfr_last_error', 'mpsfr_set_option',
            'mpsfr_reconstruct', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
+           'mpsfr_psd_to_psf',
            'mpsfr_convolve_stamps', 'mpsfr_fit_rows', 'mpsfr_sync', 'mpsfr_last_ticket', 'mpsfr_wait', 'mpsfr_abandon',
            'mpsfr_stream', 'mpsfr_stream_wait', 'mpsfr_wait_event',
            'mpsfr_host_time', 'mpsfr_debug_fetch',
@@ -383,6 +386,37 @@ class Context:
         out = np.empty((lbda.size, self.dimpsf, self.dimpsf))
         _check(self.lib.mpsfr_psf_from_psd(self._h, psd.shape[0], _dptr(psd), lbda.size, _dptr(lbda), _dptr(out)))
         return out
+
+    def psd_to_psf(self, psd, pup, D, lbda_m, phase_static=None, dimnum=None, out=None):
+        """mpsfr_psd_to_psf (psd_to_psf, psfrec.py:689-807): PSD (dim, dim) or (npsd, dim, dim), pupil (npup, npup),
+        wavelengths in metres -> (npsd, nl, dimnum, dimnum) full PSFs, each of sum 1.  phase_static is in metres
+        (see include/mpsfr.h).  dimnum defaults to dim.  `out`: None (a new host array), or a device pointer (an int,
+        e.g. a torch tensor's data_ptr()) to npsd * nl * dimnum^2 float64 on this context's device."""
+        psd = np.ascontiguousarray(psd, dtype=np.float64)
+        if psd.ndim == 2:
+            psd = psd[None]
+        if psd.ndim != 3 or psd.shape[1:] != (self.dim, self.dim):
+            raise ValueError('the PSD must be %d x %d for this context' % (self.dim, self.dim))
+        pup = np.ascontiguousarray(pup, dtype=np.float64)
+        if pup.ndim != 2 or pup.shape[0] != pup.shape[1]:
+            raise ValueError('the pupil must be a square 2-D array')
+        ph = None
+        if phase_static is not None:
+            ph = np.ascontiguousarray(phase_static, dtype=np.float64)
+            if ph.shape != pup.shape:
+                raise ValueError('phase_static must have the shape of the pupil %s, not %s' % (pup.shape, ph.shape))
+        lbda_m = np.ascontiguousarray(np.atleast_1d(lbda_m), dtype=np.float64).ravel()
+        dimnum = self.dim if dimnum is None else int(dimnum)
+        shape = (psd.shape[0], lbda_m.size, dimnum, dimnum)
+        if out is None:
+            res = np.empty(shape)
+            ptr, on_device = res.ctypes.data_as(C.c_void_p), 0
+        else:
+            res, ptr, on_device = None, C.c_void_p(int(out)), 1
+        _check(self.lib.mpsfr_psd_to_psf(self._h, psd.shape[0], _dptr(psd), pup.shape[0], _dptr(pup),
+                                         None if ph is None else _dptr(ph), float(D), lbda_m.size, _dptr(lbda_m),
+                                         dimnum, ptr, on_device))
+        return res
 
     def convolve_stamps(self, lbda, seeing, gl, l0, psf):
         """convolve_final_psf (psfrec.py:874-930) on (ntask, nl, 40, 40) stamps (or (nl, 40, 40) for one task)."""

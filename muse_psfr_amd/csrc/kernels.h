@@ -94,6 +94,17 @@ void launch_psd_image(hipStream_t s, int N, int ndir, const TaskPar& p, const do
                       double unit, double* d_psd);
 void launch_dphi_from_psd(hipStream_t s, int N, int ndir, const double* d_psd, void* d_Cm, double scale,
                           void* d_D0t, bool f64out, const void* d_tw64);
+// psd_to_psf (psd_to_psf.hip), fp64, M = dimnum (a planned length), d_twm: exp(-2 pi i m / M).
+// launch_p2p_otf: nz telescope OTFs of the pupil d_pup [P][P] (times exp(2 pi i d_phase / lambda_m[z]) when
+// d_phase is not NULL) into d_otft [nz][M/2+1][M] (scaled by `scale`); d_T1 [nz][P][M] and d_Q [nz][M][M/2+1]
+// complex workspaces.  launch_p2p_psf: nz planes d_psf [nz][M][M] (centred, sum 1) from the structure function
+// d_D0t [N/2+1][N] (launch_dphi_from_psd), the OTFs (plane z at d_otft + z otf_stride) and d_cl[z] =
+// -(2 pi / lambda_nm)^2 / 2; d_G [nz][M/2+1][M/2+1] complex workspace.
+bool p2p_supported(int M);
+void launch_p2p_otf(hipStream_t s, int M, int P, int nz, const double* d_pup, const double* d_phase,
+                    const double* d_lbda_m, double scale, void* d_T1, void* d_Q, double* d_otft, const void* d_twm);
+void launch_p2p_psf(hipStream_t s, int M, int N, int nz, const double* d_D0t, const double* d_otft, size_t otf_stride,
+                    const double* d_cl, void* d_G, double* d_psf, const void* d_twm);
 // Series form of stage A (stage_a2.hip).  d_coef: [N/2+1][N][series_terms] structure functions of the
 // terms of the expansion of the fitting PSD in 1/L0^2 about series_eps0() (launch_series_coef from the
 // fp64 planes [terms][N/2+1][N] that launch_colfft_dphi produced for the basis tasks);

@@ -157,6 +157,12 @@ struct mpsfr_ctx {
     bool stagger_armed = false;
     int stagger_lane = -1;
     DevBuf fit, sum, stage, lsum;      // lsum: [lanes][nl][40][40] per-lane partial stamp sums
+    // mpsfr_psd_to_psf: a stream and workspaces of its own, so that it never waits for nor touches the lanes
+    struct P2P {
+        hipStream_t stream = nullptr;
+        int twm_len = 0;                 // length of the twiddle table in `twm`
+        DevBuf twm, psd, cm, d0t, pup, phase, lbda, cl, t1, q, otf, g, out;
+    } p2p;
     // Small per-call parameters: one pinned host blob -> one device blob, no stream sync.  A ring
     // of NSTAGE slots (pinned blob, device blob, tip-tilt kernel spectra): the host may queue
     // NSTAGE calls ahead of the GPU, and calls in flight on different lanes never share a slot.
@@ -617,6 +623,10 @@ void mpsfr_destroy(mpsfr_ctx* c) {
                      &c->samp_a, &c->G, &c->xtab, &c->etab, &c->gtab, &c->kmuse, &c->fit, &c->sum,
                      &c->stage, &c->lsum, &c->mfclk};
     for (auto b : all) release(*b);
+    if (c->p2p.stream) { (void)hipStreamSynchronize(c->p2p.stream); (void)hipStreamDestroy(c->p2p.stream); }
+    DevBuf* p2p[] = {&c->p2p.twm, &c->p2p.psd, &c->p2p.cm, &c->p2p.d0t, &c->p2p.pup, &c->p2p.phase, &c->p2p.lbda,
+                     &c->p2p.cl, &c->p2p.t1, &c->p2p.q, &c->p2p.otf, &c->p2p.g, &c->p2p.out};
+    for (auto b : p2p) release(*b);
     if (c->seq_host) (void)hipHostFree(c->seq_host);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1886,6 +1896,102 @@ int mpsfr_convolve_stamps(mpsfr_ctx* c, int ntask, const double* seeing, const d
     io.pre_in = psf_in;
     return guarded_call(c, ntask, seeing, gl, l0, nullptr, h, 12.0, 1, nl, lbda_nm, nullptr, nullptr,
                         psf_out, nullptr, nullptr, 0, io);
+}
+
+int mpsfr_psd_to_psf(mpsfr_ctx* c, int npsd, const double* psd, int npup, const double* pup,
+                     const double* phase_static, double D, int nl, const double* lbda_m, int dimnum,
+                     double* psf_out, int on_device) {
+    if (!c) return fail(MPSFR_E_INVALID, "ctx is NULL");
+    if (!psd || !pup || !lbda_m || !psf_out) return fail(MPSFR_E_INVALID, "NULL argument");
+    const int N = c->N, M = dimnum, P = npup;
+    if (!p2p_supported(M))
+        return fail(MPSFR_E_INVALID, "dimnum=%d not supported (128, 256, 512, 1024, 1280)", M);
+    if (M > N) return fail(MPSFR_E_INVALID, "dimnum=%d larger than the grid (dim=%d)", M, N);
+    if (npsd < 1 || nl < 1) return fail(MPSFR_E_INVALID, "npsd=%d, nl=%d: both must be >= 1", npsd, nl);
+    if (P < 1 || P > M) return fail(MPSFR_E_INVALID, "npup=%d must be in [1, dimnum=%d]", P, M);
+    if (!(D > 0.0)) return fail(MPSFR_E_INVALID, "D must be > 0");
+    for (int i = 0; i < nl; ++i)
+        if (!(lbda_m[i] > 0.0)) return fail(MPSFR_E_INVALID, "lbda_m[%d] must be > 0", i);
+    double pupsum = 0.0;
+    for (long i = 0; i < (long)P * P; ++i) pupsum += pup[i];
+    if (pupsum == 0.0 || !std::isfinite(pupsum)) return fail(MPSFR_E_INVALID, "sum(pup) must be finite and non-zero");
+    HIPCHK(hipSetDevice(c->device));
+    mpsfr_ctx::P2P& w = c->p2p;
+    if (!w.stream) HIPCHK(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
+    hipStream_t s = w.stream;
+    // wavelengths per chunk: the workspace is bounded whatever nl and npsd are (~50 MB per plane at 1280^2)
+    constexpr int kChunk = 8;
+    const int CH = std::min(nl, kChunk), nchunk = (nl + CH - 1) / CH;
+    const bool phased = phase_static != nullptr;
+    const int notf = phased ? CH : 1;
+    const size_t H1 = (size_t)M / 2 + 1, plane = (size_t)M * M;
+    int rc;
+    if ((rc = ensure(c, w.twm, 2 * (size_t)M * sizeof(double)))) return rc;
+    if ((rc = ensure(c, w.psd, (size_t)N * N * sizeof(double)))) return rc;
+    if ((rc = ensure(c, w.cm, (size_t)N * (N / 2 + 1) * 2 * sizeof(double)))) return rc;
+    if ((rc = ensure(c, w.d0t, (size_t)(N / 2 + 1) * N * sizeof(double)))) return rc;
+    if ((rc = ensure(c, w.pup, (size_t)P * P * sizeof(double)))) return rc;
+    if (phased && (rc = ensure(c, w.phase, (size_t)P * P * sizeof(double)))) return rc;
+    if ((rc = ensure(c, w.lbda, (size_t)nl * sizeof(double)))) return rc;
+    if ((rc = ensure(c, w.cl, (size_t)nl * sizeof(double)))) return rc;
+    if ((rc = ensure(c, w.t1, (size_t)notf * P * M * 2 * sizeof(double)))) return rc;
+    if ((rc = ensure(c, w.q, (size_t)notf * M * H1 * 2 * sizeof(double)))) return rc;
+    if ((rc = ensure(c, w.otf, (size_t)notf * H1 * M * sizeof(double)))) return rc;
+    if ((rc = ensure(c, w.g, (size_t)CH * H1 * H1 * 2 * sizeof(double)))) return rc;
+    if (!on_device && (rc = ensure(c, w.out, (size_t)CH * plane * sizeof(double)))) return rc;
+    if (w.twm_len != M) {
+        std::vector<double> tw(2 * (size_t)M);
+        for (int m = 0; m < M; ++m) {
+            const long double ang = -2.0L * 3.141592653589793238462643383279502884L * m / M;
+            tw[2 * m] = (double)cosl(ang);
+            tw[2 * m + 1] = (double)sinl(ang);
+        }
+        HIPCHK(hipMemcpy(w.twm.p, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice));
+        w.twm_len = M;
+    }
+    // psfrec.py:717-722: Dphi(lambda) = (2 pi / lambda_nm)^2 Dphi0, Dphi0 = 2 Re(bg00 - bg) with bg of the raw PSD
+    std::vector<double> cl(nl);
+    for (int i = 0; i < nl; ++i) {
+        const double conv = 2.0 * M_PI / (lbda_m[i] * 1e9);
+        cl[i] = -0.5 * conv * conv;
+    }
+    const double L = D * N / P;                       // psfrec.py:710-711
+    const double dscale = 2.0 / (L * L);
+    const double oscale = 1.0 / ((double)M * M * (double)M * M * pupsum);
+    HIPCHK(hipMemcpyAsync(w.pup.p, pup, (size_t)P * P * sizeof(double), hipMemcpyHostToDevice, s));
+    if (phased)
+        HIPCHK(hipMemcpyAsync(w.phase.p, phase_static, (size_t)P * P * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(w.lbda.p, lbda_m, (size_t)nl * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(w.cl.p, cl.data(), (size_t)nl * sizeof(double), hipMemcpyHostToDevice, s));
+    const double* d_lbda = (const double*)w.lbda.p;
+    const double* d_cl = (const double*)w.cl.p;
+    double* d_otf = (double*)w.otf.p;
+    // the OTFs: one for the call without a static phase, else one per wavelength (built once if one chunk holds them)
+    auto build_otf = [&](int l0, int nz) {
+        launch_p2p_otf(s, M, P, nz, (const double*)w.pup.p, phased ? (const double*)w.phase.p : nullptr,
+                       d_lbda + l0, oscale, w.t1.p, w.q.p, d_otf, w.twm.p);
+    };
+    if (!phased || nchunk == 1) build_otf(0, phased ? CH : 1);
+    const size_t otf_stride = phased ? H1 * M : 0;
+    for (int p = 0; p < npsd; ++p) {
+        HIPCHK(hipMemcpyAsync(w.psd.p, psd + (size_t)p * N * N, (size_t)N * N * sizeof(double), hipMemcpyHostToDevice, s));
+        launch_dphi_from_psd(s, N, 1, (const double*)w.psd.p, w.cm.p, dscale, w.d0t.p, true, c->tw64.p);
+        for (int k = 0; k < nchunk; ++k) {
+            const int l0 = k * CH, nz = std::min(CH, nl - l0);
+            if (phased && nchunk > 1) build_otf(l0, nz);
+            double* dst = psf_out + ((size_t)p * nl + l0) * plane;
+            launch_p2p_psf(s, M, N, nz, (const double*)w.d0t.p, d_otf, otf_stride, d_cl + l0, w.g.p,
+                           on_device ? dst : (double*)w.out.p, w.twm.p);
+            HIPCHK(hipGetLastError());
+            if (!on_device) {
+                HIPCHK(hipMemcpyAsync(dst, w.out.p, (size_t)nz * plane * sizeof(double), hipMemcpyDeviceToHost, s));
+                HIPCHK(hipStreamSynchronize(s));      // (w.out is refilled by the next chunk)
+            }
+        }
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    return MPSFR_OK;
 }
 
 int mpsfr_fit_stamps(mpsfr_ctx* c, int nstamp, const double* stamps, double* fit_out,

@@ -354,6 +354,141 @@ def psf_muse(psd, lambdamuse, *, pixscale=0.2, precision='mixed', device=0):
         raise
 
 
+# ---- psd_to_psf (psfrec.py:689-807) and the pupil / resampling helpers its callers use -----------------
+
+_P2P_SIZES = (128, 256, 512, 1024, 1280)    # the transform lengths libmpsfr plans for
+
+
+def seeing2r01(seeing, lbda, zenith):
+    """r0 [m] at the wavelength `lbda` [um] and zenith angle `zenith` [deg] of a seeing [arcsec] given at
+    0.5 um (psfrec.py:183-187)."""
+    r0_500 = 0.976 * 0.5 / seeing / 4.85
+    airmass_term = np.cos(np.deg2rad(zenith)) ** (3 / 5)
+    return r0_500 * (lbda * 2) ** (6 / 5) * airmass_term
+
+
+def pupil_mask(radius, width, oc=0, inverse=False):
+    """Telescope pupil (psfrec.py:190-203): an int array (width, width), 1 where the distance to the centre
+    ((width - 1) / 2), in units of `radius` pixels, is in [oc, 1); `inverse` swaps 0 and 1."""
+    c = (width - 1) / 2
+    ax = np.arange(width)
+    rho = np.hypot((ax - c)[:, None], (ax - c)[None, :]) / radius
+    inside = (rho >= oc) & (rho < 1)
+    return (~inside if inverse else inside).astype(int)
+
+
+def crop(arr, center, size):
+    """arr[center - size:center + size] along the first two axes (psfrec.py:629-632)."""
+    lo, hi = int(center) - int(size), int(center) + int(size)
+    return arr[lo:hi, lo:hi]
+
+
+def interpolate(arr, xout, method='linear'):
+    """Bilinear sampling of the square image `arr` (sample (i, j) at integer coordinates) at the points
+    xout[0], xout[1] (psfrec.py:635-641: scipy's interpn on (arange(n), arange(n)), here in NumPy).  Points
+    outside the grid raise ValueError as interpn does; 'cubic' raises NotImplementedError as the reference."""
+    if method == 'cubic':
+        raise NotImplementedError('FIXME: use gridddata or spline ?')
+    if method != 'linear':
+        raise ValueError('method must be linear')
+    arr = np.asarray(arr)
+    n = arr.shape[0]
+    if arr.ndim != 2 or arr.shape[1] != n:
+        raise ValueError('There are %d points and %d values in dimension 1' % (n, arr.shape[-1]))
+    pts = np.asarray(xout, dtype=float).T
+    if pts.shape[-1] != 2:
+        raise ValueError('The requested sample points xi have dimension %d but this RegularGridInterpolator '
+                         'has dimension 2' % pts.shape[-1])
+    x, y = pts[..., 0], pts[..., 1]
+    for d, v in enumerate((x, y)):
+        if not np.logical_and(v >= 0, v <= n - 1).all():
+            raise ValueError('One of the requested xi is out of bounds in dimension %d' % d)
+    i = np.clip(np.floor(x).astype(int), 0, max(n - 2, 0))
+    j = np.clip(np.floor(y).astype(int), 0, max(n - 2, 0))
+    i1, j1 = np.minimum(i + 1, n - 1), np.minimum(j + 1, n - 1)
+    wx, wy = x - i, y - j
+    out = (arr[i, j] * (1 - wx) * (1 - wy) + arr[i1, j] * wx * (1 - wy) +
+           arr[i, j1] * (1 - wx) * wy + arr[i1, j1] * wx * wy)
+    return out.T
+
+
+def psd_to_psf(psd, pup, D, lbda, phase_static=None, samp=None, FoV=None, return_all=False, *,
+               precision='mixed', device=0):
+    """PSF of a residual phase PSD and a pupil (psfrec.py:689-807), on the GPU in fp64 whatever `precision`
+    (which only selects the cached context).
+
+    psd   : (dim, dim) PSD, centred, in nm^2 m^2 at the PSF wavelength; or (npsd, dim, dim)
+    pup   : (npup, npup) pupil, any real values (apodisation, spiders, segment gaps)
+    D     : pupil diameter [m]
+    lbda  : PSF wavelength [m], a scalar or a 1-D array
+    phase_static : (npup, npup) static phase or None.  It is used as the reference's code uses it,
+            exp(2 pi i phase_static / lbda) with lbda in metres, so it is in METRES (the reference's
+            docstring says nm).
+    samp  : output sampling (pixels per diffraction element); None means dim / npup.  (The reference
+            raises TypeError for None.)
+    FoV   : PSF field [arcsec]; only the reference's numerical field FoVnum is supported.
+
+    Returns the (dimnum, dimnum) PSF of sum 1, dimnum = int(fix(dim samp / sampnum / 2)) 2, with the
+    leading axes (npsd, nl) of a PSD stack and of a wavelength array; with `return_all`,
+    (psf, sampout, FoV) as psfrec.py:803-805.
+    Refused before any GPU work: FoV != FoVnum (NotImplementedError, as the reference's cubic
+    interpolation), samp > dim / npup (ValueError; the reference fails with TypeError), a phase_static
+    of another shape than pup (ValueError), a grid or dimnum without a planned transform (ValueError).
+    """
+    psd = np.asarray(psd, dtype=float)
+    pup = np.asarray(pup, dtype=float)
+    if psd.ndim not in (2, 3) or psd.shape[-1] != psd.shape[-2]:
+        raise ValueError('psd must be (dim, dim) or (npsd, dim, dim)')
+    if pup.ndim != 2 or pup.shape[0] != pup.shape[1]:
+        raise ValueError('pup must be a square 2-D array')
+    lb = np.asarray(lbda, dtype=float)
+    if lb.ndim > 1:
+        raise ValueError('lbda must be a scalar or a 1-D array')
+    dim = psd.shape[-1]
+    npup = pup.shape[0]
+    sampnum = dim / npup
+    if dim < 2 * npup:
+        logger.info("the PSD horizon must be at least two time larger than "
+                    "the pupil diameter")
+    sampin = sampnum if samp is None else samp
+    if sampin < 2:
+        logger.info('PSF should be at least nyquist sampled')
+    dimnum = int(np.fix(dim * (sampin / sampnum) / 2)) * 2
+    sampout = dimnum / npup
+    if sampin > sampnum:
+        raise ValueError('samp=%g > dim / npup = %g: the PSD would have to be extrapolated; '
+                         'use a larger PSD' % (sampin, sampnum))
+    logger.debug('input sampling: %.2f, output sampling: %.2f, max num sampling: %.2f',
+                 sampin, sampout, sampnum)
+    FoVnum = (lb / (sampnum * D)) * dim / (4.85 * 1.e-6)
+    if FoV is None:
+        FoV = FoVnum
+    if not np.allclose(FoV, FoVnum):
+        raise NotImplementedError('FIXME: use gridddata or spline ?')
+    if phase_static is not None:
+        phase_static = np.asarray(phase_static, dtype=float)
+        if phase_static.shape != pup.shape:
+            logger.info("pup and static phase must have the same number of pixels")
+            raise ValueError('phase_static must have the shape of pup %s, not %s'
+                             % (pup.shape, phase_static.shape))
+    if logger.isEnabledFor(logging.DEBUG):
+        for fv, fn in zip(np.broadcast_to(FoV, lb.shape).ravel(), FoVnum.ravel()):
+            logger.debug('input FoV: %.2f, output FoV: %.2f, Num FoV: %.2f', fv, fn, fn)
+    if dim not in _P2P_SIZES:
+        raise ValueError('grid dim=%d not supported %s' % (dim, _P2P_SIZES))
+    if dimnum not in _P2P_SIZES or dimnum < npup:
+        raise ValueError('dimnum=%d not supported (one of %s, and >= npup=%d)' % (dimnum, _P2P_SIZES, npup))
+    ctx = get_context(dim, 0.2, 40, precision, device)
+    out = ctx.psd_to_psf(psd, pup, D, lb.ravel(), phase_static=phase_static, dimnum=dimnum)
+    if psd.ndim == 2:
+        out = out[0]
+    if lb.ndim == 0:
+        out = out[..., 0, :, :]
+    if return_all:
+        return out, sampout, FoVnum * dimnum / dim
+    return out
+
+
 def convolve_final_psf(lbda, seeing, GL, L0, psf, *, pixscale=0.2, precision='mixed', device=0):
     """Convolve with the tip-tilt and MUSE PSFs to get the final PSF (psfrec.py:874-930).  `psf`:
     (nl, 40, 40)."""
