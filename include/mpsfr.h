@@ -190,6 +190,33 @@ int mpsfr_reconstruct(mpsfr_ctx* ctx, int ntask, const double* seeing, const dou
                       const uint8_t* mask_rec, const uint8_t* mask_res, double* psf_out,
                       double* psf_sum_out, double* fit_out, int on_device);
 
+/* Field-resolved PSFs: one stamp and one Moffat fit per (row, field position, wavelength), at positions the caller
+ * chooses.  The reference documents npsflin as the points where the PSF is reconstructed, then averages them
+ * (psf_muse, psfrec.py:667-674); this keeps them apart.  Stamp (t, p, l) is what compute_psf would return for row t
+ * if its PSD were the single direction p: psf_muse on that direction's PSD, convolve_final_psf with row t's
+ * tip-tilt kernel, then the fit.  Nothing is averaged over positions.
+ *
+ * npos, pos_arcsec : [npos][2] (x, y) in arcsec, 1 <= npos <= 25, in the convention of direction_perf (x is
+ *                    dirperf[0]); every coordinate finite with |x|, |y| <= 60 (twice the WFM half-field).
+ *                    direction_perf(npsflin) passed here gives exactly the directions of npsflin.  Anything else
+ *                    returns MPSFR_E_INVALID and touches nothing.
+ * psf_out          : [ntask][npos][nl][dimpsf][dimpsf] final stamps, or NULL
+ * psf_sum_out      : [npos][nl][dimpsf][dimpsf] sum over the ntask rows, or NULL
+ * fit_out          : [ntask][npos][nl][MPSFR_NFIT], fields and status bits as for mpsfr_reconstruct, or NULL
+ * Every other argument, on_device 0 / 1 / 2 included (lanes, tickets, mpsfr_wait, mpsfr_sync, mpsfr_abandon,
+ * mpsfr_stream_wait, mpsfr_wait_event), means what it means for mpsfr_reconstruct.  The eps = prune_eps + tier_eps
+ * guarantee of mpsfr_set_option holds PER STAMP: each (row, position) stamp is held to it on its own.
+ * One position at (0, 0) is mpsfr_reconstruct with npsflin = 1, bit for bit; every position is computed
+ * independently of the others in the call (psf_out and fit_out equal a call with that position alone, bit for bit).
+ * After a field call, mpsfr_debug_fetch's per-task shapes ("pre", "vkeep", "mf_work") count (row, position) pairs:
+ * [chunk tasks][npos]...; "dphi0" and "ao_tables" have npos directions. */
+int mpsfr_reconstruct_field(mpsfr_ctx* ctx, int ntask, const double* seeing, const double* gl,
+                            const double* l0, const uint8_t* three_lgs, const double h[2],
+                            double wind_speed, int npos, const double* pos_arcsec,
+                            int nl, const double* lbda_nm, const uint8_t* mask_rec,
+                            const uint8_t* mask_res, double* psf_out, double* psf_sum_out,
+                            double* fit_out, int on_device);
+
 /* The same over several devices: the reference's  Parallel(n_jobs=...)  fans the rows out over
  * worker processes (psfrec.py:1082-1083); here the rows go in contiguous, balanced shards (the
  * first ntask % nctx contexts take one row more) to `nctx` contexts -- normally one per device,

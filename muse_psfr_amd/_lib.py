@@ -65,6 +65,9 @@ def load():
     lib.mpsfr_reconstruct.argtypes = [p, C.c_int, dp, dp, dp, u8p, dp, C.c_double, C.c_int,
                                       C.c_int, dp, u8p, u8p, p, p, p, C.c_int]
     lib.mpsfr_reconstruct.restype = C.c_int
+    lib.mpsfr_reconstruct_field.argtypes = [p, C.c_int, dp, dp, dp, u8p, dp, C.c_double, C.c_int, dp,
+                                            C.c_int, dp, u8p, u8p, p, p, p, C.c_int]
+    lib.mpsfr_reconstruct_field.restype = C.c_int
     lib.mpsfr_reconstruct_multi.argtypes = [C.POINTER(p), C.c_int, C.c_int, dp, dp, dp, u8p, dp, C.c_double,
                                             C.c_int, C.c_int, dp, u8p, u8p, p, p, p]
     lib.mpsfr_reconstruct_multi.restype = C.c_int
@@ -121,7 +124,7 @@ def load():
 
 
 EXPORTS = ['mpsfr_create', 'mpsfr_destroy', 'mpsfr_last_error', 'mpsfr_set_option',
-           'mpsfr_reconstruct', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
+           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
            'mpsfr_psd_to_psf',
            'mpsfr_convolve_stamps', 'mpsfr_fit_rows', 'mpsfr_sync', 'mpsfr_last_ticket', 'mpsfr_wait', 'mpsfr_abandon',
            'mpsfr_stream', 'mpsfr_stream_wait', 'mpsfr_wait_event',
@@ -137,6 +140,31 @@ def fit_rows(fit, pixscale, out):
     assert out.dtype == np.float64 and out.ndim == 2 and out.shape[0] == f.shape[0] and out.strides[1] == 8
     _check(load().mpsfr_fit_rows(_dptr(f), f.shape[0], float(pixscale), out.ctypes.data_as(C.POINTER(C.c_double)),
                                  out.strides[0] // 8))
+
+
+MAX_FIELD_POSITIONS = 25     # AoGeom::dir[2][25]: positions of one mpsfr_reconstruct_field call
+MAX_FIELD_ARCSEC = 60.0      # |x|, |y| bound of a field position (twice the WFM half-field)
+
+
+def field_positions(positions, max_n=MAX_FIELD_POSITIONS):
+    """Validated (npos, 2) float64 C-contiguous array of field positions (x, y) in arcsec, in the convention of
+    direction_perf (x = dirperf[0]).  Raises ValueError for a wrong shape, no position, more than `max_n`, a
+    non-finite coordinate or one beyond MAX_FIELD_ARCSEC."""
+    try:
+        pos = np.array(positions, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('positions must be an (n, 2) array of (x, y) in arcsec') from None
+    if pos.ndim != 2 or pos.shape[1] != 2:
+        raise ValueError('positions must be an (n, 2) array of (x, y) in arcsec, got shape %s' % (pos.shape,))
+    if pos.shape[0] < 1:
+        raise ValueError('positions must not be empty')
+    if max_n is not None and pos.shape[0] > max_n:
+        raise ValueError('at most %d positions per call, got %d' % (max_n, pos.shape[0]))
+    if not np.all(np.isfinite(pos)):
+        raise ValueError('positions must be finite')
+    if np.any(np.abs(pos) > MAX_FIELD_ARCSEC):
+        raise ValueError('positions must satisfy |x|, |y| <= %g arcsec' % MAX_FIELD_ARCSEC)
+    return np.ascontiguousarray(pos)
 
 
 def device_count():
@@ -267,6 +295,67 @@ class Context:
             self._handed_over(ticket - 4)        # the call itself handed over the ticket four calls back
             return PendingResult(self, ticket, arrays)
         return dict(psf=psf, psf_sum=psum, fit=fit)
+
+    def reconstruct_field_async(self, *args, **kwargs):
+        """`reconstruct_field` without waiting for the GPU (on_device = 2): returns a PendingResult."""
+        return self.reconstruct_field(*args, _async=True, **kwargs)
+
+    def reconstruct_field(self, lbda, seeing, gl, l0, three_lgs=None, h=(100, 10000), positions=((0.0, 0.0),),
+                          wind_speed=None, masks=None, want_psf=True, want_sum=True, want_fit=True, _async=False):
+        """Field-resolved host-buffer call (mpsfr_reconstruct_field): one stamp and one fit per (row, position,
+        wavelength) at `positions` ((npos, 2) arcsec, npos <= 25).  Returns dict(psf (nt, npos, nl, 40, 40),
+        psf_sum (npos, nl, 40, 40), fit (nt, npos, nl, NFIT)) of float64 arrays (or None)."""
+        pos = field_positions(positions)
+        seeing, gl, l0, lbda, three, hh, wind_speed, mrec, mres = self._inputs(lbda, seeing, gl, l0, three_lgs, h,
+                                                                              wind_speed, masks)
+        nt, nl, npos, n = seeing.size, lbda.size, pos.shape[0], self.dimpsf
+        psf = np.empty((nt, npos, nl, n, n)) if want_psf else None
+        psum = np.empty((npos, nl, n, n)) if want_sum else None
+        fit = np.empty((nt, npos, nl, NFIT)) if want_fit else None
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _check(self.lib.mpsfr_reconstruct_field(
+            self._h, nt, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), _dptr(hh),
+            float(wind_speed), npos, _dptr(pos), nl, _dptr(lbda), _u8ptr(mrec), _u8ptr(mres),
+            vp(psf), vp(psum), vp(fit), 2 if _async else 0))
+        arrays = dict(psf=psf, psf_sum=psum, fit=fit)
+        if _async:
+            ticket = int(self.lib.mpsfr_last_ticket(self._h))
+            self._pending[ticket] = arrays
+            self._handed_over(ticket - 4)
+            return PendingResult(self, ticket, arrays)
+        return arrays
+
+    def reconstruct_field_device(self, lbda, seeing, gl, l0, three_lgs, h, wind_speed, positions, masks,
+                                 psf_ptr, sum_ptr, fit_ptr):
+        """Device-buffer field call (asynchronous, on_device = 1): outputs are raw device pointers (int or None)
+        on this context's GPU, shaped as in reconstruct_field."""
+        pos = field_positions(positions)
+        seeing, gl, l0, lbda, three, hh, wind_speed, mrec, mres = self._inputs(lbda, seeing, gl, l0, three_lgs, h,
+                                                                              wind_speed, masks)
+        _check(self.lib.mpsfr_reconstruct_field(
+            self._h, seeing.size, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), _dptr(hh),
+            float(wind_speed), pos.shape[0], _dptr(pos), lbda.size, _dptr(lbda), _u8ptr(mrec), _u8ptr(mres),
+            C.c_void_p(psf_ptr), C.c_void_p(sum_ptr), C.c_void_p(fit_ptr), 1))
+
+    @staticmethod
+    def _inputs(lbda, seeing, gl, l0, three_lgs, h, wind_speed, masks):
+        seeing = np.ascontiguousarray(np.atleast_1d(seeing), dtype=np.float64)
+        gl = np.ascontiguousarray(np.atleast_1d(gl), dtype=np.float64)
+        l0 = np.ascontiguousarray(np.atleast_1d(l0), dtype=np.float64)
+        lbda = np.ascontiguousarray(np.atleast_1d(lbda), dtype=np.float64)
+        three = np.zeros(seeing.size, np.uint8) if three_lgs is None else \
+            np.ascontiguousarray(np.atleast_1d(three_lgs)).astype(np.uint8)
+        if wind_speed is None:
+            wind_speed = float(np.full_like(np.array(h), 12.5)[0])      # psfrec.py:61
+        hh = np.ascontiguousarray(h, dtype=np.float64)
+        if hh.size != 2:
+            raise ValueError('exactly two layers are supported (psfrec.py:66)')
+        mrec = mres = None
+        if masks is not None:
+            mrec = np.ascontiguousarray(masks[0]).astype(np.uint8).reshape(-1)
+            mres = np.ascontiguousarray(masks[1]).astype(np.uint8).reshape(-1)
+            assert mrec.size == DIM_AO * DIM_AO and mres.size == DIM_AO * DIM_AO
+        return seeing, gl, l0, lbda, three, hh, wind_speed, mrec, mres
 
     @staticmethod
     def reconstruct_multi_async(ctxs, *args, **kwargs):

@@ -8,7 +8,7 @@ import sys
 
 from . import __version__
 from . import _minifits
-from .psfrec import _astropy, compute_psf_from_sparta, create_sparta_table
+from .psfrec import _astropy, compute_psf_from_sparta, create_sparta_table, direction_perf
 
 logger = logging.getLogger(__name__)
 RULE = '-' * 68
@@ -72,9 +72,14 @@ def main(args=None):
     add('--plot', action='store_true', help='plot reconstructed psf')
     add('--device', default=None, type=int, help='GPU index (default: device 0 for a single PSF; a SPARTA\n'
         'table fans out over the visible GPUs)')
+    add('--field', default=None, type=int, metavar='N',
+        help='also reconstruct the PSF at the N x N positions of direction_perf(N) (1..5): HDUs PSF_FIELD and\n'
+        'FIT_FIELD of the -o file')
     add('--version', action='version', version='%(prog)s ' + __version__)
     opt = parser.parse_args(args)
 
+    if opt.field is not None and not 1 <= opt.field <= 5:
+        sys.exit('--field must be between 1 and 5')
     _setup_logging(opt.verbose)
     logger.info('MUSE-PSFR version %s', __version__)
 
@@ -104,7 +109,8 @@ def main(args=None):
 
     logger.info('Computing PSF Reconstruction from Sparta data')
     res = compute_psf_from_sparta(source, lmin=500, lmax=900, nl=3, n_jobs=opt.njobs,
-                                  plot=opt.plot, device=opt.device)
+                                  plot=opt.plot, device=opt.device,
+                                  field_positions=None if opt.field is None else direction_perf(opt.field).T)
     if not res:
         sys.exit('No results')
     data = res['FIT_MEAN'].data

@@ -237,15 +237,17 @@ void launch_xtab(hipStream_t s, int N, int nl, const int* d_samp_p, const void* 
 // d_vkeep: [ntask][(nl+1)/2] lines to read per (task, wavelength pair), or nullptr for all
 void launch_colpass(hipStream_t s, int N, int ntask, int nl, const void* d_Tq, const void* d_G,
                     void* d_pre, bool f64, const int* d_vkeep);
+// tdiv: stamp group g (blockIdx.y of the launch) takes the tip-tilt kernel g / tdiv -- 1 for one group per task; the
+// field call (mpsfr_reconstruct_field) lays its chunks out as (task, position) groups and passes npos
 void launch_conv(hipStream_t s, int ntask, int nl, const void* d_pre, const void* d_ktt,
-                 const void* d_kmuse, double* d_fin, bool f64);
+                 const void* d_kmuse, double* d_fin, bool f64, int tdiv = 1);
 void launch_khat(hipStream_t s, int nker, const double* d_gamma, const double* d_alpha,
                  void* d_khat, bool f64 = false);
 // fin_f32 / stamps_f32: the final stamps are float (inside the pipeline) instead of double
 // f64: double stamps in and out, fp64 transforms, khat tables of complex double
 void launch_conv_fft(hipStream_t s, int ntask, int nl, const void* d_pre, const void* d_khat_tt,
                      const void* d_khat_muse, void* d_fin, bool fin_f32, bool f64 = false,
-                     const MfFinishArgs& finish = MfFinishArgs());
+                     const MfFinishArgs& finish = MfFinishArgs(), int tdiv = 1);
 // (sum_*: the deterministic sum of the stamps over the sum_ntask tasks of the chunk -- [sum_nl][40][40] into d_sum,
 // added to it if sum_accumulate -- as the first workgroups of the same launch; d_sum = nullptr: none)
 void launch_fit(hipStream_t s, int nstamp, const void* d_stamps, bool stamps_f32, double* d_fit,

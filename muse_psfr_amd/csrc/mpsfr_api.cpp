@@ -229,6 +229,7 @@ struct mpsfr_ctx {
     const void* cache_ao_ptr = nullptr;
     // bookkeeping for debug_fetch
     int last_ndir = 0, last_nl = 0, last_chunk_tasks = 0, last_lane = 0;
+    int last_gpp = 1;                    // stamp groups per task of the last call: npos of a field call, else 1
     bool last_mf = false, last_pruned = false, last_mf2 = false;
     float last_thr_blk = 0.f;
     bool last_floor_per_task = false;
@@ -807,6 +808,10 @@ struct StageIO {
     const double* psd_in = nullptr;   // [ndir][N][N]: the PSD of the one task, instead of the model
     const double* pre_in = nullptr;   // [ntask][nl][40][40]: stamps before the convolutions, instead of stages A + B
     bool stop_pre = false;            // psf_out receives the stamps BEFORE the convolutions (psf_muse)
+    // mpsfr_reconstruct_field: stage A evaluates the npos caller positions pos [npos][2] (arcsec) instead of the
+    // npsflin grid, and stage B keeps them apart -- every (task, position) pair is a one-direction task of its own
+    int npos = 0;
+    const double* pos = nullptr;
 };
 
 static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const double* gl,
@@ -852,6 +857,25 @@ int mpsfr_reconstruct(mpsfr_ctx* c, int ntask, const double* seeing, const doubl
                         psf_out, psf_sum_out, fit_out, on_device, StageIO());
 }
 
+int mpsfr_reconstruct_field(mpsfr_ctx* c, int ntask, const double* seeing, const double* gl,
+                            const double* l0, const uint8_t* three_lgs, const double h[2],
+                            double wind_speed, int npos, const double* pos_arcsec,
+                            int nl, const double* lbda_nm, const uint8_t* mask_rec,
+                            const uint8_t* mask_res, double* psf_out, double* psf_sum_out,
+                            double* fit_out, int on_device) {
+    if (!c) return fail(MPSFR_E_INVALID, "ctx is NULL");
+    if (npos < 1 || npos > 25) return fail(MPSFR_E_INVALID, "npos=%d out of range 1..25", npos);
+    if (!pos_arcsec) return fail(MPSFR_E_INVALID, "pos_arcsec is NULL");
+    for (int k = 0; k < 2 * npos; ++k)
+        if (!std::isfinite(pos_arcsec[k]) || std::fabs(pos_arcsec[k]) > 60.0)
+            return fail(MPSFR_E_INVALID, "position %d: need finite |x|, |y| <= 60 arcsec", k / 2);
+    StageIO io;
+    io.npos = npos;
+    io.pos = pos_arcsec;
+    return guarded_call(c, ntask, seeing, gl, l0, three_lgs, h, wind_speed, 1, nl, lbda_nm, mask_rec, mask_res,
+                        psf_out, psf_sum_out, fit_out, on_device, io);
+}
+
 static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const double* gl,
                             const double* l0, const uint8_t* three_lgs, const double h[2],
                             double wind_speed, int npsflin, int nl, const double* lbda_nm,
@@ -863,10 +887,16 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
     if (ntask < 1 || !seeing || !gl || !l0 || !h || !lbda_nm)
         return fail(MPSFR_E_INVALID, "ntask < 1 or NULL input array");
     if (nl < 1 || nl > 4096) return fail(MPSFR_E_INVALID, "nl=%d out of range", nl);
-    if (npsflin < 1 || npsflin > 5) return fail(MPSFR_E_INVALID, "npsflin=%d out of range 1..5", npsflin);
+    const bool field = io.npos > 0;
+    if (field && (staged || !io.pos)) return fail(MPSFR_E_INVALID, "field call without positions");
+    if (!field && (npsflin < 1 || npsflin > 5)) return fail(MPSFR_E_INVALID, "npsflin=%d out of range 1..5", npsflin);
     if ((mask_rec == nullptr) != (mask_res == nullptr))
         return fail(MPSFR_E_INVALID, "mask_rec and mask_res must both be given or both be NULL");
-    const int N = c->N, H1 = N / 2 + 1, ndir = npsflin * npsflin;
+    // ndir: the directions stage A evaluates per task.  Stage B sums ndb of them into a stamp, for gpp stamp groups
+    // per task: the averaged call (ndb = ndir, gpp = 1) or the field call (ndb = 1, gpp = npos: group g of a chunk is
+    // task g / npos at position g % npos, and every stage-B kernel sees tc x npos one-direction tasks)
+    const int N = c->N, H1 = N / 2 + 1, ndir = field ? io.npos : npsflin * npsflin;
+    const int gpp = field ? ndir : 1, ndb = field ? 1 : ndir;
     HIPCHK(hipSetDevice(c->device));
     int rc;
 
@@ -909,7 +939,7 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
     // Stage A in its series form needs every 1/L0^2 inside the radius of its expansion (L0 >= 7 m;
     // the SPARTA front end only lets 8 < L0 < 30 through, psfrec.py:1049-1051); a call with a shorter
     // outer scale takes the full-size transforms.
-    bool series = c->stage_a == 2 || (c->stage_a == 1 && (N >= 512 || (N >= 256 && npsflin >= 2)));
+    bool series = c->stage_a == 2 || (c->stage_a == 1 && (N >= 512 || (N >= 256 && ndir >= 2)));
     if (io.psd_in) series = false;
     for (int t = 0; t < ntask; ++t) series = series && tp[t].inv_l0sq <= series_eps_max();
 
@@ -933,8 +963,13 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
         }
     g.ndir = ndir;
     for (int d = 0; d < ndir; ++d) {
-        g.dir[0][d] = (double)(d / npsflin - npsflin / 2) * 60 / 2 / 60;
-        g.dir[1][d] = (double)(d % npsflin - npsflin / 2) * 60 / 2 / 60;
+        if (field) {                    // (the convention of direction_perf: x = dirperf[0], in arcmin here)
+            g.dir[0][d] = io.pos[2 * d] / 60;
+            g.dir[1][d] = io.pos[2 * d + 1] / 60;
+        } else {
+            g.dir[0][d] = (double)(d / npsflin - npsflin / 2) * 60 / 2 / 60;
+            g.dir[1][d] = (double)(d % npsflin - npsflin / 2) * 60 / 2 / 60;
+        }
     }
 
     // ---- asynchronous host outputs: the call writes a result set of the ring and is, from here on, a
@@ -946,9 +981,9 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
         tk->u_psf = psf_out;
         tk->u_sum = psf_sum_out;
         tk->u_fit = fit_out;
-        tk->n_psf = psf_out ? (size_t)ntask * nl * NS * NS : 0;
-        tk->n_sum = psf_sum_out ? (size_t)nl * NS * NS : 0;
-        tk->n_fit = fit_out ? (size_t)ntask * nl * NFIT : 0;
+        tk->n_psf = psf_out ? (size_t)ntask * gpp * nl * NS * NS : 0;
+        tk->n_sum = psf_sum_out ? (size_t)gpp * nl * NS * NS : 0;
+        tk->n_fit = fit_out ? (size_t)ntask * gpp * nl * NFIT : 0;
         const size_t hb = (tk->n_psf + tk->n_sum + tk->n_fit) * sizeof(double);
         if (hb > tk->host_cap) {
             if (tk->host) HIPCHK(hipHostFree(tk->host));
@@ -979,8 +1014,10 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
         // balanced chunks, a multiple of the lane count of them.  (The chunks used to be cut at ~4096
         // stamps, "enough to fill the GPU": a 125-row call then ran as 118 + 7 rows and reached 9.8 M
         // PSFs/s where one chunk reaches 14.6 M; 250 rows 11.3 -> 15.3 M, 1000 rows 14.5 -> 15.1 M.)
-        int big = 65536 / nl;
-        const int soft = (4096 + nl - 1) / nl < 8 ? 8 : (4096 + nl - 1) / nl;
+        // (stamps per task: gpp x nl)
+        const int spt = gpp * nl;
+        int big = 65536 / spt;
+        const int soft = (4096 + spt - 1) / spt < 8 ? 8 : (4096 + spt - 1) / spt;
         if (big > 512) big = 512;
         if (big < soft) big = soft;
         // (the largest workspace per task: the row transforms C of the full-size form; D and the patch
@@ -994,7 +1031,7 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
         // A synchronous call (host outputs, or pipelining off) has no neighbour call on the other lane:
         // from 8192 stamps on, one pass per lane overlaps the stages of the halves (250 rows x 35
         // wavelengths at 512^2: 0.78 -> 0.75 ms per call; 100 rows: 0.42 either way; four passes lose).
-        if (nch == 1 && NLmax > 1 && (long)ntask * nl >= 8192 && !(c->pipeline_calls && on_device != 0))
+        if (nch == 1 && NLmax > 1 && (long)ntask * spt >= 8192 && !(c->pipeline_calls && on_device != 0))
             nch = NLmax;
         TC = (ntask + nch - 1) / nch;
     }
@@ -1203,8 +1240,8 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
     if ((rc = ensure(c, c->kmuse, (size_t)nl * ksz))) return rc;
     // per-wavelength stage on the matrix cores (otf_mfma = 0: LDS FFTs on the vector pipe)
     const bool mf = !c->f64 && c->otf_mfma;
-    const bool mf2 = mf && ndir == 1 && c->mf_kernel == 2;      // thin-wave kernel (otf_mfma2.hip)
-    const bool r16 = !mf && otf_uses_r16(N, c->f64, nl, ndir);
+    const bool mf2 = mf && ndb == 1 && c->mf_kernel == 2;       // thin-wave kernel (otf_mfma2.hip)
+    const bool r16 = !mf && otf_uses_r16(N, c->f64, nl, ndb);
     // (the stamps K_OTF_MFMA2 leaves as partial tiles are finished by the FFT convolution kernel itself; a call
     // that hands out the stamps before the convolutions -- psf_muse -- or skips stage B keeps K_MF_FINISH)
     const bool fuse_finish = mf2 && c->finish_fusion && c->fft_conv && !io.stop_pre && !io.pre_in;
@@ -1317,6 +1354,7 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
 
     // ---- chunk workspaces
     const size_t per_stamp = (size_t)NS * NS;
+    const int TB = TC * gpp;                // stage-B tasks of a chunk: (task, position) pairs in a field call
     // Line pruning of the per-wavelength stage (mixed mode): the trailing lines of the OTF half
     // plane that together weigh less than eps of the PSF peak are neither transformed nor read
     // by the second pass (stage_a.hip, "Line pruning").
@@ -1324,9 +1362,10 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
     const bool prune = eps_prune > 0.0;
     // matrix-core path: half of eps for the lines, half for the 16 x 32 blocks inside them (every
     // element of a dropped block is below 2^thr_blk; both half planes, all directions)
-    const float thr_sum = prune ? (float)((mf ? 0.5 : 1.0) * eps_prune / (2.0 * N * ndir)) : 0.f;
+    // (ndb: the directions one stamp sums -- a field stamp has one, and the whole budget)
+    const float thr_sum = prune ? (float)((mf ? 0.5 : 1.0) * eps_prune / (2.0 * N * ndb)) : 0.f;
     float thr_blk = (prune && mf)
-        ? (float)std::log2(0.5 * eps_prune / (2.0 * ndir * 16 * 32 * mf_block_count(N))) : 0.f;
+        ? (float)std::log2(0.5 * eps_prune / (2.0 * ndb * 16 * 32 * mf_block_count(N))) : 0.f;
     // Precision tiers of the matrix-core stage.  The OTF is generated times 2^15, so an element
     // below 2^-29 of OTF[0][0] has both fp16 halves in the subnormal range: a block whose bound is below
     // 2^-29.01 carries a few bits per element and is dropped ("floor"); a block below 2^-18.01 runs without
@@ -1361,8 +1400,8 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
     }
     for (int j = 0; j < NL; ++j) {
         mpsfr_ctx::Lane& ln = lane_of(j);
-        if ((rc = ensure(c, ln.pre, (size_t)TC * nl * per_stamp * (c->f64 ? 8 : 4)))) return rc;
-        if ((rc = ensure(c, ln.fin, (size_t)TC * nl * per_stamp * sizeof(double)))) return rc;
+        if ((rc = ensure(c, ln.pre, (size_t)TB * nl * per_stamp * (c->f64 ? 8 : 4)))) return rc;
+        if ((rc = ensure(c, ln.fin, (size_t)TB * nl * per_stamp * sizeof(double)))) return rc;
         if (io.pre_in) continue;            // convolutions only: no workspace of stages A and B
         if (series) {
             if ((rc = ensure(c, ln.pP, (size_t)TC * ndir * NAO * NAO * sizeof(double)))) return rc;
@@ -1382,31 +1421,33 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
             if ((rc = ensure(c, ln.D0t, ((size_t)TC * ndir * H1 + 16) * N * rsize(c)))) return rc;
             if (ln.D0t.cap != cap_before) HIPCHK(hipMemset(ln.D0t.p, 0, ln.D0t.cap));
         }
-        if (!mf && (rc = ensure(c, ln.Tq, (size_t)TC * nl * H1 * NSH * 2 * rsize(c)))) return rc;
+        if (!mf && (rc = ensure(c, ln.Tq, (size_t)TB * nl * H1 * NSH * 2 * rsize(c)))) return rc;
         if (mf2) {
-            if ((rc = ensure(c, ln.mown, mf2_own_bytes(N, TC, nl)))) return rc;
-            if ((rc = ensure(c, ln.muni, mf2_uni_bytes(N, TC, nl)))) return rc;
-            if ((rc = ensure(c, ln.msched, mf2_sched_bytes(N, TC, nl, c->mf_permax)))) return rc;
-            if ((rc = ensure(c, ln.mpart, mf2_part_bytes(N, TC, nl)))) return rc;
+            if ((rc = ensure(c, ln.mown, mf2_own_bytes(N, TB, nl)))) return rc;
+            if ((rc = ensure(c, ln.muni, mf2_uni_bytes(N, TB, nl)))) return rc;
+            if ((rc = ensure(c, ln.msched, mf2_sched_bytes(N, TB, nl, c->mf_permax)))) return rc;
+            if ((rc = ensure(c, ln.mpart, mf2_part_bytes(N, TB, nl)))) return rc;
         }
         if (prune) {
             if ((rc = ensure(c, ln.dmin, (size_t)TC * ndir * H1 * sizeof(float)))) return rc;
             if ((rc = ensure(c, ln.dblk, (size_t)ndir * mf_dminb_bytes(N, TC)))) return rc;
-            if (mf && (rc = ensure(c, ln.dminb, mf_dminb_bytes(N, TC)))) return rc;
-            if (mf && (rc = ensure(c, ln.order, (size_t)TC * sizeof(int)))) return rc;
-            if (mf && (rc = ensure(c, ln.thrf, (size_t)TC * sizeof(float)))) return rc;
-            if ((rc = ensure(c, ln.vkeep, (size_t)TC * ((nl + 1) / 2) * sizeof(int)))) return rc;
+            if (mf && (rc = ensure(c, ln.dminb, mf_dminb_bytes(N, TB)))) return rc;
+            if (mf && (rc = ensure(c, ln.order, (size_t)TB * sizeof(int)))) return rc;
+            if (mf && (rc = ensure(c, ln.thrf, (size_t)TB * sizeof(float)))) return rc;
+            if ((rc = ensure(c, ln.vkeep, (size_t)TB * ((nl + 1) / 2) * sizeof(int)))) return rc;
         }
     }
-    if (NL > 1 && (rc = ensure(c, c->lsum, (size_t)NL * nl * per_stamp * sizeof(double)))) return rc;
-    if ((rc = ensure(c, c->sum, (size_t)nl * per_stamp * sizeof(double)))) return rc;
+    // (the sums run over the tasks of [task][gpp x nl] stamps: a field call sums into [npos][nl])
+    const int nsum = gpp * nl;
+    if (NL > 1 && (rc = ensure(c, c->lsum, (size_t)NL * nsum * per_stamp * sizeof(double)))) return rc;
+    if ((rc = ensure(c, c->sum, (size_t)nsum * per_stamp * sizeof(double)))) return rc;
     double* d_fin_all = nullptr;   // [ntask][nl][1600] if the caller gave a device buffer
     double* d_fit_all = nullptr;
     if (dev_out && psf_out) d_fin_all = psf_out;
     if (dev_out && fit_out) {
         d_fit_all = fit_out;
     } else {
-        if ((rc = ensure(c, c->fit, (size_t)ntask * nl * NFIT * sizeof(double)))) return rc;
+        if ((rc = ensure(c, c->fit, (size_t)ntask * gpp * nl * NFIT * sizeof(double)))) return rc;
         d_fit_all = (double*)c->fit.p;
     }
     const double cfit = fit_constant();
@@ -1447,6 +1488,7 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
     for (int t0 = 0; t0 < ntask; t0 += TC, ++ci) {
         const int tc = (ntask - t0) < TC ? (ntask - t0) : TC;
         const int ntd = tc * ndir;
+        const int tb = tc * gpp;            // stage-B tasks of the chunk
         const int j = ci % NL;
         mpsfr_ctx::Lane& ln = lane_of(j);
         hipStream_t ls = ln.stream;
@@ -1552,17 +1594,17 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
             // over a block's 16 lines itself -- K_DMIN16 was 6 us of latency at 512^2, 13 at 1280^2)
             const bool from_lines = prune && series && !io.psd_in;
             if (prune && !from_lines) launch_dmin(ls, N, ntd, ln.D0t.p, (float*)ln.dmin.p, (float*)ln.dblk.p);
-            launch_mf_prep(ls, N, tc, nl, c->mf_permax, d_lp, (prune && !from_lines) ? (const float*)ln.dblk.p : nullptr,
+            launch_mf_prep(ls, N, tb, nl, c->mf_permax, d_lp, (prune && !from_lines) ? (const float*)ln.dblk.p : nullptr,
                            (const float*)c->tlb.p, thr_eps, thr_floor, thr_mid, tier_half, ln.D0t.p, (const float*)c->tl2.p,
                            ln.mown.p, ln.muni.p, ln.msched.p, from_lines ? (const float*)ln.dlin.p : nullptr);
         } else if (prune) {
             ProfScope ps(c, mf ? K_MF_PREP : K_VKEEP, ls);
             if (series) launch_dmin16(ls, N, ntd, (const float*)ln.dlin.p, (float*)ln.dmin.p, (float*)ln.dblk.p);
             else launch_dmin(ls, N, ntd, ln.D0t.p, (float*)ln.dmin.p, (float*)ln.dblk.p, c->f64);
-            launch_vkeep(ls, N, tc, ndir, nl, d_lp, (const float*)ln.dmin.p, (const float*)ln.dblk.p,
+            launch_vkeep(ls, N, tb, ndb, nl, d_lp, (const float*)ln.dmin.p, (const float*)ln.dblk.p,
                          (const float*)c->tlmax.p, thr_sum, (int*)ln.vkeep.p, c->prune_fixed,
                          mf ? (float*)ln.dminb.p : nullptr);
-            if (mf) launch_task_order(ls, tc, nl, (const int*)ln.vkeep.p, (int*)ln.order.p);
+            if (mf) launch_task_order(ls, tb, nl, (const int*)ln.vkeep.p, (int*)ln.order.p);
         }
         const int* d_vkeep = prune ? (const int*)ln.vkeep.p : nullptr;
         if (stagger_here(2)) return fail(MPSFR_E_HIP, "hipEventRecord failed");
@@ -1572,15 +1614,15 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
             // (timed through the dispatch packet of K_OTF_MFMA2 itself: the persistent kernel alone, without
             // K_MF_FINISH and without marker packets round it)
             ProfScope ps(c, K_OTF_MFMA, ls, false);
-            launch_otf_mfma2(ls, N, tc, nl, c->mf_permax, persist_grid(c, ln, c->reserve_mf, lanes_shared), ln.D0t.p, (const float*)c->tl2.p, d_lp, c->etab.p,
+            launch_otf_mfma2(ls, N, tb, nl, c->mf_permax, persist_grid(c, ln, c->reserve_mf, lanes_shared), ln.D0t.p, (const float*)c->tl2.p, d_lp, c->etab.p,
                              c->gtab.p, ln.mown.p, ln.muni.p, ln.msched.p, ln.mpart.p, ln.pre.p,
                              c->mf_clock ? c->mfclk.p : nullptr, ps.a, ps.b, !fuse_finish);
         } else if (mf) {
             ProfScope ps(c, K_OTF_MFMA, ls);
             if (floor_per_task)
-                launch_peak_floor(ls, N, tc, ndir, ln.D0t.p, (const float*)c->tl2.p, c2min, tier_half, thr_floor,
+                launch_peak_floor(ls, N, tb, ndb, ln.D0t.p, (const float*)c->tl2.p, c2min, tier_half, thr_floor,
                                   (float*)ln.thrf.p);
-            launch_otf_mfma(ls, N, tc, ndir, nl, ln.D0t.p, (const float*)c->tl2.p, d_lp, c->etab.p,
+            launch_otf_mfma(ls, N, tb, ndb, nl, ln.D0t.p, (const float*)c->tl2.p, d_lp, c->etab.p,
                             c->gtab.p, d_vkeep, prune ? (const float*)ln.dminb.p : nullptr,
                             (const float*)c->tlb.p, thr_blk, ln.pre.p,
                             prune ? (const int*)ln.order.p : nullptr, c->mf_clock ? c->mfclk.p : nullptr,
@@ -1588,12 +1630,12 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
         } else {
             {
                 ProfScope ps(c, K_OTF_ROWFFT, ls);
-                launch_otf_rowfft(ls, N, tc, ndir, nl, ln.D0t.p, c->tel.p, d_lp,
+                launch_otf_rowfft(ls, N, tb, ndb, nl, ln.D0t.p, c->tel.p, d_lp,
                                   (const int*)c->samp_p.p, c->samp_a.p, c->xtab.p, ln.Tq.p, c->tw64.p,
                                   c->f64, c->fast_exp, d_vkeep);
             }
             ProfScope ps(c, K_COLPASS, ls);
-            launch_colpass(ls, N, tc, nl, ln.Tq.p, c->G.p, ln.pre.p, c->f64, d_vkeep);
+            launch_colpass(ls, N, tb, nl, ln.Tq.p, c->G.p, ln.pre.p, c->f64, d_vkeep);
         }
         if (io.stop_pre) {         // psf_muse: the stamps before the convolutions, as float64
             const size_t n = (size_t)tc * nl * per_stamp;
@@ -1616,32 +1658,33 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
         // final stamps: straight into the caller's device buffer (double), else a lane workspace --
         // float when the FFT convolution produces them and nobody outside reads them
         const bool fin_f32 = use_fft_conv && !c->f64 && !d_fin_all && !(psf_out && !dev_out);
-        void* d_fin = d_fin_all ? (void*)(d_fin_all + (size_t)t0 * nl * per_stamp) : ln.fin.p;
+        void* d_fin = d_fin_all ? (void*)(d_fin_all + (size_t)t0 * nsum * per_stamp) : ln.fin.p;
         {
             ProfScope ps(c, K_CONV, ls);
             const size_t koff = (size_t)t0 * ksz;
             if (use_fft_conv)
-                launch_conv_fft(ls, tc, nl, ln.pre.p, (const char*)sl.ktt.p + koff,
+                launch_conv_fft(ls, tb, nl, ln.pre.p, (const char*)sl.ktt.p + koff,
                                 c->kmuse.p, d_fin, fin_f32, c->f64,
-                                fuse_finish ? mf2_finish_args(N, tc, nl, c->mf_permax, ln.msched.p, ln.mpart.p) : MfFinishArgs());
+                                fuse_finish ? mf2_finish_args(N, tb, nl, c->mf_permax, ln.msched.p, ln.mpart.p) : MfFinishArgs(),
+                                gpp);
             else
-                launch_conv(ls, tc, nl, ln.pre.p, (const char*)sl.ktt.p + koff,
-                            c->kmuse.p, (double*)d_fin, c->f64);
+                launch_conv(ls, tb, nl, ln.pre.p, (const char*)sl.ktt.p + koff,
+                            c->kmuse.p, (double*)d_fin, c->f64, gpp);
         }
         // per-lane partial stamp sums in chunk order; combined below in lane order (deterministic)
-        double* lsum = NL > 1 ? (double*)c->lsum.p + (size_t)j * nl * per_stamp : d_sum;
+        double* lsum = NL > 1 ? (double*)c->lsum.p + (size_t)j * nsum * per_stamp : d_sum;
         if (fit_out) {             // (with the chunk's stamp sum as the first workgroups of the same launch)
             ProfScope ps(c, K_FIT, ls);
-            launch_fit(ls, tc * nl, d_fin, fin_f32, d_fit_all + (size_t)t0 * nl * NFIT, c->f64,
-                       psf_sum_out ? tc : 0, nl, psf_sum_out ? lsum : nullptr, nchunk_lane[j] > 0 ? 1 : 0);
+            launch_fit(ls, tb * nl, d_fin, fin_f32, d_fit_all + (size_t)t0 * nsum * NFIT, c->f64,
+                       psf_sum_out ? tc : 0, nsum, psf_sum_out ? lsum : nullptr, nchunk_lane[j] > 0 ? 1 : 0);
         } else if (psf_sum_out) {
             ProfScope ps(c, K_STAMP_SUM, ls);
-            launch_stamp_sum(ls, tc, nl, d_fin, fin_f32, lsum, nchunk_lane[j] > 0 ? 1 : 0);
+            launch_stamp_sum(ls, tc, nsum, d_fin, fin_f32, lsum, nchunk_lane[j] > 0 ? 1 : 0);
         }
         HIPCHK(hipGetLastError());
         if (!dev_out && psf_out) {
-            HIPCHK(hipMemcpyAsync(psf_out + (size_t)t0 * nl * per_stamp, d_fin,
-                                  (size_t)tc * nl * per_stamp * sizeof(double),
+            HIPCHK(hipMemcpyAsync(psf_out + (size_t)t0 * nsum * per_stamp, d_fin,
+                                  (size_t)tc * nsum * per_stamp * sizeof(double),
                                   hipMemcpyDeviceToHost, ls));
         }
         ++nchunk_lane[j];
@@ -1670,7 +1713,7 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
     if (psf_sum_out && NL > 1) {       // add the per-lane sums in lane order
         {
             ProfScope ps(c, K_STAMP_SUM);
-            launch_stamp_sum(s, NL, nl, c->lsum.p, false, d_sum, 0);
+            launch_stamp_sum(s, NL, nsum, c->lsum.p, false, d_sum, 0);
         }
         if (!c->lsum_done) HIPCHK(hipEventCreateWithFlags(&c->lsum_done, hipEventDisableTiming));
         HIPCHK(hipEventRecord(c->lsum_done, s));
@@ -1684,6 +1727,7 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
     sl.last_lane = lean ? (int)(&lane_of(0) - c->lane) : -1;
     sl.has_event = !zero;
     c->last_ndir = ndir;
+    c->last_gpp = gpp;
     c->last_nl = nl;
     c->last_mf = mf;
     c->last_mf2 = mf2;
@@ -1706,10 +1750,10 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
     }
     if (!dev_out) {
         if (fit_out)
-            HIPCHK(hipMemcpyAsync(fit_out, d_fit_all, (size_t)ntask * nl * NFIT * sizeof(double),
+            HIPCHK(hipMemcpyAsync(fit_out, d_fit_all, (size_t)ntask * nsum * NFIT * sizeof(double),
                                   hipMemcpyDeviceToHost, s));
         if (psf_sum_out)
-            HIPCHK(hipMemcpyAsync(psf_sum_out, d_sum, (size_t)nl * per_stamp * sizeof(double),
+            HIPCHK(hipMemcpyAsync(psf_sum_out, d_sum, (size_t)nsum * per_stamp * sizeof(double),
                                   hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
     }
@@ -2041,11 +2085,11 @@ long mpsfr_debug_fetch(mpsfr_ctx* c, const char* what, double* out, size_t capac
         src = c->lane[c->last_lane].D0t.p;
         is_real_r = true;
     } else if (!strcmp(what, "pre")) {
-        n = (size_t)c->last_chunk_tasks * c->last_nl * NS * NS;
+        n = (size_t)c->last_chunk_tasks * c->last_gpp * c->last_nl * NS * NS;
         mpsfr_ctx::Lane& lnp = c->lane[c->last_lane];
         if (c->last_pre_partial) {       // the stamps the convolution kernel finished on its way: complete them here
             if (lnp.stream) HIPCHK(hipStreamSynchronize(lnp.stream));
-            launch_mf_finish(c->stream, N, c->last_chunk_tasks, c->last_nl, c->last_permax, lnp.msched.p, lnp.mpart.p, lnp.pre.p);
+            launch_mf_finish(c->stream, N, c->last_chunk_tasks * c->last_gpp, c->last_nl, c->last_permax, lnp.msched.p, lnp.mpart.p, lnp.pre.p);
             HIPCHK(hipStreamSynchronize(c->stream));
             c->last_pre_partial = false;
         }
@@ -2057,7 +2101,7 @@ long mpsfr_debug_fetch(mpsfr_ctx* c, const char* what, double* out, size_t capac
         // [1] m-tiles with a second pass, [2] tile steps without any pruning.
         if (capacity < 3) return fail(MPSFR_E_INVALID, "capacity %zu < 3", capacity);
         if (!c->last_mf) return fail(MPSFR_E_INVALID, "the last call did not use the matrix-core kernel");
-        const int tc = c->last_chunk_tasks, nl = c->last_nl, npair = (nl + 1) / 2;
+        const int tc = c->last_chunk_tasks * c->last_gpp, nl = c->last_nl, npair = (nl + 1) / 2;
         const int nks = N / 32, nmt = (H1 + 15) / 16, nb = nmt * nks;
         const mpsfr_ctx::Lane& ln = c->lane[c->last_lane];
         std::vector<int> vk((size_t)tc * npair);
@@ -2135,7 +2179,7 @@ long mpsfr_debug_fetch(mpsfr_ctx* c, const char* what, double* out, size_t capac
         if (!c->last_pruned || c->last_mf2)
             return fail(MPSFR_E_INVALID, "no line pruning in the last call (prune_eps = 0, or the block-masked "
                                          "matrix-core kernel ran)");
-        n = (size_t)c->last_chunk_tasks * ((c->last_nl + 1) / 2);
+        n = (size_t)c->last_chunk_tasks * c->last_gpp * ((c->last_nl + 1) / 2);
         if (n > capacity) return fail(MPSFR_E_INVALID, "capacity %zu < %zu", capacity, n);
         std::vector<int> tmp(n);
         HIPCHK(hipMemcpy(tmp.data(), c->lane[c->last_lane].vkeep.p, n * sizeof(int), hipMemcpyDeviceToHost));

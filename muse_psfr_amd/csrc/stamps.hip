@@ -72,7 +72,7 @@ struct Vec4<double> { using type = double4; };
 
 template <typename R>
 __global__ void __launch_bounds__(256)
-k_conv(int nl, const R* __restrict__ pre, const R* __restrict__ ktt,
+k_conv(int nl, int tdiv, const R* __restrict__ pre, const R* __restrict__ ktt,
        const R* __restrict__ kmuse, double* __restrict__ fin) {
     constexpr int PH = NS + KS - 1;   // 80 frame rows
     constexpr int PW = 84;            // frame pitch (80 used)
@@ -99,7 +99,7 @@ k_conv(int nl, const R* __restrict__ pre, const R* __restrict__ ktt,
     const int i = 10 * wv + (active ? ln % 10 : 0), j0 = (active ? ln / 10 : 0) * SW;
     double acc[SW];
     for (int pass = 0; pass < 2; ++pass) {
-        const R* __restrict__ kg = pass == 0 ? ktt + (size_t)task * KS * KS
+        const R* __restrict__ kg = pass == 0 ? ktt + (size_t)(task / tdiv) * KS * KS
                                              : kmuse + (size_t)l * KS * KS;
         __syncthreads();
 #pragma unroll
@@ -167,7 +167,7 @@ template <typename R, typename TF>
 #define MPSFR_CONV_WAVES 4
 #endif
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(R) == 4 ? MPSFR_CONV_WAVES : 2)))
-k_conv_fft(int nl, const R* __restrict__ pre, const cx<R>* __restrict__ khat_tt,
+k_conv_fft(int nl, int tdiv, const R* __restrict__ pre, const cx<R>* __restrict__ khat_tt,
            const cx<R>* __restrict__ khat_muse, TF* __restrict__ fin, MfFinish mf) {
     extern __shared__ __align__(16) unsigned char conv_smem[];
     cx<R> (*F)[CFP] = reinterpret_cast<cx<R> (*)[CFP]>(conv_smem);
@@ -213,7 +213,7 @@ k_conv_fft(int nl, const R* __restrict__ pre, const cx<R>* __restrict__ khat_tt,
         }
     }
     for (int pass = 0; pass < 2; ++pass) {
-        const cx<R>* __restrict__ kh = pass == 0 ? khat_tt + (size_t)task * (CFH + 1) * CF
+        const cx<R>* __restrict__ kh = pass == 0 ? khat_tt + (size_t)(task / tdiv) * (CFH + 1) * CF
                                                      : khat_muse + (size_t)l * (CFH + 1) * CF;
         // the thread's kernel-spectrum values, fetched now so that the row transforms hide the
         // latency (slot 0 also carries the Nyquist column)
@@ -1269,17 +1269,17 @@ void launch_moffat_kernels(hipStream_t s, int nker, const double* d_gamma, const
 }
 
 void launch_conv(hipStream_t s, int ntask, int nl, const void* d_pre, const void* d_ktt,
-                 const void* d_kmuse, double* d_fin, bool f64) {
+                 const void* d_kmuse, double* d_fin, bool f64, int tdiv) {
     dim3 grid(nl, ntask);
     constexpr int PH = NS + KS - 1, PW = 84;
     if (f64) {
         const size_t sm = (size_t)(PH * PW) * sizeof(double);
-        hipLaunchKernelGGL(k_conv<double>, grid, dim3(256), sm, s, nl, (const double*)d_pre,
+        hipLaunchKernelGGL(k_conv<double>, grid, dim3(256), sm, s, nl, tdiv, (const double*)d_pre,
                            (const double*)d_ktt,
                            (const double*)d_kmuse, d_fin);
     } else {
         const size_t sm = (size_t)(PH * PW) * sizeof(float);
-        hipLaunchKernelGGL(k_conv<float>, grid, dim3(256), sm, s, nl, (const float*)d_pre,
+        hipLaunchKernelGGL(k_conv<float>, grid, dim3(256), sm, s, nl, tdiv, (const float*)d_pre,
                            (const float*)d_ktt,
                            (const float*)d_kmuse, d_fin);
     }
@@ -1299,22 +1299,23 @@ void launch_khat(hipStream_t s, int nker, const double* d_gamma, const double* d
 }
 
 void launch_conv_fft(hipStream_t s, int ntask, int nl, const void* d_pre, const void* d_khat_tt,
-                     const void* d_khat_muse, void* d_fin, bool fin_f32, bool f64, const MfFinishArgs& finish) {
+                     const void* d_khat_muse, void* d_fin, bool fin_f32, bool f64, const MfFinishArgs& finish,
+                     int tdiv) {
     const dim3 grid(nl, ntask);
     MfFinish mf;
     mf.gsw = f64 ? nullptr : finish.gsw; mf.part = (const f4*)finish.part;
     mf.per = finish.per; mf.ngr = finish.ngr; mf.nsw = finish.nsw;
     if (f64) {          // double stamps in, double arithmetic, double stamps out
         allow_smem((k_conv_fft<double, double>), conv_smem_bytes<double>(false));
-        hipLaunchKernelGGL((k_conv_fft<double, double>), grid, dim3(256), conv_smem_bytes<double>(false), s, nl,
+        hipLaunchKernelGGL((k_conv_fft<double, double>), grid, dim3(256), conv_smem_bytes<double>(false), s, nl, tdiv,
                            (const double*)d_pre, (const cx<double>*)d_khat_tt, (const cx<double>*)d_khat_muse,
                            (double*)d_fin, mf);
     } else if (fin_f32) {
-        hipLaunchKernelGGL((k_conv_fft<float, float>), grid, dim3(256), conv_smem_bytes<float>(false), s, nl,
+        hipLaunchKernelGGL((k_conv_fft<float, float>), grid, dim3(256), conv_smem_bytes<float>(false), s, nl, tdiv,
                            (const float*)d_pre, (const cx<float>*)d_khat_tt, (const cx<float>*)d_khat_muse,
                            (float*)d_fin, mf);
     } else {
-        hipLaunchKernelGGL((k_conv_fft<float, double>), grid, dim3(256), conv_smem_bytes<float>(false), s, nl,
+        hipLaunchKernelGGL((k_conv_fft<float, double>), grid, dim3(256), conv_smem_bytes<float>(false), s, nl, tdiv,
                            (const float*)d_pre, (const cx<float>*)d_khat_tt, (const cx<float>*)d_khat_muse,
                            (double*)d_fin, mf);
     }

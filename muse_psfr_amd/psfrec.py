@@ -520,6 +520,125 @@ def compute_psf(lbda, seeing, GL, L0, npsflin=1, h=(100, 10000), three_lgs_mode=
     return res, r['psf'][0]
 
 
+def _field_columns(lbda, pos, fit, pixscale):
+    """Columns of a field fit table from fit rows (npos, nl, NFIT): rows ordered (position, wavelength);
+    dir_idx (0-based index into `pos`), x, y (arcsec), then the columns of _fit_columns (lbda first)."""
+    pos = np.asarray(pos, dtype=float)
+    lbda = np.asarray(lbda, dtype=float)
+    npos, nl = pos.shape[0], lbda.size
+    fit = np.asarray(fit).reshape(npos * nl, -1)
+    cols = OrderedDict()
+    cols['dir_idx'] = np.repeat(np.arange(npos), nl)
+    cols['x'] = np.repeat(pos[:, 0], nl)
+    cols['y'] = np.repeat(pos[:, 1], nl)
+    cols.update(_fit_columns(np.tile(lbda, npos), fit, pixscale))
+    return cols
+
+
+def _field_request(positions, npsflin):
+    """The positions of a field call: direction_perf(npsflin) as (npos, 2) when `positions` is None, else the
+    caller's, validated (any number of them: calls of at most 25 are made)."""
+    if positions is None:
+        if isinstance(npsflin, bool) or not isinstance(npsflin, (int, np.integer)) or not 1 <= npsflin <= 5:
+            raise ValueError('npsflin must be an integer between 1 and 5')
+        return np.ascontiguousarray(direction_perf(int(npsflin)).T)
+    return _lib.field_positions(positions, max_n=None)
+
+
+def _field_groups(npos):
+    """Position ranges of the library calls a field request is split into (at most 25 positions each)."""
+    m = _lib.MAX_FIELD_POSITIONS
+    return [(a, min(a + m, npos)) for a in range(0, npos, m)]
+
+
+def compute_field_psf(lbda, seeing, GL, L0, positions=None, npsflin=1, h=(100, 10000), three_lgs_mode=False,
+                      verbose=True, *, dim=1280, dimpsf=40, pixscale=0.2, precision='mixed',
+                      cutoff_masks='host', device=0):
+    """Field-resolved form of compute_psf: the PSF at every field position instead of their mean.
+
+    ``positions``: (npos, 2) array of (x, y) in arcsec (|x|, |y| <= 60, the convention of direction_perf:
+    x = dirperf[0]); None = direction_perf(npsflin).  Stamp (p, l) is what compute_psf returns for a PSD of the
+    single direction p: psf_muse, convolve_final_psf, Moffat fit -- nothing is averaged over positions.
+
+    Returns ``(table, psf)``: ``psf`` (npos, nl, dimpsf, dimpsf) float64; ``table`` npos x nl rows ordered
+    (position, wavelength) with the columns dir_idx (0-based), x, y, lbda, the fit columns of compute_psf and
+    SEEING, GL, L0 (values in the meta too)."""
+    lbda = np.atleast_1d(np.asarray(lbda, dtype=float))
+    if lbda.ndim != 1 or lbda.size < 1 or not np.all(np.isfinite(lbda)) or np.any(lbda <= 0):
+        raise ValueError('lbda must be a non-empty 1-D array of positive wavelengths (nm)')
+    try:
+        seeing, GL, L0 = float(seeing), float(GL), float(L0)
+    except (TypeError, ValueError):
+        raise ValueError('seeing, GL and L0 must be scalars') from None
+    if not (seeing > 0 and L0 > 0 and 0 <= GL <= 1):
+        raise ValueError('need seeing > 0, L0 > 0 and 0 <= GL <= 1')
+    if np.asarray(h).size != 2:
+        raise ValueError('exactly two layers are supported (psfrec.py:66)')
+    if precision not in ('mixed', 'f64'):
+        raise ValueError("precision must be 'mixed' or 'f64'")
+    pos = _field_request(positions, npsflin)
+    masks = _resolve_masks(cutoff_masks)
+    if verbose:
+        logger.info('Compute field PSF at %d positions with seeing=%.2f GL=%.2f L0=%.2f', len(pos), seeing, GL, L0)
+        if three_lgs_mode:
+            logger.info('Using three lasers mode')
+    ctx = get_context(dim, pixscale, dimpsf, precision, device)
+    nl = lbda.size
+    psf = np.empty((len(pos), nl, dimpsf, dimpsf))
+    fit = np.empty((len(pos), nl, _lib.NFIT))
+    try:
+        for a, b in _field_groups(len(pos)):
+            r = ctx.reconstruct_field(lbda, [seeing], [GL], [L0], [1 if three_lgs_mode else 0], h, pos[a:b],
+                                      masks=masks, want_sum=False)
+            psf[a:b] = r['psf'][0]
+            fit[a:b] = r['fit'][0]
+    except MpsfrError as e:
+        if e.code == E_GRID:
+            raise ValueError(str(e)) from None
+        raise
+    cols = _field_columns(lbda, pos, fit, pixscale)
+    n = len(pos) * nl
+    cols['SEEING'] = np.full(n, seeing)
+    cols['GL'] = np.full(n, GL)
+    cols['L0'] = np.full(n, L0)
+    return _make_table(cols, {'SEEING': seeing, 'GL': GL, 'L0': L0}), psf
+
+
+def _field_sum(lbda, stats, three, pos, h, dim, dimpsf, pixscale, precision, cutoff_masks, devs):
+    """Sum over the rows of the field stamps (npos, nl, dimpsf, dimpsf): the rows in contiguous balanced shards over
+    `devs` (as mpsfr_reconstruct_multi deals them), the positions in groups of at most 25, every (shard, group) an
+    asynchronous sums-only call on its context; the shards' sums are added in device order."""
+    ntask = len(stats)
+    masks = _resolve_masks(cutoff_masks)
+    nctx = len(devs) if ntask >= len(devs) else 1
+    bounds = [0]
+    for k in range(nctx):
+        bounds.append(bounds[-1] + ntask // nctx + (1 if k < ntask % nctx else 0))
+    replica = [devs[:i].count(d) for i, d in enumerate(devs)]
+    ctxs = [get_context(dim, pixscale, dimpsf, precision, d, r) for d, r in zip(devs[:nctx], replica[:nctx])]
+    see, gl, l0 = (np.ascontiguousarray(stats[:, k], dtype=float) for k in range(3))
+    t3 = np.asarray(three).astype(np.uint8)
+    pend = []
+    try:
+        for k, ctx in enumerate(ctxs):
+            a, b = bounds[k], bounds[k + 1]
+            pend.append([ctx.reconstruct_field_async(lbda, see[a:b], gl[a:b], l0[a:b], t3[a:b], h, pos[p:q],
+                                                     masks=masks, want_psf=False, want_fit=False)
+                         for p, q in _field_groups(len(pos))])
+        total = np.empty((len(pos), lbda.size, dimpsf, dimpsf))
+        for k, parts in enumerate(pend):
+            for (p, q), part in zip(_field_groups(len(pos)), parts):
+                s = part.wait()['psf_sum']
+                total[p:q] = s if k == 0 else total[p:q] + s
+    except BaseException as e:
+        for ctx in ctxs:
+            ctx.abandon()
+        if isinstance(e, MpsfrError) and e.code == E_GRID:
+            raise ValueError(str(e)) from None
+        raise
+    return total
+
+
 def _table_hdu(cols, meta, name):
     fits, ATable = _astropy()
     if fits is not None:
@@ -537,7 +656,8 @@ def _table_hdu(cols, meta, name):
 def compute_psf_from_sparta(filename, extname='SPARTA_ATM_DATA', npsflin=1, lmin=490, lmax=930,
                             nl=35, lbda=None, h=(100, 10000), n_jobs=-1, plot=False,
                             mean_of_lgs=True, verbose=True, *, dim=1280, dimpsf=40, pixscale=0.2,
-                            precision='mixed', cutoff_masks='host', device=None, devices=None):
+                            precision='mixed', cutoff_masks='host', device=None, devices=None,
+                            field_positions=None):
     """Reconstruct a PSF from SPARTA data (psfrec.py:981-1120).
 
     ``filename`` is a FITS path or an already opened HDUList.  Returns an HDUList with
@@ -548,7 +668,20 @@ def compute_psf_from_sparta(filename, extname='SPARTA_ATM_DATA', npsflin=1, lmin
     has at least FANOUT_MIN_TASKS_PER_DEVICE tasks per device (``n_jobs`` = 1 keeps one device,
     ``n_jobs`` > 1 caps their number; a rank of a one-process-per-GPU launch keeps its own);
     ``device=k`` names the one device to use, ``devices=[...]`` several.  The per-row results do not
-    depend on the split."""
+    depend on the split.
+
+    ``field_positions``: None (the output above), ``'grid'`` (direction_perf(npsflin)) or an (n, 2) array of
+    (x, y) in arcsec: then two HDUs follow PSF_MEAN -- PSF_FIELD, the (npos, nl, dimpsf, dimpsf) mean over the
+    rows of the stamps at each position (compute_field_psf), and FIT_FIELD, the Moffat fit of each of them with
+    dir_idx, x, y and lbda columns (meta: the median SEEING, GL, L0, like FIT_MEAN)."""
+    if field_positions is None:
+        fpos = None
+    elif isinstance(field_positions, str):
+        if field_positions != 'grid':
+            raise ValueError("field_positions must be None, 'grid' or an (n, 2) array of (x, y) in arcsec")
+        fpos = _field_request(None, npsflin)
+    else:
+        fpos = _field_request(field_positions, npsflin)
     fits, _ = _astropy()
     io_mod = fits if fits is not None else _minifits
     opened = False
@@ -658,6 +791,19 @@ def compute_psf_from_sparta(filename, extname='SPARTA_ATM_DATA', npsflin=1, lmin
         out.append(fits.ImageHDU(data=psftot, name='PSF_MEAN'))
     else:
         out.append(_minifits.ImageHDU(data=psftot, name='PSF_MEAN'))
+
+    if fpos is not None:
+        # the field-resolved mean: the same rows, on the devices the batch ran on, sums only (psf_out = fit_out = NULL)
+        devs = r.get('devices', [device or 0])
+        psf_field = _field_sum(lbda, stats, three, fpos, h, dim, dimpsf, pixscale, precision, cutoff_masks,
+                               devs) / ntask
+        if fits is not None and isinstance(out, fits.HDUList):
+            out.append(fits.ImageHDU(data=psf_field, name='PSF_FIELD'))
+        else:
+            out.append(_minifits.ImageHDU(data=psf_field, name='PSF_FIELD'))
+        ffit = ctx.fit_stamps(psf_field.reshape(-1, dimpsf, dimpsf))
+        out.append(_table_hdu(_field_columns(lbda, fpos, ffit, pixscale),
+                              {'SEEING': float(seeing), 'GL': float(GL), 'L0': float(L0)}, 'FIT_FIELD'))
 
     if plot:
         import matplotlib.pyplot as plt
