@@ -217,6 +217,45 @@ int mpsfr_reconstruct_field(mpsfr_ctx* ctx, int ntask, const double* seeing, con
                             const uint8_t* mask_res, double* psf_out, double* psf_sum_out,
                             double* fit_out, int on_device);
 
+/* Multi-layer Cn2 profiles with per-layer wind.  The calls above model the reference's fixed atmosphere: two layers
+ * at h[2], one wind speed, the directions (0.628163, -0.326497) rad (simul_psd_wfm, psfrec.py:61, 66).  The model
+ * itself (dsp4muse, psfrec.py:531-613) takes any number of layers, and the residual PSD of the corrected zone is
+ * LINEAR in their weights:  PSD_AO = VK sum_k cn2_k T_k + noise,  where T_k depends only on layer k's altitude and
+ * wind, the LGS geometry and the direction.  So the library builds one table T_k per layer, once per profile, and
+ * every row mixes them with its own weights on the 80 x 80 zone; nothing else of the pipeline changes.
+ *
+ * nlayer            1 .. MPSFR_MAX_LAYERS
+ * h, wind_speed,    [nlayer] altitudes [m] in [0, 50000], wind speeds [m/s] in [0, 100], wind directions [rad]
+ *   wind_dir        (the reference's Cn2 heights, vent and arg_v); all finite
+ * cn2               [ntask][nlayer] weights, finite and >= 0, each row with a positive sum; each row is normalised
+ *                   to sum 1 (psfrec.py:57-58)
+ * gl                [ntask] only sets the tip-tilt kernel of convolve_final_psf (psfrec.py:881-883)
+ * npos = 0          the npsflin (1..5) directions, averaged: outputs as for mpsfr_reconstruct
+ * npos >= 1         field positions pos_arcsec [npos][2] (rules of mpsfr_reconstruct_field), npsflin must be 0:
+ *                   outputs as for mpsfr_reconstruct_field
+ * Every other argument, on_device 0 / 1 / 2 included, means what it means for mpsfr_reconstruct.  A bad profile,
+ * weight or npsflin / npos combination returns MPSFR_E_INVALID before anything is queued and touches nothing.
+ * The profile h = (100, 10000), wind_speed = (ws, ws), wind_dir = (0.628163, -0.326497), cn2 = [gl, 1 - gl] per row
+ * is mpsfr_reconstruct / mpsfr_reconstruct_field with h = (100, 10000) and wind_speed = ws, bit for bit.
+ * A layer whose weight is 0 in every row is left out (the result is that of the profile without it, bit for bit).
+ * The AO tables are cached on the whole profile (layers, altitudes, winds), the directions and the masks.  After a
+ * profile call mpsfr_debug_fetch("ao_tables") is [2 geometries][ndir][max(nlayer, 2) + 1][80][80]: the layer
+ * tables, then the noise (a single layer has a second table of zeros).
+ *
+ * mpsfr_simul_psd_profile is mpsfr_simul_psd for a profile: psd_out [ndir][dim][dim] in the units and layout of
+ * mpsfr_simul_psd, ndir = npsflin^2 (npos = 0) or npos (the PSD at each position, npsflin = 0).  cn2 [nlayer]. */
+#define MPSFR_MAX_LAYERS 8
+int mpsfr_reconstruct_profile(mpsfr_ctx* ctx, int ntask, const double* seeing, const double* gl,
+                              const double* l0, const uint8_t* three_lgs,
+                              int nlayer, const double* h, const double* wind_speed, const double* wind_dir,
+                              const double* cn2, int npsflin, int npos, const double* pos_arcsec,
+                              int nl, const double* lbda_nm, const uint8_t* mask_rec, const uint8_t* mask_res,
+                              double* psf_out, double* psf_sum_out, double* fit_out, int on_device);
+int mpsfr_simul_psd_profile(mpsfr_ctx* ctx, double seeing, double l0, int three_lgs,
+                            int nlayer, const double* h, const double* wind_speed, const double* wind_dir,
+                            const double* cn2, int npsflin, int npos, const double* pos_arcsec,
+                            const uint8_t* mask_rec, const uint8_t* mask_res, double* psd_out);
+
 /* The same over several devices: the reference's  Parallel(n_jobs=...)  fans the rows out over
  * worker processes (psfrec.py:1082-1083); here the rows go in contiguous, balanced shards (the
  * first ntask % nctx contexts take one row more) to `nctx` contexts -- normally one per device,
@@ -348,7 +387,8 @@ int mpsfr_host_time(mpsfr_ctx* ctx, double* seconds, long* calls);
 
 /* Copy an intermediate of the most recent mpsfr_reconstruct pipeline pass (last chunk) to the
  * host as float64 (parity tests, tests/test_gpu_parity.py).  `what`:
- *   "ao_tables"  [2 geometries][ndir][3 (T0,T1,noise)][80][80]   (psfrec.py:531-613)
+ *   "ao_tables"  [2 geometries][ndir][3 (T0,T1,noise)][80][80]   (psfrec.py:531-613); after a profile call
+ *                [2][ndir][max(nlayer, 2) + 1 (layer tables, noise)][80][80] (mpsfr_reconstruct_profile)
  *   "tel"        [dim/2+1][dim]  telescope OTF, transposed half plane (psfrec.py:784-790)
  *   "dphi0"      [chunk tasks][ndir][dim/2+1][dim] structure function / lambda-factor,
  *                transposed half plane (psfrec.py:717-722)

@@ -68,6 +68,12 @@ def load():
     lib.mpsfr_reconstruct_field.argtypes = [p, C.c_int, dp, dp, dp, u8p, dp, C.c_double, C.c_int, dp,
                                             C.c_int, dp, u8p, u8p, p, p, p, C.c_int]
     lib.mpsfr_reconstruct_field.restype = C.c_int
+    lib.mpsfr_reconstruct_profile.argtypes = [p, C.c_int, dp, dp, dp, u8p, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int,
+                                              dp, C.c_int, dp, u8p, u8p, p, p, p, C.c_int]
+    lib.mpsfr_reconstruct_profile.restype = C.c_int
+    lib.mpsfr_simul_psd_profile.argtypes = [p, C.c_double, C.c_double, C.c_int, C.c_int, dp, dp, dp, dp, C.c_int,
+                                            C.c_int, dp, u8p, u8p, dp]
+    lib.mpsfr_simul_psd_profile.restype = C.c_int
     lib.mpsfr_reconstruct_multi.argtypes = [C.POINTER(p), C.c_int, C.c_int, dp, dp, dp, u8p, dp, C.c_double,
                                             C.c_int, C.c_int, dp, u8p, u8p, p, p, p]
     lib.mpsfr_reconstruct_multi.restype = C.c_int
@@ -124,7 +130,7 @@ def load():
 
 
 EXPORTS = ['mpsfr_create', 'mpsfr_destroy', 'mpsfr_last_error', 'mpsfr_set_option',
-           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
+           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
            'mpsfr_psd_to_psf',
            'mpsfr_convolve_stamps', 'mpsfr_fit_rows', 'mpsfr_sync', 'mpsfr_last_ticket', 'mpsfr_wait', 'mpsfr_abandon',
            'mpsfr_stream', 'mpsfr_stream_wait', 'mpsfr_wait_event',
@@ -165,6 +171,55 @@ def field_positions(positions, max_n=MAX_FIELD_POSITIONS):
     if np.any(np.abs(pos) > MAX_FIELD_ARCSEC):
         raise ValueError('positions must satisfy |x|, |y| <= %g arcsec' % MAX_FIELD_ARCSEC)
     return np.ascontiguousarray(pos)
+
+
+MAX_LAYERS = 8               # MPSFR_MAX_LAYERS
+MAX_LAYER_HEIGHT = 50000.0   # m
+MAX_WIND_SPEED = 100.0       # m/s
+REF_WIND_DIR = (0.628163, -0.326497)   # the reference's two wind directions [rad] (psfrec.py:61)
+
+
+def profile_layers(h, wind_speed, wind_dir):
+    """Validated float64 arrays (h, wind_speed, wind_dir) of a Cn2 profile: 1..MAX_LAYERS layers, altitudes in
+    [0, MAX_LAYER_HEIGHT] m, speeds in [0, MAX_WIND_SPEED] m/s (a scalar speed applies to every layer), directions
+    in radians, all finite.  Raises ValueError otherwise -- the refusals of mpsfr_reconstruct_profile."""
+    try:
+        hh = np.array(h, dtype=np.float64).reshape(-1)
+        ws = np.array(wind_speed, dtype=np.float64)
+        wd = np.array(wind_dir, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError('h, wind_speed and wind_dir must be numeric') from None
+    n = hh.size
+    if not 1 <= n <= MAX_LAYERS:
+        raise ValueError('a profile has 1 to %d layers, got %d' % (MAX_LAYERS, n))
+    ws = np.full(n, float(ws)) if ws.ndim == 0 else ws.reshape(-1)
+    if ws.size != n or wd.size != n:
+        raise ValueError('h, wind_speed and wind_dir need one value per layer (%d)' % n)
+    if not (np.all(np.isfinite(hh)) and np.all(np.isfinite(ws)) and np.all(np.isfinite(wd))):
+        raise ValueError('altitudes and winds must be finite')
+    if np.any(hh < 0) or np.any(hh > MAX_LAYER_HEIGHT):
+        raise ValueError('layer altitudes must lie in [0, %g] m' % MAX_LAYER_HEIGHT)
+    if np.any(ws < 0) or np.any(ws > MAX_WIND_SPEED):
+        raise ValueError('wind speeds must lie in [0, %g] m/s' % MAX_WIND_SPEED)
+    return (np.ascontiguousarray(hh), np.ascontiguousarray(ws), np.ascontiguousarray(wd))
+
+
+def profile_weights(cn2, nrow, nlayer):
+    """Validated (nrow, nlayer) float64 weights: one row (1-D) applies to every row.  Refuses negative or
+    non-finite weights and rows that sum to 0 (ValueError)."""
+    try:
+        w = np.array(cn2, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('cn2 must be numeric') from None
+    if w.ndim == 1:
+        w = np.broadcast_to(w, (nrow, w.size))
+    if w.ndim != 2 or w.shape != (nrow, nlayer):
+        raise ValueError('cn2 must be (%d,) or (%d, %d), got shape %s' % (nlayer, nrow, nlayer, np.shape(cn2)))
+    if not np.all(np.isfinite(w)) or np.any(w < 0):
+        raise ValueError('Cn2 weights must be finite and >= 0')
+    if np.any(w.sum(axis=1) <= 0):
+        raise ValueError('every row of Cn2 weights needs a positive sum')
+    return np.ascontiguousarray(w)
 
 
 def device_count():
@@ -336,6 +391,90 @@ class Context:
             self._h, seeing.size, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), _dptr(hh),
             float(wind_speed), pos.shape[0], _dptr(pos), lbda.size, _dptr(lbda), _u8ptr(mrec), _u8ptr(mres),
             C.c_void_p(psf_ptr), C.c_void_p(sum_ptr), C.c_void_p(fit_ptr), 1))
+
+    def reconstruct_profile_async(self, *args, **kwargs):
+        """`reconstruct_profile` without waiting for the GPU (on_device = 2): returns a PendingResult."""
+        return self.reconstruct_profile(*args, _async=True, **kwargs)
+
+    def _profile_inputs(self, lbda, seeing, gl, l0, three_lgs, h, wind_speed, wind_dir, cn2, npsflin, positions,
+                        masks):
+        """Checked inputs of a profile call: every refusal of mpsfr_reconstruct_profile, as a ValueError, before
+        the library is touched."""
+        hh, ws, wd = profile_layers(h, wind_speed, wind_dir)
+        seeing, gl, l0, lbda, three, _, _, mrec, mres = self._inputs(lbda, seeing, gl, l0, three_lgs, (0.0, 0.0),
+                                                                     0.0, masks)
+        w = profile_weights(cn2, seeing.size, hh.size)
+        if positions is None:
+            npsflin = 1 if npsflin is None else npsflin
+            if isinstance(npsflin, bool) or not isinstance(npsflin, (int, np.integer)) or not 1 <= npsflin <= 5:
+                raise ValueError('npsflin must be an integer between 1 and 5')
+            pos = None
+        else:
+            if npsflin not in (0, None):
+                raise ValueError('a call with positions takes npsflin = 0')
+            pos = field_positions(positions)
+        return seeing, gl, l0, lbda, three, hh, ws, wd, w, pos, mrec, mres
+
+    def reconstruct_profile(self, lbda, seeing, gl, l0, cn2, h, wind_speed, wind_dir, three_lgs=None, npsflin=None,
+                            positions=None, masks=None, want_psf=True, want_sum=True, want_fit=True, _async=False):
+        """Host-buffer call with a Cn2 profile (mpsfr_reconstruct_profile): layers h / wind_speed / wind_dir
+        ([nlayer], m, m/s, rad), weights cn2 ([nrow, nlayer] or one [nlayer] row for all).  positions=None: the
+        npsflin directions averaged, shaped as `reconstruct`; else (npos, 2) arcsec with npsflin = 0, shaped as
+        `reconstruct_field`."""
+        seeing, gl, l0, lbda, three, hh, ws, wd, w, pos, mrec, mres = self._profile_inputs(
+            lbda, seeing, gl, l0, three_lgs, h, wind_speed, wind_dir, cn2, npsflin, positions, masks)
+        nt, nl, n = seeing.size, lbda.size, self.dimpsf
+        lead = (nt,) if pos is None else (nt, pos.shape[0])
+        psf = np.empty(lead + (nl, n, n)) if want_psf else None
+        psum = np.empty(lead[1:] + (nl, n, n)) if want_sum else None
+        fit = np.empty(lead + (nl, NFIT)) if want_fit else None
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        npos = 0 if pos is None else pos.shape[0]
+        _check(self.lib.mpsfr_reconstruct_profile(
+            self._h, nt, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), hh.size, _dptr(hh), _dptr(ws), _dptr(wd),
+            _dptr(w), 0 if npos else int(1 if npsflin is None else npsflin), npos, None if pos is None else _dptr(pos), nl, _dptr(lbda),
+            _u8ptr(mrec), _u8ptr(mres), vp(psf), vp(psum), vp(fit), 2 if _async else 0))
+        arrays = dict(psf=psf, psf_sum=psum, fit=fit)
+        if _async:
+            ticket = int(self.lib.mpsfr_last_ticket(self._h))
+            self._pending[ticket] = arrays
+            self._handed_over(ticket - 4)
+            return PendingResult(self, ticket, arrays)
+        return arrays
+
+    def reconstruct_profile_device(self, lbda, seeing, gl, l0, cn2, h, wind_speed, wind_dir, three_lgs, npsflin,
+                                   positions, masks, psf_ptr, sum_ptr, fit_ptr):
+        """Device-buffer profile call (asynchronous, on_device = 1): outputs are raw device pointers (int or None)
+        on this context's GPU, shaped as in reconstruct_profile."""
+        seeing, gl, l0, lbda, three, hh, ws, wd, w, pos, mrec, mres = self._profile_inputs(
+            lbda, seeing, gl, l0, three_lgs, h, wind_speed, wind_dir, cn2, npsflin, positions, masks)
+        npos = 0 if pos is None else pos.shape[0]
+        _check(self.lib.mpsfr_reconstruct_profile(
+            self._h, seeing.size, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), hh.size, _dptr(hh), _dptr(ws),
+            _dptr(wd), _dptr(w), 0 if npos else int(1 if npsflin is None else npsflin), npos, None if pos is None else _dptr(pos), lbda.size,
+            _dptr(lbda), _u8ptr(mrec), _u8ptr(mres), C.c_void_p(psf_ptr), C.c_void_p(sum_ptr), C.c_void_p(fit_ptr), 1))
+
+    def simul_psd_profile(self, seeing, l0, cn2, h, wind_speed, wind_dir, three_lgs=False, npsflin=1, positions=None,
+                          masks=None):
+        """simul_psd_wfm for a Cn2 profile (mpsfr_simul_psd_profile): (ndir, dim, dim) PSD, centred, reference
+        units; ndir = npsflin^2, or npos with positions (npsflin = 0)."""
+        hh, ws, wd = profile_layers(h, wind_speed, wind_dir)
+        w = profile_weights(cn2, 1, hh.size)
+        if positions is None:
+            pos, ndir, npos = None, int(npsflin) ** 2, 0
+        else:
+            pos = field_positions(positions)
+            ndir = npos = pos.shape[0]
+            npsflin = 0
+        mrec = mres = None
+        if masks is not None:
+            mrec = np.ascontiguousarray(masks[0]).astype(np.uint8).reshape(-1)
+            mres = np.ascontiguousarray(masks[1]).astype(np.uint8).reshape(-1)
+        out = np.empty((ndir, self.dim, self.dim))
+        _check(self.lib.mpsfr_simul_psd_profile(
+            self._h, float(seeing), float(l0), int(bool(three_lgs)), hh.size, _dptr(hh), _dptr(ws), _dptr(wd),
+            _dptr(w), int(npsflin), npos, None if pos is None else _dptr(pos), _u8ptr(mrec), _u8ptr(mres), _dptr(out)))
+        return out
 
     @staticmethod
     def _inputs(lbda, seeing, gl, l0, three_lgs, h, wind_speed, masks):

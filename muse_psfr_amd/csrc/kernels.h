@@ -42,6 +42,26 @@ struct AoGeom {
     double dir[2][25];      // [xy][dir] arcmin
 };
 
+// A Cn2 profile (mpsfr_reconstruct_profile): the layers that take the place of AoGeom::h / wind.  The tables of
+// the AO zone are linear in the layer weights, PSD_AO = VK sum_l w_l T_l + noise, so a profile call builds one
+// table per layer ([geom][dir][ntab + 1][80][80], ntab = max(n, 2): a single layer gets a second, zero table and
+// weight, so that the mixing sum always starts as the legacy two-layer one) and every row mixes them with its own
+// weights ([ntask][ntab], normalised to sum 1).
+constexpr int MAXLAYER = 8;
+struct AoLayers {
+    int n;                         // layers, 1..MAXLAYER
+    int ntab;                      // max(n, 2)
+    double h[MAXLAYER];            // altitudes [m]
+    double wind[2][MAXLAYER];      // wind[xy][layer] m/s
+};
+inline int ao_ntab(int nlayer) { return nlayer < 2 ? 2 : nlayer; }
+// the per-row weights a profile call hands to the kernels of stage A: d_w [task][ntab] (relative to the tasks the
+// launch sees); w = nullptr: a legacy call (TaskPar::cn2_0 / cn2_1, two layer tables)
+struct LayerMix {
+    const double* w = nullptr;
+    int ntab = 2;
+};
+
 // work lists of the thin-wave matrix-core kernel: one per work class (a lane of the consumer's wave keeps the
 // bounds of one list), then the queue head
 constexpr int kMfLists = 64;
@@ -69,6 +89,9 @@ enum KernelId {
 
 void launch_ao_tables(hipStream_t s, const AoGeom& g, const uint8_t* d_mask_rec,
                       const uint8_t* d_mask_res, double* d_tab);
+// profile tables [2][ndir][ly.ntab + 1][80][80] (layers beyond ly.n are zero)
+void launch_ao_tables_profile(hipStream_t s, const AoGeom& g, const AoLayers& ly, const uint8_t* d_mask_rec,
+                              const uint8_t* d_mask_res, double* d_tab);
 void launch_tel_otf(hipStream_t s, int N, const uint64_t* d_rows, int words, double pupsum,
                     void* d_tel, bool f64out);
 // d_dcpart: [ntd][psd_rowfft_groups(N)] the workgroups' shares of the PSD sum (bg[0,0], psfrec.py:721),
@@ -76,7 +99,7 @@ void launch_tel_otf(hipStream_t s, int N, const uint64_t* d_rows, int words, dou
 int psd_rowfft_groups(int N);
 void launch_psd_rowfft(hipStream_t s, int N, int ntd, int ndir, const TaskPar* d_tp,
                        const double* d_aotab, double cfit, void* d_C, const void* d_tw64,
-                       double* d_dcpart, bool f64);
+                       double* d_dcpart, bool f64, const LayerMix& mix = LayerMix());
 // d_zero: kMfSchedInts ints the kernel sets to zero (the work-list counters of launch_mf_prep), or nullptr
 void launch_colfft_dphi(hipStream_t s, int N, int ntd, const void* d_C, const double* d_dcpart,
                         double scale2, void* d_D0t, bool f64out, const void* d_tw64,
@@ -91,7 +114,7 @@ void launch_dmin(hipStream_t s, int N, int ntd, const void* d_D0t, float* d_dlin
 // reference's units: `unit` = (lambda_ref 1000 / 2 pi)^2), and the structure function of an arbitrary
 // PSD image: d_Cm [ndir][N][N/2+1] complex workspace, scale = 2 / L^2 for a PSD in the reference's units.
 void launch_psd_image(hipStream_t s, int N, int ndir, const TaskPar& p, const double* d_aotab, double cfit,
-                      double unit, double* d_psd);
+                      double unit, double* d_psd, const LayerMix& mix = LayerMix());
 void launch_dphi_from_psd(hipStream_t s, int N, int ndir, const double* d_psd, void* d_Cm, double scale,
                           void* d_D0t, bool f64out, const void* d_tw64);
 // psd_to_psf (psd_to_psf.hip), fp64, M = dimnum (a planned length), d_twm: exp(-2 pi i m / M).
@@ -149,7 +172,7 @@ struct PatchExtras {
 };
 void launch_patch(hipStream_t s, int N, int ntd, int ndir, const TaskPar* d_tp, const double* d_aotab,
                   double cfit, const void* d_twk, double* d_P, void* d_T, double* d_sp, bool f64,
-                  const PatchExtras& x = PatchExtras());
+                  const PatchExtras& x = PatchExtras(), const LayerMix& mix = LayerMix());
 void launch_dphi_series(hipStream_t s, int N, int ntd, int ndir, const TaskPar* d_tp, const void* d_T,
                         const double* d_sp, const void* d_coef, const void* d_twk, double scale2,
                         void* d_D0t, float* d_dlin, bool f64out, int* d_zero, int ncu,

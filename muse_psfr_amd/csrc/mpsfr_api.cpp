@@ -229,6 +229,7 @@ struct mpsfr_ctx {
     const void* cache_ao_ptr = nullptr;
     // bookkeeping for debug_fetch
     int last_ndir = 0, last_nl = 0, last_chunk_tasks = 0, last_lane = 0;
+    int last_ntab = 2;                   // layer tables per direction of the current AO tables (2: a legacy call)
     int last_gpp = 1;                    // stamp groups per task of the last call: npos of a field call, else 1
     bool last_mf = false, last_pruned = false, last_mf2 = false;
     float last_thr_blk = 0.f;
@@ -812,6 +813,10 @@ struct StageIO {
     // npsflin grid, and stage B keeps them apart -- every (task, position) pair is a one-direction task of its own
     int npos = 0;
     const double* pos = nullptr;
+    // mpsfr_reconstruct_profile / mpsfr_simul_psd_profile: the layers of the profile (they replace h, the wind speed
+    // and the fixed wind directions) and the rows' weights cn2 [ntask][layers->n] (each row normalised here)
+    const AoLayers* layers = nullptr;
+    const double* cn2 = nullptr;
 };
 
 static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const double* gl,
@@ -876,6 +881,128 @@ int mpsfr_reconstruct_field(mpsfr_ctx* c, int ntask, const double* seeing, const
                         psf_out, psf_sum_out, fit_out, on_device, io);
 }
 
+static_assert(MAXLAYER == MPSFR_MAX_LAYERS, "AoLayers holds MPSFR_MAX_LAYERS layers");
+
+// The checks of a profile call, before anything is queued: the layers (1..MAXLAYER, finite, 0 <= h <= 50 km,
+// 0 <= speed <= 100 m/s) and the rows' weights (finite, >= 0, a positive sum).  Fills `ly` (winds psfrec.py:594) and
+// `w` [ntask][ly.n] with the layers that carry weight in some row: a layer of weight 0 in every row contributes
+// nothing, and leaving it out keeps the tables, their cache key and the order of the mixing sum those of the
+// profile without it (bit for bit).
+static int profile_layers(int ntask, int nlayer, const double* h, const double* wind_speed, const double* wind_dir,
+                          const double* cn2, AoLayers& ly, std::vector<double>& w) {
+    if (nlayer < 1 || nlayer > MPSFR_MAX_LAYERS) return fail(MPSFR_E_INVALID, "nlayer=%d out of range 1..%d", nlayer, MPSFR_MAX_LAYERS);
+    if (!h || !wind_speed || !wind_dir || !cn2) return fail(MPSFR_E_INVALID, "NULL profile array");
+    memset(&ly, 0, sizeof ly);
+    ly.n = nlayer;
+    ly.ntab = ao_ntab(nlayer);
+    for (int l = 0; l < nlayer; ++l) {
+        if (!std::isfinite(h[l]) || !std::isfinite(wind_speed[l]) || !std::isfinite(wind_dir[l]))
+            return fail(MPSFR_E_INVALID, "layer %d: non-finite altitude or wind", l);
+        if (h[l] < 0.0 || h[l] > 50000.0) return fail(MPSFR_E_INVALID, "layer %d: h=%g outside [0, 50000] m", l, h[l]);
+        if (wind_speed[l] < 0.0 || wind_speed[l] > 100.0)
+            return fail(MPSFR_E_INVALID, "layer %d: wind speed %g outside [0, 100] m/s", l, wind_speed[l]);
+        ly.h[l] = h[l];
+        ly.wind[0][l] = wind_speed[l] * std::cos(wind_dir[l]);
+        ly.wind[1][l] = wind_speed[l] * std::sin(wind_dir[l]);
+    }
+    for (int t = 0; t < ntask; ++t) {
+        double sum = 0.0;
+        for (int l = 0; l < nlayer; ++l) {
+            const double w = cn2[(size_t)t * nlayer + l];
+            if (!std::isfinite(w) || w < 0.0) return fail(MPSFR_E_INVALID, "row %d: weight %d must be finite and >= 0", t, l);
+            sum += w;
+        }
+        if (!(sum > 0.0) || !std::isfinite(sum)) return fail(MPSFR_E_INVALID, "row %d: the weights sum to %g", t, sum);
+    }
+    int keep[MAXLAYER], nk = 0;
+    for (int l = 0; l < nlayer; ++l) {
+        bool used = false;
+        for (int t = 0; t < ntask && !used; ++t) used = cn2[(size_t)t * nlayer + l] != 0.0;
+        if (used) keep[nk++] = l;
+    }
+    for (int k = 0; k < nk; ++k) {
+        ly.h[k] = ly.h[keep[k]];
+        ly.wind[0][k] = ly.wind[0][keep[k]];
+        ly.wind[1][k] = ly.wind[1][keep[k]];
+    }
+    for (int k = nk; k < MAXLAYER; ++k) ly.h[k] = ly.wind[0][k] = ly.wind[1][k] = 0.0;
+    ly.n = nk;
+    ly.ntab = ao_ntab(nk);
+    w.resize((size_t)ntask * nk);
+    for (int t = 0; t < ntask; ++t)
+        for (int k = 0; k < nk; ++k) w[(size_t)t * nk + k] = cn2[(size_t)t * nlayer + keep[k]];
+    return MPSFR_OK;
+}
+
+int mpsfr_reconstruct_profile(mpsfr_ctx* c, int ntask, const double* seeing, const double* gl,
+                              const double* l0, const uint8_t* three_lgs,
+                              int nlayer, const double* h, const double* wind_speed, const double* wind_dir,
+                              const double* cn2, int npsflin, int npos, const double* pos_arcsec,
+                              int nl, const double* lbda_nm, const uint8_t* mask_rec, const uint8_t* mask_res,
+                              double* psf_out, double* psf_sum_out, double* fit_out, int on_device) {
+    if (!c) return fail(MPSFR_E_INVALID, "ctx is NULL");
+    if (ntask < 1) return fail(MPSFR_E_INVALID, "ntask < 1");
+    AoLayers ly;
+    std::vector<double> w;
+    int rc = profile_layers(ntask, nlayer, h, wind_speed, wind_dir, cn2, ly, w);
+    if (rc) return rc;
+    StageIO io;
+    io.layers = &ly;
+    io.cn2 = w.data();
+    if (npos < 0 || npos > 25) return fail(MPSFR_E_INVALID, "npos=%d out of range 0..25", npos);
+    if (npos > 0) {
+        if (npsflin != 0) return fail(MPSFR_E_INVALID, "a field call (npos >= 1) takes npsflin = 0");
+        if (!pos_arcsec) return fail(MPSFR_E_INVALID, "pos_arcsec is NULL");
+        for (int k = 0; k < 2 * npos; ++k)
+            if (!std::isfinite(pos_arcsec[k]) || std::fabs(pos_arcsec[k]) > 60.0)
+                return fail(MPSFR_E_INVALID, "position %d: need finite |x|, |y| <= 60 arcsec", k / 2);
+        io.npos = npos;
+        io.pos = pos_arcsec;
+        npsflin = 1;
+    } else if (npsflin < 1 || npsflin > 5) {
+        return fail(MPSFR_E_INVALID, "npsflin=%d out of range 1..5", npsflin);
+    }
+    const double h2[2] = {0.0, 0.0};     // (the layers come from `io`)
+    return guarded_call(c, ntask, seeing, gl, l0, three_lgs, h2, 0.0, npsflin, nl, lbda_nm, mask_rec, mask_res,
+                        psf_out, psf_sum_out, fit_out, on_device, io);
+}
+
+int mpsfr_simul_psd_profile(mpsfr_ctx* c, double seeing, double l0, int three_lgs,
+                            int nlayer, const double* h, const double* wind_speed, const double* wind_dir,
+                            const double* cn2, int npsflin, int npos, const double* pos_arcsec,
+                            const uint8_t* mask_rec, const uint8_t* mask_res, double* psd_out) {
+    if (!c || !psd_out) return fail(MPSFR_E_INVALID, "NULL argument");
+    AoLayers ly;
+    std::vector<double> w;
+    int rc = profile_layers(1, nlayer, h, wind_speed, wind_dir, cn2, ly, w);
+    if (rc) return rc;
+    StageIO io;
+    io.layers = &ly;
+    io.cn2 = w.data();
+    io.psd_out = psd_out;
+    if (npos < 0 || npos > 25) return fail(MPSFR_E_INVALID, "npos=%d out of range 0..25", npos);
+    if (npos > 0) {
+        // (the PSD of each position: stage A's directions are the positions, as in a field call)
+        if (npsflin != 0) return fail(MPSFR_E_INVALID, "positions (npos >= 1) take npsflin = 0");
+        if (!pos_arcsec) return fail(MPSFR_E_INVALID, "pos_arcsec is NULL");
+        for (int k = 0; k < 2 * npos; ++k)
+            if (!std::isfinite(pos_arcsec[k]) || std::fabs(pos_arcsec[k]) > 60.0)
+                return fail(MPSFR_E_INVALID, "position %d: need finite |x|, |y| <= 60 arcsec", k / 2);
+        io.npos = npos;
+        io.pos = pos_arcsec;
+        npsflin = 1;
+    } else if (npsflin < 1 || npsflin > 5) {
+        return fail(MPSFR_E_INVALID, "npsflin=%d out of range 1..5", npsflin);
+    }
+    const uint8_t t3 = three_lgs ? 1 : 0;
+    const double lb = 700.0;                 // (the per-wavelength tables are not used)
+    const double h2[2] = {0.0, 0.0};
+    // (gl only sets the tip-tilt kernel, which a PSD does not use)
+    const double gl = 0.5;
+    return guarded_call(c, 1, &seeing, &gl, &l0, &t3, h2, 0.0, npsflin, 1, &lb, mask_rec, mask_res,
+                        nullptr, nullptr, nullptr, 0, io);
+}
+
 static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const double* gl,
                             const double* l0, const uint8_t* three_lgs, const double h[2],
                             double wind_speed, int npsflin, int nl, const double* lbda_nm,
@@ -888,7 +1015,7 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
         return fail(MPSFR_E_INVALID, "ntask < 1 or NULL input array");
     if (nl < 1 || nl > 4096) return fail(MPSFR_E_INVALID, "nl=%d out of range", nl);
     const bool field = io.npos > 0;
-    if (field && (staged || !io.pos)) return fail(MPSFR_E_INVALID, "field call without positions");
+    if (field && ((staged && !io.psd_out) || !io.pos)) return fail(MPSFR_E_INVALID, "field call without positions");
     if (!field && (npsflin < 1 || npsflin > 5)) return fail(MPSFR_E_INVALID, "npsflin=%d out of range 1..5", npsflin);
     if ((mask_rec == nullptr) != (mask_res == nullptr))
         return fail(MPSFR_E_INVALID, "mask_rec and mask_res must both be given or both be NULL");
@@ -914,6 +1041,23 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
                         "lbda=%.3f nm needs a %d-pixel crop, outside [%d, dim=%d] "
                         "(psfrec.py:663-683)", lbda_nm[l], lp[l].npixc, NS, N);
     }
+    // ---- a profile call: every row's weights normalised to sum 1 (psfrec.py:57-58), padded to ntab with zeros
+    const AoLayers* ly = io.layers;
+    const int ntab = ly ? ly->ntab : 2;
+    std::vector<double> wts;
+    int low = 0;                         // the lowest layer
+    if (ly) {
+        if (!io.cn2) return fail(MPSFR_E_INVALID, "profile call without weights");
+        wts.assign((size_t)ntask * ntab, 0.0);
+        for (int l = 1; l < ly->n; ++l)
+            if (ly->h[l] < ly->h[low]) low = l;
+        for (int t = 0; t < ntask; ++t) {
+            const double* r = io.cn2 + (size_t)t * ly->n;
+            double sum = 0.0;
+            for (int l = 0; l < ly->n; ++l) sum += r[l];
+            for (int l = 0; l < ly->n; ++l) wts[(size_t)t * ntab + l] = r[l] / sum;
+        }
+    }
     // ---- per-task scalars (psfrec.py:57-58, 108, 183-187) and Moffat kernel parameters
     std::vector<TaskPar> tp(ntask);
     gam.resize((size_t)ntask + nl);
@@ -930,6 +1074,10 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
         tp[t].inv_l0sq = (1.0 / l0[t]) * (1.0 / l0[t]);
         tp[t].cn2_0 = c0;
         tp[t].cn2_1 = c1;
+        if (io.layers) {    // (the kernels read the weights; cn2_1 only orders the tasks: the weight above the lowest layer)
+            tp[t].cn2_0 = wts[(size_t)t * ntab + low];
+            tp[t].cn2_1 = 1.0 - tp[t].cn2_0;
+        }
         tp[t].geom = (three_lgs && three_lgs[t]) ? 1 : 0;
         tp[t].basis = 0;
         gam[t] = tiptilt_alpha(seeing[t], gl[t], l0[t], c->pixscale);
@@ -1096,13 +1244,29 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
 
     // ---- the AO tables are cached on their inputs (geometry + cut-off masks): the masks -- 12.8 KB of the ~20 KB a
     // call used to upload -- only travel with a call that rebuilds the tables
-    if ((rc = ensure(c, c->aotab, (size_t)2 * ndir * 3 * NAO * NAO * sizeof(double)))) return rc;
-    std::vector<unsigned char> key(sizeof(AoGeom) + 1 + (mask_rec ? 2 * NAO * NAO : 0));
+    // (a profile call: the key holds the whole profile too -- layers, altitudes, winds -- behind a byte that tells
+    // it from a legacy key)
+    if ((rc = ensure(c, c->aotab, (size_t)2 * ndir * (ntab + 1) * NAO * NAO * sizeof(double)))) return rc;
+    const size_t ko = sizeof(AoGeom) + 1 + (ly ? sizeof(AoLayers) : 0);
+    std::vector<unsigned char> key(ko + 1 + (mask_rec ? 2 * NAO * NAO : 0));
     memcpy(key.data(), &g, sizeof(AoGeom));
-    key[sizeof(AoGeom)] = mask_rec ? 1 : 0;
+    key[sizeof(AoGeom)] = ly ? 1 : 0;
+    if (ly) {
+        AoLayers lk;                     // (a copy without padding garbage: the key compares bytes)
+        memset(&lk, 0, sizeof lk);
+        lk.n = ly->n;
+        lk.ntab = ly->ntab;
+        for (int l = 0; l < ly->n; ++l) {
+            lk.h[l] = ly->h[l];
+            lk.wind[0][l] = ly->wind[0][l];
+            lk.wind[1][l] = ly->wind[1][l];
+        }
+        memcpy(key.data() + sizeof(AoGeom) + 1, &lk, sizeof lk);
+    }
+    key[ko] = mask_rec ? 1 : 0;
     if (mask_rec) {
-        memcpy(key.data() + sizeof(AoGeom) + 1, mask_rec, NAO * NAO);
-        memcpy(key.data() + sizeof(AoGeom) + 1 + NAO * NAO, mask_res, NAO * NAO);
+        memcpy(key.data() + ko + 1, mask_rec, NAO * NAO);
+        memcpy(key.data() + ko + 1 + NAO * NAO, mask_res, NAO * NAO);
     }
     // (stage-level calls pass placeholder geometry or wavelengths for the stages they skip: those tables are
     // neither built nor do they displace the cached ones of the last real call)
@@ -1121,7 +1285,8 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
     // (queue-fed stage A: per chunk, its lines in the order of how much uncorrected turbulence a task carries)
     const bool want_perm = c->stage_a_queue != 0 && series;
     const size_t o_perm = al16(o_ms + (send_masks ? NAO * NAO : 0));
-    const size_t blob = al16(o_perm + (want_perm ? (size_t)ntask * ndir * sizeof(int) : 0));
+    const size_t o_w = al16(o_perm + (want_perm ? (size_t)ntask * ndir * sizeof(int) : 0));    // profile weights
+    const size_t blob = al16(o_w + wts.size() * sizeof(double));
     mpsfr_ctx::Slot& sl = c->slot[c->stage_next++ % mpsfr_ctx::NSTAGE];
     double t_blocked = 0.0;
     if (sl.staged_pending) {        // the copy that last used the pinned blob must have left it
@@ -1173,6 +1338,7 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
     memcpy(hb + o_tp, tp.data(), ntask * sizeof(TaskPar));
     memcpy(hb + o_gam, gam.data(), gam.size() * sizeof(double));
     memcpy(hb + o_alp, alp.data(), alp.size() * sizeof(double));
+    if (ly) memcpy(hb + o_w, wts.data(), wts.size() * sizeof(double));
     if (want_perm) {
         // K_DPHI_SERIES_Q deals the lines of a y in this order (indices relative to the chunk): tasks by descending
         // (L0 / r0)^(5/3) x (weight of the high layer) -- the residual a ground-layer correction leaves -- so that the
@@ -1272,7 +1438,9 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
     // are extra workgroups of its second (K_PATCH_ROWS): a call on one lane with its tables cached starts with the
     // patch itself, two launches shorter ("head_fusion" = 0: K_PARAM_COPY and K_KHAT as kernels of their own).
     const bool fuse_head = c->head_fusion && series && !staged;
-    const bool fuse_copy = fuse_head && c->copy_fusion && c->param_copy_kernel && NL == 1 && lam_cached && ao_cached;
+    // (not in a profile call: its patch kernel reads the weights from the device blob)
+    const bool fuse_copy = fuse_head && c->copy_fusion && c->param_copy_kernel && NL == 1 && lam_cached && ao_cached &&
+                           !ly;
     const bool fuse_khat = fuse_head && c->fft_conv;
     sl.seq = ++c->seq_next;
     if (zero) {
@@ -1297,6 +1465,13 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
     const TaskPar* d_tp = (const TaskPar*)(db + o_tp);
     const double* d_gam = (const double*)(db + o_gam);
     const double* d_alp = (const double*)(db + o_alp);
+    const double* d_w = ly ? (const double*)(db + o_w) : nullptr;
+    auto mix_of = [&](int t0) {
+        LayerMix m;
+        m.w = ly ? d_w + (size_t)t0 * ntab : nullptr;
+        m.ntab = ntab;
+        return m;
+    };
     const uint8_t* d_mrec = send_masks ? (const uint8_t*)(db + o_mr) : nullptr;     // (read by K_AO_TABLES only)
     const uint8_t* d_mres = send_masks ? (const uint8_t*)(db + o_ms) : nullptr;
 
@@ -1306,8 +1481,10 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
                 HIPCHK(hipStreamWaitEvent(s0, lane_end(c, c->lane[k]), 0));
         if (!ao_cached) {
             ProfScope ps(c, K_AO_TABLES, s0);
-            launch_ao_tables(s0, g, d_mrec, d_mres, (double*)c->aotab.p);
+            if (ly) launch_ao_tables_profile(s0, g, *ly, d_mrec, d_mres, (double*)c->aotab.p);
+            else launch_ao_tables(s0, g, d_mrec, d_mres, (double*)c->aotab.p);
             c->cache_geom.swap(key);
+            c->last_ntab = ntab;
             c->cache_ao_ptr = c->aotab.p;
         }
         if (!lam_cached) {
@@ -1464,7 +1641,8 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
         const size_t n = (size_t)ndir * N * N;
         DevBuf img;
         if ((rc = ensure(c, img, n * sizeof(double)))) return rc;
-        launch_psd_image(s0, N, ndir, tp[0], (const double*)c->aotab.p, cfit, dphi_scale2() * 128.0, (double*)img.p);
+        launch_psd_image(s0, N, ndir, tp[0], (const double*)c->aotab.p, cfit, dphi_scale2() * 128.0, (double*)img.p,
+                         mix_of(0));
         const hipError_t e1 = hipMemcpyAsync(io.psd_out, img.p, n * sizeof(double), hipMemcpyDeviceToHost, s0);
         const hipError_t e2 = hipStreamSynchronize(s0);
         release(img);
@@ -1544,7 +1722,7 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
                     px.khat_f64 = c->f64;
                 }
                 launch_patch(ls, N, ntd, ndir, d_tp + t0, (const double*)c->aotab.p, cfit, c->stwk.p,
-                             (double*)ln.pP.p, ln.pT.p, (double*)ln.psp.p, c->f64, px);
+                             (double*)ln.pP.p, ln.pT.p, (double*)ln.psp.p, c->f64, px, mix_of(t0));
                 // (a call that is not lean frees its blob through an event: behind the kernels that read it)
                 if (fuse_copy && t0 == 0 && !zero && !lean) HIPCHK(hipEventRecord(sl.staged, ls));
             }
@@ -1568,7 +1746,7 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
             {
                 ProfScope ps(c, K_PSD_ROWFFT, ls);
                 launch_psd_rowfft(ls, N, ntd, ndir, d_tp + t0, (const double*)c->aotab.p, cfit, ln.C.p,
-                                  c->tw64.p, (double*)ln.s00.p, c->f64);
+                                  c->tw64.p, (double*)ln.s00.p, c->f64, mix_of(t0));
             }
             ProfScope ps(c, K_COLFFT_DPHI, ls);
             launch_colfft_dphi(ls, N, ntd, ln.C.p, (const double*)ln.s00.p, scale2, ln.D0t.p,
@@ -2074,7 +2252,7 @@ long mpsfr_debug_fetch(mpsfr_ctx* c, const char* what, double* out, size_t capac
     const void* src = nullptr;
     bool is_real_r = false;   // stored in the context's R type
     if (!strcmp(what, "ao_tables")) {
-        n = (size_t)2 * c->last_ndir * 3 * NAO * NAO;
+        n = (size_t)2 * c->last_ndir * (c->last_ntab + 1) * NAO * NAO;
         src = c->aotab.p;
     } else if (!strcmp(what, "tel")) {
         n = (size_t)H1 * N;

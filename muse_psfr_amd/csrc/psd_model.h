@@ -58,5 +58,30 @@ __device__ __forceinline__ double psd_with_ao(double fit, int su, int sv, const 
     return fit;
 }
 
+// the trailing (w, ntab) arguments of a kernel's profile instantiation
+__device__ __forceinline__ void mix_args(const double*& w, int& ntab, const double* w_, int ntab_) {
+    w = w_;
+    ntab = ntab_;
+}
+
+// The same for a profile call: the row's weights w[ntab] mix the layer tables tb[0..ntab) and the noise table
+// tb[ntab].  The first two terms are the legacy expression, so a two-layer profile gives the legacy bits.
+template <int NEWTON>
+__device__ __forceinline__ double psd_with_ao_mix(double fit, int su, int sv, const TaskPar& p,
+                                                  const double* __restrict__ tb, const double* __restrict__ w,
+                                                  int ntab) {
+    if (su >= -NAO / 2 && su < NAO / 2 && sv >= -NAO / 2 && sv < NAO / 2) {
+        const int ia = su < 0 ? su + NAO : su, ib = sv < 0 ? sv + NAO : sv;
+        const double g2 = (double)(su * su + sv * sv) * (1.0 / 256.0);
+        const double vk = 0.0229 * p.r0m53 * pow_m11_6<NEWTON>(g2 + p.inv_l0sq);   // :569-571
+        const int o = ia * NAO + ib;
+        double s = w[0] * tb[o] + w[1] * tb[NAO * NAO + o];
+        for (int l = 2; l < ntab; ++l) s += w[l] * tb[l * NAO * NAO + o];
+        const double ao = vk * s + tb[ntab * NAO * NAO + o];
+        fit = fmax(fit, ao);                                        // :149
+    }
+    return fit;
+}
+
 }  // namespace
 }  // namespace mpsfr

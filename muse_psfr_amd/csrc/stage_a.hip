@@ -15,7 +15,74 @@ namespace {
 // calc_mat_rec_glao_finale :218-364 (LSE, one DM layer) and calc_dsp_res_glao_finale :367-528).
 // tab[geom][dir][{T0,T1,noise}][a][b] with (a, b) = (fy index, fx index), i.e. already
 // transposed as psfrec.py:613 does, so that  PSD_AO[a][b] = VK * (cn2_0 T0 + cn2_1 T1) + noise.
+// A profile call (K_AO_TABLES_PROFILE) has one table per layer: PSD_AO = VK * sum_l w_l T_l + noise.
 // ------------------------------------------------------------------------------------------
+// |residual phase|^2 of one layer (h [m], wind (wx, wy) m/s) at frequency (gx, gy) in direction bf
+// (psfrec.py:440-489); lgs: the reconstruction term is present (haveW && !ms)
+__device__ __forceinline__ double ao_layer_T(const AoGeom& g, int geom, int n, double h, double wx, double wy,
+                                             double gx, double gy, double bf, double theta_dm, bool lgs) {
+    const double ph = 2.0 * kPi * (h * kArcminH * bf - (wx * kDeltaT * gx + wy * kDeltaT * gy));
+    double pr, pi_;
+    sincos(ph, &pi_, &pr);                                                          // :454-457
+    if (lgs) {
+        // sum_g (PbetaDM W_g) Mv[l,g] = (www/n) sum_g exp(i (theta_dm + psi_lg - phi_g))
+        const double www = sinc_pi(wx * kTi * gx + wy * kTi * gy);                  // :442
+        double sr = 0.0, si = 0.0;
+        for (int q = 0; q < n; ++q) {
+            const double pf = gx * g.poslgs[geom][0][q] + gy * g.poslgs[geom][1][q];
+            const double phi = 2.0 * kPi * pf * 1.0 * kArcminH;                     // :279-281
+            const double psi = 2.0 * kPi * pf * h * kArcminH;                       // :440-443
+            double s_, c_;
+            sincos(theta_dm + psi - phi, &s_, &c_);
+            sr += c_;
+            si += s_;
+        }
+        pr -= www / n * sr;
+        pi_ -= www / n * si;
+    }
+    return pr * pr + pi_ * pi_;                                                     // :489
+}
+
+// What the layers of a table pixel share: frequency, masks, |wfs|, direction
+struct AoPix {
+    int pix, i, j, d, geom, n;
+    double gx, gy, bf, theta_dm, wamp;
+    bool haveW, ms;
+};
+
+__device__ __forceinline__ bool ao_pix(const AoGeom& g, const uint8_t* __restrict__ mrec,
+                                       const uint8_t* __restrict__ mres, AoPix& a) {
+    a.pix = blockIdx.x * 256 + threadIdx.x;
+    if (a.pix >= NAO * NAO) return false;
+    a.d = blockIdx.y;
+    a.geom = blockIdx.z;
+    a.i = a.pix / NAO;
+    a.j = a.pix % NAO;                                   // i <-> fx, j <-> fy (reference layout)
+    const int ki = a.i < NAO / 2 ? a.i : a.i - NAO, kj = a.j < NAO / 2 ? a.j : a.j - NAO;
+    const double fx = ki / 16.0, fy = kj / 16.0;         // fftfreq(80, 0.2), psfrec.py:548
+    const double f = sqrt(fx * fx + fy * fy);
+    // psfrec.py:552-554 + :241-242: arg = arctan(fy/fx) folds the grid onto fx >= 0
+    a.gx = fabs(fx);
+    a.gy = ki < 0 ? -fy : fy;
+    bool mr;
+    if (mrec != nullptr) {
+        mr = mrec[a.pix] != 0;
+        a.ms = mres[a.pix] != 0;
+    } else {   // exact rule on the integer grid: fc = 1.5 = 24/16 (psfrec.py:254-257, 432-435)
+        const int ai = ki < 0 ? -ki : ki, aj = kj < 0 ? -kj : kj;
+        mr = ai >= 24 || aj >= 24;
+        a.ms = ai > 24 || aj > 24;
+    }
+    const double pitch = 8.0 / 24.0;
+    a.wamp = 2.0 * kPi * f * sinc_pi(pitch * a.gx) * sinc_pi(pitch * a.gy);  // |wfs|, :252
+    a.n = g.nlgs[a.geom];
+    a.haveW = !mr && a.wamp != 0.0 && a.pix != 0;       // psfrec.py:339, 351-352
+    const double b0 = g.dir[0][a.d], b1 = g.dir[1][a.d];
+    a.bf = b0 * a.gx + b1 * a.gy;
+    a.theta_dm = 2.0 * kPi * 1.0 * kArcminH * a.bf;      // :464
+    return true;
+}
+
 __global__ void __launch_bounds__(256) k_ao_tables(AoGeom g, const uint8_t* __restrict__ mrec,
                                                    const uint8_t* __restrict__ mres,
                                                    double* __restrict__ tab) {
@@ -75,6 +142,26 @@ __global__ void __launch_bounds__(256) k_ao_tables(AoGeom g, const uint8_t* __re
     o[0] = T[0];
     o[NAO * NAO] = T[1];
     o[2 * NAO * NAO] = noise;
+}
+
+// K_AO_TABLES of a profile call: tab[geom][dir][ly.ntab + 1][a][b], one table per layer, then the noise.  The
+// arithmetic is k_ao_tables' (restated in ao_pix / ao_layer_T so that the legacy kernel keeps its code); a profile of
+// the legacy two layers gives its tables bit for bit (tests/test_gpu_profile.py).
+__global__ void __launch_bounds__(256) k_ao_tables_profile(AoGeom g, AoLayers ly, const uint8_t* __restrict__ mrec,
+                                                           const uint8_t* __restrict__ mres,
+                                                           double* __restrict__ tab) {
+    AoPix a;
+    if (!ao_pix(g, mrec, mres, a)) return;
+    double* o = tab + ((size_t)(a.geom * g.ndir + a.d) * (ly.ntab + 1)) * (NAO * NAO) + a.j * NAO + a.i;
+    for (int l = 0; l < ly.ntab; ++l) {
+        double t = 0.0;
+        if (l < ly.n && a.pix != 0)                                                 // :490
+            t = ao_layer_T(g, a.geom, a.n, ly.h[l], ly.wind[0][l], ly.wind[1][l], a.gx, a.gy, a.bf, a.theta_dm,
+                           a.haveW && !a.ms);
+        o[(size_t)l * NAO * NAO] = t;
+    }
+    const double noise = a.haveW ? 1.0 / (a.n * a.wamp * a.wamp) : 0.0;             // :515 (pix 0: :516)
+    o[(size_t)ly.ntab * NAO * NAO] = noise;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -152,11 +239,15 @@ constexpr size_t a_smem() {
 // F64: the f64 mode (two Newton steps in x^(-11/6)).  dcpart[td][workgroup]: the workgroup's share of
 // S00 = sum of the PSD = Re sum_r C[td][r][0] (bg[0,0], psfrec.py:721; compact rows with su >= 40
 // stand for two rows) -- K_COLFFT_DPHI adds the shares in a fixed order.
-template <int N, bool F64>
+// Mix: empty (a legacy call: TaskPar::cn2_0 / cn2_1 and three tables per direction -- this instantiation is the
+// kernel as it was before profiles existed) or (const double* w, int ntab): a profile call, the row's weights
+// w[task][ntab] and ntab + 1 tables per direction (psd_with_ao_mix)
+template <int N, bool F64, typename... Mix>
 __global__ void __launch_bounds__((a_threads<N, false>()))
 k_psd_rowfft(int ndir, const TaskPar* __restrict__ tp, const double* __restrict__ aotab,
              double cfit, cx<double>* __restrict__ C, const cx<double>* __restrict__ twg,
-             double* __restrict__ dcpart) {
+             double* __restrict__ dcpart, Mix... mix) {
+    constexpr bool MIX = sizeof...(Mix) > 0;
     using L = LineCfg<N>;
     constexpr int TPR = L::TPR, SLOTS = a_slots<N, false>(), THREADS = a_threads<N, false>(), NPAD = L::NPAD;
     constexpr int EPT = N / TPR, NR = psd_rows<N>();
@@ -182,7 +273,16 @@ k_psd_rowfft(int ndir, const TaskPar* __restrict__ tp, const double* __restrict_
     const bool valid = 2 * pair < NR;
     const int ca = valid ? 2 * pair : 0, cb = ca + 1;       // NR is even
     const int sua = ca - NAO / 2, sub = cb - NAO / 2;
-    const double* tb = aotab + ((size_t)(p.geom * ndir + d) * 3) * (NAO * NAO);
+    const double* tb;
+    const double* w = nullptr;
+    int ntab = 2;
+    if constexpr (MIX) {
+        mix_args(w, ntab, mix...);
+        w += (size_t)task * ntab;
+        tb = aotab + ((size_t)(p.geom * ndir + d) * (ntab + 1)) * (NAO * NAO);
+    } else {
+        tb = aotab + ((size_t)(p.geom * ndir + d) * 3) * (NAO * NAO);
+    }
     cx<double> x[EPT];
     if constexpr (TPR <= 64 && EPT % 2 == 0) {
         // The fitting term depends on the column through (sv + 1/2)^2 only: columns sv and -1-sv are
@@ -212,7 +312,11 @@ k_psd_rowfft(int ndir, const TaskPar* __restrict__ tp, const double* __restrict_
         for (int e = 0; e < EPT; ++e) {
             const int c = t + e * TPR;
             const int sv = c < N / 2 ? c : c - N;
-            x[e] = {psd_with_ao<NEWTON>(x[e].x, sua, sv, p, tb), psd_with_ao<NEWTON>(x[e].y, sub, sv, p, tb)};
+            if constexpr (MIX)
+                x[e] = {psd_with_ao_mix<NEWTON>(x[e].x, sua, sv, p, tb, w, ntab),
+                        psd_with_ao_mix<NEWTON>(x[e].y, sub, sv, p, tb, w, ntab)};
+            else
+                x[e] = {psd_with_ao<NEWTON>(x[e].x, sua, sv, p, tb), psd_with_ao<NEWTON>(x[e].y, sub, sv, p, tb)};
         }
     }
     if constexpr (!REGTW) __syncthreads();      // twiddle table
@@ -388,6 +492,19 @@ __global__ void __launch_bounds__(256) k_psd_image(int N, int ndir, TaskPar p, c
     const double* tb = aotab + ((size_t)(p.geom * ndir + d) * 3) * (NAO * NAO);
     const double fit = psd_fit_value<NEWTON>(su, sv, p, cfit);
     psd[((size_t)d * N + row) * N + col] = unit * psd_with_ao<NEWTON>(fit, su, sv, p, tb);
+}
+
+// (a profile call: the weights w[ntab] of the one task)
+template <int NEWTON>
+__global__ void __launch_bounds__(256) k_psd_image_profile(int N, int ndir, TaskPar p, const double* __restrict__ aotab,
+                                                           double cfit, double unit, double* __restrict__ psd,
+                                                           const double* __restrict__ w, int ntab) {
+    const int col = blockIdx.x * 256 + threadIdx.x, row = blockIdx.y, d = blockIdx.z;
+    if (col >= N) return;
+    const int su = row - N / 2, sv = col - N / 2;
+    const double* tb = aotab + ((size_t)(p.geom * ndir + d) * (ntab + 1)) * (NAO * NAO);
+    const double fit = psd_fit_value<NEWTON>(su, sv, p, cfit);
+    psd[((size_t)d * N + row) * N + col] = unit * psd_with_ao_mix<NEWTON>(fit, su, sv, p, tb, w, ntab);
 }
 
 template <int N>
@@ -632,6 +749,12 @@ void launch_ao_tables(hipStream_t s, const AoGeom& g, const uint8_t* d_mask_rec,
     hipLaunchKernelGGL(k_ao_tables, grid, dim3(256), 0, s, g, d_mask_rec, d_mask_res, d_tab);
 }
 
+void launch_ao_tables_profile(hipStream_t s, const AoGeom& g, const AoLayers& ly, const uint8_t* d_mask_rec,
+                              const uint8_t* d_mask_res, double* d_tab) {
+    dim3 grid((NAO * NAO + 255) / 256, g.ndir, 2);
+    hipLaunchKernelGGL(k_ao_tables_profile, grid, dim3(256), 0, s, g, ly, d_mask_rec, d_mask_res, d_tab);
+}
+
 void launch_tel_otf(hipStream_t s, int N, const uint64_t* d_rows, int words, double pupsum,
                     void* d_tel, bool f64out) {
     dim3 grid((N + 255) / 256, N / 2 + 1);
@@ -651,12 +774,24 @@ int psd_rowfft_groups(int N) {
 
 void launch_psd_rowfft(hipStream_t s, int N, int ntd, int ndir, const TaskPar* d_tp,
                        const double* d_aotab, double cfit, void* d_C, const void* d_tw64,
-                       double* d_dcpart, bool f64) {
+                       double* d_dcpart, bool f64, const LayerMix& mix) {
     DISPATCH_N(N, {
         constexpr size_t sm = a_smem<NN, false>();
         constexpr int NPAIR = psd_rows<NN>() / 2, SL = a_slots<NN, false>();
         dim3 grid((NPAIR + SL - 1) / SL, ntd);
-        if (f64) {
+        if (mix.w != nullptr) {
+            if (f64) {
+                allow_smem((k_psd_rowfft<NN, true, const double*, int>), sm);
+                hipLaunchKernelGGL((k_psd_rowfft<NN, true, const double*, int>), grid, dim3(a_threads<NN, false>()), sm, s, ndir,
+                                   d_tp, d_aotab, cfit, (cx<double>*)d_C, (const cx<double>*)d_tw64, d_dcpart,
+                                   mix.w, mix.ntab);
+            } else {
+                allow_smem((k_psd_rowfft<NN, false, const double*, int>), sm);
+                hipLaunchKernelGGL((k_psd_rowfft<NN, false, const double*, int>), grid, dim3(a_threads<NN, false>()), sm, s, ndir,
+                                   d_tp, d_aotab, cfit, (cx<double>*)d_C, (const cx<double>*)d_tw64, d_dcpart,
+                                   mix.w, mix.ntab);
+            }
+        } else if (f64) {
             allow_smem((k_psd_rowfft<NN, true>), sm);
             hipLaunchKernelGGL((k_psd_rowfft<NN, true>), grid, dim3(a_threads<NN, false>()), sm, s, ndir, d_tp,
                                d_aotab, cfit, (cx<double>*)d_C, (const cx<double>*)d_tw64, d_dcpart);
@@ -721,9 +856,13 @@ void launch_colfft_dphi(hipStream_t s, int N, int ntd, const void* d_C, const do
 
 
 void launch_psd_image(hipStream_t s, int N, int ndir, const TaskPar& p, const double* d_aotab, double cfit,
-                      double unit, double* d_psd) {
+                      double unit, double* d_psd, const LayerMix& mix) {
     const dim3 grid((N + 255) / 256, N, ndir);
-    hipLaunchKernelGGL(k_psd_image<2>, grid, dim3(256), 0, s, N, ndir, p, d_aotab, cfit, unit, d_psd);
+    if (mix.w != nullptr)
+        hipLaunchKernelGGL(k_psd_image_profile<2>, grid, dim3(256), 0, s, N, ndir, p, d_aotab, cfit, unit, d_psd,
+                           mix.w, mix.ntab);
+    else
+        hipLaunchKernelGGL(k_psd_image<2>, grid, dim3(256), 0, s, N, ndir, p, d_aotab, cfit, unit, d_psd);
 }
 
 void launch_dphi_from_psd(hipStream_t s, int N, int ndir, const double* d_psd, void* d_Cm, double scale,

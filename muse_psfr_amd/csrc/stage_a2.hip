@@ -386,10 +386,12 @@ struct ParamFlag {
     int* queue_zero;
 };
 
-template <bool F64>
+// Mix: empty (a legacy call, the kernel as it was before profiles existed) or (const double* w, int ntab): a profile
+// call, the row's weights w[task][ntab] and ntab + 1 tables per direction
+template <bool F64, typename... Mix>
 __global__ void __launch_bounds__(256) k_patch_gen(int ndir, const TaskPar* __restrict__ tp,
                                                    const double* __restrict__ aotab, double cfit,
-                                                   double* __restrict__ P, ParamCopy pc) {
+                                                   double* __restrict__ P, ParamCopy pc, Mix... mix) {
     constexpr int NEWTON = F64 ? 2 : 1;
     constexpr int TPW = sizeof(TaskPar) / 8;
     static_assert(sizeof(TaskPar) % 8 == 0, "TaskPar is read in 8-byte words");
@@ -429,6 +431,21 @@ __global__ void __launch_bounds__(256) k_patch_gen(int ndir, const TaskPar* __re
     const double g2 = (double)(su * su + sv * sv) * (1.0 / 256.0);
     const double vk = 0.0229 * p.r0m53 * pow_m11_6<NEWTON>(g2 + p.inv_l0sq);        // :569-571
     const int o = ia * NAO + ib;
+    if constexpr (sizeof...(Mix) > 0) {
+        const double* w;
+        int ntab;
+        mix_args(w, ntab, mix...);
+        w += (size_t)task * ntab;
+        for (int d = 0; d < ndir; ++d) {
+            const double* tb = aotab + ((size_t)(p.geom * ndir + d) * (ntab + 1)) * (NAO * NAO);
+            // (the first two terms are the legacy expression: a two-layer profile gives the legacy bits)
+            double sw = w[0] * tb[o] + w[1] * tb[NAO * NAO + o];
+            for (int l = 2; l < ntab; ++l) sw += w[l] * tb[l * NAO * NAO + o];
+            const double ao = vk * sw + tb[ntab * NAO * NAO + o];
+            P[((size_t)task * ndir + d) * (NAO * NAO) + pix] = fmax(fit, ao) - fit;          // :149
+        }
+        return;
+    }
     if (ndir == 1) {
         const double* tb = aotab + ((size_t)p.geom * 3) * (NAO * NAO);
         const double ao = vk * (p.cn2_0 * tb[o] + p.cn2_1 * tb[NAO * NAO + o]) + tb[2 * NAO * NAO + o];
@@ -1216,7 +1233,7 @@ void launch_series_coef(hipStream_t s, int N, const double* d_planes, void* d_co
 
 void launch_patch(hipStream_t s, int N, int ntd, int ndir, const TaskPar* d_tp, const double* d_aotab,
                   double cfit, const void* d_twk, double* d_P, void* d_T, double* d_sp, bool f64,
-                  const PatchExtras& x) {
+                  const PatchExtras& x, const LayerMix& mix) {
     const int ntask = ntd / ndir;
     const bool copy = x.blob_src != nullptr;
     const dim3 ggrid((NAO * NAO + 255) / 256, ntask + (copy ? 1 : 0));
@@ -1224,7 +1241,14 @@ void launch_patch(hipStream_t s, int N, int ntd, int ndir, const TaskPar* d_tp, 
     pc.dst = (uint4*)x.blob_dst; pc.src = (const uint4*)x.blob_src; pc.n16 = copy ? (int)(x.blob_bytes / 16) : 0;
     // (with the blob in this launch the task parameters are read where the host wrote them)
     if (copy) d_tp = x.tp_host;
-    if (f64)
+    if (mix.w != nullptr) {
+        if (f64)
+            hipLaunchKernelGGL((k_patch_gen<true, const double*, int>), ggrid, dim3(256), 0, s, ndir, d_tp, d_aotab, cfit, d_P, pc,
+                               mix.w, mix.ntab);
+        else
+            hipLaunchKernelGGL((k_patch_gen<false, const double*, int>), ggrid, dim3(256), 0, s, ndir, d_tp, d_aotab, cfit, d_P, pc,
+                               mix.w, mix.ntab);
+    } else if (f64)
         hipLaunchKernelGGL(k_patch_gen<true>, ggrid, dim3(256), 0, s, ndir, d_tp, d_aotab, cfit, d_P, pc);
     else
         hipLaunchKernelGGL(k_patch_gen<false>, ggrid, dim3(256), 0, s, ndir, d_tp, d_aotab, cfit, d_P, pc);

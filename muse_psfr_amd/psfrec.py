@@ -321,11 +321,30 @@ def fit_psf_cube(lbda, psfcube, *, pixscale=0.2, precision='mixed', device=0):
 
 
 def simul_psd_wfm(Cn2, h, seeing, L0, zenith=0., plot=False, npsflin=1, dim=1280, three_lgs_mode=False,
-                  verbose=True, *, precision='mixed', cutoff_masks='host', device=0):
+                  verbose=True, *, precision='mixed', cutoff_masks='host', device=0, wind_speed=None, wind_dir=None):
     """Residual phase PSD of the MUSE wide-field mode for each evaluation direction (psfrec.py:36-151):
     (npsflin**2, dim, dim) float64, DC at [dim/2, dim/2], in nm^2 m^2 like the reference's.  Two layers
     (`Cn2` = their weights, normalised here as psfrec.py:57-58 does); the zenith angle only rescales r0
-    (psfrec.py:108, 183-187)."""
+    (psfrec.py:108, 183-187).
+
+    With ``wind_dir`` (radians, one per layer) the atmosphere is a Cn2 profile of 1 to 8 layers: ``h`` their
+    altitudes, ``wind_speed`` their speeds (scalar or per layer; by default np.full_like(h, 12.5) as
+    psfrec.py:61 has it -- 12 m/s for integer altitudes).  ``wind_speed`` without ``wind_dir`` is refused
+    (ValueError): the two-layer call keeps the reference's winds."""
+    if wind_dir is not None:
+        if wind_speed is None:
+            wind_speed = np.full_like(np.array(h), 12.5)
+        hh, ws, wd = _lib.profile_layers(h, wind_speed, wind_dir)
+        w = _lib.profile_weights(np.ravel(np.array(Cn2, dtype=float)), 1, hh.size)
+        if plot:
+            direction_perf(npsflin, plot=True)
+        seeing_los = float(seeing) / np.cos(np.deg2rad(zenith)) ** (3 / 5)
+        ctx = get_context(dim, 0.2, 40, precision, device)
+        return ctx.simul_psd_profile(seeing_los, L0, w[0], hh, ws, wd, three_lgs_mode, npsflin=npsflin,
+                                     masks=_resolve_masks(cutoff_masks))
+    if wind_speed is not None:
+        raise ValueError('wind_speed is a profile argument: give wind_dir too (without it the reference\'s '
+                         'atmosphere applies, psfrec.py:61)')
     Cn2 = np.array(Cn2, dtype=float)
     if Cn2.size != 2 or len(h) != 2:
         raise ValueError('exactly two layers are supported (psfrec.py:66 fixes two wind directions)')
@@ -602,6 +621,86 @@ def compute_field_psf(lbda, seeing, GL, L0, positions=None, npsflin=1, h=(100, 1
     cols['GL'] = np.full(n, GL)
     cols['L0'] = np.full(n, L0)
     return _make_table(cols, {'SEEING': seeing, 'GL': GL, 'L0': L0}), psf
+
+
+def compute_profile_psf(lbda, seeing, L0, cn2, h, wind_speed=12.5, wind_dir=None, GL=None, npsflin=1, positions=None,
+                        three_lgs_mode=False, verbose=True, *, dim=1280, dimpsf=40, pixscale=0.2, precision='mixed',
+                        cutoff_masks='host', device=0):
+    """compute_psf / compute_field_psf for a Cn2 profile instead of the fixed two-layer atmosphere.
+
+    ``cn2``, ``h``, ``wind_speed``, ``wind_dir``: the layers' weights (normalised here, psfrec.py:57-58), altitudes
+    [m, 0..50000], wind speeds [m/s, 0..100; a scalar applies to every layer] and directions [rad] -- the
+    reference's Cn2, hh, vent and arg_v of dsp4muse (psfrec.py:531-613), 1 to 8 layers.  ``wind_dir`` may be
+    omitted for two layers only: the reference's directions (0.628163, -0.326497).  ``GL`` only sets the tip-tilt
+    kernel (psfrec.py:881-883); by default it is the normalised weight of the lowest layer, so cn2=[GL, 1 - GL]
+    with h=(100, 10000) is what compute_psf means by GL.
+
+    positions=None: ``(table, psf)`` as compute_psf (the npsflin directions averaged, psf (nl, dimpsf, dimpsf));
+    else (npos, 2) arcsec: as compute_field_psf (psf (npos, nl, dimpsf, dimpsf), table with dir_idx, x, y).
+    Every refusal is a ValueError, raised before any GPU context exists."""
+    lbda = np.atleast_1d(np.asarray(lbda, dtype=float))
+    if lbda.ndim != 1 or lbda.size < 1 or not np.all(np.isfinite(lbda)) or np.any(lbda <= 0):
+        raise ValueError('lbda must be a non-empty 1-D array of positive wavelengths (nm)')
+    try:
+        seeing, L0 = float(seeing), float(L0)
+    except (TypeError, ValueError):
+        raise ValueError('seeing and L0 must be scalars') from None
+    if not (seeing > 0 and L0 > 0):
+        raise ValueError('need seeing > 0 and L0 > 0')
+    if wind_dir is None:
+        if np.size(h) != 2:
+            raise ValueError('wind_dir may only be omitted for two layers (the reference\'s directions)')
+        wind_dir = _lib.REF_WIND_DIR
+    hh, ws, wd = _lib.profile_layers(h, wind_speed, wind_dir)
+    if np.ndim(cn2) != 1:
+        raise ValueError('cn2 must be one weight per layer')
+    w = _lib.profile_weights(cn2, 1, hh.size)[0]
+    if GL is None:
+        GL = float(w[np.argmin(hh)] / w.sum())
+    try:
+        GL = float(GL)
+    except (TypeError, ValueError):
+        raise ValueError('GL must be a scalar') from None
+    if not 0 <= GL <= 1:
+        raise ValueError('need 0 <= GL <= 1')
+    if precision not in ('mixed', 'f64'):
+        raise ValueError("precision must be 'mixed' or 'f64'")
+    if positions is None:
+        if isinstance(npsflin, bool) or not isinstance(npsflin, (int, np.integer)) or not 1 <= npsflin <= 5:
+            raise ValueError('npsflin must be an integer between 1 and 5')
+        pos = None
+    else:
+        pos = _lib.field_positions(positions, max_n=None)
+    masks = _resolve_masks(cutoff_masks)
+    if verbose:
+        logger.info('Compute PSF for a %d-layer profile with seeing=%.2f L0=%.2f', hh.size, seeing, L0)
+        if three_lgs_mode:
+            logger.info('Using three lasers mode')
+    ctx = get_context(dim, pixscale, dimpsf, precision, device)
+    nl = lbda.size
+    args = (lbda, [seeing], [GL], [L0], w, hh, ws, wd, [1 if three_lgs_mode else 0])
+    try:
+        if pos is None:
+            r = ctx.reconstruct_profile(*args, npsflin=npsflin, masks=masks, want_sum=False)
+            psf, fit = r['psf'][0], r['fit'][0]
+            cols = _fit_columns(lbda, fit, pixscale)
+        else:
+            psf = np.empty((len(pos), nl, dimpsf, dimpsf))
+            fit = np.empty((len(pos), nl, _lib.NFIT))
+            for a, b in _field_groups(len(pos)):
+                r = ctx.reconstruct_profile(*args, npsflin=0, positions=pos[a:b], masks=masks, want_sum=False)
+                psf[a:b] = r['psf'][0]
+                fit[a:b] = r['fit'][0]
+            cols = _field_columns(lbda, pos, fit, pixscale)
+    except MpsfrError as e:
+        if e.code == E_GRID:
+            raise ValueError(str(e)) from None
+        raise
+    n = len(cols['lbda'])
+    cols['SEEING'] = np.full(n, seeing)
+    cols['GL'] = np.full(n, GL)
+    cols['L0'] = np.full(n, L0)
+    return _make_table(cols, {'SEEING': seeing, 'GL': GL, 'L0': L0, 'NLAYER': int(hh.size)}), psf
 
 
 def _field_sum(lbda, stats, three, pos, h, dim, dimpsf, pixscale, precision, cutoff_masks, devs):
