@@ -294,6 +294,24 @@ int mpsfr_wait_multi(mpsfr_ctx* const* ctxs, int nctx);
 int mpsfr_fit_stamps(mpsfr_ctx* ctx, int nstamp, const double* stamps, double* fit_out,
                      int on_device);
 
+/* Elliptical Moffat fit of caller-provided stamps (mpdaf's moffat_fit(circular=False), which the reference does not
+ * use): I (1 + Q)^-n with Q = (g / alpha^2) [(1 - e1) x^2 - 2 e2 x y + (1 + e1) y^2], g = 1 / sqrt(1 - e1^2 - e2^2),
+ * x = q - q0, y = p - p0; alpha is the geometric mean of the semi-axes.  With e = sqrt(e1^2 + e2^2):
+ * alpha_major = alpha ((1 + e)/(1 - e))^(1/4), alpha_minor = alpha ((1 - e)/(1 + e))^(1/4), the major axis at
+ * rot = atan2(e2, e1) / 2, FWHM_axis = 2 alpha_axis sqrt(2^(1/n) - 1).  At e = 0 the model is mpsfr_fit_stamps's.
+ * Arguments and on_device as mpsfr_fit_stamps: with on_device = 1 both pointers are device pointers and the call is
+ * queued on the context stream (e.g. after a device-output mpsfr_reconstruct_field / mpsfr_reconstruct_profile).
+ * stamps: [nstamp][dimpsf][dimpsf] float64; fit_out: [nstamp][MPSFR_NFIT_ELL].  Errors: the reduced-chi2 covariance
+ * (dof = npix - 7), propagated to first order.  A stamp whose elongation is not determined (e -> 0) has a finite rot
+ * and a large err_rot (at most 180); that is not a failure.  Timed under the fit's profiling id. */
+#define MPSFR_NFIT_ELL 24
+/* fit_out[k]: 0 peak  1 p0  2 q0  3 alpha_major (px)  4 alpha_minor (px)  5 n  6 rot (deg, [0,180), from +q towards +p)
+ *             7 fwhm_major (px)  8 fwhm_minor (px)  9 chi2  10 iterations  11 err_peak  12 err_p0  13 err_q0
+ *             14 err_fwhm_major  15 err_fwhm_minor  16 err_rot (deg)  17 err_n
+ *             18 status (codes and MPSFR_FIT_ILL_CONDITIONED bit as fit_out[14] of MPSFR_NFIT, same rule on n)
+ *             19 flux = peak pi alpha_major alpha_minor / (n - 1)  20 err_flux  21..23 zero (reserved) */
+int mpsfr_fit_stamps_elliptical(mpsfr_ctx* ctx, int nstamp, const double* stamps, double* fit_out, int on_device);
+
 /* The stages of the path as the reference exports them (muse_psfr/__init__.py:16: `from .psfrec import *`),
  * for a caller that holds its own PSD or its own stamps.  Host buffers, synchronous, float64; the same
  * kernels as mpsfr_reconstruct entered or left at another stage.

@@ -9,7 +9,7 @@ compute_psf_from_sparta(..., field_positions=...); compute_profile_psf (a Cn2 pr
 per-layer wind, averaged or at field positions).
 Low level: Context (ctypes binding of libmpsfr.so).
 """
-from ._lib import Context, ContextPool, MpsfrError, NFIT, FIT_ILL_CONDITIONED  # noqa: F401
+from ._lib import Context, ContextPool, MpsfrError, NFIT, NFIT_ELL, FIT_ILL_CONDITIONED  # noqa: F401
 from .synthetic import synthetic_rows, grid_pixscale  # noqa: F401
 from .psfrec import (MAX_L0, MIN_L0, compute_psf, compute_field_psf, compute_profile_psf,  # noqa: F401
                      compute_psf_from_sparta,

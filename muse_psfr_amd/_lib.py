@@ -10,6 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('MPSFR_LIB_PATH') or os.path.join(HERE, 'libmpsfr.so')
 
 NFIT = 16
+NFIT_ELL = 24                # elliptical fit rows (MPSFR_NFIT_ELL, include/mpsfr.h)
 FIT_ILL_CONDITIONED = 4      # status bit of fit_out[14] (MPSFR_FIT_ILL_CONDITIONED, include/mpsfr.h)
 DIM_AO = 80
 PREC_MIXED, PREC_F64 = 0, 1
@@ -83,6 +84,8 @@ def load():
     lib.mpsfr_wait_multi.restype = C.c_int
     lib.mpsfr_fit_stamps.argtypes = [p, C.c_int, p, p, C.c_int]
     lib.mpsfr_fit_stamps.restype = C.c_int
+    lib.mpsfr_fit_stamps_elliptical.argtypes = [p, C.c_int, p, p, C.c_int]
+    lib.mpsfr_fit_stamps_elliptical.restype = C.c_int
     lib.mpsfr_simul_psd.argtypes = [p, C.c_double, C.c_double, C.c_double, C.c_int, dp, C.c_double, C.c_int, u8p, u8p, dp]
     lib.mpsfr_simul_psd.restype = C.c_int
     lib.mpsfr_psf_from_psd.argtypes = [p, C.c_int, dp, C.c_int, dp, dp]
@@ -130,7 +133,7 @@ def load():
 
 
 EXPORTS = ['mpsfr_create', 'mpsfr_destroy', 'mpsfr_last_error', 'mpsfr_set_option',
-           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
+           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
            'mpsfr_psd_to_psf',
            'mpsfr_convolve_stamps', 'mpsfr_fit_rows', 'mpsfr_sync', 'mpsfr_last_ticket', 'mpsfr_wait', 'mpsfr_abandon',
            'mpsfr_stream', 'mpsfr_stream_wait', 'mpsfr_wait_event',
@@ -667,6 +670,25 @@ class Context:
                                          out.ctypes.data_as(C.c_void_p), 0))
         return out
 
+    def fit_stamps_elliptical(self, stamps):
+        """Elliptical Moffat fit (mpsfr_fit_stamps_elliptical) of stamps (..., dimpsf, dimpsf): (n, NFIT_ELL) rows."""
+        st = elliptical_stamps(stamps, self.dimpsf)
+        out = np.empty((st.shape[0], NFIT_ELL))
+        _check(self.lib.mpsfr_fit_stamps_elliptical(self._h, st.shape[0], st.ctypes.data_as(C.c_void_p),
+                                                    out.ctypes.data_as(C.c_void_p), 0))
+        return out
+
+    def fit_stamps_elliptical_device(self, nstamp, stamps_ptr, fit_ptr):
+        """Device-buffer elliptical fit (asynchronous, on_device = 1): `stamps_ptr` ([nstamp][dimpsf][dimpsf] float64)
+        and `fit_ptr` ([nstamp][NFIT_ELL] float64) are raw device pointers (int) on this context's GPU; the call is
+        queued on the context stream, after any device-output reconstruct of this context."""
+        if isinstance(nstamp, bool) or not isinstance(nstamp, (int, np.integer)) or nstamp < 1:
+            raise ValueError('nstamp must be a positive integer')
+        if not stamps_ptr or not fit_ptr:
+            raise ValueError('stamps_ptr and fit_ptr must be device pointers')
+        _check(self.lib.mpsfr_fit_stamps_elliptical(self._h, int(nstamp), C.c_void_p(int(stamps_ptr)),
+                                                    C.c_void_p(int(fit_ptr)), 1))
+
     def debug_fetch(self, what, shape):
         out = np.empty(int(np.prod(shape)))
         n = _check(self.lib.mpsfr_debug_fetch(self._h, what.encode(), _dptr(out), out.size))
@@ -690,6 +712,20 @@ class Context:
 
     def profile_reset(self):
         _check(self.lib.mpsfr_profile_reset(self._h))
+
+
+def elliptical_stamps(stamps, dimpsf=40):
+    """Stamps for the elliptical fit as a C-contiguous (n, dimpsf, dimpsf) float64 array; ValueError unless
+    `stamps` is a non-empty array of shape (..., dimpsf, dimpsf) with finite values."""
+    try:
+        st = np.asarray(getattr(stamps, 'data', stamps), dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('stamps must be a numeric array') from None
+    if st.ndim < 2 or st.shape[-2:] != (dimpsf, dimpsf) or st.size == 0:
+        raise ValueError('stamps must have the shape (..., %d, %d)' % (dimpsf, dimpsf))
+    if not np.all(np.isfinite(st)):
+        raise ValueError('stamps must be finite')
+    return np.ascontiguousarray(st).reshape(-1, dimpsf, dimpsf)
 
 
 class PendingResult:

@@ -1,0 +1,577 @@
+// HIP kernel of the elliptical Moffat fit, written for gfx950 (MI355X, wave64).  See DESIGN.md section 13.
+//
+// K_FIT (elliptical): 7-parameter Moffat least-squares fit per stamp -- mpdaf's Image.moffat_fit(circular=False,
+// fit_back=False), which the reference does not call (fit_psf_cube, psfrec.py:861-871, fits circularly):
+//     I (1 + Q)^-n,   Q = (g / a^2) [ (1 - e1) x^2 - 2 e2 x y + (1 + e1) y^2 ],   g = 1 / sqrt(1 - e1^2 - e2^2)
+// with x = q - q0 (column), y = p - p0 (row); a is the geometric mean of the semi-axes (the quadratic form has
+// determinant 1 / a^4).  (e1, e2) is smooth through the round case e = 0, where an (a, b, theta) parametrisation
+// has a singular normal matrix, and at e1 = e2 = 0 the model is k_fit's (stamps.hip).
+// The structure is k_fit's: one wave per stamp with the stamp in LDS, wave-wide sums on the DPP path, wave-uniform
+// Levenberg-Marquardt state (Marquardt scaling, Nielsen's damping update) in the variables
+// (I, p0, q0, w = geometric-mean FWHM, e1, e2, eta = 1/n).  Mixed mode: float iterations, then the fp64 gradient
+// polish with the last normal matrix; f64 mode: fp64 iterations throughout.
+#include "device_common.h"
+#include "fit_common.h"
+
+namespace mpsfr {
+
+namespace {
+
+constexpr int NPE = 7;                       // LM variables
+constexpr int NAE = NPE * (NPE + 1) / 2;     // upper triangle of the normal matrix
+constexpr double kEllIllCond = 100.0;        // MPSFR_FIT_ILL_CONDITIONED, include/mpsfr.h (the rule of k_fit)
+constexpr double kEllMaxE = 0.95;            // |e| bound of the step acceptance test
+constexpr int kEllMaxIt = 200;
+constexpr int kEllPolishMax = 8;
+
+template <typename T>
+struct EllNormEq {
+    T a[NAE];   // upper triangle of J^T J, row-major
+    T g[NPE];   // J^T r
+    T chi2;
+};
+
+// index of the diagonal element (k, k) in the row-major upper triangle
+__host__ __device__ constexpr int ell_diag(int k) { return k * NPE - k * (k - 1) / 2; }
+
+// Wave-uniform factors of a model pass at v = (I, p0, q0, w, e1, e2, eta).  With K = 1/a^2 = 4 (2^eta - 1) / w^2:
+// Q = A x^2 - 2 B x y + C y^2, A = gK (1 - e1), B = gK e2, C = gK (1 + e1).
+template <typename RE>
+struct EllPar {
+    RE I, p0, q0, n, gK, A, B, C, e1g2, e2g2, w2, nsq2, dKn;
+    __device__ __forceinline__ EllPar(const RE* v) {
+        I = v[0]; p0 = v[1]; q0 = v[2];
+        n = fit_rcp<RE>(v[6]);
+        const RE s_ = fit_exp2m1<RE>(v[6]);                   // 2^eta - 1
+        const RE iw = fit_rcp<RE>(v[3]);
+        const RE K = (RE)4 * s_ * iw * iw;
+        const RE e1 = v[4], e2 = v[5];
+        const RE g2 = fit_rcp<RE>((RE)1 - e1 * e1 - e2 * e2);
+        const RE g = fit_rsqrt<RE>((RE)1 - e1 * e1 - e2 * e2);
+        gK = g * K;
+        A = gK * ((RE)1 - e1); B = gK * e2; C = gK * ((RE)1 + e1);
+        e1g2 = e1 * g2; e2g2 = e2 * g2;
+        w2 = (RE)2 * iw;
+        nsq2 = n * n * (RE)0.69314718055994530942;          // n^2 ln2: the logarithm is to base 2
+        dKn = (s_ + (RE)1) * (RE)0.69314718055994530942 * fit_rcp<RE>(s_);   // (dK/d eta) / K
+    }
+};
+
+// Normal equations of the elliptical model over the lane's 25 pixels, summed over the wave (every lane ends up
+// with the totals).  Pixel map of k_fit's passes: the lane is a cell (lr, lc) of an 8 x 8 block and the 25 blocks
+// of the stamp are walked as 5 x 5, pixel (8 mo + lr, 8 mi + lc).  With c = n model / (1 + Q):
+//   d/dI = (1+Q)^-n            d/dp0 = 2c (C y - B x)         d/dq0 = 2c (A x - B y)         d/dw = 2c Q / w
+//   d/de1 = c (gK (x^2 - y^2) - e1 g^2 Q)      d/de2 = c (2 gK x y - e2 g^2 Q)
+//   d/deta = model n^2 ln(1+Q) - c Q (dK/deta)/K
+template <typename RE>
+__device__ __forceinline__ void ell_accumulate(const RE* pix, int lane, const RE* v, EllNormEq<RE>& ne) {
+    const EllPar<RE> P(v);
+    RE a[NAE], g[NPE], chi2 = (RE)0;
+#pragma unroll
+    for (int k = 0; k < NAE; ++k) a[k] = (RE)0;
+#pragma unroll
+    for (int k = 0; k < NPE; ++k) g[k] = (RE)0;
+    const RE lrf = (RE)(lane >> 3) - P.p0, lcf = (RE)(lane & 7) - P.q0;
+    const RE* pl = pix + (lane >> 3) * NS + (lane & 7);
+    static_assert(NS == 40, "5 x 5 blocks of 8 x 8 pixels");
+#pragma unroll 1
+    for (int mo = 0; mo < 5; ++mo) {
+        const RE y = (RE)(8 * mo) + lrf;
+        const RE yy = y * y;
+#pragma unroll
+        for (int mi = 0; mi < 5; ++mi) {
+            const RE x = (RE)(8 * mi) + lcf;
+            const RE xx = x * x, xy = x * y;
+            const RE Q = P.A * xx - (RE)2 * P.B * xy + P.C * yy;
+            const RE gg = (RE)1 + Q;
+            const RE lg2 = fit_log2<RE>(gg);
+            const RE e = fit_exp2<RE>(-P.n * lg2);
+            const RE m = P.I * e;
+            const RE r = m - pl[mo * 8 * NS + mi * 8];
+            const RE c = m * P.n * fit_rcp<RE>(gg);
+            const RE c2 = (RE)2 * c;
+            RE J[NPE];
+            J[0] = e;
+            J[1] = c2 * (P.C * y - P.B * x);
+            J[2] = c2 * (P.A * x - P.B * y);
+            J[3] = c2 * Q * P.w2 * (RE)0.5;
+            J[4] = c * (P.gK * (xx - yy) - P.e1g2 * Q);
+            J[5] = c * ((RE)2 * P.gK * xy - P.e2g2 * Q);
+            J[6] = m * (P.nsq2 * lg2) - c * Q * P.dKn;
+            chi2 += r * r;
+            int k = 0;
+#pragma unroll
+            for (int i = 0; i < NPE; ++i) {
+                g[i] += J[i] * r;
+#pragma unroll
+                for (int j = i; j < NPE; ++j) a[k++] += J[i] * J[j];
+            }
+        }
+    }
+    ne.chi2 = wave_total(chi2);
+#pragma unroll
+    for (int k = 0; k < NAE; ++k) ne.a[k] = wave_total(a[k]);
+#pragma unroll
+    for (int k = 0; k < NPE; ++k) ne.g[k] = wave_total(g[k]);
+}
+
+// chi2 alone at v (the residual pass without the Jacobian)
+template <typename RE>
+__device__ __forceinline__ RE ell_chi2(const RE* pix, int lane, const RE* v) {
+    const EllPar<RE> P(v);
+    RE cs[5] = {(RE)0, (RE)0, (RE)0, (RE)0, (RE)0};
+    const RE lrf = (RE)(lane >> 3) - P.p0, lcf = (RE)(lane & 7) - P.q0;
+    const RE* pl = pix + (lane >> 3) * NS + (lane & 7);
+#pragma unroll 1
+    for (int mo = 0; mo < 5; ++mo) {
+        const RE y = (RE)(8 * mo) + lrf;
+#pragma unroll
+        for (int mi = 0; mi < 5; ++mi) {
+            const RE x = (RE)(8 * mi) + lcf;
+            const RE Q = P.A * x * x - (RE)2 * P.B * x * y + P.C * y * y;
+            const RE r = P.I * fit_exp2<RE>(-P.n * fit_log2<RE>((RE)1 + Q)) - pl[mo * 8 * NS + mi * 8];
+            cs[mi] += r * r;
+        }
+    }
+    return wave_total(((cs[0] + cs[1]) + (cs[2] + cs[3])) + cs[4]);
+}
+
+// fp64 gradient J^T r over the fp64 stamp in memory, for the polish of the mixed mode (moffat_gradient of k_fit):
+// only the residual needs fp64; the Jacobian, which multiplies a residual of ~1e-3 of the peak at the solution,
+// and the per-lane partial sums run in float.
+__device__ __forceinline__ void ell_gradient(const double* __restrict__ src, int lane, const double* v, double* gout,
+                                             double* chi2out) {
+    const double n = sgpr(1.0 / v[6]);
+    const double s = lean_exp(0.69314718055994530942 * v[6]) - 1.0;
+    const double K = 4.0 * s / (v[3] * v[3]);
+    const double e1 = v[4], e2 = v[5], q = 1.0 - e1 * e1 - e2 * e2;
+    const double gK = sgpr(K / sqrt(q));
+    const double A = sgpr(gK * (1.0 - e1)), B = sgpr(gK * e2), C = sgpr(gK * (1.0 + e1));
+    const double I = sgpr(v[0]), p0 = sgpr(v[1]), q0 = sgpr(v[2]);
+    const float nf = (float)n, nsq = (float)(n * n), dKn = (float)sgpr((s + 1.0) * 0.69314718055994530942 / s);
+    const float w2 = (float)sgpr(2.0 / v[3]), gKf = (float)gK, Af = (float)A, Bf = (float)B, Cf = (float)C;
+    const float e1g2 = (float)sgpr(e1 / q), e2g2 = (float)sgpr(e2 / q);
+    float g[NPE] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, c2sum = 0.f;
+    const double lrd = (double)(lane >> 3) - p0, lcd = (double)(lane & 7) - q0;
+    const double* pl = src + (lane >> 3) * NS + (lane & 7);
+#pragma unroll 1
+    for (int mo = 0; mo < 5; ++mo) {
+        const double y = (double)(8 * mo) + lrd;
+#pragma unroll
+        for (int mi = 0; mi < 5; ++mi) {
+            const double x = (double)(8 * mi) + lcd;
+            const double Q = fma(A * x, x, fma(C * y, y, -2.0 * B * x * y));
+            const double gg = 1.0 + Q;
+            const double lg = lean_log(gg);
+            const double e = lean_exp(-n * lg);
+            const double m = I * e;
+            const float r = (float)(m - pl[mo * 8 * NS + mi * 8]);
+            c2sum += r * r;
+            const float xf = (float)x, yf = (float)y, Qf = (float)Q, mf = (float)m;
+            const float c = mf * nf * __builtin_amdgcn_rcpf((float)gg);
+            const float cr = c * r;
+            g[0] += (float)e * r;
+            g[1] += 2.f * cr * (Cf * yf - Bf * xf);
+            g[2] += 2.f * cr * (Af * xf - Bf * yf);
+            g[3] += cr * Qf * w2;
+            g[4] += cr * (gKf * (xf * xf - yf * yf) - e1g2 * Qf);
+            g[5] += cr * (2.f * gKf * xf * yf - e2g2 * Qf);
+            g[6] += (nsq * mf * (float)lg - c * Qf * dKn) * r;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NPE; ++k) gout[k] = wave_total((double)g[k]);
+    *chi2out = (double)wave_total(c2sum);
+}
+
+// Cholesky factor of the Marquardt-scaled normal matrix A'_ij = A_ij / (d_i d_j) + mu delta_ij, d_i = sqrt(A_ii)
+// (chol5 of stamps.hip for seven variables).  Li holds 1 / L_ii.  Returns false if not positive definite.
+template <typename S, typename T>
+__device__ __forceinline__ bool chol7(const EllNormEq<T>& ne, S mu, S L[NPE][NPE], S Li[NPE], S id[NPE]) {
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < NPE; ++i) {
+        const S d = (S)ne.a[ell_diag(i)];
+        ok = ok && (d > (S)0);
+        id[i] = fit_rsqrt<S>(d);
+    }
+    {
+        int k = 0;
+#pragma unroll
+        for (int i = 0; i < NPE; ++i)
+#pragma unroll
+            for (int j = i; j < NPE; ++j) {
+                L[j][i] = (S)ne.a[k] * id[i] * id[j];
+                ++k;
+            }
+    }
+#pragma unroll
+    for (int j = 0; j < NPE; ++j) {
+        S s = (S)1 + mu;
+#pragma unroll
+        for (int q = 0; q < j; ++q) s -= L[j][q] * L[j][q];
+        ok = ok && (s > (S)0);
+        Li[j] = fit_rsqrt<S>(s);
+        L[j][j] = s * Li[j];
+#pragma unroll
+        for (int i = j + 1; i < NPE; ++i) {
+            S t = L[i][j];
+#pragma unroll
+            for (int q = 0; q < j; ++q) t -= L[i][q] * L[j][q];
+            L[i][j] = t * Li[j];
+        }
+    }
+    return ok;
+}
+
+// x = A^-1 b through the factor of chol7 (b and x in unscaled units)
+template <typename S, typename X>
+__device__ __forceinline__ void chol7_solve(const S L[NPE][NPE], const S Li[NPE], const S id[NPE], const S b[NPE],
+                                            X* x) {
+    S y[NPE], z[NPE];
+#pragma unroll
+    for (int i = 0; i < NPE; ++i) {
+        S t = b[i] * id[i];
+#pragma unroll
+        for (int q = 0; q < i; ++q) t -= L[i][q] * y[q];
+        y[i] = t * Li[i];
+    }
+#pragma unroll
+    for (int i = NPE - 1; i >= 0; --i) {
+        S t = y[i];
+#pragma unroll
+        for (int q = i + 1; q < NPE; ++q) t -= L[q][i] * z[q];
+        z[i] = t * Li[i];
+    }
+#pragma unroll
+    for (int i = 0; i < NPE; ++i) x[i] = (X)(z[i] * id[i]);
+}
+
+// solve (A + mu diag(A)) x = -g
+template <typename S, typename T>
+__device__ __forceinline__ bool ell_solve(const EllNormEq<T>& ne, S mu, S* x) {
+    S L[NPE][NPE], Li[NPE], id[NPE], b[NPE];
+    if (!chol7<S, T>(ne, mu, L, Li, id)) return false;
+#pragma unroll
+    for (int i = 0; i < NPE; ++i) b[i] = -(S)ne.g[i];
+    chol7_solve<S, S>(L, Li, id, b, x);
+    return true;
+}
+
+// inverse of the symmetric normal matrix (in its own arithmetic type); false if singular
+template <typename T>
+__device__ __forceinline__ bool ell_inverse(const EllNormEq<T>& ne, double cov[NPE][NPE]) {
+    T L[NPE][NPE], Li[NPE], id[NPE];
+    if (!chol7<T, T>(ne, (T)0, L, Li, id)) return false;
+#pragma unroll
+    for (int c = 0; c < NPE; ++c) {
+        T b[NPE];
+        double x[NPE];
+#pragma unroll
+        for (int k = 0; k < NPE; ++k) b[k] = (k == c) ? (T)1 : (T)0;
+        chol7_solve<T, double>(L, Li, id, b, x);
+#pragma unroll
+        for (int k = 0; k < NPE; ++k) cov[k][c] = x[k];
+    }
+    return true;
+}
+
+// size of a step dx towards vn: relative for I, p0, q0, w, eta (k_fit's rule), absolute for e1, e2 (|e| < 1, and
+// e = 0 is the round stamp)
+template <typename S>
+__device__ __forceinline__ S ell_step_size(const S* dx, const S* vn) {
+    S rel = (S)0;
+#pragma unroll
+    for (int k = 0; k < NPE; ++k) {
+        const S den = (k == 4 || k == 5) ? (S)1 : fabs(vn[k]) + (S)1.0e-30;
+        rel = fmax(rel, fabs(dx[k]) * fit_rcp<S>(den));
+    }
+    return rel;
+}
+
+template <typename S>
+__device__ __forceinline__ bool ell_inside(const S* vn) {
+    return vn[3] > (S)1.0e-3 && vn[6] > (S)1.0e-3 && vn[6] < (S)1.0e2 &&
+           vn[4] * vn[4] + vn[5] * vn[5] <= (S)(kEllMaxE * kEllMaxE);
+}
+
+// one wave per stamp; RE = float: mixed mode (float iterations + fp64 polish), RE = double: f64 mode
+template <typename RE>
+__global__ void __launch_bounds__(64)
+k_fit_ell(int nstamp, const double* __restrict__ stamps, double* __restrict__ fit, double polish_tol) {
+    constexpr int NPX = NS * NS / 64;
+    static_assert(NPX * 64 == NS * NS, "the lane map assumes 1600 pixels");
+    using S = RE;
+    const int lane = threadIdx.x & 63;
+    const int st = (int)blockIdx.x;
+    if (st >= nstamp) return;
+    const double* src = stamps + (size_t)st * NS * NS;
+    __shared__ RE sp[NS * NS];
+    double best = -3.0e38;
+    int besto = 0;
+#pragma unroll
+    for (int m = 0; m < NPX; ++m) {
+        const int o = lane + m * 64;
+        const double d = src[o];
+        sp[o] = (RE)d;
+        if (d > best) { best = d; besto = o; }
+    }
+    __syncthreads();                 // (one wave: the LM passes read pixels other lanes wrote)
+    // argmax (first maximum in C order, as np.argmax)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ob = __shfl_xor(best, o, 64);
+        const int oo = __shfl_xor(besto, o, 64);
+        if (ob > best || (ob == best && oo < besto)) { best = ob; besto = oo; }
+    }
+    // Start values: k_fit's moment start for (I, p0, q0, w, eta) -- moments over the largest disc around the
+    // brightest pixel that fits the stamp, truncation factors by fixed-point iteration -- and the second moments
+    // over the same disc for (e1, e2) = ((Mxx - Myy), 2 Mxy) / (Mxx + Myy), exact for an untruncated profile with
+    // elliptical isophotes.
+    const int p0i = besto / NS, q0i = besto % NS;
+    const int rm = min(min(p0i, NS - 1 - p0i), min(q0i, NS - 1 - q0i));
+    int cnt = 0;
+    const double half = 0.5 * best;
+    float ms1 = 0.f, ms2 = 0.f, mxx = 0.f, myy = 0.f, mxy = 0.f;
+    {
+        const float r2 = ((float)rm + 0.5f) * ((float)rm + 0.5f);
+        const float lrf = (float)((lane >> 3) - p0i), lcf = (float)((lane & 7) - q0i);
+        const double* pl = src + (lane >> 3) * NS + (lane & 7);
+#pragma unroll
+        for (int mo = 0; mo < 5; ++mo) {
+            const float dp = (float)(8 * mo) + lrf, dp2 = dp * dp;
+#pragma unroll
+            for (int mi = 0; mi < 5; ++mi) {
+                const float dq = (float)(8 * mi) + lcf;
+                const double dd = pl[mo * 8 * NS + mi * 8];
+                cnt += dd > half ? 1 : 0;
+                const float din = fmaf(dq, dq, dp2) <= r2 ? (float)dd : 0.f;
+                ms1 += din;
+                ms2 = fmaf(din, din, ms2);
+                mxx = fmaf(din * dq, dq, mxx);
+                myy = fmaf(din * dp, dp, myy);
+                mxy = fmaf(din * dq, dp, mxy);
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    ms1 = wave_total(ms1);
+    ms2 = wave_total(ms2);
+    mxx = wave_total(mxx);
+    myy = wave_total(myy);
+    mxy = wave_total(mxy);
+    double fw0 = 2.0 * sqrt((double)cnt / kPi);
+    fw0 = fmin(fmax(fw0, 1.5), (double)NS);
+    float eta0 = 0.4f, e10 = 0.f, e20 = 0.f;
+    if (rm >= 6 && ms1 > 0.f && (float)best > 0.f) {
+        const float bf = (float)best, r2 = ((float)rm + 0.5f) * ((float)rm + 0.5f);
+        float t1 = 1.f, t2 = 1.f, nn = 2.5f, a2 = 1.f;
+#pragma unroll 1
+        for (int k = 0; k < 6; ++k) {
+            float rho = (ms2 * t1) * __builtin_amdgcn_rcpf(bf * ms1 * t2);
+            rho = fminf(fmaxf(rho, 0.05f), 0.47f);
+            nn = (1.f - rho) * __builtin_amdgcn_rcpf(1.f - 2.f * rho);
+            nn = fminf(fmaxf(nn, 1.1f), 15.f);
+            a2 = ms1 * (nn - 1.f) * __builtin_amdgcn_rcpf(t1 * bf * 3.14159265f);
+            const float lx = __builtin_amdgcn_logf(1.f + r2 * __builtin_amdgcn_rcpf(a2));
+            t1 = 1.f - __builtin_amdgcn_exp2f((1.f - nn) * lx);
+            t2 = 1.f - __builtin_amdgcn_exp2f((1.f - 2.f * nn) * lx);
+        }
+        eta0 = __builtin_amdgcn_rcpf(nn);
+        const float w = 2.f * __builtin_amdgcn_sqrtf(a2 * (__builtin_amdgcn_exp2f(eta0) - 1.f));
+        if (w == w) fw0 = fmin(fmax((double)w, 1.5), (double)NS);
+        const float tr = mxx + myy;
+        if (tr > 0.f) {
+            e10 = (mxx - myy) / tr;
+            e20 = 2.f * mxy / tr;
+            const float e = sqrtf(e10 * e10 + e20 * e20);
+            if (!(e <= 0.9f)) {                 // (NaN included)
+                const float sc = e == e ? 0.9f / e : 0.f;
+                e10 *= sc;
+                e20 *= sc;
+            }
+        }
+    }
+    S v[NPE] = {(S)best, (S)p0i, (S)q0i, (S)fw0, (S)e10, (S)e20, (S)eta0};
+    const S tol = sizeof(RE) == 4 ? (S)1.0e-3 : (S)1.0e-10;
+    EllNormEq<RE> ne;
+    ell_accumulate<RE>(sp, lane, v, ne);
+    S mu = (S)1.0e-2, nu = (S)2;
+    const S mu_max = (S)1.0e15;
+    int it = 0, status = 1;
+    while (it < kEllMaxIt) {
+        ++it;
+        S dx[NPE];
+        if (!ell_solve<S, RE>(ne, mu, dx)) {
+            mu *= nu;
+            nu *= (S)2;
+            if (mu > mu_max) { status = 2; break; }
+            continue;
+        }
+        // the step limit of k_fit on eta: a step may cut eta to a fifth at most (the whole step is scaled)
+        if (v[6] + dx[6] < (S)0.2 * v[6]) {
+            const S sc = (S)-0.8 * v[6] * fit_rcp<S>(dx[6]);
+#pragma unroll
+            for (int k = 0; k < NPE; ++k) dx[k] *= sc;
+        }
+        S vn[NPE];
+#pragma unroll
+        for (int k = 0; k < NPE; ++k) vn[k] = v[k] + dx[k];
+        const S rel = ell_step_size<S>(dx, vn);
+        const bool inside = ell_inside<S>(vn);
+        if (inside && rel < tol) {       // converged: take the last (tiny) Gauss-Newton step
+#pragma unroll
+            for (int k = 0; k < NPE; ++k) v[k] = vn[k];
+            status = 0;
+            break;
+        }
+        EllNormEq<RE> nn;
+        S rho = (S)-1;
+        if (inside) {
+            ell_accumulate<RE>(sp, lane, vn, nn);
+            S pred = (S)0;         // predicted decrease of chi2: dx^T (mu D dx - g)
+#pragma unroll
+            for (int k = 0; k < NPE; ++k) pred += dx[k] * (mu * (S)ne.a[ell_diag(k)] * dx[k] - (S)ne.g[k]);
+            rho = ((S)ne.chi2 - (S)nn.chi2) * fit_rcp<S>(pred);    // NaN -> rejected
+        }
+        if (rho > (S)0) {
+#pragma unroll
+            for (int k = 0; k < NPE; ++k) v[k] = vn[k];
+            ne = nn;
+            if (v[6] < (S)1.5e-3) { status = 0; break; }      // n > 666: Gaussian to 1e-3, stop
+            const S c = (S)2 * rho - (S)1;
+            mu = fmax(mu * fmax((S)(1.0 / 3.0), (S)1 - c * c * c), (S)1.0e-14);
+            nu = (S)2;
+        } else {
+            mu *= nu;
+            nu *= (S)2;
+            if (mu > mu_max) { status = 0; break; }   // no further descent: at the minimum
+        }
+    }
+    double vd[NPE];
+#pragma unroll
+    for (int k = 0; k < NPE; ++k) vd[k] = (double)v[k];
+    double chi2 = -1.0;
+    if constexpr (sizeof(RE) == 4) {
+        // the fp64 polish of k_fit: steps -A^-1 g, g the fp64 gradient, A the float normal matrix of the last
+        // iteration
+        EllNormEq<double> np;
+#pragma unroll
+        for (int k = 0; k < NAE; ++k) np.a[k] = (double)ne.a[k];
+        np.chi2 = -1.0;
+        for (int pz = 0; pz < kEllPolishMax && status != 2; ++pz) {
+            ell_gradient(src, lane, vd, np.g, &np.chi2);
+            double dx[NPE], vn[NPE];
+            if (!ell_solve<double, double>(np, 1.0e-10, dx)) break;
+#pragma unroll
+            for (int k = 0; k < NPE; ++k) vn[k] = vd[k] + dx[k];
+            const double rel = ell_step_size<double>(dx, vn);
+            if (!ell_inside<double>(vn) || rel >= 0.1) break;
+#pragma unroll
+            for (int k = 0; k < NPE; ++k) vd[k] = vn[k];
+            ++it;
+            chi2 = rel < 1.0e-3 ? np.chi2 : -1.0;
+            if (rel < polish_tol) break;
+        }
+        if (chi2 < 0.0) {              // a residual pass at the final point, in fp64
+            double cs = 0.0;
+            {
+                const EllPar<double> P(vd);
+                const double lrd = (double)(lane >> 3) - P.p0, lcd = (double)(lane & 7) - P.q0;
+                const double* pl = src + (lane >> 3) * NS + (lane & 7);
+#pragma unroll 1
+                for (int mo = 0; mo < 5; ++mo) {
+                    const double y = (double)(8 * mo) + lrd;
+#pragma unroll
+                    for (int mi = 0; mi < 5; ++mi) {
+                        const double x = (double)(8 * mi) + lcd;
+                        const double Q = fma(P.A * x, x, fma(P.C * y, y, -2.0 * P.B * x * y));
+                        const double r = P.I * lean_exp(-P.n * lean_log(1.0 + Q)) - pl[mo * 8 * NS + mi * 8];
+                        cs = fma(r, r, cs);
+                    }
+                }
+            }
+            chi2 = wave_total(cs);
+        }
+    } else {
+        chi2 = (double)ell_chi2<RE>(sp, lane, v);
+    }
+    if (lane != 0) return;
+    // Outputs.  n = 1/eta, alpha = w / (2 sqrt(2^eta - 1)); with e = |(e1, e2)| and f = ((1 + e)/(1 - e))^(1/4) the
+    // semi-axes are alpha f and alpha / f, the FWHMs w f and w / f, the major axis at rot = atan2(e2, e1) / 2.
+    // The covariance is the inverse of the normal matrix of the last iteration times chi2 / (npix - 7); the
+    // errors of derived values are propagated to first order.
+    const double I = vd[0], w = vd[3], e1 = vd[4], e2 = vd[5], eta = vd[6];
+    const double n = 1.0 / eta;
+    const double p2 = exp2(eta), s2 = p2 - 1.0, sq = sqrt(s2);
+    const double al = w / (2.0 * sq);
+    const double esq = e1 * e1 + e2 * e2, e = sqrt(esq);
+    const double f = sqrt(sqrt((1.0 + e) / (1.0 - e)));
+    double rot = 0.5 * atan2(e2, e1) * (180.0 / kPi);
+    if (rot < 0.0) rot += 180.0;
+    if (rot >= 180.0) rot -= 180.0;
+    const double flux = I * kPi * al * al / (n - 1.0);
+    double* o = fit + (size_t)st * NFIT_ELL;
+    o[0] = I; o[1] = vd[1]; o[2] = vd[2];
+    o[3] = al * f; o[4] = al / f; o[5] = n; o[6] = rot;
+    o[7] = w * f; o[8] = w / f;
+    o[9] = chi2;
+    o[10] = (double)it;
+    o[19] = flux;
+#pragma unroll
+    for (int k = 21; k < NFIT_ELL; ++k) o[k] = 0.0;
+    double cov[NPE][NPE];
+    if (ell_inverse(ne, cov)) {
+        const double s = chi2 / (double)(NS * NS - NPE);
+        auto quad = [&](const double* gr) {       // s g^T cov g over the variables of gr (7 entries)
+            double q = 0.0;
+#pragma unroll
+            for (int i = 0; i < NPE; ++i)
+#pragma unroll
+                for (int j = 0; j < NPE; ++j) q += gr[i] * cov[i][j] * gr[j];
+            return sqrt(fmax(q * s, 0.0));
+        };
+        const double ue1 = e > 0.0 ? e1 / e : 1.0, ue2 = e > 0.0 ? e2 / e : 0.0;
+        const double h = 0.5 / (1.0 - esq);                  // d ln f / d e
+        const double gmaj[NPE] = {0, 0, 0, f, w * f * h * ue1, w * f * h * ue2, 0};
+        const double gmin[NPE] = {0, 0, 0, 1.0 / f, -w / f * h * ue1, -w / f * h * ue2, 0};
+        o[11] = sqrt(fmax(cov[0][0] * s, 0.0));
+        o[12] = sqrt(fmax(cov[1][1] * s, 0.0));
+        o[13] = sqrt(fmax(cov[2][2] * s, 0.0));
+        o[14] = quad(gmaj);
+        o[15] = quad(gmin);
+        // rot: d/de1 = -e2 / (2 e^2), d/de2 = e1 / (2 e^2); undetermined (e -> 0): capped at 180 degrees
+        double erot = 180.0;
+        if (esq > 0.0) {
+            const double grot[NPE] = {0, 0, 0, 0, -0.5 * e2 / esq, 0.5 * e1 / esq, 0};
+            erot = fmin(quad(grot) * (180.0 / kPi), 180.0);
+            if (!(erot == erot)) erot = 180.0;
+        }
+        o[16] = erot;
+        o[17] = n * n * sqrt(fmax(cov[6][6] * s, 0.0));          // |dn/d eta| = n^2
+        // flux = I pi w^2 / (4 (2^eta - 1) (n - 1))
+        const double gfl[NPE] = {kPi * al * al / (n - 1.0), 0, 0, 2.0 * flux / w, 0, 0,
+                                 flux * (n * n / (n - 1.0) - p2 * 0.69314718055994530942 / s2)};
+        o[20] = quad(gfl);
+        if (n * n * sqrt(fmax(cov[6][6], 0.0)) * fabs(I) >= kEllIllCond) status |= 4;
+    } else {
+        for (int k = 11; k <= 17; ++k) o[k] = 0.0;
+        o[20] = 0.0;
+        if (status == 0) status = 2;
+    }
+    o[18] = (double)status;
+}
+
+}  // namespace
+
+void launch_fit_ell(hipStream_t s, int nstamp, const double* d_stamps, double* d_fit, bool f64) {
+    if (nstamp <= 0) return;
+    // one wavefront (and workgroup) per stamp, as k_fit
+    if (f64)
+        hipLaunchKernelGGL(k_fit_ell<double>, dim3(nstamp), dim3(64), 0, s, nstamp, d_stamps, d_fit, 0.0);
+    else
+        hipLaunchKernelGGL(k_fit_ell<float>, dim3(nstamp), dim3(64), 0, s, nstamp, d_stamps, d_fit, 1.0e-4);
+}
+
+}  // namespace mpsfr

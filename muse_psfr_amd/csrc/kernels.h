@@ -12,6 +12,7 @@ constexpr int NSH = NS / 2 + 1;  // samples 0..20 of a line; sample 40-i is the 
 constexpr int KS = 41;       // Moffat kernel side, psfrec.py:911-916
 constexpr int NAO = 80;      // AO-corrected zone, psfrec.py:103, 138
 constexpr int NFIT = 16;
+constexpr int NFIT_ELL = 24;     // elliptical fit (fit_ell.hip)
 constexpr int KHAT = 33 * 64;  // complex entries of one kernel spectrum (k_khat)
 constexpr int MAXLGS = 4;
 
@@ -277,6 +278,8 @@ void launch_fit(hipStream_t s, int nstamp, const void* d_stamps, bool stamps_f32
                 bool f64, int sum_ntask = 0, int sum_nl = 0, double* d_sum = nullptr, int sum_accumulate = 0);
 void launch_stamp_sum(hipStream_t s, int ntask, int nl, const void* d_fin, bool fin_f32, double* d_sum,
                       int accumulate);
+// elliptical Moffat fit (fit_ell.hip): [nstamp][40][40] double stamps -> [nstamp][NFIT_ELL]
+void launch_fit_ell(hipStream_t s, int nstamp, const double* d_stamps, double* d_fit, bool f64);
 // the call's parameter blob from pinned host memory into device memory, as a kernel of the call's own queue
 // (bytes: a multiple of 16); h_flag_pinned: a pinned host word that receives `seq` once the blob has been read
 void launch_param_copy(hipStream_t s, void* d_dst, const void* h_src_pinned, size_t bytes,

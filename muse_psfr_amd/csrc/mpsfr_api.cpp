@@ -2243,6 +2243,36 @@ int mpsfr_fit_stamps(mpsfr_ctx* c, int nstamp, const double* stamps, double* fit
     return MPSFR_OK;
 }
 
+int mpsfr_fit_stamps_elliptical(mpsfr_ctx* c, int nstamp, const double* stamps, double* fit_out, int on_device) {
+    if (!c || !stamps || !fit_out || nstamp < 1) return fail(MPSFR_E_INVALID, "bad argument");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t per = (size_t)NS * NS;
+    // the calls queued so far run on the pipeline lanes: the fit waits for them on the GPU, so that device stamps
+    // written by a device-output reconstruct of this context are complete when it reads them
+    for (int k = 0; k < mpsfr_ctx::MAX_LANES; ++k)
+        if (c->lane[k].busy && c->lane[k].stream != s) HIPCHK(hipStreamWaitEvent(s, lane_end(c, c->lane[k]), 0));
+    if (on_device) {
+        ProfScope ps(c, K_FIT);
+        launch_fit_ell(s, nstamp, stamps, fit_out, c->f64);
+        HIPCHK(hipGetLastError());
+        return MPSFR_OK;
+    }
+    int rc;
+    if ((rc = ensure(c, c->stage, (size_t)nstamp * (per + NFIT_ELL) * sizeof(double)))) return rc;
+    double* d_st = (double*)c->stage.p;
+    double* d_ft = d_st + (size_t)nstamp * per;
+    HIPCHK(hipMemcpyAsync(d_st, stamps, (size_t)nstamp * per * sizeof(double), hipMemcpyHostToDevice, s));
+    {
+        ProfScope ps(c, K_FIT);
+        launch_fit_ell(s, nstamp, d_st, d_ft, c->f64);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(fit_out, d_ft, (size_t)nstamp * NFIT_ELL * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MPSFR_OK;
+}
+
 long mpsfr_debug_fetch(mpsfr_ctx* c, const char* what, double* out, size_t capacity) {
     if (!c || !what || !out) return fail(MPSFR_E_INVALID, "NULL argument");
     HIPCHK(hipSetDevice(c->device));

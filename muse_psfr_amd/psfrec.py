@@ -31,6 +31,9 @@ logger = logging.getLogger(__name__)
 
 _FIT_COLS = ('lbda', 'center', 'flux', 'fwhm', 'n', 'peak', 'err_center', 'err_flux', 'err_fwhm',
              'err_n', 'err_peak')
+# mpdaf's moffat_fit(circular=False) columns: fwhm / err_fwhm are (major, minor), rot / err_rot in degrees
+_FIT_COLS_ELL = ('lbda', 'center', 'flux', 'fwhm', 'n', 'rot', 'peak', 'err_center', 'err_flux', 'err_fwhm', 'err_n',
+                 'err_rot', 'err_peak')
 
 
 _ASTROPY = []
@@ -265,6 +268,34 @@ def _fit_columns(lbda, fit, pixscale):
     return cols
 
 
+def _fit_columns_ell(lbda, fit, pixscale):
+    """fit: (n, NFIT_ELL) elliptical fit rows of libmpsfr -> the columns of _FIT_COLS_ELL (fwhm in arcsec)."""
+    fit = np.asarray(fit)
+    n = fit.shape[0]
+    cols = OrderedDict()
+    cols['lbda'] = np.asarray(lbda, dtype=float)
+    cols['center'] = fit[:, 1:3].copy()
+    cols['flux'] = fit[:, 19].copy()
+    cols['fwhm'] = fit[:, 7:9] * pixscale
+    cols['n'] = fit[:, 5].copy()
+    cols['rot'] = fit[:, 6].copy()
+    cols['peak'] = fit[:, 0].copy()
+    cols['err_center'] = fit[:, 12:14].copy()
+    cols['err_flux'] = fit[:, 20].copy()
+    cols['err_fwhm'] = fit[:, 14:16] * pixscale
+    cols['err_n'] = fit[:, 17].copy()
+    cols['err_rot'] = fit[:, 16].copy()
+    cols['err_peak'] = fit[:, 11].copy()
+    assert tuple(cols) == _FIT_COLS_ELL and all(len(v) == n for v in cols.values())
+    return cols
+
+
+def _check_circular(circular):
+    if not isinstance(circular, (bool, np.bool_)):
+        raise ValueError('circular must be True or False')
+    return bool(circular)
+
+
 _FIT_ROWS_DTYPE = np.dtype([('lbda', 'f8'), ('center', 'f8', (2,)), ('flux', 'f8'), ('fwhm', 'f8', (2,)),
                             ('n', 'f8'), ('peak', 'f8'), ('err_center', 'f8', (2,)), ('err_flux', 'f8'),
                             ('err_fwhm', 'f8', (2,)), ('err_n', 'f8'), ('err_peak', 'f8'), ('SEEING', 'f8'),
@@ -313,8 +344,18 @@ def _make_table(cols, meta=None):
     return Table(cols, meta)
 
 
-def fit_psf_cube(lbda, psfcube, *, pixscale=0.2, precision='mixed', device=0):
-    """Fit a Moffat PSF on each wavelength plane of the psfcube (psfrec.py:861-871)."""
+def fit_psf_cube(lbda, psfcube, *, circular=True, pixscale=0.2, precision='mixed', device=0):
+    """Fit a Moffat PSF on each wavelength plane of the psfcube (psfrec.py:861-871).
+
+    circular=False: an elliptical Moffat (mpdaf's moffat_fit(circular=False)); the table has the columns of
+    _FIT_COLS_ELL, with fwhm / err_fwhm as (major, minor) in arcsec and rot / err_rot in degrees (major axis from
+    the column axis towards the row axis, in [0, 180))."""
+    if not _check_circular(circular):
+        data = _lib.elliptical_stamps(psfcube)
+        if np.size(lbda) != data.shape[0]:
+            raise ValueError('need one wavelength per plane of psfcube')
+        ctx = get_context(128, pixscale, data.shape[-1], precision, device)
+        return _make_table(_fit_columns_ell(lbda, ctx.fit_stamps_elliptical(data), pixscale))
     data = np.asarray(getattr(psfcube, 'data', psfcube), dtype=float)
     ctx = get_context(128, pixscale, data.shape[-1], precision, device)
     return _make_table(_fit_columns(lbda, ctx.fit_stamps(data), pixscale))
@@ -539,9 +580,10 @@ def compute_psf(lbda, seeing, GL, L0, npsflin=1, h=(100, 10000), three_lgs_mode=
     return res, r['psf'][0]
 
 
-def _field_columns(lbda, pos, fit, pixscale):
+def _field_columns(lbda, pos, fit, pixscale, columns=None):
     """Columns of a field fit table from fit rows (npos, nl, NFIT): rows ordered (position, wavelength);
-    dir_idx (0-based index into `pos`), x, y (arcsec), then the columns of _fit_columns (lbda first)."""
+    dir_idx (0-based index into `pos`), x, y (arcsec), then the columns of _fit_columns (lbda first), or of
+    `columns` (_fit_columns_ell for elliptical fit rows)."""
     pos = np.asarray(pos, dtype=float)
     lbda = np.asarray(lbda, dtype=float)
     npos, nl = pos.shape[0], lbda.size
@@ -550,7 +592,7 @@ def _field_columns(lbda, pos, fit, pixscale):
     cols['dir_idx'] = np.repeat(np.arange(npos), nl)
     cols['x'] = np.repeat(pos[:, 0], nl)
     cols['y'] = np.repeat(pos[:, 1], nl)
-    cols.update(_fit_columns(np.tile(lbda, npos), fit, pixscale))
+    cols.update((columns or _fit_columns)(np.tile(lbda, npos), fit, pixscale))
     return cols
 
 
@@ -572,7 +614,7 @@ def _field_groups(npos):
 
 def compute_field_psf(lbda, seeing, GL, L0, positions=None, npsflin=1, h=(100, 10000), three_lgs_mode=False,
                       verbose=True, *, dim=1280, dimpsf=40, pixscale=0.2, precision='mixed',
-                      cutoff_masks='host', device=0):
+                      cutoff_masks='host', device=0, circular=True):
     """Field-resolved form of compute_psf: the PSF at every field position instead of their mean.
 
     ``positions``: (npos, 2) array of (x, y) in arcsec (|x|, |y| <= 60, the convention of direction_perf:
@@ -581,7 +623,9 @@ def compute_field_psf(lbda, seeing, GL, L0, positions=None, npsflin=1, h=(100, 1
 
     Returns ``(table, psf)``: ``psf`` (npos, nl, dimpsf, dimpsf) float64; ``table`` npos x nl rows ordered
     (position, wavelength) with the columns dir_idx (0-based), x, y, lbda, the fit columns of compute_psf and
-    SEEING, GL, L0 (values in the meta too)."""
+    SEEING, GL, L0 (values in the meta too).  circular=False: the fit columns are those of an elliptical Moffat
+    fitted to ``psf`` (fit_psf_cube(..., circular=False)); ``psf`` is the same."""
+    circular = _check_circular(circular)
     lbda = np.atleast_1d(np.asarray(lbda, dtype=float))
     if lbda.ndim != 1 or lbda.size < 1 or not np.all(np.isfinite(lbda)) or np.any(lbda <= 0):
         raise ValueError('lbda must be a non-empty 1-D array of positive wavelengths (nm)')
@@ -615,7 +659,10 @@ def compute_field_psf(lbda, seeing, GL, L0, positions=None, npsflin=1, h=(100, 1
         if e.code == E_GRID:
             raise ValueError(str(e)) from None
         raise
-    cols = _field_columns(lbda, pos, fit, pixscale)
+    if circular:
+        cols = _field_columns(lbda, pos, fit, pixscale)
+    else:
+        cols = _field_columns(lbda, pos, ctx.fit_stamps_elliptical(psf), pixscale, _fit_columns_ell)
     n = len(pos) * nl
     cols['SEEING'] = np.full(n, seeing)
     cols['GL'] = np.full(n, GL)
@@ -625,7 +672,7 @@ def compute_field_psf(lbda, seeing, GL, L0, positions=None, npsflin=1, h=(100, 1
 
 def compute_profile_psf(lbda, seeing, L0, cn2, h, wind_speed=12.5, wind_dir=None, GL=None, npsflin=1, positions=None,
                         three_lgs_mode=False, verbose=True, *, dim=1280, dimpsf=40, pixscale=0.2, precision='mixed',
-                        cutoff_masks='host', device=0):
+                        cutoff_masks='host', device=0, circular=True):
     """compute_psf / compute_field_psf for a Cn2 profile instead of the fixed two-layer atmosphere.
 
     ``cn2``, ``h``, ``wind_speed``, ``wind_dir``: the layers' weights (normalised here, psfrec.py:57-58), altitudes
@@ -637,7 +684,10 @@ def compute_profile_psf(lbda, seeing, L0, cn2, h, wind_speed=12.5, wind_dir=None
 
     positions=None: ``(table, psf)`` as compute_psf (the npsflin directions averaged, psf (nl, dimpsf, dimpsf));
     else (npos, 2) arcsec: as compute_field_psf (psf (npos, nl, dimpsf, dimpsf), table with dir_idx, x, y).
+    circular=False: the fit columns are those of an elliptical Moffat fitted to ``psf`` (fit_psf_cube(...,
+    circular=False)); ``psf`` is the same.
     Every refusal is a ValueError, raised before any GPU context exists."""
+    circular = _check_circular(circular)
     lbda = np.atleast_1d(np.asarray(lbda, dtype=float))
     if lbda.ndim != 1 or lbda.size < 1 or not np.all(np.isfinite(lbda)) or np.any(lbda <= 0):
         raise ValueError('lbda must be a non-empty 1-D array of positive wavelengths (nm)')
@@ -683,7 +733,8 @@ def compute_profile_psf(lbda, seeing, L0, cn2, h, wind_speed=12.5, wind_dir=None
         if pos is None:
             r = ctx.reconstruct_profile(*args, npsflin=npsflin, masks=masks, want_sum=False)
             psf, fit = r['psf'][0], r['fit'][0]
-            cols = _fit_columns(lbda, fit, pixscale)
+            cols = (_fit_columns(lbda, fit, pixscale) if circular else
+                    _fit_columns_ell(lbda, ctx.fit_stamps_elliptical(psf), pixscale))
         else:
             psf = np.empty((len(pos), nl, dimpsf, dimpsf))
             fit = np.empty((len(pos), nl, _lib.NFIT))
@@ -691,7 +742,8 @@ def compute_profile_psf(lbda, seeing, L0, cn2, h, wind_speed=12.5, wind_dir=None
                 r = ctx.reconstruct_profile(*args, npsflin=0, positions=pos[a:b], masks=masks, want_sum=False)
                 psf[a:b] = r['psf'][0]
                 fit[a:b] = r['fit'][0]
-            cols = _field_columns(lbda, pos, fit, pixscale)
+            cols = (_field_columns(lbda, pos, fit, pixscale) if circular else
+                    _field_columns(lbda, pos, ctx.fit_stamps_elliptical(psf), pixscale, _fit_columns_ell))
     except MpsfrError as e:
         if e.code == E_GRID:
             raise ValueError(str(e)) from None
