@@ -256,6 +256,38 @@ int mpsfr_simul_psd_profile(mpsfr_ctx* ctx, double seeing, double l0, int three_
                             const double* cn2, int npsflin, int npos, const double* pos_arcsec,
                             const uint8_t* mask_rec, const uint8_t* mask_res, double* psd_out);
 
+/* Band-integrated PSFs.  The PSF of a broadband image -- white light, a synthetic filter, a narrow band summed over a
+ * line -- is the spectrum-weighted mean of the monochromatic PSFs over the band,
+ *     PSF_band = int T(lambda) f(lambda) PSF_lambda dlambda / int T(lambda) f(lambda) dlambda,
+ * with T the throughput and f the source's f_lambda: not the PSF at the central wavelength.  The caller gives the
+ * quadrature weights of each band on the lbda_nm grid (e.g. band_weights in psfrec.py); the library reduces the
+ * per-wavelength stamps of every (row, position) on the GPU and fits only the band stamps.  The per-wavelength stamps
+ * never leave the device and no per-wavelength fit runs.
+ *
+ * nband, weights    : 1 <= nband <= MPSFR_MAX_BANDS bands, weights [nband][nl], finite and >= 0, each band with a
+ *                     positive sum.  Each band is normalised to sum 1 here: w_bl / sum_l w_bl = w^_bl (a power-of-two
+ *                     scale of a band's weights changes nothing, bit for bit).
+ * npos = 0          : the npsflin (1..5) directions, averaged:
+ *                       band_out [ntask][nband][dimpsf][dimpsf], band_sum_out [nband][dimpsf][dimpsf] (sum over the
+ *                       rows), band_fit_out [ntask][nband][MPSFR_NFIT]
+ * npos >= 1         : field positions pos_arcsec [npos][2] (rules of mpsfr_reconstruct_field), npsflin must be 0:
+ *                       each output gains an [npos] axis after the row axis, as in mpsfr_reconstruct_field
+ * Band stamp (t, b) is  sum_l w^_bl x  the stamp mpsfr_reconstruct / mpsfr_reconstruct_field returns for (t, l),
+ * summed in fp64 in wavelength order (the mixed mode reduces its float stamps).  A band that holds one wavelength at
+ * weight 1 is that stamp exactly.  band_fit_out is the Moffat fit of the band stamp, with the fields and status bits
+ * of MPSFR_NFIT.  The eps = prune_eps + tier_eps guarantee of mpsfr_set_option holds per band stamp: a convex
+ * combination of stamps that each meet it.  Every other argument, on_device 0 / 1 / 2 included (tickets, mpsfr_wait,
+ * mpsfr_sync, mpsfr_abandon, the staging ring), means what it means for mpsfr_reconstruct.  A bad nband, weight or
+ * npsflin / npos combination returns MPSFR_E_INVALID before anything is queued and touches nothing.
+ * Cn2 profiles (mpsfr_reconstruct_profile) with bands are not supported yet: a follow-up. */
+#define MPSFR_MAX_BANDS 16
+int mpsfr_reconstruct_band(mpsfr_ctx* ctx, int ntask, const double* seeing, const double* gl,
+                           const double* l0, const uint8_t* three_lgs, const double h[2], double wind_speed,
+                           int npsflin, int npos, const double* pos_arcsec,
+                           int nl, const double* lbda_nm, int nband, const double* weights,
+                           const uint8_t* mask_rec, const uint8_t* mask_res,
+                           double* band_out, double* band_sum_out, double* band_fit_out, int on_device);
+
 /* The same over several devices: the reference's  Parallel(n_jobs=...)  fans the rows out over
  * worker processes (psfrec.py:1082-1083); here the rows go in contiguous, balanced shards (the
  * first ntask % nctx contexts take one row more) to `nctx` contexts -- normally one per device,

@@ -6,12 +6,14 @@ simul_psd_wfm, psf_muse, convolve_final_psf,
 psd_to_psf and its helpers pupil_mask, crop, interpolate, seeing2r01.
 Beyond the reference: compute_field_psf (one PSF per field position) and the PSF_FIELD / FIT_FIELD HDUs of
 compute_psf_from_sparta(..., field_positions=...); compute_profile_psf (a Cn2 profile of up to 8 layers with
-per-layer wind, averaged or at field positions).
+per-layer wind, averaged or at field positions); compute_band_psf and band_weights (band-integrated PSFs of broadband
+images) and the FIT_BAND_ROWS / PSF_BAND / FIT_BAND HDUs of compute_psf_from_sparta(..., bands=...).
 Low level: Context (ctypes binding of libmpsfr.so).
 """
 from ._lib import Context, ContextPool, MpsfrError, NFIT, NFIT_ELL, FIT_ILL_CONDITIONED  # noqa: F401
 from .synthetic import synthetic_rows, grid_pixscale  # noqa: F401
 from .psfrec import (MAX_L0, MIN_L0, compute_psf, compute_field_psf, compute_profile_psf,  # noqa: F401
+                     band_weights, compute_band_psf,
                      compute_psf_from_sparta,
                      create_sparta_table, direction_perf, fit_psf_cube, fit_psf_with_polynom,
                      host_cutoff_masks, muse_intrinsic_psf, plot_psf, radial_profile,

@@ -75,6 +75,9 @@ def load():
     lib.mpsfr_simul_psd_profile.argtypes = [p, C.c_double, C.c_double, C.c_int, C.c_int, dp, dp, dp, dp, C.c_int,
                                             C.c_int, dp, u8p, u8p, dp]
     lib.mpsfr_simul_psd_profile.restype = C.c_int
+    lib.mpsfr_reconstruct_band.argtypes = [p, C.c_int, dp, dp, dp, u8p, dp, C.c_double, C.c_int, C.c_int, dp,
+                                           C.c_int, dp, C.c_int, dp, u8p, u8p, p, p, p, C.c_int]
+    lib.mpsfr_reconstruct_band.restype = C.c_int
     lib.mpsfr_reconstruct_multi.argtypes = [C.POINTER(p), C.c_int, C.c_int, dp, dp, dp, u8p, dp, C.c_double,
                                             C.c_int, C.c_int, dp, u8p, u8p, p, p, p]
     lib.mpsfr_reconstruct_multi.restype = C.c_int
@@ -133,7 +136,7 @@ def load():
 
 
 EXPORTS = ['mpsfr_create', 'mpsfr_destroy', 'mpsfr_last_error', 'mpsfr_set_option',
-           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
+           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
            'mpsfr_psd_to_psf',
            'mpsfr_convolve_stamps', 'mpsfr_fit_rows', 'mpsfr_sync', 'mpsfr_last_ticket', 'mpsfr_wait', 'mpsfr_abandon',
            'mpsfr_stream', 'mpsfr_stream_wait', 'mpsfr_wait_event',
@@ -222,6 +225,30 @@ def profile_weights(cn2, nrow, nlayer):
         raise ValueError('Cn2 weights must be finite and >= 0')
     if np.any(w.sum(axis=1) <= 0):
         raise ValueError('every row of Cn2 weights needs a positive sum')
+    return np.ascontiguousarray(w)
+
+
+MAX_BANDS = 16               # MPSFR_MAX_BANDS
+
+
+def band_weight_matrix(weights, nl):
+    """Validated (nband, nl) float64 C-contiguous band weights (one band may be given 1-D): 1..MAX_BANDS bands,
+    finite, >= 0, each band with a positive sum.  Raises ValueError otherwise -- the refusals of
+    mpsfr_reconstruct_band."""
+    try:
+        w = np.array(weights, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('band weights must be numeric') from None
+    if w.ndim == 1:
+        w = w[None, :]
+    if w.ndim != 2 or w.shape[1] != nl:
+        raise ValueError('band weights must be (nband, %d), got shape %s' % (nl, np.shape(weights)))
+    if not 1 <= w.shape[0] <= MAX_BANDS:
+        raise ValueError('1 to %d bands per call, got %d' % (MAX_BANDS, w.shape[0]))
+    if not np.all(np.isfinite(w)) or np.any(w < 0):
+        raise ValueError('band weights must be finite and >= 0')
+    if np.any(w.sum(axis=1) <= 0):
+        raise ValueError('every band needs a positive sum of weights')
     return np.ascontiguousarray(w)
 
 
@@ -394,6 +421,69 @@ class Context:
             self._h, seeing.size, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), _dptr(hh),
             float(wind_speed), pos.shape[0], _dptr(pos), lbda.size, _dptr(lbda), _u8ptr(mrec), _u8ptr(mres),
             C.c_void_p(psf_ptr), C.c_void_p(sum_ptr), C.c_void_p(fit_ptr), 1))
+
+    def reconstruct_band_async(self, *args, **kwargs):
+        """`reconstruct_band` without waiting for the GPU (on_device = 2): returns a PendingResult."""
+        return self.reconstruct_band(*args, _async=True, **kwargs)
+
+    def _band_inputs(self, lbda, weights, seeing, gl, l0, three_lgs, h, wind_speed, npsflin, positions, masks):
+        seeing, gl, l0, lbda, three, hh, wind_speed, mrec, mres = self._inputs(lbda, seeing, gl, l0, three_lgs, h,
+                                                                              wind_speed, masks)
+        w = band_weight_matrix(weights, lbda.size)
+        if positions is None:
+            npsflin = 1 if npsflin is None else npsflin
+            if isinstance(npsflin, bool) or not isinstance(npsflin, (int, np.integer)) or not 1 <= npsflin <= 5:
+                raise ValueError('npsflin must be an integer between 1 and 5')
+            pos = None
+        else:
+            if npsflin not in (0, None):
+                raise ValueError('a call with positions takes npsflin = 0')
+            pos = field_positions(positions)
+            npsflin = 0
+        return seeing, gl, l0, lbda, three, hh, wind_speed, mrec, mres, w, pos, npsflin
+
+    def reconstruct_band(self, lbda, weights, seeing, gl, l0, three_lgs=None, h=(100, 10000), wind_speed=None,
+                         npsflin=None, positions=None, masks=None, want_psf=True, want_sum=True, want_fit=True,
+                         _async=False):
+        """Band-integrated host-buffer call (mpsfr_reconstruct_band): the stamps reduced over wavelength with
+        `weights` ((nband, nl), each band normalised to sum 1 by the library; see band_weights in psfrec.py) and the
+        Moffat fit of every band stamp.  positions=None: the npsflin directions averaged (npsflin None means 1),
+        dict(psf (nt, nband, 40, 40), psf_sum (nband, 40, 40), fit (nt, nband, NFIT)); else (npos, 2) arcsec, each
+        output gaining an npos axis after the row axis, with npsflin left at None (or 0): a call with positions
+        evaluates no npsflin grid."""
+        seeing, gl, l0, lbda, three, hh, wind_speed, mrec, mres, w, pos, npsflin = self._band_inputs(
+            lbda, weights, seeing, gl, l0, three_lgs, h, wind_speed, npsflin, positions, masks)
+        nt, nb, n = seeing.size, w.shape[0], self.dimpsf
+        lead = (nt,) if pos is None else (nt, pos.shape[0])
+        psf = np.empty(lead + (nb, n, n)) if want_psf else None
+        psum = np.empty(lead[1:] + (nb, n, n)) if want_sum else None
+        fit = np.empty(lead + (nb, NFIT)) if want_fit else None
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        npos = 0 if pos is None else pos.shape[0]
+        _check(self.lib.mpsfr_reconstruct_band(
+            self._h, nt, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), _dptr(hh), float(wind_speed),
+            0 if npos else int(npsflin), npos, None if pos is None else _dptr(pos), lbda.size, _dptr(lbda), nb,
+            _dptr(w), _u8ptr(mrec), _u8ptr(mres), vp(psf), vp(psum), vp(fit), 2 if _async else 0))
+        arrays = dict(psf=psf, psf_sum=psum, fit=fit)
+        if _async:
+            ticket = int(self.lib.mpsfr_last_ticket(self._h))
+            self._pending[ticket] = arrays
+            self._handed_over(ticket - 4)
+            return PendingResult(self, ticket, arrays)
+        return arrays
+
+    def reconstruct_band_device(self, lbda, weights, seeing, gl, l0, three_lgs, h, wind_speed, npsflin, positions,
+                                masks, psf_ptr, sum_ptr, fit_ptr):
+        """Device-buffer band call (asynchronous, on_device = 1): outputs are raw device pointers (int or None) on
+        this context's GPU, shaped as in reconstruct_band."""
+        seeing, gl, l0, lbda, three, hh, wind_speed, mrec, mres, w, pos, npsflin = self._band_inputs(
+            lbda, weights, seeing, gl, l0, three_lgs, h, wind_speed, npsflin, positions, masks)
+        npos = 0 if pos is None else pos.shape[0]
+        _check(self.lib.mpsfr_reconstruct_band(
+            self._h, seeing.size, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), _dptr(hh), float(wind_speed),
+            0 if npos else int(npsflin), npos, None if pos is None else _dptr(pos), lbda.size, _dptr(lbda),
+            w.shape[0], _dptr(w), _u8ptr(mrec), _u8ptr(mres), C.c_void_p(psf_ptr), C.c_void_p(sum_ptr),
+            C.c_void_p(fit_ptr), 1))
 
     def reconstruct_profile_async(self, *args, **kwargs):
         """`reconstruct_profile` without waiting for the GPU (on_device = 2): returns a PendingResult."""

@@ -6,11 +6,19 @@ import io
 import logging
 import sys
 
+import numpy as np
+
 from . import __version__
 from . import _minifits
 from .psfrec import _astropy, compute_psf_from_sparta, create_sparta_table, direction_perf
 
 logger = logging.getLogger(__name__)
+
+
+def band_grid(bands, step):
+    """The wavelength grid of --band: the union of arange(lo, hi, step) with hi included, over the (lo, hi) bands."""
+    nodes = [np.append(np.arange(lo, hi, step), hi) for lo, hi in bands]
+    return np.unique(np.round(np.concatenate(nodes), 9))
 RULE = '-' * 68
 
 
@@ -75,11 +83,27 @@ def main(args=None):
     add('--field', default=None, type=int, metavar='N',
         help='also reconstruct the PSF at the N x N positions of direction_perf(N) (1..5): HDUs PSF_FIELD and\n'
         'FIT_FIELD of the -o file')
+    add('--band', action='append', default=None, metavar='LO:HI',
+        help='also reconstruct the band-integrated PSF over LO..HI nm (flat f_lambda; repeatable): HDUs\n'
+        'FIT_BAND_ROWS, PSF_BAND and FIT_BAND of the -o file')
+    add('--band-step', default=5.0, type=float, metavar='NM',
+        help='wavelength step of the band grid (default 5 nm): the union of arange(LO, HI, step), HI included')
     add('--version', action='version', version='%(prog)s ' + __version__)
     opt = parser.parse_args(args)
 
     if opt.field is not None and not 1 <= opt.field <= 5:
         sys.exit('--field must be between 1 and 5')
+    bands = band_lbda = None
+    if opt.band:
+        try:
+            bands = [tuple(float(x) for x in b.split(':')) for b in opt.band]
+        except ValueError:
+            bands = [()]
+        if any(len(b) != 2 or not 0 < b[0] < b[1] for b in bands):
+            sys.exit('--band must be LO:HI in nm with 0 < LO < HI')
+        if not opt.band_step > 0:
+            sys.exit('--band-step must be > 0')
+        band_lbda = band_grid(bands, opt.band_step)
     _setup_logging(opt.verbose)
     logger.info('MUSE-PSFR version %s', __version__)
 
@@ -110,7 +134,8 @@ def main(args=None):
     logger.info('Computing PSF Reconstruction from Sparta data')
     res = compute_psf_from_sparta(source, lmin=500, lmax=900, nl=3, n_jobs=opt.njobs,
                                   plot=opt.plot, device=opt.device,
-                                  field_positions=None if opt.field is None else direction_perf(opt.field).T)
+                                  field_positions=None if opt.field is None else direction_perf(opt.field).T,
+                                  bands=bands, band_lbda=band_lbda)
     if not res:
         sys.exit('No results')
     data = res['FIT_MEAN'].data

@@ -280,6 +280,12 @@ void launch_stamp_sum(hipStream_t s, int ntask, int nl, const void* d_fin, bool 
                       int accumulate);
 // elliptical Moffat fit (fit_ell.hip): [nstamp][40][40] double stamps -> [nstamp][NFIT_ELL]
 void launch_fit_ell(hipStream_t s, int nstamp, const double* d_stamps, double* d_fit, bool f64);
+// band-integrated stamps (band.hip): d_fin [ntb][nl][40][40] (float if fin_f32, else double) reduced over wavelength
+// into d_out [ntb][nband][40][40] double with the weights d_w [nl][band_stride(nband)] (zero beyond nband)
+constexpr int MAX_BANDS = 16;    // MPSFR_MAX_BANDS
+int band_stride(int nband);      // the power of two >= nband the kernel is instantiated for
+void launch_band_reduce(hipStream_t s, int ntb, int nl, int nband, const void* d_fin, bool fin_f32,
+                        const double* d_w, double* d_out);
 // the call's parameter blob from pinned host memory into device memory, as a kernel of the call's own queue
 // (bytes: a multiple of 16); h_flag_pinned: a pinned host word that receives `seq` once the blob has been read
 void launch_param_copy(hipStream_t s, void* d_dst, const void* h_src_pinned, size_t bytes,

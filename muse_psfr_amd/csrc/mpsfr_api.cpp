@@ -128,6 +128,7 @@ struct mpsfr_ctx {
         DevBuf pP, pT, psp, dlin;        // series form of stage A: patch, its row transforms, its sum; line minima
         DevBuf squeue;                   // the block queue of K_DPHI_SERIES_Q (one int, zeroed by K_PATCH_ROWS)
         DevBuf thrf;                     // [tasks] floor of the kernel for several directions (K_PEAK_FLOOR)
+        DevBuf band;                     // [tasks][nband][40][40] band stamps of a band call (K_BAND_REDUCE)
         // device outputs of its most recent calls: `done` is recorded behind every call of the lane,
         // so waiting for it covers all of them (a caller that rotates more buffer sets than lanes
         // must still get the calls that share a buffer in order)
@@ -602,7 +603,7 @@ void mpsfr_destroy(mpsfr_ctx* c) {
         if (ln.stream) { (void)hipStreamSynchronize(ln.stream); (void)hipStreamDestroy(ln.stream); }
         if (ln.done) (void)hipEventDestroy(ln.done);
         DevBuf* lb[] = {&ln.C, &ln.s00, &ln.D0t, &ln.Tq, &ln.pre, &ln.fin, &ln.dmin, &ln.dblk, &ln.vkeep, &ln.dminb, &ln.order, &ln.mown, &ln.muni, &ln.msched, &ln.mpart,
-                         &ln.pP, &ln.pT, &ln.psp, &ln.dlin, &ln.thrf, &ln.squeue};
+                         &ln.pP, &ln.pT, &ln.psp, &ln.dlin, &ln.thrf, &ln.squeue, &ln.band};
         for (auto b : lb) release(*b);
     }
     for (int k = 0; k < mpsfr_ctx::NSTAGE; ++k) {
@@ -817,6 +818,10 @@ struct StageIO {
     // and the fixed wind directions) and the rows' weights cn2 [ntask][layers->n] (each row normalised here)
     const AoLayers* layers = nullptr;
     const double* cn2 = nullptr;
+    // mpsfr_reconstruct_band: each (task, position)'s stamps reduced over wavelength with the weights bw [nband][nl]
+    // (every band normalised to sum 1); psf_out, psf_sum_out and fit_out hold nband planes in place of nl
+    int nband = 0;
+    const double* bw = nullptr;
 };
 
 static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const double* gl,
@@ -879,6 +884,49 @@ int mpsfr_reconstruct_field(mpsfr_ctx* c, int ntask, const double* seeing, const
     io.pos = pos_arcsec;
     return guarded_call(c, ntask, seeing, gl, l0, three_lgs, h, wind_speed, 1, nl, lbda_nm, mask_rec, mask_res,
                         psf_out, psf_sum_out, fit_out, on_device, io);
+}
+
+static_assert(MAX_BANDS == MPSFR_MAX_BANDS, "K_BAND_REDUCE keeps MPSFR_MAX_BANDS accumulators");
+
+int mpsfr_reconstruct_band(mpsfr_ctx* c, int ntask, const double* seeing, const double* gl, const double* l0,
+                           const uint8_t* three_lgs, const double h[2], double wind_speed, int npsflin, int npos,
+                           const double* pos_arcsec, int nl, const double* lbda_nm, int nband, const double* weights,
+                           const uint8_t* mask_rec, const uint8_t* mask_res, double* band_out, double* band_sum_out,
+                           double* band_fit_out, int on_device) {
+    if (!c) return fail(MPSFR_E_INVALID, "ctx is NULL");
+    if (nband < 1 || nband > MPSFR_MAX_BANDS) return fail(MPSFR_E_INVALID, "nband=%d out of range 1..%d", nband, MPSFR_MAX_BANDS);
+    if (nl < 1 || nl > 4096) return fail(MPSFR_E_INVALID, "nl=%d out of range", nl);
+    if (!weights) return fail(MPSFR_E_INVALID, "weights is NULL");
+    // every band normalised to sum 1 (a power-of-two scale of a band's weights leaves them bit for bit as they are)
+    std::vector<double> w((size_t)nband * nl);
+    for (int b = 0; b < nband; ++b) {
+        const double* r = weights + (size_t)b * nl;
+        double sum = 0.0;
+        for (int l = 0; l < nl; ++l) {
+            if (!std::isfinite(r[l]) || r[l] < 0.0) return fail(MPSFR_E_INVALID, "band %d: weight %d must be finite and >= 0", b, l);
+            sum += r[l];
+        }
+        if (!(sum > 0.0) || !std::isfinite(sum)) return fail(MPSFR_E_INVALID, "band %d: the weights sum to %g", b, sum);
+        for (int l = 0; l < nl; ++l) w[(size_t)b * nl + l] = r[l] / sum;
+    }
+    StageIO io;
+    io.nband = nband;
+    io.bw = w.data();
+    if (npos < 0 || npos > 25) return fail(MPSFR_E_INVALID, "npos=%d out of range 0..25", npos);
+    if (npos > 0) {
+        if (npsflin != 0) return fail(MPSFR_E_INVALID, "a field call (npos >= 1) takes npsflin = 0");
+        if (!pos_arcsec) return fail(MPSFR_E_INVALID, "pos_arcsec is NULL");
+        for (int k = 0; k < 2 * npos; ++k)
+            if (!std::isfinite(pos_arcsec[k]) || std::fabs(pos_arcsec[k]) > 60.0)
+                return fail(MPSFR_E_INVALID, "position %d: need finite |x|, |y| <= 60 arcsec", k / 2);
+        io.npos = npos;
+        io.pos = pos_arcsec;
+        npsflin = 1;
+    } else if (npsflin < 1 || npsflin > 5) {
+        return fail(MPSFR_E_INVALID, "npsflin=%d out of range 1..5", npsflin);
+    }
+    return guarded_call(c, ntask, seeing, gl, l0, three_lgs, h, wind_speed, npsflin, nl, lbda_nm, mask_rec, mask_res,
+                        band_out, band_sum_out, band_fit_out, on_device, io);
 }
 
 static_assert(MAXLAYER == MPSFR_MAX_LAYERS, "AoLayers holds MPSFR_MAX_LAYERS layers");
@@ -1024,6 +1072,10 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
     // task g / npos at position g % npos, and every stage-B kernel sees tc x npos one-direction tasks)
     const int N = c->N, H1 = N / 2 + 1, ndir = field ? io.npos : npsflin * npsflin;
     const int gpp = field ? ndir : 1, ndb = field ? 1 : ndir;
+    // a band call: nout = nband output planes per stamp group (else the nl wavelengths)
+    const bool band = io.nband > 0;
+    if (band && (staged || !io.bw || io.nband > MAX_BANDS)) return fail(MPSFR_E_INVALID, "bad band request");
+    const int nout = band ? io.nband : nl;
     HIPCHK(hipSetDevice(c->device));
     int rc;
 
@@ -1129,9 +1181,9 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
         tk->u_psf = psf_out;
         tk->u_sum = psf_sum_out;
         tk->u_fit = fit_out;
-        tk->n_psf = psf_out ? (size_t)ntask * gpp * nl * NS * NS : 0;
-        tk->n_sum = psf_sum_out ? (size_t)gpp * nl * NS * NS : 0;
-        tk->n_fit = fit_out ? (size_t)ntask * gpp * nl * NFIT : 0;
+        tk->n_psf = psf_out ? (size_t)ntask * gpp * nout * NS * NS : 0;
+        tk->n_sum = psf_sum_out ? (size_t)gpp * nout * NS * NS : 0;
+        tk->n_fit = fit_out ? (size_t)ntask * gpp * nout * NFIT : 0;
         const size_t hb = (tk->n_psf + tk->n_sum + tk->n_fit) * sizeof(double);
         if (hb > tk->host_cap) {
             if (tk->host) HIPCHK(hipHostFree(tk->host));
@@ -1163,7 +1215,7 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
         // stamps, "enough to fill the GPU": a 125-row call then ran as 118 + 7 rows and reached 9.8 M
         // PSFs/s where one chunk reaches 14.6 M; 250 rows 11.3 -> 15.3 M, 1000 rows 14.5 -> 15.1 M.)
         // (stamps per task: gpp x nl)
-        const int spt = gpp * nl;
+        const int spt = gpp * nl + (band ? gpp * nout : 0);    // (a band call: its band stamps too)
         int big = 65536 / spt;
         const int soft = (4096 + spt - 1) / spt < 8 ? 8 : (4096 + spt - 1) / spt;
         if (big > 512) big = 512;
@@ -1286,7 +1338,10 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
     const bool want_perm = c->stage_a_queue != 0 && series;
     const size_t o_perm = al16(o_ms + (send_masks ? NAO * NAO : 0));
     const size_t o_w = al16(o_perm + (want_perm ? (size_t)ntask * ndir * sizeof(int) : 0));    // profile weights
-    const size_t blob = al16(o_w + wts.size() * sizeof(double));
+    // (a band call: its weights [nl][band_stride(nband)], zero beyond nband)
+    const int bstride = band ? band_stride(nout) : 0;
+    const size_t o_bw = al16(o_w + wts.size() * sizeof(double));
+    const size_t blob = al16(o_bw + (size_t)nl * bstride * sizeof(double));
     mpsfr_ctx::Slot& sl = c->slot[c->stage_next++ % mpsfr_ctx::NSTAGE];
     double t_blocked = 0.0;
     if (sl.staged_pending) {        // the copy that last used the pinned blob must have left it
@@ -1339,6 +1394,11 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
     memcpy(hb + o_gam, gam.data(), gam.size() * sizeof(double));
     memcpy(hb + o_alp, alp.data(), alp.size() * sizeof(double));
     if (ly) memcpy(hb + o_w, wts.data(), wts.size() * sizeof(double));
+    if (band) {
+        double* bw = reinterpret_cast<double*>(hb + o_bw);
+        for (int l = 0; l < nl; ++l)
+            for (int b = 0; b < bstride; ++b) bw[(size_t)l * bstride + b] = b < nout ? io.bw[(size_t)b * nl + l] : 0.0;
+    }
     if (want_perm) {
         // K_DPHI_SERIES_Q deals the lines of a y in this order (indices relative to the chunk): tasks by descending
         // (L0 / r0)^(5/3) x (weight of the high layer) -- the residual a ground-layer correction leaves -- so that the
@@ -1466,6 +1526,7 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
     const double* d_gam = (const double*)(db + o_gam);
     const double* d_alp = (const double*)(db + o_alp);
     const double* d_w = ly ? (const double*)(db + o_w) : nullptr;
+    const double* d_bw = band ? (const double*)(db + o_bw) : nullptr;
     auto mix_of = [&](int t0) {
         LayerMix m;
         m.w = ly ? d_w + (size_t)t0 * ntab : nullptr;
@@ -1579,6 +1640,8 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
         mpsfr_ctx::Lane& ln = lane_of(j);
         if ((rc = ensure(c, ln.pre, (size_t)TB * nl * per_stamp * (c->f64 ? 8 : 4)))) return rc;
         if ((rc = ensure(c, ln.fin, (size_t)TB * nl * per_stamp * sizeof(double)))) return rc;
+        if (band && !(dev_out && psf_out) && (rc = ensure(c, ln.band, (size_t)TB * nout * per_stamp * sizeof(double))))
+            return rc;
         if (io.pre_in) continue;            // convolutions only: no workspace of stages A and B
         if (series) {
             if ((rc = ensure(c, ln.pP, (size_t)TC * ndir * NAO * NAO * sizeof(double)))) return rc;
@@ -1615,16 +1678,17 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
         }
     }
     // (the sums run over the tasks of [task][gpp x nl] stamps: a field call sums into [npos][nl])
-    const int nsum = gpp * nl;
+    // (a band call sums and fits its band stamps: [task][gpp x nband])
+    const int nsum = gpp * nout;
     if (NL > 1 && (rc = ensure(c, c->lsum, (size_t)NL * nsum * per_stamp * sizeof(double)))) return rc;
     if ((rc = ensure(c, c->sum, (size_t)nsum * per_stamp * sizeof(double)))) return rc;
     double* d_fin_all = nullptr;   // [ntask][nl][1600] if the caller gave a device buffer
     double* d_fit_all = nullptr;
-    if (dev_out && psf_out) d_fin_all = psf_out;
+    if (dev_out && psf_out && !band) d_fin_all = psf_out;
     if (dev_out && fit_out) {
         d_fit_all = fit_out;
     } else {
-        if ((rc = ensure(c, c->fit, (size_t)ntask * gpp * nl * NFIT * sizeof(double)))) return rc;
+        if ((rc = ensure(c, c->fit, (size_t)ntask * gpp * nout * NFIT * sizeof(double)))) return rc;
         d_fit_all = (double*)c->fit.p;
     }
     const double cfit = fit_constant();
@@ -1835,7 +1899,9 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
         }
         // final stamps: straight into the caller's device buffer (double), else a lane workspace --
         // float when the FFT convolution produces them and nobody outside reads them
-        const bool fin_f32 = use_fft_conv && !c->f64 && !d_fin_all && !(psf_out && !dev_out);
+        // (a band call keeps its per-wavelength stamps in the lane: float in mixed mode)
+        const bool fin_f32 = band ? (use_fft_conv && !c->f64)
+                                  : (use_fft_conv && !c->f64 && !d_fin_all && !(psf_out && !dev_out));
         void* d_fin = d_fin_all ? (void*)(d_fin_all + (size_t)t0 * nsum * per_stamp) : ln.fin.p;
         {
             ProfScope ps(c, K_CONV, ls);
@@ -1849,19 +1915,30 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
                 launch_conv(ls, tb, nl, ln.pre.p, (const char*)sl.ktt.p + koff,
                             c->kmuse.p, (double*)d_fin, c->f64, gpp);
         }
+        // a band call: the chunk's stamps reduced over wavelength (timed as the stamp sum); what follows -- fit, sum,
+        // copies -- then reads the double band stamps
+        void* d_res = d_fin;
+        bool res_f32 = fin_f32;
+        if (band) {
+            ProfScope ps(c, K_STAMP_SUM, ls);
+            double* d_band = (dev_out && psf_out) ? psf_out + (size_t)t0 * nsum * per_stamp : (double*)ln.band.p;
+            launch_band_reduce(ls, tb, nl, nout, d_fin, fin_f32, d_bw, d_band);
+            d_res = d_band;
+            res_f32 = false;
+        }
         // per-lane partial stamp sums in chunk order; combined below in lane order (deterministic)
         double* lsum = NL > 1 ? (double*)c->lsum.p + (size_t)j * nsum * per_stamp : d_sum;
         if (fit_out) {             // (with the chunk's stamp sum as the first workgroups of the same launch)
             ProfScope ps(c, K_FIT, ls);
-            launch_fit(ls, tb * nl, d_fin, fin_f32, d_fit_all + (size_t)t0 * nsum * NFIT, c->f64,
+            launch_fit(ls, tb * nout, d_res, res_f32, d_fit_all + (size_t)t0 * nsum * NFIT, c->f64,
                        psf_sum_out ? tc : 0, nsum, psf_sum_out ? lsum : nullptr, nchunk_lane[j] > 0 ? 1 : 0);
         } else if (psf_sum_out) {
             ProfScope ps(c, K_STAMP_SUM, ls);
-            launch_stamp_sum(ls, tc, nsum, d_fin, fin_f32, lsum, nchunk_lane[j] > 0 ? 1 : 0);
+            launch_stamp_sum(ls, tc, nsum, d_res, res_f32, lsum, nchunk_lane[j] > 0 ? 1 : 0);
         }
         HIPCHK(hipGetLastError());
         if (!dev_out && psf_out) {
-            HIPCHK(hipMemcpyAsync(psf_out + (size_t)t0 * nsum * per_stamp, d_fin,
+            HIPCHK(hipMemcpyAsync(psf_out + (size_t)t0 * nsum * per_stamp, d_res,
                                   (size_t)tc * nsum * per_stamp * sizeof(double),
                                   hipMemcpyDeviceToHost, ls));
         }

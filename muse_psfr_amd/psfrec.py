@@ -670,6 +670,229 @@ def compute_field_psf(lbda, seeing, GL, L0, positions=None, npsflin=1, h=(100, 1
     return _make_table(cols, {'SEEING': seeing, 'GL': GL, 'L0': L0}), psf
 
 
+def _hat_integrals(lb, tfun, breaks):
+    """w_l = int phi_l(x) T(x) dx over the grid lb, with phi_l the hat function of node l (1 at lb[l], 0 at its
+    neighbours) and T linear between consecutive `breaks` (its own nodes, where it may also jump).  Each piece between
+    two consecutive points of lb + breaks is integrated exactly (Simpson on a product of two linear functions); T is
+    evaluated inside the piece only, so a jump at a break is one-sided on either side."""
+    inner = np.asarray(breaks, dtype=float)
+    pts = np.union1d(lb, inner[(inner > lb[0]) & (inner < lb[-1])])
+    a, b = pts[:-1], pts[1:]
+    k = np.searchsorted(lb, a, side='right') - 1          # the grid interval of each piece
+    d = lb[k + 1] - lb[k]
+    t1, t2 = tfun(a + (b - a) / 3), tfun(a + 2 * (b - a) / 3)
+    ta, tb, tm = 2 * t1 - t2, 2 * t2 - t1, (t1 + t2) / 2
+    ua, ub = (a - lb[k]) / d, (b - lb[k]) / d             # the hat of node k + 1 on the piece
+    h = (b - a) / 6
+    right = h * (ua * ta + 2 * (ua + ub) * tm + ub * tb)
+    total = h * (ta + 4 * tm + tb)
+    w = np.zeros(lb.size)
+    np.add.at(w, k, total - right)
+    np.add.at(w, k + 1, right)
+    return w
+
+
+def _curve(pair, what):
+    """(wave_nm, values) of a throughput curve or an SED: 1-D, equal lengths >= 2, finite, wave strictly increasing,
+    values >= 0."""
+    try:
+        x = np.asarray(pair[0], dtype=float)
+        y = np.asarray(pair[1], dtype=float)
+    except (TypeError, ValueError, IndexError):
+        raise ValueError('%s must be a (wave_nm, values) pair of arrays' % what) from None
+    if x.ndim != 1 or y.shape != x.shape or x.size < 2:
+        raise ValueError('%s must be two 1-D arrays of equal length >= 2' % what)
+    if not (np.all(np.isfinite(x)) and np.all(np.isfinite(y))):
+        raise ValueError('%s must be finite' % what)
+    if np.any(np.diff(x) <= 0):
+        raise ValueError('the wavelengths of %s must be strictly increasing' % what)
+    if np.any(y < 0):
+        raise ValueError('%s must not be negative' % what)
+    return x, y
+
+
+def band_weights(lbda, bands, sed=None):
+    """Quadrature weights (nband, nl) of band-integrated PSFs on the wavelength grid ``lbda`` (nm, strictly
+    increasing, at least two nodes).  Normalised per band (as the library does), they give the PSF of a cube in
+    f_lambda units integrated over the band, int T f PSF dlambda / int T f dlambda, with T_b the throughput of band b
+    and f the source's f_lambda:
+
+        w_bl = f(lbda_l) int T_b(lambda) phi_l(lambda) dlambda
+
+    where phi_l is the hat function of node l (1 at lbda_l, falling linearly to 0 at its neighbours): the integral of
+    T_b times the PSF interpolated linearly between the grid's wavelengths, evaluated exactly.  Only where a band has
+    throughput does it give weight: a grid interval outside the band (a gap between two bands on a union grid, say)
+    contributes nothing.  Where T_b is constant over the intervals round a node this is the trapezoid rule D_l T_b(lbda_l)
+    (D_l the trapezoid weights of the grid): a top-hat over the whole grid gives exactly the trapezoid weights, and a
+    top-hat whose edges lie on nodes gives the trapezoid weights of the band's own nodes (its edge nodes half an
+    interval).  An edge between two nodes shares its interval between them linearly, so lbda_min / lbda_max (the nodes
+    with weight) may then lie just outside (lo, hi).
+
+    ``bands``: a sequence of bands (or one band), each either a top-hat ``(lo, hi)`` in nm (T = 1 on [lo, hi]) or a
+    curve ``(wave_nm, throughput)`` (linear interpolation, zero outside its range).  ``sed``: None (a flat f_lambda) or
+    ``(wave_nm, f_lambda)``, linearly interpolated; it must cover every grid node where a band has weight.
+    Raises ValueError for a grid that is not strictly increasing, a band without weight on the grid, negative values
+    and an SED that does not cover a band."""
+    lb = np.atleast_1d(np.asarray(lbda, dtype=float))
+    if lb.ndim != 1 or lb.size < 2 or not np.all(np.isfinite(lb)) or np.any(lb <= 0):
+        raise ValueError('lbda must be a 1-D array of at least two positive wavelengths (nm)')
+    if np.any(np.diff(lb) <= 0):
+        raise ValueError('lbda must be strictly increasing')
+    if isinstance(bands, (str, bytes)):
+        raise ValueError('bands must be (lo, hi) pairs or (wave_nm, throughput) curves')
+    try:
+        bands = list(bands)
+    except TypeError:
+        raise ValueError('bands must be (lo, hi) pairs or (wave_nm, throughput) curves') from None
+    if len(bands) == 2 and all(np.ndim(b) == 0 for b in bands):
+        bands = [tuple(bands)]                       # (one top-hat)
+    if not bands:
+        raise ValueError('need at least one band')
+    rows = []
+    for k, b in enumerate(bands):
+        try:
+            ok = len(b) == 2
+        except TypeError:
+            ok = False
+        if not ok:
+            raise ValueError('band %d must be (lo, hi) or (wave_nm, throughput)' % k)
+        if np.ndim(b[0]) == 0 and np.ndim(b[1]) == 0:
+            try:
+                lo, hi = float(b[0]), float(b[1])
+            except (TypeError, ValueError):
+                raise ValueError('band %d: (lo, hi) must be numbers' % k) from None
+            if not (np.isfinite(lo) and np.isfinite(hi) and 0 <= lo < hi):
+                raise ValueError('band %d: need finite 0 <= lo < hi, got (%g, %g)' % (k, lo, hi))
+            rows.append(_hat_integrals(lb, lambda v, lo=lo, hi=hi: ((v >= lo) & (v <= hi)).astype(float), [lo, hi]))
+        else:
+            x, y = _curve(b, 'band %d' % k)
+            rows.append(_hat_integrals(lb, lambda v, x=x, y=y: np.interp(v, x, y, left=0.0, right=0.0), x))
+    w = np.array(rows)
+    if sed is not None:
+        x, f = _curve(sed, 'sed')
+        for k in range(len(w)):
+            nodes = lb[w[k] > 0]
+            if nodes.size and (nodes[0] < x[0] or nodes[-1] > x[-1]):
+                raise ValueError('sed does not cover band %d (%g..%g nm)' % (k, nodes[0], nodes[-1]))
+        w = w * np.interp(lb, x, f)[None, :]
+    for k in range(len(w)):
+        if not w[k].sum() > 0:
+            raise ValueError('band %d has no weight on the wavelength grid' % k)
+    return w
+
+
+def _band_columns(lbda, w):
+    """lbda_eff (sum of the normalised weights x lbda), lbda_min / lbda_max (of the nodes with weight) per band."""
+    w = np.asarray(w, dtype=float)
+    lbda = np.asarray(lbda, dtype=float)
+    wn = w / w.sum(axis=1, keepdims=True)
+    eff = wn @ lbda
+    lo = np.array([lbda[r > 0].min() for r in w])
+    hi = np.array([lbda[r > 0].max() for r in w])
+    return eff, lo, hi
+
+
+def _band_table_columns(lbda, w, fit, pixscale, circular, pos=None):
+    """Columns of a band fit table from fit rows ((npos,) nband, NFIT or NFIT_ELL): rows ordered (position,) band;
+    band (0-based), (dir_idx, x, y,) lbda_eff, lbda_min, lbda_max, then the fit columns of compute_psf (or of
+    fit_psf_cube(circular=False)) without lbda."""
+    eff, lo, hi = _band_columns(lbda, w)
+    nb = len(eff)
+    npos = 1 if pos is None else len(pos)
+    fit = np.asarray(fit).reshape(npos * nb, -1)
+    fc = (_fit_columns if circular else _fit_columns_ell)(np.tile(eff, npos), fit, pixscale)
+    cols = OrderedDict()
+    cols['band'] = np.tile(np.arange(nb), npos)
+    if pos is not None:
+        pos = np.asarray(pos, dtype=float)
+        cols['dir_idx'] = np.repeat(np.arange(npos), nb)
+        cols['x'] = np.repeat(pos[:, 0], nb)
+        cols['y'] = np.repeat(pos[:, 1], nb)
+    cols['lbda_eff'] = np.tile(eff, npos)
+    cols['lbda_min'] = np.tile(lo, npos)
+    cols['lbda_max'] = np.tile(hi, npos)
+    for k, v in fc.items():
+        if k != 'lbda':
+            cols[k] = v
+    return cols
+
+
+def _band_groups(nband):
+    m = _lib.MAX_BANDS
+    return [(a, min(a + m, nband)) for a in range(0, nband, m)]
+
+
+def compute_band_psf(lbda, seeing, GL, L0, bands, sed=None, npsflin=1, positions=None, h=(100, 10000),
+                     three_lgs_mode=False, verbose=True, *, dim=1280, dimpsf=40, pixscale=0.2, precision='mixed',
+                     cutoff_masks='host', device=0, circular=True):
+    """Band-integrated form of compute_psf: the PSF of a broadband image, the spectrum-weighted mean of the
+    monochromatic PSFs over each band (band_weights(lbda, bands, sed) on the grid ``lbda``), reduced and fitted on the
+    GPU -- not the PSF at the band's central wavelength.
+
+    positions=None: the npsflin directions averaged, ``psf`` (nband, dimpsf, dimpsf); else (npos, 2) arcsec as in
+    compute_field_psf, ``psf`` (npos, nband, dimpsf, dimpsf).  Returns ``(table, psf)``; the table has one row per
+    (position,) band with the columns band (0-based), (dir_idx, x, y,) lbda_eff (the weighted mean wavelength),
+    lbda_min, lbda_max (the band's nodes with weight), the fit columns of compute_psf and SEEING, GL, L0.
+    circular=False: the fit columns are those of an elliptical Moffat fitted to ``psf`` (fit_psf_cube(...,
+    circular=False)); ``psf`` is the same.  Every refusal is a ValueError, raised before any GPU context exists."""
+    circular = _check_circular(circular)
+    lbda = np.atleast_1d(np.asarray(lbda, dtype=float))
+    w = band_weights(lbda, bands, sed)
+    try:
+        seeing, GL, L0 = float(seeing), float(GL), float(L0)
+    except (TypeError, ValueError):
+        raise ValueError('seeing, GL and L0 must be scalars') from None
+    if not (seeing > 0 and L0 > 0 and 0 <= GL <= 1):
+        raise ValueError('need seeing > 0, L0 > 0 and 0 <= GL <= 1')
+    if np.asarray(h).size != 2:
+        raise ValueError('exactly two layers are supported (psfrec.py:66)')
+    if precision not in ('mixed', 'f64'):
+        raise ValueError("precision must be 'mixed' or 'f64'")
+    if positions is None:
+        if isinstance(npsflin, bool) or not isinstance(npsflin, (int, np.integer)) or not 1 <= npsflin <= 5:
+            raise ValueError('npsflin must be an integer between 1 and 5')
+        pos = None
+    else:
+        pos = _lib.field_positions(positions, max_n=None)
+    masks = _resolve_masks(cutoff_masks)
+    if verbose:
+        logger.info('Compute band PSF for %d band(s) with seeing=%.2f GL=%.2f L0=%.2f', len(w), seeing, GL, L0)
+        if three_lgs_mode:
+            logger.info('Using three lasers mode')
+    ctx = get_context(dim, pixscale, dimpsf, precision, device)
+    nb = len(w)
+    npos = 1 if pos is None else len(pos)
+    psf = np.empty((npos, nb, dimpsf, dimpsf))
+    fit = np.empty((npos, nb, _lib.NFIT))
+    rows = ([seeing], [GL], [L0], [1 if three_lgs_mode else 0], h)
+    try:
+        for ba, bb in _band_groups(nb):
+            a_ = (lbda, w[ba:bb]) + rows
+            if pos is None:
+                r = ctx.reconstruct_band(*a_, npsflin=npsflin, masks=masks, want_sum=False)
+                psf[0, ba:bb] = r['psf'][0]
+                fit[0, ba:bb] = r['fit'][0]
+            else:
+                for a, b in _field_groups(npos):
+                    r = ctx.reconstruct_band(*a_, npsflin=0, positions=pos[a:b], masks=masks, want_sum=False)
+                    psf[a:b, ba:bb] = r['psf'][0]
+                    fit[a:b, ba:bb] = r['fit'][0]
+    except MpsfrError as e:
+        if e.code == E_GRID:
+            raise ValueError(str(e)) from None
+        raise
+    if not circular:
+        fit = ctx.fit_stamps_elliptical(psf).reshape(npos, nb, -1)
+    cols = _band_table_columns(lbda, w, fit, pixscale, circular, pos)
+    n = len(cols['band'])
+    cols['SEEING'] = np.full(n, seeing)
+    cols['GL'] = np.full(n, GL)
+    cols['L0'] = np.full(n, L0)
+    if pos is None:
+        psf = psf[0]
+    return _make_table(cols, {'SEEING': seeing, 'GL': GL, 'L0': L0}), psf
+
+
 def compute_profile_psf(lbda, seeing, L0, cn2, h, wind_speed=12.5, wind_dir=None, GL=None, npsflin=1, positions=None,
                         three_lgs_mode=False, verbose=True, *, dim=1280, dimpsf=40, pixscale=0.2, precision='mixed',
                         cutoff_masks='host', device=0, circular=True):
@@ -790,6 +1013,45 @@ def _field_sum(lbda, stats, three, pos, h, dim, dimpsf, pixscale, precision, cut
     return total
 
 
+def _band_rows(lbda, w, stats, three, npsflin, h, dim, dimpsf, pixscale, precision, cutoff_masks, devs):
+    """Band fits of every row (ntask, nband, NFIT) and the sum of the band stamps over the rows (nband, dimpsf,
+    dimpsf): the rows in contiguous balanced shards over `devs` (as _field_sum deals them), the bands in groups of at
+    most MAX_BANDS, every (shard, group) an asynchronous band call without stamps; the shards' sums are added in
+    device order."""
+    ntask, nb = len(stats), len(w)
+    masks = _resolve_masks(cutoff_masks)
+    nctx = len(devs) if ntask >= len(devs) else 1
+    bounds = [0]
+    for k in range(nctx):
+        bounds.append(bounds[-1] + ntask // nctx + (1 if k < ntask % nctx else 0))
+    replica = [devs[:i].count(d) for i, d in enumerate(devs)]
+    ctxs = [get_context(dim, pixscale, dimpsf, precision, d, r) for d, r in zip(devs[:nctx], replica[:nctx])]
+    see, gl, l0 = (np.ascontiguousarray(stats[:, k], dtype=float) for k in range(3))
+    t3 = np.asarray(three).astype(np.uint8)
+    pend = []
+    try:
+        for k, ctx in enumerate(ctxs):
+            a, b = bounds[k], bounds[k + 1]
+            pend.append([ctx.reconstruct_band_async(lbda, w[p:q], see[a:b], gl[a:b], l0[a:b], t3[a:b], h,
+                                                    npsflin=npsflin, masks=masks, want_psf=False)
+                         for p, q in _band_groups(nb)])
+        fit = np.empty((ntask, nb, _lib.NFIT))
+        total = np.empty((nb, dimpsf, dimpsf))
+        for k, parts in enumerate(pend):
+            a, b = bounds[k], bounds[k + 1]
+            for (p, q), part in zip(_band_groups(nb), parts):
+                r = part.wait()
+                fit[a:b, p:q] = r['fit']
+                total[p:q] = r['psf_sum'] if k == 0 else total[p:q] + r['psf_sum']
+    except BaseException as e:
+        for ctx in ctxs:
+            ctx.abandon()
+        if isinstance(e, MpsfrError) and e.code == E_GRID:
+            raise ValueError(str(e)) from None
+        raise
+    return fit, total
+
+
 def _table_hdu(cols, meta, name):
     fits, ATable = _astropy()
     if fits is not None:
@@ -808,7 +1070,7 @@ def compute_psf_from_sparta(filename, extname='SPARTA_ATM_DATA', npsflin=1, lmin
                             nl=35, lbda=None, h=(100, 10000), n_jobs=-1, plot=False,
                             mean_of_lgs=True, verbose=True, *, dim=1280, dimpsf=40, pixscale=0.2,
                             precision='mixed', cutoff_masks='host', device=None, devices=None,
-                            field_positions=None):
+                            field_positions=None, bands=None, band_sed=None, band_lbda=None):
     """Reconstruct a PSF from SPARTA data (psfrec.py:981-1120).
 
     ``filename`` is a FITS path or an already opened HDUList.  Returns an HDUList with
@@ -824,7 +1086,20 @@ def compute_psf_from_sparta(filename, extname='SPARTA_ATM_DATA', npsflin=1, lmin
     ``field_positions``: None (the output above), ``'grid'`` (direction_perf(npsflin)) or an (n, 2) array of
     (x, y) in arcsec: then two HDUs follow PSF_MEAN -- PSF_FIELD, the (npos, nl, dimpsf, dimpsf) mean over the
     rows of the stamps at each position (compute_field_psf), and FIT_FIELD, the Moffat fit of each of them with
-    dir_idx, x, y and lbda columns (meta: the median SEEING, GL, L0, like FIT_MEAN)."""
+    dir_idx, x, y and lbda columns (meta: the median SEEING, GL, L0, like FIT_MEAN).
+
+    ``bands`` (with ``band_sed``, see band_weights; ``band_lbda``: the wavelength grid of the bands, by default
+    ``lbda``): three more HDUs follow -- FIT_BAND_ROWS, the Moffat fit of each row's band PSF (rows ordered (row,
+    band), row_idx / lgs_idx as in FIT_ROWS), PSF_BAND, the (nband, dimpsf, dimpsf) mean over the rows of the band
+    PSFs, and FIT_BAND, the fit of each PSF_BAND stamp (as FIT_MEAN is that of PSF_MEAN).  The rows use the devices
+    of FIT_ROWS."""
+    bw = blbda = None
+    if bands is not None:
+        blbda = band_lbda if band_lbda is not None else (lbda if lbda is not None else np.linspace(lmin, lmax, nl))
+        blbda = np.atleast_1d(np.asarray(blbda, dtype=float))
+        bw = band_weights(blbda, bands, band_sed)
+    elif band_sed is not None or band_lbda is not None:
+        raise ValueError('band_sed and band_lbda need bands')
     if field_positions is None:
         fpos = None
     elif isinstance(field_positions, str):
@@ -955,6 +1230,30 @@ def compute_psf_from_sparta(filename, extname='SPARTA_ATM_DATA', npsflin=1, lmin
         ffit = ctx.fit_stamps(psf_field.reshape(-1, dimpsf, dimpsf))
         out.append(_table_hdu(_field_columns(lbda, fpos, ffit, pixscale),
                               {'SEEING': float(seeing), 'GL': float(GL), 'L0': float(L0)}, 'FIT_FIELD'))
+
+    if bw is not None:
+        devs = r.get('devices', [device or 0])
+        bfit, bsum = _band_rows(blbda, bw, stats, three, npsflin, h, dim, dimpsf, pixscale, precision, cutoff_masks,
+                                devs)
+        nb = len(bw)
+        eff, lo, hi = _band_columns(blbda, bw)
+        rcols = OrderedDict(band=np.tile(np.arange(nb), ntask), lbda_eff=np.tile(eff, ntask),
+                            lbda_min=np.tile(lo, ntask), lbda_max=np.tile(hi, ntask))
+        rcols.update((k, v) for k, v in _fit_columns(np.tile(eff, ntask), bfit.reshape(ntask * nb, -1),
+                                                     pixscale).items() if k != 'lbda')
+        rcols['SEEING'] = np.repeat(stats[:, 0], nb)
+        rcols['GL'] = np.repeat(stats[:, 1], nb)
+        rcols['L0'] = np.repeat(stats[:, 2], nb)
+        rcols['row_idx'] = np.repeat(np.arange(1, ntask + 1), nb)
+        rcols['lgs_idx'] = np.repeat(np.asarray(laser_idx), nb)
+        out.append(_table_hdu(rcols, {}, 'FIT_BAND_ROWS'))
+        psf_band = bsum / ntask
+        if fits is not None and isinstance(out, fits.HDUList):
+            out.append(fits.ImageHDU(data=psf_band, name='PSF_BAND'))
+        else:
+            out.append(_minifits.ImageHDU(data=psf_band, name='PSF_BAND'))
+        out.append(_table_hdu(_band_table_columns(blbda, bw, ctx.fit_stamps(psf_band), pixscale, True),
+                              {'SEEING': float(seeing), 'GL': float(GL), 'L0': float(L0)}, 'FIT_BAND'))
 
     if plot:
         import matplotlib.pyplot as plt
