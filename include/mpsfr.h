@@ -130,7 +130,11 @@ const char* mpsfr_last_error(void);
  * convolution kernel adds up the partial tiles of the stamps the matrix-core kernel split into sweeps instead of
  * a kernel between the two -- measured, -1 %); "support_skip" (default 1: the series form of stage A neither
  * evaluates nor stores the structure function on the pieces of a line where the telescope OTF is identically zero
- * -- a fifth of the half plane; the buffer keeps the zero it was allocated with there).
+ * -- a fifth of the half plane).  Those pieces of the buffer ("dphi0") hold zero after such a call: the buffer is
+ * zeroed when it is allocated, and a series call clears it first when an earlier call on its lane wrote there (the
+ * full-size form of a call with an L0 below 7 m or with "stage_a" 0, a series call with "support_skip" 0,
+ * mpsfr_psf_from_psd) -- a result never depends on the calls before it.  mpsfr_debug_fetch("d0t_clears") counts
+ * those clears.
  * "stage_a_queue" (default 0; 1: the lines of stage A's series form dealt in blocks from a queue instead of equal
  * contiguous shares -- bit-identical, 13 % slower; 2: and the lines of a task on which a lower bound of the
  * structure function from the patch's row transforms puts the whole OTF line below the eps rule of "prune_eps", or
@@ -353,7 +357,10 @@ int mpsfr_fit_stamps_elliptical(mpsfr_ctx* ctx, int nstamp, const double* stamps
  *                      psfrec.py:151).  Arguments as for mpsfr_reconstruct.
  * mpsfr_psf_from_psd   psf_muse (psfrec.py:644-686): psd [ndir][dim][dim] as above -- ANY real image, not only
  *                      the model's: every row is transformed -- to psf_out [nl][dimpsf][dimpsf], the stamps
- *                      BEFORE the convolutions (mean over the ndir directions, normalised to sum 1).
+ *                      BEFORE the convolutions (mean over the ndir directions, normalised to sum 1).  A PSD with
+ *                      a NaN or an infinity is refused (MPSFR_E_INVALID) before anything is queued; a finite PSD
+ *                      so large that its transform overflows gives non-finite stamps, and leaves no trace in the
+ *                      calls after it.
  * mpsfr_convolve_stamps  convolve_final_psf (psfrec.py:874-930): psf_in [ntask][nl][dimpsf][dimpsf] convolved
  *                      with each task's tip-tilt Moffat kernel and the instrument's, into psf_out. */
 int mpsfr_simul_psd(mpsfr_ctx* ctx, double seeing, double gl, double l0, int three_lgs, const double h[2],
@@ -449,6 +456,8 @@ int mpsfr_host_time(mpsfr_ctx* ctx, double* seconds, long* calls);
  *                m-tiles with a second pass, tile steps without pruning, tile steps with all three
  *                products, tile steps without the low half of the OTF, blocks kept by at least one
  *                wavelength summed over the tasks, blocks inside the support of the telescope OTF x tasks
+ *   "d0t_clears" [1] times a call cleared a lane's "dphi0" buffer because of what an earlier call left there
+ *                (option "support_skip"), since the context was created
  * Returns the number of doubles written (<= capacity) or a negative error. */
 long mpsfr_debug_fetch(mpsfr_ctx* ctx, const char* what, double* out, size_t capacity);
 

@@ -129,6 +129,13 @@ struct mpsfr_ctx {
         DevBuf squeue;                   // the block queue of K_DPHI_SERIES_Q (one int, zeroed by K_PATCH_ROWS)
         DevBuf thrf;                     // [tasks] floor of the kernel for several directions (K_PEAK_FLOOR)
         DevBuf band;                     // [tasks][nband][40][40] band stamps of a band call (K_BAND_REDUCE)
+        // What D0t holds outside the part the series form of stage A writes (the pieces of a line outside the support
+        // of the telescope OTF, the 16 padding lines, the lines of tasks beyond the chunk): 0 = zero or values the
+        // series form left there itself; 1 = finite values of a call that wrote whole lines (the full-size form, the
+        // series form with "support_skip" off); 2 = anything, non-finite included (a caller's PSD, mpsfr_psf_from_psd).
+        // The next call that writes D0t clears the buffer first when it would otherwise read what is there: a series
+        // call with the support skip at 1 or 2, every call at 2 ("Call-order independence").
+        int d0t_stale = 0;
         // device outputs of its most recent calls: `done` is recorded behind every call of the lane,
         // so waiting for it covers all of them (a caller that rotates more buffer sets than lanes
         // must still get the calls that share a buffer in order)
@@ -214,6 +221,7 @@ struct mpsfr_ctx {
         double* user_sum = nullptr;
     } multi;
     long ticket_next = 0;                // id of the next asynchronous host-output call
+    long d0t_clears = 0;                 // lane D0t buffers cleared because of what an earlier call left (d0t_stale)
     double host_seconds = 0.0;           // wall time spent inside mpsfr_reconstruct
     long host_calls = 0;
     // caches of the per-call tables that only depend on (lbda) / (geometry, masks)
@@ -1659,7 +1667,10 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
             // there is always a finite number
             const size_t cap_before = ln.D0t.cap;       // (a reallocation may return the same address)
             if ((rc = ensure(c, ln.D0t, ((size_t)TC * ndir * H1 + 16) * N * rsize(c)))) return rc;
-            if (ln.D0t.cap != cap_before) HIPCHK(hipMemset(ln.D0t.p, 0, ln.D0t.cap));
+            if (ln.D0t.cap != cap_before) {
+                HIPCHK(hipMemset(ln.D0t.p, 0, ln.D0t.cap));
+                ln.d0t_stale = 0;
+            }
         }
         if (!mf && (rc = ensure(c, ln.Tq, (size_t)TB * nl * H1 * NSH * 2 * rsize(c)))) return rc;
         if (mf2) {
@@ -1738,6 +1749,18 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
         if (c->stagger_armed && lane_index != c->stagger_lane) {
             HIPCHK(hipStreamWaitEvent(ls, c->stagger_ev, 0));
             c->stagger_armed = false;
+        }
+        if (!io.pre_in) {
+            // what an earlier call left in D0t where this one does not write but reads (d0t_stale): cleared once, the
+            // whole buffer, on the lane's stream behind that call's readers.  A run of series calls never comes here.
+            const bool skip_form = series && c->support_skip;
+            if (ln.d0t_stale == 2 || (ln.d0t_stale == 1 && skip_form)) {
+                HIPCHK(hipMemsetAsync(ln.D0t.p, 0, ln.D0t.cap, ls));
+                ln.d0t_stale = 0;
+                ++c->d0t_clears;
+            }
+            if (io.psd_in) ln.d0t_stale = 2;
+            else if (!skip_form && ln.d0t_stale < 1) ln.d0t_stale = 1;
         }
         if (io.pre_in) {
             // convolve_final_psf on the caller's stamps: stages A and B are skipped
@@ -2179,6 +2202,10 @@ int mpsfr_psf_from_psd(mpsfr_ctx* c, int ndir, const double* psd, int nl, const 
     for (int k = 1; k <= 5; ++k)
         if (k * k == ndir) npl = k;
     if (npl == 0) return fail(MPSFR_E_INVALID, "ndir=%d is not the square of 1..5", ndir);
+    // (a NaN or an infinity would spread through the whole transform: refused before anything is queued)
+    const size_t npix = (size_t)ndir * c->N * c->N;
+    for (size_t i = 0; i < npix; ++i)
+        if (!std::isfinite(psd[i])) return fail(MPSFR_E_INVALID, "psd[%zu] is not finite", i);
     const double one = 1.0, half = 0.5, l0 = 20.0, h[2] = {100.0, 10000.0};
     StageIO io;
     io.psd_in = psd;
@@ -2460,6 +2487,10 @@ long mpsfr_debug_fetch(mpsfr_ctx* c, const char* what, double* out, size_t capac
         HIPCHK(hipMemcpy(tmp.data(), c->mfclk.p, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < n; ++i) out[i] = (double)tmp[i];
         return (long)n;
+    } else if (!strcmp(what, "d0t_clears")) {
+        if (capacity < 1) return fail(MPSFR_E_INVALID, "capacity %zu < 1", capacity);
+        out[0] = (double)c->d0t_clears;
+        return 1;
     } else if (!strcmp(what, "vkeep")) {
         if (!c->last_pruned || c->last_mf2)
             return fail(MPSFR_E_INVALID, "no line pruning in the last call (prune_eps = 0, or the block-masked "

@@ -1,0 +1,409 @@
+"""GPU: a call's result does not depend on what ran before it on the same context.
+
+One Context serves every entry point, and they all share the per-lane workspaces of mpsfr_api.cpp (D0t, dlin, pre,
+fin, band, mpart, ...; the audit is DESIGN.md "Call-order independence").  A *checked call* run right after a
+*predecessor* on the same context must equal the same call on a fresh context with the same options, bit for bit:
+stamps, stamp sums and fits.  The context runs the checked call once before the predecessor, as a user's context has,
+so that the predecessor writes into workspaces already sized for the checked call (a reallocation would zero them).  The first row of every checked call is also held to the oracle (the tolerances of
+tests/test_gpu_random.py), so that the two sides cannot share a bug.
+
+Predecessors (each run to completion, options restored afterwards):
+  P1 a row at L0 = 5 m (the full-size form of stage A writes the whole D0t half plane)
+  P2 stage_a = 0 (the full-size form by option); the other consumers of D0t and the FFT-free convolutions by
+     option (otf_mfma 0, mf_kernel 1, fft_conv 0), the series form without the support skip
+  P3 stage_a_queue = 2 (the 1e30 lines of the skipped lines)
+  P4 psf_from_psd on a finite PSD whose transform overflows (non-finite D in the whole plane)
+  P5 psf_from_psd on a PSD with a NaN pixel (refused before anything is queued)
+  P6 layout shifts: more tasks per chunk, other direction counts, and the reverse
+  P7 the other entry points: profile, field, band, convolve_stamps, the device elliptical fit, psd_to_psf
+"""
+import numpy as np
+import pytest
+
+import psfr_oracle as O
+from conftest import H, record_margin, rel_err
+
+pytestmark = pytest.mark.gpu
+
+LB = np.array([495.0, 690.0, 915.0])      # (>= 486 nm: the crop of the native 1280^2 grid)
+SEE = np.array([0.9, 1.1, 0.7])
+GL = np.array([0.6, 0.45, 0.8])
+L0 = np.array([22.0, 13.0, 27.0])          # (9-29 m, like the bench rows: the series form of stage A)
+THREE = np.array([0, 1, 0], np.uint8)
+POS = [(0.0, 0.0), (25.0, -15.0)]
+BANDS = [(LB[0], LB[-1]), (600.0, 800.0)]
+TOL = {'mixed': 2e-5, 'f64': 1e-9}
+
+# checked calls: name -> (dim, precision, options, kind, npsflin)
+CHECKED = {
+    'd512': (512, 'mixed', {}, 'psf', 1),
+    'd512_f64': (512, 'f64', {}, 'psf', 1),
+    'd512_rowfft': (512, 'mixed', {'otf_mfma': 0}, 'psf', 1),
+    'd512_mf1': (512, 'mixed', {'mf_kernel': 1}, 'psf', 1),
+    'd256_npl2': (256, 'mixed', {}, 'psf', 2),
+    'd256': (256, 'mixed', {}, 'psf', 1),        # (one direction at 256^2: the full-size form of stage A)
+    'd1280': (1280, 'mixed', {}, 'psf', 1),
+    'field512': (512, 'mixed', {}, 'field', 1),
+    'band512': (512, 'mixed', {}, 'band', 1),
+}
+
+
+@pytest.fixture(scope='module')
+def api():
+    import muse_psfr_amd
+    return muse_psfr_amd
+
+
+def _context(api, name):
+    dim, prec, opts, _, _ = CHECKED[name]
+    ctx = api.Context(dim=dim, pixscale=api.grid_pixscale(dim), precision=prec)
+    for k, v in opts.items():
+        ctx.set_option(k, v)
+    return ctx
+
+
+def _run(api, ctx, name, l0=L0, _async=False):
+    dim, prec, opts, kind, npl = CHECKED[name]
+    if kind == 'psf':
+        return ctx.reconstruct(LB, SEE, GL, l0, THREE, H, npsflin=npl, _async=_async)
+    if kind == 'field':
+        return ctx.reconstruct_field(LB, SEE, GL, l0, THREE, H, POS, _async=_async)
+    return ctx.reconstruct_band(LB, api.band_weights(LB, BANDS), SEE, GL, l0, THREE, H, _async=_async)
+
+
+def _same(a, b):
+    return all(a[k].shape == b[k].shape and np.array_equal(a[k], b[k]) for k in ('psf', 'psf_sum', 'fit'))
+
+
+def _diff(a, b):
+    return {k: (int(np.sum(a[k] != b[k])), int(np.sum(~np.isfinite(a[k])))) for k in ('psf', 'psf_sum', 'fit')}
+
+
+_FRESH = {}
+
+
+def _fresh(api, name):
+    """The checked call on a fresh context, its first row held to the oracle (once per module)."""
+    if name in _FRESH:
+        return _FRESH[name]
+    ctx = _context(api, name)
+    r = _run(api, ctx, name)
+    ctx.close()
+    dim, prec, _, kind, npl = CHECKED[name]
+    ps = api.grid_pixscale(dim)
+    tabs = O.ao_tables(H, bool(THREE[0]), npl, exact_masks=True)
+    ofit, ofin = O.compute_psf(LB, SEE[0], GL[0], L0[0], npl, H, bool(THREE[0]), dim=dim, pixscale=ps,
+                               tables=tabs, fit=kind == 'psf' and dim == 512)
+    if kind == 'psf':
+        got = r['psf'][0]
+    elif kind == 'field':
+        got = r['psf'][0, 0]                   # (the centre position is the npsflin = 1 direction)
+    else:
+        w = api.band_weights(LB, BANDS)
+        ofin = np.einsum('bl,lij->bij', w / w.sum(axis=1, keepdims=True), ofin)
+        got = r['psf'][0]
+    e = rel_err(got, ofin)
+    record_margin('call_history_vs_oracle', **{name: e})
+    assert e < TOL[prec], (name, e)
+    if ofit is not None:
+        well = ofit[:, 4] < 10
+        dfw = np.abs(r['fit'][0][:, 5] * ps - ofit[:, 3])[well].max(initial=0.0)
+        dbe = np.abs(r['fit'][0][:, 4] - ofit[:, 4])[well].max(initial=0.0)
+        assert dfw < 1e-4 and dbe < 1e-4, (name, dfw, dbe)
+    for k in ('psf', 'psf_sum', 'fit'):
+        assert np.all(np.isfinite(r[k])), (name, k)
+    _FRESH[name] = r
+    return r
+
+
+# ---- predecessors: fn(api, ctx, name), each restores the options it changed
+
+def _npl(name):
+    return CHECKED[name][4]
+
+
+def p1_short_l0(api, ctx, name):
+    ctx.reconstruct(LB, SEE, GL, np.array([22.0, 5.0, 27.0]), THREE, H, npsflin=_npl(name))
+
+
+def p2_stage_a0(api, ctx, name):
+    ctx.set_option('stage_a', 0)
+    try:
+        ctx.reconstruct(LB, SEE, GL, L0, THREE, H, npsflin=_npl(name))
+    finally:
+        ctx.set_option('stage_a', 1)
+
+
+def _with_option(key, value, default):
+    """A predecessor that runs the rows under another option (the per-wavelength tables it caches differ), then
+    sets the option back."""
+    def pred(api, ctx, name):
+        ctx.set_option(key, value)
+        try:
+            ctx.reconstruct(LB, SEE, GL, L0, THREE, H, npsflin=_npl(name))
+        finally:
+            ctx.set_option(key, default)
+    return pred
+
+
+def p3_queue2(api, ctx, name):
+    ctx.set_option('stage_a_queue', 2)
+    try:
+        ctx.reconstruct(LB, SEE, GL, L0, THREE, H, npsflin=_npl(name))
+    finally:
+        ctx.set_option('stage_a_queue', 0)
+
+
+def _overflowing_psd(ctx, name):
+    """A realistic PSD scaled until the sums of its transform overflow fp64: finite input, non-finite D."""
+    psd = ctx.simul_psd(0.9, 0.6, 22.0, npsflin=_npl(name))
+    psd = psd * (1.0e307 / psd.max())
+    assert np.all(np.isfinite(psd))
+    return psd
+
+
+def p4_overflow(api, ctx, name):
+    ctx.psf_from_psd(_overflowing_psd(ctx, name), LB)
+
+
+def p4_overflow_4dir(api, ctx, name):
+    """P4 with four directions: the non-finite plane reaches past the lines of a one-direction call, into what the
+    padding lines behind its D read (the full-size form at 256^2 reads them too)."""
+    psd = ctx.simul_psd(0.9, 0.6, 22.0, npsflin=2)
+    ctx.psf_from_psd(psd * (1.0e307 / psd.max()), LB)
+
+
+def p5_nan_pixel(api, ctx, name):
+    psd = ctx.simul_psd(0.9, 0.6, 22.0, npsflin=_npl(name))
+    psd[0, 3, 5] = np.nan
+    with pytest.raises(api.MpsfrError):
+        ctx.psf_from_psd(psd, LB)
+
+
+def p6_more_tasks(api, ctx, name):
+    n = 8
+    ctx.reconstruct(LB, np.full(n, 0.8), np.full(n, 0.5), np.full(n, 18.0), np.zeros(n, np.uint8), H,
+                    npsflin=_npl(name))
+
+
+def p6_chunk1(api, ctx, name):
+    ctx.set_option('chunk_tasks', 1)
+    try:
+        ctx.reconstruct(LB, SEE, GL, L0, THREE, H, npsflin=_npl(name))
+    finally:
+        ctx.set_option('chunk_tasks', 0)
+
+
+def p6_npsflin3(api, ctx, name):
+    ctx.reconstruct(LB, SEE[:2], GL[:2], L0[:2], THREE[:2], H, npsflin=3)
+
+
+def p6_npsflin3_full(api, ctx, name):
+    ctx.reconstruct(LB, SEE[:2], GL[:2], np.array([5.0, 20.0]), THREE[:2], H, npsflin=3)
+
+
+def p7_profile(api, ctx, name):
+    ctx.reconstruct_profile(LB, SEE, GL, L0, np.array([0.5, 0.3, 0.2]), np.array([0.0, 3000.0, 12000.0]),
+                            np.array([8.0, 15.0, 25.0]), np.array([0.3, 1.2, 2.5]), THREE)
+
+
+def p7_field(api, ctx, name):
+    ctx.reconstruct_field(LB, SEE, GL, L0, THREE, H, [(10.0, 10.0), (-20.0, 5.0), (0.0, -30.0)])
+
+
+def p7_band(api, ctx, name):
+    ctx.reconstruct_band(LB, api.band_weights(LB, [(500.0, 700.0)]), SEE, GL, L0, THREE, H, npsflin=2)
+
+
+def p7_convolve(api, ctx, name):
+    rng = np.random.default_rng(5)
+    ctx.convolve_stamps(LB, SEE, GL, L0, rng.uniform(0.0, 1.0e3, (SEE.size, LB.size, 40, 40)))
+
+
+def p7_fit_ell_device(api, ctx, name):
+    import torch
+    dev = torch.device('cuda:0')
+    rng = np.random.default_rng(6)
+    st = torch.tensor(rng.uniform(0.0, 1.0, (5, 40, 40)), dtype=torch.float64, device=dev)
+    fe = torch.empty((5, api.NFIT_ELL), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()
+    ctx.fit_stamps_elliptical_device(5, st.data_ptr(), fe.data_ptr())
+    ctx.sync()
+    torch.cuda.synchronize()
+
+
+def p7_psd_to_psf(api, ctx, name):
+    psd = ctx.simul_psd(0.9, 0.6, 22.0)
+    n = ctx.dim // 4
+    y, x = np.mgrid[:n, :n] - (n - 1) / 2
+    pup = (np.hypot(x, y) <= n / 2).astype(float)
+    ctx.psd_to_psf(psd, pup, 8.0, LB * 1e-9)
+
+
+PRED = {
+    'P1_l0_5m': p1_short_l0,
+    'P2_stage_a0': p2_stage_a0,
+    'P3_stage_a_queue2': p3_queue2,
+    'P2_otf_mfma0': _with_option('otf_mfma', 0, 1),
+    'P2_mf_kernel1': _with_option('mf_kernel', 1, 2),
+    'P2_fft_conv0': _with_option('fft_conv', 0, 1),
+    'P2_support_skip0': _with_option('support_skip', 0, 1),
+    'P4_psd_overflow': p4_overflow,
+    'P4_psd_overflow_4dir': p4_overflow_4dir,
+    'P5_psd_nan_pixel': p5_nan_pixel,
+    'P6_more_tasks_per_chunk': p6_more_tasks,
+    'P6_chunk_tasks_1': p6_chunk1,
+    'P6_npsflin3': p6_npsflin3,
+    'P6_npsflin3_full_size': p6_npsflin3_full,
+    'P7_profile': p7_profile,
+    'P7_field': p7_field,
+    'P7_band': p7_band,
+    'P7_convolve_stamps': p7_convolve,
+    'P7_fit_ell_device': p7_fit_ell_device,
+    'P7_psd_to_psf': p7_psd_to_psf,
+}
+
+CASES = ([(p, 'd512') for p in PRED]
+         + [(p, c) for p in ('P1_l0_5m', 'P4_psd_overflow') for c in CHECKED if c != 'd512']
+         + [('P4_psd_overflow_4dir', c) for c in ('d256', 'd512_f64')])
+
+
+@pytest.mark.parametrize('pred,checked', CASES)
+def test_checked_call_after_predecessor_equals_fresh(api, pred, checked):
+    want = _fresh(api, checked)
+    ctx = _context(api, checked)
+    _run(api, ctx, checked)
+    PRED[pred](api, ctx, checked)
+    got = _run(api, ctx, checked)
+    ctx.close()
+    assert _same(got, want), (pred, checked, _diff(got, want))
+
+
+def test_reverse_layout_shifts(api):
+    """A one-direction call first, then the wider layouts (and the direction count back)."""
+    ctx = _context(api, 'd512')
+    ctx.reconstruct(LB, SEE[:1], GL[:1], L0[:1], THREE[:1], H)
+    p6_npsflin3(api, ctx, 'd512')
+    ctx.reconstruct(LB, SEE[:1], GL[:1], L0[:1], THREE[:1], H)
+    p6_more_tasks(api, ctx, 'd512')
+    got = _run(api, ctx, 'd512')
+    ctx.close()
+    assert _same(got, _fresh(api, 'd512')), _diff(got, _fresh(api, 'd512'))
+
+
+@pytest.mark.parametrize('pred', ['P1_l0_5m', 'P4_psd_overflow'])
+def test_two_lanes_both_clean(api, pred):
+    """streams = 2: the predecessor on both lanes (P1 as two asynchronous calls; psf_from_psd is synchronous and
+    takes lane 0), then two asynchronous checked calls, one per lane."""
+    def run(with_pred):
+        ctx = _context(api, 'd512')
+        ctx.set_option('streams', 2)
+        [q.wait() for q in (_run(api, ctx, 'd512', _async=True), _run(api, ctx, 'd512', _async=True))]
+        if with_pred:
+            if pred == 'P1_l0_5m':
+                a = ctx.reconstruct_async(LB, SEE, GL, np.array([22.0, 5.0, 27.0]), THREE, H)
+                b = ctx.reconstruct_async(LB, SEE, GL, np.array([5.0, 13.0, 27.0]), THREE, H)
+                a.wait()
+                b.wait()
+            else:
+                p4_overflow(api, ctx, 'd512')
+        p = [_run(api, ctx, 'd512', _async=True), _run(api, ctx, 'd512', l0=L0[::-1].copy(), _async=True)]
+        out = [q.wait() for q in p]
+        ctx.close()
+        return out
+    want, got = run(False), run(True)
+    assert _same(want[0], _fresh(api, 'd512'))
+    for k in range(2):
+        assert _same(got[k], want[k]), (pred, k, _diff(got[k], want[k]))
+
+
+def test_dphi0_after_overflow_matches_fresh_and_header(api):
+    """debug_fetch('dphi0') after P4 and a series call equals the fresh context's plane, bit for bit; on the pieces of
+    a line that lie wholly outside the telescope OTF's support (the pieces the series form skips) it holds zero
+    (include/mpsfr.h, "support_skip")."""
+    dim = 512
+    n, h1 = SEE.size, dim // 2 + 1
+
+    def plane(with_pred):
+        ctx = _context(api, 'd512')
+        _run(api, ctx, 'd512')
+        if with_pred:
+            p4_overflow(api, ctx, 'd512')
+        _run(api, ctx, 'd512')
+        d = ctx.debug_fetch('dphi0', (n, h1, dim))
+        tel = ctx.debug_fetch('tel', (h1, dim))
+        ctx.close()
+        return d, tel
+    fresh, tel = plane(False)
+    after, _ = plane(True)
+    assert np.array_equal(after, fresh), int(np.sum(after != fresh))
+    L = 32                                   # (columns of a piece at 512^2: series_lanes in stage_a2.hip)
+    skipped = ~(tel.reshape(h1, dim // L, L) > 0).any(axis=2)
+    assert skipped.any()
+    pieces = after.reshape(n, h1, dim // L, L)
+    assert np.all(pieces[:, skipped] == 0.0)
+    assert np.all(np.isfinite(after))
+
+
+@pytest.mark.parametrize('bad', [np.nan, np.inf, -np.inf])
+def test_psf_from_psd_refuses_non_finite(api, bad):
+    ctx = _context(api, 'd512')
+    _run(api, ctx, 'd512')
+    psd = ctx.simul_psd(0.9, 0.6, 22.0)
+    psd[0, 100, 200] = bad
+    with pytest.raises(api.MpsfrError):
+        ctx.psf_from_psd(psd, LB)
+    # the refusal queued nothing: the context goes on as a fresh one
+    got = _run(api, ctx, 'd512')
+    ctx.close()
+    assert _same(got, _fresh(api, 'd512'))
+
+
+def _clears(ctx):
+    return int(ctx.debug_fetch('d0t_clears', (1,))[0])
+
+
+def test_clearing_path_only_after_a_writer(api):
+    """The steady path -- the bench workload: 100 rows x 35 wavelengths at 512^2, L0 in 9-29 m, device and
+    asynchronous calls on both lanes -- never clears D0t; a call that wrote outside the series form's part makes the
+    next series call on its lane clear it once; the 1e30 lines of stage_a_queue = 2 lie inside that part."""
+    import torch
+    ps = api.grid_pixscale(512)
+    see, gl, l0 = api.synthetic_rows(100)
+    three = np.zeros(100, np.uint8)
+    lb = np.linspace(465.0, 930.0, 35)
+    ctx = api.Context(dim=512, pixscale=ps, precision='mixed')
+    dev = torch.device('cuda:0')
+    psf = torch.empty((100, 35, 40, 40), dtype=torch.float64, device=dev)
+    psum = torch.empty((35, 40, 40), dtype=torch.float64, device=dev)
+    fit = torch.empty((100, 35, api.NFIT), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()
+    for _ in range(6):
+        ctx.reconstruct_device(lb, see, gl, l0, three, H, 12.0, 1, None, psf.data_ptr(), psum.data_ptr(),
+                               fit.data_ptr())
+    ctx.sync()
+    pend = [ctx.reconstruct_async(lb, see, gl, l0, three, H, want_psf=False) for _ in range(4)]
+    [p.wait() for p in pend]
+    ctx.reconstruct(lb, see, gl, l0, three, H, want_psf=False)
+    assert _clears(ctx) == 0
+    torch.cuda.synchronize()
+    ctx.close()
+
+    ctx = _context(api, 'd512')
+    _run(api, ctx, 'd512')
+    p3_queue2(api, ctx, 'd512')
+    _run(api, ctx, 'd512')
+    assert _clears(ctx) == 0
+    steps = [(p4_overflow, 1), (None, 1), (p1_short_l0, 2), (p2_stage_a0, 3), (None, 3)]
+    for pred, want in steps:
+        if pred is not None:
+            pred(api, ctx, 'd512')
+        got = _run(api, ctx, 'd512')
+        assert _same(got, _fresh(api, 'd512'))
+        assert _clears(ctx) == want, (pred, _clears(ctx), want)
+    ctx.set_option('support_skip', 0)
+    _run(api, ctx, 'd512')
+    ctx.set_option('support_skip', 1)
+    assert _same(_run(api, ctx, 'd512'), _fresh(api, 'd512'))
+    assert _clears(ctx) == 4
+    ctx.close()
