@@ -58,6 +58,14 @@ typedef struct mpsfr_ctx mpsfr_ctx;
  * the peak moves n by 1e-4 or more (the covariance is the one err_n comes from).  That is the case where the stamp
  * is narrower than the PSF core (the 128^2 / 256^2 grids with the rescaled pixel scale, seeing > 2 arcsec at 512^2);
  * on the 512^2 ... 1280^2 grids with the SPARTA range of inputs the number stays below 30.
+ * Rule of the circular fit for stamps without a Moffat in them (any data is accepted; nothing here is an error of the call): a row whose
+ * status & 3 is 0 holds finite numbers, lies inside the search domain (fwhm > 1e-3 px, n >= 1/90) and is the
+ * least-squares minimum.  Otherwise the row says so: 2 (singular) for an all-zero stamp, for a stamp with a NaN or
+ * an infinite pixel (the other fields are then the start values or NaN), for a brightest pixel outside the
+ * amplitude range of mpsfr_fit_stamps, and where the normal matrix cannot be factored; 1 (not converged) at the
+ * iteration cap and where the iteration ended with n < 1/90, against the bound n = 0.01 of the domain, as on a constant or an
+ * all-negative stamp, which have no maximum to fit.  A single hot pixel is a Moffat of vanishing width: it converges
+ * to fwhm = 1e-3 px with the ill-conditioned bit set.
  */
 #define MPSFR_FIT_ILL_CONDITIONED 4
 
@@ -156,7 +164,10 @@ int mpsfr_set_option(mpsfr_ctx* ctx, const char* key, double value);
  * i.e. of compute_psf (psfrec.py:933-978) = simul_psd_wfm (:36-151) -> psf_muse (:644-686) ->
  * convolve_final_psf (:874-930) -> fit_psf_cube (:861-871), for ntask (seeing, GL, L0) triples.
  *
- * seeing, gl, l0 : [ntask] arcsec @500 nm, ground-layer fraction, outer scale [m]
+ * seeing, gl, l0 : [ntask] arcsec @500 nm, ground-layer fraction, outer scale [m]; seeing > 0, L0 > 0, 0 <= GL <= 1.
+ *                  GL = 1 (no turbulence above the ground layer) makes the width of the residual tip-tilt kernel 0:
+ *                  the reference's Moffat2DKernel(0, 2) is NaN there; the library returns the limit GL -> 1, the
+ *                  identity kernel (in every entry point that takes GL, mpsfr_convolve_stamps included)
  * three_lgs      : [ntask] 0/1, three_lgs_mode of simul_psd_wfm (psfrec.py:86-91)
  * h              : layer altitudes [m] (psfrec.py:60); exactly two layers (psfrec.py:66 fixes two
  *                  wind directions)
@@ -326,7 +337,20 @@ int mpsfr_reconstruct_multi_async(mpsfr_ctx* const* ctxs, int nctx, int ntask, c
 int mpsfr_wait_multi(mpsfr_ctx* const* ctxs, int nctx);
 
 /* Replacement of fit_psf_cube (psfrec.py:861-871) on caller-provided stamps, e.g. the mean PSF
- * (psfrec.py:1105).  stamps: [nstamp][dimpsf][dimpsf] float64; fit_out: [nstamp][MPSFR_NFIT]. */
+ * (psfrec.py:1105).  stamps: [nstamp][dimpsf][dimpsf] float64; fit_out: [nstamp][MPSFR_NFIT].
+ * Amplitude range: the brightest pixel of a stamp must lie in [2^-40, 2^40] (9.1e-13 ... 1.1e12) in modulus; a stamp
+ * outside it is refused with status 2 (a caller with stamps in physical flux units scales them by a power of two,
+ * which is exact).  The iterations run in fp32 in both precision modes and their sums scale with the square of the
+ * peak I: the gradient terms of the wing pixels (I^2 2^-34 at the last steps) leave the normal range of fp32 below
+ * I = 2^-46 and the fit then stops short of the minimum; from I = 2^50 on the normal matrix overflows.  Inside the range:
+ *   [2^-20, 2^40]  a factor 2^k changes no bit of (fwhm, n, alpha, p0, q0, the other err_* columns, status,
+ *                  iterations), and peak, flux, err_peak scale by 2^k and chi2 by 4^k exactly;
+ *   [2^-40, 2^-20) the parameters and the status are right to the tolerances of the precision mode, but not bit for
+ *                  bit: the squared residuals of a nearly exact fit (I^2 2^-54 and less) are subnormal in fp32
+ *                  there, so chi2 and the err_* columns, which carry chi2 / dof, are not exact multiples.
+ * The circular fits inside mpsfr_reconstruct and its siblings follow the same rule (their stamps have sum 1: peaks of
+ * 1e-4 ... 1); the elliptical fit (mpsfr_fit_stamps_elliptical and the elliptical columns) is another kernel and does
+ * not. */
 int mpsfr_fit_stamps(mpsfr_ctx* ctx, int nstamp, const double* stamps, double* fit_out,
                      int on_device);
 

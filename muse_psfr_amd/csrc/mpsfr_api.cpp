@@ -400,7 +400,15 @@ double tiptilt_alpha(double seeing, double gl, double l0, double pixscale) {
     const double fwhm = std::sqrt(coeffHL * 0.97 * 6.88 * (a * a) * std::pow(8.0, -1.0 / 3.0) *
                                   std::pow(r0HL, -5.0 / 3.0)) /
                         (4.85 * 1.0e-6) * 2.35 / pixscale;
-    return fwhm / (2.0 * std::sqrt(std::pow(2.0, 1.0 / 2.0) - 1.0));
+    // GL = 1: no turbulence above the ground layer, seeingHL = 0, r0HL = inf, and the width is 0 -- the identity
+    // kernel, the limit GL -> 1 (the reference's Moffat2DKernel(0, 2) divides 0 by 0 at its centre and is NaN).  The
+    // kernels evaluate (1 + r^2 / gamma^2)^-2 in fp64, so they need no branch if gamma stays positive: with
+    // gamma = 1e-100, r^2 / gamma^2 >= 1e200 for r >= 1, its square overflows to +inf and the tap is exactly 0, and
+    // the centre is (1 + 0 / 1e-200)^-2 = 1.  Any width below 1e-78 does (then (r / gamma)^4 > DBL_MAX); 1e-100 keeps
+    // gamma^2 a normal number.  GL = 1 - 1e-12 gives gamma ~ 1e-8 px, taps of 1e-32: the floor is never felt below 1.
+    // (The floor masks no invalid input: std::max(NaN, floor) is NaN, and the argument check refuses GL > 1.)
+    constexpr double kTipTiltFloor = 1.0e-100;
+    return std::max(fwhm / (2.0 * std::sqrt(std::pow(2.0, 1.0 / 2.0) - 1.0)), kTipTiltFloor);
 }
 
 double polyval6(const double* p, double x) {

@@ -840,6 +840,17 @@ k_fit(int nstamp, const TS* __restrict__ stamps, double* __restrict__ fit, doubl
     // iteration count.
     const int p0i = besto / NS, q0i = besto % NS;
     const int rm = min(min(p0i, NS - 1 - p0i), min(q0i, NS - 1 - q0i));
+    // Amplitude range (include/mpsfr.h, mpsfr_fit_stamps).  The normal matrix, the gradient and chi2 of the float LM
+    // phase and of the polish scale with the square of the peak I.  The products J r of the wing pixels are about
+    // I^2 * 2^-7 (Jacobian) * 2^-27 (residual at the last polish steps of the f64 mode): below I = 2^-46 they leave
+    // the normal range of fp32 (2^-126), the gradient is lost and the iteration stops where it stands.  Upwards I^2
+    // times the sums of 1600 squares (<= 2^27 at the Gaussian end of the valley) overflows from I = 2^50.  A stamp
+    // whose brightest pixel lies outside [2^-40, 2^40] is refused (status 2) rather than fitted wrongly; zero, NaN
+    // and infinite brightest pixels fail the comparison too.  A power of two changes no bit of the results for
+    // I in [2^-20, 2^40]; below 2^-20 the terms r^2 of chi2 (I^2 2^-54 and less on a nearly exact fit) are subnormal:
+    // the parameters stay right to tolerance, chi2 and what is scaled by it are no longer exact multiples.
+    const float abest = fabsf((float)best);
+    const bool amp_ok = abest >= 0x1p-40f && abest <= 0x1p40f;
     int cnt = 0;
     const TS half = (TS)0.5 * best;
     float ms1 = 0.f, ms2 = 0.f;
@@ -901,11 +912,11 @@ k_fit(int nstamp, const TS* __restrict__ stamps, double* __restrict__ fit, doubl
     lm_accumulate<RE>(sp, lane, v, ne);
     S mu = (S)1.0e-2, nu = (S)2;
     const S mu_max = sizeof(RE) == 4 ? (S)1.0e15f : (S)1.0e15;
-    int it = 0, status = 1;
+    int it = 0, status = amp_ok ? 1 : 2;
 #ifndef MPSFR_FIT_MAXIT
 #define MPSFR_FIT_MAXIT 200
 #endif
-    const int maxit = MPSFR_FIT_MAXIT;
+    const int maxit = amp_ok ? MPSFR_FIT_MAXIT : 0;
     while (it < maxit) {
         ++it;
         S dx[5];
@@ -1042,6 +1053,16 @@ k_fit(int nstamp, const TS* __restrict__ stamps, double* __restrict__ fit, doubl
             for (int k = 0; k < 6; ++k) o[8 + k] = 0.0;
             if (status == 0) status = 2;
         }
+        // A row that reports convergence holds finite numbers and lies inside the search domain.  A NaN pixel
+        // enters the gradient and chi2 but not the normal matrix, so every step is NaN, is rejected, and the damping
+        // runs out as it does at a minimum: such a row is singular (2), not converged.  A stamp without a maximum
+        // (constant, all negative) sends the iteration to the bound eta = 100 (n = 0.01) of the domain, where no
+        // further step is taken: not converged (1) from eta > 90 on, i.e. n < 1/90.
+        bool finite_row = isfinite(chi2);
+#pragma unroll
+        for (int k = 0; k < 5; ++k) finite_row = finite_row && isfinite(vd[k]);
+        if ((status & 3) == 0 && !finite_row) status = (status & 4) | 2;
+        if ((status & 3) == 0 && vd[4] > 90.0) status = (status & 4) | 1;
         o[14] = (double)status;
         o[15] = vd[0] * kPi * al * al / (n - 1.0);
     }
