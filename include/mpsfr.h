@@ -372,6 +372,38 @@ int mpsfr_fit_stamps(mpsfr_ctx* ctx, int nstamp, const double* stamps, double* f
  *             19 flux = peak pi alpha_major alpha_minor / (n - 1)  20 err_flux  21..23 zero (reserved) */
 int mpsfr_fit_stamps_elliptical(mpsfr_ctx* ctx, int nstamp, const double* stamps, double* fit_out, int on_device);
 
+/* PSF energy metrics of caller-provided stamps: encircled and ensquared energy with exact pixel overlap, and the radii
+ * that hold given fractions of the flux -- the non-parametric description of a core + halo PSF, beside the Moffat fits.
+ * Pixel (p, q) is the unit square centred on (p, q), in the pixel coordinates of the fits (p0, q0).  Per stamp:
+ *   flux     the sum of the stamp;  peak, peak_p, peak_q: the brightest pixel (the first in row-major order on a tie);
+ *   centre   (cp, cq): centers[stamp] = (p, q) if `centers` is given, else the flux-weighted first moment of the stamp;
+ *   EE_k     = sum_pq A(p, q; cp, cq, r_k) I_pq / flux, A the exact area of pixel (p, q) inside the circle of radius
+ *            r_k about the centre (analytic circle-square overlap); a circle reaching beyond the stamp counts what is on
+ *            the stamp;
+ *   SQE_k    the same for the axis-aligned box of side s_k centred on the centre (overlap length in p times in q);
+ *   R_k      a radius with |EE(R_k) - f_k| <= 1e-12, found on the exact EE(r) between 0 and the distance to the farthest
+ *            pixel corner (unique where the stamp is non-negative).
+ * Arithmetic is fp64 in both precision modes: the call measures the stamp it is given.  A stamp's row depends on that
+ * stamp and the parameters only (bit for bit), not on the batch.
+ * stamps: [nstamp][dimpsf][dimpsf] float64; centers: [nstamp][2] or NULL; radii_px / boxes_px / fractions: nrad / nbox /
+ * nfrac values, each count 0..MPSFR_MAX_METRIC_RADII, always host pointers;
+ * out: [nstamp][MPSFR_NMET_HEAD + nrad + nbox + nfrac]:
+ *   0 flux  1 peak  2 peak_p  3 peak_q  4 cp  5 cq  6 status  7 zero (reserved), then the nrad EE values, the nbox
+ *   ensquared energies and the nfrac radii (pixels).
+ * status: 0; 1: an EE radius did not reach 1e-12 (possible on a stamp with negative pixels: the value is the last
+ * iterate); 2: the stamp has a non-finite pixel or flux <= 0 (an all-zero stamp included), or the centre is not finite
+ * or farther than 1e4 pixels from the origin -- every energy field is then NaN (the centroid too); the other stamps of
+ * the call are not affected.
+ * on_device as mpsfr_fit_stamps_elliptical: with 1, stamps, centers and out are device pointers and the call is queued
+ * on the context stream (e.g. behind a device-output reconstruct).  Refused with MPSFR_E_INVALID before anything is
+ * queued (out is not touched): a count outside 0..16 or all three zero, a radius or box side that is not finite and > 0
+ * or exceeds 2 dimpsf pixels, a fraction outside (0, 1), nstamp < 1.  Timed under the fit's profiling id. */
+#define MPSFR_MAX_METRIC_RADII 16      /* also the cap on boxes and on fractions */
+#define MPSFR_NMET_HEAD 8
+int mpsfr_stamp_metrics(mpsfr_ctx* ctx, int nstamp, const double* stamps, const double* centers, int nrad,
+                        const double* radii_px, int nbox, const double* boxes_px, int nfrac, const double* fractions,
+                        double* out, int on_device);
+
 /* The stages of the path as the reference exports them (muse_psfr/__init__.py:16: `from .psfrec import *`),
  * for a caller that holds its own PSD or its own stamps.  Host buffers, synchronous, float64; the same
  * kernels as mpsfr_reconstruct entered or left at another stage.

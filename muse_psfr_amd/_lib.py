@@ -11,6 +11,8 @@ LIB_PATH = os.environ.get('MPSFR_LIB_PATH') or os.path.join(HERE, 'libmpsfr.so')
 
 NFIT = 16
 NFIT_ELL = 24                # elliptical fit rows (MPSFR_NFIT_ELL, include/mpsfr.h)
+MAX_METRIC_RADII = 16        # radii, boxes, fractions of one metrics call (MPSFR_MAX_METRIC_RADII)
+NMET_HEAD = 8                # leading fields of a metrics row (MPSFR_NMET_HEAD)
 FIT_ILL_CONDITIONED = 4      # status bit of fit_out[14] (MPSFR_FIT_ILL_CONDITIONED, include/mpsfr.h)
 DIM_AO = 80
 PREC_MIXED, PREC_F64 = 0, 1
@@ -89,6 +91,8 @@ def load():
     lib.mpsfr_fit_stamps.restype = C.c_int
     lib.mpsfr_fit_stamps_elliptical.argtypes = [p, C.c_int, p, p, C.c_int]
     lib.mpsfr_fit_stamps_elliptical.restype = C.c_int
+    lib.mpsfr_stamp_metrics.argtypes = [p, C.c_int, p, p, C.c_int, dp, C.c_int, dp, C.c_int, dp, p, C.c_int]
+    lib.mpsfr_stamp_metrics.restype = C.c_int
     lib.mpsfr_simul_psd.argtypes = [p, C.c_double, C.c_double, C.c_double, C.c_int, dp, C.c_double, C.c_int, u8p, u8p, dp]
     lib.mpsfr_simul_psd.restype = C.c_int
     lib.mpsfr_psf_from_psd.argtypes = [p, C.c_int, dp, C.c_int, dp, dp]
@@ -136,7 +140,7 @@ def load():
 
 
 EXPORTS = ['mpsfr_create', 'mpsfr_destroy', 'mpsfr_last_error', 'mpsfr_set_option',
-           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
+           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_stamp_metrics', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
            'mpsfr_psd_to_psf',
            'mpsfr_convolve_stamps', 'mpsfr_fit_rows', 'mpsfr_sync', 'mpsfr_last_ticket', 'mpsfr_wait', 'mpsfr_abandon',
            'mpsfr_stream', 'mpsfr_stream_wait', 'mpsfr_wait_event',
@@ -779,6 +783,36 @@ class Context:
         _check(self.lib.mpsfr_fit_stamps_elliptical(self._h, int(nstamp), C.c_void_p(int(stamps_ptr)),
                                                     C.c_void_p(int(fit_ptr)), 1))
 
+    def stamp_metrics(self, stamps, radii_px, boxes_px, fractions, centers=None):
+        """PSF energy metrics (mpsfr_stamp_metrics) of stamps (..., dimpsf, dimpsf): (n, NMET_HEAD + nrad + nbox +
+        nfrac) rows -- flux, peak, peak_p, peak_q, cp, cq, status, 0, then the encircled energies at `radii_px`, the
+        ensquared energies in the boxes of side `boxes_px` and the radii holding `fractions` of the flux (pixels).
+        `centers`: (n, 2) (p, q) in pixels, or None for the centroid of each stamp."""
+        st = metric_stamps(stamps, self.dimpsf)
+        rad, box, frac = metric_parameters(radii_px, boxes_px, fractions, self.dimpsf)
+        ce = None if centers is None else metric_centers(centers, st.shape[0])
+        out = np.empty((st.shape[0], NMET_HEAD + rad.size + box.size + frac.size))
+        _check(self.lib.mpsfr_stamp_metrics(self._h, st.shape[0], st.ctypes.data_as(C.c_void_p),
+                                            None if ce is None else ce.ctypes.data_as(C.c_void_p),
+                                            rad.size, _dptr(rad), box.size, _dptr(box), frac.size, _dptr(frac),
+                                            out.ctypes.data_as(C.c_void_p), 0))
+        return out
+
+    def stamp_metrics_device(self, nstamp, stamps_ptr, out_ptr, radii_px, boxes_px, fractions, centers_ptr=None):
+        """Device-buffer metrics (asynchronous, on_device = 1): `stamps_ptr` ([nstamp][dimpsf][dimpsf] float64), `out_ptr`
+        ([nstamp][NMET_HEAD + nrad + nbox + nfrac] float64) and `centers_ptr` ([nstamp][2] float64, or None for the
+        centroids) are raw device pointers (int) on this context's GPU; the call is queued on the context stream,
+        after any device-output reconstruct of this context."""
+        if isinstance(nstamp, bool) or not isinstance(nstamp, (int, np.integer)) or nstamp < 1:
+            raise ValueError('nstamp must be a positive integer')
+        if not stamps_ptr or not out_ptr:
+            raise ValueError('stamps_ptr and out_ptr must be device pointers')
+        rad, box, frac = metric_parameters(radii_px, boxes_px, fractions, self.dimpsf)
+        _check(self.lib.mpsfr_stamp_metrics(self._h, int(nstamp), C.c_void_p(int(stamps_ptr)),
+                                            C.c_void_p(int(centers_ptr)) if centers_ptr else None,
+                                            rad.size, _dptr(rad), box.size, _dptr(box), frac.size, _dptr(frac),
+                                            C.c_void_p(int(out_ptr)), 1))
+
     def debug_fetch(self, what, shape):
         out = np.empty(int(np.prod(shape)))
         n = _check(self.lib.mpsfr_debug_fetch(self._h, what.encode(), _dptr(out), out.size))
@@ -816,6 +850,56 @@ def elliptical_stamps(stamps, dimpsf=40):
     if not np.all(np.isfinite(st)):
         raise ValueError('stamps must be finite')
     return np.ascontiguousarray(st).reshape(-1, dimpsf, dimpsf)
+
+
+def metric_stamps(stamps, dimpsf=40):
+    """Stamps for the metrics as a C-contiguous (n, dimpsf, dimpsf) float64 array; ValueError unless `stamps` is a
+    non-empty numeric array of shape (..., dimpsf, dimpsf).  (Non-finite pixels are the kernel's business: such a
+    stamp gets status 2.)"""
+    try:
+        st = np.asarray(getattr(stamps, 'data', stamps), dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('stamps must be a numeric array') from None
+    if st.ndim < 2 or st.shape[-2:] != (dimpsf, dimpsf) or st.size == 0:
+        raise ValueError('stamps must have the shape (..., %d, %d)' % (dimpsf, dimpsf))
+    return np.ascontiguousarray(st).reshape(-1, dimpsf, dimpsf)
+
+
+def metric_parameters(radii_px, boxes_px, fractions, dimpsf=40):
+    """The three parameter arrays of a metrics call (pixels, pixels, fractions) as contiguous float64, validated as
+    mpsfr_stamp_metrics validates them (ValueError): 0..MAX_METRIC_RADII of each and at least one in all, radii and
+    box sides finite, > 0 and <= 2 dimpsf, fractions in (0, 1)."""
+    res = []
+    for name, v in (('radii', radii_px), ('boxes', boxes_px), ('fractions', fractions)):
+        try:
+            a = np.atleast_1d(np.asarray(() if v is None else v, dtype=np.float64))
+        except (TypeError, ValueError):
+            raise ValueError('%s must be numbers' % name) from None
+        if a.ndim != 1 or a.size > MAX_METRIC_RADII:
+            raise ValueError('%s must be a 1-D sequence of at most %d values' % (name, MAX_METRIC_RADII))
+        res.append(np.ascontiguousarray(a))
+    rad, box, frac = res
+    if rad.size + box.size + frac.size == 0:
+        raise ValueError('need at least one radius, box or fraction')
+    for name, a in (('radii', rad), ('boxes', box)):
+        if not np.all(np.isfinite(a) & (a > 0) & (a <= 2 * dimpsf)):
+            raise ValueError('%s must be finite, > 0 and at most %d pixels' % (name, 2 * dimpsf))
+    if not np.all((frac > 0) & (frac < 1)):
+        raise ValueError('fractions must lie in (0, 1)')
+    return rad, box, frac
+
+
+def metric_centers(centers, n):
+    """(n, 2) centres (p, q) in pixels as contiguous float64; ValueError unless finite and of that shape."""
+    try:
+        ce = np.asarray(centers, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('centers must be an (n, 2) array of (p, q) in pixels') from None
+    if ce.shape != (n, 2):
+        raise ValueError('centers must have the shape (%d, 2): one (p, q) per stamp' % n)
+    if not np.all(np.isfinite(ce)) or np.any(np.abs(ce) > 1.0e4):
+        raise ValueError('centers must be finite (and within 1e4 pixels)')
+    return np.ascontiguousarray(ce)
 
 
 class PendingResult:

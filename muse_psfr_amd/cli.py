@@ -88,6 +88,9 @@ def main(args=None):
         'FIT_BAND_ROWS, PSF_BAND and FIT_BAND of the -o file')
     add('--band-step', default=5.0, type=float, metavar='NM',
         help='wavelength step of the band grid (default 5 nm): the union of arange(LO, HI, step), HI included')
+    add('--metrics', action='store_true',
+        help='also compute the encircled / ensquared energy of the mean PSFs (exact pixel overlap): HDUs METRICS_MEAN\n'
+        '(and METRICS_FIELD, METRICS_BAND) of the -o file, and the 0.2" ensquared energy and EE50 radius in the summary')
     add('--version', action='version', version='%(prog)s ' + __version__)
     opt = parser.parse_args(args)
 
@@ -135,7 +138,7 @@ def main(args=None):
     res = compute_psf_from_sparta(source, lmin=500, lmax=900, nl=3, n_jobs=opt.njobs,
                                   plot=opt.plot, device=opt.device,
                                   field_positions=None if opt.field is None else direction_perf(opt.field).T,
-                                  bands=bands, band_lbda=band_lbda)
+                                  bands=bands, band_lbda=band_lbda, metrics=True if opt.metrics else None)
     if not res:
         sys.exit('No results')
     data = res['FIT_MEAN'].data
@@ -148,6 +151,12 @@ def main(args=None):
             color = False
     text = _summary(header_line, hdr['SEEING'], hdr['GL'], hdr['L0'], data['lbda'] * 10,
                     data['fwhm'][:, 0], data['n'], color)
+    if opt.metrics:
+        # (the defaults of psf_metrics: boxes[0] = 0.2 arcsec, fractions[0] = 0.5)
+        met = res['METRICS_MEAN'].data
+        text += 'SQE0.2 %s\n' % ' '.join('%.3f' % v for v in np.asarray(met['sqe'])[:, 0])
+        text += 'R_EE50 %s\n' % ' '.join('%.2f' % v for v in np.asarray(met['r_ee'])[:, 0])
+        text += RULE + '\n'
     for line in text.splitlines():
         logger.info(line)
     if opt.logfile is not None:

@@ -13,6 +13,8 @@ constexpr int KS = 41;       // Moffat kernel side, psfrec.py:911-916
 constexpr int NAO = 80;      // AO-corrected zone, psfrec.py:103, 138
 constexpr int NFIT = 16;
 constexpr int NFIT_ELL = 24;     // elliptical fit (fit_ell.hip)
+constexpr int METRIC_MAX = 16;   // MPSFR_MAX_METRIC_RADII: radii, boxes, fractions of one metrics call (metrics.hip)
+constexpr int METRIC_HEAD = 8;   // MPSFR_NMET_HEAD
 constexpr int KHAT = 33 * 64;  // complex entries of one kernel spectrum (k_khat)
 constexpr int MAXLGS = 4;
 
@@ -280,6 +282,12 @@ void launch_stamp_sum(hipStream_t s, int ntask, int nl, const void* d_fin, bool 
                       int accumulate);
 // elliptical Moffat fit (fit_ell.hip): [nstamp][40][40] double stamps -> [nstamp][NFIT_ELL]
 void launch_fit_ell(hipStream_t s, int nstamp, const double* d_stamps, double* d_fit, bool f64);
+// PSF energy metrics (metrics.hip): [nstamp][40][40] double stamps -> [nstamp][METRIC_HEAD + nrad + nbox + nfrac];
+// d_centers [nstamp][2] (p, q) or nullptr (the centroid); radii / boxes / fractions: host arrays (they travel as kernel
+// arguments), counts 0..METRIC_MAX
+void launch_stamp_metrics(hipStream_t s, int nstamp, const double* d_stamps, const double* d_centers, int nrad,
+                          const double* radii, int nbox, const double* boxes, int nfrac, const double* fractions,
+                          double* d_out);
 // band-integrated stamps (band.hip): d_fin [ntb][nl][40][40] (float if fin_f32, else double) reduced over wavelength
 // into d_out [ntb][nband][40][40] double with the weights d_w [nl][band_stride(nband)] (zero beyond nband)
 constexpr int MAX_BANDS = 16;    // MPSFR_MAX_BANDS

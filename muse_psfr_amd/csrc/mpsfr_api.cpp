@@ -2385,6 +2385,57 @@ int mpsfr_fit_stamps_elliptical(mpsfr_ctx* c, int nstamp, const double* stamps, 
     return MPSFR_OK;
 }
 
+static_assert(METRIC_MAX == MPSFR_MAX_METRIC_RADII && METRIC_HEAD == MPSFR_NMET_HEAD, "K_STAMP_METRICS row layout");
+
+int mpsfr_stamp_metrics(mpsfr_ctx* c, int nstamp, const double* stamps, const double* centers, int nrad,
+                        const double* radii_px, int nbox, const double* boxes_px, int nfrac, const double* fractions,
+                        double* out, int on_device) {
+    if (!c || !stamps || !out || nstamp < 1) return fail(MPSFR_E_INVALID, "bad argument");
+    if (nrad < 0 || nrad > METRIC_MAX || nbox < 0 || nbox > METRIC_MAX || nfrac < 0 || nfrac > METRIC_MAX ||
+        nrad + nbox + nfrac == 0)
+        return fail(MPSFR_E_INVALID, "metrics: need 0..16 radii, boxes and fractions, and at least one of them");
+    if ((nrad && !radii_px) || (nbox && !boxes_px) || (nfrac && !fractions))
+        return fail(MPSFR_E_INVALID, "metrics: NULL parameter array");
+    for (int k = 0; k < nrad; ++k)
+        if (!(radii_px[k] > 0.0 && radii_px[k] <= 2.0 * NS))
+            return fail(MPSFR_E_INVALID, "metrics: a radius must be finite, > 0 and at most 80 pixels");
+    for (int k = 0; k < nbox; ++k)
+        if (!(boxes_px[k] > 0.0 && boxes_px[k] <= 2.0 * NS))
+            return fail(MPSFR_E_INVALID, "metrics: a box side must be finite, > 0 and at most 80 pixels");
+    for (int k = 0; k < nfrac; ++k)
+        if (!(fractions[k] > 0.0 && fractions[k] < 1.0))
+            return fail(MPSFR_E_INVALID, "metrics: a fraction must lie in (0, 1)");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t per = (size_t)NS * NS, nout = (size_t)METRIC_HEAD + nrad + nbox + nfrac;
+    // as mpsfr_fit_stamps_elliptical: device stamps written by a device-output reconstruct of this context are
+    // complete when the kernel reads them
+    for (int k = 0; k < mpsfr_ctx::MAX_LANES; ++k)
+        if (c->lane[k].busy && c->lane[k].stream != s) HIPCHK(hipStreamWaitEvent(s, lane_end(c, c->lane[k]), 0));
+    if (on_device) {
+        ProfScope ps(c, K_FIT);
+        launch_stamp_metrics(s, nstamp, stamps, centers, nrad, radii_px, nbox, boxes_px, nfrac, fractions, out);
+        HIPCHK(hipGetLastError());
+        return MPSFR_OK;
+    }
+    int rc;
+    if ((rc = ensure(c, c->stage, (size_t)nstamp * (per + 2 + nout) * sizeof(double)))) return rc;
+    double* d_st = (double*)c->stage.p;
+    double* d_ce = d_st + (size_t)nstamp * per;
+    double* d_out = d_ce + (size_t)nstamp * 2;
+    HIPCHK(hipMemcpyAsync(d_st, stamps, (size_t)nstamp * per * sizeof(double), hipMemcpyHostToDevice, s));
+    if (centers) HIPCHK(hipMemcpyAsync(d_ce, centers, (size_t)nstamp * 2 * sizeof(double), hipMemcpyHostToDevice, s));
+    {
+        ProfScope ps(c, K_FIT);
+        launch_stamp_metrics(s, nstamp, d_st, centers ? d_ce : nullptr, nrad, radii_px, nbox, boxes_px, nfrac, fractions,
+                             d_out);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_out, (size_t)nstamp * nout * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MPSFR_OK;
+}
+
 long mpsfr_debug_fetch(mpsfr_ctx* c, const char* what, double* out, size_t capacity) {
     if (!c || !what || !out) return fail(MPSFR_E_INVALID, "NULL argument");
     HIPCHK(hipSetDevice(c->device));

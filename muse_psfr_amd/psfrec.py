@@ -361,6 +361,143 @@ def fit_psf_cube(lbda, psfcube, *, circular=True, pixscale=0.2, precision='mixed
     return _make_table(_fit_columns(lbda, ctx.fit_stamps(data), pixscale))
 
 
+METRIC_RADII = (0.2, 0.4, 0.6, 1.0, 2.0)      # default encircled-energy radii [arcsec]
+METRIC_BOXES = (0.2, 0.4, 0.6, 1.0)           # default ensquared-energy box sides [arcsec] (0.2": the WFM spaxel)
+METRIC_FRACTIONS = (0.5, 0.8)                 # default fractions of the EE radii
+_METRIC_COLS = ('ee', 'sqe', 'r_ee')
+
+
+def _metrics_request(metrics, pixscale, dimpsf=40):
+    """The `metrics` argument of the compute_* functions -> None, or dict(radii, boxes, fractions [arcsec], center)
+    with the defaults of psf_metrics filled in and the values validated (ValueError)."""
+    if metrics is None or metrics is False:
+        return None
+    req = dict(radii=METRIC_RADII, boxes=METRIC_BOXES, fractions=METRIC_FRACTIONS, center='centroid')
+    if metrics is not True:
+        if not isinstance(metrics, dict):
+            raise ValueError('metrics must be None, True or a dict(radii=, boxes=, fractions=, center=)')
+        extra = set(metrics) - set(req)
+        if extra:
+            raise ValueError('unknown metrics key(s): %s' % ', '.join(sorted(map(str, extra))))
+        req.update(metrics)
+    _metric_arguments(req['radii'], req['boxes'], req['fractions'], req['center'], pixscale, dimpsf)
+    return req
+
+
+def _metric_arguments(radii, boxes, fractions, center, pixscale, dimpsf, nstamp=None):
+    """Validated (radii_px, boxes_px, fractions, radii, boxes, centers) of a psf_metrics call: the pixel arrays of the
+    library call, the arcsec arrays of the meta, and the (nstamp, 2) centres or None (the centroid).  ValueError."""
+    try:
+        ps = float(pixscale)
+    except (TypeError, ValueError):
+        raise ValueError('pixscale must be a positive number') from None
+    if not (np.isfinite(ps) and ps > 0):
+        raise ValueError('pixscale must be a positive number')
+    arc = []
+    for name, v in (('radii', radii), ('boxes', boxes)):
+        try:
+            arc.append(np.atleast_1d(np.asarray(() if v is None else v, dtype=float)))
+        except (TypeError, ValueError):
+            raise ValueError('%s must be numbers (arcsec)' % name) from None
+    rad, box, frac = _lib.metric_parameters(arc[0] / ps, arc[1] / ps, fractions, dimpsf)
+    if isinstance(center, str):
+        if center not in ('centroid', 'stamp'):
+            raise ValueError("center must be 'centroid', 'stamp' or an (n, 2) array of (p, q) in pixels")
+        ce = None
+        if center == 'stamp' and nstamp is not None:
+            ce = np.full((nstamp, 2), (dimpsf - 1) / 2.0)
+    elif center is None:
+        raise ValueError("center must be 'centroid', 'stamp' or an (n, 2) array of (p, q) in pixels")
+    elif nstamp is None:
+        try:
+            ce = np.asarray(center, dtype=float)
+        except (TypeError, ValueError):
+            raise ValueError('center must be an (n, 2) array of (p, q) in pixels') from None
+        if ce.ndim != 2 or ce.shape[1] != 2 or not np.all(np.isfinite(ce)):
+            raise ValueError('center must be a finite (n, 2) array of (p, q) in pixels')
+    else:
+        ce = _lib.metric_centers(center, nstamp)
+    return rad, box, frac, arc[0], arc[1], ce
+
+
+def _metric_columns(rows, nrad, nbox, nfrac, pixscale):
+    """Library metric rows (n, NMET_HEAD + nrad + nbox + nfrac) -> the columns of psf_metrics (r_ee in arcsec)."""
+    h = _lib.NMET_HEAD
+    cols = OrderedDict()
+    cols['flux'] = rows[:, 0].copy()
+    cols['peak'] = rows[:, 1].copy()
+    cols['center'] = rows[:, 4:6].copy()
+    cols['ee'] = rows[:, h:h + nrad].copy()
+    cols['sqe'] = rows[:, h + nrad:h + nrad + nbox].copy()
+    cols['r_ee'] = rows[:, h + nrad + nbox:h + nrad + nbox + nfrac] * pixscale
+    cols['status'] = rows[:, 6].astype(np.int64)
+    return cols
+
+
+def _metric_meta(radii, boxes, fractions, center):
+    """The parameters of a metrics table for its meta / FITS header: MRAD1.., MBOX1.. [arcsec], MFRAC1.., MCENTER."""
+    meta = OrderedDict()
+    for key, vals in (('MRAD', radii), ('MBOX', boxes), ('MFRAC', fractions)):
+        for k, v in enumerate(np.atleast_1d(vals)):
+            meta['%s%d' % (key, k + 1)] = float(v)
+    meta['MCENTER'] = center if isinstance(center, str) else 'given'
+    return meta
+
+
+def psf_metrics(psfcube, radii=METRIC_RADII, boxes=METRIC_BOXES, fractions=METRIC_FRACTIONS, center='centroid', *,
+                pixscale=0.2, precision='mixed', device=0):
+    """Energy metrics of PSF stamps, on the GPU (mpsfr_stamp_metrics): the encircled energy inside the ``radii``, the
+    ensquared energy in the boxes of side ``boxes`` (both in arcsec, with the exact overlap of every pixel -- no pixel
+    mask) and the radii [arcsec] that hold the ``fractions`` of the light, as fractions of the flux on the stamp.
+
+    ``psfcube``: stamps of any leading shape (..., dimpsf, dimpsf).  ``center``: ``'centroid'`` (the flux-weighted first
+    moment of each stamp), ``'stamp'`` (the geometric centre of the stamp, pixel coordinate (dimpsf - 1) / 2 = 19.5 in
+    both axes) or an (n, 2) array of (p, q) in pixels, e.g. the ``center`` column of a fit table.  The reconstructed
+    stamps of this package peak at pixel (20, 20) (their centroid lies within 0.07 px of it), half a pixel from the
+    geometric centre: ``'stamp'`` is meant for stamps that are symmetric about the middle of the array, for the
+    reconstructed ones use ``'centroid'`` or the fit centres.
+
+    Returns a table, one row per stamp, with the columns flux (sum of the stamp), peak (brightest pixel), center (p, q
+    in pixels), ee (n, nrad), sqe (n, nbox), r_ee (n, nfrac; arcsec) and status (0; 1: an EE radius is not converged; 2:
+    non-finite pixels or flux <= 0 -- ee, sqe, r_ee are NaN); radii, boxes, fractions and the centre rule are in the meta
+    (MRADk, MBOXk, MFRACk, MCENTER).  The arithmetic is fp64 whatever ``precision`` (which only selects the cached
+    context).  Every refusal is a ValueError raised before a GPU context exists."""
+    st = _lib.metric_stamps(psfcube)
+    rad, box, frac, ra, ba, ce = _metric_arguments(radii, boxes, fractions, center, pixscale, st.shape[-1], st.shape[0])
+    if precision not in ('mixed', 'f64'):
+        raise ValueError("precision must be 'mixed' or 'f64'")
+    ctx = get_context(128, pixscale, st.shape[-1], precision, device)
+    rows = ctx.stamp_metrics(st, rad, box, frac, centers=ce)
+    return _make_table(_metric_columns(rows, rad.size, box.size, frac.size, float(pixscale)),
+                       _metric_meta(ra, ba, frac, center))
+
+
+def _append_metrics(cols, psf, req, ctx, pixscale):
+    """The ee, sqe, r_ee columns of the stamps `psf` (row for row with the fit columns of `cols`) appended to `cols`."""
+    st = _lib.metric_stamps(psf, psf.shape[-1])
+    rad, box, frac, _, _, ce = _metric_arguments(req['radii'], req['boxes'], req['fractions'], req['center'], pixscale,
+                                                 st.shape[-1], st.shape[0])
+    m = _metric_columns(ctx.stamp_metrics(st, rad, box, frac, centers=ce), rad.size, box.size, frac.size,
+                        float(pixscale))
+    for k in _METRIC_COLS:
+        cols[k] = m[k]
+
+
+def _metrics_hdu(lead, psf, req, ctx, pixscale, meta, name):
+    """A METRICS_* HDU: the columns `lead` (an OrderedDict, one row per stamp of `psf`), then those of psf_metrics
+    (2-D columns without entries are left out: a FITS column needs a width)."""
+    st = _lib.metric_stamps(psf, psf.shape[-1])
+    rad, box, frac, ra, ba, ce = _metric_arguments(req['radii'], req['boxes'], req['fractions'], req['center'],
+                                                   pixscale, st.shape[-1], st.shape[0])
+    cols = OrderedDict(lead)
+    m = _metric_columns(ctx.stamp_metrics(st, rad, box, frac, centers=ce), rad.size, box.size, frac.size,
+                        float(pixscale))
+    cols.update((k, v) for k, v in m.items() if v.ndim == 1 or v.shape[1] > 0)
+    hmeta = OrderedDict(meta)
+    hmeta.update(_metric_meta(ra, ba, frac, req['center']))
+    return _table_hdu(cols, hmeta, name)
+
+
 def simul_psd_wfm(Cn2, h, seeing, L0, zenith=0., plot=False, npsflin=1, dim=1280, three_lgs_mode=False,
                   verbose=True, *, precision='mixed', cutoff_masks='host', device=0, wind_speed=None, wind_dir=None):
     """Residual phase PSD of the MUSE wide-field mode for each evaluation direction (psfrec.py:36-151):
@@ -559,11 +696,13 @@ def convolve_final_psf(lbda, seeing, GL, L0, psf, *, pixscale=0.2, precision='mi
 
 def compute_psf(lbda, seeing, GL, L0, npsflin=1, h=(100, 10000), three_lgs_mode=False,
                 verbose=True, *, dim=1280, dimpsf=40, pixscale=0.2, precision='mixed',
-                cutoff_masks='host', device=0):
+                cutoff_masks='host', device=0, metrics=None):
     """Reconstruct a PSF from a set of seeing, GL, and L0 values (psfrec.py:933-978).
 
     Returns ``(table, psf)``: the per-wavelength Moffat fit table (with SEEING, GL, L0 columns and
-    meta) and the (nl, 40, 40) float64 PSF cube."""
+    meta) and the (nl, 40, 40) float64 PSF cube.  ``metrics``: None (the table above), True or a
+    dict(radii=, boxes=, fractions=, center=) (see psf_metrics): the columns ee, sqe, r_ee of ``psf`` follow."""
+    mreq = _metrics_request(metrics, pixscale, dimpsf)
     lbda = np.atleast_1d(np.asarray(lbda, dtype=float))
     if verbose:
         logger.info('Compute PSF with seeing=%.2f GL=%.2f L0=%.2f', seeing, GL, L0)
@@ -576,6 +715,9 @@ def compute_psf(lbda, seeing, GL, L0, npsflin=1, h=(100, 10000), three_lgs_mode=
     cols['SEEING'] = np.full(nl, float(seeing))
     cols['GL'] = np.full(nl, float(GL))
     cols['L0'] = np.full(nl, float(L0))
+    if mreq is not None:
+        _append_metrics(cols, r['psf'][0], mreq, get_context(dim, pixscale, dimpsf, precision, r['devices'][0]),
+                        pixscale)
     res = _make_table(cols, {'SEEING': float(seeing), 'GL': float(GL), 'L0': float(L0)})
     return res, r['psf'][0]
 
@@ -614,7 +756,7 @@ def _field_groups(npos):
 
 def compute_field_psf(lbda, seeing, GL, L0, positions=None, npsflin=1, h=(100, 10000), three_lgs_mode=False,
                       verbose=True, *, dim=1280, dimpsf=40, pixscale=0.2, precision='mixed',
-                      cutoff_masks='host', device=0, circular=True):
+                      cutoff_masks='host', device=0, circular=True, metrics=None):
     """Field-resolved form of compute_psf: the PSF at every field position instead of their mean.
 
     ``positions``: (npos, 2) array of (x, y) in arcsec (|x|, |y| <= 60, the convention of direction_perf:
@@ -624,8 +766,10 @@ def compute_field_psf(lbda, seeing, GL, L0, positions=None, npsflin=1, h=(100, 1
     Returns ``(table, psf)``: ``psf`` (npos, nl, dimpsf, dimpsf) float64; ``table`` npos x nl rows ordered
     (position, wavelength) with the columns dir_idx (0-based), x, y, lbda, the fit columns of compute_psf and
     SEEING, GL, L0 (values in the meta too).  circular=False: the fit columns are those of an elliptical Moffat
-    fitted to ``psf`` (fit_psf_cube(..., circular=False)); ``psf`` is the same."""
+    fitted to ``psf`` (fit_psf_cube(..., circular=False)); ``psf`` is the same.  ``metrics``: as compute_psf -- the
+    columns ee, sqe, r_ee of every stamp, row for row with the fit columns."""
     circular = _check_circular(circular)
+    mreq = _metrics_request(metrics, pixscale, dimpsf)
     lbda = np.atleast_1d(np.asarray(lbda, dtype=float))
     if lbda.ndim != 1 or lbda.size < 1 or not np.all(np.isfinite(lbda)) or np.any(lbda <= 0):
         raise ValueError('lbda must be a non-empty 1-D array of positive wavelengths (nm)')
@@ -667,6 +811,8 @@ def compute_field_psf(lbda, seeing, GL, L0, positions=None, npsflin=1, h=(100, 1
     cols['SEEING'] = np.full(n, seeing)
     cols['GL'] = np.full(n, GL)
     cols['L0'] = np.full(n, L0)
+    if mreq is not None:
+        _append_metrics(cols, psf, mreq, ctx, pixscale)
     return _make_table(cols, {'SEEING': seeing, 'GL': GL, 'L0': L0}), psf
 
 
@@ -824,7 +970,7 @@ def _band_groups(nband):
 
 def compute_band_psf(lbda, seeing, GL, L0, bands, sed=None, npsflin=1, positions=None, h=(100, 10000),
                      three_lgs_mode=False, verbose=True, *, dim=1280, dimpsf=40, pixscale=0.2, precision='mixed',
-                     cutoff_masks='host', device=0, circular=True):
+                     cutoff_masks='host', device=0, circular=True, metrics=None):
     """Band-integrated form of compute_psf: the PSF of a broadband image, the spectrum-weighted mean of the
     monochromatic PSFs over each band (band_weights(lbda, bands, sed) on the grid ``lbda``), reduced and fitted on the
     GPU -- not the PSF at the band's central wavelength.
@@ -834,8 +980,10 @@ def compute_band_psf(lbda, seeing, GL, L0, bands, sed=None, npsflin=1, positions
     (position,) band with the columns band (0-based), (dir_idx, x, y,) lbda_eff (the weighted mean wavelength),
     lbda_min, lbda_max (the band's nodes with weight), the fit columns of compute_psf and SEEING, GL, L0.
     circular=False: the fit columns are those of an elliptical Moffat fitted to ``psf`` (fit_psf_cube(...,
-    circular=False)); ``psf`` is the same.  Every refusal is a ValueError, raised before any GPU context exists."""
+    circular=False)); ``psf`` is the same.  ``metrics``: as compute_psf -- the columns ee, sqe, r_ee of every band stamp.
+    Every refusal is a ValueError, raised before any GPU context exists."""
     circular = _check_circular(circular)
+    mreq = _metrics_request(metrics, pixscale, dimpsf)
     lbda = np.atleast_1d(np.asarray(lbda, dtype=float))
     w = band_weights(lbda, bands, sed)
     try:
@@ -888,6 +1036,8 @@ def compute_band_psf(lbda, seeing, GL, L0, bands, sed=None, npsflin=1, positions
     cols['SEEING'] = np.full(n, seeing)
     cols['GL'] = np.full(n, GL)
     cols['L0'] = np.full(n, L0)
+    if mreq is not None:
+        _append_metrics(cols, psf, mreq, ctx, pixscale)
     if pos is None:
         psf = psf[0]
     return _make_table(cols, {'SEEING': seeing, 'GL': GL, 'L0': L0}), psf
@@ -895,7 +1045,7 @@ def compute_band_psf(lbda, seeing, GL, L0, bands, sed=None, npsflin=1, positions
 
 def compute_profile_psf(lbda, seeing, L0, cn2, h, wind_speed=12.5, wind_dir=None, GL=None, npsflin=1, positions=None,
                         three_lgs_mode=False, verbose=True, *, dim=1280, dimpsf=40, pixscale=0.2, precision='mixed',
-                        cutoff_masks='host', device=0, circular=True):
+                        cutoff_masks='host', device=0, circular=True, metrics=None):
     """compute_psf / compute_field_psf for a Cn2 profile instead of the fixed two-layer atmosphere.
 
     ``cn2``, ``h``, ``wind_speed``, ``wind_dir``: the layers' weights (normalised here, psfrec.py:57-58), altitudes
@@ -908,9 +1058,10 @@ def compute_profile_psf(lbda, seeing, L0, cn2, h, wind_speed=12.5, wind_dir=None
     positions=None: ``(table, psf)`` as compute_psf (the npsflin directions averaged, psf (nl, dimpsf, dimpsf));
     else (npos, 2) arcsec: as compute_field_psf (psf (npos, nl, dimpsf, dimpsf), table with dir_idx, x, y).
     circular=False: the fit columns are those of an elliptical Moffat fitted to ``psf`` (fit_psf_cube(...,
-    circular=False)); ``psf`` is the same.
+    circular=False)); ``psf`` is the same.  ``metrics``: as compute_psf -- the columns ee, sqe, r_ee of every stamp.
     Every refusal is a ValueError, raised before any GPU context exists."""
     circular = _check_circular(circular)
+    mreq = _metrics_request(metrics, pixscale, dimpsf)
     lbda = np.atleast_1d(np.asarray(lbda, dtype=float))
     if lbda.ndim != 1 or lbda.size < 1 or not np.all(np.isfinite(lbda)) or np.any(lbda <= 0):
         raise ValueError('lbda must be a non-empty 1-D array of positive wavelengths (nm)')
@@ -975,6 +1126,8 @@ def compute_profile_psf(lbda, seeing, L0, cn2, h, wind_speed=12.5, wind_dir=None
     cols['SEEING'] = np.full(n, seeing)
     cols['GL'] = np.full(n, GL)
     cols['L0'] = np.full(n, L0)
+    if mreq is not None:
+        _append_metrics(cols, psf, mreq, ctx, pixscale)
     return _make_table(cols, {'SEEING': seeing, 'GL': GL, 'L0': L0, 'NLAYER': int(hh.size)}), psf
 
 
@@ -1070,7 +1223,7 @@ def compute_psf_from_sparta(filename, extname='SPARTA_ATM_DATA', npsflin=1, lmin
                             nl=35, lbda=None, h=(100, 10000), n_jobs=-1, plot=False,
                             mean_of_lgs=True, verbose=True, *, dim=1280, dimpsf=40, pixscale=0.2,
                             precision='mixed', cutoff_masks='host', device=None, devices=None,
-                            field_positions=None, bands=None, band_sed=None, band_lbda=None):
+                            field_positions=None, bands=None, band_sed=None, band_lbda=None, metrics=None):
     """Reconstruct a PSF from SPARTA data (psfrec.py:981-1120).
 
     ``filename`` is a FITS path or an already opened HDUList.  Returns an HDUList with
@@ -1092,7 +1245,16 @@ def compute_psf_from_sparta(filename, extname='SPARTA_ATM_DATA', npsflin=1, lmin
     ``lbda``): three more HDUs follow -- FIT_BAND_ROWS, the Moffat fit of each row's band PSF (rows ordered (row,
     band), row_idx / lgs_idx as in FIT_ROWS), PSF_BAND, the (nband, dimpsf, dimpsf) mean over the rows of the band
     PSFs, and FIT_BAND, the fit of each PSF_BAND stamp (as FIT_MEAN is that of PSF_MEAN).  The rows use the devices
-    of FIT_ROWS."""
+    of FIT_ROWS.
+
+    ``metrics`` (None, True or a dict, see compute_psf and psf_metrics): the energy metrics of the mean stamps follow
+    all other HDUs -- METRICS_MEAN (of PSF_MEAN, one row per wavelength: lbda, flux, peak, center, ee, sqe, r_ee,
+    status), METRICS_FIELD (of PSF_FIELD: dir_idx, x, y, lbda, ...) and METRICS_BAND (of PSF_BAND: band, lbda_eff,
+    ...) when those exist; radii, boxes and fractions are in their headers (MRADk, MBOXk, MFRACk; a single radius, box or
+    fraction makes a scalar FITS column).  Per-row metrics of
+    the SPARTA table are not computed here: Context.reconstruct_device chained into Context.stamp_metrics_device does
+    that without downloading a stamp."""
+    mreq = _metrics_request(metrics, pixscale, dimpsf)
     bw = blbda = None
     if bands is not None:
         blbda = band_lbda if band_lbda is not None else (lbda if lbda is not None else np.linspace(lmin, lmax, nl))
@@ -1254,6 +1416,18 @@ def compute_psf_from_sparta(filename, extname='SPARTA_ATM_DATA', npsflin=1, lmin
             out.append(_minifits.ImageHDU(data=psf_band, name='PSF_BAND'))
         out.append(_table_hdu(_band_table_columns(blbda, bw, ctx.fit_stamps(psf_band), pixscale, True),
                               {'SEEING': float(seeing), 'GL': float(GL), 'L0': float(L0)}, 'FIT_BAND'))
+
+    if mreq is not None:
+        med = {'SEEING': float(seeing), 'GL': float(GL), 'L0': float(L0)}
+        out.append(_metrics_hdu(OrderedDict(lbda=lbda), psftot, mreq, ctx, pixscale, med, 'METRICS_MEAN'))
+        if fpos is not None:
+            lead = OrderedDict(dir_idx=np.repeat(np.arange(len(fpos)), nlam), x=np.repeat(fpos[:, 0], nlam),
+                               y=np.repeat(fpos[:, 1], nlam), lbda=np.tile(lbda, len(fpos)))
+            out.append(_metrics_hdu(lead, psf_field, mreq, ctx, pixscale, med, 'METRICS_FIELD'))
+        if bw is not None:
+            eff = _band_columns(blbda, bw)[0]
+            lead = OrderedDict(band=np.arange(len(bw)), lbda_eff=eff)
+            out.append(_metrics_hdu(lead, psf_band, mreq, ctx, pixscale, med, 'METRICS_BAND'))
 
     if plot:
         import matplotlib.pyplot as plt
