@@ -372,6 +372,33 @@ int mpsfr_fit_stamps(mpsfr_ctx* ctx, int nstamp, const double* stamps, double* f
  *             19 flux = peak pi alpha_major alpha_minor / (n - 1)  20 err_flux  21..23 zero (reserved) */
 int mpsfr_fit_stamps_elliptical(mpsfr_ctx* ctx, int nstamp, const double* stamps, double* fit_out, int on_device);
 
+/* Weighted Moffat fit of observed stars (mpdaf's moffat_fit(weight=True, fit_back=..., circular=...)): the minimum of
+ *     sum over the used pixels of (model - data)^2 / var,   model = Moffat [+ b]
+ * in the variables I, p0, q0, w, [e1, e2,] eta = 1/n, [b] of mpsfr_fit_stamps_elliptical (circular without
+ * MPSFR_FIT_ELLIPTICAL), with a constant background b under MPSFR_FIT_BACKGROUND.
+ * stamps: [nstamp][dimpsf][dimpsf] float64; var: the same shape, or NULL for unit weights.  A pixel is USED iff its
+ * value is finite and, when var is given, its variance is finite and > 0; every other pixel is left out of every sum
+ * and its stored value never matters (NaN data, or var <= 0 / NaN / inf, is the mask).  A +-inf value under a valid
+ * variance makes the row status 2.
+ * fit_out: [nstamp][MPSFR_NFIT_ELL] in the elliptical layout, with 21 background, 22 err_background (both 0 without
+ * MPSFR_FIT_BACKGROUND) and 23 the number of used pixels; without MPSFR_FIT_ELLIPTICAL alpha_major = alpha_minor,
+ * fwhm_major = fwhm_minor, rot = err_rot = 0.  Errors: sqrt(diag((J^T W J)^-1) chi2 / dof), dof = n_used - npar with
+ * npar = 5 ... 8, propagated to first order; chi2 (field 9) is the weighted sum.  A constant factor on var changes
+ * no parameter and no error.
+ * Status (field 18): 0, 1, 2 as for mpsfr_fit_stamps_elliptical; 2 also when n_used < npar + 1, when no used pixel
+ * exceeds the start background (the mean of the used pixels of the outer ring), and when the brightest used pixel
+ * lies outside [2^-40, 2^40] in modulus (the stamp is normalised by a power of two internally), and when a used
+ * pixel exceeds 2^60 times the brightest one in modulus (a deep negative outlier that was not masked).  The
+ * MPSFR_FIT_ILL_CONDITIONED bit is not set by this entry point: its threshold is defined for unit weights, and the
+ * formal errors carry the information here.  A row whose status & 3 is 0 holds finite numbers only.
+ * A stamp's row depends on that stamp only, bit for bit.  on_device as mpsfr_fit_stamps_elliptical (stamps, var and
+ * fit_out are device pointers, the call is queued on the context stream); timed under the fit's profiling id.
+ * MPSFR_E_INVALID, with fit_out untouched: nstamp < 1, unknown flag bits, NULL stamps or fit_out. */
+#define MPSFR_FIT_BACKGROUND 1   /* fit a constant background b: model = Moffat + b */
+#define MPSFR_FIT_ELLIPTICAL 2   /* the (e1, e2) model of mpsfr_fit_stamps_elliptical; else circular */
+int mpsfr_fit_stamps_observed(mpsfr_ctx* ctx, int nstamp, const double* stamps, const double* var, int flags,
+                              double* fit_out, int on_device);
+
 /* PSF energy metrics of caller-provided stamps: encircled and ensquared energy with exact pixel overlap, and the radii
  * that hold given fractions of the flux -- the non-parametric description of a core + halo PSF, beside the Moffat fits.
  * Pixel (p, q) is the unit square centred on (p, q), in the pixel coordinates of the fits (p0, q0).  Per stamp:

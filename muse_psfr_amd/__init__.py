@@ -12,7 +12,7 @@ psf_metrics (encircled / ensquared energy with exact pixel overlap and EE radii 
 of the compute_* functions and the METRICS_* HDUs of compute_psf_from_sparta(..., metrics=...).
 Low level: Context (ctypes binding of libmpsfr.so).
 """
-from ._lib import Context, ContextPool, MpsfrError, NFIT, NFIT_ELL, NMET_HEAD, FIT_ILL_CONDITIONED  # noqa: F401
+from ._lib import Context, ContextPool, MpsfrError, NFIT, NFIT_ELL, NMET_HEAD, FIT_ILL_CONDITIONED, FIT_BACKGROUND, FIT_ELLIPTICAL  # noqa: F401
 from .synthetic import synthetic_rows, grid_pixscale  # noqa: F401
 from .psfrec import (MAX_L0, MIN_L0, compute_psf, compute_field_psf, compute_profile_psf,  # noqa: F401
                      band_weights, compute_band_psf, psf_metrics,

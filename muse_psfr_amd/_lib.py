@@ -14,6 +14,8 @@ NFIT_ELL = 24                # elliptical fit rows (MPSFR_NFIT_ELL, include/mpsf
 MAX_METRIC_RADII = 16        # radii, boxes, fractions of one metrics call (MPSFR_MAX_METRIC_RADII)
 NMET_HEAD = 8                # leading fields of a metrics row (MPSFR_NMET_HEAD)
 FIT_ILL_CONDITIONED = 4      # status bit of fit_out[14] (MPSFR_FIT_ILL_CONDITIONED, include/mpsfr.h)
+FIT_BACKGROUND = 1           # flags of mpsfr_fit_stamps_observed (MPSFR_FIT_BACKGROUND, MPSFR_FIT_ELLIPTICAL)
+FIT_ELLIPTICAL = 2
 DIM_AO = 80
 PREC_MIXED, PREC_F64 = 0, 1
 E_GRID = -3
@@ -91,6 +93,8 @@ def load():
     lib.mpsfr_fit_stamps.restype = C.c_int
     lib.mpsfr_fit_stamps_elliptical.argtypes = [p, C.c_int, p, p, C.c_int]
     lib.mpsfr_fit_stamps_elliptical.restype = C.c_int
+    lib.mpsfr_fit_stamps_observed.argtypes = [p, C.c_int, p, p, C.c_int, p, C.c_int]
+    lib.mpsfr_fit_stamps_observed.restype = C.c_int
     lib.mpsfr_stamp_metrics.argtypes = [p, C.c_int, p, p, C.c_int, dp, C.c_int, dp, C.c_int, dp, p, C.c_int]
     lib.mpsfr_stamp_metrics.restype = C.c_int
     lib.mpsfr_simul_psd.argtypes = [p, C.c_double, C.c_double, C.c_double, C.c_int, dp, C.c_double, C.c_int, u8p, u8p, dp]
@@ -140,7 +144,7 @@ def load():
 
 
 EXPORTS = ['mpsfr_create', 'mpsfr_destroy', 'mpsfr_last_error', 'mpsfr_set_option',
-           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_stamp_metrics', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
+           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_stamp_metrics', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
            'mpsfr_psd_to_psf',
            'mpsfr_convolve_stamps', 'mpsfr_fit_rows', 'mpsfr_sync', 'mpsfr_last_ticket', 'mpsfr_wait', 'mpsfr_abandon',
            'mpsfr_stream', 'mpsfr_stream_wait', 'mpsfr_wait_event',
@@ -783,6 +787,33 @@ class Context:
         _check(self.lib.mpsfr_fit_stamps_elliptical(self._h, int(nstamp), C.c_void_p(int(stamps_ptr)),
                                                     C.c_void_p(int(fit_ptr)), 1))
 
+    def fit_stamps_observed(self, stamps, var=None, background=True, circular=True):
+        """Weighted Moffat fit of observed stars (mpsfr_fit_stamps_observed) of stamps (..., dimpsf, dimpsf): (n, NFIT_ELL)
+        rows in the elliptical layout, with 21 background, 22 err_background, 23 the number of used pixels.  `var`: the
+        variance of every pixel (same shape), or None for unit weights.  A NaN pixel, or one whose variance is not
+        finite and > 0, is masked.  `background`: fit a constant background; `circular`: a circular Moffat."""
+        st, va = observed_stamps(stamps, var, self.dimpsf)
+        flags = observed_flags(background, circular)
+        out = np.empty((st.shape[0], NFIT_ELL))
+        _check(self.lib.mpsfr_fit_stamps_observed(self._h, st.shape[0], st.ctypes.data_as(C.c_void_p),
+                                                  None if va is None else va.ctypes.data_as(C.c_void_p), flags,
+                                                  out.ctypes.data_as(C.c_void_p), 0))
+        return out
+
+    def fit_stamps_observed_device(self, nstamp, stamps_ptr, fit_ptr, var_ptr=None, background=True, circular=True):
+        """Device-buffer form (asynchronous, on_device = 1): `stamps_ptr` and `var_ptr` ([nstamp][dimpsf][dimpsf]
+        float64; var_ptr None: unit weights) and `fit_ptr` ([nstamp][NFIT_ELL] float64) are raw device pointers (int) on
+        this context's GPU; the call is queued on the context stream, after any device-output reconstruct of this
+        context."""
+        if isinstance(nstamp, bool) or not isinstance(nstamp, (int, np.integer)) or nstamp < 1:
+            raise ValueError('nstamp must be a positive integer')
+        if not stamps_ptr or not fit_ptr:
+            raise ValueError('stamps_ptr and fit_ptr must be device pointers')
+        flags = observed_flags(background, circular)
+        _check(self.lib.mpsfr_fit_stamps_observed(self._h, int(nstamp), C.c_void_p(int(stamps_ptr)),
+                                                  C.c_void_p(int(var_ptr)) if var_ptr else None, flags,
+                                                  C.c_void_p(int(fit_ptr)), 1))
+
     def stamp_metrics(self, stamps, radii_px, boxes_px, fractions, centers=None):
         """PSF energy metrics (mpsfr_stamp_metrics) of stamps (..., dimpsf, dimpsf): (n, NMET_HEAD + nrad + nbox +
         nfrac) rows -- flux, peak, peak_p, peak_q, cp, cq, status, 0, then the encircled energies at `radii_px`, the
@@ -850,6 +881,38 @@ def elliptical_stamps(stamps, dimpsf=40):
     if not np.all(np.isfinite(st)):
         raise ValueError('stamps must be finite')
     return np.ascontiguousarray(st).reshape(-1, dimpsf, dimpsf)
+
+
+def observed_flags(background, circular):
+    """The flags of mpsfr_fit_stamps_observed from two booleans (ValueError for anything else)."""
+    for name, val in (('background', background), ('circular', circular)):
+        if not isinstance(val, (bool, np.bool_)):
+            raise ValueError('%s must be True or False' % name)
+    return (FIT_BACKGROUND if background else 0) | (0 if circular else FIT_ELLIPTICAL)
+
+
+def observed_stamps(stamps, var=None, dimpsf=40):
+    """(stamps, var) for the weighted fit as C-contiguous (n, dimpsf, dimpsf) float64 arrays (var: None for unit
+    weights); ValueError unless `stamps` is a non-empty numeric array of shape (..., dimpsf, dimpsf) and `var` has
+    the same shape.  A masked array is accepted: masked pixels become NaN.  Non-finite pixels and variances that are
+    not finite and > 0 are the mask of the fit, not an error."""
+    def plane(a, what):
+        try:
+            if isinstance(a, np.ma.MaskedArray):
+                return np.ma.filled(a.astype(np.float64), np.nan)
+            return np.asarray(a, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('%s must be a numeric array' % what) from None
+    st = plane(stamps, 'stamps')
+    if st.ndim < 2 or st.shape[-2:] != (dimpsf, dimpsf) or st.size == 0:
+        raise ValueError('stamps must have the shape (..., %d, %d)' % (dimpsf, dimpsf))
+    st = np.ascontiguousarray(st).reshape(-1, dimpsf, dimpsf)
+    if var is None:
+        return st, None
+    va = plane(var, 'var')
+    if va.size != st.size or va.shape[-2:] != (dimpsf, dimpsf):
+        raise ValueError('var must have the shape of stamps')
+    return st, np.ascontiguousarray(va).reshape(-1, dimpsf, dimpsf)
 
 
 def metric_stamps(stamps, dimpsf=40):

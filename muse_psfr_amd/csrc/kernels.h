@@ -282,6 +282,10 @@ void launch_stamp_sum(hipStream_t s, int ntask, int nl, const void* d_fin, bool 
                       int accumulate);
 // elliptical Moffat fit (fit_ell.hip): [nstamp][40][40] double stamps -> [nstamp][NFIT_ELL]
 void launch_fit_ell(hipStream_t s, int nstamp, const double* d_stamps, double* d_fit, bool f64);
+// weighted Moffat fit of observed stars (fit_obs.hip): [nstamp][40][40] double stamps and variances (d_var = nullptr:
+// unit weights) -> [nstamp][NFIT_ELL]; flags: MPSFR_FIT_BACKGROUND | MPSFR_FIT_ELLIPTICAL
+void launch_fit_obs(hipStream_t s, int nstamp, const double* d_stamps, const double* d_var, int flags, double* d_fit,
+                    bool f64);
 // PSF energy metrics (metrics.hip): [nstamp][40][40] double stamps -> [nstamp][METRIC_HEAD + nrad + nbox + nfrac];
 // d_centers [nstamp][2] (p, q) or nullptr (the centroid); radii / boxes / fractions: host arrays (they travel as kernel
 // arguments), counts 0..METRIC_MAX

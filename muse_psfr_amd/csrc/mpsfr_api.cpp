@@ -2385,6 +2385,41 @@ int mpsfr_fit_stamps_elliptical(mpsfr_ctx* c, int nstamp, const double* stamps, 
     return MPSFR_OK;
 }
 
+int mpsfr_fit_stamps_observed(mpsfr_ctx* c, int nstamp, const double* stamps, const double* var, int flags,
+                              double* fit_out, int on_device) {
+    if (!c || !stamps || !fit_out || nstamp < 1) return fail(MPSFR_E_INVALID, "bad argument");
+    if (flags & ~(MPSFR_FIT_BACKGROUND | MPSFR_FIT_ELLIPTICAL))
+        return fail(MPSFR_E_INVALID, "fit_stamps_observed: unknown flag bits");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t per = (size_t)NS * NS;
+    // as mpsfr_fit_stamps_elliptical: device stamps written by a device-output reconstruct of this context are
+    // complete when the kernel reads them
+    for (int k = 0; k < mpsfr_ctx::MAX_LANES; ++k)
+        if (c->lane[k].busy && c->lane[k].stream != s) HIPCHK(hipStreamWaitEvent(s, lane_end(c, c->lane[k]), 0));
+    if (on_device) {
+        ProfScope ps(c, K_FIT);
+        launch_fit_obs(s, nstamp, stamps, var, flags, fit_out, c->f64);
+        HIPCHK(hipGetLastError());
+        return MPSFR_OK;
+    }
+    int rc;
+    if ((rc = ensure(c, c->stage, (size_t)nstamp * ((var ? 2 : 1) * per + NFIT_ELL) * sizeof(double)))) return rc;
+    double* d_st = (double*)c->stage.p;
+    double* d_va = var ? d_st + (size_t)nstamp * per : nullptr;
+    double* d_ft = d_st + (size_t)nstamp * per * (var ? 2 : 1);
+    HIPCHK(hipMemcpyAsync(d_st, stamps, (size_t)nstamp * per * sizeof(double), hipMemcpyHostToDevice, s));
+    if (var) HIPCHK(hipMemcpyAsync(d_va, var, (size_t)nstamp * per * sizeof(double), hipMemcpyHostToDevice, s));
+    {
+        ProfScope ps(c, K_FIT);
+        launch_fit_obs(s, nstamp, d_st, d_va, flags, d_ft, c->f64);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(fit_out, d_ft, (size_t)nstamp * NFIT_ELL * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MPSFR_OK;
+}
+
 static_assert(METRIC_MAX == MPSFR_MAX_METRIC_RADII && METRIC_HEAD == MPSFR_NMET_HEAD, "K_STAMP_METRICS row layout");
 
 int mpsfr_stamp_metrics(mpsfr_ctx* c, int nstamp, const double* stamps, const double* centers, int nrad,

@@ -344,13 +344,69 @@ def _make_table(cols, meta=None):
     return Table(cols, meta)
 
 
-def fit_psf_cube(lbda, psfcube, *, circular=True, pixscale=0.2, precision='mixed', device=0):
+_FIT_COLS_OBS = ('back', 'err_back', 'npix')
+
+
+def _fit_columns_obs(lbda, fit, pixscale, circular):
+    """fit: (n, NFIT_ELL) rows of the weighted fit -> the columns of _FIT_COLS (circular) or _FIT_COLS_ELL, then
+    back, err_back, npix."""
+    fit = np.asarray(fit)
+    cols = _fit_columns_ell(lbda, fit, pixscale)
+    if circular:
+        cols = OrderedDict((k, cols[k]) for k in _FIT_COLS)
+    cols['back'] = fit[:, 21].copy()
+    cols['err_back'] = fit[:, 22].copy()
+    cols['npix'] = fit[:, 23].astype(np.int64)
+    return cols
+
+
+def _observed_cube(cube, var):
+    """(data, var) of the observed path of fit_psf_cube.  `cube`: an array, a masked array, or an mpdaf-style object
+    with .data (masked pixels become NaN) and .var; `var`: None (unit weights), an array of the cube's shape, or True
+    for the object's own .var."""
+    own_var = None
+    if isinstance(cube, np.ndarray):              # plain or masked array (observed_stamps turns masked into NaN)
+        data = cube
+    elif hasattr(cube, 'data'):                   # an mpdaf-style object
+        data, own_var = cube.data, getattr(cube, 'var', None)
+        mask = getattr(cube, 'mask', None)
+        if mask is not None and mask is not np.ma.nomask and not isinstance(data, np.ma.MaskedArray):
+            data = np.ma.MaskedArray(data, mask=mask)
+    else:
+        data = cube
+    if var is True:
+        var = own_var
+        if var is None:
+            raise ValueError('var=True needs a cube with a .var plane')
+    elif var is False:
+        var = None
+    return _lib.observed_stamps(data, var)
+
+
+def fit_psf_cube(lbda, psfcube, *, circular=True, var=None, fit_back=False, pixscale=0.2, precision='mixed',
+                 device=0):
     """Fit a Moffat PSF on each wavelength plane of the psfcube (psfrec.py:861-871).
 
     circular=False: an elliptical Moffat (mpdaf's moffat_fit(circular=False)); the table has the columns of
     _FIT_COLS_ELL, with fwhm / err_fwhm as (major, minor) in arcsec and rot / err_rot in degrees (major axis from
-    the column axis towards the row axis, in [0, 180))."""
-    if not _check_circular(circular):
+    the column axis towards the row axis, in [0, 180)).
+
+    var / fit_back: the weighted fit of observed stars (mpdaf's moffat_fit(weight=True, fit_back=...)), taken when
+    `var` is given or fit_back is True.  var: the variance of every pixel (an array of the cube's shape), or True for
+    the .var of an mpdaf-style cube; NaN or masked pixels and pixels whose variance is not finite and > 0 are left
+    out.  The table then has the columns of the circular / elliptical fit plus back, err_back and npix (the number
+    of pixels used)."""
+    circular = _check_circular(circular)
+    if not isinstance(fit_back, (bool, np.bool_)):
+        raise ValueError('fit_back must be True or False')
+    if var is not None or fit_back:
+        data, va = _observed_cube(psfcube, var)
+        if np.size(lbda) != data.shape[0]:
+            raise ValueError('need one wavelength per plane of psfcube')
+        ctx = get_context(128, pixscale, data.shape[-1], precision, device)
+        fit = ctx.fit_stamps_observed(data, va, background=bool(fit_back), circular=circular)
+        return _make_table(_fit_columns_obs(lbda, fit, pixscale, circular))
+    if not circular:
         data = _lib.elliptical_stamps(psfcube)
         if np.size(lbda) != data.shape[0]:
             raise ValueError('need one wavelength per plane of psfcube')
