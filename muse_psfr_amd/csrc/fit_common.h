@@ -1,8 +1,12 @@
-// Device helpers of the Moffat fits (k_fit in stamps.hip, k_fit_ell in fit_ell.hip): wave-wide sums on the
-// DPP path and the reciprocal, square-root, exp and log forms of the Levenberg-Marquardt iterations and their
-// fp64 polish.  Everything here has internal linkage.
+// Device code shared by the Moffat fits (k_fit in stamps.hip, k_fit_ell in fit_ell.hip, k_fit_obs in fit_obs.hip):
+// wave-wide sums on the DPP path; the reciprocal, square-root, exp and log forms of the Levenberg-Marquardt
+// iterations and their fp64 polish; and, as templates over the number of variables NP, the normal equations
+// (FitNormEq), their Marquardt-scaled Cholesky factor, solve and inverse (fit_chol, fit_chol_solve, fit_lm_solve,
+// fit_spd_inverse), the wave-uniform factors of a model pass (MoffatPar), the moment start (fit_moment_start) and
+// the constants of the iteration.  Everything here has internal linkage.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "device_common.h"
 
 namespace mpsfr {
 namespace {
@@ -147,6 +151,181 @@ __device__ __forceinline__ double sgpr(double x) {
     const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(b & 0xffffffffll));
     const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(b >> 32));
     return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)lo);
+}
+
+// ------------------------------------------------------------------------------------------
+// The Levenberg-Marquardt core of the three fits, over NP variables.
+// ------------------------------------------------------------------------------------------
+
+constexpr double kFitIllCond = 100.0;       // MPSFR_FIT_ILL_CONDITIONED, include/mpsfr.h
+constexpr double kFitMaxE = 0.95;           // |e| bound of the step acceptance test of the elliptical models
+#ifndef MPSFR_FIT_MAXIT
+#define MPSFR_FIT_MAXIT 200
+#endif
+constexpr int kFitMaxIt = MPSFR_FIT_MAXIT;  // cap of the LM iterations
+constexpr double kFitMu0 = 1.0e-2, kFitMuMax = 1.0e15;      // damping: start value, and where it gives up
+
+template <typename T, int NP>
+struct FitNormEq {
+    T a[NP * (NP + 1) / 2];   // upper triangle of J^T [W] J, row-major: (0,0)(0,1)..(0,NP-1)(1,1)..
+    T g[NP];                  // J^T [W] r
+    T chi2;
+};
+
+// index of the diagonal element (k, k) in the row-major upper triangle
+template <int NP>
+__host__ __device__ constexpr int fit_diag(int k) { return k * NP - k * (k - 1) / 2; }
+
+// Cholesky factor of the Marquardt-scaled normal matrix  A'_ij = A_ij / (d_i d_j) + mu delta_ij,
+// d_i = sqrt(A_ii) -- the same system as (A + mu diag A) x = -g, but with a unit diagonal, which
+// is what lets the float phase factor it in float.  Fully unrolled: the factor lives in registers
+// (dynamic indexing put it in scratch).  Li holds 1 / L_ii.  Returns false if not positive definite.
+// ROW_FIRST: L_ji (j > i) is scaled as (a d_j^-1) d_i^-1 (k_fit) instead of (a d_i^-1) d_j^-1 (k_fit_ell, k_fit_obs).
+template <int NP, typename S, typename T, bool ROW_FIRST = false>
+__device__ __forceinline__ bool fit_chol(const FitNormEq<T, NP>& ne, S mu, S L[NP][NP], S Li[NP], S id[NP]) {
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        const S d = (S)ne.a[fit_diag<NP>(i)];
+        ok = ok && (d > (S)0);
+        id[i] = fit_rsqrt<S>(d);
+    }
+    {
+        int k = 0;
+#pragma unroll
+        for (int i = 0; i < NP; ++i)
+#pragma unroll
+            for (int j = i; j < NP; ++j) {
+                L[j][i] = ROW_FIRST ? (S)ne.a[k] * id[j] * id[i] : (S)ne.a[k] * id[i] * id[j];
+                ++k;
+            }
+    }
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        S s = (S)1 + mu;
+#pragma unroll
+        for (int q = 0; q < j; ++q) s -= L[j][q] * L[j][q];
+        ok = ok && (s > (S)0);
+        Li[j] = fit_rsqrt<S>(s);
+        L[j][j] = s * Li[j];
+#pragma unroll
+        for (int i = j + 1; i < NP; ++i) {
+            S t = L[i][j];
+#pragma unroll
+            for (int q = 0; q < j; ++q) t -= L[i][q] * L[j][q];
+            L[i][j] = t * Li[j];
+        }
+    }
+    return ok;
+}
+
+// x = A^-1 b through the factor of fit_chol (b and x in unscaled units)
+template <int NP, typename S, typename X>
+__device__ __forceinline__ void fit_chol_solve(const S L[NP][NP], const S Li[NP], const S id[NP], const S b[NP],
+                                               X* x) {
+    S y[NP], z[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        S t = b[i] * id[i];
+#pragma unroll
+        for (int q = 0; q < i; ++q) t -= L[i][q] * y[q];
+        y[i] = t * Li[i];
+    }
+#pragma unroll
+    for (int i = NP - 1; i >= 0; --i) {
+        S t = y[i];
+#pragma unroll
+        for (int q = i + 1; q < NP; ++q) t -= L[q][i] * z[q];
+        z[i] = t * Li[i];
+    }
+#pragma unroll
+    for (int i = 0; i < NP; ++i) x[i] = (X)(z[i] * id[i]);
+}
+
+// solve (A + mu diag(A)) x = -g; S = arithmetic type of the factorisation
+template <int NP, typename S, typename T, bool ROW_FIRST = false>
+__device__ __forceinline__ bool fit_lm_solve(const FitNormEq<T, NP>& ne, S mu, S* x) {
+    S L[NP][NP], Li[NP], id[NP], b[NP];
+    if (!fit_chol<NP, S, T, ROW_FIRST>(ne, mu, L, Li, id)) return false;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) b[i] = -(S)ne.g[i];
+    fit_chol_solve<NP, S, S>(L, Li, id, b, x);
+    return true;
+}
+
+// inverse of the symmetric normal matrix: one factorisation, NP back-substitutions; false if singular
+// (in the arithmetic of the normal matrix: the error columns of the mixed mode of k_fit and k_fit_ell need no fp64)
+template <int NP, typename T, bool ROW_FIRST = false>
+__device__ __forceinline__ bool fit_spd_inverse(const FitNormEq<T, NP>& ne, double cov[NP][NP]) {
+    T L[NP][NP], Li[NP], id[NP];
+    if (!fit_chol<NP, T, T, ROW_FIRST>(ne, (T)0, L, Li, id)) return false;
+#pragma unroll
+    for (int c = 0; c < NP; ++c) {
+        T b[NP];
+        double x[NP];
+#pragma unroll
+        for (int k = 0; k < NP; ++k) b[k] = (k == c) ? (T)1 : (T)0;
+        fit_chol_solve<NP, T, double>(L, Li, id, b, x);
+#pragma unroll
+        for (int k = 0; k < NP; ++k) cov[k][c] = x[k];
+    }
+    return true;
+}
+
+// Wave-uniform factors of a model pass at v = (I, p0, q0, w, [e1, e2,] eta at ieta, ...).  With
+// K = 1/a^2 = 4 (2^eta - 1) / w^2:  Q = A x^2 - 2 B x y + C y^2, A = gK (1 - e1), B = gK e2, C = gK (1 + e1),
+// g = 1 / sqrt(1 - e1^2 - e2^2); the circular model has A = C = K, B = 0.
+template <typename RE, bool ELL>
+struct MoffatPar {
+    RE I, p0, q0, n, gK, A, B, C, e1g2, e2g2, w2, nsq2, dKn;
+    __device__ __forceinline__ MoffatPar(const RE* v, int ieta) {
+        I = v[0]; p0 = v[1]; q0 = v[2];
+        n = fit_rcp<RE>(v[ieta]);
+        const RE s_ = fit_exp2m1<RE>(v[ieta]);                // 2^eta - 1
+        const RE iw = fit_rcp<RE>(v[3]);
+        const RE K = (RE)4 * s_ * iw * iw;
+        if constexpr (ELL) {
+            const RE e1 = v[4], e2 = v[5];
+            const RE g2 = fit_rcp<RE>((RE)1 - e1 * e1 - e2 * e2);
+            const RE g = fit_rsqrt<RE>((RE)1 - e1 * e1 - e2 * e2);
+            gK = g * K;
+            A = gK * ((RE)1 - e1); B = gK * e2; C = gK * ((RE)1 + e1);
+            e1g2 = e1 * g2; e2g2 = e2 * g2;
+        } else {
+            gK = K; A = K; B = (RE)0; C = K; e1g2 = (RE)0; e2g2 = (RE)0;
+        }
+        w2 = (RE)2 * iw;
+        nsq2 = n * n * (RE)0.69314718055994530942;          // n^2 ln2: the logarithm is to base 2
+        dKn = (s_ + (RE)1) * (RE)0.69314718055994530942 * fit_rcp<RE>(s_);   // (dK/d eta) / K
+    }
+};
+
+// Start values of eta and the FWHM from the moments ms1 = sum d, ms2 = sum d^2 of the stamp over the disc of radius
+// rm + 1/2 around its brightest pixel `best` (the sums are the caller's).  For a Moffat sampled at its centre
+//     S1 = I pi a^2 / (n - 1)  T1,        T1 = 1 - (1 + R^2/a^2)^(1 - n)
+//     S2 = I^2 pi a^2 / (2n - 1) T2,      T2 = 1 - (1 + R^2/a^2)^(1 - 2n)
+// so (S2/T2) / (I S1/T1) = (n - 1)/(2n - 1) gives n and then a; the truncation factors T1, T2 by fixed-point
+// iteration from T = 1.  Returns false, and leaves the values alone, when the disc is too small (brightest pixel
+// within six pixels of an edge) or the moments have no sign.
+__device__ __forceinline__ bool fit_moment_start(float ms1, float ms2, float best, int rm, float* eta0, double* fw0) {
+    const float bf = best, r2 = ((float)rm + 0.5f) * ((float)rm + 0.5f);      // (the caller's disc: one value)
+    if (!(rm >= 6 && ms1 > 0.f && best > 0.f)) return false;
+    float t1 = 1.f, t2 = 1.f, nn = 2.5f, a2 = 1.f;
+#pragma unroll 1
+    for (int k = 0; k < 6; ++k) {
+        float rho = (ms2 * t1) * __builtin_amdgcn_rcpf(bf * ms1 * t2);
+        rho = fminf(fmaxf(rho, 0.05f), 0.47f);
+        nn = (1.f - rho) * __builtin_amdgcn_rcpf(1.f - 2.f * rho);
+        nn = fminf(fmaxf(nn, 1.1f), 15.f);
+        a2 = ms1 * (nn - 1.f) * __builtin_amdgcn_rcpf(t1 * bf * 3.14159265f);
+        const float lx = __builtin_amdgcn_logf(1.f + r2 * __builtin_amdgcn_rcpf(a2));
+        t1 = 1.f - __builtin_amdgcn_exp2f((1.f - nn) * lx);
+        t2 = 1.f - __builtin_amdgcn_exp2f((1.f - 2.f * nn) * lx);
+    }
+    *eta0 = __builtin_amdgcn_rcpf(nn);
+    const float w = 2.f * __builtin_amdgcn_sqrtf(a2 * (__builtin_amdgcn_exp2f(*eta0) - 1.f));
+    if (w == w) *fw0 = fmin(fmax((double)w, 1.5), (double)NS);
+    return true;
 }
 
 }  // namespace

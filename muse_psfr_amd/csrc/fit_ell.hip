@@ -8,7 +8,9 @@
 // has a singular normal matrix, and at e1 = e2 = 0 the model is k_fit's (stamps.hip).
 // The structure is k_fit's: one wave per stamp with the stamp in LDS, wave-wide sums on the DPP path, wave-uniform
 // Levenberg-Marquardt state (Marquardt scaling, Nielsen's damping update) in the variables
-// (I, p0, q0, w = geometric-mean FWHM, e1, e2, eta = 1/n).  Mixed mode: float iterations, then the fp64 gradient
+// (I, p0, q0, w = geometric-mean FWHM, e1, e2, eta = 1/n).  The normal equations, their factorisation, solve and
+// inverse, the model factors (MoffatPar), the moment start and the constants are fit_common.h's, shared by the
+// three fits.  Mixed mode: float iterations, then the fp64 gradient
 // polish with the last normal matrix; f64 mode: fp64 iterations throughout.
 #include "device_common.h"
 #include "fit_common.h"
@@ -19,43 +21,7 @@ namespace {
 
 constexpr int NPE = 7;                       // LM variables
 constexpr int NAE = NPE * (NPE + 1) / 2;     // upper triangle of the normal matrix
-constexpr double kEllIllCond = 100.0;        // MPSFR_FIT_ILL_CONDITIONED, include/mpsfr.h (the rule of k_fit)
-constexpr double kEllMaxE = 0.95;            // |e| bound of the step acceptance test
-constexpr int kEllMaxIt = 200;
 constexpr int kEllPolishMax = 8;
-
-template <typename T>
-struct EllNormEq {
-    T a[NAE];   // upper triangle of J^T J, row-major
-    T g[NPE];   // J^T r
-    T chi2;
-};
-
-// index of the diagonal element (k, k) in the row-major upper triangle
-__host__ __device__ constexpr int ell_diag(int k) { return k * NPE - k * (k - 1) / 2; }
-
-// Wave-uniform factors of a model pass at v = (I, p0, q0, w, e1, e2, eta).  With K = 1/a^2 = 4 (2^eta - 1) / w^2:
-// Q = A x^2 - 2 B x y + C y^2, A = gK (1 - e1), B = gK e2, C = gK (1 + e1).
-template <typename RE>
-struct EllPar {
-    RE I, p0, q0, n, gK, A, B, C, e1g2, e2g2, w2, nsq2, dKn;
-    __device__ __forceinline__ EllPar(const RE* v) {
-        I = v[0]; p0 = v[1]; q0 = v[2];
-        n = fit_rcp<RE>(v[6]);
-        const RE s_ = fit_exp2m1<RE>(v[6]);                   // 2^eta - 1
-        const RE iw = fit_rcp<RE>(v[3]);
-        const RE K = (RE)4 * s_ * iw * iw;
-        const RE e1 = v[4], e2 = v[5];
-        const RE g2 = fit_rcp<RE>((RE)1 - e1 * e1 - e2 * e2);
-        const RE g = fit_rsqrt<RE>((RE)1 - e1 * e1 - e2 * e2);
-        gK = g * K;
-        A = gK * ((RE)1 - e1); B = gK * e2; C = gK * ((RE)1 + e1);
-        e1g2 = e1 * g2; e2g2 = e2 * g2;
-        w2 = (RE)2 * iw;
-        nsq2 = n * n * (RE)0.69314718055994530942;          // n^2 ln2: the logarithm is to base 2
-        dKn = (s_ + (RE)1) * (RE)0.69314718055994530942 * fit_rcp<RE>(s_);   // (dK/d eta) / K
-    }
-};
 
 // Normal equations of the elliptical model over the lane's 25 pixels, summed over the wave (every lane ends up
 // with the totals).  Pixel map of k_fit's passes: the lane is a cell (lr, lc) of an 8 x 8 block and the 25 blocks
@@ -64,8 +30,8 @@ struct EllPar {
 //   d/de1 = c (gK (x^2 - y^2) - e1 g^2 Q)      d/de2 = c (2 gK x y - e2 g^2 Q)
 //   d/deta = model n^2 ln(1+Q) - c Q (dK/deta)/K
 template <typename RE>
-__device__ __forceinline__ void ell_accumulate(const RE* pix, int lane, const RE* v, EllNormEq<RE>& ne) {
-    const EllPar<RE> P(v);
+__device__ __forceinline__ void ell_accumulate(const RE* pix, int lane, const RE* v, FitNormEq<RE, NPE>& ne) {
+    const MoffatPar<RE, true> P(v, 6);
     RE a[NAE], g[NPE], chi2 = (RE)0;
 #pragma unroll
     for (int k = 0; k < NAE; ++k) a[k] = (RE)0;
@@ -118,7 +84,7 @@ __device__ __forceinline__ void ell_accumulate(const RE* pix, int lane, const RE
 // chi2 alone at v (the residual pass without the Jacobian)
 template <typename RE>
 __device__ __forceinline__ RE ell_chi2(const RE* pix, int lane, const RE* v) {
-    const EllPar<RE> P(v);
+    const MoffatPar<RE, true> P(v, 6);
     RE cs[5] = {(RE)0, (RE)0, (RE)0, (RE)0, (RE)0};
     const RE lrf = (RE)(lane >> 3) - P.p0, lcf = (RE)(lane & 7) - P.q0;
     const RE* pl = pix + (lane >> 3) * NS + (lane & 7);
@@ -184,98 +150,6 @@ __device__ __forceinline__ void ell_gradient(const double* __restrict__ src, int
     *chi2out = (double)wave_total(c2sum);
 }
 
-// Cholesky factor of the Marquardt-scaled normal matrix A'_ij = A_ij / (d_i d_j) + mu delta_ij, d_i = sqrt(A_ii)
-// (chol5 of stamps.hip for seven variables).  Li holds 1 / L_ii.  Returns false if not positive definite.
-template <typename S, typename T>
-__device__ __forceinline__ bool chol7(const EllNormEq<T>& ne, S mu, S L[NPE][NPE], S Li[NPE], S id[NPE]) {
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < NPE; ++i) {
-        const S d = (S)ne.a[ell_diag(i)];
-        ok = ok && (d > (S)0);
-        id[i] = fit_rsqrt<S>(d);
-    }
-    {
-        int k = 0;
-#pragma unroll
-        for (int i = 0; i < NPE; ++i)
-#pragma unroll
-            for (int j = i; j < NPE; ++j) {
-                L[j][i] = (S)ne.a[k] * id[i] * id[j];
-                ++k;
-            }
-    }
-#pragma unroll
-    for (int j = 0; j < NPE; ++j) {
-        S s = (S)1 + mu;
-#pragma unroll
-        for (int q = 0; q < j; ++q) s -= L[j][q] * L[j][q];
-        ok = ok && (s > (S)0);
-        Li[j] = fit_rsqrt<S>(s);
-        L[j][j] = s * Li[j];
-#pragma unroll
-        for (int i = j + 1; i < NPE; ++i) {
-            S t = L[i][j];
-#pragma unroll
-            for (int q = 0; q < j; ++q) t -= L[i][q] * L[j][q];
-            L[i][j] = t * Li[j];
-        }
-    }
-    return ok;
-}
-
-// x = A^-1 b through the factor of chol7 (b and x in unscaled units)
-template <typename S, typename X>
-__device__ __forceinline__ void chol7_solve(const S L[NPE][NPE], const S Li[NPE], const S id[NPE], const S b[NPE],
-                                            X* x) {
-    S y[NPE], z[NPE];
-#pragma unroll
-    for (int i = 0; i < NPE; ++i) {
-        S t = b[i] * id[i];
-#pragma unroll
-        for (int q = 0; q < i; ++q) t -= L[i][q] * y[q];
-        y[i] = t * Li[i];
-    }
-#pragma unroll
-    for (int i = NPE - 1; i >= 0; --i) {
-        S t = y[i];
-#pragma unroll
-        for (int q = i + 1; q < NPE; ++q) t -= L[q][i] * z[q];
-        z[i] = t * Li[i];
-    }
-#pragma unroll
-    for (int i = 0; i < NPE; ++i) x[i] = (X)(z[i] * id[i]);
-}
-
-// solve (A + mu diag(A)) x = -g
-template <typename S, typename T>
-__device__ __forceinline__ bool ell_solve(const EllNormEq<T>& ne, S mu, S* x) {
-    S L[NPE][NPE], Li[NPE], id[NPE], b[NPE];
-    if (!chol7<S, T>(ne, mu, L, Li, id)) return false;
-#pragma unroll
-    for (int i = 0; i < NPE; ++i) b[i] = -(S)ne.g[i];
-    chol7_solve<S, S>(L, Li, id, b, x);
-    return true;
-}
-
-// inverse of the symmetric normal matrix (in its own arithmetic type); false if singular
-template <typename T>
-__device__ __forceinline__ bool ell_inverse(const EllNormEq<T>& ne, double cov[NPE][NPE]) {
-    T L[NPE][NPE], Li[NPE], id[NPE];
-    if (!chol7<T, T>(ne, (T)0, L, Li, id)) return false;
-#pragma unroll
-    for (int c = 0; c < NPE; ++c) {
-        T b[NPE];
-        double x[NPE];
-#pragma unroll
-        for (int k = 0; k < NPE; ++k) b[k] = (k == c) ? (T)1 : (T)0;
-        chol7_solve<T, double>(L, Li, id, b, x);
-#pragma unroll
-        for (int k = 0; k < NPE; ++k) cov[k][c] = x[k];
-    }
-    return true;
-}
-
 // size of a step dx towards vn: relative for I, p0, q0, w, eta (k_fit's rule), absolute for e1, e2 (|e| < 1, and
 // e = 0 is the round stamp)
 template <typename S>
@@ -292,7 +166,7 @@ __device__ __forceinline__ S ell_step_size(const S* dx, const S* vn) {
 template <typename S>
 __device__ __forceinline__ bool ell_inside(const S* vn) {
     return vn[3] > (S)1.0e-3 && vn[6] > (S)1.0e-3 && vn[6] < (S)1.0e2 &&
-           vn[4] * vn[4] + vn[5] * vn[5] <= (S)(kEllMaxE * kEllMaxE);
+           vn[4] * vn[4] + vn[5] * vn[5] <= (S)(kFitMaxE * kFitMaxE);
 }
 
 // one wave per stamp; RE = float: mixed mode (float iterations + fp64 polish), RE = double: f64 mode
@@ -364,23 +238,7 @@ k_fit_ell(int nstamp, const double* __restrict__ stamps, double* __restrict__ fi
     double fw0 = 2.0 * sqrt((double)cnt / kPi);
     fw0 = fmin(fmax(fw0, 1.5), (double)NS);
     float eta0 = 0.4f, e10 = 0.f, e20 = 0.f;
-    if (rm >= 6 && ms1 > 0.f && (float)best > 0.f) {
-        const float bf = (float)best, r2 = ((float)rm + 0.5f) * ((float)rm + 0.5f);
-        float t1 = 1.f, t2 = 1.f, nn = 2.5f, a2 = 1.f;
-#pragma unroll 1
-        for (int k = 0; k < 6; ++k) {
-            float rho = (ms2 * t1) * __builtin_amdgcn_rcpf(bf * ms1 * t2);
-            rho = fminf(fmaxf(rho, 0.05f), 0.47f);
-            nn = (1.f - rho) * __builtin_amdgcn_rcpf(1.f - 2.f * rho);
-            nn = fminf(fmaxf(nn, 1.1f), 15.f);
-            a2 = ms1 * (nn - 1.f) * __builtin_amdgcn_rcpf(t1 * bf * 3.14159265f);
-            const float lx = __builtin_amdgcn_logf(1.f + r2 * __builtin_amdgcn_rcpf(a2));
-            t1 = 1.f - __builtin_amdgcn_exp2f((1.f - nn) * lx);
-            t2 = 1.f - __builtin_amdgcn_exp2f((1.f - 2.f * nn) * lx);
-        }
-        eta0 = __builtin_amdgcn_rcpf(nn);
-        const float w = 2.f * __builtin_amdgcn_sqrtf(a2 * (__builtin_amdgcn_exp2f(eta0) - 1.f));
-        if (w == w) fw0 = fmin(fmax((double)w, 1.5), (double)NS);
+    if (fit_moment_start(ms1, ms2, (float)best, rm, &eta0, &fw0)) {
         const float tr = mxx + myy;
         if (tr > 0.f) {
             e10 = (mxx - myy) / tr;
@@ -395,15 +253,15 @@ k_fit_ell(int nstamp, const double* __restrict__ stamps, double* __restrict__ fi
     }
     S v[NPE] = {(S)best, (S)p0i, (S)q0i, (S)fw0, (S)e10, (S)e20, (S)eta0};
     const S tol = sizeof(RE) == 4 ? (S)1.0e-3 : (S)1.0e-10;
-    EllNormEq<RE> ne;
+    FitNormEq<RE, NPE> ne;
     ell_accumulate<RE>(sp, lane, v, ne);
-    S mu = (S)1.0e-2, nu = (S)2;
-    const S mu_max = (S)1.0e15;
+    S mu = (S)kFitMu0, nu = (S)2;
+    const S mu_max = (S)kFitMuMax;
     int it = 0, status = 1;
-    while (it < kEllMaxIt) {
+    while (it < kFitMaxIt) {
         ++it;
         S dx[NPE];
-        if (!ell_solve<S, RE>(ne, mu, dx)) {
+        if (!fit_lm_solve<NPE, S, RE>(ne, mu, dx)) {
             mu *= nu;
             nu *= (S)2;
             if (mu > mu_max) { status = 2; break; }
@@ -426,13 +284,13 @@ k_fit_ell(int nstamp, const double* __restrict__ stamps, double* __restrict__ fi
             status = 0;
             break;
         }
-        EllNormEq<RE> nn;
+        FitNormEq<RE, NPE> nn;
         S rho = (S)-1;
         if (inside) {
             ell_accumulate<RE>(sp, lane, vn, nn);
             S pred = (S)0;         // predicted decrease of chi2: dx^T (mu D dx - g)
 #pragma unroll
-            for (int k = 0; k < NPE; ++k) pred += dx[k] * (mu * (S)ne.a[ell_diag(k)] * dx[k] - (S)ne.g[k]);
+            for (int k = 0; k < NPE; ++k) pred += dx[k] * (mu * (S)ne.a[fit_diag<NPE>(k)] * dx[k] - (S)ne.g[k]);
             rho = ((S)ne.chi2 - (S)nn.chi2) * fit_rcp<S>(pred);    // NaN -> rejected
         }
         if (rho > (S)0) {
@@ -456,14 +314,14 @@ k_fit_ell(int nstamp, const double* __restrict__ stamps, double* __restrict__ fi
     if constexpr (sizeof(RE) == 4) {
         // the fp64 polish of k_fit: steps -A^-1 g, g the fp64 gradient, A the float normal matrix of the last
         // iteration
-        EllNormEq<double> np;
+        FitNormEq<double, NPE> np;
 #pragma unroll
         for (int k = 0; k < NAE; ++k) np.a[k] = (double)ne.a[k];
         np.chi2 = -1.0;
         for (int pz = 0; pz < kEllPolishMax && status != 2; ++pz) {
             ell_gradient(src, lane, vd, np.g, &np.chi2);
             double dx[NPE], vn[NPE];
-            if (!ell_solve<double, double>(np, 1.0e-10, dx)) break;
+            if (!fit_lm_solve<NPE, double, double>(np, 1.0e-10, dx)) break;
 #pragma unroll
             for (int k = 0; k < NPE; ++k) vn[k] = vd[k] + dx[k];
             const double rel = ell_step_size<double>(dx, vn);
@@ -477,7 +335,7 @@ k_fit_ell(int nstamp, const double* __restrict__ stamps, double* __restrict__ fi
         if (chi2 < 0.0) {              // a residual pass at the final point, in fp64
             double cs = 0.0;
             {
-                const EllPar<double> P(vd);
+                const MoffatPar<double, true> P(vd, 6);
                 const double lrd = (double)(lane >> 3) - P.p0, lcd = (double)(lane & 7) - P.q0;
                 const double* pl = src + (lane >> 3) * NS + (lane & 7);
 #pragma unroll 1
@@ -522,7 +380,7 @@ k_fit_ell(int nstamp, const double* __restrict__ stamps, double* __restrict__ fi
 #pragma unroll
     for (int k = 21; k < NFIT_ELL; ++k) o[k] = 0.0;
     double cov[NPE][NPE];
-    if (ell_inverse(ne, cov)) {
+    if (fit_spd_inverse<NPE, RE>(ne, cov)) {
         const double s = chi2 / (double)(NS * NS - NPE);
         auto quad = [&](const double* gr) {       // s g^T cov g over the variables of gr (7 entries)
             double q = 0.0;
@@ -554,7 +412,7 @@ k_fit_ell(int nstamp, const double* __restrict__ stamps, double* __restrict__ fi
         const double gfl[NPE] = {kPi * al * al / (n - 1.0), 0, 0, 2.0 * flux / w, 0, 0,
                                  flux * (n * n / (n - 1.0) - p2 * 0.69314718055994530942 / s2)};
         o[20] = quad(gfl);
-        if (n * n * sqrt(fmax(cov[6][6], 0.0)) * fabs(I) >= kEllIllCond) status |= 4;
+        if (n * n * sqrt(fmax(cov[6][6], 0.0)) * fabs(I) >= kFitIllCond) status |= 4;
     } else {
         for (int k = 11; k <= 17; ++k) o[k] = 0.0;
         o[20] = 0.0;

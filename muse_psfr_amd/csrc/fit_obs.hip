@@ -8,7 +8,9 @@
 // load on, so its stored value reaches no sum.
 // The structure is k_fit_ell's: one wave per stamp, 25 pixels per lane in the 8 x 8-block pixel map, wave-wide sums
 // on the DPP path (wave_total), wave-uniform Levenberg-Marquardt state (Marquardt scaling, Nielsen's damping) in the
-// variables (I, p0, q0, w, [e1, e2,] eta = 1/n, [b]): 5 to 8 of them, chosen at compile time.  New here: the weight
+// variables (I, p0, q0, w, [e1, e2,] eta = 1/n, [b]): 5 to 8 of them, chosen at compile time.  The normal equations,
+// their factorisation, solve and inverse, the model factors (MoffatPar) and the constants are fit_common.h's, shared
+// by the three fits.  New here: the weight
 // plane beside the stamp in LDS, the start values from used pixels only, and the normalisation of data and weights by
 // powers of two (brightest used pixel into [1, 2), largest weight into (1/2, 1]), which is exact and makes a constant
 // factor on the variance plane change no bit of the parameters and errors.
@@ -22,8 +24,6 @@ namespace mpsfr {
 
 namespace {
 
-constexpr double kObsMaxE = 0.95;            // |e| bound of the step acceptance test (fit_ell.hip)
-constexpr int kObsMaxIt = 200;
 constexpr int kObsPolishMax = 12;
 constexpr double kObsPolishSigma = 1.0e-6;   // the polish stops at a step of this fraction of the formal error
 constexpr double kObsMinWeight = 0x1p-100;   // a used pixel keeps a weight > 0 (relative to the largest one)
@@ -38,51 +38,15 @@ struct ObsDim {
     static constexpr int IB = IETA + 1;              // (only with BG)
 };
 
-template <typename T, int NP>
-struct ObsNormEq {
-    T a[NP * (NP + 1) / 2];   // upper triangle of J^T W J, row-major
-    T g[NP];                  // J^T W r
-    T chi2;
-};
-
-template <int NP>
-__host__ __device__ constexpr int obs_diag(int k) { return k * NP - k * (k - 1) / 2; }
-
-// Wave-uniform factors of a model pass (EllPar of fit_ell.hip; the circular variant has A = C = K, B = 0)
-template <typename RE, bool ELL>
-struct ObsPar {
-    RE I, p0, q0, n, gK, A, B, C, e1g2, e2g2, w2, nsq2, dKn;
-    __device__ __forceinline__ ObsPar(const RE* v, int ieta) {
-        I = v[0]; p0 = v[1]; q0 = v[2];
-        n = fit_rcp<RE>(v[ieta]);
-        const RE s_ = fit_exp2m1<RE>(v[ieta]);                // 2^eta - 1
-        const RE iw = fit_rcp<RE>(v[3]);
-        const RE K = (RE)4 * s_ * iw * iw;
-        if constexpr (ELL) {
-            const RE e1 = v[4], e2 = v[5];
-            const RE g2 = fit_rcp<RE>((RE)1 - e1 * e1 - e2 * e2);
-            const RE g = fit_rsqrt<RE>((RE)1 - e1 * e1 - e2 * e2);
-            gK = g * K;
-            A = gK * ((RE)1 - e1); B = gK * e2; C = gK * ((RE)1 + e1);
-            e1g2 = e1 * g2; e2g2 = e2 * g2;
-        } else {
-            gK = K; A = K; B = (RE)0; C = K; e1g2 = (RE)0; e2g2 = (RE)0;
-        }
-        w2 = (RE)2 * iw;
-        nsq2 = n * n * (RE)0.69314718055994530942;          // n^2 ln2: the logarithm is to base 2
-        dKn = (s_ + (RE)1) * (RE)0.69314718055994530942 * fit_rcp<RE>(s_);   // (dK/d eta) / K
-    }
-};
-
 // Weighted normal equations over the lane's 25 pixels, summed over the wave (every lane ends up with the totals).
 // pix / wt: the stamp and its weights in LDS (LT), the arithmetic runs in RE.  Derivatives as in fit_ell.hip, with
 // d/db = 1; c = n I (1+Q)^-n / (1 + Q) is taken from the Moffat term alone.
 template <typename RE, typename LT, bool ELL, bool BG>
 __device__ __forceinline__ void obs_accumulate(const LT* pix, const LT* wt, int lane, const RE* v,
-                                               ObsNormEq<RE, ObsDim<ELL, BG>::NP>& ne) {
+                                               FitNormEq<RE, ObsDim<ELL, BG>::NP>& ne) {
     using D = ObsDim<ELL, BG>;
     constexpr int NP = D::NP, NA = D::NA;
-    const ObsPar<RE, ELL> P(v, D::IETA);
+    const MoffatPar<RE, ELL> P(v, D::IETA);
     RE bk = (RE)0;
     if constexpr (BG) bk = v[D::IB];
     RE a[NA], g[NP], chi2 = (RE)0;
@@ -151,7 +115,7 @@ __device__ __forceinline__ void obs_accumulate(const LT* pix, const LT* wt, int 
 template <typename RE, bool ELL, bool BG>
 __device__ __forceinline__ RE obs_chi2(const RE* pix, const RE* wt, int lane, const RE* v) {
     using D = ObsDim<ELL, BG>;
-    const ObsPar<RE, ELL> P(v, D::IETA);
+    const MoffatPar<RE, ELL> P(v, D::IETA);
     RE bk = (RE)0;
     if constexpr (BG) bk = v[D::IB];
     RE cs[5] = {(RE)0, (RE)0, (RE)0, (RE)0, (RE)0};
@@ -245,97 +209,6 @@ __device__ __forceinline__ void obs_gradient(const double* __restrict__ src, dou
     *chi2out = (double)wave_total(c2sum);
 }
 
-// Cholesky factor of the Marquardt-scaled normal matrix A'_ij = A_ij / (d_i d_j) + mu delta_ij, d_i = sqrt(A_ii)
-// (chol7 of fit_ell.hip for NP variables).  Li holds 1 / L_ii.  Returns false if not positive definite.
-template <int NP, typename S, typename T>
-__device__ __forceinline__ bool obs_chol(const ObsNormEq<T, NP>& ne, S mu, S L[NP][NP], S Li[NP], S id[NP]) {
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        const S d = (S)ne.a[obs_diag<NP>(i)];
-        ok = ok && (d > (S)0);
-        id[i] = fit_rsqrt<S>(d);
-    }
-    {
-        int k = 0;
-#pragma unroll
-        for (int i = 0; i < NP; ++i)
-#pragma unroll
-            for (int j = i; j < NP; ++j) {
-                L[j][i] = (S)ne.a[k] * id[i] * id[j];
-                ++k;
-            }
-    }
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        S s = (S)1 + mu;
-#pragma unroll
-        for (int q = 0; q < j; ++q) s -= L[j][q] * L[j][q];
-        ok = ok && (s > (S)0);
-        Li[j] = fit_rsqrt<S>(s);
-        L[j][j] = s * Li[j];
-#pragma unroll
-        for (int i = j + 1; i < NP; ++i) {
-            S t = L[i][j];
-#pragma unroll
-            for (int q = 0; q < j; ++q) t -= L[i][q] * L[j][q];
-            L[i][j] = t * Li[j];
-        }
-    }
-    return ok;
-}
-
-// x = A^-1 b through the factor of obs_chol (b and x in unscaled units)
-template <int NP, typename S, typename X>
-__device__ __forceinline__ void obs_chol_solve(const S L[NP][NP], const S Li[NP], const S id[NP], const S b[NP],
-                                               X* x) {
-    S y[NP], z[NP];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        S t = b[i] * id[i];
-#pragma unroll
-        for (int q = 0; q < i; ++q) t -= L[i][q] * y[q];
-        y[i] = t * Li[i];
-    }
-#pragma unroll
-    for (int i = NP - 1; i >= 0; --i) {
-        S t = y[i];
-#pragma unroll
-        for (int q = i + 1; q < NP; ++q) t -= L[q][i] * z[q];
-        z[i] = t * Li[i];
-    }
-#pragma unroll
-    for (int i = 0; i < NP; ++i) x[i] = (X)(z[i] * id[i]);
-}
-
-// solve (A + mu diag(A)) x = -g
-template <int NP, typename S, typename T>
-__device__ __forceinline__ bool obs_solve(const ObsNormEq<T, NP>& ne, S mu, S* x) {
-    S L[NP][NP], Li[NP], id[NP], b[NP];
-    if (!obs_chol<NP, S, T>(ne, mu, L, Li, id)) return false;
-#pragma unroll
-    for (int i = 0; i < NP; ++i) b[i] = -(S)ne.g[i];
-    obs_chol_solve<NP, S, S>(L, Li, id, b, x);
-    return true;
-}
-
-// inverse of the symmetric normal matrix, in fp64; false if singular
-template <int NP>
-__device__ __forceinline__ bool obs_inverse(const ObsNormEq<double, NP>& ne, double cov[NP][NP]) {
-    double L[NP][NP], Li[NP], id[NP];
-    if (!obs_chol<NP, double, double>(ne, 0.0, L, Li, id)) return false;
-#pragma unroll
-    for (int c = 0; c < NP; ++c) {
-        double b[NP], x[NP];
-#pragma unroll
-        for (int k = 0; k < NP; ++k) b[k] = (k == c) ? 1.0 : 0.0;
-        obs_chol_solve<NP, double, double>(L, Li, id, b, x);
-#pragma unroll
-        for (int k = 0; k < NP; ++k) cov[k][c] = x[k];
-    }
-    return true;
-}
-
 // size of a step dx towards vn: relative for I, p0, q0, w, eta (k_fit's rule), absolute for e1, e2, and relative to
 // the amplitude for the background (which may be zero)
 template <bool ELL, bool BG, typename S>
@@ -356,7 +229,7 @@ template <bool ELL, bool BG, typename S>
 __device__ __forceinline__ bool obs_inside(const S* vn) {
     using D = ObsDim<ELL, BG>;
     bool in = vn[3] > (S)1.0e-3 && vn[D::IETA] > (S)1.0e-3 && vn[D::IETA] < (S)1.0e2;
-    if constexpr (ELL) in = in && vn[4] * vn[4] + vn[5] * vn[5] <= (S)(kObsMaxE * kObsMaxE);
+    if constexpr (ELL) in = in && vn[4] * vn[4] + vn[5] * vn[5] <= (S)(kFitMaxE * kFitMaxE);
     return in;
 }
 
@@ -501,15 +374,15 @@ k_fit_obs(int nstamp, const double* __restrict__ stamps, const double* __restric
     v[D::IETA] = (S)0.4;
     if constexpr (BG) v[D::IB] = (S)b0;
     const S tol = sizeof(RE) == 4 ? (S)1.0e-3 : (S)1.0e-12;
-    ObsNormEq<RE, NP> ne;
+    FitNormEq<RE, NP> ne;
     obs_accumulate<RE, RE, ELL, BG>(sp, sw, lane, v, ne);
-    S mu = (S)1.0e-2, nu = (S)2;
-    const S mu_max = (S)1.0e15;
+    S mu = (S)kFitMu0, nu = (S)2;
+    const S mu_max = (S)kFitMuMax;
     int it = 0, status = 1;
-    while (it < kObsMaxIt) {
+    while (it < kFitMaxIt) {
         ++it;
         S dx[NP];
-        if (!obs_solve<NP, S, RE>(ne, mu, dx)) {
+        if (!fit_lm_solve<NP, S, RE>(ne, mu, dx)) {
             mu *= nu;
             nu *= (S)2;
             if (mu > mu_max) { status = 2; break; }
@@ -532,13 +405,13 @@ k_fit_obs(int nstamp, const double* __restrict__ stamps, const double* __restric
             status = 0;
             break;
         }
-        ObsNormEq<RE, NP> nn;
+        FitNormEq<RE, NP> nn;
         S rho = (S)-1;
         if (inside) {
             obs_accumulate<RE, RE, ELL, BG>(sp, sw, lane, vn, nn);
             S pred = (S)0;         // predicted decrease of chi2: dx^T (mu D dx - g)
 #pragma unroll
-            for (int k = 0; k < NP; ++k) pred += dx[k] * (mu * (S)ne.a[obs_diag<NP>(k)] * dx[k] - (S)ne.g[k]);
+            for (int k = 0; k < NP; ++k) pred += dx[k] * (mu * (S)ne.a[fit_diag<NP>(k)] * dx[k] - (S)ne.g[k]);
             rho = ((S)ne.chi2 - (S)nn.chi2) * fit_rcp<S>(pred);    // NaN -> rejected
         }
         if (rho > (S)0) {
@@ -562,7 +435,7 @@ k_fit_obs(int nstamp, const double* __restrict__ stamps, const double* __restric
     double chi2 = -1.0;
     // the normal matrix of the covariance, fp64; only nf.a is read after the fit (the f64 mode never writes nf.g and
     // nf.chi2, the mixed mode uses them inside its polish only)
-    ObsNormEq<double, NP> nf;
+    FitNormEq<double, NP> nf;
     if constexpr (sizeof(RE) == 4) {
         // the fp64 polish of k_fit_ell: steps -A^-1 g, g the gradient of the fp64 residuals, A the float normal matrix
         // of the last iteration; it ends once a step is below kObsPolishSigma of the formal error,
@@ -573,7 +446,7 @@ k_fit_obs(int nstamp, const double* __restrict__ stamps, const double* __restric
         for (int pz = 0; pz < kObsPolishMax && status != 2; ++pz) {
             obs_gradient<ELL, BG>(src, scale, sw, lane, vd, nf.g, &nf.chi2);
             double dx[NP], vn[NP];
-            if (!obs_solve<NP, double, double>(nf, 1.0e-10, dx)) break;
+            if (!fit_lm_solve<NP, double, double>(nf, 1.0e-10, dx)) break;
 #pragma unroll
             for (int k = 0; k < NP; ++k) vn[k] = vd[k] + dx[k];
             const double rel = obs_step_size<ELL, BG, double>(dx, vn);
@@ -636,7 +509,7 @@ k_fit_obs(int nstamp, const double* __restrict__ stamps, const double* __restric
     o[23] = (double)nused;
     double cov[NP][NP];
     bool finite = true;
-    if (status != 2 && obs_inverse<NP>(nf, cov)) {
+    if (status != 2 && fit_spd_inverse<NP, double>(nf, cov)) {
         const double s = chi2 / dof;
         auto quad = [&](const double* gr) {       // s g^T cov g over the variables of gr (NP entries)
             double q = 0.0;

@@ -327,18 +327,12 @@ k_khat(const double* __restrict__ gam, const double* __restrict__ alp, cx<R>* __
 // Levenberg-Marquardt (Marquardt scaling, Nielsen's gain-ratio damping update) iterated in the
 // better-conditioned variables (I, p0, q0, w = FWHM, n) -- the minimum is the same point.
 // Per-lane sums run in the evaluation type RE (float in mixed mode, double in f64 mode); the
-// 5x5 solves of the float phase run in float on the Marquardt-scaled matrix.
+// 5x5 solves of the float phase run in float on the Marquardt-scaled matrix.  The normal equations,
+// their factorisation, solve and inverse, the moment start and the constants are fit_common.h's, shared with
+// k_fit_ell and k_fit_obs.
 // ------------------------------------------------------------------------------------------
 
-template <typename T>
-struct NormEqT {
-    T a[15];   // upper triangle of J^T J, row-major: (0,0)(0,1)..(0,4)(1,1)..(4,4)
-    T g[5];    // J^T r
-    T chi2;
-};
-using NormEq = NormEqT<double>;
-
-// Normal equations of the Moffat model at v = (I, p0, q0, w, eta), eta = 1/n,
+// Normal equations (FitNormEq<RE, 5>) of the Moffat model at v = (I, p0, q0, w, eta), eta = 1/n,
 // 1/a^2 = 4 (2^eta - 1) / w^2,
 // over the lane's pixels o = lane + 64 m of the stamp `pix` (LDS), summed over the wave.
 // Cross-lane sums run in the evaluation type: the float phase only has to reach the basin of
@@ -372,7 +366,7 @@ struct NormAcc {
         }
     }
     template <typename F>
-    __device__ __forceinline__ void totals(NormEqT<RE>& ne, F total) const {
+    __device__ __forceinline__ void totals(FitNormEq<RE, 5>& ne, F total) const {
         ne.chi2 = total(chi2);
 #pragma unroll
         for (int k = 0; k < 15; ++k) ne.a[k] = total(a[k]);
@@ -406,7 +400,7 @@ struct NormAcc<float> {
         chi2 += r * r;
     }
     template <typename F>
-    __device__ __forceinline__ void totals(NormEqT<float>& ne, F total) const {
+    __device__ __forceinline__ void totals(FitNormEq<float, 5>& ne, F total) const {
         ne.chi2 = total(chi2);
         const float a[15] = {r0a.x, r0a.y, r0b.x, r0b.y, r0c.x, a11, r1b.x, r1b.y, r1c.x,
                              r2b.x, r2b.y, r2c.x, a33, r3c.x, r4c.x};
@@ -420,7 +414,7 @@ struct NormAcc<float> {
 
 template <typename RE>
 __device__ __forceinline__ void moffat_accumulate(const RE* pix, int lane, const RE* v,
-                                                  NormEqT<RE>& ne) {
+                                                  FitNormEq<RE, 5>& ne) {
     constexpr int NPX = NS * NS / 64;
     NormAcc<RE> acc;
     acc.zero();
@@ -484,7 +478,7 @@ __device__ __forceinline__ void moffat_accumulate(const RE* pix, int lane, const
 // The accumulators hold one partial sum per half (42 registers instead of 21): the kernel's 156
 // registers at three waves per SIMD have the room (k_fit, MPSFR_FIT_WAVES).
 __device__ __forceinline__ void moffat_accumulate_pairs(const float* pix, int lane, const float* v,
-                                                        NormEqT<float>& ne) {
+                                                        FitNormEq<float, 5>& ne) {
     f32x2 A[15], G[5], C = {0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < 15; ++k) A[k] = f32x2{0.f, 0.f};
@@ -556,7 +550,7 @@ __device__ __forceinline__ void moffat_accumulate_pairs(const float* pix, int la
 
 // the float pass of the LM phase (pairs of pixels) / the generic pass
 template <typename RE>
-__device__ __forceinline__ void lm_accumulate(const RE* pix, int lane, const RE* v, NormEqT<RE>& ne) {
+__device__ __forceinline__ void lm_accumulate(const RE* pix, int lane, const RE* v, FitNormEq<RE, 5>& ne) {
     if constexpr (sizeof(RE) == 4 && MPSFR_FIT_PAIRS) moffat_accumulate_pairs(pix, lane, v, ne);
     else moffat_accumulate<RE>(pix, lane, v, ne);
 }
@@ -635,108 +629,6 @@ __device__ __forceinline__ void moffat_gradient(const TS* __restrict__ src, int 
     *chi2out = (double)wave_total(c2sum);
 }
 
-// Cholesky factor of the Marquardt-scaled normal matrix  A'_ij = A_ij / (d_i d_j) + mu delta_ij,
-// d_i = sqrt(A_ii) -- the same system as (A + mu diag A) x = -g, but with a unit diagonal, which
-// is what lets the float phase factor it in float.  Fully unrolled: the factor lives in registers
-// (dynamic indexing put it in scratch).  Li holds 1 / L_ii.  Returns false if not positive definite.
-template <typename S, typename T>
-__device__ __forceinline__ bool chol5(const NormEqT<T>& ne, S mu, S L[5][5], S Li[5], S id[5]) {
-    S A[5][5];
-    {
-        int k = 0;
-#pragma unroll
-        for (int i = 0; i < 5; ++i)
-#pragma unroll
-            for (int j = i; j < 5; ++j) {
-                A[i][j] = (S)ne.a[k];
-                A[j][i] = (S)ne.a[k];
-                ++k;
-            }
-    }
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        ok = ok && (A[i][i] > (S)0);
-        id[i] = fit_rsqrt<S>(A[i][i]);
-    }
-#pragma unroll
-    for (int i = 0; i < 5; ++i)
-#pragma unroll
-        for (int j = 0; j < 5; ++j) L[i][j] = A[i][j] * id[i] * id[j];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) L[i][i] = (S)1 + mu;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        S s = L[j][j];
-#pragma unroll
-        for (int q = 0; q < j; ++q) s -= L[j][q] * L[j][q];
-        ok = ok && (s > (S)0);
-        Li[j] = fit_rsqrt<S>(s);
-        L[j][j] = s * Li[j];
-#pragma unroll
-        for (int i = j + 1; i < 5; ++i) {
-            S t = L[i][j];
-#pragma unroll
-            for (int q = 0; q < j; ++q) t -= L[i][q] * L[j][q];
-            L[i][j] = t * Li[j];
-        }
-    }
-    return ok;
-}
-
-// x = A^-1 b through the factor of chol5 (b and x in unscaled units)
-template <typename S, typename X>
-__device__ __forceinline__ void chol5_solve(const S L[5][5], const S Li[5], const S id[5],
-                                            const S b[5], X* x) {
-    S y[5], z[5];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        S t = b[i] * id[i];
-#pragma unroll
-        for (int q = 0; q < i; ++q) t -= L[i][q] * y[q];
-        y[i] = t * Li[i];
-    }
-#pragma unroll
-    for (int i = 4; i >= 0; --i) {
-        S t = y[i];
-#pragma unroll
-        for (int q = i + 1; q < 5; ++q) t -= L[q][i] * z[q];
-        z[i] = t * Li[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 5; ++i) x[i] = (X)(z[i] * id[i]);
-}
-
-// solve (A + mu diag(A)) x = -g; S = arithmetic type of the factorisation
-template <typename S, typename T>
-__device__ __forceinline__ bool lm_solve(const NormEqT<T>& ne, S mu, S* x) {
-    S L[5][5], Li[5], id[5], b[5];
-    if (!chol5<S, T>(ne, mu, L, Li, id)) return false;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) b[i] = -(S)ne.g[i];
-    chol5_solve<S, S>(L, Li, id, b, x);
-    return true;
-}
-
-// inverse of the symmetric 5x5: one factorisation, five back-substitutions; false if singular
-// (in the arithmetic of the normal matrix: the error columns of the mixed mode need no fp64)
-template <typename T>
-__device__ __forceinline__ bool spd_inverse(const NormEqT<T>& ne, double cov[5][5]) {
-    T L[5][5], Li[5], id[5];
-    if (!chol5<T, T>(ne, (T)0, L, Li, id)) return false;
-#pragma unroll
-    for (int c = 0; c < 5; ++c) {
-        T b[5];
-        double x[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) b[k] = (k == c) ? (T)1 : (T)0;
-        chol5_solve<T, double>(L, Li, id, b, x);
-#pragma unroll
-        for (int k = 0; k < 5; ++k) cov[k][c] = x[k];
-    }
-    return true;
-}
-
 // A polish step of relative size `rel` leaves an error of about c * rel, c = the contraction
 // factor of the iteration (error of the float Gauss-Newton matrix, <~ 1e-2): steps below 1e-4 end
 // the polish without a further gradient pass (error <~ 1e-6, under what the fp32 stamps allow).
@@ -754,8 +646,6 @@ __device__ __forceinline__ bool spd_inverse(const NormEqT<T>& ne, double cov[5][
 // registers (2 waves).
 template <typename RE>
 constexpr int fit_min_waves() { return sizeof(RE) == 4 ? MPSFR_FIT_WAVES : 2; }
-
-constexpr double kFitIllCond = 100.0;       // MPSFR_FIT_ILL_CONDITIONED, include/mpsfr.h
 
 #ifndef MPSFR_FIT_MOMENT_START
 #define MPSFR_FIT_MOMENT_START 1
@@ -828,12 +718,8 @@ k_fit(int nstamp, const TS* __restrict__ stamps, double* __restrict__ fit, doubl
     // Start values.  The LM phase costs one pass over the stamp per iteration, so a start inside the
     // basin of quadratic convergence is worth a few hundred instructions of setup.  Moments of the
     // stamp over the largest disc around the brightest pixel that fits the stamp, R = (distance to the
-    // nearest edge) + 1/2: for a Moffat sampled at its centre
-    //     S1 = sum d   = I pi a^2 / (n - 1)  T1,   T1 = 1 - (1 + R^2/a^2)^(1 - n)
-    //     S2 = sum d^2 = I^2 pi a^2 / (2n - 1) T2,  T2 = 1 - (1 + R^2/a^2)^(1 - 2n)
-    // so (S2/T2) / (I S1/T1) = (n - 1)/(2n - 1) gives n and then a; the truncation factors T1, T2 by
-    // fixed-point iteration from T = 1 (five rounds: eta to ~0.01, FWHM to 1 % on the bench stamps, which
-    // are Moffat-like but not Moffats).  Mean LM passes per stamp 3.07 -> 2.34 on the bench workload,
+    // nearest edge) + 1/2, give n and a (fit_moment_start: eta to ~0.01, FWHM to 1 % on the bench stamps,
+    // which are Moffat-like but not Moffats).  Mean LM passes per stamp 3.07 -> 2.34 on the bench workload,
     // 3.69 -> 2.86 on the native-grid goldens (NumPy study with the iteration rules of this kernel); a
     // brightest pixel within six pixels of an edge (caller stamps) falls back to the half-maximum area
     // and n = 2.5.  The least-squares minimum is unique: the start only sets the
@@ -879,24 +765,7 @@ k_fit(int nstamp, const TS* __restrict__ stamps, double* __restrict__ fit, doubl
     double fw0 = 2.0 * sqrt((double)cnt / kPi);
     fw0 = fmin(fmax(fw0, 1.5), (double)NS);
     float eta0 = 0.4f;
-    if (MPSFR_FIT_MOMENT_START && rm >= 6 && ms1 > 0.f && (float)best > 0.f) {
-        const float bf = (float)best, r2 = ((float)rm + 0.5f) * ((float)rm + 0.5f);
-        float t1 = 1.f, t2 = 1.f, nn = 2.5f, a2 = 1.f;
-#pragma unroll 1
-        for (int k = 0; k < 6; ++k) {
-            float rho = (ms2 * t1) * __builtin_amdgcn_rcpf(bf * ms1 * t2);
-            rho = fminf(fmaxf(rho, 0.05f), 0.47f);
-            nn = (1.f - rho) * __builtin_amdgcn_rcpf(1.f - 2.f * rho);
-            nn = fminf(fmaxf(nn, 1.1f), 15.f);
-            a2 = ms1 * (nn - 1.f) * __builtin_amdgcn_rcpf(t1 * bf * 3.14159265f);
-            const float lx = __builtin_amdgcn_logf(1.f + r2 * __builtin_amdgcn_rcpf(a2));
-            t1 = 1.f - __builtin_amdgcn_exp2f((1.f - nn) * lx);
-            t2 = 1.f - __builtin_amdgcn_exp2f((1.f - 2.f * nn) * lx);
-        }
-        eta0 = __builtin_amdgcn_rcpf(nn);
-        const float w = 2.f * __builtin_amdgcn_sqrtf(a2 * (__builtin_amdgcn_exp2f(eta0) - 1.f));
-        if (w == w) fw0 = fmin(fmax((double)w, 1.5), (double)NS);
-    }
+    if (MPSFR_FIT_MOMENT_START) fit_moment_start(ms1, ms2, (float)best, rm, &eta0, &fw0);
     // LM variables (I, p0, q0, w = FWHM, eta = 1/n): towards broad, Gaussian-like profiles the
     // model is nearly linear in 1/n, and the valley that n -> large opens in (w, n) stays short --
     // at most 4 iterations where the fit in n took up to 29
@@ -908,19 +777,16 @@ k_fit(int nstamp, const TS* __restrict__ stamps, double* __restrict__ fit, doubl
 #define MPSFR_FIT_TOL_F32 1.0e-3
 #endif
     const S tol = sizeof(RE) == 4 ? (S)MPSFR_FIT_TOL_F32 : (S)1.0e-10;
-    NormEqT<RE> ne;
+    FitNormEq<RE, 5> ne;
     lm_accumulate<RE>(sp, lane, v, ne);
-    S mu = (S)1.0e-2, nu = (S)2;
-    const S mu_max = sizeof(RE) == 4 ? (S)1.0e15f : (S)1.0e15;
+    S mu = (S)kFitMu0, nu = (S)2;
+    const S mu_max = (S)kFitMuMax;
     int it = 0, status = amp_ok ? 1 : 2;
-#ifndef MPSFR_FIT_MAXIT
-#define MPSFR_FIT_MAXIT 200
-#endif
-    const int maxit = amp_ok ? MPSFR_FIT_MAXIT : 0;
+    const int maxit = amp_ok ? kFitMaxIt : 0;
     while (it < maxit) {
         ++it;
         S dx[5];
-        if (!lm_solve<S, RE>(ne, mu, dx)) {
+        if (!fit_lm_solve<5, S, RE, true>(ne, mu, dx)) {
             mu *= nu;
             nu *= (S)2;
             if (mu > mu_max) { status = 2; break; }
@@ -947,16 +813,15 @@ k_fit(int nstamp, const TS* __restrict__ stamps, double* __restrict__ fit, doubl
             status = 0;
             break;
         }
-        NormEqT<RE> nn;
+        FitNormEq<RE, 5> nn;
         S rho = (S)-1;
         if (inside) {
             lm_accumulate<RE>(sp, lane, vn, nn);
             // predicted decrease of chi2: dx^T (mu D dx - g)
             S pred = (S)0;
-            const int dg[5] = {0, 5, 9, 12, 14};
 #pragma unroll
             for (int k = 0; k < 5; ++k)
-                pred += dx[k] * (mu * (S)ne.a[dg[k]] * dx[k] - (S)ne.g[k]);
+                pred += dx[k] * (mu * (S)ne.a[fit_diag<5>(k)] * dx[k] - (S)ne.g[k]);
             rho = ((S)ne.chi2 - (S)nn.chi2) * fit_rcp<S>(pred);    // NaN -> rejected
         }
         if (rho > (S)0) {
@@ -982,7 +847,7 @@ k_fit(int nstamp, const TS* __restrict__ stamps, double* __restrict__ fit, doubl
         // to move beta by a few 1e-4 on flat-topped stamps.  Polish from the float solution with
         // steps  -A^-1 g,  g the fp64 gradient (moffat_gradient), A the float normal matrix of the
         // last LM iteration: one or two steps suffice.
-        NormEq np;
+        FitNormEq<double, 5> np;
 #pragma unroll
         for (int k = 0; k < 15; ++k) np.a[k] = (double)ne.a[k];
         np.chi2 = -1.0;
@@ -992,7 +857,7 @@ k_fit(int nstamp, const TS* __restrict__ stamps, double* __restrict__ fit, doubl
         for (int pz = 0; pz < MPSFR_POLISH_MAX && status != 2; ++pz) {
             moffat_gradient(src, lane, vd, np.g, &np.chi2);
             double dx[5];
-            if (!lm_solve<double, double>(np, 1.0e-10, dx)) break;
+            if (!fit_lm_solve<5, double, double, true>(np, 1.0e-10, dx)) break;
             float rel = 0.f;               // a size, compared with 0.1 / 1e-3 / polish_tol: float
 #pragma unroll
             for (int k = 0; k < 5; ++k)
@@ -1029,7 +894,7 @@ k_fit(int nstamp, const TS* __restrict__ stamps, double* __restrict__ fit, doubl
         o[7] = (double)it;
         double cov[5][5];
         const double dof = (double)(NS * NS - 5);
-        if (spd_inverse(ne, cov)) {
+        if (fit_spd_inverse<5, RE, true>(ne, cov)) {
             const double s = chi2 / dof;
             o[8] = sqrt(fmax(cov[0][0] * s, 0.0));
             o[9] = sqrt(fmax(cov[1][1] * s, 0.0));
