@@ -399,6 +399,49 @@ int mpsfr_fit_stamps_elliptical(mpsfr_ctx* ctx, int nstamp, const double* stamps
 int mpsfr_fit_stamps_observed(mpsfr_ctx* ctx, int nstamp, const double* stamps, const double* var, int flags,
                               double* fit_out, int on_device);
 
+/* PSF-model fit of observed stars: the model stamp itself, resampled, is fitted to the star.  For star stamp d with
+ * optional variance var, and model stamp P ([dimpsf][dimpsf], any real values), the minimum over the used pixels of
+ *     sum (m - d)^2 / var,   m(p, q) = F P~(p - dp, q - dq) + b,   P~(y, x) = sum_kl c(y - k) c(x - l) P[k][l]
+ * with c the Keys cubic-convolution kernel (a = -1/2): c(t) = 1.5|t|^3 - 2.5|t|^2 + 1 for |t| <= 1,
+ * -0.5|t|^3 + 2.5|t|^2 - 4|t| + 2 for 1 < |t| < 2, 0 beyond; P counts as zero outside its pixels (a model whose
+ * wings reach the edge of its stamp is cut there: the background of such a fit is biased).  The result is the weighted
+ * chi2 of the model against the data together with the star's flux, position and background: PSF-fitting photometry.
+ * Variables: (F, dp, dq, [b]); under MPSFR_FIT_FIXED_SHIFT (F, [b]) at the given shift, which is a linear problem
+ * (iterations = 1); b only under MPSFR_FIT_BACKGROUND.  Domain: |dp|, |dq| <= MPSFR_FIT_PSF_MAX_SHIFT pixels.
+ * stamps, var: as mpsfr_fit_stamps_observed (the same rule for the used pixels; var NULL: unit weights).
+ * psf: [npsf][dimpsf][dimpsf]; psf_index: [nstamp] values in 0..npsf-1, the model stamp of every star, or NULL, which
+ * requires npsf == nstamp and pairs them one to one.  shift: [nstamp][2] (dp, dq) start values -- the fixed values
+ * under MPSFR_FIT_FIXED_SHIFT, which requires it -- or NULL: the start is then the brightest used pixel of the star
+ * minus the brightest pixel of the model stamp (each the first maximum in row-major order), brought into the domain.
+ * F and b start from the closed-form weighted linear solve at that shift.
+ * fit_out: [nstamp][MPSFR_NFIT_PSF]:
+ *   0 F  1 dp  2 dq  3 back  4 chi2 (the weighted sum)  5 iterations  6 err_F  7 err_dp  8 err_dq  9 err_back
+ *   10 status  11 n_used  12 flux = F sum(P)  13 err_flux = err_F |sum(P)|  14, 15 zero (reserved)
+ * Fields of variables that are not fitted are 0; a fixed (dp, dq) is echoed.  Errors: sqrt(diag((J^T W J)^-1) chi2 /
+ * dof), dof = n_used - npar, npar = 1 ... 4, the convention of mpsfr_fit_stamps_observed: a caller whose variances are
+ * the true ones divides the errors by sqrt(chi2 / dof).
+ * Status: 0 a minimum; 1 the iteration cap, or an iteration that ended against the bound of the shift (the values are
+ * the last iterate); 2 not fitted (every other field but n_used is 0) or no covariance: an infinite pixel under a
+ * valid variance, n_used < npar + 1, a model stamp that is all zero or not finite, the brightest used pixel of the star
+ * or the brightest pixel of the model stamp outside [2^-40, 2^40] in modulus (both are normalised by powers of two
+ * internally), a used pixel beyond 2^60 times the brightest one in modulus, a singular normal matrix.  The
+ * MPSFR_FIT_ILL_CONDITIONED bit is never set.  A row whose status & 3 is 0 holds finite numbers only.
+ * A star's row depends on that star and its model stamp only, bit for bit.  A constant factor on var changes no
+ * parameter and no error; a factor 2^k on the data with 4^k on var scales F, back, flux and their errors by 2^k.
+ * on_device as mpsfr_fit_stamps_observed: with 1, stamps, var, psf, psf_index, shift and fit_out are all device
+ * pointers and the call is queued on the context stream (e.g. behind a device-output mpsfr_reconstruct_field, whose
+ * stamps are then the model); timed under the fit's profiling id.
+ * MPSFR_E_INVALID before anything is queued, with fit_out untouched: nstamp < 1 or npsf < 1; NULL stamps, psf or
+ * fit_out; unknown flag bits or MPSFR_FIT_ELLIPTICAL; psf_index NULL with npsf != nstamp; MPSFR_FIT_FIXED_SHIFT
+ * without shift; and, for host pointers, an index out of range or a shift that is not finite or outside the domain --
+ * in the device form these two make that row status 2 instead. */
+#define MPSFR_NFIT_PSF 16
+#define MPSFR_FIT_FIXED_SHIFT 4      /* with MPSFR_FIT_BACKGROUND (1); MPSFR_FIT_ELLIPTICAL is refused here */
+#define MPSFR_FIT_PSF_MAX_SHIFT 8.0  /* pixels */
+int mpsfr_fit_stamps_psf(mpsfr_ctx* ctx, int nstamp, const double* stamps, const double* var, int npsf,
+                         const double* psf, const int32_t* psf_index, const double* shift, int flags,
+                         double* fit_out, int on_device);
+
 /* PSF energy metrics of caller-provided stamps: encircled and ensquared energy with exact pixel overlap, and the radii
  * that hold given fractions of the flux -- the non-parametric description of a core + halo PSF, beside the Moffat fits.
  * Pixel (p, q) is the unit square centred on (p, q), in the pixel coordinates of the fits (p0, q0).  Per stamp:

@@ -16,6 +16,9 @@ NMET_HEAD = 8                # leading fields of a metrics row (MPSFR_NMET_HEAD)
 FIT_ILL_CONDITIONED = 4      # status bit of fit_out[14] (MPSFR_FIT_ILL_CONDITIONED, include/mpsfr.h)
 FIT_BACKGROUND = 1           # flags of mpsfr_fit_stamps_observed (MPSFR_FIT_BACKGROUND, MPSFR_FIT_ELLIPTICAL)
 FIT_ELLIPTICAL = 2
+NFIT_PSF = 16                # rows of the PSF-model fit (MPSFR_NFIT_PSF)
+FIT_FIXED_SHIFT = 4          # flag of mpsfr_fit_stamps_psf (MPSFR_FIT_FIXED_SHIFT), beside FIT_BACKGROUND
+FIT_PSF_MAX_SHIFT = 8.0      # |dp|, |dq| bound in pixels (MPSFR_FIT_PSF_MAX_SHIFT)
 DIM_AO = 80
 PREC_MIXED, PREC_F64 = 0, 1
 E_GRID = -3
@@ -95,6 +98,8 @@ def load():
     lib.mpsfr_fit_stamps_elliptical.restype = C.c_int
     lib.mpsfr_fit_stamps_observed.argtypes = [p, C.c_int, p, p, C.c_int, p, C.c_int]
     lib.mpsfr_fit_stamps_observed.restype = C.c_int
+    lib.mpsfr_fit_stamps_psf.argtypes = [p, C.c_int, p, p, C.c_int, p, p, p, C.c_int, p, C.c_int]
+    lib.mpsfr_fit_stamps_psf.restype = C.c_int
     lib.mpsfr_stamp_metrics.argtypes = [p, C.c_int, p, p, C.c_int, dp, C.c_int, dp, C.c_int, dp, p, C.c_int]
     lib.mpsfr_stamp_metrics.restype = C.c_int
     lib.mpsfr_simul_psd.argtypes = [p, C.c_double, C.c_double, C.c_double, C.c_int, dp, C.c_double, C.c_int, u8p, u8p, dp]
@@ -144,7 +149,7 @@ def load():
 
 
 EXPORTS = ['mpsfr_create', 'mpsfr_destroy', 'mpsfr_last_error', 'mpsfr_set_option',
-           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_stamp_metrics', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
+           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_fit_stamps_psf', 'mpsfr_stamp_metrics', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
            'mpsfr_psd_to_psf',
            'mpsfr_convolve_stamps', 'mpsfr_fit_rows', 'mpsfr_sync', 'mpsfr_last_ticket', 'mpsfr_wait', 'mpsfr_abandon',
            'mpsfr_stream', 'mpsfr_stream_wait', 'mpsfr_wait_event',
@@ -814,6 +819,49 @@ class Context:
                                                   C.c_void_p(int(var_ptr)) if var_ptr else None, flags,
                                                   C.c_void_p(int(fit_ptr)), 1))
 
+    def fit_stamps_psf(self, stamps, psf, var=None, psf_index=None, shift=None, background=True, fixed_shift=False):
+        """PSF-model fit of observed stars (mpsfr_fit_stamps_psf): the model stamps `psf` (..., dimpsf, dimpsf), resampled
+        by cubic convolution, are fitted to the stars `stamps` (..., dimpsf, dimpsf) in a scale F, a shift (dp, dq) in
+        pixels and, with `background`, a constant.  (n, NFIT_PSF) rows: 0 F, 1 dp, 2 dq, 3 back, 4 chi2, 5 iterations,
+        6-9 their errors, 10 status, 11 the number of used pixels, 12 flux = F sum(psf), 13 err_flux.  `var` and the
+        mask as fit_stamps_observed.  `psf_index`: (n,) the model stamp of every star, or None for one model stamp per
+        star in order.  `shift`: (n, 2) start values of (dp, dq), or None for the difference of the brightest pixels;
+        `fixed_shift`: hold them (then `shift` is required and the problem is linear)."""
+        st, va = observed_stamps(stamps, var, self.dimpsf)
+        ps, ix, sh, flags = psf_fit_arguments(st.shape[0], psf, psf_index, shift, background, fixed_shift, self.dimpsf)
+        out = np.empty((st.shape[0], NFIT_PSF))
+        vp = C.c_void_p
+        _check(self.lib.mpsfr_fit_stamps_psf(self._h, st.shape[0], st.ctypes.data_as(vp),
+                                             None if va is None else va.ctypes.data_as(vp), ps.shape[0],
+                                             ps.ctypes.data_as(vp), None if ix is None else ix.ctypes.data_as(vp),
+                                             None if sh is None else sh.ctypes.data_as(vp), flags,
+                                             out.ctypes.data_as(vp), 0))
+        return out
+
+    def fit_stamps_psf_device(self, nstamp, stamps_ptr, npsf, psf_ptr, fit_ptr, var_ptr=None, psf_index_ptr=None,
+                              shift_ptr=None, background=True, fixed_shift=False):
+        """Device-buffer form (asynchronous, on_device = 1): `stamps_ptr`, `var_ptr` ([nstamp][dimpsf][dimpsf] float64;
+        var_ptr None: unit weights), `psf_ptr` ([npsf][dimpsf][dimpsf] float64), `psf_index_ptr` ([nstamp] int32, or None
+        with npsf == nstamp), `shift_ptr` ([nstamp][2] float64, or None) and `fit_ptr` ([nstamp][NFIT_PSF] float64) are
+        raw device pointers (int) on this context's GPU; the call is queued on the context stream, after any
+        device-output reconstruct of this context.  An index out of range or a shift outside the domain makes that
+        row status 2."""
+        for name, n in (('nstamp', nstamp), ('npsf', npsf)):
+            if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+                raise ValueError('%s must be a positive integer' % name)
+        if not stamps_ptr or not psf_ptr or not fit_ptr:
+            raise ValueError('stamps_ptr, psf_ptr and fit_ptr must be device pointers')
+        if not psf_index_ptr and npsf != nstamp:
+            raise ValueError('without psf_index_ptr, npsf must equal nstamp')
+        flags = psf_fit_flags(background, fixed_shift)
+        if fixed_shift and not shift_ptr:
+            raise ValueError('fixed_shift needs shift_ptr')
+
+        def ptr(v):
+            return C.c_void_p(int(v)) if v else None
+        _check(self.lib.mpsfr_fit_stamps_psf(self._h, int(nstamp), ptr(stamps_ptr), ptr(var_ptr), int(npsf),
+                                             ptr(psf_ptr), ptr(psf_index_ptr), ptr(shift_ptr), flags, ptr(fit_ptr), 1))
+
     def stamp_metrics(self, stamps, radii_px, boxes_px, fractions, centers=None):
         """PSF energy metrics (mpsfr_stamp_metrics) of stamps (..., dimpsf, dimpsf): (n, NMET_HEAD + nrad + nbox +
         nfrac) rows -- flux, peak, peak_p, peak_q, cp, cq, status, 0, then the encircled energies at `radii_px`, the
@@ -913,6 +961,60 @@ def observed_stamps(stamps, var=None, dimpsf=40):
     if va.size != st.size or va.shape[-2:] != (dimpsf, dimpsf):
         raise ValueError('var must have the shape of stamps')
     return st, np.ascontiguousarray(va).reshape(-1, dimpsf, dimpsf)
+
+
+def psf_fit_flags(background, fixed_shift):
+    """The flags of mpsfr_fit_stamps_psf from two booleans (ValueError for anything else)."""
+    for name, val in (('background', background), ('fixed_shift', fixed_shift)):
+        if not isinstance(val, (bool, np.bool_)):
+            raise ValueError('%s must be True or False' % name)
+    return (FIT_BACKGROUND if background else 0) | (FIT_FIXED_SHIFT if fixed_shift else 0)
+
+
+def psf_fit_arguments(nstamp, psf, psf_index, shift, background, fixed_shift, dimpsf=40):
+    """(psf, psf_index, shift, flags) of a PSF-model fit of `nstamp` stars, validated as mpsfr_fit_stamps_psf validates
+    host arguments (ValueError): psf a non-empty numeric array (..., dimpsf, dimpsf) -> (npsf, dimpsf, dimpsf) float64;
+    psf_index None (then npsf == nstamp) or nstamp integers in 0..npsf-1 -> int32; shift None or (nstamp, 2) finite
+    values within FIT_PSF_MAX_SHIFT pixels, required under fixed_shift."""
+    flags = psf_fit_flags(background, fixed_shift)
+    try:
+        ps = np.asarray(getattr(psf, 'data', psf), dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('psf must be a numeric array') from None
+    if ps.ndim < 2 or ps.shape[-2:] != (dimpsf, dimpsf) or ps.size == 0:
+        raise ValueError('psf must have the shape (..., %d, %d)' % (dimpsf, dimpsf))
+    ps = np.ascontiguousarray(ps).reshape(-1, dimpsf, dimpsf)
+    ix = None
+    if psf_index is None:
+        if ps.shape[0] != nstamp:
+            raise ValueError('without psf_index there must be one model stamp per star (%d), got %d'
+                             % (nstamp, ps.shape[0]))
+    else:
+        try:
+            raw = np.asarray(psf_index)
+            ix = raw.astype(np.int64).ravel()
+        except (TypeError, ValueError):
+            raise ValueError('psf_index must be an integer array') from None
+        if raw.dtype.kind not in 'iu' or ix.size != nstamp:
+            raise ValueError('psf_index must hold one integer per star')
+        if np.any(ix < 0) or np.any(ix >= ps.shape[0]):
+            raise ValueError('psf_index must lie in 0..%d' % (ps.shape[0] - 1))
+        ix = np.ascontiguousarray(ix, dtype=np.int32)
+    sh = None
+    if shift is None:
+        if fixed_shift:
+            raise ValueError('fixed_shift needs the shift array')
+    else:
+        try:
+            sh = np.asarray(shift, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('shift must be a numeric array') from None
+        if sh.size != 2 * nstamp or sh.shape[-1:] != (2,):
+            raise ValueError('shift must have the shape (%d, 2)' % nstamp)
+        if not np.all(np.abs(sh) <= FIT_PSF_MAX_SHIFT):           # (NaN fails)
+            raise ValueError('shift must be finite and within %g pixels' % FIT_PSF_MAX_SHIFT)
+        sh = np.ascontiguousarray(sh).reshape(nstamp, 2)
+    return ps, ix, sh, flags
 
 
 def metric_stamps(stamps, dimpsf=40):

@@ -1,0 +1,598 @@
+// HIP kernel of the PSF-model fit of observed stars, written for gfx950 (MI355X, wave64).  See DESIGN.md section 18.
+//
+// K_FIT_PSF: per star the minimum of
+//     sum_used w (m - d)^2,   w = 1 / var,   m(p, q) = F P~(p - dp, q - dq) + b
+// over (F, [dp, dq,] [b]), where P~ is the model stamp P ([40][40], zero outside) resampled by cubic convolution
+// (Keys, a = -1/2):  P~(y, x) = sum_kl c(y - k) c(x - l) P[k][l].  The fractional parts of (dp, dq) are the same for
+// every pixel of a star, so the 4 + 4 tap weights and their derivatives are wave-uniform and a model pass is a 4 x 4
+// FIR over the model stamp in LDS; d m / d dp = -F sum c'(y - k) c(x - l) P[k][l] comes from the same 16 taps.
+// The structure is k_fit_obs's: one wave per star, 25 pixels per lane in the 8 x 8-block pixel map, wave-wide sums on
+// the DPP path (wave_total), wave-uniform Levenberg-Marquardt state (Marquardt scaling, Nielsen's damping); the used
+// pixels, the weight plane and the power-of-two normalisation of data and weights are its rules too (obs_pixel there,
+// psf_pixel here).  The normal equations, their factorisation, solve and inverse are fit_common.h's, for NP = 1 to 4.
+// New here: the model stamp in LDS with a zero apron of 10 pixels (|dp|, |dq| <= 8 and taps -1 .. +2: no bounds test
+// inside the domain), rows of 72 elements -- 72 = 8 mod 32, so the 4 rows x 8 columns of a 32-lane half fall on 32
+// different banks (ds_read_b32; 16 bank pairs twice for ds_read_b64), as the 40-element rows of the star do; the model
+// stamp normalised by a power of two (max |P| into [1, 2)); the start from the closed-form linear solve for (F, b).
+// With the shift held fixed the problem is linear: that solve, and one more from its solution, are the whole fit.
+// Mixed mode: float iterations, then the fp64-residual polish (model from the fp64 stamp in memory, the float normal
+// matrix of the last iteration) until the step is below 1e-6 of the formal error, then one fp64 normal matrix for the
+// covariance.  f64 mode: fp64 throughout, star, weights and model stamp as doubles in LDS (60 KB).
+#include "device_common.h"
+#include "fit_common.h"
+
+namespace mpsfr {
+
+namespace {
+
+constexpr int kPsfApron = 10;
+constexpr int kPsfSide = NS + 2 * kPsfApron;       // 60 rows
+constexpr int kPsfStride = 72;                     // elements per row (the last 12 are never read)
+constexpr double kPsfMaxShift = 8.0;               // |dp|, |dq| bound
+constexpr int kPsfPolishMax = 12;
+constexpr double kPsfPolishSigma = 1.0e-6;         // the polish stops at a step of this fraction of the formal error
+constexpr double kPsfMinWeight = 0x1p-100;         // a used pixel keeps a weight > 0 (relative to the largest one)
+constexpr int FLAG_BACKGROUND = 1, FLAG_FIXED_SHIFT = 4;     // MPSFR_FIT_BACKGROUND / MPSFR_FIT_FIXED_SHIFT
+static_assert(kPsfApron >= (int)kPsfMaxShift + 2 && kPsfStride >= kPsfSide, "the taps stay inside the apron");
+
+// variables of a variant: F, [dp, dq,] [b]
+template <bool SHIFT, bool BG>
+struct PsfDim {
+    static constexpr int NP = 1 + (SHIFT ? 2 : 0) + (BG ? 1 : 0);
+    static constexpr int NA = NP * (NP + 1) / 2;
+    static constexpr int IB = SHIFT ? 3 : 1;             // (only with BG)
+};
+
+__device__ __forceinline__ float psf_floor(float x) { return __builtin_floorf(x); }
+__device__ __forceinline__ double psf_floor(double x) { return __builtin_floor(x); }
+
+// The tap weights of one axis at the shift d: the sample position of pixel p is y = p - d = (p + f) + t with
+// f = floor(-d), t in [0, 1); the taps are the stamp's rows p + f - 1 .. p + f + 2 with the weights w = c(t + 1),
+// c(t), c(t - 1), c(t - 2) and the derivatives dw = c' at the same places (d/dy).
+template <typename RE>
+struct KeysTaps {
+    RE w[4], dw[4];
+    int f;
+    __device__ __forceinline__ explicit KeysTaps(RE d) {
+        const RE s = -d;
+        const RE fl = psf_floor(s);
+        const RE t = s - fl, t2 = t * t, t3 = t2 * t;
+        f = (int)fl;
+        w[0] = (RE)0.5 * (-t3 + (RE)2 * t2 - t);
+        w[1] = (RE)0.5 * ((RE)3 * t3 - (RE)5 * t2 + (RE)2);
+        w[2] = (RE)0.5 * ((RE)-3 * t3 + (RE)4 * t2 + t);
+        w[3] = (RE)0.5 * (t3 - t2);
+        dw[0] = (RE)0.5 * ((RE)-3 * t2 + (RE)4 * t - (RE)1);
+        dw[1] = (RE)0.5 * ((RE)9 * t2 - (RE)10 * t);
+        dw[2] = (RE)0.5 * ((RE)-9 * t2 + (RE)8 * t + (RE)1);
+        dw[3] = (RE)0.5 * ((RE)3 * t2 - (RE)2 * t);
+    }
+};
+
+// the model stamp in LDS, with its apron: tap (a, b) of pixel (p, q) without a bounds test
+template <typename LT>
+struct LdsStamp {
+    const LT* base;
+    __device__ __forceinline__ LdsStamp(const LT* pl, int fy, int fx)
+        : base(pl + (fy - 1 + kPsfApron) * kPsfStride + (fx - 1 + kPsfApron)) {}
+    template <typename RE>
+    __device__ __forceinline__ RE at(int o, int, int, int a, int b) const {
+        return (RE)base[o + a * kPsfStride + b];
+    }
+};
+// the fp64 model stamp in memory (times `scale`, the power of two of its normalisation), zero outside
+struct GlobalStamp {
+    const double* P;
+    double scale;
+    int fy, fx;
+    template <typename RE>
+    __device__ __forceinline__ RE at(int, int p, int q, int a, int b) const {
+        const int r = p + fy - 1 + a, c = q + fx - 1 + b;
+        const bool in = (unsigned)r < (unsigned)NS && (unsigned)c < (unsigned)NS;
+        const double v = P[in ? r * NS + c : 0];
+        return in ? (RE)(v * scale) : (RE)0;
+    }
+};
+
+// P~ at pixel (p, q) (o: its offset in the apron stamp) and, with DERIV, its derivatives along y and x
+template <typename RE, bool DERIV, typename ST>
+__device__ __forceinline__ void psf_interp(const ST& st, int o, int p, int q, const KeysTaps<RE>& ty,
+                                           const KeysTaps<RE>& tx, RE& val, RE& gy, RE& gx) {
+    val = (RE)0; gy = (RE)0; gx = (RE)0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        RE h = (RE)0, hd = (RE)0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const RE t = st.template at<RE>(o, p, q, a, b);
+            h += tx.w[b] * t;
+            if constexpr (DERIV) hd += tx.dw[b] * t;
+        }
+        val += ty.w[a] * h;
+        if constexpr (DERIV) {
+            gy += ty.dw[a] * h;
+            gx += ty.w[a] * hd;
+        }
+    }
+}
+
+// Weighted normal equations over the lane's 25 pixels, summed over the wave (every lane ends up with the totals).
+// pix / wt / pl: the star, its weights and the apron model stamp in LDS (LT), the arithmetic runs in RE; (dp, dq): the
+// shift (v[1], v[2] of the caller when it is fitted).  J = (P~, -F dP~/dy, -F dP~/dx, 1).
+template <typename RE, typename LT, bool SHIFT, bool BG>
+__device__ __forceinline__ void psf_accumulate(const LT* pix, const LT* wt, const LT* pl, int lane, const RE* v, RE dp,
+                                               RE dq, FitNormEq<RE, PsfDim<SHIFT, BG>::NP>& ne) {
+    using D = PsfDim<SHIFT, BG>;
+    constexpr int NP = D::NP, NA = D::NA;
+    const KeysTaps<RE> ty(dp), tx(dq);
+    const LdsStamp<LT> st(pl, ty.f, tx.f);
+    const RE F = v[0];
+    RE bk = (RE)0;
+    if constexpr (BG) bk = v[D::IB];
+    RE a[NA], g[NP], chi2 = (RE)0;
+#pragma unroll
+    for (int k = 0; k < NA; ++k) a[k] = (RE)0;
+#pragma unroll
+    for (int k = 0; k < NP; ++k) g[k] = (RE)0;
+    const int lr = lane >> 3, lc = lane & 7;
+    static_assert(NS == 40, "5 x 5 blocks of 8 x 8 pixels");
+#pragma unroll 1
+    for (int mo = 0; mo < 5; ++mo) {
+#pragma unroll
+        for (int mi = 0; mi < 5; ++mi) {
+            const int p = 8 * mo + lr, q = 8 * mi + lc;
+            const int o = p * NS + q;
+            RE val, gy, gx;
+            psf_interp<RE, SHIFT>(st, p * kPsfStride + q, p, q, ty, tx, val, gy, gx);
+            const RE w = (RE)wt[o];
+            const RE r = (F * val + bk) - (RE)pix[o];
+            RE J[NP];
+            J[0] = val;
+            if constexpr (SHIFT) {
+                J[1] = -F * gy;
+                J[2] = -F * gx;
+            }
+            if constexpr (BG) J[D::IB] = (RE)1;
+            const RE wr = w * r;
+            chi2 += wr * r;
+            int k = 0;
+#pragma unroll
+            for (int i = 0; i < NP; ++i) {
+                g[i] += J[i] * wr;
+                const RE wj = w * J[i];
+#pragma unroll
+                for (int j = i; j < NP; ++j) a[k++] += wj * J[j];
+            }
+        }
+    }
+    ne.chi2 = wave_total(chi2);
+#pragma unroll
+    for (int k = 0; k < NA; ++k) ne.a[k] = wave_total(a[k]);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) ne.g[k] = wave_total(g[k]);
+}
+
+// weighted chi2 alone at (F, dp, dq, b)
+template <typename RE>
+__device__ __forceinline__ RE psf_chi2(const RE* pix, const RE* wt, const RE* pl, int lane, RE F, RE dp, RE dq,
+                                       RE bk) {
+    const KeysTaps<RE> ty(dp), tx(dq);
+    const LdsStamp<RE> st(pl, ty.f, tx.f);
+    RE cs[5] = {(RE)0, (RE)0, (RE)0, (RE)0, (RE)0};
+    const int lr = lane >> 3, lc = lane & 7;
+#pragma unroll 1
+    for (int mo = 0; mo < 5; ++mo) {
+#pragma unroll
+        for (int mi = 0; mi < 5; ++mi) {
+            const int p = 8 * mo + lr, q = 8 * mi + lc;
+            const int o = p * NS + q;
+            RE val, gy, gx;
+            psf_interp<RE, false>(st, p * kPsfStride + q, p, q, ty, tx, val, gy, gx);
+            const RE r = (F * val + bk) - pix[o];
+            cs[mi] += wt[o] * r * r;
+        }
+    }
+    return wave_total(((cs[0] + cs[1]) + (cs[2] + cs[3])) + cs[4]);
+}
+
+// fp64-residual gradient J^T W r and chi2 for the polish of the mixed mode (obs_gradient of fit_obs.hip): the model
+// from the fp64 model stamp in memory and the residual against the fp64 star in memory (each times the power of two of
+// its normalisation) are formed in fp64; the weight and the Jacobian, which multiply a noise-sized residual, and the
+// per-lane partial sums run in float.  A pixel of weight 0 is excluded: its stored value is never used.
+template <bool SHIFT, bool BG>
+__device__ __forceinline__ void psf_gradient(const double* __restrict__ src, double scale,
+                                             const double* __restrict__ psrc, double pscale, const float* wt, int lane,
+                                             const double* v, double dp, double dq, double* gout, double* chi2out) {
+    using D = PsfDim<SHIFT, BG>;
+    constexpr int NP = D::NP;
+    const KeysTaps<double> ty(dp), tx(dq);
+    const GlobalStamp st{psrc, pscale, ty.f, tx.f};
+    const double F = sgpr(v[0]);
+    double bk = 0.0;
+    if constexpr (BG) bk = sgpr(v[D::IB]);
+    const float Ff = (float)F;
+    float g[NP], c2sum = 0.f;
+#pragma unroll
+    for (int k = 0; k < NP; ++k) g[k] = 0.f;
+    const int lr = lane >> 3, lc = lane & 7;
+#pragma unroll 1
+    for (int mo = 0; mo < 5; ++mo) {
+#pragma unroll 1
+        for (int mi = 0; mi < 5; ++mi) {
+            const int p = 8 * mo + lr, q = 8 * mi + lc;
+            const int o = p * NS + q;
+            double val, gy, gx;
+            psf_interp<double, SHIFT>(st, 0, p, q, ty, tx, val, gy, gx);
+            const float w = wt[o];
+            const double dd = src[o];
+            const float r = w > 0.f ? (float)((F * val + bk) - dd * scale) : 0.f;
+            const float wr = w * r;
+            c2sum += wr * r;
+            g[0] += (float)val * wr;
+            if constexpr (SHIFT) {
+                g[1] -= Ff * (float)gy * wr;
+                g[2] -= Ff * (float)gx * wr;
+            }
+            if constexpr (BG) g[D::IB] += wr;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NP; ++k) gout[k] = wave_total((double)g[k]);
+    *chi2out = (double)wave_total(c2sum);
+}
+
+// size of a step dx towards vn: relative to the scale F for F and b, absolute (pixels) for the shift
+template <bool SHIFT, bool BG, typename S>
+__device__ __forceinline__ S psf_step_size(const S* dx, const S* vn) {
+    using D = PsfDim<SHIFT, BG>;
+    const S iden = fit_rcp<S>(fabs(vn[0]) + (S)1.0e-30);
+    S rel = fabs(dx[0]) * iden;
+    if constexpr (SHIFT) rel = fmax(rel, fmax(fabs(dx[1]), fabs(dx[2])));
+    if constexpr (BG) rel = fmax(rel, fabs(dx[D::IB]) * iden);
+    return rel;
+}
+
+template <typename S>
+__device__ __forceinline__ bool psf_inside(S dp, S dq) {          // (NaN fails)
+    return fabs(dp) <= (S)kPsfMaxShift && fabs(dq) <= (S)kPsfMaxShift;
+}
+
+// the validity of a pixel (obs_pixel of fit_obs.hip)
+struct PsfPixel {
+    bool used, bad;       // bad: an infinite value under a valid variance (the row gets status 2)
+};
+__device__ __forceinline__ PsfPixel psf_pixel(double d, double v, bool has_var) {
+    const bool vok = !has_var || (v > 0.0 && v < __builtin_inf());       // (NaN fails both)
+    const bool fin = fabs(d) < __builtin_inf();
+    PsfPixel p;
+    p.used = vok && fin;
+    p.bad = vok && !fin && d == d;
+    return p;
+}
+
+// one wave per star; RE = float: mixed mode (float iterations + fp64 polish), RE = double: f64 mode
+template <typename RE, bool SHIFT, bool BG>
+__global__ void __launch_bounds__(64)
+k_fit_psf(int nstamp, const double* __restrict__ stamps, const double* __restrict__ var, int npsf,
+          const double* __restrict__ psf, const int32_t* __restrict__ psf_index, const double* __restrict__ shift,
+          double* __restrict__ fit) {
+    using D = PsfDim<SHIFT, BG>;
+    using DL = PsfDim<false, BG>;                  // the linear problem in (F, [b])
+    constexpr int NP = D::NP, NA = D::NA, NPL = DL::NP;
+    constexpr int NPX = NS * NS / 64;
+    static_assert(NPX * 64 == NS * NS, "the lane map assumes 1600 pixels");
+    using S = RE;
+    const int lane = threadIdx.x & 63;
+    const int st = (int)blockIdx.x;
+    if (st >= nstamp) return;
+    const double* src = stamps + (size_t)st * NS * NS;
+    const bool has_var = var != nullptr;
+    const double* vsrc = has_var ? var + (size_t)st * NS * NS : src;
+    __shared__ RE sp[NS * NS];
+    __shared__ RE sw[NS * NS];
+    __shared__ RE pl[kPsfSide * kPsfStride];
+    double* orow = fit + (size_t)st * NFIT_PSF;
+    int nused = 0;
+    auto refuse = [&]() {                   // a row that is not fitted: zeros, status 2, the number of used pixels
+        if (lane == 0) {
+#pragma unroll
+            for (int k = 0; k < NFIT_PSF; ++k) orow[k] = 0.0;
+            orow[10] = 2.0;
+            orow[11] = (double)nused;
+        }
+    };
+    // the model stamp of this star and the given shift (the device form has not seen either on the host)
+    const int ip = psf_index ? psf_index[st] : st;
+    double dp0 = 0.0, dq0 = 0.0;
+    if (shift) { dp0 = shift[2 * (size_t)st]; dq0 = shift[2 * (size_t)st + 1]; }
+    const bool args_ok = ip >= 0 && ip < npsf && psf_inside<double>(dp0, dq0);
+    const double* psrc = psf + (size_t)(args_ok ? ip : 0) * NS * NS;
+    // first pass over the star: the brightest used pixel, the smallest valid variance, the number of used pixels;
+    // over the model stamp: its first maximum, max |P|, its sum, whether it is finite
+    double best = -3.0e38, vmin = 3.0e38, amax = 0.0, pbest = -3.0e38, pamax = 0.0, psum = 0.0;
+    int besto = 0, pbesto = 0, nbad = 0, pbad = 0;
+#pragma unroll 5
+    for (int m = 0; m < NPX; ++m) {
+        const int o = lane + m * 64;
+        const double d = src[o];
+        const double v = has_var ? vsrc[o] : 1.0;
+        const PsfPixel px = psf_pixel(d, v, has_var);
+        nused += px.used ? 1 : 0;
+        nbad += px.bad ? 1 : 0;
+        if (px.used) {
+            vmin = fmin(vmin, v);
+            amax = fmax(amax, fabs(d));
+            if (d > best) { best = d; besto = o; }
+        }
+        const double pv = psrc[o];
+        pbad += fabs(pv) < __builtin_inf() ? 0 : 1;
+        pamax = fmax(pamax, fabs(pv));
+        psum += pv;
+        if (pv > pbest) { pbest = pv; pbesto = o; }
+    }
+    psum = wave_total(psum);
+    // argmax (first maximum in C order, as np.argmax), minimum and counts over the wave
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ob = __shfl_xor(best, o, 64);
+        const int oo = __shfl_xor(besto, o, 64);
+        if (ob > best || (ob == best && oo < besto)) { best = ob; besto = oo; }
+        const double pb = __shfl_xor(pbest, o, 64);
+        const int po = __shfl_xor(pbesto, o, 64);
+        if (pb > pbest || (pb == pbest && po < pbesto)) { pbest = pb; pbesto = po; }
+        vmin = fmin(vmin, __shfl_xor(vmin, o, 64));
+        amax = fmax(amax, __shfl_xor(amax, o, 64));
+        pamax = fmax(pamax, __shfl_xor(pamax, o, 64));
+        nused += __shfl_xor(nused, o, 64);
+        nbad += __shfl_xor(nbad, o, 64);
+        pbad += __shfl_xor(pbad, o, 64);
+    }
+    // rows that are not fitted: a model index or a given shift outside its range, an infinite pixel, too few used
+    // pixels, a brightest used pixel or a brightest model pixel outside [2^-40, 2^40] in modulus (an all-zero model
+    // stamp included), a model stamp that is not finite, a used pixel beyond 2^60 times the brightest one in modulus
+    // (the float copy of the normalised star must hold it)
+    const double ab = fabs(best);
+    if (!args_ok || nbad > 0 || pbad > 0 || nused < NP + 1 || !(ab >= 0x1p-40 && ab <= 0x1p40) ||
+        !(pamax >= 0x1p-40 && pamax <= 0x1p40) || amax > 0x1p60 * ab) {
+        refuse();
+        return;
+    }
+    // normalisation by powers of two: the brightest used pixel into [1, 2), the largest weight into (1/2, 1], the
+    // brightest model pixel (in modulus) into [1, 2)
+    const int kx = ilogb(ab);
+    const double scale = ldexp(1.0, -kx);
+    const int kv = has_var ? ilogb(vmin) : 0;
+    const int kp = ilogb(pamax);
+    const double pscale = ldexp(1.0, -kp);
+    for (int o = lane; o < kPsfSide * kPsfStride; o += 64) pl[o] = (RE)0;
+    __syncthreads();
+#pragma unroll 5
+    for (int m = 0; m < NPX; ++m) {
+        const int o = lane + m * 64;
+        const double d = src[o];
+        const double v = has_var ? vsrc[o] : 1.0;
+        const bool used = psf_pixel(d, v, has_var).used;
+        sp[o] = (RE)(used ? d * scale : 0.0);
+        sw[o] = (RE)(used ? fmax(1.0 / ldexp(v, -kv), kPsfMinWeight) : 0.0);
+        const int p = o / NS, q = o - p * NS;
+        pl[(p + kPsfApron) * kPsfStride + q + kPsfApron] = (RE)(psrc[o] * pscale);
+    }
+    __syncthreads();                 // (one wave: the passes read pixels other lanes wrote)
+    // Start values: the given shift, or the brightest used pixel of the star minus the first maximum of the model
+    // stamp, brought into the domain; F and b from the closed-form weighted linear solve at that shift.
+    if (!shift) {
+        dp0 = fmin(fmax((double)(besto / NS - pbesto / NS), -kPsfMaxShift), kPsfMaxShift);
+        dq0 = fmin(fmax((double)(besto % NS - pbesto % NS), -kPsfMaxShift), kPsfMaxShift);
+    }
+    S v[NP];
+    {
+        S vl[NPL], dl[NPL];
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) vl[k] = (S)0;
+        FitNormEq<RE, NPL> nl;
+        psf_accumulate<RE, RE, false, BG>(sp, sw, pl, lane, vl, (RE)dp0, (RE)dq0, nl);
+        if (!fit_lm_solve<NPL, S, RE>(nl, (S)0, dl)) {           // a singular normal matrix
+            refuse();
+            return;
+        }
+        v[0] = dl[0];
+        if constexpr (SHIFT) { v[1] = (S)dp0; v[2] = (S)dq0; }
+        if constexpr (BG) v[D::IB] = dl[DL::IB];
+    }
+    FitNormEq<RE, NP> ne;
+    int it = 0, status = 1;
+    if constexpr (!SHIFT) {
+        // the linear problem: one more solve from the solution (the rounding of the first one); the normal matrix
+        // does not depend on the variables
+        psf_accumulate<RE, RE, false, BG>(sp, sw, pl, lane, v, (RE)dp0, (RE)dq0, ne);
+        S dx[NP];
+        if (fit_lm_solve<NP, S, RE>(ne, (S)0, dx)) {
+#pragma unroll
+            for (int k = 0; k < NP; ++k) v[k] += dx[k];
+            status = 0;
+        } else {
+            status = 2;
+        }
+        it = 1;
+    } else {
+        psf_accumulate<RE, RE, true, BG>(sp, sw, pl, lane, v, v[1], v[2], ne);
+        const S tol = sizeof(RE) == 4 ? (S)1.0e-3 : (S)1.0e-12;
+        S mu = (S)kFitMu0, nu = (S)2;
+        const S mu_max = (S)kFitMuMax;
+        bool bound = false;              // the last step was refused by the domain
+        while (it < kFitMaxIt) {
+            ++it;
+            S dx[NP];
+            if (!fit_lm_solve<NP, S, RE>(ne, mu, dx)) {
+                mu *= nu;
+                nu *= (S)2;
+                if (mu > mu_max) { status = 2; break; }
+                continue;
+            }
+            S vn[NP];
+#pragma unroll
+            for (int k = 0; k < NP; ++k) vn[k] = v[k] + dx[k];
+            const S rel = psf_step_size<SHIFT, BG, S>(dx, vn);
+            const bool inside = psf_inside<S>(vn[1], vn[2]);
+            if (inside && rel < tol) {       // converged: take the last (tiny) Gauss-Newton step
+#pragma unroll
+                for (int k = 0; k < NP; ++k) v[k] = vn[k];
+                status = 0;
+                break;
+            }
+            FitNormEq<RE, NP> nn;
+            S rho = (S)-1;
+            if (inside) {
+                psf_accumulate<RE, RE, true, BG>(sp, sw, pl, lane, vn, vn[1], vn[2], nn);
+                S pred = (S)0;         // predicted decrease of chi2: dx^T (mu D dx - g)
+#pragma unroll
+                for (int k = 0; k < NP; ++k) pred += dx[k] * (mu * (S)ne.a[fit_diag<NP>(k)] * dx[k] - (S)ne.g[k]);
+                rho = ((S)ne.chi2 - (S)nn.chi2) * fit_rcp<S>(pred);    // NaN -> rejected
+            }
+            if (rho > (S)0) {
+#pragma unroll
+                for (int k = 0; k < NP; ++k) v[k] = vn[k];
+                ne = nn;
+                bound = false;
+                const S c = (S)2 * rho - (S)1;
+                mu = fmax(mu * fmax((S)(1.0 / 3.0), (S)1 - c * c * c), (S)1.0e-14);
+                nu = (S)2;
+            } else {
+                bound = !inside;
+                mu *= nu;
+                nu *= (S)2;
+                // no further descent: at the minimum, or against the bound of the shift
+                if (mu > mu_max) { status = bound ? 1 : 0; break; }
+            }
+        }
+        // a fit that rests on the bound of the shift has not found a minimum (a damped step too small to leave the
+        // bound in this arithmetic passes the convergence test)
+        if (status == 0 && !(fabs(v[1]) < (S)kPsfMaxShift && fabs(v[2]) < (S)kPsfMaxShift)) status = 1;
+    }
+    const double dof = (double)(nused - NP);
+    double vd[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) vd[k] = (double)v[k];
+    double dpf = dp0, dqf = dq0;       // the shift of the model: the fitted one, or the fixed one
+    if constexpr (SHIFT) { dpf = vd[1]; dqf = vd[2]; }
+    double chi2 = -1.0;
+    // the normal matrix of the covariance, fp64; only nf.a is read after the fit
+    FitNormEq<double, NP> nf;
+    if constexpr (sizeof(RE) == 4) {
+        // the fp64 polish of k_fit_obs: steps -A^-1 g, g the gradient of the fp64 residuals, A the float normal matrix
+        // of the last iteration; it ends once a step is below kPsfPolishSigma of the formal error,
+        // dx^T A dx <= kPsfPolishSigma^2 chi2 / dof (or below 1e-9 on a star the model fits exactly)
+#pragma unroll
+        for (int k = 0; k < NA; ++k) nf.a[k] = (double)ne.a[k];
+        nf.chi2 = -1.0;
+        for (int pz = 0; pz < kPsfPolishMax && status != 2; ++pz) {
+            psf_gradient<SHIFT, BG>(src, scale, psrc, pscale, sw, lane, vd, dpf, dqf, nf.g, &nf.chi2);
+            double dx[NP], vn[NP];
+            if (!fit_lm_solve<NP, double, double>(nf, 1.0e-10, dx)) break;
+#pragma unroll
+            for (int k = 0; k < NP; ++k) vn[k] = vd[k] + dx[k];
+            const double rel = psf_step_size<SHIFT, BG, double>(dx, vn);
+            bool inside = true;
+            if constexpr (SHIFT) inside = psf_inside<double>(vn[1], vn[2]);
+            if (!inside || rel >= 0.1) break;
+            double d2 = 0.0;
+#pragma unroll
+            for (int k = 0; k < NP; ++k) d2 -= dx[k] * nf.g[k];
+#pragma unroll
+            for (int k = 0; k < NP; ++k) vd[k] = vn[k];
+            if constexpr (SHIFT) { dpf = vd[1]; dqf = vd[2]; ++it; }
+            // nf.chi2 belongs to the point before this step: chi2 is stationary at the minimum, so after a step of
+            // `rel` it differs from the value at the new point in second order only
+            chi2 = rel < 1.0e-3 ? nf.chi2 : -1.0;
+            if (rel < 1.0e-9 || d2 <= kPsfPolishSigma * kPsfPolishSigma * nf.chi2 / dof) break;
+        }
+        if (chi2 < 0.0) {              // the residuals at the final point
+            double gtmp[NP];
+            psf_gradient<SHIFT, BG>(src, scale, psrc, pscale, sw, lane, vd, dpf, dqf, gtmp, &chi2);
+        }
+        if (status != 2) {
+            // one fp64 pass for the normal matrix of the errors (its gradient and chi2 are not used: they would come
+            // from the float copies)
+            psf_accumulate<double, float, SHIFT, BG>(sp, sw, pl, lane, vd, dpf, dqf, nf);
+        }
+    } else {
+        RE bk = (RE)0;
+        if constexpr (BG) bk = v[D::IB];
+        chi2 = (double)psf_chi2<RE>(sp, sw, pl, lane, v[0], (RE)dpf, (RE)dqf, bk);
+#pragma unroll
+        for (int k = 0; k < NA; ++k) nf.a[k] = (double)ne.a[k];
+    }
+    if (lane != 0) return;
+    // Outputs.  The amplitudes leave the normalisation: F and its error by 2^(kx - kp), b and its error by 2^kx, chi2
+    // by 2^(2 kx - kv).  The covariance is the inverse of the normal matrix times chi2 / (n_used - NP), which no scale
+    // of the weights changes.
+    const double upf = ldexp(1.0, kx - kp), up = ldexp(1.0, kx);
+    double* o = orow;
+#pragma unroll
+    for (int k = 0; k < NFIT_PSF; ++k) o[k] = 0.0;
+    o[0] = vd[0] * upf;
+    o[1] = dpf;
+    o[2] = dqf;
+    if constexpr (BG) o[3] = vd[D::IB] * up;
+    o[4] = ldexp(chi2, 2 * kx - kv);
+    o[5] = (double)it;
+    o[11] = (double)nused;
+    o[12] = o[0] * psum;
+    double cov[NP][NP];
+    if (status != 2 && fit_spd_inverse<NP, double>(nf, cov)) {
+        const double s = chi2 / dof;
+        o[6] = sqrt(fmax(cov[0][0] * s, 0.0)) * upf;
+        if constexpr (SHIFT) {
+            o[7] = sqrt(fmax(cov[1][1] * s, 0.0));
+            o[8] = sqrt(fmax(cov[2][2] * s, 0.0));
+        }
+        if constexpr (BG) o[9] = sqrt(fmax(cov[D::IB][D::IB] * s, 0.0)) * up;
+        o[13] = o[6] * fabs(psum);
+    } else {
+        if (status == 0) status = 2;
+    }
+    // a row that claims a minimum holds finite numbers only
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < NFIT_PSF; ++k) finite = finite && fabs(o[k]) < __builtin_inf();
+    if (!finite && (status & 3) == 0) status = 2;
+    o[10] = (double)status;
+}
+
+template <typename RE>
+void launch_fit_psf_variant(hipStream_t s, int nstamp, const double* d_stamps, const double* d_var, int npsf,
+                            const double* d_psf, const int32_t* d_index, const double* d_shift, int flags,
+                            double* d_fit) {
+    const dim3 grid(nstamp), block(64);
+    switch (flags & (FLAG_BACKGROUND | FLAG_FIXED_SHIFT)) {
+    case 0:
+        hipLaunchKernelGGL((k_fit_psf<RE, true, false>), grid, block, 0, s, nstamp, d_stamps, d_var, npsf, d_psf,
+                           d_index, d_shift, d_fit);
+        break;
+    case FLAG_BACKGROUND:
+        hipLaunchKernelGGL((k_fit_psf<RE, true, true>), grid, block, 0, s, nstamp, d_stamps, d_var, npsf, d_psf,
+                           d_index, d_shift, d_fit);
+        break;
+    case FLAG_FIXED_SHIFT:
+        hipLaunchKernelGGL((k_fit_psf<RE, false, false>), grid, block, 0, s, nstamp, d_stamps, d_var, npsf, d_psf,
+                           d_index, d_shift, d_fit);
+        break;
+    default:
+        hipLaunchKernelGGL((k_fit_psf<RE, false, true>), grid, block, 0, s, nstamp, d_stamps, d_var, npsf, d_psf,
+                           d_index, d_shift, d_fit);
+        break;
+    }
+}
+
+}  // namespace
+
+void launch_fit_psf(hipStream_t s, int nstamp, const double* d_stamps, const double* d_var, int npsf,
+                    const double* d_psf, const int32_t* d_index, const double* d_shift, int flags, double* d_fit,
+                    bool f64) {
+    if (nstamp <= 0) return;
+    // one wavefront (and workgroup) per star, as k_fit_obs
+    if (f64) launch_fit_psf_variant<double>(s, nstamp, d_stamps, d_var, npsf, d_psf, d_index, d_shift, flags, d_fit);
+    else launch_fit_psf_variant<float>(s, nstamp, d_stamps, d_var, npsf, d_psf, d_index, d_shift, flags, d_fit);
+}
+
+}  // namespace mpsfr

@@ -1,5 +1,6 @@
 // Launchers for the HIP kernels of the PSF-reconstruction hot path (implemented in stage_a.hip,
-// per_lambda.hip and stamps.hip).
+// per_lambda.hip and stamps.hip; the fits of caller-provided stamps in fit_ell.hip, fit_obs.hip and fit_psf.hip:
+// k_fit_psf fits a resampled model stamp -- flux scale, sub-pixel shift, background -- to an observed star).
 // Host code (mpsfr_api.cpp) sees only these plain functions.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -13,6 +14,7 @@ constexpr int KS = 41;       // Moffat kernel side, psfrec.py:911-916
 constexpr int NAO = 80;      // AO-corrected zone, psfrec.py:103, 138
 constexpr int NFIT = 16;
 constexpr int NFIT_ELL = 24;     // elliptical fit (fit_ell.hip)
+constexpr int NFIT_PSF = 16;     // PSF-model fit (fit_psf.hip)
 constexpr int METRIC_MAX = 16;   // MPSFR_MAX_METRIC_RADII: radii, boxes, fractions of one metrics call (metrics.hip)
 constexpr int METRIC_HEAD = 8;   // MPSFR_NMET_HEAD
 constexpr int KHAT = 33 * 64;  // complex entries of one kernel spectrum (k_khat)
@@ -285,6 +287,12 @@ void launch_fit_ell(hipStream_t s, int nstamp, const double* d_stamps, double* d
 // weighted Moffat fit of observed stars (fit_obs.hip): [nstamp][40][40] double stamps and variances (d_var = nullptr:
 // unit weights) -> [nstamp][NFIT_ELL]; flags: MPSFR_FIT_BACKGROUND | MPSFR_FIT_ELLIPTICAL
 void launch_fit_obs(hipStream_t s, int nstamp, const double* d_stamps, const double* d_var, int flags, double* d_fit,
+                    bool f64);
+// PSF-model fit of observed stars (fit_psf.hip): star d_stamps[k] ([nstamp][40][40], d_var as launch_fit_obs) against
+// the model stamp d_psf[d_index[k]] ([npsf][40][40]; d_index = nullptr: d_psf[k]) -> [nstamp][NFIT_PSF]; d_shift
+// [nstamp][2]: the start values of (dp, dq), or nullptr; flags: MPSFR_FIT_BACKGROUND | MPSFR_FIT_FIXED_SHIFT
+void launch_fit_psf(hipStream_t s, int nstamp, const double* d_stamps, const double* d_var, int npsf,
+                    const double* d_psf, const int32_t* d_index, const double* d_shift, int flags, double* d_fit,
                     bool f64);
 // PSF energy metrics (metrics.hip): [nstamp][40][40] double stamps -> [nstamp][METRIC_HEAD + nrad + nbox + nfrac];
 // d_centers [nstamp][2] (p, q) or nullptr (the centroid); radii / boxes / fractions: host arrays (they travel as kernel

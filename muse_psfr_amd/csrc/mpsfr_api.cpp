@@ -2420,6 +2420,68 @@ int mpsfr_fit_stamps_observed(mpsfr_ctx* c, int nstamp, const double* stamps, co
     return MPSFR_OK;
 }
 
+static_assert(NFIT_PSF == MPSFR_NFIT_PSF, "K_FIT_PSF row layout");
+
+int mpsfr_fit_stamps_psf(mpsfr_ctx* c, int nstamp, const double* stamps, const double* var, int npsf,
+                         const double* psf, const int32_t* psf_index, const double* shift, int flags,
+                         double* fit_out, int on_device) {
+    if (!c || !stamps || !psf || !fit_out || nstamp < 1 || npsf < 1) return fail(MPSFR_E_INVALID, "bad argument");
+    if (flags & ~(MPSFR_FIT_BACKGROUND | MPSFR_FIT_FIXED_SHIFT))
+        return fail(MPSFR_E_INVALID, "fit_stamps_psf: unknown flag bits (the elliptical bit has no meaning here)");
+    if (!psf_index && npsf != nstamp)
+        return fail(MPSFR_E_INVALID, "fit_stamps_psf: without psf_index, npsf must equal nstamp");
+    if ((flags & MPSFR_FIT_FIXED_SHIFT) && !shift)
+        return fail(MPSFR_E_INVALID, "fit_stamps_psf: MPSFR_FIT_FIXED_SHIFT needs the shift array");
+    if (!on_device) {
+        if (psf_index)
+            for (int k = 0; k < nstamp; ++k)
+                if (psf_index[k] < 0 || psf_index[k] >= npsf)
+                    return fail(MPSFR_E_INVALID, "fit_stamps_psf: a psf_index outside 0..npsf-1");
+        if (shift)
+            for (size_t k = 0; k < (size_t)2 * nstamp; ++k)
+                if (!(std::fabs(shift[k]) <= MPSFR_FIT_PSF_MAX_SHIFT))
+                    return fail(MPSFR_E_INVALID, "fit_stamps_psf: a shift that is not finite or beyond 8 pixels");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t per = (size_t)NS * NS;
+    // as mpsfr_fit_stamps_elliptical: device stamps written by a device-output reconstruct of this context are
+    // complete when the kernel reads them
+    for (int k = 0; k < mpsfr_ctx::MAX_LANES; ++k)
+        if (c->lane[k].busy && c->lane[k].stream != s) HIPCHK(hipStreamWaitEvent(s, lane_end(c, c->lane[k]), 0));
+    if (on_device) {
+        ProfScope ps(c, K_FIT);
+        launch_fit_psf(s, nstamp, stamps, var, npsf, psf, psf_index, shift, flags, fit_out, c->f64);
+        HIPCHK(hipGetLastError());
+        return MPSFR_OK;
+    }
+    int rc;
+    // stars, [variances,] model stamps, [shifts,] rows, then the indices (the doubles first: alignment)
+    const size_t nd = (size_t)nstamp * ((var ? 2 : 1) * per + (shift ? 2 : 0) + NFIT_PSF) + (size_t)npsf * per;
+    if ((rc = ensure(c, c->stage, nd * sizeof(double) + (psf_index ? (size_t)nstamp * sizeof(int32_t) : 0))))
+        return rc;
+    double* d_st = (double*)c->stage.p;
+    double* d_va = var ? d_st + (size_t)nstamp * per : nullptr;
+    double* d_ps = d_st + (size_t)nstamp * per * (var ? 2 : 1);
+    double* d_sh = shift ? d_ps + (size_t)npsf * per : nullptr;
+    double* d_ft = d_ps + (size_t)npsf * per + (shift ? (size_t)2 * nstamp : 0);
+    int32_t* d_ix = psf_index ? (int32_t*)(d_ft + (size_t)nstamp * NFIT_PSF) : nullptr;
+    HIPCHK(hipMemcpyAsync(d_st, stamps, (size_t)nstamp * per * sizeof(double), hipMemcpyHostToDevice, s));
+    if (var) HIPCHK(hipMemcpyAsync(d_va, var, (size_t)nstamp * per * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_ps, psf, (size_t)npsf * per * sizeof(double), hipMemcpyHostToDevice, s));
+    if (shift) HIPCHK(hipMemcpyAsync(d_sh, shift, (size_t)2 * nstamp * sizeof(double), hipMemcpyHostToDevice, s));
+    if (psf_index)
+        HIPCHK(hipMemcpyAsync(d_ix, psf_index, (size_t)nstamp * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    {
+        ProfScope ps(c, K_FIT);
+        launch_fit_psf(s, nstamp, d_st, d_va, npsf, d_ps, d_ix, d_sh, flags, d_ft, c->f64);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(fit_out, d_ft, (size_t)nstamp * NFIT_PSF * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MPSFR_OK;
+}
+
 static_assert(METRIC_MAX == MPSFR_MAX_METRIC_RADII && METRIC_HEAD == MPSFR_NMET_HEAD, "K_STAMP_METRICS row layout");
 
 int mpsfr_stamp_metrics(mpsfr_ctx* c, int nstamp, const double* stamps, const double* centers, int nrad,

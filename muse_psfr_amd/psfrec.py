@@ -417,6 +417,62 @@ def fit_psf_cube(lbda, psfcube, *, circular=True, var=None, fit_back=False, pixs
     return _make_table(_fit_columns(lbda, ctx.fit_stamps(data), pixscale))
 
 
+_FIT_COLS_PSF = ('scale', 'shift', 'back', 'flux', 'chi2', 'npix', 'status', 'err_scale', 'err_shift', 'err_back',
+                 'err_flux')
+
+
+def _fit_columns_psf(fit, pixscale):
+    """fit: (n, NFIT_PSF) rows of the PSF-model fit -> the columns of _FIT_COLS_PSF (shift in arcsec)."""
+    fit = np.asarray(fit)
+    cols = OrderedDict()
+    cols['scale'] = fit[:, 0].copy()
+    cols['shift'] = fit[:, 1:3] * pixscale
+    cols['back'] = fit[:, 3].copy()
+    cols['flux'] = fit[:, 12].copy()
+    cols['chi2'] = fit[:, 4].copy()
+    cols['npix'] = fit[:, 11].astype(np.int64)
+    cols['status'] = fit[:, 10].astype(np.int64)
+    cols['err_scale'] = fit[:, 6].copy()
+    cols['err_shift'] = fit[:, 7:9] * pixscale
+    cols['err_back'] = fit[:, 9].copy()
+    cols['err_flux'] = fit[:, 13].copy()
+    assert tuple(cols) == _FIT_COLS_PSF
+    return cols
+
+
+def fit_stars_with_psf(stars, psf, *, var=None, psf_index=None, shift=None, fit_back=True, fixed_shift=False,
+                       pixscale=0.2, precision='mixed', device=0):
+    """PSF-fitting photometry: fit the model stamps `psf` (..., 40, 40) -- e.g. reconstructed PSFs -- to the observed
+    stars `stars`, each in a flux scale, a sub-pixel shift and (fit_back) a constant background.  The model is resampled
+    by cubic convolution and counts as zero outside its stamp.
+
+    stars / var: what fit_psf_cube(var=...) accepts (an array, a masked array or an mpdaf-style object; var an array,
+    True for the object's own .var, or None for unit weights).  psf_index: the model stamp of every star, or None for
+    one model stamp per star in order.  shift: (n, 2) start values of the shift (row, column) in arcsec, or None for
+    the difference of the brightest pixels; fixed_shift=True holds them (the problem is then linear).
+
+    Returns a table with one row per star: scale (F), shift (2, arcsec), back, flux = F sum(psf), chi2 (the weighted
+    sum of squares: the goodness of the reconstruction on this star), npix (pixels used), status (0 a minimum, 1 not
+    converged or against the 8-pixel bound of the shift, 2 not fitted), err_scale, err_shift (2, arcsec), err_back,
+    err_flux (errors scaled by sqrt(chi2 / dof))."""
+    for name, val in (('fit_back', fit_back), ('fixed_shift', fixed_shift)):
+        if not isinstance(val, (bool, np.bool_)):
+            raise ValueError('%s must be True or False' % name)
+    if not (np.isfinite(pixscale) and pixscale > 0):
+        raise ValueError('pixscale must be positive')
+    data, va = _observed_cube(stars, var)
+    sh = None
+    if shift is not None:
+        try:
+            sh = np.asarray(shift, dtype=float) / pixscale
+        except (TypeError, ValueError):
+            raise ValueError('shift must be a numeric array') from None
+    ctx = get_context(128, pixscale, data.shape[-1], precision, device)
+    fit = ctx.fit_stamps_psf(data, psf, var=va, psf_index=psf_index, shift=sh, background=bool(fit_back),
+                             fixed_shift=bool(fixed_shift))
+    return _make_table(_fit_columns_psf(fit, pixscale))
+
+
 METRIC_RADII = (0.2, 0.4, 0.6, 1.0, 2.0)      # default encircled-energy radii [arcsec]
 METRIC_BOXES = (0.2, 0.4, 0.6, 1.0)           # default ensquared-energy box sides [arcsec] (0.2": the WFM spaxel)
 METRIC_FRACTIONS = (0.5, 0.8)                 # default fractions of the EE radii
