@@ -12,6 +12,7 @@ constexpr int NS = 40;       // dimpsf, psfrec.py:658
 constexpr int NSH = NS / 2 + 1;  // samples 0..20 of a line; sample 40-i is the conjugate of i
 constexpr int KS = 41;       // Moffat kernel side, psfrec.py:911-916
 constexpr int NAO = 80;      // AO-corrected zone, psfrec.py:103, 138
+constexpr int kNH = NAO / 2 + 1;   // values per line of the patch row transforms: the Hermitian half su = 0 .. 40 (stage_a2.hip)
 constexpr int NFIT = 16;
 constexpr int NFIT_ELL = 24;     // elliptical fit (fit_ell.hip)
 constexpr int NFIT_PSF = 16;     // PSF-model fit (fit_psf.hip)
@@ -136,7 +137,7 @@ void launch_p2p_psf(hipStream_t s, int M, int N, int nz, const double* d_D0t, co
 // Series form of stage A (stage_a2.hip).  d_coef: [N/2+1][N][series_terms] structure functions of the
 // terms of the expansion of the fitting PSD in 1/L0^2 about series_eps0() (launch_series_coef from the
 // fp64 planes [terms][N/2+1][N] that launch_colfft_dphi produced for the basis tasks);
-// launch_patch: d_P [ntd][80][80], d_T [ntd][N/2+1][80] complex, d_sp [ntd];
+// launch_patch: d_P [ntd][80][80], d_T [ntd][N/2+1][41] complex (kNH: the Hermitian half of a line), d_sp [ntd];
 // launch_dphi_series: D0t as launch_colfft_dphi writes it.  Valid for 1/L0^2 <= series_eps_max().
 // d_twk: the per-lane twiddle table of launch_series_twiddles (series_twiddle_bytes), which takes the
 // place of d_tw64 in launch_patch / launch_dphi_series

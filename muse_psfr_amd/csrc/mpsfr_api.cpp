@@ -1238,7 +1238,7 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
         if (big < soft) big = soft;
         // (the largest workspace per task: the row transforms C of the full-size form; D and the patch
         // transforms of the series form)
-        const double per_task = series ? (double)ndir * H1 * (N * (double)rsize(c) + NAO * 16.0)
+        const double per_task = series ? (double)ndir * H1 * (N * (double)rsize(c) + kNH * 16.0)
                                        : (double)ndir * (N / 2 + NAO / 2) * H1 * 16.0;
         const int cap = (int)(4.0 * 1024 * 1024 * 1024 / per_task);
         if (big > cap) big = cap < 1 ? 1 : cap;
@@ -1661,7 +1661,7 @@ static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const
         if (io.pre_in) continue;            // convolutions only: no workspace of stages A and B
         if (series) {
             if ((rc = ensure(c, ln.pP, (size_t)TC * ndir * NAO * NAO * sizeof(double)))) return rc;
-            if ((rc = ensure(c, ln.pT, (size_t)TC * ndir * H1 * NAO * 2 * sizeof(double)))) return rc;
+            if ((rc = ensure(c, ln.pT, (size_t)TC * ndir * H1 * kNH * 2 * sizeof(double)))) return rc;
             if ((rc = ensure(c, ln.psp, (size_t)TC * ndir * sizeof(double)))) return rc;
             if (c->stage_a_queue && (rc = ensure(c, ln.squeue, 64))) return rc;
             if (prune && (rc = ensure(c, ln.dlin, (size_t)TC * ndir * H1 * (N / 32) * sizeof(float)))) return rc;

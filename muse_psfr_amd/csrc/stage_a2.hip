@@ -22,10 +22,14 @@
 //    outputs.  Row pass (K_PATCH_ROWS): T[su][y] = sum_sv P[su][sv] W^(sv y).  Column pass
 //    (K_DPHI_SERIES): with x = 64 k1 + k2, Q = N / 64 and su = r + Q j,
 //        X[64 k1 + k2] = sum_r W_Q^(r k1) S_r[k2],   S_r[k2] = W_N^(r k2) sum_j T[r + Q j] W_64^(j k2):
-//    a lane (k2) folds the 80 inputs into Q sums and runs a Q-point transform in its own registers;
-//    its Q outputs are x = k2, 64 + k2, ...: for every k1 the 64 lanes store one 256-byte piece of the
-//    line.  No LDS pass, no barrier, no workspace of N^2 size: the 7 MB per task of row transforms
-//    (1280^2) become 0.8 MB, and the kernel is bound by its fp64 multiply-adds (~30 per pixel).
+//    a lane (k2) folds the inputs of a line into sums per class r and runs a Q-point transform in its own
+//    registers; its Q outputs are x = k2, 64 + k2, ...: for every k1 the 64 lanes store one 256-byte piece of
+//    the line.  No LDS pass, no barrier, no workspace of N^2 size.
+//    Only Re X is used, so only the Hermitian half of a line travels (hfold_valid below): the row pass
+//    stores 41 values U[su] = T[su] + conj(T[-su]) per line instead of 80, the column pass forms the classes
+//    r = 0 .. Q/2 from 41 complex multiply-adds (S_(Q-r) = conj(S_r)) and its transform is complex-to-real.
+//    The 7 MB per task of row transforms (1280^2) become 0.4 MB, and the kernel is bound by its fp64
+//    multiply-adds (~17 per pixel).
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
@@ -42,36 +46,43 @@ namespace {
 
 constexpr double kEps0 = 1.0 / 128.0;      // expansion point of 1/L0^2 (L0 = 11.3 m)
 
-// W_Q^m = exp(-2 pi i m / Q), the constant twiddles of the in-lane transforms (m <= 3 (Q/4 - 1))
+// W_Q^m = exp(-2 pi i m / Q), m < Q: the constant twiddles of the in-lane transforms
 template <int Q> struct WQ;
+template <> struct WQ<4> {
+    static constexpr double c[4] = {1.0, 0.0, -1.0, 0.0};
+    static constexpr double s[4] = {0.0, -1.0, 0.0, 1.0};
+};
 template <> struct WQ<8> {
-    static constexpr double c[4] = {1.0, 0.70710678118654752440, 0.0, -0.70710678118654752440};
-    static constexpr double s[4] = {0.0, -0.70710678118654752440, -1.0, -0.70710678118654752440};
+    static constexpr double c[8] = {1.0, 0.70710678118654752440, 0.0, -0.70710678118654752440, -1.0,
+                                    -0.70710678118654752440, 0.0, 0.70710678118654752440};
+    static constexpr double s[8] = {0.0, -0.70710678118654752440, -1.0, -0.70710678118654752440, 0.0,
+                                    0.70710678118654752440, 1.0, 0.70710678118654752440};
 };
 template <> struct WQ<16> {
-    static constexpr double c[10] = {1.0, 0.92387953251128675613, 0.70710678118654752440, 0.38268343236508977173,
-                                     0.0, -0.38268343236508977173, -0.70710678118654752440,
-                                     -0.92387953251128675613, -1.0, -0.92387953251128675613};
-    static constexpr double s[10] = {0.0, -0.38268343236508977173, -0.70710678118654752440,
-                                     -0.92387953251128675613, -1.0, -0.92387953251128675613,
-                                     -0.70710678118654752440, -0.38268343236508977173, 0.0,
+    static constexpr double c[16] = {1.0, 0.92387953251128675613, 0.70710678118654752440, 0.38268343236508977173,
+                                     0.0, -0.38268343236508977173, -0.70710678118654752440, -0.92387953251128675613,
+                                     -1.0, -0.92387953251128675613, -0.70710678118654752440,
+                                     -0.38268343236508977173, 0.0, 0.38268343236508977173, 0.70710678118654752440,
+                                     0.92387953251128675613};
+    static constexpr double s[16] = {0.0, -0.38268343236508977173, -0.70710678118654752440, -0.92387953251128675613,
+                                     -1.0, -0.92387953251128675613, -0.70710678118654752440,
+                                     -0.38268343236508977173, 0.0, 0.38268343236508977173, 0.70710678118654752440,
+                                     0.92387953251128675613, 1.0, 0.92387953251128675613, 0.70710678118654752440,
                                      0.38268343236508977173};
 };
 template <> struct WQ<20> {
-    static constexpr double c[13] = {1.0, 0.95105651629515357212, 0.80901699437494742410,
-                                     0.58778525229247312917, 0.30901699437494742410, 0.0,
-                                     -0.30901699437494742410, -0.58778525229247312917,
+    static constexpr double c[20] = {1.0, 0.95105651629515357212, 0.80901699437494742410, 0.58778525229247312917,
+                                     0.30901699437494742410, 0.0, -0.30901699437494742410, -0.58778525229247312917,
                                      -0.80901699437494742410, -0.95105651629515357212, -1.0,
-                                     -0.95105651629515357212, -0.80901699437494742410};
-    static constexpr double s[13] = {0.0, -0.30901699437494742410, -0.58778525229247312917,
-                                     -0.80901699437494742410, -0.95105651629515357212, -1.0,
-                                     -0.95105651629515357212, -0.80901699437494742410,
-                                     -0.58778525229247312917, -0.30901699437494742410, 0.0,
-                                     0.30901699437494742410, 0.58778525229247312917};
-};
-template <> struct WQ<4> {
-    static constexpr double c[1] = {1.0};
-    static constexpr double s[1] = {0.0};
+                                     -0.95105651629515357212, -0.80901699437494742410, -0.58778525229247312917,
+                                     -0.30901699437494742410, 0.0, 0.30901699437494742410, 0.58778525229247312917,
+                                     0.80901699437494742410, 0.95105651629515357212};
+    static constexpr double s[20] = {0.0, -0.30901699437494742410, -0.58778525229247312917, -0.80901699437494742410,
+                                     -0.95105651629515357212, -1.0, -0.95105651629515357212,
+                                     -0.80901699437494742410, -0.58778525229247312917, -0.30901699437494742410, 0.0,
+                                     0.30901699437494742410, 0.58778525229247312917, 0.80901699437494742410,
+                                     0.95105651629515357212, 1.0, 0.95105651629515357212, 0.80901699437494742410,
+                                     0.58778525229247312917, 0.30901699437494742410};
 };
 
 template <int M>
@@ -87,6 +98,23 @@ template <int Q> constexpr int fold_jmax() { return (NAO / 2 + Q - 1) / Q; }    
 template <int Q> constexpr int fold_nj() { return fold_jmax<Q>() - fold_jmin<Q>(); }
 constexpr bool fold_valid(int Q, int r, int j) { return r + Q * j >= -NAO / 2 && r + Q * j < NAO / 2; }
 
+// The Hermitian half of a line (K_PATCH_ROWS stores it, K_DPHI_SERIES folds it).  Only the real part of the column
+// transform is used, and with Th[su] = (T[su] + conj(T[-su])) / 2
+//     Re sum_su T[su] W^(su x) = sum_su Th[su] W^(su x),   Th[-su] = conj(Th[su]),   su in [-40, 40]
+// for any patch.  The edge row su = -40 has no partner inside the patch and is its own pair: Th[-40] = T[-40] / 2,
+// Th[40] = conj(T[-40]) / 2.  A line is the kNH = 41 values (kernels.h) U[su] = c Th[su], su = 0 .. 40, with c = 1 for su = 0
+// and c = 2 otherwise: a pair counts twice, and the doubling is exact.  For the fold su = r + Q j the symmetry reads
+// S_(Q - r) = conj(S_r): the classes r = 0 .. Q/2 are formed,
+//     r = 0:        S_0 = U[0] + sum_(j < 0) Re(conj(U[-Q j]) W_L^(j k2))           (real; the pairs through su < 0)
+//     r = Q/2:      S_(Q/2) = Re(W_N^(r k2) sum_(j >= 0) U[r + Q j] W_L^(j k2))      (real; the pairs through su > 0)
+//     0 < r < Q/2:  S'_r = 2 S_r = W_N^(r k2) sum_j Uh[r + Q j] W_L^(j k2),  Uh[su] = U[su], Uh[-su] = conj(U[su]),
+// and X[k1] = S_0 + (-1)^k1 S_(Q/2) + sum_(0 < r < Q/2) Re(S'_r W_Q^(r k1)).  su = +-40 falls in class Q/2 (Q = 16) or
+// 0 (Q = 2, 4, 8, 20), never in a general one.
+constexpr bool hfold_valid(int Q, int r, int j) {
+    const int su = r + Q * j;
+    return su >= -NAO / 2 && su <= NAO / 2 && (2 * r != Q || j >= 0);
+}
+
 template <int B, int E, typename F>
 __device__ __forceinline__ void static_for(F&& f) {
     if constexpr (B < E) {
@@ -95,36 +123,74 @@ __device__ __forceinline__ void static_for(F&& f) {
     }
 }
 
-// Re X[k1], X[k1] = sum_r S_r W_Q^(r k1), for k1 = 0..Q-1.  Q = 4 M: r = 4 r2 + r1, k1 = M a + b;
-// M-point transforms over r2, the twiddles W_Q^(r1 b), and the last radix-4 stage on real parts only.
-// G(r1, v) (r1 a std::integral_constant) fills v[r2] = S_(4 r2 + r1): the caller produces the sums of
-// one r1 at a time, so that at Q = 20 only 5 of the 20 are alive beside the partial results.
-template <int Q, typename F>
-__device__ __forceinline__ void dftq_real_out(F&& G, double* out) {
+// Re(W_Q^m z), and acc + Re(W_Q^m z); the trivial factors are resolved at compile time
+template <int Q, int MM>
+__device__ __forceinline__ double re_w(const cx<double>& z) {
+    constexpr int m = ((MM % Q) + Q) % Q;
+    constexpr double c = WQ<Q>::c[m], s = WQ<Q>::s[m];
+    if constexpr (c == 1.0) return z.x;
+    else if constexpr (c == -1.0) return -z.x;
+    else if constexpr (s == 1.0) return -z.y;
+    else if constexpr (s == -1.0) return z.y;
+    else return fma(-s, z.y, c * z.x);
+}
+template <int Q, int MM>
+__device__ __forceinline__ double add_re_w(double acc, const cx<double>& z) {
+    constexpr int m = ((MM % Q) + Q) % Q;
+    constexpr double c = WQ<Q>::c[m], s = WQ<Q>::s[m];
+    if constexpr (c == 1.0) return acc + z.x;
+    else if constexpr (c == -1.0) return acc - z.x;
+    else if constexpr (s == 1.0) return acc - z.y;
+    else if constexpr (s == -1.0) return acc + z.y;
+    else return fma(-s, z.y, fma(c, z.x, acc));
+}
+
+// X[k1] = sum_(r < Q) S_r W_Q^(r k1), k1 = 0 .. Q-1, for a Hermitian sequence S_(Q - r) = conj(S_r): a complex-to-real
+// transform.  Q = 4 M: r = 4 r2 + r1, k1 = M a + b, and with V_r1[b] = sum_r2 S_(4 r2 + r1) W_Q^((4 r2 + r1) b)
+//     X[M a + b] = V_0[b] + (-1)^a V_2[b] + 2 Re((-i)^a V_1[b]):
+// V_0 and V_2 are real (their classes are conjugate pairs within themselves) and V_3 = conj(V_1), which is never
+// formed; V_1 is the one complex M-point transform left, over the odd classes 1, 3, .. Q/2 - 1 and the conjugates of
+// the same in reverse.  s0 = S_0; EV(v) fills v[i] = S'_(2 + 2 i), i < M, of which the last is the real S_(Q/2) (in
+// .x); OD(v) fills v[i] = S'_(1 + 2 i), i < M (S' = 2 S: see above).  The caller produces the sums of one group at a
+// time, so that at Q = 20 only 5 of them are alive beside the partial results.
+template <int Q, typename FE, typename FO>
+__device__ __forceinline__ void dftq_herm_real_out(double s0, FE&& EV, FO&& OD, double* out) {
     static_assert(Q % 4 == 0, "Q = 2 is handled by the caller");
     constexpr int M = Q / 4;
     double t0[M], t1[M], t2[M], t3[M];
     {
-        cx<double> v[M];
-        G(std::integral_constant<int, 0>{}, v);
-        dftm<M>(v);
-#pragma unroll
-        for (int b = 0; b < M; ++b) t0[b] = v[b].x;
+        cx<double> e[M];
+        EV(e);
+        const double sh = e[M - 1].x;
+        static_for<0, M>([&](auto bc) {
+            constexpr int b = decltype(bc)::value;
+            const double shb = b % 2 ? -sh : sh;                   // (-1)^b S_(Q/2)
+            double v0, v2;
+            if constexpr (M % 2 == 0) {                            // Q/2 = 0 mod 4; class 2 is a general one
+                v0 = s0 + shb;
+                v2 = re_w<Q, 2 * b>(e[0]);
+            } else {                                               // Q/2 = 2 mod 4
+                v0 = s0;
+                v2 = shb;
+            }
+            static_for<(M % 2 == 0 ? 1 : 0), M - 1>([&](auto ic) {
+                constexpr int r = 2 + 2 * decltype(ic)::value;
+                if constexpr (r % 4 == 0) v0 = add_re_w<Q, r * b>(v0, e[decltype(ic)::value]);
+                else v2 = add_re_w<Q, r * b>(v2, e[decltype(ic)::value]);
+            });
+            t0[b] = v0 + v2;
+            t1[b] = v0 - v2;
+        });
     }
     {
-        cx<double> v[M];
-        G(std::integral_constant<int, 2>{}, v);
-        dftm<M>(v);
+        cx<double> o[M], v[M];
+        OD(o);
 #pragma unroll
-        for (int b = 0; b < M; ++b) {
-            const double re = b == 0 ? v[b].x : v[b].x * WQ<Q>::c[2 * b] - v[b].y * WQ<Q>::s[2 * b];
-            t1[b] = t0[b] - re;
-            t0[b] = t0[b] + re;
+        for (int r2 = 0; r2 < M; ++r2) {
+            const int r = 4 * r2 + 1;
+            if (2 * r < Q) v[r2] = o[(r - 1) / 2];
+            else v[r2] = {o[(Q - r - 1) / 2].x, -o[(Q - r - 1) / 2].y};
         }
-    }
-    {
-        cx<double> v[M];
-        G(std::integral_constant<int, 1>{}, v);
         dftm<M>(v);
 #pragma unroll
         for (int b = 0; b < M; ++b) {
@@ -134,21 +200,6 @@ __device__ __forceinline__ void dftq_real_out(F&& G, double* out) {
             } else {
                 t2[b] = v[b].x * WQ<Q>::c[b] - v[b].y * WQ<Q>::s[b];
                 t3[b] = v[b].x * WQ<Q>::s[b] + v[b].y * WQ<Q>::c[b];
-            }
-        }
-    }
-    {
-        cx<double> v[M];
-        G(std::integral_constant<int, 3>{}, v);
-        dftm<M>(v);
-#pragma unroll
-        for (int b = 0; b < M; ++b) {
-            if (b == 0) {
-                t2[b] += v[b].x;
-                t3[b] -= v[b].y;
-            } else {
-                t2[b] += v[b].x * WQ<Q>::c[3 * b] - v[b].y * WQ<Q>::s[3 * b];
-                t3[b] -= v[b].x * WQ<Q>::s[3 * b] + v[b].y * WQ<Q>::c[3 * b];
             }
         }
     }
@@ -190,9 +241,10 @@ __device__ __forceinline__ void dftq(cx<double>* v) {
 }
 
 // ------------------------------------------------------------------------------------------
-// Broadcast operands.  Every lane of a wave needs the same 80 inputs of a fold, each multiplied by the
-// lane's own twiddle.  They travel in 5 register pairs per component -- lane l holds input
-// 16 a + (l mod 16) in pair a, the same in all four rows of 16 lanes -- and the multiply-add picks its
+// Broadcast operands.  Every lane of a wave needs the same inputs of a fold (80 real ones in K_PATCH_ROWS, 41
+// complex ones in K_DPHI_SERIES), each multiplied by the lane's own twiddle.  They travel in 5 (3) register pairs
+// per component -- lane l holds input 16 a + (l mod 16) in pair a, the same in all four rows of 16 lanes -- and the
+// multiply-add picks its
 // lane with the DPP control row_newbcast (the one DPP control gfx90a+ has for 64-bit operations):
 // no LDS read, no scalar load, no extra instruction per operand.  (Through the scalar cache, the
 // first form of this kernel, the 1280 bytes per line and task were 26 s_load per 440 vector
@@ -208,7 +260,13 @@ __device__ __forceinline__ double mov_bc(double x) {                            
     return d;
 }
 
-constexpr int kNX = NAO / 16;        // register pairs per component of a fold's 80 inputs
+template <int LANE>
+__device__ __forceinline__ void fmac_bc(double& acc, double x, double w) {       // acc += x[LANE] * w
+    asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(x), "v"(w), "n"(LANE));
+}
+
+constexpr int kNX = NAO / 16;        // register pairs of the 80 real inputs of a fold of K_PATCH_ROWS
+constexpr int kNXH = (kNH + 15) / 16;  // register pairs per component of the 41 complex inputs of a line
 
 // Minima over the lanes 0-31 and 32-63 of four values at a time: five v_min_f32_dpp steps each (quad
 // swaps, half-row and row mirrors: every lane holds the minimum of its row of 16; row_bcast:15: rows 1
@@ -246,90 +304,104 @@ __device__ __forceinline__ void min16_x4(float& a, float& b, float& c, float& d)
 #undef MPSFR_MIN4
 
 // The sums of a group of CNT residues r_i = R0 + RS i:  acc[i] = sum_j in[r_i + Q j] W_64^(j k2)
-// (the factor W_N^(r k2) is the caller's).  xr / xi: the inputs as broadcast operands (index
-// su + 40; xi unused for a real input), wj[j - JMIN] = W_64^(j k2).  Term by term over j, all
-// residues of the group in one multiply-add block (dpp_groups.h): the accumulators of the group are
-// the independent chains that cover the latency of the fp64 DPP multiply-add.
-template <int Q, int R0, int RS, int CNT, int J>
+// (the factor W_N^(r k2) is the caller's), wj[j - JMIN] = W_64^(j k2).  HERM = false: the 80 real inputs of
+// K_PATCH_ROWS, xr = broadcast operands with index su + 40 (xi unused).  HERM = true: the Hermitian half of a line,
+// xr / xi with index |su|, conjugated where su < 0 (all of a term's residues are on one side: r < Q) and the terms of
+// hfold_valid.  Term by term over j, all residues of the group in one multiply-add block (dpp_groups.h): the
+// accumulators of the group are the independent chains that cover the latency of the fp64 DPP multiply-add.
+template <int Q, bool HERM, int R0, int RS, int CNT, int J>
 struct FoldValid {
     int n = 0, idx[CNT > 0 ? CNT : 1] = {};
     constexpr FoldValid() {
         for (int i = 0; i < CNT; ++i)
-            if (fold_valid(Q, R0 + RS * i, J)) idx[n++] = i;
+            if (HERM ? hfold_valid(Q, R0 + RS * i, J) : fold_valid(Q, R0 + RS * i, J)) idx[n++] = i;
     }
 };
 
-template <int Q, bool CPLX, int R0, int RS, int CNT, int J = fold_jmin<Q>()>
+template <int Q, bool HERM, int R0, int RS, int CNT, int J = fold_jmin<Q>()>
 __device__ __forceinline__ void fold_group(cx<double>* acc, const double* xr, const double* xi,
                                            const cx<double>* wj) {
     if constexpr (J < fold_jmax<Q>()) {
-        constexpr FoldValid<Q, R0, RS, CNT, J> V;
-#define MPSFR_FN(k) (R0 + RS * V.idx[k] + Q * J + NAO / 2)      /* input index of the k-th valid residue */
+        constexpr FoldValid<Q, HERM, R0, RS, CNT, J> V;
+#define MPSFR_FSU(k) (R0 + RS * V.idx[k] + Q * J)                /* su of the k-th valid residue */
+#define MPSFR_FN(k) (HERM ? (MPSFR_FSU(k) < 0 ? -MPSFR_FSU(k) : MPSFR_FSU(k)) : MPSFR_FSU(k) + NAO / 2)   /* input index */
 #define MPSFR_FA(k) acc[V.idx[k]]
 #define MPSFR_FX(k) xr[MPSFR_FN(k) / 16], xi[MPSFR_FN(k) / 16]
 #define MPSFR_FR(k) xr[MPSFR_FN(k) / 16]
 #define MPSFR_FL(k) MPSFR_FN(k) % 16
-        if constexpr (J == 0) {          // the twiddle is 1
+#define MPSFR_FGROUPS(mac, X)                                                                                  \
+    if constexpr (n == 5)                                                                                      \
+        mac##_group5<MPSFR_FL(0), MPSFR_FL(1), MPSFR_FL(2), MPSFR_FL(3), MPSFR_FL(4)>(                         \
+            MPSFR_FA(0), MPSFR_FA(1), MPSFR_FA(2), MPSFR_FA(3), MPSFR_FA(4), X(0), X(1), X(2), X(3), X(4), w); \
+    if constexpr (n == 4)                                                                                      \
+        mac##_group4<MPSFR_FL(0), MPSFR_FL(1), MPSFR_FL(2), MPSFR_FL(3)>(                                      \
+            MPSFR_FA(0), MPSFR_FA(1), MPSFR_FA(2), MPSFR_FA(3), X(0), X(1), X(2), X(3), w);                    \
+    if constexpr (n == 2 || n == 3)                                                                            \
+        mac##_group2<MPSFR_FL(0), MPSFR_FL(1)>(MPSFR_FA(0), MPSFR_FA(1), X(0), X(1), w);                       \
+    if constexpr (n == 3) mac##_group1<MPSFR_FL(2)>(MPSFR_FA(2), X(2), w);                                     \
+    if constexpr (n == 1) mac##_group1<MPSFR_FL(0)>(MPSFR_FA(0), X(0), w);
+        if constexpr (J == 0) {          // the twiddle is 1 (and su = r >= 0)
             static_for<0, V.n>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
                 acc[V.idx[k]].x += mov_bc<MPSFR_FL(k)>(xr[MPSFR_FN(k) / 16]);
-                if constexpr (CPLX) acc[V.idx[k]].y += mov_bc<MPSFR_FL(k)>(xi[MPSFR_FN(k) / 16]);
+                if constexpr (HERM) acc[V.idx[k]].y += mov_bc<MPSFR_FL(k)>(xi[MPSFR_FN(k) / 16]);
             });
         } else {
             const cx<double> w = wj[J - fold_jmin<Q>()];
             constexpr int n = V.n;
             static_assert(n <= 5, "group sizes up to 5");
-            if constexpr (CPLX) {
-                if constexpr (n == 5)
-                    cmac_group5<MPSFR_FL(0), MPSFR_FL(1), MPSFR_FL(2), MPSFR_FL(3), MPSFR_FL(4)>(
-                        MPSFR_FA(0), MPSFR_FA(1), MPSFR_FA(2), MPSFR_FA(3), MPSFR_FA(4), MPSFR_FX(0), MPSFR_FX(1),
-                        MPSFR_FX(2), MPSFR_FX(3), MPSFR_FX(4), w);
-                if constexpr (n == 4)
-                    cmac_group4<MPSFR_FL(0), MPSFR_FL(1), MPSFR_FL(2), MPSFR_FL(3)>(
-                        MPSFR_FA(0), MPSFR_FA(1), MPSFR_FA(2), MPSFR_FA(3), MPSFR_FX(0), MPSFR_FX(1), MPSFR_FX(2),
-                        MPSFR_FX(3), w);
-                if constexpr (n == 2 || n == 3)
-                    cmac_group2<MPSFR_FL(0), MPSFR_FL(1)>(MPSFR_FA(0), MPSFR_FA(1), MPSFR_FX(0), MPSFR_FX(1), w);
-                if constexpr (n == 3) cmac_group1<MPSFR_FL(2)>(MPSFR_FA(2), MPSFR_FX(2), w);
-                if constexpr (n == 1) cmac_group1<MPSFR_FL(0)>(MPSFR_FA(0), MPSFR_FX(0), w);
+            if constexpr (!HERM) {
+                MPSFR_FGROUPS(rmac, MPSFR_FR)
+            } else if constexpr (J < 0) {
+                MPSFR_FGROUPS(cmacc, MPSFR_FX)
             } else {
-                if constexpr (n == 5)
-                    rmac_group5<MPSFR_FL(0), MPSFR_FL(1), MPSFR_FL(2), MPSFR_FL(3), MPSFR_FL(4)>(
-                        MPSFR_FA(0), MPSFR_FA(1), MPSFR_FA(2), MPSFR_FA(3), MPSFR_FA(4), MPSFR_FR(0), MPSFR_FR(1),
-                        MPSFR_FR(2), MPSFR_FR(3), MPSFR_FR(4), w);
-                if constexpr (n == 4)
-                    rmac_group4<MPSFR_FL(0), MPSFR_FL(1), MPSFR_FL(2), MPSFR_FL(3)>(
-                        MPSFR_FA(0), MPSFR_FA(1), MPSFR_FA(2), MPSFR_FA(3), MPSFR_FR(0), MPSFR_FR(1), MPSFR_FR(2),
-                        MPSFR_FR(3), w);
-                if constexpr (n == 2 || n == 3)
-                    rmac_group2<MPSFR_FL(0), MPSFR_FL(1)>(MPSFR_FA(0), MPSFR_FA(1), MPSFR_FR(0), MPSFR_FR(1), w);
-                if constexpr (n == 3) rmac_group1<MPSFR_FL(2)>(MPSFR_FA(2), MPSFR_FR(2), w);
-                if constexpr (n == 1) rmac_group1<MPSFR_FL(0)>(MPSFR_FA(0), MPSFR_FR(0), w);
+                MPSFR_FGROUPS(cmac, MPSFR_FX)
             }
         }
+#undef MPSFR_FGROUPS
+#undef MPSFR_FSU
 #undef MPSFR_FN
 #undef MPSFR_FA
 #undef MPSFR_FX
 #undef MPSFR_FR
 #undef MPSFR_FL
-        fold_group<Q, CPLX, R0, RS, CNT, J + 1>(acc, xr, xi, wj);
+        fold_group<Q, HERM, R0, RS, CNT, J + 1>(acc, xr, xi, wj);
     }
 }
 
-// residues per group: the M = Q / 4 residues r = 4 r2 + r1 of one r1 (what the transform below asks for
-// at a time) where that gives at least 4 chains; all of them otherwise
-template <int Q> constexpr int group_cnt() { return Q >= 16 ? Q / 4 : (Q < 4 ? Q : 4); }
-
-// v[i] = S_r for r = R0 + RS i, i < CNT, the factor W_N^(r k2) = wrf(r) included
-template <int Q, bool CPLX, int R0, int RS, int CNT, typename WR>
+// v[i] = S_r (HERM: S'_r) for r = R0 + RS i, i < CNT, the factor W_N^(r k2) = wrf(r) included.  The class Q/2 of a
+// Hermitian line is real: only v[i].x = Re(W_N^(r k2) sum) is formed, one multiply-add pair.
+template <int Q, bool HERM, int R0, int RS, int CNT, typename WR>
 __device__ __forceinline__ void fold_sums(cx<double>* v, const double* xr, const double* xi,
                                           const cx<double>* wj, WR&& wrf) {
 #pragma unroll
     for (int i = 0; i < CNT; ++i) v[i] = {0.0, 0.0};
-    fold_group<Q, CPLX, R0, RS, CNT>(v, xr, xi, wj);
+    fold_group<Q, HERM, R0, RS, CNT>(v, xr, xi, wj);
 #pragma unroll
-    for (int i = 0; i < CNT; ++i)
-        if (R0 + RS * i > 0) v[i] = cmul(v[i], wrf(R0 + RS * i));
+    for (int i = 0; i < CNT; ++i) {
+        const int r = R0 + RS * i;
+        if (HERM && 2 * r == Q) {
+            const cx<double> w = wrf(r);
+            v[i] = {fma(-v[i].y, w.y, v[i].x * w.x), 0.0};
+        } else if (r > 0) {
+            v[i] = cmul(v[i], wrf(r));
+        }
+    }
+}
+
+// S_0 of a Hermitian line without its term U[0]: sum_(j < 0) Re(conj(U[-Q j]) W_L^(j k2)), in two chains
+template <int Q, int J = fold_jmin<Q>()>
+__device__ __forceinline__ void fold_class0(double& a, double& b, const double* xr, const double* xi,
+                                            const cx<double>* wj) {
+    if constexpr (J < 0) {
+        if constexpr (Q * J >= -NAO / 2) {
+            constexpr int n = -Q * J;
+            const cx<double> w = wj[J - fold_jmin<Q>()];
+            fmac_bc<n % 16>(a, xr[n / 16], w.x);
+            fmac_bc<n % 16>(b, xi[n / 16], w.y);
+        }
+        fold_class0<Q, J + 1>(a, b, xr, xi, wj);
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -474,20 +546,21 @@ __global__ void __launch_bounds__(256) k_patch_gen(int ndir, const TaskPar* __re
 }
 
 // ------------------------------------------------------------------------------------------
-// K_PATCH_ROWS: T[td][y][su + 40] = sum_sv P[su][sv] exp(-2 pi i sv y / N), y in [0, N/2], and
-// sp[td] = sum P.  A wave takes one, two or four adjacent rows su at a time: lane k2 folds a row's 80 values (broadcast
-// operands) into Q sums with its own twiddles, transforms them in registers and owns y = k2, 64 + k2, ...
-// K_DPHI_SERIES reads the 80 values of one (td, y) as 1280 contiguous bytes (with T[td][su][y] every
-// line of it gathered 80 cache lines: 12 of its 50 us at 512^2), so a lane stores its rows' values
-// of one y as one 32- or 64-byte piece; the waves are independent (a transposition of 8 rows through LDS
-// for 128-byte pieces cost two barriers per workgroup and, at 1280^2, all of a CU's LDS: 31 -> 46 us).
+// K_PATCH_ROWS: the row transforms Trow[su][y] = sum_sv P[su][sv] exp(-2 pi i sv y / N), y in [0, N/2], stored as
+// the Hermitian half of a line (above): T[td][y][su] = U[su] = Trow[su] + conj(Trow[-su]) for su = 1 .. 39,
+// U[0] = Re Trow[0], U[40] = conj(Trow[-40]); and sp[td] = sum P.  A wave takes one, two or four adjacent rows su at
+// a time: lane k2 folds a row's 80 values (broadcast operands) into Q sums with its own twiddles, transforms them in
+// registers and owns y = k2, 64 + k2, ...  K_DPHI_SERIES reads the 41 values of one (td, y) as 656 contiguous bytes
+// (with T[td][su][y] every line of it gathered 80 cache lines: 12 of its 50 us at 512^2).
 // ------------------------------------------------------------------------------------------
 // L = series_lanes<N>() lanes per row, R = 64 / L rows per wave and pass (one per group of L lanes),
 // Q = N / L: the same fold and in-lane transform as K_DPHI_SERIES, with a real input and a complex
-// output of which y <= N/2 is kept.  A workgroup takes `qb` groups of 4 R adjacent rows of one td, one
-// group per pass, a row set per wave.  The results of a pass meet in an LDS tile [y][4 R rows] and leave
-// as pieces of 4 R x 16 bytes (64 bytes at 1280^2, 256 at 256^2): a lane storing its own y values wrote
-// 16-byte pieces 1280 bytes apart, and at 1280^2 that alone took 25 of the kernel's 45 us.
+// output of which y <= N/2 is kept.  A workgroup takes `qb` groups of 4 R rows of one td, one group per pass, a row
+// set per wave: the 2 R adjacent rows su = -40 + 2 R g + s (s < 2 R) and their partners -su, so that every pair
+// meets in the pass's LDS tile [y][4 R rows] (the partner slot of su = -40, which has none, carries su = 0).  The
+// pairs are combined in fp64 on the way out, U = Trow[-su'] + conj(Trow[su']) for su' < 0, and leave as pieces of
+// 2 R x 16 bytes (32 bytes at 1280^2, 128 at 256^2): a lane storing its own y values wrote 16-byte pieces a line
+// apart, and at 1280^2 that alone took 25 of the kernel's 45 us.
 template <int N>
 constexpr size_t patch_rows_smem() { return (size_t)(N / 2 + 1) * (4 * (64 / series_lanes<N>()) + 1) * sizeof(cx<double>); }
 
@@ -530,6 +603,7 @@ __global__ void __launch_bounds__(256) k_patch_rows(const double* __restrict__ P
     constexpr bool WJREG = NJ <= 10;
     constexpr int NY = Q / 2 + 1;                        // values y = L k1 + k2 <= N/2 of a lane
     constexpr int RG = 4 * R, RS = RG + 1;               // rows per pass of the workgroup; padded tile row
+    constexpr int RH = RG / 2;                           // pairs per pass: slots [0, RH) su < 0, [RH, RG) the partners
     constexpr int NG = NAO / RG;                         // passes per td
     extern __shared__ __align__(16) unsigned char smem[];
     cx<double>* tile = reinterpret_cast<cx<double>*>(smem);          // [H1][RS]
@@ -542,8 +616,10 @@ __global__ void __launch_bounds__(256) k_patch_rows(const double* __restrict__ P
     int g = blockIdx.x * qb;
     double xa[kNX], xb[kNX];
     auto fetch = [&](int gg, double* xr) {
+        const int q = R * wave + rho, i = RH * gg + (q < RH ? q : q - RH);       // i = 40 - |su| of the slot's pair
+        const int row = q < RH ? i : (i == 0 ? NAO / 2 : NAO - i);
 #pragma unroll
-        for (int a = 0; a < kNX; ++a) xr[a] = Pg[(RG * gg + R * wave + rho) * NAO + 16 * a + (lane & 15)];
+        for (int a = 0; a < kNX; ++a) xr[a] = Pg[row * NAO + 16 * a + (lane & 15)];
     };
     if (g < g_end) fetch(g, xa);
     if (blockIdx.x == 0) {      // sum of the patch, in an order fixed by the launch geometry
@@ -584,10 +660,16 @@ __global__ void __launch_bounds__(256) k_patch_rows(const double* __restrict__ P
         for (int k1 = 0; k1 < NY; ++k1)
             if (L * k1 + k2 <= N / 2) tile[(L * k1 + k2) * RS + R * wave + rho] = S[k1];
         __syncthreads();
-        cx<double>* Tt = T + (size_t)td * H1 * NAO + RG * gg;
-        for (int e = threadIdx.x; e < H1 * RG; e += 256) {
-            const int y = e / RG, i = e % RG;
-            Tt[(size_t)y * NAO + i] = tile[y * RS + i];
+        cx<double>* Tt = T + (size_t)td * H1 * kNH;
+        for (int e = threadIdx.x; e < H1 * RH; e += 256) {
+            const int y = e / RH, sl = e % RH, i = RH * gg + sl;
+            const cx<double> vn = tile[y * RS + sl], vp = tile[y * RS + RH + sl];
+            if (i == 0) {       // su = -40 alone, and su = 0 in its partner's slot
+                Tt[(size_t)y * kNH + NAO / 2] = {vn.x, -vn.y};
+                Tt[(size_t)y * kNH] = {vp.x, 0.0};
+            } else {
+                Tt[(size_t)y * kNH + NAO / 2 - i] = {vp.x + vn.x, vp.y - vn.y};
+            }
         }
         __syncthreads();
     };
@@ -604,15 +686,16 @@ __global__ void __launch_bounds__(256) k_patch_rows(const double* __restrict__ P
 
 // ------------------------------------------------------------------------------------------
 // K_DPHI_SERIES: D0t[td][y][x] = r0^(-5/3) sum_k delta^k Hd_k[y][x] + scale2 (sp - Re X[x]) with
-// X[x] = sum_su T[td][y][su] exp(-2 pi i su x / N).  A wave takes one (td, y) at a time ("a line"):
-// the 80 complex inputs are broadcast operands (above), lane k2 owns x = k2, 64 + k2, ...
+// Re X[x] = Re sum_su Trow[su] exp(-2 pi i su x / N) from the Hermitian half T[td][y][0 .. 40] of the line.  A wave
+// takes one (td, y) at a time ("a line"): the 41 complex inputs are broadcast operands (above), lane k2 owns
+// x = k2, 64 + k2, ...
 //   coef: [y][x][K] (K fp32 / fp64 terms of pixel (y, x) side by side), staged in LDS per line y.
 // ------------------------------------------------------------------------------------------
 template <typename RO> struct SeriesCfg;
 template <> struct SeriesCfg<float> { static constexpr int K = 4; };
 template <> struct SeriesCfg<double> { static constexpr int K = 8; };
 
-// The lines of a wave: xv = their inputs (lane l holds input 16 a + l % 16 of ITS line in xv[a]),
+// The lines of a wave: xv = their inputs (lane l holds input min(16 a + l % 16, 40) of ITS line in xv[a]),
 // wjp[j - JMIN] = W_L^(j k2) of the lane, swr[r * L + k2] = W_N^(r k2) (LDS), scoef = the coefficients
 // of line y (LDS, [x][K]); r0m53, delta, spv, dst, dlin: the lane's line (td); k2 = lane % L.
 template <int N, typename RO, int L>
@@ -627,9 +710,9 @@ __device__ __forceinline__ void series_line(const cx<double>* xv, const cx<doubl
     constexpr int Q = N / L, K = SeriesCfg<RO>::K;
     constexpr float kSkipped = 3.0e38f;
     const int k2 = lane & (L - 1);
-    double xr[kNX], xi[kNX];
+    double xr[kNXH], xi[kNXH];
 #pragma unroll
-    for (int a = 0; a < kNX; ++a) {
+    for (int a = 0; a < kNXH; ++a) {
         xr[a] = xv[a].x;
         xi[a] = xv[a].y;
     }
@@ -643,34 +726,23 @@ __device__ __forceinline__ void series_line(const cx<double>* xv, const cx<doubl
     asm volatile("s_mov_b32 %0, 1" : "=s"(always));
     if (!always) {
 #pragma unroll
-        for (int k1 = 0; k1 < Q; ++k1) out[k1] = xr[k1 % kNX];
+        for (int k1 = 0; k1 < Q; ++k1) out[k1] = xr[k1 % kNXH];
     } else {
         auto wrf = [&](int r) { return swr[r * L + k2]; };
+        static_assert((NAO / 2) % Q == 0 || (NAO / 2) % Q == Q / 2, "su = +-40 falls in a self-conjugate class");
+        double s0 = mov_bc<0>(xr[0]), s0b = 0.0;
+        fold_class0<Q>(s0, s0b, xr, xi, wjp);
+        s0 += s0b;
         if constexpr (Q == 2) {
-            cx<double> S[2];
-            fold_sums<Q, true, 0, 1, 2>(S, xr, xi, wjp, wrf);
-            out[0] = S[0].x + S[1].x;
-            out[1] = S[0].x - S[1].x;
-        } else if constexpr (Q >= 16) {
-            // the Q / 4 residues of one r1 at a time: 4 or 5 independent accumulator pairs
-            dftq_real_out<Q>(
-                [&](auto r1c, cx<double>* v) {
-                    fold_sums<Q, true, decltype(r1c)::value, 4, Q / 4>(v, xr, xi, wjp, wrf);
-                },
-                out);
+            cx<double> S[1];
+            fold_sums<Q, true, 1, 2, 1>(S, xr, xi, wjp, wrf);
+            out[0] = s0 + S[0].x;
+            out[1] = s0 - S[0].x;
         } else {
-            // Q = 4, 8: all sums first, four residues to a group
-            cx<double> S[Q];
-            static_for<0, Q / 4>([&](auto gc) {
-                constexpr int R0 = decltype(gc)::value * 4;
-                fold_sums<Q, true, R0, 1, 4>(S + R0, xr, xi, wjp, wrf);
-            });
-            dftq_real_out<Q>(
-                [&](auto r1c, cx<double>* v) {
-#pragma unroll
-                    for (int r2 = 0; r2 < Q / 4; ++r2) v[r2] = S[4 * r2 + decltype(r1c)::value];
-                },
-                out);
+            // the even classes 2 .. Q/2, then the odd ones: Q / 4 = 4 or 5 independent accumulator pairs each
+            dftq_herm_real_out<Q>(
+                s0, [&](cx<double>* v) { fold_sums<Q, true, 2, 2, Q / 4>(v, xr, xi, wjp, wrf); },
+                [&](cx<double>* v) { fold_sums<Q, true, 1, 2, Q / 4>(v, xr, xi, wjp, wrf); }, out);
         }
     }
     // Block minima for the pruning of the per-wavelength stage, while the values are in registers
@@ -802,12 +874,12 @@ k_dphi_series(const cx<double>* __restrict__ T, const double* __restrict__ sp,
     if (zero17 != nullptr && blockIdx.x == 0 && threadIdx.x < kMfSchedInts) zero17[threadIdx.x] = 0;
     if (c0 >= c1) return;
     // (two register sets: the inputs of a unit are requested a whole unit ahead)
-    cx<double> xva[kNX], xvb[kNX];
+    cx<double> xva[kNXH], xvb[kNXH];
     auto fetch = [&](int c, cx<double>* xv) {
         const int y = c / nq, td = min(R * (c - y * nq) + rho, ntd - 1);
-        const cx<double>* src = T + ((size_t)td * H1 + y) * NAO + (lane & 15);
+        const cx<double>* src = T + ((size_t)td * H1 + y) * kNH;
 #pragma unroll
-        for (int a = 0; a < kNX; ++a) xv[a] = src[16 * a];
+        for (int a = 0; a < kNXH; ++a) xv[a] = src[min(16 * a + (lane & 15), kNH - 1)];
     };
     const int nwe = min(NW, nq);
     const bool active = wave < nwe;
@@ -886,10 +958,10 @@ k_dphi_series(const cx<double>* __restrict__ T, const double* __restrict__ sp,
 // order would leave the workgroups with the small y the whole work.  With nothing skipped the kernel takes what
 // K_DPHI_SERIES takes (a wave's lines and their arithmetic are the same, bit for bit).
 //
-// SeriesSkip -- lines stage B provably drops.  With T[y][su] the row transforms of the patch (this kernel's input),
-//     Re X_y[x] = Re sum_su T[y][su] W^(su x) <= sum_su |T[y][su]| =: B(y)
+// SeriesSkip -- lines stage B provably drops.  With U[y][su] the Hermitian half of the line (this kernel's input),
+//     Re X_y[x] = sum_su Th[y][su] W^(su x) <= |U[y][0]| + sum_(su > 0) |U[y][su]| =: B(y)     (U = 2 Th for su > 0)
 // for every x, so D(x, y) >= D_P(x, y) >= scale2 (sum P - B(y)) =: Lb(y) on the whole line (D_F >= 0: it is the
-// structure function of a non-negative PSD): 80 magnitudes against the column transform of the line.  The OTF of
+// structure function of a non-negative PSD): 41 magnitudes against the column transform of the line.  The OTF of
 // the line is below tel 2^(c' D) <= 2^(tlmax(y) + c' Lb(y)) at every wavelength when c' is that of the LONGEST one.
 // A line is skipped -- D = 1e30 stored (an OTF of exactly zero), Lb in its `dlin` entries, a valid lower bound for
 // the block minima of K_MF_PREP -- when
@@ -970,14 +1042,14 @@ k_dphi_series_q(const cx<double>* __restrict__ T, const double* __restrict__ sp,
         return r < ntd ? (perm != nullptr ? perm[r] : r) : -2;
     };
     const int td_last = perm != nullptr ? perm[ntd - 1] : ntd - 1;
-    cx<double> xva[kNX], xvb[kNX];
+    cx<double> xva[kNXH], xvb[kNXH];
     auto fetch = [&](int b, int u, cx<double>* xv) {
         int y = 0;
         const int t = unit_of(b, u, y);
         if (t == -1) return;
-        const cx<double>* src = T + ((size_t)(t >= 0 ? t : td_last) * H1 + y) * NAO + (lane & 15);
+        const cx<double>* src = T + ((size_t)(t >= 0 ? t : td_last) * H1 + y) * kNH;
 #pragma unroll
-        for (int a = 0; a < kNX; ++a) xv[a] = src[16 * a];
+        for (int a = 0; a < kNXH; ++a) xv[a] = src[min(16 * a + (lane & 15), kNH - 1)];
     };
     issue_lines(blk, 0);
     fetch(blk, wave, xva);
@@ -1006,12 +1078,12 @@ k_dphi_series_q(const cx<double>* __restrict__ T, const double* __restrict__ sp,
         }
         const unsigned kmask = support != nullptr ? (unsigned)__builtin_amdgcn_readfirstlane((int)support[y]) : 0xffffffffu;
         if (skip.tlmax != nullptr && y >= 4) {                  // (the first lines carry the peak's lower bound: never)
-            // B(y) = sum of the 80 magnitudes of the line: lane l holds inputs 16 a + l % 16 of ITS row's line
+            // B(y) = sum of the 41 magnitudes of the line: lane l holds inputs 16 a + l % 16 <= 40 of ITS row's line
             float m = 0.f;
 #pragma unroll
-            for (int a = 0; a < kNX; ++a) {
+            for (int a = 0; a < kNXH; ++a) {
                 const float re = (float)xv[a].x, im = (float)xv[a].y;
-                m += __builtin_sqrtf(fmaf(re, re, im * im));
+                if (16 * a + (lane & 15) < kNH) m += __builtin_sqrtf(fmaf(re, re, im * im));
             }
 #pragma unroll
             for (int o = 1; o < 16; o <<= 1) m += __shfl_xor(m, o, 64);
@@ -1092,11 +1164,11 @@ k_dphi_series1(const cx<double>* __restrict__ T, const double* __restrict__ sp,
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int td_end = min(ntd, (g + 1) * tg);
     int td = g * tg + wave;
-    cx<double> xva[kNX], xvb[kNX];
+    cx<double> xva[kNXH], xvb[kNXH];
     auto fetch = [&](int t, cx<double>* xv) {
-        const cx<double>* src = T + ((size_t)t * H1 + y) * NAO + (lane & 15);
+        const cx<double>* src = T + ((size_t)t * H1 + y) * kNH;
 #pragma unroll
-        for (int a = 0; a < kNX; ++a) xv[a] = src[16 * a];
+        for (int a = 0; a < kNXH; ++a) xv[a] = src[min(16 * a + (lane & 15), kNH - 1)];
     };
     if (td < td_end) fetch(td, xva);
     {
