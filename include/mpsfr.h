@@ -350,7 +350,9 @@ int mpsfr_wait_multi(mpsfr_ctx* const* ctxs, int nctx);
  *                  there, so chi2 and the err_* columns, which carry chi2 / dof, are not exact multiples.
  * The circular fits inside mpsfr_reconstruct and its siblings follow the same rule (their stamps have sum 1: peaks of
  * 1e-4 ... 1); the elliptical fit (mpsfr_fit_stamps_elliptical and the elliptical columns) is another kernel and does
- * not. */
+ * not.
+ * on_device = 1: both pointers are device pointers and the call is queued on the context stream, after every call
+ * queued so far on this context: stamps written by a device-output mpsfr_reconstruct* are complete when it reads them. */
 int mpsfr_fit_stamps(mpsfr_ctx* ctx, int nstamp, const double* stamps, double* fit_out,
                      int on_device);
 

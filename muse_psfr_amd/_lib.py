@@ -284,6 +284,61 @@ def _u8ptr(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint8))
 
 
+def _vptr(a):
+    """void* of a host array (None: NULL)."""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _devptr(v):
+    """void* of a raw device pointer (an int; None or 0: NULL)."""
+    return C.c_void_p(int(v)) if v else None
+
+
+def _host_outs(arrays):
+    return [_vptr(arrays[k]) for k in ('psf', 'psf_sum', 'fit')]
+
+
+def _device_outs(psf_ptr, sum_ptr, fit_ptr):
+    return [_devptr(psf_ptr), _devptr(sum_ptr), _devptr(fit_ptr)]
+
+
+def _device_pointers(**ptrs):
+    """ValueError unless every named raw device pointer is set."""
+    if not all(ptrs.values()):
+        names = list(ptrs)
+        raise ValueError('%s and %s must be device pointers' % (', '.join(names[:-1]), names[-1]))
+
+
+def _positive_int(name, n):
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError('%s must be a positive integer' % name)
+
+
+def _masks(masks):
+    """(mask_rec, mask_res) of a call as flat uint8 arrays, or (None, None)."""
+    if masks is None:
+        return None, None
+    mrec = np.ascontiguousarray(masks[0]).astype(np.uint8).reshape(-1)
+    mres = np.ascontiguousarray(masks[1]).astype(np.uint8).reshape(-1)
+    assert mrec.size == DIM_AO * DIM_AO and mres.size == DIM_AO * DIM_AO
+    return mrec, mres
+
+
+def _grid_or_positions(npsflin, positions):
+    """What a call evaluates: the npsflin x npsflin grid (positions None; npsflin None means 1) or the caller's
+    positions, which take npsflin None or 0.  Returns (npsflin as C takes it, npos, pos or None); ValueError for
+    anything else."""
+    if positions is None:
+        npsflin = 1 if npsflin is None else npsflin
+        if isinstance(npsflin, bool) or not isinstance(npsflin, (int, np.integer)) or not 1 <= npsflin <= 5:
+            raise ValueError('npsflin must be an integer between 1 and 5')
+        return int(npsflin), 0, None
+    if npsflin not in (0, None):
+        raise ValueError('a call with positions takes npsflin = 0')
+    pos = field_positions(positions)
+    return 0, pos.shape[0], pos
+
+
 class Context:
     """One GPU context: grid size, precision, HIP stream, workspaces."""
 
@@ -351,52 +406,61 @@ class Context:
         """hipStream_t of the context as an integer (for torch.cuda.ExternalStream)."""
         return int(self.lib.mpsfr_stream(self._h) or 0)
 
+    def _finish(self, arrays, _async):
+        """What a host-output call returns: the arrays, or for an asynchronous call a PendingResult, the arrays kept
+        alive under the call's ticket until the library has written them."""
+        if not _async:
+            return arrays
+        ticket = int(self.lib.mpsfr_last_ticket(self._h))
+        self._pending[ticket] = arrays
+        self._handed_over(ticket - 4)        # the call itself handed over the ticket four calls back
+        return PendingResult(self, ticket, arrays)
+
+    def _outputs(self, lead, planes, want_psf, want_sum, want_fit):
+        """dict(psf, psf_sum, fit) of new host arrays (None where not wanted): `lead` is (rows,) or (rows, npos), the
+        sum drops the row axis, `planes` is the number of wavelengths or bands."""
+        n = self.dimpsf
+        return dict(psf=np.empty(lead + (planes, n, n)) if want_psf else None,
+                    psf_sum=np.empty(lead[1:] + (planes, n, n)) if want_sum else None,
+                    fit=np.empty(lead + (planes, NFIT)) if want_fit else None)
+
     def reconstruct_async(self, *args, **kwargs):
         """`reconstruct` without waiting for the GPU (on_device = 2): returns a PendingResult whose
         .wait() blocks until the call has finished and returns the same dict.  Up to four such calls
         are in flight per context, overlapping on the pipeline lanes; they complete in order."""
         return self.reconstruct(*args, _async=True, **kwargs)
 
+    def _call_reconstruct(self, inputs, npsflin, outs, on_device):
+        seeing, gl, l0, lbda, three, hh, wind_speed, mrec, mres = inputs
+        _check(self.lib.mpsfr_reconstruct(
+            self._h, seeing.size, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), _dptr(hh),
+            float(wind_speed), int(npsflin), lbda.size, _dptr(lbda), _u8ptr(mrec), _u8ptr(mres), *outs, on_device))
+
     def reconstruct(self, lbda, seeing, gl, l0, three_lgs=None, h=(100, 10000), wind_speed=None,
                     npsflin=1, masks=None, want_psf=True, want_sum=True, want_fit=True, _async=False):
         """Host-buffer call.  Returns dict(psf, psf_sum, fit) of float64 arrays (or None)."""
-        seeing = np.ascontiguousarray(np.atleast_1d(seeing), dtype=np.float64)
-        gl = np.ascontiguousarray(np.atleast_1d(gl), dtype=np.float64)
-        l0 = np.ascontiguousarray(np.atleast_1d(l0), dtype=np.float64)
-        lbda = np.ascontiguousarray(np.atleast_1d(lbda), dtype=np.float64)
-        nt, nl = seeing.size, lbda.size
-        three = np.zeros(nt, np.uint8) if three_lgs is None else \
-            np.ascontiguousarray(np.atleast_1d(three_lgs)).astype(np.uint8)
-        if wind_speed is None:
-            wind_speed = float(np.full_like(np.array(h), 12.5)[0])      # psfrec.py:61
-        hh = np.ascontiguousarray(h, dtype=np.float64)
-        if hh.size != 2:
-            raise ValueError('exactly two layers are supported (psfrec.py:66)')
-        mrec = mres = None
-        if masks is not None:
-            mrec = np.ascontiguousarray(masks[0]).astype(np.uint8).reshape(-1)
-            mres = np.ascontiguousarray(masks[1]).astype(np.uint8).reshape(-1)
-            assert mrec.size == DIM_AO * DIM_AO and mres.size == DIM_AO * DIM_AO
-        n = self.dimpsf
-        psf = np.empty((nt, nl, n, n)) if want_psf else None
-        psum = np.empty((nl, n, n)) if want_sum else None
-        fit = np.empty((nt, nl, NFIT)) if want_fit else None
-        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        _check(self.lib.mpsfr_reconstruct(
-            self._h, nt, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), _dptr(hh),
-            float(wind_speed), int(npsflin), nl, _dptr(lbda), _u8ptr(mrec), _u8ptr(mres),
-            vp(psf), vp(psum), vp(fit), 2 if _async else 0))
-        if _async:
-            ticket = int(self.lib.mpsfr_last_ticket(self._h))
-            arrays = dict(psf=psf, psf_sum=psum, fit=fit)
-            self._pending[ticket] = arrays
-            self._handed_over(ticket - 4)        # the call itself handed over the ticket four calls back
-            return PendingResult(self, ticket, arrays)
-        return dict(psf=psf, psf_sum=psum, fit=fit)
+        inputs = self._inputs(lbda, seeing, gl, l0, three_lgs, h, wind_speed, masks)
+        arrays = self._outputs((inputs[0].size,), inputs[3].size, want_psf, want_sum, want_fit)
+        self._call_reconstruct(inputs, npsflin, _host_outs(arrays), 2 if _async else 0)
+        return self._finish(arrays, _async)
+
+    def reconstruct_device(self, lbda, seeing, gl, l0, three_lgs, h, wind_speed, npsflin, masks,
+                           psf_ptr, sum_ptr, fit_ptr):
+        """Device-buffer call (asynchronous): the three outputs are raw device pointers (int or
+        None) on this context's GPU, e.g. torch tensors' data_ptr()."""
+        inputs = self._inputs(lbda, seeing, gl, l0, three_lgs, h, wind_speed, masks)
+        self._call_reconstruct(inputs, npsflin, _device_outs(psf_ptr, sum_ptr, fit_ptr), 1)
 
     def reconstruct_field_async(self, *args, **kwargs):
         """`reconstruct_field` without waiting for the GPU (on_device = 2): returns a PendingResult."""
         return self.reconstruct_field(*args, _async=True, **kwargs)
+
+    def _call_field(self, inputs, pos, outs, on_device):
+        seeing, gl, l0, lbda, three, hh, wind_speed, mrec, mres = inputs
+        _check(self.lib.mpsfr_reconstruct_field(
+            self._h, seeing.size, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), _dptr(hh),
+            float(wind_speed), pos.shape[0], _dptr(pos), lbda.size, _dptr(lbda), _u8ptr(mrec), _u8ptr(mres),
+            *outs, on_device))
 
     def reconstruct_field(self, lbda, seeing, gl, l0, three_lgs=None, h=(100, 10000), positions=((0.0, 0.0),),
                           wind_speed=None, masks=None, want_psf=True, want_sum=True, want_fit=True, _async=False):
@@ -404,56 +468,37 @@ class Context:
         wavelength) at `positions` ((npos, 2) arcsec, npos <= 25).  Returns dict(psf (nt, npos, nl, 40, 40),
         psf_sum (npos, nl, 40, 40), fit (nt, npos, nl, NFIT)) of float64 arrays (or None)."""
         pos = field_positions(positions)
-        seeing, gl, l0, lbda, three, hh, wind_speed, mrec, mres = self._inputs(lbda, seeing, gl, l0, three_lgs, h,
-                                                                              wind_speed, masks)
-        nt, nl, npos, n = seeing.size, lbda.size, pos.shape[0], self.dimpsf
-        psf = np.empty((nt, npos, nl, n, n)) if want_psf else None
-        psum = np.empty((npos, nl, n, n)) if want_sum else None
-        fit = np.empty((nt, npos, nl, NFIT)) if want_fit else None
-        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        _check(self.lib.mpsfr_reconstruct_field(
-            self._h, nt, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), _dptr(hh),
-            float(wind_speed), npos, _dptr(pos), nl, _dptr(lbda), _u8ptr(mrec), _u8ptr(mres),
-            vp(psf), vp(psum), vp(fit), 2 if _async else 0))
-        arrays = dict(psf=psf, psf_sum=psum, fit=fit)
-        if _async:
-            ticket = int(self.lib.mpsfr_last_ticket(self._h))
-            self._pending[ticket] = arrays
-            self._handed_over(ticket - 4)
-            return PendingResult(self, ticket, arrays)
-        return arrays
+        inputs = self._inputs(lbda, seeing, gl, l0, three_lgs, h, wind_speed, masks)
+        arrays = self._outputs((inputs[0].size, pos.shape[0]), inputs[3].size, want_psf, want_sum, want_fit)
+        self._call_field(inputs, pos, _host_outs(arrays), 2 if _async else 0)
+        return self._finish(arrays, _async)
 
     def reconstruct_field_device(self, lbda, seeing, gl, l0, three_lgs, h, wind_speed, positions, masks,
                                  psf_ptr, sum_ptr, fit_ptr):
         """Device-buffer field call (asynchronous, on_device = 1): outputs are raw device pointers (int or None)
         on this context's GPU, shaped as in reconstruct_field."""
         pos = field_positions(positions)
-        seeing, gl, l0, lbda, three, hh, wind_speed, mrec, mres = self._inputs(lbda, seeing, gl, l0, three_lgs, h,
-                                                                              wind_speed, masks)
-        _check(self.lib.mpsfr_reconstruct_field(
-            self._h, seeing.size, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), _dptr(hh),
-            float(wind_speed), pos.shape[0], _dptr(pos), lbda.size, _dptr(lbda), _u8ptr(mrec), _u8ptr(mres),
-            C.c_void_p(psf_ptr), C.c_void_p(sum_ptr), C.c_void_p(fit_ptr), 1))
+        inputs = self._inputs(lbda, seeing, gl, l0, three_lgs, h, wind_speed, masks)
+        self._call_field(inputs, pos, _device_outs(psf_ptr, sum_ptr, fit_ptr), 1)
 
     def reconstruct_band_async(self, *args, **kwargs):
         """`reconstruct_band` without waiting for the GPU (on_device = 2): returns a PendingResult."""
         return self.reconstruct_band(*args, _async=True, **kwargs)
 
     def _band_inputs(self, lbda, weights, seeing, gl, l0, three_lgs, h, wind_speed, npsflin, positions, masks):
-        seeing, gl, l0, lbda, three, hh, wind_speed, mrec, mres = self._inputs(lbda, seeing, gl, l0, three_lgs, h,
-                                                                              wind_speed, masks)
-        w = band_weight_matrix(weights, lbda.size)
-        if positions is None:
-            npsflin = 1 if npsflin is None else npsflin
-            if isinstance(npsflin, bool) or not isinstance(npsflin, (int, np.integer)) or not 1 <= npsflin <= 5:
-                raise ValueError('npsflin must be an integer between 1 and 5')
-            pos = None
-        else:
-            if npsflin not in (0, None):
-                raise ValueError('a call with positions takes npsflin = 0')
-            pos = field_positions(positions)
-            npsflin = 0
-        return seeing, gl, l0, lbda, three, hh, wind_speed, mrec, mres, w, pos, npsflin
+        """Checked inputs of a band call, as a ValueError before the library is touched: (the row inputs, the
+        weights, npsflin as C takes it, pos or None)."""
+        inputs = self._inputs(lbda, seeing, gl, l0, three_lgs, h, wind_speed, masks)
+        w = band_weight_matrix(weights, inputs[3].size)
+        npsflin, _, pos = _grid_or_positions(npsflin, positions)
+        return inputs, w, npsflin, pos
+
+    def _call_band(self, inputs, w, npsflin, pos, outs, on_device):
+        seeing, gl, l0, lbda, three, hh, wind_speed, mrec, mres = inputs
+        _check(self.lib.mpsfr_reconstruct_band(
+            self._h, seeing.size, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), _dptr(hh), float(wind_speed),
+            npsflin, 0 if pos is None else pos.shape[0], None if pos is None else _dptr(pos), lbda.size, _dptr(lbda),
+            w.shape[0], _dptr(w), _u8ptr(mrec), _u8ptr(mres), *outs, on_device))
 
     def reconstruct_band(self, lbda, weights, seeing, gl, l0, three_lgs=None, h=(100, 10000), wind_speed=None,
                          npsflin=None, positions=None, masks=None, want_psf=True, want_sum=True, want_fit=True,
@@ -464,39 +509,20 @@ class Context:
         dict(psf (nt, nband, 40, 40), psf_sum (nband, 40, 40), fit (nt, nband, NFIT)); else (npos, 2) arcsec, each
         output gaining an npos axis after the row axis, with npsflin left at None (or 0): a call with positions
         evaluates no npsflin grid."""
-        seeing, gl, l0, lbda, three, hh, wind_speed, mrec, mres, w, pos, npsflin = self._band_inputs(
-            lbda, weights, seeing, gl, l0, three_lgs, h, wind_speed, npsflin, positions, masks)
-        nt, nb, n = seeing.size, w.shape[0], self.dimpsf
-        lead = (nt,) if pos is None else (nt, pos.shape[0])
-        psf = np.empty(lead + (nb, n, n)) if want_psf else None
-        psum = np.empty(lead[1:] + (nb, n, n)) if want_sum else None
-        fit = np.empty(lead + (nb, NFIT)) if want_fit else None
-        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        npos = 0 if pos is None else pos.shape[0]
-        _check(self.lib.mpsfr_reconstruct_band(
-            self._h, nt, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), _dptr(hh), float(wind_speed),
-            0 if npos else int(npsflin), npos, None if pos is None else _dptr(pos), lbda.size, _dptr(lbda), nb,
-            _dptr(w), _u8ptr(mrec), _u8ptr(mres), vp(psf), vp(psum), vp(fit), 2 if _async else 0))
-        arrays = dict(psf=psf, psf_sum=psum, fit=fit)
-        if _async:
-            ticket = int(self.lib.mpsfr_last_ticket(self._h))
-            self._pending[ticket] = arrays
-            self._handed_over(ticket - 4)
-            return PendingResult(self, ticket, arrays)
-        return arrays
+        inputs, w, npsflin, pos = self._band_inputs(lbda, weights, seeing, gl, l0, three_lgs, h, wind_speed, npsflin,
+                                                    positions, masks)
+        nt = inputs[0].size
+        arrays = self._outputs((nt,) if pos is None else (nt, pos.shape[0]), w.shape[0], want_psf, want_sum, want_fit)
+        self._call_band(inputs, w, npsflin, pos, _host_outs(arrays), 2 if _async else 0)
+        return self._finish(arrays, _async)
 
     def reconstruct_band_device(self, lbda, weights, seeing, gl, l0, three_lgs, h, wind_speed, npsflin, positions,
                                 masks, psf_ptr, sum_ptr, fit_ptr):
         """Device-buffer band call (asynchronous, on_device = 1): outputs are raw device pointers (int or None) on
         this context's GPU, shaped as in reconstruct_band."""
-        seeing, gl, l0, lbda, three, hh, wind_speed, mrec, mres, w, pos, npsflin = self._band_inputs(
-            lbda, weights, seeing, gl, l0, three_lgs, h, wind_speed, npsflin, positions, masks)
-        npos = 0 if pos is None else pos.shape[0]
-        _check(self.lib.mpsfr_reconstruct_band(
-            self._h, seeing.size, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), _dptr(hh), float(wind_speed),
-            0 if npos else int(npsflin), npos, None if pos is None else _dptr(pos), lbda.size, _dptr(lbda),
-            w.shape[0], _dptr(w), _u8ptr(mrec), _u8ptr(mres), C.c_void_p(psf_ptr), C.c_void_p(sum_ptr),
-            C.c_void_p(fit_ptr), 1))
+        inputs, w, npsflin, pos = self._band_inputs(lbda, weights, seeing, gl, l0, three_lgs, h, wind_speed, npsflin,
+                                                    positions, masks)
+        self._call_band(inputs, w, npsflin, pos, _device_outs(psf_ptr, sum_ptr, fit_ptr), 1)
 
     def reconstruct_profile_async(self, *args, **kwargs):
         """`reconstruct_profile` without waiting for the GPU (on_device = 2): returns a PendingResult."""
@@ -505,21 +531,21 @@ class Context:
     def _profile_inputs(self, lbda, seeing, gl, l0, three_lgs, h, wind_speed, wind_dir, cn2, npsflin, positions,
                         masks):
         """Checked inputs of a profile call: every refusal of mpsfr_reconstruct_profile, as a ValueError, before
-        the library is touched."""
-        hh, ws, wd = profile_layers(h, wind_speed, wind_dir)
-        seeing, gl, l0, lbda, three, _, _, mrec, mres = self._inputs(lbda, seeing, gl, l0, three_lgs, (0.0, 0.0),
-                                                                     0.0, masks)
-        w = profile_weights(cn2, seeing.size, hh.size)
-        if positions is None:
-            npsflin = 1 if npsflin is None else npsflin
-            if isinstance(npsflin, bool) or not isinstance(npsflin, (int, np.integer)) or not 1 <= npsflin <= 5:
-                raise ValueError('npsflin must be an integer between 1 and 5')
-            pos = None
-        else:
-            if npsflin not in (0, None):
-                raise ValueError('a call with positions takes npsflin = 0')
-            pos = field_positions(positions)
-        return seeing, gl, l0, lbda, three, hh, ws, wd, w, pos, mrec, mres
+        the library is touched.  (The row inputs, the layers (h, wind_speed, wind_dir), the weights, npsflin as C
+        takes it, pos or None.)"""
+        layers = profile_layers(h, wind_speed, wind_dir)
+        inputs = self._inputs(lbda, seeing, gl, l0, three_lgs, (0.0, 0.0), 0.0, masks)
+        w = profile_weights(cn2, inputs[0].size, layers[0].size)
+        npsflin, _, pos = _grid_or_positions(npsflin, positions)
+        return inputs, layers, w, npsflin, pos
+
+    def _call_profile(self, inputs, layers, w, npsflin, pos, outs, on_device):
+        seeing, gl, l0, lbda, three, _, _, mrec, mres = inputs
+        hh, ws, wd = layers
+        _check(self.lib.mpsfr_reconstruct_profile(
+            self._h, seeing.size, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), hh.size, _dptr(hh), _dptr(ws),
+            _dptr(wd), _dptr(w), npsflin, 0 if pos is None else pos.shape[0], None if pos is None else _dptr(pos),
+            lbda.size, _dptr(lbda), _u8ptr(mrec), _u8ptr(mres), *outs, on_device))
 
     def reconstruct_profile(self, lbda, seeing, gl, l0, cn2, h, wind_speed, wind_dir, three_lgs=None, npsflin=None,
                             positions=None, masks=None, want_psf=True, want_sum=True, want_fit=True, _async=False):
@@ -527,38 +553,21 @@ class Context:
         ([nlayer], m, m/s, rad), weights cn2 ([nrow, nlayer] or one [nlayer] row for all).  positions=None: the
         npsflin directions averaged, shaped as `reconstruct`; else (npos, 2) arcsec with npsflin = 0, shaped as
         `reconstruct_field`."""
-        seeing, gl, l0, lbda, three, hh, ws, wd, w, pos, mrec, mres = self._profile_inputs(
+        inputs, layers, w, npsflin, pos = self._profile_inputs(
             lbda, seeing, gl, l0, three_lgs, h, wind_speed, wind_dir, cn2, npsflin, positions, masks)
-        nt, nl, n = seeing.size, lbda.size, self.dimpsf
-        lead = (nt,) if pos is None else (nt, pos.shape[0])
-        psf = np.empty(lead + (nl, n, n)) if want_psf else None
-        psum = np.empty(lead[1:] + (nl, n, n)) if want_sum else None
-        fit = np.empty(lead + (nl, NFIT)) if want_fit else None
-        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        npos = 0 if pos is None else pos.shape[0]
-        _check(self.lib.mpsfr_reconstruct_profile(
-            self._h, nt, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), hh.size, _dptr(hh), _dptr(ws), _dptr(wd),
-            _dptr(w), 0 if npos else int(1 if npsflin is None else npsflin), npos, None if pos is None else _dptr(pos), nl, _dptr(lbda),
-            _u8ptr(mrec), _u8ptr(mres), vp(psf), vp(psum), vp(fit), 2 if _async else 0))
-        arrays = dict(psf=psf, psf_sum=psum, fit=fit)
-        if _async:
-            ticket = int(self.lib.mpsfr_last_ticket(self._h))
-            self._pending[ticket] = arrays
-            self._handed_over(ticket - 4)
-            return PendingResult(self, ticket, arrays)
-        return arrays
+        nt = inputs[0].size
+        arrays = self._outputs((nt,) if pos is None else (nt, pos.shape[0]), inputs[3].size, want_psf, want_sum,
+                               want_fit)
+        self._call_profile(inputs, layers, w, npsflin, pos, _host_outs(arrays), 2 if _async else 0)
+        return self._finish(arrays, _async)
 
     def reconstruct_profile_device(self, lbda, seeing, gl, l0, cn2, h, wind_speed, wind_dir, three_lgs, npsflin,
                                    positions, masks, psf_ptr, sum_ptr, fit_ptr):
         """Device-buffer profile call (asynchronous, on_device = 1): outputs are raw device pointers (int or None)
         on this context's GPU, shaped as in reconstruct_profile."""
-        seeing, gl, l0, lbda, three, hh, ws, wd, w, pos, mrec, mres = self._profile_inputs(
+        inputs, layers, w, npsflin, pos = self._profile_inputs(
             lbda, seeing, gl, l0, three_lgs, h, wind_speed, wind_dir, cn2, npsflin, positions, masks)
-        npos = 0 if pos is None else pos.shape[0]
-        _check(self.lib.mpsfr_reconstruct_profile(
-            self._h, seeing.size, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), hh.size, _dptr(hh), _dptr(ws),
-            _dptr(wd), _dptr(w), 0 if npos else int(1 if npsflin is None else npsflin), npos, None if pos is None else _dptr(pos), lbda.size,
-            _dptr(lbda), _u8ptr(mrec), _u8ptr(mres), C.c_void_p(psf_ptr), C.c_void_p(sum_ptr), C.c_void_p(fit_ptr), 1))
+        self._call_profile(inputs, layers, w, npsflin, pos, _device_outs(psf_ptr, sum_ptr, fit_ptr), 1)
 
     def simul_psd_profile(self, seeing, l0, cn2, h, wind_speed, wind_dir, three_lgs=False, npsflin=1, positions=None,
                           masks=None):
@@ -566,24 +575,19 @@ class Context:
         units; ndir = npsflin^2, or npos with positions (npsflin = 0)."""
         hh, ws, wd = profile_layers(h, wind_speed, wind_dir)
         w = profile_weights(cn2, 1, hh.size)
-        if positions is None:
-            pos, ndir, npos = None, int(npsflin) ** 2, 0
-        else:
-            pos = field_positions(positions)
-            ndir = npos = pos.shape[0]
-            npsflin = 0
-        mrec = mres = None
-        if masks is not None:
-            mrec = np.ascontiguousarray(masks[0]).astype(np.uint8).reshape(-1)
-            mres = np.ascontiguousarray(masks[1]).astype(np.uint8).reshape(-1)
-        out = np.empty((ndir, self.dim, self.dim))
+        # (npsflin defaults to 1 here, so positions simply replace it)
+        npsflin, npos, pos = _grid_or_positions(npsflin if positions is None else None, positions)
+        mrec, mres = _masks(masks)
+        out = np.empty((npos or npsflin ** 2, self.dim, self.dim))
         _check(self.lib.mpsfr_simul_psd_profile(
             self._h, float(seeing), float(l0), int(bool(three_lgs)), hh.size, _dptr(hh), _dptr(ws), _dptr(wd),
-            _dptr(w), int(npsflin), npos, None if pos is None else _dptr(pos), _u8ptr(mrec), _u8ptr(mres), _dptr(out)))
+            _dptr(w), npsflin, npos, None if pos is None else _dptr(pos), _u8ptr(mrec), _u8ptr(mres), _dptr(out)))
         return out
 
     @staticmethod
     def _inputs(lbda, seeing, gl, l0, three_lgs, h, wind_speed, masks):
+        """The inputs every reconstruct call shares, as C takes them: (seeing, gl, l0, lbda, three_lgs, h, wind_speed,
+        mask_rec, mask_res)."""
         seeing = np.ascontiguousarray(np.atleast_1d(seeing), dtype=np.float64)
         gl = np.ascontiguousarray(np.atleast_1d(gl), dtype=np.float64)
         l0 = np.ascontiguousarray(np.atleast_1d(l0), dtype=np.float64)
@@ -595,12 +599,7 @@ class Context:
         hh = np.ascontiguousarray(h, dtype=np.float64)
         if hh.size != 2:
             raise ValueError('exactly two layers are supported (psfrec.py:66)')
-        mrec = mres = None
-        if masks is not None:
-            mrec = np.ascontiguousarray(masks[0]).astype(np.uint8).reshape(-1)
-            mres = np.ascontiguousarray(masks[1]).astype(np.uint8).reshape(-1)
-            assert mrec.size == DIM_AO * DIM_AO and mres.size == DIM_AO * DIM_AO
-        return seeing, gl, l0, lbda, three, hh, wind_speed, mrec, mres
+        return (seeing, gl, l0, lbda, three, hh, wind_speed) + _masks(masks)
 
     @staticmethod
     def reconstruct_multi_async(ctxs, *args, **kwargs):
@@ -616,31 +615,11 @@ class Context:
         one host thread each inside the library: mpsfr_reconstruct_multi) -- the reference's joblib
         fan-out (psfrec.py:1082-1083).  Same outputs as the single-context call."""
         ctxs = list(ctxs)
-        seeing = np.ascontiguousarray(np.atleast_1d(seeing), dtype=np.float64)
-        gl = np.ascontiguousarray(np.atleast_1d(gl), dtype=np.float64)
-        l0 = np.ascontiguousarray(np.atleast_1d(l0), dtype=np.float64)
-        lbda = np.ascontiguousarray(np.atleast_1d(lbda), dtype=np.float64)
-        nt, nl = seeing.size, lbda.size
-        three = np.zeros(nt, np.uint8) if three_lgs is None else \
-            np.ascontiguousarray(np.atleast_1d(three_lgs)).astype(np.uint8)
-        if wind_speed is None:
-            wind_speed = float(np.full_like(np.array(h), 12.5)[0])      # psfrec.py:61
-        hh = np.ascontiguousarray(h, dtype=np.float64)
-        if hh.size != 2:
-            raise ValueError('exactly two layers are supported (psfrec.py:66)')
-        mrec = mres = None
-        if masks is not None:
-            mrec = np.ascontiguousarray(masks[0]).astype(np.uint8).reshape(-1)
-            mres = np.ascontiguousarray(masks[1]).astype(np.uint8).reshape(-1)
-            assert mrec.size == DIM_AO * DIM_AO and mres.size == DIM_AO * DIM_AO
-        n = ctxs[0].dimpsf
-        psf = np.empty((nt, nl, n, n)) if want_psf else None
-        psum = np.empty((nl, n, n)) if want_sum else None
-        fit = np.empty((nt, nl, NFIT)) if want_fit else None
-        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        seeing, gl, l0, lbda, three, hh, wind_speed, mrec, mres = Context._inputs(lbda, seeing, gl, l0, three_lgs, h,
+                                                                                 wind_speed, masks)
+        arrays = ctxs[0]._outputs((seeing.size,), lbda.size, want_psf, want_sum, want_fit)
         handles = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
         fn = ctxs[0].lib.mpsfr_reconstruct_multi_async if _async else ctxs[0].lib.mpsfr_reconstruct_multi
-        arrays = dict(psf=psf, psf_sum=psum, fit=fit)
         if _async:
             # the refusals the library makes BEFORE it queues anything are made here, with nothing touched:
             # whatever the library itself reports below is a failed shard, after which it has abandoned every
@@ -652,9 +631,9 @@ class Context:
                    for c in ctxs[1:]):
                 raise MpsfrError(-1, 'the contexts must share dim, dimpsf, pixscale and precision')
         try:
-            _check(fn(handles, len(ctxs), nt, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), _dptr(hh),
-                      float(wind_speed), int(npsflin), nl, _dptr(lbda), _u8ptr(mrec), _u8ptr(mres),
-                      vp(psf), vp(psum), vp(fit)))
+            _check(fn(handles, len(ctxs), seeing.size, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), _dptr(hh),
+                      float(wind_speed), int(npsflin), lbda.size, _dptr(lbda), _u8ptr(mrec), _u8ptr(mres),
+                      *_host_outs(arrays)))
         except MpsfrError:
             if _async:
                 # The library abandoned the shards it had queued on ctxs[0..k-1]; earlier reconstruct_async tickets
@@ -675,34 +654,12 @@ class Context:
             return PendingMulti(ctxs, handles, arrays)
         return arrays
 
-    def reconstruct_device(self, lbda, seeing, gl, l0, three_lgs, h, wind_speed, npsflin, masks,
-                           psf_ptr, sum_ptr, fit_ptr):
-        """Device-buffer call (asynchronous): the three outputs are raw device pointers (int or
-        None) on this context's GPU, e.g. torch tensors' data_ptr()."""
-        seeing = np.ascontiguousarray(seeing, dtype=np.float64)
-        gl = np.ascontiguousarray(gl, dtype=np.float64)
-        l0 = np.ascontiguousarray(l0, dtype=np.float64)
-        lbda = np.ascontiguousarray(lbda, dtype=np.float64)
-        three = np.ascontiguousarray(three_lgs).astype(np.uint8)
-        hh = np.ascontiguousarray(h, dtype=np.float64)
-        mrec = mres = None
-        if masks is not None:
-            mrec = np.ascontiguousarray(masks[0]).astype(np.uint8).reshape(-1)
-            mres = np.ascontiguousarray(masks[1]).astype(np.uint8).reshape(-1)
-        _check(self.lib.mpsfr_reconstruct(
-            self._h, seeing.size, _dptr(seeing), _dptr(gl), _dptr(l0), _u8ptr(three), _dptr(hh),
-            float(wind_speed), int(npsflin), lbda.size, _dptr(lbda), _u8ptr(mrec), _u8ptr(mres),
-            C.c_void_p(psf_ptr), C.c_void_p(sum_ptr), C.c_void_p(fit_ptr), 1))
-
     def simul_psd(self, seeing, gl, l0, three_lgs=False, h=(100, 10000), wind_speed=None, npsflin=1, masks=None):
         """simul_psd_wfm (psfrec.py:36-151): (npsflin^2, dim, dim) PSD, centred, reference units."""
         if wind_speed is None:
             wind_speed = float(np.full_like(np.array(h), 12.5)[0])      # psfrec.py:61
         hh = np.ascontiguousarray(h, dtype=np.float64)
-        mrec = mres = None
-        if masks is not None:
-            mrec = np.ascontiguousarray(masks[0]).astype(np.uint8).reshape(-1)
-            mres = np.ascontiguousarray(masks[1]).astype(np.uint8).reshape(-1)
+        mrec, mres = _masks(masks)
         out = np.empty((int(npsflin) ** 2, self.dim, self.dim))
         _check(self.lib.mpsfr_simul_psd(self._h, float(seeing), float(gl), float(l0), int(bool(three_lgs)), _dptr(hh),
                                         float(wind_speed), int(npsflin), _u8ptr(mrec), _u8ptr(mres), _dptr(out)))
@@ -741,15 +698,11 @@ class Context:
                 raise ValueError('phase_static must have the shape of the pupil %s, not %s' % (pup.shape, ph.shape))
         lbda_m = np.ascontiguousarray(np.atleast_1d(lbda_m), dtype=np.float64).ravel()
         dimnum = self.dim if dimnum is None else int(dimnum)
-        shape = (psd.shape[0], lbda_m.size, dimnum, dimnum)
-        if out is None:
-            res = np.empty(shape)
-            ptr, on_device = res.ctypes.data_as(C.c_void_p), 0
-        else:
-            res, ptr, on_device = None, C.c_void_p(int(out)), 1
+        res = np.empty((psd.shape[0], lbda_m.size, dimnum, dimnum)) if out is None else None
         _check(self.lib.mpsfr_psd_to_psf(self._h, psd.shape[0], _dptr(psd), pup.shape[0], _dptr(pup),
                                          None if ph is None else _dptr(ph), float(D), lbda_m.size, _dptr(lbda_m),
-                                         dimnum, ptr, on_device))
+                                         dimnum, _vptr(res) if out is None else C.c_void_p(int(out)),
+                                         0 if out is None else 1))
         return res
 
     def convolve_stamps(self, lbda, seeing, gl, l0, psf):
@@ -766,31 +719,55 @@ class Context:
                                               _dptr(lbda), _dptr(st), _dptr(out)))
         return out[0] if single else out
 
+    # ---- the stamp family.  Every C function's arguments are built once, by a _call_* method that takes host arrays
+    # (on_device = 0) or raw device pointers (on_device = 1; None or 0 is NULL) in the same places.
+
+    def _call_fit(self, fn, nstamp, stamps, fit, on_device):
+        p = _devptr if on_device else _vptr
+        _check(fn(self._h, int(nstamp), p(stamps), p(fit), on_device))
+
+    def _call_fit_observed(self, nstamp, stamps, var, flags, fit, on_device):
+        p = _devptr if on_device else _vptr
+        _check(self.lib.mpsfr_fit_stamps_observed(self._h, int(nstamp), p(stamps), p(var), flags, p(fit), on_device))
+
+    def _call_fit_psf(self, nstamp, stamps, var, npsf, psf, index, shift, flags, fit, on_device):
+        p = _devptr if on_device else _vptr
+        _check(self.lib.mpsfr_fit_stamps_psf(self._h, int(nstamp), p(stamps), p(var), int(npsf), p(psf), p(index),
+                                             p(shift), flags, p(fit), on_device))
+
+    def _call_metrics(self, nstamp, stamps, centers, rad, box, frac, out, on_device):
+        p = _devptr if on_device else _vptr
+        _check(self.lib.mpsfr_stamp_metrics(self._h, int(nstamp), p(stamps), p(centers), rad.size, _dptr(rad),
+                                            box.size, _dptr(box), frac.size, _dptr(frac), p(out), on_device))
+
     def fit_stamps(self, stamps):
         st = np.ascontiguousarray(stamps, dtype=np.float64).reshape(-1, self.dimpsf, self.dimpsf)
         out = np.empty((st.shape[0], NFIT))
-        _check(self.lib.mpsfr_fit_stamps(self._h, st.shape[0], st.ctypes.data_as(C.c_void_p),
-                                         out.ctypes.data_as(C.c_void_p), 0))
+        self._call_fit(self.lib.mpsfr_fit_stamps, st.shape[0], st, out, 0)
         return out
+
+    def fit_stamps_device(self, nstamp, stamps_ptr, fit_ptr):
+        """Device-buffer circular fit (asynchronous, on_device = 1): `stamps_ptr` ([nstamp][dimpsf][dimpsf] float64)
+        and `fit_ptr` ([nstamp][NFIT] float64) are raw device pointers (int) on this context's GPU; the call is
+        queued on the context stream, after any device-output reconstruct of this context."""
+        _positive_int('nstamp', nstamp)
+        _device_pointers(stamps_ptr=stamps_ptr, fit_ptr=fit_ptr)
+        self._call_fit(self.lib.mpsfr_fit_stamps, nstamp, stamps_ptr, fit_ptr, 1)
 
     def fit_stamps_elliptical(self, stamps):
         """Elliptical Moffat fit (mpsfr_fit_stamps_elliptical) of stamps (..., dimpsf, dimpsf): (n, NFIT_ELL) rows."""
         st = elliptical_stamps(stamps, self.dimpsf)
         out = np.empty((st.shape[0], NFIT_ELL))
-        _check(self.lib.mpsfr_fit_stamps_elliptical(self._h, st.shape[0], st.ctypes.data_as(C.c_void_p),
-                                                    out.ctypes.data_as(C.c_void_p), 0))
+        self._call_fit(self.lib.mpsfr_fit_stamps_elliptical, st.shape[0], st, out, 0)
         return out
 
     def fit_stamps_elliptical_device(self, nstamp, stamps_ptr, fit_ptr):
         """Device-buffer elliptical fit (asynchronous, on_device = 1): `stamps_ptr` ([nstamp][dimpsf][dimpsf] float64)
         and `fit_ptr` ([nstamp][NFIT_ELL] float64) are raw device pointers (int) on this context's GPU; the call is
         queued on the context stream, after any device-output reconstruct of this context."""
-        if isinstance(nstamp, bool) or not isinstance(nstamp, (int, np.integer)) or nstamp < 1:
-            raise ValueError('nstamp must be a positive integer')
-        if not stamps_ptr or not fit_ptr:
-            raise ValueError('stamps_ptr and fit_ptr must be device pointers')
-        _check(self.lib.mpsfr_fit_stamps_elliptical(self._h, int(nstamp), C.c_void_p(int(stamps_ptr)),
-                                                    C.c_void_p(int(fit_ptr)), 1))
+        _positive_int('nstamp', nstamp)
+        _device_pointers(stamps_ptr=stamps_ptr, fit_ptr=fit_ptr)
+        self._call_fit(self.lib.mpsfr_fit_stamps_elliptical, nstamp, stamps_ptr, fit_ptr, 1)
 
     def fit_stamps_observed(self, stamps, var=None, background=True, circular=True):
         """Weighted Moffat fit of observed stars (mpsfr_fit_stamps_observed) of stamps (..., dimpsf, dimpsf): (n, NFIT_ELL)
@@ -800,9 +777,7 @@ class Context:
         st, va = observed_stamps(stamps, var, self.dimpsf)
         flags = observed_flags(background, circular)
         out = np.empty((st.shape[0], NFIT_ELL))
-        _check(self.lib.mpsfr_fit_stamps_observed(self._h, st.shape[0], st.ctypes.data_as(C.c_void_p),
-                                                  None if va is None else va.ctypes.data_as(C.c_void_p), flags,
-                                                  out.ctypes.data_as(C.c_void_p), 0))
+        self._call_fit_observed(st.shape[0], st, va, flags, out, 0)
         return out
 
     def fit_stamps_observed_device(self, nstamp, stamps_ptr, fit_ptr, var_ptr=None, background=True, circular=True):
@@ -810,14 +785,10 @@ class Context:
         float64; var_ptr None: unit weights) and `fit_ptr` ([nstamp][NFIT_ELL] float64) are raw device pointers (int) on
         this context's GPU; the call is queued on the context stream, after any device-output reconstruct of this
         context."""
-        if isinstance(nstamp, bool) or not isinstance(nstamp, (int, np.integer)) or nstamp < 1:
-            raise ValueError('nstamp must be a positive integer')
-        if not stamps_ptr or not fit_ptr:
-            raise ValueError('stamps_ptr and fit_ptr must be device pointers')
+        _positive_int('nstamp', nstamp)
+        _device_pointers(stamps_ptr=stamps_ptr, fit_ptr=fit_ptr)
         flags = observed_flags(background, circular)
-        _check(self.lib.mpsfr_fit_stamps_observed(self._h, int(nstamp), C.c_void_p(int(stamps_ptr)),
-                                                  C.c_void_p(int(var_ptr)) if var_ptr else None, flags,
-                                                  C.c_void_p(int(fit_ptr)), 1))
+        self._call_fit_observed(nstamp, stamps_ptr, var_ptr, flags, fit_ptr, 1)
 
     def fit_stamps_psf(self, stamps, psf, var=None, psf_index=None, shift=None, background=True, fixed_shift=False):
         """PSF-model fit of observed stars (mpsfr_fit_stamps_psf): the model stamps `psf` (..., dimpsf, dimpsf), resampled
@@ -830,12 +801,7 @@ class Context:
         st, va = observed_stamps(stamps, var, self.dimpsf)
         ps, ix, sh, flags = psf_fit_arguments(st.shape[0], psf, psf_index, shift, background, fixed_shift, self.dimpsf)
         out = np.empty((st.shape[0], NFIT_PSF))
-        vp = C.c_void_p
-        _check(self.lib.mpsfr_fit_stamps_psf(self._h, st.shape[0], st.ctypes.data_as(vp),
-                                             None if va is None else va.ctypes.data_as(vp), ps.shape[0],
-                                             ps.ctypes.data_as(vp), None if ix is None else ix.ctypes.data_as(vp),
-                                             None if sh is None else sh.ctypes.data_as(vp), flags,
-                                             out.ctypes.data_as(vp), 0))
+        self._call_fit_psf(st.shape[0], st, va, ps.shape[0], ps, ix, sh, flags, out, 0)
         return out
 
     def fit_stamps_psf_device(self, nstamp, stamps_ptr, npsf, psf_ptr, fit_ptr, var_ptr=None, psf_index_ptr=None,
@@ -846,21 +812,15 @@ class Context:
         raw device pointers (int) on this context's GPU; the call is queued on the context stream, after any
         device-output reconstruct of this context.  An index out of range or a shift outside the domain makes that
         row status 2."""
-        for name, n in (('nstamp', nstamp), ('npsf', npsf)):
-            if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
-                raise ValueError('%s must be a positive integer' % name)
-        if not stamps_ptr or not psf_ptr or not fit_ptr:
-            raise ValueError('stamps_ptr, psf_ptr and fit_ptr must be device pointers')
+        _positive_int('nstamp', nstamp)
+        _positive_int('npsf', npsf)
+        _device_pointers(stamps_ptr=stamps_ptr, psf_ptr=psf_ptr, fit_ptr=fit_ptr)
         if not psf_index_ptr and npsf != nstamp:
             raise ValueError('without psf_index_ptr, npsf must equal nstamp')
         flags = psf_fit_flags(background, fixed_shift)
         if fixed_shift and not shift_ptr:
             raise ValueError('fixed_shift needs shift_ptr')
-
-        def ptr(v):
-            return C.c_void_p(int(v)) if v else None
-        _check(self.lib.mpsfr_fit_stamps_psf(self._h, int(nstamp), ptr(stamps_ptr), ptr(var_ptr), int(npsf),
-                                             ptr(psf_ptr), ptr(psf_index_ptr), ptr(shift_ptr), flags, ptr(fit_ptr), 1))
+        self._call_fit_psf(nstamp, stamps_ptr, var_ptr, npsf, psf_ptr, psf_index_ptr, shift_ptr, flags, fit_ptr, 1)
 
     def stamp_metrics(self, stamps, radii_px, boxes_px, fractions, centers=None):
         """PSF energy metrics (mpsfr_stamp_metrics) of stamps (..., dimpsf, dimpsf): (n, NMET_HEAD + nrad + nbox +
@@ -871,10 +831,7 @@ class Context:
         rad, box, frac = metric_parameters(radii_px, boxes_px, fractions, self.dimpsf)
         ce = None if centers is None else metric_centers(centers, st.shape[0])
         out = np.empty((st.shape[0], NMET_HEAD + rad.size + box.size + frac.size))
-        _check(self.lib.mpsfr_stamp_metrics(self._h, st.shape[0], st.ctypes.data_as(C.c_void_p),
-                                            None if ce is None else ce.ctypes.data_as(C.c_void_p),
-                                            rad.size, _dptr(rad), box.size, _dptr(box), frac.size, _dptr(frac),
-                                            out.ctypes.data_as(C.c_void_p), 0))
+        self._call_metrics(st.shape[0], st, ce, rad, box, frac, out, 0)
         return out
 
     def stamp_metrics_device(self, nstamp, stamps_ptr, out_ptr, radii_px, boxes_px, fractions, centers_ptr=None):
@@ -882,15 +839,10 @@ class Context:
         ([nstamp][NMET_HEAD + nrad + nbox + nfrac] float64) and `centers_ptr` ([nstamp][2] float64, or None for the
         centroids) are raw device pointers (int) on this context's GPU; the call is queued on the context stream,
         after any device-output reconstruct of this context."""
-        if isinstance(nstamp, bool) or not isinstance(nstamp, (int, np.integer)) or nstamp < 1:
-            raise ValueError('nstamp must be a positive integer')
-        if not stamps_ptr or not out_ptr:
-            raise ValueError('stamps_ptr and out_ptr must be device pointers')
+        _positive_int('nstamp', nstamp)
+        _device_pointers(stamps_ptr=stamps_ptr, out_ptr=out_ptr)
         rad, box, frac = metric_parameters(radii_px, boxes_px, fractions, self.dimpsf)
-        _check(self.lib.mpsfr_stamp_metrics(self._h, int(nstamp), C.c_void_p(int(stamps_ptr)),
-                                            C.c_void_p(int(centers_ptr)) if centers_ptr else None,
-                                            rad.size, _dptr(rad), box.size, _dptr(box), frac.size, _dptr(frac),
-                                            C.c_void_p(int(out_ptr)), 1))
+        self._call_metrics(nstamp, stamps_ptr, centers_ptr, rad, box, frac, out_ptr, 1)
 
     def debug_fetch(self, what, shape):
         out = np.empty(int(np.prod(shape)))

@@ -536,6 +536,71 @@ int build_constant_tables(mpsfr_ctx* c) {
     return build_series_tables(c);
 }
 
+// The calls queued so far run on the pipeline lanes: stream s waits for them on the GPU, so that device stamps written
+// by a device-output reconstruct of this context are complete when a kernel on s reads them.
+int wait_for_lanes(mpsfr_ctx* c, hipStream_t s) {
+    for (int k = 0; k < mpsfr_ctx::MAX_LANES; ++k)
+        if (c->lane[k].busy && c->lane[k].stream != s) HIPCHK(hipStreamWaitEvent(s, lane_end(c, c->lane[k]), 0));
+    return MPSFR_OK;
+}
+
+// An input array of a stamp call: `count` elements of `elem` bytes, or NULL for an optional that is absent.
+struct StampIn {
+    const void* p;
+    size_t count, elem;
+};
+
+// One stamp call (the fits and the metrics of caller-provided stamps) on the context stream, after the lanes, timed
+// under the fit's profiling id.  launch(s, d, d_out) receives the inputs in the order of `in` and the nout output
+// values as device pointers.  on_device: they are the caller's own pointers and the call returns once it is queued.
+// Else the arrays are staged in c->stage -- the inputs of doubles in order, then the output, then the narrower
+// inputs (int32 indices), so that everything is aligned; an absent input gets no room and stays NULL -- copied in,
+// the output is copied back and the call waits for it.
+template <size_t N, class Launch>
+int stamp_call(mpsfr_ctx* c, int on_device, const StampIn (&in)[N], double* out, size_t nout, Launch launch) {
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    int rc;
+    if ((rc = wait_for_lanes(c, s))) return rc;
+    const void* d[N];
+    double* d_out = out;
+    for (size_t i = 0; i < N; ++i) d[i] = in[i].p;
+    if (!on_device) {
+        size_t off[N] = {}, off_out = 0, bytes = 0;
+        for (int narrow = 0; narrow < 2; ++narrow) {
+            for (size_t i = 0; i < N; ++i)
+                if (in[i].p && (in[i].elem < sizeof(double)) == (narrow == 1)) {
+                    off[i] = bytes;
+                    bytes += in[i].count * in[i].elem;
+                }
+            if (!narrow) {
+                off_out = bytes;
+                bytes += nout * sizeof(double);
+            }
+        }
+        if ((rc = ensure(c, c->stage, bytes))) return rc;
+        char* base = (char*)c->stage.p;
+        d_out = (double*)(base + off_out);
+        for (size_t i = 0; i < N; ++i)
+            if (in[i].p) {
+                d[i] = base + off[i];
+                HIPCHK(hipMemcpyAsync(base + off[i], in[i].p, in[i].count * in[i].elem, hipMemcpyHostToDevice, s));
+            }
+    }
+    {
+        ProfScope ps(c, K_FIT);
+        launch(s, d, d_out);
+    }
+    HIPCHK(hipGetLastError());
+    if (!on_device) {
+        HIPCHK(hipMemcpyAsync(out, d_out, nout * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return MPSFR_OK;
+}
+
+const size_t kStampPix = (size_t)NS * NS;
+
 }  // namespace
 
 extern "C" {
@@ -840,24 +905,39 @@ struct StageIO {
     const double* bw = nullptr;
 };
 
-static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const double* gl,
-                            const double* l0, const uint8_t* three_lgs, const double h[2],
-                            double wind_speed, int npsflin, int nl, const double* lbda_nm,
-                            const uint8_t* mask_rec, const uint8_t* mask_res, double* psf_out,
-                            double* psf_sum_out, double* fit_out, int on_device, const StageIO& io = StageIO());
+// One call of the pipeline, as its entry point describes it to guarded_call and reconstruct_impl.  The defaults are
+// those of the stage-level entry points, which set only what they use: one row of the reference's atmosphere (its
+// values do not reach their result), one direction, one wavelength, host buffers.
+static const double kSeeing = 1.0, kGl = 0.5, kL0 = 20.0, kLbda = 700.0, kH[2] = {100.0, 10000.0};
+
+struct CallArgs {
+    int ntask = 1;
+    const double* seeing = &kSeeing;
+    const double* gl = &kGl;          // (gl only sets the tip-tilt kernel, which a PSD does not use)
+    const double* l0 = &kL0;
+    const uint8_t* three_lgs = nullptr;
+    const double* h = kH;             // [2]
+    double wind_speed = 12.0;
+    int npsflin = 1;
+    int nl = 1;
+    const double* lbda_nm = &kLbda;   // (a PSD does not use the per-wavelength tables)
+    const uint8_t* mask_rec = nullptr;
+    const uint8_t* mask_res = nullptr;
+    double* psf_out = nullptr;
+    double* psf_sum_out = nullptr;
+    double* fit_out = nullptr;
+    int on_device = 0;
+};
+
+static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io);
 
 // Every entry point that runs the pipeline goes through this guard.  A call that fails leaves the
 // pipelining state as it found it: the lane rotation and the ring of parameter slots do not advance, and
 // an event registered with mpsfr_wait_event is consumed (the caller may destroy it after the call,
 // whatever the outcome).
-static int guarded_call(mpsfr_ctx* c, int ntask, const double* seeing, const double* gl,
-                        const double* l0, const uint8_t* three_lgs, const double h[2],
-                        double wind_speed, int npsflin, int nl, const double* lbda_nm,
-                        const uint8_t* mask_rec, const uint8_t* mask_res, double* psf_out,
-                        double* psf_sum_out, double* fit_out, int on_device, const StageIO& io) {
+static int guarded_call(mpsfr_ctx* c, const CallArgs& a, const StageIO& io = StageIO()) {
     const unsigned lane_rr0 = c->lane_rr, stage0 = c->stage_next;
-    const int rc = reconstruct_impl(c, ntask, seeing, gl, l0, three_lgs, h, wind_speed, npsflin, nl, lbda_nm,
-                                    mask_rec, mask_res, psf_out, psf_sum_out, fit_out, on_device, io);
+    const int rc = reconstruct_impl(c, a, io);
     if (rc != MPSFR_OK) {
         // whatever the failed call has queued (it may have cleared a slot's guard and started chunks
         // on other lanes) must have drained before the next call reuses the slot and the workspaces
@@ -873,14 +953,38 @@ static int guarded_call(mpsfr_ctx* c, int ntask, const double* seeing, const dou
     return rc;
 }
 
+// The directions of a call: the npsflin x npsflin grid (npos = 0, where min_npos allows it) or the caller's npos
+// positions pos [npos][2] (arcsec), which take npsflin = 0.  Positions go to stage A through `io`, and npsflin becomes
+// 1: every position is one direction.
+static int grid_or_positions(int min_npos, int npos, const double* pos, int& npsflin, StageIO& io) {
+    if (npos < min_npos || npos > 25) return fail(MPSFR_E_INVALID, "npos=%d out of range %d..25", npos, min_npos);
+    if (npos == 0) {
+        if (npsflin < 1 || npsflin > 5) return fail(MPSFR_E_INVALID, "npsflin=%d out of range 1..5", npsflin);
+        return MPSFR_OK;
+    }
+    if (npsflin != 0) return fail(MPSFR_E_INVALID, "a call with positions (npos >= 1) takes npsflin = 0");
+    if (!pos) return fail(MPSFR_E_INVALID, "pos_arcsec is NULL");
+    for (int k = 0; k < 2 * npos; ++k)
+        if (!std::isfinite(pos[k]) || std::fabs(pos[k]) > 60.0)
+            return fail(MPSFR_E_INVALID, "position %d: need finite |x|, |y| <= 60 arcsec", k / 2);
+    io.npos = npos;
+    io.pos = pos;
+    npsflin = 1;
+    return MPSFR_OK;
+}
+
 int mpsfr_reconstruct(mpsfr_ctx* c, int ntask, const double* seeing, const double* gl,
                       const double* l0, const uint8_t* three_lgs, const double h[2],
                       double wind_speed, int npsflin, int nl, const double* lbda_nm,
                       const uint8_t* mask_rec, const uint8_t* mask_res, double* psf_out,
                       double* psf_sum_out, double* fit_out, int on_device) {
     if (!c) return fail(MPSFR_E_INVALID, "ctx is NULL");
-    return guarded_call(c, ntask, seeing, gl, l0, three_lgs, h, wind_speed, npsflin, nl, lbda_nm, mask_rec, mask_res,
-                        psf_out, psf_sum_out, fit_out, on_device, StageIO());
+    CallArgs a;
+    a.ntask = ntask, a.seeing = seeing, a.gl = gl, a.l0 = l0, a.three_lgs = three_lgs;
+    a.h = h, a.wind_speed = wind_speed, a.npsflin = npsflin;
+    a.nl = nl, a.lbda_nm = lbda_nm, a.mask_rec = mask_rec, a.mask_res = mask_res;
+    a.psf_out = psf_out, a.psf_sum_out = psf_sum_out, a.fit_out = fit_out, a.on_device = on_device;
+    return guarded_call(c, a);
 }
 
 int mpsfr_reconstruct_field(mpsfr_ctx* c, int ntask, const double* seeing, const double* gl,
@@ -890,16 +994,15 @@ int mpsfr_reconstruct_field(mpsfr_ctx* c, int ntask, const double* seeing, const
                             const uint8_t* mask_res, double* psf_out, double* psf_sum_out,
                             double* fit_out, int on_device) {
     if (!c) return fail(MPSFR_E_INVALID, "ctx is NULL");
-    if (npos < 1 || npos > 25) return fail(MPSFR_E_INVALID, "npos=%d out of range 1..25", npos);
-    if (!pos_arcsec) return fail(MPSFR_E_INVALID, "pos_arcsec is NULL");
-    for (int k = 0; k < 2 * npos; ++k)
-        if (!std::isfinite(pos_arcsec[k]) || std::fabs(pos_arcsec[k]) > 60.0)
-            return fail(MPSFR_E_INVALID, "position %d: need finite |x|, |y| <= 60 arcsec", k / 2);
     StageIO io;
-    io.npos = npos;
-    io.pos = pos_arcsec;
-    return guarded_call(c, ntask, seeing, gl, l0, three_lgs, h, wind_speed, 1, nl, lbda_nm, mask_rec, mask_res,
-                        psf_out, psf_sum_out, fit_out, on_device, io);
+    CallArgs a;
+    a.npsflin = 0;
+    if (int rc = grid_or_positions(1, npos, pos_arcsec, a.npsflin, io)) return rc;
+    a.ntask = ntask, a.seeing = seeing, a.gl = gl, a.l0 = l0, a.three_lgs = three_lgs;
+    a.h = h, a.wind_speed = wind_speed;
+    a.nl = nl, a.lbda_nm = lbda_nm, a.mask_rec = mask_rec, a.mask_res = mask_res;
+    a.psf_out = psf_out, a.psf_sum_out = psf_sum_out, a.fit_out = fit_out, a.on_device = on_device;
+    return guarded_call(c, a, io);
 }
 
 static_assert(MAX_BANDS == MPSFR_MAX_BANDS, "K_BAND_REDUCE keeps MPSFR_MAX_BANDS accumulators");
@@ -928,21 +1031,14 @@ int mpsfr_reconstruct_band(mpsfr_ctx* c, int ntask, const double* seeing, const 
     StageIO io;
     io.nband = nband;
     io.bw = w.data();
-    if (npos < 0 || npos > 25) return fail(MPSFR_E_INVALID, "npos=%d out of range 0..25", npos);
-    if (npos > 0) {
-        if (npsflin != 0) return fail(MPSFR_E_INVALID, "a field call (npos >= 1) takes npsflin = 0");
-        if (!pos_arcsec) return fail(MPSFR_E_INVALID, "pos_arcsec is NULL");
-        for (int k = 0; k < 2 * npos; ++k)
-            if (!std::isfinite(pos_arcsec[k]) || std::fabs(pos_arcsec[k]) > 60.0)
-                return fail(MPSFR_E_INVALID, "position %d: need finite |x|, |y| <= 60 arcsec", k / 2);
-        io.npos = npos;
-        io.pos = pos_arcsec;
-        npsflin = 1;
-    } else if (npsflin < 1 || npsflin > 5) {
-        return fail(MPSFR_E_INVALID, "npsflin=%d out of range 1..5", npsflin);
-    }
-    return guarded_call(c, ntask, seeing, gl, l0, three_lgs, h, wind_speed, npsflin, nl, lbda_nm, mask_rec, mask_res,
-                        band_out, band_sum_out, band_fit_out, on_device, io);
+    CallArgs a;
+    a.npsflin = npsflin;
+    if (int rc = grid_or_positions(0, npos, pos_arcsec, a.npsflin, io)) return rc;
+    a.ntask = ntask, a.seeing = seeing, a.gl = gl, a.l0 = l0, a.three_lgs = three_lgs;
+    a.h = h, a.wind_speed = wind_speed;
+    a.nl = nl, a.lbda_nm = lbda_nm, a.mask_rec = mask_rec, a.mask_res = mask_res;
+    a.psf_out = band_out, a.psf_sum_out = band_sum_out, a.fit_out = band_fit_out, a.on_device = on_device;
+    return guarded_call(c, a, io);
 }
 
 static_assert(MAXLAYER == MPSFR_MAX_LAYERS, "AoLayers holds MPSFR_MAX_LAYERS layers");
@@ -998,6 +1094,8 @@ static int profile_layers(int ntask, int nlayer, const double* h, const double* 
     return MPSFR_OK;
 }
 
+static const double kNoH[2] = {0.0, 0.0};     // h of a profile call: the layers come from StageIO
+
 int mpsfr_reconstruct_profile(mpsfr_ctx* c, int ntask, const double* seeing, const double* gl,
                               const double* l0, const uint8_t* three_lgs,
                               int nlayer, const double* h, const double* wind_speed, const double* wind_dir,
@@ -1008,27 +1106,18 @@ int mpsfr_reconstruct_profile(mpsfr_ctx* c, int ntask, const double* seeing, con
     if (ntask < 1) return fail(MPSFR_E_INVALID, "ntask < 1");
     AoLayers ly;
     std::vector<double> w;
-    int rc = profile_layers(ntask, nlayer, h, wind_speed, wind_dir, cn2, ly, w);
-    if (rc) return rc;
+    if (int rc = profile_layers(ntask, nlayer, h, wind_speed, wind_dir, cn2, ly, w)) return rc;
     StageIO io;
     io.layers = &ly;
     io.cn2 = w.data();
-    if (npos < 0 || npos > 25) return fail(MPSFR_E_INVALID, "npos=%d out of range 0..25", npos);
-    if (npos > 0) {
-        if (npsflin != 0) return fail(MPSFR_E_INVALID, "a field call (npos >= 1) takes npsflin = 0");
-        if (!pos_arcsec) return fail(MPSFR_E_INVALID, "pos_arcsec is NULL");
-        for (int k = 0; k < 2 * npos; ++k)
-            if (!std::isfinite(pos_arcsec[k]) || std::fabs(pos_arcsec[k]) > 60.0)
-                return fail(MPSFR_E_INVALID, "position %d: need finite |x|, |y| <= 60 arcsec", k / 2);
-        io.npos = npos;
-        io.pos = pos_arcsec;
-        npsflin = 1;
-    } else if (npsflin < 1 || npsflin > 5) {
-        return fail(MPSFR_E_INVALID, "npsflin=%d out of range 1..5", npsflin);
-    }
-    const double h2[2] = {0.0, 0.0};     // (the layers come from `io`)
-    return guarded_call(c, ntask, seeing, gl, l0, three_lgs, h2, 0.0, npsflin, nl, lbda_nm, mask_rec, mask_res,
-                        psf_out, psf_sum_out, fit_out, on_device, io);
+    CallArgs a;
+    a.npsflin = npsflin;
+    if (int rc = grid_or_positions(0, npos, pos_arcsec, a.npsflin, io)) return rc;
+    a.ntask = ntask, a.seeing = seeing, a.gl = gl, a.l0 = l0, a.three_lgs = three_lgs;
+    a.h = kNoH, a.wind_speed = 0.0;
+    a.nl = nl, a.lbda_nm = lbda_nm, a.mask_rec = mask_rec, a.mask_res = mask_res;
+    a.psf_out = psf_out, a.psf_sum_out = psf_sum_out, a.fit_out = fit_out, a.on_device = on_device;
+    return guarded_call(c, a, io);
 }
 
 int mpsfr_simul_psd_profile(mpsfr_ctx* c, double seeing, double l0, int three_lgs,
@@ -1038,40 +1127,29 @@ int mpsfr_simul_psd_profile(mpsfr_ctx* c, double seeing, double l0, int three_lg
     if (!c || !psd_out) return fail(MPSFR_E_INVALID, "NULL argument");
     AoLayers ly;
     std::vector<double> w;
-    int rc = profile_layers(1, nlayer, h, wind_speed, wind_dir, cn2, ly, w);
-    if (rc) return rc;
+    if (int rc = profile_layers(1, nlayer, h, wind_speed, wind_dir, cn2, ly, w)) return rc;
     StageIO io;
     io.layers = &ly;
     io.cn2 = w.data();
     io.psd_out = psd_out;
-    if (npos < 0 || npos > 25) return fail(MPSFR_E_INVALID, "npos=%d out of range 0..25", npos);
-    if (npos > 0) {
-        // (the PSD of each position: stage A's directions are the positions, as in a field call)
-        if (npsflin != 0) return fail(MPSFR_E_INVALID, "positions (npos >= 1) take npsflin = 0");
-        if (!pos_arcsec) return fail(MPSFR_E_INVALID, "pos_arcsec is NULL");
-        for (int k = 0; k < 2 * npos; ++k)
-            if (!std::isfinite(pos_arcsec[k]) || std::fabs(pos_arcsec[k]) > 60.0)
-                return fail(MPSFR_E_INVALID, "position %d: need finite |x|, |y| <= 60 arcsec", k / 2);
-        io.npos = npos;
-        io.pos = pos_arcsec;
-        npsflin = 1;
-    } else if (npsflin < 1 || npsflin > 5) {
-        return fail(MPSFR_E_INVALID, "npsflin=%d out of range 1..5", npsflin);
-    }
+    CallArgs a;
+    a.npsflin = npsflin;
+    // (with positions, the PSD of each position: stage A's directions are the positions, as in a field call)
+    if (int rc = grid_or_positions(0, npos, pos_arcsec, a.npsflin, io)) return rc;
     const uint8_t t3 = three_lgs ? 1 : 0;
-    const double lb = 700.0;                 // (the per-wavelength tables are not used)
-    const double h2[2] = {0.0, 0.0};
-    // (gl only sets the tip-tilt kernel, which a PSD does not use)
-    const double gl = 0.5;
-    return guarded_call(c, 1, &seeing, &gl, &l0, &t3, h2, 0.0, npsflin, 1, &lb, mask_rec, mask_res,
-                        nullptr, nullptr, nullptr, 0, io);
+    a.seeing = &seeing, a.l0 = &l0, a.three_lgs = &t3;
+    a.h = kNoH, a.wind_speed = 0.0;
+    a.mask_rec = mask_rec, a.mask_res = mask_res;
+    return guarded_call(c, a, io);
 }
 
-static int reconstruct_impl(mpsfr_ctx* c, int ntask, const double* seeing, const double* gl,
-                            const double* l0, const uint8_t* three_lgs, const double h[2],
-                            double wind_speed, int npsflin, int nl, const double* lbda_nm,
-                            const uint8_t* mask_rec, const uint8_t* mask_res, double* psf_out,
-                            double* psf_sum_out, double* fit_out, int on_device, const StageIO& io) {
+static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) {
+    const int ntask = a.ntask, npsflin = a.npsflin, nl = a.nl;
+    int on_device = a.on_device;
+    const double *seeing = a.seeing, *gl = a.gl, *l0 = a.l0, *h = a.h, *lbda_nm = a.lbda_nm;
+    const uint8_t *three_lgs = a.three_lgs, *mask_rec = a.mask_rec, *mask_res = a.mask_res;
+    const double wind_speed = a.wind_speed;
+    double *psf_out = a.psf_out, *psf_sum_out = a.psf_sum_out, *fit_out = a.fit_out;
     const auto t_enter = std::chrono::steady_clock::now();
     const bool staged = io.psd_out || io.psd_in || io.pre_in || io.stop_pre;
     if (staged && on_device != 0) return fail(MPSFR_E_INVALID, "stage-level calls take host buffers");
@@ -2197,11 +2275,13 @@ int mpsfr_simul_psd(mpsfr_ctx* c, double seeing, double gl, double l0, int three
                     double* psd_out) {
     if (!c || !psd_out) return fail(MPSFR_E_INVALID, "NULL argument");
     const uint8_t t3 = three_lgs ? 1 : 0;
-    const double lb = 700.0;                 // (the per-wavelength tables are not used)
     StageIO io;
     io.psd_out = psd_out;
-    return guarded_call(c, 1, &seeing, &gl, &l0, &t3, h, wind_speed, npsflin, 1, &lb, mask_rec, mask_res,
-                        nullptr, nullptr, nullptr, 0, io);
+    CallArgs a;
+    a.seeing = &seeing, a.gl = &gl, a.l0 = &l0, a.three_lgs = &t3;
+    a.h = h, a.wind_speed = wind_speed, a.npsflin = npsflin;
+    a.mask_rec = mask_rec, a.mask_res = mask_res;
+    return guarded_call(c, a, io);
 }
 
 int mpsfr_psf_from_psd(mpsfr_ctx* c, int ndir, const double* psd, int nl, const double* lbda_nm, double* psf_out) {
@@ -2214,22 +2294,23 @@ int mpsfr_psf_from_psd(mpsfr_ctx* c, int ndir, const double* psd, int nl, const 
     const size_t npix = (size_t)ndir * c->N * c->N;
     for (size_t i = 0; i < npix; ++i)
         if (!std::isfinite(psd[i])) return fail(MPSFR_E_INVALID, "psd[%zu] is not finite", i);
-    const double one = 1.0, half = 0.5, l0 = 20.0, h[2] = {100.0, 10000.0};
     StageIO io;
     io.psd_in = psd;
     io.stop_pre = true;
-    return guarded_call(c, 1, &one, &half, &l0, nullptr, h, 12.0, npl, nl, lbda_nm, nullptr, nullptr,
-                        psf_out, nullptr, nullptr, 0, io);
+    CallArgs a;
+    a.npsflin = npl, a.nl = nl, a.lbda_nm = lbda_nm, a.psf_out = psf_out;
+    return guarded_call(c, a, io);
 }
 
 int mpsfr_convolve_stamps(mpsfr_ctx* c, int ntask, const double* seeing, const double* gl, const double* l0,
                           int nl, const double* lbda_nm, const double* psf_in, double* psf_out) {
     if (!c || !psf_in || !psf_out) return fail(MPSFR_E_INVALID, "NULL argument");
-    const double h[2] = {100.0, 10000.0};
     StageIO io;
     io.pre_in = psf_in;
-    return guarded_call(c, ntask, seeing, gl, l0, nullptr, h, 12.0, 1, nl, lbda_nm, nullptr, nullptr,
-                        psf_out, nullptr, nullptr, 0, io);
+    CallArgs a;
+    a.ntask = ntask, a.seeing = seeing, a.gl = gl, a.l0 = l0;
+    a.nl = nl, a.lbda_nm = lbda_nm, a.psf_out = psf_out;
+    return guarded_call(c, a, io);
 }
 
 int mpsfr_psd_to_psf(mpsfr_ctx* c, int npsd, const double* psd, int npup, const double* pup,
@@ -2331,58 +2412,20 @@ int mpsfr_psd_to_psf(mpsfr_ctx* c, int npsd, const double* psd, int npup, const 
 int mpsfr_fit_stamps(mpsfr_ctx* c, int nstamp, const double* stamps, double* fit_out,
                      int on_device) {
     if (!c || !stamps || !fit_out || nstamp < 1) return fail(MPSFR_E_INVALID, "bad argument");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const size_t per = (size_t)NS * NS;
-    if (on_device) {
-        ProfScope ps(c, K_FIT);
-        launch_fit(s, nstamp, stamps, false, fit_out, c->f64);
-        HIPCHK(hipGetLastError());
-        return MPSFR_OK;
-    }
-    int rc;
-    if ((rc = ensure(c, c->stage, (size_t)nstamp * (per + NFIT) * sizeof(double)))) return rc;
-    double* d_st = (double*)c->stage.p;
-    double* d_ft = d_st + (size_t)nstamp * per;
-    HIPCHK(hipMemcpyAsync(d_st, stamps, (size_t)nstamp * per * sizeof(double), hipMemcpyHostToDevice, s));
-    {
-        ProfScope ps(c, K_FIT);
-        launch_fit(s, nstamp, d_st, false, d_ft, c->f64);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(fit_out, d_ft, (size_t)nstamp * NFIT * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return MPSFR_OK;
+    const StampIn in[] = {{stamps, nstamp * kStampPix, sizeof(double)}};
+    return stamp_call(c, on_device, in, fit_out, (size_t)nstamp * NFIT,
+                      [&](hipStream_t s, const void* const* d, double* d_fit) {
+                          launch_fit(s, nstamp, (const double*)d[0], false, d_fit, c->f64);
+                      });
 }
 
 int mpsfr_fit_stamps_elliptical(mpsfr_ctx* c, int nstamp, const double* stamps, double* fit_out, int on_device) {
     if (!c || !stamps || !fit_out || nstamp < 1) return fail(MPSFR_E_INVALID, "bad argument");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const size_t per = (size_t)NS * NS;
-    // the calls queued so far run on the pipeline lanes: the fit waits for them on the GPU, so that device stamps
-    // written by a device-output reconstruct of this context are complete when it reads them
-    for (int k = 0; k < mpsfr_ctx::MAX_LANES; ++k)
-        if (c->lane[k].busy && c->lane[k].stream != s) HIPCHK(hipStreamWaitEvent(s, lane_end(c, c->lane[k]), 0));
-    if (on_device) {
-        ProfScope ps(c, K_FIT);
-        launch_fit_ell(s, nstamp, stamps, fit_out, c->f64);
-        HIPCHK(hipGetLastError());
-        return MPSFR_OK;
-    }
-    int rc;
-    if ((rc = ensure(c, c->stage, (size_t)nstamp * (per + NFIT_ELL) * sizeof(double)))) return rc;
-    double* d_st = (double*)c->stage.p;
-    double* d_ft = d_st + (size_t)nstamp * per;
-    HIPCHK(hipMemcpyAsync(d_st, stamps, (size_t)nstamp * per * sizeof(double), hipMemcpyHostToDevice, s));
-    {
-        ProfScope ps(c, K_FIT);
-        launch_fit_ell(s, nstamp, d_st, d_ft, c->f64);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(fit_out, d_ft, (size_t)nstamp * NFIT_ELL * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return MPSFR_OK;
+    const StampIn in[] = {{stamps, nstamp * kStampPix, sizeof(double)}};
+    return stamp_call(c, on_device, in, fit_out, (size_t)nstamp * NFIT_ELL,
+                      [&](hipStream_t s, const void* const* d, double* d_fit) {
+                          launch_fit_ell(s, nstamp, (const double*)d[0], d_fit, c->f64);
+                      });
 }
 
 int mpsfr_fit_stamps_observed(mpsfr_ctx* c, int nstamp, const double* stamps, const double* var, int flags,
@@ -2390,34 +2433,11 @@ int mpsfr_fit_stamps_observed(mpsfr_ctx* c, int nstamp, const double* stamps, co
     if (!c || !stamps || !fit_out || nstamp < 1) return fail(MPSFR_E_INVALID, "bad argument");
     if (flags & ~(MPSFR_FIT_BACKGROUND | MPSFR_FIT_ELLIPTICAL))
         return fail(MPSFR_E_INVALID, "fit_stamps_observed: unknown flag bits");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const size_t per = (size_t)NS * NS;
-    // as mpsfr_fit_stamps_elliptical: device stamps written by a device-output reconstruct of this context are
-    // complete when the kernel reads them
-    for (int k = 0; k < mpsfr_ctx::MAX_LANES; ++k)
-        if (c->lane[k].busy && c->lane[k].stream != s) HIPCHK(hipStreamWaitEvent(s, lane_end(c, c->lane[k]), 0));
-    if (on_device) {
-        ProfScope ps(c, K_FIT);
-        launch_fit_obs(s, nstamp, stamps, var, flags, fit_out, c->f64);
-        HIPCHK(hipGetLastError());
-        return MPSFR_OK;
-    }
-    int rc;
-    if ((rc = ensure(c, c->stage, (size_t)nstamp * ((var ? 2 : 1) * per + NFIT_ELL) * sizeof(double)))) return rc;
-    double* d_st = (double*)c->stage.p;
-    double* d_va = var ? d_st + (size_t)nstamp * per : nullptr;
-    double* d_ft = d_st + (size_t)nstamp * per * (var ? 2 : 1);
-    HIPCHK(hipMemcpyAsync(d_st, stamps, (size_t)nstamp * per * sizeof(double), hipMemcpyHostToDevice, s));
-    if (var) HIPCHK(hipMemcpyAsync(d_va, var, (size_t)nstamp * per * sizeof(double), hipMemcpyHostToDevice, s));
-    {
-        ProfScope ps(c, K_FIT);
-        launch_fit_obs(s, nstamp, d_st, d_va, flags, d_ft, c->f64);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(fit_out, d_ft, (size_t)nstamp * NFIT_ELL * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return MPSFR_OK;
+    const StampIn in[] = {{stamps, nstamp * kStampPix, sizeof(double)}, {var, nstamp * kStampPix, sizeof(double)}};
+    return stamp_call(c, on_device, in, fit_out, (size_t)nstamp * NFIT_ELL,
+                      [&](hipStream_t s, const void* const* d, double* d_fit) {
+                          launch_fit_obs(s, nstamp, (const double*)d[0], (const double*)d[1], flags, d_fit, c->f64);
+                      });
 }
 
 static_assert(NFIT_PSF == MPSFR_NFIT_PSF, "K_FIT_PSF row layout");
@@ -2442,44 +2462,14 @@ int mpsfr_fit_stamps_psf(mpsfr_ctx* c, int nstamp, const double* stamps, const d
                 if (!(std::fabs(shift[k]) <= MPSFR_FIT_PSF_MAX_SHIFT))
                     return fail(MPSFR_E_INVALID, "fit_stamps_psf: a shift that is not finite or beyond 8 pixels");
     }
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const size_t per = (size_t)NS * NS;
-    // as mpsfr_fit_stamps_elliptical: device stamps written by a device-output reconstruct of this context are
-    // complete when the kernel reads them
-    for (int k = 0; k < mpsfr_ctx::MAX_LANES; ++k)
-        if (c->lane[k].busy && c->lane[k].stream != s) HIPCHK(hipStreamWaitEvent(s, lane_end(c, c->lane[k]), 0));
-    if (on_device) {
-        ProfScope ps(c, K_FIT);
-        launch_fit_psf(s, nstamp, stamps, var, npsf, psf, psf_index, shift, flags, fit_out, c->f64);
-        HIPCHK(hipGetLastError());
-        return MPSFR_OK;
-    }
-    int rc;
-    // stars, [variances,] model stamps, [shifts,] rows, then the indices (the doubles first: alignment)
-    const size_t nd = (size_t)nstamp * ((var ? 2 : 1) * per + (shift ? 2 : 0) + NFIT_PSF) + (size_t)npsf * per;
-    if ((rc = ensure(c, c->stage, nd * sizeof(double) + (psf_index ? (size_t)nstamp * sizeof(int32_t) : 0))))
-        return rc;
-    double* d_st = (double*)c->stage.p;
-    double* d_va = var ? d_st + (size_t)nstamp * per : nullptr;
-    double* d_ps = d_st + (size_t)nstamp * per * (var ? 2 : 1);
-    double* d_sh = shift ? d_ps + (size_t)npsf * per : nullptr;
-    double* d_ft = d_ps + (size_t)npsf * per + (shift ? (size_t)2 * nstamp : 0);
-    int32_t* d_ix = psf_index ? (int32_t*)(d_ft + (size_t)nstamp * NFIT_PSF) : nullptr;
-    HIPCHK(hipMemcpyAsync(d_st, stamps, (size_t)nstamp * per * sizeof(double), hipMemcpyHostToDevice, s));
-    if (var) HIPCHK(hipMemcpyAsync(d_va, var, (size_t)nstamp * per * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_ps, psf, (size_t)npsf * per * sizeof(double), hipMemcpyHostToDevice, s));
-    if (shift) HIPCHK(hipMemcpyAsync(d_sh, shift, (size_t)2 * nstamp * sizeof(double), hipMemcpyHostToDevice, s));
-    if (psf_index)
-        HIPCHK(hipMemcpyAsync(d_ix, psf_index, (size_t)nstamp * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    {
-        ProfScope ps(c, K_FIT);
-        launch_fit_psf(s, nstamp, d_st, d_va, npsf, d_ps, d_ix, d_sh, flags, d_ft, c->f64);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(fit_out, d_ft, (size_t)nstamp * NFIT_PSF * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return MPSFR_OK;
+    const StampIn in[] = {{stamps, nstamp * kStampPix, sizeof(double)}, {var, nstamp * kStampPix, sizeof(double)},
+                          {psf, npsf * kStampPix, sizeof(double)},      {shift, (size_t)2 * nstamp, sizeof(double)},
+                          {psf_index, (size_t)nstamp, sizeof(int32_t)}};
+    return stamp_call(c, on_device, in, fit_out, (size_t)nstamp * NFIT_PSF,
+                      [&](hipStream_t s, const void* const* d, double* d_fit) {
+                          launch_fit_psf(s, nstamp, (const double*)d[0], (const double*)d[1], npsf, (const double*)d[2],
+                                         (const int32_t*)d[4], (const double*)d[3], flags, d_fit, c->f64);
+                      });
 }
 
 static_assert(METRIC_MAX == MPSFR_MAX_METRIC_RADII && METRIC_HEAD == MPSFR_NMET_HEAD, "K_STAMP_METRICS row layout");
@@ -2502,35 +2492,12 @@ int mpsfr_stamp_metrics(mpsfr_ctx* c, int nstamp, const double* stamps, const do
     for (int k = 0; k < nfrac; ++k)
         if (!(fractions[k] > 0.0 && fractions[k] < 1.0))
             return fail(MPSFR_E_INVALID, "metrics: a fraction must lie in (0, 1)");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const size_t per = (size_t)NS * NS, nout = (size_t)METRIC_HEAD + nrad + nbox + nfrac;
-    // as mpsfr_fit_stamps_elliptical: device stamps written by a device-output reconstruct of this context are
-    // complete when the kernel reads them
-    for (int k = 0; k < mpsfr_ctx::MAX_LANES; ++k)
-        if (c->lane[k].busy && c->lane[k].stream != s) HIPCHK(hipStreamWaitEvent(s, lane_end(c, c->lane[k]), 0));
-    if (on_device) {
-        ProfScope ps(c, K_FIT);
-        launch_stamp_metrics(s, nstamp, stamps, centers, nrad, radii_px, nbox, boxes_px, nfrac, fractions, out);
-        HIPCHK(hipGetLastError());
-        return MPSFR_OK;
-    }
-    int rc;
-    if ((rc = ensure(c, c->stage, (size_t)nstamp * (per + 2 + nout) * sizeof(double)))) return rc;
-    double* d_st = (double*)c->stage.p;
-    double* d_ce = d_st + (size_t)nstamp * per;
-    double* d_out = d_ce + (size_t)nstamp * 2;
-    HIPCHK(hipMemcpyAsync(d_st, stamps, (size_t)nstamp * per * sizeof(double), hipMemcpyHostToDevice, s));
-    if (centers) HIPCHK(hipMemcpyAsync(d_ce, centers, (size_t)nstamp * 2 * sizeof(double), hipMemcpyHostToDevice, s));
-    {
-        ProfScope ps(c, K_FIT);
-        launch_stamp_metrics(s, nstamp, d_st, centers ? d_ce : nullptr, nrad, radii_px, nbox, boxes_px, nfrac, fractions,
-                             d_out);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, d_out, (size_t)nstamp * nout * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return MPSFR_OK;
+    const StampIn in[] = {{stamps, nstamp * kStampPix, sizeof(double)}, {centers, (size_t)2 * nstamp, sizeof(double)}};
+    return stamp_call(c, on_device, in, out, (size_t)nstamp * (METRIC_HEAD + nrad + nbox + nfrac),
+                      [&](hipStream_t s, const void* const* d, double* d_out) {
+                          launch_stamp_metrics(s, nstamp, (const double*)d[0], (const double*)d[1], nrad, radii_px, nbox,
+                                               boxes_px, nfrac, fractions, d_out);
+                      });
 }
 
 long mpsfr_debug_fetch(mpsfr_ctx* c, const char* what, double* out, size_t capacity) {

@@ -16,6 +16,7 @@ Predecessors (each run to completion, options restored afterwards):
   P5 psf_from_psd on a PSD with a NaN pixel (refused before anything is queued)
   P6 layout shifts: more tasks per chunk, other direction counts, and the reverse
   P7 the other entry points: profile, field, band, convolve_stamps, the device elliptical fit, psd_to_psf
+  P8 the device circular fit (fit_stamps_device)
 """
 import numpy as np
 import pytest
@@ -232,6 +233,18 @@ def p7_fit_ell_device(api, ctx, name):
     torch.cuda.synchronize()
 
 
+def p8_fit_device(api, ctx, name):
+    import torch
+    dev = torch.device('cuda:0')
+    rng = np.random.default_rng(8)
+    st = torch.tensor(rng.uniform(0.0, 1.0, (5, 40, 40)), dtype=torch.float64, device=dev)
+    ft = torch.empty((5, api.NFIT), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()
+    ctx.fit_stamps_device(5, st.data_ptr(), ft.data_ptr())
+    ctx.sync()
+    torch.cuda.synchronize()
+
+
 def p7_psd_to_psf(api, ctx, name):
     psd = ctx.simul_psd(0.9, 0.6, 22.0)
     n = ctx.dim // 4
@@ -261,6 +274,7 @@ PRED = {
     'P7_convolve_stamps': p7_convolve,
     'P7_fit_ell_device': p7_fit_ell_device,
     'P7_psd_to_psf': p7_psd_to_psf,
+    'P8_fit_device': p8_fit_device,
 }
 
 CASES = ([(p, 'd512') for p in PRED]
@@ -315,6 +329,97 @@ def test_two_lanes_both_clean(api, pred):
     assert _same(want[0], _fresh(api, 'd512'))
     for k in range(2):
         assert _same(got[k], want[k]), (pred, k, _diff(got[k], want[k]))
+
+
+def test_device_fits_wait_for_the_lanes(api):
+    """include/mpsfr.h: a device-buffer fit is queued after every call queued so far on its context.  streams = 2, a
+    device-output reconstruct_device into tensors filled with NaN, and with no synchronisation in between the device
+    fit of the `psf` tensor: its rows equal, bit for bit, the host-buffer fit of the stamps read back after the sync
+    (both run the same kernel on the same doubles).  The circular fit, and the elliptical one as a control.  A race
+    cannot be made to fail reliably, so this pins the contract: it does not demonstrate that a fit without the wait
+    reads unfinished stamps."""
+    import torch
+    dev = torch.device('cuda:0')
+    ctx = _context(api, 'd512')
+    ctx.set_option('streams', 2)
+    n = SEE.size * LB.size
+    psf = torch.empty((SEE.size, LB.size, 40, 40), dtype=torch.float64, device=dev)
+    psum = torch.empty((LB.size, 40, 40), dtype=torch.float64, device=dev)
+    fit = torch.empty((SEE.size, LB.size, api.NFIT), dtype=torch.float64, device=dev)
+    for device_fit, host_fit, nfit in ((ctx.fit_stamps_device, ctx.fit_stamps, api.NFIT),
+                                       (ctx.fit_stamps_elliptical_device, ctx.fit_stamps_elliptical, api.NFIT_ELL)):
+        rows = torch.empty((n, nfit), dtype=torch.float64, device=dev)
+        psf.fill_(float('nan'))
+        torch.cuda.synchronize()
+        ctx.reconstruct_device(LB, SEE, GL, L0, THREE, H, 12.0, 1, None, psf.data_ptr(), psum.data_ptr(),
+                               fit.data_ptr())
+        device_fit(n, psf.data_ptr(), rows.data_ptr())
+        ctx.sync()
+        torch.cuda.synchronize()
+        stamps = psf.cpu().numpy().reshape(n, 40, 40)
+        assert np.all(np.isfinite(stamps))
+        want = host_fit(stamps)
+        got = rows.cpu().numpy()
+        assert np.array_equal(got, want), (nfit, int(np.sum(got != want)))
+    # the circular rows are those of the reconstruct's own fit
+    assert np.array_equal(fit.cpu().numpy().reshape(n, api.NFIT), ctx.fit_stamps(stamps))
+    ctx.close()
+
+
+# ---- the refusals of the shared grid-or-positions check, made of the C entry points directly (the Python wrappers
+# refuse the same arguments before the library is reached)
+E_INVALID = -1
+REFUSALS = ['npos_out_of_range', 'npsflin_with_positions', 'null_positions', 'non_finite', 'beyond_60_arcsec']
+ENTRIES = ['field', 'band', 'profile', 'simul_psd_profile']
+
+
+def _refused_call(api, ctx, entry, refusal):
+    """The return code of `entry` called with positions that `refusal` makes invalid (all else valid)."""
+    from muse_psfr_amd._lib import _dptr, _u8ptr
+    pos = np.array(POS, dtype=np.float64)
+    npos, npsflin = 2, 0
+    if refusal == 'npos_out_of_range':
+        pos, npos = np.zeros((26, 2)), 26
+    elif refusal == 'npsflin_with_positions':
+        npsflin = 1
+    elif refusal == 'non_finite':
+        pos[1, 0] = np.nan
+    elif refusal == 'beyond_60_arcsec':
+        pos[1, 1] = -60.5
+    ppos = None if refusal == 'null_positions' else _dptr(pos)
+    hh = np.array(H, dtype=np.float64)
+    lay = [np.array(v) for v in ([0.0, 3000.0, 12000.0], [8.0, 15.0, 25.0], [0.3, 1.2, 2.5])]
+    cn2 = np.tile([0.5, 0.3, 0.2], (SEE.size, 1))
+    rows = (SEE.size, _dptr(SEE), _dptr(GL), _dptr(L0), _u8ptr(THREE))
+    nt, nl, lib = SEE.size, LB.size, ctx.lib
+    outs = [np.empty((nt, npos, nl, 40, 40)), np.empty((npos, nl, 40, 40)), np.empty((nt, npos, nl, api.NFIT))]
+    vouts = [a.ctypes.data for a in outs]
+    if entry == 'field':
+        return lib.mpsfr_reconstruct_field(ctx._h, *rows, _dptr(hh), 12.0, npos, ppos, nl, _dptr(LB), None, None,
+                                           *vouts, 0)
+    if entry == 'band':
+        w = np.ascontiguousarray(api.band_weights(LB, BANDS), dtype=np.float64)
+        return lib.mpsfr_reconstruct_band(ctx._h, *rows, _dptr(hh), 12.0, npsflin, npos, ppos, nl, _dptr(LB),
+                                          w.shape[0], _dptr(w), None, None, *vouts, 0)
+    if entry == 'profile':
+        return lib.mpsfr_reconstruct_profile(ctx._h, *rows, 3, _dptr(lay[0]), _dptr(lay[1]), _dptr(lay[2]), _dptr(cn2),
+                                             npsflin, npos, ppos, nl, _dptr(LB), None, None, *vouts, 0)
+    psd = np.empty((npos, ctx.dim, ctx.dim))
+    return lib.mpsfr_simul_psd_profile(ctx._h, 0.9, 22.0, 0, 3, _dptr(lay[0]), _dptr(lay[1]), _dptr(lay[2]),
+                                       _dptr(cn2[:1].copy()), npsflin, npos, ppos, None, None, _dptr(psd))
+
+
+@pytest.mark.parametrize('entry,refusal', [(e, r) for e in ENTRIES for r in REFUSALS
+                                           if (e, r) != ('field', 'npsflin_with_positions')])   # (it takes no npsflin)
+def test_position_refusals_leave_the_context_usable(api, entry, refusal):
+    want = _fresh(api, 'd512')
+    ctx = _context(api, 'd512')
+    _run(api, ctx, 'd512')
+    assert _refused_call(api, ctx, entry, refusal) == E_INVALID
+    assert ctx.lib.mpsfr_last_error()
+    got = _run(api, ctx, 'd512')
+    ctx.close()
+    assert _same(got, want), (entry, refusal, _diff(got, want))
 
 
 def test_dphi0_after_overflow_matches_fresh_and_header(api):
