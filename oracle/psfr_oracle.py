@@ -515,14 +515,15 @@ def _split16(x, flush=True):
     return hi.astype(np.float32), lo.astype(np.float32)
 
 
-def psf_stamps_contraction_fp16(psd, lbda_nm, dimpsf=40, pixscale=0.2, otf_shift=15, tab_shift=9):
+def psf_stamps_contraction_fp16(psd, lbda_nm, dimpsf=40, pixscale=0.2, otf_shift=15, tab_shift=9, otf_low=True):
     """Arithmetic model of the matrix-core per-wavelength kernel (muse_psfr_amd/csrc/otf_mfma.hip):
     the stamps of psf_stamps_refshaped via the half plane v in [0, N/2], the 21 distinct samples
     per direction (E_(40-i) = conj E_i, so stamp = P +- Q), fp32 OTF elements 2^(c D + log2 tel),
     every operand split into two fp16 halves (three products, fp32 accumulation) and scaled by
     2^otf_shift / 2^tab_shift out of the fp16 subnormal range.  Test infrastructure: documents what
     precision the split buys (and what an unscaled table costs); the kernel itself is checked
-    against psf_stamps_refshaped on the GPU."""
+    against psf_stamps_refshaped on the GPU.  otf_low=False leaves the product with the low half of the OTF out
+    everywhere: what the kernel's "mid" tier does to a block, applied to the whole plane."""
     lbda_nm = np.atleast_1d(np.asarray(lbda_nm, dtype=float))
     if psd.ndim == 2:
         psd = psd[None]
@@ -550,7 +551,7 @@ def psf_stamps_contraction_fp16(psd, lbda_nm, dimpsf=40, pixscale=0.2, otf_shift
         t = []
         for part in (E.real, E.imag):                          # first contraction: Tq = OTF . E
             eh, el = _split16(part)
-            t.append((al @ eh + ah @ el + ah @ eh).astype(f32))
+            t.append(((al @ eh if otf_low else 0) + ah @ el + ah @ eh).astype(f32))
         scale = f32(2.0 ** -(lg + tab_shift))
         pq = []
         for tq, part in zip(t, (G.real, G.imag)):              # second: P = Tx^T Gx, Q = Ty^T Gy
