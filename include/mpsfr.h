@@ -133,21 +133,13 @@ const char* mpsfr_last_error(void);
  * two lanes gain 5 %: profiles/r06_experiments.md);
  * "head_fusion" (default 1: in the series form of stage A the spectra of a chunk's tip-tilt Moffat kernels are
  * computed by trailing workgroups of the patch's row kernel; 0: by a kernel of their own at the head of the call);
- * "copy_fusion" (default 0; 1: the parameter blob is fetched by workgroups of the call's first kernel, which reads
- * its tasks straight from pinned host memory -- measured, no gain); "finish_fusion" (default 0; 1: the FFT
- * convolution kernel adds up the partial tiles of the stamps the matrix-core kernel split into sweeps instead of
- * a kernel between the two -- measured, -1 %); "support_skip" (default 1: the series form of stage A neither
+ * "support_skip" (default 1: the series form of stage A neither
  * evaluates nor stores the structure function on the pieces of a line where the telescope OTF is identically zero
  * -- a fifth of the half plane).  Those pieces of the buffer ("dphi0") hold zero after such a call: the buffer is
  * zeroed when it is allocated, and a series call clears it first when an earlier call on its lane wrote there (the
  * full-size form of a call with an L0 below 7 m or with "stage_a" 0, a series call with "support_skip" 0,
  * mpsfr_psf_from_psd) -- a result never depends on the calls before it.  mpsfr_debug_fetch("d0t_clears") counts
  * those clears.
- * "stage_a_queue" (default 0; 1: the lines of stage A's series form dealt in blocks from a queue instead of equal
- * contiguous shares -- bit-identical, 13 % slower; 2: and the lines of a task on which a lower bound of the
- * structure function from the patch's row transforms puts the whole OTF line below the eps rule of "prune_eps", or
- * its mass below tier_eps / (8 (N/2+1)), at the longest wavelength, are skipped: 28 % of the lines on the bench
- * rows, stamps within 1e-7 -- and 2 % of the kernel's time: measured, lost, profiles/r06_experiments.md).
  * "cold_stagger" (default 0 = off; 1 / 2: after the GPU has drained, the second lane's first chunk
  * waits once for the first lane's column transforms / per-wavelength preparation, so that the two
  * lanes do not start in step: +3 % in a sustained run of 100-row calls, -1 % on a burst of 20;

@@ -147,42 +147,22 @@ int series_terms(bool f64);
 double series_eps0();
 inline double series_eps_max() { return 1.0 / 49.0; }
 void launch_series_coef(hipStream_t s, int N, const double* d_planes, void* d_coef, bool f64);
-// Round 6: the queue-fed form of launch_dphi_series (K_DPHI_SERIES_Q) and the lines it may skip.  queue: one int the
-// launch in front (launch_patch: PatchExtras::queue_zero) sets to zero; perm [ntd]: the order in which the lines of
-// a y are dealt (nullptr: as they come); tlmax [N/2+1] (launch_tel_linemax) + c2max (log2(e) c of the longest
-// wavelength) + thr_elem / thr_mass (log2): see SeriesSkip in stage_a2.hip; tlmax = nullptr: nothing is skipped.
-struct SeriesQueue {
-    int* queue = nullptr;
-    const int* perm = nullptr;
-    const float* tlmax = nullptr;
-    float c2max = 0.f, thr_elem = -3.0e38f, thr_mass = -3.0e38f;
-};
-// What else rides in the two launches of launch_patch (round 6; all optional):
-//  * the call's parameter blob: blob_src (pinned host) -> blob_dst (device) as extra workgroups of K_PATCH_GEN, which
-//    then reads its tasks from `tp_host` (the TaskPar array INSIDE the pinned blob); `flag`: the pinned word the
-//    first workgroup of K_PATCH_ROWS sets to `seq` -- the blob may be refilled (may be NULL);
-//  * the spectra of `khat_n` tip-tilt Moffat kernels (launch_khat) as extra workgroups of K_PATCH_ROWS.
-struct PatchExtras {
-    const void* blob_src = nullptr;
-    void* blob_dst = nullptr;
-    size_t blob_bytes = 0;
-    const TaskPar* tp_host = nullptr;
-    unsigned long long* flag = nullptr;
-    unsigned long long seq = 0;
-    int* queue_zero = nullptr;
-    int khat_n = 0;
-    const double* khat_gam = nullptr;
-    const double* khat_alp = nullptr;
-    void* khat_out = nullptr;
-    bool khat_f64 = false;
+// The spectra of `n` tip-tilt Moffat kernels (launch_khat: gam, alp -> out; f64: complex double) that ride as extra
+// workgroups of K_PATCH_ROWS in launch_patch; n = 0: none
+struct PatchKhat {
+    int n = 0;
+    const double* gam = nullptr;
+    const double* alp = nullptr;
+    void* out = nullptr;
+    bool f64 = false;
 };
 void launch_patch(hipStream_t s, int N, int ntd, int ndir, const TaskPar* d_tp, const double* d_aotab,
                   double cfit, const void* d_twk, double* d_P, void* d_T, double* d_sp, bool f64,
-                  const PatchExtras& x = PatchExtras(), const LayerMix& mix = LayerMix());
+                  const PatchKhat& kh = PatchKhat(), const LayerMix& mix = LayerMix());
 void launch_dphi_series(hipStream_t s, int N, int ntd, int ndir, const TaskPar* d_tp, const void* d_T,
                         const double* d_sp, const void* d_coef, const void* d_twk, double scale2,
                         void* d_D0t, float* d_dlin, bool f64out, int* d_zero, int ncu,
-                        const unsigned* d_support = nullptr, const SeriesQueue& qx = SeriesQueue());
+                        const unsigned* d_support = nullptr);
 // d_support [N/2+1]: per line, the pieces of series_lanes(N) columns inside the support of the telescope OTF
 // (launch_series_support from d_tel, once per context); launch_dphi_series neither evaluates nor stores the others
 void launch_series_support(hipStream_t s, int N, const void* d_tel, bool f64, unsigned* d_support);
@@ -237,18 +217,7 @@ void launch_mf_prep(hipStream_t s, int N, int ntask, int nl, int permax, const L
 void launch_otf_mfma2(hipStream_t s, int N, int ntask, int nl, int permax, int ncu, const void* d_D0t,
                       const float* d_tl2, const LamPar* d_lp, const void* d_E, const void* d_G,
                       const void* d_own, const void* d_uni, void* d_sched, void* d_part, void* d_pre,
-                      void* d_clk = nullptr, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
-                      bool finish = true);
-// finish = false: K_MF_FINISH is not launched -- the stamps of the (task, wavelength group)s that ran as several sweeps
-// stay partial tiles, which K_CONV_FFT adds up on its way (round 6: one launch less between the per-wavelength stage
-// and the convolutions).  MfFinishArgs tells it where they lie; launch_mf_finish completes `pre` for other readers.
-struct MfFinishArgs {
-    const int* gsw = nullptr;      // [ntask][ngr] sweep masks; nullptr: `pre` is complete
-    const void* part = nullptr;    // partial tiles
-    int per = 1, ngr = 1, nsw = 1;
-};
-MfFinishArgs mf2_finish_args(int N, int ntask, int nl, int permax, void* d_sched, const void* d_part);
-void launch_mf_finish(hipStream_t s, int N, int ntask, int nl, int permax, void* d_sched, const void* d_part, void* d_pre);
+                      void* d_clk = nullptr, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 void launch_gtable(hipStream_t s, int N, int nl, const LamPar* d_lp, const void* d_tw64,
                    int* d_samp_p, void* d_samp_a, void* d_G, bool f64);
 void launch_moffat_kernels(hipStream_t s, int nker, const double* d_gamma, const double* d_alpha,
@@ -275,8 +244,7 @@ void launch_khat(hipStream_t s, int nker, const double* d_gamma, const double* d
 // fin_f32 / stamps_f32: the final stamps are float (inside the pipeline) instead of double
 // f64: double stamps in and out, fp64 transforms, khat tables of complex double
 void launch_conv_fft(hipStream_t s, int ntask, int nl, const void* d_pre, const void* d_khat_tt,
-                     const void* d_khat_muse, void* d_fin, bool fin_f32, bool f64 = false,
-                     const MfFinishArgs& finish = MfFinishArgs(), int tdiv = 1);
+                     const void* d_khat_muse, void* d_fin, bool fin_f32, bool f64 = false, int tdiv = 1);
 // (sum_*: the deterministic sum of the stamps over the sum_ntask tasks of the chunk -- [sum_nl][40][40] into d_sum,
 // added to it if sum_accumulate -- as the first workgroups of the same launch; d_sum = nullptr: none)
 void launch_fit(hipStream_t s, int nstamp, const void* d_stamps, bool stamps_f32, double* d_fit,

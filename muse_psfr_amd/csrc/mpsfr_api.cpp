@@ -68,18 +68,10 @@ struct mpsfr_ctx {
     // masks): the other lane's latency-bound kernels find room beside them (VERDICT r5 #1a)
     // -1 (default): ncu / 8 while the context's other lane has work in flight, 0 for a call that runs alone
     int reserve_mf = -1, reserve_a = -1;
-    // the parameter blob and the tip-tilt kernel spectra ride in the two launches of the patch (series form of stage A)
+    // the tip-tilt kernel spectra ride in the second launch of the patch (series form of stage A)
     bool head_fusion = true;
-    // K_CONV_FFT adds up the partial tiles of the stamps K_OTF_MFMA2 split into sweeps (no K_MF_FINISH launch)
-    bool finish_fusion = false;     // (measured: -1 % with two lanes, 0 with one -- profiles/r06_experiments.md)
-    bool last_pre_partial = false;
-    int last_permax = 6;   // the last chunk's `pre` lacks those stamps (a debug fetch completes it)
     // stage A (series form) skips what lies outside the support of the telescope OTF
     bool support_skip = true;
-    // K_DPHI_SERIES_Q: stage A's lines dealt in blocks from a queue (0: equal contiguous shares); 2: + the lines
-    // stage B provably drops are skipped (SeriesSkip, stage_a2.hip)
-    int stage_a_queue = 0;
-    bool copy_fusion = false;
     double pixscale = 0.2;
     bool f64 = false;
     hipStream_t stream = nullptr;
@@ -126,7 +118,6 @@ struct mpsfr_ctx {
         int ncu = 0;                     // CUs the lane's stream may use (0: all of them)
         DevBuf C, s00, D0t, Tq, pre, fin, dmin, dblk, vkeep, dminb, order, mown, muni, msched, mpart;
         DevBuf pP, pT, psp, dlin;        // series form of stage A: patch, its row transforms, its sum; line minima
-        DevBuf squeue;                   // the block queue of K_DPHI_SERIES_Q (one int, zeroed by K_PATCH_ROWS)
         DevBuf thrf;                     // [tasks] floor of the kernel for several directions (K_PEAK_FLOOR)
         DevBuf band;                     // [tasks][nband][40][40] band stamps of a band call (K_BAND_REDUCE)
         // What D0t holds outside the part the series form of stage A writes (the pieces of a line outside the support
@@ -684,7 +675,7 @@ void mpsfr_destroy(mpsfr_ctx* c) {
         if (ln.stream) { (void)hipStreamSynchronize(ln.stream); (void)hipStreamDestroy(ln.stream); }
         if (ln.done) (void)hipEventDestroy(ln.done);
         DevBuf* lb[] = {&ln.C, &ln.s00, &ln.D0t, &ln.Tq, &ln.pre, &ln.fin, &ln.dmin, &ln.dblk, &ln.vkeep, &ln.dminb, &ln.order, &ln.mown, &ln.muni, &ln.msched, &ln.mpart,
-                         &ln.pP, &ln.pT, &ln.psp, &ln.dlin, &ln.thrf, &ln.squeue, &ln.band};
+                         &ln.pP, &ln.pT, &ln.psp, &ln.dlin, &ln.thrf, &ln.band};
         for (auto b : lb) release(*b);
     }
     for (int k = 0; k < mpsfr_ctx::NSTAGE; ++k) {
@@ -776,17 +767,10 @@ int mpsfr_set_option(mpsfr_ctx* c, const char* key, double value) {
         if (value != (int)value || value < -1.0 || value > 128.0) return fail(MPSFR_E_INVALID, "%s must be -1 (automatic) or 0..128", key);
         if (key[15] == '\0' || key[16] == 'm') c->reserve_mf = (int)value;
         if (key[15] == '\0' || key[16] == 'a') c->reserve_a = (int)value;
-    } else if (!strcmp(key, "stage_a_queue")) {
-        if (value != 0.0 && value != 1.0 && value != 2.0) return fail(MPSFR_E_INVALID, "stage_a_queue must be 0, 1 or 2");
-        c->stage_a_queue = (int)value;
     } else if (!strcmp(key, "support_skip")) {
         c->support_skip = value != 0.0;
-    } else if (!strcmp(key, "finish_fusion")) {
-        c->finish_fusion = value != 0.0;
     } else if (!strcmp(key, "head_fusion")) {
         c->head_fusion = value != 0.0;
-    } else if (!strcmp(key, "copy_fusion")) {
-        c->copy_fusion = value != 0.0;
     } else if (!strcmp(key, "param_copy")) {
         c->param_copy_kernel = value != 0.0;
     } else if (!strcmp(key, "tier_eps")) {
@@ -1428,10 +1412,7 @@ static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) 
     const size_t o_alp = al16(o_gam + gam.size() * sizeof(double));
     const size_t o_mr = al16(o_alp + alp.size() * sizeof(double));
     const size_t o_ms = al16(o_mr + (send_masks ? NAO * NAO : 0));
-    // (queue-fed stage A: per chunk, its lines in the order of how much uncorrected turbulence a task carries)
-    const bool want_perm = c->stage_a_queue != 0 && series;
-    const size_t o_perm = al16(o_ms + (send_masks ? NAO * NAO : 0));
-    const size_t o_w = al16(o_perm + (want_perm ? (size_t)ntask * ndir * sizeof(int) : 0));    // profile weights
+    const size_t o_w = al16(o_ms + (send_masks ? NAO * NAO : 0));    // profile weights
     // (a band call: its weights [nl][band_stride(nband)], zero beyond nband)
     const int bstride = band ? band_stride(nout) : 0;
     const size_t o_bw = al16(o_w + wts.size() * sizeof(double));
@@ -1493,24 +1474,6 @@ static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) 
         for (int l = 0; l < nl; ++l)
             for (int b = 0; b < bstride; ++b) bw[(size_t)l * bstride + b] = b < nout ? io.bw[(size_t)b * nl + l] : 0.0;
     }
-    if (want_perm) {
-        // K_DPHI_SERIES_Q deals the lines of a y in this order (indices relative to the chunk): tasks by descending
-        // (L0 / r0)^(5/3) x (weight of the high layer) -- the residual a ground-layer correction leaves -- so that the
-        // tasks whose lines the skip rule drops sit together (a block of waves, and at 512^2 the two tasks of a
-        // wave, then skip or compute alike).  A heuristic for speed only: no result depends on the order.
-        int* pm = reinterpret_cast<int*>(hb + o_perm);
-        std::vector<int> idx;
-        for (int t0 = 0; t0 < ntask; t0 += TC) {
-            const int tc = (ntask - t0) < TC ? (ntask - t0) : TC;
-            idx.resize(tc);
-            for (int k = 0; k < tc; ++k) idx[k] = k;
-            // (variance of the uncorrected layer ~ (L0 / r0)^(5/3) x its weight)
-            auto key = [&](int k) { return tp[t0 + k].r0m53 * tp[t0 + k].cn2_1 * std::pow(tp[t0 + k].inv_l0sq, -5.0 / 6.0); };
-            std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return key(a) > key(b); });
-            for (int k = 0; k < tc; ++k)
-                for (int d = 0; d < ndir; ++d) pm[(size_t)(t0 + k) * ndir + d] = idx[k] * ndir + d;
-        }
-    }
     if (send_masks) {
         memcpy(hb + o_mr, mask_rec, NAO * NAO);
         memcpy(hb + o_ms, mask_res, NAO * NAO);
@@ -1562,9 +1525,6 @@ static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) 
     const bool mf = !c->f64 && c->otf_mfma;
     const bool mf2 = mf && ndb == 1 && c->mf_kernel == 2;       // thin-wave kernel (otf_mfma2.hip)
     const bool r16 = !mf && otf_uses_r16(N, c->f64, nl, ndb);
-    // (the stamps K_OTF_MFMA2 leaves as partial tiles are finished by the FFT convolution kernel itself; a call
-    // that hands out the stamps before the convolutions -- psf_muse -- or skips stage B keeps K_MF_FINISH)
-    const bool fuse_finish = mf2 && c->finish_fusion && c->fft_conv && !io.stop_pre && !io.pre_in;
     if (r16 && (rc = ensure(c, c->xtab, xtab_bytes(nl)))) return rc;
     if (mf) {
         if ((rc = ensure(c, c->etab, mf_etab_bytes(N, nl)))) return rc;
@@ -1587,28 +1547,22 @@ static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) 
     // another lane has to wait for them (lane_end).  With the hipMemcpyAsync form of the copy a lean call queues
     // one: the slot's event at the end of the lane's chain.
     const bool zero = lean && c->param_copy_kernel && c->seq_host != nullptr;
-    // Round 6: in the series form of stage A the blob is fetched by extra workgroups of the call's FIRST kernel
-    // (K_PATCH_GEN, which reads its tasks straight from the pinned blob), and the spectra of the tip-tilt kernels
-    // are extra workgroups of its second (K_PATCH_ROWS): a call on one lane with its tables cached starts with the
-    // patch itself, two launches shorter ("head_fusion" = 0: K_PARAM_COPY and K_KHAT as kernels of their own).
-    const bool fuse_head = c->head_fusion && series && !staged;
-    // (not in a profile call: its patch kernel reads the weights from the device blob)
-    const bool fuse_copy = fuse_head && c->copy_fusion && c->param_copy_kernel && NL == 1 && lam_cached && ao_cached &&
-                           !ly;
-    const bool fuse_khat = fuse_head && c->fft_conv;
+    // Round 6: in the series form of stage A the spectra of the tip-tilt kernels are extra workgroups of the patch's
+    // second kernel (K_PATCH_ROWS): a launch less at the head of a call ("head_fusion" = 0: K_KHAT as a kernel of
+    // its own).
+    const bool fuse_khat = c->head_fusion && series && !staged && c->fft_conv;
     sl.seq = ++c->seq_next;
     if (zero) {
-        if (!fuse_copy) launch_param_copy(s0, sl.params.p, hb, blob, c->seq_host + (&sl - c->slot), sl.seq);
+        launch_param_copy(s0, sl.params.p, hb, blob, c->seq_host + (&sl - c->slot), sl.seq);
         sl.staged_mode = 2;
     } else {
-        if (fuse_copy) ;     // (the event that frees the blob is recorded behind the patch kernels, below)
-        else if (c->param_copy_kernel) launch_param_copy(s0, sl.params.p, hb, blob, nullptr, 0);
+        if (c->param_copy_kernel) launch_param_copy(s0, sl.params.p, hb, blob, nullptr, 0);
         else HIPCHK(hipMemcpyAsync(sl.params.p, hb, blob, hipMemcpyHostToDevice, s0));
         if (lean) {
             sl.staged_ev = sl.call_done;
             sl.staged_mode = 1;
         } else {
-            if (!fuse_copy) HIPCHK(hipEventRecord(sl.staged, s0));
+            HIPCHK(hipEventRecord(sl.staged, s0));
             sl.staged_ev = sl.staged;
             sl.staged_mode = 0;
         }
@@ -1718,18 +1672,7 @@ static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) 
     float c2min = 0.f;             // log2-scaled exponent factor of the shortest wavelength (the most negative)
     for (int l = 0; l < nl; ++l) c2min = std::fmin(c2min, (float)(lp[l].c * 1.44269504088896340736));
     const float thr_mid = (tiers && c->mf_floor) ? (float)c->mf_mid_log2 : -1.0e30f;
-    float tier_half = std::isfinite(c->tier_eps) ? (float)(0.5 * c->tier_eps) : 0.f;
-    // Lines stage A may skip (stage_a_queue = 2; the thin-wave matrix-core path, where the eps rule and the tier budget
-    // are defined): SeriesSkip in stage_a2.hip.  The mass rule takes a quarter of the floor tier's half of the budget
-    // -- tier_eps / 8 over all lines of a task -- and K_MF_PREP works with the other three quarters.
-    const bool line_skip = c->stage_a_queue == 2 && mf2 && series && prune && !staged;
-    float c2max = -3.0e38f;         // log2-scaled exponent factor of the LONGEST wavelength (the least negative)
-    for (int l = 0; l < nl; ++l) c2max = std::fmax(c2max, (float)(lp[l].c * 1.44269504088896340736));
-    float line_mass_log2 = -3.0e38f;
-    if (line_skip && tiers && c->mf_floor && tier_half > 0.f) {
-        line_mass_log2 = (float)std::log2(c->tier_eps / 8.0 / (double)H1);
-        tier_half *= 0.75f;
-    }
+    const float tier_half = std::isfinite(c->tier_eps) ? (float)(0.5 * c->tier_eps) : 0.f;
     for (int j = 0; j < NL; ++j) {
         mpsfr_ctx::Lane& ln = lane_of(j);
         if ((rc = ensure(c, ln.pre, (size_t)TB * nl * per_stamp * (c->f64 ? 8 : 4)))) return rc;
@@ -1741,7 +1684,6 @@ static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) 
             if ((rc = ensure(c, ln.pP, (size_t)TC * ndir * NAO * NAO * sizeof(double)))) return rc;
             if ((rc = ensure(c, ln.pT, (size_t)TC * ndir * H1 * kNH * 2 * sizeof(double)))) return rc;
             if ((rc = ensure(c, ln.psp, (size_t)TC * ndir * sizeof(double)))) return rc;
-            if (c->stage_a_queue && (rc = ensure(c, ln.squeue, 64))) return rc;
             if (prune && (rc = ensure(c, ln.dlin, (size_t)TC * ndir * H1 * (N / 32) * sizeof(float)))) return rc;
         } else {
             // row FFTs of the PSD: only the N/2 + 40 distinct rows are stored (K_PSD_ROWFFT)
@@ -1877,44 +1819,22 @@ static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) 
         } else if (series) {
             {
                 ProfScope ps(c, K_PATCH, ls);
-                PatchExtras px;
-                if (fuse_copy && t0 == 0) {
-                    px.blob_src = hb;
-                    px.blob_dst = sl.params.p;
-                    px.blob_bytes = blob;
-                    px.tp_host = (const TaskPar*)(hb + o_tp);
-                    px.flag = zero ? c->seq_host + (&sl - c->slot) : nullptr;
-                    px.seq = sl.seq;
-                }
-                if (c->stage_a_queue) px.queue_zero = (int*)ln.squeue.p;
+                PatchKhat kh;
                 if (fuse_khat) {
-                    px.khat_n = tc;
-                    px.khat_gam = d_gam + t0;
-                    px.khat_alp = d_alp + t0;
-                    px.khat_out = (char*)sl.ktt.p + (size_t)t0 * ksz;
-                    px.khat_f64 = c->f64;
+                    kh.n = tc;
+                    kh.gam = d_gam + t0;
+                    kh.alp = d_alp + t0;
+                    kh.out = (char*)sl.ktt.p + (size_t)t0 * ksz;
+                    kh.f64 = c->f64;
                 }
                 launch_patch(ls, N, ntd, ndir, d_tp + t0, (const double*)c->aotab.p, cfit, c->stwk.p,
-                             (double*)ln.pP.p, ln.pT.p, (double*)ln.psp.p, c->f64, px, mix_of(t0));
-                // (a call that is not lean frees its blob through an event: behind the kernels that read it)
-                if (fuse_copy && t0 == 0 && !zero && !lean) HIPCHK(hipEventRecord(sl.staged, ls));
+                             (double*)ln.pP.p, ln.pT.p, (double*)ln.psp.p, c->f64, kh, mix_of(t0));
             }
             ProfScope ps(c, K_DPHI_SERIES, ls);
-            SeriesQueue sq;
-            if (c->stage_a_queue) {
-                sq.queue = (int*)ln.squeue.p;
-                sq.perm = reinterpret_cast<const int*>(db + o_perm) + (size_t)t0 * ndir;
-                if (line_skip) {
-                    sq.tlmax = (const float*)c->tlmax.p;
-                    sq.c2max = c2max;
-                    sq.thr_elem = thr_eps;
-                    sq.thr_mass = line_mass_log2;
-                }
-            }
             launch_dphi_series(ls, N, ntd, ndir, d_tp + t0, ln.pT.p, (const double*)ln.psp.p, c->scoef.p,
                                c->stwk.p, scale2, ln.D0t.p, prune ? (float*)ln.dlin.p : nullptr, c->f64,
                                mf2 ? (int*)ln.msched.p : nullptr, persist_grid(c, ln, c->reserve_a, lanes_shared),
-                               c->support_skip ? (const unsigned*)c->ssup.p : nullptr, sq);
+                               c->support_skip ? (const unsigned*)c->ssup.p : nullptr);
         } else {
             {
                 ProfScope ps(c, K_PSD_ROWFFT, ls);
@@ -1967,7 +1887,7 @@ static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) 
             ProfScope ps(c, K_OTF_MFMA, ls, false);
             launch_otf_mfma2(ls, N, tb, nl, c->mf_permax, persist_grid(c, ln, c->reserve_mf, lanes_shared), ln.D0t.p, (const float*)c->tl2.p, d_lp, c->etab.p,
                              c->gtab.p, ln.mown.p, ln.muni.p, ln.msched.p, ln.mpart.p, ln.pre.p,
-                             c->mf_clock ? c->mfclk.p : nullptr, ps.a, ps.b, !fuse_finish);
+                             c->mf_clock ? c->mfclk.p : nullptr, ps.a, ps.b);
         } else if (mf) {
             ProfScope ps(c, K_OTF_MFMA, ls);
             if (floor_per_task)
@@ -2017,9 +1937,7 @@ static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) 
             const size_t koff = (size_t)t0 * ksz;
             if (use_fft_conv)
                 launch_conv_fft(ls, tb, nl, ln.pre.p, (const char*)sl.ktt.p + koff,
-                                c->kmuse.p, d_fin, fin_f32, c->f64,
-                                fuse_finish ? mf2_finish_args(N, tb, nl, c->mf_permax, ln.msched.p, ln.mpart.p) : MfFinishArgs(),
-                                gpp);
+                                c->kmuse.p, d_fin, fin_f32, c->f64, gpp);
             else
                 launch_conv(ls, tb, nl, ln.pre.p, (const char*)sl.ktt.p + koff,
                             c->kmuse.p, (double*)d_fin, c->f64, gpp);
@@ -2095,8 +2013,6 @@ static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) 
     c->last_nl = nl;
     c->last_mf = mf;
     c->last_mf2 = mf2;
-    c->last_pre_partial = fuse_finish;
-    c->last_permax = c->mf_permax;
     c->last_pruned = prune;
     c->last_thr_blk = thr_blk;
     c->last_floor_per_task = floor_per_task;
@@ -2521,14 +2437,7 @@ long mpsfr_debug_fetch(mpsfr_ctx* c, const char* what, double* out, size_t capac
         is_real_r = true;
     } else if (!strcmp(what, "pre")) {
         n = (size_t)c->last_chunk_tasks * c->last_gpp * c->last_nl * NS * NS;
-        mpsfr_ctx::Lane& lnp = c->lane[c->last_lane];
-        if (c->last_pre_partial) {       // the stamps the convolution kernel finished on its way: complete them here
-            if (lnp.stream) HIPCHK(hipStreamSynchronize(lnp.stream));
-            launch_mf_finish(c->stream, N, c->last_chunk_tasks * c->last_gpp, c->last_nl, c->last_permax, lnp.msched.p, lnp.mpart.p, lnp.pre.p);
-            HIPCHK(hipStreamSynchronize(c->stream));
-            c->last_pre_partial = false;
-        }
-        src = lnp.pre.p;
+        src = c->lane[c->last_lane].pre.p;
         is_real_r = true;
     } else if (!strcmp(what, "mf_work")) {
         // Work of the matrix-core per-wavelength kernel in the last chunk, recomputed on the host

@@ -712,6 +712,33 @@ k_otf_mfma2(const Mf2Args a) {
 #undef MF2_NOW
 }
 
+// One wave: the partial tiles of stamp (task, l) added in sweep order, then the epilogue of K_OTF_MFMA2
+// (write_stamp) into `out`.  part: [ntask][nl][nsw][4 NJT][64] partial tiles; `m`: the sweep mask of the stamp's
+// (task, group), more than one bit set.
+__device__ __forceinline__ void finish_stamp(const f4* part, int nsw, int m, int task, int nl, int l, int lane,
+                                             float* __restrict__ out) {
+    f4 P0[NJT], Q0[NJT], R2x[NJT], R2y[NJT];
+    bool first = true;
+    for (int sw = 0; sw < nsw; ++sw) {
+        if (!((m >> sw) & 1)) continue;
+        const f4* pt = part + (((size_t)task * nl + l) * nsw + sw) * (4 * NJT * 64) + lane;
+#pragma unroll
+        for (int jt = 0; jt < NJT; ++jt) {
+            const f4 z = {0.f, 0.f, 0.f, 0.f};
+            const bool col = part_col(jt, lane & 15);
+            const f4 p = col ? pt[(0 * NJT + jt) * 64] : z, q = col ? pt[(1 * NJT + jt) * 64] : z;
+            const f4 x = col && part_r2x(lane >> 4) ? pt[(2 * NJT + jt) * 64] : z;
+            const f4 y = col && part_r2y(lane >> 4) ? pt[(3 * NJT + jt) * 64] : z;
+            P0[jt] = first ? p : P0[jt] + p;
+            Q0[jt] = first ? q : Q0[jt] + q;
+            R2x[jt] = first ? x : R2x[jt] + x;
+            R2y[jt] = first ? y : R2y[jt] + y;
+        }
+        first = false;
+    }
+    write_stamp(P0, Q0, R2x, R2y, lane & 15, lane >> 4, out);
+}
+
 // K_MF_FINISH: the stamps of the (task, group)s with several sweeps: their partial tiles added in
 // sweep order, then the epilogue of K_OTF_MFMA2.  One wave per (task, wavelength).  (One workgroup
 // per (task, group) with a wave per wavelength measured slower: 9.3 us against 7.7.)
@@ -720,9 +747,7 @@ __global__ void __launch_bounds__(64) k_mf_finish(int N, int nl, int per, int ng
     const int l = blockIdx.x, task = blockIdx.y, lane = threadIdx.x;
     const int m = gsw[task * ngr + l / per];
     if (__builtin_popcount(m) <= 1) return;
-    MfFinish f;
-    f.gsw = gsw; f.part = part; f.per = per; f.ngr = ngr; f.nsw = (mf_nmt(N) + kT2 - 1) / kT2;
-    finish_stamp(f, m, task, nl, l, lane, pre + ((size_t)task * nl + l) * NS * NS);
+    finish_stamp(part, (mf_nmt(N) + kT2 - 1) / kT2, m, task, nl, l, lane, pre + ((size_t)task * nl + l) * NS * NS);
 }
 
 }  // namespace
@@ -788,7 +813,7 @@ void launch_mf_prep(hipStream_t s, int N, int ntask, int nl, int permax, const L
 void launch_otf_mfma2(hipStream_t s, int N, int ntask, int nl, int permax, int ncu, const void* d_D0t,
                       const float* d_tl2, const LamPar* d_lp, const void* d_E, const void* d_G,
                       const void* d_own, const void* d_uni, void* d_sched, void* d_part, void* d_pre,
-                      void* d_clk, hipEvent_t ev_start, hipEvent_t ev_stop, bool finish) {
+                      void* d_clk, hipEvent_t ev_start, hipEvent_t ev_stop) {
     Mf2Args a;
     a.N = N; a.ntask = ntask; a.nl = nl;
     mf2_groups(nl, permax, &a.per, &a.ngr);
@@ -825,29 +850,8 @@ void launch_otf_mfma2(hipStream_t s, int N, int ntask, int nl, int permax, int n
         else
             hipLaunchKernelGGL(k_otf_mfma2<3>, dim3(nwg), dim3(128 * a.per), sm, s, a);
     }
-    if (finish)
-        hipLaunchKernelGGL(k_mf_finish, dim3(nl, ntask), dim3(64), 0, s, N, nl, a.per, a.ngr, (const int*)p.gsw,
-                           (const f4*)a.part, a.pre);
-}
-
-// K_MF_FINISH on its own (launch_otf_mfma2 with finish = false leaves the stamps of the (task, group)s with several
-// sweeps as partial tiles: K_CONV_FFT finishes them on its way -- MfFinishArgs -- and a reader of `pre` itself,
-// debug fetches and psf_muse, asks for this)
-void launch_mf_finish(hipStream_t s, int N, int ntask, int nl, int permax, void* d_sched, const void* d_part, void* d_pre) {
-    int per, ngr;
-    mf2_groups(nl, permax, &per, &ngr);
-    const SchedPtrs p = sched_ptrs(d_sched, ntask, nl);
-    hipLaunchKernelGGL(k_mf_finish, dim3(nl, ntask), dim3(64), 0, s, N, nl, per, ngr, (const int*)p.gsw,
-                       (const f4*)d_part, (float*)d_pre);
-}
-
-MfFinishArgs mf2_finish_args(int N, int ntask, int nl, int permax, void* d_sched, const void* d_part) {
-    MfFinishArgs f;
-    mf2_groups(nl, permax, &f.per, &f.ngr);
-    f.gsw = sched_ptrs(d_sched, ntask, nl).gsw;
-    f.part = d_part;
-    f.nsw = (int)mf2_nsw(N);
-    return f;
+    hipLaunchKernelGGL(k_mf_finish, dim3(nl, ntask), dim3(64), 0, s, N, nl, a.per, a.ngr, (const int*)p.gsw,
+                       (const f4*)a.part, a.pre);
 }
 
 }  // namespace mpsfr

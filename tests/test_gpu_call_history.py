@@ -11,7 +11,6 @@ Predecessors (each run to completion, options restored afterwards):
   P1 a row at L0 = 5 m (the full-size form of stage A writes the whole D0t half plane)
   P2 stage_a = 0 (the full-size form by option); the other consumers of D0t and the FFT-free convolutions by
      option (otf_mfma 0, mf_kernel 1, fft_conv 0), the series form without the support skip
-  P3 stage_a_queue = 2 (the 1e30 lines of the skipped lines)
   P4 psf_from_psd on a finite PSD whose transform overflows (non-finite D in the whole plane)
   P5 psf_from_psd on a PSD with a NaN pixel (refused before anything is queued)
   P6 layout shifts: more tasks per chunk, other direction counts, and the reverse
@@ -147,14 +146,6 @@ def _with_option(key, value, default):
     return pred
 
 
-def p3_queue2(api, ctx, name):
-    ctx.set_option('stage_a_queue', 2)
-    try:
-        ctx.reconstruct(LB, SEE, GL, L0, THREE, H, npsflin=_npl(name))
-    finally:
-        ctx.set_option('stage_a_queue', 0)
-
-
 def _overflowing_psd(ctx, name):
     """A realistic PSD scaled until the sums of its transform overflow fp64: finite input, non-finite D."""
     psd = ctx.simul_psd(0.9, 0.6, 22.0, npsflin=_npl(name))
@@ -256,7 +247,6 @@ def p7_psd_to_psf(api, ctx, name):
 PRED = {
     'P1_l0_5m': p1_short_l0,
     'P2_stage_a0': p2_stage_a0,
-    'P3_stage_a_queue2': p3_queue2,
     'P2_otf_mfma0': _with_option('otf_mfma', 0, 1),
     'P2_mf_kernel1': _with_option('mf_kernel', 1, 2),
     'P2_fft_conv0': _with_option('fft_conv', 0, 1),
@@ -471,7 +461,7 @@ def _clears(ctx):
 def test_clearing_path_only_after_a_writer(api):
     """The steady path -- the bench workload: 100 rows x 35 wavelengths at 512^2, L0 in 9-29 m, device and
     asynchronous calls on both lanes -- never clears D0t; a call that wrote outside the series form's part makes the
-    next series call on its lane clear it once; the 1e30 lines of stage_a_queue = 2 lie inside that part."""
+    next series call on its lane clear it once."""
     import torch
     ps = api.grid_pixscale(512)
     see, gl, l0 = api.synthetic_rows(100)
@@ -496,7 +486,6 @@ def test_clearing_path_only_after_a_writer(api):
 
     ctx = _context(api, 'd512')
     _run(api, ctx, 'd512')
-    p3_queue2(api, ctx, 'd512')
     _run(api, ctx, 'd512')
     assert _clears(ctx) == 0
     steps = [(p4_overflow, 1), (None, 1), (p1_short_l0, 2), (p2_stage_a0, 3), (None, 3)]

@@ -594,10 +594,9 @@ def test_consecutive_calls_overlap_on_lanes_and_stay_ordered_per_buffer(api):
 def test_reserved_cus_and_head_fusion_change_no_bit(api, prec):
     """Round 6: where the work of a call is queued changes no bit of its results -- the persistent grids of
     K_OTF_MFMA2 / K_DPHI_SERIES with R CUs left free ("persist_reserve": 0, 32, 100, automatic), the kernel spectra of
-    the tip-tilt kernels as workgroups of K_PATCH_ROWS or as a kernel of their own ("head_fusion"), the parameter
-    blob fetched by workgroups of K_PATCH_GEN ("copy_fusion"), the stamps K_OTF_MFMA2 split into sweeps finished by
-    K_CONV_FFT or by K_MF_FINISH ("finish_fusion") -- for host-output calls (one chunk, several chunks on
-    two lanes) and for lean device-output calls queued back to back (series form of stage A: 512^2)."""
+    the tip-tilt kernels as workgroups of K_PATCH_ROWS or as a kernel of their own ("head_fusion") -- for host-output
+    calls (one chunk, several chunks on two lanes) and for lean device-output calls queued back to back (series form
+    of stage A: 512^2)."""
     import torch
     from muse_psfr_amd import NFIT
     n = 37
@@ -610,10 +609,6 @@ def test_reserved_cus_and_head_fusion_change_no_bit(api, prec):
                 ('reserve32', {'persist_reserve': 32, 'head_fusion': 0}),
                 ('reserve100_fused', {'persist_reserve': 100}),
                 ('defaults', {}),
-                ('copy_fused', {'copy_fusion': 1}),
-                ('finish_fused', {'finish_fusion': 1}),           # K_CONV_FFT finishes the split stamps itself
-                ('stage_a_queue', {'stage_a_queue': 1}),          # K_DPHI_SERIES_Q: the same lines dealt from a queue
-                ('copy_fused_chunks', {'copy_fusion': 1, 'chunk_tasks': 10, 'streams': 2}),
                 ('fused_chunks', {'chunk_tasks': 10, 'streams': 2}))
     ref = None
     for key, opts in variants:
@@ -646,44 +641,21 @@ def test_reserved_cus_and_head_fusion_change_no_bit(api, prec):
         api.Context(dim=512, pixscale=ps).set_option('persist_reserve', 300)
 
 
-def test_lines_stage_b_drops_may_be_skipped_in_stage_a(api):
-    """`stage_a_queue` = 2 (measured, not the default: profiles/r06_experiments.md): K_DPHI_SERIES_Q skips the lines of a
-    task on which a lower bound of the structure function from the patch's row transforms alone -- D(., y) >=
-    scale2 (sum P - sum_su |T[y][su]|) -- puts every element of the OTF below the eps rule of the pruning, or the
-    line's whole mass below its share of the tier budget, at the longest wavelength.  On rows with poor seeing and a
-    weak ground layer some lines go, the stamps stay within 1e-6 of their peak and the fits within 1e-6, the lines
-    that are computed are bit-identical, and what was skipped really is where the OTF is negligible: the full
-    structure function there is above the bound the rule needs."""
-    n, dim = 24, 1280
-    see = np.linspace(0.6, 1.6, n)
-    gl = np.linspace(0.9, 0.35, n)
-    l0 = np.linspace(12.0, 28.0, n)
-    lb = np.linspace(490.0, 930.0, 5)
-    res = {}
-    for mode in (0, 2):
-        ctx = api.Context(dim=dim, pixscale=0.2)
-        ctx.set_option('stage_a_queue', mode)
-        r = ctx.reconstruct(lb, see, gl, l0, None, H)
-        d = ctx.debug_fetch('dphi0', (n, 1, dim // 2 + 1, dim))[:, 0]
-        tel = ctx.debug_fetch('tel', (dim // 2 + 1, dim))
-        ctx.close()
-        res[mode] = (r, d)
-    (ra, da), (rb, db) = res[0], res[2]
-    inside = tel > 0
-    skipped = ((db >= 1e29) | ~inside[None]).all(axis=2) & inside.any(axis=1)[None]       # (task, line)
-    assert 0.02 < skipped.mean() < 0.9, skipped.mean()
-    assert not skipped[:, :4].any()
-    kept = ~skipped
-    assert np.array_equal(da[kept], db[kept])
-    # every element of a skipped line: 2^(c' D) tel below 2^-29 of OTF[0][0] = 1 even at 930 nm
-    c2 = -0.5 * (2 * np.pi / 930.0) ** 2 * np.log2(np.e)
-    with np.errstate(divide='ignore'):
-        e = c2 * da + np.log2(np.where(inside, tel, 0.0))[None]
-    assert e[skipped].max() < -29.0, e[skipped].max()
-    peak = ra['psf'].max(axis=(2, 3), keepdims=True)
-    assert (np.abs(rb['psf'] - ra['psf']) / peak).max() < 1e-6
-    well = ra['fit'][..., 14] == 0
-    assert np.abs(rb['fit'][..., 4:6] - ra['fit'][..., 4:6])[well].max() < 1e-6
+def test_removed_round6_options_are_unknown_keys(api):
+    """The three option keys of the round-6 experiments that were taken out ("copy_fusion", "finish_fusion",
+    "stage_a_queue") are refused exactly as any unknown key is, and the context goes on working."""
+    ctx = api.Context(dim=128, pixscale=api.grid_pixscale(128))
+    with pytest.raises(api.MpsfrError) as unknown:
+        ctx.set_option('no_such_option', 1)
+    for key in ('copy_fusion', 'finish_fusion', 'stage_a_queue'):
+        for value in (0, 1):
+            with pytest.raises(api.MpsfrError) as e:
+                ctx.set_option(key, value)
+            assert e.value.code == unknown.value.code and "unknown option '%s'" % key in str(e.value), key
+    r = ctx.reconstruct([500.0, 900.0], [1.0, 0.7], [0.7, 0.5], [25.0, 15.0], [0, 1], H)
+    ctx.close()
+    assert r['psf'].shape == (2, 2, 40, 40) and np.isfinite(r['psf']).all() and np.isfinite(r['fit']).all()
+    np.testing.assert_allclose(r['psf_sum'], r['psf'].sum(axis=0), rtol=1e-13)
 
 
 def test_blocks_any_wavelength_keeps_and_the_telescope_support(api):

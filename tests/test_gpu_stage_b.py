@@ -76,8 +76,8 @@ def _compare(label, variant, mode, dim, lb, d0, pre, check=True):
     against the mode's bound, the worst recorded."""
     ps = grid_pixscale(dim)
     assert np.all(np.isfinite(d0)) and np.all(np.isfinite(pre))
-    # (no line carries the 1e30 that stage A stores for a line it skips under stage_a_queue = 2, off by default: the
-    # plane is the structure function throughout, and nothing stage A gives away is in the figure)
+    # (stage A skips no line and stores no placeholder value: the plane is the structure function throughout, and
+    # nothing stage A gives away is in the figure)
     assert d0.max() < 1e29, (label, d0.max())
     assert d0.min() >= -1e-6 * d0.max(), (label, d0.min(), d0.max())      # the kernel's clamp of D at 0 cannot matter
     err = np.empty(pre.shape[:2])
