@@ -436,6 +436,55 @@ int mpsfr_fit_stamps_psf(mpsfr_ctx* ctx, int nstamp, const double* stamps, const
                          const double* psf, const int32_t* psf_index, const double* shift, int flags,
                          double* fit_out, int on_device);
 
+/* PSF-model fit of blended stars: all sources of a group (2 to MPSFR_MAX_GROUP stars that share the pixels of one
+ * stamp) are fitted at once with one model stamp -- DAOPHOT's NSTAR for the reconstructed PSF.  Per stamp d with optional
+ * variance var, over the used pixels, the minimum of
+ *     sum (m - d)^2 / var,   m(p, q) = sum_{k < nsrc} F_k P~(p - dp_k, q - dq_k) + b
+ * with P~ the Keys resampling of the stamp's model P exactly as mpsfr_fit_stamps_psf defines it (zero outside its
+ * pixels).  All sources of a stamp share the model stamp psf[psf_index[stamp]] (one to one when psf_index is NULL).  The
+ * rule for the used pixels, the weights and the power-of-two normalisations are those of mpsfr_fit_stamps_psf.
+ * nsrc: 2 .. MPSFR_MAX_GROUP, the same for every stamp of the call (groups of several sizes: one call per size; one
+ * source is mpsfr_fit_stamps_psf and nsrc = 1 is refused).  shift: [nstamp][nsrc][2], always required: (dp_k, dq_k), the
+ * displacement of each source from the model stamp's own position, in pixels.  Three modes:
+ *   free    (neither shift flag)       variables F_k, dp_k, dq_k, [b]; npar = 3 nsrc + [1] <= 13; shift: start values
+ *   common  (MPSFR_FIT_COMMON_SHIFT)   variables F_k, Dp, Dq, [b]; npar = nsrc + 2 + [1]; dp_k = shift_k,p + Dp (and q):
+ *                                      the relative positions are the caller's (a catalogue); D starts at 0
+ *   fixed   (MPSFR_FIT_FIXED_SHIFT)    variables F_k, [b]: linear, solved in closed form (iterations = 1)
+ * b only under MPSFR_FIT_BACKGROUND.  Domain: every source keeps |dp_k|, |dq_k| <= MPSFR_FIT_PSF_MAX_SHIFT throughout
+ * (in common mode after D is added): a step that takes any source outside is refused, and a fit that ends resting on
+ * the bound has status 1.  A neighbour farther than 8 pixels from the stamp centre cannot be a member of the group.
+ * The F_k and b start from the closed-form weighted linear solve at the given positions; the iteration is that of
+ * mpsfr_fit_stamps_psf, the step size measured relative to max_k |F_k| for every F_k and b and in pixels for positions.
+ * fit_out: [nstamp][MPSFR_NFIT_GROUP]:
+ *   0 back  1 err_back  2 chi2 (the weighted sum)  3 iterations  4 status  5 n_used  6 nsrc  7 zero
+ *   8 + 8k, source k:  0 F  1 dp  2 dq  3 err_F  4 err_dp  5 err_dq  6 flux = F sum(P)  7 err_flux = err_F |sum(P)|
+ *   40 .. 45: the correlation coefficients of (F_i, F_j) from the covariance, for (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)
+ *   -- how blended two fluxes are; pairs that do not exist are 0.  46, 47 zero.
+ * Sources >= nsrc are zeros; fixed positions are echoed with error 0; in common mode every source's err_dp / err_dq is
+ * the error of Dp / Dq.  Errors: sqrt(diag((J^T W J)^-1) chi2 / dof), dof = n_used - npar.
+ * Status as mpsfr_fit_stamps_psf (0 / 1 / 2; MPSFR_FIT_ILL_CONDITIONED is never set).  Status 2 also covers
+ * n_used < npar + 1, a singular start solve (two sources at the same position) and, in the device form, an index out
+ * of range or a given position that is not finite or outside the domain.  A status-2 row is zeros except status,
+ * n_used and nsrc.  A row whose status & 3 is 0 holds finite numbers only.
+ * A stamp's row depends on that stamp, its model and its positions only, bit for bit: not on the batch or on the
+ * stamp's place in it.  A constant factor on var changes no parameter and no error.  2^k on the data with 4^k on var
+ * scales every F, back, flux and their errors by 2^k exactly and changes no other bit; 2^k on the model scales every F
+ * (and err_F) by 2^-k exactly.  Values of unused pixels never matter.  Permuting the sources of a group permutes the
+ * result to rounding only, not bit for bit: the order of the sums changes.
+ * on_device: 0 synchronous on host pointers; 1: stamps, var, psf, psf_index, shift and fit_out are all device pointers
+ * and the call is queued on the context stream behind earlier calls (e.g. a device-output mpsfr_reconstruct_field,
+ * whose stamps are then the model); timed under the fit's profiling id.
+ * MPSFR_E_INVALID before anything is queued, with fit_out untouched: nstamp < 1, npsf < 1 or nsrc outside 2 .. 4; NULL
+ * stamps, psf, shift or fit_out; both shift flags, MPSFR_FIT_ELLIPTICAL or an unknown bit; psf_index NULL with
+ * npsf != nstamp; and, for host pointers, an index out of range or a position that is not finite or outside the
+ * domain. */
+#define MPSFR_MAX_GROUP 4            /* sources per stamp */
+#define MPSFR_NFIT_GROUP 48          /* doubles per fitted group */
+#define MPSFR_FIT_COMMON_SHIFT 8     /* beside MPSFR_FIT_BACKGROUND (1), MPSFR_FIT_FIXED_SHIFT (4) */
+int mpsfr_fit_groups_psf(mpsfr_ctx* ctx, int nstamp, int nsrc, const double* stamps, const double* var, int npsf,
+                         const double* psf, const int32_t* psf_index, const double* shift, int flags,
+                         double* fit_out, int on_device);
+
 /* PSF energy metrics of caller-provided stamps: encircled and ensquared energy with exact pixel overlap, and the radii
  * that hold given fractions of the flux -- the non-parametric description of a core + halo PSF, beside the Moffat fits.
  * Pixel (p, q) is the unit square centred on (p, q), in the pixel coordinates of the fits (p0, q0).  Per stamp:

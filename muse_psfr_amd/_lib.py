@@ -19,6 +19,10 @@ FIT_ELLIPTICAL = 2
 NFIT_PSF = 16                # rows of the PSF-model fit (MPSFR_NFIT_PSF)
 FIT_FIXED_SHIFT = 4          # flag of mpsfr_fit_stamps_psf (MPSFR_FIT_FIXED_SHIFT), beside FIT_BACKGROUND
 FIT_PSF_MAX_SHIFT = 8.0      # |dp|, |dq| bound in pixels (MPSFR_FIT_PSF_MAX_SHIFT)
+NFIT_GROUP = 48              # rows of the PSF-model fit of blended groups (MPSFR_NFIT_GROUP)
+MAX_GROUP = 4                # sources per stamp (MPSFR_MAX_GROUP)
+FIT_COMMON_SHIFT = 8         # flag of mpsfr_fit_groups_psf (MPSFR_FIT_COMMON_SHIFT), beside FIT_BACKGROUND, FIT_FIXED_SHIFT
+GROUP_MODES = ('free', 'common', 'fixed')
 DIM_AO = 80
 PREC_MIXED, PREC_F64 = 0, 1
 E_GRID = -3
@@ -100,6 +104,8 @@ def load():
     lib.mpsfr_fit_stamps_observed.restype = C.c_int
     lib.mpsfr_fit_stamps_psf.argtypes = [p, C.c_int, p, p, C.c_int, p, p, p, C.c_int, p, C.c_int]
     lib.mpsfr_fit_stamps_psf.restype = C.c_int
+    lib.mpsfr_fit_groups_psf.argtypes = [p, C.c_int, C.c_int, p, p, C.c_int, p, p, p, C.c_int, p, C.c_int]
+    lib.mpsfr_fit_groups_psf.restype = C.c_int
     lib.mpsfr_stamp_metrics.argtypes = [p, C.c_int, p, p, C.c_int, dp, C.c_int, dp, C.c_int, dp, p, C.c_int]
     lib.mpsfr_stamp_metrics.restype = C.c_int
     lib.mpsfr_simul_psd.argtypes = [p, C.c_double, C.c_double, C.c_double, C.c_int, dp, C.c_double, C.c_int, u8p, u8p, dp]
@@ -149,7 +155,7 @@ def load():
 
 
 EXPORTS = ['mpsfr_create', 'mpsfr_destroy', 'mpsfr_last_error', 'mpsfr_set_option',
-           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_fit_stamps_psf', 'mpsfr_stamp_metrics', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
+           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_fit_stamps_psf', 'mpsfr_fit_groups_psf', 'mpsfr_stamp_metrics', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
            'mpsfr_psd_to_psf',
            'mpsfr_convolve_stamps', 'mpsfr_fit_rows', 'mpsfr_sync', 'mpsfr_last_ticket', 'mpsfr_wait', 'mpsfr_abandon',
            'mpsfr_stream', 'mpsfr_stream_wait', 'mpsfr_wait_event',
@@ -735,6 +741,11 @@ class Context:
         _check(self.lib.mpsfr_fit_stamps_psf(self._h, int(nstamp), p(stamps), p(var), int(npsf), p(psf), p(index),
                                              p(shift), flags, p(fit), on_device))
 
+    def _call_fit_groups(self, nstamp, nsrc, stamps, var, npsf, psf, index, shift, flags, fit, on_device):
+        p = _devptr if on_device else _vptr
+        _check(self.lib.mpsfr_fit_groups_psf(self._h, int(nstamp), int(nsrc), p(stamps), p(var), int(npsf), p(psf),
+                                             p(index), p(shift), flags, p(fit), on_device))
+
     def _call_metrics(self, nstamp, stamps, centers, rad, box, frac, out, on_device):
         p = _devptr if on_device else _vptr
         _check(self.lib.mpsfr_stamp_metrics(self._h, int(nstamp), p(stamps), p(centers), rad.size, _dptr(rad),
@@ -821,6 +832,39 @@ class Context:
         if fixed_shift and not shift_ptr:
             raise ValueError('fixed_shift needs shift_ptr')
         self._call_fit_psf(nstamp, stamps_ptr, var_ptr, npsf, psf_ptr, psf_index_ptr, shift_ptr, flags, fit_ptr, 1)
+
+    def fit_groups_psf(self, stamps, psf, shift, var=None, psf_index=None, background=True, mode='free'):
+        """PSF-model fit of blended stars (mpsfr_fit_groups_psf): every stamp (..., dimpsf, dimpsf) holds the same number
+        K = 2 .. MAX_GROUP of sources of its model stamp, at the positions `shift` (n, K, 2) in pixels from the model
+        stamp's own position; all K are fitted at once.  mode: 'free' (F_k, dp_k, dq_k; `shift` holds the start values),
+        'common' (F_k and one offset of all positions; `shift` holds catalogue positions) or 'fixed' (F_k only, closed
+        form); with `background` a constant b.  `var`, the mask and `psf_index` as fit_stamps_psf.  (n, NFIT_GROUP)
+        rows: 0 back, 1 err_back, 2 chi2, 3 iterations, 4 status, 5 n_used, 6 K; source k at 8 + 8k: F, dp, dq, err_F,
+        err_dp, err_dq, flux = F sum(psf), err_flux; 40 .. 45 the correlation coefficients of (F_i, F_j) for (0,1),
+        (0,2), (0,3), (1,2), (1,3), (2,3)."""
+        st, va = observed_stamps(stamps, var, self.dimpsf)
+        ps, ix, sh, flags = group_fit_arguments(st.shape[0], psf, psf_index, shift, background, mode, self.dimpsf)
+        out = np.empty((st.shape[0], NFIT_GROUP))
+        self._call_fit_groups(st.shape[0], sh.shape[1], st, va, ps.shape[0], ps, ix, sh, flags, out, 0)
+        return out
+
+    def fit_groups_psf_device(self, nstamp, nsrc, stamps_ptr, npsf, psf_ptr, shift_ptr, fit_ptr, var_ptr=None,
+                              psf_index_ptr=None, background=True, mode='free'):
+        """Device-buffer form (asynchronous, on_device = 1): `stamps_ptr`, `var_ptr` ([nstamp][dimpsf][dimpsf] float64;
+        var_ptr None: unit weights), `psf_ptr` ([npsf][dimpsf][dimpsf] float64), `psf_index_ptr` ([nstamp] int32, or None
+        with npsf == nstamp), `shift_ptr` ([nstamp][nsrc][2] float64) and `fit_ptr` ([nstamp][NFIT_GROUP] float64) are
+        raw device pointers (int) on this context's GPU; the call is queued on the context stream, after any
+        device-output reconstruct of this context.  An index out of range or a position that is not finite or outside
+        the domain makes that row status 2."""
+        _positive_int('nstamp', nstamp)
+        _positive_int('npsf', npsf)
+        _group_size(nsrc)
+        _device_pointers(stamps_ptr=stamps_ptr, psf_ptr=psf_ptr, shift_ptr=shift_ptr, fit_ptr=fit_ptr)
+        if not psf_index_ptr and npsf != nstamp:
+            raise ValueError('without psf_index_ptr, npsf must equal nstamp')
+        flags = group_fit_flags(background, mode)
+        self._call_fit_groups(nstamp, nsrc, stamps_ptr, var_ptr, npsf, psf_ptr, psf_index_ptr, shift_ptr, flags,
+                              fit_ptr, 1)
 
     def stamp_metrics(self, stamps, radii_px, boxes_px, fractions, centers=None):
         """PSF energy metrics (mpsfr_stamp_metrics) of stamps (..., dimpsf, dimpsf): (n, NMET_HEAD + nrad + nbox +
@@ -967,6 +1011,41 @@ def psf_fit_arguments(nstamp, psf, psf_index, shift, background, fixed_shift, di
             raise ValueError('shift must be finite and within %g pixels' % FIT_PSF_MAX_SHIFT)
         sh = np.ascontiguousarray(sh).reshape(nstamp, 2)
     return ps, ix, sh, flags
+
+
+def _group_size(nsrc):
+    if isinstance(nsrc, bool) or not isinstance(nsrc, (int, np.integer)) or not 2 <= nsrc <= MAX_GROUP:
+        raise ValueError('a group has 2 to %d sources (one source is fit_stamps_psf), not %r' % (MAX_GROUP, nsrc))
+
+
+def group_fit_flags(background, mode):
+    """The flags of mpsfr_fit_groups_psf from a boolean and the mode 'free' | 'common' | 'fixed' (ValueError for
+    anything else)."""
+    if not isinstance(background, (bool, np.bool_)):
+        raise ValueError('background must be True or False')
+    if not isinstance(mode, str) or mode not in GROUP_MODES:
+        raise ValueError("mode must be 'free', 'common' or 'fixed'")
+    return (FIT_BACKGROUND if background else 0) | {'free': 0, 'common': FIT_COMMON_SHIFT, 'fixed': FIT_FIXED_SHIFT}[mode]
+
+
+def group_fit_arguments(nstamp, psf, psf_index, shift, background, mode, dimpsf=40):
+    """(psf, psf_index, shift, flags) of a PSF-model fit of `nstamp` blended groups, validated as mpsfr_fit_groups_psf
+    validates host arguments (ValueError): psf and psf_index as psf_fit_arguments; shift required, (nstamp, K, 2) with
+    K = 2 .. MAX_GROUP, finite values within FIT_PSF_MAX_SHIFT pixels."""
+    flags = group_fit_flags(background, mode)
+    ps, ix, _, _ = psf_fit_arguments(nstamp, psf, psf_index, None, True, False, dimpsf)
+    if shift is None:
+        raise ValueError('a group fit needs the positions of its sources (shift)')
+    try:
+        sh = np.asarray(shift, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('shift must be a numeric array') from None
+    if sh.ndim < 2 or sh.shape[-1] != 2 or sh.size != nstamp * sh.shape[-2] * 2:
+        raise ValueError('shift must have the shape (%d, K, 2)' % nstamp)
+    _group_size(int(sh.shape[-2]))
+    if not np.all(np.abs(sh) <= FIT_PSF_MAX_SHIFT):           # (NaN fails)
+        raise ValueError('the positions must be finite and within %g pixels' % FIT_PSF_MAX_SHIFT)
+    return ps, ix, np.ascontiguousarray(sh).reshape(nstamp, sh.shape[-2], 2), flags
 
 
 def metric_stamps(stamps, dimpsf=40):

@@ -16,6 +16,7 @@ constexpr int kNH = NAO / 2 + 1;   // values per line of the patch row transform
 constexpr int NFIT = 16;
 constexpr int NFIT_ELL = 24;     // elliptical fit (fit_ell.hip)
 constexpr int NFIT_PSF = 16;     // PSF-model fit (fit_psf.hip)
+constexpr int NFIT_GROUP = 48;   // PSF-model fit of a blended group (fit_group.hip)
 constexpr int METRIC_MAX = 16;   // MPSFR_MAX_METRIC_RADII: radii, boxes, fractions of one metrics call (metrics.hip)
 constexpr int METRIC_HEAD = 8;   // MPSFR_NMET_HEAD
 constexpr int KHAT = 33 * 64;  // complex entries of one kernel spectrum (k_khat)
@@ -263,6 +264,12 @@ void launch_fit_obs(hipStream_t s, int nstamp, const double* d_stamps, const dou
 void launch_fit_psf(hipStream_t s, int nstamp, const double* d_stamps, const double* d_var, int npsf,
                     const double* d_psf, const int32_t* d_index, const double* d_shift, int flags, double* d_fit,
                     bool f64);
+// PSF-model fit of blended groups (fit_group.hip, fit_group_f64.hip): stamp d_stamps[k] holds nsrc (2 .. 4) sources of
+// the model stamp d_psf[d_index[k]] at the positions d_shift[k] ([nstamp][nsrc][2], required) -> [nstamp][NFIT_GROUP];
+// flags: MPSFR_FIT_BACKGROUND | one of MPSFR_FIT_FIXED_SHIFT, MPSFR_FIT_COMMON_SHIFT; grid(nstamp), block(64)
+void launch_fit_group(hipStream_t s, int nstamp, int nsrc, const double* d_stamps, const double* d_var, int npsf,
+                      const double* d_psf, const int32_t* d_index, const double* d_shift, int flags, double* d_fit,
+                      bool f64);
 // PSF energy metrics (metrics.hip): [nstamp][40][40] double stamps -> [nstamp][METRIC_HEAD + nrad + nbox + nfrac];
 // d_centers [nstamp][2] (p, q) or nullptr (the centroid); radii / boxes / fractions: host arrays (they travel as kernel
 // arguments), counts 0..METRIC_MAX

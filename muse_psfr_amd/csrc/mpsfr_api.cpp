@@ -2388,6 +2388,45 @@ int mpsfr_fit_stamps_psf(mpsfr_ctx* c, int nstamp, const double* stamps, const d
                       });
 }
 
+static_assert(NFIT_GROUP == MPSFR_NFIT_GROUP && MPSFR_NFIT_GROUP == 8 + 8 * MPSFR_MAX_GROUP + 8, "K_FIT_GROUP row layout");
+
+int mpsfr_fit_groups_psf(mpsfr_ctx* c, int nstamp, int nsrc, const double* stamps, const double* var, int npsf,
+                         const double* psf, const int32_t* psf_index, const double* shift, int flags,
+                         double* fit_out, int on_device) {
+    if (!c || !stamps || !psf || !shift || !fit_out || nstamp < 1 || npsf < 1)
+        return fail(MPSFR_E_INVALID, "fit_groups_psf: bad argument (stamps, psf, shift and fit_out are required)");
+    if (nsrc == 1)
+        return fail(MPSFR_E_INVALID, "fit_groups_psf: a group has 2 to %d sources; one source is mpsfr_fit_stamps_psf",
+                    MPSFR_MAX_GROUP);
+    if (nsrc < 2 || nsrc > MPSFR_MAX_GROUP)
+        return fail(MPSFR_E_INVALID, "fit_groups_psf: nsrc=%d outside 2..%d", nsrc, MPSFR_MAX_GROUP);
+    if (flags & ~(MPSFR_FIT_BACKGROUND | MPSFR_FIT_FIXED_SHIFT | MPSFR_FIT_COMMON_SHIFT))
+        return fail(MPSFR_E_INVALID, "fit_groups_psf: unknown flag bits (the elliptical bit has no meaning here)");
+    if ((flags & MPSFR_FIT_FIXED_SHIFT) && (flags & MPSFR_FIT_COMMON_SHIFT))
+        return fail(MPSFR_E_INVALID, "fit_groups_psf: MPSFR_FIT_FIXED_SHIFT and MPSFR_FIT_COMMON_SHIFT exclude each other");
+    if (!psf_index && npsf != nstamp)
+        return fail(MPSFR_E_INVALID, "fit_groups_psf: without psf_index, npsf must equal nstamp");
+    const size_t npos = (size_t)2 * nsrc * nstamp;
+    if (!on_device) {
+        if (psf_index)
+            for (int k = 0; k < nstamp; ++k)
+                if (psf_index[k] < 0 || psf_index[k] >= npsf)
+                    return fail(MPSFR_E_INVALID, "fit_groups_psf: a psf_index outside 0..npsf-1");
+        for (size_t k = 0; k < npos; ++k)
+            if (!(std::fabs(shift[k]) <= MPSFR_FIT_PSF_MAX_SHIFT))
+                return fail(MPSFR_E_INVALID, "fit_groups_psf: a position that is not finite or beyond 8 pixels");
+    }
+    const StampIn in[] = {{stamps, nstamp * kStampPix, sizeof(double)}, {var, nstamp * kStampPix, sizeof(double)},
+                          {psf, npsf * kStampPix, sizeof(double)},      {shift, npos, sizeof(double)},
+                          {psf_index, (size_t)nstamp, sizeof(int32_t)}};
+    return stamp_call(c, on_device, in, fit_out, (size_t)nstamp * NFIT_GROUP,
+                      [&](hipStream_t s, const void* const* d, double* d_fit) {
+                          launch_fit_group(s, nstamp, nsrc, (const double*)d[0], (const double*)d[1], npsf,
+                                           (const double*)d[2], (const int32_t*)d[4], (const double*)d[3], flags, d_fit,
+                                           c->f64);
+                      });
+}
+
 static_assert(METRIC_MAX == MPSFR_MAX_METRIC_RADII && METRIC_HEAD == MPSFR_NMET_HEAD, "K_STAMP_METRICS row layout");
 
 int mpsfr_stamp_metrics(mpsfr_ctx* c, int nstamp, const double* stamps, const double* centers, int nrad,

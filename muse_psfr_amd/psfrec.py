@@ -473,6 +473,114 @@ def fit_stars_with_psf(stars, psf, *, var=None, psf_index=None, shift=None, fit_
     return _make_table(_fit_columns_psf(fit, pixscale))
 
 
+_FIT_COLS_GROUP = ('group', 'source', 'scale', 'shift', 'flux', 'err_scale', 'err_shift', 'err_flux', 'back', 'err_back',
+                   'chi2', 'npix', 'status', 'max_corr')
+_GROUP_PAIRS = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))      # fit_out[40 .. 45] of mpsfr_fit_groups_psf
+
+
+def _group_positions(positions, n, pixscale):
+    """The `positions` argument of fit_star_groups_with_psf -> a list of n arrays (n_k, 2) in pixels, n_k = 1 ..
+    MAX_GROUP, finite and inside the domain of the fit (ValueError)."""
+    try:
+        arr = np.asarray(positions, dtype=float)
+    except (TypeError, ValueError):
+        arr = None
+    if arr is not None and arr.ndim == 3:
+        if arr.shape[0] != n or arr.shape[2] != 2:
+            raise ValueError('positions must have the shape (%d, K, 2)' % n)
+        nan = np.isnan(arr).all(axis=2)
+        groups = [g[~m] for g, m in zip(arr, nan)]
+    else:
+        try:
+            groups = [np.asarray(g, dtype=float).reshape(-1, 2) for g in positions]
+        except (TypeError, ValueError):
+            raise ValueError('positions must be an (n, K, 2) array or one (n_k, 2) array per stamp') from None
+        if len(groups) != n:
+            raise ValueError('positions must hold one entry per stamp (%d), got %d' % (n, len(groups)))
+    out = []
+    for g in groups:
+        if not 1 <= len(g) <= _lib.MAX_GROUP:
+            raise ValueError('a stamp holds 1 to %d sources, not %d' % (_lib.MAX_GROUP, len(g)))
+        px = g / pixscale
+        if not np.all(np.abs(px) <= _lib.FIT_PSF_MAX_SHIFT):          # (NaN fails)
+            raise ValueError('the positions must be finite and within %g pixels of the stamp centre'
+                             % _lib.FIT_PSF_MAX_SHIFT)
+        out.append(px)
+    return out
+
+
+def fit_star_groups_with_psf(stars, psf, positions, *, var=None, psf_index=None, fit_back=True, mode='free',
+                             pixscale=0.2, precision='mixed', device=0):
+    """PSF-fitting photometry of blended stars: every stamp of `stars` holds one to four stars of its model stamp `psf`
+    (..., 40, 40), which are fitted at once -- each in a flux scale, the positions according to `mode`, and (fit_back)
+    one constant background per stamp.
+
+    positions: where the stars of each stamp are, (row, column) in arcsec from the model stamp's own position: a
+    sequence with one (n_k, 2) array per stamp, or an (n, K, 2) array whose all-NaN rows mean "no such source".
+    mode: 'free' (every position is fitted from the given start), 'common' (the relative positions are held and one
+    offset of the whole group is fitted: catalogue positions) or 'fixed' (positions held; the problem is linear).
+    stars / var / psf_index: as fit_stars_with_psf.  The stamps are bucketed by their number of stars and fitted with
+    one library call per size; a single star goes to the PSF-model fit of fit_stars_with_psf ('common' is then a
+    free shift).  No star may be farther than 8 pixels from the stamp centre.
+
+    Returns a table with one row per star, in input order: group (the stamp), source (its number in the stamp), scale
+    (F), shift (2, arcsec), flux = F sum(psf), err_scale, err_shift (2, arcsec), err_flux, then the group's back,
+    err_back, chi2, npix and status (as fit_stars_with_psf) repeated on each of its rows, and max_corr: the largest
+    |correlation coefficient| of this star's F with that of another star of the stamp (0 for a single star) -- how
+    blended its flux is."""
+    if not isinstance(fit_back, (bool, np.bool_)):
+        raise ValueError('fit_back must be True or False')
+    if not (np.isfinite(pixscale) and pixscale > 0):
+        raise ValueError('pixscale must be positive')
+    _lib.group_fit_flags(bool(fit_back), mode)
+    data, va = _observed_cube(stars, var)
+    n = data.shape[0]
+    ps, ix, _, _ = _lib.psf_fit_arguments(n, psf, psf_index, None, True, False, data.shape[-1])
+    ix = np.arange(n, dtype=np.int32) if ix is None else ix
+    groups = _group_positions(positions, n, pixscale)
+    sizes = np.array([len(g) for g in groups])
+    first = np.concatenate([[0], np.cumsum(sizes)[:-1]])           # the first table row of each stamp
+    nrow = int(sizes.sum())
+    cols = OrderedDict()
+    cols['group'] = np.repeat(np.arange(n), sizes)
+    cols['source'] = np.concatenate([np.arange(k) for k in sizes])
+    for name in _FIT_COLS_GROUP[2:]:
+        wide = name in ('shift', 'err_shift')
+        cols[name] = np.zeros((nrow, 2) if wide else nrow, dtype=np.int64 if name in ('npix', 'status') else float)
+    ctx = get_context(128, pixscale, data.shape[-1], precision, device)
+    for K in np.unique(sizes):
+        idx = np.flatnonzero(sizes == K)
+        sh = np.array([groups[i] for i in idx])                    # (m, K, 2), pixels
+        sub_var = None if va is None else va[idx]
+        if K == 1:
+            fit = ctx.fit_stamps_psf(data[idx], ps, var=sub_var, psf_index=ix[idx], shift=sh[:, 0], background=bool(fit_back),
+                                     fixed_shift=mode == 'fixed')
+            head = fit[:, [3, 9, 4, 11, 10]]
+            src = fit[:, None, [0, 1, 2, 6, 7, 8, 12, 13]]
+            corr = np.zeros((len(idx), 1))
+        else:
+            fit = ctx.fit_groups_psf(data[idx], ps, sh, var=sub_var, psf_index=ix[idx], background=bool(fit_back), mode=mode)
+            head = fit[:, [0, 1, 2, 5, 4]]
+            src = fit[:, 8:8 + 8 * K].reshape(len(idx), K, 8)
+            cm = np.zeros((len(idx), _lib.MAX_GROUP, _lib.MAX_GROUP))
+            for c, (i, j) in enumerate(_GROUP_PAIRS):
+                cm[:, i, j] = cm[:, j, i] = np.abs(fit[:, 40 + c])
+            corr = cm.max(axis=2)[:, :K]
+        rows = (first[idx][:, None] + np.arange(K)[None, :]).ravel()
+        flat = src.reshape(-1, 8)
+        cols['scale'][rows] = flat[:, 0]
+        cols['shift'][rows] = flat[:, 1:3] * pixscale
+        cols['flux'][rows] = flat[:, 6]
+        cols['err_scale'][rows] = flat[:, 3]
+        cols['err_shift'][rows] = flat[:, 4:6] * pixscale
+        cols['err_flux'][rows] = flat[:, 7]
+        for c, name in enumerate(('back', 'err_back', 'chi2', 'npix', 'status')):
+            cols[name][rows] = np.repeat(head[:, c], K)
+        cols['max_corr'][rows] = corr.ravel()
+    assert tuple(cols) == _FIT_COLS_GROUP
+    return _make_table(cols)
+
+
 METRIC_RADII = (0.2, 0.4, 0.6, 1.0, 2.0)      # default encircled-energy radii [arcsec]
 METRIC_BOXES = (0.2, 0.4, 0.6, 1.0)           # default ensquared-energy box sides [arcsec] (0.2": the WFM spaxel)
 METRIC_FRACTIONS = (0.5, 0.8)                 # default fractions of the EE radii
