@@ -618,6 +618,10 @@ int mpsfr_host_time(mpsfr_ctx* ctx, double* seconds, long* calls);
  *   "tel"        [dim/2+1][dim]  telescope OTF, transposed half plane (psfrec.py:784-790)
  *   "dphi0"      [chunk tasks][ndir][dim/2+1][dim] structure function / lambda-factor,
  *                transposed half plane (psfrec.py:717-722)
+ *   "dlin"       [chunk tasks][ndir][dim/2+1][dim/32] line minima of the series form of stage A (option
+ *                "prune_eps" > 0): the minimum of max("dphi0", 0) over each block of 32 columns of a line, as
+ *                float (f64 mode: rounded down); >= 3e38 where the whole block lies outside the support of the
+ *                telescope OTF (option "support_skip")
  *   "pre"        [chunk tasks][nl][dimpsf][dimpsf] stamps before the convolutions (psfrec.py:685)
  *   "vkeep"      [chunk tasks][(nl+1)/2] lines of the half plane transformed per wavelength pair
  *                (option "prune_eps")

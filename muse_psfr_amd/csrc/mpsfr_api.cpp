@@ -231,7 +231,7 @@ struct mpsfr_ctx {
     int last_ndir = 0, last_nl = 0, last_chunk_tasks = 0, last_lane = 0;
     int last_ntab = 2;                   // layer tables per direction of the current AO tables (2: a legacy call)
     int last_gpp = 1;                    // stamp groups per task of the last call: npos of a field call, else 1
-    bool last_mf = false, last_pruned = false, last_mf2 = false;
+    bool last_mf = false, last_pruned = false, last_mf2 = false, last_dlin = false;
     float last_thr_blk = 0.f;
     bool last_floor_per_task = false;
     std::vector<double> last_lpc;        // c of every wavelength of the last call
@@ -2014,6 +2014,7 @@ static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) 
     c->last_mf = mf;
     c->last_mf2 = mf2;
     c->last_pruned = prune;
+    c->last_dlin = prune && series && !io.pre_in;     // (the series form of stage A wrote its line minima)
     c->last_thr_blk = thr_blk;
     c->last_floor_per_task = floor_per_task;
     c->last_lpc.resize(nl);
@@ -2474,6 +2475,16 @@ long mpsfr_debug_fetch(mpsfr_ctx* c, const char* what, double* out, size_t capac
         n = (size_t)c->last_chunk_tasks * c->last_ndir * H1 * N;
         src = c->lane[c->last_lane].D0t.p;
         is_real_r = true;
+    } else if (!strcmp(what, "dlin")) {
+        if (!c->last_dlin)
+            return fail(MPSFR_E_INVALID, "no line minima in the last call (prune_eps = 0, or stage A did not run in "
+                                         "its series form)");
+        n = (size_t)c->last_chunk_tasks * c->last_ndir * H1 * (N / 32);
+        if (n > capacity) return fail(MPSFR_E_INVALID, "capacity %zu < %zu", capacity, n);
+        std::vector<float> tmp(n);
+        HIPCHK(hipMemcpy(tmp.data(), c->lane[c->last_lane].dlin.p, n * sizeof(float), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) out[i] = (double)tmp[i];
+        return (long)n;
     } else if (!strcmp(what, "pre")) {
         n = (size_t)c->last_chunk_tasks * c->last_gpp * c->last_nl * NS * NS;
         src = c->lane[c->last_lane].pre.p;

@@ -267,41 +267,6 @@ __device__ __forceinline__ void fmac_bc(double& acc, double x, double w) {      
 constexpr int kNX = NAO / 16;        // register pairs of the 80 real inputs of a fold of K_PATCH_ROWS
 constexpr int kNXH = (kNH + 15) / 16;  // register pairs per component of the 41 complex inputs of a line
 
-// Minima over the lanes 0-31 and 32-63 of four values at a time: five v_min_f32_dpp steps each (quad
-// swaps, half-row and row mirrors: every lane holds the minimum of its row of 16; row_bcast:15: rows 1
-// and 3 hold the minima of lanes 0-31 and 32-63 -- row 0 gets min(v, 0) and row 2 the minimum of rows
-// 1 | 2, which nobody reads).  One statement: a DPP operand must not have been written in the two wait
-// states before, which the three other values' instructions provide between the steps of one value
-// (and the opening s_nop for whatever computed the inputs); hipcc does not form v_min_f32_dpp from
-// __builtin_amdgcn_update_dpp + fminf with an identity of +inf (mov, mov_dpp, two wait states, min:
-// the fused minima took a third of the kernel that way).
-#define MPSFR_MIN4(ctrl)                                                        \
-    "v_min_f32_dpp %0, %0, %0 " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
-    "v_min_f32_dpp %1, %1, %1 " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
-    "v_min_f32_dpp %2, %2, %2 " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
-    "v_min_f32_dpp %3, %3, %3 " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-__device__ __forceinline__ void min32_x4(float& a, float& b, float& c, float& d) {
-    asm("s_nop 1\n\t"
-        MPSFR_MIN4("quad_perm:[1,0,3,2]")
-        MPSFR_MIN4("quad_perm:[2,3,0,1]")
-        MPSFR_MIN4("row_half_mirror")
-        MPSFR_MIN4("row_mirror")
-        MPSFR_MIN4("row_bcast:15")
-        "s_nop 0"       /* (the next instruction may read d: written by a DPP instruction one state before) */
-        : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
-}
-// the same over the rows of 16 lanes alone (no row_bcast step): every lane holds its row's minimum
-__device__ __forceinline__ void min16_x4(float& a, float& b, float& c, float& d) {
-    asm("s_nop 1\n\t"
-        MPSFR_MIN4("quad_perm:[1,0,3,2]")
-        MPSFR_MIN4("quad_perm:[2,3,0,1]")
-        MPSFR_MIN4("row_half_mirror")
-        MPSFR_MIN4("row_mirror")
-        "s_nop 0"
-        : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
-}
-#undef MPSFR_MIN4
-
 // The sums of a group of CNT residues r_i = R0 + RS i:  acc[i] = sum_j in[r_i + Q j] W_64^(j k2)
 // (the factor W_N^(r k2) is the caller's), wj[j - JMIN] = W_64^(j k2).  HERM = false: the 80 real inputs of
 // K_PATCH_ROWS, xr = broadcast operands with index su + 40 (xi unused).  HERM = true: the Hermitian half of a line,
@@ -633,6 +598,41 @@ template <typename RO> struct SeriesCfg;
 template <> struct SeriesCfg<float> { static constexpr int K = 4; };
 template <> struct SeriesCfg<double> { static constexpr int K = 8; };
 
+// Minima over each row of 16 lanes of NV values at once (NV a power of two <= 16), transposed: at a step that pairs the
+// lanes l and l ^ B (in the order row_mirror, row_half_mirror, quad_perm [2,3,0,1], [1,0,3,2] every partner agrees with
+// the lane in the bits already used), the lanes with bit B clear go on with the first half of the values and the others
+// with the second: two selects and one DPP minimum per PAIR of values, and lane l ends with the row's minimum of value
+// l % NV -- the lane that stores it.  With fewer values than 2 B a step is a plain minimum of every value.  16 values:
+// 46 instructions with the step over the two rows of a line, where five v_min_f32_dpp steps per value and a compare
+// and a select to pick each value's lane were 112.  The DPP operand is the builtin's: hipcc folds the move into
+// v_min_i32_dpp and pads its wait states itself (tools/isa_lint.py R6 still checks them).
+template <int CTRL>
+__device__ __forceinline__ float min_dpp(float mine, float sent) {
+    // (no value is below -0 or a NaN: the order of the bit patterns as signed integers is the order of the values, and
+    // an integer minimum needs no canonical operands, so the DPP move folds into it)
+    const int a = __float_as_int(mine);
+    const int b = __builtin_amdgcn_update_dpp(0, __float_as_int(sent), CTRL, 0xf, 0xf, true);
+    return __int_as_float(a < b ? a : b);
+}
+template <int NV, int B = 8>
+__device__ __forceinline__ void rowmin_transposed(float* v, int lane) {
+    constexpr int CTRL = B == 8 ? 0x140 : (B == 4 ? 0x141 : (B == 2 ? 0x4E : 0xB1));
+    if constexpr (NV > B) {
+        static_assert(NV == 2 * B, "a power of two");
+        const bool hi = (lane & B) != 0;
+#pragma unroll
+        for (int j = 0; j < B; ++j) {
+            const float a = v[j], b = v[j + B];
+            v[j] = min_dpp<CTRL>(hi ? b : a, hi ? a : b);
+        }
+        if constexpr (B > 1) rowmin_transposed<B, B / 2>(v, lane);
+    } else {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) v[j] = min_dpp<CTRL>(v[j], v[j]);
+        if constexpr (B > 1) rowmin_transposed<NV, B / 2>(v, lane);
+    }
+}
+
 // The lines of a wave: xv = their inputs (lane l holds input min(16 a + l % 16, 40) of ITS line in xv[a]),
 // wjp[j - JMIN] = W_L^(j k2) of the lane, swr[r * L + k2] = W_N^(r k2) (LDS), scoef = the coefficients
 // of line y (LDS, [x][K]); r0m53, delta, spv, dst, dlin: the lane's line (td); k2 = lane % L.
@@ -657,9 +657,12 @@ __device__ __forceinline__ void series_line(const cx<double>* xv, const cx<doubl
     double out[Q];
     // A branch hipcc cannot fold (the flag comes out of an asm statement and is always 1): the join
     // behind it pins `out` in registers and keeps the fold and the transform apart from the
-    // polynomial phase.  As one basic block the 1280^2 kernel is allocated 256 registers + 124 bytes
-    // of scratch instead of 238 + 0 and takes 246 us instead of 180; scheduling fences alone
-    // (__builtin_amdgcn_sched_barrier) do not change that.
+    // polynomial phase.  As one basic block the 1280^2 kernel with the 80-input fold was allocated 256 registers
+    // + 124 bytes of scratch instead of 238 + 0 and took 246 us instead of 180; scheduling fences alone
+    // (__builtin_amdgcn_sched_barrier) do not change that.  With the Hermitian fold the kernel needs 144: without
+    // the branch it has 16-20 fewer 64-bit moves per unit, the same time within 0.1 us at 512^2, 161 registers at
+    // 1280^2 -- and hipcc contracts the multiply-adds of the transform differently, so that the f64-mode structure
+    // function changes in its last bit.  The branch stays.
     int always;
     asm volatile("s_mov_b32 %0, 1" : "=s"(always));
     if (!always) {
@@ -687,88 +690,105 @@ __device__ __forceinline__ void series_line(const cx<double>* xv, const cx<doubl
     // (K_DMIN read all of D back for them: 12 us at 512^2, 69 us at 1280^2): the minimum of max(D, 0)
     // over the 32 columns [32 kb, 32 kb + 32) of the line goes to dlin[kb]; K_DMIN16 takes the minima
     // over 16 lines.  A lane's values are x = L k1 + k2:
-    //   L = 64: kb = 2 k1 + (lane >= 32); min32_x4 leaves the minima in lanes 16-31 and 48-63, lane
-    //           16 + k1 % 16 (48 + k1 % 16) keeps the result of k1;
+    //   L = 64: kb = 2 k1 + (lane >= 32): the rows of 16 lanes (rowmin_transposed), then rows 1 and 3 take the minimum
+    //           with the row before them; lane 16 + k1 % 16 (48 + k1 % 16) holds the result of k1;
     //   L = 32: kb = k1, the 32 lanes of a line; the same, lanes 16-31 / 48-63 are the two lines;
-    //   L = 16: kb = k1 / 2: the two values of a lane first, then the row of 16 lanes (min16_x4); lane
-    //           kb % 16 of the line's row keeps kb.
+    //   L = 16: kb = k1 / 2: the two values of a lane first, then the row of 16 lanes; lane kb % 16 of the line's
+    //           row holds kb.
     constexpr int NB = L == 16 ? Q / 2 : Q;              // values per lane that go into the lane minima
-    float keep[(NB + 15) / 16], dq[Q < 4 ? 4 : Q];
+    float keep[(NB + 15) / 16], dq[Q];
 #pragma unroll
     for (int i = 0; i < (NB + 15) / 16; ++i) keep[i] = 0.f;
-    if constexpr (sizeof(RO) == 4) {
-        const float df = (float)delta, rf = (float)r0m53;
+    // The pieces of a line in groups of G: one wave-uniform test skips a group with no piece inside the support;
+    // otherwise the coefficients of all G pieces are read together (the whole line is in LDS: reading a skipped
+    // piece's is harmless) and their polynomials run side by side -- one LDS wait and G independent chains per
+    // basic block instead of a branch, a read and a wait per piece.  A piece outside the support is still never
+    // stored and its dq is the sentinel; a group that lies wholly inside (most) tests no piece.
+    constexpr int G = sizeof(RO) == 4 ? (Q < 4 ? Q : 4) : 2;
+    constexpr unsigned kFull = (1u << G) - 1u;
+    static_assert(Q % G == 0, "whole groups");
+    auto lane_min = [](RO d) {      // (f64: rounded down, the bound stays a bound)
+        if constexpr (sizeof(RO) == 4) return fmaxf(d, 0.f);
+        else return fmaxf(__double2float_rd(d), 0.f);
+    };
+    auto finish_group = [&](int k0, unsigned gm, const RO* d) {
+        if (sizeof(RO) == 4 && gm == kFull) {
 #pragma unroll
-        for (int k1 = 0; k1 < Q; ++k1) {
-            if (!((kmask >> k1) & 1u)) {
-                dq[k1] = kSkipped;
-                continue;
-            }
-            const float4 h = *reinterpret_cast<const float4*>(scoef + (size_t)(L * k1 + k2) * K);
-            const float dF = rf * fmaf(fmaf(fmaf(h.w, df, h.z), df, h.y), df, h.x);
-            const float d = (float)(fma(scale2, spv - out[k1], (double)dF));
-            if (valid) dst[L * k1] = d;
-            dq[k1] = fmaxf(d, 0.f);
-        }
-    } else {
-#pragma unroll
-        for (int k1 = 0; k1 < Q; ++k1) {
-            if (!((kmask >> k1) & 1u)) {
-                dq[k1] = kSkipped;
-                continue;
-            }
-            const double* h = scoef + (size_t)(L * k1 + k2) * K;
-            double a = h[K - 1];
-#pragma unroll
-            for (int k = K - 2; k >= 0; --k) a = fma(a, delta, h[k]);
-            const double d = fma(scale2, spv - out[k1], r0m53 * a);
-            if (valid) dst[L * k1] = d;
-            dq[k1] = fmaxf(__double2float_rd(d), 0.f);      // (rounded down: the bound stays a bound)
-        }
-    }
-    if (dlin != nullptr) {
-        if constexpr (Q < 4) {
-            dq[2] = dq[0];
-            dq[3] = dq[1];
-        }
-        if constexpr (L == 16) {
-            static_assert(Q % 8 == 0, "pairs of values, four pairs to a statement");
-#pragma unroll
-            for (int kb = 0; kb < NB; ++kb) dq[kb] = fminf(dq[2 * kb], dq[2 * kb + 1]);
-#pragma unroll
-            for (int kb = 0; kb < NB; kb += 4) {
-                min16_x4(dq[kb], dq[kb + 1], dq[kb + 2], dq[kb + 3]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if ((lane & 15) == ((kb + i) & 15)) keep[(kb + i) >> 4] = dq[kb + i];
-            }
+            for (int i = 0; i < G; ++i) dq[k0 + i] = lane_min(d[i]);
             if (valid) {
 #pragma unroll
-                for (int i = 0; i < (NB + 15) / 16; ++i) {
-                    const int kb = 16 * i + (lane & 15);
-                    if (kb < NB) dlin[kb] = keep[i];
-                }
+                for (int i = 0; i < G; ++i) dst[L * (k0 + i)] = d[i];
             }
         } else {
 #pragma unroll
-            for (int k1 = 0; k1 < (Q < 4 ? 4 : Q); k1 += 4) {
-                min32_x4(dq[k1], dq[k1 + 1], dq[k1 + 2], dq[k1 + 3]);
+            for (int i = 0; i < G; ++i) dq[k0 + i] = ((gm >> i) & 1u) ? lane_min(d[i]) : kSkipped;
+            if (valid) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (k1 + i < Q && (lane & 15) == ((k1 + i) & 15)) keep[(k1 + i) >> 4] = dq[k1 + i];
+                for (int i = 0; i < G; ++i)
+                    if ((gm >> i) & 1u) dst[L * (k0 + i)] = d[i];
             }
-            if (valid && (lane & 16)) {
+        }
+    };
+    const float df = (float)delta, rf = (float)r0m53;
 #pragma unroll
-                for (int i = 0; i < (Q + 15) / 16; ++i) {
-                    const int k1 = 16 * i + (lane & 15);
-                    if (k1 < Q) dlin[L == 64 ? 2 * k1 + (lane >> 5) : k1] = keep[i];
-                }
+    for (int k0 = 0; k0 < Q; k0 += G) {
+        const unsigned gm = (kmask >> k0) & kFull;
+        if (gm == 0u) {
+#pragma unroll
+            for (int i = 0; i < G; ++i) dq[k0 + i] = kSkipped;
+            continue;
+        }
+        RO d[G];
+        if constexpr (sizeof(RO) == 4) {
+            float4 h[G];
+#pragma unroll
+            for (int i = 0; i < G; ++i) h[i] = *reinterpret_cast<const float4*>(scoef + (size_t)(L * (k0 + i) + k2) * K);
+#pragma unroll
+            for (int i = 0; i < G; ++i) {
+                const float dF = rf * fmaf(fmaf(fmaf(h[i].w, df, h[i].z), df, h[i].y), df, h[i].x);
+                d[i] = (float)(fma(scale2, spv - out[k0 + i], (double)dF));
+            }
+        } else {
+            double a[G];
+#pragma unroll
+            for (int i = 0; i < G; ++i) a[i] = scoef[(size_t)(L * (k0 + i) + k2) * K + K - 1];
+#pragma unroll
+            for (int k = K - 2; k >= 0; --k) {
+#pragma unroll
+                for (int i = 0; i < G; ++i) a[i] = fma(a[i], delta, scoef[(size_t)(L * (k0 + i) + k2) * K + k]);
+            }
+#pragma unroll
+            for (int i = 0; i < G; ++i) d[i] = fma(scale2, spv - out[k0 + i], r0m53 * a[i]);
+        }
+        finish_group(k0, gm, d);
+    }
+    if (dlin != nullptr) {
+        // values 16 i .. 16 i + 15 (or what is left of them, a power of two) at a time: lane 16 i + l % 16 of a row of
+        // lanes ends with the row's minimum of value 16 i + l % 16
+        if constexpr (L == 16) {
+#pragma unroll
+            for (int kb = 0; kb < NB; ++kb) dq[kb] = fminf(dq[2 * kb], dq[2 * kb + 1]);
+        }
+        static_for<0, (NB + 15) / 16>([&](auto ic) {
+            constexpr int i = decltype(ic)::value, NV = NB - 16 * i < 16 ? NB - 16 * i : 16;
+            rowmin_transposed<NV>(dq + 16 * i, lane);
+            keep[i] = dq[16 * i];
+            // (L >= 32: rows 1 and 3 take the minimum with the row before them -- lanes 0-31 and 32-63)
+            if constexpr (L != 16) keep[i] = fminf(keep[i], __shfl_up(keep[i], 16));
+        });
+        if (valid && (L == 16 || (lane & 16))) {
+#pragma unroll
+            for (int i = 0; i < (NB + 15) / 16; ++i) {
+                const int kb = 16 * i + (lane & 15);
+                if (kb < NB) dlin[L == 64 ? 2 * kb + (lane >> 5) : kb] = keep[i];
             }
         }
     }
 }
 
-// Persistent form: one workgroup per CU, the C = (N/2+1) ntd lines in y-major order cut into equal
+// Persistent form: one workgroup per CU (12 waves, three per SIMD: with the 144-146 registers of the Hermitian fold a
+// third wave fits, 8 -> 12 waves took 1.4 us off 25.8 at 512^2 and 2.8 off 34.4 at 1280^2 x 20 rows; a fourth needs
+// 128 registers, which hipcc only reaches with 28-84 bytes of scratch), the C = (N/2+1) ntd lines in y-major order cut into equal
 // contiguous shares; the waves of a workgroup take the lines of its share in turn (wave w: lines
 // c0 + w, c0 + w + NW, ...), so every wave of the launch does the same number of lines +- 1 and the
 // set-up (twiddles, first coefficients) is paid once.  At any time the waves of a workgroup are within
@@ -778,7 +798,7 @@ __device__ __forceinline__ void series_line(const cx<double>* xv, const cx<doubl
 // per launch).  [first form: one workgroup per (y, group of tasks) -- 2056 workgroups at 512^2, whose
 // set-up and +-1 task imbalance cost 20 of its 50 us]
 #ifndef MPSFR_SERIES_THREADS
-#define MPSFR_SERIES_THREADS 512
+#define MPSFR_SERIES_THREADS 768
 #endif
 template <int N, typename RO>
 constexpr int series_threads() { return N <= 128 ? 256 : MPSFR_SERIES_THREADS; }
