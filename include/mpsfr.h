@@ -341,8 +341,10 @@ int mpsfr_wait_multi(mpsfr_ctx* const* ctxs, int nctx);
  *                  bit: the squared residuals of a nearly exact fit (I^2 2^-54 and less) are subnormal in fp32
  *                  there, so chi2 and the err_* columns, which carry chi2 / dof, are not exact multiples.
  * The circular fits inside mpsfr_reconstruct and its siblings follow the same rule (their stamps have sum 1: peaks of
- * 1e-4 ... 1); the elliptical fit (mpsfr_fit_stamps_elliptical and the elliptical columns) is another kernel and does
- * not.
+ * 1e-4 ... 1).  The elliptical fit (mpsfr_fit_stamps_elliptical and the elliptical columns) is another kernel with the
+ * same range: a brightest pixel outside [2^-40, 2^40] in modulus is refused with status 2 in both precision modes;
+ * inside it the status, the parameters and chi2, flux and the err_* columns (scaled by the powers of the factor) are
+ * right to the tolerances of the precision mode.  Bit identity under a factor 2^k is not promised there.
  * on_device = 1: both pointers are device pointers and the call is queued on the context stream, after every call
  * queued so far on this context: stamps written by a device-output mpsfr_reconstruct* are complete when it reads them. */
 int mpsfr_fit_stamps(mpsfr_ctx* ctx, int nstamp, const double* stamps, double* fit_out,
@@ -357,12 +359,23 @@ int mpsfr_fit_stamps(mpsfr_ctx* ctx, int nstamp, const double* stamps, double* f
  * queued on the context stream (e.g. after a device-output mpsfr_reconstruct_field / mpsfr_reconstruct_profile).
  * stamps: [nstamp][dimpsf][dimpsf] float64; fit_out: [nstamp][MPSFR_NFIT_ELL].  Errors: the reduced-chi2 covariance
  * (dof = npix - 7), propagated to first order.  A stamp whose elongation is not determined (e -> 0) has a finite rot
- * and a large err_rot (at most 180); that is not a failure.  Timed under the fit's profiling id. */
+ * and a large err_rot (at most 180); that is not a failure.  Timed under the fit's profiling id.
+ * Rule for stamps without such a Moffat in them (any data is accepted on_device; nothing here is an error of the
+ * call), the circular fit's: a row whose status & 3 is 0 holds finite numbers only, lies inside the search domain
+ * (fwhm > 1e-3 px, n >= 1/90, |e| <= 0.94, i.e. b/a >= 0.176) and is the least-squares minimum.  Otherwise the row
+ * says so: 2 (singular) for an all-zero stamp, for a stamp with a NaN or an infinite pixel, for a brightest pixel
+ * outside the amplitude range [2^-40, 2^40] of mpsfr_fit_stamps (the other fields are then the start values or NaN),
+ * and where the normal matrix cannot be factored; 1 (not converged) at the iteration cap, where the iteration ended
+ * with n < 1/90 against the bound n = 0.01 of the domain (a constant or an all-negative stamp), and where it ended
+ * with |e| > 0.94 against the bound |e| = 0.95: a stamp more elongated than b/a = 0.16 has its minimum outside the
+ * domain, and the row is the point of the boundary the steps were cut at, not a minimum.  A single hot pixel is a
+ * Moffat of vanishing width: away from the edge it converges with the ill-conditioned bit set. */
 #define MPSFR_NFIT_ELL 24
 /* fit_out[k]: 0 peak  1 p0  2 q0  3 alpha_major (px)  4 alpha_minor (px)  5 n  6 rot (deg, [0,180), from +q towards +p)
  *             7 fwhm_major (px)  8 fwhm_minor (px)  9 chi2  10 iterations  11 err_peak  12 err_p0  13 err_q0
  *             14 err_fwhm_major  15 err_fwhm_minor  16 err_rot (deg)  17 err_n
- *             18 status (codes and MPSFR_FIT_ILL_CONDITIONED bit as fit_out[14] of MPSFR_NFIT, same rule on n)
+ *             18 status (codes and MPSFR_FIT_ILL_CONDITIONED bit as fit_out[14] of MPSFR_NFIT, same rule on n, and the
+ *                rule on |e| above; the number behind the bit is taken from the 7-variable normal matrix)
  *             19 flux = peak pi alpha_major alpha_minor / (n - 1)  20 err_flux  21..23 zero (reserved) */
 int mpsfr_fit_stamps_elliptical(mpsfr_ctx* ctx, int nstamp, const double* stamps, double* fit_out, int on_device);
 

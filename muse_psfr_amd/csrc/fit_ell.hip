@@ -204,6 +204,12 @@ k_fit_ell(int nstamp, const double* __restrict__ stamps, double* __restrict__ fi
     // elliptical isophotes.
     const int p0i = besto / NS, q0i = besto % NS;
     const int rm = min(min(p0i, NS - 1 - p0i), min(q0i, NS - 1 - q0i));
+    // Amplitude range (include/mpsfr.h): k_fit's.  The sums of the float iterations and of the polish scale with the
+    // square of the peak, and the moment start squares the pixels in float in both modes; a stamp whose brightest
+    // pixel lies outside [2^-40, 2^40] in modulus is refused (status 2) rather than fitted wrongly.  Zero, NaN and
+    // infinite brightest pixels fail the comparison too.
+    const float abest = fabsf((float)best);
+    const bool amp_ok = abest >= 0x1p-40f && abest <= 0x1p40f;
     int cnt = 0;
     const double half = 0.5 * best;
     float ms1 = 0.f, ms2 = 0.f, mxx = 0.f, myy = 0.f, mxy = 0.f;
@@ -257,8 +263,9 @@ k_fit_ell(int nstamp, const double* __restrict__ stamps, double* __restrict__ fi
     ell_accumulate<RE>(sp, lane, v, ne);
     S mu = (S)kFitMu0, nu = (S)2;
     const S mu_max = (S)kFitMuMax;
-    int it = 0, status = 1;
-    while (it < kFitMaxIt) {
+    int it = 0, status = amp_ok ? 1 : 2;
+    const int maxit = amp_ok ? kFitMaxIt : 0;
+    while (it < maxit) {
         ++it;
         S dx[NPE];
         if (!fit_lm_solve<NPE, S, RE>(ne, mu, dx)) {
@@ -370,7 +377,7 @@ k_fit_ell(int nstamp, const double* __restrict__ stamps, double* __restrict__ fi
     if (rot < 0.0) rot += 180.0;
     if (rot >= 180.0) rot -= 180.0;
     const double flux = I * kPi * al * al / (n - 1.0);
-    double* o = fit + (size_t)st * NFIT_ELL;
+    double o[NFIT_ELL];                 // the row, in registers until the status is known
     o[0] = I; o[1] = vd[1]; o[2] = vd[2];
     o[3] = al * f; o[4] = al / f; o[5] = n; o[6] = rot;
     o[7] = w * f; o[8] = w / f;
@@ -414,11 +421,27 @@ k_fit_ell(int nstamp, const double* __restrict__ stamps, double* __restrict__ fi
         o[20] = quad(gfl);
         if (n * n * sqrt(fmax(cov[6][6], 0.0)) * fabs(I) >= kFitIllCond) status |= 4;
     } else {
+#pragma unroll
         for (int k = 11; k <= 17; ++k) o[k] = 0.0;
         o[20] = 0.0;
         if (status == 0) status = 2;
     }
+    // A row that claims a minimum holds finite numbers only and lies inside the search domain (k_fit's rule).  A NaN
+    // or -inf pixel enters the gradient and chi2 but not the normal matrix: every step is NaN, is rejected, and the
+    // damping runs out as it does at a minimum -- singular (2), not converged.  A stamp without a maximum (constant,
+    // all negative) sends the iteration to the bound eta = 100 of the domain, and one more elongated than the domain
+    // allows to the bound |e| = kFitMaxE, where steps are cut until they pass the convergence test: not converged (1)
+    // from eta > 90 (n < 1/90) and from |e| > kFitMaxE - 0.01 on.
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < NFIT_ELL; ++k)
+        if (k != 18) finite = finite && fabs(o[k]) < __builtin_inf();
+    if ((status & 3) == 0 && !finite) status = (status & 4) | 2;
+    if ((status & 3) == 0 && (eta > 90.0 || esq > (kFitMaxE - 0.01) * (kFitMaxE - 0.01))) status = (status & 4) | 1;
     o[18] = (double)status;
+    double* row = fit + (size_t)st * NFIT_ELL;
+#pragma unroll
+    for (int k = 0; k < NFIT_ELL; ++k) row[k] = o[k];
 }
 
 }  // namespace

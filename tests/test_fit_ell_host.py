@@ -126,3 +126,105 @@ def test_reference_jacobian_matches_finite_differences():
         vm[k] -= h
         fd = (M.model(vp) - M.model(vm)) / (2 * h)
         assert np.abs(fd - J[:, k]).max() <= 1e-6 * np.abs(J[:, k]).max(), k
+
+
+# ---- the fp64 yardstick of tests/test_gpu_fit_ell_columns.py
+def test_fit_full_on_an_exact_stamp_returns_the_truth():
+    e1, e2 = M.e_from_ratio(0.7, 30.0)
+    truth = np.array([1.3, 19.3, 20.6, 6.0, e1, e2, 1.0 / 2.5])
+    full = M.fit_full(M.stamp(1.3, 19.3, 20.6, 6.0, 0.7, 30.0, 2.5))
+    assert np.abs(full['v'] - truth).max() <= 1e-9
+    assert full['chi2'] < 1e-24
+    al = 6.0 / (2 * np.sqrt(2 ** 0.4 - 1))
+    assert abs(full['flux'] - 1.3 * np.pi * al * al / 1.5) <= 1e-9 * full['flux']
+    assert abs(full['alpha_major'] * full['alpha_minor'] - al * al) <= 1e-9 * al * al
+    assert abs(full['alpha_minor'] / full['alpha_major'] - 0.7) <= 1e-9
+    np.testing.assert_allclose(M.v_from_row(_row_of(full)), full['v'], rtol=0, atol=1e-12)
+
+
+def _row_of(full):
+    row = np.zeros(_lib.NFIT_ELL)
+    for k, j in M.COLUMN.items():
+        if k in full:
+            row[j] = full[k]
+    return row
+
+
+@pytest.mark.parametrize('ba,rot', [(0.7, 30.0), (0.98, 120.0), (0.3, 100.0)])
+def test_numerical_gradient_against_the_analytic_one_of_fwhm_major(ba, rot):
+    """fwhm_major = w f, f = ((1 + e)/(1 - e))^(1/4): d/dw = f, d/de_k = w f e_k / (2 e (1 - e^2))."""
+    e1, e2 = M.e_from_ratio(ba, rot)
+    v = np.array([1.0, 19.7, 20.2, 5.0, e1, e2, 0.4])
+    e = np.hypot(e1, e2)
+    f = ((1 + e) / (1 - e)) ** 0.25
+    want = np.array([0, 0, 0, f, 5.0 * f * e1 / (2 * e * (1 - e * e)), 5.0 * f * e2 / (2 * e * (1 - e * e)), 0])
+    got = M.num_gradient('fwhm_major', v)
+    assert np.abs(got - want).max() <= 1e-7 * np.abs(want).max(), (got, want)
+    # rot across its branch cut (e2 = 0, e1 < 0): the differences are taken modulo 180 degrees
+    vc = np.array([1.0, 19.7, 20.2, 5.0, -0.3, 0.0, 0.4])
+    g = M.num_gradient('rot', vc)
+    assert abs(g[5] - np.rad2deg(0.5 / -0.3)) <= 1e-7 * abs(g[5]) and abs(g[4]) <= 1e-7 * abs(g[5])
+
+
+def _symmetric_cases():
+    """Round Moffats (peak 1, n 2.5, FWHM 3 and 8) at the stamp's centre of symmetry (19.5, 19.5) plus a perturbation
+    of 1e-3 of the peak with the eight symmetries of the square: a concentric wide Moffat, or the seeded noise field of
+    tail_ref.perturbed_cases averaged over its flips and transposes.  e = 0 is then a stationary point of the
+    7-variable fit, and J^T J is block diagonal between (e1, e2) and the five circular variables."""
+    import tail_ref as T
+    rng = np.random.default_rng(77)
+    noise = rng.standard_normal((40, 40))
+    noise = sum(a for t in (noise, noise.T) for a in (t, t[::-1], t[:, ::-1], t[::-1, ::-1])) / 8.0
+    noise *= 1e-3 / np.abs(noise).max()
+    out = []
+    for fw in (3.0, 8.0):
+        base = T.moffat_stamp(1.0, 19.5, 19.5, fw, 2.5)
+        out.append(('wide_fwhm%g' % fw, fw, base + T.moffat_stamp(1e-3, 19.5, 19.5, 2.5 * fw, 1.8)))
+        out.append(('noise_fwhm%g' % fw, fw, base + noise))
+    return out
+
+
+def test_circular_columns_agree_with_the_circular_reference_at_e_0():
+    """A 5-variable MINPACK fit (tail_ref.fit) against the 7-variable fit_full of the same stamp.  The perturbed
+    stamps of tail_ref are not symmetric, so a free (e1, e2) leaves e = 0 on them and the two fits have different
+    minima; the stamps here are theirs made symmetric (_symmetric_cases), where e stays 0 by construction.  The shared
+    columns then differ by the degrees of freedom alone (1600 - 5 against 1600 - 7 under the square root)."""
+    import tail_ref as T
+    dof = np.sqrt((1600.0 - 5) / (1600.0 - 7))
+    for name, fw, st in _symmetric_cases():
+        c = T.fit(st, (1.0, 19.5, 19.5, fw, 2.5))
+        full = M.fit_full(st, (1.0, 19.5, 19.5, fw, 0.0, 0.0, 0.4))
+        assert np.hypot(full['v'][4], full['v'][5]) <= 1e-12, name
+        for k in ('peak', 'p0', 'q0', 'n', 'flux', 'chi2'):
+            assert abs(full[k] - c[k]) <= 1e-6 * abs(c[k]), (name, k, full[k], c[k])
+        for k in ('err_peak', 'err_p0', 'err_q0', 'err_n'):
+            assert abs(full[k] - c[k] * dof) <= 1e-6 * c[k], (name, k, full[k], c[k] * dof)
+        assert abs(full['err_fwhm_major'] - c['err_fwhm'] * dof) <= 1e-6 * c['err_fwhm']
+        assert abs(full['err_fwhm_minor'] - c['err_fwhm'] * dof) <= 1e-6 * c['err_fwhm']
+
+
+@pytest.mark.parametrize('fw,n', [(2.0, 8.0), (5.0, 2.5), (8.0, 20.0), (20.0, 8.0), (3.0, 1.5)])
+def test_kappa_is_the_circular_one_at_b_over_a_1(fw, n):
+    import tail_ref as T
+    for c in ((19.5, 19.5), (19.7, 20.4)):
+        k7 = M.kappa((1.0, c[0], c[1], fw, 0.0, 0.0, 1.0 / n))
+        k5 = T.kappa(1.0, c[0], c[1], fw, n)
+        assert abs(k7 - k5) <= 0.01 * k5, (c, k7, k5)
+
+
+def test_every_perturbed_case_has_one_minimum():
+    """16 cases; three starts reach the same minimum; the minimum is well conditioned (kappa below the flag's
+    threshold) and err_rot is far from its cap, so the error columns are those of a plain first-order propagation."""
+    refs = M.perturbed_references()
+    assert len(refs) == 16 and len({n for n, _, _, _ in refs}) == 16
+    for name, st, full, spread in refs:
+        a, b = np.unravel_index(st.argmax(), st.shape)
+        assert min(a, 39 - a, b, 39 - b) == (4 if name.endswith('rm4') else 19), name
+        assert spread <= 1e-8, (name, spread)
+        assert full['kappa'] < 100 and full['cond'] < 1e4, (name, full['kappa'], full['cond'])
+        assert 0.0 < full['err_rot'] < 18.0, (name, full['err_rot'])
+        assert full['chi2'] > 1e-8, name
+    print('perturbed: kappa %.3g .. %.3g, cond <= %.3g, err_rot %.3g .. %.3g deg, spread <= %.3g' % (
+        min(f['kappa'] for _, _, f, _ in refs), max(f['kappa'] for _, _, f, _ in refs),
+        max(f['cond'] for _, _, f, _ in refs), min(f['err_rot'] for _, _, f, _ in refs),
+        max(f['err_rot'] for _, _, f, _ in refs), max(s for _, _, _, s in refs)))
