@@ -53,6 +53,114 @@ __device__ __forceinline__ T wave_total(T v) {
     return lane63(v);
 }
 
+// N wave-wide sums at once, each with the additions of wave_total -- the same operands in the same tree, so the same
+// bits -- in 89 instructions for 21 sums where 21 wave_total take 147, and without their dependent chains.  After the first quad swap lanes i and i ^ 1 hold the same partial sum
+// of a value; of two values, one lane of the pair keeps the first and the other the second (one select), and the next
+// step runs on half as many registers.  The same at the second quad swap, the half-row mirror and the row mirror: value
+// k of 16 ends up alone in one lane of every row of register k / 16.  Which lane keeps which value is chosen so that the
+// mirrors, which reverse the order of the lanes they cross, bring together lanes holding the same value: with b0..b3
+// the bits of the lane in its row, the steps keep the second value of a pair where b0 ^ b2, b1 ^ b2, b2 ^ b3, b3 is set.
+// An odd value out is reduced in all lanes as in wave_total.  The rows hold different values now, which row_bcast15 /
+// row_bcast31 (lane 15 or 31 only) cannot carry: the two row steps are v_permlane16_swap (odd rows of one register
+// against the even rows of another -- two registers of 16 values fold into one) and v_permlane32_swap, each followed by
+// the addition wave_total makes there, (s1 + s0) and (s3 + s2), then their sum.  One v_readlane per value.
+template <int CTRL>
+__device__ __forceinline__ int dpp_pull(int own) {       // the value of the lane CTRL names; the lane's own where there is none
+    return __builtin_amdgcn_update_dpp(own, own, CTRL, 0xf, 0xf, false);
+}
+template <int CTRL>
+__device__ __forceinline__ float dpp_pull(float own) {
+    return __builtin_bit_cast(float, dpp_pull<CTRL>(__builtin_bit_cast(int, own)));
+}
+template <int CTRL>
+__device__ __forceinline__ double dpp_pull(double own) {
+    const long long b = __builtin_bit_cast(long long, own);
+    const unsigned lo = (unsigned)dpp_pull<CTRL>((int)(b & 0xffffffffll));
+    const unsigned hi = (unsigned)dpp_pull<CTRL>((int)(b >> 32));
+    return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)lo);
+}
+__device__ __forceinline__ float lane_pick(bool second, float a, float b) { return second ? b : a; }
+__device__ __forceinline__ double lane_pick(bool second, double a, double b) { return second ? b : a; }
+// (inline assembly: s_nop 1 is the two wait states a vector write of either operand needs before the swap reads it;
+// with the builtins of these instructions hipcc of ROCm 7.2 used the first result in place of the second)
+__device__ __forceinline__ void rows_swap16(unsigned& a, unsigned& b) {
+    asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+}
+__device__ __forceinline__ void rows_swap32(unsigned& a, unsigned& b) {
+    asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+}
+template <bool HALVES>
+__device__ __forceinline__ void rows_swap(float& a, float& b) {
+    unsigned x = __builtin_bit_cast(unsigned, a), y = __builtin_bit_cast(unsigned, b);
+    if constexpr (HALVES) rows_swap32(x, y);
+    else rows_swap16(x, y);
+    a = __builtin_bit_cast(float, x);
+    b = __builtin_bit_cast(float, y);
+}
+template <bool HALVES>
+__device__ __forceinline__ void rows_swap(double& a, double& b) {
+    const unsigned long long x = __builtin_bit_cast(unsigned long long, a), y = __builtin_bit_cast(unsigned long long, b);
+    unsigned xl = (unsigned)x, xh = (unsigned)(x >> 32), yl = (unsigned)y, yh = (unsigned)(y >> 32);
+    if constexpr (HALVES) { rows_swap32(xl, yl); rows_swap32(xh, yh); }
+    else { rows_swap16(xl, yl); rows_swap16(xh, yh); }
+    a = __builtin_bit_cast(double, ((unsigned long long)xh << 32) | xl);
+    b = __builtin_bit_cast(double, ((unsigned long long)yh << 32) | yl);
+}
+template <int LANE>
+__device__ __forceinline__ float lane_value(float x) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), LANE));
+}
+template <int LANE>
+__device__ __forceinline__ double lane_value(double x) {
+    const long long b = __builtin_bit_cast(long long, x);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(b & 0xffffffffll), LANE);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), LANE);
+    return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)lo);
+}
+// one in-row step of wave_totals: n values in, (n + 1) / 2 out
+template <int CTRL, int N, typename T>
+__device__ __forceinline__ void wave_totals_step(const T (&in)[N], T (&out)[(N + 1) / 2], bool second) {
+#pragma unroll
+    for (int j = 0; j < N / 2; ++j) {
+        const T a = in[2 * j] + dpp_term<CTRL, 0xf>(in[2 * j]);
+        const T b = in[2 * j + 1] + dpp_term<CTRL, 0xf>(in[2 * j + 1]);
+        out[j] = lane_pick(second, a, b);
+    }
+    if constexpr (N % 2 == 1) out[N / 2] = in[N - 1] + dpp_term<CTRL, 0xf>(in[N - 1]);
+}
+// the lane of a row in which value k of 16 ends up (see above)
+__host__ __device__ constexpr int wave_totals_lane(int k) {
+    const int b3 = (k >> 3) & 1, b2 = ((k >> 2) & 1) ^ b3, b1 = ((k >> 1) & 1) ^ b2, b0 = (k & 1) ^ b2;
+    return b3 * 8 + b2 * 4 + b1 * 2 + b0;
+}
+template <int K, int N, typename T>
+__device__ __forceinline__ void wave_totals_read(T (&v)[N], T r) {
+    if constexpr (K < N) {
+        v[K] = lane_value<(K >> 4) * 16 + wave_totals_lane(K & 15)>(r);
+        if constexpr (((K + 1) & 15) != 0) wave_totals_read<K + 1, N, T>(v, r);
+    }
+}
+// v[k] = wave_total(v[k]) for all k, `lane` the lane of the caller; all 64 lanes must be active
+template <int N, typename T>
+__device__ __forceinline__ void wave_totals(T (&v)[N], int lane) {
+    static_assert(N >= 1 && N <= 32, "one or two registers of 16 values");
+    constexpr int N1 = (N + 1) / 2, N2 = (N1 + 1) / 2, N3 = (N2 + 1) / 2, N4 = (N3 + 1) / 2;
+    T s1[N1], s2[N2], s3[N3], s4[N4];
+    const int b2 = (lane >> 2) & 1;
+    wave_totals_step<0xB1>(v, s1, ((lane ^ b2) & 1) != 0);                 // quad_perm [1,0,3,2]
+    wave_totals_step<0x4E>(s1, s2, (((lane >> 1) ^ b2) & 1) != 0);         // quad_perm [2,3,0,1]
+    wave_totals_step<0x141>(s2, s3, (((lane >> 3) ^ b2) & 1) != 0);        // row_half_mirror
+    wave_totals_step<0x140>(s3, s4, (lane & 8) != 0);                      // row_mirror
+    static_assert(N4 == (N + 15) / 16, "16 values per register");
+    T a = s4[0], b = s4[N4 - 1];
+    rows_swap<false>(a, b);                // a: rows (a0, b0, a2, b2); b: (a1, b1, a3, b3)
+    T p = b + a, q = p;                    // s1 + s0 and s3 + s2 of the first register in rows 0, 2, of the second in 1, 3
+    rows_swap<true>(p, q);                 // p: the lower sums in both halves, q: the upper ones
+    const T t = q + p;                     // (s3 + s2) + (s1 + s0): rows 0, 2 the first register's totals, rows 1, 3 the second's
+    wave_totals_read<0, N, T>(v, t);
+    if constexpr (N > 16) wave_totals_read<16, N, T>(v, t);
+}
+
 template <typename RE>
 __device__ __forceinline__ RE fit_log(RE x);
 template <>
@@ -269,6 +377,23 @@ __device__ __forceinline__ bool fit_spd_inverse(const FitNormEq<T, NP>& ne, doub
 #pragma unroll
         for (int k = 0; k < NP; ++k) cov[k][c] = x[k];
     }
+    return true;
+}
+
+// One column of that inverse per lane: lane c < NP solves column c (x[k] = entry (k, c)) with the factor, which every
+// lane computes from the wave-uniform normal matrix; the operations of a column are those of fit_spd_inverse.  Lanes
+// from NP on solve for a zero right-hand side.  False, and x = 0, if singular.
+template <int NP, typename T, bool ROW_FIRST = false>
+__device__ __forceinline__ bool fit_spd_inverse_column(const FitNormEq<T, NP>& ne, int lane, double x[NP]) {
+    T L[NP][NP], Li[NP], id[NP], b[NP];
+    if (!fit_chol<NP, T, T, ROW_FIRST>(ne, (T)0, L, Li, id)) {
+#pragma unroll
+        for (int k = 0; k < NP; ++k) x[k] = 0.0;
+        return false;
+    }
+#pragma unroll
+    for (int k = 0; k < NP; ++k) b[k] = (k == lane) ? (T)1 : (T)0;
+    fit_chol_solve<NP, T, double>(L, Li, id, b, x);
     return true;
 }
 

@@ -6,6 +6,7 @@
 #include "device_common.h"
 #include "conv_frames.h"
 #include "fit_common.h"
+#include <type_traits>
 
 namespace mpsfr {
 
@@ -315,6 +316,17 @@ k_khat(const double* __restrict__ gam, const double* __restrict__ alp, cx<R>* __
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
+// the 21 wave sums of a pass, (chi2, a[15], g[5]), in one reduction (wave_totals, fit_common.h)
+template <typename RE>
+__device__ __forceinline__ void norm_totals(RE (&t)[21], FitNormEq<RE, 5>& ne, int lane) {
+    wave_totals(t, lane);
+    ne.chi2 = t[0];
+#pragma unroll
+    for (int k = 0; k < 15; ++k) ne.a[k] = t[1 + k];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) ne.g[k] = t[16 + k];
+}
+
 // Accumulators of the normal equations over a lane's pixels.  Generic form: 15 + 5 + 1 multiply-adds
 // per pixel.  Float form: the same 21 sums as 9 packed multiply-adds (v_pk_fma_f32: two fp32 lanes
 // per instruction at the issue cost of one) + 3 plain ones -- with r as a sixth "column" the rows
@@ -340,13 +352,14 @@ struct NormAcc {
             for (int y = x; y < 5; ++y) a[k++] += J[x] * J[y];
         }
     }
-    template <typename F>
-    __device__ __forceinline__ void totals(FitNormEq<RE, 5>& ne, F total) const {
-        ne.chi2 = total(chi2);
+    __device__ __forceinline__ void totals(FitNormEq<RE, 5>& ne, int lane) const {
+        RE t[21];
+        t[0] = chi2;
 #pragma unroll
-        for (int k = 0; k < 15; ++k) ne.a[k] = total(a[k]);
+        for (int k = 0; k < 15; ++k) t[1 + k] = a[k];
 #pragma unroll
-        for (int k = 0; k < 5; ++k) ne.g[k] = total(g[k]);
+        for (int k = 0; k < 5; ++k) t[16 + k] = g[k];
+        norm_totals(t, ne, lane);
     }
 };
 template <>
@@ -374,16 +387,10 @@ struct NormAcc<float> {
         a33 += J[3] * J[3];
         chi2 += r * r;
     }
-    template <typename F>
-    __device__ __forceinline__ void totals(FitNormEq<float, 5>& ne, F total) const {
-        ne.chi2 = total(chi2);
-        const float a[15] = {r0a.x, r0a.y, r0b.x, r0b.y, r0c.x, a11, r1b.x, r1b.y, r1c.x,
-                             r2b.x, r2b.y, r2c.x, a33, r3c.x, r4c.x};
-        const float g[5] = {r0c.y, r1c.y, r2c.y, r3c.y, r4c.y};
-#pragma unroll
-        for (int k = 0; k < 15; ++k) ne.a[k] = total(a[k]);
-#pragma unroll
-        for (int k = 0; k < 5; ++k) ne.g[k] = total(g[k]);
+    __device__ __forceinline__ void totals(FitNormEq<float, 5>& ne, int lane) const {
+        float t[21] = {chi2, r0a.x, r0a.y, r0b.x, r0b.y, r0c.x, a11, r1b.x, r1b.y, r1c.x,
+                       r2b.x, r2b.y, r2c.x, a33, r3c.x, r4c.x, r0c.y, r1c.y, r2c.y, r3c.y, r4c.y};
+        norm_totals(t, ne, lane);
     }
 };
 
@@ -438,7 +445,7 @@ __device__ __forceinline__ void moffat_accumulate(const RE* pix, int lane, const
         acc.add(J, r);
         }
     }
-    acc.totals(ne, [](RE x) { return wave_total(x); });
+    acc.totals(ne, lane);
 }
 
 #ifndef MPSFR_FIT_PAIRS
@@ -516,11 +523,13 @@ __device__ __forceinline__ void moffat_accumulate_pairs(const float* pix, int la
         pair(dpb * dpb + dq4sv, dpb, dq4v, f32x2{pl[16 * NS + 32], pl[24 * NS + 32]}, false);
         pair(f32x2{dp4 * dp4 + dq4s, 0.f}, f32x2{dp4, 0.f}, dq4v, f32x2{pl[32 * NS + 32], 0.f}, true);
     }
-    ne.chi2 = wave_total(C.x + C.y);
+    float t[21];
+    t[0] = C.x + C.y;
 #pragma unroll
-    for (int k = 0; k < 15; ++k) ne.a[k] = wave_total(A[k].x + A[k].y);
+    for (int k = 0; k < 15; ++k) t[1 + k] = A[k].x + A[k].y;
 #pragma unroll
-    for (int k = 0; k < 5; ++k) ne.g[k] = wave_total(G[k].x + G[k].y);
+    for (int k = 0; k < 5; ++k) t[16 + k] = G[k].x + G[k].y;
+    norm_totals(t, ne, lane);
 }
 
 // the float pass of the LM phase (pairs of pixels) / the generic pass
@@ -557,10 +566,12 @@ __device__ __forceinline__ RE moffat_chi2(const DT* pix, int lane, const double*
 // matrix the step is solved with, so the polish keeps the float normal matrix of the last LM
 // iteration (relative error ~1e-3: linear convergence at that rate) and only these five sums are
 // fp64 -- 10 accumulator registers instead of 42, which is what lets four waves share a SIMD.
+// `src`: the stamp in the type it is stored in -- the LDS copy of k_fit where that holds the same bits (float stamps),
+// global memory where it does not (double stamps: the residual needs the double pixels).
 
 template <typename TS>
 __device__ __forceinline__ void moffat_gradient(const TS* __restrict__ src, int lane,
-                                                const double* v, double* gout, double* chi2out) {
+                                                const double* v, double (&gout)[5], double* chi2out) {
     // Only the residual r = model - data needs fp64: a systematic 1e-6 error of the float
     // log/exp model is what biases the fit.  The Jacobian multiplies r, which is ~1e-3 of the
     // peak at the solution, so its float rounding (6e-8, unbiased) moves the fixed point by
@@ -600,7 +611,8 @@ __device__ __forceinline__ void moffat_gradient(const TS* __restrict__ src, int 
         }
     }
 #pragma unroll
-    for (int k = 0; k < 5; ++k) gout[k] = wave_total((double)g[k]);    // lanes cancel: fp64
+    for (int k = 0; k < 5; ++k) gout[k] = (double)g[k];                // lanes cancel: fp64
+    wave_totals(gout, lane);
     *chi2out = (double)wave_total(c2sum);
 }
 
@@ -636,6 +648,27 @@ struct SumArgs {
 #ifndef MPSFR_FIT_WG
 #define MPSFR_FIT_WG 1
 #endif
+// one step of the argmax of k_fit: the pair (value, offset) of the lane CTRL names against the lane's own
+template <int CTRL, typename TS>
+__device__ __forceinline__ void fit_argmax_step(TS& best, int& besto) {
+    const TS ob = dpp_pull<CTRL>(best);
+    const int oo = dpp_pull<CTRL>(besto);
+    if (ob > best || (ob == best && oo < besto)) { best = ob; besto = oo; }
+}
+// the same across rows, which hold one pair each: the rows (HALVES: the halves of the wave) are exchanged with
+// v_permlane16_swap (v_permlane32_swap), after which every lane has both pairs
+template <bool HALVES, typename TS>
+__device__ __forceinline__ void fit_argmax_rows(TS& best, int& besto) {
+    TS b0 = best, b1 = best;
+    float o0 = __builtin_bit_cast(float, besto), o1 = o0;
+    rows_swap<HALVES>(b0, b1);
+    rows_swap<HALVES>(o0, o1);
+    const int i0 = __builtin_bit_cast(int, o0), i1 = __builtin_bit_cast(int, o1);
+    const bool second = b1 > b0 || (b1 == b0 && i1 < i0);
+    best = second ? b1 : b0;
+    besto = second ? i1 : i0;
+}
+
 template <typename RE, typename TS>
 __global__ void __launch_bounds__(64 * MPSFR_FIT_WG) __attribute__((amdgpu_waves_per_eu(fit_min_waves<RE>())))
 k_fit(int nstamp, const TS* __restrict__ stamps, double* __restrict__ fit, double polish_tol, SumArgs sa) {
@@ -684,12 +717,16 @@ k_fit(int nstamp, const TS* __restrict__ stamps, double* __restrict__ fit, doubl
         if (d > best) { best = d; besto = o; }
     }
     // argmax (first maximum in C order, as np.argmax) and the pixel count above half maximum
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const TS ob = __shfl_xor(best, o, 64);
-        const int oo = __shfl_xor(besto, o, 64);
-        if (ob > best || (ob == best && oo < besto)) { best = ob; besto = oo; }
-    }
+    // On the DPP path, with the in-row steps of wave_total, then the rows against each other (the ds_bpermute shuffles
+    // this replaces were 12 to 18 dependent round trips through the LDS crossbar at the head of every stamp).
+    // (value, -offset) is a total order with distinct offsets, so the winner does not depend on the order of the
+    // comparisons, and no NaN enters it: every lane ends up with the same pair.
+    fit_argmax_step<0xB1>(best, besto);      // quad_perm [1,0,3,2]
+    fit_argmax_step<0x4E>(best, besto);      // quad_perm [2,3,0,1]
+    fit_argmax_step<0x141>(best, besto);     // row_half_mirror
+    fit_argmax_step<0x140>(best, besto);     // row_mirror
+    fit_argmax_rows<false>(best, besto);     // rows 0 | 1 and 2 | 3
+    fit_argmax_rows<true>(best, besto);      // the two halves: every lane holds the maximum of the wave
     // Start values.  The LM phase costs one pass over the stamp per iteration, so a start inside the
     // basin of quadratic convergence is worth a few hundred instructions of setup.  Moments of the
     // stamp over the largest disc around the brightest pixel that fits the stamp, R = (distance to the
@@ -733,11 +770,12 @@ k_fit(int nstamp, const TS* __restrict__ stamps, double* __restrict__ fit, doubl
             }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-    ms1 = wave_total(ms1);
-    ms2 = wave_total(ms2);
-    double fw0 = 2.0 * sqrt((double)cnt / kPi);
+    // (the count as a float: at most 1600, so its sums are exact)
+    float ms[3] = {ms1, ms2, (float)cnt};
+    wave_totals(ms, lane);
+    ms1 = ms[0];
+    ms2 = ms[1];
+    double fw0 = 2.0 * sqrt((double)ms[2] / kPi);
     fw0 = fmin(fmax(fw0, 1.5), (double)NS);
     float eta0 = 0.4f;
     if (MPSFR_FIT_MOMENT_START) fit_moment_start(ms1, ms2, (float)best, rm, &eta0, &fw0);
@@ -830,7 +868,8 @@ k_fit(int nstamp, const TS* __restrict__ stamps, double* __restrict__ fit, doubl
 #define MPSFR_POLISH_MAX 8
 #endif
         for (int pz = 0; pz < MPSFR_POLISH_MAX && status != 2; ++pz) {
-            moffat_gradient(src, lane, vd, np.g, &np.chi2);
+            if constexpr (std::is_same<TS, RE>::value) moffat_gradient(sp, lane, vd, np.g, &np.chi2);
+            else moffat_gradient(src, lane, vd, np.g, &np.chi2);
             double dx[5];
             if (!fit_lm_solve<5, double, double, true>(np, 1.0e-10, dx)) break;
             float rel = 0.f;               // a size, compared with 0.1 / 1e-3 / polish_tol: float
@@ -861,25 +900,31 @@ k_fit(int nstamp, const TS* __restrict__ stamps, double* __restrict__ fit, doubl
     // before the final point, so equal to first order) or, without a polish, a residual pass
     double chi2 = polish_chi2;
     if (chi2 < 0.0) chi2 = (double)moffat_chi2<RE>(sp, lane, va);
+    // The covariance: lane c solves column c of the inverse with the factor every lane holds (the five columns one
+    // after the other under lane == 0 were 370 instructions issued for one lane), and the six entries the row needs
+    // are read back: entry (k, c) is x[k] of lane c.
+    double colx[5];
+    const bool spd = fit_spd_inverse_column<5, RE, true>(ne, lane, colx);
+    const double cov00 = lane_value<0>(colx[0]), cov11 = lane_value<1>(colx[1]), cov22 = lane_value<2>(colx[2]),
+                 cov33 = lane_value<3>(colx[3]), cov34 = lane_value<4>(colx[3]), cov44 = lane_value<4>(colx[4]);
     if (lane == 0) {
         double* o = fit + (size_t)st * NFIT;
         o[0] = vd[0]; o[1] = vd[1]; o[2] = vd[2]; o[3] = al; o[4] = n;
         o[5] = fabs(vd[3]);
         o[6] = chi2;
         o[7] = (double)it;
-        double cov[5][5];
         const double dof = (double)(NS * NS - 5);
-        if (fit_spd_inverse<5, RE, true>(ne, cov)) {
+        if (spd) {
             const double s = chi2 / dof;
-            o[8] = sqrt(fmax(cov[0][0] * s, 0.0));
-            o[9] = sqrt(fmax(cov[1][1] * s, 0.0));
-            o[10] = sqrt(fmax(cov[2][2] * s, 0.0));
+            o[8] = sqrt(fmax(cov00 * s, 0.0));
+            o[9] = sqrt(fmax(cov11 * s, 0.0));
+            o[10] = sqrt(fmax(cov22 * s, 0.0));
             const double aw = 1.0 / (2.0 * sq);
             const double an = -al * p2 * 0.69314718055994530942 / (2.0 * s2);     // d alpha / d eta
-            const double var = aw * aw * cov[3][3] + 2.0 * aw * an * cov[3][4] + an * an * cov[4][4];
+            const double var = aw * aw * cov33 + 2.0 * aw * an * cov34 + an * an * cov44;
             o[11] = sqrt(fmax(var * s, 0.0));
-            o[12] = n * n * sqrt(fmax(cov[4][4] * s, 0.0));                        // |dn/d eta| = n^2
-            o[13] = sqrt(fmax(cov[3][3] * s, 0.0));
+            o[12] = n * n * sqrt(fmax(cov44 * s, 0.0));                        // |dn/d eta| = n^2
+            o[13] = sqrt(fmax(cov33 * s, 0.0));
             // Ill-conditioned fits (status bit 4, round 6).  With iid pixel noise of standard deviation sigma the
             // least-squares n has the standard deviation n^2 sqrt(cov[eta][eta]) sigma: the number below is that
             // for sigma = the peak, i.e. the change of n per unit of relative pixel noise.  From kFitIllCond = 100
@@ -888,7 +933,7 @@ k_fit(int nstamp, const TS* __restrict__ stamps, double* __restrict__ fit, doubl
             // (fwhm, n) to the tolerance.  Stamps narrower than the PSF core are the case: 256^2 / 128^2 grids
             // with the rescaled pixel scale (FWHM 30 px in a 40 px stamp: 180-200); the bench rows at 512^2 stay
             // below 8 (profiles/r06_small_grid_margin.txt).
-            if (n * n * sqrt(fmax(cov[4][4], 0.0)) * fabs(vd[0]) >= kFitIllCond) status |= 4;
+            if (n * n * sqrt(fmax(cov44, 0.0)) * fabs(vd[0]) >= kFitIllCond) status |= 4;
         } else {
             for (int k = 0; k < 6; ++k) o[8 + k] = 0.0;
             if (status == 0) status = 2;
