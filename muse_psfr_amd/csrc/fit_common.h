@@ -1,9 +1,14 @@
-// Device code shared by the Moffat fits (k_fit in stamps.hip, k_fit_ell in fit_ell.hip, k_fit_obs in fit_obs.hip):
-// wave-wide sums on the DPP path; the reciprocal, square-root, exp and log forms of the Levenberg-Marquardt
-// iterations and their fp64 polish; and, as templates over the number of variables NP, the normal equations
-// (FitNormEq), their Marquardt-scaled Cholesky factor, solve and inverse (fit_chol, fit_chol_solve, fit_lm_solve,
-// fit_spd_inverse), the wave-uniform factors of a model pass (MoffatPar), the moment start (fit_moment_start) and
-// the constants of the iteration.  Everything here has internal linkage.
+// Device code shared by the fit kernels (k_fit in stamps.hip, k_fit_ell in fit_ell.hip, k_fit_obs in fit_obs.hip,
+// k_fit_psf in fit_psf.hip, k_fit_group in fit_group_impl.h): wave-wide sums on the DPP path; the reciprocal,
+// square-root, exp and log forms of the Levenberg-Marquardt iterations and their fp64 polish; and, as templates over
+// the number of variables NP, the normal equations (FitNormEq), their Marquardt-scaled Cholesky factor, solve and
+// inverse (fit_chol, fit_chol_solve, fit_lm_solve, fit_spd_inverse), the damping and the predicted decrease
+// (FitDamping, fit_predicted_decrease), the trial point with the step limit on eta (fit_trial_point), the descent loop
+// over a kernel's Model (fit_lm_descend: k_fit, k_fit_ell, k_fit_obs, k_fit_psf; k_fit_group keeps its own loop over
+// its normal equations in LDS and shares the damping and the predicted decrease), the fp64 polish (fit_polish:
+// k_fit_ell, k_fit_obs, k_fit_psf), the wave-uniform factors of a Moffat model pass (MoffatPar), the moment start
+// (fit_moment_start), the derived values and error columns of the elliptical row layout (FitEllRow, fit_ell_errors:
+// k_fit_ell, k_fit_obs) and the constants of the iteration.  Everything here has internal linkage.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "device_common.h"
@@ -262,7 +267,7 @@ __device__ __forceinline__ double sgpr(double x) {
 }
 
 // ------------------------------------------------------------------------------------------
-// The Levenberg-Marquardt core of the three fits, over NP variables.
+// The Levenberg-Marquardt core of the fits, over NP variables.
 // ------------------------------------------------------------------------------------------
 
 constexpr double kFitIllCond = 100.0;       // MPSFR_FIT_ILL_CONDITIONED, include/mpsfr.h
@@ -272,6 +277,10 @@ constexpr double kFitMaxE = 0.95;           // |e| bound of the step acceptance 
 #endif
 constexpr int kFitMaxIt = MPSFR_FIT_MAXIT;  // cap of the LM iterations
 constexpr double kFitMu0 = 1.0e-2, kFitMuMax = 1.0e15;      // damping: start value, and where it gives up
+// the polish of the weighted fits (k_fit_obs, k_fit_psf, k_fit_group): the cap of its steps, and the fraction of the
+// formal error below which a step ends it
+constexpr int kFitPolishMax = 12;
+constexpr double kFitPolishSigma = 1.0e-6;
 
 template <typename T, int NP>
 struct FitNormEq {
@@ -397,6 +406,158 @@ __device__ __forceinline__ bool fit_spd_inverse_column(const FitNormEq<T, NP>& n
     return true;
 }
 
+// Nielsen's damping of the Marquardt-scaled system: a rejected step (or a matrix that is not positive definite)
+// multiplies mu by nu = 2, 4, 8, ...; an accepted one of gain ratio rho scales it by max(1/3, 1 - (2 rho - 1)^3).
+template <typename S>
+struct FitDamping {
+    S mu = (S)kFitMu0, nu = (S)2;
+    __device__ __forceinline__ bool raise() {       // true: the damping ran out
+        mu *= nu;
+        nu *= (S)2;
+        return mu > (S)kFitMuMax;
+    }
+    __device__ __forceinline__ void lower(S rho) {
+        const S c = (S)2 * rho - (S)1;
+        mu = fmax(mu * fmax((S)(1.0 / 3.0), (S)1 - c * c * c), (S)1.0e-14);
+        nu = (S)2;
+    }
+};
+
+// predicted decrease of chi2 by the step dx of the damped system: dx^T (mu D dx - g) (k_fit_group; fit_lm_descend
+// holds the same sum written out)
+template <int NP, typename S, typename T>
+__device__ __forceinline__ S fit_predicted_decrease(const FitNormEq<T, NP>& ne, S mu, const S* dx) {
+    S pred = (S)0;
+#pragma unroll
+    for (int k = 0; k < NP; ++k) pred += dx[k] * (mu * (S)ne.a[fit_diag<NP>(k)] * dx[k] - (S)ne.g[k]);
+    return pred;
+}
+
+// The trial point vn = v + dx.  With IETA >= 0 the step limit of the Moffat fits on eta = v[IETA] comes first: a stamp
+// narrower than the PSF core has no finite minimum in n, its valley runs to the Gaussian limit eta -> 0; a step may
+// cut eta to a fifth at most (the whole step is scaled), so the valley is descended geometrically instead of through
+// rejected steps.
+// The rounding is spelled out, because the rows are held to their bits: every vn[k] is the rounded sum of v[k] and the
+// rounded dx[k] -- except eta on a limited step, which is fma(sc, dx, v) with the dx before the scaling.  That is what
+// the compiler made of `dx *= sc; vn = v + dx` while the loop was written out in each kernel (it moved the sum of eta,
+// which the test of the limit needs, into the limiting branch and contracted it there); left to itself it contracts
+// other sums as well once the code around them changes.
+template <int NP, int IETA, typename S>
+__device__ __forceinline__ void fit_trial_point(const S* v, S* dx, S* vn) {
+#pragma clang fp contract(off)
+    if constexpr (IETA >= 0) {
+        S ve = v[IETA] + dx[IETA];
+        if (ve < (S)0.2 * v[IETA]) {
+            const S sc = (S)-0.8 * v[IETA] * fit_rcp<S>(dx[IETA]);
+            ve = fma(sc, dx[IETA], v[IETA]);
+#pragma unroll
+            for (int k = 0; k < NP; ++k) dx[k] *= sc;
+        }
+#pragma unroll
+        for (int k = 0; k < NP; ++k) vn[k] = k == IETA ? ve : v[k] + dx[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < NP; ++k) vn[k] = v[k] + dx[k];
+    }
+}
+
+// The Levenberg-Marquardt descent from v, whose normal equations are ne, for at most maxit iterations (counted in
+// `it`); returns the status: `status` if the iterations run out, 0 at a minimum, 2 if the matrix stays singular.
+// Model is the kernel's:
+//     NP, ROW_FIRST (fit_chol)           IETA: the index of eta, or -1             BOUNDED
+//     accumulate(v, ne)                  step_size(dx, vn)                          inside(vn)
+// IETA >= 0 (the Moffat fits): the step limit on eta, and the stop at eta < 1.5e-3 (n > 666: Gaussian to 1e-3).
+// BOUNDED (k_fit_psf): when the damping runs out after a step the domain refused, the fit rests on the bound of the
+// domain: not converged (1).  Otherwise a damping that runs out means no further descent: at the minimum.
+// The state is wave-uniform (the totals of a model pass are), so the control flow is.
+template <typename Model, typename S, typename RE>
+__device__ __forceinline__ int fit_lm_descend(const Model& m, S tol, int maxit, int status, S (&v)[Model::NP],
+                                              FitNormEq<RE, Model::NP>& ne, int& it) {
+    constexpr int NP = Model::NP;
+    FitDamping<S> damp;
+    bool bound = false;              // the last step was refused by the domain
+    while (it < maxit) {
+        ++it;
+        S dx[NP];
+        if (!fit_lm_solve<NP, S, RE, Model::ROW_FIRST>(ne, damp.mu, dx)) {
+            if (damp.raise()) { status = 2; break; }
+            continue;
+        }
+        S vn[NP];
+        fit_trial_point<NP, Model::IETA, S>(v, dx, vn);
+        const S rel = m.step_size(dx, vn);
+        const bool inside = m.inside(vn);
+        if (inside && rel < tol) {       // converged: take the last (tiny) Gauss-Newton step
+#pragma unroll
+            for (int k = 0; k < NP; ++k) v[k] = vn[k];
+            status = 0;
+            break;
+        }
+        FitNormEq<RE, NP> nn;
+        S rho = (S)-1;
+        if (inside) {
+            m.accumulate(vn, nn);
+            // fit_predicted_decrease, written out: through the function the wave sums that end the trial pass above
+            // were scheduled one after the other (100 to 260 s_nop more per iteration in k_fit_obs, none here)
+            S pred = (S)0;
+#pragma unroll
+            for (int k = 0; k < NP; ++k) pred += dx[k] * (damp.mu * (S)ne.a[fit_diag<NP>(k)] * dx[k] - (S)ne.g[k]);
+            rho = ((S)ne.chi2 - (S)nn.chi2) * fit_rcp<S>(pred);    // NaN -> rejected
+        }
+        if (rho > (S)0) {
+#pragma unroll
+            for (int k = 0; k < NP; ++k) v[k] = vn[k];
+            ne = nn;
+            bound = false;
+            if constexpr (Model::IETA >= 0) {
+                if (v[Model::IETA] < (S)1.5e-3) { status = 0; break; }
+            }
+            damp.lower(rho);
+        } else {
+            bound = !inside;
+            if (damp.raise()) { status = (Model::BOUNDED && bound) ? 1 : 0; break; }
+        }
+    }
+    return status;
+}
+
+// The fp64 polish of the mixed mode, from the float solution vd: steps -A^-1 g, g the gradient of the fp64 residuals
+// (P::gradient), A the float normal matrix of the last iteration (nf.a; the fixed point is where g vanishes, whatever
+// matrix the step is solved with).  A step that leaves the domain or is larger than 0.1 ends it untaken.  It ends after
+// a step below end.rel, or, where end.sigma > 0, below that fraction of the formal error: dx^T A dx <= sigma^2 chi2 /
+// dof.  Returns chi2 at the point before the last step when that step was below 1e-3 -- chi2 is stationary at the
+// minimum, so it differs from the value at the new point in second order only -- and -1 otherwise.  COUNT: the steps
+// count as iterations.  P is the kernel's: gradient(vd, g, &chi2), step_size(dx, vn), inside(vn).
+struct FitPolishEnd {
+    int maxsteps;
+    double rel;                  // a step below this relative size ends the polish
+    double sigma = 0.0, dof = 1.0;
+};
+template <int NP, bool COUNT, typename P>
+__device__ __forceinline__ double fit_polish(const P& p, const FitPolishEnd& end, FitNormEq<double, NP>& nf,
+                                             double (&vd)[NP], int status, int& it) {
+    double chi2 = -1.0;
+    nf.chi2 = -1.0;
+    for (int pz = 0; pz < end.maxsteps && status != 2; ++pz) {
+        p.gradient(vd, nf.g, &nf.chi2);
+        double dx[NP], vn[NP];
+        if (!fit_lm_solve<NP, double, double>(nf, 1.0e-10, dx)) break;
+#pragma unroll
+        for (int k = 0; k < NP; ++k) vn[k] = vd[k] + dx[k];
+        const double rel = p.step_size(dx, vn);
+        if (!p.inside(vn) || rel >= 0.1) break;
+        double d2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < NP; ++k) d2 -= dx[k] * nf.g[k];
+#pragma unroll
+        for (int k = 0; k < NP; ++k) vd[k] = vn[k];
+        if constexpr (COUNT) ++it;
+        chi2 = rel < 1.0e-3 ? nf.chi2 : -1.0;
+        if (rel < end.rel || (end.sigma > 0.0 && d2 <= end.sigma * end.sigma * nf.chi2 / end.dof)) break;
+    }
+    return chi2;
+}
+
 // Wave-uniform factors of a model pass at v = (I, p0, q0, w, [e1, e2,] eta at ieta, ...).  With
 // K = 1/a^2 = 4 (2^eta - 1) / w^2:  Q = A x^2 - 2 B x y + C y^2, A = gK (1 - e1), B = gK e2, C = gK (1 + e1),
 // g = 1 / sqrt(1 - e1^2 - e2^2); the circular model has A = C = K, B = 0.
@@ -451,6 +612,92 @@ __device__ __forceinline__ bool fit_moment_start(float ms1, float ms2, float bes
     const float w = 2.f * __builtin_amdgcn_sqrtf(a2 * (__builtin_amdgcn_exp2f(*eta0) - 1.f));
     if (w == w) *fw0 = fmin(fmax((double)w, 1.5), (double)NS);
     return true;
+}
+
+
+// The derived values of a row of the elliptical layout (k_fit_ell, k_fit_obs) at v = (I, p0, q0, w, [e1, e2,] eta at
+// ieta, ...): n = 1/eta, alpha = w / (2 sqrt(2^eta - 1)); with e = |(e1, e2)| and f = ((1 + e)/(1 - e))^(1/4) the
+// semi-axes are alpha f and alpha / f, the FWHMs w f and w / f, the major axis at rot = atan2(e2, e1) / 2 (degrees in
+// [0, 180)); flux = I pi alpha^2 / (n - 1).  Without ELL: e = 0, f = 1, rot = 0.
+template <bool ELL>
+struct FitEllRow {
+    double I, w, e1, e2, n, p2, s2, al, esq, e, f, rot, flux;
+    __device__ __forceinline__ FitEllRow(const double* vd, int ieta) {
+        I = vd[0]; w = vd[3];
+        e1 = 0.0; e2 = 0.0;
+        if constexpr (ELL) { e1 = vd[4]; e2 = vd[5]; }
+        const double eta = vd[ieta];
+        n = 1.0 / eta;
+        p2 = exp2(eta); s2 = p2 - 1.0;
+        const double sq = sqrt(s2);
+        al = w / (2.0 * sq);
+        esq = e1 * e1 + e2 * e2; e = sqrt(esq);
+        f = ELL ? sqrt(sqrt((1.0 + e) / (1.0 - e))) : 1.0;
+        rot = 0.0;
+        if constexpr (ELL) {
+            rot = 0.5 * atan2(e2, e1) * (180.0 / kPi);
+            if (rot < 0.0) rot += 180.0;
+            if (rot >= 180.0) rot -= 180.0;
+        }
+        flux = I * kPi * al * al / (n - 1.0);
+    }
+    // columns 3 .. 8 and 19; `up`: the amplitude scale of the row (a power of two)
+    __device__ __forceinline__ void write(double* o, double up) const {
+        o[3] = al * f; o[4] = al / f; o[5] = n; o[6] = rot;
+        o[7] = w * f; o[8] = w / f;
+        o[19] = flux * up;
+    }
+};
+
+// The error columns of that layout from the covariance cov * s of the variables, propagated to first order: o[11 ..
+// 17] the errors of I, p0, q0, the two FWHMs, rot (degrees; undetermined for e -> 0: capped at 180) and n, o[20] that
+// of the flux; o[11] and o[20] times `up`, the amplitude scale of the row (a power of two).
+template <int NP, int IETA, bool ELL>
+__device__ __forceinline__ void fit_ell_errors(const FitEllRow<ELL>& r, const double (&cov)[NP][NP], double s,
+                                               double up, double* o) {
+    auto quad = [&](const double* gr) {       // s g^T cov g over the variables of gr (NP entries)
+        double q = 0.0;
+#pragma unroll
+        for (int i = 0; i < NP; ++i)
+#pragma unroll
+            for (int j = 0; j < NP; ++j) q += gr[i] * cov[i][j] * gr[j];
+        return sqrt(fmax(q * s, 0.0));
+    };
+    o[11] = sqrt(fmax(cov[0][0] * s, 0.0)) * up;
+    o[12] = sqrt(fmax(cov[1][1] * s, 0.0));
+    o[13] = sqrt(fmax(cov[2][2] * s, 0.0));
+    if constexpr (ELL) {
+        const double ue1 = r.e > 0.0 ? r.e1 / r.e : 1.0, ue2 = r.e > 0.0 ? r.e2 / r.e : 0.0;
+        const double h = 0.5 / (1.0 - r.esq);                  // d ln f / d e
+        double gmaj[NP], gmin[NP], grot[NP];
+#pragma unroll
+        for (int k = 0; k < NP; ++k) { gmaj[k] = 0.0; gmin[k] = 0.0; grot[k] = 0.0; }
+        gmaj[3] = r.f; gmaj[4] = r.w * r.f * h * ue1; gmaj[5] = r.w * r.f * h * ue2;
+        gmin[3] = 1.0 / r.f; gmin[4] = -r.w / r.f * h * ue1; gmin[5] = -r.w / r.f * h * ue2;
+        o[14] = quad(gmaj);
+        o[15] = quad(gmin);
+        // rot: d/de1 = -e2 / (2 e^2), d/de2 = e1 / (2 e^2)
+        double erot = 180.0;
+        if (r.esq > 0.0) {
+            grot[4] = -0.5 * r.e2 / r.esq; grot[5] = 0.5 * r.e1 / r.esq;
+            erot = fmin(quad(grot) * (180.0 / kPi), 180.0);
+            if (!(erot == erot)) erot = 180.0;
+        }
+        o[16] = erot;
+    } else {
+        o[14] = sqrt(fmax(cov[3][3] * s, 0.0));
+        o[15] = o[14];
+        o[16] = 0.0;
+    }
+    o[17] = r.n * r.n * sqrt(fmax(cov[IETA][IETA] * s, 0.0));          // |dn/d eta| = n^2
+    // flux = I pi w^2 / (4 (2^eta - 1) (n - 1))
+    double gfl[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) gfl[k] = 0.0;
+    gfl[0] = kPi * r.al * r.al / (r.n - 1.0);
+    gfl[3] = 2.0 * r.flux / r.w;
+    gfl[IETA] = r.flux * (r.n * r.n / (r.n - 1.0) - r.p2 * 0.69314718055994530942 / r.s2);
+    o[20] = quad(gfl) * up;
 }
 
 }  // namespace

@@ -9,8 +9,9 @@
 // The structure is k_fit's: one wave per stamp with the stamp in LDS, wave-wide sums on the DPP path, wave-uniform
 // Levenberg-Marquardt state (Marquardt scaling, Nielsen's damping update) in the variables
 // (I, p0, q0, w = geometric-mean FWHM, e1, e2, eta = 1/n).  The normal equations, their factorisation, solve and
-// inverse, the model factors (MoffatPar), the moment start and the constants are fit_common.h's, shared by the
-// three fits.  Mixed mode: float iterations, then the fp64 gradient
+// inverse, the descent loop and the polish (fit_lm_descend, fit_polish over EllModel), the model factors (MoffatPar),
+// the moment start, the error columns of the row (fit_ell_errors) and the constants are fit_common.h's, shared by the
+// fit kernels.  Mixed mode: float iterations, then the fp64 gradient
 // polish with the last normal matrix; f64 mode: fp64 iterations throughout.
 #include "device_common.h"
 #include "fit_common.h"
@@ -169,6 +170,26 @@ __device__ __forceinline__ bool ell_inside(const S* vn) {
            vn[4] * vn[4] + vn[5] * vn[5] <= (S)(kFitMaxE * kFitMaxE);
 }
 
+// what fit_lm_descend and fit_polish need of this fit (fit_common.h)
+template <typename RE>
+struct EllModel {
+    static constexpr int NP = NPE, IETA = 6;
+    static constexpr bool ROW_FIRST = false, BOUNDED = false;
+    const RE* sp;               // the stamp in LDS
+    const double* src;          // and in memory
+    int lane;
+    __device__ __forceinline__ void accumulate(const RE* v, FitNormEq<RE, NPE>& ne) const {
+        ell_accumulate<RE>(sp, lane, v, ne);
+    }
+    __device__ __forceinline__ void gradient(const double* v, double* g, double* chi2) const {
+        ell_gradient(src, lane, v, g, chi2);
+    }
+    template <typename S>
+    __device__ __forceinline__ S step_size(const S* dx, const S* vn) const { return ell_step_size<S>(dx, vn); }
+    template <typename S>
+    __device__ __forceinline__ bool inside(const S* vn) const { return ell_inside<S>(vn); }
+};
+
 // one wave per stamp; RE = float: mixed mode (float iterations + fp64 polish), RE = double: f64 mode
 template <typename RE>
 __global__ void __launch_bounds__(64)
@@ -259,86 +280,21 @@ k_fit_ell(int nstamp, const double* __restrict__ stamps, double* __restrict__ fi
     }
     S v[NPE] = {(S)best, (S)p0i, (S)q0i, (S)fw0, (S)e10, (S)e20, (S)eta0};
     const S tol = sizeof(RE) == 4 ? (S)1.0e-3 : (S)1.0e-10;
+    const EllModel<RE> model{sp, src, lane};
     FitNormEq<RE, NPE> ne;
-    ell_accumulate<RE>(sp, lane, v, ne);
-    S mu = (S)kFitMu0, nu = (S)2;
-    const S mu_max = (S)kFitMuMax;
-    int it = 0, status = amp_ok ? 1 : 2;
-    const int maxit = amp_ok ? kFitMaxIt : 0;
-    while (it < maxit) {
-        ++it;
-        S dx[NPE];
-        if (!fit_lm_solve<NPE, S, RE>(ne, mu, dx)) {
-            mu *= nu;
-            nu *= (S)2;
-            if (mu > mu_max) { status = 2; break; }
-            continue;
-        }
-        // the step limit of k_fit on eta: a step may cut eta to a fifth at most (the whole step is scaled)
-        if (v[6] + dx[6] < (S)0.2 * v[6]) {
-            const S sc = (S)-0.8 * v[6] * fit_rcp<S>(dx[6]);
-#pragma unroll
-            for (int k = 0; k < NPE; ++k) dx[k] *= sc;
-        }
-        S vn[NPE];
-#pragma unroll
-        for (int k = 0; k < NPE; ++k) vn[k] = v[k] + dx[k];
-        const S rel = ell_step_size<S>(dx, vn);
-        const bool inside = ell_inside<S>(vn);
-        if (inside && rel < tol) {       // converged: take the last (tiny) Gauss-Newton step
-#pragma unroll
-            for (int k = 0; k < NPE; ++k) v[k] = vn[k];
-            status = 0;
-            break;
-        }
-        FitNormEq<RE, NPE> nn;
-        S rho = (S)-1;
-        if (inside) {
-            ell_accumulate<RE>(sp, lane, vn, nn);
-            S pred = (S)0;         // predicted decrease of chi2: dx^T (mu D dx - g)
-#pragma unroll
-            for (int k = 0; k < NPE; ++k) pred += dx[k] * (mu * (S)ne.a[fit_diag<NPE>(k)] * dx[k] - (S)ne.g[k]);
-            rho = ((S)ne.chi2 - (S)nn.chi2) * fit_rcp<S>(pred);    // NaN -> rejected
-        }
-        if (rho > (S)0) {
-#pragma unroll
-            for (int k = 0; k < NPE; ++k) v[k] = vn[k];
-            ne = nn;
-            if (v[6] < (S)1.5e-3) { status = 0; break; }      // n > 666: Gaussian to 1e-3, stop
-            const S c = (S)2 * rho - (S)1;
-            mu = fmax(mu * fmax((S)(1.0 / 3.0), (S)1 - c * c * c), (S)1.0e-14);
-            nu = (S)2;
-        } else {
-            mu *= nu;
-            nu *= (S)2;
-            if (mu > mu_max) { status = 0; break; }   // no further descent: at the minimum
-        }
-    }
+    model.accumulate(v, ne);
+    int it = 0;
+    int status = fit_lm_descend<EllModel<RE>, S, RE>(model, tol, amp_ok ? kFitMaxIt : 0, amp_ok ? 1 : 2, v, ne, it);
     double vd[NPE];
 #pragma unroll
     for (int k = 0; k < NPE; ++k) vd[k] = (double)v[k];
     double chi2 = -1.0;
     if constexpr (sizeof(RE) == 4) {
-        // the fp64 polish of k_fit: steps -A^-1 g, g the fp64 gradient, A the float normal matrix of the last
-        // iteration
+        // the fp64 polish of k_fit: the float normal matrix of the last iteration, steps until one is below polish_tol
         FitNormEq<double, NPE> np;
 #pragma unroll
         for (int k = 0; k < NAE; ++k) np.a[k] = (double)ne.a[k];
-        np.chi2 = -1.0;
-        for (int pz = 0; pz < kEllPolishMax && status != 2; ++pz) {
-            ell_gradient(src, lane, vd, np.g, &np.chi2);
-            double dx[NPE], vn[NPE];
-            if (!fit_lm_solve<NPE, double, double>(np, 1.0e-10, dx)) break;
-#pragma unroll
-            for (int k = 0; k < NPE; ++k) vn[k] = vd[k] + dx[k];
-            const double rel = ell_step_size<double>(dx, vn);
-            if (!ell_inside<double>(vn) || rel >= 0.1) break;
-#pragma unroll
-            for (int k = 0; k < NPE; ++k) vd[k] = vn[k];
-            ++it;
-            chi2 = rel < 1.0e-3 ? np.chi2 : -1.0;
-            if (rel < polish_tol) break;
-        }
+        chi2 = fit_polish<NPE, true>(model, FitPolishEnd{kEllPolishMax, polish_tol}, np, vd, status, it);
         if (chi2 < 0.0) {              // a residual pass at the final point, in fp64
             double cs = 0.0;
             {
@@ -367,59 +323,18 @@ k_fit_ell(int nstamp, const double* __restrict__ stamps, double* __restrict__ fi
     // semi-axes are alpha f and alpha / f, the FWHMs w f and w / f, the major axis at rot = atan2(e2, e1) / 2.
     // The covariance is the inverse of the normal matrix of the last iteration times chi2 / (npix - 7); the
     // errors of derived values are propagated to first order.
-    const double I = vd[0], w = vd[3], e1 = vd[4], e2 = vd[5], eta = vd[6];
-    const double n = 1.0 / eta;
-    const double p2 = exp2(eta), s2 = p2 - 1.0, sq = sqrt(s2);
-    const double al = w / (2.0 * sq);
-    const double esq = e1 * e1 + e2 * e2, e = sqrt(esq);
-    const double f = sqrt(sqrt((1.0 + e) / (1.0 - e)));
-    double rot = 0.5 * atan2(e2, e1) * (180.0 / kPi);
-    if (rot < 0.0) rot += 180.0;
-    if (rot >= 180.0) rot -= 180.0;
-    const double flux = I * kPi * al * al / (n - 1.0);
+    const FitEllRow<true> r(vd, 6);
     double o[NFIT_ELL];                 // the row, in registers until the status is known
-    o[0] = I; o[1] = vd[1]; o[2] = vd[2];
-    o[3] = al * f; o[4] = al / f; o[5] = n; o[6] = rot;
-    o[7] = w * f; o[8] = w / f;
+    o[0] = vd[0]; o[1] = vd[1]; o[2] = vd[2];
+    r.write(o, 1.0);
     o[9] = chi2;
     o[10] = (double)it;
-    o[19] = flux;
 #pragma unroll
     for (int k = 21; k < NFIT_ELL; ++k) o[k] = 0.0;
     double cov[NPE][NPE];
     if (fit_spd_inverse<NPE, RE>(ne, cov)) {
-        const double s = chi2 / (double)(NS * NS - NPE);
-        auto quad = [&](const double* gr) {       // s g^T cov g over the variables of gr (7 entries)
-            double q = 0.0;
-#pragma unroll
-            for (int i = 0; i < NPE; ++i)
-#pragma unroll
-                for (int j = 0; j < NPE; ++j) q += gr[i] * cov[i][j] * gr[j];
-            return sqrt(fmax(q * s, 0.0));
-        };
-        const double ue1 = e > 0.0 ? e1 / e : 1.0, ue2 = e > 0.0 ? e2 / e : 0.0;
-        const double h = 0.5 / (1.0 - esq);                  // d ln f / d e
-        const double gmaj[NPE] = {0, 0, 0, f, w * f * h * ue1, w * f * h * ue2, 0};
-        const double gmin[NPE] = {0, 0, 0, 1.0 / f, -w / f * h * ue1, -w / f * h * ue2, 0};
-        o[11] = sqrt(fmax(cov[0][0] * s, 0.0));
-        o[12] = sqrt(fmax(cov[1][1] * s, 0.0));
-        o[13] = sqrt(fmax(cov[2][2] * s, 0.0));
-        o[14] = quad(gmaj);
-        o[15] = quad(gmin);
-        // rot: d/de1 = -e2 / (2 e^2), d/de2 = e1 / (2 e^2); undetermined (e -> 0): capped at 180 degrees
-        double erot = 180.0;
-        if (esq > 0.0) {
-            const double grot[NPE] = {0, 0, 0, 0, -0.5 * e2 / esq, 0.5 * e1 / esq, 0};
-            erot = fmin(quad(grot) * (180.0 / kPi), 180.0);
-            if (!(erot == erot)) erot = 180.0;
-        }
-        o[16] = erot;
-        o[17] = n * n * sqrt(fmax(cov[6][6] * s, 0.0));          // |dn/d eta| = n^2
-        // flux = I pi w^2 / (4 (2^eta - 1) (n - 1))
-        const double gfl[NPE] = {kPi * al * al / (n - 1.0), 0, 0, 2.0 * flux / w, 0, 0,
-                                 flux * (n * n / (n - 1.0) - p2 * 0.69314718055994530942 / s2)};
-        o[20] = quad(gfl);
-        if (n * n * sqrt(fmax(cov[6][6], 0.0)) * fabs(I) >= kFitIllCond) status |= 4;
+        fit_ell_errors<NPE, 6, true>(r, cov, chi2 / (double)(NS * NS - NPE), 1.0, o);
+        if (r.n * r.n * sqrt(fmax(cov[6][6], 0.0)) * fabs(r.I) >= kFitIllCond) status |= 4;
     } else {
 #pragma unroll
         for (int k = 11; k <= 17; ++k) o[k] = 0.0;
@@ -437,7 +352,7 @@ k_fit_ell(int nstamp, const double* __restrict__ stamps, double* __restrict__ fi
     for (int k = 0; k < NFIT_ELL; ++k)
         if (k != 18) finite = finite && fabs(o[k]) < __builtin_inf();
     if ((status & 3) == 0 && !finite) status = (status & 4) | 2;
-    if ((status & 3) == 0 && (eta > 90.0 || esq > (kFitMaxE - 0.01) * (kFitMaxE - 0.01))) status = (status & 4) | 1;
+    if ((status & 3) == 0 && (vd[6] > 90.0 || r.esq > (kFitMaxE - 0.01) * (kFitMaxE - 0.01))) status = (status & 4) | 1;
     o[18] = (double)status;
     double* row = fit + (size_t)st * NFIT_ELL;
 #pragma unroll

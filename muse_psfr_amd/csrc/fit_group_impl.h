@@ -475,24 +475,19 @@ k_fit_group(int nstamp, const double* __restrict__ stamps, const double* __restr
     if constexpr (MODE != GRP_FIXED) {
         grp_accumulate<RE, RE, K, MODE, BG>(sp, sw, pl, lane, Point(v, s0), sne);
         const S tol = sizeof(RE) == 4 ? (S)1.0e-3 : (S)1.0e-12;
-        S mu = (S)kFitMu0, nu = (S)2;
-        const S mu_max = (S)kFitMuMax;
+        FitDamping<S> damp;
         bool bound = false;              // the last step was refused by the domain
         while (it < kFitMaxIt) {
             ++it;
-            S dx[NP], pred = (S)0, chi2_cur;
+            S dx[NP], pred, chi2_cur;
             {
                 FitNormEq<RE, NP> ne;
                 grp_load<true>(sne + cur * NE, ne);
-                if (!fit_lm_solve<NP, S, RE>(ne, mu, dx)) {
-                    mu *= nu;
-                    nu *= (S)2;
-                    if (mu > mu_max) { status = 2; break; }
+                if (!fit_lm_solve<NP, S, RE>(ne, damp.mu, dx)) {
+                    if (damp.raise()) { status = 2; break; }
                     continue;
                 }
-                // predicted decrease of chi2: dx^T (mu D dx - g)
-#pragma unroll
-                for (int k = 0; k < NP; ++k) pred += dx[k] * (mu * (S)ne.a[fit_diag<NP>(k)] * dx[k] - (S)ne.g[k]);
+                pred = fit_predicted_decrease<NP, S, RE>(ne, damp.mu, dx);
                 chi2_cur = (S)ne.chi2;
             }
             S vn[NP];
@@ -518,15 +513,11 @@ k_fit_group(int nstamp, const double* __restrict__ stamps, const double* __restr
                 for (int k = 0; k < NP; ++k) v[k] = vn[k];
                 cur ^= 1;
                 bound = false;
-                const S c = (S)2 * rho - (S)1;
-                mu = fmax(mu * fmax((S)(1.0 / 3.0), (S)1 - c * c * c), (S)1.0e-14);
-                nu = (S)2;
+                damp.lower(rho);
             } else {
                 bound = !inside;
-                mu *= nu;
-                nu *= (S)2;
                 // no further descent: at the minimum, or against the bound of a position
-                if (mu > mu_max) { status = bound ? 1 : 0; break; }
+                if (damp.raise()) { status = bound ? 1 : 0; break; }
             }
         }
         // a fit that rests on the bound of a position has not found a minimum
@@ -541,13 +532,13 @@ k_fit_group(int nstamp, const double* __restrict__ stamps, const double* __restr
     const double* serr = nullptr;            // the fp64 normal matrix of the covariance
     if constexpr (sizeof(RE) == 4) {
         // the fp64 polish of k_fit_psf: steps -A^-1 g, g the gradient of the fp64 residuals, A the float normal matrix
-        // of the last iteration; it ends once a step is below kPsfPolishSigma of the formal error
-        for (int pz = 0; pz <= kPsfPolishMax && status != 2; ++pz) {
+        // of the last iteration; it ends once a step is below kFitPolishSigma of the formal error
+        for (int pz = 0; pz <= kFitPolishMax && status != 2; ++pz) {
             FitNormEq<double, NP> nf;
             grp_gradient<K, MODE, BG>(src, scale, psrc, pscale, sw, lane, GrpPoint<K, MODE, BG, double>(vd, s0), nf.g,
                                       &nf.chi2);
             chi2 = nf.chi2;                  // the residuals at the current point
-            if (pz == kPsfPolishMax) break;
+            if (pz == kFitPolishMax) break;
             grp_load<false>(sa, nf);
             double dx[NP], vn[NP];
             if (!fit_lm_solve<NP, double, double>(nf, 1.0e-10, dx)) break;
@@ -563,7 +554,7 @@ k_fit_group(int nstamp, const double* __restrict__ stamps, const double* __restr
             if constexpr (MODE != GRP_FIXED) ++it;
             // chi2 belongs to the point before this step: chi2 is stationary at the minimum, so after a step of `rel`
             // it differs from the value at the new point in second order only
-            if (rel < 1.0e-3 && (rel < 1.0e-9 || d2 <= kPsfPolishSigma * kPsfPolishSigma * chi2 / dof)) break;
+            if (rel < 1.0e-3 && (rel < 1.0e-9 || d2 <= kFitPolishSigma * kFitPolishSigma * chi2 / dof)) break;
         }
         if (status != 2) {
             // one fp64 pass for the normal matrix of the errors (its gradient and chi2 are not used: they would come

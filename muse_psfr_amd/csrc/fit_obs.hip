@@ -10,7 +10,8 @@
 // on the DPP path (wave_total), wave-uniform Levenberg-Marquardt state (Marquardt scaling, Nielsen's damping) in the
 // variables (I, p0, q0, w, [e1, e2,] eta = 1/n, [b]): 5 to 8 of them, chosen at compile time.  The normal equations,
 // their factorisation, solve and inverse, the model factors (MoffatPar) and the constants are fit_common.h's, shared
-// by the three fits.  New here: the weight
+// by the fit kernels, as are the descent loop and the polish (fit_lm_descend, fit_polish over ObsModel) and the error
+// columns of the row (fit_ell_errors).  New here: the weight
 // plane beside the stamp in LDS, the start values from used pixels only, and the normalisation of data and weights by
 // powers of two (brightest used pixel into [1, 2), largest weight into (1/2, 1]), which is exact and makes a constant
 // factor on the variance plane change no bit of the parameters and errors.
@@ -24,8 +25,6 @@ namespace mpsfr {
 
 namespace {
 
-constexpr int kObsPolishMax = 12;
-constexpr double kObsPolishSigma = 1.0e-6;   // the polish stops at a step of this fraction of the formal error
 constexpr double kObsMinWeight = 0x1p-100;   // a used pixel keeps a weight > 0 (relative to the largest one)
 constexpr int FLAG_BACKGROUND = 1, FLAG_ELLIPTICAL = 2;      // MPSFR_FIT_BACKGROUND / MPSFR_FIT_ELLIPTICAL
 
@@ -233,6 +232,29 @@ __device__ __forceinline__ bool obs_inside(const S* vn) {
     return in;
 }
 
+// what fit_lm_descend and fit_polish need of this fit (fit_common.h)
+template <typename RE, bool ELL, bool BG>
+struct ObsModel {
+    using D = ObsDim<ELL, BG>;
+    static constexpr int NP = D::NP, IETA = D::IETA;
+    static constexpr bool ROW_FIRST = false, BOUNDED = false;
+    const RE *sp, *sw;          // the stamp and its weights in LDS
+    const double* src;          // the stamp in memory, and the power of two of its normalisation
+    double scale;
+    int lane;
+    __device__ __forceinline__ void accumulate(const RE* v, FitNormEq<RE, NP>& ne) const {
+        obs_accumulate<RE, RE, ELL, BG>(sp, sw, lane, v, ne);
+    }
+    __device__ __forceinline__ void gradient(const double* v, double* g, double* chi2) const {
+        static_assert(sizeof(RE) == 4, "the fp64-residual gradient belongs to the mixed mode");
+        obs_gradient<ELL, BG>(src, scale, sw, lane, v, g, chi2);
+    }
+    template <typename S>
+    __device__ __forceinline__ S step_size(const S* dx, const S* vn) const { return obs_step_size<ELL, BG, S>(dx, vn); }
+    template <typename S>
+    __device__ __forceinline__ bool inside(const S* vn) const { return obs_inside<ELL, BG, S>(vn); }
+};
+
 // the validity of a pixel and its weight before the normalisation (1 / var, or 1 without a variance plane)
 struct ObsPixel {
     bool used, bad;       // bad: an infinite value under a valid variance (the row gets status 2)
@@ -374,60 +396,11 @@ k_fit_obs(int nstamp, const double* __restrict__ stamps, const double* __restric
     v[D::IETA] = (S)0.4;
     if constexpr (BG) v[D::IB] = (S)b0;
     const S tol = sizeof(RE) == 4 ? (S)1.0e-3 : (S)1.0e-12;
+    const ObsModel<RE, ELL, BG> model{sp, sw, src, scale, lane};
     FitNormEq<RE, NP> ne;
-    obs_accumulate<RE, RE, ELL, BG>(sp, sw, lane, v, ne);
-    S mu = (S)kFitMu0, nu = (S)2;
-    const S mu_max = (S)kFitMuMax;
-    int it = 0, status = 1;
-    while (it < kFitMaxIt) {
-        ++it;
-        S dx[NP];
-        if (!fit_lm_solve<NP, S, RE>(ne, mu, dx)) {
-            mu *= nu;
-            nu *= (S)2;
-            if (mu > mu_max) { status = 2; break; }
-            continue;
-        }
-        // the step limit of k_fit on eta: a step may cut eta to a fifth at most (the whole step is scaled)
-        if (v[D::IETA] + dx[D::IETA] < (S)0.2 * v[D::IETA]) {
-            const S sc = (S)-0.8 * v[D::IETA] * fit_rcp<S>(dx[D::IETA]);
-#pragma unroll
-            for (int k = 0; k < NP; ++k) dx[k] *= sc;
-        }
-        S vn[NP];
-#pragma unroll
-        for (int k = 0; k < NP; ++k) vn[k] = v[k] + dx[k];
-        const S rel = obs_step_size<ELL, BG, S>(dx, vn);
-        const bool inside = obs_inside<ELL, BG, S>(vn);
-        if (inside && rel < tol) {       // converged: take the last (tiny) Gauss-Newton step
-#pragma unroll
-            for (int k = 0; k < NP; ++k) v[k] = vn[k];
-            status = 0;
-            break;
-        }
-        FitNormEq<RE, NP> nn;
-        S rho = (S)-1;
-        if (inside) {
-            obs_accumulate<RE, RE, ELL, BG>(sp, sw, lane, vn, nn);
-            S pred = (S)0;         // predicted decrease of chi2: dx^T (mu D dx - g)
-#pragma unroll
-            for (int k = 0; k < NP; ++k) pred += dx[k] * (mu * (S)ne.a[fit_diag<NP>(k)] * dx[k] - (S)ne.g[k]);
-            rho = ((S)ne.chi2 - (S)nn.chi2) * fit_rcp<S>(pred);    // NaN -> rejected
-        }
-        if (rho > (S)0) {
-#pragma unroll
-            for (int k = 0; k < NP; ++k) v[k] = vn[k];
-            ne = nn;
-            if (v[D::IETA] < (S)1.5e-3) { status = 0; break; }      // n > 666: Gaussian to 1e-3, stop
-            const S c = (S)2 * rho - (S)1;
-            mu = fmax(mu * fmax((S)(1.0 / 3.0), (S)1 - c * c * c), (S)1.0e-14);
-            nu = (S)2;
-        } else {
-            mu *= nu;
-            nu *= (S)2;
-            if (mu > mu_max) { status = 0; break; }   // no further descent: at the minimum
-        }
-    }
+    model.accumulate(v, ne);
+    int it = 0;
+    int status = fit_lm_descend<ObsModel<RE, ELL, BG>, S, RE>(model, tol, kFitMaxIt, 1, v, ne, it);
     const double dof = (double)(nused - NP);
     double vd[NP];
 #pragma unroll
@@ -437,35 +410,14 @@ k_fit_obs(int nstamp, const double* __restrict__ stamps, const double* __restric
     // nf.chi2, the mixed mode uses them inside its polish only)
     FitNormEq<double, NP> nf;
     if constexpr (sizeof(RE) == 4) {
-        // the fp64 polish of k_fit_ell: steps -A^-1 g, g the gradient of the fp64 residuals, A the float normal matrix
-        // of the last iteration; it ends once a step is below kObsPolishSigma of the formal error,
-        // dx^T A dx <= kObsPolishSigma^2 chi2 / dof (or below 1e-9 relative on a stamp the model fits exactly)
+        // the fp64 polish with the float normal matrix of the last iteration; it ends once a step is below
+        // kFitPolishSigma of the formal error (or below 1e-9 relative on a stamp the model fits exactly)
 #pragma unroll
         for (int k = 0; k < NA; ++k) nf.a[k] = (double)ne.a[k];
-        nf.chi2 = -1.0;
-        for (int pz = 0; pz < kObsPolishMax && status != 2; ++pz) {
-            obs_gradient<ELL, BG>(src, scale, sw, lane, vd, nf.g, &nf.chi2);
-            double dx[NP], vn[NP];
-            if (!fit_lm_solve<NP, double, double>(nf, 1.0e-10, dx)) break;
-#pragma unroll
-            for (int k = 0; k < NP; ++k) vn[k] = vd[k] + dx[k];
-            const double rel = obs_step_size<ELL, BG, double>(dx, vn);
-            if (!obs_inside<ELL, BG, double>(vn) || rel >= 0.1) break;
-            double d2 = 0.0;
-#pragma unroll
-            for (int k = 0; k < NP; ++k) d2 -= dx[k] * nf.g[k];
-#pragma unroll
-            for (int k = 0; k < NP; ++k) vd[k] = vn[k];
-            ++it;
-            // nf.chi2 belongs to the point before this step: chi2 is stationary at the minimum, so after a step of
-            // `rel` it differs from the value at the new point in second order only (dx^T A dx, 1e-12 chi2 / dof at the
-            // step that ends the polish)
-            chi2 = rel < 1.0e-3 ? nf.chi2 : -1.0;
-            if (rel < 1.0e-9 || d2 <= kObsPolishSigma * kObsPolishSigma * nf.chi2 / dof) break;
-        }
+        chi2 = fit_polish<NP, true>(model, FitPolishEnd{kFitPolishMax, 1.0e-9, kFitPolishSigma, dof}, nf, vd, status, it);
         if (chi2 < 0.0) {              // the residuals at the final point
             double gtmp[NP];
-            obs_gradient<ELL, BG>(src, scale, sw, lane, vd, gtmp, &chi2);
+            model.gradient(vd, gtmp, &chi2);
         }
         if (status != 2) {
             // one fp64 pass for the normal matrix of the errors (its gradient and chi2 are not used: they would come
@@ -482,28 +434,12 @@ k_fit_obs(int nstamp, const double* __restrict__ stamps, const double* __restric
     // chi2 by 2^(2 kx - kv).  The covariance is the inverse of the normal matrix times chi2 / (n_used - NP), which
     // no scale of the weights changes; the errors of derived values are propagated to first order.
     const double up = ldexp(1.0, kx);
-    const double I = vd[0], w = vd[3], eta = vd[D::IETA];
-    double e1 = 0.0, e2 = 0.0;
-    if constexpr (ELL) { e1 = vd[4]; e2 = vd[5]; }
-    const double n = 1.0 / eta;
-    const double p2 = exp2(eta), s2 = p2 - 1.0, sq = sqrt(s2);
-    const double al = w / (2.0 * sq);
-    const double esq = e1 * e1 + e2 * e2, e = sqrt(esq);
-    const double f = ELL ? sqrt(sqrt((1.0 + e) / (1.0 - e))) : 1.0;
-    double rot = 0.0;
-    if constexpr (ELL) {
-        rot = 0.5 * atan2(e2, e1) * (180.0 / kPi);
-        if (rot < 0.0) rot += 180.0;
-        if (rot >= 180.0) rot -= 180.0;
-    }
-    const double flux = I * kPi * al * al / (n - 1.0);
+    const FitEllRow<ELL> r(vd, D::IETA);
     double* o = orow;
-    o[0] = I * up; o[1] = vd[1]; o[2] = vd[2];
-    o[3] = al * f; o[4] = al / f; o[5] = n; o[6] = rot;
-    o[7] = w * f; o[8] = w / f;
+    o[0] = r.I * up; o[1] = vd[1]; o[2] = vd[2];
+    r.write(o, up);
     o[9] = ldexp(chi2, 2 * kx - kv);
     o[10] = (double)it;
-    o[19] = flux * up;
     o[21] = 0.0; o[22] = 0.0;
     if constexpr (BG) o[21] = vd[D::IB] * up;
     o[23] = (double)nused;
@@ -511,49 +447,7 @@ k_fit_obs(int nstamp, const double* __restrict__ stamps, const double* __restric
     bool finite = true;
     if (status != 2 && fit_spd_inverse<NP, double>(nf, cov)) {
         const double s = chi2 / dof;
-        auto quad = [&](const double* gr) {       // s g^T cov g over the variables of gr (NP entries)
-            double q = 0.0;
-#pragma unroll
-            for (int i = 0; i < NP; ++i)
-#pragma unroll
-                for (int j = 0; j < NP; ++j) q += gr[i] * cov[i][j] * gr[j];
-            return sqrt(fmax(q * s, 0.0));
-        };
-        o[11] = sqrt(fmax(cov[0][0] * s, 0.0)) * up;
-        o[12] = sqrt(fmax(cov[1][1] * s, 0.0));
-        o[13] = sqrt(fmax(cov[2][2] * s, 0.0));
-        if constexpr (ELL) {
-            const double ue1 = e > 0.0 ? e1 / e : 1.0, ue2 = e > 0.0 ? e2 / e : 0.0;
-            const double h = 0.5 / (1.0 - esq);                  // d ln f / d e
-            double gmaj[NP], gmin[NP], grot[NP];
-#pragma unroll
-            for (int k = 0; k < NP; ++k) { gmaj[k] = 0.0; gmin[k] = 0.0; grot[k] = 0.0; }
-            gmaj[3] = f; gmaj[4] = w * f * h * ue1; gmaj[5] = w * f * h * ue2;
-            gmin[3] = 1.0 / f; gmin[4] = -w / f * h * ue1; gmin[5] = -w / f * h * ue2;
-            o[14] = quad(gmaj);
-            o[15] = quad(gmin);
-            // rot: d/de1 = -e2 / (2 e^2), d/de2 = e1 / (2 e^2); undetermined (e -> 0): capped at 180 degrees
-            double erot = 180.0;
-            if (esq > 0.0) {
-                grot[4] = -0.5 * e2 / esq; grot[5] = 0.5 * e1 / esq;
-                erot = fmin(quad(grot) * (180.0 / kPi), 180.0);
-                if (!(erot == erot)) erot = 180.0;
-            }
-            o[16] = erot;
-        } else {
-            o[14] = sqrt(fmax(cov[3][3] * s, 0.0));
-            o[15] = o[14];
-            o[16] = 0.0;
-        }
-        o[17] = n * n * sqrt(fmax(cov[D::IETA][D::IETA] * s, 0.0));          // |dn/d eta| = n^2
-        // flux = I pi w^2 / (4 (2^eta - 1) (n - 1))
-        double gfl[NP];
-#pragma unroll
-        for (int k = 0; k < NP; ++k) gfl[k] = 0.0;
-        gfl[0] = kPi * al * al / (n - 1.0);
-        gfl[3] = 2.0 * flux / w;
-        gfl[D::IETA] = flux * (n * n / (n - 1.0) - p2 * 0.69314718055994530942 / s2);
-        o[20] = quad(gfl) * up;
+        fit_ell_errors<NP, D::IETA, ELL>(r, cov, s, up, o);
         if constexpr (BG) o[22] = sqrt(fmax(cov[D::IB][D::IB] * s, 0.0)) * up;
     } else {
         for (int k = 11; k <= 17; ++k) o[k] = 0.0;

@@ -7,7 +7,7 @@
 // every pixel of a star, so the 4 + 4 tap weights and their derivatives are wave-uniform and a model pass is a 4 x 4
 // FIR over the model stamp in LDS; d m / d dp = -F sum c'(y - k) c(x - l) P[k][l] comes from the same 16 taps.
 // The structure is k_fit_obs's: one wave per star, 25 pixels per lane in the 8 x 8-block pixel map, wave-wide sums on
-// the DPP path (wave_total), wave-uniform Levenberg-Marquardt state (Marquardt scaling, Nielsen's damping); the used
+// the DPP path (wave_total), the shared Levenberg-Marquardt descent and polish (fit_lm_descend, fit_polish over PsfModel); the used
 // pixels, the weight plane and the power-of-two normalisation of data and weights are its rules too (obs_pixel there,
 // psf_pixel here).  The normal equations, their factorisation, solve and inverse are fit_common.h's, for NP = 1 to 4.
 // New here: the model stamp in LDS with a zero apron of 10 pixels (|dp|, |dq| <= 8 and taps -1 .. +2: no bounds test
@@ -170,6 +170,33 @@ __device__ __forceinline__ S psf_step_size(const S* dx, const S* vn) {
     return rel;
 }
 
+// what fit_lm_descend and fit_polish need of this fit (fit_common.h); (dp0, dq0): the shift where it is held fixed
+template <typename RE, bool SHIFT, bool BG>
+struct PsfModel {
+    using D = PsfDim<SHIFT, BG>;
+    static constexpr int NP = D::NP, IETA = -1;
+    static constexpr bool ROW_FIRST = false, BOUNDED = true;
+    const RE *sp, *sw, *pl;     // the star, its weights and the apron model stamp in LDS
+    const double *src, *psrc;   // the star and the model stamp in memory, and the powers of two of their normalisation
+    double scale, pscale, dp0, dq0;
+    int lane;
+    __device__ __forceinline__ void accumulate(const RE* v, FitNormEq<RE, NP>& ne) const {
+        if constexpr (SHIFT) psf_accumulate<RE, RE, true, BG>(sp, sw, pl, lane, v, v[1], v[2], ne);
+        else psf_accumulate<RE, RE, false, BG>(sp, sw, pl, lane, v, (RE)dp0, (RE)dq0, ne);
+    }
+    __device__ __forceinline__ void gradient(const double* v, double* g, double* chi2) const {
+        static_assert(sizeof(RE) == 4, "the fp64-residual gradient belongs to the mixed mode");
+        psf_gradient<SHIFT, BG>(src, scale, psrc, pscale, sw, lane, v, SHIFT ? v[1] : dp0, SHIFT ? v[2] : dq0, g, chi2);
+    }
+    template <typename S>
+    __device__ __forceinline__ S step_size(const S* dx, const S* vn) const { return psf_step_size<SHIFT, BG, S>(dx, vn); }
+    template <typename S>
+    __device__ __forceinline__ bool inside(const S* vn) const {
+        if constexpr (SHIFT) return psf_inside<S>(vn[1], vn[2]);
+        else return true;
+    }
+};
+
 // one wave per star; RE = float: mixed mode (float iterations + fp64 polish), RE = double: f64 mode
 template <typename RE, bool SHIFT, bool BG>
 __global__ void __launch_bounds__(64)
@@ -299,12 +326,13 @@ k_fit_psf(int nstamp, const double* __restrict__ stamps, const double* __restric
         if constexpr (SHIFT) { v[1] = (S)dp0; v[2] = (S)dq0; }
         if constexpr (BG) v[D::IB] = dl[DL::IB];
     }
+    const PsfModel<RE, SHIFT, BG> model{sp, sw, pl, src, psrc, scale, pscale, dp0, dq0, lane};
     FitNormEq<RE, NP> ne;
     int it = 0, status = 1;
     if constexpr (!SHIFT) {
         // the linear problem: one more solve from the solution (the rounding of the first one); the normal matrix
         // does not depend on the variables
-        psf_accumulate<RE, RE, false, BG>(sp, sw, pl, lane, v, (RE)dp0, (RE)dq0, ne);
+        model.accumulate(v, ne);
         S dx[NP];
         if (fit_lm_solve<NP, S, RE>(ne, (S)0, dx)) {
 #pragma unroll
@@ -315,56 +343,9 @@ k_fit_psf(int nstamp, const double* __restrict__ stamps, const double* __restric
         }
         it = 1;
     } else {
-        psf_accumulate<RE, RE, true, BG>(sp, sw, pl, lane, v, v[1], v[2], ne);
+        model.accumulate(v, ne);
         const S tol = sizeof(RE) == 4 ? (S)1.0e-3 : (S)1.0e-12;
-        S mu = (S)kFitMu0, nu = (S)2;
-        const S mu_max = (S)kFitMuMax;
-        bool bound = false;              // the last step was refused by the domain
-        while (it < kFitMaxIt) {
-            ++it;
-            S dx[NP];
-            if (!fit_lm_solve<NP, S, RE>(ne, mu, dx)) {
-                mu *= nu;
-                nu *= (S)2;
-                if (mu > mu_max) { status = 2; break; }
-                continue;
-            }
-            S vn[NP];
-#pragma unroll
-            for (int k = 0; k < NP; ++k) vn[k] = v[k] + dx[k];
-            const S rel = psf_step_size<SHIFT, BG, S>(dx, vn);
-            const bool inside = psf_inside<S>(vn[1], vn[2]);
-            if (inside && rel < tol) {       // converged: take the last (tiny) Gauss-Newton step
-#pragma unroll
-                for (int k = 0; k < NP; ++k) v[k] = vn[k];
-                status = 0;
-                break;
-            }
-            FitNormEq<RE, NP> nn;
-            S rho = (S)-1;
-            if (inside) {
-                psf_accumulate<RE, RE, true, BG>(sp, sw, pl, lane, vn, vn[1], vn[2], nn);
-                S pred = (S)0;         // predicted decrease of chi2: dx^T (mu D dx - g)
-#pragma unroll
-                for (int k = 0; k < NP; ++k) pred += dx[k] * (mu * (S)ne.a[fit_diag<NP>(k)] * dx[k] - (S)ne.g[k]);
-                rho = ((S)ne.chi2 - (S)nn.chi2) * fit_rcp<S>(pred);    // NaN -> rejected
-            }
-            if (rho > (S)0) {
-#pragma unroll
-                for (int k = 0; k < NP; ++k) v[k] = vn[k];
-                ne = nn;
-                bound = false;
-                const S c = (S)2 * rho - (S)1;
-                mu = fmax(mu * fmax((S)(1.0 / 3.0), (S)1 - c * c * c), (S)1.0e-14);
-                nu = (S)2;
-            } else {
-                bound = !inside;
-                mu *= nu;
-                nu *= (S)2;
-                // no further descent: at the minimum, or against the bound of the shift
-                if (mu > mu_max) { status = bound ? 1 : 0; break; }
-            }
-        }
+        status = fit_lm_descend<PsfModel<RE, SHIFT, BG>, S, RE>(model, tol, kFitMaxIt, 1, v, ne, it);
         // a fit that rests on the bound of the shift has not found a minimum (a damped step too small to leave the
         // bound in this arithmetic passes the convergence test)
         if (status == 0 && !(fabs(v[1]) < (S)kPsfMaxShift && fabs(v[2]) < (S)kPsfMaxShift)) status = 1;
@@ -379,36 +360,15 @@ k_fit_psf(int nstamp, const double* __restrict__ stamps, const double* __restric
     // the normal matrix of the covariance, fp64; only nf.a is read after the fit
     FitNormEq<double, NP> nf;
     if constexpr (sizeof(RE) == 4) {
-        // the fp64 polish of k_fit_obs: steps -A^-1 g, g the gradient of the fp64 residuals, A the float normal matrix
-        // of the last iteration; it ends once a step is below kPsfPolishSigma of the formal error,
-        // dx^T A dx <= kPsfPolishSigma^2 chi2 / dof (or below 1e-9 on a star the model fits exactly)
+        // the fp64 polish with the float normal matrix of the last iteration; it ends once a step is below
+        // kFitPolishSigma of the formal error (or below 1e-9 on a star the model fits exactly)
 #pragma unroll
         for (int k = 0; k < NA; ++k) nf.a[k] = (double)ne.a[k];
-        nf.chi2 = -1.0;
-        for (int pz = 0; pz < kPsfPolishMax && status != 2; ++pz) {
-            psf_gradient<SHIFT, BG>(src, scale, psrc, pscale, sw, lane, vd, dpf, dqf, nf.g, &nf.chi2);
-            double dx[NP], vn[NP];
-            if (!fit_lm_solve<NP, double, double>(nf, 1.0e-10, dx)) break;
-#pragma unroll
-            for (int k = 0; k < NP; ++k) vn[k] = vd[k] + dx[k];
-            const double rel = psf_step_size<SHIFT, BG, double>(dx, vn);
-            bool inside = true;
-            if constexpr (SHIFT) inside = psf_inside<double>(vn[1], vn[2]);
-            if (!inside || rel >= 0.1) break;
-            double d2 = 0.0;
-#pragma unroll
-            for (int k = 0; k < NP; ++k) d2 -= dx[k] * nf.g[k];
-#pragma unroll
-            for (int k = 0; k < NP; ++k) vd[k] = vn[k];
-            if constexpr (SHIFT) { dpf = vd[1]; dqf = vd[2]; ++it; }
-            // nf.chi2 belongs to the point before this step: chi2 is stationary at the minimum, so after a step of
-            // `rel` it differs from the value at the new point in second order only
-            chi2 = rel < 1.0e-3 ? nf.chi2 : -1.0;
-            if (rel < 1.0e-9 || d2 <= kPsfPolishSigma * kPsfPolishSigma * nf.chi2 / dof) break;
-        }
+        chi2 = fit_polish<NP, SHIFT>(model, FitPolishEnd{kFitPolishMax, 1.0e-9, kFitPolishSigma, dof}, nf, vd, status, it);
+        if constexpr (SHIFT) { dpf = vd[1]; dqf = vd[2]; }
         if (chi2 < 0.0) {              // the residuals at the final point
             double gtmp[NP];
-            psf_gradient<SHIFT, BG>(src, scale, psrc, pscale, sw, lane, vd, dpf, dqf, gtmp, &chi2);
+            model.gradient(vd, gtmp, &chi2);
         }
         if (status != 2) {
             // one fp64 pass for the normal matrix of the errors (its gradient and chi2 are not used: they would come

@@ -1,5 +1,5 @@
 // Device code shared by the PSF-model fits (k_fit_psf in fit_psf.hip, k_fit_group in fit_group_impl.h): the constants
-// of the model stamp in LDS and of the polish, the Keys tap weights of one axis (KeysTaps), the model stamp with its
+// of the model stamp in LDS, the Keys tap weights of one axis (KeysTaps), the model stamp with its
 // apron in LDS and the fp64 one in memory (LdsStamp, GlobalStamp), the 4 x 4 FIR with its derivatives (psf_interp),
 // the domain of the shift (psf_inside) and the validity of a pixel (psf_pixel).  See DESIGN.md sections 18 and 19.
 // Everything here has internal linkage.
@@ -14,8 +14,6 @@ constexpr int kPsfApron = 10;
 constexpr int kPsfSide = NS + 2 * kPsfApron;       // 60 rows
 constexpr int kPsfStride = 72;                     // elements per row (the last 12 are never read)
 constexpr double kPsfMaxShift = 8.0;               // |dp|, |dq| bound
-constexpr int kPsfPolishMax = 12;
-constexpr double kPsfPolishSigma = 1.0e-6;         // the polish stops at a step of this fraction of the formal error
 constexpr double kPsfMinWeight = 0x1p-100;         // a used pixel keeps a weight > 0 (relative to the largest one)
 constexpr int FLAG_BACKGROUND = 1, FLAG_FIXED_SHIFT = 4;     // MPSFR_FIT_BACKGROUND / MPSFR_FIT_FIXED_SHIFT
 static_assert(kPsfApron >= (int)kPsfMaxShift + 2 && kPsfStride >= kPsfSide, "the taps stay inside the apron");

@@ -304,8 +304,8 @@ k_khat(const double* __restrict__ gam, const double* __restrict__ alp, cx<R>* __
 // better-conditioned variables (I, p0, q0, w = FWHM, n) -- the minimum is the same point.
 // Per-lane sums run in the evaluation type RE (float in mixed mode, double in f64 mode); the
 // 5x5 solves of the float phase run in float on the Marquardt-scaled matrix.  The normal equations,
-// their factorisation, solve and inverse, the moment start and the constants are fit_common.h's, shared with
-// k_fit_ell and k_fit_obs.
+// their factorisation, solve and inverse, the descent loop (fit_lm_descend over CircModel), the moment start and the
+// constants are fit_common.h's, shared with the other fit kernels.
 // ------------------------------------------------------------------------------------------
 
 // Normal equations (FitNormEq<RE, 5>) of the Moffat model at v = (I, p0, q0, w, eta), eta = 1/n,
@@ -669,6 +669,25 @@ __device__ __forceinline__ void fit_argmax_rows(TS& best, int& besto) {
     besto = second ? i1 : i0;
 }
 
+// what fit_lm_descend needs of this fit (fit_common.h): the step size is relative in every variable
+template <typename RE>
+struct CircModel {
+    static constexpr int NP = 5, IETA = 4;
+    static constexpr bool ROW_FIRST = true, BOUNDED = false;
+    const RE* sp;               // the stamp in LDS
+    int lane;
+    __device__ __forceinline__ void accumulate(const RE* v, FitNormEq<RE, 5>& ne) const { lm_accumulate<RE>(sp, lane, v, ne); }
+    __device__ __forceinline__ RE step_size(const RE* dx, const RE* vn) const {
+        RE rel = (RE)0;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) rel = fmax(rel, fabs(dx[k]) * fit_rcp<RE>(fabs(vn[k]) + (RE)1.0e-30));
+        return rel;
+    }
+    __device__ __forceinline__ bool inside(const RE* vn) const {
+        return vn[3] > (RE)1.0e-3 && vn[4] > (RE)1.0e-3 && vn[4] < (RE)1.0e2;
+    }
+};
+
 template <typename RE, typename TS>
 __global__ void __launch_bounds__(64 * MPSFR_FIT_WG) __attribute__((amdgpu_waves_per_eu(fit_min_waves<RE>())))
 k_fit(int nstamp, const TS* __restrict__ stamps, double* __restrict__ fit, double polish_tol, SumArgs sa) {
@@ -790,67 +809,11 @@ k_fit(int nstamp, const TS* __restrict__ stamps, double* __restrict__ fit, doubl
 #define MPSFR_FIT_TOL_F32 1.0e-3
 #endif
     const S tol = sizeof(RE) == 4 ? (S)MPSFR_FIT_TOL_F32 : (S)1.0e-10;
+    const CircModel<RE> model{sp, lane};
     FitNormEq<RE, 5> ne;
-    lm_accumulate<RE>(sp, lane, v, ne);
-    S mu = (S)kFitMu0, nu = (S)2;
-    const S mu_max = (S)kFitMuMax;
-    int it = 0, status = amp_ok ? 1 : 2;
-    const int maxit = amp_ok ? kFitMaxIt : 0;
-    while (it < maxit) {
-        ++it;
-        S dx[5];
-        if (!fit_lm_solve<5, S, RE, true>(ne, mu, dx)) {
-            mu *= nu;
-            nu *= (S)2;
-            if (mu > mu_max) { status = 2; break; }
-            continue;
-        }
-        // A stamp narrower than the PSF core has no finite minimum in n: the valley runs to the
-        // Gaussian limit eta -> 0.  A step may cut eta to a fifth at most (the whole step is
-        // scaled), so the valley is descended geometrically instead of through rejected steps.
-        if (v[4] + dx[4] < (S)0.2 * v[4]) {
-            const S sc = (S)-0.8 * v[4] * fit_rcp<S>(dx[4]);
-#pragma unroll
-            for (int k = 0; k < 5; ++k) dx[k] *= sc;
-        }
-        S vn[5], rel = (S)0;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            vn[k] = v[k] + dx[k];
-            rel = fmax(rel, fabs(dx[k]) * fit_rcp<S>(fabs(vn[k]) + (S)1.0e-30));
-        }
-        const bool inside = vn[3] > (S)1.0e-3 && vn[4] > (S)1.0e-3 && vn[4] < (S)1.0e2;
-        if (inside && rel < tol) {       // converged: take the last (tiny) Gauss-Newton step
-#pragma unroll
-            for (int k = 0; k < 5; ++k) v[k] = vn[k];
-            status = 0;
-            break;
-        }
-        FitNormEq<RE, 5> nn;
-        S rho = (S)-1;
-        if (inside) {
-            lm_accumulate<RE>(sp, lane, vn, nn);
-            // predicted decrease of chi2: dx^T (mu D dx - g)
-            S pred = (S)0;
-#pragma unroll
-            for (int k = 0; k < 5; ++k)
-                pred += dx[k] * (mu * (S)ne.a[fit_diag<5>(k)] * dx[k] - (S)ne.g[k]);
-            rho = ((S)ne.chi2 - (S)nn.chi2) * fit_rcp<S>(pred);    // NaN -> rejected
-        }
-        if (rho > (S)0) {
-#pragma unroll
-            for (int k = 0; k < 5; ++k) v[k] = vn[k];
-            ne = nn;
-            if (v[4] < (S)1.5e-3) { status = 0; break; }      // n > 666: Gaussian to 1e-3, stop
-            const S c = (S)2 * rho - (S)1;
-            mu = fmax(mu * fmax((S)(1.0 / 3.0), (S)1 - c * c * c), (S)1.0e-14);
-            nu = (S)2;
-        } else {
-            mu *= nu;
-            nu *= (S)2;
-            if (mu > mu_max) { status = 0; break; }   // no further descent: at the minimum
-        }
-    }
+    model.accumulate(v, ne);
+    int it = 0;
+    int status = fit_lm_descend<CircModel<RE>, S, RE>(model, tol, amp_ok ? kFitMaxIt : 0, amp_ok ? 1 : 2, v, ne, it);
     double vd[5];                          // from here on in fp64
 #pragma unroll
     for (int k = 0; k < 5; ++k) vd[k] = (double)v[k];

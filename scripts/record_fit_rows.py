@@ -1,15 +1,19 @@
 #!/usr/bin/env python
-"""Record the 16-column rows of the circular Moffat fit (k_fit) for the seeded set of tests/fit_bits_cases.py, in mixed
-and f64 mode, standalone (double stamps) and inside a reconstruct (float and double stamps), on the GPU of this
-machine:
+"""Record the rows of the fit kernels for seeded sets of stamps, in mixed and f64 mode, on the GPU of this machine.
 
-    python scripts/record_fit_rows.py [--out tests/golden/fit_rows_gfx950.npz]
-    python scripts/record_fit_rows.py --compare tests/golden/fit_rows_gfx950.npz
+--set circular (the default): the 16-column rows of the circular Moffat fit (k_fit) for tests/fit_bits_cases.py,
+standalone (double stamps) and inside a reconstruct (float and double stamps), into tests/golden/fit_rows_gfx950.npz.
+--set models: the rows of fit_stamps_elliptical, fit_stamps_observed, fit_stamps_psf and fit_groups_psf in all their
+variants for tests/fit_models_cases.py, into tests/golden/fit_rows_models_gfx950.npz.
 
-Run it on the build whose bits are to be kept -- before a change to k_fit that must not move any -- and commit the
-file; tests/test_gpu_fit_bits.py then holds every later build to it with np.array_equal.  --compare prints, per
-key, how many rows of the loaded library differ from a record, and exits 1 if any does.  MPSFR_LIB_PATH selects
-another build of the library.
+    python scripts/record_fit_rows.py [--set models] [--out FILE]
+    python scripts/record_fit_rows.py [--set models] --compare [FILE]
+
+Run it on the build whose bits are to be kept -- before a change to a fit kernel that must not move any -- and commit
+the file; tests/test_gpu_fit_bits.py and tests/test_gpu_fit_models_bits.py then hold every later build to it with
+np.array_equal.  --compare prints, per key, how many rows of the loaded library differ from a record, and exits 1 if
+any does.  MPSFR_LIB_PATH selects another build of the library (muse_psfr_amd._build.build_library(out=...) makes one
+with the same flags).
 """
 import argparse
 import os
@@ -21,22 +25,37 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
 
 import fit_bits_cases as C     # noqa: E402
+import fit_models_cases as M   # noqa: E402
+
+STATUS_COLUMN = {'rows': 14, 'call': 14, 'ell': 18, 'obs': 18, 'psf': 10, 'grp': 4}
+ITER_COLUMN = {'rows': 7, 'call': 7, 'ell': 10, 'obs': 10, 'psf': 5, 'grp': 3}
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('--out', default=C.RECORD)
-    ap.add_argument('--compare', default=None)
+    ap.add_argument('--set', choices=('circular', 'models'), default='circular')
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--compare', nargs='?', const='', default=None)
     args = ap.parse_args()
     import muse_psfr_amd as api
     from muse_psfr_amd import _lib
     import torch
     arch = torch.cuda.get_device_properties(0).gcnArchName.split(':')[0]
-    rows = C.record(api)
-    st = C.stamps()
-    if args.compare:
-        ref = np.load(args.compare)
-        assert str(ref['stamps_sha256']) == C.digest(st), 'the stamps differ from those of the record'
+    if args.set == 'circular':
+        default, rows = C.RECORD, C.record(api)
+        st = C.stamps()
+        meta = dict(stamps_sha256=np.array(C.digest(st)), names=np.array([n for n, _ in C.cases()]), call_lbda=C.CALL_LBDA,
+                    call_seeing=C.CALL_SEEING, call_gl=C.CALL_GL, call_l0=C.CALL_L0)
+        digests = {'stamps_sha256': C.digest(st)}
+    else:
+        default, rows = M.RECORD, M.record(api)
+        digests = M.digests()
+        meta = {k: np.array(v) for k, v in digests.items()}
+        meta.update({k: np.array(v) for k, v in M.names().items()})
+    if args.compare is not None:
+        ref = np.load(args.compare or default)
+        for k, v in digests.items():
+            assert str(ref[k]) == v, 'the stamps differ from those of the record (%s)' % k
         bad = 0
         for k in sorted(rows):
             a, b = rows[k], ref[k]
@@ -45,14 +64,13 @@ def main():
             bad += d != 0
         print('library %s: %s' % (_lib.LIB_PATH, 'DIFFERS' if bad else 'bit-identical'))
         return 1 if bad else 0
-    names = np.array([n for n, _ in C.cases()])
-    np.savez_compressed(args.out, stamps_sha256=np.array(C.digest(st)), names=names, arch=np.array(arch),
-                        call_lbda=C.CALL_LBDA, call_seeing=C.CALL_SEEING, call_gl=C.CALL_GL, call_l0=C.CALL_L0, **rows)
-    print('%s: %d stamps, %d arrays, %d bytes' % (args.out, len(st), len(rows), os.path.getsize(args.out)))
+    out = args.out or default
+    np.savez_compressed(out, arch=np.array(arch), **meta, **rows)
+    print('%s: %d arrays, %d rows, %d bytes' % (out, len(rows), sum(len(r) for r in rows.values()), os.path.getsize(out)))
     for k in sorted(rows):
-        r = rows[k]
-        print('%-28s %4d rows; status %s; iterations %g..%g' % (k, len(r), sorted(set(r[:, 14].astype(int))), r[:, 7].min(),
-                                                              r[:, 7].max()))
+        r, kind = rows[k], k.split('_')[0]
+        print('%-28s %4d rows; status %s; iterations %g..%g' % (k, len(r), sorted(set(r[:, STATUS_COLUMN[kind]].astype(int))),
+                                                              r[:, ITER_COLUMN[kind]].min(), r[:, ITER_COLUMN[kind]].max()))
     return 0
 
 
