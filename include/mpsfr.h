@@ -498,6 +498,65 @@ int mpsfr_fit_groups_psf(mpsfr_ctx* ctx, int nstamp, int nsrc, const double* sta
                          const double* psf, const int32_t* psf_index, const double* shift, int flags,
                          double* fit_out, int on_device);
 
+/* PSF-model fit of star cubes: nl images of one star, fitted at once with one position and a flux per layer -- the
+ * spectrum of a star from the per-wavelength PSFs.  Per star, over the used pixels of all fitted layers, the minimum of
+ *     sum_l sum_pq (m_l - d_l)^2 / var_l,   m_l(p, q) = F_l P~_l(p - dp - sp x_l, q - dq - sq x_l) + b_l
+ * with P~_l the Keys resampling of the layer's model stamp exactly as mpsfr_fit_stamps_psf defines it.  Variables: F_l
+ * of every layer, b_l of every layer under MPSFR_FIT_BACKGROUND, and theta = (dp, dq), or (dp, dq, sp, sq) under
+ * MPSFR_FIT_DRIFT: a position that moves linearly with x_l (a chromatic drift).  Domain: |dp + sp x_l| and
+ * |dq + sq x_l| <= MPSFR_FIT_PSF_MAX_SHIFT for every fitted layer; a step that leaves it is refused.
+ * cubes, var: [nstar][nl][dimpsf][dimpsf] (var NULL: unit weights); the rule for the used pixels and the weights are
+ * those of mpsfr_fit_stamps_psf, per layer.  psf: [npsf][nl][dimpsf][dimpsf] -- the device output of
+ * mpsfr_reconstruct_field ([ntask npos][nl]...) is exactly this; psf_index: [nstar] values in 0..npsf-1, or NULL, which
+ * requires npsf == nstar.  shift: [nstar][2] start values of (dp, dq), or NULL.  x: [nl], ALWAYS a host pointer,
+ * required under MPSFR_FIT_DRIFT and ignored otherwise: finite values in [-1, 1] of which at least two differ.
+ * A layer is left out (layer status 2, its other fields zero except n_used) when it has fewer than nlin + 1 used pixels
+ * (nlin = 1, or 2 with the background), holds an infinite pixel under a valid variance, or its model stamp is all zero,
+ * not finite, or has its largest |P| outside [2^-40, 2^40].  The other layers are fitted without it: a masked sky-line
+ * layer is the ordinary case.
+ * The fit is a variable projection: at a given theta the (F_l, b_l) of a layer are its closed-form weighted linear
+ * solve, and the Levenberg-Marquardt iteration of mpsfr_fit_stamps_psf descends in theta alone (step size in pixels) on
+ * the reduced normal equations; its minimum is that of the joint problem over all variables.  Start: `shift` if given,
+ * else the first maximum of sum_l d_l / var_l (over the used pixels of the fitted layers) minus the first maximum of
+ * sum_l P_l, brought into the domain; sp = sq = 0.  This default only serves stars whose collapsed image stands above
+ * the noise: once the peak signal-to-noise per layer is below about 3.5 / sqrt(nl) it lands on a noise pixel.  Faint
+ * stars are started from a catalogue position.
+ * fit_out: [nstar][MPSFR_NFIT_SPEC + MPSFR_NFIT_SPEC_LAYER nl]:
+ *   head: 0 dp  1 dq  2 sp  3 sq  4 .. 7 their errors  8 chi2 (the weighted sum)  9 iterations  10 status
+ *         11 N_used (used pixels of the fitted layers)  12 L (fitted layers)  13 dof  14, 15 zero
+ *   layer l at 16 + 10 l: 0 F  1 back  2 err_F  3 err_back  4 flux = F sum(P_l)  5 err_flux = err_F |sum(P_l)|
+ *         6 chi2_l  7 n_used_l  8 status_l (0 or 2)  9 zero
+ * Errors: those of the joint problem, sqrt(diag((J^T W J)^-1) chi2 / dof), dof = N_used - (npos + nlin L), npos = 2 or
+ * 4: cov(theta) = S^-1 chi2 / dof with S the reduced normal matrix, and the covariance of (F_l, b_l) carries the
+ * uncertainty of the shared position.
+ * Star status: 0 a minimum; 1 the iteration cap, or the fit ended resting on the bound of the domain; 2 not fitted:
+ * the row is zeros except status, N_used, L and the per-layer n_used and status.  Status 2 covers: no fitted layer;
+ * dof < 1; drift with fewer than two distinct x among the fitted layers; the brightest used pixel of the fitted layers
+ * outside [2^-40, 2^40] in modulus or a used pixel beyond 2^60 times it (the amplitude rules of
+ * mpsfr_fit_stamps_psf); a layer whose linear solve is singular at the start; and, in the device form, an index out of
+ * range or a start that is not finite or outside the domain.  A row whose status & 3 is 0 holds finite numbers only.
+ * A star's row depends on that star, its models, x and the flags only, bit for bit: not on the batch or the star's
+ * place in it.  A constant factor on var changes no parameter and no error.  2^k on the data with 4^k on var scales
+ * every F, back, flux and their errors by 2^k exactly; 2^k on one layer's model scales that layer's F and err_F by
+ * 2^-k exactly.  Values of unused pixels and of left-out layers never matter.
+ * Both precision modes of a context run this fit in fp64 throughout: it has no float path, and a mixed context gives
+ * the rows of an f64 one.
+ * on_device: 0 synchronous on host pointers; 1: cubes, var, psf, psf_index, shift and fit_out are device pointers (x
+ * stays a host pointer; it is copied before the call returns) and the call is queued on the context stream; timed under
+ * the fit's profiling id.
+ * MPSFR_E_INVALID before anything is queued, with fit_out untouched: nstar < 1, npsf < 1 or nl outside
+ * 1 .. MPSFR_MAX_SPEC_LAYERS; NULL cubes, psf or fit_out; unknown flag bits, MPSFR_FIT_ELLIPTICAL,
+ * MPSFR_FIT_FIXED_SHIFT or MPSFR_FIT_COMMON_SHIFT; MPSFR_FIT_DRIFT with nl == 1, or with x NULL, not finite, outside
+ * [-1, 1] or all equal; psf_index NULL with npsf != nstar; and, for host pointers, an index out of range or a start
+ * that is not finite or outside the domain. */
+#define MPSFR_FIT_DRIFT 16           /* beside MPSFR_FIT_BACKGROUND (1); ELLIPTICAL, FIXED_SHIFT, COMMON_SHIFT are refused here */
+#define MPSFR_MAX_SPEC_LAYERS 4096
+#define MPSFR_NFIT_SPEC 16           /* head of a star's row */
+#define MPSFR_NFIT_SPEC_LAYER 10     /* per layer */
+int mpsfr_fit_spectra_psf(mpsfr_ctx* ctx, int nstar, int nl, const double* cubes, const double* var, int npsf,
+                          const double* psf, const int32_t* psf_index, const double* shift, const double* x,
+                          int flags, double* fit_out, int on_device);
+
 /* PSF energy metrics of caller-provided stamps: encircled and ensquared energy with exact pixel overlap, and the radii
  * that hold given fractions of the flux -- the non-parametric description of a core + halo PSF, beside the Moffat fits.
  * Pixel (p, q) is the unit square centred on (p, q), in the pixel coordinates of the fits (p0, q0).  Per stamp:

@@ -12,13 +12,15 @@ psf_metrics (encircled / ensquared energy with exact pixel overlap and EE radii 
 of the compute_* functions and the METRICS_* HDUs of compute_psf_from_sparta(..., metrics=...).
 fit_stars_with_psf (PSF-fitting photometry: a model stamp, e.g. a reconstructed PSF, fitted to observed stars in flux,
 sub-pixel shift and background) and fit_star_groups_with_psf (the same for blended stars: the two to four stars of a
-stamp fitted at once).
+stamp fitted at once); fit_star_spectra_with_psf (the spectrum of a star from its cube: one shared position, a flux
+per wavelength).
 Low level: Context (ctypes binding of libmpsfr.so).
 """
-from ._lib import Context, ContextPool, MpsfrError, NFIT, NFIT_ELL, NMET_HEAD, FIT_ILL_CONDITIONED, FIT_BACKGROUND, FIT_ELLIPTICAL, NFIT_PSF, FIT_FIXED_SHIFT, NFIT_GROUP, MAX_GROUP, FIT_COMMON_SHIFT  # noqa: F401
+from ._lib import Context, ContextPool, MpsfrError, NFIT, NFIT_ELL, NMET_HEAD, FIT_ILL_CONDITIONED, FIT_BACKGROUND, FIT_ELLIPTICAL, NFIT_PSF, FIT_FIXED_SHIFT, NFIT_GROUP, MAX_GROUP, FIT_COMMON_SHIFT, NFIT_SPEC, NFIT_SPEC_LAYER, FIT_DRIFT  # noqa: F401
 from .synthetic import synthetic_rows, grid_pixscale  # noqa: F401
 from .psfrec import (MAX_L0, MIN_L0, compute_psf, compute_field_psf, compute_profile_psf,  # noqa: F401
                      band_weights, compute_band_psf, psf_metrics, fit_stars_with_psf, fit_star_groups_with_psf,
+                     fit_star_spectra_with_psf,
                      compute_psf_from_sparta,
                      create_sparta_table, direction_perf, fit_psf_cube, fit_psf_with_polynom,
                      host_cutoff_masks, muse_intrinsic_psf, plot_psf, radial_profile,

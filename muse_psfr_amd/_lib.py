@@ -22,6 +22,10 @@ FIT_PSF_MAX_SHIFT = 8.0      # |dp|, |dq| bound in pixels (MPSFR_FIT_PSF_MAX_SHI
 NFIT_GROUP = 48              # rows of the PSF-model fit of blended groups (MPSFR_NFIT_GROUP)
 MAX_GROUP = 4                # sources per stamp (MPSFR_MAX_GROUP)
 FIT_COMMON_SHIFT = 8         # flag of mpsfr_fit_groups_psf (MPSFR_FIT_COMMON_SHIFT), beside FIT_BACKGROUND, FIT_FIXED_SHIFT
+FIT_DRIFT = 16               # flag of mpsfr_fit_spectra_psf (MPSFR_FIT_DRIFT), beside FIT_BACKGROUND
+NFIT_SPEC = 16               # head of a row of mpsfr_fit_spectra_psf (MPSFR_NFIT_SPEC)
+NFIT_SPEC_LAYER = 10         # values per layer of such a row (MPSFR_NFIT_SPEC_LAYER)
+MAX_SPEC_LAYERS = 4096       # MPSFR_MAX_SPEC_LAYERS
 GROUP_MODES = ('free', 'common', 'fixed')
 DIM_AO = 80
 PREC_MIXED, PREC_F64 = 0, 1
@@ -106,6 +110,8 @@ def load():
     lib.mpsfr_fit_stamps_psf.restype = C.c_int
     lib.mpsfr_fit_groups_psf.argtypes = [p, C.c_int, C.c_int, p, p, C.c_int, p, p, p, C.c_int, p, C.c_int]
     lib.mpsfr_fit_groups_psf.restype = C.c_int
+    lib.mpsfr_fit_spectra_psf.argtypes = [p, C.c_int, C.c_int, p, p, C.c_int, p, p, p, p, C.c_int, p, C.c_int]
+    lib.mpsfr_fit_spectra_psf.restype = C.c_int
     lib.mpsfr_stamp_metrics.argtypes = [p, C.c_int, p, p, C.c_int, dp, C.c_int, dp, C.c_int, dp, p, C.c_int]
     lib.mpsfr_stamp_metrics.restype = C.c_int
     lib.mpsfr_simul_psd.argtypes = [p, C.c_double, C.c_double, C.c_double, C.c_int, dp, C.c_double, C.c_int, u8p, u8p, dp]
@@ -155,7 +161,7 @@ def load():
 
 
 EXPORTS = ['mpsfr_create', 'mpsfr_destroy', 'mpsfr_last_error', 'mpsfr_set_option',
-           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_fit_stamps_psf', 'mpsfr_fit_groups_psf', 'mpsfr_stamp_metrics', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
+           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_fit_stamps_psf', 'mpsfr_fit_groups_psf', 'mpsfr_fit_spectra_psf', 'mpsfr_stamp_metrics', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
            'mpsfr_psd_to_psf',
            'mpsfr_convolve_stamps', 'mpsfr_fit_rows', 'mpsfr_sync', 'mpsfr_last_ticket', 'mpsfr_wait', 'mpsfr_abandon',
            'mpsfr_stream', 'mpsfr_stream_wait', 'mpsfr_wait_event',
@@ -746,6 +752,12 @@ class Context:
         _check(self.lib.mpsfr_fit_groups_psf(self._h, int(nstamp), int(nsrc), p(stamps), p(var), int(npsf), p(psf),
                                              p(index), p(shift), flags, p(fit), on_device))
 
+    def _call_fit_spectra(self, nstar, nl, cubes, var, npsf, psf, index, shift, x, flags, fit, on_device):
+        p = _devptr if on_device else _vptr
+        _check(self.lib.mpsfr_fit_spectra_psf(self._h, int(nstar), int(nl), p(cubes), p(var), int(npsf), p(psf),
+                                              p(index), p(shift), None if x is None else _dptr(x), flags, p(fit),
+                                              on_device))
+
     def _call_metrics(self, nstamp, stamps, centers, rad, box, frac, out, on_device):
         p = _devptr if on_device else _vptr
         _check(self.lib.mpsfr_stamp_metrics(self._h, int(nstamp), p(stamps), p(centers), rad.size, _dptr(rad),
@@ -865,6 +877,40 @@ class Context:
         flags = group_fit_flags(background, mode)
         self._call_fit_groups(nstamp, nsrc, stamps_ptr, var_ptr, npsf, psf_ptr, psf_index_ptr, shift_ptr, flags,
                               fit_ptr, 1)
+
+    def fit_spectra_psf(self, cubes, psf, var=None, psf_index=None, shift=None, background=True, x=None):
+        """PSF-model fit of star cubes (mpsfr_fit_spectra_psf): every star is a cube (n, nl, dimpsf, dimpsf) of nl images
+        that share one position (dp, dq) -- with `x` (nl values in [-1, 1]) a position dp + sp x_l, dq + sq x_l that
+        drifts linearly -- and have a scale F_l and, with `background`, a constant b_l per layer.  `psf`: the model cubes
+        (npsf, nl, dimpsf, dimpsf); `psf_index` (n,) or None for one model cube per star in order; `shift` (n, 2) start
+        values of (dp, dq), or None for the difference of the brightest pixels of the collapsed images (bright stars
+        only); `var` and the mask as fit_stamps_psf.  Returns (head, layers): head (n, NFIT_SPEC): 0 dp, 1 dq, 2 sp,
+        3 sq, 4-7 their errors, 8 chi2, 9 iterations, 10 status, 11 used pixels, 12 fitted layers, 13 dof; layers (n, nl,
+        NFIT_SPEC_LAYER): 0 F, 1 back, 2 err_F, 3 err_back, 4 flux = F sum(psf_l), 5 err_flux, 6 chi2_l, 7 n_used_l,
+        8 status_l (2: the layer was left out)."""
+        cu, va, ps, ix, sh, xx, flags = spectra_fit_arguments(cubes, var, psf, psf_index, shift, background, x, self.dimpsf)
+        n, nl = cu.shape[:2]
+        out = np.empty((n, NFIT_SPEC + NFIT_SPEC_LAYER * nl))
+        self._call_fit_spectra(n, nl, cu, va, ps.shape[0], ps, ix, sh, xx, flags, out, 0)
+        return out[:, :NFIT_SPEC].copy(), out[:, NFIT_SPEC:].reshape(n, nl, NFIT_SPEC_LAYER).copy()
+
+    def fit_spectra_psf_device(self, nstar, nl, cubes_ptr, npsf, psf_ptr, fit_ptr, var_ptr=None, psf_index_ptr=None,
+                               shift_ptr=None, background=True, x=None):
+        """Device-buffer form (asynchronous, on_device = 1): `cubes_ptr`, `var_ptr` ([nstar][nl][dimpsf][dimpsf] float64;
+        var_ptr None: unit weights), `psf_ptr` ([npsf][nl][dimpsf][dimpsf] float64), `psf_index_ptr` ([nstar] int32, or
+        None with npsf == nstar), `shift_ptr` ([nstar][2] float64, or None) and `fit_ptr` ([nstar][NFIT_SPEC +
+        NFIT_SPEC_LAYER nl] float64) are raw device pointers (int) on this context's GPU; `x` stays a host array.  The
+        call is queued on the context stream, after any device-output reconstruct of this context.  An index out of
+        range or a start outside the domain makes that row status 2."""
+        _positive_int('nstar', nstar)
+        _positive_int('npsf', npsf)
+        _spec_layers(nl)
+        _device_pointers(cubes_ptr=cubes_ptr, psf_ptr=psf_ptr, fit_ptr=fit_ptr)
+        if not psf_index_ptr and npsf != nstar:
+            raise ValueError('without psf_index_ptr, npsf must equal nstar')
+        flags, xx = spectra_fit_flags(background, x, nl)
+        self._call_fit_spectra(nstar, nl, cubes_ptr, var_ptr, npsf, psf_ptr, psf_index_ptr, shift_ptr, xx, flags,
+                               fit_ptr, 1)
 
     def stamp_metrics(self, stamps, radii_px, boxes_px, fractions, centers=None):
         """PSF energy metrics (mpsfr_stamp_metrics) of stamps (..., dimpsf, dimpsf): (n, NMET_HEAD + nrad + nbox +
@@ -1046,6 +1092,67 @@ def group_fit_arguments(nstamp, psf, psf_index, shift, background, mode, dimpsf=
     if not np.all(np.abs(sh) <= FIT_PSF_MAX_SHIFT):           # (NaN fails)
         raise ValueError('the positions must be finite and within %g pixels' % FIT_PSF_MAX_SHIFT)
     return ps, ix, np.ascontiguousarray(sh).reshape(nstamp, sh.shape[-2], 2), flags
+
+
+def _spec_layers(nl):
+    if isinstance(nl, bool) or not isinstance(nl, (int, np.integer)) or not 1 <= nl <= MAX_SPEC_LAYERS:
+        raise ValueError('a star cube has 1 to %d layers, not %r' % (MAX_SPEC_LAYERS, nl))
+
+
+def spectra_fit_flags(background, x, nl):
+    """(flags, x) of mpsfr_fit_spectra_psf: `x` None (no drift) or nl finite values in [-1, 1] of which at least two
+    differ -> contiguous float64 and the drift flag (ValueError for anything else)."""
+    if not isinstance(background, (bool, np.bool_)):
+        raise ValueError('background must be True or False')
+    flags = FIT_BACKGROUND if background else 0
+    if x is None:
+        return flags, None
+    try:
+        xx = np.ascontiguousarray(np.asarray(x, dtype=np.float64).ravel())
+    except (TypeError, ValueError):
+        raise ValueError('x must be a numeric array') from None
+    if nl < 2 or xx.size != nl:
+        raise ValueError('the drift needs at least two layers and one x per layer (%d)' % nl)
+    if not np.all(np.abs(xx) <= 1.0):            # (NaN fails)
+        raise ValueError('x must be finite and lie in [-1, 1]')
+    if np.all(xx == xx[0]):
+        raise ValueError('at least two values of x must differ')
+    return flags | FIT_DRIFT, xx
+
+
+def spectra_fit_arguments(cubes, var, psf, psf_index, shift, background, x, dimpsf=40):
+    """(cubes, var, psf, psf_index, shift, x, flags) of a PSF-model fit of star cubes, validated as
+    mpsfr_fit_spectra_psf validates host arguments (ValueError): cubes (n, nl, dimpsf, dimpsf) (one cube (nl, dimpsf,
+    dimpsf) is one star), var None or of the same shape, psf (npsf, nl, dimpsf, dimpsf) (or one cube); psf_index and
+    shift as psf_fit_arguments, per star; x as spectra_fit_flags."""
+    try:
+        nd = np.ndim(cubes)
+    except (TypeError, ValueError):
+        nd = 0
+    if nd not in (3, 4):
+        raise ValueError('cubes must have the shape (n, nl, %d, %d)' % (dimpsf, dimpsf))
+    shape = np.shape(cubes)
+    n = shape[0] if nd == 4 else 1
+    nl = shape[-3]
+    st, va = observed_stamps(cubes, var, dimpsf)
+    if n < 1 or st.shape[0] != n * nl:
+        raise ValueError('cubes must have the shape (n, nl, %d, %d)' % (dimpsf, dimpsf))
+    _spec_layers(int(nl))
+    flags, xx = spectra_fit_flags(background, x, nl)
+    try:
+        pnd = np.ndim(getattr(psf, 'data', psf))
+        pshape = np.shape(getattr(psf, 'data', psf))
+    except (TypeError, ValueError):
+        raise ValueError('psf must be a numeric array') from None
+    if pnd not in (3, 4) or pshape[-3] != nl:
+        raise ValueError('psf must have the shape (npsf, %d, %d, %d)' % (nl, dimpsf, dimpsf))
+    npsf = pshape[0] if pnd == 4 else 1
+    ps, _, _, _ = psf_fit_arguments(npsf * nl, psf, None, None, True, False, dimpsf)
+    ps = ps.reshape(npsf, nl, dimpsf, dimpsf)
+    # index and start: one per star, checked against the number of model cubes
+    _, ix, sh, _ = psf_fit_arguments(n, np.zeros((npsf, dimpsf, dimpsf)), psf_index, shift, True, False, dimpsf)
+    return (st.reshape(n, nl, dimpsf, dimpsf), None if va is None else va.reshape(n, nl, dimpsf, dimpsf), ps, ix, sh,
+            xx, flags)
 
 
 def metric_stamps(stamps, dimpsf=40):

@@ -270,6 +270,13 @@ void launch_fit_psf(hipStream_t s, int nstamp, const double* d_stamps, const dou
 void launch_fit_group(hipStream_t s, int nstamp, int nsrc, const double* d_stamps, const double* d_var, int npsf,
                       const double* d_psf, const int32_t* d_index, const double* d_shift, int flags, double* d_fit,
                       bool f64);
+// PSF-model fit of star cubes (fit_spec.hip): star d_cubes[k] ([nstar][nl][40][40], d_var likewise or nullptr) against
+// the model cube d_psf[d_index[k]] ([npsf][nl][40][40]; d_index = nullptr: d_psf[k]) -> [nstar][16 + 10 nl]; d_shift
+// [nstar][2]: the start of (dp, dq), or nullptr; d_x [nl] (device): the abscissa of the drift, or nullptr; flags:
+// MPSFR_FIT_BACKGROUND | MPSFR_FIT_DRIFT; nl <= 4096; grid(nstar), block(256).  Both modes run in fp64.
+void launch_fit_spec(hipStream_t s, int nstar, int nl, const double* d_cubes, const double* d_var, int npsf,
+                     const double* d_psf, const int32_t* d_index, const double* d_shift, const double* d_x, int flags,
+                     double* d_fit, bool f64);
 // PSF energy metrics (metrics.hip): [nstamp][40][40] double stamps -> [nstamp][METRIC_HEAD + nrad + nbox + nfrac];
 // d_centers [nstamp][2] (p, q) or nullptr (the centroid); radii / boxes / fractions: host arrays (they travel as kernel
 // arguments), counts 0..METRIC_MAX

@@ -155,6 +155,7 @@ struct mpsfr_ctx {
     hipEvent_t stagger_ev = nullptr;     // behind the column transforms of the first chunk after a cold start
     bool stagger_armed = false;
     int stagger_lane = -1;
+    DevBuf specx;                      // [nl] the abscissa of mpsfr_fit_spectra_psf's drift
     DevBuf fit, sum, stage, lsum;      // lsum: [lanes][nl][40][40] per-lane partial stamp sums
     // mpsfr_psd_to_psf: a stream and workspaces of its own, so that it never waits for nor touches the lanes
     struct P2P {
@@ -696,7 +697,7 @@ void mpsfr_destroy(mpsfr_ctx* c) {
     }
     DevBuf* all[] = {&c->scoef, &c->stwk, &c->ssup, &c->tw64, &c->tel, &c->rows, &c->tlmax, &c->tl2, &c->tlb, &c->aotab, &c->samp_p,
                      &c->samp_a, &c->G, &c->xtab, &c->etab, &c->gtab, &c->kmuse, &c->fit, &c->sum,
-                     &c->stage, &c->lsum, &c->mfclk};
+                     &c->stage, &c->lsum, &c->mfclk, &c->specx};
     for (auto b : all) release(*b);
     if (c->p2p.stream) { (void)hipStreamSynchronize(c->p2p.stream); (void)hipStreamDestroy(c->p2p.stream); }
     DevBuf* p2p[] = {&c->p2p.twm, &c->p2p.psd, &c->p2p.cm, &c->p2p.d0t, &c->p2p.pup, &c->p2p.phase, &c->p2p.lbda,
@@ -2425,6 +2426,57 @@ int mpsfr_fit_groups_psf(mpsfr_ctx* c, int nstamp, int nsrc, const double* stamp
                           launch_fit_group(s, nstamp, nsrc, (const double*)d[0], (const double*)d[1], npsf,
                                            (const double*)d[2], (const int32_t*)d[4], (const double*)d[3], flags, d_fit,
                                            c->f64);
+                      });
+}
+
+int mpsfr_fit_spectra_psf(mpsfr_ctx* c, int nstar, int nl, const double* cubes, const double* var, int npsf,
+                          const double* psf, const int32_t* psf_index, const double* shift, const double* x,
+                          int flags, double* fit_out, int on_device) {
+    if (!c || !cubes || !psf || !fit_out || nstar < 1 || npsf < 1)
+        return fail(MPSFR_E_INVALID, "fit_spectra_psf: bad argument (cubes, psf and fit_out are required)");
+    if (nl < 1 || nl > MPSFR_MAX_SPEC_LAYERS)
+        return fail(MPSFR_E_INVALID, "fit_spectra_psf: nl=%d outside 1..%d", nl, MPSFR_MAX_SPEC_LAYERS);
+    if (flags & ~(MPSFR_FIT_BACKGROUND | MPSFR_FIT_DRIFT))
+        return fail(MPSFR_E_INVALID, "fit_spectra_psf: unknown flag bits (only the background and the drift bit have a meaning here)");
+    if (!psf_index && npsf != nstar)
+        return fail(MPSFR_E_INVALID, "fit_spectra_psf: without psf_index, npsf must equal nstar");
+    const bool drift = (flags & MPSFR_FIT_DRIFT) != 0;
+    if (drift) {
+        if (!x || nl < 2) return fail(MPSFR_E_INVALID, "fit_spectra_psf: MPSFR_FIT_DRIFT needs x and at least two layers");
+        bool differ = false;
+        for (int l = 0; l < nl; ++l) {
+            if (!(std::fabs(x[l]) <= 1.0)) return fail(MPSFR_E_INVALID, "fit_spectra_psf: x must be finite in [-1, 1]");
+            differ = differ || x[l] != x[0];
+        }
+        if (!differ) return fail(MPSFR_E_INVALID, "fit_spectra_psf: at least two values of x must differ");
+    }
+    if (!on_device) {
+        if (psf_index)
+            for (int k = 0; k < nstar; ++k)
+                if (psf_index[k] < 0 || psf_index[k] >= npsf)
+                    return fail(MPSFR_E_INVALID, "fit_spectra_psf: a psf_index outside 0..npsf-1");
+        if (shift)
+            for (size_t k = 0; k < (size_t)2 * nstar; ++k)
+                if (!(std::fabs(shift[k]) <= MPSFR_FIT_PSF_MAX_SHIFT))
+                    return fail(MPSFR_E_INVALID, "fit_spectra_psf: a start that is not finite or beyond 8 pixels");
+    }
+    const double* d_x = nullptr;
+    if (drift) {           // x is the host's in both forms: into a buffer of the context, on the stream of the call
+        HIPCHK(hipSetDevice(c->device));
+        int rc;
+        if ((rc = ensure(c, c->specx, (size_t)nl * sizeof(double)))) return rc;
+        HIPCHK(hipMemcpyAsync(c->specx.p, x, (size_t)nl * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        d_x = (const double*)c->specx.p;
+    }
+    const size_t ncube = (size_t)nl * kStampPix;
+    const StampIn in[] = {{cubes, nstar * ncube, sizeof(double)}, {var, nstar * ncube, sizeof(double)},
+                          {psf, npsf * ncube, sizeof(double)},    {shift, (size_t)2 * nstar, sizeof(double)},
+                          {psf_index, (size_t)nstar, sizeof(int32_t)}};
+    return stamp_call(c, on_device, in, fit_out, (size_t)nstar * (MPSFR_NFIT_SPEC + (size_t)MPSFR_NFIT_SPEC_LAYER * nl),
+                      [&](hipStream_t s, const void* const* d, double* d_fit) {
+                          launch_fit_spec(s, nstar, nl, (const double*)d[0], (const double*)d[1], npsf,
+                                          (const double*)d[2], (const int32_t*)d[4], (const double*)d[3], d_x, flags,
+                                          d_fit, c->f64);
                       });
 }
 

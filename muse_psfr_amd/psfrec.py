@@ -473,6 +473,80 @@ def fit_stars_with_psf(stars, psf, *, var=None, psf_index=None, shift=None, fit_
     return _make_table(_fit_columns_psf(fit, pixscale))
 
 
+_FIT_COLS_SPEC = ('shift', 'err_shift', 'drift', 'err_drift', 'chi2', 'npix', 'nlayers', 'status', 'flux', 'err_flux',
+                  'scale', 'back', 'layer_status', 'lbda')
+
+
+def _fit_columns_spec(head, layers, lbda, pixscale):
+    """head (n, NFIT_SPEC), layers (n, nl, NFIT_SPEC_LAYER) of the fit of star cubes -> the columns of _FIT_COLS_SPEC
+    (position and drift in arcsec; the drift over half the wavelength range)."""
+    head, layers = np.asarray(head), np.asarray(layers)
+    cols = OrderedDict()
+    cols['shift'] = head[:, 0:2] * pixscale
+    cols['err_shift'] = head[:, 4:6] * pixscale
+    cols['drift'] = head[:, 2:4] * pixscale
+    cols['err_drift'] = head[:, 6:8] * pixscale
+    cols['chi2'] = head[:, 8].copy()
+    cols['npix'] = head[:, 11].astype(np.int64)
+    cols['nlayers'] = head[:, 12].astype(np.int64)
+    cols['status'] = head[:, 10].astype(np.int64)
+    cols['flux'] = layers[:, :, 4].copy()
+    cols['err_flux'] = layers[:, :, 5].copy()
+    cols['scale'] = layers[:, :, 0].copy()
+    cols['back'] = layers[:, :, 1].copy()
+    cols['layer_status'] = layers[:, :, 8].astype(np.int64)
+    cols['lbda'] = np.broadcast_to(np.asarray(lbda, dtype=float), layers.shape[:2]).copy()
+    assert tuple(cols) == _FIT_COLS_SPEC
+    return cols
+
+
+def fit_star_spectra_with_psf(cubes, psf, lbda, *, var=None, psf_index=None, shift=None, fit_back=True, drift=False,
+                              pixscale=0.2, precision='mixed', device=0):
+    """Spectra of stars from a data cube by PSF fitting: every star is a cube (n, nl, 40, 40) of its images at the nl
+    wavelengths `lbda`, and `psf` (npsf, nl, 40, 40) holds the model -- e.g. reconstructed PSFs -- of every wavelength.
+    All layers of a star share one position; each has a flux scale and (fit_back) a constant background.  drift=True
+    lets the position move linearly with wavelength: shift + drift x, x = (lbda - mid) / half-range in [-1, 1].  A
+    layer without enough valid pixels (a masked sky line) is left out and the others are fitted without it.
+
+    var: the variances (the cubes' shape) or None; NaN pixels and invalid variances are masked.  psf_index: the model
+    cube of every star, or None for one per star in order.  shift: (n, 2) start position (row, column) in arcsec, or
+    None for the difference of the brightest pixels of the collapsed images, which only serves stars that stand above
+    the noise there: start faint stars from a catalogue position.
+
+    Returns a table with one row per star: shift, err_shift, drift, err_drift (2, arcsec), chi2, npix, nlayers (the
+    layers fitted), status (0 a minimum, 1 not converged or against the 8-pixel bound, 2 not fitted) and the (n, nl)
+    columns flux = scale sum(psf_l), err_flux, scale, back, layer_status (2: left out) and lbda.  The errors are those
+    of the joint fit, scaled by sqrt(chi2 / dof)."""
+    for name, val in (('fit_back', fit_back), ('drift', drift)):
+        if not isinstance(val, (bool, np.bool_)):
+            raise ValueError('%s must be True or False' % name)
+    if not (np.isfinite(pixscale) and pixscale > 0):
+        raise ValueError('pixscale must be positive')
+    try:
+        lb = np.asarray(lbda, dtype=float).ravel()
+    except (TypeError, ValueError):
+        raise ValueError('lbda must be a numeric array') from None
+    if lb.size < 1 or not np.all(np.isfinite(lb)):
+        raise ValueError('lbda must hold one finite wavelength per layer')
+    if np.ndim(cubes) not in (3, 4) or np.shape(cubes)[-3] != lb.size:
+        raise ValueError('cubes must have the shape (n, %d, 40, 40): one layer per wavelength' % lb.size)
+    x = None
+    if drift:
+        lo, hi = lb.min(), lb.max()
+        if not hi > lo:
+            raise ValueError('drift=True needs at least two different wavelengths')
+        x = np.clip((lb - 0.5 * (lo + hi)) / (0.5 * (hi - lo)), -1.0, 1.0)
+    sh = None
+    if shift is not None:
+        try:
+            sh = np.asarray(shift, dtype=float) / pixscale
+        except (TypeError, ValueError):
+            raise ValueError('shift must be a numeric array') from None
+    ctx = get_context(128, pixscale, np.shape(cubes)[-1], precision, device)
+    head, layers = ctx.fit_spectra_psf(cubes, psf, var=var, psf_index=psf_index, shift=sh, background=bool(fit_back), x=x)
+    return _make_table(_fit_columns_spec(head, layers, lb, pixscale))
+
+
 _FIT_COLS_GROUP = ('group', 'source', 'scale', 'shift', 'flux', 'err_scale', 'err_shift', 'err_flux', 'back', 'err_back',
                    'chi2', 'npix', 'status', 'max_corr')
 _GROUP_PAIRS = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))      # fit_out[40 .. 45] of mpsfr_fit_groups_psf
