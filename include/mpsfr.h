@@ -589,6 +589,55 @@ int mpsfr_stamp_metrics(mpsfr_ctx* ctx, int nstamp, const double* stamps, const 
                         const double* radii_px, int nbox, const double* boxes_px, int nfrac, const double* fractions,
                         double* out, int on_device);
 
+/* Frame-level PSF photometry: stamps out of a frame, and the fitted models back into it -- frame -> cut_stamps -> the
+ * PSF-model fits -> render_stars -> residual frame, every step on device buffers of one context if the caller wants.
+ *
+ * A frame is [ny][nx] float64, 1 <= ny, nx <= MPSFR_MAX_IMAGE_SIDE and ny nx <= 2^26.  origin[k] = (row, column) is the
+ * frame pixel on which pixel [0][0] of star k's stamp lies: stamp pixel (p, q) is frame pixel (origin_p + p, origin_q + q).
+ * Any int32 origin with |origin| <= 2^30 is legal, on or off the frame.  `shift` is the (dp, dq) of mpsfr_fit_stamps_psf
+ * (|dp|, |dq| <= MPSFR_FIT_PSF_MAX_SHIFT) and `scale` its F: a frame cut with `origin`, fitted and rendered with the same
+ * `origin` and the fit's (F, dp, dq) reproduces the fit's model (without b) on those pixels.
+ *
+ * mpsfr_cut_stamps: stamps_out[k][p][q] = image[origin_p + p][origin_q + q], bit for bit, where that pixel is on the
+ * frame, NaN elsewhere; var_out likewise from var, 0 elsewhere (var and var_out: both NULL or both given).  NaN data and
+ * var <= 0 are the pixel mask of the observed fits, so a star at the frame's edge is fitted on the pixels it has and a
+ * stamp wholly off the frame makes the fits answer status 2.
+ *
+ * mpsfr_render_stars: for every frame pixel (Y, X), the stars taken in increasing index k,
+ *   acc_0 = image_in[Y][X] (0 if image_in is NULL),  acc_k = acc_{k-1} +- t_k,  image_out[Y][X] = acc_nstar,
+ *   t_k = scale_k P~_k(Y - origin_p,k - dp_k, X - origin_q,k - dq_k),
+ * with - under MPSFR_RENDER_SUBTRACT (which requires image_in), else +.  P~ is the cubic-convolution resampling of
+ * mpsfr_fit_stamps_psf of the model stamp psf[psf_index[k]] (psf[k] if psf_index is NULL, then npsf == nstar), zero
+ * outside the model's pixels.  A star's term is applied only on its footprint, the (dimpsf + 20)^2 window around its
+ * stamp (frame rows origin_p - 10 .. origin_p + dimpsf + 9); pixels no footprint reaches are copied unchanged, so a NaN
+ * of one model stays inside that star's footprint.  Inside it values follow IEEE rules (a NaN pixel of image_in stays
+ * NaN); the call does not inspect the model.  The product scale_k P~ is rounded before it is added.
+ * The order of the sum is part of the contract: a pixel's value depends on image_in there and on the stars whose
+ * footprint reaches it, in index order -- not on the tile grid, the batch or where the scene sits in the frame --, so
+ * one call over the stars 0 .. n-1 equals, bit for bit, two calls over 0 .. m-1 and m .. n-1, the second reading the
+ * first's output.  image_out may be image_in (in place); no other overlap is allowed.
+ * Arithmetic is fp64 in both precision modes: the call measures the data it is given.
+ * star_out (or NULL): [nstar][MPSFR_NRENDER]: 0 status, 1 the number of frame pixels inside the footprint, 2, 3 zero.
+ * status 0: rendered (scale = 0 included); 1: the footprint misses the frame, nothing added; 2: skipped, nothing added
+ * (count 0) -- in the device form a psf_index out of range, a shift that is not finite or outside the domain, a scale
+ * that is not finite, an |origin| above 2^30; for host pointers these make the call return MPSFR_E_INVALID instead.
+ * A tile's list of up to MPSFR_RENDER_SORT_CHUNK stars is sorted in LDS, a longer one in memory; the result is the same.
+ *
+ * on_device as mpsfr_fit_stamps_psf: 0 synchronous on host pointers; 1: every array is a device pointer and the call is
+ * queued on the context stream behind the lanes.  MPSFR_E_INVALID, outputs untouched: ny or nx outside 1 ..
+ * MPSFR_MAX_IMAGE_SIDE or ny nx > 2^26; nstar < 1 or npsf < 1; a NULL image, origin, psf, scale, stamps_out or
+ * image_out; var and var_out not both NULL or both given; unknown flag bits; SUBTRACT without image_in; psf_index NULL
+ * with npsf != nstar.  Both calls are timed under the fit's profiling id. */
+#define MPSFR_RENDER_SUBTRACT 1
+#define MPSFR_NRENDER 4            /* doubles per star in star_out */
+#define MPSFR_MAX_IMAGE_SIDE 16384 /* and ny * nx <= 2^26 */
+#define MPSFR_RENDER_SORT_CHUNK 256
+int mpsfr_cut_stamps(mpsfr_ctx* ctx, int ny, int nx, const double* image, const double* var, int nstar,
+                     const int32_t* origin, double* stamps_out, double* var_out, int on_device);
+int mpsfr_render_stars(mpsfr_ctx* ctx, int ny, int nx, const double* image_in, int nstar, int npsf, const double* psf,
+                       const int32_t* psf_index, const int32_t* origin, const double* shift, const double* scale,
+                       int flags, double* image_out, double* star_out, int on_device);
+
 /* The stages of the path as the reference exports them (muse_psfr/__init__.py:16: `from .psfrec import *`),
  * for a caller that holds its own PSD or its own stamps.  Host buffers, synchronous, float64; the same
  * kernels as mpsfr_reconstruct entered or left at another stage.

@@ -27,6 +27,13 @@ NFIT_SPEC = 16               # head of a row of mpsfr_fit_spectra_psf (MPSFR_NFI
 NFIT_SPEC_LAYER = 10         # values per layer of such a row (MPSFR_NFIT_SPEC_LAYER)
 MAX_SPEC_LAYERS = 4096       # MPSFR_MAX_SPEC_LAYERS
 GROUP_MODES = ('free', 'common', 'fixed')
+RENDER_SUBTRACT = 1          # flag of mpsfr_render_stars (MPSFR_RENDER_SUBTRACT)
+NRENDER = 4                  # doubles per star of its star_out (MPSFR_NRENDER): status, frame pixels in the footprint, 0, 0
+MAX_IMAGE_SIDE = 16384       # rows, columns of a frame (MPSFR_MAX_IMAGE_SIDE)
+MAX_IMAGE_PIXELS = 1 << 26   # and pixels
+MAX_ORIGIN = 1 << 30         # |origin| bound of the frame calls
+RENDER_SORT_CHUNK = 256      # stars of one frame tile that the renderer sorts in LDS (MPSFR_RENDER_SORT_CHUNK)
+RENDER_APRON = 10            # a star's footprint: its stamp and this many pixels around it
 DIM_AO = 80
 PREC_MIXED, PREC_F64 = 0, 1
 E_GRID = -3
@@ -114,6 +121,10 @@ def load():
     lib.mpsfr_fit_spectra_psf.restype = C.c_int
     lib.mpsfr_stamp_metrics.argtypes = [p, C.c_int, p, p, C.c_int, dp, C.c_int, dp, C.c_int, dp, p, C.c_int]
     lib.mpsfr_stamp_metrics.restype = C.c_int
+    lib.mpsfr_cut_stamps.argtypes = [p, C.c_int, C.c_int, p, p, C.c_int, p, p, p, C.c_int]
+    lib.mpsfr_cut_stamps.restype = C.c_int
+    lib.mpsfr_render_stars.argtypes = [p, C.c_int, C.c_int, p, C.c_int, C.c_int, p, p, p, p, p, C.c_int, p, p, C.c_int]
+    lib.mpsfr_render_stars.restype = C.c_int
     lib.mpsfr_simul_psd.argtypes = [p, C.c_double, C.c_double, C.c_double, C.c_int, dp, C.c_double, C.c_int, u8p, u8p, dp]
     lib.mpsfr_simul_psd.restype = C.c_int
     lib.mpsfr_psf_from_psd.argtypes = [p, C.c_int, dp, C.c_int, dp, dp]
@@ -161,7 +172,7 @@ def load():
 
 
 EXPORTS = ['mpsfr_create', 'mpsfr_destroy', 'mpsfr_last_error', 'mpsfr_set_option',
-           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_fit_stamps_psf', 'mpsfr_fit_groups_psf', 'mpsfr_fit_spectra_psf', 'mpsfr_stamp_metrics', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
+           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_fit_stamps_psf', 'mpsfr_fit_groups_psf', 'mpsfr_fit_spectra_psf', 'mpsfr_stamp_metrics', 'mpsfr_cut_stamps', 'mpsfr_render_stars', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
            'mpsfr_psd_to_psf',
            'mpsfr_convolve_stamps', 'mpsfr_fit_rows', 'mpsfr_sync', 'mpsfr_last_ticket', 'mpsfr_wait', 'mpsfr_abandon',
            'mpsfr_stream', 'mpsfr_stream_wait', 'mpsfr_wait_event',
@@ -934,6 +945,81 @@ class Context:
         rad, box, frac = metric_parameters(radii_px, boxes_px, fractions, self.dimpsf)
         self._call_metrics(nstamp, stamps_ptr, centers_ptr, rad, box, frac, out_ptr, 1)
 
+    def _call_cut(self, ny, nx, image, var, nstar, origin, stamps, var_out, on_device):
+        p = _devptr if on_device else _vptr
+        _check(self.lib.mpsfr_cut_stamps(self._h, int(ny), int(nx), p(image), p(var), int(nstar), p(origin), p(stamps),
+                                         p(var_out), on_device))
+
+    def _call_render(self, ny, nx, image, nstar, npsf, psf, index, origin, shift, scale, flags, out, star_out, on_device):
+        p = _devptr if on_device else _vptr
+        _check(self.lib.mpsfr_render_stars(self._h, int(ny), int(nx), p(image), int(nstar), int(npsf), p(psf), p(index),
+                                           p(origin), p(shift), p(scale), flags, p(out), p(star_out), on_device))
+
+    def cut_stamps(self, image, origin, var=None):
+        """Stamps out of a frame (mpsfr_cut_stamps): `image` (ny, nx), `origin` (n, 2) integers, the frame pixel (row,
+        column) of pixel [0][0] of every stamp, on or off the frame (|origin| <= 2^30).  Returns the (n, dimpsf, dimpsf)
+        stamps, NaN where a stamp leaves the frame; with `var` (the frame's shape) also the variance stamps, 0 there:
+        (stamps, var_stamps).  NaN and var <= 0 are the mask of the observed fits."""
+        im, va = frame_images(image, var)
+        og = star_origins(origin)
+        n = og.shape[0]
+        out = np.empty((n, self.dimpsf, self.dimpsf))
+        vout = None if va is None else np.empty((n, self.dimpsf, self.dimpsf))
+        self._call_cut(im.shape[0], im.shape[1], im, va, n, og, out, vout, 0)
+        return out if va is None else (out, vout)
+
+    def cut_stamps_device(self, ny, nx, image_ptr, nstar, origin_ptr, stamps_ptr, var_ptr=None, var_stamps_ptr=None):
+        """Device-buffer form (asynchronous, on_device = 1): `image_ptr`, `var_ptr` ([ny][nx] float64; var_ptr None: no
+        variances), `origin_ptr` ([nstar][2] int32), `stamps_ptr` and `var_stamps_ptr` ([nstar][dimpsf][dimpsf] float64;
+        given exactly when var_ptr is) are raw device pointers (int) on this context's GPU; the call is queued on the
+        context stream, after any device-output reconstruct of this context."""
+        frame_shape(ny, nx)
+        _positive_int('nstar', nstar)
+        _device_pointers(image_ptr=image_ptr, origin_ptr=origin_ptr, stamps_ptr=stamps_ptr)
+        if bool(var_ptr) != bool(var_stamps_ptr):
+            raise ValueError('var_ptr and var_stamps_ptr must both be given or both be None')
+        self._call_cut(ny, nx, image_ptr, var_ptr, nstar, origin_ptr, stamps_ptr, var_stamps_ptr, 1)
+
+    def render_stars(self, psf, origin, scale, shift=None, psf_index=None, image=None, shape=None, subtract=False,
+                     return_status=False):
+        """Model stars into a frame (mpsfr_render_stars): star k is scale[k] times the model stamp psf[psf_index[k]]
+        (psf[k] without psf_index), resampled by cubic convolution at the shift (dp, dq) in pixels (`shift` (n, 2), None:
+        zeros), with pixel [0][0] of its stamp on the frame pixel origin[k] -- the (F, dp, dq) of fit_stamps_psf on a
+        stamp cut at the same origin.  The stars are added to `image` (ny, nx), or to zeros of `shape` = (ny, nx); with
+        `subtract` they are subtracted from `image`.  At every pixel the stars are summed in index order, so one call
+        equals two calls over a split of the list, bit for bit.  Returns the frame; with `return_status` also the (n,
+        NRENDER) rows: 0 status (0 rendered, 1 off the frame), 1 the frame pixels in the star's footprint."""
+        im, ny, nx, ps, ix, og, sh, sc, flags = render_arguments(psf, origin, scale, shift, psf_index, image, shape,
+                                                                 subtract, self.dimpsf)
+        if not isinstance(return_status, (bool, np.bool_)):
+            raise ValueError('return_status must be True or False')
+        n = og.shape[0]
+        out = np.empty((ny, nx))
+        rows = np.empty((n, NRENDER)) if return_status else None
+        self._call_render(ny, nx, im, n, ps.shape[0], ps, ix, og, sh, sc, flags, out, rows, 0)
+        return (out, rows) if return_status else out
+
+    def render_stars_device(self, ny, nx, nstar, npsf, psf_ptr, origin_ptr, scale_ptr, image_out_ptr, image_ptr=None,
+                            shift_ptr=None, psf_index_ptr=None, star_out_ptr=None, subtract=False):
+        """Device-buffer form (asynchronous, on_device = 1): `psf_ptr` ([npsf][dimpsf][dimpsf] float64), `origin_ptr`
+        ([nstar][2] int32), `scale_ptr` ([nstar] float64), `shift_ptr` ([nstar][2] float64, or None for zeros),
+        `psf_index_ptr` ([nstar] int32, or None with npsf == nstar), `image_ptr` ([ny][nx] float64, or None for zeros),
+        `image_out_ptr` ([ny][nx] float64; it may be image_ptr) and `star_out_ptr` ([nstar][NRENDER] float64, or None)
+        are raw device pointers (int) on this context's GPU; the call is queued on the context stream, after any
+        device-output reconstruct of this context.  An index out of range, a shift outside the domain, a scale that is
+        not finite or an |origin| above 2^30 makes that star status 2: it is skipped."""
+        frame_shape(ny, nx)
+        _positive_int('nstar', nstar)
+        _positive_int('npsf', npsf)
+        _device_pointers(psf_ptr=psf_ptr, origin_ptr=origin_ptr, scale_ptr=scale_ptr, image_out_ptr=image_out_ptr)
+        if not psf_index_ptr and npsf != nstar:
+            raise ValueError('without psf_index_ptr, npsf must equal nstar')
+        flags = render_flags(subtract)
+        if subtract and not image_ptr:
+            raise ValueError('subtract needs image_ptr')
+        self._call_render(ny, nx, image_ptr, nstar, npsf, psf_ptr, psf_index_ptr, origin_ptr, shift_ptr, scale_ptr, flags,
+                          image_out_ptr, star_out_ptr, 1)
+
     def debug_fetch(self, what, shape):
         out = np.empty(int(np.prod(shape)))
         n = _check(self.lib.mpsfr_debug_fetch(self._h, what.encode(), _dptr(out), out.size))
@@ -1057,6 +1143,100 @@ def psf_fit_arguments(nstamp, psf, psf_index, shift, background, fixed_shift, di
             raise ValueError('shift must be finite and within %g pixels' % FIT_PSF_MAX_SHIFT)
         sh = np.ascontiguousarray(sh).reshape(nstamp, 2)
     return ps, ix, sh, flags
+
+
+def frame_shape(ny, nx):
+    """ValueError unless (ny, nx) is the shape of a frame: 1 .. MAX_IMAGE_SIDE each way, at most 2^26 pixels."""
+    for name, n in (('ny', ny), ('nx', nx)):
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= MAX_IMAGE_SIDE:
+            raise ValueError('%s must be an integer between 1 and %d' % (name, MAX_IMAGE_SIDE))
+    if int(ny) * int(nx) > MAX_IMAGE_PIXELS:
+        raise ValueError('a frame holds at most 2^26 pixels')
+    return int(ny), int(nx)
+
+
+def frame_images(image, var=None):
+    """(image, var) of a frame call as C-contiguous (ny, nx) float64 arrays (var: None if absent); ValueError unless
+    `image` is a numeric 2-D array with the shape of a frame and `var` has the same shape.  A masked array is
+    accepted: masked pixels become NaN.  Non-finite pixels are data, not an error."""
+    def plane(a, what):
+        try:
+            if isinstance(a, np.ma.MaskedArray):
+                return np.ma.filled(a.astype(np.float64), np.nan)
+            return np.asarray(a, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('%s must be a numeric array' % what) from None
+    im = plane(image, 'image')
+    if im.ndim != 2 or im.size == 0:
+        raise ValueError('image must have the shape (ny, nx)')
+    frame_shape(*im.shape)
+    if var is None:
+        return np.ascontiguousarray(im), None
+    va = plane(var, 'var')
+    if va.shape != im.shape:
+        raise ValueError('var must have the shape of image')
+    return np.ascontiguousarray(im), np.ascontiguousarray(va)
+
+
+def star_origins(origin, n=None):
+    """The (n, 2) int32 origins of a frame call; ValueError unless `origin` is a non-empty integer array of that shape
+    (of `n` rows if given) with |origin| <= MAX_ORIGIN."""
+    try:
+        raw = np.asarray(origin)
+        og = raw.astype(np.int64)
+    except (TypeError, ValueError):
+        raise ValueError('origin must be an integer array') from None
+    if raw.dtype.kind not in 'iu' or og.ndim != 2 or og.shape[1] != 2 or og.shape[0] < 1:
+        raise ValueError('origin must be an integer array of shape (n, 2)')
+    if n is not None and og.shape[0] != n:
+        raise ValueError('origin must have the shape (%d, 2)' % n)
+    if np.any(np.abs(og) > MAX_ORIGIN):
+        raise ValueError('origin must lie within 2^30 pixels')
+    return np.ascontiguousarray(og, dtype=np.int32)
+
+
+def render_flags(subtract):
+    """The flags of mpsfr_render_stars from a boolean (ValueError for anything else)."""
+    if not isinstance(subtract, (bool, np.bool_)):
+        raise ValueError('subtract must be True or False')
+    return RENDER_SUBTRACT if subtract else 0
+
+
+def render_arguments(psf, origin, scale, shift, psf_index, image, shape, subtract, dimpsf=40):
+    """(image or None, ny, nx, psf, psf_index, origin, shift, scale, flags) of a render call, validated as
+    mpsfr_render_stars validates host arguments (ValueError): origin as star_origins; psf, psf_index and shift as
+    psf_fit_arguments; scale n finite values; `image` a frame or None with `shape` = (ny, nx) (both: they must agree);
+    subtract needs the image."""
+    flags = render_flags(subtract)
+    og = star_origins(origin)
+    n = og.shape[0]
+    ps, ix, sh, _ = psf_fit_arguments(n, psf, psf_index, shift, True, False, dimpsf)
+    try:
+        sc = np.asarray(scale, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('scale must be a numeric array') from None
+    if sc.size != n or sc.ndim > 1:
+        raise ValueError('scale must hold one value per star (%d)' % n)
+    if not np.all(np.isfinite(sc)):
+        raise ValueError('scale must be finite')
+    sc = np.ascontiguousarray(sc).reshape(n)
+    if image is None:
+        if subtract:
+            raise ValueError('subtract needs the image')
+        if shape is None:
+            raise ValueError('give the image or the shape of the frame')
+        try:
+            ny, nx = shape
+        except (TypeError, ValueError):
+            raise ValueError('shape must be (ny, nx)') from None
+        ny, nx = frame_shape(ny, nx)
+        im = None
+    else:
+        im, _ = frame_images(image)
+        ny, nx = im.shape
+        if shape is not None and tuple(shape) != (ny, nx):
+            raise ValueError('shape differs from the shape of image')
+    return im, ny, nx, ps, ix, og, sh, sc, flags
 
 
 def _group_size(nsrc):

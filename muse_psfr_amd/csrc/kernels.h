@@ -283,6 +283,17 @@ void launch_fit_spec(hipStream_t s, int nstar, int nl, const double* d_cubes, co
 void launch_stamp_metrics(hipStream_t s, int nstamp, const double* d_stamps, const double* d_centers, int nrad,
                           const double* radii, int nbox, const double* boxes, int nfrac, const double* fractions,
                           double* d_out);
+// Frame-level photometry (render.hip).  launch_cut_stamps: [nstar][40][40] stamps (and variances, d_var / d_var_out both
+// nullptr or both set) out of the frame d_image [ny][nx] at d_origin [nstar][2]; NaN (0) off the frame.
+// launch_render_stars: d_image_out = d_image_in (nullptr: zeros) +- sum_k d_scale[k] P~_k, the stars in index order at
+// every pixel (mpsfr_render_stars, include/mpsfr.h); d_image_out may be d_image_in; d_star_out [nstar][4] or nullptr;
+// d_ws: render_workspace_bytes(ny, nx, nstar) bytes of work lists, which the launch itself clears on the stream.
+void launch_cut_stamps(hipStream_t s, int ny, int nx, const double* d_image, const double* d_var, int nstar,
+                       const int32_t* d_origin, double* d_stamps, double* d_var_out);
+size_t render_workspace_bytes(int ny, int nx, int nstar);
+void launch_render_stars(hipStream_t s, int ny, int nx, const double* d_image_in, int nstar, int npsf,
+                         const double* d_psf, const int32_t* d_index, const int32_t* d_origin, const double* d_shift,
+                         const double* d_scale, bool subtract, double* d_image_out, double* d_star_out, void* d_ws);
 // band-integrated stamps (band.hip): d_fin [ntb][nl][40][40] (float if fin_f32, else double) reduced over wavelength
 // into d_out [ntb][nband][40][40] double with the weights d_w [nl][band_stride(nband)] (zero beyond nband)
 constexpr int MAX_BANDS = 16;    // MPSFR_MAX_BANDS

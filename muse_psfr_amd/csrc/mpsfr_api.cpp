@@ -156,6 +156,7 @@ struct mpsfr_ctx {
     bool stagger_armed = false;
     int stagger_lane = -1;
     DevBuf specx;                      // [nl] the abscissa of mpsfr_fit_spectra_psf's drift
+    DevBuf render;                     // work lists of mpsfr_render_stars (render_workspace_bytes)
     DevBuf fit, sum, stage, lsum;      // lsum: [lanes][nl][40][40] per-lane partial stamp sums
     // mpsfr_psd_to_psf: a stream and workspaces of its own, so that it never waits for nor touches the lanes
     struct P2P {
@@ -542,37 +543,47 @@ struct StampIn {
     size_t count, elem;
 };
 
-// One stamp call (the fits and the metrics of caller-provided stamps) on the context stream, after the lanes, timed
-// under the fit's profiling id.  launch(s, d, d_out) receives the inputs in the order of `in` and the nout output
-// values as device pointers.  on_device: they are the caller's own pointers and the call returns once it is queued.
-// Else the arrays are staged in c->stage -- the inputs of doubles in order, then the output, then the narrower
-// inputs (int32 indices), so that everything is aligned; an absent input gets no room and stays NULL -- copied in,
-// the output is copied back and the call waits for it.
-template <size_t N, class Launch>
-int stamp_call(mpsfr_ctx* c, int on_device, const StampIn (&in)[N], double* out, size_t nout, Launch launch) {
+// An output array of a stamp call: `count` doubles, or NULL for an optional that is absent.
+struct StampOut {
+    double* p;
+    size_t count;
+};
+
+// One stamp call (the fits and the metrics of caller-provided stamps, the frame calls) on the context stream, after the
+// lanes, timed under the fit's profiling id.  launch(s, d, d_out) receives the inputs in the order of `in` and the
+// outputs in the order of `out` as device pointers.  on_device: they are the caller's own pointers and the call returns
+// once it is queued.  Else the arrays are staged in c->stage -- the inputs of doubles in order, then the outputs in order,
+// then the narrower inputs (int32 indices), so that everything is aligned; an absent array gets no room and stays NULL
+// -- copied in, the outputs are copied back and the call waits for them.
+template <size_t N, size_t M, class Launch>
+int stamp_call(mpsfr_ctx* c, int on_device, const StampIn (&in)[N], const StampOut (&out)[M], Launch launch) {
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     int rc;
     if ((rc = wait_for_lanes(c, s))) return rc;
     const void* d[N];
-    double* d_out = out;
+    double* d_out[M];
     for (size_t i = 0; i < N; ++i) d[i] = in[i].p;
+    for (size_t i = 0; i < M; ++i) d_out[i] = out[i].p;
     if (!on_device) {
-        size_t off[N] = {}, off_out = 0, bytes = 0;
+        size_t off[N] = {}, off_out[M] = {}, bytes = 0;
         for (int narrow = 0; narrow < 2; ++narrow) {
             for (size_t i = 0; i < N; ++i)
                 if (in[i].p && (in[i].elem < sizeof(double)) == (narrow == 1)) {
                     off[i] = bytes;
                     bytes += in[i].count * in[i].elem;
                 }
-            if (!narrow) {
-                off_out = bytes;
-                bytes += nout * sizeof(double);
-            }
+            if (!narrow)
+                for (size_t i = 0; i < M; ++i)
+                    if (out[i].p) {
+                        off_out[i] = bytes;
+                        bytes += out[i].count * sizeof(double);
+                    }
         }
         if ((rc = ensure(c, c->stage, bytes))) return rc;
         char* base = (char*)c->stage.p;
-        d_out = (double*)(base + off_out);
+        for (size_t i = 0; i < M; ++i)
+            if (out[i].p) d_out[i] = (double*)(base + off_out[i]);
         for (size_t i = 0; i < N; ++i)
             if (in[i].p) {
                 d[i] = base + off[i];
@@ -585,10 +596,20 @@ int stamp_call(mpsfr_ctx* c, int on_device, const StampIn (&in)[N], double* out,
     }
     HIPCHK(hipGetLastError());
     if (!on_device) {
-        HIPCHK(hipMemcpyAsync(out, d_out, nout * sizeof(double), hipMemcpyDeviceToHost, s));
+        for (size_t i = 0; i < M; ++i)
+            if (out[i].p)
+                HIPCHK(hipMemcpyAsync(out[i].p, d_out[i], out[i].count * sizeof(double), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
     }
     return MPSFR_OK;
+}
+
+// the common case: one output
+template <size_t N, class Launch>
+int stamp_call(mpsfr_ctx* c, int on_device, const StampIn (&in)[N], double* out, size_t nout, Launch launch) {
+    const StampOut outs[] = {{out, nout}};
+    return stamp_call(c, on_device, in, outs,
+                      [&](hipStream_t s, const void* const* d, double* const* d_out) { launch(s, d, d_out[0]); });
 }
 
 const size_t kStampPix = (size_t)NS * NS;
@@ -697,7 +718,7 @@ void mpsfr_destroy(mpsfr_ctx* c) {
     }
     DevBuf* all[] = {&c->scoef, &c->stwk, &c->ssup, &c->tw64, &c->tel, &c->rows, &c->tlmax, &c->tl2, &c->tlb, &c->aotab, &c->samp_p,
                      &c->samp_a, &c->G, &c->xtab, &c->etab, &c->gtab, &c->kmuse, &c->fit, &c->sum,
-                     &c->stage, &c->lsum, &c->mfclk, &c->specx};
+                     &c->stage, &c->lsum, &c->mfclk, &c->specx, &c->render};
     for (auto b : all) release(*b);
     if (c->p2p.stream) { (void)hipStreamSynchronize(c->p2p.stream); (void)hipStreamDestroy(c->p2p.stream); }
     DevBuf* p2p[] = {&c->p2p.twm, &c->p2p.psd, &c->p2p.cm, &c->p2p.d0t, &c->p2p.pup, &c->p2p.phase, &c->p2p.lbda,
@@ -2506,6 +2527,74 @@ int mpsfr_stamp_metrics(mpsfr_ctx* c, int nstamp, const double* stamps, const do
                           launch_stamp_metrics(s, nstamp, (const double*)d[0], (const double*)d[1], nrad, radii_px, nbox,
                                                boxes_px, nfrac, fractions, d_out);
                       });
+}
+
+static_assert(MPSFR_NRENDER == 4 && MPSFR_FIT_PSF_MAX_SHIFT == 8.0, "K_RENDER_PREPARE row layout and domain");
+
+static int frame_shape(const char* who, int ny, int nx) {
+    if (ny < 1 || ny > MPSFR_MAX_IMAGE_SIDE || nx < 1 || nx > MPSFR_MAX_IMAGE_SIDE || (size_t)ny * nx > ((size_t)1 << 26))
+        return fail(MPSFR_E_INVALID, "%s: a frame has 1..%d rows and columns and at most 2^26 pixels, not %d x %d", who,
+                    MPSFR_MAX_IMAGE_SIDE, ny, nx);
+    return MPSFR_OK;
+}
+
+int mpsfr_cut_stamps(mpsfr_ctx* c, int ny, int nx, const double* image, const double* var, int nstar,
+                     const int32_t* origin, double* stamps_out, double* var_out, int on_device) {
+    if (!c || !image || !origin || !stamps_out || nstar < 1)
+        return fail(MPSFR_E_INVALID, "cut_stamps: bad argument (image, origin and stamps_out are required)");
+    int rc;
+    if ((rc = frame_shape("cut_stamps", ny, nx))) return rc;
+    if ((var == nullptr) != (var_out == nullptr))
+        return fail(MPSFR_E_INVALID, "cut_stamps: var and var_out must both be NULL or both be given");
+    const size_t npix = (size_t)ny * nx;
+    const StampIn in[] = {{image, npix, sizeof(double)}, {var, npix, sizeof(double)},
+                          {origin, (size_t)2 * nstar, sizeof(int32_t)}};
+    const StampOut out[] = {{stamps_out, nstar * kStampPix}, {var_out, nstar * kStampPix}};
+    return stamp_call(c, on_device, in, out, [&](hipStream_t s, const void* const* d, double* const* d_out) {
+        launch_cut_stamps(s, ny, nx, (const double*)d[0], (const double*)d[1], nstar, (const int32_t*)d[2], d_out[0],
+                          d_out[1]);
+    });
+}
+
+int mpsfr_render_stars(mpsfr_ctx* c, int ny, int nx, const double* image_in, int nstar, int npsf, const double* psf,
+                       const int32_t* psf_index, const int32_t* origin, const double* shift, const double* scale,
+                       int flags, double* image_out, double* star_out, int on_device) {
+    if (!c || !psf || !origin || !scale || !image_out || nstar < 1 || npsf < 1)
+        return fail(MPSFR_E_INVALID, "render_stars: bad argument (psf, origin, scale and image_out are required)");
+    int rc;
+    if ((rc = frame_shape("render_stars", ny, nx))) return rc;
+    if (flags & ~MPSFR_RENDER_SUBTRACT) return fail(MPSFR_E_INVALID, "render_stars: unknown flag bits");
+    if ((flags & MPSFR_RENDER_SUBTRACT) && !image_in)
+        return fail(MPSFR_E_INVALID, "render_stars: MPSFR_RENDER_SUBTRACT needs image_in");
+    if (!psf_index && npsf != nstar)
+        return fail(MPSFR_E_INVALID, "render_stars: without psf_index, npsf must equal nstar");
+    if (!on_device) {
+        if (psf_index)
+            for (int k = 0; k < nstar; ++k)
+                if (psf_index[k] < 0 || psf_index[k] >= npsf)
+                    return fail(MPSFR_E_INVALID, "render_stars: a psf_index outside 0..npsf-1");
+        if (shift)
+            for (size_t k = 0; k < (size_t)2 * nstar; ++k)
+                if (!(std::fabs(shift[k]) <= MPSFR_FIT_PSF_MAX_SHIFT))
+                    return fail(MPSFR_E_INVALID, "render_stars: a shift that is not finite or beyond 8 pixels");
+        for (int k = 0; k < nstar; ++k)
+            if (!std::isfinite(scale[k])) return fail(MPSFR_E_INVALID, "render_stars: a scale that is not finite");
+        for (size_t k = 0; k < (size_t)2 * nstar; ++k)
+            if (origin[k] < -(1 << 30) || origin[k] > (1 << 30))
+                return fail(MPSFR_E_INVALID, "render_stars: an origin beyond 2^30");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = ensure(c, c->render, render_workspace_bytes(ny, nx, nstar)))) return rc;
+    const size_t npix = (size_t)ny * nx;
+    const StampIn in[] = {{image_in, npix, sizeof(double)},         {psf, npsf * kStampPix, sizeof(double)},
+                          {shift, (size_t)2 * nstar, sizeof(double)}, {scale, (size_t)nstar, sizeof(double)},
+                          {origin, (size_t)2 * nstar, sizeof(int32_t)}, {psf_index, (size_t)nstar, sizeof(int32_t)}};
+    const StampOut out[] = {{image_out, npix}, {star_out, (size_t)nstar * MPSFR_NRENDER}};
+    return stamp_call(c, on_device, in, out, [&](hipStream_t s, const void* const* d, double* const* d_out) {
+        launch_render_stars(s, ny, nx, (const double*)d[0], nstar, npsf, (const double*)d[1], (const int32_t*)d[5],
+                            (const int32_t*)d[4], (const double*)d[2], (const double*)d[3],
+                            (flags & MPSFR_RENDER_SUBTRACT) != 0, d_out[0], d_out[1], c->render.p);
+    });
 }
 
 long mpsfr_debug_fetch(mpsfr_ctx* c, const char* what, double* out, size_t capacity) {

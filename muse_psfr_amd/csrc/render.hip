@@ -1,0 +1,333 @@
+// Frame-level PSF photometry: k_cut_stamps gathers 40 x 40 stamps out of a frame, and the
+// renderer adds or subtracts scaled, resampled model stamps in a frame as a gather over 32 x 32 frame tiles:
+//   k_render_prepare  one thread per star: validates it, writes star_out, counts the star on the tiles its footprint
+//                     (the kPsfSide x kPsfSide window around its stamp) reaches
+//   k_render_scan     exclusive scan of the tile counts (one workgroup)
+//   k_render_fill     writes each star's index into the lists of its tiles at an atomic cursor (arbitrary order)
+//   k_render_tiles    one workgroup per tile: sorts its list by star index, then walks it in that order -- the model
+//                     stamp part the tile needs goes into LDS (two buffers, the next star fetched while this one is
+//                     evaluated), every thread keeps four pixels in registers
+// The order of the sum at a pixel is the star index, whatever the tile grid or the scheduling; no floating-point atomics.
+// Arithmetic is fp64 in both precision modes; P~ is psf_interp of fit_psf_common.h with KeysTaps<double>.
+#include "fit_psf_common.h"
+
+namespace mpsfr {
+namespace {
+
+constexpr int kTile = 32;                                     // frame tile side
+constexpr int kTileThreads = 256;
+constexpr int kTileRows = kTileThreads / kTile;               // threads per tile column
+constexpr int kTilePix = kTile / kTileRows;                   // pixels per thread: adjacent rows of one column
+constexpr int kWaveRows = 64 / kTile * kTilePix;               // tile rows one wave holds
+constexpr int kStageSide = kTile + 3;                         // model rows / columns the 4 taps of a tile touch
+constexpr int kStageStride = kStageSide + 1;
+constexpr int kStageLoads = (kStageSide * kStageSide + kTileThreads - 1) / kTileThreads;     // per thread
+constexpr int kSortChunk = 256;                               // MPSFR_RENDER_SORT_CHUNK: lists up to here sort in LDS
+constexpr int kMaxOrigin = 1 << 30;
+constexpr int kScanThreads = 1024;
+static_assert(kTile * kTile == kTileThreads * kTilePix && kTileRows * kTile == kTileThreads, "tile layout");
+static_assert(kSortChunk == kTileThreads, "one list entry per thread in the LDS copy");
+
+__global__ __launch_bounds__(256) void k_cut_stamps(int ny, int nx, const double* __restrict__ image,
+                                                    const double* __restrict__ var, const int32_t* __restrict__ origin,
+                                                    double* __restrict__ out, double* __restrict__ var_out) {
+    const int k = blockIdx.x;
+    const long long op = origin[2 * k], oq = origin[2 * k + 1];
+    for (int i = threadIdx.x; i < NS * NS; i += 256) {
+        const int p = i / NS, q = i - p * NS;
+        const long long Y = op + p, X = oq + q;
+        const bool in = Y >= 0 && Y < ny && X >= 0 && X < nx;
+        const size_t src = in ? (size_t)Y * nx + (size_t)X : 0;
+        const size_t dst = (size_t)k * (NS * NS) + i;
+        const double d = image[src];
+        out[dst] = in ? d : __builtin_nan("");
+        if (var) {
+            const double v = var[src];
+            var_out[dst] = in ? v : 0.0;
+        }
+    }
+}
+
+// the frame pixels inside the footprint of a star at (op, oq): rows y0 .. y1 - 1, columns x0 .. x1 - 1
+__device__ __forceinline__ bool footprint(int ny, int nx, int op, int oq, int& y0, int& y1, int& x0, int& x1) {
+    y0 = max(op - kPsfApron, 0);
+    y1 = min(op + NS + kPsfApron, ny);
+    x0 = max(oq - kPsfApron, 0);
+    x1 = min(oq + NS + kPsfApron, nx);
+    return y0 < y1 && x0 < x1;
+}
+
+__global__ __launch_bounds__(256) void k_render_prepare(int ny, int nx, int ntx, int nstar, int npsf,
+                                                        const int32_t* __restrict__ index,
+                                                        const int32_t* __restrict__ origin,
+                                                        const double* __restrict__ shift,
+                                                        const double* __restrict__ scale, int* __restrict__ count,
+                                                        int* __restrict__ status, double* __restrict__ star_out) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= nstar) return;
+    const int op = origin[2 * k], oq = origin[2 * k + 1];
+    const int ix = index ? index[k] : k;
+    const double dp = shift ? shift[2 * k] : 0.0, dq = shift ? shift[2 * k + 1] : 0.0;
+    const bool ok = (unsigned)ix < (unsigned)npsf && psf_inside(dp, dq) && fabs(scale[k]) < __builtin_inf() &&
+                    op >= -kMaxOrigin && op <= kMaxOrigin && oq >= -kMaxOrigin && oq <= kMaxOrigin;
+    int st = 2, npix = 0;
+    if (ok) {
+        int y0, y1, x0, x1;
+        const bool hit = footprint(ny, nx, op, oq, y0, y1, x0, x1);
+        st = hit ? 0 : 1;
+        if (hit) {
+            npix = (y1 - y0) * (x1 - x0);
+            for (int ty = y0 / kTile; ty <= (y1 - 1) / kTile; ++ty)
+                for (int tx = x0 / kTile; tx <= (x1 - 1) / kTile; ++tx) atomicAdd(&count[ty * ntx + tx], 1);
+        }
+    }
+    status[k] = st;
+    if (star_out) {
+        star_out[4 * (size_t)k + 0] = (double)st;
+        star_out[4 * (size_t)k + 1] = (double)npix;
+        star_out[4 * (size_t)k + 2] = 0.0;
+        star_out[4 * (size_t)k + 3] = 0.0;
+    }
+}
+
+// offset[t] = sum of count[0 .. t - 1], offset[nt] = the total
+__global__ __launch_bounds__(kScanThreads) void k_render_scan(int nt, const int* __restrict__ count,
+                                                              int* __restrict__ offset) {
+    __shared__ int part[kScanThreads];
+    const int tid = threadIdx.x;
+    const int per = (nt + kScanThreads - 1) / kScanThreads;
+    const int b = min(tid * per, nt), e = min(b + per, nt);
+    int sum = 0;
+    for (int i = b; i < e; ++i) sum += count[i];
+    part[tid] = sum;
+    __syncthreads();
+    for (int d = 1; d < kScanThreads; d <<= 1) {
+        const int add = tid >= d ? part[tid - d] : 0;
+        __syncthreads();
+        part[tid] += add;
+        __syncthreads();
+    }
+    int run = part[tid] - sum;
+    for (int i = b; i < e; ++i) {
+        offset[i] = run;
+        run += count[i];
+    }
+    if (tid == kScanThreads - 1) offset[nt] = part[tid];
+}
+
+__global__ __launch_bounds__(256) void k_render_fill(int ny, int nx, int ntx, int nstar,
+                                                     const int32_t* __restrict__ origin,
+                                                     const int* __restrict__ status, const int* __restrict__ offset,
+                                                     int* __restrict__ cursor, int* __restrict__ pairs) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= nstar || status[k] != 0) return;
+    int y0, y1, x0, x1;
+    footprint(ny, nx, origin[2 * k], origin[2 * k + 1], y0, y1, x0, x1);
+    for (int ty = y0 / kTile; ty <= (y1 - 1) / kTile; ++ty)
+        for (int tx = x0 / kTile; tx <= (x1 - 1) / kTile; ++tx) {
+            const int t = ty * ntx + tx;
+            pairs[offset[t] + atomicAdd(&cursor[t], 1)] = k;
+        }
+}
+
+// Ascending bitonic sort of v[0 .. n - 1] by the whole workgroup (n is the same for all its threads); v is in LDS or,
+// for a list longer than kSortChunk, the tile's own part of the work list in memory.  Every compare-exchange puts the
+// smaller value at the lower place, so the places n .. 2^k - 1 count as +infinity without being stored.
+__device__ void sort_indices(int* v, int n) {
+    __syncthreads();
+    if (n < 2) return;
+    int m = 2;
+    while (m < n) m <<= 1;
+    const int tid = threadIdx.x;
+    for (int k = 2; k <= m; k <<= 1) {
+        const int hk = k >> 1;
+        for (int i = tid; i < (m >> 1); i += kTileThreads) {
+            const int off = i & (hk - 1), a = ((i - off) << 1) + off, b = a + k - 1 - 2 * off;
+            if (b < n) {
+                const int va = v[a], vb = v[b];
+                if (va > vb) {
+                    v[a] = vb;
+                    v[b] = va;
+                }
+            }
+        }
+        __syncthreads();
+        for (int j = hk >> 1; j >= 1; j >>= 1) {
+            for (int i = tid; i < (m >> 1); i += kTileThreads) {
+                const int off = i & (j - 1), a = ((i - off) << 1) + off, b = a + j;
+                if (b < n) {
+                    const int va = v[a], vb = v[b];
+                    if (va > vb) {
+                        v[a] = vb;
+                        v[b] = va;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// the part of a model stamp a tile needs, in LDS, zero outside the model's pixels: tap (a, b) of the pixel at offset o
+struct TileStamp {
+    const double* base;
+    template <typename RE>
+    __device__ __forceinline__ RE at(int o, int, int, int a, int b) const {
+        return (RE)base[o + a * kStageStride + b];
+    }
+};
+
+// One star as a tile sees it: its parameters (the same for all threads) and the model pixel of stage[0][0]
+struct TileStar {
+    int op, oq, r0, c0;
+    double sc;
+    const double* P;
+    KeysTaps<double> ty{0.0}, tx{0.0};
+    __device__ __forceinline__ void load(int k, int Y0, int X0, const double* psf, const int32_t* index,
+                                         const int32_t* origin, const double* shift, const double* scale) {
+        op = origin[2 * k];
+        oq = origin[2 * k + 1];
+        sc = scale[k];
+        ty = KeysTaps<double>(shift ? shift[2 * k] : 0.0);
+        tx = KeysTaps<double>(shift ? shift[2 * k + 1] : 0.0);
+        P = psf + (size_t)(index ? index[k] : k) * (NS * NS);
+        r0 = Y0 - op + ty.f - 1;
+        c0 = X0 - oq + tx.f - 1;
+    }
+    // this thread's share of the kStageSide^2 model pixels the tile's taps can touch, zero outside the model
+    __device__ __forceinline__ void fetch(int tid, double (&pre)[kStageLoads]) const {
+#pragma unroll
+        for (int m = 0; m < kStageLoads; ++m) {
+            const int e = tid + m * kTileThreads, si = e / kStageSide, sj = e - si * kStageSide;
+            const int r = r0 + si, c = c0 + sj;
+            const bool in = e < kStageSide * kStageSide && (unsigned)r < (unsigned)NS && (unsigned)c < (unsigned)NS;
+            const double v = P[in ? r * NS + c : 0];
+            pre[m] = in ? v : 0.0;
+        }
+    }
+};
+
+// acc +- scale * val, the product rounded before the sum
+__device__ __forceinline__ double add_term(double acc, double scale, double val, bool subtract) {
+#pragma clang fp contract(off)
+    const double t = scale * val;
+    return subtract ? acc - t : acc + t;
+}
+
+__global__ __launch_bounds__(kTileThreads) void k_render_tiles(int ny, int nx, const double* image_in,
+                                                               const double* __restrict__ psf,
+                                                               const int32_t* __restrict__ index,
+                                                               const int32_t* __restrict__ origin,
+                                                               const double* __restrict__ shift,
+                                                               const double* __restrict__ scale, int subtract,
+                                                               const int* __restrict__ offset, int* pairs,
+                                                               double* image_out) {
+    __shared__ double stage[2 * kStageSide * kStageStride];
+    __shared__ int slist[kSortChunk];
+    const int tid = threadIdx.x, lx = tid & (kTile - 1), ly0 = tid / kTile;
+    const int t = blockIdx.y * gridDim.x + blockIdx.x;
+    const int Y0 = blockIdx.y * kTile, X0 = blockIdx.x * kTile, X = X0 + lx;
+    const int first = offset[t], n = offset[t + 1] - first;
+    // (image_out may be image_in: every pixel is read here and written at the end by the same thread)
+    double acc[kTilePix];
+    bool on[kTilePix];
+#pragma unroll
+    for (int j = 0; j < kTilePix; ++j) {
+        const int Y = Y0 + kTilePix * ly0 + j;
+        on[j] = Y < ny && X < nx;
+        acc[j] = on[j] && image_in ? image_in[(size_t)Y * nx + X] : 0.0;
+    }
+    const int* list = slist;
+    if (n <= kSortChunk) {
+        if (tid < n) slist[tid] = pairs[first + tid];
+        sort_indices(slist, n);
+    } else {
+        sort_indices(pairs + first, n);
+        list = pairs + first;
+    }
+    // Star i + 1 is fetched into registers while star i is evaluated, and the stage alternates between two buffers:
+    // one barrier per star (a buffer is rewritten two stars later, behind the barrier that every thread reaches only
+    // after its last read of it).
+    TileStar cur, nxt;
+    double pre[kStageLoads];
+    if (n > 0) {
+        cur.load(list[0], Y0, X0, psf, index, origin, shift, scale);
+        cur.fetch(tid, pre);
+    }
+    for (int i = 0; i < n; ++i) {
+        double* buf = stage + (i & 1) * (kStageSide * kStageStride);
+#pragma unroll
+        for (int m = 0; m < kStageLoads; ++m) {
+            const int e = tid + m * kTileThreads;
+            if (e < kStageSide * kStageSide) buf[(e / kStageSide) * kStageStride + e % kStageSide] = pre[m];
+        }
+        if (i + 1 < n) {
+            nxt.load(list[i + 1], Y0, X0, psf, index, origin, shift, scale);
+            nxt.fetch(tid, pre);
+        }
+        __syncthreads();
+        const TileStamp st{buf};
+        const int q = X - cur.oq;
+        // (a wave holds kWaveRows rows of the tile: it skips a star whose footprint lies above or below them)
+        const int pw = Y0 + (tid / 64) * kWaveRows - cur.op;
+        if (pw + kWaveRows > -kPsfApron && pw < NS + kPsfApron) {
+#pragma unroll
+            for (int j = 0; j < kTilePix; ++j) {
+                // (evaluated on every pixel of the wave -- the stage covers the whole tile, and the four rows of a
+                // thread share the loads of their taps --, applied on the footprint only)
+                const int ly = kTilePix * ly0 + j, p = Y0 + ly - cur.op;
+                double val, gy, gx;
+                psf_interp<double, false>(st, ly * kStageStride + lx, p, q, cur.ty, cur.tx, val, gy, gx);
+                const bool inside = on[j] && p >= -kPsfApron && p < NS + kPsfApron && q >= -kPsfApron &&
+                                    q < NS + kPsfApron;
+                const double sum = add_term(acc[j], cur.sc, val, subtract != 0);
+                acc[j] = inside ? sum : acc[j];
+            }
+        }
+        cur = nxt;
+    }
+#pragma unroll
+    for (int j = 0; j < kTilePix; ++j) {
+        const int Y = Y0 + kTilePix * ly0 + j;
+        if (on[j]) image_out[(size_t)Y * nx + X] = acc[j];
+    }
+}
+
+}  // namespace
+
+void launch_cut_stamps(hipStream_t s, int ny, int nx, const double* d_image, const double* d_var, int nstar,
+                       const int32_t* d_origin, double* d_stamps, double* d_var_out) {
+    hipLaunchKernelGGL(k_cut_stamps, dim3(nstar), dim3(256), 0, s, ny, nx, d_image, d_var, d_origin, d_stamps,
+                       d_var_out);
+}
+
+static int render_tiles_x(int nx) { return (nx + kTile - 1) / kTile; }
+
+size_t render_workspace_bytes(int ny, int nx, int nstar) {
+    const size_t nt = (size_t)render_tiles_x(ny) * render_tiles_x(nx);
+    // count [nt], cursor [nt], offset [nt + 1], status [nstar], pairs [9 nstar]: a footprint reaches at most 3 x 3 tiles
+    return (3 * nt + 1 + (size_t)nstar * 10) * sizeof(int);
+}
+
+void launch_render_stars(hipStream_t s, int ny, int nx, const double* d_image_in, int nstar, int npsf,
+                         const double* d_psf, const int32_t* d_index, const int32_t* d_origin, const double* d_shift,
+                         const double* d_scale, bool subtract, double* d_image_out, double* d_star_out, void* d_ws) {
+    static_assert(kPsfSide + kTile - 1 <= 3 * kTile, "a footprint reaches at most 3 x 3 tiles");
+    const int ntx = render_tiles_x(nx), nty = render_tiles_x(ny), nt = ntx * nty;
+    int* count = (int*)d_ws;
+    int* cursor = count + nt;
+    int* offset = cursor + nt;
+    int* status = offset + nt + 1;
+    int* pairs = status + nstar;
+    (void)hipMemsetAsync(count, 0, (size_t)2 * nt * sizeof(int), s);
+    const int gstar = (nstar + 255) / 256;
+    hipLaunchKernelGGL(k_render_prepare, dim3(gstar), dim3(256), 0, s, ny, nx, ntx, nstar, npsf, d_index, d_origin,
+                       d_shift, d_scale, count, status, d_star_out);
+    hipLaunchKernelGGL(k_render_scan, dim3(1), dim3(kScanThreads), 0, s, nt, count, offset);
+    hipLaunchKernelGGL(k_render_fill, dim3(gstar), dim3(256), 0, s, ny, nx, ntx, nstar, d_origin, status, offset, cursor,
+                       pairs);
+    hipLaunchKernelGGL(k_render_tiles, dim3(ntx, nty), dim3(kTileThreads), 0, s, ny, nx, d_image_in, d_psf, d_index,
+                       d_origin, d_shift, d_scale, subtract ? 1 : 0, offset, pairs, d_image_out);
+}
+
+}  // namespace mpsfr

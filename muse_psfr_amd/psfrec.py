@@ -655,6 +655,110 @@ def fit_star_groups_with_psf(stars, psf, positions, *, var=None, psf_index=None,
     return _make_table(cols)
 
 
+def _pixscale(pixscale):
+    if not (np.isfinite(pixscale) and pixscale > 0):
+        raise ValueError('pixscale must be positive')
+
+
+def cut_star_stamps(image, positions, var=None, dimpsf=40, *, pixscale=0.2, precision='mixed', device=0):
+    """Stamps of stars out of a frame, on the GPU: `image` (ny, nx), `positions` (n, 2) the (row, column) star centres
+    in pixels.  Stamp k starts at origin[k] = rint(positions[k]) - dimpsf // 2, so the star sits within half a pixel of
+    the stamp's pixel (dimpsf // 2, dimpsf // 2); where a stamp leaves the frame its pixels are NaN (variance 0), which
+    the fits mask.  var: the variance frame (the image's shape) or None.
+
+    Returns (stamps, var_stamps or None, origin): (n, dimpsf, dimpsf) arrays and the (n, 2) int32 origins that
+    render_star_field and subtract_stars take."""
+    try:
+        pos = np.asarray(positions, dtype=float)
+    except (TypeError, ValueError):
+        raise ValueError('positions must be a numeric array') from None
+    if pos.ndim != 2 or pos.shape[1] != 2 or pos.shape[0] < 1:
+        raise ValueError('positions must have the shape (n, 2)')
+    if not np.all(np.isfinite(pos)) or np.any(np.abs(pos) > _lib.MAX_ORIGIN - dimpsf):
+        raise ValueError('positions must be finite and within 2^30 pixels')
+    origin = (np.rint(pos) - dimpsf // 2).astype(np.int32)
+    ctx = get_context(128, pixscale, dimpsf, precision, device)
+    res = ctx.cut_stamps(image, origin, var=var)
+    return (res, None, origin) if var is None else (res[0], res[1], origin)
+
+
+def _shift_pixels(shift, pixscale):
+    if shift is None:
+        return None
+    try:
+        return np.asarray(shift, dtype=float) / pixscale
+    except (TypeError, ValueError):
+        raise ValueError('shift must be a numeric array') from None
+
+
+def render_star_field(shape, psf, origin, scale, shift=None, psf_index=None, pixscale=0.2, *, image=None,
+                      return_status=False, precision='mixed', device=0):
+    """A star field from model stamps, on the GPU: star k is scale[k] times the model stamp psf[psf_index[k]] (psf[k]
+    without psf_index; (..., 40, 40), e.g. reconstructed PSFs) resampled by cubic convolution at the sub-pixel `shift`
+    (n, 2) (row, column) in arcsec, like the fit tables; None: no shift), with its stamp's pixel [0][0] on the frame
+    pixel origin[k].  The stars are added to `image`, or to an empty frame of `shape` = (ny, nx).  Returns the frame;
+    with return_status also the (n,) render status (0 rendered, 1 off the frame)."""
+    _pixscale(pixscale)
+    ctx = get_context(128, pixscale, np.shape(psf)[-1] if np.ndim(psf) >= 2 else 40, precision, device)
+    res = ctx.render_stars(psf, origin, scale, shift=_shift_pixels(shift, pixscale), psf_index=psf_index, image=image,
+                           shape=shape, return_status=return_status)
+    return (res[0], res[1][:, 0].astype(np.int64)) if return_status else res
+
+
+def subtract_stars(image, psf, origin, fit, psf_index=None, pixscale=0.2, keep=None, *, precision='mixed', device=0):
+    """The residual frame of PSF-fitting photometry: `image` minus the fitted models of the stars of `fit`, a table of
+    fit_stars_with_psf (row k is the star whose stamp was cut at origin[k]) or of fit_star_groups_with_psf (one row per
+    source; its `group` column indexes `origin` and `psf_index`).  psf / psf_index as the fit took them; pixscale the
+    one the fit used (the tables hold the shift in arcsec).  Rows with status & 3 == 2 (not fitted) are not subtracted;
+    `keep` is an optional boolean mask of rows to leave in the frame -- subtract the neighbours and keep the target.
+    A row whose scale or shift is not finite, or whose shift lies beyond 8 pixels, is skipped like a status-2 row.
+
+    Returns (residual, status): the frame and per row 0 subtracted, 1 the star's footprint misses the frame, 2 skipped
+    because of its values, -1 not asked for (status 2 in the table, or kept)."""
+    _pixscale(pixscale)
+    try:
+        sc = np.asarray(fit['scale'], dtype=float).ravel()
+        sh = np.asarray(fit['shift'], dtype=float).reshape(-1, 2) / pixscale
+        st = np.asarray(fit['status']).astype(np.int64).ravel()
+    except (KeyError, TypeError, ValueError, IndexError):
+        raise ValueError('fit must be a table with the columns scale, shift and status') from None
+    nrow = sc.size
+    if nrow < 1 or sh.shape[0] != nrow or st.size != nrow:
+        raise ValueError('fit must hold at least one row')
+    try:
+        grp = np.asarray(fit['group']).astype(np.int64).ravel()
+    except KeyError:
+        grp = np.arange(nrow)
+    if grp.size != nrow:
+        raise ValueError('the group column must hold one entry per row')
+    og = _lib.star_origins(origin)
+    if np.any(grp < 0) or np.any(grp >= og.shape[0]):
+        raise ValueError('origin must hold one row per star (or group) of the fit')
+    ngroup = og.shape[0]
+    ps, ix, _, _ = _lib.psf_fit_arguments(ngroup, psf, psf_index, None, True, False, np.shape(psf)[-1])
+    ix = np.arange(ngroup, dtype=np.int32) if ix is None else ix
+    if keep is None:
+        kp = np.zeros(nrow, dtype=bool)
+    else:
+        kp = np.asarray(keep)
+        if kp.dtype != np.bool_ or kp.shape != (nrow,):
+            raise ValueError('keep must be a boolean mask with one entry per row of fit')
+    im, _ = _lib.frame_images(image)
+    status = np.full(nrow, -1, dtype=np.int64)
+    want = ((st & 3) != 2) & ~kp
+    with np.errstate(invalid='ignore'):
+        good = np.isfinite(sc) & np.all(np.abs(sh) <= _lib.FIT_PSF_MAX_SHIFT, axis=1)
+    status[want & ~good] = 2
+    rows = np.flatnonzero(want & good)
+    if rows.size == 0:
+        return im.copy(), status
+    ctx = get_context(128, pixscale, ps.shape[-1], precision, device)
+    res, out = ctx.render_stars(ps, og[grp[rows]], sc[rows], shift=sh[rows], psf_index=ix[grp[rows]], image=im,
+                                subtract=True, return_status=True)
+    status[rows] = out[:, 0].astype(np.int64)
+    return res, status
+
+
 METRIC_RADII = (0.2, 0.4, 0.6, 1.0, 2.0)      # default encircled-energy radii [arcsec]
 METRIC_BOXES = (0.2, 0.4, 0.6, 1.0)           # default ensquared-energy box sides [arcsec] (0.2": the WFM spaxel)
 METRIC_FRACTIONS = (0.5, 0.8)                 # default fractions of the EE radii
