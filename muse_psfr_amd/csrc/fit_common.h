@@ -1,5 +1,7 @@
 // Device code shared by the fit kernels (k_fit in stamps.hip, k_fit_ell in fit_ell.hip, k_fit_obs in fit_obs.hip,
-// k_fit_psf in fit_psf.hip, k_fit_group in fit_group_impl.h): wave-wide sums on the DPP path; the reciprocal,
+// k_fit_psf in fit_psf.hip, k_fit_group in fit_group_impl.h, k_fit_spec in fit_spec.hip): wave-wide sums on the DPP
+// path; the shared intake of the weighted fits, at the end of the file (fit_pixel, wave_first_max, FitStarScan, the
+// refusal rules, FitNorm; wave_first_max also serves k_fit_ell and k_stamp_metrics); the reciprocal,
 // square-root, exp and log forms of the Levenberg-Marquardt iterations and their fp64 polish; and, as templates over
 // the number of variables NP, the normal equations (FitNormEq), their Marquardt-scaled Cholesky factor, solve and
 // inverse (fit_chol, fit_chol_solve, fit_lm_solve, fit_spd_inverse), the damping and the predicted decrease
@@ -699,6 +701,114 @@ __device__ __forceinline__ void fit_ell_errors(const FitEllRow<ELL>& r, const do
     gfl[IETA] = r.flux * (r.n * r.n / (r.n - 1.0) - r.p2 * 0.69314718055994530942 / r.s2);
     o[20] = quad(gfl) * up;
 }
+
+// The shared intake of the weighted fits (all of it in k_fit_psf and k_fit_spec, the pixel rule,
+// the argmax step and the weight in k_fit_obs and k_fit_group, which keep the rest written out for their speed): what
+// a kernel does with a star between reading its pointers and its first model pass.  Everything here is exact whatever
+// the order -- maxima, minima, integer counts, products by powers of two -- so a row does not depend on which kernel
+// or which lane map took the star in.  A lane's pixels are o = lane + 64 m, m = 0 .. kFitPix - 1.
+constexpr int kFitPix = NS * NS / 64;
+static_assert(kFitPix * 64 == NS * NS, "the lane map assumes 1600 pixels");
+constexpr double kFitMinWeight = 0x1p-100;   // a used pixel keeps a weight > 0 (relative to the largest one)
+
+// The validity of a pixel.  used: the value is finite and, with a variance plane, the variance is finite and > 0;
+// every other pixel carries weight 0 and data 0 from the load on, so its stored value reaches no sum.
+struct FitPixel {
+    bool used, bad;       // bad: an infinite value under a valid variance (the row gets status 2)
+};
+__device__ __forceinline__ FitPixel fit_pixel(double d, double v, bool has_var) {
+    const bool vok = !has_var || (v > 0.0 && v < __builtin_inf());       // (NaN fails both)
+    const bool fin = fabs(d) < __builtin_inf();
+    FitPixel p;
+    p.used = vok && fin;
+    p.bad = vok && !fin && d == d;
+    return p;
+}
+
+// First maximum (in C order, as np.argmax) of a value per lane and its offset, over the wave; every lane gets it.
+// One step of the ladder (the tie rule, written once) and the ladder.
+__device__ __forceinline__ void wave_first_max_step(double& best, int& besto, int o) {
+    const double ob = __shfl_xor(best, o, 64);
+    const int oo = __shfl_xor(besto, o, 64);
+    if (ob > best || (ob == best && oo < besto)) { best = ob; besto = oo; }
+}
+__device__ __forceinline__ void wave_first_max(double& best, int& besto) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) wave_first_max_step(best, besto, o);
+}
+
+// The first pass over a star (vsrc is read only with has_var): the brightest used pixel (ARGMAX: and its offset, the
+// first in C order), the smallest valid variance, the largest used modulus, the used and the bad pixels.  add() takes
+// one pixel and reduce_step() is one step of the ladder over the wave: a kernel with a model stamp takes star and stamp
+// in one loop and one ladder (psf_scan, fit_psf_common.h: k_fit_psf, k_fit_spec).  k_fit_obs and k_fit_group keep
+// their first pass written out, for their speed (fit_obs.hip, fit_group_impl.h).
+template <bool ARGMAX>
+struct FitStarScan {
+    double best = -3.0e38, vmin = 3.0e38, amax = 0.0;
+    int besto = 0, nused = 0, nbad = 0;
+    __device__ __forceinline__ void add(int o, double d, double v, bool has_var) {
+        const FitPixel px = fit_pixel(d, v, has_var);
+        nused += px.used ? 1 : 0;
+        nbad += px.bad ? 1 : 0;
+        if (px.used) {
+            vmin = fmin(vmin, v);
+            amax = fmax(amax, fabs(d));
+            if constexpr (ARGMAX) {
+                if (d > best) { best = d; besto = o; }
+            } else {
+                best = fmax(best, d);
+            }
+        }
+    }
+    __device__ __forceinline__ void reduce_step(int o) {
+        if constexpr (ARGMAX) wave_first_max_step(best, besto, o);
+        else best = fmax(best, __shfl_xor(best, o, 64));
+        vmin = fmin(vmin, __shfl_xor(vmin, o, 64));
+        amax = fmax(amax, __shfl_xor(amax, o, 64));
+        nused += __shfl_xor(nused, o, 64);
+        nbad += __shfl_xor(nbad, o, 64);
+    }
+};
+
+// The refusal rules of a star.  An amplitude (the brightest used pixel of a star, the brightest pixel of a model
+// stamp, in modulus) must lie in [2^-40, 2^40]: zero and NaN fail.
+__device__ __forceinline__ bool fit_amplitude_ok(double a) { return a >= 0x1p-40 && a <= 0x1p40; }
+// the pixels: an infinite pixel, or too few used pixels for np variables
+__device__ __forceinline__ bool fit_pixels_refused(int nused, int nbad, int np) { return nbad > 0 || nused < np + 1; }
+// the range: the brightest used pixel outside the amplitude range, or a used pixel beyond 2^60 times the brightest
+// one in modulus (a deep negative outlier: the float copy of the normalised star must hold it)
+__device__ __forceinline__ bool fit_range_refused(double best, double amax) {
+    const double ab = fabs(best);
+    return !fit_amplitude_ok(ab) || amax > 0x1p60 * ab;
+}
+template <bool ARGMAX>
+__device__ __forceinline__ bool fit_star_refused(const FitStarScan<ARGMAX>& s, int np) {
+    return fit_pixels_refused(s.nused, s.nbad, np) || fit_range_refused(s.best, s.amax);
+}
+
+// the weight of a used pixel of variance v (1 without a variance plane), the largest one normalised by 2^kv
+__device__ __forceinline__ double fit_weight(double v, int kv) { return fmax(1.0 / ldexp(v, -kv), kFitMinWeight); }
+
+// The normalisation by powers of two, which is exact: the brightest used pixel into [1, 2) (data times 2^-kx), the
+// largest weight into (1/2, 1] (weights 2^kv / var).  A constant factor 4^k on the variance plane or 2^k on the data
+// therefore changes no bit of the normalised star.
+struct FitNorm {
+    int kx = 0, kv = 0;
+    double scale = 1.0;                      // 2^-kx
+    FitNorm() = default;
+    __device__ __forceinline__ FitNorm(double best, double vmin, bool has_var)
+        : kx(ilogb(fabs(best))), kv(has_var ? ilogb(vmin) : 0), scale(ldexp(1.0, -kx)) {}
+    // normalised value and weight of pixel o (0, 0 if it is not used); returns whether it is used
+    __device__ __forceinline__ bool pixel(const double* src, const double* vsrc, bool has_var, int o, double& dn,
+                                          double& wn) const {
+        const double d = src[o];
+        const double v = has_var ? vsrc[o] : 1.0;
+        const bool used = fit_pixel(d, v, has_var).used;
+        dn = used ? d * scale : 0.0;
+        wn = used ? fit_weight(v, kv) : 0.0;
+        return used;
+    }
+};
 
 }  // namespace
 }  // namespace mpsfr

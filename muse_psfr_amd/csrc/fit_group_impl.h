@@ -335,8 +335,6 @@ k_fit_group(int nstamp, const double* __restrict__ stamps, const double* __restr
     using D = GrpDim<K, MODE, BG>;
     using DL = GrpDim<K, GRP_FIXED, BG>;            // the linear problem in (F_k, [b])
     constexpr int NP = D::NP, NA = D::NA, NPL = DL::NP;
-    constexpr int NPX = NS * NS / 64;
-    static_assert(NPX * 64 == NS * NS, "the lane map assumes 1600 pixels");
     static_assert(K >= 2 && K <= kGroupMax, "2 to 4 sources");
     using S = RE;
     using Point = GrpPoint<K, MODE, BG, S>;
@@ -375,16 +373,20 @@ k_fit_group(int nstamp, const double* __restrict__ stamps, const double* __restr
         args_ok = args_ok && psf_inside<double>(s0[2 * k], s0[2 * k + 1]);
     }
     const double* psrc = psf + (size_t)(args_ok ? ip : 0) * NS * NS;
-    // first pass over the stamp: the brightest used pixel, the smallest valid variance, the number of used pixels;
+    // The intake of this kernel is written out over the shared pixel rule and weight (fit_pixel, fit_weight): through
+    // psf_scan, the shared refusal predicates, FitNorm and psf_stamp_load the rows were the same, but the compiler
+    // allocated the registers of the whole kernel differently and k_fit_group<double, 4, 1, true> ran 0.5 % slower
+    // (profiles/fit_intake_shared.md).  The rules are those of the shared intake.
+    // First pass over the stamp: the brightest used pixel, the smallest valid variance, the number of used pixels;
     // over the model stamp: max |P|, its sum, whether it is finite
     double best = -3.0e38, vmin = 3.0e38, amax = 0.0, pamax = 0.0, psum = 0.0;
     int nbad = 0, pbad = 0;
 #pragma unroll 5
-    for (int m = 0; m < NPX; ++m) {
+    for (int m = 0; m < kFitPix; ++m) {
         const int o = lane + m * 64;
         const double d = src[o];
         const double v = has_var ? vsrc[o] : 1.0;
-        const PsfPixel px = psf_pixel(d, v, has_var);
+        const FitPixel px = fit_pixel(d, v, has_var);
         nused += px.used ? 1 : 0;
         nbad += px.bad ? 1 : 0;
         if (px.used) {
@@ -408,7 +410,8 @@ k_fit_group(int nstamp, const double* __restrict__ stamps, const double* __restr
         nbad += __shfl_xor(nbad, o, 64);
         pbad += __shfl_xor(pbad, o, 64);
     }
-    // rows that are not fitted: the rules of k_fit_psf with NP the variables of the group
+    // rows that are not fitted: the rules of k_fit_psf with NP the variables of the group (fit_star_refused and
+    // PsfStampScan::refused, written out)
     const double ab = fabs(best);
     if (!args_ok || nbad > 0 || pbad > 0 || nused < NP + 1 || !(ab >= 0x1p-40 && ab <= 0x1p40) ||
         !(pamax >= 0x1p-40 && pamax <= 0x1p40) || amax > 0x1p60 * ab) {
@@ -425,13 +428,13 @@ k_fit_group(int nstamp, const double* __restrict__ stamps, const double* __restr
     for (int o = lane; o < kPsfSide * kPsfStride; o += 64) pl[o] = (RE)0;
     __syncthreads();
 #pragma unroll 5
-    for (int m = 0; m < NPX; ++m) {
+    for (int m = 0; m < kFitPix; ++m) {
         const int o = lane + m * 64;
         const double d = src[o];
         const double v = has_var ? vsrc[o] : 1.0;
-        const bool used = psf_pixel(d, v, has_var).used;
+        const bool used = fit_pixel(d, v, has_var).used;
         sp[o] = (RE)(used ? d * scale : 0.0);
-        sw[o] = (RE)(used ? fmax(1.0 / ldexp(v, -kv), kPsfMinWeight) : 0.0);
+        sw[o] = (RE)(used ? fit_weight(v, kv) : 0.0);
         const int p = o / NS, q = o - p * NS;
         pl[(p + kPsfApron) * kPsfStride + q + kPsfApron] = (RE)(psrc[o] * pscale);
     }

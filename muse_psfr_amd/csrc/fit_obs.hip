@@ -25,7 +25,6 @@ namespace mpsfr {
 
 namespace {
 
-constexpr double kObsMinWeight = 0x1p-100;   // a used pixel keeps a weight > 0 (relative to the largest one)
 constexpr int FLAG_BACKGROUND = 1, FLAG_ELLIPTICAL = 2;      // MPSFR_FIT_BACKGROUND / MPSFR_FIT_ELLIPTICAL
 
 // variables of a variant: I, p0, q0, w, [e1, e2,] eta, [b]
@@ -255,27 +254,12 @@ struct ObsModel {
     __device__ __forceinline__ bool inside(const S* vn) const { return obs_inside<ELL, BG, S>(vn); }
 };
 
-// the validity of a pixel and its weight before the normalisation (1 / var, or 1 without a variance plane)
-struct ObsPixel {
-    bool used, bad;       // bad: an infinite value under a valid variance (the row gets status 2)
-};
-__device__ __forceinline__ ObsPixel obs_pixel(double d, double v, bool has_var) {
-    const bool vok = !has_var || (v > 0.0 && v < __builtin_inf());       // (NaN fails both)
-    const bool fin = fabs(d) < __builtin_inf();
-    ObsPixel p;
-    p.used = vok && fin;
-    p.bad = vok && !fin && d == d;
-    return p;
-}
-
 // one wave per stamp; RE = float: mixed mode (float iterations + fp64 polish), RE = double: f64 mode
 template <typename RE, bool ELL, bool BG>
 __global__ void __launch_bounds__(64)
 k_fit_obs(int nstamp, const double* __restrict__ stamps, const double* __restrict__ var, double* __restrict__ fit) {
     using D = ObsDim<ELL, BG>;
     constexpr int NP = D::NP, NA = D::NA;
-    constexpr int NPX = NS * NS / 64;
-    static_assert(NPX * 64 == NS * NS, "the lane map assumes 1600 pixels");
     using S = RE;
     const int lane = threadIdx.x & 63;
     const int st = (int)blockIdx.x;
@@ -285,15 +269,19 @@ k_fit_obs(int nstamp, const double* __restrict__ stamps, const double* __restric
     const double* vsrc = has_var ? var + (size_t)st * NS * NS : src;
     __shared__ RE sp[NS * NS];
     __shared__ RE sw[NS * NS];
-    // first pass over the stamp: the brightest used pixel, the smallest valid variance, the number of used pixels
+    // The intake of this kernel is written out, over the shared pixel rule, argmax step and weight (fit_pixel,
+    // wave_first_max_step, fit_weight): through FitStarScan, the shared refusal predicates or FitNorm the compiler
+    // allocates the registers of the whole kernel differently, and the elliptical instantiations with a background ran
+    // 2 % slower (profiles/fit_intake_shared.md).  The rules are those of the shared intake.
+    // First pass over the stamp: the brightest used pixel, the smallest valid variance, the number of used pixels.
     double best = -3.0e38, vmin = 3.0e38, amax = 0.0;
     int besto = 0, nused = 0, nbad = 0;
 #pragma unroll 5
-    for (int m = 0; m < NPX; ++m) {
+    for (int m = 0; m < kFitPix; ++m) {
         const int o = lane + m * 64;
         const double d = src[o];
         const double v = has_var ? vsrc[o] : 1.0;
-        const ObsPixel px = obs_pixel(d, v, has_var);
+        const FitPixel px = fit_pixel(d, v, has_var);
         nused += px.used ? 1 : 0;
         nbad += px.bad ? 1 : 0;
         if (px.used) {
@@ -302,12 +290,9 @@ k_fit_obs(int nstamp, const double* __restrict__ stamps, const double* __restric
             if (d > best) { best = d; besto = o; }
         }
     }
-    // argmax (first maximum in C order, as np.argmax), minimum and counts over the wave
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-        const double ob = __shfl_xor(best, o, 64);
-        const int oo = __shfl_xor(besto, o, 64);
-        if (ob > best || (ob == best && oo < besto)) { best = ob; besto = oo; }
+        wave_first_max_step(best, besto, o);
         vmin = fmin(vmin, __shfl_xor(vmin, o, 64));
         amax = fmax(amax, __shfl_xor(amax, o, 64));
         nused += __shfl_xor(nused, o, 64);
@@ -315,8 +300,7 @@ k_fit_obs(int nstamp, const double* __restrict__ stamps, const double* __restric
     }
     double* orow = fit + (size_t)st * NFIT_ELL;
     // rows that are not fitted: an infinite pixel, too few used pixels, a brightest used pixel outside [2^-40, 2^40],
-    // a used pixel beyond 2^60 times the brightest one in modulus (a deep negative outlier: the float copy of the
-    // normalised stamp must hold it)
+    // a used pixel beyond 2^60 times the brightest one in modulus (fit_star_refused, written out)
     const double ab = fabs(best);
     if (nbad > 0 || nused < NP + 1 || !(ab >= 0x1p-40 && ab <= 0x1p40) || amax > 0x1p60 * ab) {
         if (lane == 0) {
@@ -328,20 +312,21 @@ k_fit_obs(int nstamp, const double* __restrict__ stamps, const double* __restric
         }
         return;
     }
-    // normalisation by powers of two: the brightest used pixel into [1, 2), the largest weight into (1/2, 1]
+    // normalisation by powers of two (FitNorm, written out): the brightest used pixel into [1, 2), the largest weight
+    // into (1/2, 1]; the normalised stamp and its weights into LDS, and in the same pass the sums of the outer ring
     const int kx = ilogb(ab);
     const double scale = ldexp(1.0, -kx);
     const int kv = has_var ? ilogb(vmin) : 0;
     double ringsum = 0.0;
     int ringcnt = 0;
 #pragma unroll 5
-    for (int m = 0; m < NPX; ++m) {
+    for (int m = 0; m < kFitPix; ++m) {
         const int o = lane + m * 64;
         const double d = src[o];
         const double v = has_var ? vsrc[o] : 1.0;
-        const bool used = obs_pixel(d, v, has_var).used;
+        const bool used = fit_pixel(d, v, has_var).used;
         const double dn = used ? d * scale : 0.0;
-        const double wn = used ? fmax(1.0 / ldexp(v, -kv), kObsMinWeight) : 0.0;
+        const double wn = used ? fit_weight(v, kv) : 0.0;
         sp[o] = (RE)dn;
         sw[o] = (RE)wn;
         if constexpr (BG) {

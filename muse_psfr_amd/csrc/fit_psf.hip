@@ -8,8 +8,8 @@
 // FIR over the model stamp in LDS; d m / d dp = -F sum c'(y - k) c(x - l) P[k][l] comes from the same 16 taps.
 // The structure is k_fit_obs's: one wave per star, 25 pixels per lane in the 8 x 8-block pixel map, wave-wide sums on
 // the DPP path (wave_total), the shared Levenberg-Marquardt descent and polish (fit_lm_descend, fit_polish over PsfModel); the used
-// pixels, the weight plane and the power-of-two normalisation of data and weights are its rules too (obs_pixel there,
-// psf_pixel here).  The normal equations, their factorisation, solve and inverse are fit_common.h's, for NP = 1 to 4.
+// pixels, the weight plane and the power-of-two normalisation of data and weights are the shared intake's
+// (fit_common.h, fit_psf_common.h).  The normal equations, their factorisation, solve and inverse are fit_common.h's, for NP = 1 to 4.
 // New here: the model stamp in LDS with a zero apron of 10 pixels (|dp|, |dq| <= 8 and taps -1 .. +2: no bounds test
 // inside the domain), rows of 72 elements -- 72 = 8 mod 32, so the 4 rows x 8 columns of a 32-lane half fall on 32
 // different banks (ds_read_b32; 16 bank pairs twice for ds_read_b64), as the 40-element rows of the star do; the model
@@ -206,8 +206,6 @@ k_fit_psf(int nstamp, const double* __restrict__ stamps, const double* __restric
     using D = PsfDim<SHIFT, BG>;
     using DL = PsfDim<false, BG>;                  // the linear problem in (F, [b])
     constexpr int NP = D::NP, NA = D::NA, NPL = DL::NP;
-    constexpr int NPX = NS * NS / 64;
-    static_assert(NPX * 64 == NS * NS, "the lane map assumes 1600 pixels");
     using S = RE;
     const int lane = threadIdx.x & 63;
     const int st = (int)blockIdx.x;
@@ -219,13 +217,13 @@ k_fit_psf(int nstamp, const double* __restrict__ stamps, const double* __restric
     __shared__ RE sw[NS * NS];
     __shared__ RE pl[kPsfSide * kPsfStride];
     double* orow = fit + (size_t)st * NFIT_PSF;
-    int nused = 0;
+    FitStarScan<true> star;
     auto refuse = [&]() {                   // a row that is not fitted: zeros, status 2, the number of used pixels
         if (lane == 0) {
 #pragma unroll
             for (int k = 0; k < NFIT_PSF; ++k) orow[k] = 0.0;
             orow[10] = 2.0;
-            orow[11] = (double)nused;
+            orow[11] = (double)star.nused;
         }
     };
     // the model stamp of this star and the given shift (the device form has not seen either on the host)
@@ -234,76 +232,24 @@ k_fit_psf(int nstamp, const double* __restrict__ stamps, const double* __restric
     if (shift) { dp0 = shift[2 * (size_t)st]; dq0 = shift[2 * (size_t)st + 1]; }
     const bool args_ok = ip >= 0 && ip < npsf && psf_inside<double>(dp0, dq0);
     const double* psrc = psf + (size_t)(args_ok ? ip : 0) * NS * NS;
-    // first pass over the star: the brightest used pixel, the smallest valid variance, the number of used pixels;
-    // over the model stamp: its first maximum, max |P|, its sum, whether it is finite
-    double best = -3.0e38, vmin = 3.0e38, amax = 0.0, pbest = -3.0e38, pamax = 0.0, psum = 0.0;
-    int besto = 0, pbesto = 0, nbad = 0, pbad = 0;
-#pragma unroll 5
-    for (int m = 0; m < NPX; ++m) {
-        const int o = lane + m * 64;
-        const double d = src[o];
-        const double v = has_var ? vsrc[o] : 1.0;
-        const PsfPixel px = psf_pixel(d, v, has_var);
-        nused += px.used ? 1 : 0;
-        nbad += px.bad ? 1 : 0;
-        if (px.used) {
-            vmin = fmin(vmin, v);
-            amax = fmax(amax, fabs(d));
-            if (d > best) { best = d; besto = o; }
-        }
-        const double pv = psrc[o];
-        pbad += fabs(pv) < __builtin_inf() ? 0 : 1;
-        pamax = fmax(pamax, fabs(pv));
-        psum += pv;
-        if (pv > pbest) { pbest = pv; pbesto = o; }
-    }
-    psum = wave_total(psum);
-    // argmax (first maximum in C order, as np.argmax), minimum and counts over the wave
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ob = __shfl_xor(best, o, 64);
-        const int oo = __shfl_xor(besto, o, 64);
-        if (ob > best || (ob == best && oo < besto)) { best = ob; besto = oo; }
-        const double pb = __shfl_xor(pbest, o, 64);
-        const int po = __shfl_xor(pbesto, o, 64);
-        if (pb > pbest || (pb == pbest && po < pbesto)) { pbest = pb; pbesto = po; }
-        vmin = fmin(vmin, __shfl_xor(vmin, o, 64));
-        amax = fmax(amax, __shfl_xor(amax, o, 64));
-        pamax = fmax(pamax, __shfl_xor(pamax, o, 64));
-        nused += __shfl_xor(nused, o, 64);
-        nbad += __shfl_xor(nbad, o, 64);
-        pbad += __shfl_xor(pbad, o, 64);
-    }
-    // rows that are not fitted: a model index or a given shift outside its range, an infinite pixel, too few used
-    // pixels, a brightest used pixel or a brightest model pixel outside [2^-40, 2^40] in modulus (an all-zero model
-    // stamp included), a model stamp that is not finite, a used pixel beyond 2^60 times the brightest one in modulus
-    // (the float copy of the normalised star must hold it)
-    const double ab = fabs(best);
-    if (!args_ok || nbad > 0 || pbad > 0 || nused < NP + 1 || !(ab >= 0x1p-40 && ab <= 0x1p40) ||
-        !(pamax >= 0x1p-40 && pamax <= 0x1p40) || amax > 0x1p60 * ab) {
+    // first pass over the star and over the model stamp (the shared intake)
+    PsfStampScan<true> mod;
+    psf_scan(star, mod, src, vsrc, has_var, psrc, lane);
+    // rows that are not fitted: a model index or a given shift outside its range, and the rules of the intake for the
+    // star and for the model stamp
+    if (!args_ok || fit_star_refused(star, NP) || mod.refused()) {
         refuse();
         return;
     }
-    // normalisation by powers of two: the brightest used pixel into [1, 2), the largest weight into (1/2, 1], the
-    // brightest model pixel (in modulus) into [1, 2)
-    const int kx = ilogb(ab);
-    const double scale = ldexp(1.0, -kx);
-    const int kv = has_var ? ilogb(vmin) : 0;
-    const int kp = ilogb(pamax);
+    const FitNorm norm(star.best, star.vmin, has_var);
+    const double scale = norm.scale;
+    const int kx = norm.kx, kv = norm.kv, nused = star.nused, besto = star.besto, pbesto = mod.pbesto;
+    const int kp = ilogb(mod.pamax);
     const double pscale = ldexp(1.0, -kp);
-    for (int o = lane; o < kPsfSide * kPsfStride; o += 64) pl[o] = (RE)0;
+    psf_stamp_clear(pl, lane);
     __syncthreads();
-#pragma unroll 5
-    for (int m = 0; m < NPX; ++m) {
-        const int o = lane + m * 64;
-        const double d = src[o];
-        const double v = has_var ? vsrc[o] : 1.0;
-        const bool used = psf_pixel(d, v, has_var).used;
-        sp[o] = (RE)(used ? d * scale : 0.0);
-        sw[o] = (RE)(used ? fmax(1.0 / ldexp(v, -kv), kPsfMinWeight) : 0.0);
-        const int p = o / NS, q = o - p * NS;
-        pl[(p + kPsfApron) * kPsfStride + q + kPsfApron] = (RE)(psrc[o] * pscale);
-    }
+    const PsfStarPlanes<RE> planes{norm, src, vsrc, has_var, sp, sw};
+    const double psum = wave_total(psf_stamp_load(psrc, kp, pl, lane, planes));
     __syncthreads();                 // (one wave: the passes read pixels other lanes wrote)
     // Start values: the given shift, or the brightest used pixel of the star minus the first maximum of the model
     // stamp, brought into the domain; F and b from the closed-form weighted linear solve at that shift.

@@ -1,8 +1,10 @@
-// Device code shared by the PSF-model fits (k_fit_psf in fit_psf.hip, k_fit_group in fit_group_impl.h): the constants
-// of the model stamp in LDS, the Keys tap weights of one axis (KeysTaps), the model stamp with its
-// apron in LDS and the fp64 one in memory (LdsStamp, GlobalStamp), the 4 x 4 FIR with its derivatives (psf_interp),
-// the domain of the shift (psf_inside) and the validity of a pixel (psf_pixel).  See DESIGN.md sections 18 and 19.
-// Everything here has internal linkage.
+// Device code shared by the kernels that resample a PSF model stamp (k_fit_psf in fit_psf.hip, k_fit_group in
+// fit_group_impl.h, k_fit_spec in fit_spec.hip, k_render_tiles in render.hip): the constants of the model stamp in LDS,
+// the Keys tap weights of one axis (KeysTaps), the model stamp with its apron in LDS and the fp64 one in memory
+// (LdsStamp, GlobalStamp), the 4 x 4 FIR with its derivatives (psf_interp), the domain of the shift (psf_inside) and
+// the intake of a model stamp (k_fit_psf, k_fit_spec): its first pass, taken with the star's (PsfStampScan,
+// psf_scan), its refusal rule and its load into the apron layout (psf_stamp_clear, psf_stamp_load).  The intake of the
+// star is fit_common.h's.  See DESIGN.md sections 13, 18 and 19.  Everything here has internal linkage.
 #pragma once
 #include "device_common.h"
 #include "fit_common.h"
@@ -14,7 +16,6 @@ constexpr int kPsfApron = 10;
 constexpr int kPsfSide = NS + 2 * kPsfApron;       // 60 rows
 constexpr int kPsfStride = 72;                     // elements per row (the last 12 are never read)
 constexpr double kPsfMaxShift = 8.0;               // |dp|, |dq| bound
-constexpr double kPsfMinWeight = 0x1p-100;         // a used pixel keeps a weight > 0 (relative to the largest one)
 constexpr int FLAG_BACKGROUND = 1, FLAG_FIXED_SHIFT = 4;     // MPSFR_FIT_BACKGROUND / MPSFR_FIT_FIXED_SHIFT
 static_assert(kPsfApron >= (int)kPsfMaxShift + 2 && kPsfStride >= kPsfSide, "the taps stay inside the apron");
 
@@ -96,17 +97,93 @@ __device__ __forceinline__ bool psf_inside(S dp, S dq) {          // (NaN fails)
     return fabs(dp) <= (S)kPsfMaxShift && fabs(dq) <= (S)kPsfMaxShift;
 }
 
-// the validity of a pixel (obs_pixel of fit_obs.hip)
-struct PsfPixel {
-    bool used, bad;       // bad: an infinite value under a valid variance (the row gets status 2)
+// The first pass over a model stamp: max |P|, the pixels that are not finite and, with ARGMAX, its first maximum in C
+// order; add() takes one pixel, reduce_step() is one step of the ladder over the wave.
+template <bool ARGMAX>
+struct PsfStampScan {
+    double pbest = -3.0e38, pamax = 0.0;
+    int pbesto = 0, pbad = 0;
+    __device__ __forceinline__ void add(int o, double pv) {
+        pbad += fabs(pv) < __builtin_inf() ? 0 : 1;
+        pamax = fmax(pamax, fabs(pv));
+        if constexpr (ARGMAX) {
+            if (pv > pbest) { pbest = pv; pbesto = o; }
+        }
+    }
+    __device__ __forceinline__ void reduce_step(int o) {
+        if constexpr (ARGMAX) wave_first_max_step(pbest, pbesto, o);
+        pamax = fmax(pamax, __shfl_xor(pamax, o, 64));
+        pbad += __shfl_xor(pbad, o, 64);
+    }
+    // a model stamp that is not fitted: not finite, or its brightest pixel outside [2^-40, 2^40] in modulus (an
+    // all-zero stamp included)
+    __device__ __forceinline__ bool refused() const { return pbad > 0 || !fit_amplitude_ok(pamax); }
 };
-__device__ __forceinline__ PsfPixel psf_pixel(double d, double v, bool has_var) {
-    const bool vok = !has_var || (v > 0.0 && v < __builtin_inf());       // (NaN fails both)
-    const bool fin = fabs(d) < __builtin_inf();
-    PsfPixel p;
-    p.used = vok && fin;
-    p.bad = vok && !fin && d == d;
-    return p;
+
+// the first pass over a star and its model stamp: one loop over a lane's pixels (o = lane + 64 m), one ladder
+template <bool AS, bool AM>
+__device__ __forceinline__ void psf_scan(FitStarScan<AS>& star, PsfStampScan<AM>& mod, const double* src,
+                                         const double* vsrc, bool has_var, const double* psrc, int lane) {
+#pragma unroll 5
+    for (int m = 0; m < kFitPix; ++m) {
+        const int o = lane + m * 64;
+        star.add(o, src[o], has_var ? vsrc[o] : 1.0, has_var);
+        mod.add(o, psrc[o]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        star.reduce_step(o);
+        mod.reduce_step(o);
+    }
+}
+
+// the apron stamp, all of it, to zero (the caller synchronises before the interior is written)
+template <typename LT>
+__device__ __forceinline__ void psf_stamp_clear(LT* pl, int lane) {
+    for (int o = lane; o < kPsfSide * kPsfStride; o += 64) pl[o] = (LT)0;
+}
+// The planes of a star in LDS and what fills them: the normalised values into sp, the weights into sw
+template <typename LT>
+struct PsfStarPlanes {
+    const FitNorm& norm;
+    const double *src, *vsrc;
+    bool has_var;
+    LT *sp, *sw;
+};
+// The model stamp times 2^-kp (its brightest pixel in modulus into [1, 2)) into the interior of the apron stamp and,
+// with STAR, the normalised star and its weights into their planes in the same loop.  Returns the lane's share of
+// sum P, its pixels added in ascending m: wave_total of it is the sum the flux columns use.
+template <bool STAR, typename LT>
+__device__ __forceinline__ double psf_stamp_load_loop(const double* __restrict__ psrc, int kp, LT* pl, int lane,
+                                                      const PsfStarPlanes<LT>* star) {
+    const double pscale = ldexp(1.0, -kp);
+    double ps = 0.0;
+#pragma unroll 5
+    for (int m = 0; m < kFitPix; ++m) {
+        const int o = lane + m * 64;
+        if constexpr (STAR) {
+            double dn, wn;
+            star->norm.pixel(star->src, star->vsrc, star->has_var, o, dn, wn);
+            star->sp[o] = (LT)dn;
+            star->sw[o] = (LT)wn;
+        }
+        const double pv = psrc[o];
+        ps += pv;
+        const int p = o / NS, q = o - p * NS;
+        pl[(p + kPsfApron) * kPsfStride + q + kPsfApron] = (LT)(pv * pscale);
+    }
+    return ps;
+}
+// the model stamp alone (k_fit_spec, which reads the layers of its star from memory at every pass)
+template <typename LT>
+__device__ __forceinline__ double psf_stamp_load(const double* __restrict__ psrc, int kp, LT* pl, int lane) {
+    return psf_stamp_load_loop<false, LT>(psrc, kp, pl, lane, nullptr);
+}
+// the model stamp and the star (k_fit_psf)
+template <typename LT>
+__device__ __forceinline__ double psf_stamp_load(const double* __restrict__ psrc, int kp, LT* pl, int lane,
+                                                 const PsfStarPlanes<LT>& star) {
+    return psf_stamp_load_loop<true, LT>(psrc, kp, pl, lane, &star);
 }
 
 }  // namespace

@@ -34,8 +34,6 @@ constexpr int FLAG_DRIFT = 16;                       // MPSFR_FIT_DRIFT
 constexpr int kSpecStamp = kPsfSide * kPsfStride;    // elements of a model stamp with its apron
 constexpr short kSpecLeftOut = -32768;               // lkp of a layer that is not fitted
 constexpr int kSpecRed = 16;                         // values a wave hands to the combination
-constexpr int kSpecPix = NS * NS / 64;               // pixels per lane
-static_assert(kSpecPix * 64 == NS * NS, "the lane map assumes 1600 pixels");
 static_assert(2 * NS * NS <= kSpecStamp, "the collapsed images of the start fit into a wave's stamp");
 
 // what a wave needs of its star to read a layer
@@ -43,34 +41,8 @@ struct SpecStar {
     const double *src, *vsrc, *psrc, *x;     // cube, variance (or the cube), model cube of the star; x [nl] or nullptr
     bool has_var;
     int nl;
-    double scale;                            // 2^-kx of the data
-    int kv;                                  // the weights are 2^kv / var
+    FitNorm norm;                            // one normalisation of data and weights for all layers of the star
 };
-
-// normalised value and weight of a pixel (0, 0 if it is not used)
-__device__ __forceinline__ void spec_pixel(const SpecStar& s, const double* src, const double* vsrc, int o, double& dn,
-                                           double& wn) {
-    const double d = src[o];
-    const double v = s.has_var ? vsrc[o] : 1.0;
-    const bool used = psf_pixel(d, v, s.has_var).used;
-    dn = used ? d * s.scale : 0.0;
-    wn = used ? fmax(1.0 / ldexp(v, -s.kv), kPsfMinWeight) : 0.0;
-}
-
-// layer l's model stamp, times 2^-kp, into the interior of the wave's apron stamp; returns the lane's share of sum P
-__device__ __forceinline__ double spec_load_stamp(const double* __restrict__ psrc, int kp, double* pl, int lane) {
-    const double pscale = ldexp(1.0, -kp);
-    double ps = 0.0;
-#pragma unroll 5
-    for (int m = 0; m < kSpecPix; ++m) {
-        const int o = lane + m * 64;
-        const int p = o / NS, q = o - p * NS;
-        const double pv = psrc[o];
-        ps += pv;
-        pl[(p + kPsfApron) * kPsfStride + q + kPsfApron] = pv * pscale;
-    }
-    return ps;
-}
 
 // The linear problem of a layer at the shift (dpl, dql): the normal matrix over (F, [b]), its right-hand side, the
 // solution and the inverse.  ok: the matrix is positive definite.
@@ -98,7 +70,7 @@ __device__ __forceinline__ void spec_linear(const SpecStar& s, const double* src
             const int o = p * NS + q;
             double val, gy, gx, dn, wn;
             psf_interp<double, false>(st, p * kPsfStride + q, p, q, ty, tx, val, gy, gx);
-            spec_pixel(s, src, vsrc, o, dn, wn);
+            s.norm.pixel(src, vsrc, s.has_var, o, dn, wn);
             nu += wn > 0.0 ? 1 : 0;
             const double wp = wn * val;
             app += wp * val;
@@ -158,7 +130,7 @@ __device__ __forceinline__ void spec_blocks(const SpecStar& s, const double* src
             const int o = p * NS + q;
             double val, gy, gx, dn, wn;
             psf_interp<double, true>(st, p * kPsfStride + q, p, q, ty, tx, val, gy, gx);
-            spec_pixel(s, src, vsrc, o, dn, wn);
+            s.norm.pixel(src, vsrc, s.has_var, o, dn, wn);
             const double r = (F * val + b) - dn;
             const double j0 = -F * gy, j1 = -F * gx;
             const double wr = wn * r;
@@ -257,7 +229,7 @@ struct SpecModel {
             const int kp = l < s.nl ? __builtin_amdgcn_readfirstlane((int)lkp[l]) : (int)kSpecLeftOut;
             const bool act = kp != (int)kSpecLeftOut;
             const size_t off = (size_t)(act ? l : 0) * NS * NS;
-            if (act) spec_load_stamp(s.psrc + off, kp, pl, lane);
+            if (act) psf_stamp_load(s.psrc + off, kp, pl, lane);
             __syncthreads();
             if (act) {
                 const double xl = DRIFT ? sgpr(s.x[l]) : 0.0;
@@ -315,16 +287,6 @@ struct SpecModel {
     }
 };
 
-// first maximum (in C order) of a value per lane and its offset, over the wave
-__device__ __forceinline__ void spec_argmax(double& best, int& besto) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ob = __shfl_xor(best, o, 64);
-        const int oo = __shfl_xor(besto, o, 64);
-        if (ob > best || (ob == best && oo < besto)) { best = ob; besto = oo; }
-    }
-}
-
 template <typename RE, bool DRIFT, bool BG>
 __global__ void __launch_bounds__(64 * kSpecWaves)
 k_fit_spec(int nstar, int nl, const double* __restrict__ cubes, const double* __restrict__ var, int npsf,
@@ -356,8 +318,6 @@ k_fit_spec(int nstar, int nl, const double* __restrict__ cubes, const double* __
     s.x = x;
     s.has_var = has_var;
     s.nl = nl;
-    s.scale = 1.0;
-    s.kv = 0;
 
     // First pass over the wave's layers: which are fitted, and over the fitted ones the brightest used pixel, the
     // smallest valid variance, the largest used modulus, the used pixels, the range of x.  The layer blocks get their
@@ -366,40 +326,16 @@ k_fit_spec(int nstar, int nl, const double* __restrict__ cubes, const double* __
     int wused = 0, wfit = 0;
     for (int l = wave; l < nl; l += kSpecWaves) {
         const size_t off = (size_t)l * NS * NS;
-        double best = -3.0e38, vmin = 3.0e38, amax = 0.0, pamax = 0.0;
-        int nused = 0, nbad = 0, pbad = 0;
-#pragma unroll 5
-        for (int m = 0; m < kSpecPix; ++m) {
-            const int o = lane + m * 64;
-            const double d = s.src[off + o];
-            const double v = has_var ? s.vsrc[off + o] : 1.0;
-            const PsfPixel px = psf_pixel(d, v, has_var);
-            nused += px.used ? 1 : 0;
-            nbad += px.bad ? 1 : 0;
-            if (px.used) {
-                vmin = fmin(vmin, v);
-                amax = fmax(amax, fabs(d));
-                best = fmax(best, d);
-            }
-            const double pv = s.psrc[off + o];
-            pbad += fabs(pv) < __builtin_inf() ? 0 : 1;
-            pamax = fmax(pamax, fabs(pv));
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            best = fmax(best, __shfl_xor(best, o, 64));
-            vmin = fmin(vmin, __shfl_xor(vmin, o, 64));
-            amax = fmax(amax, __shfl_xor(amax, o, 64));
-            pamax = fmax(pamax, __shfl_xor(pamax, o, 64));
-            nused += __shfl_xor(nused, o, 64);
-            nbad += __shfl_xor(nbad, o, 64);
-            pbad += __shfl_xor(pbad, o, 64);
-        }
-        const bool fitted = nbad == 0 && pbad == 0 && nused >= NLIN + 1 && pamax >= 0x1p-40 && pamax <= 0x1p40;
+        FitStarScan<false> ls;
+        PsfStampScan<false> lm;
+        psf_scan(ls, lm, s.src + off, s.vsrc + off, has_var, s.psrc + off, lane);
+        const int nused = ls.nused;
+        // a layer is fitted if its pixels suffice for its linear variables and its model stamp is fit to use
+        const bool fitted = !fit_pixels_refused(nused, ls.nbad, NLIN) && !lm.refused();
         if (fitted) {
-            wbest = fmax(wbest, best);
-            wvmin = fmin(wvmin, vmin);
-            wamax = fmax(wamax, amax);
+            wbest = fmax(wbest, ls.best);
+            wvmin = fmin(wvmin, ls.vmin);
+            wamax = fmax(wamax, ls.amax);
             wused += nused;
             wfit += 1;
             if constexpr (DRIFT) {
@@ -409,7 +345,7 @@ k_fit_spec(int nstar, int nl, const double* __restrict__ cubes, const double* __
             }
         }
         if (lane == 0) {
-            lkp[l] = fitted ? (short)ilogb(pamax) : kSpecLeftOut;
+            lkp[l] = fitted ? (short)ilogb(lm.pamax) : kSpecLeftOut;
             double* ol = orow + kSpecHead + (size_t)kSpecLayer * l;
 #pragma unroll
             for (int k = 0; k < kSpecLayer; ++k) ol[k] = 0.0;
@@ -446,20 +382,17 @@ k_fit_spec(int nstar, int nl, const double* __restrict__ cubes, const double* __
         }
     };
     // Rows that are not fitted: a model index or a given start outside its range, no fitted layer, too few used pixels
-    // for the variables, with the drift fewer than two distinct x among the fitted layers, a brightest used pixel
-    // outside [2^-40, 2^40] in modulus, a used pixel beyond 2^60 times the brightest one in modulus.
-    const double ab = fabs(best);
-    if (!args_ok || nfit < 1 || dofi < 1 || (DRIFT && !(xmax > xmin)) || !(ab >= 0x1p-40 && ab <= 0x1p40) ||
-        amax > 0x1p60 * ab) {
+    // for the variables, with the drift fewer than two distinct x among the fitted layers, and the range rule of the
+    // intake over the used pixels of the fitted layers.
+    if (!args_ok || nfit < 1 || dofi < 1 || (DRIFT && !(xmax > xmin)) || fit_range_refused(best, amax)) {
         head(2);
         return;
     }
-    const int kx = ilogb(ab);
-    s.scale = ldexp(1.0, -kx);
-    s.kv = has_var ? ilogb(vmin) : 0;
+    s.norm = FitNorm(best, vmin, has_var);
+    const int kx = s.norm.kx;
 
-    // the wave's stamp: zero, apron included
-    for (int o = lane; o < kSpecStamp; o += 64) pl[o] = 0.0;
+    // the wave's stamp: zero, apron included (the layers are loaded into its interior, one after the other)
+    psf_stamp_clear(pl, lane);
     __syncthreads();
     if (!shift) {
         // The start: the first maximum of sum_l w_l d_l over the used pixels of the fitted layers minus the first
@@ -469,10 +402,10 @@ k_fit_spec(int nstar, int nl, const double* __restrict__ cubes, const double* __
             if (__builtin_amdgcn_readfirstlane((int)lkp[l]) == (int)kSpecLeftOut) continue;
             const size_t off = (size_t)l * NS * NS;
 #pragma unroll 5
-            for (int m = 0; m < kSpecPix; ++m) {
+            for (int m = 0; m < kFitPix; ++m) {
                 const int o = lane + m * 64;
                 double dn, wn;
-                spec_pixel(s, s.src + off, s.vsrc + off, o, dn, wn);
+                s.norm.pixel(s.src + off, s.vsrc + off, has_var, o, dn, wn);
                 pl[o] += wn * dn;
                 pl[NS * NS + o] += s.psrc[off + o];
             }
@@ -481,7 +414,7 @@ k_fit_spec(int nstar, int nl, const double* __restrict__ cubes, const double* __
         double cb = -3.0e38, pb = -3.0e38;
         int cbo = 0, pbo = 0;
 #pragma unroll 5
-        for (int m = 0; m < kSpecPix; ++m) {
+        for (int m = 0; m < kFitPix; ++m) {
             const int o = lane + m * 64;
             double c = pls[0][o], p = pls[0][NS * NS + o];
 #pragma unroll
@@ -489,8 +422,8 @@ k_fit_spec(int nstar, int nl, const double* __restrict__ cubes, const double* __
             if (c > cb) { cb = c; cbo = o; }
             if (p > pb) { pb = p; pbo = o; }
         }
-        spec_argmax(cb, cbo);
-        spec_argmax(pb, pbo);
+        wave_first_max(cb, cbo);
+        wave_first_max(pb, pbo);
         cbo = __builtin_amdgcn_readfirstlane(cbo);
         pbo = __builtin_amdgcn_readfirstlane(pbo);
         dp0 = fmin(fmax((double)(cbo / NS - pbo / NS), -kPsfMaxShift), kPsfMaxShift);
@@ -537,7 +470,7 @@ k_fit_spec(int nstar, int nl, const double* __restrict__ cubes, const double* __
     }
     // Last pass: the layer blocks.  The amplitudes leave the normalisation: F and its error by 2^(kx - kp), b and its
     // error by 2^kx, chi2 by 2^(2 kx - kv).  cov(F, b) = (A_ll^-1 + B cov(theta) B^T) chi2 / dof, B = A_ll^-1 A_lt X_l.
-    const double up = ldexp(1.0, kx), upc = ldexp(1.0, 2 * kx - s.kv);
+    const double up = ldexp(1.0, kx), upc = ldexp(1.0, 2 * kx - s.norm.kv);
     double notfinite = 0.0;
     for (int l0 = 0; l0 < nl; l0 += kSpecWaves) {
         const int l = l0 + wave;
@@ -545,7 +478,7 @@ k_fit_spec(int nstar, int nl, const double* __restrict__ cubes, const double* __
         const bool act = kp != (int)kSpecLeftOut;
         const size_t off = (size_t)(act ? l : 0) * NS * NS;
         double psum = 0.0;
-        if (act) psum = spec_load_stamp(s.psrc + off, kp, pl, lane);
+        if (act) psum = psf_stamp_load(s.psrc + off, kp, pl, lane);
         __syncthreads();
         if (act) {
             psum = wave_total(psum);

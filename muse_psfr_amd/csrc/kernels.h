@@ -1,6 +1,7 @@
 // Launchers for the HIP kernels of the PSF-reconstruction hot path (implemented in stage_a.hip,
-// per_lambda.hip and stamps.hip; the fits of caller-provided stamps in fit_ell.hip, fit_obs.hip and fit_psf.hip:
-// k_fit_psf fits a resampled model stamp -- flux scale, sub-pixel shift, background -- to an observed star).
+// per_lambda.hip and stamps.hip; the fits of caller-provided stamps in fit_ell.hip, fit_obs.hip, fit_psf.hip,
+// fit_group*.hip and fit_spec.hip: the last three fit a resampled model stamp -- flux scale, sub-pixel shift,
+// background -- to an observed star, a blended group or a star cube; the photometry of a frame in render.hip).
 // Host code (mpsfr_api.cpp) sees only these plain functions.
 #pragma once
 #include <hip/hip_runtime.h>

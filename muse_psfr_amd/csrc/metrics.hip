@@ -173,12 +173,7 @@ k_stamp_metrics(int nstamp, const double* __restrict__ stamps, const double* __r
         sq = fma((double)(8 * mi + L.lc), d, sq);
         if (d > best) { best = d; besto = (8 * mo + L.lr) * NS + 8 * mi + L.lc; }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ob = __shfl_xor(best, o, 64);
-        const int oo = __shfl_xor(besto, o, 64);
-        if (ob > best || (ob == best && oo < besto)) { best = ob; besto = oo; }
-    }
+    wave_first_max(best, besto);
     if (besto >= NS * NS) besto = 0;                        // (no pixel compares: all NaN)
     const double flux = wave_total(s0);
     sp = wave_total(sp);

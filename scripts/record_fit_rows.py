@@ -5,13 +5,16 @@
 standalone (double stamps) and inside a reconstruct (float and double stamps), into tests/golden/fit_rows_gfx950.npz.
 --set models: the rows of fit_stamps_elliptical, fit_stamps_observed, fit_stamps_psf and fit_groups_psf in all their
 variants for tests/fit_models_cases.py, into tests/golden/fit_rows_models_gfx950.npz.
+--set spec: the rows of fit_spectra_psf (k_fit_spec), head and layers side by side, for tests/fit_spec_cases.py, into
+tests/golden/fit_rows_spec_gfx950.npz.  Both modes run the fp64 kernel: the record holds one array per variant, the
+two modes must agree to be recorded, and --compare holds each of them to it.
 
-    python scripts/record_fit_rows.py [--set models] [--out FILE]
-    python scripts/record_fit_rows.py [--set models] --compare [FILE]
+    python scripts/record_fit_rows.py [--set models|spec] [--out FILE]
+    python scripts/record_fit_rows.py [--set models|spec] --compare [FILE]
 
 Run it on the build whose bits are to be kept -- before a change to a fit kernel that must not move any -- and commit
-the file; tests/test_gpu_fit_bits.py and tests/test_gpu_fit_models_bits.py then hold every later build to it with
-np.array_equal.  --compare prints, per key, how many rows of the loaded library differ from a record, and exits 1 if
+the file; tests/test_gpu_fit_bits.py, tests/test_gpu_fit_models_bits.py and tests/test_gpu_fit_spec_bits.py then hold
+every later build to it with np.array_equal.  --compare prints, per key, how many rows of the loaded library differ from a record, and exits 1 if
 any does.  MPSFR_LIB_PATH selects another build of the library (muse_psfr_amd._build.build_library(out=...) makes one
 with the same flags).
 """
@@ -26,14 +29,20 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
 
 import fit_bits_cases as C     # noqa: E402
 import fit_models_cases as M   # noqa: E402
+import fit_spec_cases as S     # noqa: E402
 
-STATUS_COLUMN = {'rows': 14, 'call': 14, 'ell': 18, 'obs': 18, 'psf': 10, 'grp': 4}
-ITER_COLUMN = {'rows': 7, 'call': 7, 'ell': 10, 'obs': 10, 'psf': 5, 'grp': 3}
+STATUS_COLUMN = {'rows': 14, 'call': 14, 'ell': 18, 'obs': 18, 'psf': 10, 'grp': 4, 'spec': 10}
+ITER_COLUMN = {'rows': 7, 'call': 7, 'ell': 10, 'obs': 10, 'psf': 5, 'grp': 3, 'spec': 9}
+
+
+def same(a, b):
+    """per row: every column equal, NaN equal to NaN"""
+    return ((a == b) | (np.isnan(a) & np.isnan(b))).all(axis=1)
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('--set', choices=('circular', 'models'), default='circular')
+    ap.add_argument('--set', choices=('circular', 'models', 'spec'), default='circular')
     ap.add_argument('--out', default=None)
     ap.add_argument('--compare', nargs='?', const='', default=None)
     args = ap.parse_args()
@@ -48,22 +57,29 @@ def main():
                     call_seeing=C.CALL_SEEING, call_gl=C.CALL_GL, call_l0=C.CALL_L0)
         digests = {'stamps_sha256': C.digest(st)}
     else:
-        default, rows = M.RECORD, M.record(api)
-        digests = M.digests()
+        cases = M if args.set == 'models' else S
+        default, rows = cases.RECORD, (M.record(api) if cases is M else S.record(api, 'f64'))
+        digests = cases.digests()
         meta = {k: np.array(v) for k, v in digests.items()}
-        meta.update({k: np.array(v) for k, v in M.names().items()})
+        meta.update({k: np.array(v) for k, v in cases.names().items()})
+    # what is held to the record: (key of the record, label, rows); the spec set again in the mixed mode
+    held = [(k, k, rows[k]) for k in sorted(rows)]
+    if args.set == 'spec':
+        held += [(k, k + ' [mixed]', v) for k, v in sorted(S.record(api, 'mixed').items())]
     if args.compare is not None:
         ref = np.load(args.compare or default)
         for k, v in digests.items():
             assert str(ref[k]) == v, 'the stamps differ from those of the record (%s)' % k
         bad = 0
-        for k in sorted(rows):
-            a, b = rows[k], ref[k]
-            d = int((~((a == b) | (np.isnan(a) & np.isnan(b)))).any(axis=1).sum()) if a.shape == b.shape else -1
-            print('%-28s %4d rows, %d differ' % (k, len(a), d))
+        for k, label, a in held:
+            b = ref[k]
+            d = int((~same(a, b)).sum()) if a.shape == b.shape else -1
+            print('%-28s %4d rows, %d differ' % (label, len(a), d))
             bad += d != 0
         print('library %s: %s' % (_lib.LIB_PATH, 'DIFFERS' if bad else 'bit-identical'))
         return 1 if bad else 0
+    for k, label, v in held:
+        assert same(v, rows[k]).all(), 'the modes differ (%s)' % label
     out = args.out or default
     np.savez_compressed(out, arch=np.array(arch), **meta, **rows)
     print('%s: %d arrays, %d rows, %d bytes' % (out, len(rows), sum(len(r) for r in rows.values()), os.path.getsize(out)))
