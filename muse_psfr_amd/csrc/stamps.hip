@@ -205,31 +205,51 @@ k_conv_fft(int nl, int tdiv, const R* __restrict__ pre, const cx<R>* __restrict_
         __syncthreads();
         {   // columns: forward, multiply by the kernel spectrum, inverse (conjugation trick).  A thread
             // consumes exactly the elements t + 8 e its last pass produces, so the results of the
-            // transforms stay in registers (fft_pass, TOREG) -- except in slot 0, whose packed DC /
-            // Nyquist column needs the mirrored elements of the forward transform.
-            cx<R> y[8];
+            // transforms stay in registers (fft_pass, TOREG).  The forward transform is one call for all
+            // 32 slots: slot 0 shares wave 0 with slots 1-7, and a transform of its own under the branch
+            // was a third transform issued by that wave.  Only the split of slot 0's packed DC / Nyquist
+            // column is left under the branch (cf_split0's expressions).  It needs the mirrored element
+            // (CF - kx) % CF of kx = t + 8 e: lane 8 - t of the slot holds it as v[7 - e], lane 0 its own
+            // as v[(8 - e) % 8].  Float: two DPP moves (mirror of the 8 lanes, then one lane up), no LDS --
+            // through the line buffer the kernel no longer fits 128 registers (20-40 bytes of scratch).
+            // Double: the slot's spectrum goes through its line buffer and cf_split0 reads it as before;
+            // the registers are there, and with the DPP form hipcc fuses the other product of b0.y's
+            // two (a0.x k.y instead of a0.y k.x), which is another last bit.
+            static_assert(fft_last_nbt<CF>() == 1 && fft_last_radix<CF>() == 8, "v[e] is element t + 8 e");
+            cx<R> y[8], xin[8], v[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int r = t + 8 * e;
+                xin[e] = r < NS ? F[r][slot] : cx<R>{(R)0, (R)0};
+            }
+            fft_forward_regs_lastreg<R, CF, true>(xin, buf, buf, tw.w, t, v);
             if (slot == 0) {
-                const cx<R>* res = cf_col_forward(F, NS, buf, tw, slot, t);
+                if constexpr (sizeof(R) == 8) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) buf[lds_out<CF, 8>(t + 8 * e)] = v[e];
+                    fft_sync<true>();
+                }
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     cx<R> a0, a32;
-                    cf_split0(res, t + 8 * e, a0, a32);
+                    if constexpr (sizeof(R) == 8) {
+                        cf_split0(buf, t + 8 * e, a0, a32);
+                    } else {
+                        const cx<R> own = v[(8 - e) % 8];
+                        const cx<R> up = {dpp_pull<0x111>(dpp_pull<0x141>(v[7 - e].x)),      // row_half_mirror, row_shr:1
+                                          dpp_pull<0x111>(dpp_pull<0x141>(v[7 - e].y))};
+                        const cx<R> p = v[e], pm = t == 0 ? own : up;
+                        a0 = {(R)0.5 * (p.x + pm.x), (R)0.5 * (p.y - pm.y)};
+                        a32 = {(R)0.5 * (p.y + pm.y), -(R)0.5 * (p.x - pm.x)};
+                    }
                     const cx<R> b0 = cmul(a0, khv[e]), b32 = cmul(a32, khn[e]);
                     y[e] = conjf<R>(cx<R>{b0.x - b32.y, b0.y + b32.x});
                 }
-                fft_sync<true>();           // the line buffer is rewritten by the inverse transform
             } else {
-                cx<R> xin[8], v[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const int r = t + 8 * e;
-                    xin[e] = r < NS ? F[r][slot] : cx<R>{(R)0, (R)0};
-                }
-                fft_forward_regs_lastreg<R, CF, true>(xin, buf, buf, tw.w, t, v);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) y[e] = conjf<R>(cmul(v[e], khv[e]));
-                fft_sync<true>();
             }
+            fft_sync<true>();               // the line buffer is rewritten by the inverse transform
             cx<R> r2[8];
             fft_forward_regs_lastreg<R, CF, true>(y, buf, buf, tw.w, t, r2);
 #pragma unroll
