@@ -638,6 +638,53 @@ int mpsfr_render_stars(mpsfr_ctx* ctx, int ny, int nx, const double* image_in, i
                        const int32_t* psf_index, const int32_t* origin, const double* shift, const double* scale,
                        int flags, double* image_out, double* star_out, int on_device);
 
+/* The star finder: matched-filter detection on a frame -- the source of the positions the frame calls above take, and
+ * the FIND of the loop find -> cut -> fit -> subtract -> find on the residual.
+ *
+ * image [ny][nx] and var (NULL or the same shape) are a frame as above.  psf is ONE model stamp [dimpsf][dimpsf]; the
+ * filter K is its (2 half + 1)^2 core centred on stamp pixel (dimpsf/2, dimpsf/2), used as given, without any
+ * normalisation, so that an amplitude is the `scale` F of mpsfr_fit_stamps_psf.  Arithmetic is fp64 in both precision
+ * modes: a mixed context gives the bits of an f64 one.
+ *
+ * The pixel mask is that of the observed fits: a datum that is NaN or not finite, var <= 0 or not finite, a pixel off
+ * the frame.  w = 1/var on a valid pixel (1 without var) and 0 on a masked one, whose datum counts as 0.
+ * The map: for the frame pixel (Y, X), over its window in row-major tap order (rows outer, columns inner; the order is
+ * part of the contract),
+ *   S0 = sum w,  S1 = sum w K,  S2 = sum w K^2,  S3 = sum w D,  S4 = sum w K D,
+ *   den = S2 - S1^2 / S0,   H = (S4 - S1 S3 / S0) / den,   b = (S3 - H S1) / S0:
+ * H is the least-squares amplitude of the model on the window beside a free constant background b.  The statistic T is
+ * H sqrt(den) with var (the significance H / sigma_H) and H without.  T is defined where the centre pixel is valid, more
+ * than half of the window's pixels are valid and den > 0, and NaN elsewhere: a star at the frame's edge is found on the
+ * pixels it has.  map_out (or NULL) receives T [ny][nx].
+ * Peaks: pixel i = Y nx + X is a peak when T(i) >= threshold and every other pixel j with a finite T in the
+ * (2 sep + 1)^2 square around it has T(j) < T(i), or T(j) == T(i) and j > i (on a plateau the first pixel wins).
+ * Rows: the peaks in increasing pixel index.  count_out[0] is their number in the frame; if it exceeds max_stars the
+ * first max_stars are written.  Rows and their order depend on the frame alone, not on the tile grid, the scheduling or
+ * where the scene sits in the frame.  star_out [max_stars][MPSFR_NFIND]:
+ *   0 Y + dy   1 X + dx   2 T at the peak pixel   3 H   4 b   5 sharpness   6 valid pixels in the window   7 flags
+ * dy = clamp(0.5 (T- - T+) / (T- - 2 T0 + T+), +-0.5), the parabola through T along the row axis, dx along the column
+ * axis; the offset is 0 and flag bit 0 (rows) or 1 (columns) is set when a neighbour is not finite or off the frame or
+ * the curvature is not negative.  sharpness = (D0 - mD) / (H (K0 - mK)) with mD, mK the unweighted means of D and K over
+ * the other valid pixels of the window: 1 for the model itself on any constant background, far above 1 for a hot pixel,
+ * below 1 for something extended; NaN and flag bit 2 when there is no other valid pixel or the denominator is 0.
+ * origin_out (or NULL) [max_stars][2]: (Y - dimpsf/2, X - dimpsf/2), the origin mpsfr_cut_stamps and mpsfr_render_stars
+ * take; with it (dy, dx) is a legal start shift.
+ * Rows from count_out[0] up to max_stars are NaN in all columns and have the origin (-2^30, -2^30): legal and off the
+ * frame, so that cut_stamps makes an all-NaN stamp of it, the fits answer status 2 and render_stars skips it -- find ->
+ * cut -> fit -> subtract run at the fixed size max_stars on device buffers without a host synchronisation between them.
+ *
+ * on_device as mpsfr_render_stars.  MPSFR_E_INVALID, outputs untouched, nothing queued: ny or nx out of range; a NULL
+ * image, psf, star_out or count_out; half outside 1 .. MPSFR_FIND_MAX_HALF or above dimpsf/2; sep outside 1 ..
+ * MPSFR_FIND_MAX_SEP; max_stars outside 1 .. 2^24; a threshold that is not finite; on host pointers a core with a value
+ * that is not finite or with all values equal (in the device form such a core gives a map without peaks and
+ * count_out[0] = 0).  Timed under the fit's profiling id. */
+#define MPSFR_NFIND          8    /* doubles per star in star_out */
+#define MPSFR_FIND_MAX_HALF  8
+#define MPSFR_FIND_MAX_SEP   16
+int mpsfr_find_stars(mpsfr_ctx* ctx, int ny, int nx, const double* image, const double* var, const double* psf,
+                     int half, int sep, double threshold, int max_stars, double* star_out, int32_t* origin_out,
+                     int32_t* count_out, double* map_out, int on_device);
+
 /* The stages of the path as the reference exports them (muse_psfr/__init__.py:16: `from .psfrec import *`),
  * for a caller that holds its own PSD or its own stamps.  Host buffers, synchronous, float64; the same
  * kernels as mpsfr_reconstruct entered or left at another stage.

@@ -34,6 +34,10 @@ MAX_IMAGE_PIXELS = 1 << 26   # and pixels
 MAX_ORIGIN = 1 << 30         # |origin| bound of the frame calls
 RENDER_SORT_CHUNK = 256      # stars of one frame tile that the renderer sorts in LDS (MPSFR_RENDER_SORT_CHUNK)
 RENDER_APRON = 10            # a star's footprint: its stamp and this many pixels around it
+NFIND = 8                    # doubles per star of mpsfr_find_stars (MPSFR_NFIND): Y, X, T, H, b, sharpness, pixels, flags
+FIND_MAX_HALF = 8            # half side of the filter core (MPSFR_FIND_MAX_HALF)
+FIND_MAX_SEP = 16            # half side of the square a peak dominates (MPSFR_FIND_MAX_SEP)
+FIND_MAX_STARS = 1 << 24     # rows of one call
 DIM_AO = 80
 PREC_MIXED, PREC_F64 = 0, 1
 E_GRID = -3
@@ -125,6 +129,9 @@ def load():
     lib.mpsfr_cut_stamps.restype = C.c_int
     lib.mpsfr_render_stars.argtypes = [p, C.c_int, C.c_int, p, C.c_int, C.c_int, p, p, p, p, p, C.c_int, p, p, C.c_int]
     lib.mpsfr_render_stars.restype = C.c_int
+    lib.mpsfr_find_stars.argtypes = [p, C.c_int, C.c_int, p, p, p, C.c_int, C.c_int, C.c_double, C.c_int, p, p, p, p,
+                                     C.c_int]
+    lib.mpsfr_find_stars.restype = C.c_int
     lib.mpsfr_simul_psd.argtypes = [p, C.c_double, C.c_double, C.c_double, C.c_int, dp, C.c_double, C.c_int, u8p, u8p, dp]
     lib.mpsfr_simul_psd.restype = C.c_int
     lib.mpsfr_psf_from_psd.argtypes = [p, C.c_int, dp, C.c_int, dp, dp]
@@ -172,7 +179,7 @@ def load():
 
 
 EXPORTS = ['mpsfr_create', 'mpsfr_destroy', 'mpsfr_last_error', 'mpsfr_set_option',
-           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_fit_stamps_psf', 'mpsfr_fit_groups_psf', 'mpsfr_fit_spectra_psf', 'mpsfr_stamp_metrics', 'mpsfr_cut_stamps', 'mpsfr_render_stars', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
+           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_fit_stamps_psf', 'mpsfr_fit_groups_psf', 'mpsfr_fit_spectra_psf', 'mpsfr_stamp_metrics', 'mpsfr_cut_stamps', 'mpsfr_render_stars', 'mpsfr_find_stars', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
            'mpsfr_psd_to_psf',
            'mpsfr_convolve_stamps', 'mpsfr_fit_rows', 'mpsfr_sync', 'mpsfr_last_ticket', 'mpsfr_wait', 'mpsfr_abandon',
            'mpsfr_stream', 'mpsfr_stream_wait', 'mpsfr_wait_event',
@@ -1020,6 +1027,50 @@ class Context:
         self._call_render(ny, nx, image_ptr, nstar, npsf, psf_ptr, psf_index_ptr, origin_ptr, shift_ptr, scale_ptr, flags,
                           image_out_ptr, star_out_ptr, 1)
 
+    def _call_find(self, ny, nx, image, var, psf, half, sep, threshold, max_stars, rows, origin, count, tmap, on_device):
+        p = _devptr if on_device else _vptr
+        _check(self.lib.mpsfr_find_stars(self._h, int(ny), int(nx), p(image), p(var), p(psf), int(half), int(sep),
+                                         float(threshold), int(max_stars), p(rows), p(origin), p(count), p(tmap),
+                                         on_device))
+
+    def find_stars(self, image, psf, *, var=None, half=3, sep=3, threshold=5.0, max_stars=4096, return_map=False):
+        """The stars of a frame (mpsfr_find_stars): the matched filter of `image` (ny, nx; `var` of the same shape or
+        None) with the (2 half + 1)^2 core of the model stamp `psf` (dimpsf, dimpsf) beside a free local background,
+        and the peaks of its statistic T (the significance with var, the amplitude without) at or above `threshold`
+        that dominate the (2 sep + 1)^2 square around them.  Returns (rows[:n], origin[:n], nfound): the (n, NFIND)
+        rows in pixel order -- 0 row and 1 column position with the parabola's sub-pixel offset, 2 T, 3 the amplitude (the
+        `scale` of fit_stamps_psf), 4 the local background, 5 the sharpness (1 for the model, far above for a hot pixel),
+        6 the valid pixels of the window, 7 flags --, the (n, 2) int32 origins cut_stamps and render_stars take, and the
+        number of peaks in the frame; n = min(nfound, max_stars).  With `return_map` also T (ny, nx)."""
+        im, va, ps, half, sep, threshold, max_stars = find_arguments(image, var, psf, half, sep, threshold, max_stars,
+                                                                     self.dimpsf)
+        if not isinstance(return_map, (bool, np.bool_)):
+            raise ValueError('return_map must be True or False')
+        ny, nx = im.shape
+        rows = np.empty((max_stars, NFIND))
+        origin = np.empty((max_stars, 2), dtype=np.int32)
+        count = np.zeros(1, dtype=np.int32)
+        tmap = np.empty((ny, nx)) if return_map else None
+        self._call_find(ny, nx, im, va, ps, half, sep, threshold, max_stars, rows, origin, count, tmap, 0)
+        nfound = int(count[0])
+        n = min(nfound, max_stars)
+        return (rows[:n], origin[:n], nfound) + ((tmap,) if return_map else ())
+
+    def find_stars_device(self, ny, nx, image_ptr, psf_ptr, half, sep, threshold, max_stars, star_out_ptr, count_ptr, *,
+                          var_ptr=None, origin_ptr=None, map_ptr=None):
+        """Device-buffer form (asynchronous, on_device = 1): `image_ptr`, `var_ptr` ([ny][nx] float64; None: no
+        variances), `psf_ptr` ([dimpsf][dimpsf] float64), `star_out_ptr` ([max_stars][NFIND] float64), `count_ptr` ([1]
+        int32), `origin_ptr` ([max_stars][2] int32, or None) and `map_ptr` ([ny][nx] float64, or None) are raw device
+        pointers (int) on this context's GPU; the call is queued on the context stream, after any device-output
+        reconstruct of this context.  The rows behind the count are NaN with the origin (-2^30, -2^30), which the frame
+        calls and the fits skip, so that the next calls can run at the fixed size max_stars.  A core that is not
+        finite or constant gives no peaks."""
+        frame_shape(ny, nx)
+        half, sep, threshold, max_stars = find_parameters(half, sep, threshold, max_stars, self.dimpsf)
+        _device_pointers(image_ptr=image_ptr, psf_ptr=psf_ptr, star_out_ptr=star_out_ptr, count_ptr=count_ptr)
+        self._call_find(ny, nx, image_ptr, var_ptr, psf_ptr, half, sep, threshold, max_stars, star_out_ptr, origin_ptr,
+                        count_ptr, map_ptr, 1)
+
     def debug_fetch(self, what, shape):
         out = np.empty(int(np.prod(shape)))
         n = _check(self.lib.mpsfr_debug_fetch(self._h, what.encode(), _dptr(out), out.size))
@@ -1237,6 +1288,42 @@ def render_arguments(psf, origin, scale, shift, psf_index, image, shape, subtrac
         if shape is not None and tuple(shape) != (ny, nx):
             raise ValueError('shape differs from the shape of image')
     return im, ny, nx, ps, ix, og, sh, sc, flags
+
+
+def find_parameters(half, sep, threshold, max_stars, dimpsf=40):
+    """(half, sep, threshold, max_stars) of a find call, validated as mpsfr_find_stars validates them (ValueError)."""
+    def integer(name, n, lo, hi):
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not lo <= n <= hi:
+            raise ValueError('%s must be an integer between %d and %d' % (name, lo, hi))
+        return int(n)
+    half = integer('half', half, 1, min(FIND_MAX_HALF, dimpsf // 2))
+    sep = integer('sep', sep, 1, FIND_MAX_SEP)
+    max_stars = integer('max_stars', max_stars, 1, FIND_MAX_STARS)
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(threshold):
+        raise ValueError('threshold must be a finite number')
+    return half, sep, float(threshold), max_stars
+
+
+def find_arguments(image, var, psf, half, sep, threshold, max_stars, dimpsf=40):
+    """(image, var or None, psf, half, sep, threshold, max_stars) of a host find call, validated as mpsfr_find_stars
+    validates host arguments (ValueError): the frame as frame_images, `psf` one numeric (dimpsf, dimpsf) stamp whose
+    (2 half + 1)^2 core is finite and not constant."""
+    im, va = frame_images(image, var)
+    half, sep, threshold, max_stars = find_parameters(half, sep, threshold, max_stars, dimpsf)
+    try:
+        ps = np.ascontiguousarray(psf, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('psf must be a numeric array') from None
+    if ps.shape != (dimpsf, dimpsf):
+        raise ValueError('psf must be one model stamp of shape (%d, %d)' % (dimpsf, dimpsf))
+    c = dimpsf // 2
+    core = ps[c - half:c + half + 1, c - half:c + half + 1]
+    if not np.all(np.isfinite(core)):
+        raise ValueError('psf must be finite over its core')
+    if np.all(core == core[0, 0]):
+        raise ValueError('psf must not be constant over its core')
+    return im, va, ps, half, sep, threshold, max_stars
 
 
 def _group_size(nsrc):

@@ -295,6 +295,15 @@ size_t render_workspace_bytes(int ny, int nx, int nstar);
 void launch_render_stars(hipStream_t s, int ny, int nx, const double* d_image_in, int nstar, int npsf,
                          const double* d_psf, const int32_t* d_index, const int32_t* d_origin, const double* d_shift,
                          const double* d_scale, bool subtract, double* d_image_out, double* d_star_out, void* d_ws);
+// The star finder (find.hip; mpsfr_find_stars, include/mpsfr.h): the statistic T of every pixel of d_image [ny][nx]
+// (d_var [ny][nx] or nullptr) with the (2 half + 1)^2 core of the model stamp d_psf [40][40], its peaks over (2 sep + 1)^2
+// squares at or above `threshold` in pixel order into d_star_out [max_stars][8] and d_origin_out [max_stars][2] (or
+// nullptr), their number into d_count_out [1], filler rows behind them; T into d_map_out [ny][nx] if it is given.
+// d_ws: find_workspace_bytes(ny, nx, max_stars, d_map_out != nullptr) bytes; the launch writes every word of it before it reads it.
+size_t find_workspace_bytes(int ny, int nx, int max_stars, bool with_map);
+void launch_find_stars(hipStream_t s, int ny, int nx, const double* d_image, const double* d_var, const double* d_psf,
+                       int half, int sep, double threshold, int max_stars, double* d_star_out, int32_t* d_origin_out,
+                       int32_t* d_count_out, double* d_map_out, void* d_ws);
 // band-integrated stamps (band.hip): d_fin [ntb][nl][40][40] (float if fin_f32, else double) reduced over wavelength
 // into d_out [ntb][nband][40][40] double with the weights d_w [nl][band_stride(nband)] (zero beyond nband)
 constexpr int MAX_BANDS = 16;    // MPSFR_MAX_BANDS

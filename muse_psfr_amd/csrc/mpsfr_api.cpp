@@ -157,6 +157,7 @@ struct mpsfr_ctx {
     int stagger_lane = -1;
     DevBuf specx;                      // [nl] the abscissa of mpsfr_fit_spectra_psf's drift
     DevBuf render;                     // work lists of mpsfr_render_stars (render_workspace_bytes)
+    DevBuf find;                       // core, map, masks and counts of mpsfr_find_stars (find_workspace_bytes)
     DevBuf fit, sum, stage, lsum;      // lsum: [lanes][nl][40][40] per-lane partial stamp sums
     // mpsfr_psd_to_psf: a stream and workspaces of its own, so that it never waits for nor touches the lanes
     struct P2P {
@@ -543,10 +544,11 @@ struct StampIn {
     size_t count, elem;
 };
 
-// An output array of a stamp call: `count` doubles, or NULL for an optional that is absent.
+// An output array of a stamp call: `count` elements of `elem` bytes (doubles unless said otherwise), or NULL for an
+// optional that is absent.
 struct StampOut {
-    double* p;
-    size_t count;
+    void* p;
+    size_t count, elem = sizeof(double);
 };
 
 // One stamp call (the fits and the metrics of caller-provided stamps, the frame calls) on the context stream, after the
@@ -564,7 +566,7 @@ int stamp_call(mpsfr_ctx* c, int on_device, const StampIn (&in)[N], const StampO
     const void* d[N];
     double* d_out[M];
     for (size_t i = 0; i < N; ++i) d[i] = in[i].p;
-    for (size_t i = 0; i < M; ++i) d_out[i] = out[i].p;
+    for (size_t i = 0; i < M; ++i) d_out[i] = (double*)out[i].p;
     if (!on_device) {
         size_t off[N] = {}, off_out[M] = {}, bytes = 0;
         for (int narrow = 0; narrow < 2; ++narrow) {
@@ -577,7 +579,7 @@ int stamp_call(mpsfr_ctx* c, int on_device, const StampIn (&in)[N], const StampO
                 for (size_t i = 0; i < M; ++i)
                     if (out[i].p) {
                         off_out[i] = bytes;
-                        bytes += out[i].count * sizeof(double);
+                        bytes += (out[i].count * out[i].elem + 7) & ~(size_t)7;
                     }
         }
         if ((rc = ensure(c, c->stage, bytes))) return rc;
@@ -598,7 +600,7 @@ int stamp_call(mpsfr_ctx* c, int on_device, const StampIn (&in)[N], const StampO
     if (!on_device) {
         for (size_t i = 0; i < M; ++i)
             if (out[i].p)
-                HIPCHK(hipMemcpyAsync(out[i].p, d_out[i], out[i].count * sizeof(double), hipMemcpyDeviceToHost, s));
+                HIPCHK(hipMemcpyAsync(out[i].p, d_out[i], out[i].count * out[i].elem, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
     }
     return MPSFR_OK;
@@ -718,7 +720,7 @@ void mpsfr_destroy(mpsfr_ctx* c) {
     }
     DevBuf* all[] = {&c->scoef, &c->stwk, &c->ssup, &c->tw64, &c->tel, &c->rows, &c->tlmax, &c->tl2, &c->tlb, &c->aotab, &c->samp_p,
                      &c->samp_a, &c->G, &c->xtab, &c->etab, &c->gtab, &c->kmuse, &c->fit, &c->sum,
-                     &c->stage, &c->lsum, &c->mfclk, &c->specx, &c->render};
+                     &c->stage, &c->lsum, &c->mfclk, &c->specx, &c->render, &c->find};
     for (auto b : all) release(*b);
     if (c->p2p.stream) { (void)hipStreamSynchronize(c->p2p.stream); (void)hipStreamDestroy(c->p2p.stream); }
     DevBuf* p2p[] = {&c->p2p.twm, &c->p2p.psd, &c->p2p.cm, &c->p2p.d0t, &c->p2p.pup, &c->p2p.phase, &c->p2p.lbda,
@@ -2594,6 +2596,47 @@ int mpsfr_render_stars(mpsfr_ctx* c, int ny, int nx, const double* image_in, int
         launch_render_stars(s, ny, nx, (const double*)d[0], nstar, npsf, (const double*)d[1], (const int32_t*)d[5],
                             (const int32_t*)d[4], (const double*)d[2], (const double*)d[3],
                             (flags & MPSFR_RENDER_SUBTRACT) != 0, d_out[0], d_out[1], c->render.p);
+    });
+}
+
+static_assert(MPSFR_NFIND == 8 && MPSFR_FIND_MAX_HALF <= NS / 2, "K_FIND_ROWS row layout and the core");
+
+int mpsfr_find_stars(mpsfr_ctx* c, int ny, int nx, const double* image, const double* var, const double* psf, int half,
+                     int sep, double threshold, int max_stars, double* star_out, int32_t* origin_out,
+                     int32_t* count_out, double* map_out, int on_device) {
+    if (!c || !image || !psf || !star_out || !count_out)
+        return fail(MPSFR_E_INVALID, "find_stars: bad argument (image, psf, star_out and count_out are required)");
+    int rc;
+    if ((rc = frame_shape("find_stars", ny, nx))) return rc;
+    if (half < 1 || half > MPSFR_FIND_MAX_HALF || half > NS / 2)
+        return fail(MPSFR_E_INVALID, "find_stars: half=%d outside 1..%d", half, MPSFR_FIND_MAX_HALF);
+    if (sep < 1 || sep > MPSFR_FIND_MAX_SEP)
+        return fail(MPSFR_E_INVALID, "find_stars: sep=%d outside 1..%d", sep, MPSFR_FIND_MAX_SEP);
+    if (max_stars < 1 || max_stars > (1 << 24))
+        return fail(MPSFR_E_INVALID, "find_stars: max_stars=%d outside 1..2^24", max_stars);
+    if (!std::isfinite(threshold)) return fail(MPSFR_E_INVALID, "find_stars: threshold is not finite");
+    if (!on_device) {
+        bool differ = false;
+        const double* core = psf + (NS / 2 - half) * NS + (NS / 2 - half);
+        for (int a = 0; a <= 2 * half; ++a)
+            for (int b = 0; b <= 2 * half; ++b) {
+                if (!std::isfinite(core[a * NS + b]))
+                    return fail(MPSFR_E_INVALID, "find_stars: psf has a value that is not finite in its core");
+                differ = differ || core[a * NS + b] != core[0];
+            }
+        if (!differ) return fail(MPSFR_E_INVALID, "find_stars: psf is constant over its core");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = ensure(c, c->find, find_workspace_bytes(ny, nx, max_stars, map_out != nullptr)))) return rc;
+    const size_t npix = (size_t)ny * nx;
+    const StampIn in[] = {{image, npix, sizeof(double)}, {var, npix, sizeof(double)}, {psf, kStampPix, sizeof(double)}};
+    const StampOut out[] = {{star_out, (size_t)max_stars * MPSFR_NFIND},
+                            {map_out, npix},
+                            {origin_out, (size_t)2 * max_stars, sizeof(int32_t)},
+                            {count_out, 1, sizeof(int32_t)}};
+    return stamp_call(c, on_device, in, out, [&](hipStream_t s, const void* const* d, double* const* d_out) {
+        launch_find_stars(s, ny, nx, (const double*)d[0], (const double*)d[1], (const double*)d[2], half, sep, threshold,
+                          max_stars, d_out[0], (int32_t*)d_out[2], (int32_t*)d_out[3], d_out[1], c->find.p);
     });
 }
 

@@ -10,6 +10,7 @@
 // The order of the sum at a pixel is the star index, whatever the tile grid or the scheduling; no floating-point atomics.
 // Arithmetic is fp64 in both precision modes; P~ is psf_interp of fit_psf_common.h with KeysTaps<double>.
 #include "fit_psf_common.h"
+#include "scan_common.h"
 
 namespace mpsfr {
 namespace {
@@ -24,7 +25,6 @@ constexpr int kStageStride = kStageSide + 1;
 constexpr int kStageLoads = (kStageSide * kStageSide + kTileThreads - 1) / kTileThreads;     // per thread
 constexpr int kSortChunk = 256;                               // MPSFR_RENDER_SORT_CHUNK: lists up to here sort in LDS
 constexpr int kMaxOrigin = 1 << 30;
-constexpr int kScanThreads = 1024;
 static_assert(kTile * kTile == kTileThreads * kTilePix && kTileRows * kTile == kTileThreads, "tile layout");
 static_assert(kSortChunk == kTileThreads, "one list entry per thread in the LDS copy");
 
@@ -94,25 +94,7 @@ __global__ __launch_bounds__(256) void k_render_prepare(int ny, int nx, int ntx,
 __global__ __launch_bounds__(kScanThreads) void k_render_scan(int nt, const int* __restrict__ count,
                                                               int* __restrict__ offset) {
     __shared__ int part[kScanThreads];
-    const int tid = threadIdx.x;
-    const int per = (nt + kScanThreads - 1) / kScanThreads;
-    const int b = min(tid * per, nt), e = min(b + per, nt);
-    int sum = 0;
-    for (int i = b; i < e; ++i) sum += count[i];
-    part[tid] = sum;
-    __syncthreads();
-    for (int d = 1; d < kScanThreads; d <<= 1) {
-        const int add = tid >= d ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += add;
-        __syncthreads();
-    }
-    int run = part[tid] - sum;
-    for (int i = b; i < e; ++i) {
-        offset[i] = run;
-        run += count[i];
-    }
-    if (tid == kScanThreads - 1) offset[nt] = part[tid];
+    scan_shares(nt, count, offset, part);
 }
 
 __global__ __launch_bounds__(256) void k_render_fill(int ny, int nx, int ntx, int nstar,

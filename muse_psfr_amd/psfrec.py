@@ -660,6 +660,62 @@ def _pixscale(pixscale):
         raise ValueError('pixscale must be positive')
 
 
+def _sharp_bounds(sharp):
+    try:
+        lo, hi = sharp
+        lo, hi = (None if v is None else float(v) for v in (lo, hi))
+    except (TypeError, ValueError):
+        raise ValueError('sharp must be (lower, upper), each a number or None') from None
+    if any(v is not None and np.isnan(v) for v in (lo, hi)):
+        raise ValueError('sharp bounds must not be NaN')
+    return lo, hi
+
+
+def find_stars(image, psf, var=None, *, threshold=5.0, half=3, sep=None, sharp=(None, None), max_stars=4096,
+               pixscale=0.2, precision='mixed', device=0):
+    """The stars of a frame, on the GPU: the matched filter of `image` (ny, nx) with the (2 half + 1)^2 core of the
+    model stamp `psf` (40, 40) -- e.g. a reconstructed PSF -- beside a free local background, and the peaks of its
+    statistic at or above `threshold` that dominate the (2 sep + 1)^2 square around them (sep=None: half).  With the
+    variance frame `var` the statistic is the significance of the amplitude in sigma; without, the amplitude itself.
+    NaN pixels and var <= 0 are masked.  sharp = (lower, upper): keep only the rows whose sharpness lies within the
+    bounds (None: open) -- 1 is the model itself, a cosmic ray lies far above, a galaxy below.  More peaks than
+    max_stars cost a second call.
+
+    Returns a table, brightest statistic first (ties in pixel order): position (2, pixels: row, column), origin (2,
+    int32: what cut_stamps, render_star_field and subtract_stars take), statistic, scale (the amplitude: the start of
+    the fit's F), back, sharp, npix (valid pixels of the window), flags (1, 2: no parabola along rows, columns; 4: no
+    sharpness) and shift (2, arcsec): the start value fit_stars_with_psf(shift=...) takes for stamps cut at origin."""
+    _pixscale(pixscale)
+    lo, hi = _sharp_bounds(sharp)
+    sep = half if sep is None else sep
+    ctx = get_context(128, pixscale, np.shape(psf)[-1] if np.ndim(psf) >= 2 else 40, precision, device)
+    rows, origin, nfound = ctx.find_stars(image, psf, var=var, half=half, sep=sep, threshold=threshold,
+                                          max_stars=max_stars)
+    if nfound > rows.shape[0]:
+        rows, origin, nfound = ctx.find_stars(image, psf, var=var, half=half, sep=sep, threshold=threshold,
+                                              max_stars=nfound)
+    with np.errstate(invalid='ignore'):
+        keep = np.ones(rows.shape[0], dtype=bool)
+        if lo is not None:
+            keep &= rows[:, 5] >= lo
+        if hi is not None:
+            keep &= rows[:, 5] <= hi
+    rows, origin = rows[keep], origin[keep]
+    order = np.argsort(-rows[:, 2], kind='stable')
+    rows, origin = rows[order], origin[order]
+    cols = OrderedDict()
+    cols['position'] = rows[:, 0:2].copy()
+    cols['origin'] = origin.astype(np.int32)
+    cols['statistic'] = rows[:, 2].copy()
+    cols['scale'] = rows[:, 3].copy()
+    cols['back'] = rows[:, 4].copy()
+    cols['sharp'] = rows[:, 5].copy()
+    cols['npix'] = rows[:, 6].astype(np.int64)
+    cols['flags'] = rows[:, 7].astype(np.int64)
+    cols['shift'] = (rows[:, 0:2] - (origin + ctx.dimpsf // 2)) * pixscale
+    return _make_table(cols)
+
+
 def cut_star_stamps(image, positions, var=None, dimpsf=40, *, pixscale=0.2, precision='mixed', device=0):
     """Stamps of stars out of a frame, on the GPU: `image` (ny, nx), `positions` (n, 2) the (row, column) star centres
     in pixels.  Stamp k starts at origin[k] = rint(positions[k]) - dimpsf // 2, so the star sits within half a pixel of
