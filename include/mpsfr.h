@@ -685,6 +685,54 @@ int mpsfr_find_stars(mpsfr_ctx* ctx, int ny, int nx, const double* image, const 
                      int half, int sep, double threshold, int max_stars, double* star_out, int32_t* origin_out,
                      int32_t* count_out, double* map_out, int on_device);
 
+/* Friends-of-friends groups of found stars (DAOPHOT's GROUP): the connected components of the relation "closer than
+ * crit", as the tables mpsfr_cut_stamps, mpsfr_fit_stamps_psf and mpsfr_fit_groups_psf take as they are -- the step
+ * between mpsfr_find_stars and the fits in a crowded frame.
+ *
+ * pos [nstar][stride] doubles, stride >= 2: columns 0 and 1 are (y, x) in frame pixels; the star_out of mpsfr_find_stars
+ * is passed as it is with stride = MPSFR_NFIND.  A row with NaN in either coordinate is a filler (the finder's filler
+ * rows are such rows): it belongs to no group and gets the label -1.  Any other row outside [-1, ny] x [-1, nx],
+ * +-infinity included, makes the call return MPSFR_E_INVALID on host pointers; in the device form it is treated as a
+ * filler with the label -2.
+ * The link rule: stars i and j are linked when d2 <= c2, with dy = y_i - y_j, dx = x_i - x_j, d2 = dy dy + dx dx (each
+ * product rounded, then the sum: no fused multiply-add) and c2 = crit crit rounded.  The relation is symmetric bit for
+ * bit, and two stars at one position are linked.  A group is a connected component: a chain of any length is one group.
+ * label_out [nstar]: the smallest star index of the star's group.
+ * Groups come in five classes: 1, 2, 3, 4 members, then oversize (more than MPSFR_MAX_GROUP).  Rows are ordered by class
+ * first and by label within a class.  count_out [6]: the number of groups, then the number in each class -- of the frame,
+ * so they may exceed max_groups; then the first max_groups rows are written.  offset_k, the first row of class k, is the
+ * sum of the class counts before it.
+ * group_out [max_groups][MPSFR_NGROUP] int32:  0 members n   1 flags   2 label   3 zero   4..7 the member indices in
+ * ascending order, -1 beyond n; of an oversize group the four smallest.
+ * origin_out [max_groups][2] int32, for n <= 4: per axis, c = 0.5 (lo + hi) over the members' coordinates and
+ * origin = (int)floor(c + 0.5) - dimpsf/2: the stamp is centred on the group's bounding box.
+ * shift_out: member k of a group has, per axis, shift = pos_k - (double)(origin + dimpsf/2), one subtraction.  The buffer
+ * is [max_groups][8] doubles, and the shifts of class k lie in it AT THE PITCH OF THEIR CLASS: row r of the class (row
+ * offset_k + r of the tables), member m, axis a is shift_out[8 offset_k + 2 k r + 2 m + a].  So shift_out + 8 offset_k is
+ * the [count_k][k][2] array mpsfr_fit_groups_psf takes with nsrc = k, and for k = 1 the [count_1][2] array
+ * mpsfr_fit_stamps_psf takes, beside origin_out + 2 offset_k for mpsfr_cut_stamps -- no repacking.  Every other double
+ * of the buffer is 0.  A row beyond max_groups is not written in this buffer either.
+ * MPSFR_GROUP_WIDE is set when a member's |shift| exceeds MPSFR_FIT_PSF_MAX_SHIFT on an axis; the row is still written
+ * (the fits refuse such a start).  An oversize group has MPSFR_GROUP_OVERSIZE, the origin (-2^30, -2^30) and no shifts:
+ * the caller regroups its stars -- label_out says which they are -- with a smaller crit, as DAOPHOT does.
+ * Rows from the number of groups up to max_groups are fillers: n = 0, flags 0, label 0, members -1, origin
+ * (-2^30, -2^30), which mpsfr_cut_stamps turns into an all-NaN stamp.
+ * Every output depends on the positions and crit alone -- not on the launch geometry, the cell grid, earlier calls or
+ * the order in which workgroups run -- and is an integer or a single rounding.
+ *
+ * origin_out and shift_out: both or neither.  on_device as mpsfr_render_stars; in the device form reading count_out
+ * back is the one host synchronisation of find -> group -> cut -> fit.  MPSFR_E_INVALID, outputs untouched, nothing
+ * queued: ny or nx out of range; nstar outside 1 .. 2^24; stride < 2; crit not finite, <= 0 or above
+ * MPSFR_GROUP_MAX_CRIT; max_groups < 1; a NULL pos, label_out, group_out or count_out; exactly one of origin_out and
+ * shift_out; on host pointers a position out of range.  Timed under the fit's profiling id. */
+#define MPSFR_GROUP_MAX_CRIT 16.0   /* pixels: 2 MPSFR_FIT_PSF_MAX_SHIFT, beyond it two stars cannot share a stamp */
+#define MPSFR_NGROUP 8              /* int32 per group row */
+#define MPSFR_GROUP_OVERSIZE 1      /* flag: more than MPSFR_MAX_GROUP members */
+#define MPSFR_GROUP_WIDE 2          /* flag: a member's |shift| exceeds MPSFR_FIT_PSF_MAX_SHIFT */
+int mpsfr_group_stars(mpsfr_ctx* ctx, int ny, int nx, int nstar, const double* pos, int stride, double crit,
+                      int max_groups, int32_t* label_out, int32_t* group_out, int32_t* origin_out,
+                      double* shift_out, int32_t* count_out, int on_device);
+
 /* The stages of the path as the reference exports them (muse_psfr/__init__.py:16: `from .psfrec import *`),
  * for a caller that holds its own PSD or its own stamps.  Host buffers, synchronous, float64; the same
  * kernels as mpsfr_reconstruct entered or left at another stage.

@@ -38,6 +38,12 @@ NFIND = 8                    # doubles per star of mpsfr_find_stars (MPSFR_NFIND
 FIND_MAX_HALF = 8            # half side of the filter core (MPSFR_FIND_MAX_HALF)
 FIND_MAX_SEP = 16            # half side of the square a peak dominates (MPSFR_FIND_MAX_SEP)
 FIND_MAX_STARS = 1 << 24     # rows of one call
+NGROUP = 8                   # int32 per group row of mpsfr_group_stars (MPSFR_NGROUP): n, flags, label, 0, 4 members
+GROUP_MAX_CRIT = 16.0        # largest critical separation in pixels (MPSFR_GROUP_MAX_CRIT)
+GROUP_OVERSIZE = 1           # group flag: more than MAX_GROUP members (MPSFR_GROUP_OVERSIZE)
+GROUP_WIDE = 2               # group flag: a member's |shift| beyond FIT_PSF_MAX_SHIFT (MPSFR_GROUP_WIDE)
+GROUP_MAX_STARS = 1 << 24    # stars of one call
+GROUP_FILLER_ORIGIN = -(1 << 30)   # origin of filler rows and of oversize groups
 DIM_AO = 80
 PREC_MIXED, PREC_F64 = 0, 1
 E_GRID = -3
@@ -132,6 +138,9 @@ def load():
     lib.mpsfr_find_stars.argtypes = [p, C.c_int, C.c_int, p, p, p, C.c_int, C.c_int, C.c_double, C.c_int, p, p, p, p,
                                      C.c_int]
     lib.mpsfr_find_stars.restype = C.c_int
+    lib.mpsfr_group_stars.argtypes = [p, C.c_int, C.c_int, C.c_int, p, C.c_int, C.c_double, C.c_int, p, p, p, p, p,
+                                      C.c_int]
+    lib.mpsfr_group_stars.restype = C.c_int
     lib.mpsfr_simul_psd.argtypes = [p, C.c_double, C.c_double, C.c_double, C.c_int, dp, C.c_double, C.c_int, u8p, u8p, dp]
     lib.mpsfr_simul_psd.restype = C.c_int
     lib.mpsfr_psf_from_psd.argtypes = [p, C.c_int, dp, C.c_int, dp, dp]
@@ -179,7 +188,7 @@ def load():
 
 
 EXPORTS = ['mpsfr_create', 'mpsfr_destroy', 'mpsfr_last_error', 'mpsfr_set_option',
-           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_fit_stamps_psf', 'mpsfr_fit_groups_psf', 'mpsfr_fit_spectra_psf', 'mpsfr_stamp_metrics', 'mpsfr_cut_stamps', 'mpsfr_render_stars', 'mpsfr_find_stars', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
+           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_fit_stamps_psf', 'mpsfr_fit_groups_psf', 'mpsfr_fit_spectra_psf', 'mpsfr_stamp_metrics', 'mpsfr_cut_stamps', 'mpsfr_render_stars', 'mpsfr_find_stars', 'mpsfr_group_stars', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
            'mpsfr_psd_to_psf',
            'mpsfr_convolve_stamps', 'mpsfr_fit_rows', 'mpsfr_sync', 'mpsfr_last_ticket', 'mpsfr_wait', 'mpsfr_abandon',
            'mpsfr_stream', 'mpsfr_stream_wait', 'mpsfr_wait_event',
@@ -1071,6 +1080,51 @@ class Context:
         self._call_find(ny, nx, image_ptr, var_ptr, psf_ptr, half, sep, threshold, max_stars, star_out_ptr, origin_ptr,
                         count_ptr, map_ptr, 1)
 
+    def _call_group(self, ny, nx, nstar, pos, stride, crit, max_groups, label, groups, origin, shift, count, on_device):
+        p = _devptr if on_device else _vptr
+        _check(self.lib.mpsfr_group_stars(self._h, int(ny), int(nx), int(nstar), p(pos), int(stride), float(crit),
+                                          int(max_groups), p(label), p(groups), p(origin), p(shift), p(count),
+                                          on_device))
+
+    def group_stars(self, pos, crit, shape, *, max_groups=None):
+        """Friends-of-friends groups of stars (mpsfr_group_stars): `pos` (nstar, stride >= 2) holds (row, column) in its
+        first two columns -- the rows of find_stars as they are --, rows with a NaN are fillers; `shape` = (ny, nx) is
+        the frame; stars closer than `crit` pixels are linked and a group is a connected component.  Returns (label,
+        groups[:n], origin[:n], shift[:n], counts): the (nstar,) int32 label of every star (the smallest index of its
+        group; -1 for a filler), the (n, NGROUP) int32 group rows -- 0 members, 1 flags (GROUP_OVERSIZE, GROUP_WIDE),
+        2 label, 4..7 the members ascending, -1 beyond them -- ordered by class (1, 2, 3, 4 members, oversize) and by
+        label within a class, the (n, 2) int32 origins cut_stamps takes, the (n, MAX_GROUP, 2) shifts of the members
+        from their stamp's centre pixel (0 beyond the members) and the six counts: all groups, then each class;
+        n = min(counts[0], max_groups), and max_groups=None stands for nstar.  The library writes the shifts at the
+        pitch of each class (group_shift_rows); here they are returned one group per row."""
+        po, ny, nx, crit, max_groups = group_arguments(pos, crit, shape, max_groups)
+        nstar, stride = po.shape
+        label = np.empty(nstar, dtype=np.int32)
+        groups = np.empty((max_groups, NGROUP), dtype=np.int32)
+        origin = np.empty((max_groups, 2), dtype=np.int32)
+        shift = np.empty((max_groups, MAX_GROUP, 2))
+        counts = np.zeros(1 + MAX_GROUP + 1, dtype=np.int32)
+        self._call_group(ny, nx, nstar, po, stride, crit, max_groups, label, groups, origin, shift, counts, 0)
+        n = min(int(counts[0]), max_groups)
+        return label, groups[:n], origin[:n], group_shift_rows(shift, counts)[:n], counts
+
+    def group_stars_device(self, ny, nx, nstar, pos_ptr, stride, crit, max_groups, label_ptr, group_ptr, count_ptr, *,
+                           origin_ptr=None, shift_ptr=None):
+        """Device-buffer form (asynchronous, on_device = 1): `pos_ptr` ([nstar][stride] float64), `label_ptr` ([nstar]
+        int32), `group_ptr` ([max_groups][NGROUP] int32), `count_ptr` ([6] int32), `origin_ptr` ([max_groups][2] int32)
+        and `shift_ptr` ([max_groups][MAX_GROUP][2] float64; both or neither) are raw device pointers (int) on this
+        context's GPU; the call is queued on the context stream.  With the counts c and offset_k = c[1] + .. + c[k - 1],
+        origin_ptr + 8 offset_k bytes and shift_ptr + 64 offset_k bytes are what cut_stamps_device and
+        fit_groups_psf_device (fit_stamps_psf_device for k = 1) take for the c[k] groups of k stars.  A position out of
+        range is a filler with the label -2."""
+        frame_shape(ny, nx)
+        nstar, stride, crit, max_groups = group_parameters(nstar, stride, crit, max_groups)
+        _device_pointers(pos_ptr=pos_ptr, label_ptr=label_ptr, group_ptr=group_ptr, count_ptr=count_ptr)
+        if bool(origin_ptr) != bool(shift_ptr):
+            raise ValueError('origin_ptr and shift_ptr must both be None or both be device pointers')
+        self._call_group(ny, nx, nstar, pos_ptr, stride, crit, max_groups, label_ptr, group_ptr, origin_ptr, shift_ptr,
+                         count_ptr, 1)
+
     def debug_fetch(self, what, shape):
         out = np.empty(int(np.prod(shape)))
         n = _check(self.lib.mpsfr_debug_fetch(self._h, what.encode(), _dptr(out), out.size))
@@ -1324,6 +1378,72 @@ def find_arguments(image, var, psf, half, sep, threshold, max_stars, dimpsf=40):
     if np.all(core == core[0, 0]):
         raise ValueError('psf must not be constant over its core')
     return im, va, ps, half, sep, threshold, max_stars
+
+
+def group_parameters(nstar, stride, crit, max_groups):
+    """(nstar, stride, crit, max_groups) of a group call, validated as mpsfr_group_stars validates them (ValueError);
+    max_groups=None stands for nstar."""
+    def integer(name, n, lo, hi):
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not lo <= n <= hi:
+            raise ValueError('%s must be an integer between %d and %d' % (name, lo, hi))
+        return int(n)
+    nstar = integer('nstar', nstar, 1, GROUP_MAX_STARS)
+    stride = integer('stride', stride, 2, (1 << 31) - 1)
+    max_groups = nstar if max_groups is None else integer('max_groups', max_groups, 1, (1 << 31) - 1)
+    if isinstance(crit, bool) or not isinstance(crit, (int, float, np.integer, np.floating)) \
+            or not 0.0 < crit <= GROUP_MAX_CRIT:
+        raise ValueError('crit must be a number above 0 and at most %g pixels' % GROUP_MAX_CRIT)
+    return nstar, stride, float(crit), max_groups
+
+
+def group_arguments(pos, crit, shape, max_groups=None):
+    """(pos, ny, nx, crit, max_groups) of a host group call, validated as mpsfr_group_stars validates host arguments
+    (ValueError): `pos` a numeric (nstar, stride >= 2) array whose first two columns are (row, column); a row with a NaN
+    in either is a filler, every other row lies within [-1, ny] x [-1, nx]; `shape` = (ny, nx) the shape of a frame."""
+    try:
+        ny, nx = shape
+    except (TypeError, ValueError):
+        raise ValueError('shape must be (ny, nx)') from None
+    ny, nx = frame_shape(ny, nx)
+    try:
+        po = np.ascontiguousarray(pos, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('pos must be a numeric array') from None
+    if po.ndim != 2 or po.shape[0] < 1 or po.shape[1] < 2:
+        raise ValueError('pos must have the shape (nstar, stride) with nstar >= 1 and stride >= 2')
+    nstar, stride, crit, max_groups = group_parameters(po.shape[0], po.shape[1], crit, max_groups)
+    y, x = po[:, 0], po[:, 1]
+    star = ~(np.isnan(y) | np.isnan(x))
+    with np.errstate(invalid='ignore'):
+        inside = (y >= -1.0) & (y <= ny) & (x >= -1.0) & (x <= nx)
+    if np.any(star & ~inside):
+        raise ValueError('a position lies outside [-1, ny] x [-1, nx]')
+    return po, ny, nx, crit, max_groups
+
+
+def group_offsets(counts):
+    """The first row of every class in the tables of mpsfr_group_stars, from its six counts: offsets[k - 1] for the
+    groups of k = 1 .. MAX_GROUP stars, offsets[MAX_GROUP] for the oversize ones, offsets[MAX_GROUP + 1] the total."""
+    c = np.asarray(counts, dtype=np.int64)
+    if c.shape != (MAX_GROUP + 2,):
+        raise ValueError('counts must hold the %d counts of a group call' % (MAX_GROUP + 2))
+    return np.concatenate(([0], np.cumsum(c[1:])))
+
+
+def group_shift_rows(shift, counts):
+    """The shifts of mpsfr_group_stars one group per row: (max_groups, MAX_GROUP, 2), zero beyond a group's members,
+    from the buffer `shift` of max_groups * MAX_GROUP * 2 doubles, in which the shifts of the groups of k stars lie at
+    a pitch of 2 k doubles from 8 offset_k on."""
+    buf = np.asarray(shift, dtype=np.float64).reshape(-1)
+    rows = buf.size // (2 * MAX_GROUP)
+    out = np.zeros((rows, MAX_GROUP, 2))
+    off = group_offsets(counts)
+    for k in range(1, MAX_GROUP + 1):
+        lo = int(min(off[k - 1], rows))
+        n = int(min(off[k], rows)) - lo
+        if n > 0:
+            out[lo:lo + n, :k] = buf[8 * lo:8 * lo + 2 * k * n].reshape(n, k, 2)
+    return out
 
 
 def _group_size(nsrc):

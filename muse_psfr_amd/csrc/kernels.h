@@ -304,6 +304,15 @@ size_t find_workspace_bytes(int ny, int nx, int max_stars, bool with_map);
 void launch_find_stars(hipStream_t s, int ny, int nx, const double* d_image, const double* d_var, const double* d_psf,
                        int half, int sep, double threshold, int max_stars, double* d_star_out, int32_t* d_origin_out,
                        int32_t* d_count_out, double* d_map_out, void* d_ws);
+// Friends-of-friends groups of stars (group.hip; mpsfr_group_stars, include/mpsfr.h): the connected components of
+// "d2 <= crit^2" over the positions d_pos [nstar][stride] (columns 0 and 1: y, x) -- labels into d_label_out [nstar],
+// rows in (class, label) order into d_group_out [max_groups][8] and d_origin_out [max_groups][2], shifts at the
+// per-class pitch into d_shift_out [max_groups][8] (both or neither), the six counts into d_count_out.
+// d_ws: group_workspace_bytes(ny, nx, nstar, max_groups) bytes; the launch writes every word of it before it reads it.
+size_t group_workspace_bytes(int ny, int nx, int nstar, int max_groups);
+void launch_group_stars(hipStream_t s, int ny, int nx, int nstar, const double* d_pos, int stride, double crit,
+                        int max_groups, int32_t* d_label_out, int32_t* d_group_out, int32_t* d_origin_out,
+                        double* d_shift_out, int32_t* d_count_out, void* d_ws);
 // band-integrated stamps (band.hip): d_fin [ntb][nl][40][40] (float if fin_f32, else double) reduced over wavelength
 // into d_out [ntb][nband][40][40] double with the weights d_w [nl][band_stride(nband)] (zero beyond nband)
 constexpr int MAX_BANDS = 16;    // MPSFR_MAX_BANDS

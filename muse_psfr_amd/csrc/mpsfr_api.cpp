@@ -158,6 +158,7 @@ struct mpsfr_ctx {
     DevBuf specx;                      // [nl] the abscissa of mpsfr_fit_spectra_psf's drift
     DevBuf render;                     // work lists of mpsfr_render_stars (render_workspace_bytes)
     DevBuf find;                       // core, map, masks and counts of mpsfr_find_stars (find_workspace_bytes)
+    DevBuf group;                      // cells, union-find and row lists of mpsfr_group_stars (group_workspace_bytes)
     DevBuf fit, sum, stage, lsum;      // lsum: [lanes][nl][40][40] per-lane partial stamp sums
     // mpsfr_psd_to_psf: a stream and workspaces of its own, so that it never waits for nor touches the lanes
     struct P2P {
@@ -720,7 +721,7 @@ void mpsfr_destroy(mpsfr_ctx* c) {
     }
     DevBuf* all[] = {&c->scoef, &c->stwk, &c->ssup, &c->tw64, &c->tel, &c->rows, &c->tlmax, &c->tl2, &c->tlb, &c->aotab, &c->samp_p,
                      &c->samp_a, &c->G, &c->xtab, &c->etab, &c->gtab, &c->kmuse, &c->fit, &c->sum,
-                     &c->stage, &c->lsum, &c->mfclk, &c->specx, &c->render, &c->find};
+                     &c->stage, &c->lsum, &c->mfclk, &c->specx, &c->render, &c->find, &c->group};
     for (auto b : all) release(*b);
     if (c->p2p.stream) { (void)hipStreamSynchronize(c->p2p.stream); (void)hipStreamDestroy(c->p2p.stream); }
     DevBuf* p2p[] = {&c->p2p.twm, &c->p2p.psd, &c->p2p.cm, &c->p2p.d0t, &c->p2p.pup, &c->p2p.phase, &c->p2p.lbda,
@@ -2637,6 +2638,44 @@ int mpsfr_find_stars(mpsfr_ctx* c, int ny, int nx, const double* image, const do
     return stamp_call(c, on_device, in, out, [&](hipStream_t s, const void* const* d, double* const* d_out) {
         launch_find_stars(s, ny, nx, (const double*)d[0], (const double*)d[1], (const double*)d[2], half, sep, threshold,
                           max_stars, d_out[0], (int32_t*)d_out[2], (int32_t*)d_out[3], d_out[1], c->find.p);
+    });
+}
+
+static_assert(MPSFR_NGROUP == 8 && MPSFR_MAX_GROUP == 4 && MPSFR_GROUP_MAX_CRIT == 2.0 * MPSFR_FIT_PSF_MAX_SHIFT,
+              "K_GROUP_ROWS row layout, the member slots and the cell side");
+
+int mpsfr_group_stars(mpsfr_ctx* c, int ny, int nx, int nstar, const double* pos, int stride, double crit,
+                      int max_groups, int32_t* label_out, int32_t* group_out, int32_t* origin_out, double* shift_out,
+                      int32_t* count_out, int on_device) {
+    if (!c || !pos || !label_out || !group_out || !count_out)
+        return fail(MPSFR_E_INVALID, "group_stars: bad argument (pos, label_out, group_out and count_out are required)");
+    int rc;
+    if ((rc = frame_shape("group_stars", ny, nx))) return rc;
+    if (nstar < 1 || nstar > (1 << 24)) return fail(MPSFR_E_INVALID, "group_stars: nstar=%d outside 1..2^24", nstar);
+    if (stride < 2) return fail(MPSFR_E_INVALID, "group_stars: stride=%d below 2", stride);
+    if (!(crit > 0.0 && crit <= MPSFR_GROUP_MAX_CRIT))
+        return fail(MPSFR_E_INVALID, "group_stars: crit must be finite, > 0 and at most %g pixels", MPSFR_GROUP_MAX_CRIT);
+    if (max_groups < 1) return fail(MPSFR_E_INVALID, "group_stars: max_groups=%d below 1", max_groups);
+    if ((origin_out == nullptr) != (shift_out == nullptr))
+        return fail(MPSFR_E_INVALID, "group_stars: origin_out and shift_out must both be NULL or both be given");
+    if (!on_device)
+        for (int k = 0; k < nstar; ++k) {
+            const double y = pos[(size_t)k * stride], x = pos[(size_t)k * stride + 1];
+            if (std::isnan(y) || std::isnan(x)) continue;
+            if (!(y >= -1.0 && y <= (double)ny && x >= -1.0 && x <= (double)nx))
+                return fail(MPSFR_E_INVALID, "group_stars: a position outside [-1, ny] x [-1, nx]");
+        }
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = ensure(c, c->group, group_workspace_bytes(ny, nx, nstar, max_groups)))) return rc;
+    const StampIn in[] = {{pos, (size_t)nstar * stride, sizeof(double)}};
+    const StampOut out[] = {{shift_out, (size_t)max_groups * 8},
+                            {label_out, (size_t)nstar, sizeof(int32_t)},
+                            {group_out, (size_t)max_groups * MPSFR_NGROUP, sizeof(int32_t)},
+                            {origin_out, (size_t)2 * max_groups, sizeof(int32_t)},
+                            {count_out, 6, sizeof(int32_t)}};
+    return stamp_call(c, on_device, in, out, [&](hipStream_t s, const void* const* d, double* const* d_out) {
+        launch_group_stars(s, ny, nx, nstar, (const double*)d[0], stride, crit, max_groups, (int32_t*)d_out[1],
+                           (int32_t*)d_out[2], (int32_t*)d_out[3], d_out[0], (int32_t*)d_out[4], c->group.p);
     });
 }
 

@@ -716,6 +716,156 @@ def find_stars(image, psf, var=None, *, threshold=5.0, half=3, sep=None, sharp=(
     return _make_table(cols)
 
 
+def _star_positions(positions):
+    """(n, 2) float64 (row, column) in pixels from an (n, 2) array or a find_stars table (its `position` column)."""
+    try:
+        pos = positions['position']
+    except (KeyError, IndexError, TypeError, ValueError):
+        pos = positions
+    try:
+        pos = np.asarray(pos, dtype=float)
+    except (TypeError, ValueError):
+        raise ValueError('positions must be a numeric array or a find_stars table') from None
+    if pos.ndim != 2 or pos.shape[1] != 2 or pos.shape[0] < 1:
+        raise ValueError('positions must have the shape (n, 2)')
+    return np.ascontiguousarray(pos)
+
+
+def _group_all(ctx, pos, crit, shape):
+    """ctx.group_stars with room for every group; also the row of every star's group in the tables (-1: a filler)."""
+    label, groups, origin, shift, counts = ctx.group_stars(pos, crit, shape)
+    row = np.full(pos.shape[0], -1, dtype=np.int64)
+    row[groups[:, 2]] = np.arange(groups.shape[0])
+    star_row = np.where(label >= 0, row[np.maximum(label, 0)], -1)
+    return label, groups, origin, shift, counts, star_row
+
+
+def group_stars(positions, crit, shape=None, *, pixscale=0.2, precision='mixed', device=0):
+    """Friends-of-friends groups of stars, on the GPU (DAOPHOT's GROUP): stars closer than `crit` pixels (at most 16)
+    are linked, and a group is a connected component -- the stars that have to be fitted together.  `positions`: an
+    (n, 2) array of (row, column) in pixels, or a find_stars table; rows with a NaN belong to no group.  `shape`:
+    (ny, nx) of the frame, in which the positions lie within [-1, ny] x [-1, nx]; None: the smallest frame that
+    holds them.
+
+    Returns (stars, groups).  stars, one row per position in input order: label (the smallest index of the star's
+    group, -1 for a NaN row), size (members of its group) and flags (those of its group).  groups, ordered by size
+    (1, 2, 3, 4 members, then larger ones) and by label within a size: label, size, members (4; the indices in
+    ascending order, -1 beyond the group, the four smallest of a larger group), origin (2, int32: the stamp
+    cut_star_stamps-like calls take, centred on the group), shift (4, 2, pixels: every member from the centre pixel of
+    that stamp) and flags (1: more than four members, no origin -- group again with a smaller crit; 2: a member lies
+    more than 8 pixels from the stamp's centre, beyond the domain of the fits)."""
+    _pixscale(pixscale)
+    pos = _star_positions(positions)
+    if shape is None:
+        finite = pos[np.all(np.isfinite(pos), axis=1)]
+        shape = (1, 1) if finite.size == 0 else tuple(int(max(1, np.ceil(v))) for v in finite.max(axis=0))
+    ctx = get_context(128, pixscale, 40, precision, device)
+    label, groups, origin, shift, counts, star_row = _group_all(ctx, pos, crit, shape)
+    stars = OrderedDict()
+    stars['label'] = label.astype(np.int64)
+    stars['size'] = np.where(star_row >= 0, groups[np.maximum(star_row, 0), 0], 0).astype(np.int64)
+    stars['flags'] = np.where(star_row >= 0, groups[np.maximum(star_row, 0), 1], 0).astype(np.int64)
+    cols = OrderedDict()
+    cols['label'] = groups[:, 2].astype(np.int64)
+    cols['size'] = groups[:, 0].astype(np.int64)
+    cols['members'] = groups[:, 4:8].astype(np.int64)
+    cols['origin'] = origin.astype(np.int32)
+    cols['shift'] = shift.copy()
+    cols['flags'] = groups[:, 1].astype(np.int64)
+    return _make_table(stars), _make_table(cols, {'counts': [int(c) for c in counts]})
+
+
+_FIT_COLS_FOUND = _FIT_COLS_GROUP + ('nsrc', 'label', 'crowded')
+
+
+def fit_found_stars(image, psf, found, *, var=None, crit, fit_back=True, mode='free', pixscale=0.2, precision='mixed',
+                    device=0):
+    """PSF-fitting photometry of the stars found in a frame, singles and blends alike, on the GPU: the stars `found` (a
+    find_stars table or an (n, 2) array of (row, column) in pixels) are grouped by friends of friends at the critical
+    separation `crit` (pixels, at most 16); one stamp per group is cut out of `image` (`var`: its variance frame or
+    None), centred on the group, and the model stamp `psf` (40, 40) is fitted to all stars of a group at once -- a
+    single star as fit_stars_with_psf does, two to four as fit_star_groups_with_psf does (fit_back, mode: as there),
+    with one cut and one fit call per group size that occurs.
+
+    Returns (fit, origin) in the form subtract_stars takes (with psf_index = zeros for the one model): `origin`
+    (ngroup, 2) int32 holds the stamp origin of every group, and `fit` has one row per star in input order with the
+    columns of fit_star_groups_with_psf -- `group` indexes `origin`, `source` numbers the star within its group -- plus
+    nsrc (stars in its group), label (the smallest star index of its group) and crowded: True for the stars of a group
+    of more than four or of one wider than the fit's domain (a member farther than 8 pixels from the stamp centre).
+    Those are not fitted: their rows carry status 2 and NaN; fit them after grouping again with a smaller crit."""
+    if not isinstance(fit_back, (bool, np.bool_)):
+        raise ValueError('fit_back must be True or False')
+    _pixscale(pixscale)
+    _lib.group_fit_flags(bool(fit_back), mode)
+    pos = _star_positions(found)
+    if not np.all(np.isfinite(pos)):
+        raise ValueError('the positions of the stars must be finite')
+    im, va = _lib.frame_images(image, var)
+    try:
+        ps = np.ascontiguousarray(psf, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('psf must be a numeric array') from None
+    if ps.ndim != 2 or ps.shape[0] != ps.shape[1]:
+        raise ValueError('psf must be one model stamp (40, 40)')
+    ctx = get_context(128, pixscale, ps.shape[-1], precision, device)
+    label, groups, origin, shift, counts, star_row = _group_all(ctx, pos, crit, im.shape)
+    nstar = pos.shape[0]
+    order = np.lexsort((np.arange(nstar), label))                  # the stars of a group together, ascending
+    first = np.concatenate([[True], label[order][1:] != label[order][:-1]])
+    start = np.maximum.accumulate(np.where(first, np.arange(nstar), 0))
+    source = np.empty(nstar, dtype=np.int64)
+    source[order] = np.arange(nstar) - start
+    cols = OrderedDict()
+    cols['group'] = star_row.copy()
+    cols['source'] = source
+    for name in _FIT_COLS_GROUP[2:]:
+        wide = name in ('shift', 'err_shift')
+        if name in ('npix', 'status'):
+            cols[name] = np.full(nstar, 2 if name == 'status' else 0, dtype=np.int64)
+        else:
+            cols[name] = np.full((nstar, 2) if wide else nstar, np.nan)
+    off = _lib.group_offsets(counts)
+    for K in range(1, _lib.MAX_GROUP + 1):
+        idx = np.arange(off[K - 1], off[K])
+        idx = idx[(groups[idx, 1] & _lib.GROUP_WIDE) == 0]
+        if idx.size == 0:
+            continue
+        res = ctx.cut_stamps(im, origin[idx], var=va)
+        stamps, sub_var = (res, None) if va is None else res
+        zeros = np.zeros(idx.size, dtype=np.int32)
+        if K == 1:
+            fit = ctx.fit_stamps_psf(stamps, ps[None], var=sub_var, psf_index=zeros, shift=shift[idx, 0],
+                                     background=bool(fit_back), fixed_shift=mode == 'fixed')
+            head = fit[:, [3, 9, 4, 11, 10]]
+            src = fit[:, None, [0, 1, 2, 6, 7, 8, 12, 13]]
+            corr = np.zeros((idx.size, 1))
+        else:
+            fit = ctx.fit_groups_psf(stamps, ps[None], shift[idx, :K], var=sub_var, psf_index=zeros,
+                                     background=bool(fit_back), mode=mode)
+            head = fit[:, [0, 1, 2, 5, 4]]
+            src = fit[:, 8:8 + 8 * K].reshape(idx.size, K, 8)
+            cm = np.zeros((idx.size, _lib.MAX_GROUP, _lib.MAX_GROUP))
+            for c, (i, j) in enumerate(_GROUP_PAIRS):
+                cm[:, i, j] = cm[:, j, i] = np.abs(fit[:, 40 + c])
+            corr = cm.max(axis=2)[:, :K]
+        rows = groups[idx, 4:4 + K].astype(np.int64).ravel()       # the stars themselves: input order
+        flat = src.reshape(-1, 8)
+        cols['scale'][rows] = flat[:, 0]
+        cols['shift'][rows] = flat[:, 1:3] * pixscale
+        cols['flux'][rows] = flat[:, 6]
+        cols['err_scale'][rows] = flat[:, 3]
+        cols['err_shift'][rows] = flat[:, 4:6] * pixscale
+        cols['err_flux'][rows] = flat[:, 7]
+        for c, name in enumerate(('back', 'err_back', 'chi2', 'npix', 'status')):
+            cols[name][rows] = np.repeat(head[:, c], K)
+        cols['max_corr'][rows] = corr.ravel()
+    cols['nsrc'] = groups[star_row, 0].astype(np.int64)
+    cols['label'] = label.astype(np.int64)
+    cols['crowded'] = groups[star_row, 1] != 0
+    assert tuple(cols) == _FIT_COLS_FOUND
+    return _make_table(cols), origin.astype(np.int32)
+
+
 def cut_star_stamps(image, positions, var=None, dimpsf=40, *, pixscale=0.2, precision='mixed', device=0):
     """Stamps of stars out of a frame, on the GPU: `image` (ny, nx), `positions` (n, 2) the (row, column) star centres
     in pixels.  Stamp k starts at origin[k] = rint(positions[k]) - dimpsf // 2, so the star sits within half a pixel of
