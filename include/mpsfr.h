@@ -733,6 +733,60 @@ int mpsfr_group_stars(mpsfr_ctx* ctx, int ny, int nx, int nstar, const double* p
                       int max_groups, int32_t* label_out, int32_t* group_out, int32_t* origin_out,
                       double* shift_out, int32_t* count_out, int on_device);
 
+/* Crowded-field PSF photometry: the fluxes of ALL stars of a frame in one solve -- positions known (the finder's or a
+ * catalogue's), PSF known, no limit on how many stars touch each other.  The step after mpsfr_group_stars for the
+ * groups it flags MPSFR_GROUP_OVERSIZE or MPSFR_GROUP_WIDE.
+ *
+ * image, var, psf, psf_index, origin, shift: as for mpsfr_render_stars and mpsfr_cut_stamps.  Star k is F_k P~_k, P~_k the
+ * cubic-convolution resampling of psf[psf_index[k]] placed by origin[k] and shifted by shift[k], zero outside its
+ * footprint (the (dimpsf + 20)^2 window); its centre is c_k = (double)(origin_k + dimpsf/2) + shift_k per axis.
+ * Arithmetic is fp64 in both precision modes.
+ * A pixel is valid when its datum is finite and var is finite and > 0 (var NULL: unit weights); w = 1 / var.
+ * The fit domain Omega: the valid pixels (Y, X) with dy dy + dx dx <= radius radius for an accepted star, dy = Y - c_y,
+ * dx = X - c_x (each product rounded, then the sum: no fused multiply-add; radius radius rounded).  radius in [1, 20].
+ * A star is accepted when index, shift and origin pass mpsfr_render_stars' per-star rule, its footprint meets the
+ * frame, its own disc holds a valid pixel and sum w P~_k^2 over the valid pixels of its own disc is positive and finite
+ * (so N_kk > 0: Omega only adds terms that are not negative).  Any other star is left out of the solve and of
+ * resid_out: its row is status 2 (1: its footprint misses the frame) and zero otherwise.
+ * Minimised over the F_k of the accepted stars and, with MPSFR_FIT_BACKGROUND, one constant b:
+ *     sum over Omega of w (D - b - sum_k F_k P~_k)^2;
+ * a pixel of Omega sees every star whose footprint reaches it.  Solver: conjugate gradients on the normal equations
+ * N u = A^T W D with the diagonal of N as preconditioner M, matrix-free; start F = scale0 (NULL: 0; a value that is not
+ * finite counts as 0 in the device form), b = 0; stop when r.M^-1 r <= tol^2 (r0.M^-1 r0), when r0 = 0, or after
+ * max_iter (1 .. 1000) steps; tol in (0, 1).  The loop is queued whole, without a host synchronisation: once the stop
+ * test has passed the kernels of the remaining iterations return at once.
+ *
+ * star_out [nstar][MPSFR_NFRAMEFIT]:  0 F   1 err_F   2 flux = F sum P   3 err_flux = err_F |sum P|   4 overlap
+ *     5 valid pixels in the star's own disc   6 N_kk = sum over Omega of w P~_k^2   7 status (0 fitted)
+ *   err_F = sqrt((chi2 / dof) / N_kk), dof = |Omega| - unknowns: the CONDITIONAL error, every other star held fixed.
+ *   overlap = sum_{l != k} N_kl / N_kk says when that is optimistic (0: the star is alone).  Marginal errors, the
+ *   diagonal of N^-1, are not computed; groups of up to four stars get them from mpsfr_fit_groups_psf.
+ * head_out [8]:  0 b   1 err_b = sqrt((chi2 / dof) / sum w)   2 chi2 of the result, from the residual frame itself
+ *     3 |Omega|   4 iterations done   5 the last sqrt(r.M^-1 r / r0.M^-1 r0)   6 accepted stars
+ *     7 status: 0 converged, 1 max_iter reached (the values are the last iterate), 2 nothing fitted -- no accepted star,
+ *     or |Omega| < unknowns + 1; the star rows are then status 2 or 1 and resid_out is a copy of image.
+ * resid_out [ny][nx] or NULL: image - sum_k F_k P~_k (b is not subtracted), made by the renderer: bit for bit what
+ *   mpsfr_render_stars(MPSFR_RENDER_SUBTRACT) gives with the fitted scales over the accepted stars in index order.
+ *
+ * The same call gives the same bits, a mixed context those of an f64 one; no sum depends on scheduling.  A power of two
+ * on var, or 2^k on the data (and scale0) with 4^k on var, scales F, b, the fluxes, the errors, chi2 and N_kk by exact
+ * powers of two and changes no other bit.  Two accepted stars at one position are no error: N is singular, their sum
+ * is determined, their split is not, and the call may end with status 1.
+ * Work memory, in one buffer of the context: render's lists, two frames of doubles, and
+ * 7 nstar + 4 ceil(ny nx / 4096) + 9 doubles and 2 nstar + 5 int32.
+ * on_device as mpsfr_render_stars.  MPSFR_E_INVALID, outputs untouched, nothing queued: ny or nx out of range; nstar
+ * outside 1 .. 2^20; npsf < 1; a NULL image, psf, origin, star_out or head_out; psf_index NULL with npsf != nstar;
+ * radius, tol or max_iter out of range or not finite; flag bits other than MPSFR_FIT_BACKGROUND; on host pointers what
+ * mpsfr_render_stars refuses (an index, shift or origin out of range, a scale0 that is not finite).  Timed under the
+ * fit's profiling id. */
+#define MPSFR_NFRAMEFIT 8                 /* doubles per star in star_out, and in head_out */
+#define MPSFR_FRAME_FIT_MAX_RADIUS 20.0   /* pixels */
+#define MPSFR_FRAME_FIT_MAX_ITER 1000
+int mpsfr_fit_frame_psf(mpsfr_ctx* ctx, int ny, int nx, const double* image, const double* var, int nstar, int npsf,
+                        const double* psf, const int32_t* psf_index, const int32_t* origin, const double* shift,
+                        const double* scale0, double radius, int flags, int max_iter, double tol, double* star_out,
+                        double* head_out, double* resid_out, int on_device);
+
 /* The stages of the path as the reference exports them (muse_psfr/__init__.py:16: `from .psfrec import *`),
  * for a caller that holds its own PSD or its own stamps.  Host buffers, synchronous, float64; the same
  * kernels as mpsfr_reconstruct entered or left at another stage.

@@ -44,6 +44,10 @@ GROUP_OVERSIZE = 1           # group flag: more than MAX_GROUP members (MPSFR_GR
 GROUP_WIDE = 2               # group flag: a member's |shift| beyond FIT_PSF_MAX_SHIFT (MPSFR_GROUP_WIDE)
 GROUP_MAX_STARS = 1 << 24    # stars of one call
 GROUP_FILLER_ORIGIN = -(1 << 30)   # origin of filler rows and of oversize groups
+NFRAMEFIT = 8                # doubles per star of mpsfr_fit_frame_psf (MPSFR_NFRAMEFIT), and of its head
+FRAME_FIT_MAX_RADIUS = 20.0  # largest fit radius in pixels (MPSFR_FRAME_FIT_MAX_RADIUS)
+FRAME_FIT_MAX_ITER = 1000    # MPSFR_FRAME_FIT_MAX_ITER
+FRAME_FIT_MAX_STARS = 1 << 20
 DIM_AO = 80
 PREC_MIXED, PREC_F64 = 0, 1
 E_GRID = -3
@@ -141,6 +145,9 @@ def load():
     lib.mpsfr_group_stars.argtypes = [p, C.c_int, C.c_int, C.c_int, p, C.c_int, C.c_double, C.c_int, p, p, p, p, p,
                                       C.c_int]
     lib.mpsfr_group_stars.restype = C.c_int
+    lib.mpsfr_fit_frame_psf.argtypes = [p, C.c_int, C.c_int, p, p, C.c_int, C.c_int, p, p, p, p, p, C.c_double, C.c_int,
+                                        C.c_int, C.c_double, p, p, p, C.c_int]
+    lib.mpsfr_fit_frame_psf.restype = C.c_int
     lib.mpsfr_simul_psd.argtypes = [p, C.c_double, C.c_double, C.c_double, C.c_int, dp, C.c_double, C.c_int, u8p, u8p, dp]
     lib.mpsfr_simul_psd.restype = C.c_int
     lib.mpsfr_psf_from_psd.argtypes = [p, C.c_int, dp, C.c_int, dp, dp]
@@ -188,7 +195,7 @@ def load():
 
 
 EXPORTS = ['mpsfr_create', 'mpsfr_destroy', 'mpsfr_last_error', 'mpsfr_set_option',
-           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_fit_stamps_psf', 'mpsfr_fit_groups_psf', 'mpsfr_fit_spectra_psf', 'mpsfr_stamp_metrics', 'mpsfr_cut_stamps', 'mpsfr_render_stars', 'mpsfr_find_stars', 'mpsfr_group_stars', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
+           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_fit_stamps_psf', 'mpsfr_fit_groups_psf', 'mpsfr_fit_spectra_psf', 'mpsfr_stamp_metrics', 'mpsfr_cut_stamps', 'mpsfr_render_stars', 'mpsfr_find_stars', 'mpsfr_group_stars', 'mpsfr_fit_frame_psf', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
            'mpsfr_psd_to_psf',
            'mpsfr_convolve_stamps', 'mpsfr_fit_rows', 'mpsfr_sync', 'mpsfr_last_ticket', 'mpsfr_wait', 'mpsfr_abandon',
            'mpsfr_stream', 'mpsfr_stream_wait', 'mpsfr_wait_event',
@@ -1125,6 +1132,62 @@ class Context:
         self._call_group(ny, nx, nstar, pos_ptr, stride, crit, max_groups, label_ptr, group_ptr, origin_ptr, shift_ptr,
                          count_ptr, 1)
 
+    def _call_frame_fit(self, ny, nx, image, var, nstar, npsf, psf, index, origin, shift, scale0, radius, flags, max_iter,
+                        tol, rows, head, resid, on_device):
+        p = _devptr if on_device else _vptr
+        _check(self.lib.mpsfr_fit_frame_psf(self._h, int(ny), int(nx), p(image), p(var), int(nstar), int(npsf), p(psf),
+                                            p(index), p(origin), p(shift), p(scale0), float(radius), flags,
+                                            int(max_iter), float(tol), p(rows), p(head), p(resid), on_device))
+
+    def fit_frame_psf(self, image, psf, origin, *, var=None, shift=None, psf_index=None, scale0=None, radius=8.0,
+                      background=True, max_iter=100, tol=1e-10, return_residual=False):
+        """Crowded-field photometry (mpsfr_fit_frame_psf): the fluxes of all stars of `image` (ny, nx; `var` of the
+        same shape or None) at once, star k being F_k times the model stamp psf[psf_index[k]] (psf[k] without
+        psf_index) resampled at `shift` (n, 2) pixels with its stamp's pixel [0][0] on origin[k] -- as render_stars
+        takes them.  One weighted linear least-squares problem over the valid pixels within `radius` (1 .. 20 pixels)
+        of a star, with one constant if `background`, solved by preconditioned conjugate gradients from `scale0` (n,;
+        None: zeros) to the relative residual `tol` or max_iter (1 .. 1000) steps.  Returns (rows, head) and, with
+        return_residual, the frame minus the fitted stars.  rows (n, NFRAMEFIT): 0 F, 1 its conditional error (the
+        other stars held fixed), 2 flux, 3 its error, 4 overlap (sum of the star's off-diagonal terms of the normal
+        matrix over its diagonal term: 0 for a star alone), 5 valid pixels in its disc, 6 its diagonal term, 7 status
+        (0 fitted, 1 off the frame, 2 left out).  head (NFRAMEFIT,): 0 b, 1 its error, 2 chi2, 3 pixels fitted, 4
+        iterations, 5 the last relative residual, 6 stars fitted, 7 status (0 converged, 1 max_iter reached, 2 nothing
+        fitted)."""
+        im, va, ps, ix, og, sh, s0, radius, flags, max_iter, tol = frame_fit_arguments(
+            image, var, psf, psf_index, origin, shift, scale0, radius, background, max_iter, tol, self.dimpsf)
+        if not isinstance(return_residual, (bool, np.bool_)):
+            raise ValueError('return_residual must be True or False')
+        ny, nx = im.shape
+        n = og.shape[0]
+        rows = np.empty((n, NFRAMEFIT))
+        head = np.empty(NFRAMEFIT)
+        resid = np.empty((ny, nx)) if return_residual else None
+        self._call_frame_fit(ny, nx, im, va, n, ps.shape[0], ps, ix, og, sh, s0, radius, flags, max_iter, tol, rows, head,
+                             resid, 0)
+        return (rows, head) + ((resid,) if return_residual else ())
+
+    def fit_frame_psf_device(self, ny, nx, image_ptr, nstar, npsf, psf_ptr, origin_ptr, star_out_ptr, head_ptr, *,
+                             var_ptr=None, shift_ptr=None, psf_index_ptr=None, scale0_ptr=None, resid_ptr=None,
+                             radius=8.0, background=True, max_iter=100, tol=1e-10):
+        """Device-buffer form (asynchronous, on_device = 1): `image_ptr`, `var_ptr`, `resid_ptr` ([ny][nx] float64;
+        var_ptr None: unit weights, resid_ptr None: no residual frame), `psf_ptr` ([npsf][dimpsf][dimpsf] float64),
+        `origin_ptr` ([nstar][2] int32), `shift_ptr` ([nstar][2] float64, or None for zeros), `psf_index_ptr` ([nstar]
+        int32, or None with npsf == nstar), `scale0_ptr` ([nstar] float64, or None for zeros), `star_out_ptr`
+        ([nstar][NFRAMEFIT] float64) and `head_ptr` ([NFRAMEFIT] float64) are raw device pointers (int) on this
+        context's GPU; the whole solve is queued on the context stream, after any device-output reconstruct of this
+        context, without a host synchronisation.  An index out of range, a shift outside the domain or an |origin|
+        above 2^30 makes that star status 2; the finder's filler rows are such stars."""
+        frame_shape(ny, nx)
+        nstar = frame_fit_stars(nstar)
+        _positive_int('npsf', npsf)
+        _device_pointers(image_ptr=image_ptr, psf_ptr=psf_ptr, origin_ptr=origin_ptr, star_out_ptr=star_out_ptr,
+                         head_ptr=head_ptr)
+        if not psf_index_ptr and npsf != nstar:
+            raise ValueError('without psf_index_ptr, npsf must equal nstar')
+        radius, flags, max_iter, tol = frame_fit_parameters(radius, background, max_iter, tol)
+        self._call_frame_fit(ny, nx, image_ptr, var_ptr, nstar, npsf, psf_ptr, psf_index_ptr, origin_ptr, shift_ptr,
+                             scale0_ptr, radius, flags, max_iter, tol, star_out_ptr, head_ptr, resid_ptr, 1)
+
     def debug_fetch(self, what, shape):
         out = np.empty(int(np.prod(shape)))
         n = _check(self.lib.mpsfr_debug_fetch(self._h, what.encode(), _dptr(out), out.size))
@@ -1378,6 +1441,56 @@ def find_arguments(image, var, psf, half, sep, threshold, max_stars, dimpsf=40):
     if np.all(core == core[0, 0]):
         raise ValueError('psf must not be constant over its core')
     return im, va, ps, half, sep, threshold, max_stars
+
+
+def frame_fit_stars(nstar):
+    """The number of stars of a frame fit: an integer in 1 .. FRAME_FIT_MAX_STARS (ValueError)."""
+    if isinstance(nstar, bool) or not isinstance(nstar, (int, np.integer)) or not 1 <= nstar <= FRAME_FIT_MAX_STARS:
+        raise ValueError('nstar must be an integer between 1 and %d' % FRAME_FIT_MAX_STARS)
+    return int(nstar)
+
+
+def frame_fit_parameters(radius, background, max_iter, tol):
+    """(radius, flags, max_iter, tol) of a frame fit, validated as mpsfr_fit_frame_psf validates them (ValueError)."""
+    def number(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError('%s must be a finite number' % name)
+        return float(v)
+    radius = number('radius', radius)
+    if not 1.0 <= radius <= FRAME_FIT_MAX_RADIUS:
+        raise ValueError('radius must lie between 1 and %g pixels' % FRAME_FIT_MAX_RADIUS)
+    tol = number('tol', tol)
+    if not 0.0 < tol < 1.0:
+        raise ValueError('tol must lie in (0, 1)')
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) \
+            or not 1 <= max_iter <= FRAME_FIT_MAX_ITER:
+        raise ValueError('max_iter must be an integer between 1 and %d' % FRAME_FIT_MAX_ITER)
+    if not isinstance(background, (bool, np.bool_)):
+        raise ValueError('background must be True or False')
+    return radius, FIT_BACKGROUND if background else 0, int(max_iter), tol
+
+
+def frame_fit_arguments(image, var, psf, psf_index, origin, shift, scale0, radius, background, max_iter, tol, dimpsf=40):
+    """(image, var or None, psf, psf_index, origin, shift, scale0 or None, radius, flags, max_iter, tol) of a host frame
+    fit, validated as mpsfr_fit_frame_psf validates host arguments (ValueError): the frame as frame_images, origin as
+    star_origins, psf, psf_index and shift as psf_fit_arguments, scale0 n finite values or None."""
+    im, va = frame_images(image, var)
+    og = star_origins(origin)
+    n = frame_fit_stars(og.shape[0])
+    ps, ix, sh, _ = psf_fit_arguments(n, psf, psf_index, shift, True, False, dimpsf)
+    radius, flags, max_iter, tol = frame_fit_parameters(radius, background, max_iter, tol)
+    s0 = None
+    if scale0 is not None:
+        try:
+            s0 = np.asarray(scale0, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('scale0 must be a numeric array') from None
+        if s0.size != n or s0.ndim > 1:
+            raise ValueError('scale0 must hold one value per star (%d)' % n)
+        if not np.all(np.isfinite(s0)):
+            raise ValueError('scale0 must be finite')
+        s0 = np.ascontiguousarray(s0).reshape(n)
+    return im, va, ps, ix, og, sh, s0, radius, flags, max_iter, tol
 
 
 def group_parameters(nstar, stride, crit, max_groups):

@@ -1,0 +1,492 @@
+// Crowded-field PSF photometry (mpsfr_fit_frame_psf, include/mpsfr.h): the fluxes of all stars of
+// a frame, and one constant, as one weighted linear least-squares problem, solved by Jacobi-preconditioned conjugate
+// gradients on the normal equations without ever forming them.  A x is the renderer's tile walk (render.hip) over lists
+// built once per solve; what is new here:
+//   k_ff_star<false>  one workgroup per star: judges it (render's rule, the footprint, the valid pixels of its own disc,
+//                     sum w P~^2 over them) and takes sum P of its model
+//   k_ff_domain       one workgroup per frame tile: W = w [pixel in Omega], Omega the valid pixels in the disc of an
+//                     accepted star, from the tile's star list
+//   k_ff_star<true>   the projection, one workgroup per accepted star: g_k = sum W P~_k (V + c) over its footprint and,
+//                     in the first pass, N_kk = sum W P~_k^2 -- the model stamp with the rows and columns its taps
+//                     reach staged once in LDS, every thread a fixed set of footprint pixels, a fixed tree
+//   k_ff_reduce       sum W (V + c), sum W, sum W (V + c)^2 and |Omega| over chunks of the frame, one partial per chunk
+//   k_ff_step<phase>  one workgroup: the conjugate-gradient step over the unknowns, the stop test and the done word; the
+//                     first residual; the rows of the result
+// Every sum has a fixed order (no floating-point atomics), all arithmetic is fp64, and nothing waits for the host: the
+// scalars live in the work buffer, and once the done word is set the queued kernels of the later iterations return.
+#include "fit_psf_common.h"
+
+namespace mpsfr {
+namespace {
+
+constexpr int kStarThreads = 256;
+constexpr int kFootPix = kPsfSide * kPsfSide;                              // 3600 footprint pixels
+constexpr int kFootShare = (kFootPix + kStarThreads - 1) / kStarThreads;    // per thread: e = tid + 256 m
+constexpr int kFootBatch = 5;                                               // of them loaded at once (3, 15: slower)
+static_assert(kFootShare % kFootBatch == 0, "whole batches");
+constexpr int kFootSide = kPsfSide + 3;                                     // model rows / columns a footprint's taps touch
+constexpr int kFootStride = kFootSide + 1;
+constexpr int kChunk = 4096;                                                // frame pixels per partial of k_ff_reduce
+constexpr int kStepThreads = 1024;
+constexpr int kMaxOrigin = 1 << 30;
+constexpr int kTile = 32;                                                   // the renderer's frame tile
+constexpr int NROW = 8;                                                     // MPSFR_NFRAMEFIT
+
+// the scalars of a solve: doubles, then ints
+enum { S_RHO = 0, S_RHO0, S_REL, S_WSUM, S_NDOUBLE };
+enum { I_DONE = 0, I_ITER, I_STATUS, I_NACC, I_NOMEGA, I_NINT };
+
+// the footprint's part of a model stamp in LDS, zero outside the model: tap (a, b) of the pixel at offset o
+struct FootStamp {
+    const double* base;
+    template <typename RE>
+    __device__ __forceinline__ RE at(int o, int, int, int a, int b) const {
+        return (RE)base[o + a * kFootStride + b];
+    }
+};
+
+// the sum of v over the workgroup's T threads in a fixed tree (the wave's ladder, then the waves in order); every
+// thread gets it.  `part`: T / 64 doubles of LDS, free again on return.
+template <int T>
+__device__ __forceinline__ double block_sum(double v, double* part) {
+    v = wave_sum(v);
+    const int tid = threadIdx.x;
+    __syncthreads();
+    if ((tid & 63) == 0) part[tid >> 6] = v;
+    __syncthreads();
+    double s = part[0];
+#pragma unroll
+    for (int w = 1; w < T / 64; ++w) s += part[w];
+    return s;
+}
+
+// is the frame pixel (Y, X) in the disc of the star centred on (cy, cx)?  Each product rounded, then the sum.
+__device__ __forceinline__ bool in_disc(int Y, int X, double cy, double cx, double r2) {
+#pragma clang fp contract(off)
+    const double dy = (double)Y - cy, dx = (double)X - cx;
+    const double a = dy * dy, b = dx * dx;
+    return a + b <= r2;
+}
+
+// PROJECT = false: the star is judged; accept, stat, ndisc, sump, diag (the sum over its own disc) and x (its start)
+// are written.  PROJECT = true: g[k] = sum W P~ (V + csign c) and, with diag, diag[k] = sum W P~^2 for an accepted star.
+template <bool PROJECT>
+__global__ __launch_bounds__(kStarThreads) void k_ff_star(int ny, int nx, int npsf, const double* __restrict__ image,
+                                                         const double* __restrict__ var,
+                                                         const double* __restrict__ psf,
+                                                         const int32_t* __restrict__ index,
+                                                         const int32_t* __restrict__ origin,
+                                                         const double* __restrict__ shift,
+                                                         const double* __restrict__ scale0, double r2,
+                                                         const double* __restrict__ W, const double* __restrict__ V,
+                                                         const double* __restrict__ cptr, double csign,
+                                                         int32_t* __restrict__ accept, int32_t* __restrict__ stat,
+                                                         double* __restrict__ ndisc, double* __restrict__ sump,
+                                                         double* __restrict__ x, double* __restrict__ g,
+                                                         double* __restrict__ diag, const int32_t* __restrict__ done) {
+    __shared__ double stage[kFootSide * kFootStride];
+    __shared__ double part[kStarThreads / 64];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    if constexpr (PROJECT) {
+        if ((done && *done) || !accept[k]) return;
+    }
+    const int op = origin[2 * k], oq = origin[2 * k + 1];
+    const int ix = index ? index[k] : k;
+    const double dp = shift ? shift[2 * k] : 0.0, dq = shift ? shift[2 * k + 1] : 0.0;
+    if constexpr (!PROJECT) {
+        const bool ok = (unsigned)ix < (unsigned)npsf && psf_inside(dp, dq) && op >= -kMaxOrigin && op <= kMaxOrigin &&
+                        oq >= -kMaxOrigin && oq <= kMaxOrigin;
+        const bool hit = ok && op - kPsfApron < ny && op + NS + kPsfApron > 0 && oq - kPsfApron < nx &&
+                         oq + NS + kPsfApron > 0;
+        if (!hit) {                                   // (the same for all threads)
+            if (tid == 0) {
+                accept[k] = 0;
+                stat[k] = ok ? 1 : 2;
+                ndisc[k] = 0.0;
+                sump[k] = 0.0;
+                diag[k] = 0.0;
+                x[k] = 0.0;
+            }
+            return;
+        }
+    }
+    const double* P = psf + (size_t)ix * (NS * NS);
+    const KeysTaps<double> ty(dp), tx(dq);
+    // stage[i][j] = model pixel (ty.f - 11 + i, tx.f - 11 + j): the taps of footprint pixel (p, q) = (pr - 10, qc - 10)
+    // are the model rows p + f - 1 + a, that is the stage rows pr + a
+    const int r0 = ty.f - 1 - kPsfApron, c0 = tx.f - 1 - kPsfApron;
+    double ps = 0.0;
+    for (int e = tid; e < kFootSide * kFootSide; e += kStarThreads) {
+        const int i = e / kFootSide, j = e - i * kFootSide;
+        const int r = r0 + i, c = c0 + j;
+        const bool in = (unsigned)r < (unsigned)NS && (unsigned)c < (unsigned)NS;
+        const double v = P[in ? r * NS + c : 0];
+        stage[i * kFootStride + j] = in ? v : 0.0;
+    }
+    if constexpr (!PROJECT)
+        for (int e = tid; e < NS * NS; e += kStarThreads) ps += P[e];
+    __syncthreads();
+    const FootStamp st{stage};
+    const double cy = (double)(op + NS / 2) + dp, cx = (double)(oq + NS / 2) + dq;
+    const double cval = PROJECT && cptr ? csign * *cptr : 0.0;
+    double sg = 0.0, sn = 0.0;
+    int cnt = 0;
+    // the thread's pixels of the two frames a batch at a time, the loads of a batch in flight together, then its
+    // arithmetic: a workgroup is short, and what it waits for is memory
+#pragma unroll 1
+    for (int m0 = 0; m0 < kFootShare; m0 += kFootBatch) {
+        double fa[kFootBatch], fb[kFootBatch];        // W and V; or the variance and the datum
+#pragma unroll
+        for (int j = 0; j < kFootBatch; ++j) {
+            const int e = tid + (m0 + j) * kStarThreads, pr = e / kPsfSide, qc = e - pr * kPsfSide;
+            const int Y = op - kPsfApron + pr, X = oq - kPsfApron + qc;
+            const bool on = e < kFootPix && Y >= 0 && Y < ny && X >= 0 && X < nx;
+            const size_t src = on ? (size_t)Y * nx + (size_t)X : 0;
+            if constexpr (PROJECT) {
+                fa[j] = W[src];
+                fb[j] = V[src];
+            } else {
+                fa[j] = var ? var[src] : 1.0;
+                fb[j] = image[src];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kFootBatch; ++j) {
+            const int e = tid + (m0 + j) * kStarThreads, pr = e / kPsfSide, qc = e - pr * kPsfSide;
+            const int Y = op - kPsfApron + pr, X = oq - kPsfApron + qc;
+            const bool on = e < kFootPix && Y >= 0 && Y < ny && X >= 0 && X < nx;
+            double w, v = 0.0;
+            bool use;
+            if constexpr (PROJECT) {
+                w = fa[j];
+                v = fb[j];
+                use = on && w > 0.0;              // (W is 0 outside Omega; a masked datum may be NaN: selected out)
+            } else {
+                use = on && fit_pixel(fb[j], fa[j], var != nullptr).used && in_disc(Y, X, cy, cx, r2);
+                w = 1.0 / fa[j];
+            }
+            if (use) {
+                double val, gy, gx;
+                psf_interp<double, false>(st, pr * kFootStride + qc, 0, 0, ty, tx, val, gy, gx);
+                const double wv = w * val;
+                sn += wv * val;
+                if constexpr (PROJECT) sg += wv * (v + cval);
+                ++cnt;
+            }
+        }
+    }
+    if constexpr (PROJECT) {
+        const double tg = block_sum<kStarThreads>(sg, part);
+        if (tid == 0) g[k] = tg;
+        if (diag) {
+            const double tn = block_sum<kStarThreads>(sn, part);
+            if (tid == 0) diag[k] = tn;
+        }
+    } else {
+        const double tn = block_sum<kStarThreads>(sn, part);
+        const double tc = block_sum<kStarThreads>((double)cnt, part);
+        const double tp = block_sum<kStarThreads>(ps, part);
+        if (tid == 0) {
+            const bool acc = tc > 0.0 && tn > 0.0 && tn < __builtin_inf();
+            const double s0 = scale0 ? scale0[k] : 0.0;
+            accept[k] = acc ? 1 : 0;
+            stat[k] = acc ? 0 : 2;
+            ndisc[k] = tc;
+            sump[k] = tp;
+            diag[k] = tn;
+            x[k] = acc && fabs(s0) < __builtin_inf() ? s0 : 0.0;
+        }
+    }
+}
+
+// W of one frame tile from its star list: the centres of up to 256 stars at a time in LDS
+__global__ __launch_bounds__(256) void k_ff_domain(int ny, int nx, const double* __restrict__ image,
+                                                  const double* __restrict__ var, const int32_t* __restrict__ origin,
+                                                  const double* __restrict__ shift, double r2,
+                                                  const int* __restrict__ offset, const int* __restrict__ pairs,
+                                                  double* __restrict__ W) {
+    __shared__ double scy[256], scx[256];
+    const int tid = threadIdx.x, lx = tid & (kTile - 1), ly0 = tid / kTile;
+    const int t = blockIdx.y * gridDim.x + blockIdx.x;
+    const int Y0 = blockIdx.y * kTile, X = blockIdx.x * kTile + lx;
+    const int first = offset[t], n = offset[t + 1] - first;
+    bool in[4] = {false, false, false, false};
+    for (int base = 0; base < n; base += 256) {
+        const int m = min(256, n - base);
+        __syncthreads();
+        if (tid < m) {
+            const int k = pairs[first + base + tid];
+            scy[tid] = (double)(origin[2 * k] + NS / 2) + (shift ? shift[2 * k] : 0.0);
+            scx[tid] = (double)(origin[2 * k + 1] + NS / 2) + (shift ? shift[2 * k + 1] : 0.0);
+        }
+        __syncthreads();
+        for (int i = 0; i < m; ++i) {
+            const double cy = scy[i], cx = scx[i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) in[j] = in[j] || in_disc(Y0 + ly0 + 8 * j, X, cy, cx, r2);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int Y = Y0 + ly0 + 8 * j;
+        if (Y < ny && X < nx) {
+            const size_t o = (size_t)Y * nx + X;
+            const double vv = var ? var[o] : 1.0;
+            const bool use = in[j] && fit_pixel(image[o], vv, var != nullptr).used;
+            W[o] = use ? 1.0 / vv : 0.0;
+        }
+    }
+}
+
+// partial sums over chunk blockIdx.x of the frame: part[0][c] = sum W (V + csign c), [1] sum W, [2] sum W (V + ..)^2,
+// [3] the pixels with W > 0
+__global__ __launch_bounds__(256) void k_ff_reduce(size_t npix, int nchunk, const double* __restrict__ W,
+                                                  const double* __restrict__ V, const double* __restrict__ cptr,
+                                                  double csign, double* __restrict__ partial,
+                                                  const int32_t* __restrict__ done) {
+    __shared__ double part[256 / 64];
+    if (done && *done) return;
+    const int tid = threadIdx.x, c = blockIdx.x;
+    const double cval = cptr ? csign * *cptr : 0.0;
+    double s1 = 0.0, s0 = 0.0, s2 = 0.0, cnt = 0.0;
+#pragma unroll 4
+    for (int j = 0; j < kChunk / 256; ++j) {
+        const size_t o = (size_t)c * kChunk + (size_t)j * 256 + tid;
+        const double w = o < npix ? W[o] : 0.0;
+        if (w > 0.0) {
+            const double v = V[o] + cval, wv = w * v;
+            s1 += wv;
+            s0 += w;
+            s2 += wv * v;
+            cnt += 1.0;
+        }
+    }
+    s1 = block_sum<256>(s1, part);
+    s0 = block_sum<256>(s0, part);
+    s2 = block_sum<256>(s2, part);
+    cnt = block_sum<256>(cnt, part);
+    if (tid == 0) {
+        partial[c] = s1;
+        partial[nchunk + c] = s0;
+        partial[2 * (size_t)nchunk + c] = s2;
+        partial[3 * (size_t)nchunk + c] = cnt;
+    }
+}
+
+// the sum of a[0 .. n - 1] by the step kernel's workgroup: thread t takes t, t + 1024, ... in order, then the tree
+__device__ __forceinline__ double step_sum(const double* __restrict__ a, int n, double* part) {
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += kStepThreads) s += a[i];
+    return block_sum<kStepThreads>(s, part);
+}
+
+enum { STEP_INIT = 0, STEP_ITER = 1, STEP_FINAL = 2 };
+
+// One workgroup over the nu = nstar + 1 unknowns (the constant last; it takes part with `back` only).  x, r, p, q, diag:
+// [nu].  STEP_INIT: the first residual from q (the projection of the data minus the start) and the partials.  STEP_ITER:
+// one conjugate-gradient step from q = N p.  STEP_FINAL: the rows, from q = N 1 and the partials of the residual frame.
+template <int PHASE>
+__global__ __launch_bounds__(kStepThreads) void k_ff_step(int nstar, int back, int nchunk, double tol2,
+                                                         const int32_t* __restrict__ accept,
+                                                         const int32_t* __restrict__ stat,
+                                                         const double* __restrict__ ndisc,
+                                                         const double* __restrict__ sump, double* __restrict__ x,
+                                                         double* __restrict__ r, double* __restrict__ p,
+                                                         double* __restrict__ q, double* __restrict__ diag,
+                                                         const double* __restrict__ partial, double* __restrict__ sd,
+                                                         int32_t* __restrict__ si, double* __restrict__ star_out,
+                                                         double* __restrict__ head_out) {
+    __shared__ double part[kStepThreads / 64];
+    const int tid = threadIdx.x;
+    const int nu = nstar + (back ? 1 : 0);
+    // (an unknown that takes part: an accepted star, or the constant)
+    auto live = [&](int i) { return i >= nstar || accept[i] != 0; };
+    if constexpr (PHASE == STEP_INIT) {
+        const double gb = step_sum(partial, nchunk, part);
+        const double wsum = step_sum(partial + nchunk, nchunk, part);
+        const double nomega = step_sum(partial + 3 * (size_t)nchunk, nchunk, part);
+        double na = 0.0;
+        for (int i = tid; i < nstar; i += kStepThreads) na += accept[i] ? 1.0 : 0.0;
+        const double nacc = block_sum<kStepThreads>(na, part);
+        const bool none = nacc < 1.0 || nomega < nacc + (back ? 1.0 : 0.0) + 1.0;
+        double rz = 0.0;
+        for (int i = tid; i <= nstar; i += kStepThreads) {
+            if (i == nstar) {
+                diag[i] = wsum;
+                x[i] = 0.0;
+            }
+            const bool on = !none && i < nu && live(i);
+            const double ri = on ? (i == nstar ? gb : q[i]) : 0.0;
+            const double zi = on ? ri / diag[i] : 0.0;
+            if (none) x[i] = 0.0;
+            r[i] = ri;
+            p[i] = zi;
+            rz += ri * zi;
+        }
+        const double rho = block_sum<kStepThreads>(rz, part);
+        if (tid == 0) {
+            const bool more = !none && rho > 0.0 && rho < __builtin_inf();
+            sd[S_RHO] = rho;
+            sd[S_RHO0] = rho;
+            sd[S_REL] = more ? 1.0 : 0.0;
+            sd[S_WSUM] = wsum;
+            si[I_DONE] = more ? 0 : 1;
+            si[I_ITER] = 0;
+            si[I_STATUS] = none ? 2 : (rho == 0.0 ? 0 : 1);  // 1 until the stop test passes
+            si[I_NACC] = (int)nacc;
+            si[I_NOMEGA] = (int)nomega;
+        }
+    } else if constexpr (PHASE == STEP_ITER) {
+        if (si[I_DONE]) return;
+        const double rho = sd[S_RHO], rho0 = sd[S_RHO0];
+        if (back) {
+            const double qb = step_sum(partial, nchunk, part);
+            if (tid == 0) q[nstar] = qb;
+            __syncthreads();
+        }
+        double s = 0.0;
+        for (int i = tid; i < nu; i += kStepThreads)
+            if (live(i)) s += p[i] * q[i];
+        const double pq = block_sum<kStepThreads>(s, part);
+        const bool fine = pq > 0.0 && pq < __builtin_inf();          // (not so: N is singular along p, the step ends)
+        const double alpha = fine ? rho / pq : 0.0;
+        double rz = 0.0;
+        for (int i = tid; i < nu; i += kStepThreads)
+            if (live(i)) {
+                x[i] += alpha * p[i];
+                const double ri = r[i] - alpha * q[i];
+                r[i] = ri;
+                rz += ri * (ri / diag[i]);
+            }
+        const double rho1 = block_sum<kStepThreads>(rz, part);
+        const bool stop = rho1 <= tol2 * rho0;
+        const bool end = stop || !fine || !(rho1 < __builtin_inf());
+        const double beta = end ? 0.0 : rho1 / rho;
+        for (int i = tid; i < nu; i += kStepThreads)
+            if (live(i)) p[i] = r[i] / diag[i] + beta * p[i];
+        if (tid == 0) {
+            sd[S_RHO] = rho1;
+            sd[S_REL] = sqrt(rho1 / rho0);
+            si[I_ITER] += 1;
+            if (end) si[I_DONE] = 1;
+            if (stop) si[I_STATUS] = 0;
+        }
+    } else {
+        const int status = si[I_STATUS], nacc = si[I_NACC], nomega = si[I_NOMEGA];
+        const bool none = status == 2;
+        const double chi2 = step_sum(partial + 2 * (size_t)nchunk, nchunk, part);
+        const double dof = (double)nomega - (double)nacc - (back ? 1.0 : 0.0);
+        const double s2 = none ? 0.0 : chi2 / dof;
+        for (int k = tid; k < nstar; k += kStepThreads) {
+            double* o = star_out + (size_t)NROW * k;
+            const bool on = !none && accept[k] != 0;
+            const double F = on ? x[k] : 0.0, nkk = on ? diag[k] : 0.0;
+            const double eF = on ? sqrt(s2 / nkk) : 0.0;
+            o[0] = F;
+            o[1] = eF;
+            o[2] = on ? F * sump[k] : 0.0;
+            o[3] = on ? eF * fabs(sump[k]) : 0.0;
+            o[4] = on ? (q[k] - nkk) / nkk : 0.0;
+            o[5] = on ? ndisc[k] : 0.0;
+            o[6] = nkk;
+            o[7] = on ? 0.0 : (stat[k] == 1 ? 1.0 : 2.0);
+        }
+        if (tid == 0) {
+            const bool b = back && !none;
+            head_out[0] = b ? x[nstar] : 0.0;
+            head_out[1] = b ? sqrt(s2 / sd[S_WSUM]) : 0.0;
+            head_out[2] = none ? 0.0 : chi2;
+            head_out[3] = (double)nomega;
+            head_out[4] = (double)si[I_ITER];
+            head_out[5] = none ? 0.0 : sd[S_REL];
+            head_out[6] = (double)nacc;
+            head_out[7] = (double)status;
+        }
+    }
+}
+
+// p[k] = 1 for every star (the renderer reads the accepted ones): the scales of the overlap's render
+__global__ __launch_bounds__(256) void k_ff_ones(int n, double* __restrict__ p) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) p[i] = 1.0;
+}
+
+size_t align8(size_t n) { return (n + 7) & ~(size_t)7; }
+int frame_chunks(int ny, int nx) { return (int)(((size_t)ny * nx + kChunk - 1) / kChunk); }
+
+}  // namespace
+
+// render's lists; the frames W and M; x, r, p, q, diag [nstar + 1], ndisc, sump [nstar]; the partials [4][chunks]; the
+// scalars; accept, stat [nstar]
+size_t frame_fit_workspace_bytes(int ny, int nx, int nstar) {
+    const size_t npix = (size_t)ny * nx, nu = (size_t)nstar + 1;
+    return align8(render_workspace_bytes(ny, nx, nstar)) +
+           (2 * npix + 5 * nu + 2 * (size_t)nstar + 4 * (size_t)frame_chunks(ny, nx) + S_NDOUBLE) * sizeof(double) +
+           (I_NINT + 2 * (size_t)nstar) * sizeof(int32_t);
+}
+
+void launch_fit_frame(hipStream_t s, int ny, int nx, const double* d_image, const double* d_var, int nstar, int npsf,
+                      const double* d_psf, const int32_t* d_index, const int32_t* d_origin, const double* d_shift,
+                      const double* d_scale0, double radius, bool background, int max_iter, double tol,
+                      double* d_star_out, double* d_head_out, double* d_resid_out, void* d_ws) {
+    const size_t npix = (size_t)ny * nx, nu = (size_t)nstar + 1;
+    const int nchunk = frame_chunks(ny, nx), back = background ? 1 : 0;
+    char* base = (char*)d_ws;
+    void* lists = base;
+    double* W = (double*)(base + align8(render_workspace_bytes(ny, nx, nstar)));
+    double* M = W + npix;
+    double* x = M + npix;
+    double* r = x + nu;
+    double* p = r + nu;
+    double* q = p + nu;
+    double* diag = q + nu;
+    double* ndisc = diag + nu;
+    double* sump = ndisc + nstar;
+    double* partial = sump + nstar;
+    double* sd = partial + 4 * (size_t)nchunk;
+    int32_t* si = (int32_t*)(sd + S_NDOUBLE);
+    int32_t* accept = si + I_NINT;
+    int32_t* stat = accept + nstar;
+    const int32_t* done = si + I_DONE;
+    const double r2 = radius * radius, tol2 = tol * tol;
+    const RenderLists l = render_lists(ny, nx, nstar, lists);
+    auto project = [&](const double* V, const double* c, double* g, double* dg, const int32_t* dn) {
+        hipLaunchKernelGGL(k_ff_star<true>, dim3(nstar), dim3(kStarThreads), 0, s, ny, nx, npsf, nullptr, nullptr, d_psf,
+                           d_index, d_origin, d_shift, nullptr, r2, W, V, c, 1.0, accept, stat, nullptr, nullptr, nullptr,
+                           g, dg, dn);
+    };
+    auto reduce = [&](const double* V, const double* c, double csign, const int32_t* dn) {
+        hipLaunchKernelGGL(k_ff_reduce, dim3(nchunk), dim3(256), 0, s, npix, nchunk, W, V, c, csign, partial, dn);
+    };
+    // the stars judged, the lists of the accepted ones (once per solve), the weights on Omega
+    hipLaunchKernelGGL(k_ff_star<false>, dim3(nstar), dim3(kStarThreads), 0, s, ny, nx, npsf, d_image, d_var, d_psf,
+                       d_index, d_origin, d_shift, d_scale0, r2, nullptr, nullptr, nullptr, 0.0, accept, stat, ndisc,
+                       sump, x, nullptr, diag, nullptr);
+    launch_render_lists(s, ny, nx, nstar, npsf, d_index, d_origin, d_shift, nullptr, accept, nullptr, lists);
+    hipLaunchKernelGGL(k_ff_domain, dim3(l.ntx, l.nty), dim3(256), 0, s, ny, nx, d_image, d_var, d_origin, d_shift, r2,
+                       l.offset, l.pairs, W);
+    // r0 = A^T W (D - A x0), and the diagonal of N
+    launch_render_walk(s, ny, nx, d_image, nstar, d_psf, d_index, d_origin, d_shift, x, true, M, lists, nullptr);
+    project(M, nullptr, q, diag, nullptr);
+    reduce(M, nullptr, 1.0, nullptr);
+    hipLaunchKernelGGL(k_ff_step<STEP_INIT>, dim3(1), dim3(kStepThreads), 0, s, nstar, back, nchunk, tol2, accept, stat,
+                       ndisc, sump, x, r, p, q, diag, partial, sd, si, d_star_out, d_head_out);
+    for (int it = 0; it < max_iter; ++it) {           // q = N p: one tile walk, one projection, one frame reduction
+        launch_render_walk(s, ny, nx, nullptr, nstar, d_psf, d_index, d_origin, d_shift, p, false, M, lists, done);
+        project(M, p + nstar, q, nullptr, done);
+        if (back) reduce(M, p + nstar, 1.0, done);
+        hipLaunchKernelGGL(k_ff_step<STEP_ITER>, dim3(1), dim3(kStepThreads), 0, s, nstar, back, nchunk, tol2, accept,
+                           stat, ndisc, sump, x, r, p, q, diag, partial, sd, si, d_star_out, d_head_out);
+    }
+    // the residual frame by the renderer itself, chi2 from it, the overlap from N 1
+    double* R = d_resid_out ? d_resid_out : M;
+    launch_render_walk(s, ny, nx, d_image, nstar, d_psf, d_index, d_origin, d_shift, x, true, R, lists, nullptr);
+    reduce(R, x + nstar, -1.0, nullptr);
+    hipLaunchKernelGGL(k_ff_ones, dim3((nstar + 255) / 256), dim3(256), 0, s, nstar, p);
+    launch_render_walk(s, ny, nx, nullptr, nstar, d_psf, d_index, d_origin, d_shift, p, false, M, lists, nullptr);
+    project(M, nullptr, q, nullptr, nullptr);
+    hipLaunchKernelGGL(k_ff_step<STEP_FINAL>, dim3(1), dim3(kStepThreads), 0, s, nstar, back, nchunk, tol2, accept, stat,
+                       ndisc, sump, x, r, p, q, diag, partial, sd, si, d_star_out, d_head_out);
+}
+
+}  // namespace mpsfr

@@ -295,6 +295,21 @@ size_t render_workspace_bytes(int ny, int nx, int nstar);
 void launch_render_stars(hipStream_t s, int ny, int nx, const double* d_image_in, int nstar, int npsf,
                          const double* d_psf, const int32_t* d_index, const int32_t* d_origin, const double* d_shift,
                          const double* d_scale, bool subtract, double* d_image_out, double* d_star_out, void* d_ws);
+// The two halves of launch_render_stars, for a caller that walks the same lists many times (frame_fit.hip):
+// launch_render_lists builds the per-tile star lists in d_ws (prepare, scan, fill) -- with d_accept [nstar] only of the
+// stars it marks, which pass render's rule but for the scale (d_scale may then be nullptr) --, launch_render_walk is the
+// tile walk alone; with d_done it does nothing once *d_done is not 0.  render_lists: where the lists lie in d_ws.
+struct RenderLists {
+    int *count, *cursor, *offset, *status, *pairs;      // [nt], [nt], [nt + 1], [nstar], [9 nstar]
+    int ntx, nty;                                       // 32 x 32 frame tiles each way, nt = ntx nty
+};
+RenderLists render_lists(int ny, int nx, int nstar, void* d_ws);
+void launch_render_lists(hipStream_t s, int ny, int nx, int nstar, int npsf, const int32_t* d_index,
+                         const int32_t* d_origin, const double* d_shift, const double* d_scale,
+                         const int32_t* d_accept, double* d_star_out, void* d_ws);
+void launch_render_walk(hipStream_t s, int ny, int nx, const double* d_image_in, int nstar, const double* d_psf,
+                        const int32_t* d_index, const int32_t* d_origin, const double* d_shift, const double* d_scale,
+                        bool subtract, double* d_image_out, void* d_ws, const int32_t* d_done);
 // The star finder (find.hip; mpsfr_find_stars, include/mpsfr.h): the statistic T of every pixel of d_image [ny][nx]
 // (d_var [ny][nx] or nullptr) with the (2 half + 1)^2 core of the model stamp d_psf [40][40], its peaks over (2 sep + 1)^2
 // squares at or above `threshold` in pixel order into d_star_out [max_stars][8] and d_origin_out [max_stars][2] (or
@@ -313,6 +328,16 @@ size_t group_workspace_bytes(int ny, int nx, int nstar, int max_groups);
 void launch_group_stars(hipStream_t s, int ny, int nx, int nstar, const double* d_pos, int stride, double crit,
                         int max_groups, int32_t* d_label_out, int32_t* d_group_out, int32_t* d_origin_out,
                         double* d_shift_out, int32_t* d_count_out, void* d_ws);
+// Crowded-field photometry (frame_fit.hip; mpsfr_fit_frame_psf, include/mpsfr.h): the fluxes of all accepted stars and,
+// with `background`, one constant by preconditioned conjugate gradients on the frame d_image / d_var (or nullptr), at
+// most max_iter steps queued at once, into d_star_out [nstar][8], d_head_out [8] and d_resid_out [ny][nx] (or nullptr).
+// d_ws: frame_fit_workspace_bytes(ny, nx, nstar) bytes -- render_workspace_bytes, two frames of doubles,
+// 7 nstar + 4 ceil(ny nx / 4096) + 9 doubles, 2 nstar + 5 int32; the launch writes every word of it before it reads it.
+size_t frame_fit_workspace_bytes(int ny, int nx, int nstar);
+void launch_fit_frame(hipStream_t s, int ny, int nx, const double* d_image, const double* d_var, int nstar, int npsf,
+                      const double* d_psf, const int32_t* d_index, const int32_t* d_origin, const double* d_shift,
+                      const double* d_scale0, double radius, bool background, int max_iter, double tol,
+                      double* d_star_out, double* d_head_out, double* d_resid_out, void* d_ws);
 // band-integrated stamps (band.hip): d_fin [ntb][nl][40][40] (float if fin_f32, else double) reduced over wavelength
 // into d_out [ntb][nband][40][40] double with the weights d_w [nl][band_stride(nband)] (zero beyond nband)
 constexpr int MAX_BANDS = 16;    // MPSFR_MAX_BANDS

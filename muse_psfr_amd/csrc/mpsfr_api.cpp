@@ -159,6 +159,7 @@ struct mpsfr_ctx {
     DevBuf render;                     // work lists of mpsfr_render_stars (render_workspace_bytes)
     DevBuf find;                       // core, map, masks and counts of mpsfr_find_stars (find_workspace_bytes)
     DevBuf group;                      // cells, union-find and row lists of mpsfr_group_stars (group_workspace_bytes)
+    DevBuf framefit;                   // lists, frames, vectors and scalars of mpsfr_fit_frame_psf (frame_fit_workspace_bytes)
     DevBuf fit, sum, stage, lsum;      // lsum: [lanes][nl][40][40] per-lane partial stamp sums
     // mpsfr_psd_to_psf: a stream and workspaces of its own, so that it never waits for nor touches the lanes
     struct P2P {
@@ -721,7 +722,7 @@ void mpsfr_destroy(mpsfr_ctx* c) {
     }
     DevBuf* all[] = {&c->scoef, &c->stwk, &c->ssup, &c->tw64, &c->tel, &c->rows, &c->tlmax, &c->tl2, &c->tlb, &c->aotab, &c->samp_p,
                      &c->samp_a, &c->G, &c->xtab, &c->etab, &c->gtab, &c->kmuse, &c->fit, &c->sum,
-                     &c->stage, &c->lsum, &c->mfclk, &c->specx, &c->render, &c->find, &c->group};
+                     &c->stage, &c->lsum, &c->mfclk, &c->specx, &c->render, &c->find, &c->group, &c->framefit};
     for (auto b : all) release(*b);
     if (c->p2p.stream) { (void)hipStreamSynchronize(c->p2p.stream); (void)hipStreamDestroy(c->p2p.stream); }
     DevBuf* p2p[] = {&c->p2p.twm, &c->p2p.psd, &c->p2p.cm, &c->p2p.d0t, &c->p2p.pup, &c->p2p.phase, &c->p2p.lbda,
@@ -2676,6 +2677,62 @@ int mpsfr_group_stars(mpsfr_ctx* c, int ny, int nx, int nstar, const double* pos
     return stamp_call(c, on_device, in, out, [&](hipStream_t s, const void* const* d, double* const* d_out) {
         launch_group_stars(s, ny, nx, nstar, (const double*)d[0], stride, crit, max_groups, (int32_t*)d_out[1],
                            (int32_t*)d_out[2], (int32_t*)d_out[3], d_out[0], (int32_t*)d_out[4], c->group.p);
+    });
+}
+
+static_assert(MPSFR_NFRAMEFIT == 8 && MPSFR_FRAME_FIT_MAX_RADIUS + MPSFR_FIT_PSF_MAX_SHIFT + 2.0 <= NS / 2 + 10.0,
+              "K_FRAME_FIT row layout; a disc stays inside its footprint at any legal shift");
+
+int mpsfr_fit_frame_psf(mpsfr_ctx* c, int ny, int nx, const double* image, const double* var, int nstar, int npsf,
+                        const double* psf, const int32_t* psf_index, const int32_t* origin, const double* shift,
+                        const double* scale0, double radius, int flags, int max_iter, double tol, double* star_out,
+                        double* head_out, double* resid_out, int on_device) {
+    if (!c || !image || !psf || !origin || !star_out || !head_out || npsf < 1)
+        return fail(MPSFR_E_INVALID, "fit_frame_psf: bad argument (image, psf, origin, star_out and head_out are required)");
+    int rc;
+    if ((rc = frame_shape("fit_frame_psf", ny, nx))) return rc;
+    if (nstar < 1 || nstar > (1 << 20)) return fail(MPSFR_E_INVALID, "fit_frame_psf: nstar=%d outside 1..2^20", nstar);
+    if (flags & ~MPSFR_FIT_BACKGROUND)
+        return fail(MPSFR_E_INVALID, "fit_frame_psf: unknown flag bits (only the background bit has a meaning here)");
+    if (!psf_index && npsf != nstar)
+        return fail(MPSFR_E_INVALID, "fit_frame_psf: without psf_index, npsf must equal nstar");
+    if (!(radius >= 1.0 && radius <= MPSFR_FRAME_FIT_MAX_RADIUS))
+        return fail(MPSFR_E_INVALID, "fit_frame_psf: radius must be finite, in 1..%g pixels", MPSFR_FRAME_FIT_MAX_RADIUS);
+    if (!(tol > 0.0 && tol < 1.0)) return fail(MPSFR_E_INVALID, "fit_frame_psf: tol must lie in (0, 1)");
+    if (max_iter < 1 || max_iter > MPSFR_FRAME_FIT_MAX_ITER)
+        return fail(MPSFR_E_INVALID, "fit_frame_psf: max_iter=%d outside 1..%d", max_iter, MPSFR_FRAME_FIT_MAX_ITER);
+    if (!on_device) {
+        if (psf_index)
+            for (int k = 0; k < nstar; ++k)
+                if (psf_index[k] < 0 || psf_index[k] >= npsf)
+                    return fail(MPSFR_E_INVALID, "fit_frame_psf: a psf_index outside 0..npsf-1");
+        if (shift)
+            for (size_t k = 0; k < (size_t)2 * nstar; ++k)
+                if (!(std::fabs(shift[k]) <= MPSFR_FIT_PSF_MAX_SHIFT))
+                    return fail(MPSFR_E_INVALID, "fit_frame_psf: a shift that is not finite or beyond 8 pixels");
+        if (scale0)
+            for (int k = 0; k < nstar; ++k)
+                if (!std::isfinite(scale0[k])) return fail(MPSFR_E_INVALID, "fit_frame_psf: a scale0 that is not finite");
+        for (size_t k = 0; k < (size_t)2 * nstar; ++k)
+            if (origin[k] < -(1 << 30) || origin[k] > (1 << 30))
+                return fail(MPSFR_E_INVALID, "fit_frame_psf: an origin beyond 2^30");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = ensure(c, c->framefit, frame_fit_workspace_bytes(ny, nx, nstar)))) return rc;
+    const size_t npix = (size_t)ny * nx;
+    const StampIn in[] = {{image, npix, sizeof(double)},
+                          {var, npix, sizeof(double)},
+                          {psf, npsf * kStampPix, sizeof(double)},
+                          {shift, (size_t)2 * nstar, sizeof(double)},
+                          {scale0, (size_t)nstar, sizeof(double)},
+                          {origin, (size_t)2 * nstar, sizeof(int32_t)},
+                          {psf_index, (size_t)nstar, sizeof(int32_t)}};
+    const StampOut out[] = {{star_out, (size_t)nstar * MPSFR_NFRAMEFIT}, {head_out, MPSFR_NFRAMEFIT}, {resid_out, npix}};
+    return stamp_call(c, on_device, in, out, [&](hipStream_t s, const void* const* d, double* const* d_out) {
+        launch_fit_frame(s, ny, nx, (const double*)d[0], (const double*)d[1], nstar, npsf, (const double*)d[2],
+                         (const int32_t*)d[6], (const int32_t*)d[5], (const double*)d[3], (const double*)d[4], radius,
+                         (flags & MPSFR_FIT_BACKGROUND) != 0, max_iter, tol, d_out[0], d_out[1], d_out[2],
+                         c->framefit.p);
     });
 }
 

@@ -1,7 +1,8 @@
 // Frame-level PSF photometry: k_cut_stamps gathers 40 x 40 stamps out of a frame, and the
 // renderer adds or subtracts scaled, resampled model stamps in a frame as a gather over 32 x 32 frame tiles:
 //   k_render_prepare  one thread per star: validates it, writes star_out, counts the star on the tiles its footprint
-//                     (the kPsfSide x kPsfSide window around its stamp) reaches
+//                     (the kPsfSide x kPsfSide window around its stamp) reaches; with `accept` (the frame fit of
+//                     frame_fit.hip, which has judged the stars already) only the stars it marks are listed
 //   k_render_scan     exclusive scan of the tile counts (one workgroup)
 //   k_render_fill     writes each star's index into the lists of its tiles at an atomic cursor (arbitrary order)
 //   k_render_tiles    one workgroup per tile: sorts its list by star index, then walks it in that order -- the model
@@ -61,14 +62,16 @@ __global__ __launch_bounds__(256) void k_render_prepare(int ny, int nx, int ntx,
                                                         const int32_t* __restrict__ index,
                                                         const int32_t* __restrict__ origin,
                                                         const double* __restrict__ shift,
-                                                        const double* __restrict__ scale, int* __restrict__ count,
+                                                        const double* __restrict__ scale,
+                                                        const int32_t* __restrict__ accept, int* __restrict__ count,
                                                         int* __restrict__ status, double* __restrict__ star_out) {
     const int k = blockIdx.x * 256 + threadIdx.x;
     if (k >= nstar) return;
     const int op = origin[2 * k], oq = origin[2 * k + 1];
     const int ix = index ? index[k] : k;
     const double dp = shift ? shift[2 * k] : 0.0, dq = shift ? shift[2 * k + 1] : 0.0;
-    const bool ok = (unsigned)ix < (unsigned)npsf && psf_inside(dp, dq) && fabs(scale[k]) < __builtin_inf() &&
+    const bool ok = (unsigned)ix < (unsigned)npsf && psf_inside(dp, dq) &&
+                    (accept ? accept[k] != 0 : fabs(scale[k]) < __builtin_inf()) &&
                     op >= -kMaxOrigin && op <= kMaxOrigin && oq >= -kMaxOrigin && oq <= kMaxOrigin;
     int st = 2, npix = 0;
     if (ok) {
@@ -203,9 +206,10 @@ __global__ __launch_bounds__(kTileThreads) void k_render_tiles(int ny, int nx, c
                                                                const double* __restrict__ shift,
                                                                const double* __restrict__ scale, int subtract,
                                                                const int* __restrict__ offset, int* pairs,
-                                                               double* image_out) {
+                                                               const int32_t* __restrict__ done, double* image_out) {
     __shared__ double stage[2 * kStageSide * kStageStride];
     __shared__ int slist[kSortChunk];
+    if (done && *done) return;          // (a queued walk of the frame fit after its stop test has passed)
     const int tid = threadIdx.x, lx = tid & (kTile - 1), ly0 = tid / kTile;
     const int t = blockIdx.y * gridDim.x + blockIdx.x;
     const int Y0 = blockIdx.y * kTile, X0 = blockIdx.x * kTile, X = X0 + lx;
@@ -291,25 +295,49 @@ size_t render_workspace_bytes(int ny, int nx, int nstar) {
     return (3 * nt + 1 + (size_t)nstar * 10) * sizeof(int);
 }
 
+// the work lists in d_ws: count [nt], cursor [nt], offset [nt + 1], status [nstar], pairs [9 nstar]
+RenderLists render_lists(int ny, int nx, int nstar, void* d_ws) {
+    RenderLists l;
+    l.ntx = render_tiles_x(nx);
+    l.nty = render_tiles_x(ny);
+    const int nt = l.ntx * l.nty;
+    l.count = (int*)d_ws;
+    l.cursor = l.count + nt;
+    l.offset = l.cursor + nt;
+    l.status = l.offset + nt + 1;
+    l.pairs = l.status + nstar;
+    return l;
+}
+
+void launch_render_lists(hipStream_t s, int ny, int nx, int nstar, int npsf, const int32_t* d_index,
+                         const int32_t* d_origin, const double* d_shift, const double* d_scale,
+                         const int32_t* d_accept, double* d_star_out, void* d_ws) {
+    static_assert(kPsfSide + kTile - 1 <= 3 * kTile, "a footprint reaches at most 3 x 3 tiles");
+    const RenderLists l = render_lists(ny, nx, nstar, d_ws);
+    const int nt = l.ntx * l.nty;
+    (void)hipMemsetAsync(l.count, 0, (size_t)2 * nt * sizeof(int), s);
+    const int gstar = (nstar + 255) / 256;
+    hipLaunchKernelGGL(k_render_prepare, dim3(gstar), dim3(256), 0, s, ny, nx, l.ntx, nstar, npsf, d_index, d_origin,
+                       d_shift, d_scale, d_accept, l.count, l.status, d_star_out);
+    hipLaunchKernelGGL(k_render_scan, dim3(1), dim3(kScanThreads), 0, s, nt, l.count, l.offset);
+    hipLaunchKernelGGL(k_render_fill, dim3(gstar), dim3(256), 0, s, ny, nx, l.ntx, nstar, d_origin, l.status, l.offset,
+                       l.cursor, l.pairs);
+}
+
+void launch_render_walk(hipStream_t s, int ny, int nx, const double* d_image_in, int nstar, const double* d_psf,
+                        const int32_t* d_index, const int32_t* d_origin, const double* d_shift, const double* d_scale,
+                        bool subtract, double* d_image_out, void* d_ws, const int32_t* d_done) {
+    const RenderLists l = render_lists(ny, nx, nstar, d_ws);
+    hipLaunchKernelGGL(k_render_tiles, dim3(l.ntx, l.nty), dim3(kTileThreads), 0, s, ny, nx, d_image_in, d_psf, d_index,
+                       d_origin, d_shift, d_scale, subtract ? 1 : 0, l.offset, l.pairs, d_done, d_image_out);
+}
+
 void launch_render_stars(hipStream_t s, int ny, int nx, const double* d_image_in, int nstar, int npsf,
                          const double* d_psf, const int32_t* d_index, const int32_t* d_origin, const double* d_shift,
                          const double* d_scale, bool subtract, double* d_image_out, double* d_star_out, void* d_ws) {
-    static_assert(kPsfSide + kTile - 1 <= 3 * kTile, "a footprint reaches at most 3 x 3 tiles");
-    const int ntx = render_tiles_x(nx), nty = render_tiles_x(ny), nt = ntx * nty;
-    int* count = (int*)d_ws;
-    int* cursor = count + nt;
-    int* offset = cursor + nt;
-    int* status = offset + nt + 1;
-    int* pairs = status + nstar;
-    (void)hipMemsetAsync(count, 0, (size_t)2 * nt * sizeof(int), s);
-    const int gstar = (nstar + 255) / 256;
-    hipLaunchKernelGGL(k_render_prepare, dim3(gstar), dim3(256), 0, s, ny, nx, ntx, nstar, npsf, d_index, d_origin,
-                       d_shift, d_scale, count, status, d_star_out);
-    hipLaunchKernelGGL(k_render_scan, dim3(1), dim3(kScanThreads), 0, s, nt, count, offset);
-    hipLaunchKernelGGL(k_render_fill, dim3(gstar), dim3(256), 0, s, ny, nx, ntx, nstar, d_origin, status, offset, cursor,
-                       pairs);
-    hipLaunchKernelGGL(k_render_tiles, dim3(ntx, nty), dim3(kTileThreads), 0, s, ny, nx, d_image_in, d_psf, d_index,
-                       d_origin, d_shift, d_scale, subtract ? 1 : 0, offset, pairs, d_image_out);
+    launch_render_lists(s, ny, nx, nstar, npsf, d_index, d_origin, d_shift, d_scale, nullptr, d_star_out, d_ws);
+    launch_render_walk(s, ny, nx, d_image_in, nstar, d_psf, d_index, d_origin, d_shift, d_scale, subtract, d_image_out,
+                       d_ws, nullptr);
 }
 
 }  // namespace mpsfr

@@ -778,8 +778,8 @@ def group_stars(positions, crit, shape=None, *, pixscale=0.2, precision='mixed',
 _FIT_COLS_FOUND = _FIT_COLS_GROUP + ('nsrc', 'label', 'crowded')
 
 
-def fit_found_stars(image, psf, found, *, var=None, crit, fit_back=True, mode='free', pixscale=0.2, precision='mixed',
-                    device=0):
+def fit_found_stars(image, psf, found, *, var=None, crit, fit_back=True, mode='free', crowded='skip', radius=8.0,
+                    pixscale=0.2, precision='mixed', device=0):
     """PSF-fitting photometry of the stars found in a frame, singles and blends alike, on the GPU: the stars `found` (a
     find_stars table or an (n, 2) array of (row, column) in pixels) are grouped by friends of friends at the critical
     separation `crit` (pixels, at most 16); one stamp per group is cut out of `image` (`var`: its variance frame or
@@ -792,9 +792,17 @@ def fit_found_stars(image, psf, found, *, var=None, crit, fit_back=True, mode='f
     columns of fit_star_groups_with_psf -- `group` indexes `origin`, `source` numbers the star within its group -- plus
     nsrc (stars in its group), label (the smallest star index of its group) and crowded: True for the stars of a group
     of more than four or of one wider than the fit's domain (a member farther than 8 pixels from the stamp centre).
-    Those are not fitted: their rows carry status 2 and NaN; fit them after grouping again with a smaller crit."""
+    With crowded='skip' those are not fitted: their rows carry status 2 and NaN.  With crowded='frame' the fitted
+    singles and blends are subtracted from the frame and the crowded stars are solved together on that residual, as
+    fit_crowded_stars does, at their found positions within `radius` pixels and with fit_back as given: their rows get
+    scale, flux and the conditional errors (err_scale, err_flux), the shift from their own stamp origin with error 0,
+    the back, err_back, chi2 and npix of the frame solve and max_corr NaN; `origin` gains one row per such star and
+    their `group` column points at it, so that subtract_stars(image, psf, origin, fit) removes every star."""
     if not isinstance(fit_back, (bool, np.bool_)):
         raise ValueError('fit_back must be True or False')
+    if crowded not in ('skip', 'frame'):
+        raise ValueError("crowded must be 'skip' or 'frame'")
+    _lib.frame_fit_parameters(radius, bool(fit_back), 1, 0.5)
     _pixscale(pixscale)
     _lib.group_fit_flags(bool(fit_back), mode)
     pos = _star_positions(found)
@@ -863,7 +871,106 @@ def fit_found_stars(image, psf, found, *, var=None, crit, fit_back=True, mode='f
     cols['label'] = label.astype(np.int64)
     cols['crowded'] = groups[star_row, 1] != 0
     assert tuple(cols) == _FIT_COLS_FOUND
-    return _make_table(cols), origin.astype(np.int32)
+    origin = origin.astype(np.int32)
+    rows = np.flatnonzero(cols['crowded'])
+    if crowded == 'frame' and rows.size:
+        resid, _ = subtract_stars(im, ps, origin, cols, psf_index=np.zeros(origin.shape[0], dtype=np.int32),
+                                  pixscale=pixscale, precision=precision, device=device)
+        own = (np.rint(pos[rows]) - ps.shape[-1] // 2).astype(np.int32)
+        shift_px = pos[rows] - (own + ps.shape[-1] // 2)
+        start = None
+        try:
+            start = np.nan_to_num(np.asarray(found['scale'], dtype=float)[rows], nan=0.0, posinf=0.0, neginf=0.0)
+        except (KeyError, IndexError, TypeError, ValueError):
+            pass
+        out, head = ctx.fit_frame_psf(resid, ps[None], own, var=va, shift=shift_px,
+                                      psf_index=np.zeros(rows.size, dtype=np.int32), scale0=start, radius=radius,
+                                      background=bool(fit_back))
+        ok = out[:, 7] == 0
+        fill = rows[ok]
+        cols['scale'][fill] = out[ok, 0]
+        cols['flux'][fill] = out[ok, 2]
+        cols['err_scale'][fill] = out[ok, 1]
+        cols['err_flux'][fill] = out[ok, 3]
+        cols['shift'][fill] = shift_px[ok] * pixscale
+        cols['err_shift'][fill] = 0.0
+        cols['back'][fill] = head[0]
+        cols['err_back'][fill] = head[1]
+        cols['chi2'][fill] = head[2]
+        cols['npix'][fill] = int(head[3])
+        cols['status'][fill] = int(head[7])
+        cols['group'][rows] = origin.shape[0] + np.arange(rows.size)
+        origin = np.concatenate([origin, own])
+    return _make_table(cols), origin
+
+
+_FIT_COLS_CROWDED = ('scale', 'shift', 'flux', 'err_scale', 'err_flux', 'overlap', 'npix', 'status')
+
+
+def fit_crowded_stars(image, psf, positions, *, var=None, psf_index=None, radius=8.0, fit_back=True, start=None,
+                      max_iter=100, tol=1e-10, return_residual=False, pixscale=0.2, precision='mixed', device=0):
+    """Crowded-field PSF photometry, on the GPU: the fluxes of ALL stars of a frame at known positions in one linear
+    least-squares solve -- no limit on how many stars touch each other; the step for the groups fit_found_stars
+    marks `crowded`.  `image` (ny, nx), `var` its variance frame or None (NaN pixels and var <= 0 are masked);
+    `positions` an (n, 2) array of (row, column) in pixels or a find_stars table; `psf` (..., 40, 40) model stamps,
+    e.g. reconstructed PSFs, star k taking psf[psf_index[k]] (one stamp: every star takes it).  The fit runs over the
+    valid pixels within `radius` (1 .. 20) pixels of a star, with one constant background under fit_back, by
+    preconditioned conjugate gradients to the relative residual `tol` or max_iter steps, from `start`: None (zeros),
+    'found' (the `scale` column of a find_stars table) or n values.
+
+    Returns (fit, origin) in the form subtract_stars takes (pass it the same psf_index): origin[k] =
+    rint(positions[k]) - 20 as cut_star_stamps places stamps, and `fit` with one row per star: scale (F), shift (2,
+    arcsec, echoed: the position from the stamp centre), flux, err_scale and err_flux (CONDITIONAL errors: the other
+    stars held fixed), overlap (the sum of the star's off-diagonal terms of the normal matrix over its diagonal term;
+    far from 0 the conditional error is optimistic), npix (valid pixels within `radius` of the star) and status (0
+    fitted, 1 off the frame, 2 left out: no valid pixel, or no model there).  fit.meta: back, err_back, chi2, npix
+    (pixels of the solve), iterations, residual (the last relative preconditioned residual), status (0 converged, 1
+    max_iter reached, 2 nothing fitted).  With return_residual also the frame minus the fitted stars."""
+    _pixscale(pixscale)
+    if not isinstance(fit_back, (bool, np.bool_)):
+        raise ValueError('fit_back must be True or False')
+    pos = _star_positions(positions)
+    n = pos.shape[0]
+    try:
+        ps = np.asarray(getattr(psf, 'data', psf), dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('psf must be a numeric array') from None
+    if ps.ndim < 2 or ps.shape[-1] != ps.shape[-2] or ps.size == 0:
+        raise ValueError('psf must have the shape (..., 40, 40)')
+    dimpsf = ps.shape[-1]
+    if not np.all(np.isfinite(pos)) or np.any(np.abs(pos) > _lib.MAX_ORIGIN - dimpsf):
+        raise ValueError('positions must be finite and within 2^30 pixels')
+    if psf_index is None and ps.size == dimpsf * dimpsf:
+        psf_index = np.zeros(n, dtype=np.int32)
+    if isinstance(start, str):
+        if start != 'found':
+            raise ValueError("start must be None, 'found' or one value per star")
+        try:
+            start = np.asarray(positions['scale'], dtype=float)
+        except (KeyError, IndexError, TypeError, ValueError):
+            raise ValueError("start='found' needs a find_stars table") from None
+    origin = (np.rint(pos) - dimpsf // 2).astype(np.int32)
+    shift_px = pos - (origin + dimpsf // 2)
+    ctx = get_context(128, pixscale, dimpsf, precision, device)
+    res = ctx.fit_frame_psf(image, ps, origin, var=var, shift=shift_px, psf_index=psf_index, scale0=start,
+                            radius=radius, background=bool(fit_back), max_iter=max_iter, tol=tol,
+                            return_residual=return_residual)
+    rows, head = res[0], res[1]
+    cols = OrderedDict()
+    cols['scale'] = rows[:, 0].copy()
+    cols['shift'] = shift_px * pixscale
+    cols['flux'] = rows[:, 2].copy()
+    cols['err_scale'] = rows[:, 1].copy()
+    cols['err_flux'] = rows[:, 3].copy()
+    cols['overlap'] = rows[:, 4].copy()
+    cols['npix'] = rows[:, 5].astype(np.int64)
+    cols['status'] = rows[:, 7].astype(np.int64)
+    assert tuple(cols) == _FIT_COLS_CROWDED
+    meta = OrderedDict([('back', float(head[0])), ('err_back', float(head[1])), ('chi2', float(head[2])),
+                        ('npix', int(head[3])), ('iterations', int(head[4])), ('residual', float(head[5])),
+                        ('status', int(head[7]))])
+    fit = _make_table(cols, meta)
+    return (fit, origin) + ((res[2],) if return_residual else ())
 
 
 def cut_star_stamps(image, positions, var=None, dimpsf=40, *, pixscale=0.2, precision='mixed', device=0):
