@@ -71,24 +71,63 @@ struct Tw64 {
 template <typename R>
 __device__ __forceinline__ cx<R> conjf(cx<R> a) { return {a.x, -a.y}; }
 
+template <int CTRL>
+__device__ __forceinline__ float cf_dpp(float own) {     // the value of the lane CTRL names; the lane's own where there is none
+    const int w = __builtin_bit_cast(int, own);
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(w, w, CTRL, 0xf, 0xf, false));
+}
+// element (CF - k) % CF of a slot's spectrum beside element k = t + 8 e, for a thread that holds v[q] = Z[t + 8 q]
+// (fft_forward_regs_lastreg): lane 8 - t of the slot has it as v[7 - e], lane 0 its own as v[(8 - e) % 8].  Two DPP
+// moves per word (mirror of the 8 lanes, then one lane up: both stay inside the slot for t > 0), no LDS.  Every lane
+// of the slot must call this.
+__device__ __forceinline__ cx<float> cf_mirror(const cx<float>* v, int e, int t) {
+    const cx<float> own = v[(8 - e) % 8];
+    const cx<float> up = {cf_dpp<0x111>(cf_dpp<0x141>(v[7 - e].x)),      // row_half_mirror, row_shr:1
+                          cf_dpp<0x111>(cf_dpp<0x141>(v[7 - e].y))};
+    return t == 0 ? own : up;
+}
+
 // rows ra = 2 slot, rb = ra + 1 of a real image, x[e] = (row ra, row rb) at column t + 8 e (zero
-// beyond the image) -> half spectra in F
+// beyond the image) -> half spectra in F.
+// Float: the spectrum stays in registers (fft_pass, TOREG) and the mirrored element comes by cf_mirror: 12 LDS
+// instructions in this phase instead of 28.  Double: through the line buffer, as for the split of the packed
+// column (stamps.hip).
 template <typename R>
 __device__ __forceinline__ void cf_rows_forward(const cx<R>* x, cx<R> (*F)[CFP],
                                                 cx<R>* buf, const Tw64<R>& tw, int slot, int t) {
     const int ra = 2 * slot, rb = ra + 1;
-    const cx<R>* res = fft_forward_regs<R, CF, true>(x, buf, buf, tw.w, t);
+    if constexpr (sizeof(R) == 4) {
+        cx<R> v[8];
+        fft_forward_regs_lastreg<R, CF, true>(x, buf, buf, tw.w, t, v);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int k = t + 8 * e;
-        const cx<R> zk = res[lds_out<CF, 8>(k)], zm = res[lds_out<CF, 8>((CF - k) % CF)];
-        if (k == 0) {
-            const cx<R> zn = res[lds_out<CF, 8>(CFH)];
-            F[ra][0] = {zk.x, zn.x};      // (DC, Nyquist) of row ra, both real
-            F[rb][0] = {zk.y, zn.y};
-        } else {
-            F[ra][k] = {(R)0.5 * (zk.x + zm.x), (R)0.5 * (zk.y - zm.y)};
-            F[rb][k] = {(R)0.5 * (zk.y + zm.y), -(R)0.5 * (zk.x - zm.x)};
+        for (int e = 0; e < 4; ++e) {
+            const int k = t + 8 * e;
+            const cx<R> zk = v[e], zm = cf_mirror(v, e, t);
+            cx<R> fa = {(R)0.5 * (zk.x + zm.x), (R)0.5 * (zk.y - zm.y)};
+            cx<R> fb = {(R)0.5 * (zk.y + zm.y), -(R)0.5 * (zk.x - zm.x)};
+            // k = 0 (lane 0, e = 0): (DC, Nyquist) of the row, both real; Z[32] is lane 0's own v[4].  A select, not a
+            // branch: with the transform's last butterfly split over two basic blocks hipcc leaves two of its
+            // multiply-adds unfused, and the last bit of the stamps moves.
+            const bool dc = e == 0 && k == 0;
+            fa = {dc ? zk.x : fa.x, dc ? v[4].x : fa.y};
+            fb = {dc ? zk.y : fb.x, dc ? v[4].y : fb.y};
+            F[ra][k] = fa;
+            F[rb][k] = fb;
+        }
+    } else {
+        const cx<R>* res = fft_forward_regs<R, CF, true>(x, buf, buf, tw.w, t);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int k = t + 8 * e;
+            const cx<R> zk = res[lds_out<CF, 8>(k)], zm = res[lds_out<CF, 8>((CF - k) % CF)];
+            if (k == 0) {
+                const cx<R> zn = res[lds_out<CF, 8>(CFH)];
+                F[ra][0] = {zk.x, zn.x};      // (DC, Nyquist) of row ra, both real
+                F[rb][0] = {zk.y, zn.y};
+            } else {
+                F[ra][k] = {(R)0.5 * (zk.x + zm.x), (R)0.5 * (zk.y - zm.y)};
+                F[rb][k] = {(R)0.5 * (zk.y + zm.y), -(R)0.5 * (zk.x - zm.x)};
+            }
         }
     }
 }

@@ -210,7 +210,7 @@ k_conv_fft(int nl, int tdiv, const R* __restrict__ pre, const cx<R>* __restrict_
             // was a third transform issued by that wave.  Only the split of slot 0's packed DC / Nyquist
             // column is left under the branch (cf_split0's expressions).  It needs the mirrored element
             // (CF - kx) % CF of kx = t + 8 e: lane 8 - t of the slot holds it as v[7 - e], lane 0 its own
-            // as v[(8 - e) % 8].  Float: two DPP moves (mirror of the 8 lanes, then one lane up), no LDS --
+            // as v[(8 - e) % 8].  Float: two DPP moves (cf_mirror: mirror of the 8 lanes, then one lane up), no LDS --
             // through the line buffer the kernel no longer fits 128 registers (20-40 bytes of scratch).
             // Double: the slot's spectrum goes through its line buffer and cf_split0 reads it as before;
             // the registers are there, and with the DPP form hipcc fuses the other product of b0.y's
@@ -235,10 +235,7 @@ k_conv_fft(int nl, int tdiv, const R* __restrict__ pre, const cx<R>* __restrict_
                     if constexpr (sizeof(R) == 8) {
                         cf_split0(buf, t + 8 * e, a0, a32);
                     } else {
-                        const cx<R> own = v[(8 - e) % 8];
-                        const cx<R> up = {dpp_pull<0x111>(dpp_pull<0x141>(v[7 - e].x)),      // row_half_mirror, row_shr:1
-                                          dpp_pull<0x111>(dpp_pull<0x141>(v[7 - e].y))};
-                        const cx<R> p = v[e], pm = t == 0 ? own : up;
+                        const cx<R> p = v[e], pm = cf_mirror(v, e, t);
                         a0 = {(R)0.5 * (p.x + pm.x), (R)0.5 * (p.y - pm.y)};
                         a32 = {(R)0.5 * (p.y + pm.y), -(R)0.5 * (p.x - pm.x)};
                     }
