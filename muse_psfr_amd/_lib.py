@@ -1370,6 +1370,19 @@ def render_flags(subtract):
     return RENDER_SUBTRACT if subtract else 0
 
 
+def star_scales(name, scale, n):
+    """`scale` (the argument `name`) as n finite float64 values, one per star (ValueError)."""
+    try:
+        sc = np.asarray(scale, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('%s must be a numeric array' % name) from None
+    if sc.size != n or sc.ndim > 1:
+        raise ValueError('%s must hold one value per star (%d)' % (name, n))
+    if not np.all(np.isfinite(sc)):
+        raise ValueError('%s must be finite' % name)
+    return np.ascontiguousarray(sc).reshape(n)
+
+
 def render_arguments(psf, origin, scale, shift, psf_index, image, shape, subtract, dimpsf=40):
     """(image or None, ny, nx, psf, psf_index, origin, shift, scale, flags) of a render call, validated as
     mpsfr_render_stars validates host arguments (ValueError): origin as star_origins; psf, psf_index and shift as
@@ -1379,15 +1392,7 @@ def render_arguments(psf, origin, scale, shift, psf_index, image, shape, subtrac
     og = star_origins(origin)
     n = og.shape[0]
     ps, ix, sh, _ = psf_fit_arguments(n, psf, psf_index, shift, True, False, dimpsf)
-    try:
-        sc = np.asarray(scale, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError('scale must be a numeric array') from None
-    if sc.size != n or sc.ndim > 1:
-        raise ValueError('scale must hold one value per star (%d)' % n)
-    if not np.all(np.isfinite(sc)):
-        raise ValueError('scale must be finite')
-    sc = np.ascontiguousarray(sc).reshape(n)
+    sc = star_scales('scale', scale, n)
     if image is None:
         if subtract:
             raise ValueError('subtract needs the image')
@@ -1479,17 +1484,7 @@ def frame_fit_arguments(image, var, psf, psf_index, origin, shift, scale0, radiu
     n = frame_fit_stars(og.shape[0])
     ps, ix, sh, _ = psf_fit_arguments(n, psf, psf_index, shift, True, False, dimpsf)
     radius, flags, max_iter, tol = frame_fit_parameters(radius, background, max_iter, tol)
-    s0 = None
-    if scale0 is not None:
-        try:
-            s0 = np.asarray(scale0, dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError('scale0 must be a numeric array') from None
-        if s0.size != n or s0.ndim > 1:
-            raise ValueError('scale0 must hold one value per star (%d)' % n)
-        if not np.all(np.isfinite(s0)):
-            raise ValueError('scale0 must be finite')
-        s0 = np.ascontiguousarray(s0).reshape(n)
+    s0 = None if scale0 is None else star_scales('scale0', scale0, n)
     return im, va, ps, ix, og, sh, s0, radius, flags, max_iter, tol
 
 

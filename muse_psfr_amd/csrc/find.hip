@@ -7,7 +7,7 @@
 //   k_find_peaks   one workgroup per tile: T with a `sep` apron in LDS, the peak rule, one 32-bit mask per (frame row,
 //                  tile column) segment by a half-wave ballot
 //   k_find_count   the peaks of every chunk of kChunkSegs segments (segments in (row, tile column) order: pixel order)
-//   k_find_scan    exclusive scan of the chunk counts (scan_common.h, one workgroup)
+//   k_scan_counts  exclusive scan of the chunk counts (render.hip, one workgroup)
 //   k_find_list    one thread per four segments: its place in pixel order from the chunk's offset and a scan inside the
 //                  chunk, then the pixel index of every peak below max_stars into a list
 //   k_find_rows    one wave per listed peak: the window into LDS, the sums again, in the same order by the same code,
@@ -15,13 +15,13 @@
 //   k_find_fill    the filler rows from the count up to max_stars
 // Every pixel's sums run over the window in row-major tap order with the same operations, whatever its place in a tile:
 // the rows depend on the frame alone.  fp64 in both precision modes; no atomics at all.
-#include "kernels.h"
-#include "scan_common.h"
+#include "frame_common.h"
 
 namespace mpsfr {
 namespace {
 
-constexpr int kTile = 32;                                     // frame tile side, that of render.hip
+// (the bits of a mask word, k_find_peaks' half-wave ballot: the renderer's kFrameTile by value, not by construction)
+constexpr int kTile = 32;                                     // frame tile side
 constexpr int kTileThreads = 256;
 constexpr int kTilePix = kTile * kTile / kTileThreads;        // pixels per thread: adjacent rows of one column
 constexpr int kMaxHalf = 8, kMaxSep = 16;                     // MPSFR_FIND_MAX_HALF, MPSFR_FIND_MAX_SEP
@@ -31,7 +31,6 @@ constexpr int kMapPlane = (kTile + 2 * kMaxHalf) * kMapQ + 8;  // and the pitch 
 constexpr int kPeakStride = kTile + 2 * kMaxSep;
 constexpr int kChunkThreads = 256, kThreadSegs = 4, kChunkSegs = kChunkThreads * kThreadSegs;
 constexpr int kRowThreads = 64, kRowBlocks = 8192;                // k_find_rows: one wave per peak, blocks striding over them
-constexpr int kFillerOrigin = -(1 << 30);
 static_assert(kTilePix == 4 && kTileThreads / kTile * kTilePix == kTile, "tile layout");
 
 // The pixel rule of the observed fits on frame pixel (Y, X): weight w (0 on a masked pixel or off the frame), datum d
@@ -204,31 +203,13 @@ __device__ __forceinline__ int chunk_masks(int nseg, const uint32_t* __restrict_
     return n;
 }
 
-// part[tid] becomes the sum of part[0 .. tid] over the kChunkThreads threads of the workgroup
-__device__ __forceinline__ void chunk_scan(int* part) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    for (int d = 1; d < kChunkThreads; d <<= 1) {
-        const int add = tid >= d ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += add;
-        __syncthreads();
-    }
-}
-
 __global__ __launch_bounds__(kChunkThreads) void k_find_count(int nseg, const uint32_t* __restrict__ mask,
                                                               int* __restrict__ count) {
     __shared__ int part[kChunkThreads];
     uint32_t m[kThreadSegs];
     part[threadIdx.x] = chunk_masks(nseg, mask, m);
-    chunk_scan(part);
+    block_scan<kChunkThreads>(part);
     if (threadIdx.x == kChunkThreads - 1) count[blockIdx.x] = part[threadIdx.x];
-}
-
-__global__ __launch_bounds__(kScanThreads) void k_find_scan(int nt, const int* __restrict__ count,
-                                                            int* __restrict__ offset) {
-    __shared__ int part[kScanThreads];
-    scan_shares(nt, count, offset, part);
 }
 
 // the three-point parabola through (tm, t0, tp): the offset of its top, or 0 and `bit` where it has none
@@ -251,7 +232,7 @@ __global__ __launch_bounds__(kChunkThreads) void k_find_list(int ny, int ntx, in
     uint32_t m[kThreadSegs];
     const int mine = chunk_masks(nseg, mask, m);
     part[tid] = mine;
-    chunk_scan(part);
+    block_scan<kChunkThreads>(part);
     if (blockIdx.x == 0 && tid == 0) count_out[0] = offset[gridDim.x];
     int k = offset[blockIdx.x] + part[tid] - mine;
     const int seg0 = (blockIdx.x * kChunkThreads + tid) * kThreadSegs;
@@ -338,44 +319,49 @@ __global__ __launch_bounds__(256) void k_find_fill(const int* __restrict__ total
     }
 }
 
-int tiles(int n) { return (n + kTile - 1) / kTile; }
-int chunks(int ny, int nx) { return (ny * tiles(nx) + kChunkSegs - 1) / kChunkSegs; }
-size_t round8(size_t bytes) { return (bytes + 7) & ~(size_t)7; }
+// The workspace: kk [2][kMaxTaps], T [ny][nx] unless the caller takes the map, mask [ny][ntx], then from the next
+// multiple of 8 bytes count [nchunk], offset [nchunk + 1], list [max_stars]
+struct FindWork {
+    int ntx, nty, nseg, nchunk;
+    double *kk, *tmap;
+    uint32_t* mask;
+    int *count, *offset, *list;
+    FindWork(WorkspaceCarver& ws, int ny, int nx, int max_stars, bool with_map)
+        : ntx((nx + kTile - 1) / kTile), nty((ny + kTile - 1) / kTile), nseg(ny * ntx),
+          nchunk((nseg + kChunkSegs - 1) / kChunkSegs), kk(ws.take<double>(2 * kMaxTaps)),
+          tmap(with_map ? nullptr : ws.take<double>((size_t)ny * nx)), mask(ws.take<uint32_t>(nseg)),
+          count(ws.take<int>(nchunk, 8)), offset(ws.take<int>((size_t)nchunk + 1)), list(ws.take<int>(max_stars)) {}
+};
 
 }  // namespace
 
 size_t find_workspace_bytes(int ny, int nx, int max_stars, bool with_map) {
-    // kk [2][kMaxTaps] doubles, T [ny][nx] doubles unless the caller takes the map, mask [ny][ntx], count [nchunk],
-    // offset [nchunk + 1], list [max_stars]
-    const size_t nseg = (size_t)ny * tiles(nx), nchunk = chunks(ny, nx);
-    return 2 * kMaxTaps * sizeof(double) + (with_map ? 0 : (size_t)ny * nx * sizeof(double)) +
-           round8(nseg * sizeof(uint32_t)) + (2 * nchunk + 2 + (size_t)max_stars) * sizeof(int);
+    return workspace_bytes<FindWork>(ny, nx, max_stars, with_map);
 }
 
 void launch_find_stars(hipStream_t s, int ny, int nx, const double* d_image, const double* d_var, const double* d_psf,
                        int half, int sep, double threshold, int max_stars, double* d_star_out, int32_t* d_origin_out,
                        int32_t* d_count_out, double* d_map_out, void* d_ws) {
     static_assert(kMaxHalf <= NS / 2, "the core lies inside the model stamp");
-    const int ntx = tiles(nx), nty = tiles(ny), nseg = ny * ntx, nchunk = chunks(ny, nx);
-    double* kk = (double*)d_ws;
-    double* tmap = d_map_out ? d_map_out : kk + 2 * kMaxTaps;
-    uint32_t* mask = (uint32_t*)(kk + 2 * kMaxTaps + (d_map_out ? 0 : (size_t)ny * nx));
-    int* count = (int*)((char*)mask + round8((size_t)nseg * sizeof(uint32_t)));
-    int* offset = count + nchunk;
-    int* list = offset + nchunk + 1;
+    WorkspaceCarver ws(d_ws);
+    const FindWork w(ws, ny, nx, max_stars, d_map_out != nullptr);
+    double* tmap = d_map_out ? d_map_out : w.tmap;
+    const int* total = w.offset + w.nchunk;
     // (every word of the workspace that is read is written before by this call: nothing to clear; of `list` the rows
     // kernel reads the places below the count only, which k_find_list has written)
-    hipLaunchKernelGGL(k_find_core, dim3(1), dim3(kTileThreads), 0, s, d_psf, half, kk);
-    hipLaunchKernelGGL(k_find_map, dim3(ntx, nty), dim3(kTileThreads), 0, s, ny, nx, d_image, d_var, kk, half, tmap);
-    hipLaunchKernelGGL(k_find_peaks, dim3(ntx, nty), dim3(kTileThreads), 0, s, ny, nx, ntx, tmap, sep, threshold, mask);
-    hipLaunchKernelGGL(k_find_count, dim3(nchunk), dim3(kChunkThreads), 0, s, nseg, mask, count);
-    hipLaunchKernelGGL(k_find_scan, dim3(1), dim3(kScanThreads), 0, s, nchunk, count, offset);
-    hipLaunchKernelGGL(k_find_list, dim3(nchunk), dim3(kChunkThreads), 0, s, ny, ntx, nx, mask, offset, max_stars, list,
-                       d_count_out);
+    hipLaunchKernelGGL(k_find_core, dim3(1), dim3(kTileThreads), 0, s, d_psf, half, w.kk);
+    hipLaunchKernelGGL(k_find_map, dim3(w.ntx, w.nty), dim3(kTileThreads), 0, s, ny, nx, d_image, d_var, w.kk, half,
+                       tmap);
+    hipLaunchKernelGGL(k_find_peaks, dim3(w.ntx, w.nty), dim3(kTileThreads), 0, s, ny, nx, w.ntx, tmap, sep, threshold,
+                       w.mask);
+    hipLaunchKernelGGL(k_find_count, dim3(w.nchunk), dim3(kChunkThreads), 0, s, w.nseg, w.mask, w.count);
+    launch_scan_counts(s, w.nchunk, w.count, w.offset);
+    hipLaunchKernelGGL(k_find_list, dim3(w.nchunk), dim3(kChunkThreads), 0, s, ny, w.ntx, nx, w.mask, w.offset, max_stars,
+                       w.list, d_count_out);
     hipLaunchKernelGGL(k_find_rows, dim3(max_stars < kRowBlocks ? max_stars : kRowBlocks), dim3(kRowThreads), 0, s, ny, nx,
-                       d_image, d_var, kk, half, tmap, list, offset + nchunk, max_stars, d_star_out, d_origin_out);
-    hipLaunchKernelGGL(k_find_fill, dim3((max_stars + 255) / 256), dim3(256), 0, s, offset + nchunk, max_stars,
-                       d_star_out, d_origin_out);
+                       d_image, d_var, w.kk, half, tmap, w.list, total, max_stars, d_star_out, d_origin_out);
+    hipLaunchKernelGGL(k_find_fill, dim3((max_stars + 255) / 256), dim3(256), 0, s, total, max_stars, d_star_out,
+                       d_origin_out);
 }
 
 }  // namespace mpsfr

@@ -2,8 +2,8 @@
 // a frame, and one constant, as one weighted linear least-squares problem, solved by Jacobi-preconditioned conjugate
 // gradients on the normal equations without ever forming them.  A x is the renderer's tile walk (render.hip) over lists
 // built once per solve; what is new here:
-//   k_ff_star<false>  one workgroup per star: judges it (render's rule, the footprint, the valid pixels of its own disc,
-//                     sum w P~^2 over them) and takes sum P of its model
+//   k_ff_star<false>  one workgroup per star: judges it (FrameStar's rule and footprint, which are the renderer's; the
+//                     valid pixels of its own disc, sum w P~^2 over them) and takes sum P of its model
 //   k_ff_domain       one workgroup per frame tile: W = w [pixel in Omega], Omega the valid pixels in the disc of an
 //                     accepted star, from the tile's star list
 //   k_ff_star<true>   the projection, one workgroup per accepted star: g_k = sum W P~_k (V + c) over its footprint and,
@@ -14,7 +14,9 @@
 //                     first residual; the rows of the result
 // Every sum has a fixed order (no floating-point atomics), all arithmetic is fp64, and nothing waits for the host: the
 // scalars live in the work buffer, and once the done word is set the queued kernels of the later iterations return.
-#include "fit_psf_common.h"
+#include <type_traits>
+
+#include "frame_common.h"
 
 namespace mpsfr {
 namespace {
@@ -28,22 +30,12 @@ constexpr int kFootSide = kPsfSide + 3;                                     // m
 constexpr int kFootStride = kFootSide + 1;
 constexpr int kChunk = 4096;                                                // frame pixels per partial of k_ff_reduce
 constexpr int kStepThreads = 1024;
-constexpr int kMaxOrigin = 1 << 30;
-constexpr int kTile = 32;                                                   // the renderer's frame tile
+constexpr int kTile = kFrameTile;                                            // k_ff_domain walks the renderer's lists
 constexpr int NROW = 8;                                                     // MPSFR_NFRAMEFIT
 
 // the scalars of a solve: doubles, then ints
 enum { S_RHO = 0, S_RHO0, S_REL, S_WSUM, S_NDOUBLE };
 enum { I_DONE = 0, I_ITER, I_STATUS, I_NACC, I_NOMEGA, I_NINT };
-
-// the footprint's part of a model stamp in LDS, zero outside the model: tap (a, b) of the pixel at offset o
-struct FootStamp {
-    const double* base;
-    template <typename RE>
-    __device__ __forceinline__ RE at(int o, int, int, int a, int b) const {
-        return (RE)base[o + a * kFootStride + b];
-    }
-};
 
 // the sum of v over the workgroup's T threads in a fixed tree (the wave's ladder, then the waves in order); every
 // thread gets it.  `part`: T / 64 doubles of LDS, free again on return.
@@ -68,67 +60,66 @@ __device__ __forceinline__ bool in_disc(int Y, int X, double cy, double cx, doub
     return a + b <= r2;
 }
 
-// PROJECT = false: the star is judged; accept, stat, ndisc, sump, diag (the sum over its own disc) and x (its start)
-// are written.  PROJECT = true: g[k] = sum W P~ (V + csign c) and, with diag, diag[k] = sum W P~^2 for an accepted star.
+// What k_ff_star<false> reads beside the stars and writes: the verdict on every star, the sum over its own disc (diag)
+// and its start (x)
+struct StarJudging {
+    const double *image, *var, *scale0;
+    int32_t *accept, *stat;
+    double *ndisc, *sump, *diag, *x;
+};
+// What k_ff_star<true> reads and writes: g[k] = sum W P~ (V + c) (c: nullptr for 0) and, with diag, diag[k] = sum W P~^2
+// for an accepted star; nothing once *done is set
+struct StarProjection {
+    const double *W, *V, *c;
+    const int32_t *accept, *done;
+    double *g, *diag;
+};
+
+// PROJECT = false: the star is judged.  PROJECT = true: the projection on an accepted star.
 template <bool PROJECT>
-__global__ __launch_bounds__(kStarThreads) void k_ff_star(int ny, int nx, int npsf, const double* __restrict__ image,
-                                                         const double* __restrict__ var,
-                                                         const double* __restrict__ psf,
-                                                         const int32_t* __restrict__ index,
-                                                         const int32_t* __restrict__ origin,
-                                                         const double* __restrict__ shift,
-                                                         const double* __restrict__ scale0, double r2,
-                                                         const double* __restrict__ W, const double* __restrict__ V,
-                                                         const double* __restrict__ cptr, double csign,
-                                                         int32_t* __restrict__ accept, int32_t* __restrict__ stat,
-                                                         double* __restrict__ ndisc, double* __restrict__ sump,
-                                                         double* __restrict__ x, double* __restrict__ g,
-                                                         double* __restrict__ diag, const int32_t* __restrict__ done) {
+__global__ __launch_bounds__(kStarThreads) void k_ff_star(
+    int ny, int nx, StarList stars, double r2, std::conditional_t<PROJECT, StarProjection, StarJudging> io) {
     __shared__ double stage[kFootSide * kFootStride];
     __shared__ double part[kStarThreads / 64];
     const int k = blockIdx.x, tid = threadIdx.x;
     if constexpr (PROJECT) {
-        if ((done && *done) || !accept[k]) return;
+        if ((io.done && *io.done) || !io.accept[k]) return;
     }
-    const int op = origin[2 * k], oq = origin[2 * k + 1];
-    const int ix = index ? index[k] : k;
-    const double dp = shift ? shift[2 * k] : 0.0, dq = shift ? shift[2 * k + 1] : 0.0;
+    const FrameStar star(stars, k);
+    const int op = star.op, oq = star.oq;
     if constexpr (!PROJECT) {
-        const bool ok = (unsigned)ix < (unsigned)npsf && psf_inside(dp, dq) && op >= -kMaxOrigin && op <= kMaxOrigin &&
-                        oq >= -kMaxOrigin && oq <= kMaxOrigin;
-        const bool hit = ok && op - kPsfApron < ny && op + NS + kPsfApron > 0 && oq - kPsfApron < nx &&
-                         oq + NS + kPsfApron > 0;
+        int y0, y1, x0, x1;
+        const bool ok = star.valid(stars.npsf);
+        const bool hit = ok && star.footprint(ny, nx, y0, y1, x0, x1);
         if (!hit) {                                   // (the same for all threads)
             if (tid == 0) {
-                accept[k] = 0;
-                stat[k] = ok ? 1 : 2;
-                ndisc[k] = 0.0;
-                sump[k] = 0.0;
-                diag[k] = 0.0;
-                x[k] = 0.0;
+                io.accept[k] = 0;
+                io.stat[k] = ok ? 1 : 2;
+                io.ndisc[k] = 0.0;
+                io.sump[k] = 0.0;
+                io.diag[k] = 0.0;
+                io.x[k] = 0.0;
             }
             return;
         }
     }
-    const double* P = psf + (size_t)ix * (NS * NS);
-    const KeysTaps<double> ty(dp), tx(dq);
+    const double* P = star.model(stars);
+    const KeysTaps<double> ty(star.dp), tx(star.dq);
     // stage[i][j] = model pixel (ty.f - 11 + i, tx.f - 11 + j): the taps of footprint pixel (p, q) = (pr - 10, qc - 10)
     // are the model rows p + f - 1 + a, that is the stage rows pr + a
     const int r0 = ty.f - 1 - kPsfApron, c0 = tx.f - 1 - kPsfApron;
     double ps = 0.0;
     for (int e = tid; e < kFootSide * kFootSide; e += kStarThreads) {
         const int i = e / kFootSide, j = e - i * kFootSide;
-        const int r = r0 + i, c = c0 + j;
-        const bool in = (unsigned)r < (unsigned)NS && (unsigned)c < (unsigned)NS;
-        const double v = P[in ? r * NS + c : 0];
-        stage[i * kFootStride + j] = in ? v : 0.0;
+        stage[i * kFootStride + j] = model_pixel(P, r0 + i, c0 + j);
     }
     if constexpr (!PROJECT)
         for (int e = tid; e < NS * NS; e += kStarThreads) ps += P[e];
     __syncthreads();
-    const FootStamp st{stage};
-    const double cy = (double)(op + NS / 2) + dp, cx = (double)(oq + NS / 2) + dq;
-    const double cval = PROJECT && cptr ? csign * *cptr : 0.0;
+    const StagedStamp<kFootStride> st{stage};
+    const double cy = star.cy(), cx = star.cx();
+    double cval = 0.0;
+    if constexpr (PROJECT) cval = io.c ? *io.c : 0.0;
     double sg = 0.0, sn = 0.0;
     int cnt = 0;
     // the thread's pixels of the two frames a batch at a time, the loads of a batch in flight together, then its
@@ -143,11 +134,11 @@ __global__ __launch_bounds__(kStarThreads) void k_ff_star(int ny, int nx, int np
             const bool on = e < kFootPix && Y >= 0 && Y < ny && X >= 0 && X < nx;
             const size_t src = on ? (size_t)Y * nx + (size_t)X : 0;
             if constexpr (PROJECT) {
-                fa[j] = W[src];
-                fb[j] = V[src];
+                fa[j] = io.W[src];
+                fb[j] = io.V[src];
             } else {
-                fa[j] = var ? var[src] : 1.0;
-                fb[j] = image[src];
+                fa[j] = io.var ? io.var[src] : 1.0;
+                fb[j] = io.image[src];
             }
         }
 #pragma unroll
@@ -162,7 +153,7 @@ __global__ __launch_bounds__(kStarThreads) void k_ff_star(int ny, int nx, int np
                 v = fb[j];
                 use = on && w > 0.0;              // (W is 0 outside Omega; a masked datum may be NaN: selected out)
             } else {
-                use = on && fit_pixel(fb[j], fa[j], var != nullptr).used && in_disc(Y, X, cy, cx, r2);
+                use = on && fit_pixel(fb[j], fa[j], io.var != nullptr).used && in_disc(Y, X, cy, cx, r2);
                 w = 1.0 / fa[j];
             }
             if (use) {
@@ -177,10 +168,10 @@ __global__ __launch_bounds__(kStarThreads) void k_ff_star(int ny, int nx, int np
     }
     if constexpr (PROJECT) {
         const double tg = block_sum<kStarThreads>(sg, part);
-        if (tid == 0) g[k] = tg;
-        if (diag) {
+        if (tid == 0) io.g[k] = tg;
+        if (io.diag) {
             const double tn = block_sum<kStarThreads>(sn, part);
-            if (tid == 0) diag[k] = tn;
+            if (tid == 0) io.diag[k] = tn;
         }
     } else {
         const double tn = block_sum<kStarThreads>(sn, part);
@@ -188,21 +179,20 @@ __global__ __launch_bounds__(kStarThreads) void k_ff_star(int ny, int nx, int np
         const double tp = block_sum<kStarThreads>(ps, part);
         if (tid == 0) {
             const bool acc = tc > 0.0 && tn > 0.0 && tn < __builtin_inf();
-            const double s0 = scale0 ? scale0[k] : 0.0;
-            accept[k] = acc ? 1 : 0;
-            stat[k] = acc ? 0 : 2;
-            ndisc[k] = tc;
-            sump[k] = tp;
-            diag[k] = tn;
-            x[k] = acc && fabs(s0) < __builtin_inf() ? s0 : 0.0;
+            const double s0 = io.scale0 ? io.scale0[k] : 0.0;
+            io.accept[k] = acc ? 1 : 0;
+            io.stat[k] = acc ? 0 : 2;
+            io.ndisc[k] = tc;
+            io.sump[k] = tp;
+            io.diag[k] = tn;
+            io.x[k] = acc && fabs(s0) < __builtin_inf() ? s0 : 0.0;
         }
     }
 }
 
 // W of one frame tile from its star list: the centres of up to 256 stars at a time in LDS
 __global__ __launch_bounds__(256) void k_ff_domain(int ny, int nx, const double* __restrict__ image,
-                                                  const double* __restrict__ var, const int32_t* __restrict__ origin,
-                                                  const double* __restrict__ shift, double r2,
+                                                  const double* __restrict__ var, StarList stars, double r2,
                                                   const int* __restrict__ offset, const int* __restrict__ pairs,
                                                   double* __restrict__ W) {
     __shared__ double scy[256], scx[256];
@@ -215,9 +205,9 @@ __global__ __launch_bounds__(256) void k_ff_domain(int ny, int nx, const double*
         const int m = min(256, n - base);
         __syncthreads();
         if (tid < m) {
-            const int k = pairs[first + base + tid];
-            scy[tid] = (double)(origin[2 * k] + NS / 2) + (shift ? shift[2 * k] : 0.0);
-            scx[tid] = (double)(origin[2 * k + 1] + NS / 2) + (shift ? shift[2 * k + 1] : 0.0);
+            const FrameStar star(stars, pairs[first + base + tid]);
+            scy[tid] = star.cy();
+            scx[tid] = star.cx();
         }
         __syncthreads();
         for (int i = 0; i < m; ++i) {
@@ -411,82 +401,82 @@ __global__ __launch_bounds__(256) void k_ff_ones(int n, double* __restrict__ p) 
     if (i < n) p[i] = 1.0;
 }
 
-size_t align8(size_t n) { return (n + 7) & ~(size_t)7; }
-int frame_chunks(int ny, int nx) { return (int)(((size_t)ny * nx + kChunk - 1) / kChunk); }
+// The workspace of a solve: the renderer's lists (at its start: launch_render_lists and launch_render_walk take d_ws);
+// the frames W and M; x, r, p, q, diag [nstar + 1], ndisc, sump [nstar]; the partials [4][chunks]; the scalars; accept,
+// stat [nstar]
+struct FrameFitWork {
+    RenderLists lists;
+    size_t npix, nu;
+    int nchunk;
+    double *W, *M, *x, *r, *p, *q, *diag, *ndisc, *sump, *partial, *sd;
+    int32_t *si, *accept, *stat;
+    FrameFitWork(WorkspaceCarver& ws, int ny, int nx, int nstar)
+        : lists(ws, ny, nx, nstar), npix((size_t)ny * nx), nu((size_t)nstar + 1), nchunk((int)((npix + kChunk - 1) / kChunk)),
+          W(ws.take<double>(npix)), M(ws.take<double>(npix)), x(ws.take<double>(nu)), r(ws.take<double>(nu)),
+          p(ws.take<double>(nu)), q(ws.take<double>(nu)), diag(ws.take<double>(nu)), ndisc(ws.take<double>(nstar)),
+          sump(ws.take<double>(nstar)), partial(ws.take<double>(4 * (size_t)nchunk)), sd(ws.take<double>(S_NDOUBLE)),
+          si(ws.take<int32_t>(I_NINT)), accept(ws.take<int32_t>(nstar)), stat(ws.take<int32_t>(nstar)) {}
+};
+
+template <int PHASE>
+void launch_step(hipStream_t s, const FrameFitWork& w, int nstar, int back, double tol2, double* d_star_out,
+                 double* d_head_out) {
+    hipLaunchKernelGGL(k_ff_step<PHASE>, dim3(1), dim3(kStepThreads), 0, s, nstar, back, w.nchunk, tol2, w.accept, w.stat,
+                       w.ndisc, w.sump, w.x, w.r, w.p, w.q, w.diag, w.partial, w.sd, w.si, d_star_out, d_head_out);
+}
 
 }  // namespace
 
-// render's lists; the frames W and M; x, r, p, q, diag [nstar + 1], ndisc, sump [nstar]; the partials [4][chunks]; the
-// scalars; accept, stat [nstar]
-size_t frame_fit_workspace_bytes(int ny, int nx, int nstar) {
-    const size_t npix = (size_t)ny * nx, nu = (size_t)nstar + 1;
-    return align8(render_workspace_bytes(ny, nx, nstar)) +
-           (2 * npix + 5 * nu + 2 * (size_t)nstar + 4 * (size_t)frame_chunks(ny, nx) + S_NDOUBLE) * sizeof(double) +
-           (I_NINT + 2 * (size_t)nstar) * sizeof(int32_t);
-}
+size_t frame_fit_workspace_bytes(int ny, int nx, int nstar) { return workspace_bytes<FrameFitWork>(ny, nx, nstar); }
 
-void launch_fit_frame(hipStream_t s, int ny, int nx, const double* d_image, const double* d_var, int nstar, int npsf,
-                      const double* d_psf, const int32_t* d_index, const int32_t* d_origin, const double* d_shift,
+void launch_fit_frame(hipStream_t s, int ny, int nx, const double* d_image, const double* d_var, StarList stars,
                       const double* d_scale0, double radius, bool background, int max_iter, double tol,
                       double* d_star_out, double* d_head_out, double* d_resid_out, void* d_ws) {
-    const size_t npix = (size_t)ny * nx, nu = (size_t)nstar + 1;
-    const int nchunk = frame_chunks(ny, nx), back = background ? 1 : 0;
-    char* base = (char*)d_ws;
-    void* lists = base;
-    double* W = (double*)(base + align8(render_workspace_bytes(ny, nx, nstar)));
-    double* M = W + npix;
-    double* x = M + npix;
-    double* r = x + nu;
-    double* p = r + nu;
-    double* q = p + nu;
-    double* diag = q + nu;
-    double* ndisc = diag + nu;
-    double* sump = ndisc + nstar;
-    double* partial = sump + nstar;
-    double* sd = partial + 4 * (size_t)nchunk;
-    int32_t* si = (int32_t*)(sd + S_NDOUBLE);
-    int32_t* accept = si + I_NINT;
-    int32_t* stat = accept + nstar;
-    const int32_t* done = si + I_DONE;
+    WorkspaceCarver ws(d_ws);
+    const FrameFitWork w(ws, ny, nx, stars.nstar);
+    const int nstar = stars.nstar, back = background ? 1 : 0;
+    const int32_t* done = w.si + I_DONE;
     const double r2 = radius * radius, tol2 = tol * tol;
-    const RenderLists l = render_lists(ny, nx, nstar, lists);
+    // out = in (nullptr: zeros) +- sum scale_k P~_k over the accepted stars: the renderer's tile walk
+    auto walk = [&](const double* in, const double* scale, bool subtract, double* out, const int32_t* dn) {
+        launch_render_walk(s, ny, nx, in, stars, scale, subtract, out, d_ws, dn);
+    };
+    // g = A^T W (V + c) and, with dg, the diagonal of N
     auto project = [&](const double* V, const double* c, double* g, double* dg, const int32_t* dn) {
-        hipLaunchKernelGGL(k_ff_star<true>, dim3(nstar), dim3(kStarThreads), 0, s, ny, nx, npsf, nullptr, nullptr, d_psf,
-                           d_index, d_origin, d_shift, nullptr, r2, W, V, c, 1.0, accept, stat, nullptr, nullptr, nullptr,
-                           g, dg, dn);
+        hipLaunchKernelGGL(k_ff_star<true>, dim3(nstar), dim3(kStarThreads), 0, s, ny, nx, stars, r2,
+                           StarProjection{w.W, V, c, w.accept, dn, g, dg});
     };
+    // the partials of sum W (V + csign c), sum W, sum W (V + csign c)^2 and |Omega|
     auto reduce = [&](const double* V, const double* c, double csign, const int32_t* dn) {
-        hipLaunchKernelGGL(k_ff_reduce, dim3(nchunk), dim3(256), 0, s, npix, nchunk, W, V, c, csign, partial, dn);
+        hipLaunchKernelGGL(k_ff_reduce, dim3(w.nchunk), dim3(256), 0, s, w.npix, w.nchunk, w.W, V, c, csign, w.partial,
+                           dn);
     };
+    const double* constant = w.p + nstar;             // the constant's component of the direction p
     // the stars judged, the lists of the accepted ones (once per solve), the weights on Omega
-    hipLaunchKernelGGL(k_ff_star<false>, dim3(nstar), dim3(kStarThreads), 0, s, ny, nx, npsf, d_image, d_var, d_psf,
-                       d_index, d_origin, d_shift, d_scale0, r2, nullptr, nullptr, nullptr, 0.0, accept, stat, ndisc,
-                       sump, x, nullptr, diag, nullptr);
-    launch_render_lists(s, ny, nx, nstar, npsf, d_index, d_origin, d_shift, nullptr, accept, nullptr, lists);
-    hipLaunchKernelGGL(k_ff_domain, dim3(l.ntx, l.nty), dim3(256), 0, s, ny, nx, d_image, d_var, d_origin, d_shift, r2,
-                       l.offset, l.pairs, W);
+    hipLaunchKernelGGL(k_ff_star<false>, dim3(nstar), dim3(kStarThreads), 0, s, ny, nx, stars, r2,
+                       StarJudging{d_image, d_var, d_scale0, w.accept, w.stat, w.ndisc, w.sump, w.diag, w.x});
+    launch_render_lists(s, ny, nx, stars, nullptr, w.accept, nullptr, d_ws);
+    hipLaunchKernelGGL(k_ff_domain, dim3(w.lists.ntx, w.lists.nty), dim3(256), 0, s, ny, nx, d_image, d_var, stars, r2,
+                       w.lists.offset, w.lists.pairs, w.W);
     // r0 = A^T W (D - A x0), and the diagonal of N
-    launch_render_walk(s, ny, nx, d_image, nstar, d_psf, d_index, d_origin, d_shift, x, true, M, lists, nullptr);
-    project(M, nullptr, q, diag, nullptr);
-    reduce(M, nullptr, 1.0, nullptr);
-    hipLaunchKernelGGL(k_ff_step<STEP_INIT>, dim3(1), dim3(kStepThreads), 0, s, nstar, back, nchunk, tol2, accept, stat,
-                       ndisc, sump, x, r, p, q, diag, partial, sd, si, d_star_out, d_head_out);
+    walk(d_image, w.x, true, w.M, nullptr);
+    project(w.M, nullptr, w.q, w.diag, nullptr);
+    reduce(w.M, nullptr, 1.0, nullptr);
+    launch_step<STEP_INIT>(s, w, nstar, back, tol2, d_star_out, d_head_out);
     for (int it = 0; it < max_iter; ++it) {           // q = N p: one tile walk, one projection, one frame reduction
-        launch_render_walk(s, ny, nx, nullptr, nstar, d_psf, d_index, d_origin, d_shift, p, false, M, lists, done);
-        project(M, p + nstar, q, nullptr, done);
-        if (back) reduce(M, p + nstar, 1.0, done);
-        hipLaunchKernelGGL(k_ff_step<STEP_ITER>, dim3(1), dim3(kStepThreads), 0, s, nstar, back, nchunk, tol2, accept,
-                           stat, ndisc, sump, x, r, p, q, diag, partial, sd, si, d_star_out, d_head_out);
+        walk(nullptr, w.p, false, w.M, done);
+        project(w.M, constant, w.q, nullptr, done);
+        if (back) reduce(w.M, constant, 1.0, done);
+        launch_step<STEP_ITER>(s, w, nstar, back, tol2, d_star_out, d_head_out);
     }
     // the residual frame by the renderer itself, chi2 from it, the overlap from N 1
-    double* R = d_resid_out ? d_resid_out : M;
-    launch_render_walk(s, ny, nx, d_image, nstar, d_psf, d_index, d_origin, d_shift, x, true, R, lists, nullptr);
-    reduce(R, x + nstar, -1.0, nullptr);
-    hipLaunchKernelGGL(k_ff_ones, dim3((nstar + 255) / 256), dim3(256), 0, s, nstar, p);
-    launch_render_walk(s, ny, nx, nullptr, nstar, d_psf, d_index, d_origin, d_shift, p, false, M, lists, nullptr);
-    project(M, nullptr, q, nullptr, nullptr);
-    hipLaunchKernelGGL(k_ff_step<STEP_FINAL>, dim3(1), dim3(kStepThreads), 0, s, nstar, back, nchunk, tol2, accept, stat,
-                       ndisc, sump, x, r, p, q, diag, partial, sd, si, d_star_out, d_head_out);
+    double* R = d_resid_out ? d_resid_out : w.M;
+    walk(d_image, w.x, true, R, nullptr);
+    reduce(R, w.x + nstar, -1.0, nullptr);
+    hipLaunchKernelGGL(k_ff_ones, dim3((nstar + 255) / 256), dim3(256), 0, s, nstar, w.p);
+    walk(nullptr, w.p, false, w.M, nullptr);
+    project(w.M, nullptr, w.q, nullptr, nullptr);
+    launch_step<STEP_FINAL>(s, w, nstar, back, tol2, d_star_out, d_head_out);
 }
 
 }  // namespace mpsfr

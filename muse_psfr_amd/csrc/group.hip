@@ -2,22 +2,21 @@
 // the tables mpsfr_cut_stamps, mpsfr_fit_stamps_psf and mpsfr_fit_groups_psf take.
 //   k_group_init     one thread per star: its kind (star, filler, out of range), a compact copy of its position, the
 //                    union-find parent, the member slots and the size, and the count of its cell
-//   k_group_scan     exclusive scan of the cell counts (scan_common.h, one workgroup)
+//   k_scan_counts    exclusive scan of the cell counts (render.hip, one workgroup)
 //   k_group_scatter  the stars of every cell at an atomic cursor (arbitrary order inside a cell)
 //   k_group_link     one thread per star: the stars j < i of its 3 x 3 cells that the link rule joins to it are united
 //                    with it in a lock-free union-find that hooks the larger root under the smaller
 //   k_group_gather   one thread per star: its root (the label), the size of the root's group by an integer add and the
 //                    group's four smallest members by a cascade of integer minima
 //   k_group_count    the roots of every class in every chunk of kChunk stars
-//   k_group_scan     again, over the (class, chunk) counts: class first, star index second -- the row order
+//   k_scan_counts    again, over the (class, chunk) counts: class first, star index second -- the row order
 //   k_group_rows     one thread per star: a root's row from its class, chunk and rank; the group and origin rows
 //   k_group_tail     one thread per output row: filler rows, the shifts at the per-class pitch, the six counts
 // The order of the stars inside a cell and the interleaving of the atomics decide nothing: a root is the smallest index
 // of its component however the hooks arrive, sizes are integer sums and the member slots hold the smallest indices
 // whatever the order of the minima.  Integer atomics only; every workspace word that is read is written before by the
 // same call.
-#include "kernels.h"
-#include "scan_common.h"
+#include "frame_common.h"
 
 namespace mpsfr {
 namespace {
@@ -30,12 +29,11 @@ constexpr int kThreads = 256, kChunk = kThreads;              // stars of one wo
 constexpr int kClasses = 5;                                   // 1, 2, 3, 4 members, oversize
 constexpr int kMaxGroup = 4;                                  // MPSFR_MAX_GROUP
 constexpr int kEmpty = 0x7fffffff;                            // a member slot nobody has claimed
-constexpr int kFillerOrigin = -(1 << 30);
 constexpr int kWide = 2;                                      // MPSFR_GROUP_WIDE
 constexpr int kOversize = 1;                                  // MPSFR_GROUP_OVERSIZE
 constexpr double kMaxShift = 8.0;                             // MPSFR_FIT_PSF_MAX_SHIFT
 
-__device__ __forceinline__ int cells(int n) { return (n + kCell) / kCell + 1; }
+__host__ __device__ __forceinline__ int cells(int n) { return (n + kCell) / kCell + 1; }
 
 // the cell of a position inside [-1, ny] x [-1, nx]
 __device__ __forceinline__ int cell_of(double v) { return ((int)floor(v) + kCell) / kCell; }
@@ -62,12 +60,6 @@ __global__ __launch_bounds__(kThreads) void k_group_init(int ny, int nx, int nst
 #pragma unroll
     for (int s = 0; s < kMaxGroup - 1; ++s) slots[(size_t)i * (kMaxGroup - 1) + s] = kEmpty;
     if (k == 0) atomicAdd(&cellcount[cell_of(y) * cells(nx) + cell_of(x)], 1);
-}
-
-__global__ __launch_bounds__(kScanThreads) void k_group_scan(int nt, const int* __restrict__ count,
-                                                             int* __restrict__ offset) {
-    __shared__ int part[kScanThreads];
-    scan_shares(nt, count, offset, part);
 }
 
 __global__ __launch_bounds__(kThreads) void k_group_scatter(int nx, int nstar, const double2* __restrict__ yx,
@@ -333,54 +325,50 @@ __global__ __launch_bounds__(kThreads) void k_group_tail(int nchunk, const int* 
     for (int j = 0; j < 8; ++j) shift_out[(size_t)g * 8 + j] = v[j];
 }
 
-int host_cells(int n) { return (n + kCell) / kCell + 1; }
-int chunks(int nstar) { return (nstar + kChunk - 1) / kChunk; }
-size_t round8(size_t bytes) { return (bytes + 7) & ~(size_t)7; }
+// The workspace: yx [nstar] double2; then ints: cellcount [nc], cursor [nc], celloff [nc + 1], cellstars, kind, parent,
+// size [nstar] each, slots [3 nstar], count [5 nchunk], offset [5 nchunk + 1], rowroot [min(nstar, max_groups)]
+struct GroupWork {
+    int nc, nchunk;
+    double2* yx;
+    int *cellcount, *cursor, *celloff, *cellstars, *kind, *parent, *size, *slots, *count, *offset, *rowroot;
+    GroupWork(WorkspaceCarver& ws, int ny, int nx, int nstar, int max_groups)
+        : nc(cells(ny) * cells(nx)), nchunk((nstar + kChunk - 1) / kChunk), yx(ws.take<double2>(nstar)),
+          cellcount(ws.take<int>(nc)), cursor(ws.take<int>(nc)), celloff(ws.take<int>((size_t)nc + 1)),
+          cellstars(ws.take<int>(nstar)), kind(ws.take<int>(nstar)), parent(ws.take<int>(nstar)),
+          size(ws.take<int>(nstar)), slots(ws.take<int>((size_t)nstar * (kMaxGroup - 1))),
+          count(ws.take<int>((size_t)kClasses * nchunk)), offset(ws.take<int>((size_t)kClasses * nchunk + 1)),
+          rowroot(ws.take<int>(nstar < max_groups ? nstar : max_groups)) {}
+};
 
 }  // namespace
 
 size_t group_workspace_bytes(int ny, int nx, int nstar, int max_groups) {
-    // yx [nstar] double2; then ints: cellcount [nc], cursor [nc], celloff [nc + 1], cellstars, kind, parent, size
-    // [nstar] each, slots [3 nstar], count [5 nchunk], offset [5 nchunk + 1], rowroot [min(nstar, max_groups)]
-    const size_t nc = (size_t)host_cells(ny) * host_cells(nx), nchunk = chunks(nstar);
-    const size_t rows = (size_t)(nstar < max_groups ? nstar : max_groups);
-    return (size_t)nstar * sizeof(double2) +
-           round8((3 * nc + 1 + (size_t)nstar * (4 + kMaxGroup - 1) + 2 * kClasses * nchunk + 1 + rows) * sizeof(int));
+    return workspace_bytes<GroupWork>(ny, nx, nstar, max_groups);
 }
 
 void launch_group_stars(hipStream_t s, int ny, int nx, int nstar, const double* d_pos, int stride, double crit,
                         int max_groups, int32_t* d_label_out, int32_t* d_group_out, int32_t* d_origin_out,
                         double* d_shift_out, int32_t* d_count_out, void* d_ws) {
-    const int nc = host_cells(ny) * host_cells(nx), nchunk = chunks(nstar);
-    double2* yx = (double2*)d_ws;
-    int* cellcount = (int*)(yx + nstar);
-    int* cursor = cellcount + nc;
-    int* celloff = cursor + nc;
-    int* cellstars = celloff + nc + 1;
-    int* kind = cellstars + nstar;
-    int* parent = kind + nstar;
-    int* size = parent + nstar;
-    int* slots = size + nstar;
-    int* count = slots + (size_t)nstar * (kMaxGroup - 1);
-    int* offset = count + kClasses * nchunk;
-    int* rowroot = offset + kClasses * nchunk + 1;
+    WorkspaceCarver ws(d_ws);
+    const GroupWork w(ws, ny, nx, nstar, max_groups);
+    const int nchunk = w.nchunk;
     const double c2 = crit * crit;
-    (void)hipMemsetAsync(cellcount, 0, (size_t)2 * nc * sizeof(int), s);
-    hipLaunchKernelGGL(k_group_init, dim3(nchunk), dim3(kThreads), 0, s, ny, nx, nstar, d_pos, stride, yx, kind, parent,
-                       size, slots, cellcount);
-    hipLaunchKernelGGL(k_group_scan, dim3(1), dim3(kScanThreads), 0, s, nc, cellcount, celloff);
-    hipLaunchKernelGGL(k_group_scatter, dim3(nchunk), dim3(kThreads), 0, s, nx, nstar, yx, kind, celloff, cursor,
-                       cellstars);
-    hipLaunchKernelGGL(k_group_link, dim3(nchunk), dim3(kThreads), 0, s, ny, nx, nstar, yx, kind, c2, celloff,
-                       cellstars, parent);
-    hipLaunchKernelGGL(k_group_gather, dim3(nchunk), dim3(kThreads), 0, s, nstar, kind, parent, size, slots,
+    (void)hipMemsetAsync(w.cellcount, 0, (size_t)2 * w.nc * sizeof(int), s);         // cellcount and cursor
+    hipLaunchKernelGGL(k_group_init, dim3(nchunk), dim3(kThreads), 0, s, ny, nx, nstar, d_pos, stride, w.yx, w.kind,
+                       w.parent, w.size, w.slots, w.cellcount);
+    launch_scan_counts(s, w.nc, w.cellcount, w.celloff);
+    hipLaunchKernelGGL(k_group_scatter, dim3(nchunk), dim3(kThreads), 0, s, nx, nstar, w.yx, w.kind, w.celloff, w.cursor,
+                       w.cellstars);
+    hipLaunchKernelGGL(k_group_link, dim3(nchunk), dim3(kThreads), 0, s, ny, nx, nstar, w.yx, w.kind, c2, w.celloff,
+                       w.cellstars, w.parent);
+    hipLaunchKernelGGL(k_group_gather, dim3(nchunk), dim3(kThreads), 0, s, nstar, w.kind, w.parent, w.size, w.slots,
                        d_label_out);
-    hipLaunchKernelGGL(k_group_count, dim3(nchunk), dim3(kThreads), 0, s, nstar, d_label_out, size, count);
-    hipLaunchKernelGGL(k_group_scan, dim3(1), dim3(kScanThreads), 0, s, kClasses * nchunk, count, offset);
-    hipLaunchKernelGGL(k_group_rows, dim3(nchunk), dim3(kThreads), 0, s, nstar, d_label_out, size, slots, yx, offset,
-                       max_groups, rowroot, d_group_out, d_origin_out);
-    hipLaunchKernelGGL(k_group_tail, dim3((max_groups - 1) / kThreads + 1), dim3(kThreads), 0, s, nchunk, offset,
-                       size, slots, yx, rowroot, max_groups, d_group_out, d_origin_out, d_shift_out, d_count_out);
+    hipLaunchKernelGGL(k_group_count, dim3(nchunk), dim3(kThreads), 0, s, nstar, d_label_out, w.size, w.count);
+    launch_scan_counts(s, kClasses * nchunk, w.count, w.offset);
+    hipLaunchKernelGGL(k_group_rows, dim3(nchunk), dim3(kThreads), 0, s, nstar, d_label_out, w.size, w.slots, w.yx,
+                       w.offset, max_groups, w.rowroot, d_group_out, d_origin_out);
+    hipLaunchKernelGGL(k_group_tail, dim3((max_groups - 1) / kThreads + 1), dim3(kThreads), 0, s, nchunk, w.offset,
+                       w.size, w.slots, w.yx, w.rowroot, max_groups, d_group_out, d_origin_out, d_shift_out, d_count_out);
 }
 
 }  // namespace mpsfr

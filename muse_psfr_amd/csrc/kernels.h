@@ -1,7 +1,8 @@
 // Launchers for the HIP kernels of the PSF-reconstruction hot path (implemented in stage_a.hip,
 // per_lambda.hip and stamps.hip; the fits of caller-provided stamps in fit_ell.hip, fit_obs.hip, fit_psf.hip,
 // fit_group*.hip and fit_spec.hip: the last three fit a resampled model stamp -- flux scale, sub-pixel shift,
-// background -- to an observed star, a blended group or a star cube; the photometry of a frame in render.hip).
+// background -- to an observed star, a blended group or a star cube; the frame calls in render.hip, find.hip,
+// group.hip and frame_fit.hip, which share frame_common.h).
 // Host code (mpsfr_api.cpp) sees only these plain functions.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -291,25 +292,29 @@ void launch_stamp_metrics(hipStream_t s, int nstamp, const double* d_stamps, con
 // d_ws: render_workspace_bytes(ny, nx, nstar) bytes of work lists, which the launch itself clears on the stream.
 void launch_cut_stamps(hipStream_t s, int ny, int nx, const double* d_image, const double* d_var, int nstar,
                        const int32_t* d_origin, double* d_stamps, double* d_var_out);
-size_t render_workspace_bytes(int ny, int nx, int nstar);
-void launch_render_stars(hipStream_t s, int ny, int nx, const double* d_image_in, int nstar, int npsf,
-                         const double* d_psf, const int32_t* d_index, const int32_t* d_origin, const double* d_shift,
-                         const double* d_scale, bool subtract, double* d_image_out, double* d_star_out, void* d_ws);
-// The two halves of launch_render_stars, for a caller that walks the same lists many times (frame_fit.hip):
-// launch_render_lists builds the per-tile star lists in d_ws (prepare, scan, fill) -- with d_accept [nstar] only of the
-// stars it marks, which pass render's rule but for the scale (d_scale may then be nullptr) --, launch_render_walk is the
-// tile walk alone; with d_done it does nothing once *d_done is not 0.  render_lists: where the lists lie in d_ws.
-struct RenderLists {
-    int *count, *cursor, *offset, *status, *pairs;      // [nt], [nt], [nt + 1], [nstar], [9 nstar]
-    int ntx, nty;                                       // 32 x 32 frame tiles each way, nt = ntx nty
+// The stars of a frame call, by value to launchers and kernels (device pointers): star k is the model stamp
+// psf[index[k]] (index nullptr: psf[k]) of psf [npsf][40][40], its pixel [0][0] on the frame pixel origin[2 k], [2 k + 1],
+// resampled at shift[2 k], [2 k + 1] (nullptr: zeros).  The scales are an argument of their own: the frame fit walks one
+// list with several vectors.  (Here and not in frame_common.h, because the host code fills it.)
+struct StarList {
+    int nstar, npsf;
+    const double* psf;
+    const int32_t *index, *origin;
+    const double* shift;
 };
-RenderLists render_lists(int ny, int nx, int nstar, void* d_ws);
-void launch_render_lists(hipStream_t s, int ny, int nx, int nstar, int npsf, const int32_t* d_index,
-                         const int32_t* d_origin, const double* d_shift, const double* d_scale,
-                         const int32_t* d_accept, double* d_star_out, void* d_ws);
-void launch_render_walk(hipStream_t s, int ny, int nx, const double* d_image_in, int nstar, const double* d_psf,
-                        const int32_t* d_index, const int32_t* d_origin, const double* d_shift, const double* d_scale,
+size_t render_workspace_bytes(int ny, int nx, int nstar);
+void launch_render_stars(hipStream_t s, int ny, int nx, const double* d_image_in, StarList stars, const double* d_scale,
+                         bool subtract, double* d_image_out, double* d_star_out, void* d_ws);
+// The two halves of launch_render_stars, for a caller that walks the same lists many times (frame_fit.hip):
+// launch_render_lists builds the per-tile star lists in d_ws (prepare, scan, fill; RenderLists of frame_common.h is
+// where they lie) -- with d_accept [nstar] only of the stars it marks, which pass FrameStar's rule (d_scale may then be
+// nullptr) --, launch_render_walk is the tile walk alone; with d_done it does nothing once *d_done is not 0.
+void launch_render_lists(hipStream_t s, int ny, int nx, StarList stars, const double* d_scale, const int32_t* d_accept,
+                         double* d_star_out, void* d_ws);
+void launch_render_walk(hipStream_t s, int ny, int nx, const double* d_image_in, StarList stars, const double* d_scale,
                         bool subtract, double* d_image_out, void* d_ws, const int32_t* d_done);
+// d_offset[t] = sum of d_count[0 .. t - 1], d_offset[nt] = the total: the scan of the frame calls' counts (render.hip)
+void launch_scan_counts(hipStream_t s, int nt, const int* d_count, int* d_offset);
 // The star finder (find.hip; mpsfr_find_stars, include/mpsfr.h): the statistic T of every pixel of d_image [ny][nx]
 // (d_var [ny][nx] or nullptr) with the (2 half + 1)^2 core of the model stamp d_psf [40][40], its peaks over (2 sep + 1)^2
 // squares at or above `threshold` in pixel order into d_star_out [max_stars][8] and d_origin_out [max_stars][2] (or
@@ -331,11 +336,11 @@ void launch_group_stars(hipStream_t s, int ny, int nx, int nstar, const double* 
 // Crowded-field photometry (frame_fit.hip; mpsfr_fit_frame_psf, include/mpsfr.h): the fluxes of all accepted stars and,
 // with `background`, one constant by preconditioned conjugate gradients on the frame d_image / d_var (or nullptr), at
 // most max_iter steps queued at once, into d_star_out [nstar][8], d_head_out [8] and d_resid_out [ny][nx] (or nullptr).
-// d_ws: frame_fit_workspace_bytes(ny, nx, nstar) bytes -- render_workspace_bytes, two frames of doubles,
-// 7 nstar + 4 ceil(ny nx / 4096) + 9 doubles, 2 nstar + 5 int32; the launch writes every word of it before it reads it.
+// d_ws: frame_fit_workspace_bytes(ny, nx, nstar) bytes -- the renderer's lists, two frames of doubles, 7 nstar +
+// 4 ceil(ny nx / 4096) + 9 doubles, 2 nstar + 5 int32 (FrameFitWork, frame_fit.hip); the launch writes every word of it
+// before it reads it.
 size_t frame_fit_workspace_bytes(int ny, int nx, int nstar);
-void launch_fit_frame(hipStream_t s, int ny, int nx, const double* d_image, const double* d_var, int nstar, int npsf,
-                      const double* d_psf, const int32_t* d_index, const int32_t* d_origin, const double* d_shift,
+void launch_fit_frame(hipStream_t s, int ny, int nx, const double* d_image, const double* d_var, StarList stars,
                       const double* d_scale0, double radius, bool background, int max_iter, double tol,
                       double* d_star_out, double* d_head_out, double* d_resid_out, void* d_ws);
 // band-integrated stamps (band.hip): d_fin [ntb][nl][40][40] (float if fin_f32, else double) reduced over wavelength

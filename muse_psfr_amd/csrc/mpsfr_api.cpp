@@ -618,6 +618,31 @@ int stamp_call(mpsfr_ctx* c, int on_device, const StampIn (&in)[N], double* out,
 
 const size_t kStampPix = (size_t)NS * NS;
 
+// The host form's refusal of a model list: every psf_index (n of them, or nullptr) in 0..npsf-1, then every one of the
+// nshift shifts (or nullptr) finite and within 8 pixels; `what` is the caller's noun for a shift.
+int check_model_list(const char* who, const char* what, int n, int npsf, const int32_t* psf_index, const double* shift,
+                     size_t nshift) {
+    if (psf_index)
+        for (int k = 0; k < n; ++k)
+            if (psf_index[k] < 0 || psf_index[k] >= npsf)
+                return fail(MPSFR_E_INVALID, "%s: a psf_index outside 0..npsf-1", who);
+    if (shift)
+        for (size_t k = 0; k < nshift; ++k)
+            if (!(std::fabs(shift[k]) <= MPSFR_FIT_PSF_MAX_SHIFT))
+                return fail(MPSFR_E_INVALID, "%s: a %s that is not finite or beyond 8 pixels", who, what);
+    return MPSFR_OK;
+}
+
+// ... and of the stars of a frame: finite scales (or nullptr), then origins within 2^30
+int check_frame_stars(const char* who, int n, const int32_t* origin, const double* scale, const char* scale_name) {
+    if (scale)
+        for (int k = 0; k < n; ++k)
+            if (!std::isfinite(scale[k])) return fail(MPSFR_E_INVALID, "%s: a %s that is not finite", who, scale_name);
+    for (size_t k = 0; k < (size_t)2 * n; ++k)
+        if (origin[k] < -(1 << 30) || origin[k] > (1 << 30)) return fail(MPSFR_E_INVALID, "%s: an origin beyond 2^30", who);
+    return MPSFR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2395,16 +2420,10 @@ int mpsfr_fit_stamps_psf(mpsfr_ctx* c, int nstamp, const double* stamps, const d
         return fail(MPSFR_E_INVALID, "fit_stamps_psf: without psf_index, npsf must equal nstamp");
     if ((flags & MPSFR_FIT_FIXED_SHIFT) && !shift)
         return fail(MPSFR_E_INVALID, "fit_stamps_psf: MPSFR_FIT_FIXED_SHIFT needs the shift array");
-    if (!on_device) {
-        if (psf_index)
-            for (int k = 0; k < nstamp; ++k)
-                if (psf_index[k] < 0 || psf_index[k] >= npsf)
-                    return fail(MPSFR_E_INVALID, "fit_stamps_psf: a psf_index outside 0..npsf-1");
-        if (shift)
-            for (size_t k = 0; k < (size_t)2 * nstamp; ++k)
-                if (!(std::fabs(shift[k]) <= MPSFR_FIT_PSF_MAX_SHIFT))
-                    return fail(MPSFR_E_INVALID, "fit_stamps_psf: a shift that is not finite or beyond 8 pixels");
-    }
+    int rc;
+    if (!on_device &&
+        (rc = check_model_list("fit_stamps_psf", "shift", nstamp, npsf, psf_index, shift, (size_t)2 * nstamp)))
+        return rc;
     const StampIn in[] = {{stamps, nstamp * kStampPix, sizeof(double)}, {var, nstamp * kStampPix, sizeof(double)},
                           {psf, npsf * kStampPix, sizeof(double)},      {shift, (size_t)2 * nstamp, sizeof(double)},
                           {psf_index, (size_t)nstamp, sizeof(int32_t)}};
@@ -2434,15 +2453,9 @@ int mpsfr_fit_groups_psf(mpsfr_ctx* c, int nstamp, int nsrc, const double* stamp
     if (!psf_index && npsf != nstamp)
         return fail(MPSFR_E_INVALID, "fit_groups_psf: without psf_index, npsf must equal nstamp");
     const size_t npos = (size_t)2 * nsrc * nstamp;
-    if (!on_device) {
-        if (psf_index)
-            for (int k = 0; k < nstamp; ++k)
-                if (psf_index[k] < 0 || psf_index[k] >= npsf)
-                    return fail(MPSFR_E_INVALID, "fit_groups_psf: a psf_index outside 0..npsf-1");
-        for (size_t k = 0; k < npos; ++k)
-            if (!(std::fabs(shift[k]) <= MPSFR_FIT_PSF_MAX_SHIFT))
-                return fail(MPSFR_E_INVALID, "fit_groups_psf: a position that is not finite or beyond 8 pixels");
-    }
+    int rc;
+    if (!on_device && (rc = check_model_list("fit_groups_psf", "position", nstamp, npsf, psf_index, shift, npos)))
+        return rc;
     const StampIn in[] = {{stamps, nstamp * kStampPix, sizeof(double)}, {var, nstamp * kStampPix, sizeof(double)},
                           {psf, npsf * kStampPix, sizeof(double)},      {shift, npos, sizeof(double)},
                           {psf_index, (size_t)nstamp, sizeof(int32_t)}};
@@ -2475,20 +2488,12 @@ int mpsfr_fit_spectra_psf(mpsfr_ctx* c, int nstar, int nl, const double* cubes, 
         }
         if (!differ) return fail(MPSFR_E_INVALID, "fit_spectra_psf: at least two values of x must differ");
     }
-    if (!on_device) {
-        if (psf_index)
-            for (int k = 0; k < nstar; ++k)
-                if (psf_index[k] < 0 || psf_index[k] >= npsf)
-                    return fail(MPSFR_E_INVALID, "fit_spectra_psf: a psf_index outside 0..npsf-1");
-        if (shift)
-            for (size_t k = 0; k < (size_t)2 * nstar; ++k)
-                if (!(std::fabs(shift[k]) <= MPSFR_FIT_PSF_MAX_SHIFT))
-                    return fail(MPSFR_E_INVALID, "fit_spectra_psf: a start that is not finite or beyond 8 pixels");
-    }
+    int rc;
+    if (!on_device && (rc = check_model_list("fit_spectra_psf", "start", nstar, npsf, psf_index, shift, (size_t)2 * nstar)))
+        return rc;
     const double* d_x = nullptr;
     if (drift) {           // x is the host's in both forms: into a buffer of the context, on the stream of the call
         HIPCHK(hipSetDevice(c->device));
-        int rc;
         if ((rc = ensure(c, c->specx, (size_t)nl * sizeof(double)))) return rc;
         HIPCHK(hipMemcpyAsync(c->specx.p, x, (size_t)nl * sizeof(double), hipMemcpyHostToDevice, c->stream));
         d_x = (const double*)c->specx.p;
@@ -2573,19 +2578,8 @@ int mpsfr_render_stars(mpsfr_ctx* c, int ny, int nx, const double* image_in, int
     if (!psf_index && npsf != nstar)
         return fail(MPSFR_E_INVALID, "render_stars: without psf_index, npsf must equal nstar");
     if (!on_device) {
-        if (psf_index)
-            for (int k = 0; k < nstar; ++k)
-                if (psf_index[k] < 0 || psf_index[k] >= npsf)
-                    return fail(MPSFR_E_INVALID, "render_stars: a psf_index outside 0..npsf-1");
-        if (shift)
-            for (size_t k = 0; k < (size_t)2 * nstar; ++k)
-                if (!(std::fabs(shift[k]) <= MPSFR_FIT_PSF_MAX_SHIFT))
-                    return fail(MPSFR_E_INVALID, "render_stars: a shift that is not finite or beyond 8 pixels");
-        for (int k = 0; k < nstar; ++k)
-            if (!std::isfinite(scale[k])) return fail(MPSFR_E_INVALID, "render_stars: a scale that is not finite");
-        for (size_t k = 0; k < (size_t)2 * nstar; ++k)
-            if (origin[k] < -(1 << 30) || origin[k] > (1 << 30))
-                return fail(MPSFR_E_INVALID, "render_stars: an origin beyond 2^30");
+        if ((rc = check_model_list("render_stars", "shift", nstar, npsf, psf_index, shift, (size_t)2 * nstar))) return rc;
+        if ((rc = check_frame_stars("render_stars", nstar, origin, scale, "scale"))) return rc;
     }
     HIPCHK(hipSetDevice(c->device));
     if ((rc = ensure(c, c->render, render_workspace_bytes(ny, nx, nstar)))) return rc;
@@ -2595,8 +2589,9 @@ int mpsfr_render_stars(mpsfr_ctx* c, int ny, int nx, const double* image_in, int
                           {origin, (size_t)2 * nstar, sizeof(int32_t)}, {psf_index, (size_t)nstar, sizeof(int32_t)}};
     const StampOut out[] = {{image_out, npix}, {star_out, (size_t)nstar * MPSFR_NRENDER}};
     return stamp_call(c, on_device, in, out, [&](hipStream_t s, const void* const* d, double* const* d_out) {
-        launch_render_stars(s, ny, nx, (const double*)d[0], nstar, npsf, (const double*)d[1], (const int32_t*)d[5],
-                            (const int32_t*)d[4], (const double*)d[2], (const double*)d[3],
+        const StarList stars{nstar, npsf, (const double*)d[1], (const int32_t*)d[5], (const int32_t*)d[4],
+                             (const double*)d[2]};
+        launch_render_stars(s, ny, nx, (const double*)d[0], stars, (const double*)d[3],
                             (flags & MPSFR_RENDER_SUBTRACT) != 0, d_out[0], d_out[1], c->render.p);
     });
 }
@@ -2702,20 +2697,8 @@ int mpsfr_fit_frame_psf(mpsfr_ctx* c, int ny, int nx, const double* image, const
     if (max_iter < 1 || max_iter > MPSFR_FRAME_FIT_MAX_ITER)
         return fail(MPSFR_E_INVALID, "fit_frame_psf: max_iter=%d outside 1..%d", max_iter, MPSFR_FRAME_FIT_MAX_ITER);
     if (!on_device) {
-        if (psf_index)
-            for (int k = 0; k < nstar; ++k)
-                if (psf_index[k] < 0 || psf_index[k] >= npsf)
-                    return fail(MPSFR_E_INVALID, "fit_frame_psf: a psf_index outside 0..npsf-1");
-        if (shift)
-            for (size_t k = 0; k < (size_t)2 * nstar; ++k)
-                if (!(std::fabs(shift[k]) <= MPSFR_FIT_PSF_MAX_SHIFT))
-                    return fail(MPSFR_E_INVALID, "fit_frame_psf: a shift that is not finite or beyond 8 pixels");
-        if (scale0)
-            for (int k = 0; k < nstar; ++k)
-                if (!std::isfinite(scale0[k])) return fail(MPSFR_E_INVALID, "fit_frame_psf: a scale0 that is not finite");
-        for (size_t k = 0; k < (size_t)2 * nstar; ++k)
-            if (origin[k] < -(1 << 30) || origin[k] > (1 << 30))
-                return fail(MPSFR_E_INVALID, "fit_frame_psf: an origin beyond 2^30");
+        if ((rc = check_model_list("fit_frame_psf", "shift", nstar, npsf, psf_index, shift, (size_t)2 * nstar))) return rc;
+        if ((rc = check_frame_stars("fit_frame_psf", nstar, origin, scale0, "scale0"))) return rc;
     }
     HIPCHK(hipSetDevice(c->device));
     if ((rc = ensure(c, c->framefit, frame_fit_workspace_bytes(ny, nx, nstar)))) return rc;
@@ -2729,8 +2712,9 @@ int mpsfr_fit_frame_psf(mpsfr_ctx* c, int ny, int nx, const double* image, const
                           {psf_index, (size_t)nstar, sizeof(int32_t)}};
     const StampOut out[] = {{star_out, (size_t)nstar * MPSFR_NFRAMEFIT}, {head_out, MPSFR_NFRAMEFIT}, {resid_out, npix}};
     return stamp_call(c, on_device, in, out, [&](hipStream_t s, const void* const* d, double* const* d_out) {
-        launch_fit_frame(s, ny, nx, (const double*)d[0], (const double*)d[1], nstar, npsf, (const double*)d[2],
-                         (const int32_t*)d[6], (const int32_t*)d[5], (const double*)d[3], (const double*)d[4], radius,
+        const StarList stars{nstar, npsf, (const double*)d[2], (const int32_t*)d[6], (const int32_t*)d[5],
+                             (const double*)d[3]};
+        launch_fit_frame(s, ny, nx, (const double*)d[0], (const double*)d[1], stars, (const double*)d[4], radius,
                          (flags & MPSFR_FIT_BACKGROUND) != 0, max_iter, tol, d_out[0], d_out[1], d_out[2],
                          c->framefit.p);
     });

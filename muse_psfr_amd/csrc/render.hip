@@ -3,20 +3,19 @@
 //   k_render_prepare  one thread per star: validates it, writes star_out, counts the star on the tiles its footprint
 //                     (the kPsfSide x kPsfSide window around its stamp) reaches; with `accept` (the frame fit of
 //                     frame_fit.hip, which has judged the stars already) only the stars it marks are listed
-//   k_render_scan     exclusive scan of the tile counts (one workgroup)
+//   k_scan_counts     exclusive scan of the tile counts (one workgroup; the finder and the grouping scan with it too)
 //   k_render_fill     writes each star's index into the lists of its tiles at an atomic cursor (arbitrary order)
 //   k_render_tiles    one workgroup per tile: sorts its list by star index, then walks it in that order -- the model
 //                     stamp part the tile needs goes into LDS (two buffers, the next star fetched while this one is
 //                     evaluated), every thread keeps four pixels in registers
 // The order of the sum at a pixel is the star index, whatever the tile grid or the scheduling; no floating-point atomics.
 // Arithmetic is fp64 in both precision modes; P~ is psf_interp of fit_psf_common.h with KeysTaps<double>.
-#include "fit_psf_common.h"
-#include "scan_common.h"
+#include "frame_common.h"
 
 namespace mpsfr {
 namespace {
 
-constexpr int kTile = 32;                                     // frame tile side
+constexpr int kTile = 32;                                     // frame tile side: kFrameTile, spelt out for the layout below
 constexpr int kTileThreads = 256;
 constexpr int kTileRows = kTileThreads / kTile;               // threads per tile column
 constexpr int kTilePix = kTile / kTileRows;                   // pixels per thread: adjacent rows of one column
@@ -25,15 +24,17 @@ constexpr int kStageSide = kTile + 3;                         // model rows / co
 constexpr int kStageStride = kStageSide + 1;
 constexpr int kStageLoads = (kStageSide * kStageSide + kTileThreads - 1) / kTileThreads;     // per thread
 constexpr int kSortChunk = 256;                               // MPSFR_RENDER_SORT_CHUNK: lists up to here sort in LDS
-constexpr int kMaxOrigin = 1 << 30;
+constexpr int kScanThreads = 1024;
+static_assert(kTile == kFrameTile, "the lists are built (RenderLists) and walked on one tile grid");
 static_assert(kTile * kTile == kTileThreads * kTilePix && kTileRows * kTile == kTileThreads, "tile layout");
 static_assert(kSortChunk == kTileThreads, "one list entry per thread in the LDS copy");
 
 __global__ __launch_bounds__(256) void k_cut_stamps(int ny, int nx, const double* __restrict__ image,
-                                                    const double* __restrict__ var, const int32_t* __restrict__ origin,
+                                                    const double* __restrict__ var, StarList stars,
                                                     double* __restrict__ out, double* __restrict__ var_out) {
     const int k = blockIdx.x;
-    const long long op = origin[2 * k], oq = origin[2 * k + 1];
+    const FrameStar star(stars, k);              // (any origin: a stamp off the frame is NaN)
+    const long long op = star.op, oq = star.oq;
     for (int i = threadIdx.x; i < NS * NS; i += 256) {
         const int p = i / NS, q = i - p * NS;
         const long long Y = op + p, X = oq + q;
@@ -49,34 +50,18 @@ __global__ __launch_bounds__(256) void k_cut_stamps(int ny, int nx, const double
     }
 }
 
-// the frame pixels inside the footprint of a star at (op, oq): rows y0 .. y1 - 1, columns x0 .. x1 - 1
-__device__ __forceinline__ bool footprint(int ny, int nx, int op, int oq, int& y0, int& y1, int& x0, int& x1) {
-    y0 = max(op - kPsfApron, 0);
-    y1 = min(op + NS + kPsfApron, ny);
-    x0 = max(oq - kPsfApron, 0);
-    x1 = min(oq + NS + kPsfApron, nx);
-    return y0 < y1 && x0 < x1;
-}
-
-__global__ __launch_bounds__(256) void k_render_prepare(int ny, int nx, int ntx, int nstar, int npsf,
-                                                        const int32_t* __restrict__ index,
-                                                        const int32_t* __restrict__ origin,
-                                                        const double* __restrict__ shift,
+__global__ __launch_bounds__(256) void k_render_prepare(int ny, int nx, int ntx, StarList stars,
                                                         const double* __restrict__ scale,
                                                         const int32_t* __restrict__ accept, int* __restrict__ count,
                                                         int* __restrict__ status, double* __restrict__ star_out) {
     const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= nstar) return;
-    const int op = origin[2 * k], oq = origin[2 * k + 1];
-    const int ix = index ? index[k] : k;
-    const double dp = shift ? shift[2 * k] : 0.0, dq = shift ? shift[2 * k + 1] : 0.0;
-    const bool ok = (unsigned)ix < (unsigned)npsf && psf_inside(dp, dq) &&
-                    (accept ? accept[k] != 0 : fabs(scale[k]) < __builtin_inf()) &&
-                    op >= -kMaxOrigin && op <= kMaxOrigin && oq >= -kMaxOrigin && oq <= kMaxOrigin;
+    if (k >= stars.nstar) return;
+    const FrameStar star(stars, k);
+    const bool ok = star.valid(stars.npsf) && (accept ? accept[k] != 0 : fabs(scale[k]) < __builtin_inf());
     int st = 2, npix = 0;
     if (ok) {
         int y0, y1, x0, x1;
-        const bool hit = footprint(ny, nx, op, oq, y0, y1, x0, x1);
+        const bool hit = star.footprint(ny, nx, y0, y1, x0, x1);
         st = hit ? 0 : 1;
         if (hit) {
             npix = (y1 - y0) * (x1 - x0);
@@ -93,21 +78,33 @@ __global__ __launch_bounds__(256) void k_render_prepare(int ny, int nx, int ntx,
     }
 }
 
-// offset[t] = sum of count[0 .. t - 1], offset[nt] = the total
-__global__ __launch_bounds__(kScanThreads) void k_render_scan(int nt, const int* __restrict__ count,
+// The exclusive scan of up to a few million counts by one workgroup: offset[t] = sum of count[0 .. t - 1], offset[nt] =
+// the total.  Every thread sums a contiguous share, the shares are scanned in LDS.
+__global__ __launch_bounds__(kScanThreads) void k_scan_counts(int nt, const int* __restrict__ count,
                                                               int* __restrict__ offset) {
     __shared__ int part[kScanThreads];
-    scan_shares(nt, count, offset, part);
+    const int tid = threadIdx.x;
+    const int per = (nt + kScanThreads - 1) / kScanThreads;
+    const int b = min(tid * per, nt), e = min(b + per, nt);
+    int sum = 0;
+    for (int i = b; i < e; ++i) sum += count[i];
+    part[tid] = sum;
+    block_scan<kScanThreads>(part);
+    int run = part[tid] - sum;
+    for (int i = b; i < e; ++i) {
+        offset[i] = run;
+        run += count[i];
+    }
+    if (tid == kScanThreads - 1) offset[nt] = part[tid];
 }
 
-__global__ __launch_bounds__(256) void k_render_fill(int ny, int nx, int ntx, int nstar,
-                                                     const int32_t* __restrict__ origin,
+__global__ __launch_bounds__(256) void k_render_fill(int ny, int nx, int ntx, StarList stars,
                                                      const int* __restrict__ status, const int* __restrict__ offset,
                                                      int* __restrict__ cursor, int* __restrict__ pairs) {
     const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= nstar || status[k] != 0) return;
+    if (k >= stars.nstar || status[k] != 0) return;
     int y0, y1, x0, x1;
-    footprint(ny, nx, origin[2 * k], origin[2 * k + 1], y0, y1, x0, x1);
+    FrameStar(stars, k).footprint(ny, nx, y0, y1, x0, x1);
     for (int ty = y0 / kTile; ty <= (y1 - 1) / kTile; ++ty)
         for (int tx = x0 / kTile; tx <= (x1 - 1) / kTile; ++tx) {
             const int t = ty * ntx + tx;
@@ -153,29 +150,20 @@ __device__ void sort_indices(int* v, int n) {
     }
 }
 
-// the part of a model stamp a tile needs, in LDS, zero outside the model's pixels: tap (a, b) of the pixel at offset o
-struct TileStamp {
-    const double* base;
-    template <typename RE>
-    __device__ __forceinline__ RE at(int o, int, int, int a, int b) const {
-        return (RE)base[o + a * kStageStride + b];
-    }
-};
-
 // One star as a tile sees it: its parameters (the same for all threads) and the model pixel of stage[0][0]
 struct TileStar {
     int op, oq, r0, c0;
     double sc;
     const double* P;
     KeysTaps<double> ty{0.0}, tx{0.0};
-    __device__ __forceinline__ void load(int k, int Y0, int X0, const double* psf, const int32_t* index,
-                                         const int32_t* origin, const double* shift, const double* scale) {
-        op = origin[2 * k];
-        oq = origin[2 * k + 1];
+    __device__ __forceinline__ void load(int k, int Y0, int X0, const StarList& stars, const double* scale) {
+        const FrameStar star(stars, k);
+        op = star.op;
+        oq = star.oq;
         sc = scale[k];
-        ty = KeysTaps<double>(shift ? shift[2 * k] : 0.0);
-        tx = KeysTaps<double>(shift ? shift[2 * k + 1] : 0.0);
-        P = psf + (size_t)(index ? index[k] : k) * (NS * NS);
+        ty = KeysTaps<double>(star.dp);
+        tx = KeysTaps<double>(star.dq);
+        P = star.model(stars);
         r0 = Y0 - op + ty.f - 1;
         c0 = X0 - oq + tx.f - 1;
     }
@@ -184,10 +172,7 @@ struct TileStar {
 #pragma unroll
         for (int m = 0; m < kStageLoads; ++m) {
             const int e = tid + m * kTileThreads, si = e / kStageSide, sj = e - si * kStageSide;
-            const int r = r0 + si, c = c0 + sj;
-            const bool in = e < kStageSide * kStageSide && (unsigned)r < (unsigned)NS && (unsigned)c < (unsigned)NS;
-            const double v = P[in ? r * NS + c : 0];
-            pre[m] = in ? v : 0.0;
+            pre[m] = model_pixel(P, r0 + si, c0 + sj, e < kStageSide * kStageSide);
         }
     }
 };
@@ -199,11 +184,7 @@ __device__ __forceinline__ double add_term(double acc, double scale, double val,
     return subtract ? acc - t : acc + t;
 }
 
-__global__ __launch_bounds__(kTileThreads) void k_render_tiles(int ny, int nx, const double* image_in,
-                                                               const double* __restrict__ psf,
-                                                               const int32_t* __restrict__ index,
-                                                               const int32_t* __restrict__ origin,
-                                                               const double* __restrict__ shift,
+__global__ __launch_bounds__(kTileThreads) void k_render_tiles(int ny, int nx, const double* image_in, StarList stars,
                                                                const double* __restrict__ scale, int subtract,
                                                                const int* __restrict__ offset, int* pairs,
                                                                const int32_t* __restrict__ done, double* image_out) {
@@ -237,7 +218,7 @@ __global__ __launch_bounds__(kTileThreads) void k_render_tiles(int ny, int nx, c
     TileStar cur, nxt;
     double pre[kStageLoads];
     if (n > 0) {
-        cur.load(list[0], Y0, X0, psf, index, origin, shift, scale);
+        cur.load(list[0], Y0, X0, stars, scale);
         cur.fetch(tid, pre);
     }
     for (int i = 0; i < n; ++i) {
@@ -248,11 +229,11 @@ __global__ __launch_bounds__(kTileThreads) void k_render_tiles(int ny, int nx, c
             if (e < kStageSide * kStageSide) buf[(e / kStageSide) * kStageStride + e % kStageSide] = pre[m];
         }
         if (i + 1 < n) {
-            nxt.load(list[i + 1], Y0, X0, psf, index, origin, shift, scale);
+            nxt.load(list[i + 1], Y0, X0, stars, scale);
             nxt.fetch(tid, pre);
         }
         __syncthreads();
-        const TileStamp st{buf};
+        const StagedStamp<kStageStride> st{buf};
         const int q = X - cur.oq;
         // (a wave holds kWaveRows rows of the tile: it skips a star whose footprint lies above or below them)
         const int pw = Y0 + (tid / 64) * kWaveRows - cur.op;
@@ -283,61 +264,42 @@ __global__ __launch_bounds__(kTileThreads) void k_render_tiles(int ny, int nx, c
 
 void launch_cut_stamps(hipStream_t s, int ny, int nx, const double* d_image, const double* d_var, int nstar,
                        const int32_t* d_origin, double* d_stamps, double* d_var_out) {
-    hipLaunchKernelGGL(k_cut_stamps, dim3(nstar), dim3(256), 0, s, ny, nx, d_image, d_var, d_origin, d_stamps,
-                       d_var_out);
+    const StarList stars{nstar, 0, nullptr, nullptr, d_origin, nullptr};          // the origins alone
+    hipLaunchKernelGGL(k_cut_stamps, dim3(nstar), dim3(256), 0, s, ny, nx, d_image, d_var, stars, d_stamps, d_var_out);
 }
 
-static int render_tiles_x(int nx) { return (nx + kTile - 1) / kTile; }
-
-size_t render_workspace_bytes(int ny, int nx, int nstar) {
-    const size_t nt = (size_t)render_tiles_x(ny) * render_tiles_x(nx);
-    // count [nt], cursor [nt], offset [nt + 1], status [nstar], pairs [9 nstar]: a footprint reaches at most 3 x 3 tiles
-    return (3 * nt + 1 + (size_t)nstar * 10) * sizeof(int);
+void launch_scan_counts(hipStream_t s, int nt, const int* d_count, int* d_offset) {
+    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(kScanThreads), 0, s, nt, d_count, d_offset);
 }
 
-// the work lists in d_ws: count [nt], cursor [nt], offset [nt + 1], status [nstar], pairs [9 nstar]
-RenderLists render_lists(int ny, int nx, int nstar, void* d_ws) {
-    RenderLists l;
-    l.ntx = render_tiles_x(nx);
-    l.nty = render_tiles_x(ny);
-    const int nt = l.ntx * l.nty;
-    l.count = (int*)d_ws;
-    l.cursor = l.count + nt;
-    l.offset = l.cursor + nt;
-    l.status = l.offset + nt + 1;
-    l.pairs = l.status + nstar;
-    return l;
-}
+size_t render_workspace_bytes(int ny, int nx, int nstar) { return workspace_bytes<RenderLists>(ny, nx, nstar); }
 
-void launch_render_lists(hipStream_t s, int ny, int nx, int nstar, int npsf, const int32_t* d_index,
-                         const int32_t* d_origin, const double* d_shift, const double* d_scale,
-                         const int32_t* d_accept, double* d_star_out, void* d_ws) {
+void launch_render_lists(hipStream_t s, int ny, int nx, StarList stars, const double* d_scale, const int32_t* d_accept,
+                         double* d_star_out, void* d_ws) {
     static_assert(kPsfSide + kTile - 1 <= 3 * kTile, "a footprint reaches at most 3 x 3 tiles");
-    const RenderLists l = render_lists(ny, nx, nstar, d_ws);
-    const int nt = l.ntx * l.nty;
-    (void)hipMemsetAsync(l.count, 0, (size_t)2 * nt * sizeof(int), s);
-    const int gstar = (nstar + 255) / 256;
-    hipLaunchKernelGGL(k_render_prepare, dim3(gstar), dim3(256), 0, s, ny, nx, l.ntx, nstar, npsf, d_index, d_origin,
-                       d_shift, d_scale, d_accept, l.count, l.status, d_star_out);
-    hipLaunchKernelGGL(k_render_scan, dim3(1), dim3(kScanThreads), 0, s, nt, l.count, l.offset);
-    hipLaunchKernelGGL(k_render_fill, dim3(gstar), dim3(256), 0, s, ny, nx, l.ntx, nstar, d_origin, l.status, l.offset,
-                       l.cursor, l.pairs);
+    WorkspaceCarver ws(d_ws);
+    const RenderLists l(ws, ny, nx, stars.nstar);
+    (void)hipMemsetAsync(l.count, 0, (size_t)2 * l.nt * sizeof(int), s);          // count and cursor
+    const int gstar = (stars.nstar + 255) / 256;
+    hipLaunchKernelGGL(k_render_prepare, dim3(gstar), dim3(256), 0, s, ny, nx, l.ntx, stars, d_scale, d_accept, l.count,
+                       l.status, d_star_out);
+    launch_scan_counts(s, l.nt, l.count, l.offset);
+    hipLaunchKernelGGL(k_render_fill, dim3(gstar), dim3(256), 0, s, ny, nx, l.ntx, stars, l.status, l.offset, l.cursor,
+                       l.pairs);
 }
 
-void launch_render_walk(hipStream_t s, int ny, int nx, const double* d_image_in, int nstar, const double* d_psf,
-                        const int32_t* d_index, const int32_t* d_origin, const double* d_shift, const double* d_scale,
+void launch_render_walk(hipStream_t s, int ny, int nx, const double* d_image_in, StarList stars, const double* d_scale,
                         bool subtract, double* d_image_out, void* d_ws, const int32_t* d_done) {
-    const RenderLists l = render_lists(ny, nx, nstar, d_ws);
-    hipLaunchKernelGGL(k_render_tiles, dim3(l.ntx, l.nty), dim3(kTileThreads), 0, s, ny, nx, d_image_in, d_psf, d_index,
-                       d_origin, d_shift, d_scale, subtract ? 1 : 0, l.offset, l.pairs, d_done, d_image_out);
+    WorkspaceCarver ws(d_ws);
+    const RenderLists l(ws, ny, nx, stars.nstar);
+    hipLaunchKernelGGL(k_render_tiles, dim3(l.ntx, l.nty), dim3(kTileThreads), 0, s, ny, nx, d_image_in, stars, d_scale,
+                       subtract ? 1 : 0, l.offset, l.pairs, d_done, d_image_out);
 }
 
-void launch_render_stars(hipStream_t s, int ny, int nx, const double* d_image_in, int nstar, int npsf,
-                         const double* d_psf, const int32_t* d_index, const int32_t* d_origin, const double* d_shift,
-                         const double* d_scale, bool subtract, double* d_image_out, double* d_star_out, void* d_ws) {
-    launch_render_lists(s, ny, nx, nstar, npsf, d_index, d_origin, d_shift, d_scale, nullptr, d_star_out, d_ws);
-    launch_render_walk(s, ny, nx, d_image_in, nstar, d_psf, d_index, d_origin, d_shift, d_scale, subtract, d_image_out,
-                       d_ws, nullptr);
+void launch_render_stars(hipStream_t s, int ny, int nx, const double* d_image_in, StarList stars, const double* d_scale,
+                         bool subtract, double* d_image_out, double* d_star_out, void* d_ws) {
+    launch_render_lists(s, ny, nx, stars, d_scale, nullptr, d_star_out, d_ws);
+    launch_render_walk(s, ny, nx, d_image_in, stars, d_scale, subtract, d_image_out, d_ws, nullptr);
 }
 
 }  // namespace mpsfr
