@@ -799,7 +799,10 @@ int mpsfr_fit_frame_psf(mpsfr_ctx* ctx, int ny, int nx, const double* image, con
  *                      BEFORE the convolutions (mean over the ndir directions, normalised to sum 1).  A PSD with
  *                      a NaN or an infinity is refused (MPSFR_E_INVALID) before anything is queued; a finite PSD
  *                      so large that its transform overflows gives non-finite stamps, and leaves no trace in the
- *                      calls after it.
+ *                      calls after it.  (mpsfr_psd_to_psf below does NOT look at its PSDs: a PSD with a NaN is
+ *                      accepted, return code 0, and every pixel of every plane of that PSD comes back NaN -- the
+ *                      NaN goes through both passes of the structure function's transform; the other PSDs of the
+ *                      same call are computed as ever, and nothing of it is left in the calls after it.)
  * mpsfr_convolve_stamps  convolve_final_psf (psfrec.py:874-930): psf_in [ntask][nl][dimpsf][dimpsf] convolved
  *                      with each task's tip-tilt Moffat kernel and the instrument's, into psf_out. */
 int mpsfr_simul_psd(mpsfr_ctx* ctx, double seeing, double gl, double l0, int three_lgs, const double h[2],
@@ -813,7 +816,7 @@ int mpsfr_convolve_stamps(mpsfr_ctx* ctx, int ntask, const double* seeing, const
 /* psd_to_psf (psfrec.py:689-807): the full dimnum x dimnum PSF of any PSD, any pupil and an optional static
  * phase, for FoV == FoVnum and samp <= dim / npup (the reference's other branches are not supported).
  *   psd           [npsd][dim][dim] float64, centred (DC at [dim/2][dim/2]), nm^2 m^2 at the PSF wavelength;
- *                 dim is the context's grid
+ *                 dim is the context's grid.  Not checked for NaN: see mpsfr_psf_from_psd above
  *   pup           [npup][npup] float64, any real values (apodised, spiders, gaps); sum(pup) != 0
  *   phase_static  [npup][npup] or NULL.  The field is pup exp(2 pi i phase_static / lbda_m) as psfrec.py:785-786
  *                 computes it: phase_static is in METRES (the reference's docstring says nm; its code divides
