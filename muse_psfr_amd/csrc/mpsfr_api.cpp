@@ -919,13 +919,8 @@ int mpsfr_wait_event(mpsfr_ctx* c, void* hip_event) {
     return MPSFR_OK;
 }
 
-// Hooks of the stage-level entry points (mpsfr_simul_psd, mpsfr_psf_from_psd, mpsfr_convolve_stamps):
-// the same pipeline, entered or left at another stage.  Host buffers, synchronous, one pipeline pass.
+// What the entry points other than mpsfr_reconstruct add to a pipeline call.
 struct StageIO {
-    double* psd_out = nullptr;        // [ndir][N][N]: leave with the PSD of task 0 (simul_psd_wfm)
-    const double* psd_in = nullptr;   // [ndir][N][N]: the PSD of the one task, instead of the model
-    const double* pre_in = nullptr;   // [ntask][nl][40][40]: stamps before the convolutions, instead of stages A + B
-    bool stop_pre = false;            // psf_out receives the stamps BEFORE the convolutions (psf_muse)
     // mpsfr_reconstruct_field: stage A evaluates the npos caller positions pos [npos][2] (arcsec) instead of the
     // npsflin grid, and stage B keeps them apart -- every (task, position) pair is a one-direction task of its own
     int npos = 0;
@@ -964,15 +959,33 @@ struct CallArgs {
     int on_device = 0;
 };
 
-static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io);
+// The rows, wavelengths, masks and outputs of an entry point (what the five pipeline entry points share)
+static CallArgs pipeline_args(int ntask, const double* seeing, const double* gl, const double* l0,
+                              const uint8_t* three_lgs, int nl, const double* lbda_nm, const uint8_t* mask_rec,
+                              const uint8_t* mask_res, double* psf_out, double* psf_sum_out, double* fit_out,
+                              int on_device) {
+    CallArgs a;
+    a.ntask = ntask, a.seeing = seeing, a.gl = gl, a.l0 = l0, a.three_lgs = three_lgs;
+    a.nl = nl, a.lbda_nm = lbda_nm, a.mask_rec = mask_rec, a.mask_res = mask_res;
+    a.psf_out = psf_out, a.psf_sum_out = psf_sum_out, a.fit_out = fit_out, a.on_device = on_device;
+    return a;
+}
 
-// Every entry point that runs the pipeline goes through this guard.  A call that fails leaves the
+// The drivers: the pipeline, and the three stage-level calls that enter or leave it at another stage (host buffers,
+// synchronous, on the same lanes, slots and tables)
+static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io);
+static int simul_psd_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io, double* psd_out);
+static int psf_from_psd_impl(mpsfr_ctx* c, const CallArgs& a, const double* psd_in);
+static int convolve_stamps_impl(mpsfr_ctx* c, const CallArgs& a, const double* pre_in);
+
+// Every entry point that runs a driver goes through this guard.  A call that fails leaves the
 // pipelining state as it found it: the lane rotation and the ring of parameter slots do not advance, and
 // an event registered with mpsfr_wait_event is consumed (the caller may destroy it after the call,
 // whatever the outcome).
-static int guarded_call(mpsfr_ctx* c, const CallArgs& a, const StageIO& io = StageIO()) {
+extern "C++" template <class Driver>
+static int guarded(mpsfr_ctx* c, Driver&& run) {
     const unsigned lane_rr0 = c->lane_rr, stage0 = c->stage_next;
-    const int rc = reconstruct_impl(c, a, io);
+    const int rc = run();
     if (rc != MPSFR_OK) {
         // whatever the failed call has queued (it may have cleared a slot's guard and started chunks
         // on other lanes) must have drained before the next call reuses the slot and the workspaces
@@ -986,6 +999,10 @@ static int guarded_call(mpsfr_ctx* c, const CallArgs& a, const StageIO& io = Sta
         for (int k = 0; k < mpsfr_ctx::NSTAGE; ++k) c->slot[k].staged_pending = false;
     }
     return rc;
+}
+
+static int guarded_call(mpsfr_ctx* c, const CallArgs& a, const StageIO& io = StageIO()) {
+    return guarded(c, [&] { return reconstruct_impl(c, a, io); });
 }
 
 // The directions of a call: the npsflin x npsflin grid (npos = 0, where min_npos allows it) or the caller's npos
@@ -1014,11 +1031,9 @@ int mpsfr_reconstruct(mpsfr_ctx* c, int ntask, const double* seeing, const doubl
                       const uint8_t* mask_rec, const uint8_t* mask_res, double* psf_out,
                       double* psf_sum_out, double* fit_out, int on_device) {
     if (!c) return fail(MPSFR_E_INVALID, "ctx is NULL");
-    CallArgs a;
-    a.ntask = ntask, a.seeing = seeing, a.gl = gl, a.l0 = l0, a.three_lgs = three_lgs;
+    CallArgs a = pipeline_args(ntask, seeing, gl, l0, three_lgs, nl, lbda_nm, mask_rec, mask_res, psf_out, psf_sum_out,
+                               fit_out, on_device);
     a.h = h, a.wind_speed = wind_speed, a.npsflin = npsflin;
-    a.nl = nl, a.lbda_nm = lbda_nm, a.mask_rec = mask_rec, a.mask_res = mask_res;
-    a.psf_out = psf_out, a.psf_sum_out = psf_sum_out, a.fit_out = fit_out, a.on_device = on_device;
     return guarded_call(c, a);
 }
 
@@ -1030,13 +1045,11 @@ int mpsfr_reconstruct_field(mpsfr_ctx* c, int ntask, const double* seeing, const
                             double* fit_out, int on_device) {
     if (!c) return fail(MPSFR_E_INVALID, "ctx is NULL");
     StageIO io;
-    CallArgs a;
+    CallArgs a = pipeline_args(ntask, seeing, gl, l0, three_lgs, nl, lbda_nm, mask_rec, mask_res, psf_out, psf_sum_out,
+                               fit_out, on_device);
     a.npsflin = 0;
     if (int rc = grid_or_positions(1, npos, pos_arcsec, a.npsflin, io)) return rc;
-    a.ntask = ntask, a.seeing = seeing, a.gl = gl, a.l0 = l0, a.three_lgs = three_lgs;
     a.h = h, a.wind_speed = wind_speed;
-    a.nl = nl, a.lbda_nm = lbda_nm, a.mask_rec = mask_rec, a.mask_res = mask_res;
-    a.psf_out = psf_out, a.psf_sum_out = psf_sum_out, a.fit_out = fit_out, a.on_device = on_device;
     return guarded_call(c, a, io);
 }
 
@@ -1066,13 +1079,11 @@ int mpsfr_reconstruct_band(mpsfr_ctx* c, int ntask, const double* seeing, const 
     StageIO io;
     io.nband = nband;
     io.bw = w.data();
-    CallArgs a;
+    CallArgs a = pipeline_args(ntask, seeing, gl, l0, three_lgs, nl, lbda_nm, mask_rec, mask_res, band_out, band_sum_out,
+                               band_fit_out, on_device);
     a.npsflin = npsflin;
     if (int rc = grid_or_positions(0, npos, pos_arcsec, a.npsflin, io)) return rc;
-    a.ntask = ntask, a.seeing = seeing, a.gl = gl, a.l0 = l0, a.three_lgs = three_lgs;
     a.h = h, a.wind_speed = wind_speed;
-    a.nl = nl, a.lbda_nm = lbda_nm, a.mask_rec = mask_rec, a.mask_res = mask_res;
-    a.psf_out = band_out, a.psf_sum_out = band_sum_out, a.fit_out = band_fit_out, a.on_device = on_device;
     return guarded_call(c, a, io);
 }
 
@@ -1145,13 +1156,11 @@ int mpsfr_reconstruct_profile(mpsfr_ctx* c, int ntask, const double* seeing, con
     StageIO io;
     io.layers = &ly;
     io.cn2 = w.data();
-    CallArgs a;
+    CallArgs a = pipeline_args(ntask, seeing, gl, l0, three_lgs, nl, lbda_nm, mask_rec, mask_res, psf_out, psf_sum_out,
+                               fit_out, on_device);
     a.npsflin = npsflin;
     if (int rc = grid_or_positions(0, npos, pos_arcsec, a.npsflin, io)) return rc;
-    a.ntask = ntask, a.seeing = seeing, a.gl = gl, a.l0 = l0, a.three_lgs = three_lgs;
     a.h = kNoH, a.wind_speed = 0.0;
-    a.nl = nl, a.lbda_nm = lbda_nm, a.mask_rec = mask_rec, a.mask_res = mask_res;
-    a.psf_out = psf_out, a.psf_sum_out = psf_sum_out, a.fit_out = fit_out, a.on_device = on_device;
     return guarded_call(c, a, io);
 }
 
@@ -1166,7 +1175,6 @@ int mpsfr_simul_psd_profile(mpsfr_ctx* c, double seeing, double l0, int three_lg
     StageIO io;
     io.layers = &ly;
     io.cn2 = w.data();
-    io.psd_out = psd_out;
     CallArgs a;
     a.npsflin = npsflin;
     // (with positions, the PSD of each position: stage A's directions are the positions, as in a field call)
@@ -1175,112 +1183,157 @@ int mpsfr_simul_psd_profile(mpsfr_ctx* c, double seeing, double l0, int three_lg
     a.seeing = &seeing, a.l0 = &l0, a.three_lgs = &t3;
     a.h = kNoH, a.wind_speed = 0.0;
     a.mask_rec = mask_rec, a.mask_res = mask_res;
-    return guarded_call(c, a, io);
+    return guarded(c, [&] { return simul_psd_impl(c, a, io, psd_out); });
 }
 
-static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) {
-    const int ntask = a.ntask, npsflin = a.npsflin, nl = a.nl;
-    int on_device = a.on_device;
-    const double *seeing = a.seeing, *gl = a.gl, *l0 = a.l0, *h = a.h, *lbda_nm = a.lbda_nm;
-    const uint8_t *three_lgs = a.three_lgs, *mask_rec = a.mask_rec, *mask_res = a.mask_res;
-    const double wind_speed = a.wind_speed;
-    double *psf_out = a.psf_out, *psf_sum_out = a.psf_sum_out, *fit_out = a.fit_out;
-    const auto t_enter = std::chrono::steady_clock::now();
-    const bool staged = io.psd_out || io.psd_in || io.pre_in || io.stop_pre;
-    if (staged && on_device != 0) return fail(MPSFR_E_INVALID, "stage-level calls take host buffers");
-    if (ntask < 1 || !seeing || !gl || !l0 || !h || !lbda_nm)
-        return fail(MPSFR_E_INVALID, "ntask < 1 or NULL input array");
-    if (nl < 1 || nl > 4096) return fail(MPSFR_E_INVALID, "nl=%d out of range", nl);
-    const bool field = io.npos > 0;
-    if (field && ((staged && !io.psd_out) || !io.pos)) return fail(MPSFR_E_INVALID, "field call without positions");
-    if (!field && (npsflin < 1 || npsflin > 5)) return fail(MPSFR_E_INVALID, "npsflin=%d out of range 1..5", npsflin);
-    if ((mask_rec == nullptr) != (mask_res == nullptr))
-        return fail(MPSFR_E_INVALID, "mask_rec and mask_res must both be given or both be NULL");
+// ===== The call path on the host ("The call path on the host").  Three kinds of steps, kept apart:
+//   preparation   pure host arithmetic on the arguments; takes the context const, makes no HIP call and is the only
+//                 place a call is refused for its arguments -- so a refused call has touched nothing;
+//   context steps ticket, lanes, slot, waits, cached tables, workspaces, the call's end: they change context state
+//                 and may queue waits, copies and table kernels;
+//   chunk stages  stage A, stage B and the tail of one chunk on one lane: kernel launches only.
+
+// ---- preparation
+
+// The pruning and tier thresholds of the per-wavelength stage
+struct Thresholds {
+    bool prune = false;            // trailing OTF lines below eps of the PSF peak are neither transformed nor read
+    bool floor_per_task = false;   // the kernel for several directions takes a per-task floor from K_PEAK_FLOOR
+    float thr_sum = 0.f, thr_blk = 0.f, thr_eps = 0.f, thr_floor = -1.0e30f, thr_mid = -1.0e30f, tier_half = 0.f;
+    float c2min = 0.f;             // log2-scaled exponent factor of the shortest wavelength (the most negative)
+};
+
+// What a call computes from its arguments before it touches the context: the shape, the paths its stages take, the
+// scalars of its rows and wavelengths.  Later steps only read it.
+struct CallPrep {
+    int ntask = 0, nl = 0, N = 0, H1 = 0;
     // ndir: the directions stage A evaluates per task.  Stage B sums ndb of them into a stamp, for gpp stamp groups
     // per task: the averaged call (ndb = ndir, gpp = 1) or the field call (ndb = 1, gpp = npos: group g of a chunk is
     // task g / npos at position g % npos, and every stage-B kernel sees tc x npos one-direction tasks)
-    const int N = c->N, H1 = N / 2 + 1, ndir = field ? io.npos : npsflin * npsflin;
-    const int gpp = field ? ndir : 1, ndb = field ? 1 : ndir;
-    // a band call: nout = nband output planes per stamp group (else the nl wavelengths)
-    const bool band = io.nband > 0;
-    if (band && (staged || !io.bw || io.nband > MAX_BANDS)) return fail(MPSFR_E_INVALID, "bad band request");
-    const int nout = band ? io.nband : nl;
-    HIPCHK(hipSetDevice(c->device));
-    int rc;
+    int ndir = 0, gpp = 1, ndb = 0;
+    // a band call: nout = nband output planes per stamp group (else the nl wavelengths); nsum = gpp x nout planes of
+    // a task: the sums run over the tasks of [task][nsum] stamps
+    int nout = 0, nsum = 0;
+    bool band = false;
+    const double* bw = nullptr;          // [nband][nl] the normalised weights of a band call
+    const AoLayers* ly = nullptr;        // a profile call
+    int ntab = 2, low = 0;               // layer tables per direction; the lowest layer
+    bool series = false;                 // stage A in its series + patch form (stage_a2.hip)
+    bool fft_conv = true;                // convolutions through 64-point FFTs (f64 mode: the same transforms in fp64)
+    size_t ksz = 0;                      // bytes of one convolution kernel (spectrum or taps)
+    bool mf = false, mf2 = false, r16 = false;   // stage B: matrix cores, its thin-wave kernel; the radix-16 row pass
+    Thresholds th;
+    AoGeom g;
+    std::vector<LamPar> lp;              // [nl]
+    std::vector<TaskPar> tp;             // [ntask]
+    std::vector<double> gam, alp;        // [ntask + nl] Moffat widths and exponents: tip-tilt kernels, instrument kernels
+    std::vector<double> wts;             // [ntask][ntab] profile weights, each row normalised
+};
 
-    // ---- per-wavelength scalars (psfrec.py:662-665, 717)
-    std::vector<LamPar> lp(nl);
-    std::vector<double> gam, alp;
-    for (int l = 0; l < nl; ++l) {
-        if (!(lbda_nm[l] > 0.0)) return fail(MPSFR_E_INVALID, "lbda[%d] must be > 0", l);
-        const double k = 2.0 * M_PI / lbda_nm[l];
-        lp[l].c = -0.5 * k * k;
-        lp[l].npixc = npix_crop(lbda_nm[l], c->dimpsf, c->pixscale);
-        lp[l].pad = 0;
-        if (!io.pre_in && !io.psd_out && (lp[l].npixc > N || lp[l].npixc < NS))
+// The argument checks every driver shares, and the shape integers
+static int call_shape(const mpsfr_ctx* c, const CallArgs& a, const StageIO& io, CallPrep& p) {
+    if (a.ntask < 1 || !a.seeing || !a.gl || !a.l0 || !a.h || !a.lbda_nm)
+        return fail(MPSFR_E_INVALID, "ntask < 1 or NULL input array");
+    if (a.nl < 1 || a.nl > 4096) return fail(MPSFR_E_INVALID, "nl=%d out of range", a.nl);
+    const bool field = io.npos > 0;
+    if (field && !io.pos) return fail(MPSFR_E_INVALID, "field call without positions");
+    if (!field && (a.npsflin < 1 || a.npsflin > 5)) return fail(MPSFR_E_INVALID, "npsflin=%d out of range 1..5", a.npsflin);
+    if ((a.mask_rec == nullptr) != (a.mask_res == nullptr))
+        return fail(MPSFR_E_INVALID, "mask_rec and mask_res must both be given or both be NULL");
+    p.band = io.nband > 0;
+    if (p.band && (!io.bw || io.nband > MAX_BANDS)) return fail(MPSFR_E_INVALID, "bad band request");
+    p.ntask = a.ntask, p.nl = a.nl, p.N = c->N, p.H1 = c->N / 2 + 1;
+    p.ndir = field ? io.npos : a.npsflin * a.npsflin;
+    p.gpp = field ? p.ndir : 1;
+    p.ndb = field ? 1 : p.ndir;
+    p.nout = p.band ? io.nband : a.nl;
+    p.nsum = p.gpp * p.nout;
+    p.bw = io.bw;
+    p.fft_conv = c->fft_conv;
+    p.ksz = p.fft_conv ? (size_t)KHAT * 2 * rsize(c) : (size_t)KS * KS * rsize(c);
+    return MPSFR_OK;
+}
+
+// Per-wavelength scalars (psfrec.py:662-665, 717).  cropped: the call crops the OTF at npixc, which must fit the grid.
+static int wavelength_scalars(const mpsfr_ctx* c, const CallArgs& a, bool cropped, CallPrep& p) {
+    p.lp.resize(a.nl);
+    for (int l = 0; l < a.nl; ++l) {
+        if (!(a.lbda_nm[l] > 0.0)) return fail(MPSFR_E_INVALID, "lbda[%d] must be > 0", l);
+        const double k = 2.0 * M_PI / a.lbda_nm[l];
+        p.lp[l].c = -0.5 * k * k;
+        p.lp[l].npixc = npix_crop(a.lbda_nm[l], c->dimpsf, c->pixscale);
+        p.lp[l].pad = 0;
+        if (cropped && (p.lp[l].npixc > c->N || p.lp[l].npixc < NS))
             return fail(MPSFR_E_GRID,
                         "lbda=%.3f nm needs a %d-pixel crop, outside [%d, dim=%d] "
-                        "(psfrec.py:663-683)", lbda_nm[l], lp[l].npixc, NS, N);
+                        "(psfrec.py:663-683)", a.lbda_nm[l], p.lp[l].npixc, NS, c->N);
     }
-    // ---- a profile call: every row's weights normalised to sum 1 (psfrec.py:57-58), padded to ntab with zeros
-    const AoLayers* ly = io.layers;
-    const int ntab = ly ? ly->ntab : 2;
-    std::vector<double> wts;
-    int low = 0;                         // the lowest layer
-    if (ly) {
+    return MPSFR_OK;
+}
+
+// Per-task scalars (psfrec.py:57-58, 108, 183-187), the weights of a profile call -- every row normalised to sum 1
+// (psfrec.py:57-58), padded to ntab with zeros -- and the Moffat parameters of the tip-tilt and instrument kernels.
+// Decides the form of stage A: the series form needs every 1/L0^2 inside the radius of its expansion (L0 >= 7 m; the
+// SPARTA front end only lets 8 < L0 < 30 through, psfrec.py:1049-1051); a call with a shorter outer scale takes the
+// full-size transforms.
+static int task_scalars(const mpsfr_ctx* c, const CallArgs& a, const StageIO& io, CallPrep& p) {
+    const int ntask = a.ntask, nl = a.nl;
+    p.ly = io.layers;
+    p.ntab = p.ly ? p.ly->ntab : 2;
+    p.low = 0;
+    if (p.ly) {
         if (!io.cn2) return fail(MPSFR_E_INVALID, "profile call without weights");
-        wts.assign((size_t)ntask * ntab, 0.0);
-        for (int l = 1; l < ly->n; ++l)
-            if (ly->h[l] < ly->h[low]) low = l;
+        p.wts.assign((size_t)ntask * p.ntab, 0.0);
+        for (int l = 1; l < p.ly->n; ++l)
+            if (p.ly->h[l] < p.ly->h[p.low]) p.low = l;
         for (int t = 0; t < ntask; ++t) {
-            const double* r = io.cn2 + (size_t)t * ly->n;
+            const double* r = io.cn2 + (size_t)t * p.ly->n;
             double sum = 0.0;
-            for (int l = 0; l < ly->n; ++l) sum += r[l];
-            for (int l = 0; l < ly->n; ++l) wts[(size_t)t * ntab + l] = r[l] / sum;
+            for (int l = 0; l < p.ly->n; ++l) sum += r[l];
+            for (int l = 0; l < p.ly->n; ++l) p.wts[(size_t)t * p.ntab + l] = r[l] / sum;
         }
     }
-    // ---- per-task scalars (psfrec.py:57-58, 108, 183-187) and Moffat kernel parameters
-    std::vector<TaskPar> tp(ntask);
-    gam.resize((size_t)ntask + nl);
-    alp.resize((size_t)ntask + nl);
+    p.tp.resize(ntask);
+    p.gam.resize((size_t)ntask + nl);
+    p.alp.resize((size_t)ntask + nl);
     for (int t = 0; t < ntask; ++t) {
-        if (!(seeing[t] > 0.0) || !(l0[t] > 0.0) || !(gl[t] >= 0.0) || !(gl[t] <= 1.0))
+        if (!(a.seeing[t] > 0.0) || !(a.l0[t] > 0.0) || !(a.gl[t] >= 0.0) || !(a.gl[t] <= 1.0))
             return fail(MPSFR_E_INVALID, "task %d: need seeing > 0, L0 > 0, 0 <= GL <= 1", t);
-        const double r0 = 0.976 * 0.5 / seeing[t] / 4.85;
-        double c0 = gl[t], c1 = 1.0 - gl[t];
+        const double r0 = 0.976 * 0.5 / a.seeing[t] / 4.85;
+        double c0 = a.gl[t], c1 = 1.0 - a.gl[t];
         const double cs = c0 + c1;
         c0 /= cs;
         c1 /= cs;
-        tp[t].r0m53 = std::pow(r0, -5.0 / 3.0);
-        tp[t].inv_l0sq = (1.0 / l0[t]) * (1.0 / l0[t]);
-        tp[t].cn2_0 = c0;
-        tp[t].cn2_1 = c1;
-        if (io.layers) {    // (the kernels read the weights; cn2_1 only orders the tasks: the weight above the lowest layer)
-            tp[t].cn2_0 = wts[(size_t)t * ntab + low];
-            tp[t].cn2_1 = 1.0 - tp[t].cn2_0;
+        TaskPar& tp = p.tp[t];
+        tp.r0m53 = std::pow(r0, -5.0 / 3.0);
+        tp.inv_l0sq = (1.0 / a.l0[t]) * (1.0 / a.l0[t]);
+        tp.cn2_0 = c0;
+        tp.cn2_1 = c1;
+        if (p.ly) {    // (the kernels read the weights; cn2_1 only orders the tasks: the weight above the lowest layer)
+            tp.cn2_0 = p.wts[(size_t)t * p.ntab + p.low];
+            tp.cn2_1 = 1.0 - tp.cn2_0;
         }
-        tp[t].geom = (three_lgs && three_lgs[t]) ? 1 : 0;
-        tp[t].basis = 0;
-        gam[t] = tiptilt_alpha(seeing[t], gl[t], l0[t], c->pixscale);
-        alp[t] = 2.0;                                    // beta_tt, psfrec.py:879
+        tp.geom = (a.three_lgs && a.three_lgs[t]) ? 1 : 0;
+        tp.basis = 0;
+        p.gam[t] = tiptilt_alpha(a.seeing[t], a.gl[t], a.l0[t], c->pixscale);
+        p.alp[t] = 2.0;                                    // beta_tt, psfrec.py:879
     }
-    for (int l = 0; l < nl; ++l) muse_kernel_params(lbda_nm[l], c->pixscale, &gam[ntask + l], &alp[ntask + l]);
-    // Stage A in its series form needs every 1/L0^2 inside the radius of its expansion (L0 >= 7 m;
-    // the SPARTA front end only lets 8 < L0 < 30 through, psfrec.py:1049-1051); a call with a shorter
-    // outer scale takes the full-size transforms.
-    bool series = c->stage_a == 2 || (c->stage_a == 1 && (N >= 512 || (N >= 256 && ndir >= 2)));
-    if (io.psd_in) series = false;
-    for (int t = 0; t < ntask; ++t) series = series && tp[t].inv_l0sq <= series_eps_max();
+    for (int l = 0; l < nl; ++l) muse_kernel_params(a.lbda_nm[l], c->pixscale, &p.gam[ntask + l], &p.alp[ntask + l]);
+    p.series = c->stage_a == 2 || (c->stage_a == 1 && (p.N >= 512 || (p.N >= 256 && p.ndir >= 2)));
+    for (int t = 0; t < ntask; ++t) p.series = p.series && p.tp[t].inv_l0sq <= series_eps_max();
+    return MPSFR_OK;
+}
 
-    // ---- geometry of the AO tables (psfrec.py:61, 66, 86-93, 99, 154-158, 536-537, 594)
+// Geometry of the AO tables (psfrec.py:61, 66, 86-93, 99, 154-158, 536-537, 594)
+static AoGeom ao_geometry(const CallArgs& a, const StageIO& io, int ndir) {
     AoGeom g;
     memset(&g, 0, sizeof g);
-    g.h[0] = h[0];
-    g.h[1] = h[1];
+    g.h[0] = a.h[0];
+    g.h[1] = a.h[1];
     const double arg_v[2] = {0.628163, -0.326497};
     for (int l = 0; l < 2; ++l) {
-        g.wind[0][l] = wind_speed * std::cos(arg_v[l]);
-        g.wind[1][l] = wind_speed * std::sin(arg_v[l]);
+        g.wind[0][l] = a.wind_speed * std::cos(arg_v[l]);
+        g.wind[1][l] = a.wind_speed * std::sin(arg_v[l]);
     }
     const double pos4[4][2] = {{1, 1}, {-1, -1}, {-1, 1}, {1, -1}};
     g.nlgs[0] = 4;
@@ -1291,8 +1344,9 @@ static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) 
             g.poslgs[ge][1][q] = pos4[q][1] * 63.0 / 60;
         }
     g.ndir = ndir;
+    const int npsflin = a.npsflin;
     for (int d = 0; d < ndir; ++d) {
-        if (field) {                    // (the convention of direction_perf: x = dirperf[0], in arcmin here)
+        if (io.npos > 0) {              // (the convention of direction_perf: x = dirperf[0], in arcmin here)
             g.dir[0][d] = io.pos[2 * d] / 60;
             g.dir[1][d] = io.pos[2 * d + 1] / 60;
         } else {
@@ -1300,134 +1354,99 @@ static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) 
             g.dir[1][d] = (double)(d % npsflin - npsflin / 2) * 60 / 2 / 60;
         }
     }
+    return g;
+}
 
-    // ---- asynchronous host outputs: the call writes a result set of the ring and is, from here on, a
-    // device-output call; the join stream then copies the set to its pinned mirror
-    mpsfr_ctx::Ticket* tk = nullptr;
-    if (on_device == 2) {
-        tk = &c->ticket[c->ticket_next % mpsfr_ctx::NTICKET];
-        if ((rc = complete_ticket(c, *tk))) return rc;         // NTICKET calls ago: hand it over first
-        tk->u_psf = psf_out;
-        tk->u_sum = psf_sum_out;
-        tk->u_fit = fit_out;
-        tk->n_psf = psf_out ? (size_t)ntask * gpp * nout * NS * NS : 0;
-        tk->n_sum = psf_sum_out ? (size_t)gpp * nout * NS * NS : 0;
-        tk->n_fit = fit_out ? (size_t)ntask * gpp * nout * NFIT : 0;
-        const size_t hb = (tk->n_psf + tk->n_sum + tk->n_fit) * sizeof(double);
-        if (hb > tk->host_cap) {
-            if (tk->host) HIPCHK(hipHostFree(tk->host));
-            tk->host = nullptr;
-            tk->host_cap = 0;
-            HIPCHK(hipHostMalloc(&tk->host, hb + hb / 8, hipHostMallocDefault));
-            tk->host_cap = hb + hb / 8;
-        }
-        if (tk->n_psf && (rc = ensure(c, tk->dpsf, tk->n_psf * sizeof(double)))) return rc;
-        if (tk->n_sum && (rc = ensure(c, tk->dsum, tk->n_sum * sizeof(double)))) return rc;
-        if (tk->n_fit && (rc = ensure(c, tk->dfit, tk->n_fit * sizeof(double)))) return rc;
-        if (!tk->done) HIPCHK(hipEventCreateWithFlags(&tk->done, hipEventDisableTiming));
-        psf_out = tk->n_psf ? (double*)tk->dpsf.p : nullptr;
-        psf_sum_out = tk->n_sum ? (double*)tk->dsum.p : nullptr;
-        fit_out = tk->n_fit ? (double*)tk->dfit.p : nullptr;
-        on_device = 1;
+// The paths of stage B and its thresholds.
+// Line pruning of the per-wavelength stage (mixed mode): the trailing lines of the OTF half plane that together
+// weigh less than eps of the PSF peak are neither transformed nor read by the second pass (stage_a.hip, "Line
+// pruning").  Matrix-core path: half of eps for the lines, half for the 16 x 32 blocks inside them (every element of
+// a dropped block is below 2^thr_blk; both half planes, all directions; ndb: the directions one stamp sums -- a field
+// stamp has one, and the whole budget).
+// Precision tiers of the matrix-core stage.  The OTF is generated times 2^15, so an element
+// below 2^-29 of OTF[0][0] has both fp16 halves in the subnormal range: a block whose bound is below
+// 2^-29.01 carries a few bits per element and is dropped ("floor"); a block below 2^-18.01 runs without
+// the low half ("mid").  Both are approximations (the matrix cores do not flush subnormals), held to a
+// budget: per (task, wavelength) the OTF mass each tier leaves out -- an upper bound from the block bounds --
+// stays below tier_eps / 2 of a lower bound of the PSF peak; K_MF_PREP lowers the thresholds where it
+// would not.  The kernel for several directions (otf_mfma.hip) has no such pass: its floor is the
+// per-task floor from K_PEAK_FLOOR (the same budget against the OTF of the shortest wavelength, blocks counted).
+static void stage_b_paths(const mpsfr_ctx* c, CallPrep& p) {
+    const int N = p.N, ndb = p.ndb;
+    // per-wavelength stage on the matrix cores (otf_mfma = 0: LDS FFTs on the vector pipe)
+    p.mf = !c->f64 && c->otf_mfma;
+    p.mf2 = p.mf && ndb == 1 && c->mf_kernel == 2;       // thin-wave kernel (otf_mfma2.hip)
+    p.r16 = !p.mf && otf_uses_r16(N, c->f64, p.nl, ndb);
+    Thresholds& th = p.th;
+    const double eps_prune = c->f64 ? c->prune_eps_f64 : c->prune_eps;
+    th.prune = eps_prune > 0.0;
+    th.thr_sum = th.prune ? (float)((p.mf ? 0.5 : 1.0) * eps_prune / (2.0 * N * ndb)) : 0.f;
+    th.thr_blk = (th.prune && p.mf)
+        ? (float)std::log2(0.5 * eps_prune / (2.0 * ndb * 16 * 32 * mf_block_count(N))) : 0.f;
+    th.thr_eps = th.thr_blk;
+    th.thr_floor = -1.0e30f;
+    const bool tiers = th.prune && p.mf && c->tier_eps > 0.0;
+    th.floor_per_task = tiers && c->mf_floor && !p.mf2 && std::isfinite(c->tier_eps);
+    if (tiers && c->mf_floor) {
+        th.thr_floor = (float)c->mf_floor_log2;
+        // tier_eps = inf: the plain floor
+        if (!p.mf2 && !th.floor_per_task && th.thr_blk < th.thr_floor) th.thr_blk = th.thr_floor;
     }
+    th.c2min = 0.f;
+    for (int l = 0; l < p.nl; ++l) th.c2min = std::fmin(th.c2min, (float)(p.lp[l].c * 1.44269504088896340736));
+    th.thr_mid = (tiers && c->mf_floor) ? (float)c->mf_mid_log2 : -1.0e30f;
+    th.tier_half = std::isfinite(c->tier_eps) ? (float)(0.5 * c->tier_eps) : 0.f;
+}
 
-    // ---- chunking and lanes
-    // Tasks per pipeline pass (below).  Consecutive chunks go to
-    // successive lanes (HIP streams with their own workspaces); the rotation carries over from
-    // call to call, so back-to-back asynchronous calls overlap like the chunks of one call do
-    // (+20 % PSFs/s on the 100-row bench step, +13 % inside a 1000-row call).
-    const int NLmax = c->nlanes == 0 ? 2 : c->nlanes;
-    int TC = c->chunk_tasks;
-    if (TC <= 0) {
-        // One chunk as long as it fits: up to 512 tasks (65536 stamps) and 4 GiB of C.  Beyond that,
-        // balanced chunks, a multiple of the lane count of them.  (The chunks used to be cut at ~4096
-        // stamps, "enough to fill the GPU": a 125-row call then ran as 118 + 7 rows and reached 9.8 M
-        // PSFs/s where one chunk reaches 14.6 M; 250 rows 11.3 -> 15.3 M, 1000 rows 14.5 -> 15.1 M.)
-        // (stamps per task: gpp x nl)
-        const int spt = gpp * nl + (band ? gpp * nout : 0);    // (a band call: its band stamps too)
-        int big = 65536 / spt;
-        const int soft = (4096 + spt - 1) / spt < 8 ? 8 : (4096 + spt - 1) / spt;
-        if (big > 512) big = 512;
-        if (big < soft) big = soft;
-        // (the largest workspace per task: the row transforms C of the full-size form; D and the patch
-        // transforms of the series form)
-        const double per_task = series ? (double)ndir * H1 * (N * (double)rsize(c) + kNH * 16.0)
-                                       : (double)ndir * (N / 2 + NAO / 2) * H1 * 16.0;
-        const int cap = (int)(4.0 * 1024 * 1024 * 1024 / per_task);
+// Everything a pipeline call computes from its arguments, and every refusal for them
+static int prepare_call(const mpsfr_ctx* c, const CallArgs& a, const StageIO& io, CallPrep& p) {
+    if (int rc = call_shape(c, a, io, p)) return rc;
+    if (int rc = wavelength_scalars(c, a, true, p)) return rc;
+    if (int rc = task_scalars(c, a, io, p)) return rc;
+    p.g = ao_geometry(a, io, p.ndir);
+    stage_b_paths(c, p);
+    return MPSFR_OK;
+}
+
+// Tasks per pipeline pass of a call that does not set "chunk_tasks".  spt: stamps per task; ws_per_task: bytes of
+// the largest workspace a task takes (0: none that counts); alone: the call has no neighbour call on another lane.
+// One chunk as long as it fits: up to 512 tasks (65536 stamps) and 4 GiB of that workspace.  Beyond that,
+// balanced chunks, a multiple of the lane count of them.  (The chunks used to be cut at ~4096
+// stamps, "enough to fill the GPU": a 125-row call then ran as 118 + 7 rows and reached 9.8 M
+// PSFs/s where one chunk reaches 14.6 M; 250 rows 11.3 -> 15.3 M, 1000 rows 14.5 -> 15.1 M.)
+static int auto_chunk_tasks(int ntask, int spt, double ws_per_task, int nlanes, bool alone) {
+    int big = 65536 / spt;
+    const int soft = (4096 + spt - 1) / spt < 8 ? 8 : (4096 + spt - 1) / spt;
+    if (big > 512) big = 512;
+    if (big < soft) big = soft;
+    if (ws_per_task > 0.0) {
+        const int cap = (int)(4.0 * 1024 * 1024 * 1024 / ws_per_task);
         if (big > cap) big = cap < 1 ? 1 : cap;
-        int nch = (ntask + big - 1) / big;
-        if (nch > 1) nch = (nch + NLmax - 1) / NLmax * NLmax;
-        // A synchronous call (host outputs, or pipelining off) has no neighbour call on the other lane:
-        // from 8192 stamps on, one pass per lane overlaps the stages of the halves (250 rows x 35
-        // wavelengths at 512^2: 0.78 -> 0.75 ms per call; 100 rows: 0.42 either way; four passes lose).
-        if (nch == 1 && NLmax > 1 && (long)ntask * spt >= 8192 && !(c->pipeline_calls && on_device != 0))
-            nch = NLmax;
-        TC = (ntask + nch - 1) / nch;
     }
-    // stage-level calls on one task's PSD: one pass.  (convolve_final_psf on caller stamps keeps the normal
-    // chunking: its host copies are per chunk, and it needs none of the workspaces of stages A and B.)
-    if (staged && !io.pre_in) TC = ntask;
-    if (TC > ntask) TC = ntask;
-    const int nchunks = (ntask + TC - 1) / TC;
-    // never more lanes than chunks: a lane without a chunk would leave its partial stamp sum
-    // unwritten, and the final sum over lanes would read stale memory
-    const int NL = NLmax < nchunks ? NLmax : nchunks;
-    const bool dev_out = on_device != 0;
-    // join: everything queued on the lanes becomes a dependency of the context's stream -- if anybody uses that
-    // stream: a caller that asked for it (mpsfr_stream), the copies of host outputs, the sum over several lanes.
-    // A device-output call on one lane of a context whose stream was never asked for stays on its lane: this GPU
-    // runs two active queues well and a third one at a loss (profiles/r05_experiments.md).
-    const bool join = c->stream_exported || tk != nullptr || !dev_out || NL > 1 || !c->pipeline_calls;
-    const bool lean = !join;
-    if (!(c->pipeline_calls && dev_out)) c->lane_rr = 0;       // synchronous calls: nothing to overlap
-    const int L0 = (int)(c->lane_rr % (unsigned)NLmax);
-    c->lane_rr += (unsigned)nchunks;
-    auto lane_of = [&](int j) -> mpsfr_ctx::Lane& { return c->lane[(L0 + j) % NLmax]; };
-    for (int j = 0; j < NL; ++j) {
-        mpsfr_ctx::Lane& ln = lane_of(j);
-        if (!ln.stream) {
-            const int li = (int)(&ln - c->lane);
-            if (c->cu_partition && NLmax > 1) {
-                // CU-mask bit i is CU i / 8 of XCD i % 8 (the driver deals the bits round the XCDs), so a
-                // contiguous range of bits is the same share of every XCD: each lane keeps all eight L2s
-                const int lo = c->ncu * li / NLmax, hi = c->ncu * (li + 1) / NLmax;
-                uint32_t mask[16] = {0};
-                for (int b = lo; b < hi && b < 512; ++b) mask[b >> 5] |= 1u << (b & 31);
-                HIPCHK(hipExtStreamCreateWithCUMask(&ln.stream, (uint32_t)((c->ncu + 31) / 32), mask));
-                ln.ncu = hi - lo;
-            } else {
-                HIPCHK(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
-                ln.ncu = 0;
-            }
-        }
-        if (!ln.done) HIPCHK(hipEventCreateWithFlags(&ln.done, hipEventDisableTiming));
-    }
-    hipStream_t s0 = lane_of(0).stream;        // the call's tables are produced on its first lane
-    // Stagger of the lanes at a cold start.  Two lanes that start together -- the first two calls (or
-    // chunks) after the GPU has drained -- settle into one of two phase relations, which then persists
-    // for as long as the pipeline stays full; on the bench workload (100 rows x 35 wavelengths, 512^2)
-    // the one they mostly find from a standing start is the slower (14.1 M PSFs/s against 14.6 M).  So
-    // the first chunk after a cold start records an event behind its column transforms and the next
-    // chunk on another lane waits for it: a one-time offset of half a stage A, after which the lanes run
-    // free.  OFF by default ("cold_stagger" = 1 / 2 switches it on): which relation a one-time offset
-    // selects depends on the shape of the call (measured in the sustained run: 100 rows +3 %, 125 rows 0,
-    // 250 rows -3 %, 500 rows +2.5 %, 1024^2 -2 %, 1280^2 -1 %), and the offset itself costs a short burst
-    // of calls what it gains a long one (20 calls from a standing start: -1 %).
-    const int stagger = c->cold_stagger;
-    bool cold_first = false;
-    if (stagger && NLmax > 1) {
-        cold_first = true;
-        for (int k = 0; k < mpsfr_ctx::MAX_LANES; ++k)
-            if (c->lane[k].busy && (c->lane[k].marked ? hipEventQuery(c->lane[k].done_ev) : hipStreamQuery(c->lane[k].stream)) != hipSuccess)
-                cold_first = false;
-        if (!c->stagger_ev) HIPCHK(hipEventCreateWithFlags(&c->stagger_ev, hipEventDisableTiming));
-    }
+    int nch = (ntask + big - 1) / big;
+    if (nch > 1) nch = (nch + nlanes - 1) / nlanes * nlanes;
+    // A synchronous call (host outputs, or pipelining off) has no neighbour call on the other lane:
+    // from 8192 stamps on, one pass per lane overlaps the stages of the halves (250 rows x 35
+    // wavelengths at 512^2: 0.78 -> 0.75 ms per call; 100 rows: 0.42 either way; four passes lose).
+    if (nch == 1 && nlanes > 1 && (long)ntask * spt >= 8192 && alone) nch = nlanes;
+    return (ntask + nch - 1) / nch;
+}
 
-    // ---- the AO tables are cached on their inputs (geometry + cut-off masks): the masks -- 12.8 KB of the ~20 KB a
-    // call used to upload -- only travel with a call that rebuilds the tables
-    // (a profile call: the key holds the whole profile too -- layers, altitudes, winds -- behind a byte that tells
-    // it from a legacy key)
-    if ((rc = ensure(c, c->aotab, (size_t)2 * ndir * (ntab + 1) * NAO * NAO * sizeof(double)))) return rc;
+// ... of a call through stages A and B (stamps per task: gpp x nl, and the band stamps of a band call; the largest
+// workspace per task: the row transforms C of the full-size form; D and the patch transforms of the series form)
+static int pipeline_chunk_tasks(const mpsfr_ctx* c, const CallPrep& p, bool alone) {
+    if (c->chunk_tasks > 0) return c->chunk_tasks;
+    const int spt = p.gpp * p.nl + (p.band ? p.gpp * p.nout : 0);
+    const double ws = p.series ? (double)p.ndir * p.H1 * (p.N * (double)rsize(c) + kNH * 16.0)
+                               : (double)p.ndir * (p.N / 2 + NAO / 2) * p.H1 * 16.0;
+    return auto_chunk_tasks(p.ntask, spt, ws, c->nlanes == 0 ? 2 : c->nlanes, alone);
+}
+
+// The AO tables are cached on their inputs (geometry + cut-off masks): the masks -- 12.8 KB of the ~20 KB a call used
+// to upload -- only travel with a call that rebuilds the tables.  A profile call: the key holds the whole profile
+// too -- layers, altitudes, winds -- behind a byte that tells it from a legacy key.
+static std::vector<unsigned char> ao_cache_key(const AoGeom& g, const AoLayers* ly, const uint8_t* mask_rec,
+                                               const uint8_t* mask_res) {
     const size_t ko = sizeof(AoGeom) + 1 + (ly ? sizeof(AoLayers) : 0);
     std::vector<unsigned char> key(ko + 1 + (mask_rec ? 2 * NAO * NAO : 0));
     memcpy(key.data(), &g, sizeof(AoGeom));
@@ -1449,28 +1468,238 @@ static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) 
         memcpy(key.data() + ko + 1, mask_rec, NAO * NAO);
         memcpy(key.data() + ko + 1 + NAO * NAO, mask_res, NAO * NAO);
     }
-    // (stage-level calls pass placeholder geometry or wavelengths for the stages they skip: those tables are
-    // neither built nor do they displace the cached ones of the last real call)
-    const bool need_ao = !io.pre_in && !io.psd_in;
-    const bool ao_cached = !need_ao || (key == c->cache_geom && c->cache_ao_ptr == c->aotab.p);
-    const bool send_masks = mask_rec && !ao_cached;
+    return key;
+}
 
-    // ---- uploads: one pinned blob [LamPar nl][TaskPar ntask][gam][alp]([mask_rec][mask_res])
-    auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t o_lp = 0;
-    const size_t o_tp = al16(o_lp + nl * sizeof(LamPar));
-    const size_t o_gam = al16(o_tp + ntask * sizeof(TaskPar));
-    const size_t o_alp = al16(o_gam + gam.size() * sizeof(double));
-    const size_t o_mr = al16(o_alp + alp.size() * sizeof(double));
-    const size_t o_ms = al16(o_mr + (send_masks ? NAO * NAO : 0));
-    const size_t o_w = al16(o_ms + (send_masks ? NAO * NAO : 0));    // profile weights
-    // (a band call: its weights [nl][band_stride(nband)], zero beyond nband)
-    const int bstride = band ? band_stride(nout) : 0;
-    const size_t o_bw = al16(o_w + wts.size() * sizeof(double));
-    const size_t blob = al16(o_bw + (size_t)nl * bstride * sizeof(double));
+// The device views of a call's parameter blob, and what else the kernels of a chunk read from its slot
+struct DevParams {
+    const LamPar* lp = nullptr;
+    const TaskPar* tp = nullptr;
+    const double *gam = nullptr, *alp = nullptr, *w = nullptr, *bw = nullptr;
+    const uint8_t *mrec = nullptr, *mres = nullptr;     // (read by K_AO_TABLES only)
+    int ntab = 2;
+    const char* ktt = nullptr;           // [ntask] tip-tilt kernels of the call (spectra or taps), ksz bytes each
+    LayerMix mix(int t0) const {
+        LayerMix m;
+        m.w = w ? w + (size_t)t0 * ntab : nullptr;
+        m.ntab = ntab;
+        return m;
+    }
+};
+
+// The small per-call parameters: one pinned blob [LamPar nl][TaskPar ntask][gam][alp]([mask_rec][mask_res])
+// ([profile weights])([band weights])
+struct Blob {
+    size_t o_lp, o_tp, o_gam, o_alp, o_mr, o_ms, o_w, o_bw, bytes;
+    int bstride;                         // a band call: its weights [nl][band_stride(nband)], zero beyond nband
+    bool masks;
+    static size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
+    Blob(const CallPrep& p, bool send_masks) : masks(send_masks) {
+        o_lp = 0;
+        o_tp = al16(o_lp + p.nl * sizeof(LamPar));
+        o_gam = al16(o_tp + p.ntask * sizeof(TaskPar));
+        o_alp = al16(o_gam + p.gam.size() * sizeof(double));
+        o_mr = al16(o_alp + p.alp.size() * sizeof(double));
+        o_ms = al16(o_mr + (masks ? NAO * NAO : 0));
+        o_w = al16(o_ms + (masks ? NAO * NAO : 0));
+        bstride = p.band ? band_stride(p.nout) : 0;
+        o_bw = al16(o_w + p.wts.size() * sizeof(double));
+        bytes = al16(o_bw + (size_t)p.nl * bstride * sizeof(double));
+    }
+    void fill(void* host, const CallPrep& p, const uint8_t* mask_rec, const uint8_t* mask_res) const {
+        char* hb = (char*)host;
+        memcpy(hb + o_lp, p.lp.data(), p.nl * sizeof(LamPar));
+        memcpy(hb + o_tp, p.tp.data(), p.ntask * sizeof(TaskPar));
+        memcpy(hb + o_gam, p.gam.data(), p.gam.size() * sizeof(double));
+        memcpy(hb + o_alp, p.alp.data(), p.alp.size() * sizeof(double));
+        if (p.ly) memcpy(hb + o_w, p.wts.data(), p.wts.size() * sizeof(double));
+        if (p.band) {
+            double* bw = reinterpret_cast<double*>(hb + o_bw);
+            for (int l = 0; l < p.nl; ++l)
+                for (int b = 0; b < bstride; ++b) bw[(size_t)l * bstride + b] = b < p.nout ? p.bw[(size_t)b * p.nl + l] : 0.0;
+        }
+        if (masks) {
+            memcpy(hb + o_mr, mask_rec, NAO * NAO);
+            memcpy(hb + o_ms, mask_res, NAO * NAO);
+        }
+    }
+    DevParams views(const mpsfr_ctx::Slot& sl, const CallPrep& p) const {
+        const char* db = (const char*)sl.params.p;
+        DevParams d;
+        d.lp = (const LamPar*)(db + o_lp);
+        d.tp = (const TaskPar*)(db + o_tp);
+        d.gam = (const double*)(db + o_gam);
+        d.alp = (const double*)(db + o_alp);
+        d.w = p.ly ? (const double*)(db + o_w) : nullptr;
+        d.bw = p.band ? (const double*)(db + o_bw) : nullptr;
+        d.mrec = masks ? (const uint8_t*)(db + o_mr) : nullptr;
+        d.mres = masks ? (const uint8_t*)(db + o_ms) : nullptr;
+        d.ntab = p.ntab;
+        d.ktt = (const char*)sl.ktt.p;
+        return d;
+    }
+};
+
+// ---- context steps
+
+// Host cost of queueing a call: the wall time inside it, not the time spent waiting for the GPU to catch up
+struct HostClock {
+    std::chrono::steady_clock::time_point enter = std::chrono::steady_clock::now();
+    double blocked = 0.0;
+    void finish(mpsfr_ctx* c) const {
+        c->host_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - enter).count() - blocked;
+        c->host_calls += 1;
+    }
+};
+
+// Where a call's results go: the caller's pointers (host or device), or the result set of a ticket
+struct CallOuts {
+    double *psf = nullptr, *sum = nullptr, *fit = nullptr;
+    bool dev = false;                    // they are device buffers
+    // where the chunks write: d_fin_all [ntask][nsum][1600] if the stamps go straight to a device buffer (else the
+    // lanes' workspaces), the fits of the whole call, the stamp sum
+    double *d_fin_all = nullptr, *d_fit_all = nullptr, *d_sum = nullptr;
+};
+
+// Asynchronous host outputs: the call writes a result set of the ring and is, from here on, a device-output call;
+// ticket_finish then copies the set to its pinned mirror on the join stream
+static int ticket_begin(mpsfr_ctx* c, const CallPrep& p, CallOuts& o, mpsfr_ctx::Ticket*& out) {
+    int rc;
+    mpsfr_ctx::Ticket* tk = &c->ticket[c->ticket_next % mpsfr_ctx::NTICKET];
+    if ((rc = complete_ticket(c, *tk))) return rc;         // NTICKET calls ago: hand it over first
+    tk->u_psf = o.psf;
+    tk->u_sum = o.sum;
+    tk->u_fit = o.fit;
+    tk->n_psf = o.psf ? (size_t)p.ntask * p.nsum * NS * NS : 0;
+    tk->n_sum = o.sum ? (size_t)p.nsum * NS * NS : 0;
+    tk->n_fit = o.fit ? (size_t)p.ntask * p.nsum * NFIT : 0;
+    const size_t hb = (tk->n_psf + tk->n_sum + tk->n_fit) * sizeof(double);
+    if (hb > tk->host_cap) {
+        if (tk->host) HIPCHK(hipHostFree(tk->host));
+        tk->host = nullptr;
+        tk->host_cap = 0;
+        HIPCHK(hipHostMalloc(&tk->host, hb + hb / 8, hipHostMallocDefault));
+        tk->host_cap = hb + hb / 8;
+    }
+    if (tk->n_psf && (rc = ensure(c, tk->dpsf, tk->n_psf * sizeof(double)))) return rc;
+    if (tk->n_sum && (rc = ensure(c, tk->dsum, tk->n_sum * sizeof(double)))) return rc;
+    if (tk->n_fit && (rc = ensure(c, tk->dfit, tk->n_fit * sizeof(double)))) return rc;
+    if (!tk->done) HIPCHK(hipEventCreateWithFlags(&tk->done, hipEventDisableTiming));
+    o.psf = tk->n_psf ? (double*)tk->dpsf.p : nullptr;
+    o.sum = tk->n_sum ? (double*)tk->dsum.p : nullptr;
+    o.fit = tk->n_fit ? (double*)tk->dfit.p : nullptr;
+    o.dev = true;
+    out = tk;
+    return MPSFR_OK;
+}
+
+static int ticket_finish(mpsfr_ctx* c, mpsfr_ctx::Ticket* tk) {
+    hipStream_t s = c->stream;
+    double* h = (double*)tk->host;
+    if (tk->n_psf) HIPCHK(hipMemcpyAsync(h, tk->dpsf.p, tk->n_psf * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (tk->n_sum) HIPCHK(hipMemcpyAsync(h + tk->n_psf, tk->dsum.p, tk->n_sum * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (tk->n_fit)
+        HIPCHK(hipMemcpyAsync(h + tk->n_psf + tk->n_sum, tk->dfit.p, tk->n_fit * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipEventRecord(tk->done, s));
+    tk->id = c->ticket_next++;
+    tk->pending = true;
+    return MPSFR_OK;
+}
+
+// The lanes of a call.  Consecutive chunks go to successive lanes (HIP streams with their own workspaces); the
+// rotation carries over from call to call, so back-to-back asynchronous calls overlap like the chunks of one call do
+// (+20 % PSFs/s on the 100-row bench step, +13 % inside a 1000-row call).
+struct CallLanes {
+    int NLmax = 2;       // lanes of the context
+    int TC = 1;          // tasks per chunk
+    int nchunks = 1;
+    int NL = 1;          // lanes this call uses.  Never more than chunks: a lane without a chunk would leave its
+                         // partial stamp sum unwritten, and the final sum over lanes would read stale memory
+    int first = 0;       // lane of the first chunk
+    // Stagger of the lanes at a cold start.  Two lanes that start together -- the first two calls (or
+    // chunks) after the GPU has drained -- settle into one of two phase relations, which then persists
+    // for as long as the pipeline stays full; on the bench workload (100 rows x 35 wavelengths, 512^2)
+    // the one they mostly find from a standing start is the slower (14.1 M PSFs/s against 14.6 M).  So
+    // the first chunk after a cold start records an event behind its column transforms and the next
+    // chunk on another lane waits for it: a one-time offset of half a stage A, after which the lanes run
+    // free.  OFF by default ("cold_stagger" = 1 / 2 switches it on): which relation a one-time offset
+    // selects depends on the shape of the call (measured in the sustained run: 100 rows +3 %, 125 rows 0,
+    // 250 rows -3 %, 500 rows +2.5 %, 1024^2 -2 %, 1280^2 -1 %), and the offset itself costs a short burst
+    // of calls what it gains a long one (20 calls from a standing start: -1 %).
+    bool cold_first = false;             // this call found every lane idle: its first chunk records the stagger event
+    int index(int j) const { return (first + j) % NLmax; }
+    mpsfr_ctx::Lane& at(mpsfr_ctx* c, int j) const { return c->lane[index(j)]; }
+};
+
+static bool lane_idle(const mpsfr_ctx::Lane& ln) {
+    return (ln.marked ? hipEventQuery(ln.done_ev) : hipStreamQuery(ln.stream)) == hipSuccess;
+}
+
+// Takes the call's place in the lane rotation and creates what its lanes lack.  rotate: the call is pipelined with
+// its neighbours (a synchronous call has nothing to overlap, and starts on lane 0).
+static int lanes_begin(mpsfr_ctx* c, int ntask, int chunk_tasks, bool rotate, CallLanes& L) {
+    L.NLmax = c->nlanes == 0 ? 2 : c->nlanes;
+    L.TC = chunk_tasks > ntask ? ntask : chunk_tasks;
+    L.nchunks = (ntask + L.TC - 1) / L.TC;
+    L.NL = L.NLmax < L.nchunks ? L.NLmax : L.nchunks;
+    if (!rotate) c->lane_rr = 0;
+    L.first = (int)(c->lane_rr % (unsigned)L.NLmax);
+    c->lane_rr += (unsigned)L.nchunks;
+    for (int j = 0; j < L.NL; ++j) {
+        mpsfr_ctx::Lane& ln = L.at(c, j);
+        if (!ln.stream) {
+            const int li = L.index(j);
+            if (c->cu_partition && L.NLmax > 1) {
+                // CU-mask bit i is CU i / 8 of XCD i % 8 (the driver deals the bits round the XCDs), so a
+                // contiguous range of bits is the same share of every XCD: each lane keeps all eight L2s
+                const int lo = c->ncu * li / L.NLmax, hi = c->ncu * (li + 1) / L.NLmax;
+                uint32_t mask[16] = {0};
+                for (int b = lo; b < hi && b < 512; ++b) mask[b >> 5] |= 1u << (b & 31);
+                HIPCHK(hipExtStreamCreateWithCUMask(&ln.stream, (uint32_t)((c->ncu + 31) / 32), mask));
+                ln.ncu = hi - lo;
+            } else {
+                HIPCHK(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
+                ln.ncu = 0;
+            }
+        }
+        if (!ln.done) HIPCHK(hipEventCreateWithFlags(&ln.done, hipEventDisableTiming));
+    }
+    L.cold_first = false;
+    if (c->cold_stagger && L.NLmax > 1) {
+        L.cold_first = true;
+        for (int k = 0; k < mpsfr_ctx::MAX_LANES; ++k)
+            if (c->lane[k].busy && !lane_idle(c->lane[k])) L.cold_first = false;
+        if (!c->stagger_ev) HIPCHK(hipEventCreateWithFlags(&c->stagger_ev, hipEventDisableTiming));
+    }
+    return MPSFR_OK;
+}
+
+// The cold-start stagger at point `which` of a chunk (1: behind the column transforms, 2: behind the preparation of
+// the per-wavelength stage): the first chunk of a call that found every lane idle records the event there
+static int stagger_here(mpsfr_ctx* c, CallLanes& L, int which, mpsfr_ctx::Lane& ln) {
+    if (L.cold_first && c->cold_stagger == which) {
+        if (hipEventRecord(c->stagger_ev, ln.stream) != hipSuccess) return fail(MPSFR_E_HIP, "hipEventRecord failed");
+        c->stagger_armed = true;
+        c->stagger_lane = (int)(&ln - c->lane);
+        L.cold_first = false;
+    }
+    return MPSFR_OK;
+}
+
+// ... and the next chunk on another lane waits for it, once
+static int stagger_wait(mpsfr_ctx* c, mpsfr_ctx::Lane& ln) {
+    if (c->stagger_armed && (int)(&ln - c->lane) != c->stagger_lane) {
+        HIPCHK(hipStreamWaitEvent(ln.stream, c->stagger_ev, 0));
+        c->stagger_armed = false;
+    }
+    return MPSFR_OK;
+}
+
+// Takes the next slot of the ring -- pinned blob, device blob, tip-tilt kernels -- once the copy that last used the
+// pinned blob has left it, and sizes it.  `blocked` receives the time spent waiting for that.
+static int slot_acquire(mpsfr_ctx* c, size_t blob, size_t ktt_bytes, mpsfr_ctx::Slot*& out, double& blocked) {
     mpsfr_ctx::Slot& sl = c->slot[c->stage_next++ % mpsfr_ctx::NSTAGE];
-    double t_blocked = 0.0;
-    if (sl.staged_pending) {        // the copy that last used the pinned blob must have left it
+    if (sl.staged_pending) {
         const auto tb = std::chrono::steady_clock::now();
         if (sl.staged_mode == 2) {               // (only blocks once the host is NSTAGE calls ahead)
             volatile unsigned long long* flag = c->seq_host + (&sl - c->slot);
@@ -1498,7 +1727,7 @@ static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) 
         } else {
             HIPCHK(hipEventSynchronize(sl.staged_ev));
         }
-        t_blocked = std::chrono::duration<double>(std::chrono::steady_clock::now() - tb).count();
+        blocked = std::chrono::duration<double>(std::chrono::steady_clock::now() - tb).count();
         sl.staged_pending = false;
     }
     if (blob > sl.host_cap) {
@@ -1510,51 +1739,38 @@ static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) 
     }
     if (!sl.staged) HIPCHK(hipEventCreateWithFlags(&sl.staged, hipEventDisableTiming));
     if (!sl.call_done) HIPCHK(hipEventCreateWithFlags(&sl.call_done, hipEventDisableTiming));
-    const bool use_fft_conv = c->fft_conv;      // (f64 mode: the same transforms in fp64)
-    const size_t ksz = use_fft_conv ? (size_t)KHAT * 2 * rsize(c) : (size_t)KS * KS * rsize(c);
+    int rc;
     if ((rc = ensure(c, sl.params, blob))) return rc;
-    if ((rc = ensure(c, sl.ktt, (size_t)ntask * ksz))) return rc;
-    char* hb = (char*)sl.host;
-    memcpy(hb + o_lp, lp.data(), nl * sizeof(LamPar));
-    memcpy(hb + o_tp, tp.data(), ntask * sizeof(TaskPar));
-    memcpy(hb + o_gam, gam.data(), gam.size() * sizeof(double));
-    memcpy(hb + o_alp, alp.data(), alp.size() * sizeof(double));
-    if (ly) memcpy(hb + o_w, wts.data(), wts.size() * sizeof(double));
-    if (band) {
-        double* bw = reinterpret_cast<double*>(hb + o_bw);
-        for (int l = 0; l < nl; ++l)
-            for (int b = 0; b < bstride; ++b) bw[(size_t)l * bstride + b] = b < nout ? io.bw[(size_t)b * nl + l] : 0.0;
-    }
-    if (send_masks) {
-        memcpy(hb + o_mr, mask_rec, NAO * NAO);
-        memcpy(hb + o_ms, mask_res, NAO * NAO);
-    }
-    // ---- what the call's lanes must wait for before they touch anything
-    //  * the call that used this slot NSTAGE calls ago (device blob, tip-tilt spectra);
-    //  * an event the caller registered (mpsfr_wait_event);
-    //  * the most recent call of any other lane that wrote the same output buffers (a caller that
-    //    reuses its buffers gets its calls in order);
-    //  * the previous consumer of the per-lane partial sums.
-    const void* outs[3] = {dev_out ? (const void*)psf_out : nullptr,
-                           dev_out ? (const void*)psf_sum_out : nullptr,
-                           dev_out ? (const void*)fit_out : nullptr};
+    if ((rc = ensure(c, sl.ktt, ktt_bytes))) return rc;
+    out = &sl;
+    return MPSFR_OK;
+}
+
+// What the call's lanes must wait for before they touch anything:
+//  * the call that used this slot NSTAGE calls ago (device blob, tip-tilt spectra);
+//  * an event the caller registered (mpsfr_wait_event);
+//  * the most recent call of any other lane that wrote the same output buffers `outs` (a caller that
+//    reuses its buffers gets its calls in order);
+//  * the previous consumer of the per-lane partial sums.
+static int queue_call_waits(mpsfr_ctx* c, const CallLanes& L, mpsfr_ctx::Slot& sl, const void* const outs[3]) {
     // (an event the caller registered that has already happened is no dependency any more)
     if (c->wait_next && hipEventQuery(c->wait_next) == hipSuccess) c->wait_next = nullptr;
     // (the call that used this slot NSTAGE calls ago has usually finished: then no lane waits for it)
     const bool slot_done = sl.call_pending && sl.has_event && hipEventQuery(sl.call_done) == hipSuccess;
-    for (int j = 0; j < NL; ++j) {
-        hipStream_t ls = lane_of(j).stream;
+    for (int j = 0; j < L.NL; ++j) {
+        mpsfr_ctx::Lane& ln = L.at(c, j);
+        hipStream_t ls = ln.stream;
         // (a lean call ran on one lane: on that lane stream order suffices; another lane waits for the slot's
         // event, or -- the call queued none -- for the end of that lane as it stands now)
-        if (sl.call_pending && !slot_done && sl.last_lane != (int)(&lane_of(j) - c->lane)) {
+        if (sl.call_pending && !slot_done && sl.last_lane != L.index(j)) {
             if (sl.has_event) HIPCHK(hipStreamWaitEvent(ls, sl.call_done, 0));
             else if (sl.last_lane >= 0) HIPCHK(hipStreamWaitEvent(ls, lane_end(c, c->lane[sl.last_lane]), 0));
         }
         if (c->wait_next) HIPCHK(hipStreamWaitEvent(ls, c->wait_next, 0));
-        if (c->lsum_busy && NL > 1) HIPCHK(hipStreamWaitEvent(ls, c->lsum_done, 0));
+        if (c->lsum_busy && L.NL > 1) HIPCHK(hipStreamWaitEvent(ls, c->lsum_done, 0));
         for (int k = 0; k < mpsfr_ctx::MAX_LANES; ++k) {
             mpsfr_ctx::Lane& o = c->lane[k];
-            if (&o == &lane_of(j) || !o.busy) continue;
+            if (&o == &ln || !o.busy) continue;
             bool same = false;
             for (int hsl = 0; hsl < mpsfr_ctx::Lane::NHIST; ++hsl)
                 for (int a = 0; a < 3; ++a)
@@ -1564,52 +1780,41 @@ static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) 
     }
     c->wait_next = nullptr;
     sl.call_pending = false;
-    // ---- tables cached on their inputs (geometry + masks; wavelengths).  A rebuild waits for
-    // every lane (an older call may still read the old tables) and is announced by `cache_ready`,
-    // which every later call's lanes wait for.
-    if ((rc = ensure(c, c->samp_p, (size_t)nl * NS * sizeof(int)))) return rc;
-    if ((rc = ensure(c, c->samp_a, (size_t)nl * NS * rsize(c)))) return rc;
-    // G rows are padded to a multiple of 8 lines (paired-line layout of the fp32 second pass)
-    if ((rc = ensure(c, c->G, (size_t)nl * ((H1 + 7) / 8 * 8) * NS * 2 * rsize(c)))) return rc;
-    if ((rc = ensure(c, c->kmuse, (size_t)nl * ksz))) return rc;
-    // per-wavelength stage on the matrix cores (otf_mfma = 0: LDS FFTs on the vector pipe)
-    const bool mf = !c->f64 && c->otf_mfma;
-    const bool mf2 = mf && ndb == 1 && c->mf_kernel == 2;       // thin-wave kernel (otf_mfma2.hip)
-    const bool r16 = !mf && otf_uses_r16(N, c->f64, nl, ndb);
-    if (r16 && (rc = ensure(c, c->xtab, xtab_bytes(nl)))) return rc;
-    if (mf) {
-        if ((rc = ensure(c, c->etab, mf_etab_bytes(N, nl)))) return rc;
-        if ((rc = ensure(c, c->gtab, mf_gtab_bytes(N, nl)))) return rc;
+    return MPSFR_OK;
+}
+
+// How much of the join a call can do without.
+// join: everything queued on the lanes becomes a dependency of the context's stream -- if anybody uses that
+// stream: a caller that asked for it (mpsfr_stream), the copies of host outputs, the sum over several lanes.
+// A device-output call on one lane of a context whose stream was never asked for stays on its lane: this GPU
+// runs two active queues well and a third one at a loss (profiles/r05_experiments.md).
+// "lean" calls -- device outputs on one lane of a context whose stream nobody uses -- queue NO marker packet
+// (a marker is a packet the queue stops at: ~7 us in the kernel trace, and the three of a call -- behind the
+// parameter copy, the lane's, the slot's -- were a tenth of a 100-row call): the copy kernel itself tells the
+// host, through a pinned word, when the blob may be refilled ("zero"); the slot and the lane get an event only when
+// another lane has to wait for them (lane_end).  With the hipMemcpyAsync form of the copy a lean call queues
+// one: the slot's event at the end of the lane's chain.
+struct Markers {
+    bool lean, zero;
+    Markers(const mpsfr_ctx* c, bool dev_out, bool ticket, int nlanes) {
+        const bool join = c->stream_exported || ticket || !dev_out || nlanes > 1 || !c->pipeline_calls;
+        lean = !join;
+        zero = lean && c->param_copy_kernel && c->seq_host != nullptr;
     }
-    const bool need_lam = !io.psd_out;
-    const std::vector<double> lb_key(lbda_nm, lbda_nm + nl);
-    const bool lam_cached = !need_lam || (lb_key == c->cache_lbda && c->cache_lbda_mode == (use_fft_conv ? 1 : 0) &&
-                            c->cache_G_ptr == c->G.p && c->cache_kmuse_ptr == c->kmuse.p &&
-                            (!r16 || (c->cache_xtab_valid && c->cache_xtab_ptr == c->xtab.p)) &&
-                            (!mf || (c->cache_mf_valid && c->cache_etab_ptr == c->etab.p &&
-                                     c->cache_gtab_ptr == c->gtab.p)));
-    // The blob travels as a KERNEL of the call's own queue that reads the pinned host memory: a
-    // hipMemcpyAsync of these ~20 KB is a hand-over to a copy engine and back, and sat at the head of every
-    // call ("param_copy" = 0 brings it back).
-    // "lean" calls -- device outputs on one lane of a context whose stream nobody uses -- queue NO marker packet
-    // (a marker is a packet the queue stops at: ~7 us in the kernel trace, and the three of a call -- behind the
-    // parameter copy, the lane's, the slot's -- were a tenth of a 100-row call): the copy kernel itself tells the
-    // host, through a pinned word, when the blob may be refilled; the slot and the lane get an event only when
-    // another lane has to wait for them (lane_end).  With the hipMemcpyAsync form of the copy a lean call queues
-    // one: the slot's event at the end of the lane's chain.
-    const bool zero = lean && c->param_copy_kernel && c->seq_host != nullptr;
-    // Round 6: in the series form of stage A the spectra of the tip-tilt kernels are extra workgroups of the patch's
-    // second kernel (K_PATCH_ROWS): a launch less at the head of a call ("head_fusion" = 0: K_KHAT as a kernel of
-    // its own).
-    const bool fuse_khat = c->head_fusion && series && !staged && c->fft_conv;
+};
+
+// Sends the blob of the slot to the device at the head of the call's first lane.  It travels as a KERNEL of the
+// call's own queue that reads the pinned host memory: a hipMemcpyAsync of these ~20 KB is a hand-over to a copy
+// engine and back, and sat at the head of every call ("param_copy" = 0 brings it back).
+static int send_params(mpsfr_ctx* c, mpsfr_ctx::Slot& sl, hipStream_t s0, size_t blob, const Markers& m) {
     sl.seq = ++c->seq_next;
-    if (zero) {
-        launch_param_copy(s0, sl.params.p, hb, blob, c->seq_host + (&sl - c->slot), sl.seq);
+    if (m.zero) {
+        launch_param_copy(s0, sl.params.p, sl.host, blob, c->seq_host + (&sl - c->slot), sl.seq);
         sl.staged_mode = 2;
     } else {
-        if (c->param_copy_kernel) launch_param_copy(s0, sl.params.p, hb, blob, nullptr, 0);
-        else HIPCHK(hipMemcpyAsync(sl.params.p, hb, blob, hipMemcpyHostToDevice, s0));
-        if (lean) {
+        if (c->param_copy_kernel) launch_param_copy(s0, sl.params.p, sl.host, blob, nullptr, 0);
+        else HIPCHK(hipMemcpyAsync(sl.params.p, sl.host, blob, hipMemcpyHostToDevice, s0));
+        if (m.lean) {
             sl.staged_ev = sl.call_done;
             sl.staged_mode = 1;
         } else {
@@ -1619,56 +1824,83 @@ static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) 
         }
     }
     sl.staged_pending = true;
-    const char* db = (const char*)sl.params.p;
-    const LamPar* d_lp = (const LamPar*)(db + o_lp);
-    const TaskPar* d_tp = (const TaskPar*)(db + o_tp);
-    const double* d_gam = (const double*)(db + o_gam);
-    const double* d_alp = (const double*)(db + o_alp);
-    const double* d_w = ly ? (const double*)(db + o_w) : nullptr;
-    const double* d_bw = band ? (const double*)(db + o_bw) : nullptr;
-    auto mix_of = [&](int t0) {
-        LayerMix m;
-        m.w = ly ? d_w + (size_t)t0 * ntab : nullptr;
-        m.ntab = ntab;
-        return m;
-    };
-    const uint8_t* d_mrec = send_masks ? (const uint8_t*)(db + o_mr) : nullptr;     // (read by K_AO_TABLES only)
-    const uint8_t* d_mres = send_masks ? (const uint8_t*)(db + o_ms) : nullptr;
+    return MPSFR_OK;
+}
 
-    if (!ao_cached || !lam_cached) {
+// ---- cached tables: the AO tables on (geometry, masks, profile), the per-wavelength tables on (wavelengths, form of
+// the convolutions, paths of stage B).  Sizing comes first, because a buffer that moved is no cache hit; a stage-level
+// call sizes and builds only the tables it reads, and so never displaces the cached ones of the last real call.
+
+static int size_ao_tables(mpsfr_ctx* c, const CallPrep& p, const std::vector<unsigned char>& key, bool& cached) {
+    if (int rc = ensure(c, c->aotab, (size_t)2 * p.ndir * (p.ntab + 1) * NAO * NAO * sizeof(double))) return rc;
+    cached = key == c->cache_geom && c->cache_ao_ptr == c->aotab.p;
+    return MPSFR_OK;
+}
+
+static int size_wavelength_tables(mpsfr_ctx* c, const CallPrep& p, const std::vector<double>& lb_key, bool& cached) {
+    int rc;
+    const int nl = p.nl;
+    if ((rc = ensure(c, c->samp_p, (size_t)nl * NS * sizeof(int)))) return rc;
+    if ((rc = ensure(c, c->samp_a, (size_t)nl * NS * rsize(c)))) return rc;
+    // G rows are padded to a multiple of 8 lines (paired-line layout of the fp32 second pass)
+    if ((rc = ensure(c, c->G, (size_t)nl * ((p.H1 + 7) / 8 * 8) * NS * 2 * rsize(c)))) return rc;
+    if ((rc = ensure(c, c->kmuse, (size_t)nl * p.ksz))) return rc;
+    if (p.r16 && (rc = ensure(c, c->xtab, xtab_bytes(nl)))) return rc;
+    if (p.mf) {
+        if ((rc = ensure(c, c->etab, mf_etab_bytes(p.N, nl)))) return rc;
+        if ((rc = ensure(c, c->gtab, mf_gtab_bytes(p.N, nl)))) return rc;
+    }
+    cached = lb_key == c->cache_lbda && c->cache_lbda_mode == (p.fft_conv ? 1 : 0) &&
+             c->cache_G_ptr == c->G.p && c->cache_kmuse_ptr == c->kmuse.p &&
+             (!p.r16 || (c->cache_xtab_valid && c->cache_xtab_ptr == c->xtab.p)) &&
+             (!p.mf || (c->cache_mf_valid && c->cache_etab_ptr == c->etab.p && c->cache_gtab_ptr == c->gtab.p));
+    return MPSFR_OK;
+}
+
+static void build_ao_tables(mpsfr_ctx* c, hipStream_t s0, const CallPrep& p, const DevParams& d,
+                            std::vector<unsigned char>& key) {
+    ProfScope ps(c, K_AO_TABLES, s0);
+    if (p.ly) launch_ao_tables_profile(s0, p.g, *p.ly, d.mrec, d.mres, (double*)c->aotab.p);
+    else launch_ao_tables(s0, p.g, d.mrec, d.mres, (double*)c->aotab.p);
+    c->cache_geom.swap(key);
+    c->last_ntab = p.ntab;
+    c->cache_ao_ptr = c->aotab.p;
+}
+
+static void build_wavelength_tables(mpsfr_ctx* c, hipStream_t s0, const CallPrep& p, const DevParams& d,
+                                    const std::vector<double>& lb_key) {
+    const int N = p.N, nl = p.nl;
+    {
+        ProfScope ps(c, K_GTABLE, s0);
+        launch_gtable(s0, N, nl, d.lp, c->tw64.p, (int*)c->samp_p.p, c->samp_a.p, c->G.p, c->f64);
+        if (p.r16) launch_xtab(s0, N, nl, (const int*)c->samp_p.p, c->samp_a.p, c->tw64.p, c->xtab.p);
+        if (p.mf) launch_mf_tables(s0, N, nl, d.lp, c->tw64.p, c->etab.p, c->gtab.p);
+    }
+    ProfScope ps(c, K_MOFFAT_KERNELS, s0);
+    if (p.fft_conv) launch_khat(s0, nl, d.gam + p.ntask, d.alp + p.ntask, c->kmuse.p, c->f64);
+    else launch_moffat_kernels(s0, nl, d.gam + p.ntask, d.alp + p.ntask, c->kmuse.p, c->f64);
+    c->cache_lbda = lb_key;
+    c->cache_lbda_mode = p.fft_conv ? 1 : 0;
+    c->cache_G_ptr = c->G.p;
+    c->cache_kmuse_ptr = c->kmuse.p;
+    c->cache_xtab_ptr = c->xtab.p;
+    c->cache_xtab_valid = p.r16;
+    c->cache_etab_ptr = c->etab.p;
+    c->cache_gtab_ptr = c->gtab.p;
+    c->cache_mf_valid = p.mf;
+}
+
+// Rebuilds on s0 the tables whose key is given (ao_key / lb_key: nullptr for a table that is cached, or that the call
+// does not read).  A rebuild waits for every lane (an older call may still read the old tables) and is announced by
+// `cache_ready`, which every later call's first lane waits for.
+static int refresh_tables(mpsfr_ctx* c, hipStream_t s0, const CallPrep& p, const DevParams& d,
+                          std::vector<unsigned char>* ao_key, const std::vector<double>* lb_key) {
+    if (ao_key || lb_key) {
         for (int k = 0; k < mpsfr_ctx::MAX_LANES; ++k)
             if (c->lane[k].busy && c->lane[k].stream != s0)
                 HIPCHK(hipStreamWaitEvent(s0, lane_end(c, c->lane[k]), 0));
-        if (!ao_cached) {
-            ProfScope ps(c, K_AO_TABLES, s0);
-            if (ly) launch_ao_tables_profile(s0, g, *ly, d_mrec, d_mres, (double*)c->aotab.p);
-            else launch_ao_tables(s0, g, d_mrec, d_mres, (double*)c->aotab.p);
-            c->cache_geom.swap(key);
-            c->last_ntab = ntab;
-            c->cache_ao_ptr = c->aotab.p;
-        }
-        if (!lam_cached) {
-            {
-                ProfScope ps(c, K_GTABLE, s0);
-                launch_gtable(s0, N, nl, d_lp, c->tw64.p, (int*)c->samp_p.p, c->samp_a.p, c->G.p,
-                              c->f64);
-                if (r16)
-                    launch_xtab(s0, N, nl, (const int*)c->samp_p.p, c->samp_a.p, c->tw64.p, c->xtab.p);
-                if (mf) launch_mf_tables(s0, N, nl, d_lp, c->tw64.p, c->etab.p, c->gtab.p);
-            }
-            ProfScope ps(c, K_MOFFAT_KERNELS, s0);
-            if (use_fft_conv) launch_khat(s0, nl, d_gam + ntask, d_alp + ntask, c->kmuse.p, c->f64);
-            else launch_moffat_kernels(s0, nl, d_gam + ntask, d_alp + ntask, c->kmuse.p, c->f64);
-            c->cache_lbda = lb_key;
-            c->cache_lbda_mode = use_fft_conv ? 1 : 0;
-            c->cache_G_ptr = c->G.p;
-            c->cache_kmuse_ptr = c->kmuse.p;
-            c->cache_xtab_ptr = c->xtab.p;
-            c->cache_xtab_valid = r16;
-            c->cache_etab_ptr = c->etab.p;
-            c->cache_gtab_ptr = c->gtab.p;
-            c->cache_mf_valid = mf;
-        }
+        if (ao_key) build_ao_tables(c, s0, p, d, *ao_key);
+        if (lb_key) build_wavelength_tables(c, s0, p, d, *lb_key);
         if (!c->cache_ready) HIPCHK(hipEventCreateWithFlags(&c->cache_ready, hipEventDisableTiming));
         HIPCHK(hipEventRecord(c->cache_ready, s0));
         c->cache_ready_valid = true;
@@ -1678,60 +1910,39 @@ static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) 
         if (hipEventQuery(c->cache_ready) == hipSuccess) c->cache_ready_valid = false;
         else HIPCHK(hipStreamWaitEvent(s0, c->cache_ready, 0));
     }
-    {   // Tip-tilt kernels of this call's tasks (psfrec.py:879-917).  (Measured: moving this small
-        // launch to a side stream, off the head of the call's chain, and folding the DC sum into
-        // the column-transform kernel both LOWER the two-lane throughput, by 2-4 %: the short
-        // serial kernels keep the two lanes out of phase.)
-        // Round 6: in the series form of stage A they are extra workgroups of K_PATCH_ROWS, per chunk (fuse_khat).
-        ProfScope ps(c, K_MOFFAT_KERNELS, s0);
-        if (fuse_khat) ;
-        else if (use_fft_conv) launch_khat(s0, ntask, d_gam, d_alp, sl.ktt.p, c->f64);   // [n][33][64] complex
-        else launch_moffat_kernels(s0, ntask, d_gam, d_alp, sl.ktt.p, c->f64);
-    }
+    return MPSFR_OK;
+}
 
-    // ---- chunk workspaces
-    const size_t per_stamp = (size_t)NS * NS;
-    const int TB = TC * gpp;                // stage-B tasks of a chunk: (task, position) pairs in a field call
-    // Line pruning of the per-wavelength stage (mixed mode): the trailing lines of the OTF half
-    // plane that together weigh less than eps of the PSF peak are neither transformed nor read
-    // by the second pass (stage_a.hip, "Line pruning").
-    const double eps_prune = c->f64 ? c->prune_eps_f64 : c->prune_eps;
-    const bool prune = eps_prune > 0.0;
-    // matrix-core path: half of eps for the lines, half for the 16 x 32 blocks inside them (every
-    // element of a dropped block is below 2^thr_blk; both half planes, all directions)
-    // (ndb: the directions one stamp sums -- a field stamp has one, and the whole budget)
-    const float thr_sum = prune ? (float)((mf ? 0.5 : 1.0) * eps_prune / (2.0 * N * ndb)) : 0.f;
-    float thr_blk = (prune && mf)
-        ? (float)std::log2(0.5 * eps_prune / (2.0 * ndb * 16 * 32 * mf_block_count(N))) : 0.f;
-    // Precision tiers of the matrix-core stage.  The OTF is generated times 2^15, so an element
-    // below 2^-29 of OTF[0][0] has both fp16 halves in the subnormal range: a block whose bound is below
-    // 2^-29.01 carries a few bits per element and is dropped ("floor"); a block below 2^-18.01 runs without
-    // the low half ("mid").  Both are approximations (the matrix cores do not flush subnormals), held to a
-    // budget: per (task, wavelength) the OTF mass each tier leaves out -- an upper bound from the block bounds --
-    // stays below tier_eps / 2 of a lower bound of the PSF peak; K_MF_PREP lowers the thresholds where it
-    // would not.  The kernel for several directions (otf_mfma.hip) has no such pass: its floor is the
-    // per-task floor from K_PEAK_FLOOR (the same budget against the OTF of the shortest wavelength, blocks counted).
-    const float thr_eps = thr_blk;
-    float thr_floor = -1.0e30f;
-    const bool tiers = prune && mf && c->tier_eps > 0.0;
-    // (the kernel for several directions takes a per-task floor under the same budget from K_PEAK_FLOOR)
-    const bool floor_per_task = tiers && c->mf_floor && !mf2 && std::isfinite(c->tier_eps);
-    if (tiers && c->mf_floor) {
-        thr_floor = (float)c->mf_floor_log2;
-        if (!mf2 && !floor_per_task && thr_blk < thr_floor) thr_blk = thr_floor;     // tier_eps = inf: the plain floor
-    }
-    float c2min = 0.f;             // log2-scaled exponent factor of the shortest wavelength (the most negative)
-    for (int l = 0; l < nl; ++l) c2min = std::fmin(c2min, (float)(lp[l].c * 1.44269504088896340736));
-    const float thr_mid = (tiers && c->mf_floor) ? (float)c->mf_mid_log2 : -1.0e30f;
-    const float tier_half = std::isfinite(c->tier_eps) ? (float)(0.5 * c->tier_eps) : 0.f;
-    for (int j = 0; j < NL; ++j) {
-        mpsfr_ctx::Lane& ln = lane_of(j);
-        if ((rc = ensure(c, ln.pre, (size_t)TB * nl * per_stamp * (c->f64 ? 8 : 4)))) return rc;
+// Tip-tilt kernels of this call's tasks (psfrec.py:879-917) into the slot.  (Measured: moving this small
+// launch to a side stream, off the head of the call's chain, and folding the DC sum into
+// the column-transform kernel both LOWER the two-lane throughput, by 2-4 %: the short
+// serial kernels keep the two lanes out of phase.)
+// fused: in the series form of stage A they are extra workgroups of K_PATCH_ROWS, per chunk -- a launch less at the
+// head of a call ("head_fusion" = 0: K_KHAT as a kernel of its own); the timed scope stays, empty.
+static void launch_tiptilt(mpsfr_ctx* c, hipStream_t s0, const CallPrep& p, const DevParams& d, mpsfr_ctx::Slot& sl,
+                           bool fused) {
+    ProfScope ps(c, K_MOFFAT_KERNELS, s0);
+    if (fused) return;
+    if (p.fft_conv) launch_khat(s0, p.ntask, d.gam, d.alp, sl.ktt.p, c->f64);   // [n][33][64] complex
+    else launch_moffat_kernels(s0, p.ntask, d.gam, d.alp, sl.ktt.p, c->f64);
+}
+
+// The workspaces of a lane for chunks of TC tasks, for the stages the call runs on it
+enum : unsigned { STAGE_A = 1, STAGE_B = 2, STAGE_TAIL = 4 };
+
+static int size_lane(mpsfr_ctx* c, mpsfr_ctx::Lane& ln, const CallPrep& p, int TC, unsigned stages, bool band_buf) {
+    int rc;
+    const int N = p.N, H1 = p.H1, nl = p.nl, ndir = p.ndir;
+    const int TB = TC * p.gpp;              // stage-B tasks of a chunk: (task, position) pairs in a field call
+    const size_t per_stamp = kStampPix;
+    const bool prune = p.th.prune;
+    if ((rc = ensure(c, ln.pre, (size_t)TB * nl * per_stamp * (c->f64 ? 8 : 4)))) return rc;
+    if (stages & STAGE_TAIL) {
         if ((rc = ensure(c, ln.fin, (size_t)TB * nl * per_stamp * sizeof(double)))) return rc;
-        if (band && !(dev_out && psf_out) && (rc = ensure(c, ln.band, (size_t)TB * nout * per_stamp * sizeof(double))))
-            return rc;
-        if (io.pre_in) continue;            // convolutions only: no workspace of stages A and B
-        if (series) {
+        if (band_buf && (rc = ensure(c, ln.band, (size_t)TB * p.nout * per_stamp * sizeof(double)))) return rc;
+    }
+    if (stages & STAGE_A) {
+        if (p.series) {
             if ((rc = ensure(c, ln.pP, (size_t)TC * ndir * NAO * NAO * sizeof(double)))) return rc;
             if ((rc = ensure(c, ln.pT, (size_t)TC * ndir * H1 * kNH * 2 * sizeof(double)))) return rc;
             if ((rc = ensure(c, ln.psp, (size_t)TC * ndir * sizeof(double)))) return rc;
@@ -1741,295 +1952,89 @@ static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) 
             if ((rc = ensure(c, ln.C, (size_t)TC * ndir * (N / 2 + NAO / 2) * H1 * 2 * sizeof(double)))) return rc;
             if ((rc = ensure(c, ln.s00, (size_t)TC * ndir * psd_rowfft_groups(N) * sizeof(double)))) return rc;
         }
-        {   // 16 lines of padding behind D: the last m-tile of the matrix-core kernel reads past line
-            // N/2 (where its telescope table is -inf); fresh memory is zeroed so that what it reads
-            // there is always a finite number
-            const size_t cap_before = ln.D0t.cap;       // (a reallocation may return the same address)
-            if ((rc = ensure(c, ln.D0t, ((size_t)TC * ndir * H1 + 16) * N * rsize(c)))) return rc;
-            if (ln.D0t.cap != cap_before) {
-                HIPCHK(hipMemset(ln.D0t.p, 0, ln.D0t.cap));
-                ln.d0t_stale = 0;
-            }
-        }
-        if (!mf && (rc = ensure(c, ln.Tq, (size_t)TB * nl * H1 * NSH * 2 * rsize(c)))) return rc;
-        if (mf2) {
-            if ((rc = ensure(c, ln.mown, mf2_own_bytes(N, TB, nl)))) return rc;
-            if ((rc = ensure(c, ln.muni, mf2_uni_bytes(N, TB, nl)))) return rc;
-            if ((rc = ensure(c, ln.msched, mf2_sched_bytes(N, TB, nl, c->mf_permax)))) return rc;
-            if ((rc = ensure(c, ln.mpart, mf2_part_bytes(N, TB, nl)))) return rc;
-        }
-        if (prune) {
-            if ((rc = ensure(c, ln.dmin, (size_t)TC * ndir * H1 * sizeof(float)))) return rc;
-            if ((rc = ensure(c, ln.dblk, (size_t)ndir * mf_dminb_bytes(N, TC)))) return rc;
-            if (mf && (rc = ensure(c, ln.dminb, mf_dminb_bytes(N, TB)))) return rc;
-            if (mf && (rc = ensure(c, ln.order, (size_t)TB * sizeof(int)))) return rc;
-            if (mf && (rc = ensure(c, ln.thrf, (size_t)TB * sizeof(float)))) return rc;
-            if ((rc = ensure(c, ln.vkeep, (size_t)TB * ((nl + 1) / 2) * sizeof(int)))) return rc;
+    }
+    if (!(stages & (STAGE_A | STAGE_B))) return MPSFR_OK;
+    {   // 16 lines of padding behind D: the last m-tile of the matrix-core kernel reads past line
+        // N/2 (where its telescope table is -inf); fresh memory is zeroed so that what it reads
+        // there is always a finite number
+        const size_t cap_before = ln.D0t.cap;       // (a reallocation may return the same address)
+        if ((rc = ensure(c, ln.D0t, ((size_t)TC * ndir * H1 + 16) * N * rsize(c)))) return rc;
+        if (ln.D0t.cap != cap_before) {
+            HIPCHK(hipMemset(ln.D0t.p, 0, ln.D0t.cap));
+            ln.d0t_stale = 0;
         }
     }
-    // (the sums run over the tasks of [task][gpp x nl] stamps: a field call sums into [npos][nl])
-    // (a band call sums and fits its band stamps: [task][gpp x nband])
-    const int nsum = gpp * nout;
-    if (NL > 1 && (rc = ensure(c, c->lsum, (size_t)NL * nsum * per_stamp * sizeof(double)))) return rc;
-    if ((rc = ensure(c, c->sum, (size_t)nsum * per_stamp * sizeof(double)))) return rc;
-    double* d_fin_all = nullptr;   // [ntask][nl][1600] if the caller gave a device buffer
-    double* d_fit_all = nullptr;
-    if (dev_out && psf_out && !band) d_fin_all = psf_out;
-    if (dev_out && fit_out) {
-        d_fit_all = fit_out;
-    } else {
-        if ((rc = ensure(c, c->fit, (size_t)ntask * gpp * nout * NFIT * sizeof(double)))) return rc;
-        d_fit_all = (double*)c->fit.p;
+    if (!p.mf && (rc = ensure(c, ln.Tq, (size_t)TB * nl * H1 * NSH * 2 * rsize(c)))) return rc;
+    if (p.mf2) {
+        if ((rc = ensure(c, ln.mown, mf2_own_bytes(N, TB, nl)))) return rc;
+        if ((rc = ensure(c, ln.muni, mf2_uni_bytes(N, TB, nl)))) return rc;
+        if ((rc = ensure(c, ln.msched, mf2_sched_bytes(N, TB, nl, c->mf_permax)))) return rc;
+        if ((rc = ensure(c, ln.mpart, mf2_part_bytes(N, TB, nl)))) return rc;
     }
-    const double cfit = fit_constant();
-    const double scale2 = dphi_scale2();
-    double* d_sum = (dev_out && psf_sum_out) ? psf_sum_out : (double*)c->sum.p;
+    if (prune) {
+        if ((rc = ensure(c, ln.dmin, (size_t)TC * ndir * H1 * sizeof(float)))) return rc;
+        if ((rc = ensure(c, ln.dblk, (size_t)ndir * mf_dminb_bytes(N, TC)))) return rc;
+        if (p.mf && (rc = ensure(c, ln.dminb, mf_dminb_bytes(N, TB)))) return rc;
+        if (p.mf && (rc = ensure(c, ln.order, (size_t)TB * sizeof(int)))) return rc;
+        if (p.mf && (rc = ensure(c, ln.thrf, (size_t)TB * sizeof(float)))) return rc;
+        if ((rc = ensure(c, ln.vkeep, (size_t)TB * ((nl + 1) / 2) * sizeof(int)))) return rc;
+    }
+    return MPSFR_OK;
+}
 
-    // the call's tables are produced on its first lane; the other lanes wait for them
-    if (NL > 1) {
+// Where the chunks of a pipeline call write: the caller's device buffers, or the context's
+static int size_outputs(mpsfr_ctx* c, const CallPrep& p, int NL, CallOuts& o) {
+    int rc;
+    if (NL > 1 && (rc = ensure(c, c->lsum, (size_t)NL * p.nsum * kStampPix * sizeof(double)))) return rc;
+    if ((rc = ensure(c, c->sum, (size_t)p.nsum * kStampPix * sizeof(double)))) return rc;
+    o.d_fin_all = (o.dev && o.psf && !p.band) ? o.psf : nullptr;
+    if (o.dev && o.fit) {
+        o.d_fit_all = o.fit;
+    } else {
+        if ((rc = ensure(c, c->fit, (size_t)p.ntask * p.nsum * NFIT * sizeof(double)))) return rc;
+        o.d_fit_all = (double*)c->fit.p;
+    }
+    o.d_sum = (o.dev && o.sum) ? o.sum : (double*)c->sum.p;
+    return MPSFR_OK;
+}
+
+// the call's tables are produced on its first lane; the other lanes wait for them
+static int share_tables(mpsfr_ctx* c, const CallLanes& L) {
+    if (L.NL > 1) {
         if (!c->tables_ready) HIPCHK(hipEventCreateWithFlags(&c->tables_ready, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(c->tables_ready, s0));
-        for (int j = 1; j < NL; ++j) HIPCHK(hipStreamWaitEvent(lane_of(j).stream, c->tables_ready, 0));
+        HIPCHK(hipEventRecord(c->tables_ready, L.at(c, 0).stream));
+        for (int j = 1; j < L.NL; ++j) HIPCHK(hipStreamWaitEvent(L.at(c, j).stream, c->tables_ready, 0));
     }
-    if (io.psd_out) {          // simul_psd_wfm: the PSD of task 0, every direction, as an image
-        const size_t n = (size_t)ndir * N * N;
-        DevBuf img;
-        if ((rc = ensure(c, img, n * sizeof(double)))) return rc;
-        launch_psd_image(s0, N, ndir, tp[0], (const double*)c->aotab.p, cfit, dphi_scale2() * 128.0, (double*)img.p,
-                         mix_of(0));
-        const hipError_t e1 = hipMemcpyAsync(io.psd_out, img.p, n * sizeof(double), hipMemcpyDeviceToHost, s0);
-        const hipError_t e2 = hipStreamSynchronize(s0);
-        release(img);
-        if (e1 != hipSuccess || e2 != hipSuccess) return fail(MPSFR_E_HIP, "copying the PSD image failed");
-        return MPSFR_OK;
-    }
-    // Does this call share the GPU with another lane's kernels?  Then its two persistent kernels leave an eighth of
-    // the CUs free (persist_grid): K_OTF_MFMA2 (136 KB of LDS, 3 x 168 registers per SIMD) and K_DPHI_SERIES (two
-    // waves of 238 registers) admit nothing beside them on a CU they hold, and the other lane's latency-bound
-    // kernels (the patch, K_MF_PREP, K_MF_FINISH) stood parked behind them for 30-50 us (profiles/r05_trace_gaps.txt).
-    // A call that runs alone keeps the whole chip (one lane: -5 % with the reserve).
-    bool lanes_shared = NL > 1;
-    if (!lanes_shared && NLmax > 1 && c->pipeline_calls && (c->reserve_mf < 0 || c->reserve_a < 0))
+    return MPSFR_OK;
+}
+
+// Does this call share the GPU with another lane's kernels?  Then its two persistent kernels leave an eighth of
+// the CUs free (persist_grid): K_OTF_MFMA2 (136 KB of LDS, 3 x 168 registers per SIMD) and K_DPHI_SERIES (two
+// waves of 238 registers) admit nothing beside them on a CU they hold, and the other lane's latency-bound
+// kernels (the patch, K_MF_PREP, K_MF_FINISH) stood parked behind them for 30-50 us (profiles/r05_trace_gaps.txt).
+// A call that runs alone keeps the whole chip (one lane: -5 % with the reserve).
+static bool lanes_are_shared(const mpsfr_ctx* c, const CallLanes& L) {
+    if (L.NL > 1) return true;
+    if (L.NLmax > 1 && c->pipeline_calls && (c->reserve_mf < 0 || c->reserve_a < 0))
         for (int k = 0; k < mpsfr_ctx::MAX_LANES; ++k) {
             const mpsfr_ctx::Lane& o = c->lane[k];
-            if (&o == &lane_of(0) || !o.busy || !o.stream) continue;
-            if ((o.marked ? hipEventQuery(o.done_ev) : hipStreamQuery(o.stream)) != hipSuccess) lanes_shared = true;
+            if (k == L.index(0) || !o.busy || !o.stream) continue;
+            if (!lane_idle(o)) return true;
         }
-    int nchunk_lane[mpsfr_ctx::MAX_LANES] = {0, 0, 0, 0};      // by lane position j in this call
-    int ci = 0;
-    for (int t0 = 0; t0 < ntask; t0 += TC, ++ci) {
-        const int tc = (ntask - t0) < TC ? (ntask - t0) : TC;
-        const int ntd = tc * ndir;
-        const int tb = tc * gpp;            // stage-B tasks of the chunk
-        const int j = ci % NL;
-        mpsfr_ctx::Lane& ln = lane_of(j);
-        hipStream_t ls = ln.stream;
-        const int lane_index = (int)(&ln - c->lane);
-        if (c->stagger_armed && lane_index != c->stagger_lane) {
-            HIPCHK(hipStreamWaitEvent(ls, c->stagger_ev, 0));
-            c->stagger_armed = false;
-        }
-        if (!io.pre_in) {
-            // what an earlier call left in D0t where this one does not write but reads (d0t_stale): cleared once, the
-            // whole buffer, on the lane's stream behind that call's readers.  A run of series calls never comes here.
-            const bool skip_form = series && c->support_skip;
-            if (ln.d0t_stale == 2 || (ln.d0t_stale == 1 && skip_form)) {
-                HIPCHK(hipMemsetAsync(ln.D0t.p, 0, ln.D0t.cap, ls));
-                ln.d0t_stale = 0;
-                ++c->d0t_clears;
-            }
-            if (io.psd_in) ln.d0t_stale = 2;
-            else if (!skip_form && ln.d0t_stale < 1) ln.d0t_stale = 1;
-        }
-        if (io.pre_in) {
-            // convolve_final_psf on the caller's stamps: stages A and B are skipped
-            const size_t n = (size_t)tc * nl * per_stamp;
-            if (c->f64) {
-                HIPCHK(hipMemcpyAsync(ln.pre.p, io.pre_in + (size_t)t0 * nl * per_stamp, n * sizeof(double),
-                                      hipMemcpyHostToDevice, ls));
-                HIPCHK(hipStreamSynchronize(ls));
-            } else {
-                std::vector<float> tmp(n);
-                for (size_t i = 0; i < n; ++i) tmp[i] = (float)io.pre_in[(size_t)t0 * nl * per_stamp + i];
-                HIPCHK(hipMemcpyAsync(ln.pre.p, tmp.data(), n * sizeof(float), hipMemcpyHostToDevice, ls));
-                HIPCHK(hipStreamSynchronize(ls));
-            }
-        } else if (io.psd_in) {
-            // psf_muse on the caller's PSD (one task, ndir planes, centred, in the reference's units)
-            const size_t n = (size_t)ndir * N * N;
-            DevBuf img, cm;
-            if ((rc = ensure(c, img, n * sizeof(double)))) return rc;
-            if ((rc = ensure(c, cm, (size_t)ndir * N * H1 * 2 * sizeof(double)))) { release(img); return rc; }
-            hipError_t e1 = hipMemcpyAsync(img.p, io.psd_in, n * sizeof(double), hipMemcpyHostToDevice, ls);
-            launch_dphi_from_psd(ls, N, ndir, (const double*)img.p, cm.p, 2.0 / 256.0, ln.D0t.p, c->f64, c->tw64.p);
-            if (mf2 && e1 == hipSuccess) e1 = hipMemsetAsync(ln.msched.p, 0, kMfSchedInts * sizeof(int), ls);
-            const hipError_t e2 = hipStreamSynchronize(ls);
-            release(img);
-            release(cm);
-            if (e1 != hipSuccess || e2 != hipSuccess) return fail(MPSFR_E_HIP, "the structure function of the PSD failed");
-        } else if (series) {
-            {
-                ProfScope ps(c, K_PATCH, ls);
-                PatchKhat kh;
-                if (fuse_khat) {
-                    kh.n = tc;
-                    kh.gam = d_gam + t0;
-                    kh.alp = d_alp + t0;
-                    kh.out = (char*)sl.ktt.p + (size_t)t0 * ksz;
-                    kh.f64 = c->f64;
-                }
-                launch_patch(ls, N, ntd, ndir, d_tp + t0, (const double*)c->aotab.p, cfit, c->stwk.p,
-                             (double*)ln.pP.p, ln.pT.p, (double*)ln.psp.p, c->f64, kh, mix_of(t0));
-            }
-            ProfScope ps(c, K_DPHI_SERIES, ls);
-            launch_dphi_series(ls, N, ntd, ndir, d_tp + t0, ln.pT.p, (const double*)ln.psp.p, c->scoef.p,
-                               c->stwk.p, scale2, ln.D0t.p, prune ? (float*)ln.dlin.p : nullptr, c->f64,
-                               mf2 ? (int*)ln.msched.p : nullptr, persist_grid(c, ln, c->reserve_a, lanes_shared),
-                               c->support_skip ? (const unsigned*)c->ssup.p : nullptr);
-        } else {
-            {
-                ProfScope ps(c, K_PSD_ROWFFT, ls);
-                launch_psd_rowfft(ls, N, ntd, ndir, d_tp + t0, (const double*)c->aotab.p, cfit, ln.C.p,
-                                  c->tw64.p, (double*)ln.s00.p, c->f64, mix_of(t0));
-            }
-            ProfScope ps(c, K_COLFFT_DPHI, ls);
-            launch_colfft_dphi(ls, N, ntd, ln.C.p, (const double*)ln.s00.p, scale2, ln.D0t.p,
-                               c->f64, c->tw64.p, mf2 ? (int*)ln.msched.p : nullptr);
-        }
-        auto stagger_here = [&](int which) -> int {
-            if (cold_first && stagger == which) {           // (the first chunk of a call that found every lane idle)
-                if (hipEventRecord(c->stagger_ev, ls) != hipSuccess) return -1;
-                c->stagger_armed = true;
-                c->stagger_lane = lane_index;
-                cold_first = false;
-            }
-            return 0;
-        };
-        if (stagger_here(1)) return fail(MPSFR_E_HIP, "hipEventRecord failed");
-        if (io.pre_in) {
-            // (nothing: the stamps are there)
-        } else if (mf2) {
-            // thin-wave kernel: block minima (one direction: they are the minima over the directions),
-            // then masks and work lists (otf_mfma2.hip); no line bounds needed
-            ProfScope ps(c, K_MF_PREP, ls);
-            // (series form of stage A: the per-line minima go straight to K_MF_PREP, which takes the minimum
-            // over a block's 16 lines itself -- K_DMIN16 was 6 us of latency at 512^2, 13 at 1280^2)
-            const bool from_lines = prune && series && !io.psd_in;
-            if (prune && !from_lines) launch_dmin(ls, N, ntd, ln.D0t.p, (float*)ln.dmin.p, (float*)ln.dblk.p);
-            launch_mf_prep(ls, N, tb, nl, c->mf_permax, d_lp, (prune && !from_lines) ? (const float*)ln.dblk.p : nullptr,
-                           (const float*)c->tlb.p, thr_eps, thr_floor, thr_mid, tier_half, ln.D0t.p, (const float*)c->tl2.p,
-                           ln.mown.p, ln.muni.p, ln.msched.p, from_lines ? (const float*)ln.dlin.p : nullptr);
-        } else if (prune) {
-            ProfScope ps(c, mf ? K_MF_PREP : K_VKEEP, ls);
-            if (series) launch_dmin16(ls, N, ntd, (const float*)ln.dlin.p, (float*)ln.dmin.p, (float*)ln.dblk.p);
-            else launch_dmin(ls, N, ntd, ln.D0t.p, (float*)ln.dmin.p, (float*)ln.dblk.p, c->f64);
-            launch_vkeep(ls, N, tb, ndb, nl, d_lp, (const float*)ln.dmin.p, (const float*)ln.dblk.p,
-                         (const float*)c->tlmax.p, thr_sum, (int*)ln.vkeep.p, c->prune_fixed,
-                         mf ? (float*)ln.dminb.p : nullptr);
-            if (mf) launch_task_order(ls, tb, nl, (const int*)ln.vkeep.p, (int*)ln.order.p);
-        }
-        const int* d_vkeep = prune ? (const int*)ln.vkeep.p : nullptr;
-        if (stagger_here(2)) return fail(MPSFR_E_HIP, "hipEventRecord failed");
-        if (io.pre_in) {
-            // (nothing)
-        } else if (mf2) {
-            // (timed through the dispatch packet of K_OTF_MFMA2 itself: the persistent kernel alone, without
-            // K_MF_FINISH and without marker packets round it)
-            ProfScope ps(c, K_OTF_MFMA, ls, false);
-            launch_otf_mfma2(ls, N, tb, nl, c->mf_permax, persist_grid(c, ln, c->reserve_mf, lanes_shared), ln.D0t.p, (const float*)c->tl2.p, d_lp, c->etab.p,
-                             c->gtab.p, ln.mown.p, ln.muni.p, ln.msched.p, ln.mpart.p, ln.pre.p,
-                             c->mf_clock ? c->mfclk.p : nullptr, ps.a, ps.b);
-        } else if (mf) {
-            ProfScope ps(c, K_OTF_MFMA, ls);
-            if (floor_per_task)
-                launch_peak_floor(ls, N, tb, ndb, ln.D0t.p, (const float*)c->tl2.p, c2min, tier_half, thr_floor,
-                                  (float*)ln.thrf.p);
-            launch_otf_mfma(ls, N, tb, ndb, nl, ln.D0t.p, (const float*)c->tl2.p, d_lp, c->etab.p,
-                            c->gtab.p, d_vkeep, prune ? (const float*)ln.dminb.p : nullptr,
-                            (const float*)c->tlb.p, thr_blk, ln.pre.p,
-                            prune ? (const int*)ln.order.p : nullptr, c->mf_clock ? c->mfclk.p : nullptr,
-                            floor_per_task ? (const float*)ln.thrf.p : nullptr);
-        } else {
-            {
-                ProfScope ps(c, K_OTF_ROWFFT, ls);
-                launch_otf_rowfft(ls, N, tb, ndb, nl, ln.D0t.p, c->tel.p, d_lp,
-                                  (const int*)c->samp_p.p, c->samp_a.p, c->xtab.p, ln.Tq.p, c->tw64.p,
-                                  c->f64, c->fast_exp, d_vkeep);
-            }
-            ProfScope ps(c, K_COLPASS, ls);
-            launch_colpass(ls, N, tb, nl, ln.Tq.p, c->G.p, ln.pre.p, c->f64, d_vkeep);
-        }
-        if (io.stop_pre) {         // psf_muse: the stamps before the convolutions, as float64
-            const size_t n = (size_t)tc * nl * per_stamp;
-            if (c->f64) {
-                HIPCHK(hipMemcpyAsync(psf_out + (size_t)t0 * nl * per_stamp, ln.pre.p, n * sizeof(double),
-                                      hipMemcpyDeviceToHost, ls));
-                HIPCHK(hipStreamSynchronize(ls));
-            } else {
-                std::vector<float> tmp(n);
-                HIPCHK(hipMemcpyAsync(tmp.data(), ln.pre.p, n * sizeof(float), hipMemcpyDeviceToHost, ls));
-                HIPCHK(hipStreamSynchronize(ls));
-                for (size_t i = 0; i < n; ++i) psf_out[(size_t)t0 * nl * per_stamp + i] = (double)tmp[i];
-            }
-            HIPCHK(hipGetLastError());
-            ++nchunk_lane[j];
-            c->last_chunk_tasks = tc;
-            c->last_lane = (L0 + j) % NLmax;
-            continue;
-        }
-        // final stamps: straight into the caller's device buffer (double), else a lane workspace --
-        // float when the FFT convolution produces them and nobody outside reads them
-        // (a band call keeps its per-wavelength stamps in the lane: float in mixed mode)
-        const bool fin_f32 = band ? (use_fft_conv && !c->f64)
-                                  : (use_fft_conv && !c->f64 && !d_fin_all && !(psf_out && !dev_out));
-        void* d_fin = d_fin_all ? (void*)(d_fin_all + (size_t)t0 * nsum * per_stamp) : ln.fin.p;
-        {
-            ProfScope ps(c, K_CONV, ls);
-            const size_t koff = (size_t)t0 * ksz;
-            if (use_fft_conv)
-                launch_conv_fft(ls, tb, nl, ln.pre.p, (const char*)sl.ktt.p + koff,
-                                c->kmuse.p, d_fin, fin_f32, c->f64, gpp);
-            else
-                launch_conv(ls, tb, nl, ln.pre.p, (const char*)sl.ktt.p + koff,
-                            c->kmuse.p, (double*)d_fin, c->f64, gpp);
-        }
-        // a band call: the chunk's stamps reduced over wavelength (timed as the stamp sum); what follows -- fit, sum,
-        // copies -- then reads the double band stamps
-        void* d_res = d_fin;
-        bool res_f32 = fin_f32;
-        if (band) {
-            ProfScope ps(c, K_STAMP_SUM, ls);
-            double* d_band = (dev_out && psf_out) ? psf_out + (size_t)t0 * nsum * per_stamp : (double*)ln.band.p;
-            launch_band_reduce(ls, tb, nl, nout, d_fin, fin_f32, d_bw, d_band);
-            d_res = d_band;
-            res_f32 = false;
-        }
-        // per-lane partial stamp sums in chunk order; combined below in lane order (deterministic)
-        double* lsum = NL > 1 ? (double*)c->lsum.p + (size_t)j * nsum * per_stamp : d_sum;
-        if (fit_out) {             // (with the chunk's stamp sum as the first workgroups of the same launch)
-            ProfScope ps(c, K_FIT, ls);
-            launch_fit(ls, tb * nout, d_res, res_f32, d_fit_all + (size_t)t0 * nsum * NFIT, c->f64,
-                       psf_sum_out ? tc : 0, nsum, psf_sum_out ? lsum : nullptr, nchunk_lane[j] > 0 ? 1 : 0);
-        } else if (psf_sum_out) {
-            ProfScope ps(c, K_STAMP_SUM, ls);
-            launch_stamp_sum(ls, tc, nsum, d_res, res_f32, lsum, nchunk_lane[j] > 0 ? 1 : 0);
-        }
-        HIPCHK(hipGetLastError());
-        if (!dev_out && psf_out) {
-            HIPCHK(hipMemcpyAsync(psf_out + (size_t)t0 * nsum * per_stamp, d_res,
-                                  (size_t)tc * nsum * per_stamp * sizeof(double),
-                                  hipMemcpyDeviceToHost, ls));
-        }
-        ++nchunk_lane[j];
-        c->last_chunk_tasks = tc;
-        c->last_lane = (L0 + j) % NLmax;
-    }
+    return false;
+}
+
+// The end of a call on its lanes, its slot and the join stream: the lanes' markers (none, the slot's or their own:
+// Markers), the outputs they wrote, the sum of the per-lane stamp sums in lane order (d_sum, or nullptr for a call
+// without one)
+static int call_end(mpsfr_ctx* c, const CallLanes& L, mpsfr_ctx::Slot& sl, const Markers& m, const void* const outs[3],
+                    int nsum, double* d_sum) {
     hipStream_t s = c->stream;
-    for (int j = 0; j < NL; ++j) {
-        mpsfr_ctx::Lane& ln = lane_of(j);
-        if (zero) {
+    for (int j = 0; j < L.NL; ++j) {
+        mpsfr_ctx::Lane& ln = L.at(c, j);
+        if (m.zero) {
             ln.marked = false;               // (lane_end records a marker if somebody has to wait for the lane)
-        } else if (lean) {
+        } else if (m.lean) {
             HIPCHK(hipEventRecord(sl.call_done, ln.stream));
             ln.done_ev = sl.call_done;
             ln.marked = true;
@@ -2043,56 +2048,503 @@ static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) 
         for (int a = 0; a < 3; ++a) ln.outs[ln.nouts % mpsfr_ctx::Lane::NHIST][a] = outs[a];
         ln.nouts += 1;
     }
-    if (psf_sum_out && NL > 1) {       // add the per-lane sums in lane order
+    if (d_sum && L.NL > 1) {       // add the per-lane sums in lane order
         {
             ProfScope ps(c, K_STAMP_SUM);
-            launch_stamp_sum(s, NL, nsum, c->lsum.p, false, d_sum, 0);
+            launch_stamp_sum(s, L.NL, nsum, c->lsum.p, false, d_sum, 0);
         }
         if (!c->lsum_done) HIPCHK(hipEventCreateWithFlags(&c->lsum_done, hipEventDisableTiming));
         HIPCHK(hipEventRecord(c->lsum_done, s));
         c->lsum_busy = true;
     }
-    if (!lean) {
+    if (!m.lean) {
         HIPCHK(hipEventRecord(sl.call_done, s));
         if (!c->stream_tail) HIPCHK(hipEventCreateWithFlags(&c->stream_tail, hipEventDisableTiming));
     }
     sl.call_pending = true;
-    sl.last_lane = lean ? (int)(&lane_of(0) - c->lane) : -1;
-    sl.has_event = !zero;
-    c->last_ndir = ndir;
-    c->last_gpp = gpp;
-    c->last_nl = nl;
-    c->last_mf = mf;
-    c->last_mf2 = mf2;
-    c->last_pruned = prune;
-    c->last_dlin = prune && series && !io.pre_in;     // (the series form of stage A wrote its line minima)
-    c->last_thr_blk = thr_blk;
-    c->last_floor_per_task = floor_per_task;
-    c->last_lpc.resize(nl);
-    for (int l = 0; l < nl; ++l) c->last_lpc[l] = lp[l].c;
-    if (tk) {
-        double* h = (double*)tk->host;
-        if (tk->n_psf) HIPCHK(hipMemcpyAsync(h, tk->dpsf.p, tk->n_psf * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (tk->n_sum) HIPCHK(hipMemcpyAsync(h + tk->n_psf, tk->dsum.p, tk->n_sum * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (tk->n_fit)
-            HIPCHK(hipMemcpyAsync(h + tk->n_psf + tk->n_sum, tk->dfit.p, tk->n_fit * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipEventRecord(tk->done, s));
-        tk->id = c->ticket_next++;
-        tk->pending = true;
+    sl.last_lane = m.lean ? L.index(0) : -1;
+    sl.has_event = !m.zero;
+    return MPSFR_OK;
+}
+
+// bookkeeping for debug_fetch.  dlin: the series form of stage A wrote its line minima
+static void remember_call(mpsfr_ctx* c, const CallPrep& p, bool dlin) {
+    c->last_ndir = p.ndir;
+    c->last_gpp = p.gpp;
+    c->last_nl = p.nl;
+    c->last_mf = p.mf;
+    c->last_mf2 = p.mf2;
+    c->last_pruned = p.th.prune;
+    c->last_dlin = dlin;
+    c->last_thr_blk = p.th.thr_blk;
+    c->last_floor_per_task = p.th.floor_per_task;
+    c->last_lpc.resize(p.nl);
+    for (int l = 0; l < p.nl; ++l) c->last_lpc[l] = p.lp[l].c;
+}
+
+// ---- chunk stages: tasks [t0, t0 + tc) of a call on one lane
+
+struct Chunk {
+    int t0, tc;
+    int j;               // position of the lane among the call's lanes
+    bool accumulate;     // the lane has summed a chunk of this call already
+    bool shared;         // the call shares the GPU with another lane's kernels (lanes_are_shared)
+};
+
+// What an earlier call left in D0t where this one does not write but reads (Lane::d0t_stale): cleared once, the whole
+// buffer, on the lane's stream behind that call's readers.  A run of series calls never comes here.  skip_form: the
+// writer is the series form with the support skip; `leaves`: the state the writer leaves behind.
+static int d0t_begin(mpsfr_ctx* c, mpsfr_ctx::Lane& ln, bool skip_form, int leaves) {
+    if (ln.d0t_stale == 2 || (ln.d0t_stale == 1 && skip_form)) {
+        HIPCHK(hipMemsetAsync(ln.D0t.p, 0, ln.D0t.cap, ln.stream));
+        ln.d0t_stale = 0;
+        ++c->d0t_clears;
     }
-    if (!dev_out) {
-        if (fit_out)
-            HIPCHK(hipMemcpyAsync(fit_out, d_fit_all, (size_t)ntask * nsum * NFIT * sizeof(double),
+    if (ln.d0t_stale < leaves) ln.d0t_stale = leaves;
+    return MPSFR_OK;
+}
+
+// Stage A: the structure functions D of the chunk's tasks and directions into the lane's D0t, in the series + patch
+// form or through the full-size transforms.  fuse_khat: the chunk's tip-tilt spectra ride in the patch launch.
+static int stage_a(mpsfr_ctx* c, mpsfr_ctx::Lane& ln, const CallPrep& p, const DevParams& d, const Chunk& ck,
+                   bool fuse_khat) {
+    hipStream_t ls = ln.stream;
+    const int N = p.N, ndir = p.ndir, ntd = ck.tc * ndir, t0 = ck.t0;
+    const bool skip_form = p.series && c->support_skip;
+    if (int rc = d0t_begin(c, ln, skip_form, skip_form ? 0 : 1)) return rc;
+    const double cfit = fit_constant(), scale2 = dphi_scale2();
+    int* msched = p.mf2 ? (int*)ln.msched.p : nullptr;
+    if (p.series) {
+        {
+            ProfScope ps(c, K_PATCH, ls);
+            PatchKhat kh;
+            if (fuse_khat) {
+                kh.n = ck.tc;
+                kh.gam = d.gam + t0;
+                kh.alp = d.alp + t0;
+                kh.out = const_cast<char*>(d.ktt) + (size_t)t0 * p.ksz;
+                kh.f64 = c->f64;
+            }
+            launch_patch(ls, N, ntd, ndir, d.tp + t0, (const double*)c->aotab.p, cfit, c->stwk.p,
+                         (double*)ln.pP.p, ln.pT.p, (double*)ln.psp.p, c->f64, kh, d.mix(t0));
+        }
+        ProfScope ps(c, K_DPHI_SERIES, ls);
+        launch_dphi_series(ls, N, ntd, ndir, d.tp + t0, ln.pT.p, (const double*)ln.psp.p, c->scoef.p,
+                           c->stwk.p, scale2, ln.D0t.p, p.th.prune ? (float*)ln.dlin.p : nullptr, c->f64,
+                           msched, persist_grid(c, ln, c->reserve_a, ck.shared),
+                           c->support_skip ? (const unsigned*)c->ssup.p : nullptr);
+    } else {
+        {
+            ProfScope ps(c, K_PSD_ROWFFT, ls);
+            launch_psd_rowfft(ls, N, ntd, ndir, d.tp + t0, (const double*)c->aotab.p, cfit, ln.C.p,
+                              c->tw64.p, (double*)ln.s00.p, c->f64, d.mix(t0));
+        }
+        ProfScope ps(c, K_COLFFT_DPHI, ls);
+        launch_colfft_dphi(ls, N, ntd, ln.C.p, (const double*)ln.s00.p, scale2, ln.D0t.p,
+                           c->f64, c->tw64.p, msched);
+    }
+    return MPSFR_OK;
+}
+
+// Stage B: its preparation (line and block bounds, masks, work lists) and the per-wavelength stage itself, from the
+// lane's D0t into its `pre` stamps: the thin-wave kernel, the kernel for several directions, or the FFTs.
+// from_lines: stage A's series form left the per-line minima in dlin.
+static int stage_b(mpsfr_ctx* c, mpsfr_ctx::Lane& ln, const CallPrep& p, const DevParams& d, const Chunk& ck,
+                   bool from_lines, CallLanes& L) {
+    hipStream_t ls = ln.stream;
+    const int N = p.N, nl = p.nl, ndb = p.ndb, ntd = ck.tc * p.ndir;
+    const int tb = ck.tc * p.gpp;            // stage-B tasks of the chunk
+    const Thresholds& th = p.th;
+    const bool prune = th.prune;
+    if (p.mf2) {
+        // thin-wave kernel: block minima (one direction: they are the minima over the directions),
+        // then masks and work lists (otf_mfma2.hip); no line bounds needed
+        ProfScope ps(c, K_MF_PREP, ls);
+        // (series form of stage A: the per-line minima go straight to K_MF_PREP, which takes the minimum
+        // over a block's 16 lines itself -- K_DMIN16 was 6 us of latency at 512^2, 13 at 1280^2)
+        const bool lines = prune && from_lines;
+        if (prune && !lines) launch_dmin(ls, N, ntd, ln.D0t.p, (float*)ln.dmin.p, (float*)ln.dblk.p);
+        launch_mf_prep(ls, N, tb, nl, c->mf_permax, d.lp, (prune && !lines) ? (const float*)ln.dblk.p : nullptr,
+                       (const float*)c->tlb.p, th.thr_eps, th.thr_floor, th.thr_mid, th.tier_half, ln.D0t.p,
+                       (const float*)c->tl2.p, ln.mown.p, ln.muni.p, ln.msched.p,
+                       lines ? (const float*)ln.dlin.p : nullptr);
+    } else if (prune) {
+        ProfScope ps(c, p.mf ? K_MF_PREP : K_VKEEP, ls);
+        if (from_lines) launch_dmin16(ls, N, ntd, (const float*)ln.dlin.p, (float*)ln.dmin.p, (float*)ln.dblk.p);
+        else launch_dmin(ls, N, ntd, ln.D0t.p, (float*)ln.dmin.p, (float*)ln.dblk.p, c->f64);
+        launch_vkeep(ls, N, tb, ndb, nl, d.lp, (const float*)ln.dmin.p, (const float*)ln.dblk.p,
+                     (const float*)c->tlmax.p, th.thr_sum, (int*)ln.vkeep.p, c->prune_fixed,
+                     p.mf ? (float*)ln.dminb.p : nullptr);
+        if (p.mf) launch_task_order(ls, tb, nl, (const int*)ln.vkeep.p, (int*)ln.order.p);
+    }
+    const int* d_vkeep = prune ? (const int*)ln.vkeep.p : nullptr;
+    if (int rc = stagger_here(c, L, 2, ln)) return rc;
+    if (p.mf2) {
+        // (timed through the dispatch packet of K_OTF_MFMA2 itself: the persistent kernel alone, without
+        // K_MF_FINISH and without marker packets round it)
+        ProfScope ps(c, K_OTF_MFMA, ls, false);
+        launch_otf_mfma2(ls, N, tb, nl, c->mf_permax, persist_grid(c, ln, c->reserve_mf, ck.shared), ln.D0t.p,
+                         (const float*)c->tl2.p, d.lp, c->etab.p, c->gtab.p, ln.mown.p, ln.muni.p, ln.msched.p,
+                         ln.mpart.p, ln.pre.p, c->mf_clock ? c->mfclk.p : nullptr, ps.a, ps.b);
+    } else if (p.mf) {
+        ProfScope ps(c, K_OTF_MFMA, ls);
+        if (th.floor_per_task)
+            launch_peak_floor(ls, N, tb, ndb, ln.D0t.p, (const float*)c->tl2.p, th.c2min, th.tier_half, th.thr_floor,
+                              (float*)ln.thrf.p);
+        launch_otf_mfma(ls, N, tb, ndb, nl, ln.D0t.p, (const float*)c->tl2.p, d.lp, c->etab.p,
+                        c->gtab.p, d_vkeep, prune ? (const float*)ln.dminb.p : nullptr,
+                        (const float*)c->tlb.p, th.thr_blk, ln.pre.p,
+                        prune ? (const int*)ln.order.p : nullptr, c->mf_clock ? c->mfclk.p : nullptr,
+                        th.floor_per_task ? (const float*)ln.thrf.p : nullptr);
+    } else {
+        {
+            ProfScope ps(c, K_OTF_ROWFFT, ls);
+            launch_otf_rowfft(ls, N, tb, ndb, nl, ln.D0t.p, c->tel.p, d.lp,
+                              (const int*)c->samp_p.p, c->samp_a.p, c->xtab.p, ln.Tq.p, c->tw64.p,
+                              c->f64, c->fast_exp, d_vkeep);
+        }
+        ProfScope ps(c, K_COLPASS, ls);
+        launch_colpass(ls, N, tb, nl, ln.Tq.p, c->G.p, ln.pre.p, c->f64, d_vkeep);
+    }
+    return MPSFR_OK;
+}
+
+// The tail: the two convolutions of the lane's `pre` stamps, the band reduction of a band call, the fit with the
+// chunk's stamp sum (or the sum alone), the copy of host stamps.  NL: the lanes of the call (several: the lane sums
+// into its own partial sum).
+static int chunk_tail(mpsfr_ctx* c, mpsfr_ctx::Lane& ln, const CallPrep& p, const DevParams& d, const CallOuts& o,
+                      const Chunk& ck, int NL) {
+    hipStream_t ls = ln.stream;
+    const int nl = p.nl, nsum = p.nsum, t0 = ck.t0, tc = ck.tc;
+    const int tb = tc * p.gpp;
+    const size_t per_stamp = kStampPix;
+    // final stamps: straight into the caller's device buffer (double), else a lane workspace --
+    // float when the FFT convolution produces them and nobody outside reads them
+    // (a band call keeps its per-wavelength stamps in the lane: float in mixed mode)
+    const bool fin_f32 = p.band ? (p.fft_conv && !c->f64)
+                                : (p.fft_conv && !c->f64 && !o.d_fin_all && !(o.psf && !o.dev));
+    void* d_fin = o.d_fin_all ? (void*)(o.d_fin_all + (size_t)t0 * nsum * per_stamp) : ln.fin.p;
+    {
+        ProfScope ps(c, K_CONV, ls);
+        const char* ktt = d.ktt + (size_t)t0 * p.ksz;
+        if (p.fft_conv) launch_conv_fft(ls, tb, nl, ln.pre.p, ktt, c->kmuse.p, d_fin, fin_f32, c->f64, p.gpp);
+        else launch_conv(ls, tb, nl, ln.pre.p, ktt, c->kmuse.p, (double*)d_fin, c->f64, p.gpp);
+    }
+    // a band call: the chunk's stamps reduced over wavelength (timed as the stamp sum); what follows -- fit, sum,
+    // copies -- then reads the double band stamps
+    void* d_res = d_fin;
+    bool res_f32 = fin_f32;
+    if (p.band) {
+        ProfScope ps(c, K_STAMP_SUM, ls);
+        double* d_band = (o.dev && o.psf) ? o.psf + (size_t)t0 * nsum * per_stamp : (double*)ln.band.p;
+        launch_band_reduce(ls, tb, nl, p.nout, d_fin, fin_f32, d.bw, d_band);
+        d_res = d_band;
+        res_f32 = false;
+    }
+    // per-lane partial stamp sums in chunk order; combined in lane order by call_end (deterministic)
+    double* lsum = !o.sum ? nullptr : NL > 1 ? (double*)c->lsum.p + (size_t)ck.j * nsum * per_stamp : o.d_sum;
+    if (o.fit) {               // (with the chunk's stamp sum as the first workgroups of the same launch)
+        ProfScope ps(c, K_FIT, ls);
+        launch_fit(ls, tb * p.nout, d_res, res_f32, o.d_fit_all + (size_t)t0 * nsum * NFIT, c->f64,
+                   o.sum ? tc : 0, nsum, o.sum ? lsum : nullptr, ck.accumulate ? 1 : 0);
+    } else if (o.sum) {
+        ProfScope ps(c, K_STAMP_SUM, ls);
+        launch_stamp_sum(ls, tc, nsum, d_res, res_f32, lsum, ck.accumulate ? 1 : 0);
+    }
+    HIPCHK(hipGetLastError());
+    if (!o.dev && o.psf) {
+        HIPCHK(hipMemcpyAsync(o.psf + (size_t)t0 * nsum * per_stamp, d_res,
+                              (size_t)tc * nsum * per_stamp * sizeof(double), hipMemcpyDeviceToHost, ls));
+    }
+    return MPSFR_OK;
+}
+
+// The chunks of a call in order over its lanes: run(lane, chunk) queues one
+extern "C++" template <class Run>
+static int for_each_chunk(mpsfr_ctx* c, int ntask, const CallLanes& L, bool shared, Run&& run) {
+    int nchunk_lane[mpsfr_ctx::MAX_LANES] = {0, 0, 0, 0};      // by lane position j in this call
+    int ci = 0;
+    for (int t0 = 0; t0 < ntask; t0 += L.TC, ++ci) {
+        const int j = ci % L.NL;
+        const Chunk ck = {t0, (ntask - t0) < L.TC ? (ntask - t0) : L.TC, j, nchunk_lane[j] > 0, shared};
+        mpsfr_ctx::Lane& ln = L.at(c, j);
+        int rc;
+        if ((rc = stagger_wait(c, ln))) return rc;
+        if ((rc = run(ln, ck))) return rc;
+        ++nchunk_lane[j];
+        c->last_chunk_tasks = ck.tc;
+        c->last_lane = L.index(j);
+    }
+    return MPSFR_OK;
+}
+
+// ---- the drivers
+
+// The pipeline: every stamp, sum and fit of mpsfr_reconstruct, _field, _band, _profile and _multi*.
+// (refuses) marks the steps that may refuse the call for its arguments; everything after them only fails with the GPU.
+static int reconstruct_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io) {
+    HostClock clock;
+    CallPrep p;
+    int rc;
+    if ((rc = prepare_call(c, a, io, p))) return rc;                      // (refuses)  pure host
+    HIPCHK(hipSetDevice(c->device));
+    // context state: ticket, lanes, slot
+    CallOuts o;
+    o.psf = a.psf_out, o.sum = a.psf_sum_out, o.fit = a.fit_out, o.dev = a.on_device != 0;
+    mpsfr_ctx::Ticket* tk = nullptr;
+    if (a.on_device == 2 && (rc = ticket_begin(c, p, o, tk))) return rc;
+    const bool pipelined = c->pipeline_calls && o.dev;     // (else a synchronous call: no neighbour on another lane)
+    CallLanes L;
+    if ((rc = lanes_begin(c, p.ntask, pipeline_chunk_tasks(c, p, !pipelined), pipelined, L))) return rc;
+    const Markers marks(c, o.dev, tk != nullptr, L.NL);
+    hipStream_t s0 = L.at(c, 0).stream;        // the call's tables are produced on its first lane
+    std::vector<unsigned char> ao_key = ao_cache_key(p.g, p.ly, a.mask_rec, a.mask_res);
+    bool ao_cached = false, lam_cached = false;
+    if ((rc = size_ao_tables(c, p, ao_key, ao_cached))) return rc;
+    const Blob blob(p, a.mask_rec && !ao_cached);
+    mpsfr_ctx::Slot* sl = nullptr;
+    if ((rc = slot_acquire(c, blob.bytes, (size_t)p.ntask * p.ksz, sl, clock.blocked))) return rc;
+    blob.fill(sl->host, p, a.mask_rec, a.mask_res);
+    // queueing: waits, parameters, tables
+    const void* outs[3] = {o.dev ? (const void*)o.psf : nullptr, o.dev ? (const void*)o.sum : nullptr,
+                           o.dev ? (const void*)o.fit : nullptr};
+    if ((rc = queue_call_waits(c, L, *sl, outs))) return rc;
+    const std::vector<double> lb_key(a.lbda_nm, a.lbda_nm + a.nl);
+    if ((rc = size_wavelength_tables(c, p, lb_key, lam_cached))) return rc;
+    if ((rc = send_params(c, *sl, s0, blob.bytes, marks))) return rc;
+    const DevParams d = blob.views(*sl, p);
+    if ((rc = refresh_tables(c, s0, p, d, ao_cached ? nullptr : &ao_key, lam_cached ? nullptr : &lb_key))) return rc;
+    const bool fuse_khat = c->head_fusion && p.series && p.fft_conv;
+    launch_tiptilt(c, s0, p, d, *sl, fuse_khat);
+    // workspaces
+    for (int j = 0; j < L.NL; ++j)
+        if ((rc = size_lane(c, L.at(c, j), p, L.TC, STAGE_A | STAGE_B | STAGE_TAIL, p.band && !(o.dev && o.psf))))
+            return rc;
+    if ((rc = size_outputs(c, p, L.NL, o))) return rc;
+    if ((rc = share_tables(c, L))) return rc;
+    // the chunks
+    rc = for_each_chunk(c, p.ntask, L, lanes_are_shared(c, L), [&](mpsfr_ctx::Lane& ln, const Chunk& ck) {
+        int r;
+        if ((r = stage_a(c, ln, p, d, ck, fuse_khat))) return r;
+        if ((r = stagger_here(c, L, 1, ln))) return r;
+        if ((r = stage_b(c, ln, p, d, ck, p.th.prune && p.series, L))) return r;
+        return chunk_tail(c, ln, p, d, o, ck, L.NL);
+    });
+    if (rc) return rc;
+    // the end: markers, lane sum, slot; results to the host
+    if ((rc = call_end(c, L, *sl, marks, outs, p.nsum, o.sum ? o.d_sum : nullptr))) return rc;
+    remember_call(c, p, p.th.prune && p.series);
+    if (tk && (rc = ticket_finish(c, tk))) return rc;
+    if (!o.dev) {
+        hipStream_t s = c->stream;
+        if (o.fit)
+            HIPCHK(hipMemcpyAsync(o.fit, o.d_fit_all, (size_t)p.ntask * p.nsum * NFIT * sizeof(double),
                                   hipMemcpyDeviceToHost, s));
-        if (psf_sum_out)
-            HIPCHK(hipMemcpyAsync(psf_sum_out, d_sum, (size_t)nsum * per_stamp * sizeof(double),
-                                  hipMemcpyDeviceToHost, s));
+        if (o.sum)
+            HIPCHK(hipMemcpyAsync(o.sum, o.d_sum, (size_t)p.nsum * kStampPix * sizeof(double), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
     }
-    // host cost of queueing the call: not the time spent waiting for the GPU to catch up
-    c->host_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_enter).count() - t_blocked;
-    c->host_calls += 1;
+    clock.finish(c);
     return MPSFR_OK;
+}
+
+// A device buffer that lives as long as a stage-level driver's call, released on every path out of it
+struct ScopedBuf : DevBuf {
+    ~ScopedBuf() { release(*this); }
+};
+
+// What the stage-level drivers share with the pipeline at their head: lanes for chunks of `chunk_tasks` tasks, a slot,
+// the call's waits, the parameters on their way, the cached tables the call reads (`tables`) and the tip-tilt
+// spectra.  Synchronous host-buffer calls: they join, and they name no device outputs.
+enum : unsigned { TABLES_AO = 1, TABLES_WAVELENGTH = 2 };
+static const void* const kNoOuts[3] = {nullptr, nullptr, nullptr};
+
+struct StageCall {
+    CallLanes L;
+    mpsfr_ctx::Slot* sl = nullptr;
+    hipStream_t s0 = nullptr;
+    DevParams d;
+};
+
+static int stage_call_begin(mpsfr_ctx* c, const CallPrep& p, const CallArgs& a, int chunk_tasks, unsigned tables,
+                            HostClock& clock, StageCall& sc) {
+    int rc;
+    std::vector<unsigned char> ao_key;
+    bool ao_cached = true, lam_cached = true;
+    if (tables & TABLES_AO) {
+        ao_key = ao_cache_key(p.g, p.ly, a.mask_rec, a.mask_res);
+        if ((rc = size_ao_tables(c, p, ao_key, ao_cached))) return rc;
+    }
+    const Blob blob(p, a.mask_rec && !ao_cached);
+    if ((rc = lanes_begin(c, p.ntask, chunk_tasks, false, sc.L))) return rc;
+    sc.s0 = sc.L.at(c, 0).stream;
+    if ((rc = slot_acquire(c, blob.bytes, (size_t)p.ntask * p.ksz, sc.sl, clock.blocked))) return rc;
+    blob.fill(sc.sl->host, p, a.mask_rec, a.mask_res);
+    if ((rc = queue_call_waits(c, sc.L, *sc.sl, kNoOuts))) return rc;
+    const std::vector<double> lb_key(a.lbda_nm, a.lbda_nm + a.nl);
+    if ((tables & TABLES_WAVELENGTH) && (rc = size_wavelength_tables(c, p, lb_key, lam_cached))) return rc;
+    if ((rc = send_params(c, *sc.sl, sc.s0, blob.bytes, Markers(c, false, false, sc.L.NL)))) return rc;
+    sc.d = blob.views(*sc.sl, p);
+    if ((rc = refresh_tables(c, sc.s0, p, sc.d, ao_cached ? nullptr : &ao_key, lam_cached ? nullptr : &lb_key))) return rc;
+    launch_tiptilt(c, sc.s0, p, sc.d, *sc.sl, false);
+    return MPSFR_OK;
+}
+
+// ... and at their end: the lanes' markers, the slot, `last_*`, the join stream drained
+static int stage_call_end(mpsfr_ctx* c, const CallPrep& p, StageCall& sc, const HostClock& clock) {
+    if (int rc = call_end(c, sc.L, *sc.sl, Markers(c, false, false, sc.L.NL), kNoOuts, p.nsum, nullptr)) return rc;
+    remember_call(c, p, false);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    clock.finish(c);
+    return MPSFR_OK;
+}
+
+// Stamps between the host's doubles and a lane's `pre` (float in mixed mode), n values, synchronously
+static int copy_pre(mpsfr_ctx* c, mpsfr_ctx::Lane& ln, const double* in, double* out, size_t n) {
+    hipStream_t ls = ln.stream;
+    if (c->f64) {
+        if (in) HIPCHK(hipMemcpyAsync(ln.pre.p, in, n * sizeof(double), hipMemcpyHostToDevice, ls));
+        else HIPCHK(hipMemcpyAsync(out, ln.pre.p, n * sizeof(double), hipMemcpyDeviceToHost, ls));
+        HIPCHK(hipStreamSynchronize(ls));
+        return MPSFR_OK;
+    }
+    std::vector<float> tmp(n);
+    if (in) {
+        for (size_t i = 0; i < n; ++i) tmp[i] = (float)in[i];
+        HIPCHK(hipMemcpyAsync(ln.pre.p, tmp.data(), n * sizeof(float), hipMemcpyHostToDevice, ls));
+        HIPCHK(hipStreamSynchronize(ls));
+    } else {
+        HIPCHK(hipMemcpyAsync(tmp.data(), ln.pre.p, n * sizeof(float), hipMemcpyDeviceToHost, ls));
+        HIPCHK(hipStreamSynchronize(ls));
+        for (size_t i = 0; i < n; ++i) out[i] = (double)tmp[i];
+    }
+    return MPSFR_OK;
+}
+
+// simul_psd_wfm: the PSD of task 0, every direction, as an image.  Parameters up, AO tables, the image, copy out.
+// Nothing of it stays in flight, so it leaves the lane and the slot unmarked (and its host time uncounted).
+static int simul_psd_impl(mpsfr_ctx* c, const CallArgs& a, const StageIO& io, double* psd_out) {
+    HostClock clock;
+    CallPrep p;
+    int rc;
+    if ((rc = call_shape(c, a, io, p))) return rc;                        // (refuses)
+    if ((rc = wavelength_scalars(c, a, false, p))) return rc;             // (the placeholder wavelength)
+    if ((rc = task_scalars(c, a, io, p))) return rc;                      // (refuses)
+    p.g = ao_geometry(a, io, p.ndir);
+    HIPCHK(hipSetDevice(c->device));
+    StageCall sc;
+    if ((rc = stage_call_begin(c, p, a, p.ntask, TABLES_AO, clock, sc))) return rc;
+    const size_t n = (size_t)p.ndir * p.N * p.N;
+    ScopedBuf img;
+    if ((rc = ensure(c, img, n * sizeof(double)))) return rc;
+    launch_psd_image(sc.s0, p.N, p.ndir, p.tp[0], (const double*)c->aotab.p, fit_constant(), dphi_scale2() * 128.0,
+                     (double*)img.p, sc.d.mix(0));
+    const hipError_t e1 = hipMemcpyAsync(psd_out, img.p, n * sizeof(double), hipMemcpyDeviceToHost, sc.s0);
+    const hipError_t e2 = hipStreamSynchronize(sc.s0);
+    if (e1 != hipSuccess || e2 != hipSuccess) return fail(MPSFR_E_HIP, "copying the PSD image failed");
+    return MPSFR_OK;
+}
+
+// psf_muse on the caller's PSD (one task, ndir planes, centred, in the reference's units): wavelength tables, the
+// structure function of the PSD into a lane's D0t, stage B, and the stamps before the convolutions out as float64.
+// The caller's PSD may leave anything in D0t (d0t_stale 2): the next call that writes it clears it first.
+static int psf_from_psd_impl(mpsfr_ctx* c, const CallArgs& a, const double* psd_in) {
+    HostClock clock;
+    CallPrep p;
+    int rc;
+    if ((rc = call_shape(c, a, StageIO(), p))) return rc;                 // (refuses)
+    if ((rc = wavelength_scalars(c, a, true, p))) return rc;              // (refuses)
+    if ((rc = task_scalars(c, a, StageIO(), p))) return rc;               // (the placeholder row)
+    p.series = false;
+    stage_b_paths(c, p);
+    HIPCHK(hipSetDevice(c->device));
+    StageCall sc;
+    if ((rc = stage_call_begin(c, p, a, p.ntask, TABLES_WAVELENGTH, clock, sc))) return rc;
+    if ((rc = size_lane(c, sc.L.at(c, 0), p, sc.L.TC, STAGE_B, false))) return rc;
+    rc = for_each_chunk(c, p.ntask, sc.L, lanes_are_shared(c, sc.L), [&](mpsfr_ctx::Lane& ln, const Chunk& ck) {
+        int r;
+        hipStream_t ls = ln.stream;
+        const int N = p.N, ndir = p.ndir;
+        const size_t n = (size_t)ndir * N * N;
+        if ((r = d0t_begin(c, ln, false, 2))) return r;
+        {
+            ScopedBuf img, cm;
+            if ((r = ensure(c, img, n * sizeof(double)))) return r;
+            if ((r = ensure(c, cm, (size_t)ndir * N * p.H1 * 2 * sizeof(double)))) return r;
+            hipError_t e1 = hipMemcpyAsync(img.p, psd_in, n * sizeof(double), hipMemcpyHostToDevice, ls);
+            launch_dphi_from_psd(ls, N, ndir, (const double*)img.p, cm.p, 2.0 / 256.0, ln.D0t.p, c->f64, c->tw64.p);
+            if (p.mf2 && e1 == hipSuccess) e1 = hipMemsetAsync(ln.msched.p, 0, kMfSchedInts * sizeof(int), ls);
+            const hipError_t e2 = hipStreamSynchronize(ls);
+            if (e1 != hipSuccess || e2 != hipSuccess) return fail(MPSFR_E_HIP, "the structure function of the PSD failed");
+        }
+        if ((r = stagger_here(c, sc.L, 1, ln))) return r;
+        if ((r = stage_b(c, ln, p, sc.d, ck, false, sc.L))) return r;
+        if ((r = copy_pre(c, ln, nullptr, a.psf_out, (size_t)ck.tc * p.nl * kStampPix))) return r;
+        HIPCHK(hipGetLastError());
+        return MPSFR_OK;
+    });
+    if (rc) return rc;
+    return stage_call_end(c, p, sc, clock);
+}
+
+// convolve_final_psf on the caller's stamps: wavelength tables and tip-tilt spectra, the stamps into a lane per
+// chunk, the tail.  It needs none of the workspaces of stages A and B and leaves D0t alone; its host copies are per
+// chunk, so it keeps the chunking of a call's stamps.
+static int convolve_stamps_impl(mpsfr_ctx* c, const CallArgs& a, const double* pre_in) {
+    HostClock clock;
+    CallPrep p;
+    int rc;
+    if ((rc = call_shape(c, a, StageIO(), p))) return rc;                 // (refuses)
+    if ((rc = wavelength_scalars(c, a, false, p))) return rc;             // (refuses)
+    if ((rc = task_scalars(c, a, StageIO(), p))) return rc;               // (refuses)
+    stage_b_paths(c, p);                 // (which tables ride with the wavelengths' cache; last_* as a pipeline call)
+    HIPCHK(hipSetDevice(c->device));
+    const int nlanes = c->nlanes == 0 ? 2 : c->nlanes;
+    const int TC = c->chunk_tasks > 0 ? c->chunk_tasks : auto_chunk_tasks(p.ntask, p.nl, 0.0, nlanes, true);
+    StageCall sc;
+    if ((rc = stage_call_begin(c, p, a, TC, TABLES_WAVELENGTH, clock, sc))) return rc;
+    for (int j = 0; j < sc.L.NL; ++j)
+        if ((rc = size_lane(c, sc.L.at(c, j), p, sc.L.TC, STAGE_TAIL, false))) return rc;
+    if ((rc = share_tables(c, sc.L))) return rc;
+    CallOuts o;
+    o.psf = a.psf_out;
+    rc = for_each_chunk(c, p.ntask, sc.L, false, [&](mpsfr_ctx::Lane& ln, const Chunk& ck) {
+        int r;
+        const size_t first = (size_t)ck.t0 * p.nl * kStampPix;
+        if ((r = copy_pre(c, ln, pre_in + first, nullptr, (size_t)ck.tc * p.nl * kStampPix))) return r;
+        if ((r = stagger_here(c, sc.L, 1, ln)) || (r = stagger_here(c, sc.L, 2, ln))) return r;
+        return chunk_tail(c, ln, p, sc.d, o, ck, sc.L.NL);
+    });
+    if (rc) return rc;
+    return stage_call_end(c, p, sc, clock);
+}
+
+// The checks the multi-context calls share: the contexts are there, and ...
+static int check_multi(mpsfr_ctx* const* ctxs, int nctx, int ntask, int nl) {
+    if (!ctxs || nctx < 1) return fail(MPSFR_E_INVALID, "need at least one context");
+    for (int k = 0; k < nctx; ++k)
+        if (!ctxs[k]) return fail(MPSFR_E_INVALID, "context %d is NULL", k);
+    if (ntask < 1 || nl < 1) return fail(MPSFR_E_INVALID, "ntask and nl must be positive");
+    return MPSFR_OK;
+}
+
+// ... they are alike
+static int check_multi_alike(mpsfr_ctx* const* ctxs, int nctx) {
+    for (int k = 1; k < nctx; ++k)
+        if (ctxs[k]->dimpsf != ctxs[0]->dimpsf || ctxs[k]->N != ctxs[0]->N || ctxs[k]->prec != ctxs[0]->prec ||
+            ctxs[k]->pixscale != ctxs[0]->pixscale)
+            return fail(MPSFR_E_INVALID, "the contexts must share dim, dimpsf, pixscale and precision "
+                                         "(context %d differs from context 0)", k);
+    return MPSFR_OK;
+}
+
+// Contiguous, balanced row shards over `used` contexts: start[k] .. start[k + 1], the first ntask % used one row more
+// (start has nctx + 1 entries: the contexts beyond `used` get no rows)
+static std::vector<int> shard_bounds(int ntask, int nctx, int used) {
+    std::vector<int> start(nctx + 1, ntask);
+    start[0] = 0;
+    for (int k = 0; k < used; ++k) start[k + 1] = start[k] + ntask / used + (k < ntask % used ? 1 : 0);
+    return start;
 }
 
 // Row shards over several contexts (one per device), one host thread each.
@@ -2101,22 +2553,13 @@ int mpsfr_reconstruct_multi(mpsfr_ctx* const* ctxs, int nctx, int ntask, const d
                             const double h[2], double wind_speed, int npsflin, int nl,
                             const double* lbda_nm, const uint8_t* mask_rec, const uint8_t* mask_res,
                             double* psf_out, double* psf_sum_out, double* fit_out) {
-    if (!ctxs || nctx < 1) return fail(MPSFR_E_INVALID, "need at least one context");
-    for (int k = 0; k < nctx; ++k)
-        if (!ctxs[k]) return fail(MPSFR_E_INVALID, "context %d is NULL", k);
-    if (ntask < 1 || nl < 1) return fail(MPSFR_E_INVALID, "ntask and nl must be positive");
+    if (int rc = check_multi(ctxs, nctx, ntask, nl)) return rc;
     if (nctx == 1 || ntask < nctx)
         return mpsfr_reconstruct(ctxs[0], ntask, seeing, gl, l0, three_lgs, h, wind_speed, npsflin, nl,
                                  lbda_nm, mask_rec, mask_res, psf_out, psf_sum_out, fit_out, 0);
     const size_t per_stamp = (size_t)ctxs[0]->dimpsf * ctxs[0]->dimpsf;
-    for (int k = 1; k < nctx; ++k)
-        if (ctxs[k]->dimpsf != ctxs[0]->dimpsf || ctxs[k]->N != ctxs[0]->N || ctxs[k]->prec != ctxs[0]->prec ||
-            ctxs[k]->pixscale != ctxs[0]->pixscale)
-            return fail(MPSFR_E_INVALID, "the contexts must share dim, dimpsf, pixscale and precision "
-                                         "(context %d differs from context 0)", k);
-    // contiguous, balanced shards: the first ntask % nctx contexts get one row more
-    std::vector<int> start(nctx + 1, 0);
-    for (int k = 0; k < nctx; ++k) start[k + 1] = start[k] + ntask / nctx + (k < ntask % nctx ? 1 : 0);
+    if (int rc = check_multi_alike(ctxs, nctx)) return rc;
+    const std::vector<int> start = shard_bounds(ntask, nctx, nctx);
     std::vector<std::vector<double>> sums(psf_sum_out ? nctx : 0);
     for (auto& v : sums) v.resize((size_t)nl * per_stamp);
     std::vector<int> rcs(nctx, MPSFR_OK);
@@ -2150,22 +2593,13 @@ int mpsfr_reconstruct_multi_async(mpsfr_ctx* const* ctxs, int nctx, int ntask, c
                                   const double h[2], double wind_speed, int npsflin, int nl,
                                   const double* lbda_nm, const uint8_t* mask_rec, const uint8_t* mask_res,
                                   double* psf_out, double* psf_sum_out, double* fit_out) {
-    if (!ctxs || nctx < 1) return fail(MPSFR_E_INVALID, "need at least one context");
-    for (int k = 0; k < nctx; ++k)
-        if (!ctxs[k]) return fail(MPSFR_E_INVALID, "context %d is NULL", k);
-    if (ntask < 1 || nl < 1) return fail(MPSFR_E_INVALID, "ntask and nl must be positive");
+    if (int rc = check_multi(ctxs, nctx, ntask, nl)) return rc;
     mpsfr_ctx::Multi& m = ctxs[0]->multi;
     if (m.pending) return fail(MPSFR_E_INVALID, "a multi-context call is pending on this context: mpsfr_wait_multi first");
-    for (int k = 1; k < nctx; ++k)
-        if (ctxs[k]->dimpsf != ctxs[0]->dimpsf || ctxs[k]->N != ctxs[0]->N || ctxs[k]->prec != ctxs[0]->prec ||
-            ctxs[k]->pixscale != ctxs[0]->pixscale)
-            return fail(MPSFR_E_INVALID, "the contexts must share dim, dimpsf, pixscale and precision "
-                                         "(context %d differs from context 0)", k);
+    if (int rc = check_multi_alike(ctxs, nctx)) return rc;
     const size_t per_stamp = (size_t)ctxs[0]->dimpsf * ctxs[0]->dimpsf;
     const int used = ntask < nctx ? 1 : nctx;            // (like the blocking form: too few rows go to context 0)
-    std::vector<int> start(nctx + 1, 0);
-    for (int k = 0; k < nctx; ++k)
-        start[k + 1] = used == 1 ? ntask : start[k] + ntask / nctx + (k < ntask % nctx ? 1 : 0);
+    const std::vector<int> start = shard_bounds(ntask, nctx, used);
     m.nctx = nctx;
     m.n = (size_t)nl * per_stamp;
     m.user_sum = psf_sum_out;
@@ -2243,13 +2677,11 @@ int mpsfr_simul_psd(mpsfr_ctx* c, double seeing, double gl, double l0, int three
                     double* psd_out) {
     if (!c || !psd_out) return fail(MPSFR_E_INVALID, "NULL argument");
     const uint8_t t3 = three_lgs ? 1 : 0;
-    StageIO io;
-    io.psd_out = psd_out;
     CallArgs a;
     a.seeing = &seeing, a.gl = &gl, a.l0 = &l0, a.three_lgs = &t3;
     a.h = h, a.wind_speed = wind_speed, a.npsflin = npsflin;
     a.mask_rec = mask_rec, a.mask_res = mask_res;
-    return guarded_call(c, a, io);
+    return guarded(c, [&] { return simul_psd_impl(c, a, StageIO(), psd_out); });
 }
 
 int mpsfr_psf_from_psd(mpsfr_ctx* c, int ndir, const double* psd, int nl, const double* lbda_nm, double* psf_out) {
@@ -2262,23 +2694,18 @@ int mpsfr_psf_from_psd(mpsfr_ctx* c, int ndir, const double* psd, int nl, const 
     const size_t npix = (size_t)ndir * c->N * c->N;
     for (size_t i = 0; i < npix; ++i)
         if (!std::isfinite(psd[i])) return fail(MPSFR_E_INVALID, "psd[%zu] is not finite", i);
-    StageIO io;
-    io.psd_in = psd;
-    io.stop_pre = true;
     CallArgs a;
     a.npsflin = npl, a.nl = nl, a.lbda_nm = lbda_nm, a.psf_out = psf_out;
-    return guarded_call(c, a, io);
+    return guarded(c, [&] { return psf_from_psd_impl(c, a, psd); });
 }
 
 int mpsfr_convolve_stamps(mpsfr_ctx* c, int ntask, const double* seeing, const double* gl, const double* l0,
                           int nl, const double* lbda_nm, const double* psf_in, double* psf_out) {
     if (!c || !psf_in || !psf_out) return fail(MPSFR_E_INVALID, "NULL argument");
-    StageIO io;
-    io.pre_in = psf_in;
     CallArgs a;
     a.ntask = ntask, a.seeing = seeing, a.gl = gl, a.l0 = l0;
     a.nl = nl, a.lbda_nm = lbda_nm, a.psf_out = psf_out;
-    return guarded_call(c, a, io);
+    return guarded(c, [&] { return convolve_stamps_impl(c, a, psf_in); });
 }
 
 int mpsfr_psd_to_psf(mpsfr_ctx* c, int npsd, const double* psd, int npup, const double* pup,
