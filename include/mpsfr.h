@@ -902,6 +902,26 @@ int mpsfr_host_time(mpsfr_ctx* ctx, double* seconds, long* calls);
  *                m-tiles with a second pass, tile steps without pruning, tile steps with all three
  *                products, tile steps without the low half of the OTF, blocks kept by at least one
  *                wavelength summed over the tasks, blocks inside the support of the telescope OTF x tasks
+ * The work plan of the per-wavelength stage in the last chunk, as its kernels read it (tests/test_gpu_mf_plan.py;
+ * tc = chunk tasks x stamp groups per task, nks = dim/32, nmt = ceil((dim/2+1)/16), nsw = ceil(nmt/8); a mask word
+ * holds bit ks of its m-tile or sweep -- at most 40 bits, which a double carries exactly).  Each name fails with a
+ * message when the last call did not produce that buffer; none launches anything or changes a buffer:
+ *   "mf_par"     [9 + nl] the host's thresholds thr_eps, thr_floor, thr_mid, tier_half, thr_blk, thr_sum, c2min (floats),
+ *                then per, ngr (wavelengths per group, groups) and c = -1/2 (2 pi / lambda)^2 of every wavelength
+ *   "mf_own"     [tc][nl][nmt][2] thin-wave kernel: the full blocks (word 0) and mid blocks (word 1) of a wavelength
+ *   "mf_uni"     [tc][ngr][nmt] the blocks a wavelength group stages
+ *   "mf_ksum"    [tc][nl][nsw] the k-steps with work per sweep of eight m-tiles, of a wavelength
+ *   "mf_kuni"    [tc][ngr][nsw] the same of a wavelength group
+ *   "mf_gsw"     [tc][ngr] bit sw: the sweep has work
+ *   "mf_sched"   [64] the lengths of the work lists, by work class
+ *   "mf_items"   [sum of "mf_sched"][5] the filled part of every list: class, task, group, sweep, sweeps of the (task, group)
+ *   "tlb"        [nmt][nks] log2 of the largest telescope OTF element of a block (-inf outside the support)
+ *   "dminb"      [tc][nmt][nks] block minima of max("dphi0", 0) over the directions, as the matrix-core kernels prune on
+ *                them (not when the thin-wave kernel took the line minima "dlin" instead)
+ *   "dblk"       [chunk tasks][ndir][nmt][nks] the block minima per direction (same condition)
+ *   "dline"      [chunk tasks][ndir][dim/2+1] the line minima per direction (same condition)
+ *   "thrf"       [tc] log2 floor per task of the kernel for several directions (finite "tier_eps" > 0)
+ *   "order"      [tc] dispatch order of the tasks (blocked matrix-core kernel, "prune_eps" > 0)
  *   "d0t_clears" [1] times a call cleared a lane's "dphi0" buffer because of what an earlier call left there
  *                (option "support_skip"), since the context was created
  * Returns the number of doubles written (<= capacity) or a negative error. */

@@ -240,6 +240,8 @@ struct mpsfr_ctx {
     float last_thr_blk = 0.f;
     bool last_floor_per_task = false;
     std::vector<double> last_lpc;        // c of every wavelength of the last call
+    // thr_eps, thr_floor, thr_mid, tier_half, thr_blk, thr_sum, c2min of the last call ("mf_par")
+    float last_thr[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     // profiling
     double prof_ms[K_COUNT] = {0};
     long prof_n[K_COUNT] = {0};
@@ -2078,6 +2080,9 @@ static void remember_call(mpsfr_ctx* c, const CallPrep& p, bool dlin) {
     c->last_dlin = dlin;
     c->last_thr_blk = p.th.thr_blk;
     c->last_floor_per_task = p.th.floor_per_task;
+    const float thr[7] = {p.th.thr_eps, p.th.thr_floor, p.th.thr_mid, p.th.tier_half, p.th.thr_blk, p.th.thr_sum,
+                          p.th.c2min};
+    for (int k = 0; k < 7; ++k) c->last_thr[k] = thr[k];
     c->last_lpc.resize(p.nl);
     for (int l = 0; l < p.nl; ++l) c->last_lpc[l] = p.lp[l].c;
 }
@@ -3274,6 +3279,104 @@ long mpsfr_debug_fetch(mpsfr_ctx* c, const char* what, double* out, size_t capac
         HIPCHK(hipMemcpy(tmp.data(), c->lane[c->last_lane].vkeep.p, n * sizeof(int), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < n; ++i) out[i] = (double)tmp[i];
         return (long)n;
+    } else if (!strcmp(what, "mf_par") || !strcmp(what, "mf_own") || !strcmp(what, "mf_uni") ||
+               !strcmp(what, "mf_ksum") || !strcmp(what, "mf_kuni") || !strcmp(what, "mf_gsw") ||
+               !strcmp(what, "mf_sched") || !strcmp(what, "mf_items") || !strcmp(what, "tlb") ||
+               !strcmp(what, "dminb") || !strcmp(what, "dblk") || !strcmp(what, "dline") || !strcmp(what, "thrf") ||
+               !strcmp(what, "order")) {
+        // The work plan of the per-wavelength stage in the last chunk, as its kernels read it (K_MF_PREP, K_DMIN,
+        // K_VKEEP, K_TASK_ORDER, K_PEAK_FLOOR): copies only, nothing is launched or written.
+        if (c->last_nl <= 0) return fail(MPSFR_E_INVALID, "no call yet");
+        const mpsfr_ctx::Lane& ln = c->lane[c->last_lane];
+        const int tc = c->last_chunk_tasks * c->last_gpp, ntd = c->last_chunk_tasks * c->last_ndir, nl = c->last_nl;
+        const int nks = N / 32, nmt = (H1 + 15) / 16, nsw = (nmt + 7) / 8;
+        int per = 0, ngr = 0;
+        mf2_groups(nl, c->mf_permax, &per, &ngr);
+        const bool mf2 = c->last_mf && c->last_mf2, mf1 = c->last_mf && !c->last_mf2;
+        // K_DMIN / K_DMIN16 ran: always before K_VKEEP, before K_MF_PREP only without the line minima of stage A
+        const bool dmin_ran = c->last_pruned && !(mf2 && c->last_dlin);
+        auto put = [&](const void* dev, size_t count, auto tag) -> long {
+            using T = decltype(tag);
+            if (count > capacity) return fail(MPSFR_E_INVALID, "capacity %zu < %zu", capacity, count);
+            std::vector<T> tmp(count);
+            if (count) HIPCHK(hipMemcpy(tmp.data(), dev, count * sizeof(T), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < count; ++i) out[i] = (double)tmp[i];
+            return (long)count;
+        };
+        typedef unsigned long long u64;
+        if (!strcmp(what, "mf_par")) {
+            n = 9 + (size_t)nl;
+            if (n > capacity) return fail(MPSFR_E_INVALID, "capacity %zu < %zu", capacity, n);
+            for (int k = 0; k < 7; ++k) out[k] = (double)c->last_thr[k];
+            out[7] = per;
+            out[8] = ngr;
+            for (int l = 0; l < nl; ++l) out[9 + l] = c->last_lpc[l];
+            return (long)n;
+        }
+        if (!strcmp(what, "tlb")) {
+            if (!c->tlb.p) return fail(MPSFR_E_INVALID, "no block maxima of the telescope OTF (otf_mfma = 0, or f64 mode)");
+            return put(c->tlb.p, (size_t)nmt * nks, float());
+        }
+        if (!strncmp(what, "mf_", 3)) {
+            if (!mf2) return fail(MPSFR_E_INVALID, "the last call did not use the thin-wave matrix-core kernel");
+            const u64* uni = (const u64*)ln.muni.p;
+            const u64* ksum = uni + (size_t)tc * nl * nmt;
+            const u64* kuni = ksum + (size_t)tc * nl * nsw;
+            const int* sched = (const int*)ln.msched.p;
+            const int* gsw = sched + 68;
+            if (!strcmp(what, "mf_own")) return put(ln.mown.p, (size_t)tc * nl * nmt * 2, u64());
+            if (!strcmp(what, "mf_uni")) return put(uni, (size_t)tc * ngr * nmt, u64());
+            if (!strcmp(what, "mf_ksum")) return put(ksum, (size_t)tc * nl * nsw, u64());
+            if (!strcmp(what, "mf_kuni")) return put(kuni, (size_t)tc * ngr * nsw, u64());
+            if (!strcmp(what, "mf_gsw")) return put(gsw, (size_t)tc * ngr, int());
+            if (!strcmp(what, "mf_sched")) return put(sched, (size_t)kMfLists, int());
+            // mf_items: the filled part of every list, (class, task, grp, sweep, sweeps) per item
+            int len[kMfLists];
+            HIPCHK(hipMemcpy(len, sched, sizeof(len), hipMemcpyDeviceToHost));
+            const size_t cap = (size_t)tc * ngr * nsw;
+            const int* items = sched + 68 + (((size_t)tc * nl + 3) & ~(size_t)3);
+            for (int k = 0; k < kMfLists; ++k) {
+                if (len[k] < 0 || (size_t)len[k] > cap) return fail(MPSFR_E_INVALID, "work list %d holds %d items of at most %zu", k, len[k], cap);
+                n += (size_t)len[k];
+            }
+            if (5 * n > capacity) return fail(MPSFR_E_INVALID, "capacity %zu < %zu", capacity, 5 * n);
+            std::vector<int> tmp;
+            size_t o = 0;
+            for (int k = 0; k < kMfLists; ++k) {
+                if (!len[k]) continue;
+                tmp.resize((size_t)4 * len[k]);
+                HIPCHK(hipMemcpy(tmp.data(), items + (size_t)k * cap * 4, tmp.size() * sizeof(int), hipMemcpyDeviceToHost));
+                for (int i = 0; i < len[k]; ++i, o += 5) {
+                    out[o] = k;
+                    for (int j = 0; j < 4; ++j) out[o + 1 + j] = tmp[(size_t)4 * i + j];
+                }
+            }
+            return (long)(5 * n);
+        }
+        if (!strcmp(what, "dminb")) {
+            // one direction and the thin-wave kernel: the block minima of K_DMIN are the minima over the directions
+            if (mf2 && dmin_ran) return put(ln.dblk.p, (size_t)tc * nmt * nks, float());
+            if (mf1 && c->last_pruned) return put(ln.dminb.p, (size_t)tc * nmt * nks, float());
+            return fail(MPSFR_E_INVALID, "no block minima over the directions in the last call (prune_eps = 0, the "
+                                         "FFT form, or the thin-wave kernel on the line minima of stage A)");
+        }
+        if (!strcmp(what, "dblk") || !strcmp(what, "dline")) {
+            if (!dmin_ran)
+                return fail(MPSFR_E_INVALID, "no minima per direction in the last call (prune_eps = 0, or the thin-wave "
+                                             "kernel on the line minima of stage A)");
+            if (!strcmp(what, "dblk")) return put(ln.dblk.p, (size_t)ntd * nmt * nks, float());
+            return put(ln.dmin.p, (size_t)ntd * H1, float());
+        }
+        if (!strcmp(what, "thrf")) {
+            if (!(mf1 && c->last_pruned && c->last_floor_per_task))
+                return fail(MPSFR_E_INVALID, "no floor per task in the last call (the kernel for several directions "
+                                             "with a finite tier_eps > 0 writes it)");
+            return put(ln.thrf.p, (size_t)tc, float());
+        }
+        if (!(mf1 && c->last_pruned))
+            return fail(MPSFR_E_INVALID, "no task order in the last call (mf_kernel = 1 or several directions, "
+                                         "prune_eps > 0)");
+        return put(ln.order.p, (size_t)tc, int());
     } else {
         return fail(MPSFR_E_INVALID, "unknown buffer '%s'", what);
     }
