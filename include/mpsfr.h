@@ -787,6 +787,43 @@ int mpsfr_fit_frame_psf(mpsfr_ctx* ctx, int ny, int nx, const double* image, con
                         const double* scale0, double radius, int flags, int max_iter, double tol, double* star_out,
                         double* head_out, double* resid_out, int on_device);
 
+/* Crowded-field photometry of a cube: the spectra of ALL stars, one solve of mpsfr_fit_frame_psf per wavelength layer,
+ * the layers of a batch side by side in the same kernels -- positions shared by the layers, the PSF of each layer its own.
+ *
+ * cube [nl][ny][nx]; var of the same shape, or NULL.  psf [npsf][nl][40][40], the layout of mpsfr_fit_spectra_psf: star k
+ * of layer l is psf[psf_index[k]][l].  origin, shift, psf_index: per star, for all layers, as for mpsfr_fit_frame_psf.
+ * layer_shift [nl][2] or NULL: one offset per layer common to all stars (differential refraction).  The shift of star
+ * k in layer l is shift[k] + layer_shift[l] per axis, one rounded addition (a NULL shift counts as 0); NULL: shift[k]
+ * itself.  The footprint is placed by origin alone and does not move with the layer; the centre, the taps of the
+ * resampling and the discs do.  scale0 [nl][nstar] or NULL.
+ * star_out [nl][nstar][MPSFR_NFRAMEFIT], head_out [nl][8], resid_out [nl][ny][nx] or NULL: columns, statuses, acceptance
+ * rule (per layer), Omega, stop rule (per layer), errors and on_device exactly as for mpsfr_fit_frame_psf.
+ *
+ * THE CONTRACT: layer l of the three outputs is bit for bit what mpsfr_fit_frame_psf returns on cube[l], var[l], the
+ * contiguous copy of psf[:, l], shift + layer_shift[l], scale0[l] and the same radius, flags, max_iter and tol --
+ * whatever layer_batch is, in both precision modes, on host and on device pointers.  In the device form a star whose
+ * summed shift leaves the +-8 pixels in some layer is status 2 in that layer only.
+ *
+ * nl in 1 .. MPSFR_CUBE_FIT_MAX_LAYERS.  layer_batch >= 0: the layers solved side by side; values above nl count as nl;
+ * 0: as many as MPSFR_CUBE_FIT_WORK_BYTES of per-layer work memory hold (at least one).  All max_iter iterations of a
+ * batch are queued without a host synchronisation; every layer has its own done word, and once it is set the
+ * workgroups of that layer return at once while the other layers of the batch go on.
+ * Work memory, in one buffer of the context: render's lists once (built from the origins and indices alone, sorted once),
+ * and per layer of a batch two frames of doubles, 7 nstar + 4 ceil(ny nx / 4096) + 9 doubles and 2 nstar + 5 int32.  The
+ * host form stages the layers batch by batch: besides the per-star inputs and layer_shift, per layer of a batch one
+ * frame for each of cube, var and resid_out that is given, npsf model stamps, and 9 nstar + 8 doubles (scale0, rows,
+ * head); it waits for each batch before it refills the stage.
+ * MPSFR_E_INVALID, outputs untouched, nothing queued: whatever mpsfr_fit_frame_psf refuses (cube in the place of image);
+ * nl out of range; layer_batch < 0; on host pointers a layer_shift that is not finite or that takes the summed shift of
+ * any star beyond 8 pixels, and a scale0 that is not finite.  Timed under the fit's profiling id. */
+#define MPSFR_CUBE_FIT_MAX_LAYERS 4096
+#define MPSFR_CUBE_FIT_WORK_BYTES ((size_t)256 << 20)   /* budget of per-layer work memory behind layer_batch = 0 */
+int mpsfr_fit_cube_psf(mpsfr_ctx* ctx, int nl, int ny, int nx, const double* cube, const double* var, int nstar, int npsf,
+                       const double* psf, const int32_t* psf_index, const int32_t* origin, const double* shift,
+                       const double* layer_shift, const double* scale0, double radius, int flags, int max_iter,
+                       double tol, int layer_batch, double* star_out, double* head_out, double* resid_out,
+                       int on_device);
+
 /* The stages of the path as the reference exports them (muse_psfr/__init__.py:16: `from .psfrec import *`),
  * for a caller that holds its own PSD or its own stamps.  Host buffers, synchronous, float64; the same
  * kernels as mpsfr_reconstruct entered or left at another stage.

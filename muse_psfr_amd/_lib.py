@@ -48,6 +48,7 @@ NFRAMEFIT = 8                # doubles per star of mpsfr_fit_frame_psf (MPSFR_NF
 FRAME_FIT_MAX_RADIUS = 20.0  # largest fit radius in pixels (MPSFR_FRAME_FIT_MAX_RADIUS)
 FRAME_FIT_MAX_ITER = 1000    # MPSFR_FRAME_FIT_MAX_ITER
 FRAME_FIT_MAX_STARS = 1 << 20
+CUBE_FIT_MAX_LAYERS = 4096   # layers of one mpsfr_fit_cube_psf call (MPSFR_CUBE_FIT_MAX_LAYERS)
 DIM_AO = 80
 PREC_MIXED, PREC_F64 = 0, 1
 E_GRID = -3
@@ -148,6 +149,9 @@ def load():
     lib.mpsfr_fit_frame_psf.argtypes = [p, C.c_int, C.c_int, p, p, C.c_int, C.c_int, p, p, p, p, p, C.c_double, C.c_int,
                                         C.c_int, C.c_double, p, p, p, C.c_int]
     lib.mpsfr_fit_frame_psf.restype = C.c_int
+    lib.mpsfr_fit_cube_psf.argtypes = [p, C.c_int, C.c_int, C.c_int, p, p, C.c_int, C.c_int, p, p, p, p, p, p, C.c_double,
+                                       C.c_int, C.c_int, C.c_double, C.c_int, p, p, p, C.c_int]
+    lib.mpsfr_fit_cube_psf.restype = C.c_int
     lib.mpsfr_simul_psd.argtypes = [p, C.c_double, C.c_double, C.c_double, C.c_int, dp, C.c_double, C.c_int, u8p, u8p, dp]
     lib.mpsfr_simul_psd.restype = C.c_int
     lib.mpsfr_psf_from_psd.argtypes = [p, C.c_int, dp, C.c_int, dp, dp]
@@ -195,7 +199,7 @@ def load():
 
 
 EXPORTS = ['mpsfr_create', 'mpsfr_destroy', 'mpsfr_last_error', 'mpsfr_set_option',
-           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_fit_stamps_psf', 'mpsfr_fit_groups_psf', 'mpsfr_fit_spectra_psf', 'mpsfr_stamp_metrics', 'mpsfr_cut_stamps', 'mpsfr_render_stars', 'mpsfr_find_stars', 'mpsfr_group_stars', 'mpsfr_fit_frame_psf', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
+           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_fit_stamps_psf', 'mpsfr_fit_groups_psf', 'mpsfr_fit_spectra_psf', 'mpsfr_stamp_metrics', 'mpsfr_cut_stamps', 'mpsfr_render_stars', 'mpsfr_find_stars', 'mpsfr_group_stars', 'mpsfr_fit_frame_psf', 'mpsfr_fit_cube_psf', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
            'mpsfr_psd_to_psf',
            'mpsfr_convolve_stamps', 'mpsfr_fit_rows', 'mpsfr_sync', 'mpsfr_last_ticket', 'mpsfr_wait', 'mpsfr_abandon',
            'mpsfr_stream', 'mpsfr_stream_wait', 'mpsfr_wait_event',
@@ -1188,6 +1192,61 @@ class Context:
         self._call_frame_fit(ny, nx, image_ptr, var_ptr, nstar, npsf, psf_ptr, psf_index_ptr, origin_ptr, shift_ptr,
                              scale0_ptr, radius, flags, max_iter, tol, star_out_ptr, head_ptr, resid_ptr, 1)
 
+    def _call_cube_fit(self, nl, ny, nx, cube, var, nstar, npsf, psf, index, origin, shift, layer_shift, scale0, radius,
+                       flags, max_iter, tol, layer_batch, rows, head, resid, on_device):
+        p = _devptr if on_device else _vptr
+        _check(self.lib.mpsfr_fit_cube_psf(self._h, int(nl), int(ny), int(nx), p(cube), p(var), int(nstar), int(npsf),
+                                           p(psf), p(index), p(origin), p(shift), p(layer_shift), p(scale0),
+                                           float(radius), flags, int(max_iter), float(tol), int(layer_batch), p(rows),
+                                           p(head), p(resid), on_device))
+
+    def fit_cube_psf(self, cube, psf, origin, *, var=None, shift=None, layer_shift=None, psf_index=None, scale0=None,
+                     radius=8.0, background=True, max_iter=100, tol=1e-10, layer_batch=0, return_residual=False):
+        """Crowded-field photometry of a cube (mpsfr_fit_cube_psf): fit_frame_psf on every layer of `cube` (nl, ny, nx;
+        `var` of the same shape or None), the layers of a batch side by side on the GPU.  `psf` (npsf, nl, dimpsf,
+        dimpsf): star k of layer l is psf[psf_index[k], l] (psf[k, l] without psf_index); origin, shift, psf_index per
+        star for all layers; `layer_shift` (nl, 2) pixels or None, one offset per layer added to every star's shift
+        (the sums must stay within FIT_PSF_MAX_SHIFT); `scale0` (nl, n) or None; `layer_batch` layers at once (0: as
+        many as the library's budget of work memory holds).  Returns rows (nl, n, NFRAMEFIT), head (nl, NFRAMEFIT) and,
+        with return_residual, the residual cube -- layer by layer the bits of fit_frame_psf on that layer."""
+        cu, va, ps, ix, og, sh, ls, s0, radius, flags, max_iter, tol, layer_batch = cube_fit_arguments(
+            cube, var, psf, psf_index, origin, shift, layer_shift, scale0, radius, background, max_iter, tol, layer_batch,
+            self.dimpsf)
+        if not isinstance(return_residual, (bool, np.bool_)):
+            raise ValueError('return_residual must be True or False')
+        nl, ny, nx = cu.shape
+        n = og.shape[0]
+        rows = np.empty((nl, n, NFRAMEFIT))
+        head = np.empty((nl, NFRAMEFIT))
+        resid = np.empty((nl, ny, nx)) if return_residual else None
+        self._call_cube_fit(nl, ny, nx, cu, va, n, ps.shape[0], ps, ix, og, sh, ls, s0, radius, flags, max_iter, tol,
+                            layer_batch, rows, head, resid, 0)
+        return (rows, head) + ((resid,) if return_residual else ())
+
+    def fit_cube_psf_device(self, nl, ny, nx, cube_ptr, nstar, npsf, psf_ptr, origin_ptr, star_out_ptr, head_ptr, *,
+                            var_ptr=None, shift_ptr=None, layer_shift_ptr=None, psf_index_ptr=None, scale0_ptr=None,
+                            resid_ptr=None, radius=8.0, background=True, max_iter=100, tol=1e-10, layer_batch=0):
+        """Device-buffer form (asynchronous, on_device = 1) of fit_cube_psf: `cube_ptr`, `var_ptr`, `resid_ptr`
+        ([nl][ny][nx] float64), `psf_ptr` ([npsf][nl][dimpsf][dimpsf] float64), `origin_ptr`, `shift_ptr`,
+        `psf_index_ptr` as for fit_frame_psf_device, `layer_shift_ptr` ([nl][2] float64 or None), `scale0_ptr`
+        ([nl][nstar] float64 or None), `star_out_ptr` ([nl][nstar][NFRAMEFIT] float64) and `head_ptr` ([nl][NFRAMEFIT]
+        float64) are raw device pointers (int) on this context's GPU; all batches are queued on the context stream
+        without a host synchronisation.  A star whose shift plus the layer's offset leaves the domain is status 2 in
+        that layer only."""
+        nl = cube_fit_layers(nl)
+        frame_shape(ny, nx)
+        nstar = frame_fit_stars(nstar)
+        _positive_int('npsf', npsf)
+        _device_pointers(cube_ptr=cube_ptr, psf_ptr=psf_ptr, origin_ptr=origin_ptr, star_out_ptr=star_out_ptr,
+                         head_ptr=head_ptr)
+        if not psf_index_ptr and npsf != nstar:
+            raise ValueError('without psf_index_ptr, npsf must equal nstar')
+        radius, flags, max_iter, tol = frame_fit_parameters(radius, background, max_iter, tol)
+        layer_batch = cube_fit_batch(layer_batch)
+        self._call_cube_fit(nl, ny, nx, cube_ptr, var_ptr, nstar, npsf, psf_ptr, psf_index_ptr, origin_ptr, shift_ptr,
+                            layer_shift_ptr, scale0_ptr, radius, flags, max_iter, tol, layer_batch, star_out_ptr, head_ptr,
+                            resid_ptr, 1)
+
     def debug_fetch(self, what, shape):
         out = np.empty(int(np.prod(shape)))
         n = _check(self.lib.mpsfr_debug_fetch(self._h, what.encode(), _dptr(out), out.size))
@@ -1486,6 +1545,86 @@ def frame_fit_arguments(image, var, psf, psf_index, origin, shift, scale0, radiu
     radius, flags, max_iter, tol = frame_fit_parameters(radius, background, max_iter, tol)
     s0 = None if scale0 is None else star_scales('scale0', scale0, n)
     return im, va, ps, ix, og, sh, s0, radius, flags, max_iter, tol
+
+
+def cube_fit_layers(nl):
+    """The number of layers of a cube fit: an integer in 1 .. CUBE_FIT_MAX_LAYERS (ValueError)."""
+    if isinstance(nl, bool) or not isinstance(nl, (int, np.integer)) or not 1 <= nl <= CUBE_FIT_MAX_LAYERS:
+        raise ValueError('a cube has 1 to %d layers, not %r' % (CUBE_FIT_MAX_LAYERS, nl))
+    return int(nl)
+
+
+def cube_fit_batch(layer_batch):
+    """layer_batch of a cube fit: an integer >= 0 (ValueError)."""
+    if isinstance(layer_batch, bool) or not isinstance(layer_batch, (int, np.integer)) \
+            or not 0 <= layer_batch <= (1 << 31) - 1:
+        raise ValueError('layer_batch must be an integer, 0 or above')
+    return int(layer_batch)
+
+
+def cube_fit_arguments(cube, var, psf, psf_index, origin, shift, layer_shift, scale0, radius, background, max_iter, tol,
+                       layer_batch, dimpsf=40):
+    """(cube, var or None, psf, psf_index, origin, shift, layer_shift or None, scale0 or None, radius, flags, max_iter,
+    tol, layer_batch) of a host cube fit, validated as mpsfr_fit_cube_psf validates host arguments (ValueError): every
+    layer of cube and var a frame of frame_images (masked pixels become NaN), 1 .. CUBE_FIT_MAX_LAYERS of them; psf a
+    numeric (npsf, nl, dimpsf, dimpsf) array; origin, psf_index, shift, radius, background, max_iter and tol as
+    frame_fit_arguments takes them; layer_shift None or (nl, 2) finite values that keep every shift[k] + layer_shift[l]
+    within FIT_PSF_MAX_SHIFT; scale0 None or (nl, n) finite values; layer_batch an integer >= 0."""
+    def volume(a, what):
+        try:
+            if isinstance(a, np.ma.MaskedArray):
+                return np.ma.filled(a.astype(np.float64), np.nan)
+            return np.asarray(getattr(a, 'data', a), dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('%s must be a numeric array' % what) from None
+    cu = volume(cube, 'cube')
+    if cu.ndim != 3 or cu.size == 0:
+        raise ValueError('cube must have the shape (nl, ny, nx)')
+    nl = cube_fit_layers(cu.shape[0])
+    va = None
+    if var is not None:
+        va = volume(var, 'var')
+        if va.shape != cu.shape:
+            raise ValueError('var must have the shape of cube')
+    try:
+        ps = np.asarray(getattr(psf, 'data', psf), dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('psf must be a numeric array') from None
+    if ps.ndim != 4 or ps.shape[1:] != (nl, dimpsf, dimpsf) or ps.size == 0:
+        raise ValueError('psf must have the shape (npsf, %d, %d, %d)' % (nl, dimpsf, dimpsf))
+    # one layer through the frame fit's own validation: the frame, the stars, the model list, the parameters
+    _, _, _, ix, og, sh, _, radius, flags, max_iter, tol = frame_fit_arguments(
+        cu[0], None if va is None else va[0], ps[:, 0], psf_index, origin, shift, None, radius, background, max_iter, tol,
+        dimpsf)
+    n = og.shape[0]
+    ls = None
+    if layer_shift is not None:
+        try:
+            ls = np.asarray(layer_shift, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('layer_shift must be a numeric array') from None
+        if ls.shape != (nl, 2):
+            raise ValueError('layer_shift must have the shape (%d, 2)' % nl)
+        if not np.all(np.isfinite(ls)):
+            raise ValueError('layer_shift must be finite')
+        total = ls[:, None, :] if sh is None else sh[None, :, :] + ls[:, None, :]
+        if not np.all(np.abs(total) <= FIT_PSF_MAX_SHIFT):
+            raise ValueError('shift + layer_shift must stay within %g pixels' % FIT_PSF_MAX_SHIFT)
+        ls = np.ascontiguousarray(ls)
+    s0 = None
+    if scale0 is not None:
+        try:
+            s0 = np.asarray(scale0, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('scale0 must be a numeric array') from None
+        if s0.shape != (nl, n):
+            raise ValueError('scale0 must have the shape (%d, %d)' % (nl, n))
+        if not np.all(np.isfinite(s0)):
+            raise ValueError('scale0 must be finite')
+        s0 = np.ascontiguousarray(s0)
+    layer_batch = cube_fit_batch(layer_batch)
+    return (np.ascontiguousarray(cu), None if va is None else np.ascontiguousarray(va), np.ascontiguousarray(ps), ix, og,
+            sh, ls, s0, radius, flags, max_iter, tol, layer_batch)
 
 
 def group_parameters(nstar, stride, crit, max_groups):

@@ -1,6 +1,6 @@
 // Device code shared by the kernels that resample a PSF model stamp (k_fit_psf in fit_psf.hip, k_fit_group in
 // fit_group_impl.h, k_fit_spec in fit_spec.hip and, through frame_common.h, k_render_tiles in render.hip and k_ff_star
-// in frame_fit.hip): the constants of the model stamp in LDS, the Keys tap weights of one axis (KeysTaps), the model
+// in frame_fit_impl.h): the constants of the model stamp in LDS, the Keys tap weights of one axis (KeysTaps), the model
 // stamp with its apron in LDS and the fp64 one in memory (LdsStamp, GlobalStamp), the 4 x 4 FIR with its
 // derivatives (psf_interp), the domain of the shift (psf_inside) and
 // the intake of a model stamp (k_fit_psf, k_fit_spec): its first pass, taken with the star's (PsfStampScan,

@@ -1,4 +1,4 @@
-// What the frame calls share (render.hip, frame_fit.hip, find.hip, group.hip; DESIGN.md sections 21 to 24): one star
+// What the frame calls share (render.hip, frame_fit.hip and cube_fit.hip, find.hip, group.hip; DESIGN.md sections 21 to 25): one star
 // of a StarList (kernels.h) as every kernel sees it, with the rule that admits it and its footprint (FrameStar); the
 // frame tile; a model stamp part staged in LDS (StagedStamp) and the pixel rule of staging it (model_pixel); the scan
 // of a workgroup's counts in LDS (block_scan); and the one description of a workspace that both *_workspace_bytes and
@@ -20,12 +20,19 @@ struct FrameStar {
     double dp, dq;
     __device__ __forceinline__ FrameStar(const StarList& l, int k)
         : op(l.origin[2 * k]), oq(l.origin[2 * k + 1]), ix(l.index ? l.index[k] : k),
-          dp(l.shift ? l.shift[2 * k] : 0.0), dq(l.shift ? l.shift[2 * k + 1] : 0.0) {}
-    // the rule of the device form: anything else is status 2 (a NaN shift fails)
-    __device__ __forceinline__ bool valid(int npsf) const {
-        return (unsigned)ix < (unsigned)npsf && psf_inside(dp, dq) && op >= -kMaxOrigin && op <= kMaxOrigin &&
-               oq >= -kMaxOrigin && oq <= kMaxOrigin;
+          dp(l.shift ? l.shift[2 * k] : 0.0), dq(l.shift ? l.shift[2 * k + 1] : 0.0) {
+        if (l.lshift) {                        // (a layer of a cube: its offset, common to all stars)
+            dp = dp + l.lshift[2 * l.layer];
+            dq = dq + l.lshift[2 * l.layer + 1];
+        }
     }
+    // index and origin in range: what places a star, whatever its shift
+    __device__ __forceinline__ bool placed(int npsf) const {
+        return (unsigned)ix < (unsigned)npsf && op >= -kMaxOrigin && op <= kMaxOrigin && oq >= -kMaxOrigin &&
+               oq <= kMaxOrigin;
+    }
+    // the rule of the device form: anything else is status 2 (a NaN shift fails)
+    __device__ __forceinline__ bool valid(int npsf) const { return placed(npsf) && psf_inside(dp, dq); }
     // the frame pixels inside the footprint (the kPsfSide x kPsfSide window around the stamp): rows y0 .. y1 - 1,
     // columns x0 .. x1 - 1; false if there is none
     __device__ __forceinline__ bool footprint(int ny, int nx, int& y0, int& y1, int& x0, int& x1) const {
@@ -38,7 +45,9 @@ struct FrameStar {
     // the centre in frame pixels
     __device__ __forceinline__ double cy() const { return (double)(op + NS / 2) + dp; }
     __device__ __forceinline__ double cx() const { return (double)(oq + NS / 2) + dq; }
-    __device__ __forceinline__ const double* model(const StarList& l) const { return l.psf + (size_t)ix * (NS * NS); }
+    __device__ __forceinline__ const double* model(const StarList& l) const {
+        return l.psf + ((size_t)ix * l.nl + l.layer) * (NS * NS);
+    }
 };
 
 // Pixel (r, c) of the fp64 model stamp P in memory, or zero outside the model (and where it is not `wanted`); the load

@@ -2,7 +2,7 @@
 // per_lambda.hip and stamps.hip; the fits of caller-provided stamps in fit_ell.hip, fit_obs.hip, fit_psf.hip,
 // fit_group*.hip and fit_spec.hip: the last three fit a resampled model stamp -- flux scale, sub-pixel shift,
 // background -- to an observed star, a blended group or a star cube; the frame calls in render.hip, find.hip,
-// group.hip and frame_fit.hip, which share frame_common.h).
+// group.hip, frame_fit.hip and cube_fit.hip, which share frame_common.h).
 // Host code (mpsfr_api.cpp) sees only these plain functions.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -296,11 +296,16 @@ void launch_cut_stamps(hipStream_t s, int ny, int nx, const double* d_image, con
 // psf[index[k]] (index nullptr: psf[k]) of psf [npsf][40][40], its pixel [0][0] on the frame pixel origin[2 k], [2 k + 1],
 // resampled at shift[2 k], [2 k + 1] (nullptr: zeros).  The scales are an argument of their own: the frame fit walks one
 // list with several vectors.  (Here and not in frame_common.h, because the host code fills it.)
+// For the layers of a cube (cube_fit.hip) psf is [npsf][nl][40][40] and star k of layer `layer` is the model stamp
+// psf[index[k]][layer] resampled at shift[k] + lshift[2 layer], [2 layer + 1] (one rounded addition; lshift nullptr:
+// shift[k] itself); a frame call is the one layer of nl = 1.
 struct StarList {
     int nstar, npsf;
     const double* psf;
     const int32_t *index, *origin;
     const double* shift;
+    const double* lshift = nullptr;
+    int nl = 1, layer = 0;
 };
 size_t render_workspace_bytes(int ny, int nx, int nstar);
 void launch_render_stars(hipStream_t s, int ny, int nx, const double* d_image_in, StarList stars, const double* d_scale,
@@ -313,6 +318,15 @@ void launch_render_lists(hipStream_t s, int ny, int nx, StarList stars, const do
                          double* d_star_out, void* d_ws);
 void launch_render_walk(hipStream_t s, int ny, int nx, const double* d_image_in, StarList stars, const double* d_scale,
                         bool subtract, double* d_image_out, void* d_ws, const int32_t* d_done);
+// For the layers of a cube (cube_fit.hip, through frame_fit_impl.h): launch_render_lists with neither d_scale nor
+// d_accept lists every star whose index and origin are in range and whose footprint meets the frame, whatever its shift;
+// launch_render_sort sorts every tile's list by star index in place, once; launch_render_walk_layers is the tile walk
+// of `layers` frames side by side over such lists -- frame, scales (at a pitch of scale_pitch doubles) and done word
+// (at done_pitch int32) of layer b, star k of it summed only where d_accept[b nstar + k] is not 0, in index order.
+void launch_render_sort(hipStream_t s, int ny, int nx, int nstar, void* d_ws);
+void launch_render_walk_layers(hipStream_t s, int ny, int nx, int layers, const double* d_image_in, StarList stars,
+                               const double* d_scale, int scale_pitch, const int32_t* d_accept, bool subtract,
+                               double* d_image_out, void* d_ws, const int32_t* d_done, int done_pitch);
 // d_offset[t] = sum of d_count[0 .. t - 1], d_offset[nt] = the total: the scan of the frame calls' counts (render.hip)
 void launch_scan_counts(hipStream_t s, int nt, const int* d_count, int* d_offset);
 // The star finder (find.hip; mpsfr_find_stars, include/mpsfr.h): the statistic T of every pixel of d_image [ny][nx]
@@ -337,12 +351,22 @@ void launch_group_stars(hipStream_t s, int ny, int nx, int nstar, const double* 
 // with `background`, one constant by preconditioned conjugate gradients on the frame d_image / d_var (or nullptr), at
 // most max_iter steps queued at once, into d_star_out [nstar][8], d_head_out [8] and d_resid_out [ny][nx] (or nullptr).
 // d_ws: frame_fit_workspace_bytes(ny, nx, nstar) bytes -- the renderer's lists, two frames of doubles, 7 nstar +
-// 4 ceil(ny nx / 4096) + 9 doubles, 2 nstar + 5 int32 (FrameFitWork, frame_fit.hip); the launch writes every word of it
+// 4 ceil(ny nx / 4096) + 9 doubles, 2 nstar + 5 int32 (FrameFitWork, frame_fit_impl.h); the launch writes every word of it
 // before it reads it.
 size_t frame_fit_workspace_bytes(int ny, int nx, int nstar);
 void launch_fit_frame(hipStream_t s, int ny, int nx, const double* d_image, const double* d_var, StarList stars,
                       const double* d_scale0, double radius, bool background, int max_iter, double tol,
                       double* d_star_out, double* d_head_out, double* d_resid_out, void* d_ws);
+// Crowded-field photometry of the layers of a cube (cube_fit.hip; mpsfr_fit_cube_psf, include/mpsfr.h): `layers` solves
+// of launch_fit_frame side by side, bit for bit -- d_cube, d_var (or nullptr), d_resid_out (or nullptr)
+// [layers][ny][nx], d_scale0 [layers][nstar] (or nullptr), d_star_out [layers][nstar][8], d_head_out [layers][8];
+// layer b takes the models stars.psf[index][b] of [npsf][stars.nl][40][40] and the shifts stars.shift[k] +
+// stars.lshift[2 b], [2 b + 1] (nullptr: stars.shift[k]).  d_ws: cube_fit_workspace_bytes(ny, nx, nstar, layers) bytes:
+// the renderer's lists once, and `layers` times what launch_fit_frame has behind them.
+size_t cube_fit_workspace_bytes(int ny, int nx, int nstar, int layers);
+void launch_fit_cube(hipStream_t s, int ny, int nx, int layers, const double* d_cube, const double* d_var,
+                     StarList stars, const double* d_scale0, double radius, bool background, int max_iter, double tol,
+                     double* d_star_out, double* d_head_out, double* d_resid_out, void* d_ws);
 // band-integrated stamps (band.hip): d_fin [ntb][nl][40][40] (float if fin_f32, else double) reduced over wavelength
 // into d_out [ntb][nband][40][40] double with the weights d_w [nl][band_stride(nband)] (zero beyond nband)
 constexpr int MAX_BANDS = 16;    // MPSFR_MAX_BANDS

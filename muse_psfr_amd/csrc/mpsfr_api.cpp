@@ -160,6 +160,7 @@ struct mpsfr_ctx {
     DevBuf find;                       // core, map, masks and counts of mpsfr_find_stars (find_workspace_bytes)
     DevBuf group;                      // cells, union-find and row lists of mpsfr_group_stars (group_workspace_bytes)
     DevBuf framefit;                   // lists, frames, vectors and scalars of mpsfr_fit_frame_psf (frame_fit_workspace_bytes)
+    DevBuf cubefit;                    // the same for a batch of layers of mpsfr_fit_cube_psf (cube_fit_workspace_bytes)
     DevBuf fit, sum, stage, lsum;      // lsum: [lanes][nl][40][40] per-lane partial stamp sums
     // mpsfr_psd_to_psf: a stream and workspaces of its own, so that it never waits for nor touches the lanes
     struct P2P {
@@ -749,7 +750,7 @@ void mpsfr_destroy(mpsfr_ctx* c) {
     }
     DevBuf* all[] = {&c->scoef, &c->stwk, &c->ssup, &c->tw64, &c->tel, &c->rows, &c->tlmax, &c->tl2, &c->tlb, &c->aotab, &c->samp_p,
                      &c->samp_a, &c->G, &c->xtab, &c->etab, &c->gtab, &c->kmuse, &c->fit, &c->sum,
-                     &c->stage, &c->lsum, &c->mfclk, &c->specx, &c->render, &c->find, &c->group, &c->framefit};
+                     &c->stage, &c->lsum, &c->mfclk, &c->specx, &c->render, &c->find, &c->group, &c->framefit, &c->cubefit};
     for (auto b : all) release(*b);
     if (c->p2p.stream) { (void)hipStreamSynchronize(c->p2p.stream); (void)hipStreamDestroy(c->p2p.stream); }
     DevBuf* p2p[] = {&c->p2p.twm, &c->p2p.psd, &c->p2p.cm, &c->p2p.d0t, &c->p2p.pup, &c->p2p.phase, &c->p2p.lbda,
@@ -3110,6 +3111,23 @@ int mpsfr_group_stars(mpsfr_ctx* c, int ny, int nx, int nstar, const double* pos
 static_assert(MPSFR_NFRAMEFIT == 8 && MPSFR_FRAME_FIT_MAX_RADIUS + MPSFR_FIT_PSF_MAX_SHIFT + 2.0 <= NS / 2 + 10.0,
               "K_FRAME_FIT row layout; a disc stays inside its footprint at any legal shift");
 
+// what mpsfr_fit_frame_psf and mpsfr_fit_cube_psf refuse alike, whatever the pointers are: shape, counts, parameters
+static int frame_fit_ranges(const char* who, int ny, int nx, int nstar, int npsf, const int32_t* psf_index, double radius,
+                            int flags, int max_iter, double tol) {
+    int rc;
+    if ((rc = frame_shape(who, ny, nx))) return rc;
+    if (nstar < 1 || nstar > (1 << 20)) return fail(MPSFR_E_INVALID, "%s: nstar=%d outside 1..2^20", who, nstar);
+    if (flags & ~MPSFR_FIT_BACKGROUND)
+        return fail(MPSFR_E_INVALID, "%s: unknown flag bits (only the background bit has a meaning here)", who);
+    if (!psf_index && npsf != nstar) return fail(MPSFR_E_INVALID, "%s: without psf_index, npsf must equal nstar", who);
+    if (!(radius >= 1.0 && radius <= MPSFR_FRAME_FIT_MAX_RADIUS))
+        return fail(MPSFR_E_INVALID, "%s: radius must be finite, in 1..%g pixels", who, MPSFR_FRAME_FIT_MAX_RADIUS);
+    if (!(tol > 0.0 && tol < 1.0)) return fail(MPSFR_E_INVALID, "%s: tol must lie in (0, 1)", who);
+    if (max_iter < 1 || max_iter > MPSFR_FRAME_FIT_MAX_ITER)
+        return fail(MPSFR_E_INVALID, "%s: max_iter=%d outside 1..%d", who, max_iter, MPSFR_FRAME_FIT_MAX_ITER);
+    return MPSFR_OK;
+}
+
 int mpsfr_fit_frame_psf(mpsfr_ctx* c, int ny, int nx, const double* image, const double* var, int nstar, int npsf,
                         const double* psf, const int32_t* psf_index, const int32_t* origin, const double* shift,
                         const double* scale0, double radius, int flags, int max_iter, double tol, double* star_out,
@@ -3117,17 +3135,7 @@ int mpsfr_fit_frame_psf(mpsfr_ctx* c, int ny, int nx, const double* image, const
     if (!c || !image || !psf || !origin || !star_out || !head_out || npsf < 1)
         return fail(MPSFR_E_INVALID, "fit_frame_psf: bad argument (image, psf, origin, star_out and head_out are required)");
     int rc;
-    if ((rc = frame_shape("fit_frame_psf", ny, nx))) return rc;
-    if (nstar < 1 || nstar > (1 << 20)) return fail(MPSFR_E_INVALID, "fit_frame_psf: nstar=%d outside 1..2^20", nstar);
-    if (flags & ~MPSFR_FIT_BACKGROUND)
-        return fail(MPSFR_E_INVALID, "fit_frame_psf: unknown flag bits (only the background bit has a meaning here)");
-    if (!psf_index && npsf != nstar)
-        return fail(MPSFR_E_INVALID, "fit_frame_psf: without psf_index, npsf must equal nstar");
-    if (!(radius >= 1.0 && radius <= MPSFR_FRAME_FIT_MAX_RADIUS))
-        return fail(MPSFR_E_INVALID, "fit_frame_psf: radius must be finite, in 1..%g pixels", MPSFR_FRAME_FIT_MAX_RADIUS);
-    if (!(tol > 0.0 && tol < 1.0)) return fail(MPSFR_E_INVALID, "fit_frame_psf: tol must lie in (0, 1)");
-    if (max_iter < 1 || max_iter > MPSFR_FRAME_FIT_MAX_ITER)
-        return fail(MPSFR_E_INVALID, "fit_frame_psf: max_iter=%d outside 1..%d", max_iter, MPSFR_FRAME_FIT_MAX_ITER);
+    if ((rc = frame_fit_ranges("fit_frame_psf", ny, nx, nstar, npsf, psf_index, radius, flags, max_iter, tol))) return rc;
     if (!on_device) {
         if ((rc = check_model_list("fit_frame_psf", "shift", nstar, npsf, psf_index, shift, (size_t)2 * nstar))) return rc;
         if ((rc = check_frame_stars("fit_frame_psf", nstar, origin, scale0, "scale0"))) return rc;
@@ -3150,6 +3158,117 @@ int mpsfr_fit_frame_psf(mpsfr_ctx* c, int ny, int nx, const double* image, const
                          (flags & MPSFR_FIT_BACKGROUND) != 0, max_iter, tol, d_out[0], d_out[1], d_out[2],
                          c->framefit.p);
     });
+}
+
+int mpsfr_fit_cube_psf(mpsfr_ctx* c, int nl, int ny, int nx, const double* cube, const double* var, int nstar, int npsf,
+                       const double* psf, const int32_t* psf_index, const int32_t* origin, const double* shift,
+                       const double* layer_shift, const double* scale0, double radius, int flags, int max_iter,
+                       double tol, int layer_batch, double* star_out, double* head_out, double* resid_out,
+                       int on_device) {
+    const char* who = "fit_cube_psf";
+    if (!c || !cube || !psf || !origin || !star_out || !head_out || npsf < 1)
+        return fail(MPSFR_E_INVALID, "%s: bad argument (cube, psf, origin, star_out and head_out are required)", who);
+    int rc;
+    if ((rc = frame_fit_ranges(who, ny, nx, nstar, npsf, psf_index, radius, flags, max_iter, tol))) return rc;
+    if (nl < 1 || nl > MPSFR_CUBE_FIT_MAX_LAYERS)
+        return fail(MPSFR_E_INVALID, "%s: nl=%d outside 1..%d", who, nl, MPSFR_CUBE_FIT_MAX_LAYERS);
+    if (layer_batch < 0) return fail(MPSFR_E_INVALID, "%s: layer_batch=%d is negative", who, layer_batch);
+    if (!on_device) {
+        if ((rc = check_model_list(who, "shift", nstar, npsf, psf_index, shift, (size_t)2 * nstar))) return rc;
+        if ((rc = check_frame_stars(who, nstar, origin, nullptr, "scale0"))) return rc;
+        if (scale0)
+            for (size_t k = 0; k < (size_t)nl * nstar; ++k)
+                if (!std::isfinite(scale0[k])) return fail(MPSFR_E_INVALID, "%s: a scale0 that is not finite", who);
+        if (layer_shift) {
+            // (rounding is monotone: the sums of a layer stay in range when those of the extreme shifts do)
+            double lo[2] = {0.0, 0.0}, hi[2] = {0.0, 0.0};
+            for (int k = 0; shift && k < 2 * nstar; ++k) {
+                lo[k & 1] = k < 2 ? shift[k] : std::min(lo[k & 1], shift[k]);
+                hi[k & 1] = k < 2 ? shift[k] : std::max(hi[k & 1], shift[k]);
+            }
+            for (int k = 0; k < 2 * nl; ++k) {
+                const double t = layer_shift[k];
+                if (!std::isfinite(t)) return fail(MPSFR_E_INVALID, "%s: a layer_shift that is not finite", who);
+                if (!(std::fabs(lo[k & 1] + t) <= MPSFR_FIT_PSF_MAX_SHIFT && std::fabs(hi[k & 1] + t) <= MPSFR_FIT_PSF_MAX_SHIFT))
+                    return fail(MPSFR_E_INVALID, "%s: shift + layer_shift beyond 8 pixels", who);
+            }
+        }
+    }
+    HIPCHK(hipSetDevice(c->device));
+    // the layers of a batch: asked for, or what the budget of work memory holds
+    const size_t fixed = cube_fit_workspace_bytes(ny, nx, nstar, 0), per = cube_fit_workspace_bytes(ny, nx, nstar, 1) - fixed;
+    int nb = layer_batch > 0 ? layer_batch : (int)std::min<size_t>((size_t)nl, MPSFR_CUBE_FIT_WORK_BYTES / per);
+    nb = std::max(1, std::min(nb, nl));
+    if ((rc = ensure(c, c->cubefit, cube_fit_workspace_bytes(ny, nx, nstar, nb)))) return rc;
+    hipStream_t s = c->stream;
+    if ((rc = wait_for_lanes(c, s))) return rc;
+    const bool back = (flags & MPSFR_FIT_BACKGROUND) != 0;
+    const size_t npix = (size_t)ny * nx, nrow = (size_t)nstar * MPSFR_NFRAMEFIT;
+    if (on_device) {
+        ProfScope ps(c, K_FIT);
+        for (int l0 = 0; l0 < nl; l0 += nb) {
+            const size_t o = (size_t)l0;
+            StarList stars{nstar, npsf, psf + o * kStampPix, psf_index, origin, shift};
+            stars.lshift = layer_shift ? layer_shift + 2 * o : nullptr;
+            stars.nl = nl;
+            launch_fit_cube(s, ny, nx, std::min(nb, nl - l0), cube + o * npix, var ? var + o * npix : nullptr, stars,
+                            scale0 ? scale0 + o * nstar : nullptr, radius, back, max_iter, tol, star_out + o * nrow,
+                            head_out + o * MPSFR_NFRAMEFIT, resid_out ? resid_out + o * npix : nullptr, c->cubefit.p);
+        }
+        HIPCHK(hipGetLastError());
+        return MPSFR_OK;
+    }
+    // Host pointers: what all layers share is staged once, the layers batch by batch -- cube, var, the models of the
+    // batch as [npsf][layers][40][40], scale0, and the three outputs
+    const size_t B = (size_t)nb;
+    size_t off = 0;
+    auto room = [&](bool wanted, size_t count) {
+        const size_t at = off;
+        if (wanted) off += (count * sizeof(double) + 7) & ~(size_t)7;
+        return at;
+    };
+    const size_t o_shift = room(shift, (size_t)2 * nstar), o_lshift = room(layer_shift, (size_t)2 * nl);
+    const size_t o_cube = room(true, B * npix), o_var = room(var, B * npix), o_psf = room(true, npsf * B * kStampPix);
+    const size_t o_s0 = room(scale0, B * nstar), o_rows = room(true, B * nrow), o_head = room(true, B * MPSFR_NFRAMEFIT);
+    const size_t o_res = room(resid_out, B * npix);
+    const size_t o_origin = room(true, (size_t)nstar), o_index = room(psf_index, ((size_t)nstar + 1) / 2);
+    if ((rc = ensure(c, c->stage, off))) return rc;
+    char* base = (char*)c->stage.p;
+    auto dbl = [&](bool wanted, size_t at) { return wanted ? (double*)(base + at) : nullptr; };
+    auto put = [&](void* dst, const void* src, size_t bytes) {
+        return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
+    };
+    if (shift) HIPCHK(put(base + o_shift, shift, (size_t)2 * nstar * sizeof(double)));
+    if (layer_shift) HIPCHK(put(base + o_lshift, layer_shift, (size_t)2 * nl * sizeof(double)));
+    HIPCHK(put(base + o_origin, origin, (size_t)2 * nstar * sizeof(int32_t)));
+    if (psf_index) HIPCHK(put(base + o_index, psf_index, (size_t)nstar * sizeof(int32_t)));
+    {
+        ProfScope ps(c, K_FIT);
+        for (int l0 = 0; l0 < nl; l0 += nb) {
+            const size_t o = (size_t)l0, n = (size_t)std::min(nb, nl - l0), frames = n * npix * sizeof(double);
+            HIPCHK(put(base + o_cube, cube + o * npix, frames));
+            if (var) HIPCHK(put(base + o_var, var + o * npix, frames));
+            if (scale0) HIPCHK(put(base + o_s0, scale0 + o * nstar, n * nstar * sizeof(double)));
+            const size_t width = n * kStampPix * sizeof(double);
+            HIPCHK(hipMemcpy2DAsync(base + o_psf, width, psf + o * kStampPix, (size_t)nl * kStampPix * sizeof(double),
+                                    width, (size_t)npsf, hipMemcpyHostToDevice, s));
+            StarList stars{nstar, npsf, dbl(true, o_psf), psf_index ? (const int32_t*)(base + o_index) : nullptr,
+                           (const int32_t*)(base + o_origin), dbl(shift, o_shift)};
+            stars.lshift = layer_shift ? dbl(true, o_lshift) + 2 * o : nullptr;
+            stars.nl = (int)n;
+            launch_fit_cube(s, ny, nx, (int)n, dbl(true, o_cube), dbl(var, o_var), stars, dbl(scale0, o_s0), radius, back,
+                            max_iter, tol, dbl(true, o_rows), dbl(true, o_head), dbl(resid_out, o_res), c->cubefit.p);
+            HIPCHK(hipGetLastError());
+            auto get = [&](void* dst, const void* src, size_t bytes) {
+                return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s);
+            };
+            HIPCHK(get(star_out + o * nrow, base + o_rows, n * nrow * sizeof(double)));
+            HIPCHK(get(head_out + o * MPSFR_NFRAMEFIT, base + o_head, n * MPSFR_NFRAMEFIT * sizeof(double)));
+            if (resid_out) HIPCHK(get(resid_out + o * npix, base + o_res, frames));
+            HIPCHK(hipStreamSynchronize(s));      // (the staged batch is refilled by the next one)
+        }
+    }
+    return MPSFR_OK;
 }
 
 long mpsfr_debug_fetch(mpsfr_ctx* c, const char* what, double* out, size_t capacity) {

@@ -8,8 +8,13 @@
 //   k_render_tiles    one workgroup per tile: sorts its list by star index, then walks it in that order -- the model
 //                     stamp part the tile needs goes into LDS (two buffers, the next star fetched while this one is
 //                     evaluated), every thread keeps four pixels in registers
+//   k_render_sort     (the layers of a cube, cube_fit.hip) sorts every tile's list once, in place; k_render_tiles<true>
+//                     then walks the frames of a batch of layers over the sorted lists, which hold every placed star,
+//                     and skips the stars its layer has not accepted
 // The order of the sum at a pixel is the star index, whatever the tile grid or the scheduling; no floating-point atomics.
 // Arithmetic is fp64 in both precision modes; P~ is psf_interp of fit_psf_common.h with KeysTaps<double>.
+#include <type_traits>
+
 #include "frame_common.h"
 
 namespace mpsfr {
@@ -57,7 +62,10 @@ __global__ __launch_bounds__(256) void k_render_prepare(int ny, int nx, int ntx,
     const int k = blockIdx.x * 256 + threadIdx.x;
     if (k >= stars.nstar) return;
     const FrameStar star(stars, k);
-    const bool ok = star.valid(stars.npsf) && (accept ? accept[k] != 0 : fabs(scale[k]) < __builtin_inf());
+    // (neither accept nor scale: the lists of a cube, from what places a star alone -- index, origin, footprint)
+    const bool ok = accept  ? star.valid(stars.npsf) && accept[k] != 0
+                    : scale ? star.valid(stars.npsf) && fabs(scale[k]) < __builtin_inf()
+                            : star.placed(stars.npsf);
     int st = 2, npix = 0;
     if (ok) {
         int y0, y1, x0, x1;
@@ -150,6 +158,12 @@ __device__ void sort_indices(int* v, int n) {
     }
 }
 
+// every tile's list sorted once, in place, for the walks that take it sorted (k_render_tiles<true>)
+__global__ __launch_bounds__(kTileThreads) void k_render_sort(const int* __restrict__ offset, int* pairs) {
+    const int first = offset[blockIdx.x];
+    sort_indices(pairs + first, offset[blockIdx.x + 1] - first);
+}
+
 // One star as a tile sees it: its parameters (the same for all threads) and the model pixel of stage[0][0]
 struct TileStar {
     int op, oq, r0, c0;
@@ -184,12 +198,32 @@ __device__ __forceinline__ double add_term(double acc, double scale, double val,
     return subtract ? acc - t : acc + t;
 }
 
+// LAYERS: the frames of a batch of layers (blockIdx.z) side by side -- frames of ny nx pixels, scales at a pitch of
+// lay.scale_pitch, done words at lay.done_pitch, lay.accept [layers][nstar] --, over lists that are sorted already and
+// hold every placed star: a star its layer has not accepted is skipped.
+struct NoLayers {};
+struct WalkLayers {
+    const int32_t* accept;
+    int scale_pitch, done_pitch;
+};
+template <bool LAYERS>
 __global__ __launch_bounds__(kTileThreads) void k_render_tiles(int ny, int nx, const double* image_in, StarList stars,
                                                                const double* __restrict__ scale, int subtract,
                                                                const int* __restrict__ offset, int* pairs,
-                                                               const int32_t* __restrict__ done, double* image_out) {
+                                                               const int32_t* __restrict__ done, double* image_out,
+                                                               std::conditional_t<LAYERS, WalkLayers, NoLayers> lay) {
     __shared__ double stage[2 * kStageSide * kStageStride];
-    __shared__ int slist[kSortChunk];
+    __shared__ int slist[LAYERS ? 1 : kSortChunk];
+    const int32_t* accept = nullptr;
+    if constexpr (LAYERS) {
+        const int b = blockIdx.z;
+        if (done) done += (size_t)b * lay.done_pitch;
+        if (image_in) image_in += (size_t)b * ny * nx;
+        image_out += (size_t)b * ny * nx;
+        scale += (size_t)b * lay.scale_pitch;
+        accept = lay.accept + (size_t)b * stars.nstar;
+        stars.layer = b;
+    }
     if (done && *done) return;          // (a queued walk of the frame fit after its stop test has passed)
     const int tid = threadIdx.x, lx = tid & (kTile - 1), ly0 = tid / kTile;
     const int t = blockIdx.y * gridDim.x + blockIdx.x;
@@ -205,31 +239,41 @@ __global__ __launch_bounds__(kTileThreads) void k_render_tiles(int ny, int nx, c
         acc[j] = on[j] && image_in ? image_in[(size_t)Y * nx + X] : 0.0;
     }
     const int* list = slist;
-    if (n <= kSortChunk) {
+    if constexpr (LAYERS) {
+        list = pairs + first;
+    } else if (n <= kSortChunk) {
         if (tid < n) slist[tid] = pairs[first + tid];
         sort_indices(slist, n);
     } else {
         sort_indices(pairs + first, n);
         list = pairs + first;
     }
+    // the first place of the list from i on whose star takes part
+    auto next = [&](int i) {
+        if constexpr (LAYERS)
+            while (i < n && !accept[list[i]]) ++i;
+        return i;
+    };
     // Star i + 1 is fetched into registers while star i is evaluated, and the stage alternates between two buffers:
     // one barrier per star (a buffer is rewritten two stars later, behind the barrier that every thread reaches only
     // after its last read of it).
     TileStar cur, nxt;
     double pre[kStageLoads];
-    if (n > 0) {
-        cur.load(list[0], Y0, X0, stars, scale);
+    int i = next(0);
+    if (i < n) {
+        cur.load(list[i], Y0, X0, stars, scale);
         cur.fetch(tid, pre);
     }
-    for (int i = 0; i < n; ++i) {
-        double* buf = stage + (i & 1) * (kStageSide * kStageStride);
+    for (int turn = 0; i < n; ++turn) {
+        double* buf = stage + (turn & 1) * (kStageSide * kStageStride);
 #pragma unroll
         for (int m = 0; m < kStageLoads; ++m) {
             const int e = tid + m * kTileThreads;
             if (e < kStageSide * kStageSide) buf[(e / kStageSide) * kStageStride + e % kStageSide] = pre[m];
         }
-        if (i + 1 < n) {
-            nxt.load(list[i + 1], Y0, X0, stars, scale);
+        i = next(i + 1);
+        if (i < n) {
+            nxt.load(list[i], Y0, X0, stars, scale);
             nxt.fetch(tid, pre);
         }
         __syncthreads();
@@ -292,8 +336,24 @@ void launch_render_walk(hipStream_t s, int ny, int nx, const double* d_image_in,
                         bool subtract, double* d_image_out, void* d_ws, const int32_t* d_done) {
     WorkspaceCarver ws(d_ws);
     const RenderLists l(ws, ny, nx, stars.nstar);
-    hipLaunchKernelGGL(k_render_tiles, dim3(l.ntx, l.nty), dim3(kTileThreads), 0, s, ny, nx, d_image_in, stars, d_scale,
-                       subtract ? 1 : 0, l.offset, l.pairs, d_done, d_image_out);
+    hipLaunchKernelGGL(k_render_tiles<false>, dim3(l.ntx, l.nty), dim3(kTileThreads), 0, s, ny, nx, d_image_in, stars,
+                       d_scale, subtract ? 1 : 0, l.offset, l.pairs, d_done, d_image_out, NoLayers{});
+}
+
+void launch_render_sort(hipStream_t s, int ny, int nx, int nstar, void* d_ws) {
+    WorkspaceCarver ws(d_ws);
+    const RenderLists l(ws, ny, nx, nstar);
+    hipLaunchKernelGGL(k_render_sort, dim3(l.nt), dim3(kTileThreads), 0, s, l.offset, l.pairs);
+}
+
+void launch_render_walk_layers(hipStream_t s, int ny, int nx, int layers, const double* d_image_in, StarList stars,
+                               const double* d_scale, int scale_pitch, const int32_t* d_accept, bool subtract,
+                               double* d_image_out, void* d_ws, const int32_t* d_done, int done_pitch) {
+    WorkspaceCarver ws(d_ws);
+    const RenderLists l(ws, ny, nx, stars.nstar);
+    hipLaunchKernelGGL(k_render_tiles<true>, dim3(l.ntx, l.nty, layers), dim3(kTileThreads), 0, s, ny, nx, d_image_in,
+                       stars, d_scale, subtract ? 1 : 0, l.offset, l.pairs, d_done, d_image_out,
+                       WalkLayers{d_accept, scale_pitch, done_pitch});
 }
 
 void launch_render_stars(hipStream_t s, int ny, int nx, const double* d_image_in, StarList stars, const double* d_scale,

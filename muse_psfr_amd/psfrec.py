@@ -973,6 +973,93 @@ def fit_crowded_stars(image, psf, positions, *, var=None, psf_index=None, radius
     return (fit, origin) + ((res[2],) if return_residual else ())
 
 
+_FIT_COLS_CROWDED_SPECTRA = ('shift', 'scale', 'flux', 'err_scale', 'err_flux', 'overlap', 'npix', 'status')
+_META_CROWDED_SPECTRA = ('back', 'err_back', 'chi2', 'npix', 'iterations', 'residual', 'status')
+
+
+def fit_crowded_spectra(cube, psf, positions, *, lbda=None, var=None, psf_index=None, layer_shift=None, radius=8.0,
+                        fit_back=True, start=None, max_iter=100, tol=1e-10, layer_batch=0, return_residual=False,
+                        pixscale=0.2, precision='mixed', device=0):
+    """Crowded-field PSF spectroscopy, on the GPU: the spectra of ALL stars of a cube at known positions -- the solve
+    of fit_crowded_stars on every wavelength layer, the layers side by side in one call, bit for bit what a loop of
+    fit_crowded_stars over the layers gives.  `cube` (nl, ny, nx), `var` its variance cube or None (NaN pixels and var
+    <= 0 are masked); `positions` an (n, 2) array of (row, column) in pixels or a find_stars table, the same in every
+    layer; `layer_shift` (nl, 2) arcsec or None: the offset of a layer common to all stars (differential refraction),
+    added to every star's position in that layer -- a position plus offset must stay within 8 pixels of the star's
+    stamp centre; `psf` (nl, 40, 40), one model cube for every star, e.g. the reconstructed PSF per wavelength, or
+    (npsf, nl, 40, 40) with star k taking psf[psf_index[k]].  radius, fit_back, max_iter, tol: as fit_crowded_stars,
+    per layer.  `start`: None (zeros), 'found' (the `scale` column of a find_stars table, for every layer) or (nl, n)
+    values.  `layer_batch`: layers solved side by side (0: as many as the library's work memory budget holds).
+    `lbda` (nl,): wavelengths, echoed into fit.meta.
+
+    Returns (fit, origin): origin as fit_crowded_stars places it, and `fit` with one row per star: shift (2, arcsec,
+    echoed: the position from the stamp centre, without the layer's offset) and the (n, nl) columns scale, flux,
+    err_scale, err_flux, overlap, npix and status of fit_crowded_stars.  fit.meta holds the per-layer arrays (nl,) back,
+    err_back, chi2, npix, iterations, residual and status, and lbda if given.  With return_residual also the cube minus
+    the fitted stars."""
+    _pixscale(pixscale)
+    if not isinstance(fit_back, (bool, np.bool_)):
+        raise ValueError('fit_back must be True or False')
+    pos = _star_positions(positions)
+    n = pos.shape[0]
+    try:
+        ps = np.asarray(getattr(psf, 'data', psf), dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('psf must be a numeric array') from None
+    if ps.ndim not in (3, 4) or ps.shape[-1] != ps.shape[-2] or ps.size == 0:
+        raise ValueError('psf must have the shape (nl, 40, 40) or (npsf, nl, 40, 40)')
+    dimpsf = ps.shape[-1]
+    if not np.all(np.isfinite(pos)) or np.any(np.abs(pos) > _lib.MAX_ORIGIN - dimpsf):
+        raise ValueError('positions must be finite and within 2^30 pixels')
+    if ps.ndim == 3:
+        if psf_index is not None:
+            raise ValueError('psf_index needs psf of the shape (npsf, nl, 40, 40)')
+        ps = ps[None]
+        psf_index = np.zeros(n, dtype=np.int32)
+    nl = ps.shape[1]
+    if lbda is not None:
+        try:
+            lbda = np.array(lbda, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('lbda must be a numeric array') from None
+        if lbda.shape != (nl,):
+            raise ValueError('lbda must hold one wavelength per layer (%d)' % nl)
+    if layer_shift is not None:
+        try:
+            layer_shift = np.asarray(layer_shift, dtype=np.float64) / pixscale
+        except (TypeError, ValueError):
+            raise ValueError('layer_shift must be a numeric array') from None
+    if isinstance(start, str):
+        if start != 'found':
+            raise ValueError("start must be None, 'found' or (nl, n) values")
+        try:
+            found = np.asarray(positions['scale'], dtype=float)
+        except (KeyError, IndexError, TypeError, ValueError):
+            raise ValueError("start='found' needs a find_stars table") from None
+        start = np.broadcast_to(found, (nl, n))
+    origin = (np.rint(pos) - dimpsf // 2).astype(np.int32)
+    shift_px = pos - (origin + dimpsf // 2)
+    ctx = get_context(128, pixscale, dimpsf, precision, device)
+    res = ctx.fit_cube_psf(cube, ps, origin, var=var, shift=shift_px, layer_shift=layer_shift, psf_index=psf_index,
+                           scale0=start, radius=radius, background=bool(fit_back), max_iter=max_iter, tol=tol,
+                           layer_batch=layer_batch, return_residual=return_residual)
+    rows, head = res[0], res[1]                                    # (nl, n, 8), (nl, 8)
+    cols = OrderedDict()
+    cols['shift'] = shift_px * pixscale
+    for name, c in (('scale', 0), ('flux', 2), ('err_scale', 1), ('err_flux', 3), ('overlap', 4)):
+        cols[name] = np.ascontiguousarray(rows[:, :, c].T)
+    cols['npix'] = np.ascontiguousarray(rows[:, :, 5].T).astype(np.int64)
+    cols['status'] = np.ascontiguousarray(rows[:, :, 7].T).astype(np.int64)
+    assert tuple(cols) == _FIT_COLS_CROWDED_SPECTRA
+    meta = OrderedDict()
+    for name, c in zip(_META_CROWDED_SPECTRA, (0, 1, 2, 3, 4, 5, 7)):
+        meta[name] = head[:, c].astype(np.int64) if name in ('npix', 'iterations', 'status') else head[:, c].copy()
+    if lbda is not None:
+        meta['lbda'] = lbda
+    fit = _make_table(cols, meta)
+    return (fit, origin) + ((res[2],) if return_residual else ())
+
+
 def cut_star_stamps(image, positions, var=None, dimpsf=40, *, pixscale=0.2, precision='mixed', device=0):
     """Stamps of stars out of a frame, on the GPU: `image` (ny, nx), `positions` (n, 2) the (row, column) star centres
     in pixels.  Stamp k starts at origin[k] = rint(positions[k]) - dimpsf // 2, so the star sits within half a pixel of
