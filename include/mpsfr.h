@@ -787,6 +787,76 @@ int mpsfr_fit_frame_psf(mpsfr_ctx* ctx, int ny, int nx, const double* image, con
                         const double* scale0, double radius, int flags, int max_iter, double tol, double* star_out,
                         double* head_out, double* resid_out, int on_device);
 
+/* Crowded-field PSF photometry with free positions: mpsfr_fit_frame_psf with the shifts of the stars as unknowns beside
+ * their fluxes -- the fluxes AND positions of all stars of a frame refined at once by Gauss-Newton, no limit on how
+ * many stars touch each other (DAOPHOT's ALLSTAR step).
+ *
+ * image .. tol: as for mpsfr_fit_frame_psf.  The given shift is the start s0.  The valid pixels, the accepted stars and
+ * Omega (the discs of `radius` around the START centres) are decided once, from s0, by mpsfr_fit_frame_psf's rules, and
+ * stay for the whole call: Omega does not follow the stars.  Minimised over the F_k of the accepted stars, the shifts
+ * s_k of the free stars and, with MPSFR_FIT_BACKGROUND, one constant b:
+ *     sum over Omega of w (D - b - sum_k F_k P~_k(s_k))^2,      P~_k(s) placed by origin[k], which never moves.
+ * 1. Opening solve: F and b at s0 from scale0, positions held.
+ * 2. Up to max_outer Gauss-Newton steps.  A star is FREE in a step when it is accepted, its F from the solve before is
+ *    finite and > 0, F > min_snr err_F, and its derivative columns have a positive finite norm; any other star is HELD
+ *    in that step.  err_F = sqrt((chi2 / dof) / N_kk) is the conditional error of the solve before, taken where the step
+ *    starts: chi2 of the residual of that F and b at the current shifts, N_kk at them, dof = |Omega| - accepted - [b].
+ *    No star is free when |Omega| < 3 accepted + [b] + 1.  A free star has three columns at the current shifts, P~_k,
+ *    dP~_k/ds_y and dP~_k/ds_x, the exact derivatives of the cubic-convolution taps; a held star has P~_k alone.  The
+ *    linear least-squares problem in (F_k, a_k, c_k, b) over Omega is solved by Jacobi-preconditioned conjugate gradients
+ *    on the normal equations, matrix-free, from the F and b before and a = c = 0.  Then delta_k = (a_k, c_k) / F_k with
+ *    the new F_k (0 if that is not finite or not positive, or if the quotient is not finite); each axis is clipped to
+ *    +- max_step, then so that |s_k - s0_k| <= max_move and |s_k| <= 8.  The loop ends when the largest unclipped
+ *    |delta| over the free stars is <= pos_tol, or when no star is free.
+ * 3. Closing solve: F and b at the final shifts, positions held, from the F and b before.  Columns 0-7, the head's
+ *    first eight and resid_out belong to the returned shifts.
+ * Every solve stops when r.M^-1 r <= tol^2 (g.M^-1 g), g = A^T W D over its live unknowns and M = diag(N) -- relative to
+ * the right-hand side, so that a solve started at its solution ends at once --, when g = 0, or after max_iter steps.
+ * Everything is queued whole, without a host synchronisation; behind a done word the queued kernels return at once.
+ *
+ * star_out [nstar][MPSFR_NFRAMEFREE]:  0-7 as mpsfr_fit_frame_psf, of the closing solve, with
+ *     dof = |Omega| - accepted - 2 (stars ever free) - [b]
+ *     8, 9 the final shift y, x   10, 11 their errors   12, 13 final minus start   14 flags   15 outer steps in which
+ *     the star was free.
+ *   The position errors are conditional on the other stars, as err_F is: the star's own 3 x 3 block of N (F, a, c) at
+ *   its last free step, inverted, times chi2 / dof of the closing solve, over F^2 of the closing solve; 0 for a star
+ *   that was never free.  Flags: MPSFR_FRAME_FREE_HELD held in the last outer step that ran; of the star's last free
+ *   step, MPSFR_FRAME_FREE_BOUND resting on max_move or on the +-8 bound and MPSFR_FRAME_FREE_CLIPPED clipped by
+ *   max_step.  A left-out star keeps its input shift in 8, 9, its status in 7, and zeros elsewhere.
+ * shift_out [nstar][2], required: the final shifts, at the pitch mpsfr_render_stars and mpsfr_fit_frame_psf read.
+ * head_out [MPSFR_NFRAMEFREE_HEAD]:  0-7 as mpsfr_fit_frame_psf, of the closing solve (5: the last
+ *     sqrt(r.M^-1 r / g.M^-1 g))   8 outer steps done   9 the last largest |delta| over the free stars   10 free stars in
+ *     the last step   11 inner iterations summed over all solves.
+ *     7 status: 0 the position test AND the closing solve's stop test have passed (max_outer = 0, or no star free:
+ *     the position test counts as passed); 1 anything else that was fitted; 2 nothing fitted.
+ * resid_out [ny][nx] or NULL: bit for bit mpsfr_render_stars(MPSFR_RENDER_SUBTRACT) with shift_out and column 0 over
+ *   the accepted stars.
+ * max_outer in 0 .. 16 (0: the opening solve alone, reported as the closing one); pos_tol finite and > 0; max_step in
+ * (0, 1]; max_move in (0, 4]; min_snr finite and >= 0.
+ *
+ * The same call gives the same bits, a mixed context those of an f64 one, host and device pointers the same; no
+ * floating-point atomics, every sum in a fixed order.  mpsfr_fit_frame_psf's two power-of-two laws hold: they scale F,
+ * b, the fluxes, their errors, chi2 and N_kk by exact powers of two, and every position, position error, flag and count
+ * keeps its bits.
+ * Work memory, in one buffer of the context: render's lists, two frames of doubles, and
+ * 36 nstar + 8 ceil(ny nx / 4096) + 11 doubles and 6 nstar + 12 int32.
+ * on_device as mpsfr_render_stars.  MPSFR_E_INVALID, outputs untouched, nothing queued: whatever mpsfr_fit_frame_psf
+ * refuses; a NULL shift_out; max_outer, pos_tol, max_step, max_move or min_snr out of range or not finite.  The cube
+ * form (one position, the layers side by side) is the follow-up.  Timed under the fit's profiling id. */
+#define MPSFR_NFRAMEFREE 16               /* doubles per star in star_out */
+#define MPSFR_NFRAMEFREE_HEAD 12          /* doubles in head_out */
+#define MPSFR_FRAME_FREE_MAX_OUTER 16
+#define MPSFR_FRAME_FREE_MAX_STEP 1.0     /* pixels */
+#define MPSFR_FRAME_FREE_MAX_MOVE 4.0     /* pixels */
+#define MPSFR_FRAME_FREE_HELD 1           /* flag: held in the last outer step */
+#define MPSFR_FRAME_FREE_BOUND 2          /* flag: resting on max_move or on the +-8 bound */
+#define MPSFR_FRAME_FREE_CLIPPED 4        /* flag: the last step was clipped by max_step */
+int mpsfr_fit_frame_psf_free(mpsfr_ctx* ctx, int ny, int nx, const double* image, const double* var, int nstar, int npsf,
+                             const double* psf, const int32_t* psf_index, const int32_t* origin, const double* shift,
+                             const double* scale0, double radius, int flags, int max_iter, double tol, int max_outer,
+                             double pos_tol, double max_step, double max_move, double min_snr, double* star_out,
+                             double* shift_out, double* head_out, double* resid_out, int on_device);
+
 /* Crowded-field photometry of a cube: the spectra of ALL stars, one solve of mpsfr_fit_frame_psf per wavelength layer,
  * the layers of a batch side by side in the same kernels -- positions shared by the layers, the PSF of each layer its own.
  *

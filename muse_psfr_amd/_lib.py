@@ -49,6 +49,14 @@ FRAME_FIT_MAX_RADIUS = 20.0  # largest fit radius in pixels (MPSFR_FRAME_FIT_MAX
 FRAME_FIT_MAX_ITER = 1000    # MPSFR_FRAME_FIT_MAX_ITER
 FRAME_FIT_MAX_STARS = 1 << 20
 CUBE_FIT_MAX_LAYERS = 4096   # layers of one mpsfr_fit_cube_psf call (MPSFR_CUBE_FIT_MAX_LAYERS)
+NFRAMEFREE = 16              # doubles per star of mpsfr_fit_frame_psf_free (MPSFR_NFRAMEFREE)
+NFRAMEFREE_HEAD = 12         # doubles of its head (MPSFR_NFRAMEFREE_HEAD)
+FRAME_FREE_MAX_OUTER = 16    # most Gauss-Newton steps of one call (MPSFR_FRAME_FREE_MAX_OUTER)
+FRAME_FREE_MAX_STEP = 1.0    # largest max_step in pixels (MPSFR_FRAME_FREE_MAX_STEP)
+FRAME_FREE_MAX_MOVE = 4.0    # largest max_move in pixels (MPSFR_FRAME_FREE_MAX_MOVE)
+FRAME_FREE_HELD = 1          # flag in column 14: held in the last outer step (MPSFR_FRAME_FREE_HELD)
+FRAME_FREE_BOUND = 2         # resting on max_move or on the +-8 bound (MPSFR_FRAME_FREE_BOUND)
+FRAME_FREE_CLIPPED = 4       # the last step was clipped by max_step (MPSFR_FRAME_FREE_CLIPPED)
 DIM_AO = 80
 PREC_MIXED, PREC_F64 = 0, 1
 E_GRID = -3
@@ -149,6 +157,10 @@ def load():
     lib.mpsfr_fit_frame_psf.argtypes = [p, C.c_int, C.c_int, p, p, C.c_int, C.c_int, p, p, p, p, p, C.c_double, C.c_int,
                                         C.c_int, C.c_double, p, p, p, C.c_int]
     lib.mpsfr_fit_frame_psf.restype = C.c_int
+    lib.mpsfr_fit_frame_psf_free.argtypes = [p, C.c_int, C.c_int, p, p, C.c_int, C.c_int, p, p, p, p, p, C.c_double,
+                                             C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double,
+                                             C.c_double, p, p, p, p, C.c_int]
+    lib.mpsfr_fit_frame_psf_free.restype = C.c_int
     lib.mpsfr_fit_cube_psf.argtypes = [p, C.c_int, C.c_int, C.c_int, p, p, C.c_int, C.c_int, p, p, p, p, p, p, C.c_double,
                                        C.c_int, C.c_int, C.c_double, C.c_int, p, p, p, C.c_int]
     lib.mpsfr_fit_cube_psf.restype = C.c_int
@@ -199,7 +211,7 @@ def load():
 
 
 EXPORTS = ['mpsfr_create', 'mpsfr_destroy', 'mpsfr_last_error', 'mpsfr_set_option',
-           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_fit_stamps_psf', 'mpsfr_fit_groups_psf', 'mpsfr_fit_spectra_psf', 'mpsfr_stamp_metrics', 'mpsfr_cut_stamps', 'mpsfr_render_stars', 'mpsfr_find_stars', 'mpsfr_group_stars', 'mpsfr_fit_frame_psf', 'mpsfr_fit_cube_psf', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
+           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_fit_stamps_psf', 'mpsfr_fit_groups_psf', 'mpsfr_fit_spectra_psf', 'mpsfr_stamp_metrics', 'mpsfr_cut_stamps', 'mpsfr_render_stars', 'mpsfr_find_stars', 'mpsfr_group_stars', 'mpsfr_fit_frame_psf', 'mpsfr_fit_frame_psf_free', 'mpsfr_fit_cube_psf', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
            'mpsfr_psd_to_psf',
            'mpsfr_convolve_stamps', 'mpsfr_fit_rows', 'mpsfr_sync', 'mpsfr_last_ticket', 'mpsfr_wait', 'mpsfr_abandon',
            'mpsfr_stream', 'mpsfr_stream_wait', 'mpsfr_wait_event',
@@ -1192,6 +1204,70 @@ class Context:
         self._call_frame_fit(ny, nx, image_ptr, var_ptr, nstar, npsf, psf_ptr, psf_index_ptr, origin_ptr, shift_ptr,
                              scale0_ptr, radius, flags, max_iter, tol, star_out_ptr, head_ptr, resid_ptr, 1)
 
+    def _call_frame_free(self, ny, nx, image, var, nstar, npsf, psf, index, origin, shift, scale0, radius, flags,
+                         max_iter, tol, free, rows, shift_out, head, resid, on_device):
+        p = _devptr if on_device else _vptr
+        max_outer, pos_tol, max_step, max_move, min_snr = free
+        _check(self.lib.mpsfr_fit_frame_psf_free(self._h, int(ny), int(nx), p(image), p(var), int(nstar), int(npsf),
+                                                 p(psf), p(index), p(origin), p(shift), p(scale0), float(radius), flags,
+                                                 int(max_iter), float(tol), int(max_outer), float(pos_tol),
+                                                 float(max_step), float(max_move), float(min_snr), p(rows), p(shift_out),
+                                                 p(head), p(resid), on_device))
+
+    def fit_frame_psf_free(self, image, psf, origin, *, var=None, shift=None, psf_index=None, scale0=None, radius=8.0,
+                           background=True, max_iter=100, tol=1e-10, max_outer=8, pos_tol=1e-3, max_step=0.5,
+                           max_move=2.0, min_snr=3.0, return_residual=False):
+        """Crowded-field photometry with free positions (mpsfr_fit_frame_psf_free): fit_frame_psf with the shifts of
+        the stars as unknowns.  `shift` is the start; the valid pixels, the accepted stars and the discs of `radius`
+        around the START centres are decided from it once.  An opening solve of the fluxes, then up to `max_outer`
+        (0 .. 16) Gauss-Newton steps over the fluxes and the shifts of the free stars -- the accepted ones with
+        F > min_snr err_F --, every step clipped per axis to `max_step` (0 .. 1] px and every shift to within `max_move`
+        (0 .. 4] px of its start and 8 px of its origin, until the largest step is <= `pos_tol` px; then a closing
+        solve at the final shifts.  Every inner solve is fit_frame_psf's, to `tol` relative to its right-hand side or
+        `max_iter` steps.  Returns (rows, shifts, head) and, with return_residual, the frame minus the fitted stars at
+        the final shifts.  rows (n, NFRAMEFREE): 0-7 as fit_frame_psf at the final shifts, 8-9 the final shift, 10-11
+        its conditional errors, 12-13 final minus start, 14 flags (FRAME_FREE_HELD, FRAME_FREE_BOUND,
+        FRAME_FREE_CLIPPED), 15 the outer steps in which the star was free.  shifts (n, 2): columns 8-9 as
+        render_stars and fit_frame_psf take them.  head (NFRAMEFREE_HEAD,): 0-7 as fit_frame_psf for the closing solve
+        (7: 0 only if the positions and the closing solve have both converged), 8 outer steps, 9 the last largest
+        step, 10 free stars in the last step, 11 inner iterations in all."""
+        im, va, ps, ix, og, sh, s0, radius, flags, max_iter, tol = frame_fit_arguments(
+            image, var, psf, psf_index, origin, shift, scale0, radius, background, max_iter, tol, self.dimpsf)
+        free = frame_free_parameters(max_outer, pos_tol, max_step, max_move, min_snr)
+        if not isinstance(return_residual, (bool, np.bool_)):
+            raise ValueError('return_residual must be True or False')
+        ny, nx = im.shape
+        n = og.shape[0]
+        rows = np.empty((n, NFRAMEFREE))
+        shifts = np.empty((n, 2))
+        head = np.empty(NFRAMEFREE_HEAD)
+        resid = np.empty((ny, nx)) if return_residual else None
+        self._call_frame_free(ny, nx, im, va, n, ps.shape[0], ps, ix, og, sh, s0, radius, flags, max_iter, tol, free,
+                              rows, shifts, head, resid, 0)
+        return (rows, shifts, head) + ((resid,) if return_residual else ())
+
+    def fit_frame_psf_free_device(self, ny, nx, image_ptr, nstar, npsf, psf_ptr, origin_ptr, star_out_ptr,
+                                  shift_out_ptr, head_ptr, *, var_ptr=None, shift_ptr=None, psf_index_ptr=None,
+                                  scale0_ptr=None, resid_ptr=None, radius=8.0, background=True, max_iter=100, tol=1e-10,
+                                  max_outer=8, pos_tol=1e-3, max_step=0.5, max_move=2.0, min_snr=3.0):
+        """Device-buffer form (asynchronous, on_device = 1) of fit_frame_psf_free: the pointers of
+        fit_frame_psf_device, with `star_out_ptr` ([nstar][NFRAMEFREE] float64), `shift_out_ptr` ([nstar][2] float64:
+        what render_stars_device and fit_frame_psf_device take as shift_ptr) and `head_ptr` ([NFRAMEFREE_HEAD]
+        float64).  The whole call -- every solve of every outer step -- is queued on the context stream without a host
+        synchronisation."""
+        frame_shape(ny, nx)
+        nstar = frame_fit_stars(nstar)
+        _positive_int('npsf', npsf)
+        _device_pointers(image_ptr=image_ptr, psf_ptr=psf_ptr, origin_ptr=origin_ptr, star_out_ptr=star_out_ptr,
+                         shift_out_ptr=shift_out_ptr, head_ptr=head_ptr)
+        if not psf_index_ptr and npsf != nstar:
+            raise ValueError('without psf_index_ptr, npsf must equal nstar')
+        radius, flags, max_iter, tol = frame_fit_parameters(radius, background, max_iter, tol)
+        free = frame_free_parameters(max_outer, pos_tol, max_step, max_move, min_snr)
+        self._call_frame_free(ny, nx, image_ptr, var_ptr, nstar, npsf, psf_ptr, psf_index_ptr, origin_ptr, shift_ptr,
+                              scale0_ptr, radius, flags, max_iter, tol, free, star_out_ptr, shift_out_ptr, head_ptr,
+                              resid_ptr, 1)
+
     def _call_cube_fit(self, nl, ny, nx, cube, var, nstar, npsf, psf, index, origin, shift, layer_shift, scale0, radius,
                        flags, max_iter, tol, layer_batch, rows, head, resid, on_device):
         p = _devptr if on_device else _vptr
@@ -1532,6 +1608,31 @@ def frame_fit_parameters(radius, background, max_iter, tol):
     if not isinstance(background, (bool, np.bool_)):
         raise ValueError('background must be True or False')
     return radius, FIT_BACKGROUND if background else 0, int(max_iter), tol
+
+
+def frame_free_parameters(max_outer, pos_tol, max_step, max_move, min_snr):
+    """(max_outer, pos_tol, max_step, max_move, min_snr) of a frame fit with free positions, validated as
+    mpsfr_fit_frame_psf_free validates them (ValueError)."""
+    def number(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError('%s must be a finite number' % name)
+        return float(v)
+    if isinstance(max_outer, bool) or not isinstance(max_outer, (int, np.integer)) \
+            or not 0 <= max_outer <= FRAME_FREE_MAX_OUTER:
+        raise ValueError('max_outer must be an integer between 0 and %d' % FRAME_FREE_MAX_OUTER)
+    pos_tol = number('pos_tol', pos_tol)
+    if not pos_tol > 0.0:
+        raise ValueError('pos_tol must be > 0')
+    max_step = number('max_step', max_step)
+    if not 0.0 < max_step <= FRAME_FREE_MAX_STEP:
+        raise ValueError('max_step must lie in (0, %g] pixels' % FRAME_FREE_MAX_STEP)
+    max_move = number('max_move', max_move)
+    if not 0.0 < max_move <= FRAME_FREE_MAX_MOVE:
+        raise ValueError('max_move must lie in (0, %g] pixels' % FRAME_FREE_MAX_MOVE)
+    min_snr = number('min_snr', min_snr)
+    if not min_snr >= 0.0:
+        raise ValueError('min_snr must be >= 0')
+    return int(max_outer), pos_tol, max_step, max_move, min_snr
 
 
 def frame_fit_arguments(image, var, psf, psf_index, origin, shift, scale0, radius, background, max_iter, tol, dimpsf=40):

@@ -357,6 +357,19 @@ size_t frame_fit_workspace_bytes(int ny, int nx, int nstar);
 void launch_fit_frame(hipStream_t s, int ny, int nx, const double* d_image, const double* d_var, StarList stars,
                       const double* d_scale0, double radius, bool background, int max_iter, double tol,
                       double* d_star_out, double* d_head_out, double* d_resid_out, void* d_ws);
+// Crowded-field photometry with free positions (frame_free.hip; mpsfr_fit_frame_psf_free, include/mpsfr.h): an opening
+// solve of launch_fit_frame's problem at the shifts of `stars`, up to max_outer Gauss-Newton steps over the fluxes and
+// the shifts of the free stars, a closing solve at the final shifts; Omega and the accepted stars are those of the
+// start.  d_star_out [nstar][16], d_shift_out [nstar][2], d_head_out [12], d_resid_out [ny][nx] (or nullptr); everything
+// is queued at once.  d_ws: frame_free_workspace_bytes(ny, nx, nstar) bytes -- the renderer's lists, two frames of
+// doubles, 36 nstar + 8 ceil(ny nx / 4096) + 11 doubles, 6 nstar + 12 int32 (FrameFreeWork, frame_free.hip); the launch
+// writes every word of it before it reads it.
+size_t frame_free_workspace_bytes(int ny, int nx, int nstar);
+void launch_fit_frame_free(hipStream_t s, int ny, int nx, const double* d_image, const double* d_var, StarList stars,
+                           const double* d_scale0, double radius, bool background, int max_iter, double tol,
+                           int max_outer, double pos_tol, double max_step, double max_move, double min_snr,
+                           double* d_star_out, double* d_shift_out, double* d_head_out, double* d_resid_out,
+                           void* d_ws);
 // Crowded-field photometry of the layers of a cube (cube_fit.hip; mpsfr_fit_cube_psf, include/mpsfr.h): `layers` solves
 // of launch_fit_frame side by side, bit for bit -- d_cube, d_var (or nullptr), d_resid_out (or nullptr)
 // [layers][ny][nx], d_scale0 [layers][nstar] (or nullptr), d_star_out [layers][nstar][8], d_head_out [layers][8];

@@ -3160,6 +3160,56 @@ int mpsfr_fit_frame_psf(mpsfr_ctx* c, int ny, int nx, const double* image, const
     });
 }
 
+static_assert(MPSFR_NFRAMEFREE == 16 && MPSFR_NFRAMEFREE_HEAD == 12 && MPSFR_FRAME_FREE_HELD == 1 &&
+                  MPSFR_FRAME_FREE_BOUND == 2 && MPSFR_FRAME_FREE_CLIPPED == 4,
+              "k_fr_step<FR_FINAL> row layout and flags");
+
+int mpsfr_fit_frame_psf_free(mpsfr_ctx* c, int ny, int nx, const double* image, const double* var, int nstar, int npsf,
+                             const double* psf, const int32_t* psf_index, const int32_t* origin, const double* shift,
+                             const double* scale0, double radius, int flags, int max_iter, double tol, int max_outer,
+                             double pos_tol, double max_step, double max_move, double min_snr, double* star_out,
+                             double* shift_out, double* head_out, double* resid_out, int on_device) {
+    const char* who = "fit_frame_psf_free";
+    if (!c || !image || !psf || !origin || !star_out || !shift_out || !head_out || npsf < 1)
+        return fail(MPSFR_E_INVALID,
+                    "%s: bad argument (image, psf, origin, star_out, shift_out and head_out are required)", who);
+    int rc;
+    if ((rc = frame_fit_ranges(who, ny, nx, nstar, npsf, psf_index, radius, flags, max_iter, tol))) return rc;
+    if (max_outer < 0 || max_outer > MPSFR_FRAME_FREE_MAX_OUTER)
+        return fail(MPSFR_E_INVALID, "%s: max_outer=%d outside 0..%d", who, max_outer, MPSFR_FRAME_FREE_MAX_OUTER);
+    if (!(pos_tol > 0.0 && std::isfinite(pos_tol))) return fail(MPSFR_E_INVALID, "%s: pos_tol must be finite and > 0", who);
+    if (!(max_step > 0.0 && max_step <= MPSFR_FRAME_FREE_MAX_STEP))
+        return fail(MPSFR_E_INVALID, "%s: max_step must lie in (0, %g] pixels", who, MPSFR_FRAME_FREE_MAX_STEP);
+    if (!(max_move > 0.0 && max_move <= MPSFR_FRAME_FREE_MAX_MOVE))
+        return fail(MPSFR_E_INVALID, "%s: max_move must lie in (0, %g] pixels", who, MPSFR_FRAME_FREE_MAX_MOVE);
+    if (!(min_snr >= 0.0 && std::isfinite(min_snr))) return fail(MPSFR_E_INVALID, "%s: min_snr must be finite and >= 0", who);
+    if (!on_device) {
+        if ((rc = check_model_list(who, "shift", nstar, npsf, psf_index, shift, (size_t)2 * nstar))) return rc;
+        if ((rc = check_frame_stars(who, nstar, origin, scale0, "scale0"))) return rc;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = ensure(c, c->framefit, frame_free_workspace_bytes(ny, nx, nstar)))) return rc;
+    const size_t npix = (size_t)ny * nx;
+    const StampIn in[] = {{image, npix, sizeof(double)},
+                          {var, npix, sizeof(double)},
+                          {psf, npsf * kStampPix, sizeof(double)},
+                          {shift, (size_t)2 * nstar, sizeof(double)},
+                          {scale0, (size_t)nstar, sizeof(double)},
+                          {origin, (size_t)2 * nstar, sizeof(int32_t)},
+                          {psf_index, (size_t)nstar, sizeof(int32_t)}};
+    const StampOut out[] = {{star_out, (size_t)nstar * MPSFR_NFRAMEFREE},
+                            {shift_out, (size_t)2 * nstar},
+                            {head_out, MPSFR_NFRAMEFREE_HEAD},
+                            {resid_out, npix}};
+    return stamp_call(c, on_device, in, out, [&](hipStream_t s, const void* const* d, double* const* d_out) {
+        const StarList stars{nstar, npsf, (const double*)d[2], (const int32_t*)d[6], (const int32_t*)d[5],
+                             (const double*)d[3]};
+        launch_fit_frame_free(s, ny, nx, (const double*)d[0], (const double*)d[1], stars, (const double*)d[4], radius,
+                              (flags & MPSFR_FIT_BACKGROUND) != 0, max_iter, tol, max_outer, pos_tol, max_step, max_move,
+                              min_snr, d_out[0], d_out[1], d_out[2], d_out[3], c->framefit.p);
+    });
+}
+
 int mpsfr_fit_cube_psf(mpsfr_ctx* c, int nl, int ny, int nx, const double* cube, const double* var, int nstar, int npsf,
                        const double* psf, const int32_t* psf_index, const int32_t* origin, const double* shift,
                        const double* layer_shift, const double* scale0, double radius, int flags, int max_iter,

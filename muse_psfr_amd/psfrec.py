@@ -797,11 +797,13 @@ def fit_found_stars(image, psf, found, *, var=None, crit, fit_back=True, mode='f
     fit_crowded_stars does, at their found positions within `radius` pixels and with fit_back as given: their rows get
     scale, flux and the conditional errors (err_scale, err_flux), the shift from their own stamp origin with error 0,
     the back, err_back, chi2 and npix of the frame solve and max_corr NaN; `origin` gains one row per such star and
-    their `group` column points at it, so that subtract_stars(image, psf, origin, fit) removes every star."""
+    their `group` column points at it, so that subtract_stars(image, psf, origin, fit) removes every star.  With
+    crowded='free' the same, with the positions of the crowded stars refined beside their fluxes as
+    refine_crowded_stars does (its defaults): their rows get the refined shift and its conditional error."""
     if not isinstance(fit_back, (bool, np.bool_)):
         raise ValueError('fit_back must be True or False')
-    if crowded not in ('skip', 'frame'):
-        raise ValueError("crowded must be 'skip' or 'frame'")
+    if crowded not in ('skip', 'frame', 'free'):
+        raise ValueError("crowded must be 'skip', 'frame' or 'free'")
     _lib.frame_fit_parameters(radius, bool(fit_back), 1, 0.5)
     _pixscale(pixscale)
     _lib.group_fit_flags(bool(fit_back), mode)
@@ -873,7 +875,7 @@ def fit_found_stars(image, psf, found, *, var=None, crit, fit_back=True, mode='f
     assert tuple(cols) == _FIT_COLS_FOUND
     origin = origin.astype(np.int32)
     rows = np.flatnonzero(cols['crowded'])
-    if crowded == 'frame' and rows.size:
+    if crowded != 'skip' and rows.size:
         resid, _ = subtract_stars(im, ps, origin, cols, psf_index=np.zeros(origin.shape[0], dtype=np.int32),
                                   pixscale=pixscale, precision=precision, device=device)
         own = (np.rint(pos[rows]) - ps.shape[-1] // 2).astype(np.int32)
@@ -883,9 +885,16 @@ def fit_found_stars(image, psf, found, *, var=None, crit, fit_back=True, mode='f
             start = np.nan_to_num(np.asarray(found['scale'], dtype=float)[rows], nan=0.0, posinf=0.0, neginf=0.0)
         except (KeyError, IndexError, TypeError, ValueError):
             pass
-        out, head = ctx.fit_frame_psf(resid, ps[None], own, var=va, shift=shift_px,
-                                      psf_index=np.zeros(rows.size, dtype=np.int32), scale0=start, radius=radius,
-                                      background=bool(fit_back))
+        err_px = np.zeros((rows.size, 2))
+        if crowded == 'free':
+            out, shift_px, head = ctx.fit_frame_psf_free(resid, ps[None], own, var=va, shift=shift_px,
+                                                         psf_index=np.zeros(rows.size, dtype=np.int32), scale0=start,
+                                                         radius=radius, background=bool(fit_back))
+            err_px = out[:, 10:12]
+        else:
+            out, head = ctx.fit_frame_psf(resid, ps[None], own, var=va, shift=shift_px,
+                                          psf_index=np.zeros(rows.size, dtype=np.int32), scale0=start, radius=radius,
+                                          background=bool(fit_back))
         ok = out[:, 7] == 0
         fill = rows[ok]
         cols['scale'][fill] = out[ok, 0]
@@ -893,7 +902,7 @@ def fit_found_stars(image, psf, found, *, var=None, crit, fit_back=True, mode='f
         cols['err_scale'][fill] = out[ok, 1]
         cols['err_flux'][fill] = out[ok, 3]
         cols['shift'][fill] = shift_px[ok] * pixscale
-        cols['err_shift'][fill] = 0.0
+        cols['err_shift'][fill] = err_px[ok] * pixscale
         cols['back'][fill] = head[0]
         cols['err_back'][fill] = head[1]
         cols['chi2'][fill] = head[2]
@@ -907,25 +916,9 @@ def fit_found_stars(image, psf, found, *, var=None, crit, fit_back=True, mode='f
 _FIT_COLS_CROWDED = ('scale', 'shift', 'flux', 'err_scale', 'err_flux', 'overlap', 'npix', 'status')
 
 
-def fit_crowded_stars(image, psf, positions, *, var=None, psf_index=None, radius=8.0, fit_back=True, start=None,
-                      max_iter=100, tol=1e-10, return_residual=False, pixscale=0.2, precision='mixed', device=0):
-    """Crowded-field PSF photometry, on the GPU: the fluxes of ALL stars of a frame at known positions in one linear
-    least-squares solve -- no limit on how many stars touch each other; the step for the groups fit_found_stars
-    marks `crowded`.  `image` (ny, nx), `var` its variance frame or None (NaN pixels and var <= 0 are masked);
-    `positions` an (n, 2) array of (row, column) in pixels or a find_stars table; `psf` (..., 40, 40) model stamps,
-    e.g. reconstructed PSFs, star k taking psf[psf_index[k]] (one stamp: every star takes it).  The fit runs over the
-    valid pixels within `radius` (1 .. 20) pixels of a star, with one constant background under fit_back, by
-    preconditioned conjugate gradients to the relative residual `tol` or max_iter steps, from `start`: None (zeros),
-    'found' (the `scale` column of a find_stars table) or n values.
-
-    Returns (fit, origin) in the form subtract_stars takes (pass it the same psf_index): origin[k] =
-    rint(positions[k]) - 20 as cut_star_stamps places stamps, and `fit` with one row per star: scale (F), shift (2,
-    arcsec, echoed: the position from the stamp centre), flux, err_scale and err_flux (CONDITIONAL errors: the other
-    stars held fixed), overlap (the sum of the star's off-diagonal terms of the normal matrix over its diagonal term;
-    far from 0 the conditional error is optimistic), npix (valid pixels within `radius` of the star) and status (0
-    fitted, 1 off the frame, 2 left out: no valid pixel, or no model there).  fit.meta: back, err_back, chi2, npix
-    (pixels of the solve), iterations, residual (the last relative preconditioned residual), status (0 converged, 1
-    max_iter reached, 2 nothing fitted).  With return_residual also the frame minus the fitted stars."""
+def _crowded_inputs(psf, positions, psf_index, fit_back, start, pixscale):
+    """(psf, psf_index, start, origin, shift in pixels) of fit_crowded_stars and refine_crowded_stars: the model stamps,
+    the stars placed as cut_star_stamps places stamps, the start resolved."""
     _pixscale(pixscale)
     if not isinstance(fit_back, (bool, np.bool_)):
         raise ValueError('fit_back must be True or False')
@@ -951,6 +944,30 @@ def fit_crowded_stars(image, psf, positions, *, var=None, psf_index=None, radius
             raise ValueError("start='found' needs a find_stars table") from None
     origin = (np.rint(pos) - dimpsf // 2).astype(np.int32)
     shift_px = pos - (origin + dimpsf // 2)
+    return ps, psf_index, start, origin, shift_px
+
+
+def fit_crowded_stars(image, psf, positions, *, var=None, psf_index=None, radius=8.0, fit_back=True, start=None,
+                      max_iter=100, tol=1e-10, return_residual=False, pixscale=0.2, precision='mixed', device=0):
+    """Crowded-field PSF photometry, on the GPU: the fluxes of ALL stars of a frame at known positions in one linear
+    least-squares solve -- no limit on how many stars touch each other; the step for the groups fit_found_stars
+    marks `crowded`.  `image` (ny, nx), `var` its variance frame or None (NaN pixels and var <= 0 are masked);
+    `positions` an (n, 2) array of (row, column) in pixels or a find_stars table; `psf` (..., 40, 40) model stamps,
+    e.g. reconstructed PSFs, star k taking psf[psf_index[k]] (one stamp: every star takes it).  The fit runs over the
+    valid pixels within `radius` (1 .. 20) pixels of a star, with one constant background under fit_back, by
+    preconditioned conjugate gradients to the relative residual `tol` or max_iter steps, from `start`: None (zeros),
+    'found' (the `scale` column of a find_stars table) or n values.
+
+    Returns (fit, origin) in the form subtract_stars takes (pass it the same psf_index): origin[k] =
+    rint(positions[k]) - 20 as cut_star_stamps places stamps, and `fit` with one row per star: scale (F), shift (2,
+    arcsec, echoed: the position from the stamp centre), flux, err_scale and err_flux (CONDITIONAL errors: the other
+    stars held fixed), overlap (the sum of the star's off-diagonal terms of the normal matrix over its diagonal term;
+    far from 0 the conditional error is optimistic), npix (valid pixels within `radius` of the star) and status (0
+    fitted, 1 off the frame, 2 left out: no valid pixel, or no model there).  fit.meta: back, err_back, chi2, npix
+    (pixels of the solve), iterations, residual (the last relative preconditioned residual), status (0 converged, 1
+    max_iter reached, 2 nothing fitted).  With return_residual also the frame minus the fitted stars."""
+    ps, psf_index, start, origin, shift_px = _crowded_inputs(psf, positions, psf_index, fit_back, start, pixscale)
+    dimpsf = ps.shape[-1]
     ctx = get_context(128, pixscale, dimpsf, precision, device)
     res = ctx.fit_frame_psf(image, ps, origin, var=var, shift=shift_px, psf_index=psf_index, scale0=start,
                             radius=radius, background=bool(fit_back), max_iter=max_iter, tol=tol,
@@ -971,6 +988,62 @@ def fit_crowded_stars(image, psf, positions, *, var=None, psf_index=None, radius
                         ('status', int(head[7]))])
     fit = _make_table(cols, meta)
     return (fit, origin) + ((res[2],) if return_residual else ())
+
+
+_FIT_COLS_REFINED = ('scale', 'shift', 'position', 'flux', 'err_scale', 'err_shift', 'err_flux', 'overlap', 'moved', 'npix',
+                     'free', 'flags', 'status')
+
+
+def refine_crowded_stars(image, psf, positions, *, var=None, psf_index=None, radius=8.0, fit_back=True, start=None,
+                         max_iter=100, tol=1e-10, max_outer=8, pos_tol=1e-3, max_step=0.5, max_move=2.0, min_snr=3.0,
+                         return_residual=False, pixscale=0.2, precision='mixed', device=0):
+    """Crowded-field PSF photometry with free positions, on the GPU: fit_crowded_stars with the positions of the stars
+    refined beside their fluxes -- all stars at once, by Gauss-Newton, no limit on how many stars touch each other.
+    image, var, psf, psf_index, positions, radius, fit_back, start, max_iter and tol: as fit_crowded_stars; `positions`
+    is the start.  The pixels fitted are those within `radius` of the START positions and stay.  Up to `max_outer`
+    (0 .. 16) steps move the stars whose flux stands `min_snr` conditional errors above zero, every step clipped to
+    `max_step` (0 .. 1] pixels per axis and every star kept within `max_move` (0 .. 4] pixels of its start, until the
+    largest step is <= `pos_tol` pixels; the fluxes returned are solved at the final positions.
+
+    Returns (fit, origin) in the form subtract_stars takes (pass it the same psf_index): origin as fit_crowded_stars
+    places it, from the START positions -- it does not move --, and `fit` with one row per star: scale (F), shift (2,
+    arcsec: the REFINED position from the stamp centre), position (2, pixels: the refined (row, column)), flux,
+    err_scale, err_shift (2, arcsec) and err_flux (CONDITIONAL errors: the other stars held fixed), overlap, moved (2,
+    arcsec: refined minus start), npix, free (the steps in which the star moved), flags (FRAME_FREE_HELD,
+    FRAME_FREE_BOUND, FRAME_FREE_CLIPPED of muse_psfr_amd) and status (0 fitted, 1 off the frame, 2 left out).
+    fit.meta: back, err_back, chi2, npix, iterations (of the closing solve), residual, status (0 positions and fluxes
+    converged, 1 fitted but not converged, 2 nothing fitted), outer (steps done), step (the last largest step, pixels),
+    nfree (stars free in the last step), inner (iterations of all solves).  With return_residual also the frame minus
+    the fitted stars at the refined positions."""
+    ps, psf_index, start, origin, shift_px = _crowded_inputs(psf, positions, psf_index, fit_back, start, pixscale)
+    dimpsf = ps.shape[-1]
+    ctx = get_context(128, pixscale, dimpsf, precision, device)
+    res = ctx.fit_frame_psf_free(image, ps, origin, var=var, shift=shift_px, psf_index=psf_index, scale0=start,
+                                 radius=radius, background=bool(fit_back), max_iter=max_iter, tol=tol,
+                                 max_outer=max_outer, pos_tol=pos_tol, max_step=max_step, max_move=max_move,
+                                 min_snr=min_snr, return_residual=return_residual)
+    rows, shifts, head = res[0], res[1], res[2]
+    cols = OrderedDict()
+    cols['scale'] = rows[:, 0].copy()
+    cols['shift'] = shifts * pixscale
+    cols['position'] = (origin + dimpsf // 2) + shifts
+    cols['flux'] = rows[:, 2].copy()
+    cols['err_scale'] = rows[:, 1].copy()
+    cols['err_shift'] = rows[:, 10:12] * pixscale
+    cols['err_flux'] = rows[:, 3].copy()
+    cols['overlap'] = rows[:, 4].copy()
+    cols['moved'] = rows[:, 12:14] * pixscale
+    cols['npix'] = rows[:, 5].astype(np.int64)
+    cols['free'] = rows[:, 15].astype(np.int64)
+    cols['flags'] = rows[:, 14].astype(np.int64)
+    cols['status'] = rows[:, 7].astype(np.int64)
+    assert tuple(cols) == _FIT_COLS_REFINED
+    meta = OrderedDict([('back', float(head[0])), ('err_back', float(head[1])), ('chi2', float(head[2])),
+                        ('npix', int(head[3])), ('iterations', int(head[4])), ('residual', float(head[5])),
+                        ('status', int(head[7])), ('outer', int(head[8])), ('step', float(head[9])),
+                        ('nfree', int(head[10])), ('inner', int(head[11]))])
+    fit = _make_table(cols, meta)
+    return (fit, origin) + ((res[3],) if return_residual else ())
 
 
 _FIT_COLS_CROWDED_SPECTRA = ('shift', 'scale', 'flux', 'err_scale', 'err_flux', 'overlap', 'npix', 'status')
