@@ -842,7 +842,8 @@ int mpsfr_fit_frame_psf(mpsfr_ctx* ctx, int ny, int nx, const double* image, con
  * 36 nstar + 8 ceil(ny nx / 4096) + 11 doubles and 6 nstar + 12 int32.
  * on_device as mpsfr_render_stars.  MPSFR_E_INVALID, outputs untouched, nothing queued: whatever mpsfr_fit_frame_psf
  * refuses; a NULL shift_out; max_outer, pos_tol, max_step, max_move or min_snr out of range or not finite.  The cube
- * form (one position, the layers side by side) is the follow-up.  Timed under the fit's profiling id. */
+ * form (one position from all layers, the layers side by side) is mpsfr_fit_cube_psf_free below.  Timed under the fit's
+ * profiling id. */
 #define MPSFR_NFRAMEFREE 16               /* doubles per star in star_out */
 #define MPSFR_NFRAMEFREE_HEAD 12          /* doubles in head_out */
 #define MPSFR_FRAME_FREE_MAX_OUTER 16
@@ -893,6 +894,86 @@ int mpsfr_fit_cube_psf(mpsfr_ctx* ctx, int nl, int ny, int nx, const double* cub
                        const double* layer_shift, const double* scale0, double radius, int flags, int max_iter,
                        double tol, int layer_batch, double* star_out, double* head_out, double* resid_out,
                        int on_device);
+
+/* Crowded-field photometry of a cube with free positions: ONE position per star from all layers jointly, each layer
+ * with its own PSF and its own refraction offset -- mpsfr_fit_frame_psf_free's Gauss-Newton loop on the layers of
+ * mpsfr_fit_cube_psf, all layers side by side in the same kernels.
+ *
+ * Inputs.  cube, var, psf, psf_index, origin, layer_shift, scale0, radius, flags, max_iter, tol: as for
+ * mpsfr_fit_cube_psf.  shift: the start s0.  max_outer, pos_tol, max_step, max_move, min_snr: as for
+ * mpsfr_fit_frame_psf_free, with the same ranges.  There is no layer_batch: all layers are solved together.
+ *
+ * Objective.  The shift of star k in layer l is s_k + layer_shift[l] per axis, one rounded addition, as for
+ * mpsfr_fit_cube_psf.  Per layer, once, from s0, by mpsfr_fit_cube_psf's own judging: the valid pixels, accept[l][k]
+ * and Omega_l (the discs around the START centres of layer l); they stay for the whole call.  A layer with fewer than
+ * one accepted star, or with |Omega_l| < acc_l + [b] + 1, is DEAD: nothing of it is fitted, its head status is 2, and
+ * the other layers are blind to it.  Minimised over the F_kl of the accepted stars, one s_k per free star and, with
+ * MPSFR_FIT_BACKGROUND, one b_l per layer:
+ *     sum_l sum over Omega_l of w_l (D_l - b_l - sum_k F_kl P~_kl(s_k + t_l))^2,          t_l = layer_shift[l].
+ * 1. Opening solve: all F_kl, b_l at s0 from scale0, positions held.
+ * 2. Up to max_outer joint Gauss-Newton steps.  Layer l CARRIES star k in a step when the star is accepted in l, F_kl
+ *    from the solve before is finite and > 0, F_kl > min_snr err_F,kl with err_F,kl = sqrt(s2_l / N_kk,l) and
+ *    s2_l = chi2_l / (|Omega_l| - acc_l - [b]), both at the current shifts from the opening pass of the step (as
+ *    mpsfr_fit_frame_psf_free takes them per frame), and both derivative norms B_AA,kl, B_CC,kl are positive and
+ *    finite.  Star k is FREE when at least one live layer carries it.  No star is free when
+ *    sum over the live layers of |Omega_l| < sum over the live layers of (acc_l + [b]) + 2 A + 1, A the number of
+ *    stars accepted in some live layer.  The linear problem has the unknowns (F_kl, b_l, delta_k); the column of
+ *    delta_k,y is sum over the layers that carry k of F0_kl dP~_kl/ds_y, F0 the flux before the step, the exact
+ *    derivatives of the cubic-convolution taps; the same for x.  It is solved by Jacobi-preconditioned conjugate
+ *    gradients on the normal equations, matrix-free, from the F and b before and delta = 0, over ONE vector of
+ *    nl (nstar + 1) + 2 nstar places (layer after layer its F and b, then delta_y, then delta_x) with a live mask.  The
+ *    preconditioner of delta_k,y is sum_l F0_kl^2 B_AA,kl, summed in layer order.  Then delta_k is the solved value
+ *    (0 if it is not finite); each axis is clipped to +- max_step, then to |s - s0| <= max_move, then so that
+ *    |s_k + layer_shift[l]| <= 8 after rounding in EVERY layer of the call (the bound depends on layer_shift alone).
+ *    The loop ends when the largest unclipped |delta| over the free stars is <= pos_tol, or when no star is free.
+ * 3. Closing solve at the final shifts, positions held, from the F and b before.
+ * Every solve stops when r.M^-1 r <= tol^2 (g.M^-1 g), g = A^T W D over all live unknowns of all layers and M = diag(N):
+ * mpsfr_fit_frame_psf_free's rule on the joint vector, one done word per solve for all layers; a solve started at its
+ * solution ends at once.  Everything is queued whole, without a host synchronisation.
+ *
+ * star_out [nl][nstar][MPSFR_NFRAMEFIT], head_out [nl][8]: mpsfr_fit_cube_psf's columns of the closing solve, with
+ *     dof_l = |Omega_l| - acc_l - [b];  head 4 the closing solve's iteration count (the same in every layer), 5 the
+ *     layer's own sqrt(r_l.M^-1 r_l / g_l.M^-1 g_l), 7: 2 for a dead layer, else the call's status.
+ * pos_out [nstar][MPSFR_NCUBEFREE_POS]:  0, 1 the final shift   2, 3 its errors   4, 5 final minus start   6 flags
+ *     (MPSFR_FRAME_FREE_HELD: free in no layer in the last outer step that ran; _BOUND, _CLIPPED of the last free step)
+ *     7 outer steps in which the star was free.  A star accepted in no live layer keeps its input shift and zeros.
+ *   The position errors are conditional on the other stars, as err_F is.  S_k = the sum over the layers that carried k
+ *   in its last free step of (F_kl^2 / s2_l) times the 2 x 2 Schur complement of (a, c) over F in that layer's 3 x 3
+ *   block of N of that step, F_kl and s2_l those of the closing solve, in layer order; the errors are the roots of the
+ *   diagonal of S_k^-1, and 0 for a star that was never free or where that is not positive and finite.
+ * shift_out [nstar][2], required: the final shifts, at the pitch mpsfr_fit_cube_psf and mpsfr_render_stars read.
+ * call_out [MPSFR_NCUBEFREE_CALL]:  0 sum of chi2_l   1 sum of dof_l - 2 (stars ever free)   2 outer steps done
+ *     3 the last largest |delta|   4 free stars in the last step   5 inner iterations summed over all solves
+ *     6 status: 0 the position test AND the closing solve's stop test have passed, 1 anything else that was fitted,
+ *     2 every layer dead   7 the last joint sqrt(r.M^-1 r / g.M^-1 g).
+ * resid_out [nl][ny][nx] or NULL: layer l is bit for bit mpsfr_render_stars(MPSFR_RENDER_SUBTRACT) with
+ *   shift_out + layer_shift[l] and column 0 of layer l over its accepted stars.
+ *
+ * The same call gives the same bits, a mixed context those of an f64 one, host and device pointers the same; no
+ * floating-point atomics, every sum in a fixed order: star-index order in the walks, mpsfr_fit_frame_psf's tree in the
+ * projections, layer order wherever layers are summed (the places of one layer are summed by one wave, lane j taking
+ * the places j, j + 64, ..., then the wave's ladder; a joint scalar product is the sum over the layers plus the sum
+ * over the delta places).  mpsfr_fit_frame_psf's two power-of-two laws hold on the whole cube: they scale the fluxes,
+ * errors, chi2 and N_kk exactly, and every position, position error, flag and count keeps its bits.  At nl = 1 the
+ * call agrees with mpsfr_fit_frame_psf_free within the bounds of the two solves, not in bits: there the unknowns are
+ * a = F delta, here delta itself.
+ * Work memory, in one buffer of the context, all layers resident: render's lists once; per layer two frames of
+ * doubles, 25 nstar + 8 ceil(ny nx / 4096) + 17 doubles and 4 nstar + 5 int32; once 14 nstar + 10 doubles and
+ * 5 nstar + 11 int32.  A call that needs more than MPSFR_CUBE_FREE_WORK_BYTES is refused (a budget, not a measured
+ * value): positions come from a few dozen layers or bins, the spectra of a whole cube from mpsfr_fit_cube_psf at
+ * shift_out.  The host form stages everything once and copies back.
+ * MPSFR_E_INVALID, outputs untouched, nothing queued: whatever mpsfr_fit_cube_psf and mpsfr_fit_frame_psf_free refuse;
+ * a NULL pos_out, shift_out or call_out; work memory above the budget.  MPSFR_E_NOMEM if the work memory cannot be
+ * had.  Timed under the fit's profiling id. */
+#define MPSFR_NCUBEFREE_POS 8             /* doubles per star in pos_out */
+#define MPSFR_NCUBEFREE_CALL 8            /* doubles in call_out */
+#define MPSFR_CUBE_FREE_WORK_BYTES ((size_t)4 << 30)    /* budget of work memory of one call */
+int mpsfr_fit_cube_psf_free(mpsfr_ctx* ctx, int nl, int ny, int nx, const double* cube, const double* var, int nstar,
+                            int npsf, const double* psf, const int32_t* psf_index, const int32_t* origin,
+                            const double* shift, const double* layer_shift, const double* scale0, double radius,
+                            int flags, int max_iter, double tol, int max_outer, double pos_tol, double max_step,
+                            double max_move, double min_snr, double* star_out, double* head_out, double* pos_out,
+                            double* shift_out, double* call_out, double* resid_out, int on_device);
 
 /* The stages of the path as the reference exports them (muse_psfr/__init__.py:16: `from .psfrec import *`),
  * for a caller that holds its own PSD or its own stamps.  Host buffers, synchronous, float64; the same

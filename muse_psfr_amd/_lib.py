@@ -57,6 +57,9 @@ FRAME_FREE_MAX_MOVE = 4.0    # largest max_move in pixels (MPSFR_FRAME_FREE_MAX_
 FRAME_FREE_HELD = 1          # flag in column 14: held in the last outer step (MPSFR_FRAME_FREE_HELD)
 FRAME_FREE_BOUND = 2         # resting on max_move or on the +-8 bound (MPSFR_FRAME_FREE_BOUND)
 FRAME_FREE_CLIPPED = 4       # the last step was clipped by max_step (MPSFR_FRAME_FREE_CLIPPED)
+NCUBEFREE_POS = 8            # doubles per star of pos_out of mpsfr_fit_cube_psf_free (MPSFR_NCUBEFREE_POS)
+NCUBEFREE_CALL = 8           # doubles of its call_out (MPSFR_NCUBEFREE_CALL)
+CUBE_FREE_WORK_BYTES = 4 << 30   # budget of work memory of one such call (MPSFR_CUBE_FREE_WORK_BYTES)
 DIM_AO = 80
 PREC_MIXED, PREC_F64 = 0, 1
 E_GRID = -3
@@ -164,6 +167,10 @@ def load():
     lib.mpsfr_fit_cube_psf.argtypes = [p, C.c_int, C.c_int, C.c_int, p, p, C.c_int, C.c_int, p, p, p, p, p, p, C.c_double,
                                        C.c_int, C.c_int, C.c_double, C.c_int, p, p, p, C.c_int]
     lib.mpsfr_fit_cube_psf.restype = C.c_int
+    lib.mpsfr_fit_cube_psf_free.argtypes = [p, C.c_int, C.c_int, C.c_int, p, p, C.c_int, C.c_int, p, p, p, p, p, p,
+                                            C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double,
+                                            C.c_double, C.c_double, p, p, p, p, p, p, C.c_int]
+    lib.mpsfr_fit_cube_psf_free.restype = C.c_int
     lib.mpsfr_simul_psd.argtypes = [p, C.c_double, C.c_double, C.c_double, C.c_int, dp, C.c_double, C.c_int, u8p, u8p, dp]
     lib.mpsfr_simul_psd.restype = C.c_int
     lib.mpsfr_psf_from_psd.argtypes = [p, C.c_int, dp, C.c_int, dp, dp]
@@ -211,7 +218,7 @@ def load():
 
 
 EXPORTS = ['mpsfr_create', 'mpsfr_destroy', 'mpsfr_last_error', 'mpsfr_set_option',
-           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_fit_stamps_psf', 'mpsfr_fit_groups_psf', 'mpsfr_fit_spectra_psf', 'mpsfr_stamp_metrics', 'mpsfr_cut_stamps', 'mpsfr_render_stars', 'mpsfr_find_stars', 'mpsfr_group_stars', 'mpsfr_fit_frame_psf', 'mpsfr_fit_frame_psf_free', 'mpsfr_fit_cube_psf', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
+           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_fit_stamps_psf', 'mpsfr_fit_groups_psf', 'mpsfr_fit_spectra_psf', 'mpsfr_stamp_metrics', 'mpsfr_cut_stamps', 'mpsfr_render_stars', 'mpsfr_find_stars', 'mpsfr_group_stars', 'mpsfr_fit_frame_psf', 'mpsfr_fit_frame_psf_free', 'mpsfr_fit_cube_psf', 'mpsfr_fit_cube_psf_free', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
            'mpsfr_psd_to_psf',
            'mpsfr_convolve_stamps', 'mpsfr_fit_rows', 'mpsfr_sync', 'mpsfr_last_ticket', 'mpsfr_wait', 'mpsfr_abandon',
            'mpsfr_stream', 'mpsfr_stream_wait', 'mpsfr_wait_event',
@@ -1323,6 +1330,77 @@ class Context:
                             layer_shift_ptr, scale0_ptr, radius, flags, max_iter, tol, layer_batch, star_out_ptr, head_ptr,
                             resid_ptr, 1)
 
+    def _call_cube_free(self, nl, ny, nx, cube, var, nstar, npsf, psf, index, origin, shift, layer_shift, scale0, radius,
+                        flags, max_iter, tol, free, rows, head, pos, shift_out, call, resid, on_device):
+        p = _devptr if on_device else _vptr
+        max_outer, pos_tol, max_step, max_move, min_snr = free
+        _check(self.lib.mpsfr_fit_cube_psf_free(self._h, int(nl), int(ny), int(nx), p(cube), p(var), int(nstar),
+                                                int(npsf), p(psf), p(index), p(origin), p(shift), p(layer_shift),
+                                                p(scale0), float(radius), flags, int(max_iter), float(tol),
+                                                int(max_outer), float(pos_tol), float(max_step), float(max_move),
+                                                float(min_snr), p(rows), p(head), p(pos), p(shift_out), p(call),
+                                                p(resid), on_device))
+
+    def fit_cube_psf_free(self, cube, psf, origin, *, var=None, shift=None, layer_shift=None, psf_index=None,
+                          scale0=None, radius=8.0, background=True, max_iter=100, tol=1e-10, max_outer=8, pos_tol=1e-3,
+                          max_step=0.5, max_move=2.0, min_snr=3.0, return_residual=False):
+        """Crowded-field photometry of a cube with free positions (mpsfr_fit_cube_psf_free): ONE shift per star from
+        all layers of `cube` jointly -- fit_frame_psf_free's Gauss-Newton loop on the layers of fit_cube_psf, every
+        layer with its own models psf[:, l] and its own offset layer_shift[l], all layers side by side on the GPU.
+        The arrays are fit_cube_psf's (`shift` is the start), the outer loop's parameters fit_frame_psf_free's.  A
+        layer carries a star when the star is accepted there with F > min_snr err_F; a star is free when some layer
+        carries it; a layer with no accepted star or too few pixels is dead (head status 2) and the others are blind
+        to it.  Returns (rows, pos, shifts, head, call) and, with return_residual, the residual cube at the final
+        shifts.  rows (nl, n, NFRAMEFIT), head (nl, NFRAMEFIT): fit_cube_psf's columns of the closing solve (head 4 the
+        closing solve's iterations, 5 the layer's own relative residual, 7: 2 for a dead layer, else the call's
+        status).  pos (n, NCUBEFREE_POS): 0-1 the final shift, 2-3 its conditional errors, 4-5 final minus start, 6
+        flags (FRAME_FREE_HELD, FRAME_FREE_BOUND, FRAME_FREE_CLIPPED), 7 the outer steps in which the star was free.
+        shifts (n, 2): what fit_cube_psf takes as shift.  call (NCUBEFREE_CALL,): 0 chi2 summed, 1 its degrees of
+        freedom, 2 outer steps, 3 the last largest step, 4 free stars in the last step, 5 inner iterations in all, 6
+        status (0 positions and closing solve converged, 1 anything else fitted, 2 every layer dead), 7 the last
+        joint relative residual.  All layers are resident: a call above CUBE_FREE_WORK_BYTES of work memory is
+        refused (take the positions from fewer layers, the spectra from fit_cube_psf)."""
+        cu, va, ps, ix, og, sh, ls, s0, radius, flags, max_iter, tol, free = cube_free_arguments(
+            cube, var, psf, psf_index, origin, shift, layer_shift, scale0, radius, background, max_iter, tol, max_outer,
+            pos_tol, max_step, max_move, min_snr, self.dimpsf)
+        if not isinstance(return_residual, (bool, np.bool_)):
+            raise ValueError('return_residual must be True or False')
+        nl, ny, nx = cu.shape
+        n = og.shape[0]
+        rows = np.empty((nl, n, NFRAMEFIT))
+        head = np.empty((nl, NFRAMEFIT))
+        pos = np.empty((n, NCUBEFREE_POS))
+        shifts = np.empty((n, 2))
+        call = np.empty(NCUBEFREE_CALL)
+        resid = np.empty((nl, ny, nx)) if return_residual else None
+        self._call_cube_free(nl, ny, nx, cu, va, n, ps.shape[0], ps, ix, og, sh, ls, s0, radius, flags, max_iter, tol,
+                             free, rows, head, pos, shifts, call, resid, 0)
+        return (rows, pos, shifts, head, call) + ((resid,) if return_residual else ())
+
+    def fit_cube_psf_free_device(self, nl, ny, nx, cube_ptr, nstar, npsf, psf_ptr, origin_ptr, star_out_ptr, head_ptr,
+                                 pos_ptr, shift_out_ptr, call_ptr, *, var_ptr=None, shift_ptr=None, layer_shift_ptr=None,
+                                 psf_index_ptr=None, scale0_ptr=None, resid_ptr=None, radius=8.0, background=True,
+                                 max_iter=100, tol=1e-10, max_outer=8, pos_tol=1e-3, max_step=0.5, max_move=2.0,
+                                 min_snr=3.0):
+        """Device-buffer form (asynchronous, on_device = 1) of fit_cube_psf_free: the pointers of fit_cube_psf_device,
+        with `pos_ptr` ([nstar][NCUBEFREE_POS] float64), `shift_out_ptr` ([nstar][2] float64: what fit_cube_psf_device
+        takes as shift_ptr) and `call_ptr` ([NCUBEFREE_CALL] float64).  The whole call -- every solve of every outer
+        step, all layers -- is queued on the context stream without a host synchronisation."""
+        nl = cube_fit_layers(nl)
+        frame_shape(ny, nx)
+        nstar = frame_fit_stars(nstar)
+        _positive_int('npsf', npsf)
+        _device_pointers(cube_ptr=cube_ptr, psf_ptr=psf_ptr, origin_ptr=origin_ptr, star_out_ptr=star_out_ptr,
+                         head_ptr=head_ptr, pos_ptr=pos_ptr, shift_out_ptr=shift_out_ptr, call_ptr=call_ptr)
+        if not psf_index_ptr and npsf != nstar:
+            raise ValueError('without psf_index_ptr, npsf must equal nstar')
+        radius, flags, max_iter, tol = frame_fit_parameters(radius, background, max_iter, tol)
+        free = frame_free_parameters(max_outer, pos_tol, max_step, max_move, min_snr)
+        cube_free_work(nl, ny, nx, nstar)
+        self._call_cube_free(nl, ny, nx, cube_ptr, var_ptr, nstar, npsf, psf_ptr, psf_index_ptr, origin_ptr, shift_ptr,
+                             layer_shift_ptr, scale0_ptr, radius, flags, max_iter, tol, free, star_out_ptr, head_ptr,
+                             pos_ptr, shift_out_ptr, call_ptr, resid_ptr, 1)
+
     def debug_fetch(self, what, shape):
         out = np.empty(int(np.prod(shape)))
         n = _check(self.lib.mpsfr_debug_fetch(self._h, what.encode(), _dptr(out), out.size))
@@ -1726,6 +1804,40 @@ def cube_fit_arguments(cube, var, psf, psf_index, origin, shift, layer_shift, sc
     layer_batch = cube_fit_batch(layer_batch)
     return (np.ascontiguousarray(cu), None if va is None else np.ascontiguousarray(va), np.ascontiguousarray(ps), ix, og,
             sh, ls, s0, radius, flags, max_iter, tol, layer_batch)
+
+
+def cube_free_work(nl, ny, nx, nstar):
+    """The bytes of work memory of a cube fit with free positions, as mpsfr_fit_cube_psf_free counts them (include/
+    mpsfr.h): render's lists once, per layer two frames and the per-layer vectors, the joint ones once.  Above
+    CUBE_FREE_WORK_BYTES: ValueError, as C refuses the call."""
+    def up(at, align):
+        return (at + align - 1) // align * align
+    nl, ny, nx, n = int(nl), int(ny), int(nx), int(nstar)
+    nt = ((ny + 31) // 32) * ((nx + 31) // 32)
+    npix, nchunk = ny * nx, (ny * nx + 4095) // 4096
+    at = 4 * (nt + nt + nt + 1 + n + 9 * n)                                   # the renderer's lists (int32)
+    at = up(at, 8) + 8 * (nl * (2 * npix + 25 * n + 8 * nchunk + 17) + 14 * n + 10)
+    at += 4 * (nl * (4 * n + 5) + 5 * n + 11)
+    if at > CUBE_FREE_WORK_BYTES:
+        raise ValueError('%d layers of %d x %d pixels and %d stars need %d bytes of work memory, above the budget of '
+                         '%d: take the positions from fewer layers' % (nl, ny, nx, n, at, CUBE_FREE_WORK_BYTES))
+    return at
+
+
+def cube_free_arguments(cube, var, psf, psf_index, origin, shift, layer_shift, scale0, radius, background, max_iter, tol,
+                        max_outer, pos_tol, max_step, max_move, min_snr, dimpsf=40):
+    """(cube, var or None, psf, psf_index, origin, shift, layer_shift or None, scale0 or None, radius, flags, max_iter,
+    tol, (max_outer, pos_tol, max_step, max_move, min_snr)) of a host cube fit with free positions, validated as
+    mpsfr_fit_cube_psf_free validates host arguments (ValueError): the arrays as cube_fit_arguments, the outer loop as
+    frame_free_parameters, the work memory as cube_free_work."""
+    shape, nstar = np.shape(getattr(cube, 'data', cube)), np.shape(origin)[:1]
+    if len(shape) == 3 and nstar and all(0 < v < 1 << 24 for v in shape + nstar):
+        cube_free_work(shape[0], shape[1], shape[2], nstar[0])               # (before any array of that size is made)
+    cu, va, ps, ix, og, sh, ls, s0, radius, flags, max_iter, tol, _ = cube_fit_arguments(
+        cube, var, psf, psf_index, origin, shift, layer_shift, scale0, radius, background, max_iter, tol, 0, dimpsf)
+    free = frame_free_parameters(max_outer, pos_tol, max_step, max_move, min_snr)
+    cube_free_work(cu.shape[0], cu.shape[1], cu.shape[2], og.shape[0])
+    return cu, va, ps, ix, og, sh, ls, s0, radius, flags, max_iter, tol, free
 
 
 def group_parameters(nstar, stride, crit, max_groups):

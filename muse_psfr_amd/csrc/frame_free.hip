@@ -5,36 +5,20 @@
 // preconditioned conjugate gradients over the 3 nstar + 1 unknowns (F [nstar], a [nstar], c [nstar], b) with a live
 // mask: a held star has its F alone, a free star F, a = F delta_y and c = F delta_x on the columns P~, dP~/ds_y, dP~/ds_x.
 //   k_fr_begin     the working shifts, the counters and the scalars of a call
-//   k_fr_walk      the three-column tile walk: sum_k (F_k P~_k + a_k d_y + c_k d_x) at every pixel, in star-index order,
-//                  over the sorted tile lists; the LDS stage and the two-buffer pipeline of k_render_tiles, the
-//                  derivative columns from the second tap vector of each axis (KeysTaps::dw) on the same staged pixels
-//   k_fr_project   one workgroup per accepted star, the footprint batches of k_ff_star<true>: three sums per pass and,
-//                  in the first pass of a solve, the three sums of the data (the stop rule's g) and the six sums of the
-//                  star's 3 x 3 block of N
+//   k_fr_walk      the three-column tile walk and
+//   k_fr_project   the three-column projection with the star's 3 x 3 block of N: frame_free_impl.h, which the cube form
+//                  (cube_free.hip) shares; here in their LAYERS = false forms
 //   k_fr_step      one workgroup: FR_INIT (who is free, the live mask, the first residual, the stop reference),
 //                  FR_ITER (a conjugate-gradient step), FR_APPLY (delta = (a, c) / F, its clips, the new shifts, the
 //                  outer done word), FR_FINAL (the rows)
 // k_ff_reduce, k_ff_ones and the renderer's own walk (first residuals, the residual frame, the overlap) are reused as
 // they are.  Every sum has a fixed order, all arithmetic is fp64, nothing waits for the host.
-#include "frame_fit_impl.h"
+#include "frame_free_impl.h"
 
 namespace mpsfr {
 namespace {
 
-// the tile layout of k_render_tiles (render.hip)
-constexpr int kWThreads = 256;
-constexpr int kWRows = kWThreads / kTile;
-constexpr int kWPix = kTile / kWRows;                         // pixels per thread: adjacent rows of one column
-constexpr int kWWaveRows = 64 / kTile * kWPix;
-constexpr int kWSide = kTile + 3;
-constexpr int kWStride = kWSide + 1;
-constexpr int kWLoads = (kWSide * kWSide + kWThreads - 1) / kWThreads;
-static_assert(kTile * kTile == kWThreads * kWPix && kWRows * kTile == kWThreads, "tile layout");
-
 constexpr int NFREE = 16;                                     // MPSFR_NFRAMEFREE; the head: MPSFR_NFRAMEFREE_HEAD = 12
-constexpr int FLAG_HELD = 1, FLAG_BOUND = 2, FLAG_CLIPPED = 4;
-// the places of a star's block of N: the diagonal (the preconditioner) first
-enum { B_FF = 0, B_AA, B_CC, B_FA, B_FC, B_AC, B_N };
 
 // the scalars of a call: doubles, then ints
 enum { D_RHO = 0, D_RHOG, D_REL, D_WSUM, D_MAXD, D_NDOUBLE };
@@ -45,27 +29,11 @@ enum {
     J_ITER, J_ITERSUM, J_STOP, J_NONE, J_NACC, J_NOMEGA, J_NOUTER, J_NFREE, J_POSOK, J_NINT
 };
 
-template <int T>
-__device__ __forceinline__ double block_max(double v, double* part) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    const int tid = threadIdx.x;
-    __syncthreads();
-    if ((tid & 63) == 0) part[tid >> 6] = v;
-    __syncthreads();
-    double s = part[0];
-#pragma unroll
-    for (int w = 1; w < T / 64; ++w) s = fmax(s, part[w]);
-    return s;
-}
-
 // v, computed here and now: the sums of FR_INIT's reductions one after the other, not all their partials held at once
 __device__ __forceinline__ double settled(double v) {
     asm volatile("" : "+v"(v));
     return v;
 }
-
-__device__ __forceinline__ bool positive_finite(double v) { return v > 0.0 && v < __builtin_inf(); }
 
 __global__ __launch_bounds__(256) void k_fr_begin(int n, const double* __restrict__ shift_in, double* __restrict__ shift0,
                                                   double* __restrict__ wshift, double* __restrict__ x,
@@ -87,212 +55,6 @@ __global__ __launch_bounds__(256) void k_fr_begin(int n, const double* __restric
     }
     if (i < D_NDOUBLE) sd[i] = 0.0;
     if (i < J_NINT) si[i] = i == J_POSOK ? posok : 0;
-}
-
-// One star as a tile sees it (TileStar of render.hip, with the three scales of the star)
-struct WalkStar {
-    int op, oq, r0, c0, three;
-    double f, a, c;
-    const double* P;
-    KeysTaps<double> ty{0.0}, tx{0.0};
-    __device__ __forceinline__ void load(int k, int Y0, int X0, const StarList& stars, const double* vec,
-                                         const int32_t* freem) {
-        const FrameStar star(stars, k);
-        const int n = stars.nstar;
-        op = star.op;
-        oq = star.oq;
-        three = freem[k];
-        f = vec[k];
-        a = three ? vec[n + k] : 0.0;
-        c = three ? vec[2 * n + k] : 0.0;
-        ty = KeysTaps<double>(star.dp);
-        tx = KeysTaps<double>(star.dq);
-        P = star.model(stars);
-        r0 = Y0 - op + ty.f - 1;
-        c0 = X0 - oq + tx.f - 1;
-    }
-    __device__ __forceinline__ void fetch(int tid, double (&pre)[kWLoads]) const {
-#pragma unroll
-        for (int m = 0; m < kWLoads; ++m) {
-            const int e = tid + m * kWThreads, si = e / kWSide, sj = e - si * kWSide;
-            pre[m] = model_pixel(P, r0 + si, c0 + sj, e < kWSide * kWSide);
-        }
-    }
-};
-
-// f val + a py + c px, every product rounded, summed in this order
-__device__ __forceinline__ double three_terms(double f, double val, double a, double py, double c, double px) {
-#pragma clang fp contract(off)
-    const double t0 = f * val, t1 = a * py, t2 = c * px;
-    return (t0 + t1) + t2;
-}
-
-// out = sum_k (vec[k] P~_k + vec[n + k] dP~_k/ds_y + vec[2 n + k] dP~_k/ds_x), the derivative columns for the stars
-// freem marks, over the tile lists of d_ws, which are sorted.  Nothing once *done is set.
-__global__ __launch_bounds__(kWThreads) void k_fr_walk(int ny, int nx, StarList stars, const double* __restrict__ vec,
-                                                       const int32_t* __restrict__ freem,
-                                                       const int* __restrict__ offset, const int* __restrict__ pairs,
-                                                       const int32_t* __restrict__ done, double* __restrict__ out) {
-    __shared__ double stage[2 * kWSide * kWStride];
-    if (*done) return;
-    const int tid = threadIdx.x, lx = tid & (kTile - 1), ly0 = tid / kTile;
-    const int t = blockIdx.y * gridDim.x + blockIdx.x;
-    const int Y0 = blockIdx.y * kTile, X0 = blockIdx.x * kTile, X = X0 + lx;
-    const int first = offset[t], n = offset[t + 1] - first;
-    const int* list = pairs + first;
-    double acc[kWPix];
-    bool on[kWPix];
-#pragma unroll
-    for (int j = 0; j < kWPix; ++j) {
-        on[j] = Y0 + kWPix * ly0 + j < ny && X < nx;
-        acc[j] = 0.0;
-    }
-    // (the pipeline of k_render_tiles: star i + 1 fetched into registers while star i is evaluated, two buffers, one
-    // barrier per star)
-    WalkStar cur, nxt;
-    double pre[kWLoads];
-    int i = 0;
-    if (i < n) {
-        cur.load(list[i], Y0, X0, stars, vec, freem);
-        cur.fetch(tid, pre);
-    }
-    for (int turn = 0; i < n; ++turn) {
-        double* buf = stage + (turn & 1) * (kWSide * kWStride);
-#pragma unroll
-        for (int m = 0; m < kWLoads; ++m) {
-            const int e = tid + m * kWThreads;
-            if (e < kWSide * kWSide) buf[(e / kWSide) * kWStride + e % kWSide] = pre[m];
-        }
-        ++i;
-        if (i < n) {
-            nxt.load(list[i], Y0, X0, stars, vec, freem);
-            nxt.fetch(tid, pre);
-        }
-        __syncthreads();
-        const StagedStamp<kWStride> st{buf};
-        const int q = X - cur.oq;
-        const int pw = Y0 + (tid / 64) * kWWaveRows - cur.op;
-        if (pw + kWWaveRows > -kPsfApron && pw < NS + kPsfApron) {
-#pragma unroll
-            for (int j = 0; j < kWPix; ++j) {
-                const int ly = kWPix * ly0 + j, p = Y0 + ly - cur.op;
-                double val, gy, gx, term;
-                if (cur.three) {          // (the same for the whole workgroup)
-                    psf_interp<double, true>(st, ly * kWStride + lx, p, q, cur.ty, cur.tx, val, gy, gx);
-                    term = three_terms(cur.f, val, cur.a, -gy, cur.c, -gx);     // d/ds = -d/dy
-                } else {
-                    psf_interp<double, false>(st, ly * kWStride + lx, p, q, cur.ty, cur.tx, val, gy, gx);
-                    term = three_terms(cur.f, val, 0.0, 0.0, 0.0, 0.0);
-                }
-                const bool inside = on[j] && p >= -kPsfApron && p < NS + kPsfApron && q >= -kPsfApron &&
-                                    q < NS + kPsfApron;
-                acc[j] = inside ? acc[j] + term : acc[j];
-            }
-        }
-        cur = nxt;
-    }
-#pragma unroll
-    for (int j = 0; j < kWPix; ++j) {
-        const int Y = Y0 + kWPix * ly0 + j;
-        if (on[j]) out[(size_t)Y * nx + X] = acc[j];
-    }
-}
-
-// What the projection reads and writes.  q[k], q[n + k], q[2 n + k] = sum W col (V + csign c) for the columns of star k
-// (the derivative ones: of a star freem marks; FIRST: of every accepted star); FIRST: g the same of the data D, and
-// blk[6 k ..] the star's block of N.
-struct FreeProjection {
-    const double *W, *V, *D, *c;
-    double csign;
-    const int32_t *accept, *freem, *done;
-    double *q, *g, *blk;
-};
-
-template <bool FIRST>
-__global__ __launch_bounds__(kStarThreads) void k_fr_project(int ny, int nx, StarList stars, FreeProjection io) {
-    __shared__ double stage[kFootSide * kFootStride];
-    __shared__ double part[kStarThreads / 64];
-    const int k = blockIdx.x, tid = threadIdx.x, n = stars.nstar;
-    if ((io.done && *io.done) || !io.accept[k]) return;
-    const bool three = FIRST || io.freem[k] != 0;
-    const FrameStar star(stars, k);
-    const int op = star.op, oq = star.oq;
-    const double* P = star.model(stars);
-    const KeysTaps<double> ty(star.dp), tx(star.dq);
-    const int r0 = ty.f - 1 - kPsfApron, c0 = tx.f - 1 - kPsfApron;
-    for (int e = tid; e < kFootSide * kFootSide; e += kStarThreads) {
-        const int i = e / kFootSide, j = e - i * kFootSide;
-        stage[i * kFootStride + j] = model_pixel(P, r0 + i, c0 + j);
-    }
-    __syncthreads();
-    const StagedStamp<kFootStride> st{stage};
-    const double cval = io.c ? io.csign * *io.c : 0.0;
-    double sq[3] = {0.0, 0.0, 0.0}, sg[3] = {0.0, 0.0, 0.0}, sb[B_N] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-#pragma unroll 1
-    for (int m0 = 0; m0 < kFootShare; m0 += kFootBatch) {
-        double fa[kFootBatch], fb[kFootBatch], fd[kFootBatch];
-#pragma unroll
-        for (int j = 0; j < kFootBatch; ++j) {
-            const int e = tid + (m0 + j) * kStarThreads, pr = e / kPsfSide, qc = e - pr * kPsfSide;
-            const int Y = op - kPsfApron + pr, X = oq - kPsfApron + qc;
-            const bool on = e < kFootPix && Y >= 0 && Y < ny && X >= 0 && X < nx;
-            const size_t src = on ? (size_t)Y * nx + (size_t)X : 0;
-            fa[j] = io.W[src];
-            fb[j] = io.V[src];
-            if constexpr (FIRST) fd[j] = io.D[src];
-        }
-#pragma unroll
-        for (int j = 0; j < kFootBatch; ++j) {
-            const int e = tid + (m0 + j) * kStarThreads, pr = e / kPsfSide, qc = e - pr * kPsfSide;
-            const int Y = op - kPsfApron + pr, X = oq - kPsfApron + qc;
-            const bool on = e < kFootPix && Y >= 0 && Y < ny && X >= 0 && X < nx;
-            const double w = fa[j];
-            if (on && w > 0.0) {                      // (W is 0 outside Omega; a masked datum may be NaN: selected out)
-                double val, gy, gx;
-                const double u = w * (fb[j] + cval);
-                if (three) {
-                    psf_interp<double, true>(st, pr * kFootStride + qc, 0, 0, ty, tx, val, gy, gx);
-                    const double py = -gy, px = -gx;
-                    sq[0] += u * val;
-                    sq[1] += u * py;
-                    sq[2] += u * px;
-                    if constexpr (FIRST) {
-                        const double ud = w * fd[j], wv = w * val, wy = w * py;
-                        sg[0] += ud * val;
-                        sg[1] += ud * py;
-                        sg[2] += ud * px;
-                        sb[B_FF] += wv * val;
-                        sb[B_AA] += wy * py;
-                        sb[B_CC] += (w * px) * px;
-                        sb[B_FA] += wv * py;
-                        sb[B_FC] += wv * px;
-                        sb[B_AC] += wy * px;
-                    }
-                } else {
-                    psf_interp<double, false>(st, pr * kFootStride + qc, 0, 0, ty, tx, val, gy, gx);
-                    sq[0] += u * val;
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-        if (j == 0 || three) {                        // (the same for the whole workgroup)
-            const double tq = block_sum<kStarThreads>(sq[j], part);
-            if (tid == 0) io.q[j * n + k] = tq;
-        }
-    if constexpr (FIRST) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const double tg = block_sum<kStarThreads>(sg[j], part);
-            if (tid == 0) io.g[j * n + k] = tg;
-        }
-#pragma unroll
-        for (int j = 0; j < B_N; ++j) {
-            const double tb = block_sum<kStarThreads>(sb[j], part);
-            if (tid == 0) io.blk[(size_t)B_N * k + j] = tb;
-        }
-    }
 }
 
 enum { FR_INIT = 0, FR_ITER, FR_APPLY, FR_FINAL };
@@ -597,9 +359,9 @@ void launch_fit_frame_free(hipStream_t s, int ny, int nx, const double* d_image,
     auto project = [&](bool first, const double* V, const double* c, double csign, const int32_t* dn) {
         const FreeProjection io{w.W, V, d_image, c, csign, w.accept, w.freem, dn, w.q, w.g, w.blk};
         if (first)
-            hipLaunchKernelGGL(k_fr_project<true>, dim3(n), dim3(kStarThreads), 0, s, ny, nx, stars, io);
+            hipLaunchKernelGGL((k_fr_project<true, false>), dim3(n), dim3(kStarThreads), 0, s, ny, nx, stars, io);
         else
-            hipLaunchKernelGGL(k_fr_project<false>, dim3(n), dim3(kStarThreads), 0, s, ny, nx, stars, io);
+            hipLaunchKernelGGL((k_fr_project<false, false>), dim3(n), dim3(kStarThreads), 0, s, ny, nx, stars, io);
     };
     auto reduce = [&](const double* V, const double* c, double csign, double* partial, const int32_t* dn) {
         hipLaunchKernelGGL(k_ff_reduce<false>, dim3(w.nchunk), dim3(256), 0, s, w.npix, w.nchunk, w.W, V, c, nu, csign,
@@ -625,8 +387,8 @@ void launch_fit_frame_free(hipStream_t s, int ny, int nx, const double* d_image,
         reduce(d_image, nullptr, 1.0, w.partial_d, outer);
         step(std::integral_constant<int, FR_INIT>{}, gn, nullptr);
         for (int it = 0; it < max_iter; ++it) {           // q = N p: one tile walk, one projection, one frame reduction
-            hipLaunchKernelGGL(k_fr_walk, dim3(w.lists.ntx, w.lists.nty), dim3(kWThreads), 0, s, ny, nx, stars, w.p,
-                               w.freem, w.lists.offset, w.lists.pairs, inner, w.M);
+            hipLaunchKernelGGL(k_fr_walk<false>, dim3(w.lists.ntx, w.lists.nty), dim3(kWThreads), 0, s, ny, nx, stars,
+                               w.p, w.freem, w.lists.offset, w.lists.pairs, inner, w.M, NoFreeLayers{});
             project(false, w.M, pb, 1.0, inner);
             if (back) reduce(w.M, pb, 1.0, w.partial, inner);
             step(std::integral_constant<int, FR_ITER>{}, gn, inner);

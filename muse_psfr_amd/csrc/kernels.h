@@ -380,6 +380,19 @@ size_t cube_fit_workspace_bytes(int ny, int nx, int nstar, int layers);
 void launch_fit_cube(hipStream_t s, int ny, int nx, int layers, const double* d_cube, const double* d_var,
                      StarList stars, const double* d_scale0, double radius, bool background, int max_iter, double tol,
                      double* d_star_out, double* d_head_out, double* d_resid_out, void* d_ws);
+// Crowded-field photometry of a cube with free positions (cube_free.hip; mpsfr_fit_cube_psf_free, include/mpsfr.h):
+// launch_fit_frame_free's loop over all `layers` layers jointly, one shift per star -- the arrays of launch_fit_cube,
+// d_star_out [layers][nstar][8], d_head_out [layers][8], d_pos_out [nstar][8], d_shift_out [nstar][2], d_call_out [8],
+// d_resid_out [layers][ny][nx] (or nullptr); everything is queued at once.  d_ws: cube_free_workspace_bytes(ny, nx,
+// nstar, layers) bytes -- the renderer's lists once; per layer two frames of doubles, 25 nstar + 8 ceil(ny nx / 4096) +
+// 17 doubles and 4 nstar + 5 int32; once 14 nstar + 10 doubles and 5 nstar + 11 int32 (CubeFreeWork, cube_free.hip); the
+// launch writes every word of it before it reads it.
+size_t cube_free_workspace_bytes(int ny, int nx, int nstar, int layers);
+void launch_fit_cube_free(hipStream_t s, int ny, int nx, int layers, const double* d_cube, const double* d_var,
+                          StarList stars, const double* d_scale0, double radius, bool background, int max_iter,
+                          double tol, int max_outer, double pos_tol, double max_step, double max_move, double min_snr,
+                          double* d_star_out, double* d_head_out, double* d_pos_out, double* d_shift_out,
+                          double* d_call_out, double* d_resid_out, void* d_ws);
 // band-integrated stamps (band.hip): d_fin [ntb][nl][40][40] (float if fin_f32, else double) reduced over wavelength
 // into d_out [ntb][nband][40][40] double with the weights d_w [nl][band_stride(nband)] (zero beyond nband)
 constexpr int MAX_BANDS = 16;    // MPSFR_MAX_BANDS

@@ -3164,6 +3164,20 @@ static_assert(MPSFR_NFRAMEFREE == 16 && MPSFR_NFRAMEFREE_HEAD == 12 && MPSFR_FRA
                   MPSFR_FRAME_FREE_BOUND == 2 && MPSFR_FRAME_FREE_CLIPPED == 4,
               "k_fr_step<FR_FINAL> row layout and flags");
 
+// what mpsfr_fit_frame_psf_free and mpsfr_fit_cube_psf_free refuse alike: the parameters of the outer loop
+static int frame_free_ranges(const char* who, int max_outer, double pos_tol, double max_step, double max_move,
+                             double min_snr) {
+    if (max_outer < 0 || max_outer > MPSFR_FRAME_FREE_MAX_OUTER)
+        return fail(MPSFR_E_INVALID, "%s: max_outer=%d outside 0..%d", who, max_outer, MPSFR_FRAME_FREE_MAX_OUTER);
+    if (!(pos_tol > 0.0 && std::isfinite(pos_tol))) return fail(MPSFR_E_INVALID, "%s: pos_tol must be finite and > 0", who);
+    if (!(max_step > 0.0 && max_step <= MPSFR_FRAME_FREE_MAX_STEP))
+        return fail(MPSFR_E_INVALID, "%s: max_step must lie in (0, %g] pixels", who, MPSFR_FRAME_FREE_MAX_STEP);
+    if (!(max_move > 0.0 && max_move <= MPSFR_FRAME_FREE_MAX_MOVE))
+        return fail(MPSFR_E_INVALID, "%s: max_move must lie in (0, %g] pixels", who, MPSFR_FRAME_FREE_MAX_MOVE);
+    if (!(min_snr >= 0.0 && std::isfinite(min_snr))) return fail(MPSFR_E_INVALID, "%s: min_snr must be finite and >= 0", who);
+    return MPSFR_OK;
+}
+
 int mpsfr_fit_frame_psf_free(mpsfr_ctx* c, int ny, int nx, const double* image, const double* var, int nstar, int npsf,
                              const double* psf, const int32_t* psf_index, const int32_t* origin, const double* shift,
                              const double* scale0, double radius, int flags, int max_iter, double tol, int max_outer,
@@ -3175,14 +3189,7 @@ int mpsfr_fit_frame_psf_free(mpsfr_ctx* c, int ny, int nx, const double* image, 
                     "%s: bad argument (image, psf, origin, star_out, shift_out and head_out are required)", who);
     int rc;
     if ((rc = frame_fit_ranges(who, ny, nx, nstar, npsf, psf_index, radius, flags, max_iter, tol))) return rc;
-    if (max_outer < 0 || max_outer > MPSFR_FRAME_FREE_MAX_OUTER)
-        return fail(MPSFR_E_INVALID, "%s: max_outer=%d outside 0..%d", who, max_outer, MPSFR_FRAME_FREE_MAX_OUTER);
-    if (!(pos_tol > 0.0 && std::isfinite(pos_tol))) return fail(MPSFR_E_INVALID, "%s: pos_tol must be finite and > 0", who);
-    if (!(max_step > 0.0 && max_step <= MPSFR_FRAME_FREE_MAX_STEP))
-        return fail(MPSFR_E_INVALID, "%s: max_step must lie in (0, %g] pixels", who, MPSFR_FRAME_FREE_MAX_STEP);
-    if (!(max_move > 0.0 && max_move <= MPSFR_FRAME_FREE_MAX_MOVE))
-        return fail(MPSFR_E_INVALID, "%s: max_move must lie in (0, %g] pixels", who, MPSFR_FRAME_FREE_MAX_MOVE);
-    if (!(min_snr >= 0.0 && std::isfinite(min_snr))) return fail(MPSFR_E_INVALID, "%s: min_snr must be finite and >= 0", who);
+    if ((rc = frame_free_ranges(who, max_outer, pos_tol, max_step, max_move, min_snr))) return rc;
     if (!on_device) {
         if ((rc = check_model_list(who, "shift", nstar, npsf, psf_index, shift, (size_t)2 * nstar))) return rc;
         if ((rc = check_frame_stars(who, nstar, origin, scale0, "scale0"))) return rc;
@@ -3210,6 +3217,34 @@ int mpsfr_fit_frame_psf_free(mpsfr_ctx* c, int ny, int nx, const double* image, 
     });
 }
 
+// what mpsfr_fit_cube_psf and mpsfr_fit_cube_psf_free refuse alike on host pointers: the model list, the stars, scale0,
+// layer_shift and the summed shifts
+static int cube_fit_host_arguments(const char* who, int nl, int nstar, int npsf, const int32_t* psf_index,
+                                   const int32_t* origin, const double* shift, const double* layer_shift,
+                                   const double* scale0) {
+    int rc;
+    if ((rc = check_model_list(who, "shift", nstar, npsf, psf_index, shift, (size_t)2 * nstar))) return rc;
+    if ((rc = check_frame_stars(who, nstar, origin, nullptr, "scale0"))) return rc;
+    if (scale0)
+        for (size_t k = 0; k < (size_t)nl * nstar; ++k)
+            if (!std::isfinite(scale0[k])) return fail(MPSFR_E_INVALID, "%s: a scale0 that is not finite", who);
+    if (layer_shift) {
+        // (rounding is monotone: the sums of a layer stay in range when those of the extreme shifts do)
+        double lo[2] = {0.0, 0.0}, hi[2] = {0.0, 0.0};
+        for (int k = 0; shift && k < 2 * nstar; ++k) {
+            lo[k & 1] = k < 2 ? shift[k] : std::min(lo[k & 1], shift[k]);
+            hi[k & 1] = k < 2 ? shift[k] : std::max(hi[k & 1], shift[k]);
+        }
+        for (int k = 0; k < 2 * nl; ++k) {
+            const double t = layer_shift[k];
+            if (!std::isfinite(t)) return fail(MPSFR_E_INVALID, "%s: a layer_shift that is not finite", who);
+            if (!(std::fabs(lo[k & 1] + t) <= MPSFR_FIT_PSF_MAX_SHIFT && std::fabs(hi[k & 1] + t) <= MPSFR_FIT_PSF_MAX_SHIFT))
+                return fail(MPSFR_E_INVALID, "%s: shift + layer_shift beyond 8 pixels", who);
+        }
+    }
+    return MPSFR_OK;
+}
+
 int mpsfr_fit_cube_psf(mpsfr_ctx* c, int nl, int ny, int nx, const double* cube, const double* var, int nstar, int npsf,
                        const double* psf, const int32_t* psf_index, const int32_t* origin, const double* shift,
                        const double* layer_shift, const double* scale0, double radius, int flags, int max_iter,
@@ -3224,25 +3259,7 @@ int mpsfr_fit_cube_psf(mpsfr_ctx* c, int nl, int ny, int nx, const double* cube,
         return fail(MPSFR_E_INVALID, "%s: nl=%d outside 1..%d", who, nl, MPSFR_CUBE_FIT_MAX_LAYERS);
     if (layer_batch < 0) return fail(MPSFR_E_INVALID, "%s: layer_batch=%d is negative", who, layer_batch);
     if (!on_device) {
-        if ((rc = check_model_list(who, "shift", nstar, npsf, psf_index, shift, (size_t)2 * nstar))) return rc;
-        if ((rc = check_frame_stars(who, nstar, origin, nullptr, "scale0"))) return rc;
-        if (scale0)
-            for (size_t k = 0; k < (size_t)nl * nstar; ++k)
-                if (!std::isfinite(scale0[k])) return fail(MPSFR_E_INVALID, "%s: a scale0 that is not finite", who);
-        if (layer_shift) {
-            // (rounding is monotone: the sums of a layer stay in range when those of the extreme shifts do)
-            double lo[2] = {0.0, 0.0}, hi[2] = {0.0, 0.0};
-            for (int k = 0; shift && k < 2 * nstar; ++k) {
-                lo[k & 1] = k < 2 ? shift[k] : std::min(lo[k & 1], shift[k]);
-                hi[k & 1] = k < 2 ? shift[k] : std::max(hi[k & 1], shift[k]);
-            }
-            for (int k = 0; k < 2 * nl; ++k) {
-                const double t = layer_shift[k];
-                if (!std::isfinite(t)) return fail(MPSFR_E_INVALID, "%s: a layer_shift that is not finite", who);
-                if (!(std::fabs(lo[k & 1] + t) <= MPSFR_FIT_PSF_MAX_SHIFT && std::fabs(hi[k & 1] + t) <= MPSFR_FIT_PSF_MAX_SHIFT))
-                    return fail(MPSFR_E_INVALID, "%s: shift + layer_shift beyond 8 pixels", who);
-            }
-        }
+        if ((rc = cube_fit_host_arguments(who, nl, nstar, npsf, psf_index, origin, shift, layer_shift, scale0))) return rc;
     }
     HIPCHK(hipSetDevice(c->device));
     // the layers of a batch: asked for, or what the budget of work memory holds
@@ -3319,6 +3336,54 @@ int mpsfr_fit_cube_psf(mpsfr_ctx* c, int nl, int ny, int nx, const double* cube,
         }
     }
     return MPSFR_OK;
+}
+
+static_assert(MPSFR_NCUBEFREE_POS == 8 && MPSFR_NCUBEFREE_CALL == 8, "k_cf_step<CF_FINAL> row layout");
+
+int mpsfr_fit_cube_psf_free(mpsfr_ctx* c, int nl, int ny, int nx, const double* cube, const double* var, int nstar,
+                            int npsf, const double* psf, const int32_t* psf_index, const int32_t* origin,
+                            const double* shift, const double* layer_shift, const double* scale0, double radius,
+                            int flags, int max_iter, double tol, int max_outer, double pos_tol, double max_step,
+                            double max_move, double min_snr, double* star_out, double* head_out, double* pos_out,
+                            double* shift_out, double* call_out, double* resid_out, int on_device) {
+    const char* who = "fit_cube_psf_free";
+    if (!c || !cube || !psf || !origin || !star_out || !head_out || !pos_out || !shift_out || !call_out || npsf < 1)
+        return fail(MPSFR_E_INVALID,
+                    "%s: bad argument (cube, psf, origin, star_out, head_out, pos_out, shift_out and call_out are required)",
+                    who);
+    int rc;
+    if ((rc = frame_fit_ranges(who, ny, nx, nstar, npsf, psf_index, radius, flags, max_iter, tol))) return rc;
+    if (nl < 1 || nl > MPSFR_CUBE_FIT_MAX_LAYERS)
+        return fail(MPSFR_E_INVALID, "%s: nl=%d outside 1..%d", who, nl, MPSFR_CUBE_FIT_MAX_LAYERS);
+    if ((rc = frame_free_ranges(who, max_outer, pos_tol, max_step, max_move, min_snr))) return rc;
+    if (!on_device && (rc = cube_fit_host_arguments(who, nl, nstar, npsf, psf_index, origin, shift, layer_shift, scale0)))
+        return rc;
+    const size_t work = cube_free_workspace_bytes(ny, nx, nstar, nl);
+    if (work > MPSFR_CUBE_FREE_WORK_BYTES)
+        return fail(MPSFR_E_INVALID, "%s: %zu bytes of work memory for %d layers, above the budget of %zu: take the "
+                                     "positions from fewer layers", who, work, nl, (size_t)MPSFR_CUBE_FREE_WORK_BYTES);
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = ensure(c, c->cubefit, work))) return rc;
+    const size_t L = (size_t)nl, npix = (size_t)ny * nx;
+    const StampIn in[] = {{cube, L * npix, sizeof(double)},
+                          {var, L * npix, sizeof(double)},
+                          {psf, npsf * L * kStampPix, sizeof(double)},
+                          {shift, (size_t)2 * nstar, sizeof(double)},
+                          {layer_shift, 2 * L, sizeof(double)},
+                          {scale0, L * nstar, sizeof(double)},
+                          {origin, (size_t)2 * nstar, sizeof(int32_t)},
+                          {psf_index, (size_t)nstar, sizeof(int32_t)}};
+    const StampOut out[] = {{star_out, L * nstar * MPSFR_NFRAMEFIT}, {head_out, L * MPSFR_NFRAMEFIT},
+                            {pos_out, (size_t)nstar * MPSFR_NCUBEFREE_POS}, {shift_out, (size_t)2 * nstar},
+                            {call_out, MPSFR_NCUBEFREE_CALL}, {resid_out, L * npix}};
+    return stamp_call(c, on_device, in, out, [&](hipStream_t s, const void* const* d, double* const* d_out) {
+        StarList stars{nstar, npsf, (const double*)d[2], (const int32_t*)d[7], (const int32_t*)d[6], (const double*)d[3]};
+        stars.lshift = (const double*)d[4];
+        stars.nl = nl;
+        launch_fit_cube_free(s, ny, nx, nl, (const double*)d[0], (const double*)d[1], stars, (const double*)d[5], radius,
+                             (flags & MPSFR_FIT_BACKGROUND) != 0, max_iter, tol, max_outer, pos_tol, max_step, max_move,
+                             min_snr, d_out[0], d_out[1], d_out[2], d_out[3], d_out[4], d_out[5], c->cubefit.p);
+    });
 }
 
 long mpsfr_debug_fetch(mpsfr_ctx* c, const char* what, double* out, size_t capacity) {

@@ -1046,30 +1046,10 @@ def refine_crowded_stars(image, psf, positions, *, var=None, psf_index=None, rad
     return (fit, origin) + ((res[3],) if return_residual else ())
 
 
-_FIT_COLS_CROWDED_SPECTRA = ('shift', 'scale', 'flux', 'err_scale', 'err_flux', 'overlap', 'npix', 'status')
-_META_CROWDED_SPECTRA = ('back', 'err_back', 'chi2', 'npix', 'iterations', 'residual', 'status')
-
-
-def fit_crowded_spectra(cube, psf, positions, *, lbda=None, var=None, psf_index=None, layer_shift=None, radius=8.0,
-                        fit_back=True, start=None, max_iter=100, tol=1e-10, layer_batch=0, return_residual=False,
-                        pixscale=0.2, precision='mixed', device=0):
-    """Crowded-field PSF spectroscopy, on the GPU: the spectra of ALL stars of a cube at known positions -- the solve
-    of fit_crowded_stars on every wavelength layer, the layers side by side in one call, bit for bit what a loop of
-    fit_crowded_stars over the layers gives.  `cube` (nl, ny, nx), `var` its variance cube or None (NaN pixels and var
-    <= 0 are masked); `positions` an (n, 2) array of (row, column) in pixels or a find_stars table, the same in every
-    layer; `layer_shift` (nl, 2) arcsec or None: the offset of a layer common to all stars (differential refraction),
-    added to every star's position in that layer -- a position plus offset must stay within 8 pixels of the star's
-    stamp centre; `psf` (nl, 40, 40), one model cube for every star, e.g. the reconstructed PSF per wavelength, or
-    (npsf, nl, 40, 40) with star k taking psf[psf_index[k]].  radius, fit_back, max_iter, tol: as fit_crowded_stars,
-    per layer.  `start`: None (zeros), 'found' (the `scale` column of a find_stars table, for every layer) or (nl, n)
-    values.  `layer_batch`: layers solved side by side (0: as many as the library's work memory budget holds).
-    `lbda` (nl,): wavelengths, echoed into fit.meta.
-
-    Returns (fit, origin): origin as fit_crowded_stars places it, and `fit` with one row per star: shift (2, arcsec,
-    echoed: the position from the stamp centre, without the layer's offset) and the (n, nl) columns scale, flux,
-    err_scale, err_flux, overlap, npix and status of fit_crowded_stars.  fit.meta holds the per-layer arrays (nl,) back,
-    err_back, chi2, npix, iterations, residual and status, and lbda if given.  With return_residual also the cube minus
-    the fitted stars."""
+def _crowded_spectra_inputs(psf, positions, lbda, psf_index, layer_shift, fit_back, start, pixscale):
+    """(psf (npsf, nl, 40, 40), psf_index, lbda, layer_shift in pixels, start, origin, shift in pixels) of
+    fit_crowded_spectra and refine_crowded_spectra: the model cubes, the stars placed as cut_star_stamps places stamps,
+    the start resolved."""
     _pixscale(pixscale)
     if not isinstance(fit_back, (bool, np.bool_)):
         raise ValueError('fit_back must be True or False')
@@ -1112,6 +1092,36 @@ def fit_crowded_spectra(cube, psf, positions, *, lbda=None, var=None, psf_index=
         start = np.broadcast_to(found, (nl, n))
     origin = (np.rint(pos) - dimpsf // 2).astype(np.int32)
     shift_px = pos - (origin + dimpsf // 2)
+    return ps, psf_index, lbda, layer_shift, start, origin, shift_px
+
+
+_FIT_COLS_CROWDED_SPECTRA = ('shift', 'scale', 'flux', 'err_scale', 'err_flux', 'overlap', 'npix', 'status')
+_META_CROWDED_SPECTRA = ('back', 'err_back', 'chi2', 'npix', 'iterations', 'residual', 'status')
+
+
+def fit_crowded_spectra(cube, psf, positions, *, lbda=None, var=None, psf_index=None, layer_shift=None, radius=8.0,
+                        fit_back=True, start=None, max_iter=100, tol=1e-10, layer_batch=0, return_residual=False,
+                        pixscale=0.2, precision='mixed', device=0):
+    """Crowded-field PSF spectroscopy, on the GPU: the spectra of ALL stars of a cube at known positions -- the solve
+    of fit_crowded_stars on every wavelength layer, the layers side by side in one call, bit for bit what a loop of
+    fit_crowded_stars over the layers gives.  `cube` (nl, ny, nx), `var` its variance cube or None (NaN pixels and var
+    <= 0 are masked); `positions` an (n, 2) array of (row, column) in pixels or a find_stars table, the same in every
+    layer; `layer_shift` (nl, 2) arcsec or None: the offset of a layer common to all stars (differential refraction),
+    added to every star's position in that layer -- a position plus offset must stay within 8 pixels of the star's
+    stamp centre; `psf` (nl, 40, 40), one model cube for every star, e.g. the reconstructed PSF per wavelength, or
+    (npsf, nl, 40, 40) with star k taking psf[psf_index[k]].  radius, fit_back, max_iter, tol: as fit_crowded_stars,
+    per layer.  `start`: None (zeros), 'found' (the `scale` column of a find_stars table, for every layer) or (nl, n)
+    values.  `layer_batch`: layers solved side by side (0: as many as the library's work memory budget holds).
+    `lbda` (nl,): wavelengths, echoed into fit.meta.
+
+    Returns (fit, origin): origin as fit_crowded_stars places it, and `fit` with one row per star: shift (2, arcsec,
+    echoed: the position from the stamp centre, without the layer's offset) and the (n, nl) columns scale, flux,
+    err_scale, err_flux, overlap, npix and status of fit_crowded_stars.  fit.meta holds the per-layer arrays (nl,) back,
+    err_back, chi2, npix, iterations, residual and status, and lbda if given.  With return_residual also the cube minus
+    the fitted stars."""
+    ps, psf_index, lbda, layer_shift, start, origin, shift_px = _crowded_spectra_inputs(
+        psf, positions, lbda, psf_index, layer_shift, fit_back, start, pixscale)
+    dimpsf = ps.shape[-1]
     ctx = get_context(128, pixscale, dimpsf, precision, device)
     res = ctx.fit_cube_psf(cube, ps, origin, var=var, shift=shift_px, layer_shift=layer_shift, psf_index=psf_index,
                            scale0=start, radius=radius, background=bool(fit_back), max_iter=max_iter, tol=tol,
@@ -1131,6 +1141,119 @@ def fit_crowded_spectra(cube, psf, positions, *, lbda=None, var=None, psf_index=
         meta['lbda'] = lbda
     fit = _make_table(cols, meta)
     return (fit, origin) + ((res[2],) if return_residual else ())
+
+
+_FIT_COLS_REFINED_SPECTRA = ('shift', 'position', 'scale', 'flux', 'err_scale', 'err_shift', 'err_flux', 'overlap', 'moved',
+                             'npix', 'free', 'flags', 'status')
+_META_REFINED_SPECTRA = ('chi2_all', 'dof', 'outer', 'step', 'nfree', 'inner', 'call_status', 'call_residual')
+
+
+def _take_layers(a, sel):
+    """The layers `sel` of a cube-like argument (an array, a masked array or an object with .data), or None."""
+    if a is None:
+        return None
+    if not isinstance(a, np.ma.MaskedArray):
+        a = getattr(a, 'data', a)
+    if not isinstance(a, np.ma.MaskedArray):
+        try:
+            a = np.asarray(a, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('cube and var must be numeric arrays') from None
+    if a.ndim != 3:
+        raise ValueError('cube and var must have the shape (nl, ny, nx)')
+    return a[sel]
+
+
+def refine_crowded_spectra(cube, psf, positions, *, lbda=None, var=None, psf_index=None, layer_shift=None,
+                           position_layers=None, radius=8.0, fit_back=True, start=None, max_iter=100, tol=1e-10,
+                           max_outer=8, pos_tol=1e-3, max_step=0.5, max_move=2.0, min_snr=3.0, return_residual=False,
+                           pixscale=0.2, precision='mixed', device=0):
+    """Crowded-field PSF spectroscopy with free positions, on the GPU: fit_crowded_spectra with ONE position per star
+    refined from the layers of the cube jointly -- every layer with its own PSF and its own offset `layer_shift`, all
+    stars and all layers in one Gauss-Newton loop (refine_crowded_stars' on the whole cube).  cube, psf, positions
+    (the start), lbda, var, psf_index, layer_shift, radius, fit_back, start, max_iter, tol: as fit_crowded_spectra;
+    max_outer, pos_tol, max_step, max_move, min_snr: as refine_crowded_stars.  A layer moves a star only where the
+    star's flux stands `min_snr` conditional errors above zero in that layer.
+
+    `position_layers`: an index array or a slice of the layers that determine the positions; None: all layers, which
+    must then fit into the library's work memory budget (CUBE_FREE_WORK_BYTES).  With a proper subset the positions
+    are refined on those layers, and the spectra of the WHOLE cube are then solved at the refined positions by
+    fit_crowded_spectra's solve -- this is how a cube of thousands of layers is served: positions from a few dozen
+    layers, spectra from all.
+
+    Returns (fit, origin): origin as fit_crowded_spectra places it, from the START positions, and `fit` with one row
+    per star: shift (2, arcsec: the REFINED position from the stamp centre, without the layer's offset), position (2,
+    pixels), err_shift (2, arcsec, conditional), moved (2, arcsec: refined minus start), free (the steps in which the
+    star moved), flags (FRAME_FREE_HELD, FRAME_FREE_BOUND, FRAME_FREE_CLIPPED) and the (n, nl) columns scale, flux,
+    err_scale, err_flux, overlap, npix and status of fit_crowded_spectra.  fit.meta: the per-layer arrays of
+    fit_crowded_spectra, the head of the position call -- chi2_all, dof, outer, step, nfree, inner, call_status (0
+    positions and closing solve converged, 1 anything else fitted, 2 nothing fitted), call_residual --,
+    position_layers, and lbda if given.  With return_residual also the cube minus the fitted stars at the refined
+    positions."""
+    ps, psf_index, lbda, layer_shift, start, origin, shift_px = _crowded_spectra_inputs(
+        psf, positions, lbda, psf_index, layer_shift, fit_back, start, pixscale)
+    dimpsf, nl = ps.shape[-1], ps.shape[1]
+    if position_layers is None:
+        sel = np.arange(nl)
+    else:
+        try:
+            sel = np.arange(nl)[position_layers]
+        except (IndexError, TypeError, ValueError):
+            raise ValueError('position_layers must be a slice or an array of layer indices in 0 .. %d' % (nl - 1)) from None
+        sel = np.atleast_1d(sel)
+        if sel.ndim != 1 or sel.size == 0 or np.unique(sel).size != sel.size:
+            raise ValueError('position_layers must name at least one layer, and each layer once')
+    whole = sel.size == nl and np.array_equal(sel, np.arange(nl))
+    ctx = get_context(128, pixscale, dimpsf, precision, device)
+    free = dict(radius=radius, background=bool(fit_back), max_iter=max_iter, tol=tol, max_outer=max_outer,
+                pos_tol=pos_tol, max_step=max_step, max_move=max_move, min_snr=min_snr)
+    if whole:
+        res = ctx.fit_cube_psf_free(cube, ps, origin, var=var, shift=shift_px, layer_shift=layer_shift,
+                                    psf_index=psf_index, scale0=start, return_residual=return_residual, **free)
+        rows, pos_rows, shifts, head, call = res[:5]
+        resid = res[5] if return_residual else None
+    else:
+        sub_start = None if start is None else np.asarray(start, dtype=np.float64)
+        if sub_start is not None and sub_start.shape != (nl, origin.shape[0]):
+            raise ValueError('start must have the shape (%d, %d)' % (nl, origin.shape[0]))
+        sub_cube = _take_layers(cube, sel)
+        if _take_layers(cube, slice(None)).shape[0] != nl:
+            raise ValueError('cube must have the %d layers of psf' % nl)
+        if layer_shift is not None and np.shape(layer_shift) != (nl, 2):
+            raise ValueError('layer_shift must have the shape (%d, 2)' % nl)
+        _, pos_rows, shifts, _, call = ctx.fit_cube_psf_free(
+            sub_cube, ps[:, sel], origin, var=_take_layers(var, sel), shift=shift_px,
+            layer_shift=None if layer_shift is None else layer_shift[sel], psf_index=psf_index,
+            scale0=None if sub_start is None else sub_start[sel], **free)
+        res = ctx.fit_cube_psf(cube, ps, origin, var=var, shift=shifts, layer_shift=layer_shift, psf_index=psf_index,
+                               scale0=start, radius=radius, background=bool(fit_back), max_iter=max_iter, tol=tol,
+                               return_residual=return_residual)
+        rows, head = res[0], res[1]
+        resid = res[2] if return_residual else None
+    cols = OrderedDict()
+    cols['shift'] = shifts * pixscale
+    cols['position'] = (origin + dimpsf // 2) + shifts
+    for name, c in (('scale', 0), ('flux', 2), ('err_scale', 1)):
+        cols[name] = np.ascontiguousarray(rows[:, :, c].T)
+    cols['err_shift'] = pos_rows[:, 2:4] * pixscale
+    for name, c in (('err_flux', 3), ('overlap', 4)):
+        cols[name] = np.ascontiguousarray(rows[:, :, c].T)
+    cols['moved'] = pos_rows[:, 4:6] * pixscale
+    cols['npix'] = np.ascontiguousarray(rows[:, :, 5].T).astype(np.int64)
+    cols['free'] = pos_rows[:, 7].astype(np.int64)
+    cols['flags'] = pos_rows[:, 6].astype(np.int64)
+    cols['status'] = np.ascontiguousarray(rows[:, :, 7].T).astype(np.int64)
+    assert tuple(cols) == _FIT_COLS_REFINED_SPECTRA
+    meta = OrderedDict()
+    for name, c in zip(_META_CROWDED_SPECTRA, (0, 1, 2, 3, 4, 5, 7)):
+        meta[name] = head[:, c].astype(np.int64) if name in ('npix', 'iterations', 'status') else head[:, c].copy()
+    for name, c in zip(_META_REFINED_SPECTRA, range(8)):
+        meta[name] = int(call[c]) if name in ('outer', 'nfree', 'inner', 'call_status') else float(call[c])
+    meta['position_layers'] = sel.copy()
+    if lbda is not None:
+        meta['lbda'] = lbda
+    fit = _make_table(cols, meta)
+    return (fit, origin) + ((resid,) if return_residual else ())
 
 
 def cut_star_stamps(image, positions, var=None, dimpsf=40, *, pixscale=0.2, precision='mixed', device=0):
