@@ -350,6 +350,22 @@ int mpsfr_wait_multi(mpsfr_ctx* const* ctxs, int nctx);
 int mpsfr_fit_stamps(mpsfr_ctx* ctx, int nstamp, const double* stamps, double* fit_out,
                      int on_device);
 
+/* What a call writes.  This holds for the fourteen stamp, frame and cube entry points below (mpsfr_fit_stamps_elliptical,
+ * _observed, _psf, mpsfr_fit_groups_psf, mpsfr_fit_spectra_psf, mpsfr_stamp_metrics, mpsfr_cut_stamps,
+ * mpsfr_render_stars, mpsfr_find_stars, mpsfr_group_stars, mpsfr_fit_frame_psf, _free, mpsfr_fit_cube_psf, _free), in
+ * the host and in the device form alike:
+ *   - a call that returns MPSFR_OK writes EVERY element of every output array it is given, at the size stated for the
+ *     array: a row that holds no result -- a stamp or star with status 1 or 2, a star left out of one layer, a layer with
+ *     nothing to fit, the rows of mpsfr_find_stars from count_out[0] up to max_stars, the rows of mpsfr_group_stars
+ *     from the number of groups up to max_groups and the doubles of shift_out that belong to no member -- is written
+ *     with the zeros, NaNs or fillers stated for it, never left as the caller's buffer held it;
+ *   - it writes nothing behind that size: the rows beyond max_stars or max_groups of a frame with more peaks or groups
+ *     do not exist for the call;
+ *   - an optional output passed as NULL is not written, and changes no other output;
+ *   - a refused call (MPSFR_E_INVALID) writes nothing.
+ * No output depends on what the context ran before: the work memory of these calls is reused from
+ * call to call and never cleared, and every word a call reads from it the same call has written. */
+
 /* Elliptical Moffat fit of caller-provided stamps (mpdaf's moffat_fit(circular=False), which the reference does not
  * use): I (1 + Q)^-n with Q = (g / alpha^2) [(1 - e1) x^2 - 2 e2 x y + (1 + e1) y^2], g = 1 / sqrt(1 - e1^2 - e2^2),
  * x = q - q0, y = p - p0; alpha is the geometric mean of the semi-axes.  With e = sqrt(e1^2 + e2^2):

@@ -16,10 +16,14 @@ Predecessors (each run to completion, options restored afterwards):
   P6 layout shifts: more tasks per chunk, other direction counts, and the reverse
   P7 the other entry points: profile, field, band, convolve_stamps, the device elliptical fit, psd_to_psf
   P8 the device circular fit (fit_stamps_device)
+  P10 psd_to_psf at a smaller transform length, and on a PSD with a NaN (its own workspaces left holding NaN)
+  P9 the fourteen stamp, frame and cube calls of tests/stamp_history_cases.py in sequence (the staging buffer and the
+     frame workspaces; the other direction is tests/test_gpu_stamp_call_history.py)
 """
 import numpy as np
 import pytest
 
+import psd_to_psf_ref as PR
 import psfr_oracle as O
 from conftest import H, record_margin, rel_err
 
@@ -45,7 +49,33 @@ CHECKED = {
     'd1280': (1280, 'mixed', {}, 'psf', 1),
     'field512': (512, 'mixed', {}, 'field', 1),
     'band512': (512, 'mixed', {}, 'band', 1),
+    # mpsfr_reconstruct_profile on the three-layer profile of tests/golden/g9_profile.npz (case a, the reference's
+    # cut-off masks) and mpsfr_psd_to_psf at the transform length 256 on the 512^2 grid, both precisions of the context
+    'profile512': (512, 'mixed', {}, 'profile', 1),
+    'profile512_f64': (512, 'f64', {}, 'profile', 1),
+    'psd2psf512': (512, 'mixed', {}, 'p2p', 1),
+    'psd2psf512_f64': (512, 'f64', {}, 'p2p', 1),
 }
+_GOLD = {}
+
+
+@pytest.fixture(scope='module', autouse=True)
+def _fixtures(golden, ref_masks):
+    _GOLD.update(g9=golden('g9_profile'), masks=ref_masks)
+
+
+_P2P = {}
+
+
+def _p2p_inputs():
+    """psd_to_psf as tests/test_gpu_psd_to_psf_inputs.py::test_sizes calls it at (512, 256), phased: an odd random
+    pupil, the PSD without symmetry, a random static phase, two wavelengths."""
+    if not _P2P:
+        dimnum, lb = 256, 500e-9
+        pup = PR.rand_pupil(dimnum // 2 - 3)
+        _P2P.update(pup=pup, psd=PR.scaled_psd(PR.asym_psd(512), pup, 8.0, lb, dimnum, 10.0), dimnum=dimnum,
+                    phase=PR.rand_phase(dimnum // 2 - 3, 1.0, lb), lbda=np.array([lb, 850e-9]))
+    return _P2P
 
 
 @pytest.fixture(scope='module')
@@ -68,15 +98,47 @@ def _run(api, ctx, name, l0=L0, _async=False):
         return ctx.reconstruct(LB, SEE, GL, l0, THREE, H, npsflin=npl, _async=_async)
     if kind == 'field':
         return ctx.reconstruct_field(LB, SEE, GL, l0, THREE, H, POS, _async=_async)
+    if kind == 'profile':
+        g = _GOLD['g9']
+        return ctx.reconstruct_profile(g['a_lbda'], [float(g['a_seeing'])], [float(g['a_gl'])], [float(g['a_L0'])],
+                                       g['a_cn2'], g['a_h'], g['a_ws'], g['a_wd'], three_lgs=[int(g['a_three'])],
+                                       npsflin=int(g['a_npsflin']), masks=_GOLD['masks'], _async=_async)
+    if kind == 'p2p':
+        a = _p2p_inputs()
+        return dict(psf=ctx.psd_to_psf(a['psd'], a['pup'], 8.0, a['lbda'], phase_static=a['phase'],
+                                       dimnum=a['dimnum'])[0])
     return ctx.reconstruct_band(LB, api.band_weights(LB, BANDS), SEE, GL, l0, THREE, H, _async=_async)
 
 
+def _keys(a, b):
+    assert sorted(a) == sorted(b) and ('psf' in a) and (len(a) == 1 or sorted(a) == ['fit', 'psf', 'psf_sum'])
+    return sorted(a)                           # (psd_to_psf returns its planes alone)
+
+
 def _same(a, b):
-    return all(a[k].shape == b[k].shape and np.array_equal(a[k], b[k]) for k in ('psf', 'psf_sum', 'fit'))
+    return all(a[k].shape == b[k].shape and np.array_equal(a[k], b[k]) for k in _keys(a, b))
 
 
 def _diff(a, b):
-    return {k: (int(np.sum(a[k] != b[k])), int(np.sum(~np.isfinite(a[k])))) for k in ('psf', 'psf_sum', 'fit')}
+    return {k: (int(np.sum(a[k] != b[k])), int(np.sum(~np.isfinite(a[k])))) for k in _keys(a, b)}
+
+
+def _hold_profile(name, r, prec):
+    """Case a of tests/golden/g9_profile.npz as tests/test_gpu_profile.py holds it: the reference's final stamps and
+    its Moffat fits, at that test's tolerances."""
+    import test_gpu_profile as TP
+    from muse_psfr_amd import grid_pixscale
+    e = TP.check_final_stamps_and_fits(_GOLD['g9'], 'a', prec, grid_pixscale(512), r, 1)
+    record_margin('call_history_vs_oracle', **{name: e})
+
+
+def _hold_p2p(name, r):
+    """Every plane against the fp64 yardstick tests/psd_to_psf_ref.py with the checks and the bound of
+    tests/test_gpu_psd_to_psf_inputs.py."""
+    import test_gpu_psd_to_psf_inputs as TI
+    a = _p2p_inputs()
+    TI._check('call_history_' + name, r['psf'], PR.psd_to_psf_ref(a['psd'], a['pup'], 8.0, a['lbda'], a['phase'],
+                                                                 a['dimnum']))
 
 
 _FRESH = {}
@@ -90,6 +152,14 @@ def _fresh(api, name):
     r = _run(api, ctx, name)
     ctx.close()
     dim, prec, _, kind, npl = CHECKED[name]
+    if kind in ('profile', 'p2p'):
+        if kind == 'profile':
+            _hold_profile(name, r, prec)
+        else:
+            _hold_p2p(name, r)
+        assert all(np.all(np.isfinite(v)) for v in r.values()), name
+        _FRESH[name] = r
+        return r
     ps = api.grid_pixscale(dim)
     tabs = O.ao_tables(H, bool(THREE[0]), npl, exact_masks=True)
     ofit, ofin = O.compute_psf(LB, SEE[0], GL[0], L0[0], npl, H, bool(THREE[0]), dim=dim, pixscale=ps,
@@ -244,6 +314,26 @@ def p7_psd_to_psf(api, ctx, name):
     ctx.psd_to_psf(psd, pup, 8.0, LB * 1e-9)
 
 
+def p10_psd_to_psf_small(api, ctx, name):
+    pup = PR.rand_pupil(61)
+    ctx.psd_to_psf(PR.scaled_psd(PR.asym_psd(ctx.dim), pup, 8.0, 500e-9, 128, 10.0), pup, 8.0, np.array([500e-9]),
+                   dimnum=128)
+
+
+def p10_psd_to_psf_nan(api, ctx, name):
+    """include/mpsfr.h: a PSD with a NaN is not refused, its planes are NaN in every pixel."""
+    a = _p2p_inputs()
+    psd = PR.scaled_psd(PR.asym_psd(ctx.dim), a['pup'], 8.0, 500e-9, a['dimnum'], 10.0)
+    psd[200, 13] = np.nan
+    out = ctx.psd_to_psf(psd, a['pup'], 8.0, a['lbda'], phase_static=a['phase'], dimnum=a['dimnum'])[0]
+    assert np.isnan(out).all()
+
+
+def p9_stamp_frame_cube_calls(api, ctx, name):
+    import stamp_history_cases as S
+    S.run_all(api, ctx)
+
+
 PRED = {
     'P1_l0_5m': p1_short_l0,
     'P2_stage_a0': p2_stage_a0,
@@ -265,11 +355,21 @@ PRED = {
     'P7_fit_ell_device': p7_fit_ell_device,
     'P7_psd_to_psf': p7_psd_to_psf,
     'P8_fit_device': p8_fit_device,
+    'P9_stamp_frame_cube_calls': p9_stamp_frame_cube_calls,
+    'P10_psd_to_psf_small': p10_psd_to_psf_small,
+    'P10_psd_to_psf_nan': p10_psd_to_psf_nan,
 }
 
 CASES = ([(p, 'd512') for p in PRED]
          + [(p, c) for p in ('P1_l0_5m', 'P4_psd_overflow') for c in CHECKED if c != 'd512']
-         + [('P4_psd_overflow_4dir', c) for c in ('d256', 'd512_f64')])
+         + [('P4_psd_overflow_4dir', c) for c in ('d256', 'd512_f64')]
+         + [('P9_stamp_frame_cube_calls', c) for c in ('d512_f64', 'band512')]
+         # reconstruct_profile and psd_to_psf as checked calls: P1 and P4 come with the line above; the stage-A form
+         # by option, the refused PSD, the layout shifts, the other entry points and the stamp, frame and cube calls
+         + [(p, c) for c in ('profile512', 'profile512_f64', 'psd2psf512', 'psd2psf512_f64')
+            for p in ('P2_stage_a0', 'P5_psd_nan_pixel', 'P6_more_tasks_per_chunk', 'P6_npsflin3', 'P7_profile',
+                      'P7_field', 'P7_band', 'P7_convolve_stamps', 'P7_psd_to_psf', 'P9_stamp_frame_cube_calls',
+                      'P10_psd_to_psf_small', 'P10_psd_to_psf_nan')])
 
 
 @pytest.mark.parametrize('pred,checked', CASES)
@@ -487,6 +587,9 @@ def test_clearing_path_only_after_a_writer(api):
     ctx = _context(api, 'd512')
     _run(api, ctx, 'd512')
     _run(api, ctx, 'd512')
+    assert _clears(ctx) == 0
+    p9_stamp_frame_cube_calls(api, ctx, 'd512')          # (no stamp, frame or cube call writes D0t)
+    assert _same(_run(api, ctx, 'd512'), _fresh(api, 'd512'))
     assert _clears(ctx) == 0
     steps = [(p4_overflow, 1), (None, 1), (p1_short_l0, 2), (p2_stage_a0, 3), (None, 3)]
     for pred, want in steps:

@@ -168,8 +168,23 @@ def test_parity_with_the_converged_yardstick(ctx, prec, with_var, background, ra
 @pytest.mark.parametrize('prec', PRECS)
 def test_one_step_on_the_noisy_cube_follows_the_rule(ctx, prec):
     c = Q.cube(True)
-    ref = Q.run(c, max_outer=1)
     rows, pos, shifts, head, call = _free(ctx, c, max_iter=MAX_ITER, tol=TOL, max_outer=1)
+    ref = check_one_step(c, rows, pos, shifts, head, call)
+    record_margin('cube_free', **{'one_step_%s' % prec: ref['ratio']})
+
+
+_ONE_STEP = {}
+
+
+def check_one_step(c, rows, pos, shifts, head, call, **kw):
+    """The outputs of a call with max_iter = MAX_ITER, tol = TOL, max_outer = 1 and the step parameters `kw` on the
+    three-layer case `c` = Q.cube(True) (var, background, radius 8) against one step of the rule with exact solves.  Returns the
+    yardstick's run with the worst position error / bound under 'ratio'."""
+    assert c is Q.cube(True)                     # (the yardstick is kept per step parameters, of this case alone)
+    key = tuple(sorted(kw.items()))
+    if key not in _ONE_STEP:
+        _ONE_STEP[key] = Q.run(c, max_outer=1, **kw)
+    ref = _ONE_STEP[key]
     free = ref['last']['free']
     _, by, bx = R.inner_bounds(ref['last'], TOL, MAX_ITER, Q.NL)
     ratio = float(np.max(np.abs(shifts[free] - ref['shift'][free]) / np.stack([by, bx], axis=1)))
@@ -183,7 +198,7 @@ def test_one_step_on_the_noisy_cube_follows_the_rule(ctx, prec):
     held = np.flatnonzero(seen & (ref['nfree'] == 0))
     assert _same(shifts[held], c['shift'][held]) and not pos[held, 2:6].any()
     np.testing.assert_allclose(pos[free, 2:4], ref['err_shift'][free], rtol=1e-6)
-    record_margin('cube_free', **{'one_step_%s' % prec: ratio})
+    return dict(ref, ratio=ratio)
 
 
 # ---- 2. the residual cube is the renderer's

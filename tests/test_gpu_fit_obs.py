@@ -71,6 +71,25 @@ def test_parity_with_scipy_on_noisy_masked_stamps(ctx, prec, ell, back):
     assert np.all(_status(fit) & 3 == 0), _status(fit)
     assert np.all(_status(fit) & 4 == 0)
     assert np.all(np.isfinite(fit))
+    worst, worst_err = parity_worst(fit, ref, ell, back)
+    tag = '%s_%s%s' % (prec, 'ell' if ell else 'circ', '_back' if back else '')
+    print('fit_obs parity %s: worst |d| / sigma %s; worst relative error of the error columns %s' % (
+        tag, {k: '%.2e' % v for k, v in worst.items()}, {k: '%.2e' % v for k, v in worst_err.items()}))
+    record_margin('fit_obs', **{'sigma_%s_%s' % (tag, k): v for k, v in worst.items()})
+    record_margin('fit_obs', **{'err_%s_%s' % (tag, k): v for k, v in worst_err.items()})
+    assert max(worst.values()) <= SIGMA_TOL[prec], worst
+    assert max(worst_err.values()) <= ERR_TOL, worst_err
+    if not ell:
+        assert np.array_equal(fit[:, 3], fit[:, 4]) and np.array_equal(fit[:, 7], fit[:, 8])
+        assert np.array_equal(fit[:, 14], fit[:, 15]) and np.all(fit[:, 6] == 0) and np.all(fit[:, 16] == 0)
+    if not back:
+        assert np.all(fit[:, 21:23] == 0)
+
+
+def parity_worst(fit, ref, ell, back):
+    """Per fitted variable the worst |difference| in units of the yardstick's formal error and the worst relative
+    difference of the error columns, of the rows `fit` against the yardstick's fits `ref`; the used pixels and chi2
+    are asserted here."""
     keys = [k for k in R.KEYS if (ell or k != 'rot') and (back or k != 'back')]
     worst, worst_err = {}, {}
     for row, want in zip(fit, ref):
@@ -89,18 +108,7 @@ def test_parity_with_scipy_on_noisy_masked_stamps(ctx, prec, ell, back):
             worst[k] = max(worst.get(k, 0.0), dv / sig)
             worst_err[k] = max(worst_err.get(k, 0.0), abs(err[i] - want['verr'][i]) / want['verr'][i])
         assert abs(row[9] - want['chi2']) <= ERR_TOL * want['chi2']
-    tag = '%s_%s%s' % (prec, 'ell' if ell else 'circ', '_back' if back else '')
-    print('fit_obs parity %s: worst |d| / sigma %s; worst relative error of the error columns %s' % (
-        tag, {k: '%.2e' % v for k, v in worst.items()}, {k: '%.2e' % v for k, v in worst_err.items()}))
-    record_margin('fit_obs', **{'sigma_%s_%s' % (tag, k): v for k, v in worst.items()})
-    record_margin('fit_obs', **{'err_%s_%s' % (tag, k): v for k, v in worst_err.items()})
-    assert max(worst.values()) <= SIGMA_TOL[prec], worst
-    assert max(worst_err.values()) <= ERR_TOL, worst_err
-    if not ell:
-        assert np.array_equal(fit[:, 3], fit[:, 4]) and np.array_equal(fit[:, 7], fit[:, 8])
-        assert np.array_equal(fit[:, 14], fit[:, 15]) and np.all(fit[:, 6] == 0) and np.all(fit[:, 16] == 0)
-    if not back:
-        assert np.all(fit[:, 21:23] == 0)
+    return worst, worst_err
 
 
 # ---- 2. consistency with the existing kernels
