@@ -350,10 +350,10 @@ int mpsfr_wait_multi(mpsfr_ctx* const* ctxs, int nctx);
 int mpsfr_fit_stamps(mpsfr_ctx* ctx, int nstamp, const double* stamps, double* fit_out,
                      int on_device);
 
-/* What a call writes.  This holds for the fourteen stamp, frame and cube entry points below (mpsfr_fit_stamps_elliptical,
+/* What a call writes.  This holds for the fifteen stamp, frame and cube entry points below (mpsfr_fit_stamps_elliptical,
  * _observed, _psf, mpsfr_fit_groups_psf, mpsfr_fit_spectra_psf, mpsfr_stamp_metrics, mpsfr_cut_stamps,
- * mpsfr_render_stars, mpsfr_find_stars, mpsfr_group_stars, mpsfr_fit_frame_psf, _free, mpsfr_fit_cube_psf, _free), in
- * the host and in the device form alike:
+ * mpsfr_render_stars, mpsfr_find_stars, mpsfr_group_stars, mpsfr_fit_frame_psf, _free, mpsfr_fit_cube_psf, _free,
+ * mpsfr_frame_background), in the host and in the device form alike:
  *   - a call that returns MPSFR_OK writes EVERY element of every output array it is given, at the size stated for the
  *     array: a row that holds no result -- a stamp or star with status 1 or 2, a star left out of one layer, a layer with
  *     nothing to fit, the rows of mpsfr_find_stars from count_out[0] up to max_stars, the rows of mpsfr_group_stars
@@ -764,7 +764,8 @@ int mpsfr_group_stars(mpsfr_ctx* ctx, int ny, int nx, int nstar, const double* p
  * frame, its own disc holds a valid pixel and sum w P~_k^2 over the valid pixels of its own disc is positive and finite
  * (so N_kk > 0: Omega only adds terms that are not negative).  Any other star is left out of the solve and of
  * resid_out: its row is status 2 (1: its footprint misses the frame) and zero otherwise.
- * Minimised over the F_k of the accepted stars and, with MPSFR_FIT_BACKGROUND, one constant b:
+ * Minimised over the F_k of the accepted stars and, with MPSFR_FIT_BACKGROUND, one constant b (a background that varies
+ * over the frame is taken out beforehand with mpsfr_frame_background, whose applied_out is an image for this call):
  *     sum over Omega of w (D - b - sum_k F_k P~_k)^2;
  * a pixel of Omega sees every star whose footprint reaches it.  Solver: conjugate gradients on the normal equations
  * N u = A^T W D with the diagonal of N as preconditioner M, matrix-free; start F = scale0 (NULL: 0; a value that is not
@@ -990,6 +991,71 @@ int mpsfr_fit_cube_psf_free(mpsfr_ctx* ctx, int nl, int ny, int nx, const double
                             int flags, int max_iter, double tol, int max_outer, double pos_tol, double max_step,
                             double max_move, double min_snr, double* star_out, double* head_out, double* pos_out,
                             double* shift_out, double* call_out, double* resid_out, int on_device);
+
+/* The background map of a frame or cube: a robust mesh of clipped medians, a smooth full-resolution map of it and an rms
+ * map (what SExtractor and photutils' Background2D build on the CPU), and optionally a second frame minus the map in the
+ * same call, so that fit -> residual -> background of the residual -> subtract -> refit runs on device buffers without a
+ * host synchronisation.
+ *
+ * image [nl][ny][nx], var the same shape or NULL, apply_to [nl][ny][nx] or NULL; a frame is nl = 1.  The frame rules of
+ * mpsfr_render_stars apply, with nl ny nx <= 2^26 in total.  Arithmetic is fp64 in both precision modes: a mixed context
+ * gives the bits of an f64 one.  A pixel is valid when its datum is finite and var, if given, is finite and > 0; var is
+ * a mask only, the estimator is unweighted.  A valid zero counts as +0 (x + 0.0 at intake): no order statistic depends
+ * on the sign of a zero.
+ * Mesh: cells of side box (MPSFR_BACKGROUND_MIN_BOX .. MPSFR_BACKGROUND_MAX_BOX) from pixel (0, 0), my = ceil(ny / box),
+ * mx = ceil(nx / box); edge cells are partial, npix is the number of a cell's pixels on the frame.
+ * Cell estimate: med(v) of n values in ascending order is v[(n-1)/2] for odd n and 0.5 v[n/2-1] + 0.5 v[n/2] for even
+ * n.  S_0 = the valid pixels of the cell, n_valid = |S_0|; the cell is valid iff n_valid >= 1 and (double)n_valid >=
+ * min_frac (double)npix (one rounded product).  For pass p = 0, 1, ...: m = med(S_p); d_i = |x_i - m| (one rounded
+ * subtraction); MAD = med(d); if p == max_clip the loop stops with MPSFR_BACK_CLIP_CAP, if MAD == 0 with MPSFR_BACK_FLAT
+ * (both when both hold); else t = kc MAD with kc = kappa 1.4826 rounded once on the host, S_(p+1) = {i in S_p : d_i <=
+ * t}, and the loop stops if nothing was rejected.  kappa >= 1 keeps S non-empty.  raw level = m, raw rms = 1.4826 MAD
+ * (one rounded product), n_used = |S_last|, passes = p.  Every quantity is an order statistic, an integer or a single
+ * rounding: the raw columns have no rounding freedom.
+ * Filter and fill: filter in {1, 3, 5}, h = (filter - 1) / 2.  For cell (i, j), W_r is the set of VALID cells in rows
+ * i-r .. i+r and columns j-r .. j+r inside the mesh; r starts at h and grows by 1 while W_r is empty and r < max(my,
+ * mx).  level = med of the raw levels over W_r, rms = med of the raw rms over W_r, taken separately.  A cell that is
+ * itself invalid has MPSFR_BACK_FILLED.  A layer without any valid cell has head status 2, level and rms NaN in every
+ * cell and NaN maps.
+ * mesh_out [nl][my][mx][MPSFR_NBACK]:
+ *   0 level   1 rms   2 raw level   3 raw rms (both NaN for an invalid cell)   4 n_used (0 for an invalid cell)
+ *   5 n_valid   6 passes   7 flags
+ * head_out [nl][MPSFR_NBACK_HEAD]: 0 status (0 fine, 1 some cells filled, 2 no valid cell)  1 valid cells  2 filled cells
+ *   3 zero
+ * map_out (or NULL) [nl][ny][nx]: the cubic-convolution interpolation of the level plane with the Keys polynomials of
+ * mpsfr_fit_stamps_psf.  Node i of an axis sits at pixel (i + 0.5) box - 0.5.  For pixel Y: u = ((double)Y + 0.5) /
+ * (double)box - 0.5, i0 = floor(u), t = u - i0; the taps i0-1 .. i0+2 carry the Keys weights c(t+1), c(t), c(t-1),
+ * c(t-2).  Beyond the mesh the plane continues linearly: E[-j] = M[0] + j (M[0] - M[1]) and E[m-1+j] = M[m-1] +
+ * j (M[m-1] - M[m-2]) for j = 1, 2 (every tap is M[0] on an axis of one cell), columns first, then rows.  The sum is
+ * separable: columns inner, rows outer, both ascending.  A plane on the nodes is reproduced over the whole frame up to
+ * rounding; replicated edge nodes would flatten gradients in the outer half cell.
+ * rms_out (or NULL): the same interpolation of the rms plane, values below 0 replaced by 0.  applied_out = apply_to -
+ * map, one rounded subtraction (a NaN of apply_to stays NaN); apply_to and applied_out are given together or both NULL,
+ * they may be the same buffer, and applied_out may not be image.
+ *
+ * Layer l of every output equals the call on layer l alone, bit for bit.  The same call repeated, host and device
+ * pointers, mixed and f64 contexts, optional outputs given or NULL (the other outputs do not change) give the same bits.
+ * A permutation of the pixels inside a cell changes no bit of columns 2 - 7 of that cell.  Negating the data negates the
+ * levels exactly and keeps every other column; a factor 2^k on the data scales levels and rms exactly, away from
+ * subnormals.  No floating-point atomics are used.
+ *
+ * on_device as mpsfr_render_stars: queued on the context stream behind the lanes, no host synchronisation.
+ * MPSFR_E_INVALID, outputs untouched, nothing queued: nl < 1 or the size out of range; box outside 8 .. 64; filter not 1,
+ * 3 or 5; kappa not finite or outside [1, 100]; max_clip outside 0 .. MPSFR_BACKGROUND_MAX_CLIP; min_frac not finite or
+ * outside (0, 1]; a NULL image, mesh_out or head_out; exactly one of apply_to and applied_out; applied_out == image.
+ * Timed under the fit's profiling id. */
+#define MPSFR_NBACK 8                  /* doubles per mesh cell */
+#define MPSFR_NBACK_HEAD 4             /* doubles per layer in head_out */
+#define MPSFR_BACKGROUND_MIN_BOX 8
+#define MPSFR_BACKGROUND_MAX_BOX 64
+#define MPSFR_BACKGROUND_MAX_CLIP 16
+#define MPSFR_BACK_FILLED 1            /* cell invalid: level and rms come from neighbours */
+#define MPSFR_BACK_CLIP_CAP 2          /* the clipping ended at max_clip */
+#define MPSFR_BACK_FLAT 4              /* MAD == 0 at the last pass */
+int mpsfr_frame_background(mpsfr_ctx* ctx, int nl, int ny, int nx, const double* image, const double* var,
+                           int box, int filter, double kappa, int max_clip, double min_frac,
+                           const double* apply_to, double* mesh_out, double* head_out, double* map_out,
+                           double* rms_out, double* applied_out, int on_device);
 
 /* The stages of the path as the reference exports them (muse_psfr/__init__.py:16: `from .psfrec import *`),
  * for a caller that holds its own PSD or its own stamps.  Host buffers, synchronous, float64; the same

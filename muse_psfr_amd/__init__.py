@@ -25,15 +25,17 @@ same with the positions free: fluxes and positions of all stars refined at once 
 crowded='free' mode of fit_found_stars) and fit_crowded_spectra (the solve of fit_crowded_stars on every wavelength
 layer of a cube, the layers side by side in one call: the spectra of all stars) and refine_crowded_spectra (the same
 with ONE position per star refined from the layers jointly, every layer with its own PSF and refraction offset).
+background_map (the sky of a frame or cube: a mesh of clipped medians, a smooth map of it and an rms map, all on the
+GPU) and the sky= argument of fit_crowded_stars (fit, background of the residual, subtract, refit).
 Low level: Context (ctypes binding of libmpsfr.so).
 """
-from ._lib import Context, ContextPool, MpsfrError, NFIT, NFIT_ELL, NMET_HEAD, FIT_ILL_CONDITIONED, FIT_BACKGROUND, FIT_ELLIPTICAL, NFIT_PSF, FIT_FIXED_SHIFT, NFIT_GROUP, MAX_GROUP, FIT_COMMON_SHIFT, NFIT_SPEC, NFIT_SPEC_LAYER, FIT_DRIFT, NRENDER, RENDER_SUBTRACT, RENDER_SORT_CHUNK, NFIND, FIND_MAX_HALF, FIND_MAX_SEP, NGROUP, GROUP_MAX_CRIT, GROUP_OVERSIZE, GROUP_WIDE, NFRAMEFIT, FRAME_FIT_MAX_RADIUS, CUBE_FIT_MAX_LAYERS, NFRAMEFREE, NFRAMEFREE_HEAD, FRAME_FREE_MAX_OUTER, FRAME_FREE_MAX_STEP, FRAME_FREE_MAX_MOVE, FRAME_FREE_HELD, FRAME_FREE_BOUND, FRAME_FREE_CLIPPED, NCUBEFREE_POS, NCUBEFREE_CALL, CUBE_FREE_WORK_BYTES  # noqa: F401
+from ._lib import Context, ContextPool, MpsfrError, NFIT, NFIT_ELL, NMET_HEAD, FIT_ILL_CONDITIONED, FIT_BACKGROUND, FIT_ELLIPTICAL, NFIT_PSF, FIT_FIXED_SHIFT, NFIT_GROUP, MAX_GROUP, FIT_COMMON_SHIFT, NFIT_SPEC, NFIT_SPEC_LAYER, FIT_DRIFT, NRENDER, RENDER_SUBTRACT, RENDER_SORT_CHUNK, NFIND, FIND_MAX_HALF, FIND_MAX_SEP, NGROUP, GROUP_MAX_CRIT, GROUP_OVERSIZE, GROUP_WIDE, NFRAMEFIT, FRAME_FIT_MAX_RADIUS, CUBE_FIT_MAX_LAYERS, NFRAMEFREE, NFRAMEFREE_HEAD, FRAME_FREE_MAX_OUTER, FRAME_FREE_MAX_STEP, FRAME_FREE_MAX_MOVE, FRAME_FREE_HELD, FRAME_FREE_BOUND, FRAME_FREE_CLIPPED, NCUBEFREE_POS, NCUBEFREE_CALL, CUBE_FREE_WORK_BYTES, NBACK, NBACK_HEAD, BACKGROUND_MIN_BOX, BACKGROUND_MAX_BOX, BACKGROUND_MAX_CLIP, BACK_FILLED, BACK_CLIP_CAP, BACK_FLAT  # noqa: F401
 from .synthetic import synthetic_rows, grid_pixscale  # noqa: F401
 from .psfrec import (MAX_L0, MIN_L0, compute_psf, compute_field_psf, compute_profile_psf,  # noqa: F401
                      band_weights, compute_band_psf, psf_metrics, fit_stars_with_psf, fit_star_groups_with_psf,
                      fit_star_spectra_with_psf, cut_star_stamps, render_star_field, subtract_stars, find_stars,
                      group_stars, fit_found_stars, fit_crowded_stars, refine_crowded_stars, fit_crowded_spectra,
-                     refine_crowded_spectra,
+                     refine_crowded_spectra, background_map,
                      compute_psf_from_sparta,
                      create_sparta_table, direction_perf, fit_psf_cube, fit_psf_with_polynom,
                      host_cutoff_masks, muse_intrinsic_psf, plot_psf, radial_profile,

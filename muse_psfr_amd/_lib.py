@@ -60,6 +60,15 @@ FRAME_FREE_CLIPPED = 4       # the last step was clipped by max_step (MPSFR_FRAM
 NCUBEFREE_POS = 8            # doubles per star of pos_out of mpsfr_fit_cube_psf_free (MPSFR_NCUBEFREE_POS)
 NCUBEFREE_CALL = 8           # doubles of its call_out (MPSFR_NCUBEFREE_CALL)
 CUBE_FREE_WORK_BYTES = 4 << 30   # budget of work memory of one such call (MPSFR_CUBE_FREE_WORK_BYTES)
+NBACK = 8                    # doubles per mesh cell of mpsfr_frame_background (MPSFR_NBACK)
+NBACK_HEAD = 4               # doubles per layer of its head (MPSFR_NBACK_HEAD)
+BACKGROUND_MIN_BOX = 8       # side of a mesh cell in pixels (MPSFR_BACKGROUND_MIN_BOX, MPSFR_BACKGROUND_MAX_BOX)
+BACKGROUND_MAX_BOX = 64
+BACKGROUND_MAX_CLIP = 16     # most clipping passes of a cell (MPSFR_BACKGROUND_MAX_CLIP)
+BACKGROUND_MAX_KAPPA = 100.0
+BACK_FILLED = 1              # cell flag: invalid, level and rms come from neighbours (MPSFR_BACK_FILLED)
+BACK_CLIP_CAP = 2            # the clipping ended at max_clip (MPSFR_BACK_CLIP_CAP)
+BACK_FLAT = 4                # MAD == 0 at the last pass (MPSFR_BACK_FLAT)
 DIM_AO = 80
 PREC_MIXED, PREC_F64 = 0, 1
 E_GRID = -3
@@ -154,6 +163,9 @@ def load():
     lib.mpsfr_find_stars.argtypes = [p, C.c_int, C.c_int, p, p, p, C.c_int, C.c_int, C.c_double, C.c_int, p, p, p, p,
                                      C.c_int]
     lib.mpsfr_find_stars.restype = C.c_int
+    lib.mpsfr_frame_background.argtypes = [p, C.c_int, C.c_int, C.c_int, p, p, C.c_int, C.c_int, C.c_double, C.c_int,
+                                           C.c_double, p, p, p, p, p, p, C.c_int]
+    lib.mpsfr_frame_background.restype = C.c_int
     lib.mpsfr_group_stars.argtypes = [p, C.c_int, C.c_int, C.c_int, p, C.c_int, C.c_double, C.c_int, p, p, p, p, p,
                                       C.c_int]
     lib.mpsfr_group_stars.restype = C.c_int
@@ -218,7 +230,7 @@ def load():
 
 
 EXPORTS = ['mpsfr_create', 'mpsfr_destroy', 'mpsfr_last_error', 'mpsfr_set_option',
-           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_fit_stamps_psf', 'mpsfr_fit_groups_psf', 'mpsfr_fit_spectra_psf', 'mpsfr_stamp_metrics', 'mpsfr_cut_stamps', 'mpsfr_render_stars', 'mpsfr_find_stars', 'mpsfr_group_stars', 'mpsfr_fit_frame_psf', 'mpsfr_fit_frame_psf_free', 'mpsfr_fit_cube_psf', 'mpsfr_fit_cube_psf_free', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
+           'mpsfr_reconstruct', 'mpsfr_reconstruct_field', 'mpsfr_reconstruct_profile', 'mpsfr_simul_psd_profile', 'mpsfr_reconstruct_band', 'mpsfr_reconstruct_multi', 'mpsfr_reconstruct_multi_async', 'mpsfr_wait_multi', 'mpsfr_fit_stamps', 'mpsfr_fit_stamps_elliptical', 'mpsfr_fit_stamps_observed', 'mpsfr_fit_stamps_psf', 'mpsfr_fit_groups_psf', 'mpsfr_fit_spectra_psf', 'mpsfr_stamp_metrics', 'mpsfr_cut_stamps', 'mpsfr_render_stars', 'mpsfr_find_stars', 'mpsfr_group_stars', 'mpsfr_fit_frame_psf', 'mpsfr_fit_frame_psf_free', 'mpsfr_fit_cube_psf', 'mpsfr_fit_cube_psf_free', 'mpsfr_frame_background', 'mpsfr_simul_psd', 'mpsfr_psf_from_psd',
            'mpsfr_psd_to_psf',
            'mpsfr_convolve_stamps', 'mpsfr_fit_rows', 'mpsfr_sync', 'mpsfr_last_ticket', 'mpsfr_wait', 'mpsfr_abandon',
            'mpsfr_stream', 'mpsfr_stream_wait', 'mpsfr_wait_event',
@@ -1110,6 +1122,61 @@ class Context:
         self._call_find(ny, nx, image_ptr, var_ptr, psf_ptr, half, sep, threshold, max_stars, star_out_ptr, origin_ptr,
                         count_ptr, map_ptr, 1)
 
+    def _call_background(self, nl, ny, nx, image, var, box, filter, kappa, max_clip, min_frac, apply_to, mesh, head, bmap,
+                         rms, applied, on_device):
+        p = _devptr if on_device else _vptr
+        _check(self.lib.mpsfr_frame_background(self._h, int(nl), int(ny), int(nx), p(image), p(var), int(box),
+                                               int(filter), float(kappa), int(max_clip), float(min_frac), p(apply_to),
+                                               p(mesh), p(head), p(bmap), p(rms), p(applied), on_device))
+
+    def frame_background(self, image, var=None, *, box=32, filter=3, kappa=3.0, max_clip=5, min_frac=0.25, apply_to=None,
+                         return_rms=True):
+        """The background of a frame (ny, nx) or of every layer of a cube (nl, ny, nx) (mpsfr_frame_background): the
+        median and 1.4826 MAD of every `box` x `box` cell (8 .. 64 pixels) under iterated clipping at `kappa` MADs-as-sigma
+        (at most `max_clip` passes), over the valid pixels (finite, and `var` finite and > 0: var is a mask, nothing is
+        weighted); a cell with fewer than `min_frac` of its pixels valid is filled from its neighbours; a median over
+        `filter` x `filter` cells (1, 3, 5); cubic interpolation to the frame.  Returns (map, rms, mesh, head): the
+        maps of the input's shape (rms None without `return_rms`), mesh (nl, my, mx, NBACK) -- 0 level, 1 rms, 2 raw
+        level, 3 raw rms, 4 pixels used, 5 valid pixels, 6 clipping passes, 7 flags (BACK_FILLED, BACK_CLIP_CAP,
+        BACK_FLAT) -- and head (nl, NBACK_HEAD): 0 status (0 fine, 1 some cells filled, 2 no valid cell), 1 valid and 2
+        filled cells; without the layer axis for a frame.  With `apply_to` (the input's shape) also apply_to - map, as
+        a fifth value."""
+        im, va, ap, box, filter, kappa, max_clip, min_frac = background_arguments(image, var, apply_to, box, filter, kappa,
+                                                                                  max_clip, min_frac)
+        if not isinstance(return_rms, (bool, np.bool_)):
+            raise ValueError('return_rms must be True or False')
+        nl = im.shape[0] if im.ndim == 3 else 1
+        ny, nx = im.shape[-2:]
+        my, mx = -(-ny // box), -(-nx // box)
+        lead = im.shape[:-2]
+        mesh = np.empty(lead + (my, mx, NBACK))
+        head = np.empty(lead + (NBACK_HEAD,))
+        bmap = np.empty(im.shape)
+        rms = np.empty(im.shape) if return_rms else None
+        applied = None if ap is None else np.empty(im.shape)
+        self._call_background(nl, ny, nx, im, va, box, filter, kappa, max_clip, min_frac, ap, mesh, head, bmap, rms,
+                              applied, 0)
+        return (bmap, rms, mesh, head) + (() if ap is None else (applied,))
+
+    def frame_background_device(self, nl, ny, nx, image_ptr, mesh_ptr, head_ptr, *, var_ptr=None, map_ptr=None,
+                                rms_ptr=None, apply_to_ptr=None, applied_ptr=None, box=32, filter=3, kappa=3.0,
+                                max_clip=5, min_frac=0.25):
+        """Device-buffer form (asynchronous, on_device = 1): `image_ptr`, `var_ptr`, `apply_to_ptr`, `map_ptr`, `rms_ptr`
+        and `applied_ptr` ([nl][ny][nx] float64; the optional ones None), `mesh_ptr` ([nl][my][mx][NBACK] float64) and
+        `head_ptr` ([nl][NBACK_HEAD] float64) are raw device pointers (int) on this context's GPU; the call is queued on
+        the context stream, after any device-output reconstruct of this context, without a host synchronisation.
+        apply_to_ptr and applied_ptr are given together; they may be the same buffer, and applied_ptr may not be
+        image_ptr."""
+        nl, ny, nx = background_shape(nl, ny, nx)
+        box, filter, kappa, max_clip, min_frac = background_parameters(box, filter, kappa, max_clip, min_frac)
+        _device_pointers(image_ptr=image_ptr, mesh_ptr=mesh_ptr, head_ptr=head_ptr)
+        if bool(apply_to_ptr) != bool(applied_ptr):
+            raise ValueError('apply_to_ptr and applied_ptr must both be None or both be device pointers')
+        if applied_ptr and int(applied_ptr) == int(image_ptr):
+            raise ValueError('applied_ptr may not be image_ptr')
+        self._call_background(nl, ny, nx, image_ptr, var_ptr, box, filter, kappa, max_clip, min_frac, apply_to_ptr,
+                              mesh_ptr, head_ptr, map_ptr, rms_ptr, applied_ptr, 1)
+
     def _call_group(self, ny, nx, nstar, pos, stride, crit, max_groups, label, groups, origin, shift, count, on_device):
         p = _devptr if on_device else _vptr
         _check(self.lib.mpsfr_group_stars(self._h, int(ny), int(nx), int(nstar), p(pos), int(stride), float(crit),
@@ -1659,6 +1726,67 @@ def find_arguments(image, var, psf, half, sep, threshold, max_stars, dimpsf=40):
     if np.all(core == core[0, 0]):
         raise ValueError('psf must not be constant over its core')
     return im, va, ps, half, sep, threshold, max_stars
+
+
+def background_parameters(box, filter, kappa, max_clip, min_frac):
+    """(box, filter, kappa, max_clip, min_frac) of a background call, validated as mpsfr_frame_background validates them
+    (ValueError)."""
+    def integer(name, n, lo, hi):
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not lo <= n <= hi:
+            raise ValueError('%s must be an integer between %d and %d' % (name, lo, hi))
+        return int(n)
+
+    def number(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError('%s must be a finite number' % name)
+        return float(v)
+    box = integer('box', box, BACKGROUND_MIN_BOX, BACKGROUND_MAX_BOX)
+    if isinstance(filter, bool) or not isinstance(filter, (int, np.integer)) or filter not in (1, 3, 5):
+        raise ValueError('filter must be 1, 3 or 5')
+    max_clip = integer('max_clip', max_clip, 0, BACKGROUND_MAX_CLIP)
+    kappa = number('kappa', kappa)
+    if not 1.0 <= kappa <= BACKGROUND_MAX_KAPPA:
+        raise ValueError('kappa must lie between 1 and %g' % BACKGROUND_MAX_KAPPA)
+    min_frac = number('min_frac', min_frac)
+    if not 0.0 < min_frac <= 1.0:
+        raise ValueError('min_frac must lie in (0, 1]')
+    return box, int(filter), kappa, max_clip, min_frac
+
+
+def background_shape(nl, ny, nx):
+    """ValueError unless (nl, ny, nx) is the shape of a background call: layers that are frames, 2^26 pixels in all."""
+    _positive_int('nl', nl)
+    ny, nx = frame_shape(ny, nx)
+    if int(nl) * ny * nx > MAX_IMAGE_PIXELS:
+        raise ValueError('a background call holds at most 2^26 pixels')
+    return int(nl), ny, nx
+
+
+def background_arguments(image, var, apply_to, box, filter, kappa, max_clip, min_frac):
+    """(image, var or None, apply_to or None, box, filter, kappa, max_clip, min_frac) of a host background call,
+    validated as mpsfr_frame_background validates host arguments (ValueError): `image` a frame of frame_images or a
+    numeric (nl, ny, nx) cube of such frames with at most 2^26 pixels (masked pixels become NaN); var and apply_to None
+    or of its shape."""
+    def volume(a, what):
+        try:
+            if isinstance(a, np.ma.MaskedArray):
+                return np.ma.filled(a.astype(np.float64), np.nan)
+            return np.asarray(a, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('%s must be a numeric array' % what) from None
+    im = volume(image, 'image')
+    if im.ndim not in (2, 3) or im.size == 0:
+        raise ValueError('image must have the shape (ny, nx) or (nl, ny, nx)')
+    background_shape(*((1,) * (3 - im.ndim) + im.shape))
+    others = []
+    for a, what in ((var, 'var'), (apply_to, 'apply_to')):
+        if a is not None:
+            a = volume(a, what)
+            if a.shape != im.shape:
+                raise ValueError('%s must have the shape of image' % what)
+            a = np.ascontiguousarray(a)
+        others.append(a)
+    return (np.ascontiguousarray(im), others[0], others[1]) + background_parameters(box, filter, kappa, max_clip, min_frac)
 
 
 def frame_fit_stars(nstar):

@@ -338,6 +338,15 @@ size_t find_workspace_bytes(int ny, int nx, int max_stars, bool with_map);
 void launch_find_stars(hipStream_t s, int ny, int nx, const double* d_image, const double* d_var, const double* d_psf,
                        int half, int sep, double threshold, int max_stars, double* d_star_out, int32_t* d_origin_out,
                        int32_t* d_count_out, double* d_map_out, void* d_ws);
+// The background map (background.hip; mpsfr_frame_background, include/mpsfr.h): the clipped median and MAD of every
+// box x box cell of every layer of d_image [nl][ny][nx] (d_var of that shape or nullptr: a mask), kc = kappa 1.4826,
+// filtered over filter x filter cells into d_mesh_out [nl][my][mx][8] and d_head_out [nl][4]; the level plane
+// interpolated into d_map_out, the rms plane into d_rms_out, d_apply_to minus the map into d_applied_out (each
+// [nl][ny][nx] or nullptr; d_applied_out may be d_apply_to).  No work memory: the later kernels read mesh_out and head_out.
+void launch_frame_background(hipStream_t s, int nl, int ny, int nx, const double* d_image, const double* d_var, int box,
+                             int filter, double kc, int max_clip, double min_frac, const double* d_apply_to,
+                             double* d_mesh_out, double* d_head_out, double* d_map_out, double* d_rms_out,
+                             double* d_applied_out);
 // Friends-of-friends groups of stars (group.hip; mpsfr_group_stars, include/mpsfr.h): the connected components of
 // "d2 <= crit^2" over the positions d_pos [nstar][stride] (columns 0 and 1: y, x) -- labels into d_label_out [nstar],
 // rows in (class, label) order into d_group_out [max_groups][8] and d_origin_out [max_groups][2], shifts at the

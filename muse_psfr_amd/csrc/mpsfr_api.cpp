@@ -3070,6 +3070,49 @@ int mpsfr_find_stars(mpsfr_ctx* c, int ny, int nx, const double* image, const do
     });
 }
 
+static_assert(MPSFR_NBACK == 8 && MPSFR_NBACK_HEAD == 4 && MPSFR_BACKGROUND_MAX_BOX == 64 && MPSFR_BACK_FILLED == 1 &&
+                  MPSFR_BACK_CLIP_CAP == 2 && MPSFR_BACK_FLAT == 4,
+              "k_bg_cell row layout, the keys of a cell in LDS and the flags");
+
+int mpsfr_frame_background(mpsfr_ctx* c, int nl, int ny, int nx, const double* image, const double* var, int box,
+                           int filter, double kappa, int max_clip, double min_frac, const double* apply_to,
+                           double* mesh_out, double* head_out, double* map_out, double* rms_out, double* applied_out,
+                           int on_device) {
+    const char* who = "frame_background";
+    if (!c || !image || !mesh_out || !head_out)
+        return fail(MPSFR_E_INVALID, "%s: bad argument (image, mesh_out and head_out are required)", who);
+    int rc;
+    if ((rc = frame_shape(who, ny, nx))) return rc;
+    if (nl < 1 || (size_t)nl * ny * nx > ((size_t)1 << 26))
+        return fail(MPSFR_E_INVALID, "%s: 1 or more layers of at most 2^26 pixels in total, not %d x %d x %d", who, nl, ny,
+                    nx);
+    if (box < MPSFR_BACKGROUND_MIN_BOX || box > MPSFR_BACKGROUND_MAX_BOX)
+        return fail(MPSFR_E_INVALID, "%s: box=%d outside %d..%d", who, box, MPSFR_BACKGROUND_MIN_BOX,
+                    MPSFR_BACKGROUND_MAX_BOX);
+    if (filter != 1 && filter != 3 && filter != 5)
+        return fail(MPSFR_E_INVALID, "%s: filter=%d is not 1, 3 or 5", who, filter);
+    if (!(kappa >= 1.0 && kappa <= 100.0)) return fail(MPSFR_E_INVALID, "%s: kappa must be finite, in 1..100", who);
+    if (max_clip < 0 || max_clip > MPSFR_BACKGROUND_MAX_CLIP)
+        return fail(MPSFR_E_INVALID, "%s: max_clip=%d outside 0..%d", who, max_clip, MPSFR_BACKGROUND_MAX_CLIP);
+    if (!(min_frac > 0.0 && min_frac <= 1.0)) return fail(MPSFR_E_INVALID, "%s: min_frac must lie in (0, 1]", who);
+    if ((apply_to == nullptr) != (applied_out == nullptr))
+        return fail(MPSFR_E_INVALID, "%s: apply_to and applied_out must both be NULL or both be given", who);
+    if (applied_out && applied_out == image) return fail(MPSFR_E_INVALID, "%s: applied_out may not be image", who);
+    const double kc = kappa * 1.4826;
+    const size_t npix = (size_t)nl * ny * nx;
+    const size_t ncell = (size_t)nl * ((ny + box - 1) / box) * ((nx + box - 1) / box);
+    const StampIn in[] = {{image, npix, sizeof(double)}, {var, npix, sizeof(double)}, {apply_to, npix, sizeof(double)}};
+    const StampOut out[] = {{mesh_out, ncell * MPSFR_NBACK},
+                            {head_out, (size_t)nl * MPSFR_NBACK_HEAD},
+                            {map_out, npix},
+                            {rms_out, npix},
+                            {applied_out, npix}};
+    return stamp_call(c, on_device, in, out, [&](hipStream_t s, const void* const* d, double* const* d_out) {
+        launch_frame_background(s, nl, ny, nx, (const double*)d[0], (const double*)d[1], box, filter, kc, max_clip,
+                                min_frac, (const double*)d[2], d_out[0], d_out[1], d_out[2], d_out[3], d_out[4]);
+    });
+}
+
 static_assert(MPSFR_NGROUP == 8 && MPSFR_MAX_GROUP == 4 && MPSFR_GROUP_MAX_CRIT == 2.0 * MPSFR_FIT_PSF_MAX_SHIFT,
               "K_GROUP_ROWS row layout, the member slots and the cell side");
 

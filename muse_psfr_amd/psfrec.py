@@ -947,8 +947,61 @@ def _crowded_inputs(psf, positions, psf_index, fit_back, start, pixscale):
     return ps, psf_index, start, origin, shift_px
 
 
+_BACK_COLS = ('level', 'rms', 'raw_level', 'raw_rms', 'n_used', 'n_valid', 'passes', 'flags')
+SKY_MAX_PASSES = 8
+
+
+def background_map(image, var=None, *, box=32, filter=3, kappa=3.0, max_clip=5, min_frac=0.25, pixscale=0.2,
+                   precision='mixed', device=0):
+    """The background of a frame (ny, nx) or of every layer of a cube (nl, ny, nx), on the GPU: a mesh of `box` x `box`
+    cells (8 .. 64 pixels), in each the median and 1.4826 x the median absolute deviation of the valid pixels under
+    iterated clipping at `kappa` such sigmas (at most `max_clip` passes) -- exact order statistics, no sums --, a cell
+    with fewer than `min_frac` of its pixels valid filled from its neighbours, a median filter over `filter` x
+    `filter` cells (1, 3, 5) and a bicubic interpolation to the frame that continues gradients to the frame's edge.
+    NaN pixels and var <= 0 are masked; var is a mask only.  Mask the stars (NaN) or pass the residual of a fit.
+
+    Returns (map, rms, mesh): the background and its noise at every pixel, of the input's shape -- rms squared is a
+    usable `var` for find_stars -- and a table with one row per cell in (layer, row, column) order: level, rms (after
+    filter and fill), raw_level, raw_rms (NaN for a cell without enough valid pixels), n_used, n_valid, passes, flags
+    (1 filled from neighbours, 2 clipping ended at max_clip, 4 MAD = 0).  mesh.meta: box, shape (the mesh: (my, mx), with
+    nl in front for a cube), status (0 fine, 1 some cells filled, 2 no valid cell), valid_cells, filled_cells -- per
+    layer for a cube."""
+    _pixscale(pixscale)
+    ctx = get_context(128, pixscale, 40, precision, device)
+    bmap, rms, mesh, head = ctx.frame_background(image, var, box=box, filter=filter, kappa=kappa, max_clip=max_clip,
+                                                 min_frac=min_frac)
+    rows = mesh.reshape(-1, _lib.NBACK)
+    cols = OrderedDict()
+    for k, name in enumerate(_BACK_COLS):
+        cols[name] = rows[:, k].copy() if k < 4 else rows[:, k].astype(np.int64)
+    per_layer = (lambda v: [int(x) for x in v]) if head.ndim == 2 else int
+    meta = OrderedDict([('box', int(box)), ('shape', tuple(mesh.shape[:-1])), ('status', per_layer(head[..., 0])),
+                        ('valid_cells', per_layer(head[..., 1])), ('filled_cells', per_layer(head[..., 2]))])
+    return bmap, rms, _make_table(cols, meta)
+
+
+def _sky_parameters(sky):
+    """(passes, background parameters) of the `sky` argument of fit_crowded_stars: True or a dict (ValueError)."""
+    if sky is True:
+        sky = {}
+    if not isinstance(sky, dict):
+        raise ValueError('sky must be None, True or a dict of background_map parameters and passes')
+    par = dict(box=32, filter=3, kappa=3.0, max_clip=5, min_frac=0.25, passes=2)
+    unknown = set(sky) - set(par)
+    if unknown:
+        raise ValueError('sky: unknown keys %s' % sorted(unknown))
+    par.update(sky)
+    passes = par.pop('passes')
+    if isinstance(passes, bool) or not isinstance(passes, (int, np.integer)) or not 1 <= passes <= SKY_MAX_PASSES:
+        raise ValueError('sky: passes must be an integer between 1 and %d' % SKY_MAX_PASSES)
+    box, filt, kappa, max_clip, min_frac = _lib.background_parameters(par['box'], par['filter'], par['kappa'],
+                                                                      par['max_clip'], par['min_frac'])
+    return int(passes), dict(box=box, filter=filt, kappa=kappa, max_clip=max_clip, min_frac=min_frac)
+
+
 def fit_crowded_stars(image, psf, positions, *, var=None, psf_index=None, radius=8.0, fit_back=True, start=None,
-                      max_iter=100, tol=1e-10, return_residual=False, pixscale=0.2, precision='mixed', device=0):
+                      max_iter=100, tol=1e-10, return_residual=False, sky=None, return_sky=False, pixscale=0.2,
+                      precision='mixed', device=0):
     """Crowded-field PSF photometry, on the GPU: the fluxes of ALL stars of a frame at known positions in one linear
     least-squares solve -- no limit on how many stars touch each other; the step for the groups fit_found_stars
     marks `crowded`.  `image` (ny, nx), `var` its variance frame or None (NaN pixels and var <= 0 are masked);
@@ -965,10 +1018,35 @@ def fit_crowded_stars(image, psf, positions, *, var=None, psf_index=None, radius
     far from 0 the conditional error is optimistic), npix (valid pixels within `radius` of the star) and status (0
     fitted, 1 off the frame, 2 left out: no valid pixel, or no model there).  fit.meta: back, err_back, chi2, npix
     (pixels of the solve), iterations, residual (the last relative preconditioned residual), status (0 converged, 1
-    max_iter reached, 2 nothing fitted).  With return_residual also the frame minus the fitted stars."""
+    max_iter reached, 2 nothing fitted).  With return_residual also the frame minus the fitted stars.
+
+    sky: None (the default: the single solve above), True or a dict of background_map's parameters (box, filter, kappa,
+    max_clip, min_frac) and `passes` (default 2): a background that varies over the frame is estimated between solves
+    instead of being pushed into the fluxes.  From map_0 = 0, for p = 1 .. passes: image - map_(p-1) is fitted with one
+    constant, and map_p = map_(p-1) + the background map of that fit's residual; the final fit, with fit_back as given
+    and started from the last fluxes, runs on image - map_passes.  fit.meta gains sky_passes; with return_sky the
+    map is appended to the returned tuple (the residual is that of the final fit: the sky is taken out of it)."""
     ps, psf_index, start, origin, shift_px = _crowded_inputs(psf, positions, psf_index, fit_back, start, pixscale)
     dimpsf = ps.shape[-1]
+    if not isinstance(return_sky, (bool, np.bool_)):
+        raise ValueError('return_sky must be True or False')
+    if sky is None and return_sky:
+        raise ValueError('return_sky needs sky')
+    passes, sky_par = (0, None) if sky is None else _sky_parameters(sky)
     ctx = get_context(128, pixscale, dimpsf, precision, device)
+    sky_map = None
+    if passes:
+        image, var = _lib.frame_images(image, var)
+        sky_map = np.zeros(image.shape)
+        frame = image
+        for _ in range(passes):
+            rows, _, resid = ctx.fit_frame_psf(frame, ps, origin, var=var, shift=shift_px, psf_index=psf_index,
+                                               scale0=start, radius=radius, background=True, max_iter=max_iter, tol=tol,
+                                               return_residual=True)
+            sky_map = sky_map + ctx.frame_background(resid, var, return_rms=False, **sky_par)[0]
+            frame = image - sky_map
+            start = np.where(np.isfinite(rows[:, 0]), rows[:, 0], 0.0)
+        image = frame
     res = ctx.fit_frame_psf(image, ps, origin, var=var, shift=shift_px, psf_index=psf_index, scale0=start,
                             radius=radius, background=bool(fit_back), max_iter=max_iter, tol=tol,
                             return_residual=return_residual)
@@ -986,8 +1064,10 @@ def fit_crowded_stars(image, psf, positions, *, var=None, psf_index=None, radius
     meta = OrderedDict([('back', float(head[0])), ('err_back', float(head[1])), ('chi2', float(head[2])),
                         ('npix', int(head[3])), ('iterations', int(head[4])), ('residual', float(head[5])),
                         ('status', int(head[7]))])
+    if passes:
+        meta['sky_passes'] = passes
     fit = _make_table(cols, meta)
-    return (fit, origin) + ((res[2],) if return_residual else ())
+    return (fit, origin) + ((res[2],) if return_residual else ()) + ((sky_map,) if return_sky else ())
 
 
 _FIT_COLS_REFINED = ('scale', 'shift', 'position', 'flux', 'err_scale', 'err_shift', 'err_flux', 'overlap', 'moved', 'npix',
