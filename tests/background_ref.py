@@ -1,6 +1,8 @@
 """NumPy restatement of mpsfr_frame_background (include/mpsfr.h), written literally: the sort-based med, the pass loop of
 a cell, filter and fill, the linear continuation of the mesh and the Keys taps; the a-priori bound of the interpolated
 maps; the scenes the host and the GPU tests share.  mesh and head have no rounding freedom and are compared bit for bit.
+fill_plan states a second time, from ring membership alone, which valid cells a cell's level and rms come from: the
+certificates of tests/background_cases.py are read from it.
 """
 import functools
 
@@ -92,6 +94,32 @@ def layer_mesh(image, var, box, filter, kappa, max_clip, min_frac):
     nvalid = int(good.sum())
     head = np.array([0.0 if nvalid == my * mx else 1.0 if nvalid else 2.0, nvalid, my * mx - nvalid, 0.0])
     return mesh, head
+
+
+def fill_plan(good, filter):
+    """Where every cell of a layer's mesh takes its level and rms from, written from ring membership alone (not from
+    layer_mesh's slices): plan[i][j] = (radius used, [(i', j') of the valid cells found at that radius]).  `good` (my, mx)
+    marks the valid cells.  Radius h = (filter - 1) / 2 stands for the filter window, the whole square
+    max(|di|, |dj|) <= h; a cell whose window holds no valid cell takes the ring max(|di|, |dj|) == r of the first
+    r = h + 1 .. max(my, mx) that holds one.  (None, []) in a layer without a valid cell."""
+    good = np.asarray(good, dtype=bool)
+    my, mx = good.shape
+    h = (filter - 1) // 2
+    live = [(int(a), int(b)) for a, b in zip(*np.nonzero(good))]
+    plan = [[(None, []) for _ in range(mx)] for _ in range(my)]
+    for i in range(my):
+        for j in range(mx):
+            dist = [max(abs(a - i), abs(b - j)) for a, b in live]
+            window = [c for c, d in zip(live, dist) if d <= h]
+            if window:
+                plan[i][j] = (h, window)
+                continue
+            for r in range(h + 1, max(my, mx) + 1):
+                ring = [c for c, d in zip(live, dist) if d == r]
+                if ring:
+                    plan[i][j] = (r, ring)
+                    break
+    return plan
 
 
 def keys_weights(t):

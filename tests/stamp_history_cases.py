@@ -15,7 +15,9 @@ with the kind of the leftovers:
   X  the other tenant of the workspace (fit_frame_psf <-> fit_frame_psf_free on framefit, fit_cube_psf <->
      fit_cube_psf_free on cubefit, the host form of fit_cube_psf with layer_batch = 2 over 5 layers, render_stars with
      the pile of 300 before a fit of the same frame shape; for the stamp calls the host form of fit_cube_psf, which lays
-     the staging buffer out by hand)
+     the staging buffer out by hand; frame_background, which has no workspace and leaves three input and five output
+     planes in the staging buffer, before the frame calls and cut_stamps, and find, a frame fit and the cube's host form
+     before it)
   T  another terminal state at the same shape: only the steering words differ
   N  the same entry point on data of NaN, +-inf and +-1e300: the workspaces are left holding non-finite doubles
   F  a refused call of the same entry point (MPSFR_E_INVALID) between two good ones
@@ -23,6 +25,7 @@ Every predecessor is a legal call: nothing is poisoned.
 """
 import numpy as np
 
+import background_ref as BG
 import cube_fit_cases as K
 import cube_free_cases as Q
 import cube_free_ref as CR
@@ -445,6 +448,27 @@ def hold_metrics(api, out, prec):
     assert max(worst.values()) <= 1.0, worst
 
 
+BACK_OUT = ('mesh', 'head', 'map', 'rms', 'applied')
+
+
+def background(ctx, image, var=None, apply=None, **kw):
+    """mpsfr_frame_background through the raw call of its parity test (canaries behind every output)."""
+    import test_gpu_background as T
+    return T.raw_back(ctx, image, var, apply, **kw)
+
+
+def run_background(api, ctx):
+    s = BG.scene()
+    return _arrays(background(ctx, s['image'], s['var'], s['apply']), BACK_OUT)
+
+
+def hold_background(api, out, prec):
+    import test_gpu_background as T
+    ref = BG.scene_reference(True, BG.DEFAULTS['box'], BG.DEFAULTS['filter'], BG.DEFAULTS['max_clip'])
+    assert (ref['mesh'][0][..., 7].astype(int) & BG.FILLED).any() and np.any(ref['mesh'][0][..., 6] >= 2)
+    T.assert_parity(out, ref, 'call history', BG.scene()['apply'])
+
+
 CHECKED = {
     'render_stars': (run_render, hold_render),
     'cut_stamps': (run_cut, hold_cut),
@@ -460,9 +484,11 @@ CHECKED = {
     'fit_groups_psf': (run_fit_groups, hold_fit_groups),
     'fit_spectra_psf': (run_fit_spectra, hold_fit_spectra),
     'stamp_metrics': (run_metrics, hold_metrics),
+    'frame_background': (run_background, hold_background),
 }
 FRAME_CALLS = ('render_stars', 'find_stars', 'group_stars', 'fit_frame_psf', 'fit_frame_psf_free', 'fit_cube_psf',
-               'fit_cube_psf_free')
+               'fit_cube_psf_free', 'frame_background')
+AFTER_BACKGROUND = tuple(c for c in FRAME_CALLS if c != 'frame_background') + ('cut_stamps',)      # have X_background
 
 
 # ---- variants: other terminal states as the checked call itself -----------------------------------------------------
@@ -641,6 +667,32 @@ def _dead_layer(c, l=1):
     return d
 
 
+_BACK_SCENES = {}
+
+
+def _back_scenes():
+    """The frames of the background predecessors: `cube` 3 x 200 x 310 with var and apply (every array of the checked
+    call lies over its planes in the staging buffer), `tiny` 9 x 11, `large` the L frame of the suite with a NaN tile
+    and its variances."""
+    if not _BACK_SCENES:
+        rng = np.random.default_rng(31)
+        shape = (3, 200, 310)
+        lf = _large()
+        tile = lf['image'].copy()
+        tile[32:64, 64:96] = np.nan
+        _BACK_SCENES.update(cube=rng.normal(size=shape) + 4.0, cube_var=rng.uniform(0.5, 1.5, shape),
+                            cube_apply=rng.normal(size=shape), tiny=rng.normal(size=(9, 11)), large=tile,
+                            large_var=lf['var'])
+    return _BACK_SCENES
+
+
+def _background_large(api, ctx):
+    """X_background: the staging buffer's newest tenant before a frame call -- three input and five output planes."""
+    b = _back_scenes()
+    out = background(ctx, b['large'], b['large_var'], b['large'], box=32, filter=3)
+    assert out['head'][0, 0] == 1.0 and out['applied'] is not None
+
+
 def _fit_family(call, scene, large, small, wild, other, kw, free):
     """The predecessors of a frame or cube fit: `call` is the entry point on a scene dict, `other` the other tenant of
     its workspace, `kw` the solver's keywords of the checked call, `free` whether the positions are free."""
@@ -781,6 +833,23 @@ def _predecessors():
         'X_host_batches_of_2': _cube_host_batches,
         'T_dead_layer_1': lambda api, ctx: cube_free(ctx, _dead_layer(Q.cube(True)), **kwf),
         'F_refused': _cube_free_refusal})
+    # frame_background: a tenant of the staging buffer with no workspace of its own
+    bs, bk = BG.scene(), _back_scenes()
+    P['frame_background'] = {
+        'L_larger': lambda api, ctx: background(ctx, bk['cube'], bk['cube_var'], bk['cube_apply'], box=64, filter=5),
+        'S_smaller': lambda api, ctx: background(ctx, bk['tiny'], None, bk['tiny'], box=8, filter=1),
+        'X_find': lambda api, ctx: _find(ctx, fs['image'], fs['psf'], fs['var'], threshold=thr),
+        'X_frame_fit': lambda api, ctx: frame_fit(ctx, F.scene()),
+        'X_cube_host': _cube_host_small,
+        'T_all_dead': lambda api, ctx: background(ctx, np.full(BG.FRAME, np.nan), bs['var'], bs['apply']),
+        'T_mesh_only': lambda api, ctx: background(ctx, bs['image'], bs['var'], None, want=()),
+        'N_non_finite': lambda api, ctx: background(ctx, wild_copy(bs['image']), wild_copy(bs['var'], 42),
+                                                    wild_copy(bs['apply'], 43)),
+        'F_refused': lambda api, ctx: _refused(background(ctx, bs['image'], expect_rc=E_INVALID, box=7)['rc']),
+    }
+    # ... and a predecessor of the frame calls and of cut_stamps
+    for name in AFTER_BACKGROUND:
+        P[name]['X_background'] = _background_large
     # the variants: the family of their entry point at the variant's own keywords, and the checked call before them
     def variant(name, base, call, scene, large, small, other, kw, free, refusal, extra=()):
         p = _fit_family(call, scene, large, small, (lambda: large(wild=True)), other, kw, free)
@@ -893,24 +962,27 @@ _FIT = ['L_larger', 'S_smaller', 'X_other_tenant', 'X_other_tenant_larger', 'X_r
         'T_nothing_fitted', 'T_background_off', 'T_no_variance', 'N_non_finite', 'F_refused']
 _FREE = ['T_max_outer_0', 'T_max_outer_6', 'T_all_held', 'T_none_held']
 _STAMP = ['L_more_stamps', 'S_fewer_stamps', 'N_non_finite', 'X_cube_host', 'X_cube_host_batches_of_2', 'F_refused']
+_BACK = ['X_background']                       # of AFTER_BACKGROUND
 LABELS = {
     'render_stars': ['L_larger', 'S_smaller', 'X_frame_fit', 'X_frame_free', 'T_nothing_on_the_frame',
-                     'T_added_to_zeros', 'N_non_finite', 'F_refused'],
-    'cut_stamps': ['L_larger', 'S_smaller_no_var', 'N_non_finite', 'X_cube_host', 'F_refused'],
+                     'T_added_to_zeros', 'N_non_finite', 'F_refused'] + _BACK,
+    'cut_stamps': ['L_larger', 'S_smaller_no_var', 'N_non_finite', 'X_cube_host', 'F_refused'] + _BACK,
     'find_stars': ['L_larger', 'S_smaller', 'T_without_map', 'T_without_origin', 'T_more_peaks_than_max_stars',
-                   'T_no_variance_half_8', 'T_no_peaks', 'N_non_finite', 'X_render_pile', 'F_refused'],
+                   'T_no_variance_half_8', 'T_no_peaks', 'N_non_finite', 'X_render_pile', 'F_refused'] + _BACK,
     'group_stars': ['L_larger', 'S_smaller', 'T_oversize_chains', 'T_max_groups_too_small', 'T_chains_max_groups_2',
-                    'T_without_tables', 'T_widest_crit', 'N_fillers', 'X_find', 'F_refused'],
-    'fit_frame_psf': _FIT,
-    'fit_frame_psf_free': _FIT + _FREE,
-    'fit_cube_psf': _FIT + ['X_host_batches_of_2', 'T_dead_layer_1', 'T_one_layer_at_a_time'],
-    'fit_cube_psf_free': _FIT + _FREE + ['X_host_batches_of_2', 'T_dead_layer_1'],
+                    'T_without_tables', 'T_widest_crit', 'N_fillers', 'X_find', 'F_refused'] + _BACK,
+    'fit_frame_psf': _FIT + _BACK,
+    'fit_frame_psf_free': _FIT + _FREE + _BACK,
+    'fit_cube_psf': _FIT + ['X_host_batches_of_2', 'T_dead_layer_1', 'T_one_layer_at_a_time'] + _BACK,
+    'fit_cube_psf_free': _FIT + _FREE + ['X_host_batches_of_2', 'T_dead_layer_1'] + _BACK,
     'fit_stamps_elliptical': _STAMP,
     'fit_stamps_observed': _STAMP,
     'fit_stamps_psf': _STAMP,
     'fit_groups_psf': _STAMP,
     'fit_spectra_psf': _STAMP + ['T_drift_x_then_another_x_then_none'],
     'stamp_metrics': _STAMP,
+    'frame_background': ['L_larger', 'S_smaller', 'X_find', 'X_frame_fit', 'X_cube_host', 'T_all_dead', 'T_mesh_only',
+                         'N_non_finite', 'F_refused'],
     'find_stars.no_map': ['T_with_map', 'T_without_origin', 'L_larger', 'S_smaller', 'N_non_finite', 'X_render_pile',
                           'F_refused'],
     'fit_frame_psf.max_iter_1': _FIT + ['T_checked_call'],
@@ -923,7 +995,8 @@ LABELS = {
 # f64: the frame and cube calls run the same fp64 kernels in both modes -- L, X and one T per checked call; the stamp
 # calls have kernels of their own per mode and run their whole list
 _F64_FRAME = ('L_larger', 'X_other_tenant', 'X_cube_host', 'X_frame_fit', 'X_find', 'X_render_pile', 'T_max_iter_1',
-              'T_without_map', 'T_oversize_chains', 'T_nothing_on_the_frame', 'T_checked_call', 'T_with_map')
+              'T_without_map', 'T_oversize_chains', 'T_nothing_on_the_frame', 'T_checked_call', 'T_with_map',
+              'X_background', 'T_mesh_only')
 F64_LABELS = {name: [p for p in labels if p in _F64_FRAME]
               if name in FRAME_CALLS + VARIANTS + ('cut_stamps',) else list(labels)
               for name, labels in LABELS.items()}
@@ -1078,6 +1151,17 @@ def dev_cube_free(api, ctx, torch, o):
     return t
 
 
+def dev_background(api, ctx, torch, o):
+    s = BG.scene()
+    ny, nx = s['image'].shape
+    my, mx = BG.mesh_shape(ny, nx, BG.DEFAULTS['box'])
+    t = [_up(torch, np.array(s[k])) for k in ('image', 'var', 'apply')]          # (the scene's arrays are read-only)
+    ctx.frame_background_device(1, ny, nx, t[0].data_ptr(), o.new('mesh', (1, my, mx, 8)), o.new('head', (1, 4)),
+                                var_ptr=t[1].data_ptr(), map_ptr=o.new('map', (ny, nx)), rms_ptr=o.new('rms', (ny, nx)),
+                                apply_to_ptr=t[2].data_ptr(), applied_ptr=o.new('applied', (ny, nx)), **BG.DEFAULTS)
+    return t
+
+
 def dev_fit_ell(api, ctx, torch, o):
     st = _up(torch, np.array([M.stamp(*p) for p in _ell_pars()]))
     ctx.fit_stamps_elliptical_device(len(st), st.data_ptr(), o.new('fit', (len(st), api.NFIT_ELL)))
@@ -1144,7 +1228,7 @@ DEVICE = {
     'fit_frame_psf': dev_frame_fit, 'fit_frame_psf_free': dev_frame_free, 'fit_cube_psf': dev_cube_fit,
     'fit_cube_psf_free': dev_cube_free, 'fit_stamps_elliptical': dev_fit_ell, 'fit_stamps_observed': dev_fit_obs,
     'fit_stamps_psf': dev_fit_psf, 'fit_groups_psf': dev_fit_groups, 'fit_spectra_psf': dev_fit_spectra,
-    'stamp_metrics': dev_metrics,
+    'stamp_metrics': dev_metrics, 'frame_background': dev_background,
 }
 
 

@@ -3,7 +3,11 @@
 1. parity with the NumPy restatement (background_ref) on the 97 x 150 scene, with and without var, box 8, 16, 33 and 64,
    filter 1, 3 and 5, max_clip 0 and 5: mesh_out and head_out bit for bit; map_out, rms_out and applied_out within the
    reference's a-priori bound, NaN exactly where the reference has it.
-2. the shapes and cell contents where the kernel can go wrong, against the same reference.
+2. the shapes and cell contents where the kernel can go wrong, against the same reference; the case table of
+   background_cases.py, each case certified on the reference to reach its path: rows of more than 256 pixels (each map
+   also asked for alone), more than 256 cells, a cube of dense, sparse and dead layers (each layer = the call on it,
+   device = host), the ring search on sparse and long meshes, ties on a ring, n_valid across the sort sizes, 16 passes and
+   one-sided clipping, min_frac at equality, the rms clamp (exactly 0 where the unclamped reference is negative).
 3. invariances, bit for bit: host = device pointers, mixed = f64, a second call, a call after other work of the context,
    each optional output given or NULL, a layer of a cube = the call on that layer, permutations inside the cells,
    negation, a factor 2^11, the scene moved inside a NaN frame.
@@ -20,6 +24,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import background_cases as K
 import background_ref as B
 from conftest import record_margin
 
@@ -100,10 +105,20 @@ def raw_back(ctx, image, var=None, apply_to=None, want=('map', 'rms'), expect_rc
     return out
 
 
-def assert_parity(got, ref, tag):
-    """mesh and head bit for bit, the maps within the a-priori bounds; returns the worst error / bound."""
+def assert_parity(got, ref, tag, apply=None):
+    """mesh and head bit for bit, the maps within the a-priori bounds; returns the worst error / bound.
+    applied_out is apply_to - map_out in one rounded subtraction (include/mpsfr.h).  Against the reference its bound
+    is therefore the map's and the two subtractions' own roundings: fl(a - m) - fl(a - m') = (m' - m) + (a - m) d -
+    (a - m') d' with |d|, |d'| <= eps, to first order |m - m'| + 2 eps |a - m'| (where the map is small beside
+    apply_to, half an ulp of the difference is more than the whole bound of the map).  With `apply` given and both
+    planes asked for, applied_out is also held to the call's own map_out, bit for bit."""
     assert _same(got['mesh'], ref['mesh'].reshape(got['mesh'].shape)), tag
     assert _same(got['head'], ref['head'].reshape(got['head'].shape)), tag
+    if apply is not None and got.get('map') is not None and got.get('applied') is not None:
+        with np.errstate(invalid='ignore'):
+            own = np.asarray(apply, dtype=np.float64).reshape(got['map'].shape) - got['map']
+        fin = np.isfinite(own)
+        assert np.array_equal(np.isnan(got['applied']), np.isnan(own)) and _same(got['applied'][fin], own[fin]), tag
     worst = 0.0
     for k, bk in (('map', 'map_bound'), ('rms', 'rms_bound'), ('applied', 'map_bound')):
         if got.get(k) is None or ref.get(k) is None:
@@ -113,6 +128,8 @@ def assert_parity(got, ref, tag):
         fin = np.isfinite(ref[k])
         assert _same(got[k][~nan & ~fin], ref[k][~nan & ~fin]), (tag, k)
         err, bnd = np.abs(got[k][fin] - ref[k][fin]), ref[bk][fin]
+        if k == 'applied':
+            bnd = bnd + 2.0 * B.EPS * np.abs(ref[k][fin])
         some = err > 0
         ratio = float(np.max(err[some] / bnd[some])) if some.any() else 0.0
         print('%s %s: worst error / bound %.3f' % (tag, k, ratio))
@@ -131,7 +148,7 @@ def test_parity_with_numpy_on_the_scene(ctx, prec, usevar, box, filter, max_clip
     s = B.scene()
     ref = B.scene_reference(usevar, box, filter, max_clip)
     got = raw_back(ctx, s['image'], s['var'] if usevar else None, s['apply'], box=box, filter=filter, max_clip=max_clip)
-    worst = assert_parity(got, ref, 'scene var=%d box=%d filter=%d clip=%d' % (usevar, box, filter, max_clip))
+    worst = assert_parity(got, ref, 'scene var=%d box=%d filter=%d clip=%d' % (usevar, box, filter, max_clip), s['apply'])
     record_margin('background', map_error_over_bound=worst)
 
 
@@ -175,7 +192,7 @@ def test_shapes_and_cells_where_the_kernel_can_go_wrong(ctx, prec, name):
     image, var, par = CASES[name]
     ref = B.background(image, var, apply_to=image, **par)
     got = raw_back(ctx, image, var, image, **par)
-    assert_parity(got, ref, name)
+    assert_parity(got, ref, name, image)
     if name == 'all NaN':
         assert np.all(got['head'] == [2.0, 0.0, 15.0, 0.0]) and np.all(np.isnan(got['map'])) and np.all(np.isnan(got['rms']))
         assert np.all(np.isnan(got['mesh'][..., :4])) and np.all(got['mesh'][..., 4:7] == 0) and np.all(got['mesh'][..., 7] == 1)
@@ -185,6 +202,39 @@ def test_shapes_and_cells_where_the_kernel_can_go_wrong(ctx, prec, name):
     if name == 'one and two valid':
         m = got['mesh'][0]
         assert m[0, 0, 2] == 2.5 and m[0, 0, 5] == 1 and m[1, 0, 2] == 1.5 and m[1, 0, 3] == 1.4826 * 2.5 and m[1, 0, 5] == 2
+
+
+@pytest.mark.parametrize('name', K.NAMES)
+@pytest.mark.parametrize('prec', PRECS)
+def test_parity_on_the_case_table(ctx, prec, name):
+    """The cases of background_cases.py: wide rows, more than 256 cells, the ring search, ties, the sort sizes, long and
+    one-sided clipping, min_frac at equality, the rms clamp.  That a case reaches its path is its certificate on the
+    reference (test_background_cases_host.py, and once more here); the comparison is the one of the scene."""
+    d, ref = K.inputs(name), K.reference(name)
+    failed = [claim for claim, holds in K.certificate(name) if not holds]
+    assert not failed, failed
+    image, var, apply, par, family = d['image'], d['var'], d['apply'], d['par'], K.family(name)
+    got = raw_back(ctx, image, var, apply, **par)
+    worst = assert_parity(got, ref, name, apply)
+    if family == 'clamp':
+        below = K.clamped_pixels(ref)
+        assert below.any() and np.all(got['rms'][below] == 0.0)
+    if family == 'wide':
+        # one plane at a time: the level and the rms branch of the fill of sE each on their own, past the first block
+        alone = raw_back(ctx, image, var, None, want=('rms',), **par)
+        assert alone['map'] is None and alone['applied'] is None and _same(alone['rms'], got['rms'])
+        worst = max(worst, assert_parity(alone, ref, name + ', rms_out alone'))
+        alone = raw_back(ctx, image, var, apply, want=(), **par)
+        assert alone['map'] is None and alone['rms'] is None and _same(alone['applied'], got['applied'])
+        worst = max(worst, assert_parity(alone, ref, name + ', applied_out alone'))
+    if image.ndim == 3 and family == 'cells':
+        for layer in range(len(image)):
+            one = raw_back(ctx, image[layer], None, apply[layer], **par)
+            for k in OUTS:
+                assert _same(got[k][layer], one[k][0] if k in ('mesh', 'head') else one[k]), (layer, k)
+        assert _equal(device_back(ctx, image, None, apply, **par), got)
+    print('%s (%s): worst error / bound %.3f' % (name, family, worst))
+    record_margin('background', map_error_over_bound=worst, **{'map_error_over_bound_' + family: worst})
 
 
 @pytest.mark.parametrize('prec', PRECS)

@@ -17,7 +17,7 @@ Predecessors (each run to completion, options restored afterwards):
   P7 the other entry points: profile, field, band, convolve_stamps, the device elliptical fit, psd_to_psf
   P8 the device circular fit (fit_stamps_device)
   P10 psd_to_psf at a smaller transform length, and on a PSD with a NaN (its own workspaces left holding NaN)
-  P9 the fourteen stamp, frame and cube calls of tests/stamp_history_cases.py in sequence (the staging buffer and the
+  P9 the fifteen stamp, frame and cube calls of tests/stamp_history_cases.py in sequence (the staging buffer and the
      frame workspaces; the other direction is tests/test_gpu_stamp_call_history.py)
 """
 import numpy as np

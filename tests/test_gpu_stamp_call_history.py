@@ -1,6 +1,6 @@
 """GPU: a stamp, frame or cube call's result does not depend on what ran before it on the same context.
 
-The fourteen entry points behind the staging buffer and the grow-only frame workspaces of mpsfr_api.cpp (stage, specx,
+The fifteen entry points behind the staging buffer and the grow-only frame workspaces of mpsfr_api.cpp (stage, specx,
 render, find, group, framefit, cubefit; the audit is DESIGN.md "Call-order independence", the second table) follow the
 protocol of tests/test_gpu_call_history.py: on one context the checked call runs once, so that the workspaces are sized
 for it, then a predecessor, then the checked call again -- and every output array of that second run equals, byte for
