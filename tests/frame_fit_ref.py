@@ -28,6 +28,9 @@ The bound of y is the sum of the four, in the 2-norm over all unknowns.  F_k alo
                 the residual frame carries |dR| <= (L + 20) EPS S per pixel, S = |D| + sum |F| |P~| + |b|, and the sum over
                 Omega (|Omega| + 4) EPS chi2: 2 sqrt(chi2 sum w dR^2) + sum w dR^2 + (|Omega| + 4) EPS chi2.
 None of these is fitted to what the GPU gives.
+
+solve_sparse() is solve() with a sparse design matrix, for thousands of stars or millions of pixels; it solves the normal
+equations with refinement, and bounds() then takes its a-posteriori 'ref_err' for the reference term (its docstring).
 """
 import numpy as np
 
@@ -156,6 +159,132 @@ def solve(image, var, psf, index, origin, shift, radius, background):
     return out
 
 
+REFINE = 3
+
+
+def solve_sparse(image, var, psf, index, origin, shift, radius, background):
+    """solve() for thousands of stars or millions of pixels: the same contract and the same dict keys, with the design
+    matrix A a scipy.sparse CSR matrix over Omega whose columns come from render_ref.window on each star's footprint
+    (no per-star frame is kept; the disc lies inside the footprint, so the disc rule is evaluated there with the same
+    operations).  N, Nabs and dg are dense, (nstar + 1)^2.
+
+    x is not lstsq's: the scaled normal equations Ns y = Dg^(-1/2) A^T W D by numpy.linalg.solve, then REFINE rounds of
+    refinement on the gradient g(x) = A^T W (D - A x).  Its error is accounted for a posteriori.  The gradient is
+    linear, g(x) = N (x* - x), so Dg^(1/2) (x - x*) = Ns^-1 Dg^(-1/2) g(x) and |y - y*| <= |Dg^(-1/2) g(x)| / lmin for
+    the exact gradient at the x returned.  The computed gradient differs from the exact one by rounding: the residual
+    of a pixel, a sum of at most L + 1 products, by (L + 3) EPS (|D| + |A| |x|) =: dres, and entry k of the projection,
+    a sum of at most m terms (m the longest column), by (m + 3) EPS (|A|^T W |res|)_k + (|A|^T W dres)_k.  'ref_err' is
+    (|Dg^(-1/2) g| + |Dg^(-1/2) dg|) / lmin in the 2-norm: the term bounds() takes in place of lstsq's."""
+    import scipy.sparse as sp
+    image = np.asarray(image, dtype=np.float64)
+    shape = image.shape
+    ny, nx = shape
+    n = len(origin)
+    ok = valid_pixels(image, var)
+    w = np.where(ok, 1.0 / np.where(ok, 1.0 if var is None else var, 1.0), 0.0)
+    status = np.zeros(n, dtype=int)
+    ndisc = np.zeros(n)
+    wins, omega = {}, np.zeros(shape, dtype=bool)
+    r2 = np.float64(radius) * np.float64(radius)
+    for k in range(n):
+        ix = k if index is None else int(index[k])
+        sh = None if shift is None else shift[k]
+        fine = 0 <= ix < len(psf) and np.all(np.abs(origin[k]) <= MAX_ORIGIN) and \
+            (sh is None or bool(np.all(np.abs(sh) <= MAX_SHIFT)))
+        if not fine:
+            status[k] = 2
+            continue
+        y0, y1, x0, x1 = Y.footprint(shape, origin[k])
+        if y0 >= y1 or x0 >= x1:
+            status[k] = 1
+            continue
+        dp, dq = (0.0, 0.0) if sh is None else sh
+        win = Y.window(psf[ix], dp, dq)
+        wy, wx = y0 - (int(origin[k][0]) - APRON), x0 - (int(origin[k][1]) - APRON)
+        col = win[wy:wy + y1 - y0, wx:wx + x1 - x0]
+        c = centre(origin[k], sh)
+        dy = (np.arange(y0, y1, dtype=np.float64) - c[0])[:, None]
+        dx = (np.arange(x0, x1, dtype=np.float64) - c[1])[None, :]
+        a, b = dy * dy, dx * dx
+        dk = (a + b <= r2) & ok[y0:y1, x0:x1]
+        own = float(np.sum(w[y0:y1, x0:x1][dk] * col[dk] ** 2))
+        if dk.sum() == 0 or not (own > 0 and np.isfinite(own)):
+            status[k] = 2
+            continue
+        ndisc[k] = dk.sum()
+        wins[k] = (y0, y1, x0, x1, col)
+        omega[y0:y1, x0:x1] |= dk
+    acc = sorted(wins)
+    nomega, nacc = int(omega.sum()), len(acc)
+    nunk = nacc + (1 if background else 0)
+    out = dict(status=status, F=np.zeros(n), err=np.zeros(n), flux=np.zeros(n), err_flux=np.zeros(n),
+               overlap=np.zeros(n), ndisc=np.zeros(n), nkk=np.zeros(n), sigma=np.zeros(n), b=0.0, err_b=0.0, chi2=0.0,
+               nomega=nomega, nacc=nacc, omega=omega, acc=np.array(acc, dtype=int), resid=image.copy(), head_status=0)
+    if nacc == 0 or nomega < nunk + 1:
+        out['status'] = np.where(status == 1, 1, 2)
+        out['head_status'] = 2
+        return out
+    place = np.full(shape, -1, dtype=np.int64)
+    place[omega] = np.arange(nomega)                       # (boolean indexing runs in pixel order, as A[omega] does)
+    ri, ci, vals = [], [], []
+    for j, k in enumerate(acc):
+        y0, y1, x0, x1, col = wins[k]
+        p = place[y0:y1, x0:x1]
+        on = (p >= 0) & (col != 0.0)
+        ri.append(p[on])
+        ci.append(np.full(int(on.sum()), j, dtype=np.int64))
+        vals.append(col[on])
+    if background:
+        ri.append(np.arange(nomega))
+        ci.append(np.full(nomega, nacc, dtype=np.int64))
+        vals.append(np.ones(nomega))
+    A = sp.csr_matrix((np.concatenate(vals), (np.concatenate(ri), np.concatenate(ci))), shape=(nomega, nunk))
+    Aabs = abs(A)
+    wo, d = w[omega], image[omega]
+    W = sp.diags(wo)
+    N = np.asarray((A.T @ W @ A).todense())
+    Nabs = np.asarray((Aabs.T @ W @ Aabs).todense())
+    dg = np.diag(N).copy()
+    s = 1.0 / np.sqrt(dg)
+    Ns = N * s[:, None] * s[None, :]
+    x = np.zeros(nunk)
+    for _ in range(1 + REFINE):
+        g = A.T @ (wo * (d - A @ x))
+        x = x + s * np.linalg.solve(Ns, s * g)
+    res = d - A @ x
+    g = A.T @ (wo * res)
+    L = int(np.max(np.diff(A[:, :nacc].tocsr().indptr)))
+    m = int(np.max(np.diff(A.tocsc().indptr)))
+    dres = (L + 3) * EPS * (np.abs(d) + Aabs @ np.abs(x))
+    dgrad = (m + 3) * EPS * (Aabs.T @ (wo * np.abs(res))) + Aabs.T @ (wo * dres)
+    lmin = float(np.linalg.eigvalsh(Ns)[0])
+    ref_err = (float(np.linalg.norm(s * g)) + float(np.linalg.norm(s * dgrad))) / lmin
+    chi2 = float(np.sum(wo * res * res))
+    s2 = chi2 / (nomega - nunk)
+    cov = np.linalg.inv(N)
+    sump = np.array([psf[k if index is None else int(index[k])].sum() for k in acc])
+    F = x[:nacc]
+    out['F'][acc] = F
+    out['err'][acc] = np.sqrt(s2 / dg[:nacc])
+    out['flux'][acc] = F * sump
+    out['err_flux'][acc] = out['err'][acc] * np.abs(sump)
+    out['overlap'][acc] = (N[:nacc, :nacc].sum(axis=1) - dg[:nacc]) / dg[:nacc]
+    out['ndisc'][acc] = ndisc[acc]
+    out['nkk'][acc] = dg[:nacc]
+    out['sigma'][acc] = np.sqrt(np.diag(cov)[:nacc])
+    if background:
+        out['b'], out['err_b'] = float(x[nacc]), float(np.sqrt(s2 / dg[nacc]))
+    out['chi2'] = chi2
+    resid = image.copy()
+    for i, k in enumerate(acc):
+        y0, y1, x0, x1, col = wins[k]
+        resid[y0:y1, x0:x1] = resid[y0:y1, x0:x1] - F[i] * col
+    out['resid'] = resid
+    out.update(A=A, w=wo, d=d, x=x, N=N, Nabs=Nabs, dg=dg, res=res, background=background, sparse=True, L=L,
+               ref_err=ref_err)
+    return out
+
+
 def scaled(ref):
     """(Ns, |N|s, y*) of the docstring."""
     s = 1.0 / np.sqrt(ref['dg'])
@@ -164,27 +293,34 @@ def scaled(ref):
 
 def bounds(ref, tol, max_iter):
     """The a-priori bounds of the docstring for a solve from a zero start: dict(y, kappa, nkk_rel, overlap (per accepted
-    star), chi2, terms (the four parts of y))."""
+    star), chi2, terms (the four parts of y)).  Of a solve_sparse() result the `reference` term is not lstsq's but the
+    a-posteriori 'ref_err' derived in its docstring; the three other terms and every other bound are the same
+    expressions on the sparse A."""
     A, wo, d = ref['A'], ref['w'], ref['d']
     nacc = ref['nacc']
+    sparse = bool(ref.get('sparse'))
+    Aabs = abs(A) if sparse else np.abs(A)
     Ns, Nsabs, ys = scaled(ref)
     ev = np.linalg.eigvalsh(Ns)
     lmin, lmax = float(ev[0]), float(ev[-1])
     kappa = lmax / lmin
     mu = float(np.linalg.norm(Nsabs, 2))
     ynorm = float(np.linalg.norm(ys))
-    L = int(np.max(np.count_nonzero(A[:, :nacc], axis=1)))
+    L = ref['L'] if sparse else int(np.max(np.count_nonzero(A[:, :nacc], axis=1)))
     g = (NS + 2 * APRON) ** 2 + L + 40
     conv = kappa * tol * ynorm
     gap = (max_iter + 1) * g * EPS * mu * 2.0 * ynorm / lmin
-    rhs = g * EPS * float(np.linalg.norm((np.abs(A).T @ (wo * np.abs(d))) / np.sqrt(ref['dg']))) / lmin
-    wres = float(np.sqrt(np.sum(wo * ref['res'] ** 2)))
-    lsq = 8 * len(ys) * EPS * (np.sqrt(kappa) * ynorm + kappa * wres / np.sqrt(lmax))
+    rhs = g * EPS * float(np.linalg.norm((Aabs.T @ (wo * np.abs(d))) / np.sqrt(ref['dg']))) / lmin
+    if sparse:
+        lsq = ref['ref_err']
+    else:
+        wres = float(np.sqrt(np.sum(wo * ref['res'] ** 2)))
+        lsq = 8 * len(ys) * EPS * (np.sqrt(kappa) * ynorm + kappa * wres / np.sqrt(lmax))
     by = conv + gap + rhs + lsq
     dg = ref['dg'][:nacc]
     ovl = (ref['N'][:nacc, :nacc].sum(axis=1) - dg) / dg
     b_ovl = 2 * g * EPS * (ref['Nabs'][:nacc, :nacc].sum(axis=1) / dg + 1.0 + np.abs(ovl))
-    S = np.abs(d) + np.abs(A) @ np.abs(ref['x'])
+    S = np.abs(d) + Aabs @ np.abs(ref['x'])
     dR = (L + 20) * EPS * S
     sdr = float(np.sum(wo * dR * dR))
     b_chi2 = lmax * by * by + 2.0 * np.sqrt(ref['chi2'] * sdr) + sdr + (len(d) + 4) * EPS * ref['chi2']
