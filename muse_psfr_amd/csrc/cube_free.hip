@@ -16,7 +16,10 @@
 //                       pos_out, call_out)
 // k_ff_star<false, true>, k_ff_domain<true>, k_ff_reduce<true>, k_ff_ones and the renderer's layered walk are reused as
 // they are: their done word is per layer at a pitch of I_NINT, so the step kernel keeps the call's three done words once
-// (si) and a copy per layer (gate), a dead layer's copies always set.
+// (si) and a copy per layer (gate), a dead layer's copies always set.  The step kernel's loops and the order of its sums
+// are its own (below); what it computes at one place, one row, one head or one shift is the frame's: cg_advance,
+// cg_direct, cg_alpha, cg_end, cg_beta, star_row, solve_head (frame_fit_impl.h), carries, first_place, free_iter_end,
+// move_shift, outer_end and the shared scalar words (frame_free_impl.h).
 //
 // The order of every sum (none depends on a grid):
 //   over the places of ONE layer, and over the chunks of a layer's frame reductions: lane j of a wave takes the places
@@ -37,14 +40,9 @@ constexpr int NPOS = 8;                                       // MPSFR_NCUBEFREE
 constexpr int kStepWaves = kStepThreads / 64;
 constexpr int kMaxLayers = 4096;                              // MPSFR_CUBE_FIT_MAX_LAYERS
 
-// the scalars of a call: doubles, then ints
-enum { D_RHO = 0, D_RHOG, D_REL, D_MAXD, D_RHO_D, D_RHOG_D, D_LO8, D_HI8 = D_LO8 + 2, D_NDOUBLE = D_HI8 + 2 };
-enum {
-    J_DONE = 0,   // the solve under way has ended
-    J_GN,         // ... or the outer loop has: what the kernels of a Gauss-Newton step's iterations look at
-    J_OUTER,      // the outer loop has ended
-    J_ITER, J_ITERSUM, J_STOP, J_ALLDEAD, J_NOUTER, J_NFREE, J_FREENOW, J_POSOK, J_NINT
-};
+// the scalars of a call: the shared ones (frame_free_impl.h), then the cube's own
+enum { D_RHO_D = D_SHARED, D_RHOG_D, D_LO8, D_HI8 = D_LO8 + 2, D_NDOUBLE = D_HI8 + 2 };
+enum { J_ALLDEAD = J_SHARED, J_FREENOW, J_NINT };
 // the words of a layer's gate (pitch I_NINT): copies of the first three, 1 for a dead layer; and whether it is dead
 enum { G_DONE = J_DONE, G_GN = J_GN, G_OUTER = J_OUTER, G_DEAD };
 static_assert(G_DEAD < I_NINT, "a layer's gate has the pitch of section 25's scalars");
@@ -197,13 +195,8 @@ __global__ __launch_bounds__(kStepThreads) void k_cf_step(CubeStep a) {
             for (int l = 0; l < nl; ++l) {
                 const size_t o = (size_t)l * n + k;
                 const bool acc = !dead(l) && a.accept[o] != 0;
-                bool cr = false;
-                if (a.gn && acc) {
-                    const double F = a.x[(size_t)l * nv + k];
-                    const double* b = a.blk + (size_t)B_N * o;
-                    cr = positive_finite(F) && positive_finite(b[B_AA]) && positive_finite(b[B_CC]) &&
-                         F > a.min_snr * sqrt(lw(L_S2, l) / b[B_FF]);
-                }
+                const bool cr = a.gn && acc &&
+                                carries(a.x[(size_t)l * nv + k], a.blk + (size_t)B_N * o, lw(L_S2, l), a.min_snr);
                 a.carry[o] = cr ? 1 : 0;
                 anyacc = anyacc || acc;
                 anycarry = anycarry || cr;
@@ -255,15 +248,8 @@ __global__ __launch_bounds__(kStepThreads) void k_cf_step(CubeStep a) {
 #pragma unroll
             for (int ax = 0; ax < 2; ++ax) {
                 const size_t i = NB + (size_t)ax * n + k;
-                const bool on = fr;
-                const double di = on ? d[ax] : 1.0, ri = on ? rr[ax] : 0.0, gi = on ? gg[ax] : 0.0;
-                const double zi = on ? ri / di : 0.0;
                 a.x[i] = 0.0;                 // delta = 0 at the start of every solve
-                a.diag[i] = di;
-                a.r[i] = ri;
-                a.p[i] = zi;
-                rz += ri * zi;
-                gz += on ? gi * (gi / di) : 0.0;
+                first_place(fr, fr ? d[ax] : 1.0, rr[ax], gg[ax], a.diag, a.r, a.p, i, rz, gz);
             }
             nf += fr ? 1.0 : 0.0;
         }
@@ -306,14 +292,7 @@ __global__ __launch_bounds__(kStepThreads) void k_cf_step(CubeStep a) {
                     gi = on ? g3[i] : 0.0;
                 }
                 if (dd) a.x[at] = 0.0;
-                ri = on ? ri : 0.0;
-                gi = on ? gi : 0.0;
-                const double zi = on ? ri / di : 0.0;
-                a.diag[at] = di;
-                a.r[at] = ri;
-                a.p[at] = zi;
-                lz += ri * zi;
-                lg += on ? gi * (gi / di) : 0.0;
+                first_place(on, di, ri, gi, a.diag, a.r, a.p, at, lz, lg);
             }
             lz = wave_sum(lz), lg = wave_sum(lg);
             if (lane == 0) {
@@ -390,8 +369,7 @@ __global__ __launch_bounds__(kStepThreads) void k_cf_step(CubeStep a) {
         }
         const double pq_d = block_sum<kStepThreads>(sdl, part);
         const double pq = layers_sum(L_PQ) + pq_d;
-        const bool fine = positive_finite(pq);                       // (not so: N is singular along p, the solve ends)
-        const double alpha = fine ? rho / pq : 0.0;
+        const double alpha = cg_alpha(rho, pq);
 #pragma unroll 1
         for (int l = wave; l < nl; l += kStepWaves) {
             if (dead(l)) continue;
@@ -399,13 +377,8 @@ __global__ __launch_bounds__(kStepThreads) void k_cf_step(CubeStep a) {
             const double* q3 = a.q3 + (size_t)l * 3 * n;
             double lz = 0.0;
             for (int i = lane; i < nb; i += 64)
-                if (i == n || a.accept[(size_t)l * n + i]) {
-                    const size_t at = (size_t)l * nv + i;
-                    a.x[at] += alpha * a.p[at];
-                    const double ri = a.r[at] - alpha * (i == n ? qb : q3[i]);
-                    a.r[at] = ri;
-                    lz += ri * (ri / a.diag[at]);
-                }
+                if (i == n || a.accept[(size_t)l * n + i])
+                    lz += cg_advance(alpha, i == n ? qb : q3[i], a.x, a.r, a.p, a.diag, (size_t)l * nv + i);
             lz = wave_sum(lz);
             if (lane == 0) {
                 lw(L_RHO, l) = lz;
@@ -417,48 +390,25 @@ __global__ __launch_bounds__(kStepThreads) void k_cf_step(CubeStep a) {
         for (int k = tid; k < n; k += kStepThreads) {
             if (!a.freem[k]) continue;
 #pragma unroll
-            for (int ax = 0; ax < 2; ++ax) {
-                const size_t at = NB + (size_t)ax * n + k;
-                a.x[at] += alpha * a.p[at];
-                const double ri = a.r[at] - alpha * a.qd[ax * n + k];
-                a.r[at] = ri;
-                rz += ri * (ri / a.diag[at]);
-            }
+            for (int ax = 0; ax < 2; ++ax)
+                rz += cg_advance(alpha, a.qd[ax * n + k], a.x, a.r, a.p, a.diag, NB + (size_t)ax * n + k);
         }
         const double rho_d = block_sum<kStepThreads>(rz, part);
-        const double rho1 = layers_sum(L_RHO) + rho_d;
-        const bool stop = rho1 <= a.tol2 * rhog;
-        const bool end = stop || !fine || !(rho1 < __builtin_inf());
-        const double beta = end ? 0.0 : rho1 / rho;
+        const CgEnd e = cg_end(layers_sum(L_RHO) + rho_d, pq, a.tol2, rhog);
+        const double beta = cg_beta(e, rho);
 #pragma unroll 1
         for (int l = wave; l < nl; l += kStepWaves) {
             if (dead(l)) continue;
             for (int i = lane; i < nb; i += 64)
-                if (i == n || a.accept[(size_t)l * n + i]) {
-                    const size_t at = (size_t)l * nv + i;
-                    a.p[at] = a.r[at] / a.diag[at] + beta * a.p[at];
-                }
+                if (i == n || a.accept[(size_t)l * n + i]) cg_direct(beta, a.r, a.diag, a.p, (size_t)l * nv + i);
         }
         for (int k = tid; k < n; k += kStepThreads) {
             if (!a.freem[k]) continue;
 #pragma unroll
-            for (int ax = 0; ax < 2; ++ax) {
-                const size_t at = NB + (size_t)ax * n + k;
-                a.p[at] = a.r[at] / a.diag[at] + beta * a.p[at];
-            }
+            for (int ax = 0; ax < 2; ++ax) cg_direct(beta, a.r, a.diag, a.p, NB + (size_t)ax * n + k);
         }
-        if (tid == 0) {
-            sd[D_RHO] = rho1;
-            sd[D_REL] = sqrt(rho1 / rhog);
-            si[J_ITER] += 1;
-            si[J_ITERSUM] += 1;
-            if (end) {
-                si[J_DONE] = 1;
-                si[J_GN] = 1;
-            }
-            if (stop) si[J_STOP] = 0;
-        }
-        if (end) set_gates(1, 1, si[J_OUTER]);         // (the outer word is not written in this phase)
+        if (tid == 0) free_iter_end(e, rhog, sd, si);
+        if (e.end) set_gates(1, 1, si[J_OUTER]);       // (the outer word is not written in this phase)
     } else if constexpr (PHASE == CF_APPLY) {
         if (si[J_OUTER]) return;
         double md = 0.0;
@@ -467,39 +417,15 @@ __global__ __launch_bounds__(kStepThreads) void k_cf_step(CubeStep a) {
             int flag = 0;
 #pragma unroll
             for (int ax = 0; ax < 2; ++ax) {
-                double d = a.x[NB + (size_t)ax * n + k];
-                if (!(fabs(d) < __builtin_inf())) d = 0.0;
-                md = fmax(md, fabs(d));
-                if (fabs(d) > a.max_step) {
-                    d = d > 0.0 ? a.max_step : -a.max_step;
-                    flag |= FLAG_CLIPPED;
-                }
-                const double s0 = a.shift0[2 * k + ax];
-                const double lo = fmax(s0 - a.max_move, sd[D_LO8 + ax]), hi = fmin(s0 + a.max_move, sd[D_HI8 + ax]);
-                double s = a.wshift[2 * k + ax] + d;
-                if (s <= lo) {
-                    s = lo;
-                    flag |= FLAG_BOUND;
-                } else if (s >= hi) {
-                    s = hi;
-                    flag |= FLAG_BOUND;
-                }
-                a.wshift[2 * k + ax] = s;
+                double absd;
+                a.wshift[2 * k + ax] = move_shift(a.x[NB + (size_t)ax * n + k], a.wshift[2 * k + ax],
+                                                  a.shift0[2 * k + ax], a.max_step, a.max_move, sd[D_LO8 + ax],
+                                                  sd[D_HI8 + ax], flag, absd);
+                md = fmax(md, absd);
             }
             a.sflag[k] = flag;
         }
-        const double maxd = block_max<kStepThreads>(md, part);
-        const bool over = maxd <= a.pos_tol;
-        if (tid == 0) {
-            si[J_NOUTER] += 1;
-            sd[D_MAXD] = maxd;
-            if (over) {
-                si[J_OUTER] = 1;
-                si[J_GN] = 1;
-                si[J_POSOK] = 1;
-            }
-        }
-        if (over) set_gates(si[J_DONE], 1, 1);          // (J_DONE is not written in this phase)
+        if (outer_end(md, a.pos_tol, sd, si, part)) set_gates(si[J_DONE], 1, 1);   // (J_DONE is not written here)
     } else {
         const bool alldead = si[J_ALLDEAD] != 0;
         const double status = alldead ? 2.0 : (si[J_STOP] == 0 && si[J_POSOK] != 0 ? 0.0 : 1.0);
@@ -516,30 +442,14 @@ __global__ __launch_bounds__(kStepThreads) void k_cf_step(CubeStep a) {
             const double dof = nomega - nacc - back, s2 = dd ? 0.0 : chi2 / dof;
             const double* q3 = a.q3 + (size_t)l * 3 * n;
             for (int k = lane; k < n; k += 64) {
-                const size_t o = (size_t)l * n + k;
-                double* row = a.star_out + (size_t)NROW * o;
-                const bool on = !dd && a.accept[o] != 0;
-                const double F = on ? a.x[(size_t)l * nv + k] : 0.0, nkk = on ? a.diag[(size_t)l * nv + k] : 0.0;
-                const double eF = on ? sqrt(s2 / nkk) : 0.0;
-                row[0] = F;
-                row[1] = eF;
-                row[2] = on ? F * a.sump[o] : 0.0;
-                row[3] = on ? eF * fabs(a.sump[o]) : 0.0;
-                row[4] = on ? (q3[k] - nkk) / nkk : 0.0;
-                row[5] = on ? a.ndisc[o] : 0.0;
-                row[6] = nkk;
-                row[7] = on ? 0.0 : (a.stat[o] == 1 ? 1.0 : 2.0);
+                const size_t o = (size_t)l * n + k, at = (size_t)l * nv + k;
+                star_row(a.star_out + (size_t)NROW * o, !dd && a.accept[o] != 0, a.x[at], a.diag[at], q3[k], s2,
+                         a.sump[o], a.ndisc[o], a.stat[o]);
             }
             if (lane == 0) {
-                const bool b = a.back && !dd;
                 double* h = a.head_out + (size_t)NROW * l;
-                h[0] = b ? a.x[(size_t)l * nv + n] : 0.0;
-                h[1] = b ? sqrt(s2 / lw(L_WSUM, l)) : 0.0;
-                h[2] = dd ? 0.0 : chi2;
-                h[3] = nomega;
-                h[4] = (double)si[J_ITER];
-                h[5] = dd ? 0.0 : lw(L_REL, l);
-                h[6] = nacc;
+                solve_head(h, a.back != 0, dd, a.x[(size_t)l * nv + n], s2, lw(L_WSUM, l), chi2, nomega,
+                           (double)si[J_ITER], lw(L_REL, l), nacc);
                 h[7] = dd ? 2.0 : status;
                 lw(L_CHI, l) = chi2;
                 lw(L_S2, l) = s2;

@@ -12,6 +12,11 @@
 //   k_ff_reduce       sum W (V + c), sum W, sum W (V + c)^2 and |Omega| over chunks of the frame, one partial per chunk
 //   k_ff_step<phase>  one workgroup: the conjugate-gradient step over the unknowns, the stop test and the done word; the
 //                     first residual; the rows of the result
+// What the step kernels of the whole family (k_ff_step; k_fr_step, frame_free.hip; k_cf_step, cube_free.hip) have in
+// common stands here once: block_reduce (block_sum, block_max), the conjugate-gradient step over a flat vector (cg_step)
+// with its per-place updates (cg_advance, cg_direct) and its end (cg_alpha, cg_end, cg_beta), columns 0 to 7 of a star's
+// row (star_row) and columns 0 to 6 of a head (solve_head).  What only the fits with free positions share is in
+// frame_free_impl.h.
 // Every sum has a fixed order (no floating-point atomics), all arithmetic is fp64, and nothing waits for the host: the
 // scalars live in the work buffer, and once the done word is set the queued kernels of the later iterations return.
 //
@@ -46,20 +51,32 @@ constexpr int NROW = 8;                                                     // M
 enum { S_RHO = 0, S_RHO0, S_REL, S_WSUM, S_NDOUBLE };
 enum { I_DONE = 0, I_ITER, I_STATUS, I_NACC, I_NOMEGA, I_NINT };
 
-// the sum of v over the workgroup's T threads in a fixed tree (the wave's ladder, then the waves in order); every
-// thread gets it.  `part`: T / 64 doubles of LDS, free again on return.
-template <int T>
-__device__ __forceinline__ double block_sum(double v, double* part) {
-    v = wave_sum(v);
+// op over the v of the workgroup's T threads in a fixed tree -- the wave's ladder (wave_sum's: v = op(v, the lane 32,
+// 16, ... 1 away)), then the waves in order from wave 0 --; every thread gets it.  `part`: T / 64 doubles of LDS, free
+// again on return.  The tree, and the two barriers, are part of every result of this family: they do not change.
+template <int T, class Op>
+__device__ __forceinline__ double block_reduce(double v, double* part, Op op) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
     const int tid = threadIdx.x;
     __syncthreads();
     if ((tid & 63) == 0) part[tid >> 6] = v;
     __syncthreads();
     double s = part[0];
 #pragma unroll
-    for (int w = 1; w < T / 64; ++w) s += part[w];
+    for (int w = 1; w < T / 64; ++w) s = op(s, part[w]);
     return s;
 }
+template <int T>
+__device__ __forceinline__ double block_sum(double v, double* part) {
+    return block_reduce<T>(v, part, [](double a, double b) { return a + b; });
+}
+template <int T>
+__device__ __forceinline__ double block_max(double v, double* part) {
+    return block_reduce<T>(v, part, [](double a, double b) { return fmax(a, b); });
+}
+
+__device__ __forceinline__ bool positive_finite(double v) { return v > 0.0 && v < __builtin_inf(); }
 
 // is the frame pixel (Y, X) in the disc of the star centred on (cy, cx)?  Each product rounded, then the sum.
 __device__ __forceinline__ bool in_disc(int Y, int X, double cy, double cx, double r2) {
@@ -325,6 +342,97 @@ __device__ __forceinline__ double step_sum(const double* __restrict__ a, int n, 
     return block_sum<kStepThreads>(s, part);
 }
 
+// The pieces below are the step kernels' of all four fits (k_ff_step here, k_fr_step of frame_free.hip, k_cf_step of
+// cube_free.hip).  What fixes the bits of those calls, and so holds for every change here: thread t of the step
+// workgroup takes the places t, t + 1024, ... in order (lane j of a layer's wave in k_cf_step: j, j + 64, ...); the
+// number and the order of the reductions of a phase stay; every expression keeps its shape down to the parentheses --
+// ri * (ri / d) is not (ri * ri) / d, and the build contracts a product and a sum into one rounding wherever they
+// stand next to each other, so a term that is split or re-associated rounds differently.
+
+// One place of a conjugate-gradient step: x += alpha p, r -= alpha q; returns the place's term of rho1 = r . (r / diag)
+__device__ __forceinline__ double cg_advance(double alpha, double qi, double* x, double* r, const double* p,
+                                             const double* diag, size_t at) {
+    x[at] += alpha * p[at];
+    const double ri = r[at] - alpha * qi;
+    r[at] = ri;
+    return ri * (ri / diag[at]);
+}
+// ... and its new direction, p = r / diag + beta p
+__device__ __forceinline__ void cg_direct(double beta, const double* r, const double* diag, double* p, size_t at) {
+    p[at] = r[at] / diag[at] + beta * p[at];
+}
+
+struct CgEnd {
+    double rho1;       // r . (r / diag) after the step
+    bool stop, end;    // the stop test has passed; the solve ends (stop, or N singular along p, or rho1 not finite)
+};
+// How a step ends: from p . q whether it is taken at all (not so: N is singular along p, the solve ends), from rho1 the
+// stop test against tol2 `ref`
+__device__ __forceinline__ double cg_alpha(double rho, double pq) { return positive_finite(pq) ? rho / pq : 0.0; }
+__device__ __forceinline__ CgEnd cg_end(double rho1, double pq, double tol2, double ref) {
+    const bool stop = rho1 <= tol2 * ref;
+    return {rho1, stop, stop || !positive_finite(pq) || !(rho1 < __builtin_inf())};
+}
+__device__ __forceinline__ double cg_beta(const CgEnd& e, double rho) { return e.end ? 0.0 : e.rho1 / rho; }
+
+// One conjugate-gradient step of the step workgroup over the flat vectors x, r, p, q, diag [nu] from q = N p, on the
+// places live(i) says.  With `back` the last place is the constant, whose q is the sum of the partials [nchunk] of
+// k_ff_reduce.  rho = r . z before the step; the stop test is rho1 <= tol2 ref.  Three reductions in this order: the
+// constant's q, p . q, rho1.
+template <class Live>
+__device__ __forceinline__ CgEnd cg_step(int nu, bool back, Live live, double* x, double* r, double* p, double* q,
+                                         const double* diag, const double* partial, int nchunk, double rho, double ref,
+                                         double tol2, double* part) {
+    const int tid = threadIdx.x;
+    if (back) {
+        const double qb = step_sum(partial, nchunk, part);
+        if (tid == 0) q[nu - 1] = qb;
+        __syncthreads();
+    }
+    double s = 0.0;
+    for (int i = tid; i < nu; i += kStepThreads)
+        if (live(i)) s += p[i] * q[i];
+    const double pq = block_sum<kStepThreads>(s, part);
+    const double alpha = cg_alpha(rho, pq);
+    double rz = 0.0;
+    for (int i = tid; i < nu; i += kStepThreads)
+        if (live(i)) rz += cg_advance(alpha, q[i], x, r, p, diag, i);
+    const CgEnd e = cg_end(block_sum<kStepThreads>(rz, part), pq, tol2, ref);
+    const double beta = cg_beta(e, rho);
+    for (int i = tid; i < nu; i += kStepThreads)
+        if (live(i)) cg_direct(beta, r, diag, p, i);
+    return e;
+}
+
+// Columns 0 to 7 of a star's row (MPSFR_NFRAMEFIT; the first eight of the free fits' rows) from its places of the
+// closing solve: x, diag, q = (N 1)_k.  `on`: the star was fitted.  Returns F.
+__device__ __forceinline__ double star_row(double* o, bool on, double x, double diag, double q, double s2, double sump,
+                                           double ndisc, int stat) {
+    const double F = on ? x : 0.0, nkk = on ? diag : 0.0;
+    const double eF = on ? sqrt(s2 / nkk) : 0.0;
+    o[0] = F;
+    o[1] = eF;
+    o[2] = on ? F * sump : 0.0;
+    o[3] = on ? eF * fabs(sump) : 0.0;
+    o[4] = on ? (q - nkk) / nkk : 0.0;
+    o[5] = on ? ndisc : 0.0;
+    o[6] = nkk;
+    o[7] = on ? 0.0 : (stat == 1 ? 1.0 : 2.0);
+    return F;
+}
+// Columns 0 to 6 of the head of a solve.  `none`: nothing was fitted; b: the constant's place of x.
+__device__ __forceinline__ void solve_head(double* h, bool back, bool none, double b, double s2, double wsum,
+                                           double chi2, double nomega, double iter, double rel, double nacc) {
+    const bool on = back && !none;
+    h[0] = on ? b : 0.0;
+    h[1] = on ? sqrt(s2 / wsum) : 0.0;
+    h[2] = none ? 0.0 : chi2;
+    h[3] = nomega;
+    h[4] = iter;
+    h[5] = none ? 0.0 : rel;
+    h[6] = nacc;
+}
+
 enum { STEP_INIT = 0, STEP_ITER = 1, STEP_FINAL = 2 };
 
 // One workgroup over the nu = nstar + 1 unknowns (the constant last; it takes part with `back` only).  x, r, p, q, diag:
@@ -394,38 +502,14 @@ __global__ __launch_bounds__(kStepThreads) void k_ff_step(int nstar, int back, i
         }
     } else if constexpr (PHASE == STEP_ITER) {
         if (si[I_DONE]) return;
-        const double rho = sd[S_RHO], rho0 = sd[S_RHO0];
-        if (back) {
-            const double qb = step_sum(partial, nchunk, part);
-            if (tid == 0) q[nstar] = qb;
-            __syncthreads();
-        }
-        double s = 0.0;
-        for (int i = tid; i < nu; i += kStepThreads)
-            if (live(i)) s += p[i] * q[i];
-        const double pq = block_sum<kStepThreads>(s, part);
-        const bool fine = pq > 0.0 && pq < __builtin_inf();          // (not so: N is singular along p, the step ends)
-        const double alpha = fine ? rho / pq : 0.0;
-        double rz = 0.0;
-        for (int i = tid; i < nu; i += kStepThreads)
-            if (live(i)) {
-                x[i] += alpha * p[i];
-                const double ri = r[i] - alpha * q[i];
-                r[i] = ri;
-                rz += ri * (ri / diag[i]);
-            }
-        const double rho1 = block_sum<kStepThreads>(rz, part);
-        const bool stop = rho1 <= tol2 * rho0;
-        const bool end = stop || !fine || !(rho1 < __builtin_inf());
-        const double beta = end ? 0.0 : rho1 / rho;
-        for (int i = tid; i < nu; i += kStepThreads)
-            if (live(i)) p[i] = r[i] / diag[i] + beta * p[i];
+        const double rho0 = sd[S_RHO0];
+        const CgEnd e = cg_step(nu, back != 0, live, x, r, p, q, diag, partial, nchunk, sd[S_RHO], rho0, tol2, part);
         if (tid == 0) {
-            sd[S_RHO] = rho1;
-            sd[S_REL] = sqrt(rho1 / rho0);
+            sd[S_RHO] = e.rho1;
+            sd[S_REL] = sqrt(e.rho1 / rho0);
             si[I_ITER] += 1;
-            if (end) si[I_DONE] = 1;
-            if (stop) si[I_STATUS] = 0;
+            if (e.end) si[I_DONE] = 1;
+            if (e.stop) si[I_STATUS] = 0;
         }
     } else {
         const int status = si[I_STATUS], nacc = si[I_NACC], nomega = si[I_NOMEGA];
@@ -433,29 +517,12 @@ __global__ __launch_bounds__(kStepThreads) void k_ff_step(int nstar, int back, i
         const double chi2 = step_sum(partial + 2 * (size_t)nchunk, nchunk, part);
         const double dof = (double)nomega - (double)nacc - (back ? 1.0 : 0.0);
         const double s2 = none ? 0.0 : chi2 / dof;
-        for (int k = tid; k < nstar; k += kStepThreads) {
-            double* o = star_out + (size_t)NROW * k;
-            const bool on = !none && accept[k] != 0;
-            const double F = on ? x[k] : 0.0, nkk = on ? diag[k] : 0.0;
-            const double eF = on ? sqrt(s2 / nkk) : 0.0;
-            o[0] = F;
-            o[1] = eF;
-            o[2] = on ? F * sump[k] : 0.0;
-            o[3] = on ? eF * fabs(sump[k]) : 0.0;
-            o[4] = on ? (q[k] - nkk) / nkk : 0.0;
-            o[5] = on ? ndisc[k] : 0.0;
-            o[6] = nkk;
-            o[7] = on ? 0.0 : (stat[k] == 1 ? 1.0 : 2.0);
-        }
+        for (int k = tid; k < nstar; k += kStepThreads)
+            star_row(star_out + (size_t)NROW * k, !none && accept[k] != 0, x[k], diag[k], q[k], s2, sump[k], ndisc[k],
+                     stat[k]);
         if (tid == 0) {
-            const bool b = back && !none;
-            head_out[0] = b ? x[nstar] : 0.0;
-            head_out[1] = b ? sqrt(s2 / sd[S_WSUM]) : 0.0;
-            head_out[2] = none ? 0.0 : chi2;
-            head_out[3] = (double)nomega;
-            head_out[4] = (double)si[I_ITER];
-            head_out[5] = none ? 0.0 : sd[S_REL];
-            head_out[6] = (double)nacc;
+            solve_head(head_out, back != 0, none, x[nstar], s2, sd[S_WSUM], chi2, (double)nomega, (double)si[I_ITER],
+                       sd[S_REL], (double)nacc);
             head_out[7] = (double)status;
         }
     }

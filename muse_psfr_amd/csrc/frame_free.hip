@@ -12,7 +12,9 @@
 //                  FR_ITER (a conjugate-gradient step), FR_APPLY (delta = (a, c) / F, its clips, the new shifts, the
 //                  outer done word), FR_FINAL (the rows)
 // k_ff_reduce, k_ff_ones and the renderer's own walk (first residuals, the residual frame, the overlap) are reused as
-// they are.  Every sum has a fixed order, all arithmetic is fp64, nothing waits for the host.
+// they are.  FR_ITER is cg_step, the rows and the head star_row and solve_head (frame_fit_impl.h); the carry rule, a
+// place of the first residual and the position update are frame_free_impl.h's, which k_cf_step shares.  Every sum has
+// a fixed order, all arithmetic is fp64, nothing waits for the host.
 #include "frame_free_impl.h"
 
 namespace mpsfr {
@@ -20,14 +22,9 @@ namespace {
 
 constexpr int NFREE = 16;                                     // MPSFR_NFRAMEFREE; the head: MPSFR_NFRAMEFREE_HEAD = 12
 
-// the scalars of a call: doubles, then ints
-enum { D_RHO = 0, D_RHOG, D_REL, D_WSUM, D_MAXD, D_NDOUBLE };
-enum {
-    J_DONE = 0,   // the solve under way has ended
-    J_GN,         // ... or the outer loop has: what the kernels of a Gauss-Newton step's iterations look at
-    J_OUTER,      // the outer loop has ended
-    J_ITER, J_ITERSUM, J_STOP, J_NONE, J_NACC, J_NOMEGA, J_NOUTER, J_NFREE, J_POSOK, J_NINT
-};
+// the scalars of a call: the shared ones (frame_free_impl.h), then the frame's own
+enum { D_WSUM = D_SHARED, D_NDOUBLE };
+enum { J_NONE = J_SHARED, J_NACC, J_NOMEGA, J_NINT };
 
 // v, computed here and now: the sums of FR_INIT's reductions one after the other, not all their partials held at once
 __device__ __forceinline__ double settled(double v) {
@@ -101,12 +98,7 @@ __global__ __launch_bounds__(kStepThreads) void k_fr_step(FreeStep a) {
         for (int k = tid; k < n; k += kStepThreads) {
             const bool acc = !none && a.accept[k] != 0;
             const double* b = a.blk + (size_t)B_N * k;
-            bool fr = false;
-            if (movable && acc) {
-                const double F = a.x[k];
-                fr = positive_finite(F) && positive_finite(b[B_AA]) && positive_finite(b[B_CC]) &&
-                     F > a.min_snr * sqrt(s2 / b[B_FF]);
-            }
+            const bool fr = movable && acc && carries(a.x[k], b, s2, a.min_snr);
             a.freem[k] = fr ? 1 : 0;
             if (a.gn) {
                 a.held[k] = acc && !fr ? 1 : 0;
@@ -136,14 +128,7 @@ __global__ __launch_bounds__(kStepThreads) void k_fr_step(FreeStep a) {
                 gi = on ? a.g[i] : 0.0;
             }
             if (none || (i >= n && i < nb)) a.x[i] = 0.0;      // a = c = 0 at the start of every solve
-            ri = on ? ri : 0.0;
-            gi = on ? gi : 0.0;
-            const double zi = on ? ri / d : 0.0;
-            a.diag[i] = d;
-            a.r[i] = ri;
-            a.p[i] = zi;
-            rz += ri * zi;
-            gz += on ? gi * (gi / d) : 0.0;
+            first_place(on, d, ri, gi, a.diag, a.r, a.p, i, rz, gz);
         }
         const double rho = block_sum<kStepThreads>(rz, part);
         const double rhog = block_sum<kStepThreads>(gz, part);
@@ -171,48 +156,14 @@ __global__ __launch_bounds__(kStepThreads) void k_fr_step(FreeStep a) {
         }
     } else if constexpr (PHASE == FR_ITER) {
         if (*a.gate) return;
-        const double rho = sd[D_RHO], rhog = sd[D_RHOG];
+        const double rhog = sd[D_RHOG];
         auto live = [&](int i) {
             if (i == nb) return a.back != 0;
             return i < n ? a.accept[i] != 0 : a.freem[star_of(i)] != 0;
         };
-        const int nu = nb + (a.back ? 1 : 0);
-        if (a.back) {
-            const double qb = step_sum(a.partial, a.nchunk, part);
-            if (tid == 0) a.q[nb] = qb;
-            __syncthreads();
-        }
-        double s = 0.0;
-        for (int i = tid; i < nu; i += kStepThreads)
-            if (live(i)) s += a.p[i] * a.q[i];
-        const double pq = block_sum<kStepThreads>(s, part);
-        const bool fine = positive_finite(pq);                       // (not so: N is singular along p, the solve ends)
-        const double alpha = fine ? rho / pq : 0.0;
-        double rz = 0.0;
-        for (int i = tid; i < nu; i += kStepThreads)
-            if (live(i)) {
-                a.x[i] += alpha * a.p[i];
-                const double ri = a.r[i] - alpha * a.q[i];
-                a.r[i] = ri;
-                rz += ri * (ri / a.diag[i]);
-            }
-        const double rho1 = block_sum<kStepThreads>(rz, part);
-        const bool stop = rho1 <= a.tol2 * rhog;
-        const bool end = stop || !fine || !(rho1 < __builtin_inf());
-        const double beta = end ? 0.0 : rho1 / rho;
-        for (int i = tid; i < nu; i += kStepThreads)
-            if (live(i)) a.p[i] = a.r[i] / a.diag[i] + beta * a.p[i];
-        if (tid == 0) {
-            sd[D_RHO] = rho1;
-            sd[D_REL] = sqrt(rho1 / rhog);
-            si[J_ITER] += 1;
-            si[J_ITERSUM] += 1;
-            if (end) {
-                si[J_DONE] = 1;
-                si[J_GN] = 1;
-            }
-            if (stop) si[J_STOP] = 0;
-        }
+        const CgEnd e = cg_step(nb + (a.back ? 1 : 0), a.back != 0, live, a.x, a.r, a.p, a.q, a.diag, a.partial,
+                                a.nchunk, sd[D_RHO], rhog, a.tol2, part);
+        if (tid == 0) free_iter_end(e, rhog, sd, si);
     } else if constexpr (PHASE == FR_APPLY) {
         if (si[J_OUTER]) return;
         double md = 0.0;
@@ -222,37 +173,15 @@ __global__ __launch_bounds__(kStepThreads) void k_fr_step(FreeStep a) {
             const bool ok = positive_finite(F);
             int flag = 0;
             for (int ax = 0; ax < 2; ++ax) {
-                double d = ok ? a.x[(ax + 1) * n + k] / F : 0.0;
-                if (!(fabs(d) < __builtin_inf())) d = 0.0;
-                md = fmax(md, fabs(d));
-                if (fabs(d) > a.max_step) {
-                    d = d > 0.0 ? a.max_step : -a.max_step;
-                    flag |= FLAG_CLIPPED;
-                }
-                const double s0 = a.shift0[2 * k + ax];
-                const double lo = fmax(s0 - a.max_move, -kPsfMaxShift), hi = fmin(s0 + a.max_move, kPsfMaxShift);
-                double s = a.wshift[2 * k + ax] + d;
-                if (s <= lo) {
-                    s = lo;
-                    flag |= FLAG_BOUND;
-                } else if (s >= hi) {
-                    s = hi;
-                    flag |= FLAG_BOUND;
-                }
-                a.wshift[2 * k + ax] = s;
+                double absd;
+                a.wshift[2 * k + ax] = move_shift(ok ? a.x[(ax + 1) * n + k] / F : 0.0, a.wshift[2 * k + ax],
+                                                  a.shift0[2 * k + ax], a.max_step, a.max_move, -kPsfMaxShift,
+                                                  kPsfMaxShift, flag, absd);
+                md = fmax(md, absd);
             }
             a.sflag[k] = flag;
         }
-        const double maxd = block_max<kStepThreads>(md, part);
-        if (tid == 0) {
-            si[J_NOUTER] += 1;
-            sd[D_MAXD] = maxd;
-            if (maxd <= a.pos_tol) {
-                si[J_OUTER] = 1;
-                si[J_GN] = 1;
-                si[J_POSOK] = 1;
-            }
-        }
+        outer_end(md, a.pos_tol, sd, si, part);
     } else {
         const bool none = si[J_NONE] != 0;
         const int nacc = si[J_NACC], nomega = si[J_NOMEGA];
@@ -265,17 +194,8 @@ __global__ __launch_bounds__(kStepThreads) void k_fr_step(FreeStep a) {
         for (int k = tid; k < n; k += kStepThreads) {
             double* o = a.star_out + (size_t)NFREE * k;
             const bool on = !none && a.accept[k] != 0;
-            const double F = on ? a.x[k] : 0.0, nkk = on ? a.diag[k] : 0.0;
-            const double eF = on ? sqrt(s2 / nkk) : 0.0;
+            const double F = star_row(o, on, a.x[k], a.diag[k], a.q[k], s2, a.sump[k], a.ndisc[k], a.stat[k]);
             const double sy = a.wshift[2 * k], sx = a.wshift[2 * k + 1];
-            o[0] = F;
-            o[1] = eF;
-            o[2] = on ? F * a.sump[k] : 0.0;
-            o[3] = on ? eF * fabs(a.sump[k]) : 0.0;
-            o[4] = on ? (a.q[k] - nkk) / nkk : 0.0;
-            o[5] = on ? a.ndisc[k] : 0.0;
-            o[6] = nkk;
-            o[7] = on ? 0.0 : (a.stat[k] == 1 ? 1.0 : 2.0);
             o[8] = sy;
             o[9] = sx;
             double ey = 0.0, ex = 0.0;
@@ -298,15 +218,9 @@ __global__ __launch_bounds__(kStepThreads) void k_fr_step(FreeStep a) {
             a.shift_out[2 * k + 1] = sx;
         }
         if (tid == 0) {
-            const bool b = a.back && !none;
             double* h = a.head_out;
-            h[0] = b ? a.x[nb] : 0.0;
-            h[1] = b ? sqrt(s2 / sd[D_WSUM]) : 0.0;
-            h[2] = none ? 0.0 : chi2;
-            h[3] = (double)nomega;
-            h[4] = (double)si[J_ITER];
-            h[5] = none ? 0.0 : sd[D_REL];
-            h[6] = (double)nacc;
+            solve_head(h, a.back != 0, none, a.x[nb], s2, sd[D_WSUM], chi2, (double)nomega, (double)si[J_ITER],
+                       sd[D_REL], (double)nacc);
             h[7] = none ? 2.0 : (si[J_STOP] == 0 && si[J_POSOK] != 0 ? 0.0 : 1.0);
             h[8] = (double)si[J_NOUTER];
             h[9] = sd[D_MAXD];

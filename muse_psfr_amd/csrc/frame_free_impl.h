@@ -11,6 +11,9 @@
 // [layers][nstar] says which of them a layer sums, and the two derivative scales of a star that its layer carries are
 // a = F0[l][k] delta[k], c = F0[l][k] delta[n + k], one rounded product each, before three_terms.  The arithmetic of a
 // layer, and the order of every sum, is that of the frame: the same code.
+// And what the two step kernels k_fr_step and k_cf_step share beyond frame_fit_impl.h's pieces: the scalar words of a
+// call, the carry rule (carries), a place of the first residual (first_place), the end of an inner step (free_iter_end),
+// the move of a shift along one axis (move_shift) and the end of an outer step (outer_end).
 #pragma once
 #include "frame_fit_impl.h"
 
@@ -31,21 +34,91 @@ constexpr int FLAG_HELD = 1, FLAG_BOUND = 2, FLAG_CLIPPED = 4;
 // the places of a star's block of N: the diagonal (the preconditioner) first
 enum { B_FF = 0, B_AA, B_CC, B_FA, B_FC, B_AC, B_N };
 
-template <int T>
-__device__ __forceinline__ double block_max(double v, double* part) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    const int tid = threadIdx.x;
-    __syncthreads();
-    if ((tid & 63) == 0) part[tid >> 6] = v;
-    __syncthreads();
-    double s = part[0];
-#pragma unroll
-    for (int w = 1; w < T / 64; ++w) s = fmax(s, part[w]);
-    return s;
+// The scalars of a call that mean the same in both free fits, doubles and ints; each fit appends its own
+enum { D_RHO = 0, D_RHOG, D_REL, D_MAXD, D_SHARED };
+enum {
+    J_DONE = 0,   // the solve under way has ended
+    J_GN,         // ... or the outer loop has: what the kernels of a Gauss-Newton step's iterations look at
+    J_OUTER,      // the outer loop has ended
+    J_ITER, J_ITERSUM, J_STOP, J_NOUTER, J_NFREE, J_POSOK, J_SHARED
+};
+
+// The pieces of the step kernels k_fr_step and k_cf_step that are one text (the invariants: frame_fit_impl.h, above
+// cg_advance).
+
+// The carry rule: the positions of a star count in a solve when its flux stands min_snr conditional errors above zero
+// and its block b of N has a usable diagonal
+__device__ __forceinline__ bool carries(double F, const double* b, double s2, double min_snr) {
+    return positive_finite(F) && positive_finite(b[B_AA]) && positive_finite(b[B_CC]) &&
+           F > min_snr * sqrt(s2 / b[B_FF]);
 }
 
-__device__ __forceinline__ bool positive_finite(double v) { return v > 0.0 && v < __builtin_inf(); }
+// One place of the first residual of a solve: d its place of the preconditioner, ri of the residual, gi of the data's
+// projection, all as if 0 unless `on`.  Writes diag, r and p = r / d at `at`; adds to rz (rho) and gz (the stop
+// reference rhog).
+__device__ __forceinline__ void first_place(bool on, double d, double ri, double gi, double* diag, double* r, double* p,
+                                            size_t at, double& rz, double& gz) {
+    ri = on ? ri : 0.0;
+    gi = on ? gi : 0.0;
+    const double zi = on ? ri / d : 0.0;
+    diag[at] = d;
+    r[at] = ri;
+    p[at] = zi;
+    rz += ri * zi;
+    gz += on ? gi * (gi / d) : 0.0;
+}
+
+// The end of a conjugate-gradient step of a free fit, by thread 0: the scalars and the done words of the call
+__device__ __forceinline__ void free_iter_end(const CgEnd& e, double rhog, double* sd, int32_t* si) {
+    sd[D_RHO] = e.rho1;
+    sd[D_REL] = sqrt(e.rho1 / rhog);
+    si[J_ITER] += 1;
+    si[J_ITERSUM] += 1;
+    if (e.end) {
+        si[J_DONE] = 1;
+        si[J_GN] = 1;
+    }
+    if (e.stop) si[J_STOP] = 0;
+}
+
+// The move of one star's shift s along one axis by the step d: a step that is not finite is none, |d| is clipped to
+// max_step (FLAG_CLIPPED), the new shift to within max_move of the start s0 and to [lo8, hi8], the +-8 px domain
+// (FLAG_BOUND).  Returns the new shift; absd: |d| before the clips.
+__device__ __forceinline__ double move_shift(double d, double s, double s0, double max_step, double max_move, double lo8,
+                                             double hi8, int& flag, double& absd) {
+    if (!(fabs(d) < __builtin_inf())) d = 0.0;
+    absd = fabs(d);
+    if (fabs(d) > max_step) {
+        d = d > 0.0 ? max_step : -max_step;
+        flag |= FLAG_CLIPPED;
+    }
+    const double lo = fmax(s0 - max_move, lo8), hi = fmin(s0 + max_move, hi8);
+    s += d;
+    if (s <= lo) {
+        s = lo;
+        flag |= FLAG_BOUND;
+    } else if (s >= hi) {
+        s = hi;
+        flag |= FLAG_BOUND;
+    }
+    return s;
+}
+// The end of an outer step: the largest |d| of the workgroup (md: the thread's own) against pos_tol.  Returns whether
+// the outer loop has ended; thread 0 writes the scalars.
+__device__ __forceinline__ bool outer_end(double md, double pos_tol, double* sd, int32_t* si, double* part) {
+    const double maxd = block_max<kStepThreads>(md, part);
+    const bool over = maxd <= pos_tol;
+    if (threadIdx.x == 0) {
+        si[J_NOUTER] += 1;
+        sd[D_MAXD] = maxd;
+        if (over) {
+            si[J_OUTER] = 1;
+            si[J_GN] = 1;
+            si[J_POSOK] = 1;
+        }
+    }
+    return over;
+}
 
 // What the layered walk reads beside the frame's arguments: vec is [layers][nstar + 1] (the fluxes' places of the joint
 // vector), freem [layers][nstar] marks the stars a layer carries, delta [2 nstar] the shifts' places, f0 [layers][nstar]

@@ -356,6 +356,10 @@ size_t group_workspace_bytes(int ny, int nx, int nstar, int max_groups);
 void launch_group_stars(hipStream_t s, int ny, int nx, int nstar, const double* d_pos, int stride, double crit,
                         int max_groups, int32_t* d_label_out, int32_t* d_group_out, int32_t* d_origin_out,
                         double* d_shift_out, int32_t* d_count_out, void* d_ws);
+// The four crowded-field fits below are one family.  frame_fit_impl.h holds the flux-only solve in its frame and layer
+// forms and what every step kernel shares (the block reduction, the conjugate-gradient step, a star's row, a head);
+// frame_free_impl.h the three-column walk and projection and what the two fits with free positions share (the scalar
+// words, the carry rule, the first residual's places, the position update).
 // Crowded-field photometry (frame_fit.hip; mpsfr_fit_frame_psf, include/mpsfr.h): the fluxes of all accepted stars and,
 // with `background`, one constant by preconditioned conjugate gradients on the frame d_image / d_var (or nullptr), at
 // most max_iter steps queued at once, into d_star_out [nstar][8], d_head_out [8] and d_resid_out [ny][nx] (or nullptr).
