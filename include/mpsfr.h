@@ -582,8 +582,8 @@ int mpsfr_fit_spectra_psf(mpsfr_ctx* ctx, int nstar, int nl, const double* cubes
  *            r_k about the centre (analytic circle-square overlap); a circle reaching beyond the stamp counts what is on
  *            the stamp;
  *   SQE_k    the same for the axis-aligned box of side s_k centred on the centre (overlap length in p times in q);
- *   R_k      a radius with |EE(R_k) - f_k| <= 1e-12, found on the exact EE(r) between 0 and the distance to the farthest
- *            pixel corner (unique where the stamp is non-negative).
+ *   R_k      a radius with |EE(R_k) - f_k| <= 1e-12 where the status is 0, found on the exact EE(r) between 0 and the
+ *            distance to the farthest pixel corner (unique where the stamp is non-negative).
  * Arithmetic is fp64 in both precision modes: the call measures the stamp it is given.  A stamp's row depends on that
  * stamp and the parameters only (bit for bit), not on the batch.
  * stamps: [nstamp][dimpsf][dimpsf] float64; centers: [nstamp][2] or NULL; radii_px / boxes_px / fractions: nrad / nbox /
@@ -591,16 +591,20 @@ int mpsfr_fit_spectra_psf(mpsfr_ctx* ctx, int nstar, int nl, const double* cubes
  * out: [nstamp][MPSFR_NMET_HEAD + nrad + nbox + nfrac]:
  *   0 flux  1 peak  2 peak_p  3 peak_q  4 cp  5 cq  6 status  7 zero (reserved), then the nrad EE values, the nbox
  *   ensquared energies and the nfrac radii (pixels).
- * status: 0; 1: an EE radius did not reach 1e-12 (possible on a stamp with negative pixels: the value is the last
- * iterate); 2: the stamp has a non-finite pixel or flux <= 0 (an all-zero stamp included), or the centre is not finite
- * or farther than 1e4 pixels from the origin -- every energy field is then NaN (the centroid too); the other stamps of
- * the call are not affected.
+ * status: 0; 1: an EE radius did not reach 1e-12 (the value is the last iterate, finite and inside the search interval):
+ * the fp64 sums of EE(r) cancel too much for the iteration to settle, on a stamp of mixed signs once sum |I| / flux
+ * reaches ~1e4 (seen at 1e4, not at 1e2; not seen on a non-negative stamp);
+ * 2: the stamp has a non-finite pixel or flux <= 0 (an all-zero stamp included), or the centre is not finite, or |cp|
+ * or |cq| exceeds MPSFR_METRIC_CENTER_MAX pixels (the overlap area of a pixel is good to ~eps r^2, and a radius is
+ * searched up to the centre's distance: farther out the 1e-12 of R_k could not be kept) -- every energy field is then
+ * NaN (the centroid too); the other stamps of the call are not affected.
  * on_device as mpsfr_fit_stamps_elliptical: with 1, stamps, centers and out are device pointers and the call is queued
  * on the context stream (e.g. behind a device-output reconstruct).  Refused with MPSFR_E_INVALID before anything is
  * queued (out is not touched): a count outside 0..16 or all three zero, a radius or box side that is not finite and > 0
  * or exceeds 2 dimpsf pixels, a fraction outside (0, 1), nstamp < 1.  Timed under the fit's profiling id. */
 #define MPSFR_MAX_METRIC_RADII 16      /* also the cap on boxes and on fractions */
 #define MPSFR_NMET_HEAD 8
+#define MPSFR_METRIC_CENTER_MAX 100.0  /* |cp|, |cq| of a centre, pixels */
 int mpsfr_stamp_metrics(mpsfr_ctx* ctx, int nstamp, const double* stamps, const double* centers, int nrad,
                         const double* radii_px, int nbox, const double* boxes_px, int nfrac, const double* fractions,
                         double* out, int on_device);

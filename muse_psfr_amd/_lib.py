@@ -2167,16 +2167,20 @@ def metric_parameters(radii_px, boxes_px, fractions, dimpsf=40):
     return rad, box, frac
 
 
+METRIC_CENTER_MAX = 100.0       # kCenterMax of metrics.hip: beyond it the kernel gives status 2
+
+
 def metric_centers(centers, n):
-    """(n, 2) centres (p, q) in pixels as contiguous float64; ValueError unless finite and of that shape."""
+    """(n, 2) centres (p, q) in pixels as contiguous float64; ValueError unless finite, within METRIC_CENTER_MAX and of
+    that shape."""
     try:
         ce = np.asarray(centers, dtype=np.float64)
     except (TypeError, ValueError):
         raise ValueError('centers must be an (n, 2) array of (p, q) in pixels') from None
     if ce.shape != (n, 2):
         raise ValueError('centers must have the shape (%d, 2): one (p, q) per stamp' % n)
-    if not np.all(np.isfinite(ce)) or np.any(np.abs(ce) > 1.0e4):
-        raise ValueError('centers must be finite (and within 1e4 pixels)')
+    if not np.all(np.isfinite(ce)) or np.any(np.abs(ce) > METRIC_CENTER_MAX):
+        raise ValueError('centers must be finite, with |p| and |q| at most %g pixels' % METRIC_CENTER_MAX)
     return np.ascontiguousarray(ce)
 
 

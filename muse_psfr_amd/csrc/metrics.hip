@@ -25,10 +25,16 @@ namespace {
 
 constexpr int NPXL = NS * NS / 64;           // pixels per lane
 constexpr int MQ = 256;                      // queue of cut pixels (the geometry allows ~170)
-constexpr double kCenterMax = 1.0e4;         // |cp|, |cq| bound of a centre (pixels); beyond it: status 2
+constexpr double kCenterMax = 100.0;         // |cp|, |cq| bound of a centre (pixels); beyond it: status 2.  The overlap
+                                             // area of a pixel is good to ~eps r^2 (1e-16 r^2 off the axes) and an EE
+                                             // radius is searched up to the centre's distance: within this bound the
+                                             // error of EE(r) stays below 1e-13 and the promise on R_k holds with a
+                                             // factor 4 to spare
 constexpr double kRootGoal = 2.0e-14;        // |EE(r) - f| at which the Newton iteration stops (Newton converges
                                              // quadratically: the step that gets below 1e-12 usually lands here)
-constexpr double kRootTol = 5.0e-13;         // ... and above which the radius is flagged (the ABI promises 1e-12)
+constexpr double kRootTol = 5.0e-13;         // ... and above which the radius is flagged (the ABI promises 1e-12):
+                                             // where this fp64 EE(r) is too coarse to settle -- the cancelling sums
+                                             // of a stamp of mixed signs from sum |I| / flux ~1e4 on
 constexpr int kRootMaxIt = 100;
 
 struct MetricPar {
