@@ -64,8 +64,26 @@ __device__ __forceinline__ void mix_args(const double*& w, int& ntab, const doub
     ntab = ntab_;
 }
 
+// Sum over the layers of w[l] * tb[l] at pixel o, the mixing of a profile call.  Only the layers that carry weight in
+// this row are taken, and the first two of them go into the legacy two-term expression: a two-layer profile gives the
+// legacy bits, and a row's sum does not depend on layers that only other rows of the call use (the host drops a layer
+// when no row uses it, so a row alone and the same row in a batch may see different tables around its own).  Skipping
+// a later term of weight 0 changes no bit by itself (s + 0 * t = s); choosing the first two does.
+__device__ __forceinline__ double ao_mix_sum(const double* __restrict__ tb, int o, const double* __restrict__ w,
+                                             int ntab) {
+    int a = 0;
+    while (a < ntab - 1 && w[a] == 0.0) ++a;        // (a row's weights sum to 1: one of them is not 0)
+    int b = a + 1;
+    while (b < ntab && w[b] == 0.0) ++b;
+    if (b >= ntab) return w[a] * tb[a * NAO * NAO + o];
+    double s = w[a] * tb[a * NAO * NAO + o] + w[b] * tb[b * NAO * NAO + o];
+    for (int l = b + 1; l < ntab; ++l)
+        if (w[l] != 0.0) s += w[l] * tb[l * NAO * NAO + o];
+    return s;
+}
+
 // The same for a profile call: the row's weights w[ntab] mix the layer tables tb[0..ntab) and the noise table
-// tb[ntab].  The first two terms are the legacy expression, so a two-layer profile gives the legacy bits.
+// tb[ntab] (ao_mix_sum).
 template <int NEWTON>
 __device__ __forceinline__ double psd_with_ao_mix(double fit, int su, int sv, const TaskPar& p,
                                                   const double* __restrict__ tb, const double* __restrict__ w,
@@ -75,9 +93,7 @@ __device__ __forceinline__ double psd_with_ao_mix(double fit, int su, int sv, co
         const double g2 = (double)(su * su + sv * sv) * (1.0 / 256.0);
         const double vk = 0.0229 * p.r0m53 * pow_m11_6<NEWTON>(g2 + p.inv_l0sq);   // :569-571
         const int o = ia * NAO + ib;
-        double s = w[0] * tb[o] + w[1] * tb[NAO * NAO + o];
-        for (int l = 2; l < ntab; ++l) s += w[l] * tb[l * NAO * NAO + o];
-        const double ao = vk * s + tb[ntab * NAO * NAO + o];
+        const double ao = vk * ao_mix_sum(tb, o, w, ntab) + tb[ntab * NAO * NAO + o];
         fit = fmax(fit, ao);                                        // :149
     }
     return fit;

@@ -425,10 +425,8 @@ __global__ void __launch_bounds__(256) k_patch_gen(int ndir, const TaskPar* __re
         w += (size_t)task * ntab;
         for (int d = 0; d < ndir; ++d) {
             const double* tb = aotab + ((size_t)(p.geom * ndir + d) * (ntab + 1)) * (NAO * NAO);
-            // (the first two terms are the legacy expression: a two-layer profile gives the legacy bits)
-            double sw = w[0] * tb[o] + w[1] * tb[NAO * NAO + o];
-            for (int l = 2; l < ntab; ++l) sw += w[l] * tb[l * NAO * NAO + o];
-            const double ao = vk * sw + tb[ntab * NAO * NAO + o];
+            // (the first two terms taken are the legacy expression: a two-layer profile gives the legacy bits)
+            const double ao = vk * ao_mix_sum(tb, o, w, ntab) + tb[ntab * NAO * NAO + o];
             P[((size_t)task * ndir + d) * (NAO * NAO) + pix] = fmax(fit, ao) - fit;          // :149
         }
         return;

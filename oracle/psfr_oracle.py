@@ -83,7 +83,8 @@ def _ao_freqs():
     return f, f * np.cos(arg), f * np.sin(arg)
 
 
-def ao_tables(h, three_lgs_mode, npsflin, exact_masks=False, masks=None):
+def ao_tables(h, three_lgs_mode, npsflin, exact_masks=False, masks=None, wind_speed=None, wind_dir=None,
+              directions=None):
     """Row-independent part of dsp4muse (psfrec.py:531-613, :218-364, :367-528).
 
     Returns (T, noise): T[layer, dir, 80, 80] = |proj_layer|**2 and noise[dir, 80, 80] =
@@ -101,12 +102,22 @@ def ao_tables(h, three_lgs_mode, npsflin, exact_masks=False, masks=None):
     reference's [i_fx][j_fy] indexing) imposes a captured outcome, e.g. the one of the NumPy that
     generated tests/golden (g1_ao_zone.npz).  The choice moves (fwhm, beta) by up to 3e-3
     (measured, DESIGN.md "cut-off masks"), far above the 1e-4 parity tolerance, hence the knob.
+
+    A Cn2 profile: dsp4muse itself takes any number of layers with a wind speed `vent` and a wind
+    direction `arg_v` each, and any evaluation directions (psfrec.py:531-547); only its caller
+    simul_psd_wfm pins two layers, one speed and two directions (psfrec.py:61, :66, :154-158).
+    ``wind_speed`` [m/s] and ``wind_dir`` [rad] give one value per layer of ``h`` (a scalar applies to
+    every layer); ``directions`` is a (2, ndir) array in arcsec that replaces
+    ``eval_directions(npsflin)``.  Left at None, each is what simul_psd_wfm passes, bit for bit.
     """
     h = np.array(h)
-    vent = wind_speed_for(h)
+    vent = wind_speed_for(h) if wind_speed is None else \
+        np.broadcast_to(np.asarray(wind_speed, dtype=float), h.shape)
+    wdir = WIND_DIR if wind_dir is None else np.broadcast_to(np.asarray(wind_dir, dtype=float), h.shape)
     f, f_x, f_y = _ao_freqs()
     poslgs = lgs_positions(three_lgs_mode) / 60          # arcmin, psfrec.py:536
-    dirperf = eval_directions(npsflin) / 60
+    dirperf = (eval_directions(npsflin) if directions is None else
+               np.asarray(directions, dtype=float).reshape(2, -1)) / 60
     ngs = poslgs.shape[1]
     pitch = DPUP / NACT
     fc = 1 / (2 * pitch)
@@ -147,7 +158,7 @@ def ao_tables(h, three_lgs_mode, npsflin, exact_masks=False, masks=None):
 
     # --- residual, psfrec.py:400-523 with tempo=True
     wfs = shack(True)
-    wind = np.stack([vent * np.cos(WIND_DIR), vent * np.sin(WIND_DIR)])
+    wind = np.stack([vent * np.cos(wdir), vent * np.sin(wdir)])
     ti = 1 / FSAMP
     td = DELAY_MS * 1e-3
     deltaT = ti + td
@@ -185,11 +196,14 @@ def numpy_cutoff_masks():
     return rec, res
 
 
-def ao_zone_psd(Cn2, h, L0, r0, three_lgs_mode, npsflin, tables=None):
-    """dsp4muse, psfrec.py:531-613: (ndir, 80, 80) residual PSD of the corrected zone."""
+def ao_zone_psd(Cn2, h, L0, r0, three_lgs_mode, npsflin, tables=None, wind_speed=None, wind_dir=None,
+                directions=None):
+    """dsp4muse, psfrec.py:531-613: (ndir, 80, 80) residual PSD of the corrected zone.  Any number of
+    layers; wind_speed / wind_dir / directions as in ao_tables (unused when `tables` is given)."""
     Cn2 = np.atleast_1d(np.asarray(Cn2, dtype=float))
     f, _, _ = _ao_freqs()
-    T, noise = tables if tables is not None else ao_tables(h, three_lgs_mode, npsflin)
+    T, noise = tables if tables is not None else ao_tables(
+        h, three_lgs_mode, npsflin, wind_speed=wind_speed, wind_dir=wind_dir, directions=directions)
     with np.errstate(all='ignore'):
         cphi = (0.0229 * (Cn2[:, None, None] ** (-3 / 5) * r0) ** (-5 / 3) *
                 (f ** 2 + (1 / L0) ** 2) ** (-11 / 6))            # psfrec.py:569-571
@@ -212,13 +226,15 @@ def fitting_psd(dim, L, r0, L0, fc):
     return out
 
 
-def residual_psd(Cn2, h, seeing, L0, npsflin=1, dim=1280, three_lgs_mode=False, tables=None):
-    """simul_psd_wfm, psfrec.py:36-151: (ndir, dim, dim) PSD [nm^2 m^2], DC at [dim/2, dim/2]."""
+def residual_psd(Cn2, h, seeing, L0, npsflin=1, dim=1280, three_lgs_mode=False, tables=None, wind_speed=None,
+                 wind_dir=None, directions=None):
+    """simul_psd_wfm, psfrec.py:36-151: (ndir, dim, dim) PSD [nm^2 m^2], DC at [dim/2, dim/2].  Any
+    number of layers; wind_speed / wind_dir / directions as in ao_tables."""
     Cn2 = np.array(Cn2, dtype=float)
     Cn2 /= Cn2.sum()
     r0 = seeing_to_r0(seeing, 0.5, 0.0)
     fc = 1 / (2 * DPUP / NACT)
-    dsp = ao_zone_psd(Cn2, h, L0, r0, three_lgs_mode, npsflin, tables)
+    dsp = ao_zone_psd(Cn2, h, L0, r0, three_lgs_mode, npsflin, tables, wind_speed, wind_dir, directions)
     dspa = fftshift(fitting_psd(dim, 2 * DPUP, r0, L0, fc))
     dspf = np.resize(dspa, (dsp.shape[0], dim, dim))
     half = DIM_AO // 2
