@@ -12,8 +12,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libmpsfr.so')
 SOURCES = ['stage_a.hip', 'stage_a2.hip', 'per_lambda.hip', 'otf_mfma.hip', 'otf_mfma2.hip', 'stamps.hip', 'psd_to_psf.hip', 'fit_ell.hip', 'fit_obs.hip', 'fit_psf.hip', 'fit_spec.hip', 'fit_group.hip', 'fit_group_k4.hip', 'fit_group_f64.hip', 'band.hip', 'metrics.hip', 'render.hip', 'find.hip', 'background.hip', 'group.hip', 'frame_fit.hip', 'cube_fit.hip', 'frame_free.hip', 'cube_free.hip',
-           'mpsfr_api.cpp']
-HEADERS = ['kernels.h', 'fft_lds.h', 'fft_r16.h', 'device_common.h', 'mf_common.h', 'coeff_l0_table.h', 'psd_model.h', 'dpp_groups.h', 'conv_frames.h', 'fit_common.h', 'fit_psf_common.h', 'fit_group_impl.h', 'frame_common.h', 'frame_fit_impl.h', 'frame_free_impl.h',
+           'mpsfr_api.cpp', 'stamp_calls.cpp']
+HEADERS = ['kernels.h', 'fft_lds.h', 'fft_r16.h', 'device_common.h', 'mf_common.h', 'coeff_l0_table.h', 'psd_model.h', 'dpp_groups.h', 'conv_frames.h', 'fit_common.h', 'fit_psf_common.h', 'fit_group_impl.h', 'frame_common.h', 'frame_fit_impl.h', 'frame_free_impl.h', 'host_ctx.h', 'stage_layout.h',
            os.path.join('..', '..', 'include', 'mpsfr.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-result',
          '-fno-slp-vectorize']

@@ -1,7 +1,5 @@
-// Host side of libmpsfr: context, workspaces, the chunked pipeline and the C ABI of
-// include/mpsfr.h.  Reference citations are to /root/reference/muse_psfr/psfrec.py.
-#include "../../include/mpsfr.h"
-
+// Host side of libmpsfr: context, workspaces, the chunked pipeline and its part of the C ABI of
+// include/mpsfr.h (the stamp, frame and cube calls are in stamp_calls.cpp).  Reference citations are to /root/reference/muse_psfr/psfrec.py.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,350 +13,12 @@
 #include <vector>
 
 #include "coeff_l0_table.h"
-#include "kernels.h"
+#include "host_ctx.h"
 
 using namespace mpsfr;
+using namespace mpsfr::host;
 
-namespace {
-
-thread_local std::string g_err;
-
-// log2 of the smallest OTF element (relative to OTF[0][0] = 1) that still has a normal fp16 high half
-// (mf_common.h: kShift = 15), with a margin for the fp32 rounding of the bound
-constexpr float kMfFloorLog2 = -29.01f;
-
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define HIPCHK(call)                                                                      \
-    do {                                                                                  \
-        hipError_t e_ = (call);                                                           \
-        if (e_ != hipSuccess)                                                             \
-            return fail(MPSFR_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
-                        __FILE__, __LINE__);                                              \
-    } while (0)
-
-const char* kKernelNames[K_COUNT] = {
-    "ao_tables", "tel_otf", "psd_rowfft", "colfft_dphi", "gtable",
-    "moffat_kernels", "otf_rowfft", "colpass", "conv", "fit", "stamp_sum", "vkeep", "otf_mfma", "mf_prep",
-    "patch", "dphi_series"};
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-};
-
-struct Pending {
-    int id;
-    hipEvent_t a, b;
-};
-
-}  // namespace
-
-struct mpsfr_ctx {
-    int device = 0, N = 0, dimpsf = 0, prec = 0, ncu = 256;
-    // CUs the two persistent grids leave free (K_OTF_MFMA2 / K_DPHI_SERIES launch ncu - R workgroups, no CU
-    // masks): the other lane's latency-bound kernels find room beside them (VERDICT r5 #1a)
-    // -1 (default): ncu / 8 while the context's other lane has work in flight, 0 for a call that runs alone
-    int reserve_mf = -1, reserve_a = -1;
-    // the tip-tilt kernel spectra ride in the second launch of the patch (series form of stage A)
-    bool head_fusion = true;
-    // stage A (series form) skips what lies outside the support of the telescope OTF
-    bool support_skip = true;
-    double pixscale = 0.2;
-    bool f64 = false;
-    hipStream_t stream = nullptr;
-    // options
-    int chunk_tasks = 0;   // 0 = automatic
-    bool fast_exp = true;    // mixed mode: exp(x) = v_exp_f32(x log2 e)
-    bool profile = false;
-    int prof_only = -1;          // >= 0: time only this kernel id
-    int prof_every = 1;          // time every n-th launch of a slot (a timed launch stops its queue twice)
-    unsigned prof_count[64] = {};
-    bool fft_conv = true;   // mixed mode: convolutions through 64-point FFTs
-    int prune_fixed = 0;         // experiments: transform exactly this many lines (wrong results)
-    double prune_eps = 1.0e-9;   // mixed mode: line pruning of the per-wavelength stage (0 = off)
-    double prune_eps_f64 = 1.0e-13;  // f64 mode: the same, far below what its 1e-11 stamps resolve
-    bool otf_mfma = true;        // mixed mode: per-wavelength stage on the matrix cores (otf_mfma.hip)
-    bool mf_floor = true;        // matrix-core stage: skip blocks below the fp16 representation floor
-    int mf_kernel = 2;           // 2: thin-wave kernel with precision tiers (otf_mfma2.hip, one direction); 1: otf_mfma.hip
-    int mf_permax = 6;           // wavelengths per workgroup of the thin-wave kernel (6: 12 waves, 7: 14 waves)
-    double mf_mid_log2 = -18.01; // blocks below 2^this need no low half of the OTF (see otf_mfma2.hip)
-    double mf_floor_log2 = kMfFloorLog2;   // blocks below 2^this are dropped
-    double tier_eps = 4.0e-6;    // budget of the two precision tiers, of the PSF peak (0: no tiers; inf: no budget)
-    bool mf_clock = false;       // experiments: phase time stamps of the matrix-core kernel
-    int stage_a = 1;             // stage A: 1 = automatic (the series + patch form of stage_a2.hip from 512^2 on, and at
-                                 // 256^2 with several directions; the full-size transforms otherwise: one direction at
-                                 // 256^2 19.2 against 18.3 M PSFs/s, nine directions 7.9 against 8.8), 0 = full-size
-                                 // transforms, 2 = series + patch form on every grid
-    DevBuf mfclk;
-    // constant tables
-    DevBuf tw64, tel, rows, tlmax, tl2, tlb, scoef, stwk, ssup;
-    // per-call tables
-    DevBuf aotab, samp_p, samp_a, G, kmuse, xtab, etab, gtab;
-    // Pipeline lanes: each lane owns a HIP stream and a set of chunk workspaces.  Consecutive
-    // chunks -- of one call or of consecutive asynchronous calls -- go to successive lanes, so one
-    // chunk's low-occupancy tail (convolutions, fit) overlaps the next chunk's transforms.
-    // `stream` is only the join stream: it waits for the lanes at the end of every call.
-    struct Lane {
-        hipStream_t stream = nullptr;
-        hipEvent_t done = nullptr;       // after the lane's last chunk of the most recent call (calls that join)
-        hipEvent_t done_ev = nullptr;    // the event that marks the end of the lane's most recent call: `done`, or
-                                         // the slot event of a call that queued a single marker (see "lean" below)
-        bool busy = false;               // the lane has run a call
-        bool marked = false;             // `done_ev` marks the end of the lane's most recent call (else: no marker was
-                                         // queued for it -- lane_end() records one when somebody needs it)
-        int ncu = 0;                     // CUs the lane's stream may use (0: all of them)
-        DevBuf C, s00, D0t, Tq, pre, fin, dmin, dblk, vkeep, dminb, order, mown, muni, msched, mpart;
-        DevBuf pP, pT, psp, dlin;        // series form of stage A: patch, its row transforms, its sum; line minima
-        DevBuf thrf;                     // [tasks] floor of the kernel for several directions (K_PEAK_FLOOR)
-        DevBuf band;                     // [tasks][nband][40][40] band stamps of a band call (K_BAND_REDUCE)
-        // What D0t holds outside the part the series form of stage A writes (the pieces of a line outside the support
-        // of the telescope OTF, the 16 padding lines, the lines of tasks beyond the chunk): 0 = zero or values the
-        // series form left there itself; 1 = finite values of a call that wrote whole lines (the full-size form, the
-        // series form with "support_skip" off); 2 = anything, non-finite included (a caller's PSD, mpsfr_psf_from_psd).
-        // The next call that writes D0t clears the buffer first when it would otherwise read what is there: a series
-        // call with the support skip at 1 or 2, every call at 2 ("Call-order independence").
-        int d0t_stale = 0;
-        // device outputs of its most recent calls: `done` is recorded behind every call of the lane,
-        // so waiting for it covers all of them (a caller that rotates more buffer sets than lanes
-        // must still get the calls that share a buffer in order)
-        static constexpr int NHIST = 8;
-        const void* outs[NHIST][3] = {};
-        unsigned nouts = 0;
-    };
-    static constexpr int MAX_LANES = 4;
-    Lane lane[MAX_LANES];
-    int nlanes = 0;              // 0 = automatic (two lanes)
-    int cu_partition = 0;        // 1: every lane's stream owns 1/lanes of the CUs (hipExtStreamCreateWithCUMask)
-    bool param_copy_kernel = true;   // the parameter blob of a call is fetched by a kernel (else hipMemcpyAsync)
-    bool stream_exported = false;    // mpsfr_stream() has been called: every call joins its lanes into `stream`
-    hipEvent_t stream_tail = nullptr;    // created once a call has queued work on `stream` (mpsfr_stream_wait)
-    bool pipeline_calls = true;  // successive asynchronous calls rotate over the lanes
-    unsigned lane_rr = 0;        // lane of the next chunk
-    hipEvent_t tables_ready = nullptr;
-    hipEvent_t cache_ready = nullptr;    // cached per-wavelength / geometry tables are complete
-    bool cache_ready_valid = false;
-    hipEvent_t lsum_done = nullptr;      // the per-lane partial stamp sums have been consumed
-    bool lsum_busy = false;
-    hipEvent_t wait_next = nullptr;      // caller's event the next call must wait for
-    // Stagger of the lanes at a cold start (see mpsfr_reconstruct)
-    int cold_stagger = 0;                // 0: off; 1: behind the column transforms; 2: behind the preparation of the
-                                         // per-wavelength stage
-    hipEvent_t stagger_ev = nullptr;     // behind the column transforms of the first chunk after a cold start
-    bool stagger_armed = false;
-    int stagger_lane = -1;
-    DevBuf specx;                      // [nl] the abscissa of mpsfr_fit_spectra_psf's drift
-    DevBuf render;                     // work lists of mpsfr_render_stars (render_workspace_bytes)
-    DevBuf find;                       // core, map, masks and counts of mpsfr_find_stars (find_workspace_bytes)
-    DevBuf group;                      // cells, union-find and row lists of mpsfr_group_stars (group_workspace_bytes)
-    DevBuf framefit;                   // lists, frames, vectors and scalars of mpsfr_fit_frame_psf (frame_fit_workspace_bytes)
-    DevBuf cubefit;                    // the same for a batch of layers of mpsfr_fit_cube_psf (cube_fit_workspace_bytes)
-    DevBuf fit, sum, stage, lsum;      // lsum: [lanes][nl][40][40] per-lane partial stamp sums
-    // mpsfr_psd_to_psf: a stream and workspaces of its own, so that it never waits for nor touches the lanes
-    struct P2P {
-        hipStream_t stream = nullptr;
-        int twm_len = 0;                 // length of the twiddle table in `twm`
-        DevBuf twm, psd, cm, d0t, pup, phase, lbda, cl, t1, q, otf, g, out;
-    } p2p;
-    // Small per-call parameters: one pinned host blob -> one device blob, no stream sync.  A ring
-    // of NSTAGE slots (pinned blob, device blob, tip-tilt kernel spectra): the host may queue
-    // NSTAGE calls ahead of the GPU, and calls in flight on different lanes never share a slot.
-    static constexpr int NSTAGE = 4;
-    struct Slot {
-        void* host = nullptr;
-        size_t host_cap = 0;
-        hipEvent_t staged = nullptr;     // after the H2D copy (the pinned blob may be refilled)
-        hipEvent_t staged_ev = nullptr;  // what the host waits for before it refills the blob: `staged` or `call_done`
-        bool staged_pending = false;
-        hipEvent_t call_done = nullptr;  // after the call that used the slot (join stream, or the call's lane)
-        bool call_pending = false;
-        int last_lane = -1;              // lane of a lean call (stream order covers the slot's reuse there)
-        bool has_event = true;           // `call_done` was recorded for the slot's last call
-        unsigned long long seq = 0;      // staged_mode 2: the value the parameter-copy kernel writes into seq_host[slot]
-        int staged_mode = 0;             // what frees the pinned blob: 0 `staged`, 1 `call_done`, 2 the kernel's flag
-        DevBuf params, ktt;
-    };
-    Slot slot[NSTAGE];
-    unsigned stage_next = 0;
-    // Pinned host words the parameter-copy kernels write when they have read their blob (one per slot): the host
-    // polls them instead of waiting for an event, so that a lean call queues no marker packet at all.
-    unsigned long long* seq_host = nullptr;
-    unsigned long long seq_next = 0;
-    // Asynchronous host outputs (on_device = 2): a ring of result sets -- device buffers the call
-    // writes, a pinned host mirror the join stream copies them to -- and the caller's arrays, filled
-    // when the ticket is waited for.  The host queues up to NTICKET such calls ahead of the GPU and the
-    // calls rotate over the lanes like device-output calls do.
-    struct Ticket {
-        long id = -1;
-        bool pending = false;
-        hipEvent_t done = nullptr;
-        DevBuf dpsf, dsum, dfit;
-        void* host = nullptr;
-        size_t host_cap = 0;
-        double *u_psf = nullptr, *u_sum = nullptr, *u_fit = nullptr;
-        size_t n_psf = 0, n_sum = 0, n_fit = 0;
-    };
-    static constexpr int NTICKET = 4;
-    Ticket ticket[NTICKET];
-    // mpsfr_reconstruct_multi_async (held by ctxs[0]): the shards' stamp sums until mpsfr_wait_multi adds them
-    struct Multi {
-        bool pending = false;
-        int nctx = 0;
-        size_t n = 0;                    // nl * 1600
-        std::vector<double> sums;        // [nctx][n]
-        std::vector<long> tickets;       // per context (-1: no shard)
-        double* user_sum = nullptr;
-    } multi;
-    long ticket_next = 0;                // id of the next asynchronous host-output call
-    long d0t_clears = 0;                 // lane D0t buffers cleared because of what an earlier call left (d0t_stale)
-    double host_seconds = 0.0;           // wall time spent inside mpsfr_reconstruct
-    long host_calls = 0;
-    // caches of the per-call tables that only depend on (lbda) / (geometry, masks)
-    std::vector<double> cache_lbda;
-    int cache_lbda_mode = -1;
-    const void* cache_G_ptr = nullptr;
-    const void* cache_kmuse_ptr = nullptr;
-    const void* cache_xtab_ptr = nullptr;
-    bool cache_xtab_valid = false;
-    const void* cache_etab_ptr = nullptr;
-    const void* cache_gtab_ptr = nullptr;
-    bool cache_mf_valid = false;
-    std::vector<unsigned char> cache_geom;
-    const void* cache_ao_ptr = nullptr;
-    // bookkeeping for debug_fetch
-    int last_ndir = 0, last_nl = 0, last_chunk_tasks = 0, last_lane = 0;
-    int last_ntab = 2;                   // layer tables per direction of the current AO tables (2: a legacy call)
-    int last_gpp = 1;                    // stamp groups per task of the last call: npos of a field call, else 1
-    bool last_mf = false, last_pruned = false, last_mf2 = false, last_dlin = false;
-    float last_thr_blk = 0.f;
-    bool last_floor_per_task = false;
-    std::vector<double> last_lpc;        // c of every wavelength of the last call
-    // thr_eps, thr_floor, thr_mid, tier_half, thr_blk, thr_sum, c2min of the last call ("mf_par")
-    float last_thr[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    // profiling
-    double prof_ms[K_COUNT] = {0};
-    long prof_n[K_COUNT] = {0};
-    std::vector<Pending> pending;
-    std::vector<hipEvent_t> pool;
-};
-
-namespace {
-
-size_t rsize(const mpsfr_ctx* c) { return c->f64 ? sizeof(double) : sizeof(float); }
-
-int ensure(mpsfr_ctx* c, DevBuf& b, size_t bytes) {
-    if (bytes <= b.cap) return MPSFR_OK;
-    if (b.p) {
-        HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipFree(b.p));
-        b.p = nullptr;
-        b.cap = 0;
-    }
-    const size_t want = bytes + bytes / 8;
-    if (hipMalloc(&b.p, want) != hipSuccess) {
-        b.p = nullptr;
-        return fail(MPSFR_E_NOMEM, "hipMalloc of %zu bytes failed", want);
-    }
-    b.cap = want;
-    return MPSFR_OK;
-}
-
-void release(DevBuf& b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-}
-
-// wait for an asynchronous host-output call and hand its results to the caller's arrays
-int complete_ticket(mpsfr_ctx* c, mpsfr_ctx::Ticket& tk) {
-    if (!tk.pending) return MPSFR_OK;
-    HIPCHK(hipEventSynchronize(tk.done));
-    const double* h = (const double*)tk.host;
-    if (tk.u_psf) memcpy(tk.u_psf, h, tk.n_psf * sizeof(double));
-    if (tk.u_sum) memcpy(tk.u_sum, h + tk.n_psf, tk.n_sum * sizeof(double));
-    if (tk.u_fit) memcpy(tk.u_fit, h + tk.n_psf + tk.n_sum, tk.n_fit * sizeof(double));
-    tk.pending = false;
-    return MPSFR_OK;
-}
-
-// The event behind the lane's most recent call; a lean call queued none, so it is recorded here, at the lane's
-// present tail (at or behind the end of that call: conservative), when somebody needs to wait for the lane.
-hipEvent_t lane_end(mpsfr_ctx* c, mpsfr_ctx::Lane& ln) {
-    // (a lane whose stream has been dropped -- "streams" / "cu_partition" reset -- has drained: nothing to record,
-    // and recording on the NULL stream would synchronise with every blocking stream)
-    if (!ln.marked && ln.stream != nullptr) {
-        if (!ln.done) (void)hipEventCreateWithFlags(&ln.done, hipEventDisableTiming);
-        (void)hipEventRecord(ln.done, ln.stream);
-        ln.done_ev = ln.done;
-        ln.marked = true;
-    }
-    return ln.done_ev;
-}
-
-hipEvent_t get_event(mpsfr_ctx* c) {
-    if (!c->pool.empty()) {
-        hipEvent_t e = c->pool.back();
-        c->pool.pop_back();
-        return e;
-    }
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    return e;
-}
-
-int resolve_profile(mpsfr_ctx* c);
-
-// workgroups of a persistent kernel on a lane: one per CU the lane may use, less the reserve
-template <class LaneT>
-int persist_grid(const mpsfr_ctx* c, const LaneT& ln, int reserve, bool shared) {
-    const int n = ln.ncu ? ln.ncu : c->ncu;
-    if (reserve < 0) reserve = (shared && !ln.ncu) ? n / 8 : 0;         // (CU-masked lanes are partitioned already)
-    return n - reserve >= n / 2 ? n - reserve : n / 2;
-}
-
-struct ProfScope {
-    mpsfr_ctx* c;
-    int id;
-    hipEvent_t a = nullptr, b = nullptr;
-    hipStream_t st;
-    bool on = false;
-    bool markers;              // false: the launch itself carries the events (hipExtLaunchKernelGGL)
-    ProfScope(mpsfr_ctx* ctx, int kid, hipStream_t stream = nullptr, bool use_markers = true)
-        : c(ctx), id(kid), st(stream ? stream : ctx->stream), markers(use_markers) {
-        on = c->profile && (c->prof_only < 0 || c->prof_only == kid);
-        if (on && c->prof_every > 1 && kid >= 0 && kid < 64) on = (c->prof_count[kid]++ % (unsigned)c->prof_every) == 0;
-        if (on) {
-            a = get_event(c);
-            b = get_event(c);
-            if (!a || !b) {          // out of events: this launch goes untimed
-                if (a) c->pool.push_back(a);
-                if (b) c->pool.push_back(b);
-                a = b = nullptr;
-                on = false;
-            } else if (markers) {
-                (void)hipEventRecord(a, st);
-            }
-        }
-    }
-    ~ProfScope() {
-        if (on) {
-            if (markers) (void)hipEventRecord(b, st);
-            c->pending.push_back({id, a, b});
-            // a caller that never reads the profile must not grow the event list without bound
-            if (c->pending.size() >= 8192) (void)resolve_profile(c);
-        }
-    }
-};
-
-int resolve_profile(mpsfr_ctx* c) {
+int mpsfr::host::resolve_profile(mpsfr_ctx* c) {
     if (c->pending.empty()) return MPSFR_OK;
     HIPCHK(hipStreamSynchronize(c->stream));
     for (int k = 0; k < mpsfr_ctx::MAX_LANES; ++k)
@@ -374,6 +34,33 @@ int resolve_profile(mpsfr_ctx* c) {
     }
     c->pending.clear();
     return MPSFR_OK;
+}
+
+namespace {
+
+const char* kKernelNames[K_COUNT] = {
+    "ao_tables", "tel_otf", "psd_rowfft", "colfft_dphi", "gtable",
+    "moffat_kernels", "otf_rowfft", "colpass", "conv", "fit", "stamp_sum", "vkeep", "otf_mfma", "mf_prep",
+    "patch", "dphi_series"};
+
+// wait for an asynchronous host-output call and hand its results to the caller's arrays
+int complete_ticket(mpsfr_ctx* c, mpsfr_ctx::Ticket& tk) {
+    if (!tk.pending) return MPSFR_OK;
+    HIPCHK(hipEventSynchronize(tk.done));
+    const double* h = (const double*)tk.host;
+    if (tk.u_psf) memcpy(tk.u_psf, h, tk.n_psf * sizeof(double));
+    if (tk.u_sum) memcpy(tk.u_sum, h + tk.n_psf, tk.n_sum * sizeof(double));
+    if (tk.u_fit) memcpy(tk.u_fit, h + tk.n_psf + tk.n_sum, tk.n_fit * sizeof(double));
+    tk.pending = false;
+    return MPSFR_OK;
+}
+
+// workgroups of a persistent kernel on a lane: one per CU the lane may use, less the reserve
+template <class LaneT>
+int persist_grid(const mpsfr_ctx* c, const LaneT& ln, int reserve, bool shared) {
+    const int n = ln.ncu ? ln.ncu : c->ncu;
+    if (reserve < 0) reserve = (shared && !ln.ncu) ? n / 8 : 0;         // (CU-masked lanes are partitioned already)
+    return n - reserve >= n / 2 ? n - reserve : n / 2;
 }
 
 bool supported_dim(int n) { return n == 128 || n == 256 || n == 512 || n == 1024 || n == 1280; }
@@ -535,116 +222,6 @@ int build_constant_tables(mpsfr_ctx* c) {
     return build_series_tables(c);
 }
 
-// The calls queued so far run on the pipeline lanes: stream s waits for them on the GPU, so that device stamps written
-// by a device-output reconstruct of this context are complete when a kernel on s reads them.
-int wait_for_lanes(mpsfr_ctx* c, hipStream_t s) {
-    for (int k = 0; k < mpsfr_ctx::MAX_LANES; ++k)
-        if (c->lane[k].busy && c->lane[k].stream != s) HIPCHK(hipStreamWaitEvent(s, lane_end(c, c->lane[k]), 0));
-    return MPSFR_OK;
-}
-
-// An input array of a stamp call: `count` elements of `elem` bytes, or NULL for an optional that is absent.
-struct StampIn {
-    const void* p;
-    size_t count, elem;
-};
-
-// An output array of a stamp call: `count` elements of `elem` bytes (doubles unless said otherwise), or NULL for an
-// optional that is absent.
-struct StampOut {
-    void* p;
-    size_t count, elem = sizeof(double);
-};
-
-// One stamp call (the fits and the metrics of caller-provided stamps, the frame calls) on the context stream, after the
-// lanes, timed under the fit's profiling id.  launch(s, d, d_out) receives the inputs in the order of `in` and the
-// outputs in the order of `out` as device pointers.  on_device: they are the caller's own pointers and the call returns
-// once it is queued.  Else the arrays are staged in c->stage -- the inputs of doubles in order, then the outputs in order,
-// then the narrower inputs (int32 indices), so that everything is aligned; an absent array gets no room and stays NULL
-// -- copied in, the outputs are copied back and the call waits for them.
-template <size_t N, size_t M, class Launch>
-int stamp_call(mpsfr_ctx* c, int on_device, const StampIn (&in)[N], const StampOut (&out)[M], Launch launch) {
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    int rc;
-    if ((rc = wait_for_lanes(c, s))) return rc;
-    const void* d[N];
-    double* d_out[M];
-    for (size_t i = 0; i < N; ++i) d[i] = in[i].p;
-    for (size_t i = 0; i < M; ++i) d_out[i] = (double*)out[i].p;
-    if (!on_device) {
-        size_t off[N] = {}, off_out[M] = {}, bytes = 0;
-        for (int narrow = 0; narrow < 2; ++narrow) {
-            for (size_t i = 0; i < N; ++i)
-                if (in[i].p && (in[i].elem < sizeof(double)) == (narrow == 1)) {
-                    off[i] = bytes;
-                    bytes += in[i].count * in[i].elem;
-                }
-            if (!narrow)
-                for (size_t i = 0; i < M; ++i)
-                    if (out[i].p) {
-                        off_out[i] = bytes;
-                        bytes += (out[i].count * out[i].elem + 7) & ~(size_t)7;
-                    }
-        }
-        if ((rc = ensure(c, c->stage, bytes))) return rc;
-        char* base = (char*)c->stage.p;
-        for (size_t i = 0; i < M; ++i)
-            if (out[i].p) d_out[i] = (double*)(base + off_out[i]);
-        for (size_t i = 0; i < N; ++i)
-            if (in[i].p) {
-                d[i] = base + off[i];
-                HIPCHK(hipMemcpyAsync(base + off[i], in[i].p, in[i].count * in[i].elem, hipMemcpyHostToDevice, s));
-            }
-    }
-    {
-        ProfScope ps(c, K_FIT);
-        launch(s, d, d_out);
-    }
-    HIPCHK(hipGetLastError());
-    if (!on_device) {
-        for (size_t i = 0; i < M; ++i)
-            if (out[i].p)
-                HIPCHK(hipMemcpyAsync(out[i].p, d_out[i], out[i].count * out[i].elem, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    return MPSFR_OK;
-}
-
-// the common case: one output
-template <size_t N, class Launch>
-int stamp_call(mpsfr_ctx* c, int on_device, const StampIn (&in)[N], double* out, size_t nout, Launch launch) {
-    const StampOut outs[] = {{out, nout}};
-    return stamp_call(c, on_device, in, outs,
-                      [&](hipStream_t s, const void* const* d, double* const* d_out) { launch(s, d, d_out[0]); });
-}
-
-const size_t kStampPix = (size_t)NS * NS;
-
-// The host form's refusal of a model list: every psf_index (n of them, or nullptr) in 0..npsf-1, then every one of the
-// nshift shifts (or nullptr) finite and within 8 pixels; `what` is the caller's noun for a shift.
-int check_model_list(const char* who, const char* what, int n, int npsf, const int32_t* psf_index, const double* shift,
-                     size_t nshift) {
-    if (psf_index)
-        for (int k = 0; k < n; ++k)
-            if (psf_index[k] < 0 || psf_index[k] >= npsf)
-                return fail(MPSFR_E_INVALID, "%s: a psf_index outside 0..npsf-1", who);
-    if (shift)
-        for (size_t k = 0; k < nshift; ++k)
-            if (!(std::fabs(shift[k]) <= MPSFR_FIT_PSF_MAX_SHIFT))
-                return fail(MPSFR_E_INVALID, "%s: a %s that is not finite or beyond 8 pixels", who, what);
-    return MPSFR_OK;
-}
-
-// ... and of the stars of a frame: finite scales (or nullptr), then origins within 2^30
-int check_frame_stars(const char* who, int n, const int32_t* origin, const double* scale, const char* scale_name) {
-    if (scale)
-        for (int k = 0; k < n; ++k)
-            if (!std::isfinite(scale[k])) return fail(MPSFR_E_INVALID, "%s: a %s that is not finite", who, scale_name);
-    for (size_t k = 0; k < (size_t)2 * n; ++k)
-        if (origin[k] < -(1 << 30) || origin[k] > (1 << 30)) return fail(MPSFR_E_INVALID, "%s: an origin beyond 2^30", who);
-    return MPSFR_OK;
-}
 
 }  // namespace
 
@@ -2656,28 +2233,6 @@ int mpsfr_wait_multi(mpsfr_ctx* const* ctxs, int nctx) {
     return MPSFR_OK;
 }
 
-int mpsfr_fit_rows(const double* fit, long n, double pixscale, double* out, long stride) {
-    if (!fit || !out || n < 0 || stride < 14) return fail(MPSFR_E_INVALID, "mpsfr_fit_rows: bad argument");
-    for (long r = 0; r < n; ++r) {
-        const double* f = fit + (size_t)r * NFIT;
-        double* o = out + (size_t)r * stride;
-        o[0] = f[1];                     // center
-        o[1] = f[2];
-        o[2] = f[15];                    // flux
-        o[3] = o[4] = f[5] * pixscale;   // fwhm
-        o[5] = f[4];                     // n
-        o[6] = f[0];                     // peak
-        o[7] = f[9];                     // err_center
-        o[8] = f[10];
-        const double a = f[8] / f[0], b = 2.0 * f[11] / f[3], d = f[12] / (f[4] - 1.0);
-        o[9] = std::fabs(f[15]) * std::sqrt(a * a + b * b + d * d);      // err_flux
-        o[10] = o[11] = f[13] * pixscale;                                // err_fwhm
-        o[12] = f[12];                   // err_n
-        o[13] = f[8];                    // err_peak
-    }
-    return MPSFR_OK;
-}
-
 int mpsfr_simul_psd(mpsfr_ctx* c, double seeing, double gl, double l0, int three_lgs, const double h[2],
                     double wind_speed, int npsflin, const uint8_t* mask_rec, const uint8_t* mask_res,
                     double* psd_out) {
@@ -2808,625 +2363,6 @@ int mpsfr_psd_to_psf(mpsfr_ctx* c, int npsd, const double* psd, int npup, const 
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
     return MPSFR_OK;
-}
-
-int mpsfr_fit_stamps(mpsfr_ctx* c, int nstamp, const double* stamps, double* fit_out,
-                     int on_device) {
-    if (!c || !stamps || !fit_out || nstamp < 1) return fail(MPSFR_E_INVALID, "bad argument");
-    const StampIn in[] = {{stamps, nstamp * kStampPix, sizeof(double)}};
-    return stamp_call(c, on_device, in, fit_out, (size_t)nstamp * NFIT,
-                      [&](hipStream_t s, const void* const* d, double* d_fit) {
-                          launch_fit(s, nstamp, (const double*)d[0], false, d_fit, c->f64);
-                      });
-}
-
-int mpsfr_fit_stamps_elliptical(mpsfr_ctx* c, int nstamp, const double* stamps, double* fit_out, int on_device) {
-    if (!c || !stamps || !fit_out || nstamp < 1) return fail(MPSFR_E_INVALID, "bad argument");
-    const StampIn in[] = {{stamps, nstamp * kStampPix, sizeof(double)}};
-    return stamp_call(c, on_device, in, fit_out, (size_t)nstamp * NFIT_ELL,
-                      [&](hipStream_t s, const void* const* d, double* d_fit) {
-                          launch_fit_ell(s, nstamp, (const double*)d[0], d_fit, c->f64);
-                      });
-}
-
-int mpsfr_fit_stamps_observed(mpsfr_ctx* c, int nstamp, const double* stamps, const double* var, int flags,
-                              double* fit_out, int on_device) {
-    if (!c || !stamps || !fit_out || nstamp < 1) return fail(MPSFR_E_INVALID, "bad argument");
-    if (flags & ~(MPSFR_FIT_BACKGROUND | MPSFR_FIT_ELLIPTICAL))
-        return fail(MPSFR_E_INVALID, "fit_stamps_observed: unknown flag bits");
-    const StampIn in[] = {{stamps, nstamp * kStampPix, sizeof(double)}, {var, nstamp * kStampPix, sizeof(double)}};
-    return stamp_call(c, on_device, in, fit_out, (size_t)nstamp * NFIT_ELL,
-                      [&](hipStream_t s, const void* const* d, double* d_fit) {
-                          launch_fit_obs(s, nstamp, (const double*)d[0], (const double*)d[1], flags, d_fit, c->f64);
-                      });
-}
-
-static_assert(NFIT_PSF == MPSFR_NFIT_PSF, "K_FIT_PSF row layout");
-
-int mpsfr_fit_stamps_psf(mpsfr_ctx* c, int nstamp, const double* stamps, const double* var, int npsf,
-                         const double* psf, const int32_t* psf_index, const double* shift, int flags,
-                         double* fit_out, int on_device) {
-    if (!c || !stamps || !psf || !fit_out || nstamp < 1 || npsf < 1) return fail(MPSFR_E_INVALID, "bad argument");
-    if (flags & ~(MPSFR_FIT_BACKGROUND | MPSFR_FIT_FIXED_SHIFT))
-        return fail(MPSFR_E_INVALID, "fit_stamps_psf: unknown flag bits (the elliptical bit has no meaning here)");
-    if (!psf_index && npsf != nstamp)
-        return fail(MPSFR_E_INVALID, "fit_stamps_psf: without psf_index, npsf must equal nstamp");
-    if ((flags & MPSFR_FIT_FIXED_SHIFT) && !shift)
-        return fail(MPSFR_E_INVALID, "fit_stamps_psf: MPSFR_FIT_FIXED_SHIFT needs the shift array");
-    int rc;
-    if (!on_device &&
-        (rc = check_model_list("fit_stamps_psf", "shift", nstamp, npsf, psf_index, shift, (size_t)2 * nstamp)))
-        return rc;
-    const StampIn in[] = {{stamps, nstamp * kStampPix, sizeof(double)}, {var, nstamp * kStampPix, sizeof(double)},
-                          {psf, npsf * kStampPix, sizeof(double)},      {shift, (size_t)2 * nstamp, sizeof(double)},
-                          {psf_index, (size_t)nstamp, sizeof(int32_t)}};
-    return stamp_call(c, on_device, in, fit_out, (size_t)nstamp * NFIT_PSF,
-                      [&](hipStream_t s, const void* const* d, double* d_fit) {
-                          launch_fit_psf(s, nstamp, (const double*)d[0], (const double*)d[1], npsf, (const double*)d[2],
-                                         (const int32_t*)d[4], (const double*)d[3], flags, d_fit, c->f64);
-                      });
-}
-
-static_assert(NFIT_GROUP == MPSFR_NFIT_GROUP && MPSFR_NFIT_GROUP == 8 + 8 * MPSFR_MAX_GROUP + 8, "K_FIT_GROUP row layout");
-
-int mpsfr_fit_groups_psf(mpsfr_ctx* c, int nstamp, int nsrc, const double* stamps, const double* var, int npsf,
-                         const double* psf, const int32_t* psf_index, const double* shift, int flags,
-                         double* fit_out, int on_device) {
-    if (!c || !stamps || !psf || !shift || !fit_out || nstamp < 1 || npsf < 1)
-        return fail(MPSFR_E_INVALID, "fit_groups_psf: bad argument (stamps, psf, shift and fit_out are required)");
-    if (nsrc == 1)
-        return fail(MPSFR_E_INVALID, "fit_groups_psf: a group has 2 to %d sources; one source is mpsfr_fit_stamps_psf",
-                    MPSFR_MAX_GROUP);
-    if (nsrc < 2 || nsrc > MPSFR_MAX_GROUP)
-        return fail(MPSFR_E_INVALID, "fit_groups_psf: nsrc=%d outside 2..%d", nsrc, MPSFR_MAX_GROUP);
-    if (flags & ~(MPSFR_FIT_BACKGROUND | MPSFR_FIT_FIXED_SHIFT | MPSFR_FIT_COMMON_SHIFT))
-        return fail(MPSFR_E_INVALID, "fit_groups_psf: unknown flag bits (the elliptical bit has no meaning here)");
-    if ((flags & MPSFR_FIT_FIXED_SHIFT) && (flags & MPSFR_FIT_COMMON_SHIFT))
-        return fail(MPSFR_E_INVALID, "fit_groups_psf: MPSFR_FIT_FIXED_SHIFT and MPSFR_FIT_COMMON_SHIFT exclude each other");
-    if (!psf_index && npsf != nstamp)
-        return fail(MPSFR_E_INVALID, "fit_groups_psf: without psf_index, npsf must equal nstamp");
-    const size_t npos = (size_t)2 * nsrc * nstamp;
-    int rc;
-    if (!on_device && (rc = check_model_list("fit_groups_psf", "position", nstamp, npsf, psf_index, shift, npos)))
-        return rc;
-    const StampIn in[] = {{stamps, nstamp * kStampPix, sizeof(double)}, {var, nstamp * kStampPix, sizeof(double)},
-                          {psf, npsf * kStampPix, sizeof(double)},      {shift, npos, sizeof(double)},
-                          {psf_index, (size_t)nstamp, sizeof(int32_t)}};
-    return stamp_call(c, on_device, in, fit_out, (size_t)nstamp * NFIT_GROUP,
-                      [&](hipStream_t s, const void* const* d, double* d_fit) {
-                          launch_fit_group(s, nstamp, nsrc, (const double*)d[0], (const double*)d[1], npsf,
-                                           (const double*)d[2], (const int32_t*)d[4], (const double*)d[3], flags, d_fit,
-                                           c->f64);
-                      });
-}
-
-int mpsfr_fit_spectra_psf(mpsfr_ctx* c, int nstar, int nl, const double* cubes, const double* var, int npsf,
-                          const double* psf, const int32_t* psf_index, const double* shift, const double* x,
-                          int flags, double* fit_out, int on_device) {
-    if (!c || !cubes || !psf || !fit_out || nstar < 1 || npsf < 1)
-        return fail(MPSFR_E_INVALID, "fit_spectra_psf: bad argument (cubes, psf and fit_out are required)");
-    if (nl < 1 || nl > MPSFR_MAX_SPEC_LAYERS)
-        return fail(MPSFR_E_INVALID, "fit_spectra_psf: nl=%d outside 1..%d", nl, MPSFR_MAX_SPEC_LAYERS);
-    if (flags & ~(MPSFR_FIT_BACKGROUND | MPSFR_FIT_DRIFT))
-        return fail(MPSFR_E_INVALID, "fit_spectra_psf: unknown flag bits (only the background and the drift bit have a meaning here)");
-    if (!psf_index && npsf != nstar)
-        return fail(MPSFR_E_INVALID, "fit_spectra_psf: without psf_index, npsf must equal nstar");
-    const bool drift = (flags & MPSFR_FIT_DRIFT) != 0;
-    if (drift) {
-        if (!x || nl < 2) return fail(MPSFR_E_INVALID, "fit_spectra_psf: MPSFR_FIT_DRIFT needs x and at least two layers");
-        bool differ = false;
-        for (int l = 0; l < nl; ++l) {
-            if (!(std::fabs(x[l]) <= 1.0)) return fail(MPSFR_E_INVALID, "fit_spectra_psf: x must be finite in [-1, 1]");
-            differ = differ || x[l] != x[0];
-        }
-        if (!differ) return fail(MPSFR_E_INVALID, "fit_spectra_psf: at least two values of x must differ");
-    }
-    int rc;
-    if (!on_device && (rc = check_model_list("fit_spectra_psf", "start", nstar, npsf, psf_index, shift, (size_t)2 * nstar)))
-        return rc;
-    const double* d_x = nullptr;
-    if (drift) {           // x is the host's in both forms: into a buffer of the context, on the stream of the call
-        HIPCHK(hipSetDevice(c->device));
-        if ((rc = ensure(c, c->specx, (size_t)nl * sizeof(double)))) return rc;
-        HIPCHK(hipMemcpyAsync(c->specx.p, x, (size_t)nl * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        d_x = (const double*)c->specx.p;
-    }
-    const size_t ncube = (size_t)nl * kStampPix;
-    const StampIn in[] = {{cubes, nstar * ncube, sizeof(double)}, {var, nstar * ncube, sizeof(double)},
-                          {psf, npsf * ncube, sizeof(double)},    {shift, (size_t)2 * nstar, sizeof(double)},
-                          {psf_index, (size_t)nstar, sizeof(int32_t)}};
-    return stamp_call(c, on_device, in, fit_out, (size_t)nstar * (MPSFR_NFIT_SPEC + (size_t)MPSFR_NFIT_SPEC_LAYER * nl),
-                      [&](hipStream_t s, const void* const* d, double* d_fit) {
-                          launch_fit_spec(s, nstar, nl, (const double*)d[0], (const double*)d[1], npsf,
-                                          (const double*)d[2], (const int32_t*)d[4], (const double*)d[3], d_x, flags,
-                                          d_fit, c->f64);
-                      });
-}
-
-static_assert(METRIC_MAX == MPSFR_MAX_METRIC_RADII && METRIC_HEAD == MPSFR_NMET_HEAD, "K_STAMP_METRICS row layout");
-
-int mpsfr_stamp_metrics(mpsfr_ctx* c, int nstamp, const double* stamps, const double* centers, int nrad,
-                        const double* radii_px, int nbox, const double* boxes_px, int nfrac, const double* fractions,
-                        double* out, int on_device) {
-    if (!c || !stamps || !out || nstamp < 1) return fail(MPSFR_E_INVALID, "bad argument");
-    if (nrad < 0 || nrad > METRIC_MAX || nbox < 0 || nbox > METRIC_MAX || nfrac < 0 || nfrac > METRIC_MAX ||
-        nrad + nbox + nfrac == 0)
-        return fail(MPSFR_E_INVALID, "metrics: need 0..16 radii, boxes and fractions, and at least one of them");
-    if ((nrad && !radii_px) || (nbox && !boxes_px) || (nfrac && !fractions))
-        return fail(MPSFR_E_INVALID, "metrics: NULL parameter array");
-    for (int k = 0; k < nrad; ++k)
-        if (!(radii_px[k] > 0.0 && radii_px[k] <= 2.0 * NS))
-            return fail(MPSFR_E_INVALID, "metrics: a radius must be finite, > 0 and at most 80 pixels");
-    for (int k = 0; k < nbox; ++k)
-        if (!(boxes_px[k] > 0.0 && boxes_px[k] <= 2.0 * NS))
-            return fail(MPSFR_E_INVALID, "metrics: a box side must be finite, > 0 and at most 80 pixels");
-    for (int k = 0; k < nfrac; ++k)
-        if (!(fractions[k] > 0.0 && fractions[k] < 1.0))
-            return fail(MPSFR_E_INVALID, "metrics: a fraction must lie in (0, 1)");
-    const StampIn in[] = {{stamps, nstamp * kStampPix, sizeof(double)}, {centers, (size_t)2 * nstamp, sizeof(double)}};
-    return stamp_call(c, on_device, in, out, (size_t)nstamp * (METRIC_HEAD + nrad + nbox + nfrac),
-                      [&](hipStream_t s, const void* const* d, double* d_out) {
-                          launch_stamp_metrics(s, nstamp, (const double*)d[0], (const double*)d[1], nrad, radii_px, nbox,
-                                               boxes_px, nfrac, fractions, d_out);
-                      });
-}
-
-static_assert(MPSFR_NRENDER == 4 && MPSFR_FIT_PSF_MAX_SHIFT == 8.0, "K_RENDER_PREPARE row layout and domain");
-
-static int frame_shape(const char* who, int ny, int nx) {
-    if (ny < 1 || ny > MPSFR_MAX_IMAGE_SIDE || nx < 1 || nx > MPSFR_MAX_IMAGE_SIDE || (size_t)ny * nx > ((size_t)1 << 26))
-        return fail(MPSFR_E_INVALID, "%s: a frame has 1..%d rows and columns and at most 2^26 pixels, not %d x %d", who,
-                    MPSFR_MAX_IMAGE_SIDE, ny, nx);
-    return MPSFR_OK;
-}
-
-int mpsfr_cut_stamps(mpsfr_ctx* c, int ny, int nx, const double* image, const double* var, int nstar,
-                     const int32_t* origin, double* stamps_out, double* var_out, int on_device) {
-    if (!c || !image || !origin || !stamps_out || nstar < 1)
-        return fail(MPSFR_E_INVALID, "cut_stamps: bad argument (image, origin and stamps_out are required)");
-    int rc;
-    if ((rc = frame_shape("cut_stamps", ny, nx))) return rc;
-    if ((var == nullptr) != (var_out == nullptr))
-        return fail(MPSFR_E_INVALID, "cut_stamps: var and var_out must both be NULL or both be given");
-    const size_t npix = (size_t)ny * nx;
-    const StampIn in[] = {{image, npix, sizeof(double)}, {var, npix, sizeof(double)},
-                          {origin, (size_t)2 * nstar, sizeof(int32_t)}};
-    const StampOut out[] = {{stamps_out, nstar * kStampPix}, {var_out, nstar * kStampPix}};
-    return stamp_call(c, on_device, in, out, [&](hipStream_t s, const void* const* d, double* const* d_out) {
-        launch_cut_stamps(s, ny, nx, (const double*)d[0], (const double*)d[1], nstar, (const int32_t*)d[2], d_out[0],
-                          d_out[1]);
-    });
-}
-
-int mpsfr_render_stars(mpsfr_ctx* c, int ny, int nx, const double* image_in, int nstar, int npsf, const double* psf,
-                       const int32_t* psf_index, const int32_t* origin, const double* shift, const double* scale,
-                       int flags, double* image_out, double* star_out, int on_device) {
-    if (!c || !psf || !origin || !scale || !image_out || nstar < 1 || npsf < 1)
-        return fail(MPSFR_E_INVALID, "render_stars: bad argument (psf, origin, scale and image_out are required)");
-    int rc;
-    if ((rc = frame_shape("render_stars", ny, nx))) return rc;
-    if (flags & ~MPSFR_RENDER_SUBTRACT) return fail(MPSFR_E_INVALID, "render_stars: unknown flag bits");
-    if ((flags & MPSFR_RENDER_SUBTRACT) && !image_in)
-        return fail(MPSFR_E_INVALID, "render_stars: MPSFR_RENDER_SUBTRACT needs image_in");
-    if (!psf_index && npsf != nstar)
-        return fail(MPSFR_E_INVALID, "render_stars: without psf_index, npsf must equal nstar");
-    if (!on_device) {
-        if ((rc = check_model_list("render_stars", "shift", nstar, npsf, psf_index, shift, (size_t)2 * nstar))) return rc;
-        if ((rc = check_frame_stars("render_stars", nstar, origin, scale, "scale"))) return rc;
-    }
-    HIPCHK(hipSetDevice(c->device));
-    if ((rc = ensure(c, c->render, render_workspace_bytes(ny, nx, nstar)))) return rc;
-    const size_t npix = (size_t)ny * nx;
-    const StampIn in[] = {{image_in, npix, sizeof(double)},         {psf, npsf * kStampPix, sizeof(double)},
-                          {shift, (size_t)2 * nstar, sizeof(double)}, {scale, (size_t)nstar, sizeof(double)},
-                          {origin, (size_t)2 * nstar, sizeof(int32_t)}, {psf_index, (size_t)nstar, sizeof(int32_t)}};
-    const StampOut out[] = {{image_out, npix}, {star_out, (size_t)nstar * MPSFR_NRENDER}};
-    return stamp_call(c, on_device, in, out, [&](hipStream_t s, const void* const* d, double* const* d_out) {
-        const StarList stars{nstar, npsf, (const double*)d[1], (const int32_t*)d[5], (const int32_t*)d[4],
-                             (const double*)d[2]};
-        launch_render_stars(s, ny, nx, (const double*)d[0], stars, (const double*)d[3],
-                            (flags & MPSFR_RENDER_SUBTRACT) != 0, d_out[0], d_out[1], c->render.p);
-    });
-}
-
-static_assert(MPSFR_NFIND == 8 && MPSFR_FIND_MAX_HALF <= NS / 2, "K_FIND_ROWS row layout and the core");
-
-int mpsfr_find_stars(mpsfr_ctx* c, int ny, int nx, const double* image, const double* var, const double* psf, int half,
-                     int sep, double threshold, int max_stars, double* star_out, int32_t* origin_out,
-                     int32_t* count_out, double* map_out, int on_device) {
-    if (!c || !image || !psf || !star_out || !count_out)
-        return fail(MPSFR_E_INVALID, "find_stars: bad argument (image, psf, star_out and count_out are required)");
-    int rc;
-    if ((rc = frame_shape("find_stars", ny, nx))) return rc;
-    if (half < 1 || half > MPSFR_FIND_MAX_HALF || half > NS / 2)
-        return fail(MPSFR_E_INVALID, "find_stars: half=%d outside 1..%d", half, MPSFR_FIND_MAX_HALF);
-    if (sep < 1 || sep > MPSFR_FIND_MAX_SEP)
-        return fail(MPSFR_E_INVALID, "find_stars: sep=%d outside 1..%d", sep, MPSFR_FIND_MAX_SEP);
-    if (max_stars < 1 || max_stars > (1 << 24))
-        return fail(MPSFR_E_INVALID, "find_stars: max_stars=%d outside 1..2^24", max_stars);
-    if (!std::isfinite(threshold)) return fail(MPSFR_E_INVALID, "find_stars: threshold is not finite");
-    if (!on_device) {
-        bool differ = false;
-        const double* core = psf + (NS / 2 - half) * NS + (NS / 2 - half);
-        for (int a = 0; a <= 2 * half; ++a)
-            for (int b = 0; b <= 2 * half; ++b) {
-                if (!std::isfinite(core[a * NS + b]))
-                    return fail(MPSFR_E_INVALID, "find_stars: psf has a value that is not finite in its core");
-                differ = differ || core[a * NS + b] != core[0];
-            }
-        if (!differ) return fail(MPSFR_E_INVALID, "find_stars: psf is constant over its core");
-    }
-    HIPCHK(hipSetDevice(c->device));
-    if ((rc = ensure(c, c->find, find_workspace_bytes(ny, nx, max_stars, map_out != nullptr)))) return rc;
-    const size_t npix = (size_t)ny * nx;
-    const StampIn in[] = {{image, npix, sizeof(double)}, {var, npix, sizeof(double)}, {psf, kStampPix, sizeof(double)}};
-    const StampOut out[] = {{star_out, (size_t)max_stars * MPSFR_NFIND},
-                            {map_out, npix},
-                            {origin_out, (size_t)2 * max_stars, sizeof(int32_t)},
-                            {count_out, 1, sizeof(int32_t)}};
-    return stamp_call(c, on_device, in, out, [&](hipStream_t s, const void* const* d, double* const* d_out) {
-        launch_find_stars(s, ny, nx, (const double*)d[0], (const double*)d[1], (const double*)d[2], half, sep, threshold,
-                          max_stars, d_out[0], (int32_t*)d_out[2], (int32_t*)d_out[3], d_out[1], c->find.p);
-    });
-}
-
-static_assert(MPSFR_NBACK == 8 && MPSFR_NBACK_HEAD == 4 && MPSFR_BACKGROUND_MAX_BOX == 64 && MPSFR_BACK_FILLED == 1 &&
-                  MPSFR_BACK_CLIP_CAP == 2 && MPSFR_BACK_FLAT == 4,
-              "k_bg_cell row layout, the keys of a cell in LDS and the flags");
-
-int mpsfr_frame_background(mpsfr_ctx* c, int nl, int ny, int nx, const double* image, const double* var, int box,
-                           int filter, double kappa, int max_clip, double min_frac, const double* apply_to,
-                           double* mesh_out, double* head_out, double* map_out, double* rms_out, double* applied_out,
-                           int on_device) {
-    const char* who = "frame_background";
-    if (!c || !image || !mesh_out || !head_out)
-        return fail(MPSFR_E_INVALID, "%s: bad argument (image, mesh_out and head_out are required)", who);
-    int rc;
-    if ((rc = frame_shape(who, ny, nx))) return rc;
-    if (nl < 1 || (size_t)nl * ny * nx > ((size_t)1 << 26))
-        return fail(MPSFR_E_INVALID, "%s: 1 or more layers of at most 2^26 pixels in total, not %d x %d x %d", who, nl, ny,
-                    nx);
-    if (box < MPSFR_BACKGROUND_MIN_BOX || box > MPSFR_BACKGROUND_MAX_BOX)
-        return fail(MPSFR_E_INVALID, "%s: box=%d outside %d..%d", who, box, MPSFR_BACKGROUND_MIN_BOX,
-                    MPSFR_BACKGROUND_MAX_BOX);
-    if (filter != 1 && filter != 3 && filter != 5)
-        return fail(MPSFR_E_INVALID, "%s: filter=%d is not 1, 3 or 5", who, filter);
-    if (!(kappa >= 1.0 && kappa <= 100.0)) return fail(MPSFR_E_INVALID, "%s: kappa must be finite, in 1..100", who);
-    if (max_clip < 0 || max_clip > MPSFR_BACKGROUND_MAX_CLIP)
-        return fail(MPSFR_E_INVALID, "%s: max_clip=%d outside 0..%d", who, max_clip, MPSFR_BACKGROUND_MAX_CLIP);
-    if (!(min_frac > 0.0 && min_frac <= 1.0)) return fail(MPSFR_E_INVALID, "%s: min_frac must lie in (0, 1]", who);
-    if ((apply_to == nullptr) != (applied_out == nullptr))
-        return fail(MPSFR_E_INVALID, "%s: apply_to and applied_out must both be NULL or both be given", who);
-    if (applied_out && applied_out == image) return fail(MPSFR_E_INVALID, "%s: applied_out may not be image", who);
-    const double kc = kappa * 1.4826;
-    const size_t npix = (size_t)nl * ny * nx;
-    const size_t ncell = (size_t)nl * ((ny + box - 1) / box) * ((nx + box - 1) / box);
-    const StampIn in[] = {{image, npix, sizeof(double)}, {var, npix, sizeof(double)}, {apply_to, npix, sizeof(double)}};
-    const StampOut out[] = {{mesh_out, ncell * MPSFR_NBACK},
-                            {head_out, (size_t)nl * MPSFR_NBACK_HEAD},
-                            {map_out, npix},
-                            {rms_out, npix},
-                            {applied_out, npix}};
-    return stamp_call(c, on_device, in, out, [&](hipStream_t s, const void* const* d, double* const* d_out) {
-        launch_frame_background(s, nl, ny, nx, (const double*)d[0], (const double*)d[1], box, filter, kc, max_clip,
-                                min_frac, (const double*)d[2], d_out[0], d_out[1], d_out[2], d_out[3], d_out[4]);
-    });
-}
-
-static_assert(MPSFR_NGROUP == 8 && MPSFR_MAX_GROUP == 4 && MPSFR_GROUP_MAX_CRIT == 2.0 * MPSFR_FIT_PSF_MAX_SHIFT,
-              "K_GROUP_ROWS row layout, the member slots and the cell side");
-
-int mpsfr_group_stars(mpsfr_ctx* c, int ny, int nx, int nstar, const double* pos, int stride, double crit,
-                      int max_groups, int32_t* label_out, int32_t* group_out, int32_t* origin_out, double* shift_out,
-                      int32_t* count_out, int on_device) {
-    if (!c || !pos || !label_out || !group_out || !count_out)
-        return fail(MPSFR_E_INVALID, "group_stars: bad argument (pos, label_out, group_out and count_out are required)");
-    int rc;
-    if ((rc = frame_shape("group_stars", ny, nx))) return rc;
-    if (nstar < 1 || nstar > (1 << 24)) return fail(MPSFR_E_INVALID, "group_stars: nstar=%d outside 1..2^24", nstar);
-    if (stride < 2) return fail(MPSFR_E_INVALID, "group_stars: stride=%d below 2", stride);
-    if (!(crit > 0.0 && crit <= MPSFR_GROUP_MAX_CRIT))
-        return fail(MPSFR_E_INVALID, "group_stars: crit must be finite, > 0 and at most %g pixels", MPSFR_GROUP_MAX_CRIT);
-    if (max_groups < 1) return fail(MPSFR_E_INVALID, "group_stars: max_groups=%d below 1", max_groups);
-    if ((origin_out == nullptr) != (shift_out == nullptr))
-        return fail(MPSFR_E_INVALID, "group_stars: origin_out and shift_out must both be NULL or both be given");
-    if (!on_device)
-        for (int k = 0; k < nstar; ++k) {
-            const double y = pos[(size_t)k * stride], x = pos[(size_t)k * stride + 1];
-            if (std::isnan(y) || std::isnan(x)) continue;
-            if (!(y >= -1.0 && y <= (double)ny && x >= -1.0 && x <= (double)nx))
-                return fail(MPSFR_E_INVALID, "group_stars: a position outside [-1, ny] x [-1, nx]");
-        }
-    HIPCHK(hipSetDevice(c->device));
-    if ((rc = ensure(c, c->group, group_workspace_bytes(ny, nx, nstar, max_groups)))) return rc;
-    const StampIn in[] = {{pos, (size_t)nstar * stride, sizeof(double)}};
-    const StampOut out[] = {{shift_out, (size_t)max_groups * 8},
-                            {label_out, (size_t)nstar, sizeof(int32_t)},
-                            {group_out, (size_t)max_groups * MPSFR_NGROUP, sizeof(int32_t)},
-                            {origin_out, (size_t)2 * max_groups, sizeof(int32_t)},
-                            {count_out, 6, sizeof(int32_t)}};
-    return stamp_call(c, on_device, in, out, [&](hipStream_t s, const void* const* d, double* const* d_out) {
-        launch_group_stars(s, ny, nx, nstar, (const double*)d[0], stride, crit, max_groups, (int32_t*)d_out[1],
-                           (int32_t*)d_out[2], (int32_t*)d_out[3], d_out[0], (int32_t*)d_out[4], c->group.p);
-    });
-}
-
-static_assert(MPSFR_NFRAMEFIT == 8 && MPSFR_FRAME_FIT_MAX_RADIUS + MPSFR_FIT_PSF_MAX_SHIFT + 2.0 <= NS / 2 + 10.0,
-              "K_FRAME_FIT row layout; a disc stays inside its footprint at any legal shift");
-
-// what mpsfr_fit_frame_psf and mpsfr_fit_cube_psf refuse alike, whatever the pointers are: shape, counts, parameters
-static int frame_fit_ranges(const char* who, int ny, int nx, int nstar, int npsf, const int32_t* psf_index, double radius,
-                            int flags, int max_iter, double tol) {
-    int rc;
-    if ((rc = frame_shape(who, ny, nx))) return rc;
-    if (nstar < 1 || nstar > (1 << 20)) return fail(MPSFR_E_INVALID, "%s: nstar=%d outside 1..2^20", who, nstar);
-    if (flags & ~MPSFR_FIT_BACKGROUND)
-        return fail(MPSFR_E_INVALID, "%s: unknown flag bits (only the background bit has a meaning here)", who);
-    if (!psf_index && npsf != nstar) return fail(MPSFR_E_INVALID, "%s: without psf_index, npsf must equal nstar", who);
-    if (!(radius >= 1.0 && radius <= MPSFR_FRAME_FIT_MAX_RADIUS))
-        return fail(MPSFR_E_INVALID, "%s: radius must be finite, in 1..%g pixels", who, MPSFR_FRAME_FIT_MAX_RADIUS);
-    if (!(tol > 0.0 && tol < 1.0)) return fail(MPSFR_E_INVALID, "%s: tol must lie in (0, 1)", who);
-    if (max_iter < 1 || max_iter > MPSFR_FRAME_FIT_MAX_ITER)
-        return fail(MPSFR_E_INVALID, "%s: max_iter=%d outside 1..%d", who, max_iter, MPSFR_FRAME_FIT_MAX_ITER);
-    return MPSFR_OK;
-}
-
-int mpsfr_fit_frame_psf(mpsfr_ctx* c, int ny, int nx, const double* image, const double* var, int nstar, int npsf,
-                        const double* psf, const int32_t* psf_index, const int32_t* origin, const double* shift,
-                        const double* scale0, double radius, int flags, int max_iter, double tol, double* star_out,
-                        double* head_out, double* resid_out, int on_device) {
-    if (!c || !image || !psf || !origin || !star_out || !head_out || npsf < 1)
-        return fail(MPSFR_E_INVALID, "fit_frame_psf: bad argument (image, psf, origin, star_out and head_out are required)");
-    int rc;
-    if ((rc = frame_fit_ranges("fit_frame_psf", ny, nx, nstar, npsf, psf_index, radius, flags, max_iter, tol))) return rc;
-    if (!on_device) {
-        if ((rc = check_model_list("fit_frame_psf", "shift", nstar, npsf, psf_index, shift, (size_t)2 * nstar))) return rc;
-        if ((rc = check_frame_stars("fit_frame_psf", nstar, origin, scale0, "scale0"))) return rc;
-    }
-    HIPCHK(hipSetDevice(c->device));
-    if ((rc = ensure(c, c->framefit, frame_fit_workspace_bytes(ny, nx, nstar)))) return rc;
-    const size_t npix = (size_t)ny * nx;
-    const StampIn in[] = {{image, npix, sizeof(double)},
-                          {var, npix, sizeof(double)},
-                          {psf, npsf * kStampPix, sizeof(double)},
-                          {shift, (size_t)2 * nstar, sizeof(double)},
-                          {scale0, (size_t)nstar, sizeof(double)},
-                          {origin, (size_t)2 * nstar, sizeof(int32_t)},
-                          {psf_index, (size_t)nstar, sizeof(int32_t)}};
-    const StampOut out[] = {{star_out, (size_t)nstar * MPSFR_NFRAMEFIT}, {head_out, MPSFR_NFRAMEFIT}, {resid_out, npix}};
-    return stamp_call(c, on_device, in, out, [&](hipStream_t s, const void* const* d, double* const* d_out) {
-        const StarList stars{nstar, npsf, (const double*)d[2], (const int32_t*)d[6], (const int32_t*)d[5],
-                             (const double*)d[3]};
-        launch_fit_frame(s, ny, nx, (const double*)d[0], (const double*)d[1], stars, (const double*)d[4], radius,
-                         (flags & MPSFR_FIT_BACKGROUND) != 0, max_iter, tol, d_out[0], d_out[1], d_out[2],
-                         c->framefit.p);
-    });
-}
-
-static_assert(MPSFR_NFRAMEFREE == 16 && MPSFR_NFRAMEFREE_HEAD == 12 && MPSFR_FRAME_FREE_HELD == 1 &&
-                  MPSFR_FRAME_FREE_BOUND == 2 && MPSFR_FRAME_FREE_CLIPPED == 4,
-              "k_fr_step<FR_FINAL> row layout and flags");
-
-// what mpsfr_fit_frame_psf_free and mpsfr_fit_cube_psf_free refuse alike: the parameters of the outer loop
-static int frame_free_ranges(const char* who, int max_outer, double pos_tol, double max_step, double max_move,
-                             double min_snr) {
-    if (max_outer < 0 || max_outer > MPSFR_FRAME_FREE_MAX_OUTER)
-        return fail(MPSFR_E_INVALID, "%s: max_outer=%d outside 0..%d", who, max_outer, MPSFR_FRAME_FREE_MAX_OUTER);
-    if (!(pos_tol > 0.0 && std::isfinite(pos_tol))) return fail(MPSFR_E_INVALID, "%s: pos_tol must be finite and > 0", who);
-    if (!(max_step > 0.0 && max_step <= MPSFR_FRAME_FREE_MAX_STEP))
-        return fail(MPSFR_E_INVALID, "%s: max_step must lie in (0, %g] pixels", who, MPSFR_FRAME_FREE_MAX_STEP);
-    if (!(max_move > 0.0 && max_move <= MPSFR_FRAME_FREE_MAX_MOVE))
-        return fail(MPSFR_E_INVALID, "%s: max_move must lie in (0, %g] pixels", who, MPSFR_FRAME_FREE_MAX_MOVE);
-    if (!(min_snr >= 0.0 && std::isfinite(min_snr))) return fail(MPSFR_E_INVALID, "%s: min_snr must be finite and >= 0", who);
-    return MPSFR_OK;
-}
-
-int mpsfr_fit_frame_psf_free(mpsfr_ctx* c, int ny, int nx, const double* image, const double* var, int nstar, int npsf,
-                             const double* psf, const int32_t* psf_index, const int32_t* origin, const double* shift,
-                             const double* scale0, double radius, int flags, int max_iter, double tol, int max_outer,
-                             double pos_tol, double max_step, double max_move, double min_snr, double* star_out,
-                             double* shift_out, double* head_out, double* resid_out, int on_device) {
-    const char* who = "fit_frame_psf_free";
-    if (!c || !image || !psf || !origin || !star_out || !shift_out || !head_out || npsf < 1)
-        return fail(MPSFR_E_INVALID,
-                    "%s: bad argument (image, psf, origin, star_out, shift_out and head_out are required)", who);
-    int rc;
-    if ((rc = frame_fit_ranges(who, ny, nx, nstar, npsf, psf_index, radius, flags, max_iter, tol))) return rc;
-    if ((rc = frame_free_ranges(who, max_outer, pos_tol, max_step, max_move, min_snr))) return rc;
-    if (!on_device) {
-        if ((rc = check_model_list(who, "shift", nstar, npsf, psf_index, shift, (size_t)2 * nstar))) return rc;
-        if ((rc = check_frame_stars(who, nstar, origin, scale0, "scale0"))) return rc;
-    }
-    HIPCHK(hipSetDevice(c->device));
-    if ((rc = ensure(c, c->framefit, frame_free_workspace_bytes(ny, nx, nstar)))) return rc;
-    const size_t npix = (size_t)ny * nx;
-    const StampIn in[] = {{image, npix, sizeof(double)},
-                          {var, npix, sizeof(double)},
-                          {psf, npsf * kStampPix, sizeof(double)},
-                          {shift, (size_t)2 * nstar, sizeof(double)},
-                          {scale0, (size_t)nstar, sizeof(double)},
-                          {origin, (size_t)2 * nstar, sizeof(int32_t)},
-                          {psf_index, (size_t)nstar, sizeof(int32_t)}};
-    const StampOut out[] = {{star_out, (size_t)nstar * MPSFR_NFRAMEFREE},
-                            {shift_out, (size_t)2 * nstar},
-                            {head_out, MPSFR_NFRAMEFREE_HEAD},
-                            {resid_out, npix}};
-    return stamp_call(c, on_device, in, out, [&](hipStream_t s, const void* const* d, double* const* d_out) {
-        const StarList stars{nstar, npsf, (const double*)d[2], (const int32_t*)d[6], (const int32_t*)d[5],
-                             (const double*)d[3]};
-        launch_fit_frame_free(s, ny, nx, (const double*)d[0], (const double*)d[1], stars, (const double*)d[4], radius,
-                              (flags & MPSFR_FIT_BACKGROUND) != 0, max_iter, tol, max_outer, pos_tol, max_step, max_move,
-                              min_snr, d_out[0], d_out[1], d_out[2], d_out[3], c->framefit.p);
-    });
-}
-
-// what mpsfr_fit_cube_psf and mpsfr_fit_cube_psf_free refuse alike on host pointers: the model list, the stars, scale0,
-// layer_shift and the summed shifts
-static int cube_fit_host_arguments(const char* who, int nl, int nstar, int npsf, const int32_t* psf_index,
-                                   const int32_t* origin, const double* shift, const double* layer_shift,
-                                   const double* scale0) {
-    int rc;
-    if ((rc = check_model_list(who, "shift", nstar, npsf, psf_index, shift, (size_t)2 * nstar))) return rc;
-    if ((rc = check_frame_stars(who, nstar, origin, nullptr, "scale0"))) return rc;
-    if (scale0)
-        for (size_t k = 0; k < (size_t)nl * nstar; ++k)
-            if (!std::isfinite(scale0[k])) return fail(MPSFR_E_INVALID, "%s: a scale0 that is not finite", who);
-    if (layer_shift) {
-        // (rounding is monotone: the sums of a layer stay in range when those of the extreme shifts do)
-        double lo[2] = {0.0, 0.0}, hi[2] = {0.0, 0.0};
-        for (int k = 0; shift && k < 2 * nstar; ++k) {
-            lo[k & 1] = k < 2 ? shift[k] : std::min(lo[k & 1], shift[k]);
-            hi[k & 1] = k < 2 ? shift[k] : std::max(hi[k & 1], shift[k]);
-        }
-        for (int k = 0; k < 2 * nl; ++k) {
-            const double t = layer_shift[k];
-            if (!std::isfinite(t)) return fail(MPSFR_E_INVALID, "%s: a layer_shift that is not finite", who);
-            if (!(std::fabs(lo[k & 1] + t) <= MPSFR_FIT_PSF_MAX_SHIFT && std::fabs(hi[k & 1] + t) <= MPSFR_FIT_PSF_MAX_SHIFT))
-                return fail(MPSFR_E_INVALID, "%s: shift + layer_shift beyond 8 pixels", who);
-        }
-    }
-    return MPSFR_OK;
-}
-
-int mpsfr_fit_cube_psf(mpsfr_ctx* c, int nl, int ny, int nx, const double* cube, const double* var, int nstar, int npsf,
-                       const double* psf, const int32_t* psf_index, const int32_t* origin, const double* shift,
-                       const double* layer_shift, const double* scale0, double radius, int flags, int max_iter,
-                       double tol, int layer_batch, double* star_out, double* head_out, double* resid_out,
-                       int on_device) {
-    const char* who = "fit_cube_psf";
-    if (!c || !cube || !psf || !origin || !star_out || !head_out || npsf < 1)
-        return fail(MPSFR_E_INVALID, "%s: bad argument (cube, psf, origin, star_out and head_out are required)", who);
-    int rc;
-    if ((rc = frame_fit_ranges(who, ny, nx, nstar, npsf, psf_index, radius, flags, max_iter, tol))) return rc;
-    if (nl < 1 || nl > MPSFR_CUBE_FIT_MAX_LAYERS)
-        return fail(MPSFR_E_INVALID, "%s: nl=%d outside 1..%d", who, nl, MPSFR_CUBE_FIT_MAX_LAYERS);
-    if (layer_batch < 0) return fail(MPSFR_E_INVALID, "%s: layer_batch=%d is negative", who, layer_batch);
-    if (!on_device) {
-        if ((rc = cube_fit_host_arguments(who, nl, nstar, npsf, psf_index, origin, shift, layer_shift, scale0))) return rc;
-    }
-    HIPCHK(hipSetDevice(c->device));
-    // the layers of a batch: asked for, or what the budget of work memory holds
-    const size_t fixed = cube_fit_workspace_bytes(ny, nx, nstar, 0), per = cube_fit_workspace_bytes(ny, nx, nstar, 1) - fixed;
-    int nb = layer_batch > 0 ? layer_batch : (int)std::min<size_t>((size_t)nl, MPSFR_CUBE_FIT_WORK_BYTES / per);
-    nb = std::max(1, std::min(nb, nl));
-    if ((rc = ensure(c, c->cubefit, cube_fit_workspace_bytes(ny, nx, nstar, nb)))) return rc;
-    hipStream_t s = c->stream;
-    if ((rc = wait_for_lanes(c, s))) return rc;
-    const bool back = (flags & MPSFR_FIT_BACKGROUND) != 0;
-    const size_t npix = (size_t)ny * nx, nrow = (size_t)nstar * MPSFR_NFRAMEFIT;
-    if (on_device) {
-        ProfScope ps(c, K_FIT);
-        for (int l0 = 0; l0 < nl; l0 += nb) {
-            const size_t o = (size_t)l0;
-            StarList stars{nstar, npsf, psf + o * kStampPix, psf_index, origin, shift};
-            stars.lshift = layer_shift ? layer_shift + 2 * o : nullptr;
-            stars.nl = nl;
-            launch_fit_cube(s, ny, nx, std::min(nb, nl - l0), cube + o * npix, var ? var + o * npix : nullptr, stars,
-                            scale0 ? scale0 + o * nstar : nullptr, radius, back, max_iter, tol, star_out + o * nrow,
-                            head_out + o * MPSFR_NFRAMEFIT, resid_out ? resid_out + o * npix : nullptr, c->cubefit.p);
-        }
-        HIPCHK(hipGetLastError());
-        return MPSFR_OK;
-    }
-    // Host pointers: what all layers share is staged once, the layers batch by batch -- cube, var, the models of the
-    // batch as [npsf][layers][40][40], scale0, and the three outputs
-    const size_t B = (size_t)nb;
-    size_t off = 0;
-    auto room = [&](bool wanted, size_t count) {
-        const size_t at = off;
-        if (wanted) off += (count * sizeof(double) + 7) & ~(size_t)7;
-        return at;
-    };
-    const size_t o_shift = room(shift, (size_t)2 * nstar), o_lshift = room(layer_shift, (size_t)2 * nl);
-    const size_t o_cube = room(true, B * npix), o_var = room(var, B * npix), o_psf = room(true, npsf * B * kStampPix);
-    const size_t o_s0 = room(scale0, B * nstar), o_rows = room(true, B * nrow), o_head = room(true, B * MPSFR_NFRAMEFIT);
-    const size_t o_res = room(resid_out, B * npix);
-    const size_t o_origin = room(true, (size_t)nstar), o_index = room(psf_index, ((size_t)nstar + 1) / 2);
-    if ((rc = ensure(c, c->stage, off))) return rc;
-    char* base = (char*)c->stage.p;
-    auto dbl = [&](bool wanted, size_t at) { return wanted ? (double*)(base + at) : nullptr; };
-    auto put = [&](void* dst, const void* src, size_t bytes) {
-        return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
-    };
-    if (shift) HIPCHK(put(base + o_shift, shift, (size_t)2 * nstar * sizeof(double)));
-    if (layer_shift) HIPCHK(put(base + o_lshift, layer_shift, (size_t)2 * nl * sizeof(double)));
-    HIPCHK(put(base + o_origin, origin, (size_t)2 * nstar * sizeof(int32_t)));
-    if (psf_index) HIPCHK(put(base + o_index, psf_index, (size_t)nstar * sizeof(int32_t)));
-    {
-        ProfScope ps(c, K_FIT);
-        for (int l0 = 0; l0 < nl; l0 += nb) {
-            const size_t o = (size_t)l0, n = (size_t)std::min(nb, nl - l0), frames = n * npix * sizeof(double);
-            HIPCHK(put(base + o_cube, cube + o * npix, frames));
-            if (var) HIPCHK(put(base + o_var, var + o * npix, frames));
-            if (scale0) HIPCHK(put(base + o_s0, scale0 + o * nstar, n * nstar * sizeof(double)));
-            const size_t width = n * kStampPix * sizeof(double);
-            HIPCHK(hipMemcpy2DAsync(base + o_psf, width, psf + o * kStampPix, (size_t)nl * kStampPix * sizeof(double),
-                                    width, (size_t)npsf, hipMemcpyHostToDevice, s));
-            StarList stars{nstar, npsf, dbl(true, o_psf), psf_index ? (const int32_t*)(base + o_index) : nullptr,
-                           (const int32_t*)(base + o_origin), dbl(shift, o_shift)};
-            stars.lshift = layer_shift ? dbl(true, o_lshift) + 2 * o : nullptr;
-            stars.nl = (int)n;
-            launch_fit_cube(s, ny, nx, (int)n, dbl(true, o_cube), dbl(var, o_var), stars, dbl(scale0, o_s0), radius, back,
-                            max_iter, tol, dbl(true, o_rows), dbl(true, o_head), dbl(resid_out, o_res), c->cubefit.p);
-            HIPCHK(hipGetLastError());
-            auto get = [&](void* dst, const void* src, size_t bytes) {
-                return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s);
-            };
-            HIPCHK(get(star_out + o * nrow, base + o_rows, n * nrow * sizeof(double)));
-            HIPCHK(get(head_out + o * MPSFR_NFRAMEFIT, base + o_head, n * MPSFR_NFRAMEFIT * sizeof(double)));
-            if (resid_out) HIPCHK(get(resid_out + o * npix, base + o_res, frames));
-            HIPCHK(hipStreamSynchronize(s));      // (the staged batch is refilled by the next one)
-        }
-    }
-    return MPSFR_OK;
-}
-
-static_assert(MPSFR_NCUBEFREE_POS == 8 && MPSFR_NCUBEFREE_CALL == 8, "k_cf_step<CF_FINAL> row layout");
-
-int mpsfr_fit_cube_psf_free(mpsfr_ctx* c, int nl, int ny, int nx, const double* cube, const double* var, int nstar,
-                            int npsf, const double* psf, const int32_t* psf_index, const int32_t* origin,
-                            const double* shift, const double* layer_shift, const double* scale0, double radius,
-                            int flags, int max_iter, double tol, int max_outer, double pos_tol, double max_step,
-                            double max_move, double min_snr, double* star_out, double* head_out, double* pos_out,
-                            double* shift_out, double* call_out, double* resid_out, int on_device) {
-    const char* who = "fit_cube_psf_free";
-    if (!c || !cube || !psf || !origin || !star_out || !head_out || !pos_out || !shift_out || !call_out || npsf < 1)
-        return fail(MPSFR_E_INVALID,
-                    "%s: bad argument (cube, psf, origin, star_out, head_out, pos_out, shift_out and call_out are required)",
-                    who);
-    int rc;
-    if ((rc = frame_fit_ranges(who, ny, nx, nstar, npsf, psf_index, radius, flags, max_iter, tol))) return rc;
-    if (nl < 1 || nl > MPSFR_CUBE_FIT_MAX_LAYERS)
-        return fail(MPSFR_E_INVALID, "%s: nl=%d outside 1..%d", who, nl, MPSFR_CUBE_FIT_MAX_LAYERS);
-    if ((rc = frame_free_ranges(who, max_outer, pos_tol, max_step, max_move, min_snr))) return rc;
-    if (!on_device && (rc = cube_fit_host_arguments(who, nl, nstar, npsf, psf_index, origin, shift, layer_shift, scale0)))
-        return rc;
-    const size_t work = cube_free_workspace_bytes(ny, nx, nstar, nl);
-    if (work > MPSFR_CUBE_FREE_WORK_BYTES)
-        return fail(MPSFR_E_INVALID, "%s: %zu bytes of work memory for %d layers, above the budget of %zu: take the "
-                                     "positions from fewer layers", who, work, nl, (size_t)MPSFR_CUBE_FREE_WORK_BYTES);
-    HIPCHK(hipSetDevice(c->device));
-    if ((rc = ensure(c, c->cubefit, work))) return rc;
-    const size_t L = (size_t)nl, npix = (size_t)ny * nx;
-    const StampIn in[] = {{cube, L * npix, sizeof(double)},
-                          {var, L * npix, sizeof(double)},
-                          {psf, npsf * L * kStampPix, sizeof(double)},
-                          {shift, (size_t)2 * nstar, sizeof(double)},
-                          {layer_shift, 2 * L, sizeof(double)},
-                          {scale0, L * nstar, sizeof(double)},
-                          {origin, (size_t)2 * nstar, sizeof(int32_t)},
-                          {psf_index, (size_t)nstar, sizeof(int32_t)}};
-    const StampOut out[] = {{star_out, L * nstar * MPSFR_NFRAMEFIT}, {head_out, L * MPSFR_NFRAMEFIT},
-                            {pos_out, (size_t)nstar * MPSFR_NCUBEFREE_POS}, {shift_out, (size_t)2 * nstar},
-                            {call_out, MPSFR_NCUBEFREE_CALL}, {resid_out, L * npix}};
-    return stamp_call(c, on_device, in, out, [&](hipStream_t s, const void* const* d, double* const* d_out) {
-        StarList stars{nstar, npsf, (const double*)d[2], (const int32_t*)d[7], (const int32_t*)d[6], (const double*)d[3]};
-        stars.lshift = (const double*)d[4];
-        stars.nl = nl;
-        launch_fit_cube_free(s, ny, nx, nl, (const double*)d[0], (const double*)d[1], stars, (const double*)d[5], radius,
-                             (flags & MPSFR_FIT_BACKGROUND) != 0, max_iter, tol, max_outer, pos_tol, max_step, max_move,
-                             min_snr, d_out[0], d_out[1], d_out[2], d_out[3], d_out[4], d_out[5], c->cubefit.p);
-    });
 }
 
 long mpsfr_debug_fetch(mpsfr_ctx* c, const char* what, double* out, size_t capacity) {

@@ -14,8 +14,8 @@ with the kind of the leftovers:
   S  the same entry point, smaller (frame 40 x 45: 2 x 2 ragged tiles, a few stars or stamps, 1 or 2 layers)
   X  the other tenant of the workspace (fit_frame_psf <-> fit_frame_psf_free on framefit, fit_cube_psf <->
      fit_cube_psf_free on cubefit, the host form of fit_cube_psf with layer_batch = 2 over 5 layers, render_stars with
-     the pile of 300 before a fit of the same frame shape; for the stamp calls the host form of fit_cube_psf, which lays
-     the staging buffer out by hand; frame_background, which has no workspace and leaves three input and five output
+     the pile of 300 before a fit of the same frame shape; for the stamp calls the host form of fit_cube_psf, which holds
+     one batch of layers at a time in the staging buffer; frame_background, which has no workspace and leaves three input and five output
      planes in the staging buffer, before the frame calls and cut_stamps, and find, a frame fit and the cube's host form
      before it)
   T  another terminal state at the same shape: only the steering words differ
@@ -649,7 +649,7 @@ def _refused(rc):
 
 def _cube_host_batches(api, ctx):
     """The host form of fit_cube_psf on the five layers of cube_fit_cases two at a time: a ragged last batch, the
-    staging buffer laid out by hand and refilled batch by batch."""
+    staging buffer laid out for one batch and refilled batch by batch."""
     cube_fit(ctx, K.cube(), layer_batch=2)
 
 

@@ -1,6 +1,6 @@
 """GPU: a stamp, frame or cube call's result does not depend on what ran before it on the same context.
 
-The fifteen entry points behind the staging buffer and the grow-only frame workspaces of mpsfr_api.cpp (stage, specx,
+The fifteen entry points behind the staging buffer and the grow-only frame workspaces of stamp_calls.cpp (stage, specx,
 render, find, group, framefit, cubefit; the audit is DESIGN.md "Call-order independence", the second table) follow the
 protocol of tests/test_gpu_call_history.py: on one context the checked call runs once, so that the workspaces are sized
 for it, then a predecessor, then the checked call again -- and every output array of that second run equals, byte for
@@ -12,7 +12,7 @@ precision runs every pair; f64 the whole list of the stamp calls, and L, X and o
 kernels are the same fp64 ones in both modes.
 
 R: a frame or cube call issued while device-output reconstructs are still in flight on both lanes (the wait_for_lanes
-path of stamp_call and of fit_cube_psf) equals the fresh call, and the reconstructs equal theirs.
+path of Staged::run and of fit_cube_psf) equals the fresh call, and the reconstructs equal theirs.
 
 Every documented output is written, and nothing else (include/mpsfr.h, "What a call writes"): each entry point once in
 its device form into buffers prefilled with the byte 0xA5 -- every element equals the host form's fresh value, none
