@@ -21,7 +21,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from . import _lib, _minifits
+from . import _args, _lib, _minifits
 from ._lib import Context, MpsfrError, E_GRID
 
 MIN_L0 = 8    # minimum L0 in m (psfrec.py:30)
@@ -291,9 +291,34 @@ def _fit_columns_ell(lbda, fit, pixscale):
 
 
 def _check_circular(circular):
-    if not isinstance(circular, (bool, np.bool_)):
-        raise ValueError('circular must be True or False')
-    return bool(circular)
+    return bool(_args.flag('circular', circular))
+
+
+def _check_precision(precision):
+    if precision not in ('mixed', 'f64'):
+        raise ValueError("precision must be 'mixed' or 'f64'")
+
+
+def _grid_or_field(npsflin, positions):
+    """What a call with optional positions evaluates: None for the npsflin x npsflin grid, else the caller's positions,
+    validated (any number of them)."""
+    if positions is None:
+        _args.grid_side(npsflin)
+        return None
+    return _lib.field_positions(positions, max_n=None)
+
+
+def _two_layer_atmosphere(seeing, GL, L0, h):
+    """(seeing, GL, L0) as floats of a call on the reference's two-layer atmosphere (ValueError)."""
+    try:
+        seeing, GL, L0 = float(seeing), float(GL), float(L0)
+    except (TypeError, ValueError):
+        raise ValueError('seeing, GL and L0 must be scalars') from None
+    if not (seeing > 0 and L0 > 0 and 0 <= GL <= 1):
+        raise ValueError('need seeing > 0, L0 > 0 and 0 <= GL <= 1')
+    if np.asarray(h).size != 2:
+        raise ValueError('exactly two layers are supported (psfrec.py:66)')
+    return seeing, GL, L0
 
 
 _FIT_ROWS_DTYPE = np.dtype([('lbda', 'f8'), ('center', 'f8', (2,)), ('flux', 'f8'), ('fwhm', 'f8', (2,)),
@@ -397,8 +422,7 @@ def fit_psf_cube(lbda, psfcube, *, circular=True, var=None, fit_back=False, pixs
     out.  The table then has the columns of the circular / elliptical fit plus back, err_back and npix (the number
     of pixels used)."""
     circular = _check_circular(circular)
-    if not isinstance(fit_back, (bool, np.bool_)):
-        raise ValueError('fit_back must be True or False')
+    _args.flag('fit_back', fit_back)
     if var is not None or fit_back:
         data, va = _observed_cube(psfcube, var)
         if np.size(lbda) != data.shape[0]:
@@ -455,18 +479,11 @@ def fit_stars_with_psf(stars, psf, *, var=None, psf_index=None, shift=None, fit_
     sum of squares: the goodness of the reconstruction on this star), npix (pixels used), status (0 a minimum, 1 not
     converged or against the 8-pixel bound of the shift, 2 not fitted), err_scale, err_shift (2, arcsec), err_back,
     err_flux (errors scaled by sqrt(chi2 / dof))."""
-    for name, val in (('fit_back', fit_back), ('fixed_shift', fixed_shift)):
-        if not isinstance(val, (bool, np.bool_)):
-            raise ValueError('%s must be True or False' % name)
-    if not (np.isfinite(pixscale) and pixscale > 0):
-        raise ValueError('pixscale must be positive')
+    _args.flag('fit_back', fit_back)
+    _args.flag('fixed_shift', fixed_shift)
+    _pixscale(pixscale)
     data, va = _observed_cube(stars, var)
-    sh = None
-    if shift is not None:
-        try:
-            sh = np.asarray(shift, dtype=float) / pixscale
-        except (TypeError, ValueError):
-            raise ValueError('shift must be a numeric array') from None
+    sh = _shift_pixels(shift, pixscale)
     ctx = get_context(128, pixscale, data.shape[-1], precision, device)
     fit = ctx.fit_stamps_psf(data, psf, var=va, psf_index=psf_index, shift=sh, background=bool(fit_back),
                              fixed_shift=bool(fixed_shift))
@@ -517,15 +534,10 @@ def fit_star_spectra_with_psf(cubes, psf, lbda, *, var=None, psf_index=None, shi
     layers fitted), status (0 a minimum, 1 not converged or against the 8-pixel bound, 2 not fitted) and the (n, nl)
     columns flux = scale sum(psf_l), err_flux, scale, back, layer_status (2: left out) and lbda.  The errors are those
     of the joint fit, scaled by sqrt(chi2 / dof)."""
-    for name, val in (('fit_back', fit_back), ('drift', drift)):
-        if not isinstance(val, (bool, np.bool_)):
-            raise ValueError('%s must be True or False' % name)
-    if not (np.isfinite(pixscale) and pixscale > 0):
-        raise ValueError('pixscale must be positive')
-    try:
-        lb = np.asarray(lbda, dtype=float).ravel()
-    except (TypeError, ValueError):
-        raise ValueError('lbda must be a numeric array') from None
+    _args.flag('fit_back', fit_back)
+    _args.flag('drift', drift)
+    _pixscale(pixscale)
+    lb = _args.array('lbda', lbda).ravel()
     if lb.size < 1 or not np.all(np.isfinite(lb)):
         raise ValueError('lbda must hold one finite wavelength per layer')
     if np.ndim(cubes) not in (3, 4) or np.shape(cubes)[-3] != lb.size:
@@ -536,12 +548,7 @@ def fit_star_spectra_with_psf(cubes, psf, lbda, *, var=None, psf_index=None, shi
         if not hi > lo:
             raise ValueError('drift=True needs at least two different wavelengths')
         x = np.clip((lb - 0.5 * (lo + hi)) / (0.5 * (hi - lo)), -1.0, 1.0)
-    sh = None
-    if shift is not None:
-        try:
-            sh = np.asarray(shift, dtype=float) / pixscale
-        except (TypeError, ValueError):
-            raise ValueError('shift must be a numeric array') from None
+    sh = _shift_pixels(shift, pixscale)
     ctx = get_context(128, pixscale, np.shape(cubes)[-1], precision, device)
     head, layers = ctx.fit_spectra_psf(cubes, psf, var=var, psf_index=psf_index, shift=sh, background=bool(fit_back), x=x)
     return _make_table(_fit_columns_spec(head, layers, lb, pixscale))
@@ -602,8 +609,7 @@ def fit_star_groups_with_psf(stars, psf, positions, *, var=None, psf_index=None,
     err_back, chi2, npix and status (as fit_stars_with_psf) repeated on each of its rows, and max_corr: the largest
     |correlation coefficient| of this star's F with that of another star of the stamp (0 for a single star) -- how
     blended its flux is."""
-    if not isinstance(fit_back, (bool, np.bool_)):
-        raise ValueError('fit_back must be True or False')
+    _args.flag('fit_back', fit_back)
     if not (np.isfinite(pixscale) and pixscale > 0):
         raise ValueError('pixscale must be positive')
     _lib.group_fit_flags(bool(fit_back), mode)
@@ -800,8 +806,7 @@ def fit_found_stars(image, psf, found, *, var=None, crit, fit_back=True, mode='f
     their `group` column points at it, so that subtract_stars(image, psf, origin, fit) removes every star.  With
     crowded='free' the same, with the positions of the crowded stars refined beside their fluxes as
     refine_crowded_stars does (its defaults): their rows get the refined shift and its conditional error."""
-    if not isinstance(fit_back, (bool, np.bool_)):
-        raise ValueError('fit_back must be True or False')
+    _args.flag('fit_back', fit_back)
     if crowded not in ('skip', 'frame', 'free'):
         raise ValueError("crowded must be 'skip', 'frame' or 'free'")
     _lib.frame_fit_parameters(radius, bool(fit_back), 1, 0.5)
@@ -811,10 +816,7 @@ def fit_found_stars(image, psf, found, *, var=None, crit, fit_back=True, mode='f
     if not np.all(np.isfinite(pos)):
         raise ValueError('the positions of the stars must be finite')
     im, va = _lib.frame_images(image, var)
-    try:
-        ps = np.ascontiguousarray(psf, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError('psf must be a numeric array') from None
+    ps = np.ascontiguousarray(_args.array('psf', psf))
     if ps.ndim != 2 or ps.shape[0] != ps.shape[1]:
         raise ValueError('psf must be one model stamp (40, 40)')
     ctx = get_context(128, pixscale, ps.shape[-1], precision, device)
@@ -920,14 +922,10 @@ def _crowded_inputs(psf, positions, psf_index, fit_back, start, pixscale):
     """(psf, psf_index, start, origin, shift in pixels) of fit_crowded_stars and refine_crowded_stars: the model stamps,
     the stars placed as cut_star_stamps places stamps, the start resolved."""
     _pixscale(pixscale)
-    if not isinstance(fit_back, (bool, np.bool_)):
-        raise ValueError('fit_back must be True or False')
+    _args.flag('fit_back', fit_back)
     pos = _star_positions(positions)
     n = pos.shape[0]
-    try:
-        ps = np.asarray(getattr(psf, 'data', psf), dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError('psf must be a numeric array') from None
+    ps = _args.array('psf', psf, unwrap=True)
     if ps.ndim < 2 or ps.shape[-1] != ps.shape[-2] or ps.size == 0:
         raise ValueError('psf must have the shape (..., 40, 40)')
     dimpsf = ps.shape[-1]
@@ -992,11 +990,11 @@ def _sky_parameters(sky):
         raise ValueError('sky: unknown keys %s' % sorted(unknown))
     par.update(sky)
     passes = par.pop('passes')
-    if isinstance(passes, bool) or not isinstance(passes, (int, np.integer)) or not 1 <= passes <= SKY_MAX_PASSES:
-        raise ValueError('sky: passes must be an integer between 1 and %d' % SKY_MAX_PASSES)
+    passes = _args.integer('passes', passes, 1, SKY_MAX_PASSES,
+                           'sky: passes must be an integer between 1 and %d' % SKY_MAX_PASSES)
     box, filt, kappa, max_clip, min_frac = _lib.background_parameters(par['box'], par['filter'], par['kappa'],
                                                                       par['max_clip'], par['min_frac'])
-    return int(passes), dict(box=box, filter=filt, kappa=kappa, max_clip=max_clip, min_frac=min_frac)
+    return passes, dict(box=box, filter=filt, kappa=kappa, max_clip=max_clip, min_frac=min_frac)
 
 
 def fit_crowded_stars(image, psf, positions, *, var=None, psf_index=None, radius=8.0, fit_back=True, start=None,
@@ -1028,8 +1026,7 @@ def fit_crowded_stars(image, psf, positions, *, var=None, psf_index=None, radius
     map is appended to the returned tuple (the residual is that of the final fit: the sky is taken out of it)."""
     ps, psf_index, start, origin, shift_px = _crowded_inputs(psf, positions, psf_index, fit_back, start, pixscale)
     dimpsf = ps.shape[-1]
-    if not isinstance(return_sky, (bool, np.bool_)):
-        raise ValueError('return_sky must be True or False')
+    _args.flag('return_sky', return_sky)
     if sky is None and return_sky:
         raise ValueError('return_sky needs sky')
     passes, sky_par = (0, None) if sky is None else _sky_parameters(sky)
@@ -1131,14 +1128,10 @@ def _crowded_spectra_inputs(psf, positions, lbda, psf_index, layer_shift, fit_ba
     fit_crowded_spectra and refine_crowded_spectra: the model cubes, the stars placed as cut_star_stamps places stamps,
     the start resolved."""
     _pixscale(pixscale)
-    if not isinstance(fit_back, (bool, np.bool_)):
-        raise ValueError('fit_back must be True or False')
+    _args.flag('fit_back', fit_back)
     pos = _star_positions(positions)
     n = pos.shape[0]
-    try:
-        ps = np.asarray(getattr(psf, 'data', psf), dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError('psf must be a numeric array') from None
+    ps = _args.array('psf', psf, unwrap=True)
     if ps.ndim not in (3, 4) or ps.shape[-1] != ps.shape[-2] or ps.size == 0:
         raise ValueError('psf must have the shape (nl, 40, 40) or (npsf, nl, 40, 40)')
     dimpsf = ps.shape[-1]
@@ -1151,17 +1144,11 @@ def _crowded_spectra_inputs(psf, positions, lbda, psf_index, layer_shift, fit_ba
         psf_index = np.zeros(n, dtype=np.int32)
     nl = ps.shape[1]
     if lbda is not None:
-        try:
-            lbda = np.array(lbda, dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError('lbda must be a numeric array') from None
+        lbda = np.array(_args.array('lbda', lbda))          # (the caller's array is not handed on)
         if lbda.shape != (nl,):
             raise ValueError('lbda must hold one wavelength per layer (%d)' % nl)
     if layer_shift is not None:
-        try:
-            layer_shift = np.asarray(layer_shift, dtype=np.float64) / pixscale
-        except (TypeError, ValueError):
-            raise ValueError('layer_shift must be a numeric array') from None
+        layer_shift = _args.array('layer_shift', layer_shift) / pixscale
     if isinstance(start, str):
         if start != 'found':
             raise ValueError("start must be None, 'found' or (nl, n) values")
@@ -1344,10 +1331,7 @@ def cut_star_stamps(image, positions, var=None, dimpsf=40, *, pixscale=0.2, prec
 
     Returns (stamps, var_stamps or None, origin): (n, dimpsf, dimpsf) arrays and the (n, 2) int32 origins that
     render_star_field and subtract_stars take."""
-    try:
-        pos = np.asarray(positions, dtype=float)
-    except (TypeError, ValueError):
-        raise ValueError('positions must be a numeric array') from None
+    pos = _args.array('positions', positions)
     if pos.ndim != 2 or pos.shape[1] != 2 or pos.shape[0] < 1:
         raise ValueError('positions must have the shape (n, 2)')
     if not np.all(np.isfinite(pos)) or np.any(np.abs(pos) > _lib.MAX_ORIGIN - dimpsf):
@@ -1359,12 +1343,7 @@ def cut_star_stamps(image, positions, var=None, dimpsf=40, *, pixscale=0.2, prec
 
 
 def _shift_pixels(shift, pixscale):
-    if shift is None:
-        return None
-    try:
-        return np.asarray(shift, dtype=float) / pixscale
-    except (TypeError, ValueError):
-        raise ValueError('shift must be a numeric array') from None
+    return None if shift is None else _args.array('shift', shift) / pixscale
 
 
 def render_star_field(shape, psf, origin, scale, shift=None, psf_index=None, pixscale=0.2, *, image=None,
@@ -1538,8 +1517,7 @@ def psf_metrics(psfcube, radii=METRIC_RADII, boxes=METRIC_BOXES, fractions=METRI
     context).  Every refusal is a ValueError raised before a GPU context exists."""
     st = _lib.metric_stamps(psfcube)
     rad, box, frac, ra, ba, ce = _metric_arguments(radii, boxes, fractions, center, pixscale, st.shape[-1], st.shape[0])
-    if precision not in ('mixed', 'f64'):
-        raise ValueError("precision must be 'mixed' or 'f64'")
+    _check_precision(precision)
     ctx = get_context(128, pixscale, st.shape[-1], precision, device)
     rows = ctx.stamp_metrics(st, rad, box, frac, centers=ce)
     return _make_table(_metric_columns(rows, rad.size, box.size, frac.size, float(pixscale)),
@@ -1816,9 +1794,7 @@ def _field_request(positions, npsflin):
     """The positions of a field call: direction_perf(npsflin) as (npos, 2) when `positions` is None, else the
     caller's, validated (any number of them: calls of at most 25 are made)."""
     if positions is None:
-        if isinstance(npsflin, bool) or not isinstance(npsflin, (int, np.integer)) or not 1 <= npsflin <= 5:
-            raise ValueError('npsflin must be an integer between 1 and 5')
-        return np.ascontiguousarray(direction_perf(int(npsflin)).T)
+        return np.ascontiguousarray(direction_perf(_args.grid_side(npsflin)).T)
     return _lib.field_positions(positions, max_n=None)
 
 
@@ -1847,16 +1823,8 @@ def compute_field_psf(lbda, seeing, GL, L0, positions=None, npsflin=1, h=(100, 1
     lbda = np.atleast_1d(np.asarray(lbda, dtype=float))
     if lbda.ndim != 1 or lbda.size < 1 or not np.all(np.isfinite(lbda)) or np.any(lbda <= 0):
         raise ValueError('lbda must be a non-empty 1-D array of positive wavelengths (nm)')
-    try:
-        seeing, GL, L0 = float(seeing), float(GL), float(L0)
-    except (TypeError, ValueError):
-        raise ValueError('seeing, GL and L0 must be scalars') from None
-    if not (seeing > 0 and L0 > 0 and 0 <= GL <= 1):
-        raise ValueError('need seeing > 0, L0 > 0 and 0 <= GL <= 1')
-    if np.asarray(h).size != 2:
-        raise ValueError('exactly two layers are supported (psfrec.py:66)')
-    if precision not in ('mixed', 'f64'):
-        raise ValueError("precision must be 'mixed' or 'f64'")
+    seeing, GL, L0 = _two_layer_atmosphere(seeing, GL, L0, h)
+    _check_precision(precision)
     pos = _field_request(positions, npsflin)
     masks = _resolve_masks(cutoff_masks)
     if verbose:
@@ -2060,22 +2028,9 @@ def compute_band_psf(lbda, seeing, GL, L0, bands, sed=None, npsflin=1, positions
     mreq = _metrics_request(metrics, pixscale, dimpsf)
     lbda = np.atleast_1d(np.asarray(lbda, dtype=float))
     w = band_weights(lbda, bands, sed)
-    try:
-        seeing, GL, L0 = float(seeing), float(GL), float(L0)
-    except (TypeError, ValueError):
-        raise ValueError('seeing, GL and L0 must be scalars') from None
-    if not (seeing > 0 and L0 > 0 and 0 <= GL <= 1):
-        raise ValueError('need seeing > 0, L0 > 0 and 0 <= GL <= 1')
-    if np.asarray(h).size != 2:
-        raise ValueError('exactly two layers are supported (psfrec.py:66)')
-    if precision not in ('mixed', 'f64'):
-        raise ValueError("precision must be 'mixed' or 'f64'")
-    if positions is None:
-        if isinstance(npsflin, bool) or not isinstance(npsflin, (int, np.integer)) or not 1 <= npsflin <= 5:
-            raise ValueError('npsflin must be an integer between 1 and 5')
-        pos = None
-    else:
-        pos = _lib.field_positions(positions, max_n=None)
+    seeing, GL, L0 = _two_layer_atmosphere(seeing, GL, L0, h)
+    _check_precision(precision)
+    pos = _grid_or_field(npsflin, positions)
     masks = _resolve_masks(cutoff_masks)
     if verbose:
         logger.info('Compute band PSF for %d band(s) with seeing=%.2f GL=%.2f L0=%.2f', len(w), seeing, GL, L0)
@@ -2161,14 +2116,8 @@ def compute_profile_psf(lbda, seeing, L0, cn2, h, wind_speed=12.5, wind_dir=None
         raise ValueError('GL must be a scalar') from None
     if not 0 <= GL <= 1:
         raise ValueError('need 0 <= GL <= 1')
-    if precision not in ('mixed', 'f64'):
-        raise ValueError("precision must be 'mixed' or 'f64'")
-    if positions is None:
-        if isinstance(npsflin, bool) or not isinstance(npsflin, (int, np.integer)) or not 1 <= npsflin <= 5:
-            raise ValueError('npsflin must be an integer between 1 and 5')
-        pos = None
-    else:
-        pos = _lib.field_positions(positions, max_n=None)
+    _check_precision(precision)
+    pos = _grid_or_field(npsflin, positions)
     masks = _resolve_masks(cutoff_masks)
     if verbose:
         logger.info('Compute PSF for a %d-layer profile with seeing=%.2f L0=%.2f', hh.size, seeing, L0)
